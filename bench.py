@@ -8,7 +8,12 @@ seed 20240907).  N>1 (launched by torch.distributed.run, one rank per GPU): weak
 1 s window, sharded by time range with a per-pixel halo; per step one all-reduce of the count map (as saturated bytes) and one
 of the fp64 normal-equation pack over RCCL (emba_amd/sharded.py).
 
-Prints ONE JSON line on rank 0.  The `roofline` object prices the dominant kernel (emba_warp_residual_kernel) with
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`) with the run's configuration; --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+Everything else is measured only with --full: per-kernel samples inside the timed region, the with / without ep blocks, the
+long block with the card's clocks and power, the collectives alone, `roofline` and `cpu_baseline`.
+
+With --full, the `roofline` object prices the dominant kernel (emba_warp_residual_kernel) with
 SURVEY §8d's 244 algorithmic bytes per event against the 8 TB/s HBM3E peak, its duration measured live with HIP events on
 the stream the kernel runs on.  `cpu_baseline` times the CPU oracle (single-threaded port of the reference algorithm) on the
 GPU box's host, rank 0, N=1 only; it is reported, not measured-as-product.
@@ -27,6 +32,43 @@ sys.path.insert(0, ROOT)
 ALGO_BYTES_PER_EVENT = 244
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 EVENTS_PER_GPU = 1_000_000
+DUMP_MAX_EP = 1 << 20               # --dump-outputs: a longer ep vector is cut to a fixed, seeded sample of entries,
+DUMP_MAX_PIX = 1 << 19              # ... so are the per-pixel arrays beyond this many active pixels,
+DUMP_MAX_MAP = 1 << 22              # ... count maps with more entries,
+DUMP_MAX_A11 = 1 << 20              # ... and A11 to a sample of its rows beyond this many entries
+DUMP_SEED = 20240907
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample(n, cap):
+    """Sorted row indices of the fixed sample of an n-row array (all rows when n <= cap): a pure function of (n, cap)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(m, alpha, out_dir, n_inl, P):
+    """What a caller of the timed single-GPU step receives after the last timed step, as .npy files in out_dir: the L2-regularised normal
+    equations (A11, b1, the active pixels with their A22 | b2 blocks), the reference-order residual vector ep, the count map and the two
+    counts.  float64, except the count map (float32: exact for counts below 2^24).  Arrays beyond the DUMP_MAX_* sizes are written as a fixed,
+    seeded sample (one sample of pixels for all three per-pixel arrays): at most 60 MiB in all."""
+    ne = m._finish(alpha, False)                     # download only: the step applied L2 already (as tests/test_gpu_parity.py reads it)
+    _, ep, nem = m.eval_finish(want_ep=True, want_map=True)
+    px = _sample(P, DUMP_MAX_PIX)
+    nem = nem.reshape(-1)
+    dim = ne["b1"].size
+    out = {"counts": np.array([n_inl, P], dtype=np.float64),
+           "A11": ne["A11"][_sample(dim, max(DUMP_MAX_A11 // dim, 1))], "b1": ne["b1"],
+           "active": ne["active"].astype(np.float64)[px], "A22": ne["A22"][px], "b2": ne["b2"].reshape(-1, 2)[px].reshape(-1),
+           "ep": ep[_sample(ep.size, DUMP_MAX_EP)],
+           "num_ev_map": nem[_sample(nem.size, DUMP_MAX_MAP)].astype(np.float32)}
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return total
 
 
 def pmc_traffic(workload_desc):
@@ -211,7 +253,14 @@ def main():
                          "(RCCL refuses two ranks on one device); exercises the launcher, the sharding and the protocol, not xGMI")
     ap.add_argument("--force-collectives", action="store_true",
                     help="rehearsal on ONE GPU: initialise RCCL with world_size 1 and run both all-reduces of the sharded protocol")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel samples, roofline, the ep blocks, the long block, clocks and power, "
+                         "collectives, cpu_baseline (the --no-* options and --long-steps select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (one GPU, resident step only)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.one_device or args.force_collectives):
+        ap.error("--dump-outputs needs the single-GPU step (--gpus 1, no --one-device, no --force-collectives)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -357,14 +406,17 @@ def main():
     # Kernel durations by HIP events on the kernels' stream, sampled on every 8th step of the timed region (at most 16 samples), each sample in
     # its own set of events that is read AFTER the loop: an event record opens a bubble of a few us in front of the next kernel, and reading one
     # back inside the loop would make the host wait for the Gram kernel — timing every step would distort the very throughput being measured.
+    # (--full only: a plain run times the steps alone)
     every = max(8, (args.steps + 15) // 16)
     slots = []
+    timed = False
     t0 = time.perf_counter()
     for i in range(args.steps):
-        timed = (i % every == every // 2)      # (not step 0: the first step of the region starts on an idle device; K = 20: steps 4 and 12)
-        if timed:
-            slots.append(len(slots))
-        m.enable_kernel_timing(timed, slots[-1] if timed else 0)
+        if args.full:
+            timed = (i % every == every // 2)      # (not step 0: the first step of the region starts on an idle device; K = 20: steps 4 and 12)
+            if timed:
+                slots.append(len(slots))
+            m.enable_kernel_timing(timed, slots[-1] if timed else 0)
         if os.environ.get("BENCH_DEBUG"):
             t_s = time.perf_counter(); n_inl, _ = step(); t_s = time.perf_counter() - t_s
             if t_s > 1e-3: print(f"[bench debug] step {i} took {t_s * 1e3:.2f} ms (timed={timed})", file=sys.stderr)
@@ -372,7 +424,10 @@ def main():
             n_inl, _ = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    m.enable_kernel_timing(False)
+    if args.dump_outputs:
+        print(f"bench: {dump_outputs(m, w.alpha, args.dump_outputs, n_inl, sh.P)} bytes of outputs in {args.dump_outputs}", file=sys.stderr)
+    if args.full:
+        m.enable_kernel_timing(False)
     warp_ms, accum_ms = [], []
     for sl in slots:
         a, b = m.kernel_ms_slot(sl)
@@ -388,7 +443,7 @@ def main():
     # long for the tail form), the step followed by the stand-alone compaction (config.with_ep_ms_per_step).
     with_ep_ms, no_ep_ms = None, None
     ep_in_step = (world == 1 and not args.force_collectives and m.get_option("step_ep") == 1 and m.get_option("ep_valid") == 1)
-    if not args.no_with_ep:
+    if args.full and not args.no_with_ep:
         barrier()
         t_e = time.perf_counter()
         for _ in range(args.steps):
@@ -414,7 +469,7 @@ def main():
     # an EMPTY kernel on this box (bracket_overhead_us), the shader clock a probe kernel measures right behind the block, and the card's own
     # report of its clocks and power cap.  None of it touches `value`.
     long_ms, kern_all, bracket_us, clocks, power_state = None, None, None, None, None
-    if args.long_steps > 0:
+    if args.full and args.long_steps > 0:
         n_long = int(min(args.long_steps, max(32, np.ceil(3.0 / max(t_b, 1e-6)))))        # at most ~3 s of stepping
         try:
             pci = m.pci_bus_id()
@@ -465,7 +520,7 @@ def main():
 
     # the exchanges alone (same buffers, same sizes, same stream), untimed w.r.t. `value`: what a step spends in collectives
     coll_ms = None
-    if use_dist:
+    if args.full and use_dist:
         plen = int(sh.pack_len) if sh.pack_len else pack_t.numel()
         barrier()
         t_c = time.perf_counter()
@@ -478,27 +533,9 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = n_total / (elapsed / args.steps)
-        wk_raw = float(np.mean(warp_ms))
-        # The bracket's own cost, calibrated in this run, two ways.  (i) empty_kernel_bracket_us: an EMPTY kernel between two events, queued behind work —
-        # an upper bound (it contains the empty kernel's own dispatch-to-completion time, which a profiler also counts as that kernel's duration).
-        # (ii) bracket_overhead_us: the steps sampled with consecutive events around all four launches are slower than their unsampled neighbours of the
-        # same block by exactly what the event records add — (sum of the four intervals - ms_per_step_long) / 4 per interval.  The dominant kernel's
-        # time is reported NET of (ii) (the figure rocprofv3's kernel trace agrees with), the raw reading beside it.
-        bracket_cost_us = None
-        if kern_all and long_ms:
-            bracket_cost_us = max(0.0, (kern_all["prep_pose_texel"] + kern_all["warp"] + kern_all["post_warp_a"] + kern_all["gram"] - long_ms) * 1e3 / 4.0)
-        wk = max(wk_raw - (bracket_cost_us if bracket_cost_us is not None else 0.0) * 1e-3, 1e-6)
         n_launch = local.size()
         n_cand = m.event_counts()[1]
         inl_frac = float(n_inl) / max(n_launch, 1)
-        # inlier-weighted byte model (VERDICT r4 #4c): event + link + predecessor are read for every event (36 B); the map gathers, ep, the count
-        # and A22 | b2 read-modify-writes and the 112-B A12 factor happen per INLIER (208 B)
-        wbytes = 36.0 + 208.0 * inl_frac
-        # (a shard-of-N run times one rank's part of the stream: its traffic summary is keyed by the shard, not by the whole window's description)
-        wkey = w.describe() if args.shard_of == 1 else f"{w.describe()} shard {args.shard_rank} of {args.shard_of}"
-        tr = pmc_traffic(wkey) if world == 1 else None
-        achieved = ALGO_BYTES_PER_EVENT * n_launch / (wk * 1e-3) / 1e9
-        counter = (tr["hbm_bytes_per_launch"] / (wk * 1e-3) / 1e9) if tr else None   # the bytes the counters saw, over the same time
         out = {
             "metric": "events/sec through warp+Jacobian+JtJ build, 1M events, 1024x2048 pano",
             "value": value, "unit": "events/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -515,33 +552,52 @@ def main():
                        "backend": ("gloo, all ranks on device 0 (rehearsal)" if args.one_device else "rccl") if use_dist else None,
                        "inliers_rank0": int(n_inl), "inlier_frac": inl_frac, "candidates_rank0": int(n_cand), "active_pixels": int(sh.P), "set_events_s": round(t_set, 3),
                        "settle": settle, "setup": m.setup_info()},
-            "roofline": {"bound": "hbm", "kernel": "emba_warp_tiled_kernel" if m.setup_info()["tile_order"] else "emba_warp_residual_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": (tr["hbm_bytes_per_launch"] if tr else None), "traffic_unit": "bytes/launch (rocprofv3 PMC, profiles/)",
-                         "counter_GBs": counter, "counter_frac": (counter / HBM_PEAK_GBS if counter else None),
-                         "algorithmic_bytes_per_launch": ALGO_BYTES_PER_EVENT * n_launch,
-                         "bytes_per_event": ALGO_BYTES_PER_EVENT, "events_per_launch": n_launch, "kernel_ms": wk, "kernel_ms_raw": wk_raw,
-                         "bracket_overhead_us": bracket_cost_us, "empty_kernel_bracket_us": bracket_us,
-                         "accumulate_kernel_ms": float(np.mean(accum_ms)),
-                         "path_frac": ALGO_BYTES_PER_EVENT * n_launch / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "inlier_weighted": {"bytes_per_event": wbytes, "model": "36 + 208 x inlier_frac", "inlier_frac": inl_frac,
-                                             "frac": wbytes * n_launch / (wk * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                             "path_frac": wbytes * n_launch / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}},
         }
-        if kern_all:
-            ksum = kern_all["prep_pose_texel"] + kern_all["warp"] + kern_all["post_warp_a"] + kern_all["gram"]
-            # consecutive events: the four intervals tile a sampled step from its first launch to the end of its last kernel (each includes the
-            # record of the event that ends it, ~bracket_overhead_us less what queuing hides); gap_ms = what a step of the SAME block costs on
-            # the host's clock beyond that — negative when the sampled steps' event records make them slower than the unsampled ones
-            out["kernels_ms"] = dict(kern_all, sum=ksum, gap_ms=(long_ms - ksum) if long_ms else None,
-                                     gap_vs_timed_region_ms=ms_per_step - ksum,
-                                     note="HIP events around all launches of every 16th step of the long block; intervals, not net of the bracket overhead")
-        out["device"] = {"clock_probe": clocks, "sysfs": power_state,
-                         "note": "sysfs: the card's own report sampled WHILE a block of steps ran, right behind the long block (the clock the kernels had; at the power cap it sits below the "
-                                 "attribute's peak).  clock_probe: shader cycles (s_memtime) per second of the constant-rate clock around a light fp32 chain on every "
-                                 "SIMD, right behind the block — the clock the chip returns to when the load is light"}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(w)
+        if args.full:
+            wk_raw = float(np.mean(warp_ms))
+            # The bracket's own cost, calibrated in this run, two ways.  (i) empty_kernel_bracket_us: an EMPTY kernel between two events, queued behind work —
+            # an upper bound (it contains the empty kernel's own dispatch-to-completion time, which a profiler also counts as that kernel's duration).
+            # (ii) bracket_overhead_us: the steps sampled with consecutive events around all four launches are slower than their unsampled neighbours of the
+            # same block by exactly what the event records add — (sum of the four intervals - ms_per_step_long) / 4 per interval.  The dominant kernel's
+            # time is reported NET of (ii) (the figure rocprofv3's kernel trace agrees with), the raw reading beside it.
+            bracket_cost_us = None
+            if kern_all and long_ms:
+                bracket_cost_us = max(0.0, (kern_all["prep_pose_texel"] + kern_all["warp"] + kern_all["post_warp_a"] + kern_all["gram"] - long_ms) * 1e3 / 4.0)
+            wk = max(wk_raw - (bracket_cost_us if bracket_cost_us is not None else 0.0) * 1e-3, 1e-6)
+            # inlier-weighted byte model (VERDICT r4 #4c): event + link + predecessor are read for every event (36 B); the map gathers, ep, the count
+            # and A22 | b2 read-modify-writes and the 112-B A12 factor happen per INLIER (208 B)
+            wbytes = 36.0 + 208.0 * inl_frac
+            # (a shard-of-N run times one rank's part of the stream: its traffic summary is keyed by the shard, not by the whole window's description)
+            wkey = w.describe() if args.shard_of == 1 else f"{w.describe()} shard {args.shard_rank} of {args.shard_of}"
+            tr = pmc_traffic(wkey) if world == 1 else None
+            achieved = ALGO_BYTES_PER_EVENT * n_launch / (wk * 1e-3) / 1e9
+            counter = (tr["hbm_bytes_per_launch"] / (wk * 1e-3) / 1e9) if tr else None   # the bytes the counters saw, over the same time
+            out["roofline"] = {"bound": "hbm", "kernel": "emba_warp_tiled_kernel" if m.setup_info()["tile_order"] else "emba_warp_residual_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                              "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                              "traffic": (tr["hbm_bytes_per_launch"] if tr else None), "traffic_unit": "bytes/launch (rocprofv3 PMC, profiles/)",
+                              "counter_GBs": counter, "counter_frac": (counter / HBM_PEAK_GBS if counter else None),
+                              "algorithmic_bytes_per_launch": ALGO_BYTES_PER_EVENT * n_launch,
+                              "bytes_per_event": ALGO_BYTES_PER_EVENT, "events_per_launch": n_launch, "kernel_ms": wk, "kernel_ms_raw": wk_raw,
+                              "bracket_overhead_us": bracket_cost_us, "empty_kernel_bracket_us": bracket_us,
+                              "accumulate_kernel_ms": float(np.mean(accum_ms)),
+                              "path_frac": ALGO_BYTES_PER_EVENT * n_launch / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "inlier_weighted": {"bytes_per_event": wbytes, "model": "36 + 208 x inlier_frac", "inlier_frac": inl_frac,
+                                                  "frac": wbytes * n_launch / (wk * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                  "path_frac": wbytes * n_launch / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+            if kern_all:
+                ksum = kern_all["prep_pose_texel"] + kern_all["warp"] + kern_all["post_warp_a"] + kern_all["gram"]
+                # consecutive events: the four intervals tile a sampled step from its first launch to the end of its last kernel (each includes the
+                # record of the event that ends it, ~bracket_overhead_us less what queuing hides); gap_ms = what a step of the SAME block costs on
+                # the host's clock beyond that — negative when the sampled steps' event records make them slower than the unsampled ones
+                out["kernels_ms"] = dict(kern_all, sum=ksum, gap_ms=(long_ms - ksum) if long_ms else None,
+                                         gap_vs_timed_region_ms=ms_per_step - ksum,
+                                         note="HIP events around all launches of every 16th step of the long block; intervals, not net of the bracket overhead")
+            out["device"] = {"clock_probe": clocks, "sysfs": power_state,
+                             "note": "sysfs: the card's own report sampled WHILE a block of steps ran, right behind the long block (the clock the kernels had; at the power cap it sits below the "
+                                     "attribute's peak).  clock_probe: shader cycles (s_memtime) per second of the constant-rate clock around a light fp32 chain on every "
+                                     "SIMD, right behind the block — the clock the chip returns to when the load is light"}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out), file=json_out, flush=True)
     if use_dist:
         dist.barrier()

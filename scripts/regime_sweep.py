@@ -32,7 +32,7 @@ WORK = {
 
 
 def run(tag, work, opts, steps):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "3", "--no-cpu-baseline", "--no-with-ep", "--long-steps", "0"] + WORK[work].split()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "3", "--no-cpu-baseline", "--no-with-ep", "--long-steps", "0"] + WORK[work].split()
     for o in opts:
         cmd += ["--opt", o]
     t0 = time.time()

@@ -15,6 +15,8 @@ import pytest
 from helpers import small_workload, oracle_run
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "so3_spline_n2.npz")
+# what the reference build under oracle/_ref returned for the inputs of the two tests that compare with it (tests/golden/make_ref_build_golden.py)
+REF_GOLD = os.path.join(os.path.dirname(__file__), "golden", "ref_build_vectors.npz")
 
 
 def test_spline_matches_reference_golden_bitwise(oracle_mod):
@@ -50,22 +52,35 @@ def test_spline_rejects_times_outside_knots(oracle_mod):
     assert oracle_mod.spline_eval(k, t0, dt, t0 + dt * (K - 1) - 1) is not None
 
 
-@pytest.mark.skipif(not __import__("oracle.oracle", fromlist=["x"]).ref_available(), reason="oracle/_ref not built/shipped")
-def test_primitives_match_reference_build_bitwise(oracle_mod):
-    O = oracle_mod
+def primitive_inputs():
+    """The rotation vectors of test_primitives_match_reference_build_bitwise: 200 random directions at each scale, then both sides of the
+    Taylor switch of Jl / Jl^-1, which sits at |phi|^2 = 1e-10 (sophus_utils.hpp:351,392)."""
     rng = np.random.default_rng(5)
+    W = []
     for scale in (1e-12, 1e-7, 1e-4, 0.05, 0.7, 2.0, 3.0):
         for _ in range(200):
             w = rng.normal(size=3)
-            w = w / np.linalg.norm(w) * scale * rng.uniform(0.5, 1.0)
-            assert np.array_equal(O.so3_exp(w), O.so3_exp(w, use_ref=True))
-            q = O.so3_exp(w, use_ref=True)
-            assert np.array_equal(O.so3_log(q), O.so3_log(q, use_ref=True))
-            a, b = O.left_jacobian(w), O.left_jacobian(w, use_ref=True)
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-    # the Taylor switch of Jl/Jl^-1 sits at |phi|^2 = 1e-10 (sophus_utils.hpp:351,392)
-    for n in (0.99e-5, 1.01e-5):
-        w = np.array([n, 0, 0.0])
+            W.append(w / np.linalg.norm(w) * scale * rng.uniform(0.5, 1.0))
+    W += [np.array([n, 0, 0.0]) for n in (0.99e-5, 1.01e-5)]
+    return np.array(W)
+
+
+def test_primitives_match_reference_build_bitwise(oracle_mod):
+    """so3_exp, so3_log and left_jacobian bit for bit against the reference build: against the vectors it recorded (REF_GOLD) everywhere,
+    and live where oracle/_ref is present."""
+    O = oracle_mod
+    g = np.load(REF_GOLD)
+    for i, w in enumerate(g["prim_w"]):
+        assert np.array_equal(O.so3_exp(w), g["prim_exp"][i]), i
+        assert np.array_equal(O.so3_log(g["prim_exp"][i]), g["prim_log"][i]), i
+        a = O.left_jacobian(w)
+        assert np.array_equal(a[0], g["prim_jl"][i]) and np.array_equal(a[1], g["prim_jl_inv"][i]), i
+    if not O.ref_available():
+        return
+    for w in primitive_inputs():
+        assert np.array_equal(O.so3_exp(w), O.so3_exp(w, use_ref=True))
+        q = O.so3_exp(w, use_ref=True)
+        assert np.array_equal(O.so3_log(q), O.so3_log(q, use_ref=True))
         a, b = O.left_jacobian(w), O.left_jacobian(w, use_ref=True)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
@@ -439,13 +454,15 @@ def test_cg_matches_the_reference_eigen_golden(oracle_mod):
         assert np.allclose(got, ex, rtol=1e-7, atol=1e-9 * np.abs(ex).max())
 
 
-def test_solver_restatements_live_against_the_reference_eigen_build(oracle_mod):
-    """Where oracle/_ref/libref_eigen.so is present (authoring container, and the GPU box: it travels prebuilt): random systems beyond the
-    golden file — SPD, semi-definite with zero rows, indefinite — same pivots, same zero pattern, same solution."""
-    O = oracle_mod
-    if O.ref_eigen() is None:
-        pytest.skip("oracle/_ref/libref_eigen.so not present")
+CG_WORKLOAD = dict(n_events=3000, pano_h=64, K=6, sensor=(12, 8), focal=10.0, seed=11)
+CG_CASES = ((1e-3, 3), (1e-1, 0))     # (lambda, leading unknowns fixed)
+
+
+def solver_inputs():
+    """The systems of test_solver_restatements_live_against_the_reference_eigen_build beyond the golden file — SPD, semi-definite with zero
+    rows, indefinite, equal diagonal entries — and the 2 x 2 matrices."""
     rng = np.random.default_rng(7)
+    systems = []
     for trial in range(40):
         n = int(rng.integers(2, 60))
         B = rng.normal(size=(n, n))
@@ -459,20 +476,51 @@ def test_solver_restatements_live_against_the_reference_eigen_build(oracle_mod):
             S[rng.integers(0, n), rng.integers(0, n)] *= -3; S = 0.5 * (S + S.T)
         elif kind == 3:    # equal diagonal entries: the pivot search must take the FIRST maximum
             S = np.eye(n) * 2.0 + 0.1 * (B + B.T) / n; np.fill_diagonal(S, 2.0)
-        a, b = O.ldlt_solve(S, rhs), O.ref_ldlt_solve(S, rhs)
-        assert np.array_equal(a[2], b[2]) and a[3] == b[3], f"trial {trial}: pivots / info"
-        assert np.array_equal(a[0] == 0, b[0] == 0)
-        assert np.allclose(a[0], b[0], rtol=1e-8, atol=1e-10 * np.abs(b[0]).max()), f"trial {trial}"
-    for _ in range(100):
-        A = rng.normal(size=4)
-        assert np.array_equal(O.inverse2(A), O.ref_inverse2(A))
+        systems.append((S, rhs))
+    return systems, np.array([rng.normal(size=4) for _ in range(100)])
+
+
+def _check_ldlt(O, S, rhs, x, piv, info, what):
+    a = O.ldlt_solve(S, rhs)
+    assert np.array_equal(a[2], piv) and a[3] == info, f"{what}: pivots / info"
+    assert np.array_equal(a[0] == 0, x == 0)
+    assert np.allclose(a[0], x, rtol=1e-8, atol=1e-10 * np.abs(x).max()), what
+
+
+def _check_cg(o, ne, r, w, lam, skip, ex, itr, errr):
+    x1, x2, it, err = o.solve_cg_sparse(ne, r["ep"], w.K, r["num_ev_map"], w.thres_valid_pixel, 0, 0.0, lam, bool(skip))
+    assert it == itr and err == pytest.approx(errr, rel=1e-6)
+    got = np.concatenate([x1[skip:], x2])
+    assert np.allclose(got, ex, rtol=1e-7, atol=1e-9 * np.abs(ex).max())
+
+
+def test_solver_restatements_live_against_the_reference_eigen_build(oracle_mod):
+    """Random systems beyond the golden file — SPD, semi-definite with zero rows, indefinite — same pivots, same zero pattern, same solution
+    as the reference's own Eigen: against what it returned for them (REF_GOLD) everywhere, and live where oracle/_ref/libref_eigen.so is
+    present (authoring container, and the GPU box: it travels prebuilt)."""
+    O = oracle_mod
+    g = np.load(REF_GOLD)
+    ends = np.cumsum(g["ldlt_n"]); S_ends = np.cumsum(g["ldlt_n"] ** 2)
+    for t, n in enumerate(g["ldlt_n"]):
+        S = g["ldlt_S"][S_ends[t] - n * n:S_ends[t]].reshape(n, n)
+        sl = slice(ends[t] - n, ends[t])
+        _check_ldlt(O, S, g["ldlt_rhs"][sl], g["ldlt_x"][sl], g["ldlt_piv"][sl], int(g["ldlt_info"][t]), f"golden trial {t}")
+    for A, inv in zip(g["inv2_A"], g["inv2_out"]):
+        assert np.array_equal(O.inverse2(A), inv)
     # solveNormalEqCG end to end by the reference's own assembly code (eigen_utils.cpp) on a system that is not in the golden file
-    w = small_workload(n_events=3000, pano_h=64, K=6, sensor=(12, 8), focal=10.0, seed=11)
+    w = small_workload(**CG_WORKLOAD)
     r = oracle_run(O, w, dense_A12=True)
     ne, o = r["ne"], r["oracle"]
-    for lam, skip in ((1e-3, 3), (1e-1, 0)):
+    for i, (lam, skip) in enumerate(CG_CASES):
+        _check_cg(o, ne, r, w, lam, skip, g[f"cg{i}_x"], int(g[f"cg{i}_iters"]), float(g[f"cg{i}_err"]))
+    if O.ref_eigen() is None:
+        return
+    systems, A2 = solver_inputs()
+    for trial, (S, rhs) in enumerate(systems):
+        b = O.ref_ldlt_solve(S, rhs)
+        _check_ldlt(O, S, rhs, b[0], b[2], b[3], f"trial {trial}")
+    for A in A2:
+        assert np.array_equal(O.inverse2(A), O.ref_inverse2(A))
+    for lam, skip in CG_CASES:
         x1r, x2r, itr, errr, _ = O.ref_solve_normal_eq_cg(ne["A11"][skip:, skip:], ne["A12"][skip:, :], ne["A22"], ne["b1"][skip:], ne["b2"], lam)
-        x1, x2, it, err = o.solve_cg_sparse(ne, r["ep"], w.K, r["num_ev_map"], w.thres_valid_pixel, 0, 0.0, lam, bool(skip))
-        assert it == itr and err == pytest.approx(errr, rel=1e-6)
-        ex = np.concatenate([x1r, x2r]); got = np.concatenate([x1[skip:], x2])
-        assert np.allclose(got, ex, rtol=1e-7, atol=1e-9 * np.abs(ex).max())
+        _check_cg(o, ne, r, w, lam, skip, np.concatenate([x1r, x2r]), itr, errr)
