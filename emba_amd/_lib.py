@@ -87,6 +87,8 @@ SIGNATURES = {
     "emba_get_map_active": (C.c_int, [C.c_void_p, _dp, C.c_size_t]),
     "emba_set_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "emba_reconstruct_intensity": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "emba_render_map_images": (C.c_int, [C.c_void_p, C.c_double, _u8p, _u8p, _u8p, _u8p]),
+    "emba_normalize_robust": (C.c_int, [C.c_void_p, _dp, C.c_size_t, C.c_double, _u8p, _dp, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "emba_count_map_ready": (C.c_int, [C.c_void_p]),
     "emba_count_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

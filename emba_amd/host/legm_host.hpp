@@ -123,6 +123,13 @@ public:
     // applyL2Reg(A22_blocks, b2, active, alpha, Gx, Gy)   model.cpp:689-719 (on the device-resident blocks; call once)
     void applyL2Reg(NormalEquations& ne, double alpha) { finish(ne, alpha, false); }
 
+    // record_data's map images (EMBA::saveEvoData / saveOptData, solver.cpp:370-479) of the map the next evaluation would use, rendered on the device:
+    // pano_height*pano_width bytes each (rgb: x3, interleaved R, G, B); nullptr skips an image (poisson: also the Poisson solve).  Writes no file.
+    void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson)
+    {
+        check(emba_render_map_images(ctx_, pct_discard, gx, gy, rgb, poisson));
+    }
+
     emba_ctx* ctx() { return ctx_; }
 
 private:

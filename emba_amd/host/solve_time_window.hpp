@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <filesystem>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <system_error>
@@ -147,8 +148,12 @@ inline void incrementalUpdate(std::vector<double>& knots_xyzw, const std::vector
 // EMBA::solveTimeWindow(traj, Gx, Gy, events) — solver.cpp:11-368 — resident on the device(s) behind `model`.
 // traj: the window's initial control poses + spline timing; Gx / Gy: the initial map planes (H x W, row-major, uploaded once);
 // rl: optional run-time records.  Returns the refined poses, the final cost and the iteration log; model.downloadMap() gives the refined map.
+// record: optional record_data callback (iter, final) at the reference's three points — every loop iteration (solver.cpp:173, final = false),
+// convergence (:332-336) and forced termination (:360-364) (final = true: saveEvoData + saveOptData).  The map resident when it is called is the
+// accepted one (model.render_map_images renders it); the caller writes the files.
 inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0, const EventPacket& events, const double* Gx, const double* Gy,
-                                const BASettings& ba = BASettings(), const LMSettings& lm = LMSettings(), RuntimeLog* rl = nullptr)
+                                const BASettings& ba = BASettings(), const LMSettings& lm = LMSettings(), RuntimeLog* rl = nullptr,
+                                const std::function<void(int, bool)>& record = nullptr)
 {
     using clock = std::chrono::steady_clock;
     auto secs = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
@@ -187,6 +192,7 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
             if (rl) { model.sync(); rl->add(RuntimeLog::FormEqs, iter, secs(t0)); }                             // :105-151
         }
         if (rl) rl->iteration(iter, lambda, cost_min, cost_new, cost_data, cost_reg);                           // :170-178
+        if (record) record(iter, false);                                                                      // :173 saveEvoData
         std::vector<double> x1;
         int cg_it = -1;
         bool numeric_failure = false;
@@ -239,7 +245,11 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
             lambda /= 10;
             cost_min_old = cost_min; cost_min = cost_new; cost_data = cost_data_new; cost_reg = cost_reg_new;
             if (std::fabs(1 - cost_min / (cost_min_old + 1e-10)) < lm.tol_fun) {
-                if (++count_tol >= lm.num_times_tol_fun_sat) { res.converged = true; break; }
+                if (++count_tol >= lm.num_times_tol_fun_sat) {
+                    res.converged = true;
+                    if (record) record(iter, true);                                                           // :332-336
+                    break;
+                }
             }
         } else {                                                                                                // :340-352
             cost_has_decreased = false;
@@ -248,6 +258,7 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
             count_tol = 0;
         }
     }
+    if (!res.converged && record) record(iter, true);                                                         // :360-364 forced termination
     res.knots_xyzw = knots; res.cost_min = cost_min; res.iterations = iter;
     res.loop_ms = secs(t_loop) * 1e3;
     return res;

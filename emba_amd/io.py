@@ -12,6 +12,7 @@
                                                                       projectPixelTo3dRay for a monocular plumb_bob camera)
   normalize_robust / save_pgm    image_util::normalizeRobust          src/utils/image_utils.cpp:13-38   (8-bit display images of maps and of the
                                                                       Poisson-reconstructed panorama, solver.cpp:417-425; PGM instead of PNG)
+  save_png                       cv::imwrite of an 8-bit image         solver.cpp:381-479 (record_data's map images; grey or RGB, standard-library zlib)
   save_events / load_events      a flat .npz replacing the rosbag of src/utils/rosbag_loading.cpp (x, y u16; polarity u8; t_ns i64, sorted)
 
 Host-side, O(K) or file-sized work; the per-event path is emba_amd.LEGM.
@@ -179,6 +180,31 @@ def save_pgm(path, img_u8):
     with open(path, "wb") as f:
         f.write(b"P5\n%d %d\n255\n" % (img_u8.shape[1], img_u8.shape[0]))
         f.write(img_u8.tobytes())
+
+
+def save_png(path, img_u8, level=1):
+    """8-bit greyscale (H x W) or RGB (H x W x 3) PNG: filter type 0 on every row, deflated with the standard library's zlib at `level`."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(img_u8, dtype=np.uint8)
+    if a.ndim == 2:
+        color, ch = 0, 1
+    elif a.ndim == 3 and a.shape[2] == 3:
+        color, ch = 2, 3
+    else:
+        raise ValueError(f"save_png takes H x W or H x W x 3 uint8, not {a.shape}")
+    h, w = a.shape[:2]
+    raw = np.empty((h, 1 + w * ch), np.uint8)
+    raw[:, 0] = 0
+    raw[:, 1:] = a.reshape(h, w * ch)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, color, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), level)))
+        f.write(chunk(b"IEND", b""))
 
 
 # ---- events ---------------------------------------------------------------------------------------------------------------

@@ -367,6 +367,27 @@ class LEGM:
         self._check(self._L.emba_reconstruct_intensity(self._ctx, _p(Gx, _dp), _p(Gy, _dp), _p(M, _dp)))
         return M
 
+    def renderMapImages(self, pct=0.1, poisson=True):
+        """The images EMBA::saveEvoData / saveOptData write (solver.cpp:370-479), rendered on the device from the map the next evaluation would
+        use (the one downloadMap returns): {"Gx", "Gy": normalizeRobust(G, pct), "G_hsv": H x W x 3 RGB (hue = orientation, value = magnitude),
+        "map_poisson": normalizeRobust(reconstructIntensity(), pct) or None with poisson=False}, all uint8.  Synchronous: the images are in host
+        memory when it returns."""
+        H, W = self.H, self.W
+        gx, gy = np.empty((H, W), np.uint8), np.empty((H, W), np.uint8)
+        rgb = np.empty((H, W, 3), np.uint8)
+        mp = np.empty((H, W), np.uint8) if poisson else None
+        self._check(self._L.emba_render_map_images(self._ctx, float(pct), _p(gx, _u8p), _p(gy, _u8p), _p(rgb, _u8p), _p(mp, _u8p)))
+        return {"Gx": gx, "Gy": gy, "G_hsv": rgb, "map_poisson": mp}
+
+    def normalizeRobust(self, img, pct=0.1, with_range=False):
+        """image_util::normalizeRobust (image_utils.cpp:14-38) of any float64 plane on the device: bit for bit io.normalize_robust.
+        with_range=True also returns the order statistics (rmin, rmax)."""
+        a = np.ascontiguousarray(img, dtype=np.float64)
+        out = np.empty(a.shape, np.uint8)
+        rmin, rmax = C.c_double(), C.c_double()
+        self._check(self._L.emba_normalize_robust(self._ctx, _p(a, _dp), a.size, float(pct), _p(out, _u8p), C.byref(rmin), C.byref(rmax)))
+        return (out, (rmin.value, rmax.value)) if with_range else out
+
     def A12_sparse(self):
         """Rank-1 factors of A12 (one per measurement candidate; pix == -1 marks outliers/inactive)."""
         _, M = self.event_counts()

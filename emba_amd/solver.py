@@ -85,6 +85,69 @@ class RuntimeLog:
         self._app("CG_iterations.txt", f"iter #{it} iter_times = {iters} error = {err:g}")
 
 
+class MapRecorder:
+    """The map images of the reference's record_data output (EMBA::saveEvoData / saveOptData, solver.cpp:370-479) under <result_dir>:
+    Gx_evo/, Gy_evo/, G_hsv_evo/, map_poisson_evo/ (an evo set per record point) and map_opt/ (the final set), file names
+    {win}Gx_evo_{iter:04d}.png ... {win}map_poisson_opt_{iter:04d}.png with win = "win_%04d_" (the first window is win_0000_, solver.cpp:52-54).
+    The images are rendered on the device (model.renderMapImages) synchronously — their copy to the host has completed when record() returns;
+    PNG encoding and writing run on `writers` background threads.  close() joins them and re-raises a failed write.  render_s / encode_s: the
+    total time spent rendering (on the loop's thread) and encoding + writing (summed over the writer threads)."""
+
+    EVO = (("Gx", "Gx_evo", "Gx_evo"), ("Gy", "Gy_evo", "Gy_evo"), ("G_hsv", "G_hsv_evo", "G_hsv_evo"), ("map_poisson", "map_poisson_evo", "map_poisson_evo"))
+    OPT = (("Gx", "map_opt", "Gx_opt"), ("Gy", "map_opt", "Gy_opt"), ("G_hsv", "map_opt", "G_hsv_opt"), ("map_poisson", "map_opt", "map_poisson_opt"))
+
+    def __init__(self, result_dir, png_level=1, writers=2, pct=0.1):
+        import os
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        self.dir, self.png_level, self.pct = result_dir, png_level, pct
+        for d in ("Gx_evo", "Gy_evo", "G_hsv_evo", "map_poisson_evo", "map_opt"):
+            os.makedirs(os.path.join(result_dir, d), exist_ok=True)
+        self.window = -1                     # new_window() makes the first one win_0000_
+        self.render_s = self.encode_s = 0.0
+        self.sets = 0
+        self.files = []                      # paths in the order they were queued
+        self._lock = threading.Lock()
+        self._pool = ThreadPoolExecutor(max_workers=max(1, int(writers)), thread_name_prefix="map_recorder")
+        self._futures = []
+
+    def new_window(self):
+        self.window += 1
+
+    def record(self, model, it, final=False):
+        """saveEvoData(Gx, Gy, win, it), and saveOptData too with final=True (one render serves both sets)."""
+        import os
+        import time
+        if self.window < 0:
+            self.window = 0
+        t0 = time.perf_counter()
+        imgs = model.renderMapImages(self.pct, poisson=True)
+        self.render_s += time.perf_counter() - t0
+        win = "win_%04d_" % self.window
+        for table in ((self.EVO, self.OPT) if final else (self.EVO,)):
+            self.sets += 1
+            for key, folder, stem in table:
+                path = os.path.join(self.dir, folder, f"{win}{stem}_{it:04d}.png")
+                self.files.append(path)
+                self._futures.append(self._pool.submit(self._write, path, imgs[key]))
+
+    def _write(self, path, img):
+        import time
+        t0 = time.perf_counter()
+        emba_io.save_png(path, img, self.png_level)
+        with self._lock:
+            self.encode_s += time.perf_counter() - t0
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+        futures, self._futures = self._futures, []
+        for f in futures:
+            f.result()
+
+    def summary(self):
+        return dict(sets=self.sets, files=len(self.files), render_s=self.render_s, encode_s=self.encode_s)
+
+
 class _Phases:
     """The three things the loop asks of the model, through the reference-shaped methods (evaluateDataError returns ep and the count
     map to the host, as LEGM::evaluateDataError does) or, with resident=True, through the phase-level calls that leave both in HBM."""
@@ -130,15 +193,20 @@ class _Phases:
             m.applyL2Reg(ba.alpha)                                                   # :130
 
 
-def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSettings(), verbose=False, resident=False, runtime_log=None):
+def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSettings(), verbose=False, resident=False, runtime_log=None, map_recorder=None):
     """model: emba_amd.LEGM.  The refined map stays on the device (model.downloadMap()); returns LMResult.
     resident=True keeps residuals and count map in HBM too (only costs, counts and the 3K pose increments reach the host).
     runtime_log: a RuntimeLog — the reference's runtime_*.txt / iterations.txt records (each timed phase then ends in a host synchronisation,
-    as it does in the reference's synchronous calls)."""
+    as it does in the reference's synchronous calls).
+    map_recorder: a MapRecorder — record_data's map images at the reference's three points: an evo set every loop iteration (solver.cpp:173),
+    evo + opt at convergence (:332-336) and at forced termination (:360-364)."""
     import time
     rl = runtime_log
+    mr = map_recorder
     if rl is not None:
         rl.new_window()
+    if mr is not None:
+        mr.new_window()
 
     def timed(key, it_, fn, Np=None):
         if rl is None:
@@ -165,6 +233,8 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
             timed("formEqs", it, lambda: ph.form(traj.size()))                       # :93-131 (+ :105-151 runtime_formEqs.txt)
         if rl is not None:                                                           # :170-178
             rl.iteration(it, lam, cost_min, cost_new, *cost_parts)
+        if mr is not None:                                                           # :173 saveEvoData
+            mr.record(model, it)
         # x2 goes from the solver to updateMap and nowhere else (solver.cpp:193-239): a device model keeps it in HBM (x2 is None here)
         rkw = dict(resident_x2=True) if getattr(model, "supports_resident_x2", False) else {}
         try:
@@ -208,6 +278,8 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
             if abs(1 - cost_min / (cost_min_old + 1e-10)) < lm.tol_fun:
                 count_tol += 1
                 if count_tol >= lm.num_times_tol_fun_sat:
+                    if mr is not None:                                               # :332-336 saveEvoData + saveOptData
+                        mr.record(model, it, final=True)
                     return LMResult(traj, cost_min, it, True, log, "tolerance")
         else:                                                                        # :340-352
             decreased = False
@@ -223,4 +295,6 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
             lam *= 10
             count_tol = 0
     reason = "max_iter" if it > lm.max_num_iter else ("cost" if cost_min <= 1e-16 else "lambda")
+    if mr is not None:                                                               # :360-364 forced termination
+        mr.record(model, it, final=True)
     return LMResult(traj, cost_min, it, False, log, reason)

@@ -9,7 +9,8 @@
 
 Inputs: events (.npz: x, y u16; polarity u8; t_ns i64), initial poses ("t tx ty tz qx qy qz qw" per line), initial map
 (Gx.bin / Gy.bin raw float64, H x 2H), calibration (.npz: K [3,3], D [<=5] plumb_bob, width, height).
-Outputs: <out>/refined_traj.txt, <out>/Gx.bin, <out>/Gy.bin (the files emba.cpp:300-330 writes), <out>/map_poisson_opt.pgm."""
+Outputs: <out>/refined_traj.txt, <out>/Gx.bin, <out>/Gy.bin (the files emba.cpp:300-330 writes), <out>/map_poisson_opt.pgm; with --record-data
+also the reference's record_data map images (solver.cpp:173-179, 332-336, 360-364): <out>/{Gx_evo,Gy_evo,G_hsv_evo,map_poisson_evo,map_opt}/*.png."""
 import argparse
 import os
 import sys
@@ -21,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from emba_amd import LEGM, io as eio, so3, synth                      # noqa: E402
 from emba_amd.legm import LinearTrajectory                            # noqa: E402
-from emba_amd.solver import BASettings, LMSettings, RuntimeLog, solve_time_window  # noqa: E402
+from emba_amd.solver import BASettings, LMSettings, MapRecorder, RuntimeLog, solve_time_window  # noqa: E402
 
 
 def main():
@@ -40,6 +41,8 @@ def main():
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--runtime-log", action="store_true", help="write the reference's run-time records under <out>/final_results (every timed phase then ends in a host synchronisation)")
+    ap.add_argument("--record-data", action="store_true", help="write the reference's record_data map images (PNG, rendered on the device) under <out>/ "
+                    "at every LM iteration and at the end (rank 0)")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
     a = ap.parse_args()
     if a.alpha is None:
@@ -97,8 +100,15 @@ def main():
     t0 = time.time()
     # the reference's run-time records (final_results/runtime_{formEqs,solveEqs,objFuncs}.txt, iterations.txt: solver.cpp:105-151, 170-178, 205-223, 271-291)
     rlog = RuntimeLog(a.out) if (a.runtime_log and rank == 0) else None
-    res = solve_time_window(model, traj, events, Gx, Gy, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True, runtime_log=rlog)
+    mrec = MapRecorder(a.out) if (a.record_data and rank == 0) else None
+    res = solve_time_window(model, traj, events, Gx, Gy, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True, runtime_log=rlog,
+                            map_recorder=mrec)
     dt = time.time() - t0
+    if mrec is not None:
+        mrec.close()
+        sm = mrec.summary()
+        print(f"record_data: {sm['files']} PNG files in {sm['sets']} sets; rendering {sm['render_s'] * 1e3:.1f} ms (in the loop), "
+              f"encoding + writing {sm['encode_s'] * 1e3:.1f} ms (writer threads)")
     if rank != 0:                                           # every rank holds the same result; rank 0 writes it
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()

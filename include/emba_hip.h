@@ -243,6 +243,21 @@ emba_status emba_get_map_active(emba_ctx* ctx, double* gxy_host, size_t cap_P);
  * use and kept (8 (H^2 + W^2) bytes). */
 emba_status emba_reconstruct_intensity(emba_ctx* ctx, const double* Gx_host, const double* Gy_host, double* M_host);
 
+/* The map images of the reference's record_data output (EMBA::saveEvoData / saveOptData, solver.cpp:370-479), rendered on the device from the map the
+ * next evaluation would use (the one emba_download_map copies).  Host pointers, H x W bytes each (rgb_u8: H x W x 3, interleaved R, G, B); a NULL pointer
+ * skips that image, a NULL poisson_u8 also skips the Poisson solve.
+ *   gx_u8 / gy_u8   image_util::normalizeRobust(G, pct_discard) (image_utils.cpp:14-38): rmin / rmax are the exact order statistics of ranks
+ *                   int(f32(0.5 pct / 100) * n) and int(f32(1 - 0.5 pct / 100) * n) (clamped to n - 1), u8 = sat(rint(scale (v - rmin))),
+ *                   scale = 255 / (rmax - rmin) or 1 when rmax == rmin — bit for bit emba_amd/io.normalize_robust
+ *   rgb_u8          hue = 0.5 * orientation of (Gx, Gy) in degrees, min-max normalised to [0, 179]; S = 255; value = magnitude, min-max normalised to
+ *                   [0, 255]; OpenCV's 8-bit HSV -> RGB (render_kernels.h states the arithmetic; not pinned against OpenCV's approximate cartToPolar)
+ *   poisson_u8      emba_reconstruct_intensity of the resident map, robust-normalised as above
+ * The images come back through the context's pinned staging buffers; the call returns when they are in host memory. */
+emba_status emba_render_map_images(emba_ctx* ctx, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8);
+/* The same robust normalisation of any plane of n doubles (host memory): dst_host (n bytes, or NULL) and the order statistics rmin / rmax (or NULL).
+ * Needs a context only (no map, no events). */
+emba_status emba_normalize_robust(emba_ctx* ctx, const double* src_host, size_t n, double pct_discard, uint8_t* dst_host, double* rmin, double* rmax);
+
 /* Schur-complement solve: LEGM::solveNormalEq(A11, A12, A22_blocks, b1, b2, lambda, x1, x2), model.cpp:721-792,
  * on the device-resident normal equations of the last emba_form_finish (so after applyL2Reg, as in solver.cpp:130,190-202),
  * consuming the SPARSE A12 factors: S = A11m - A12 A22m^-1 A12^T is formed chunk-wise from per-pixel column pairs built from the
