@@ -22,7 +22,6 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "kernels.h"
@@ -37,12 +36,37 @@ namespace {
 
 thread_local std::string g_create_error;
 
+}  // namespace
+
+// Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
+// (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
+// The memory goes with the buffer (move-only); the context frees its buffers after draining its stream, the group each rank's with the rank's device current.
 struct DevBuf {
     void* p = nullptr;
-    size_t bytes = 0;
+    size_t bytes = 0;     // capacity
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+    ~DevBuf() { reset(); }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    // at least n bytes (8 at the least); *fresh: the memory is new — uninitialised, or 0xFF bytes (written on `s`) with poison
+    hipError_t ensure(size_t n, bool* fresh = nullptr, bool poison = false, hipStream_t s = nullptr)
+    {
+        n = std::max<size_t>(n, 8);
+        if (fresh) *fresh = false;
+        if (p && bytes >= n) return hipSuccess;
+        reset();
+        hipError_t e = hipMalloc(&p, n);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = n;
+        if (fresh) *fresh = true;
+        return poison ? hipMemsetAsync(p, 0xFF, n, s) : hipSuccess;
+    }
 };
 
-}  // namespace
+// a record set: what one evaluation wrote, per candidate slot (records_valid: stamped with the evaluation number `stamp`)
+struct RecordSet { DevBuf rec, tag; uint32_t stamp = 0; };
 
 struct SolveLists { uint32_t* off = nullptr; emba::RecView sorted{}; };   // per-pixel record lists of a solve — sorted: the participating records in pixel order; off[i]: first record of pixel i
 
@@ -59,30 +83,31 @@ struct emba_ctx {
     double fov_x = M_PI, fov_y = M_PI;    // the sensor's field of view (rad), from the bearing LUT
 
     // persistent device buffers
-    double* d_lut = nullptr;
-    double* d_texel = nullptr;
-    double* d_Gx_own = nullptr; double* d_Gy_own = nullptr;
+    DevBuf d_lut;
+    DevBuf d_texel;
+    DevBuf d_Gx_own, d_Gy_own;
     const double* d_Gx = nullptr; const double* d_Gy = nullptr;   // the map planes the next evaluation reads (current or trial)
     const double* d_Gx_cur = nullptr; const double* d_Gy_cur = nullptr;   // current (accepted) map: own upload, bound, or accepted trial
-    double* d_Gx_trial = nullptr; double* d_Gy_trial = nullptr; bool map_is_trial = false;
-    // the per-pixel record lists + pixel-ordered records of the last LOCAL solve (workspaces 0, 33): a re-solve of the same equations with another
+    DevBuf d_Gx_trial, d_Gy_trial; bool map_is_trial = false;
+    // the per-pixel record lists + pixel-ordered records of the last LOCAL solve (lists.off, lists.sorted): a re-solve of the same equations with another
     // lambda (a rejected LM trial, solver.cpp:340-352) reuses them
     bool lists_valid = false; uint32_t lists_stamp = 0; size_t lists_P = 0, lists_nrec = 0;
     // round 6: ... and so does the SHARDED solve — lists_packed: the workspaces hold the records this rank RECEIVED as the owner of the pixels
     // [lists_lo, lists_lo + lists_P), keyed by its own working set's stamp (the ranks evaluate and form in lockstep); a re-solve skips count, pack and the all-to-all
     bool lists_packed = false; long lists_lo = 0;
-    struct CgShard { bool active = false; int rank = 0, n_ranks = 1, n = 0, skip = 0; size_t lo = 0, npix = 0, Nl = 0; double lambda = 0;
-                     double *x = nullptr, *r = nullptr, *p = nullptr, *z = nullptr, *t = nullptr, *invd = nullptr, *sc = nullptr; SolveLists L; } cg;   // emba_cg_shard_*
+    // emba_cg_shard_*: the session's sizes; its vectors are the solve scratch (sv), its lists the lists cache.  active: begin succeeded, and since then neither
+    // another solve nor a failed emba_cg_shard_* call has taken the scratch
+    struct CgShard { bool active = false; int rank = 0, n_ranks = 1, n = 0, skip = 0; size_t lo = 0, npix = 0, Nl = 0; double lambda = 0; } cg;
     uint32_t count_stamp = 0;   // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
     size_t perm_lo = 0, perm_n = 0;   // ... of the pixels [perm_lo, perm_lo + perm_n) of the active set (a rank's owned range in the sharded solve)
-    bool perm_valid = false; uint32_t* d_perm = nullptr;   // column order of U for the local Schur solve (solve_perm), valid with the lists
+    bool perm_valid = false;   // sv.perm holds the column order of U for the local Schur solve (solve_perm), valid with the lists
     int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
     double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of emba_costs, written by the kernel itself
-    double* h_cost_dev = nullptr; double* d_cost_acc = nullptr; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
-    double* d_x2 = nullptr; size_t x2_cap = 0; size_t x2_resident_P = (size_t)-1;   // x2_resident_P: d_x2 holds the x2 of the last solve on this context (for that many pixels)
-    int32_t* d_count_own = nullptr; int32_t* d_count = nullptr;
+    double* h_cost_dev = nullptr; DevBuf d_cost_acc; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
+    DevBuf d_x2; size_t x2_resident_P = (size_t)-1;   // x2_resident_P: d_x2 holds the x2 of the last solve on this context (for that many pixels)
+    DevBuf d_count_own; int32_t* d_count = nullptr;
     bool counts_raw = false;   // the count map holds the warp kernel's markers, not yet the counts (see ensure_counts)
-    double* d_pixacc = nullptr; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
+    DevBuf d_pixacc; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
     bool pixacc_clean = false;     // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
     bool pixacc_consumed = false;  // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
     bool step_consume = false;     // set by emba_step around its emba_form_active: this gather is the sums' only reader
@@ -90,19 +115,19 @@ struct emba_ctx {
     int32_t count_mark = 0;        // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
     int use_texel = 0;    // what the current evaluation uses: 0 fly, 1 full pack, 3 rectangle
-    int* d_rect = nullptr;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
-    int* d_blk_rect = nullptr;   // per prep-block boxes
-    int32_t* d_compact = nullptr; uint8_t* d_active_bits = nullptr;   // 1 bit per pixel: count >= thres of the current active set
-    uint32_t* d_active = nullptr;
-    uint32_t* d_ablk_cnt = nullptr; uint32_t* d_ablk_off = nullptr; size_t n_ablk = 0;
-    double* d_pack_own = nullptr; size_t pack_own_cap = 0;
-    double* d_pack = nullptr; size_t pack_cap = 0; bool pack_bound = false;
-    double* d_knots = nullptr; int knots_cap = 0;
+    DevBuf d_rect;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
+    DevBuf d_blk_rect;   // per prep-block boxes
+    DevBuf d_compact, d_active_bits;   // 1 bit per pixel: count >= thres of the current active set
+    DevBuf d_active;
+    DevBuf d_ablk_cnt, d_ablk_off; size_t n_ablk = 0;
+    DevBuf d_pack_own;
+    double* d_pack = nullptr; size_t pack_cap = 0; bool pack_bound = false;   // d_pack_own, or the caller's buffer (emba_bind_exchange_buffers)
+    DevBuf d_knots;
     int* d_err = nullptr;           // status word of the CURRENT evaluation: one of the two words of d_err2 (they alternate: an evaluation's first launch
-    int* d_err2 = nullptr;          // clears the NEXT evaluation's word while its own pose threads may already be setting bits of the current one)
+    DevBuf d_err2;                  // clears the NEXT evaluation's word while its own pose threads may already be setting bits of the current one)
     uint32_t eval_seq = 0;
-    uint32_t* d_total = nullptr;    // [0] inliers, [1] active pixels
-    double* d_scalar = nullptr;     // cost reductions
+    DevBuf d_total;                 // [0] inliers, [1] active pixels
+    DevBuf d_scalar;                // cost reductions
     std::vector<uint32_t> h_pix_starts; uint32_t pix_starts_seq = 0;   // emba_get_inlier_pixel_starts of evaluation number pix_starts_seq (eval_seq), for emba_get_ep_by_pixel
     void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
     int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3] step sequence number
@@ -116,15 +141,14 @@ struct emba_ctx {
     bool have_events = false, have_map = false;
     size_t n_in = 0, n_used = 0, n_halo = 0, n_pm = 0, n_sorted = 0, n_batch = 0, n_cand = 0;   // n_pm: pm-order entries (events + halo); n_sorted: entries of the device order
     long nblk = 0;
-    uint32_t* d_pm_pix = nullptr; uint32_t* d_pm_batch = nullptr; uint32_t* d_pm_orig = nullptr;   // pm-order = (sensor pixel, time): the reference's per-pixel vectors laid end to end
-    uint32_t* d_ev_pix = nullptr; uint32_t* d_ev_batch = nullptr; uint32_t* d_ev_slot = nullptr;    // device order (== pm-order arrays in pixel order; own arrays in tile order)
-    uint32_t* d_ev_pix_own = nullptr; uint32_t* d_ev_batch_own = nullptr;                          // tile order: the arrays d_ev_pix / d_ev_batch point to
-    uint32_t* d_ev_pm = nullptr;                                                                    // tile order only: entry -> pm index
+    DevBuf d_pm_pix, d_pm_batch, d_pm_orig;                                                         // pm-order = (sensor pixel, time): the reference's per-pixel vectors laid end to end
+    uint32_t* d_ev_pix = nullptr; uint32_t* d_ev_batch = nullptr; DevBuf d_ev_slot;                 // device order (== pm-order arrays in pixel order; own arrays in tile order)
+    DevBuf d_ev_pix_own, d_ev_batch_own;                                                            // tile order: the arrays d_ev_pix / d_ev_batch point to
+    DevBuf d_ev_pm;                                                                                 // tile order only: entry -> pm index
     bool have_ev_pm = false;
-    std::unordered_map<void**, size_t> caps;                                                        // capacities of the grow-only device buffers (dev_alloc)
-    uint16_t* d_cp = nullptr; double* d_batch_u = nullptr;                                          // control-pose index (= spline segment) and spline parameter per batch
-    double* d_ev_u = nullptr; uint16_t* d_ev_seg = nullptr;                                         // tile order: the same per entry of the device order
-    ChunkDesc* d_chunks = nullptr; long n_chunks = 0;                                               // tile order: one per workgroup of the tiled warp kernel
+    DevBuf d_cp, d_batch_u;                                                                         // control-pose index (= spline segment) and spline parameter per batch
+    DevBuf d_ev_u, d_ev_seg;                                                                        // tile order: the same per entry of the device order
+    DevBuf d_chunks; long n_chunks = 0;                                                             // tile order: one per workgroup of the tiled warp kernel
     int segpose_mode = 0;      // option segpose (A/B; 0 auto = yes, 1 no, 2 yes): pixel order evaluates the pose per event from segment records (default: yes)
     bool segpose = false;      // ... in the current evaluation
     bool chunks_lpt = false;   // the chunk list is sorted longest first and walked in grid order (no XCD-contiguous remapping)
@@ -132,28 +156,27 @@ struct emba_ctx {
     double order_per_px = 0.0, order_lead_frac = 0.0;   // what the last order decision saw (diagnostics: emba_last_order_stats)
     bool tile_order = false; int order_mode = 0;   // option order: 0 auto, 1 pixel, 2 tile
     size_t n_lead = 0;                             // lead-in copies the tile order added
-    int64_t* d_batch_t = nullptr; double* d_pose = nullptr;   // pose table: 112 B per batch (pixel order; the tile order only uses it to predict the bins)
-    double* d_seg = nullptr; int seg_cap = 0;                 // tile order: per-segment constants the tiled kernel evaluates each event's pose from (12 doubles per segment)
+    DevBuf d_batch_t, d_pose;   // pose table: 112 B per batch (pixel order; the tile order only uses it to predict the bins)
+    DevBuf d_seg;                                             // tile order: per-segment constants the tiled kernel evaluates each event's pose from (12 doubles per segment)
     int step_gather = 2;    // option step_gather: how emba_step writes its active set + A22 | b2 rows — 0 the sweeping kernel (emba_active_write_kernel), 1 the list-driven
                             // gather as a kernel of its own, 2 (default) the list-driven gather as the head of the compact Gram kernel
-    uint16_t* d_seg_act = nullptr;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
+    DevBuf d_seg_act;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
     bool aw_in_gram = false; ActiveWriteParams aw_saved{};   // the gather of the running step, to be issued with its Gram launch (emba_form_accumulate)
     int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
     bool no_alt_set = false;   // set by emba_step around its evaluation: the step re-forms the equations itself, nothing of the previous ones can be gone back to —
                                // no second record set (+12.8 GB at 100 M events for callers that can never reject)
     int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
-    double* d_tag = nullptr; int use_tags = 1;   // per-slot {pano pixel, stamp}: lets the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
-    double* d_rec = nullptr; uint32_t* d_slot_key = nullptr; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
-    // Two record sets (a rejected LM trial must not cost a re-evaluation).  d_rec / d_tag / set_stamp are the WORKING set: what
+    int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
+    DevBuf d_slot_key; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
+    // Two record sets (a rejected LM trial must not cost a re-evaluation).  `work` is the WORKING set: what
     // the last evaluation wrote and what formNormalEq and the solvers read.  An evaluation that would overwrite records the current normal
     // equations were formed from (accum_done) first swaps in the other set; emba_map_reject / emba_trial_reject swaps back, so the solver can be
     // called again with a larger lambda on untouched equations (solver.cpp:340-352 reuses A, b).  Nothing else needs a second copy: the
     // pack, the active set and the compact index are written by formNormalEq only, which never runs on a rejected trial.
-    double* d_rec2 = nullptr; double* d_tag2 = nullptr;
-    uint32_t set_stamp = 0, set_stamp2 = 0;      // stamp of the evaluation that wrote each set
+    RecordSet work, alt;
     bool eq_in_alt = false;                      // the equations in the pack belong to the OTHER set (a trial evaluation has been written since)
     struct EqState { bool active_done = false, accum_done = false, finish_done = false, compact_valid = false, l2_fused = false; size_t P = 0, pack_len = 0; int K = 0, thres = 0, irls = 0; double eta = 0; } eq_saved;
-    double* d_e_sorted = nullptr; uint8_t* d_flag = nullptr; int32_t* d_inl_idx = nullptr;
+    DevBuf d_e_sorted, d_flag, d_inl_idx;
     size_t n_outside_tile = 0; int n_rebin = 0; uint32_t last_rebin_stamp = 0;   // tile order: inliers found outside their tile in the last evaluation; how often the window was re-binned
     bool inl_idx_valid = false;   // the per-event inlier numbers are produced on demand (dumps, caller-supplied ep): 4 B/event the step does not write
     bool ep_valid = false;        // d_ep holds the current evaluation's residuals in the reference's order (the resident step's Gram launch compacts them in its tail blocks)
@@ -166,9 +189,9 @@ struct emba_ctx {
     int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
     bool step_wants_ep = false;   // set by emba_step around its emba_form_active
     const uint8_t* global_u8 = nullptr;   // set by emba_step_form_active around its emba_form_active: the all-reduced saturated byte counts activity is decided from
-    uint32_t* d_fblk_cnt = nullptr; uint32_t* d_fblk_off = nullptr; long n_fblk = 0;   // inlier-flag counts per kFlagBlk pm-order entries
-    uint32_t* d_fsup = nullptr; long n_fsup = 0; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (two arrays used alternately; fsup_half: the one the last launch A filled)
-    double* d_ep = nullptr;
+    DevBuf d_fblk_cnt, d_fblk_off; long n_fblk = 0;   // inlier-flag counts per kFlagBlk pm-order entries
+    DevBuf d_fsup; long n_fsup = 0; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (two arrays used alternately; fsup_half: the one the last launch A filled)
+    DevBuf d_ep;
     // order / key cache
     bool keys_ready = false; int64_t key_t0 = 0, key_dt = 0; int key_K = 0;
     double set_events_ms = 0, prepare_ms = 0;   // wall time of the last emba_set_events[_dev] / order preparation (diagnostics)
@@ -194,22 +217,49 @@ struct emba_ctx {
     bool kt_valid[16][3]{};
     bool kt_all = false;        // emba_kernel_timing_all: also record [4], so that the four intervals [4]->[0]->[1]->[2]->[3] tile the whole step (prep | warp | post-warp | Gram)
     hipEvent_t cal_ev[2]{};     // emba_bracket_overhead_us / emba_clock_probe
-    unsigned long long* d_probe = nullptr;
+    DevBuf d_probe;
     bool kt_warp_valid = false, kt_accum_valid = false;
     int n_cu = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     int ablate = 0;  // diagnostics builds only (-DEMBA_DIAG): EMBA_ABLATE bit mask; always 0 in the shipped library
     bool finish_done = false;   // emba_form_finish ran (L2 applied): the state emba_solve_normal_eq works on
     int solve_info = 0;         // last Schur solve: bit 0 a 2x2 block not positive definite (error), bit 1 a pivot of S vanished (zero update, like Eigen's ldlt)
-    // grow-only workspaces of the Schur solve (an LM loop calls it every iteration)
-    struct { void* p = nullptr; size_t bytes = 0; } ws[44];   // 0-15 and 32-39 Schur solve, 16-31 sort / order preparation, 42 pixel starts of ep, 43 unpacked A22 | b2 of a download
+    // ---- grow-only scratch, by phase.  A buffer named for two roles serves both (no phase holds it while the other runs): sharing keeps the peak down.
+    struct {   // once-per-window order preparation (set_events_core, prepare_order) and the device scan / sort
+        DevBuf scan_sums, scan_offs;   // dev_scan
+        DevBuf sort_hist;              // dev_sort
+        DevBuf status;                 // 64 B of status words: set_events_core, prepare_order
+        DevBuf keys[2], vals[2];       // radix-sort pairs: set_events_core (pm-order), prepare_order (tile order, record slots)
+        DevBuf flags;                  // set_events_core: candidate flags; prepare_order: chain-head flags, the tile binning's emit flags, candidate flags
+        DevBuf pos;                    // set_events_core: candidate positions; prepare_order: head / emit positions, candidate positions
+        DevBuf bin, used;              // prepare_order: tile of every entry, occupied bins
+        DevBuf bin_start_or_x;         // prepare_order: first entry of every tile; emba_set_events: upload of x
+        DevBuf pred_or_y;              // prepare_order: predicted pixels; emba_set_events: upload of y
+        DevBuf heads_or_pol;           // prepare_order: chain heads; emba_set_events: upload of the polarities
+        DevBuf halo;                   // emba_set_events: upload of the halo (times, x, y)
+    } ord;
+    struct Solve {   // the solvers (an LM loop solves every iteration).  Schur: emba_solve_normal_eq, emba_solve_shard_*; CG: emba_solve_normal_eq_cg, emba_cg_shard_*
+        DevBuf S_or_x, rhs_or_r, U_or_p, y_or_z, cf_or_t, x2_or_invd;   // Schur: S_aug, x1, U block, y, 2x2 factors, x2; CG: x, r, p, z, t, inverse diagonal
+        DevBuf info_or_sc;             // Schur: status word; CG: device scalars
+        DevBuf slab, mask, list, cnt, range, pair_items, items;         // schur_accumulate: the block-sparse SYRK
+        DevBuf perm_cnt, perm_tick, perm;   // solve_perm (perm: the column order, valid with perm_valid)
+        DevBuf shard_cnt;              // emba_solve_shard_count -> emba_solve_shard_pack: counts, offsets, cursors per rank
+    } sv;
+    struct {   // build_lists.  off / sorted are the lists cache (lists_valid) that a re-solve, emba_solve_shard_cached / _finish and a CG session read
+        DevBuf off, cursor, sorted, tmp;
+    } lists;
+    struct {   // downloads
+        DevBuf out;          // emba_get_map_active, emba_get_inlier_pixels, the pixel list of emba_get_inlier_pixel_starts
+        DevBuf pix_starts;   // emba_get_inlier_pixel_starts
+        DevBuf A22b2;        // emba_form_finish: unpacked A22 | b2
+    } dl;
     // f3 (Poisson reconstruction): sine matrices and eigenvalues of the two transform lengths, scratch planes
-    double *d_SH = nullptr, *d_SW = nullptr, *d_lamH = nullptr, *d_lamW = nullptr, *d_pF = nullptr, *d_pT = nullptr, *d_pGx = nullptr, *d_pGy = nullptr;
-    double* d_thomas = nullptr;   // Thomas factors of T_W + lambda1[i] I (W x H)
-    double* d_Sfold = nullptr;    // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
-    double* d_pE = nullptr;       // [E | O] of the folded transform (W x H/2 each)
+    DevBuf d_SH, d_SW, d_lamH, d_lamW, d_pF, d_pT, d_pGx, d_pGy;
+    DevBuf d_thomas;              // Thomas factors of T_W + lambda1[i] I (W x H)
+    DevBuf d_Sfold;               // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
+    DevBuf d_pE;                  // [E | O] of the folded transform (W x H/2 each)
     // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload
-    emba::RenderState* d_rstate = nullptr; unsigned int* d_rhist = nullptr; unsigned long long* d_rcand = nullptr;
-    uint8_t* d_img = nullptr; double* d_nsrc = nullptr;
+    DevBuf d_rstate, d_rhist, d_rcand;
+    DevBuf d_img, d_nsrc;
 };
 
 namespace {
@@ -233,49 +283,23 @@ emba_status fail(emba_ctx* c, emba_status st, const char* fmt, ...)
                         __FILE__, __LINE__);                                                     \
     } while (0)
 
-// Grow-only device buffers: a buffer is re-allocated only when it has to grow, so that registering the next window of a sliding-window
-// run (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around
-// 10 ms of kernels).  `fresh` tells the caller that the memory is new (uninitialised).
+// a grow-only buffer of the context (DevBuf) holds at least `count` elements of T.  Option poison (tests): new memory reads as NaN / 0xFFFFFFFF, so that a
+// read of never-written memory shows.
 template <typename T>
-emba_status dev_alloc(emba_ctx* c, T** p, size_t count, bool* fresh = nullptr)
+emba_status ensure(emba_ctx* c, DevBuf& b, size_t count, bool* fresh = nullptr)
 {
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    void** key = reinterpret_cast<void**>(p);
-    auto it = c->caps.find(key);
-    if (*p && it != c->caps.end() && it->second >= bytes) { if (fresh) *fresh = false; return EMBA_OK; }
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    c->caps.erase(key);
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(p), bytes));
-    if (c->opt_poison) HIP_TRY(c, hipMemsetAsync(*p, 0xFF, bytes, c->stream));
-    c->caps[key] = bytes;
-    if (fresh) *fresh = true;
+    const hipError_t e = b.ensure(count * sizeof(T), fresh, c->opt_poison != 0, c->stream);
+    if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
     return EMBA_OK;
 }
 
-template <typename T>
-void dev_free(emba_ctx* c, T*& p)
-{
-    if (p) (void)hipFree(p);
-    if (c) c->caps.erase(reinterpret_cast<void**>(&p));
-    p = nullptr;
-}
-
 void free_window(emba_ctx* c)
-{   // (the buffers stay: the next window reuses them, see dev_alloc)
+{   // (the buffers stay: the next window reuses them, see DevBuf)
     c->d_ev_pix = nullptr; c->d_ev_batch = nullptr;
     c->have_events = false; c->keys_ready = false; c->tile_order = false; c->have_ev_pm = false; c->n_chunks = 0; c->n_lead = 0; c->P_prev = 0;
     c->eval_launched = c->eval_done = c->active_done = c->accum_done = false;
     // (counters of the previous window that were never resolved must not be read as this window's)
     c->inl_pending = c->P_pending = false; c->ep_deferred = false; c->ep_valid = false; c->inl_idx_valid = false; c->seq_armed = false;
-}
-
-void free_all_buffers(emba_ctx* c)
-{
-    std::vector<void**> keys;
-    for (auto& kv : c->caps) keys.push_back(kv.first);
-    for (void** k : keys) { if (*k) (void)hipFree(*k); *k = nullptr; }
-    c->caps.clear();
 }
 
 // ros::Time/Duration midpoint of a batch (model.cpp:116-119; rostime semantics per SURVEY Appendix A):
@@ -294,36 +318,17 @@ int64_t batch_mid_ns(int64_t t_first, int64_t t_last)
 }
 
 // ---- device-side helpers of the once-per-window structure (order_kernels.h) ----------------------------------------------------
-emba_status ws_get(emba_ctx* c, int slot, size_t bytes, void** out)
-{
-    auto& w = c->ws[slot];
-    if (w.bytes < bytes || !w.p) {
-        if (w.p) (void)hipFree(w.p);
-        w.p = nullptr; w.bytes = 0;
-        if (hipMalloc(&w.p, std::max<size_t>(bytes, 8)) != hipSuccess) return fail(c, EMBA_ERR_HIP, "hipMalloc of %zu bytes failed (workspace %d)", bytes, slot);
-        w.bytes = std::max<size_t>(bytes, 8);
-        if (c->opt_poison) { (void)hipMemsetAsync(w.p, 0xFF, w.bytes, c->stream); }      // option poison (tests): new memory reads as NaN / 0xFFFFFFFF, so that a read of never-written workspace shows
-    }
-    *out = w.p;
-    return EMBA_OK;
-}
-
-void ws_release(emba_ctx* c, int first, int last)
-{
-    for (int i = first; i <= last; ++i) { if (c->ws[i].p) (void)hipFree(c->ws[i].p); c->ws[i].p = nullptr; c->ws[i].bytes = 0; }
-}
-
 inline unsigned nblocks(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>((n + per - 1) / per, 1); }
 
-// out[i] = sum_{j<i} in[j]; total_dev[0] = sum of all (may be nullptr).  Workspaces 16, 17.
+// out[i] = sum_{j<i} in[j]; total_dev[0] = sum of all (may be nullptr).  Scratch: ord.scan_sums, ord.scan_offs.
 emba_status dev_scan(emba_ctx* c, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total_dev, int* total_host = nullptr, const int* err_dev = nullptr, int* err_host = nullptr)
 {   // (total_host / err_host: pinned, device-visible words the middle launch writes the total and the evaluation's status word to — no copy node)
     hipStream_t s = c->stream;
     const size_t ntiles = (n + kScanTile - 1) / kScanTile;
-    uint32_t *sums = nullptr, *offs = nullptr, *tot = nullptr;
     emba_status st;
-    if ((st = ws_get(c, 16, (ntiles + 1) * 4, (void**)&sums)) || (st = ws_get(c, 17, (ntiles + 2) * 4, (void**)&offs))) return st;
-    tot = total_dev ? total_dev : offs + ntiles + 1;
+    if ((st = ensure<uint32_t>(c, c->ord.scan_sums, ntiles + 1)) || (st = ensure<uint32_t>(c, c->ord.scan_offs, ntiles + 2))) return st;
+    uint32_t *sums = c->ord.scan_sums.as<uint32_t>(), *offs = c->ord.scan_offs.as<uint32_t>();
+    uint32_t* tot = total_dev ? total_dev : offs + ntiles + 1;
     if (!n) { HIP_TRY(c, hipMemsetAsync(tot, 0, 4, s)); return EMBA_OK; }
     hipLaunchKernelGGL(emba_scan_tile_sums_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, in, (long)n, sums);
     hipLaunchKernelGGL(emba_scan_kernel, dim3(1), dim3(256), 0, s, sums, offs, (long)ntiles, tot, total_host, err_dev, err_host);
@@ -333,15 +338,15 @@ emba_status dev_scan(emba_ctx* c, const uint32_t* in, uint32_t* out, size_t n, u
 }
 
 // Stable LSD radix sort of (keys, vals) on the low `bits` bits of the keys; the sorted arrays end up in (*keys, *vals), the other
-// pair of buffers is scratch (pointers are swapped per pass).  Workspace 18 (+ 16, 17 through dev_scan).
+// pair of buffers is scratch (pointers are swapped per pass).  Scratch: ord.sort_hist (+ dev_scan's).
 emba_status dev_sort(emba_ctx* c, uint32_t** keys, uint32_t** vals, uint32_t** keys_alt, uint32_t** vals_alt, size_t n, int bits)
 {
     if (n < 2 || bits <= 0) return EMBA_OK;
     hipStream_t s = c->stream;
     const size_t ntiles = (n + kSortTile - 1) / kSortTile;
-    uint32_t* hist = nullptr;
     emba_status st;
-    if ((st = ws_get(c, 18, 256 * ntiles * 4, (void**)&hist))) return st;
+    if ((st = ensure<uint32_t>(c, c->ord.sort_hist, 256 * ntiles))) return st;
+    uint32_t* hist = c->ord.sort_hist.as<uint32_t>();
     for (int shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(emba_sort_hist_kernel, dim3(nblocks(ntiles, 4)), dim3(256), 0, s, *keys, (long)n, shift, (long)ntiles, hist);
         if ((st = dev_scan(c, hist, hist, 256 * ntiles, nullptr))) return st;
@@ -349,6 +354,15 @@ emba_status dev_sort(emba_ctx* c, uint32_t** keys, uint32_t** vals, uint32_t** k
         std::swap(*keys, *keys_alt); std::swap(*vals, *vals_alt);
     }
     HIP_TRY(c, hipGetLastError());
+    return EMBA_OK;
+}
+
+// the two (keys, values) pairs of a sort of n entries
+emba_status ensure_sort_pairs(emba_ctx* c, size_t n)
+{
+    emba_status st;
+    for (int i = 0; i < 2; ++i)
+        if ((st = ensure<uint32_t>(c, c->ord.keys[i], n)) || (st = ensure<uint32_t>(c, c->ord.vals[i], n))) return st;
     return EMBA_OK;
 }
 
@@ -371,17 +385,17 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     c->order_per_px = 0.0; c->order_lead_frac = 0.0; c->order_inl_pred = 0.0;
 
     // control-pose index per batch; a batch outside the knots is an error (BASALT_ASSERT_STREAM at so3_spline.h:221-229)
-    uint32_t* d_err = nullptr;
-    if ((st = ws_get(c, 19, 64, (void**)&d_err))) return st;
+    if ((st = ensure<uint32_t>(c, c->ord.status, 16))) return st;
+    uint32_t* d_err = c->ord.status.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
-    if ((st = dev_alloc(c, &c->d_cp, nbatch)) || (st = dev_alloc(c, &c->d_batch_u, nbatch))) return st;
-    if (nbatch) hipLaunchKernelGGL(emba_batch_cp_kernel, dim3(nblocks(nbatch)), dim3(256), 0, s, c->d_batch_t, (long)nbatch, t0, dt, K, c->d_cp, c->d_batch_u, d_err);
+    if ((st = ensure<uint16_t>(c, c->d_cp, nbatch)) || (st = ensure<double>(c, c->d_batch_u, nbatch))) return st;
+    if (nbatch) hipLaunchKernelGGL(emba_batch_cp_kernel, dim3(nblocks(nbatch)), dim3(256), 0, s, c->d_batch_t.as<int64_t>(), (long)nbatch, t0, dt, K, c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), d_err);
     uint32_t h_err[16];
     HIP_TRY(c, hipMemcpyAsync(h_err, d_err, 64, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h_err[0] != 0xFFFFFFFFu) {
         int64_t tb = 0;
-        (void)hipMemcpy(&tb, c->d_batch_t + h_err[0], 8, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&tb, c->d_batch_t.as<int64_t>() + h_err[0], 8, hipMemcpyDeviceToHost);
         return fail(c, EMBA_ERR_TIME_RANGE, "batch %u midpoint %lld ns outside spline [%lld, %lld) (K=%d)", h_err[0], (long long)tb, (long long)t0,
                     (long long)(t0 + dt * (K - 1)), K);
     }
@@ -398,19 +412,19 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     // (auto on a window below tile_min_events never takes the tile order: nothing to analyse — 1.2 -> 0.3 ms of a 1 M-event window's first evaluation)
     if (c->order_mode != 1 && ns && knots_host && (c->order_mode == 2 || c->n_used >= (size_t)c->opt_tile_min_events)) {
         const size_t max_bins = (size_t)((c->W + 7) / 8) * ((c->H + 1) / 2) + 1;      // (the finest pitch any candidate uses is 8 x 2)
-        if ((st = ws_get(c, 20, ns * 4, (void**)&d_bin)) || (st = ws_get(c, 21, ns * 4, (void**)&d_emit)) || (st = ws_get(c, 22, ns * 4, (void**)&d_pos)) ||
-            (st = ws_get(c, 23, max_bins + 8, (void**)&d_used)) || (st = ws_get(c, 29, ns * 4, (void**)&d_pred)))
+        if ((st = ensure<uint32_t>(c, c->ord.bin, ns)) || (st = ensure<uint32_t>(c, c->ord.flags, ns)) || (st = ensure<uint32_t>(c, c->ord.pos, ns)) ||
+            (st = ensure<uint8_t>(c, c->ord.used, max_bins + 8)) || (st = ensure<uint32_t>(c, c->ord.pred_or_y, ns)) || (st = ensure<uint32_t>(c, c->ord.heads_or_pol, ns)))
             return st;
+        d_bin = c->ord.bin.as<uint32_t>(); d_emit = c->ord.flags.as<uint32_t>(); d_pos = c->ord.pos.as<uint32_t>(); d_used = c->ord.used.as<uint8_t>(); d_pred = c->ord.pred_or_y.as<uint32_t>();
         d_breaks = reinterpret_cast<unsigned long long*>(d_err + 8);
         // the poses the caller starts from (staged through the pinned buffer like every evaluation's)
-        HIP_TRY(c, hipMemcpyAsync(c->d_knots, knots_host, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(emba_pose_kernel, dim3(nblocks(nbatch, 64)), dim3(64), 0, s, c->d_batch_t, (int)nbatch, c->d_knots, K, t0, dt, c->d_pose, c->d_err);
-        hipLaunchKernelGGL(emba_predict_pixel_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix, c->d_pm_batch, (long)ns, c->d_pose, kPoseStride, c->d_lut,
+        HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), knots_host, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(emba_pose_kernel, dim3(nblocks(nbatch, 64)), dim3(64), 0, s, c->d_batch_t.as<int64_t>(), (int)nbatch, c->d_knots.as<double>(), K, t0, dt, c->d_pose.as<double>(), c->d_err);
+        hipLaunchKernelGGL(emba_predict_pixel_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_pose.as<double>(), kPoseStride, c->d_lut.as<double>(),
                            c->fx, c->fy, c->cx, c->cy, c->W, c->H, d_pred);
         // the chains of the pm-order: heads -> list (one wave of the assignment kernel per chain)
-        uint32_t *d_hflag = d_emit, *d_hpos = d_pos, *d_heads = nullptr, *d_nheads = d_err + 6;
-        if ((st = ws_get(c, 30, ns * 4, (void**)&d_heads))) return st;
-        hipLaunchKernelGGL(emba_head_flag_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix, (long)ns, d_hflag);
+        uint32_t *d_hflag = d_emit, *d_hpos = d_pos, *d_heads = c->ord.heads_or_pol.as<uint32_t>(), *d_nheads = d_err + 6;
+        hipLaunchKernelGGL(emba_head_flag_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), (long)ns, d_hflag);
         if ((st = dev_scan(c, d_hflag, d_hpos, ns, d_nheads))) return st;
         hipLaunchKernelGGL(emba_head_list_kernel, dim3(nblocks(ns)), dim3(256), 0, s, d_hflag, d_hpos, (long)ns, d_heads);
         uint32_t h_nheads = 0;
@@ -420,7 +434,7 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
         double f_pred = 1.0;
         {
             HIP_TRY(c, hipMemsetAsync(d_breaks, 0, 8, s));
-            hipLaunchKernelGGL(emba_count_pred_inliers_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, c->d_pm_pix, d_pred, (long)ns, c->outlier_px, d_breaks);
+            hipLaunchKernelGGL(emba_count_pred_inliers_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_pred, (long)ns, c->outlier_px, d_breaks);
             unsigned long long hi = 0;
             HIP_TRY(c, hipMemcpyAsync(&hi, d_breaks, 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
@@ -444,8 +458,8 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
             const size_t nb_ = (size_t)q.nbx * q.nby + 1;
             HIP_TRY(c, hipMemsetAsync(d_used, 0, nb_, s));
             HIP_TRY(c, hipMemsetAsync(d_breaks, 0, 8, s));
-            hipLaunchKernelGGL(emba_assign_tiles_kernel, dim3((unsigned)((n_heads + 3) / 4)), dim3(256), 0, s, c->d_pm_pix, d_pred, d_heads, n_heads, (long)ns, q, d_bin, d_used);
-            hipLaunchKernelGGL(emba_expand_count_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix, d_bin, (long)ns, d_emit);
+            hipLaunchKernelGGL(emba_assign_tiles_kernel, dim3((unsigned)((n_heads + 3) / 4)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_pred, d_heads, n_heads, (long)ns, q, d_bin, d_used);
+            hipLaunchKernelGGL(emba_expand_count_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_bin, (long)ns, d_emit);
             hipLaunchKernelGGL(emba_count_breaks_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, d_emit, (long)ns, d_breaks);
             unsigned long long hb = 0;
             HIP_TRY(c, hipMemcpyAsync(h_used.data(), d_used, nb_, hipMemcpyDeviceToHost, s));
@@ -515,11 +529,11 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     }
 
     if (!tile) {
-        c->d_ev_pix = c->d_pm_pix; c->d_ev_batch = c->d_pm_batch;
+        c->d_ev_pix = c->d_pm_pix.as<uint32_t>(); c->d_ev_batch = c->d_pm_batch.as<uint32_t>();
         c->n_sorted = ns;
         // per entry the spline parameter and segment of its batch (the warp kernel's per-event pose: 10 B per entry, streamed with the event words)
-        if ((st = dev_alloc(c, &c->d_ev_u, std::max<size_t>(ns, 1))) || (st = dev_alloc(c, &c->d_ev_seg, std::max<size_t>(ns, 1)))) return st;
-        if (ns) hipLaunchKernelGGL(emba_entry_pose_args_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_batch, (long)ns, c->d_cp, c->d_batch_u, c->d_ev_seg, c->d_ev_u);
+        if ((st = ensure<double>(c, c->d_ev_u, std::max<size_t>(ns, 1))) || (st = ensure<uint16_t>(c, c->d_ev_seg, std::max<size_t>(ns, 1)))) return st;
+        if (ns) hipLaunchKernelGGL(emba_entry_pose_args_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>());
     } else {
         // expanded list: every event, plus a lead-in copy of its predecessor where its chain enters a tile -> stable sort by tile
         uint32_t* d_tot = d_err + 4;
@@ -528,21 +542,20 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
         HIP_TRY(c, hipMemcpyAsync(&nd32, d_tot, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         const size_t nd = nd32;
-        uint32_t *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr, *d_bin_start = nullptr;
-        if ((st = ws_get(c, 24, nd * 4, (void**)&k0)) || (st = ws_get(c, 25, nd * 4, (void**)&v0)) || (st = ws_get(c, 26, nd * 4, (void**)&k1)) ||
-            (st = ws_get(c, 27, nd * 4, (void**)&v1)) || (st = ws_get(c, 28, (nbins + 1) * 4, (void**)&d_bin_start)))
-            return st;
-        hipLaunchKernelGGL(emba_expand_write_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix, d_bin, d_emit, d_pos, (long)ns, k0, v0);
+        if ((st = ensure_sort_pairs(c, nd)) || (st = ensure<uint32_t>(c, c->ord.bin_start_or_x, nbins + 1))) return st;
+        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+        uint32_t* d_bin_start = c->ord.bin_start_or_x.as<uint32_t>();
+        hipLaunchKernelGGL(emba_expand_write_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_bin, d_emit, d_pos, (long)ns, k0, v0);
         if ((st = dev_sort(c, &k0, &v0, &k1, &v1, nd, bits_for(nbins)))) return st;
-        if ((st = dev_alloc(c, &c->d_ev_pix_own, nd)) || (st = dev_alloc(c, &c->d_ev_batch_own, nd)) || (st = dev_alloc(c, &c->d_ev_pm, nd)) ||
-            (st = dev_alloc(c, &c->d_ev_u, nd)) || (st = dev_alloc(c, &c->d_ev_seg, nd)))
+        if ((st = ensure<uint32_t>(c, c->d_ev_pix_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_batch_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_pm, nd)) ||
+            (st = ensure<double>(c, c->d_ev_u, nd)) || (st = ensure<uint16_t>(c, c->d_ev_seg, nd)))
             return st;
-        c->d_ev_pix = c->d_ev_pix_own; c->d_ev_batch = c->d_ev_batch_own; c->have_ev_pm = true;
+        c->d_ev_pix = c->d_ev_pix_own.as<uint32_t>(); c->d_ev_batch = c->d_ev_batch_own.as<uint32_t>(); c->have_ev_pm = true;
         HIP_TRY(c, hipMemsetAsync(d_bin_start, 0xFF, (nbins + 1) * 4, s));
         uint32_t* d_cf = d_emit;    // (emit is dead: its buffer now takes the candidate flags of the device order — nd <= 2 ns may exceed it)
-        if (nd > ns && (st = ws_get(c, 21, nd * 4, (void**)&d_cf))) return st;
-        hipLaunchKernelGGL(emba_dev_gather_kernel, dim3(nblocks(nd)), dim3(256), 0, s, k0, v0, (long)nd, c->d_pm_pix, c->d_pm_batch, c->d_ev_pix, c->d_ev_batch,
-                           c->d_ev_pm, c->d_cp, c->d_batch_u, c->d_ev_seg, c->d_ev_u, d_cf, d_bin_start);
+        if (nd > ns) { if ((st = ensure<uint32_t>(c, c->ord.flags, nd))) return st; d_cf = c->ord.flags.as<uint32_t>(); }
+        hipLaunchKernelGGL(emba_dev_gather_kernel, dim3(nblocks(nd)), dim3(256), 0, s, k0, v0, (long)nd, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), c->d_ev_pix, c->d_ev_batch,
+                           c->d_ev_pm.as<uint32_t>(), c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>(), d_cf, d_bin_start);
         // chunks: every occupied tile is cut into workgroup-sized pieces (host: <= 32 k tiles)
         std::vector<uint32_t> h_start(nbins + 1);
         HIP_TRY(c, hipMemcpyAsync(h_start.data(), d_bin_start, (nbins + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -581,8 +594,8 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
         if (c->chunks_lpt) std::stable_sort(h_chunks.begin(), h_chunks.end(), [](const ChunkDesc& a, const ChunkDesc& b) { return a.end - a.begin > b.end - b.begin; });
         }
         c->n_chunks = (long)h_chunks.size();
-        if ((st = dev_alloc(c, &c->d_chunks, h_chunks.size()))) return st;
-        HIP_TRY(c, hipMemcpyAsync(c->d_chunks, h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, s));
+        if ((st = ensure<ChunkDesc>(c, c->d_chunks, h_chunks.size()))) return st;
+        HIP_TRY(c, hipMemcpyAsync(c->d_chunks.as<ChunkDesc>(), h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         c->n_sorted = nd; c->n_lead = nd - c->n_used; c->tile_order = true;
         d_emit = d_cf;
@@ -593,20 +606,19 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     // record slots sorted by control-pose pair: candidates of the device order -> (key, entry) -> stable sort -> slot
     {
         const size_t M = c->n_cand;
-        uint32_t *d_cf = nullptr, *d_cpos = nullptr, *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr;
-        if ((st = ws_get(c, 22, std::max<size_t>(nd, 1) * 4, (void**)&d_cpos))) return st;
-        if (tile) d_cf = d_emit;
-        else {
-            if ((st = ws_get(c, 21, std::max<size_t>(nd, 1) * 4, (void**)&d_cf))) return st;
+        if ((st = ensure<uint32_t>(c, c->ord.pos, std::max<size_t>(nd, 1)))) return st;
+        uint32_t *d_cf = d_emit, *d_cpos = c->ord.pos.as<uint32_t>();
+        if (!tile) {
+            if ((st = ensure<uint32_t>(c, c->ord.flags, std::max<size_t>(nd, 1)))) return st;
+            d_cf = c->ord.flags.as<uint32_t>();
             if (nd) hipLaunchKernelGGL(emba_cand_flag_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->d_ev_pix, (long)nd, d_cf);
         }
         if ((st = dev_scan(c, d_cf, d_cpos, nd, nullptr))) return st;
-        if ((st = ws_get(c, 24, std::max<size_t>(M, 1) * 4, (void**)&k0)) || (st = ws_get(c, 25, std::max<size_t>(M, 1) * 4, (void**)&v0)) ||
-            (st = ws_get(c, 26, std::max<size_t>(M, 1) * 4, (void**)&k1)) || (st = ws_get(c, 27, std::max<size_t>(M, 1) * 4, (void**)&v1)))
-            return st;
-        if ((st = dev_alloc(c, &c->d_ev_slot, nd))) return st;
-        HIP_TRY(c, hipMemsetAsync(c->d_ev_slot, 0xFF, std::max<size_t>(nd, 1) * 4, s));
-        if (nd) hipLaunchKernelGGL(emba_cand_keys_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->d_ev_pix, c->d_ev_batch, c->d_cp, (long)nd, d_cpos, k0, v0);
+        if ((st = ensure_sort_pairs(c, std::max<size_t>(M, 1)))) return st;
+        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+        if ((st = ensure<uint32_t>(c, c->d_ev_slot, nd))) return st;
+        HIP_TRY(c, hipMemsetAsync(c->d_ev_slot.as<uint32_t>(), 0xFF, std::max<size_t>(nd, 1) * 4, s));
+        if (nd) hipLaunchKernelGGL(emba_cand_keys_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->d_ev_pix, c->d_ev_batch, c->d_cp.as<uint16_t>(), (long)nd, d_cpos, k0, v0);
         // the key's low half is cp_p, the high half cp_c, both < K: sort on the bits they really use
         const int kb = bits_for((size_t)K);
         if (kb <= 8) {   // fold the two halves into one 16-bit key for the sort (two passes instead of four)
@@ -614,12 +626,12 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
             if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 16))) return st;
             if (M) hipLaunchKernelGGL(emba_fold_keys_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, (long)M, 0);
         } else if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 32))) return st;
-        if (M) hipLaunchKernelGGL(emba_slot_assign_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, v0, (long)M, c->d_ev_slot, c->d_slot_key);
+        if (M) hipLaunchKernelGGL(emba_slot_assign_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, v0, (long)M, c->d_ev_slot.as<uint32_t>(), c->d_slot_key.as<uint32_t>());
     }
     // per-entry outputs of the evaluations
     // per-event outputs of the evaluations, indexed in pm-order in both orders
-    if ((st = dev_alloc(c, &c->d_e_sorted, ns)) || (st = dev_alloc(c, &c->d_flag, ns)) || (st = dev_alloc(c, &c->d_inl_idx, ns))) return st;
-    HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, std::max<size_t>(ns, 1), s));
+    if ((st = ensure<double>(c, c->d_e_sorted, ns)) || (st = ensure<uint8_t>(c, c->d_flag, ns)) || (st = ensure<int32_t>(c, c->d_inl_idx, ns))) return st;
+    HIP_TRY(c, hipMemsetAsync(c->d_flag.as<uint8_t>(), 0, std::max<size_t>(ns, 1), s));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
     c->keys_ready = true; c->key_t0 = t0; c->key_dt = dt; c->key_K = K;
@@ -639,14 +651,10 @@ emba_status ensure_pack(emba_ctx* c, int K)
             return fail(c, EMBA_ERR_CAPACITY, "bound pack buffer too small for K=%d", K);
         return EMBA_OK;
     }
-    if (c->pack_own_cap < need) {
-        dev_free(c, c->d_pack_own);
-        emba_status st = dev_alloc(c, &c->d_pack_own, need);
-        if (st) return st;
-        c->pack_own_cap = need;
-    }
-    c->d_pack = c->d_pack_own;
-    c->pack_cap = c->pack_own_cap;
+    emba_status st = ensure<double>(c, c->d_pack_own, need);
+    if (st) return st;
+    c->d_pack = c->d_pack_own.as<double>();
+    c->pack_cap = c->d_pack_own.bytes / sizeof(double);
     return EMBA_OK;
 }
 
@@ -662,10 +670,10 @@ emba_status ensure_compact(emba_ctx* c)
 {
     if (c->compact_valid) return EMBA_OK;
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_compact, 0xFF, c->npix * sizeof(int32_t), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_compact.as<int32_t>(), 0xFF, c->npix * sizeof(int32_t), s));
     const size_t bound = c->P_pending ? c->npix : c->P;
     if (bound)
-        hipLaunchKernelGGL(emba_compact_map_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, c->d_active, c->d_total + 1, c->d_compact);
+        hipLaunchKernelGGL(emba_compact_map_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_total.as<uint32_t>() + 1, c->d_compact.as<int32_t>());
     HIP_TRY(c, hipGetLastError());
     c->compact_valid = true;
     return EMBA_OK;
@@ -678,8 +686,8 @@ emba_status ensure_counts(emba_ctx* c)
 {
     if (!c->counts_raw) return EMBA_OK;
     c->counts_raw = false;
-    c->count_stamp = (c->d_count == c->d_count_own) ? c->set_stamp : 0u;
-    hipLaunchKernelGGL(emba_count_materialise_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc, (long)c->npix, c->count_mark);
+    c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
+    hipLaunchKernelGGL(emba_count_materialise_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix, c->count_mark);
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
 }
@@ -693,16 +701,16 @@ emba_status launch_ep_compaction(emba_ctx* c)
     hipStream_t s = c->stream;
     if (c->n_pm) {
         const uint32_t* perm = nullptr;    // (flags and residuals are stored in pm-order by both warp kernels)
-        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_flag, perm, (long)c->n_pm, c->d_fblk_cnt);
+        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_flag.as<uint8_t>(), perm, (long)c->n_pm, c->d_fblk_cnt.as<uint32_t>());
         // (round 6: the block counts by the three-launch scan — one 256-thread block walked all of them before: 101 us for 97 k counts at 100 M events)
-        { emba_status st = dev_scan(c, c->d_fblk_cnt, c->d_fblk_off, (size_t)c->n_fblk, c->d_total, c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted, c->d_flag, perm, c->d_fblk_off,
-                           (long)c->n_pm, c->d_ep, c->d_inl_idx);
+        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
+        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
+                           (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
         c->inl_idx_valid = true; c->ep_valid = true;
         HIP_TRY(c, hipGetLastError());
     } else {
-        HIP_TRY(c, hipMemsetAsync(c->d_total, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[0], c->d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemsetAsync(c->d_total.as<uint32_t>(), 0, sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[0], c->d_total.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
     }
     c->inl_pending = true;
@@ -715,9 +723,9 @@ emba_status ensure_inl_idx(emba_ctx* c)
     { emba_status st = launch_ep_compaction(c); if (st) return st; }
     if (c->inl_idx_valid || !c->n_pm) return EMBA_OK;
     // (the fused step leaves the per-block inlier counts of this evaluation in d_fblk_cnt, not their prefix)
-    { emba_status st = dev_scan(c, c->d_fblk_cnt, c->d_fblk_off, (size_t)c->n_fblk, c->d_total); if (st) return st; }
-    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, c->stream, c->d_e_sorted, c->d_flag, (const uint32_t*)nullptr, c->d_fblk_off,
-                       (long)c->n_pm, c->d_ep, c->d_inl_idx);   // (ep is rewritten with the same values)
+    { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>()); if (st) return st; }
+    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
+                       (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
     HIP_TRY(c, hipGetLastError());
     c->inl_idx_valid = true; c->ep_valid = true;
     return EMBA_OK;
@@ -948,8 +956,8 @@ emba_status emba_create(const emba_cfg* cfg, emba_ctx** out)
     CREATE_TRY(hipSetDevice(c->device));
     if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
     else { CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    CREATE_TRY(hipMalloc((void**)&c->d_lut, c->S * 3 * sizeof(double))); c->caps[reinterpret_cast<void**>(&c->d_lut)] = c->S * 3 * sizeof(double);
-    CREATE_TRY(hipMemcpy(c->d_lut, cfg->bearing_lut, c->S * 3 * sizeof(double), hipMemcpyHostToDevice));
+    CREATE_TRY(c->d_lut.ensure(c->S * 3 * sizeof(double)));
+    CREATE_TRY(hipMemcpy(c->d_lut.as<double>(), cfg->bearing_lut, c->S * 3 * sizeof(double), hipMemcpyHostToDevice));
     {   // the sensor's field of view from the bearing vectors (x / z, y / z extents): what schur_accumulate estimates the band of U with
         double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
         for (size_t i = 0; i < c->S; ++i) {
@@ -961,25 +969,25 @@ emba_status emba_create(const emba_cfg* cfg, emba_ctx** out)
         c->fov_x = x1 > x0 ? x1 - x0 : M_PI; c->fov_y = y1 > y0 ? y1 - y0 : M_PI;
     }
     c->cfg.bearing_lut = nullptr;  // not retained
-    CREATE_TRY(hipMalloc((void**)&c->d_texel, c->npix * kTexelStride * sizeof(double))); c->caps[reinterpret_cast<void**>(&c->d_texel)] = c->npix * kTexelStride * sizeof(double);
-    CREATE_TRY(hipMalloc((void**)&c->d_count_own, c->npix * sizeof(int32_t))); c->caps[reinterpret_cast<void**>(&c->d_count_own)] = c->npix * sizeof(int32_t);
-    c->d_count = c->d_count_own;
-    CREATE_TRY(hipMalloc((void**)&c->d_pixacc, c->npix * kPixAccStride * sizeof(double))); c->caps[reinterpret_cast<void**>(&c->d_pixacc)] = c->npix * kPixAccStride * sizeof(double);
-    CREATE_TRY(hipMalloc((void**)&c->d_compact, c->npix * sizeof(int32_t))); c->caps[reinterpret_cast<void**>(&c->d_compact)] = c->npix * sizeof(int32_t);
-    CREATE_TRY(hipMalloc((void**)&c->d_active_bits, (c->npix + 31) / 32 * 4 + 8)); c->caps[reinterpret_cast<void**>(&c->d_active_bits)] = (c->npix + 31) / 32 * 4 + 8;
-    CREATE_TRY(hipMalloc((void**)&c->d_active, c->npix * sizeof(uint32_t))); c->caps[reinterpret_cast<void**>(&c->d_active)] = c->npix * sizeof(uint32_t);
+    CREATE_TRY(c->d_texel.ensure(c->npix * kTexelStride * sizeof(double)));
+    CREATE_TRY(c->d_count_own.ensure(c->npix * sizeof(int32_t)));
+    c->d_count = c->d_count_own.as<int32_t>();
+    CREATE_TRY(c->d_pixacc.ensure(c->npix * kPixAccStride * sizeof(double)));
+    CREATE_TRY(c->d_compact.ensure(c->npix * sizeof(int32_t)));
+    CREATE_TRY(c->d_active_bits.ensure((c->npix + 31) / 32 * 4 + 8));
+    CREATE_TRY(c->d_active.ensure(c->npix * sizeof(uint32_t)));
     c->n_ablk = (c->npix + kActivePix - 1) / kActivePix;
-    CREATE_TRY(hipMalloc((void**)&c->d_seg_act, c->n_ablk * kActivePix * sizeof(uint16_t))); c->caps[reinterpret_cast<void**>(&c->d_seg_act)] = c->n_ablk * kActivePix * sizeof(uint16_t);
-    CREATE_TRY(hipMalloc((void**)&c->d_ablk_cnt, c->n_ablk * sizeof(uint32_t))); c->caps[reinterpret_cast<void**>(&c->d_ablk_cnt)] = c->n_ablk * sizeof(uint32_t);
-    CREATE_TRY(hipMalloc((void**)&c->d_ablk_off, c->n_ablk * sizeof(uint32_t))); c->caps[reinterpret_cast<void**>(&c->d_ablk_off)] = c->n_ablk * sizeof(uint32_t);
-    CREATE_TRY(hipMalloc((void**)&c->d_err2, 2 * sizeof(int))); c->caps[reinterpret_cast<void**>(&c->d_err2)] = 2 * sizeof(int);
-    CREATE_TRY(hipMemset(c->d_err2, 0, 2 * sizeof(int)));
-    c->d_err = c->d_err2;
-    CREATE_TRY(hipMalloc((void**)&c->d_rect, 4 * sizeof(int))); c->caps[reinterpret_cast<void**>(&c->d_rect)] = 4 * sizeof(int);
-    { const int init[4] = {0x7FFFFFFF, 0x7FFFFFFF, -1, -1}; CREATE_TRY(hipMemcpy(c->d_rect, init, sizeof init, hipMemcpyHostToDevice)); }
-    CREATE_TRY(hipMalloc((void**)&c->d_blk_rect, c->n_ablk * 4 * sizeof(int))); c->caps[reinterpret_cast<void**>(&c->d_blk_rect)] = c->n_ablk * 4 * sizeof(int);   // per active-count block: box of the touched pixels
-    CREATE_TRY(hipMalloc((void**)&c->d_total, 4 * sizeof(uint32_t))); c->caps[reinterpret_cast<void**>(&c->d_total)] = 4 * sizeof(uint32_t);   // [0] inliers [1] P [2] scratch total
-    CREATE_TRY(hipMalloc((void**)&c->d_scalar, 2 * sizeof(double))); c->caps[reinterpret_cast<void**>(&c->d_scalar)] = 2 * sizeof(double);
+    CREATE_TRY(c->d_seg_act.ensure(c->n_ablk * kActivePix * sizeof(uint16_t)));
+    CREATE_TRY(c->d_ablk_cnt.ensure(c->n_ablk * sizeof(uint32_t)));
+    CREATE_TRY(c->d_ablk_off.ensure(c->n_ablk * sizeof(uint32_t)));
+    CREATE_TRY(c->d_err2.ensure(2 * sizeof(int)));
+    CREATE_TRY(hipMemset(c->d_err2.as<int>(), 0, 2 * sizeof(int)));
+    c->d_err = c->d_err2.as<int>();
+    CREATE_TRY(c->d_rect.ensure(4 * sizeof(int)));
+    { const int init[4] = {0x7FFFFFFF, 0x7FFFFFFF, -1, -1}; CREATE_TRY(hipMemcpy(c->d_rect.as<int>(), init, sizeof init, hipMemcpyHostToDevice)); }
+    CREATE_TRY(c->d_blk_rect.ensure(c->n_ablk * 4 * sizeof(int)));   // per active-count block: box of the touched pixels
+    CREATE_TRY(c->d_total.ensure(4 * sizeof(uint32_t)));   // [0] inliers [1] P [2] scratch total
+    CREATE_TRY(c->d_scalar.ensure(2 * sizeof(double)));
     CREATE_TRY(hipHostMalloc((void**)&c->h_pinned, 64, hipHostMallocMapped));
     memset(c->h_pinned, 0, 64);
     CREATE_TRY(hipHostGetDevicePointer((void**)&c->h_pinned_dev, c->h_pinned, 0));
@@ -988,7 +996,7 @@ emba_status emba_create(const emba_cfg* cfg, emba_ctx** out)
     // pause inside bench.py's timed loop, once per process, at the first use of a new slot — the runtime growing its signal pool)
     for (int k = 0; k < 16; ++k) for (int i = 0; i < 5; ++i) CREATE_TRY(hipEventCreate(&c->kt_sets[k][i]));
     for (int i = 0; i < 2; ++i) CREATE_TRY(hipEventCreate(&c->cal_ev[i]));
-    CREATE_TRY(hipMalloc((void**)&c->d_probe, 8 * sizeof(unsigned long long))); c->caps[reinterpret_cast<void**>(&c->d_probe)] = 8 * sizeof(unsigned long long);
+    CREATE_TRY(c->d_probe.ensure(8 * sizeof(unsigned long long)));
     CREATE_TRY(hipEventCreateWithFlags(&c->knots_copied, hipEventDisableTiming));
     CREATE_TRY(hipDeviceSynchronize());      // (the memsets above ran on the default stream, which does not order the context's non-blocking stream behind it)
 #undef CREATE_TRY
@@ -1002,24 +1010,35 @@ void emba_destroy(emba_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_window(c);
-    free_all_buffers(c);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_cost) (void)hipHostFree(c->h_cost);
-    if (c->d_cost_acc) (void)hipFree(c->d_cost_acc);
     if (c->h_knots) (void)hipHostFree(c->h_knots);
     for (int k = 0; k < 2; ++k) { if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]); if (c->stage_ev[k]) (void)hipEventDestroy(c->stage_ev[k]); }
     if (c->knots_copied) (void)hipEventDestroy(c->knots_copied);
     for (int i = 0; i < 8; ++i) { if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]); if (c->ev_stop[i]) (void)hipEventDestroy(c->ev_stop[i]); }
     for (int k = 0; k < 16; ++k) for (int i = 0; i < 5; ++i) if (c->kt_sets[k][i]) (void)hipEventDestroy(c->kt_sets[k][i]);
     for (int i = 0; i < 2; ++i) if (c->cal_ev[i]) (void)hipEventDestroy(c->cal_ev[i]);
-    for (auto& w : c->ws) if (w.p) (void)hipFree(w.p);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    const hipStream_t own = c->own_stream ? c->stream : nullptr;
+    delete c;      // (its device buffers go with it: after the stream has drained, before the stream itself)
+    if (own) (void)hipStreamDestroy(own);
 }
 
 }  // extern "C"
 
 namespace {
+
+// A record set for n_cand candidates.  A record is valid iff it carries the current evaluation's stamp (record_valid): a reused buffer holds older
+// stamps only, new memory is cleared.
+emba_status size_record_set(emba_ctx* c, RecordSet& rs, size_t n_cand)
+{
+    bool rec_fresh = false, tag_fresh = false;
+    emba_status st;
+    if ((st = ensure<double>(c, rs.rec, (std::max<size_t>(n_cand, 1) + kGramPad) * kRecStride, &rec_fresh)) || (st = ensure<double>(c, rs.tag, n_cand + kGramPad, &tag_fresh)))
+        return st;
+    if (rec_fresh) HIP_TRY(c, hipMemsetAsync(rs.rec.p, 0, rs.rec.bytes, c->stream));
+    if (tag_fresh) HIP_TRY(c, hipMemsetAsync(rs.tag.p, 0, rs.tag.bytes, c->stream));
+    return EMBA_OK;
+}
 
 // Shared by emba_set_events (host arrays: uploaded first) and emba_set_events_dev (arrays already in HBM).  x, y, pol, hx, hy, hbt are
 // DEVICE pointers; t_dev (device) or batch_t_host (the nb midpoints, computed by the caller) supplies the times.
@@ -1035,26 +1054,26 @@ emba_status set_events_core(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
     const size_t ns = n_used + n_halo;
     c->n_pm = ns; c->n_sorted = ns;
     emba_status st;
-    uint32_t* d_err = nullptr;
-    if ((st = ws_get(c, 19, 64, (void**)&d_err))) return st;
+    if ((st = ensure<uint32_t>(c, c->ord.status, 16))) return st;
+    uint32_t* d_err = c->ord.status.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
     hipLaunchKernelGGL(emba_validate_events_kernel, dim3(nblocks(std::max(n_used, n_halo))), dim3(256), 0, s, x, y, t_dev, (long)n_used, c->sw, c->sh, hx, hy,
                        (long)n_halo, d_err);
-    if ((st = dev_alloc(c, &c->d_batch_t, c->n_batch))) return st;
-    if (t_dev) { if (nb) hipLaunchKernelGGL(emba_batch_mid_kernel, dim3(nblocks(nb)), dim3(256), 0, s, t_dev, (long)nb, c->d_batch_t); }
-    else if (nb) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t, batch_t_host, nb * 8, hipMemcpyHostToDevice, s));
-    if (n_halo) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t + nb, hbt, n_halo * 8, hipMemcpyDeviceToDevice, s));
+    if ((st = ensure<int64_t>(c, c->d_batch_t, c->n_batch))) return st;
+    if (t_dev) { if (nb) hipLaunchKernelGGL(emba_batch_mid_kernel, dim3(nblocks(nb)), dim3(256), 0, s, t_dev, (long)nb, c->d_batch_t.as<int64_t>()); }
+    else if (nb) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t.as<int64_t>(), batch_t_host, nb * 8, hipMemcpyHostToDevice, s));
+    if (n_halo) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t.as<int64_t>() + nb, hbt, n_halo * 8, hipMemcpyDeviceToDevice, s));
 
     // pm-order: stable sort by sensor pixel == the per-pixel vectors of EventMap::addEvent (event_map.h:34-37), halo entries in front
-    uint32_t *k0 = nullptr, *v0 = nullptr, *k1 = nullptr, *v1 = nullptr, *d_cf = nullptr, *d_cpos = nullptr;
-    if ((st = ws_get(c, 24, std::max<size_t>(ns, 1) * 4, (void**)&k0)) || (st = ws_get(c, 25, std::max<size_t>(ns, 1) * 4, (void**)&v0)) ||
-        (st = ws_get(c, 26, std::max<size_t>(ns, 1) * 4, (void**)&k1)) || (st = ws_get(c, 27, std::max<size_t>(ns, 1) * 4, (void**)&v1)) ||
-        (st = ws_get(c, 21, std::max<size_t>(ns, 1) * 4, (void**)&d_cf)) || (st = ws_get(c, 22, std::max<size_t>(ns, 1) * 4, (void**)&d_cpos)))
+    if ((st = ensure_sort_pairs(c, std::max<size_t>(ns, 1))) || (st = ensure<uint32_t>(c, c->ord.flags, std::max<size_t>(ns, 1))) ||
+        (st = ensure<uint32_t>(c, c->ord.pos, std::max<size_t>(ns, 1))))
         return st;
+    uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+    uint32_t *d_cf = c->ord.flags.as<uint32_t>(), *d_cpos = c->ord.pos.as<uint32_t>();
     if (ns) hipLaunchKernelGGL(emba_pixel_keys_kernel, dim3(nblocks(ns)), dim3(256), 0, s, x, y, (long)n_used, c->sw, hx, hy, (long)n_halo, k0, v0);
     if ((st = dev_sort(c, &k0, &v0, &k1, &v1, ns, bits_for(c->S)))) return st;
-    if ((st = dev_alloc(c, &c->d_pm_pix, ns)) || (st = dev_alloc(c, &c->d_pm_batch, ns)) || (st = dev_alloc(c, &c->d_pm_orig, ns))) return st;
-    if (ns) hipLaunchKernelGGL(emba_pm_gather_kernel, dim3(nblocks(ns)), dim3(256), 0, s, k0, v0, (long)ns, pol, (long)nb, c->d_pm_pix, c->d_pm_batch, c->d_pm_orig, d_cf);
+    if ((st = ensure<uint32_t>(c, c->d_pm_pix, ns)) || (st = ensure<uint32_t>(c, c->d_pm_batch, ns)) || (st = ensure<uint32_t>(c, c->d_pm_orig, ns))) return st;
+    if (ns) hipLaunchKernelGGL(emba_pm_gather_kernel, dim3(nblocks(ns)), dim3(256), 0, s, k0, v0, (long)ns, pol, (long)nb, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), c->d_pm_orig.as<uint32_t>(), d_cf);
     uint32_t* d_tot = d_err + 4;
     if ((st = dev_scan(c, d_cf, d_cpos, ns, d_tot))) return st;    // (only the total is used: the number of measurement candidates)
     uint32_t h_err[16];
@@ -1066,30 +1085,17 @@ emba_status set_events_core(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
     c->n_cand = ns ? h_err[4] : 0;
     const size_t n_cand = c->n_cand;
 
-    if ((st = dev_alloc(c, &c->d_pose, c->n_batch * kPoseStride))) return st;
-    bool rec_fresh = false;
-    if ((st = dev_alloc(c, &c->d_rec, (std::max<size_t>(n_cand, 1) + kGramPad) * kRecStride, &rec_fresh))) return st;
-    if ((st = dev_alloc(c, &c->d_slot_key, n_cand))) return st;
-    {
-        bool tag_fresh = false;
-        if ((st = dev_alloc(c, &c->d_tag, n_cand + kGramPad, &tag_fresh))) return st;
-        if (tag_fresh) HIP_TRY(c, hipMemsetAsync(c->d_tag, 0, c->caps[reinterpret_cast<void**>(&c->d_tag)], s));
-    }
+    if ((st = ensure<double>(c, c->d_pose, c->n_batch * kPoseStride))) return st;
+    if ((st = size_record_set(c, c->work, n_cand))) return st;
+    if ((st = ensure<uint32_t>(c, c->d_slot_key, n_cand))) return st;
     c->n_fblk = (long)std::max<size_t>((ns + kFlagBlk - 1) / kFlagBlk, 1);
-    if ((st = dev_alloc(c, &c->d_fblk_cnt, (size_t)c->n_fblk)) || (st = dev_alloc(c, &c->d_fblk_off, (size_t)c->n_fblk))) return st;
+    if ((st = ensure<uint32_t>(c, c->d_fblk_cnt, (size_t)c->n_fblk)) || (st = ensure<uint32_t>(c, c->d_fblk_off, (size_t)c->n_fblk))) return st;
     c->n_fsup = (c->n_fblk + kFlagSup - 1) / kFlagSup;
-    if ((st = dev_alloc(c, &c->d_fsup, (size_t)2 * c->n_fsup * kFlagSupStride))) return st;
-    HIP_TRY(c, hipMemsetAsync(c->d_fsup, 0, (size_t)2 * c->n_fsup * kFlagSupStride * sizeof(uint32_t), c->stream));      // (both halves: launch A adds into one and zeroes the other for the next step)
-    if ((st = dev_alloc(c, &c->d_ep, ns))) return st;
-    // a record is valid iff it carries the current evaluation's stamp (record_valid): a reused buffer holds older stamps only, new memory is cleared
-    if (rec_fresh) HIP_TRY(c, hipMemsetAsync(c->d_rec, 0, c->caps[reinterpret_cast<void**>(&c->d_rec)], s));
+    if ((st = ensure<uint32_t>(c, c->d_fsup, (size_t)2 * c->n_fsup * kFlagSupStride))) return st;
+    HIP_TRY(c, hipMemsetAsync(c->d_fsup.as<uint32_t>(), 0, (size_t)2 * c->n_fsup * kFlagSupStride * sizeof(uint32_t), c->stream));      // (both halves: launch A adds into one and zeroes the other for the next step)
+    if ((st = ensure<double>(c, c->d_ep, ns))) return st;
     c->eq_in_alt = false;
-    if (c->d_rec2) {   // the second record set (if an LM loop has made one) follows the window's size
-        bool f2 = false, t2 = false;
-        if ((st = dev_alloc(c, &c->d_rec2, (std::max<size_t>(n_cand, 1) + kGramPad) * kRecStride, &f2)) || (st = dev_alloc(c, &c->d_tag2, n_cand + kGramPad, &t2))) return st;
-        if (f2) HIP_TRY(c, hipMemsetAsync(c->d_rec2, 0, c->caps[reinterpret_cast<void**>(&c->d_rec2)], s));
-        if (t2) HIP_TRY(c, hipMemsetAsync(c->d_tag2, 0, c->caps[reinterpret_cast<void**>(&c->d_tag2)], s));
-    }
+    if (c->alt.rec.p && (st = size_record_set(c, c->alt, n_cand))) return st;   // the second record set (if an LM loop has made one) follows the window's size
     HIP_TRY(c, hipStreamSynchronize(s));
     c->nblk = (long)((ns + kWarpNew - 1) / kWarpNew);
     c->have_events = true;
@@ -1119,12 +1125,14 @@ emba_status emba_set_events(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
     for (size_t b = 0; b < nb; ++b) bt[b] = batch_mid_ns(t_ns[100 * b], t_ns[100 * b + 99]);
     // x, y, polarity (5 B per event) and the halo go to the device as they are
     hipStream_t s = c->stream;
-    uint16_t *dx = nullptr, *dy = nullptr, *dhx = nullptr, *dhy = nullptr; uint8_t* dp = nullptr; int64_t* dhb = nullptr;
     emba_status st;
-    if ((st = ws_get(c, 28, std::max<size_t>(n_used, 1) * 2, (void**)&dx)) || (st = ws_get(c, 29, std::max<size_t>(n_used, 1) * 2, (void**)&dy)) ||
-        (st = ws_get(c, 30, std::max<size_t>(n_used, 1), (void**)&dp)) || (st = ws_get(c, 31, std::max<size_t>(n_halo, 1) * 12, (void**)&dhb)))
+    if ((st = ensure<uint16_t>(c, c->ord.bin_start_or_x, std::max<size_t>(n_used, 1))) || (st = ensure<uint16_t>(c, c->ord.pred_or_y, std::max<size_t>(n_used, 1))) ||
+        (st = ensure<uint8_t>(c, c->ord.heads_or_pol, std::max<size_t>(n_used, 1))) || (st = ensure<uint8_t>(c, c->ord.halo, std::max<size_t>(n_halo, 1) * 12)))
         return st;
-    dhx = reinterpret_cast<uint16_t*>(dhb + n_halo); dhy = dhx + n_halo;
+    uint16_t *dx = c->ord.bin_start_or_x.as<uint16_t>(), *dy = c->ord.pred_or_y.as<uint16_t>();
+    uint8_t* dp = c->ord.heads_or_pol.as<uint8_t>();
+    int64_t* dhb = c->ord.halo.as<int64_t>();
+    uint16_t *dhx = reinterpret_cast<uint16_t*>(dhb + n_halo), *dhy = dhx + n_halo;
     if (n_used) {
         HIP_TRY(c, hipMemcpyAsync(dx, x, n_used * 2, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(dy, y, n_used * 2, hipMemcpyHostToDevice, s));
@@ -1214,14 +1222,11 @@ emba_status emba_upload_map(emba_ctx* c, const double* Gx, const double* Gy)
 {
     if (!c || !Gx || !Gy) return c ? fail(c, EMBA_ERR_INVALID_ARG, "Gx/Gy NULL") : EMBA_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_Gx_own) {
-        emba_status st;
-        if ((st = dev_alloc(c, &c->d_Gx_own, c->npix))) return st;
-        if ((st = dev_alloc(c, &c->d_Gy_own, c->npix))) return st;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_Gx_own, Gx, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_Gy_own, Gy, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    c->d_Gx = c->d_Gx_cur = c->d_Gx_own; c->d_Gy = c->d_Gy_cur = c->d_Gy_own;
+    emba_status st;
+    if ((st = ensure<double>(c, c->d_Gx_own, c->npix)) || (st = ensure<double>(c, c->d_Gy_own, c->npix))) return st;
+    HIP_TRY(c, hipMemcpyAsync(c->d_Gx_own.as<double>(), Gx, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_Gy_own.as<double>(), Gy, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->d_Gx = c->d_Gx_cur = c->d_Gx_own.as<double>(); c->d_Gy = c->d_Gy_cur = c->d_Gy_own.as<double>();
     c->map_is_trial = false;
     c->have_map = true;
     return EMBA_OK;
@@ -1239,13 +1244,7 @@ emba_status emba_bind_map_dev(emba_ctx* c, const double* Gx_dev, const double* G
 namespace {
 emba_status ensure_x2(emba_ctx* c, size_t P)
 {
-    if (c->x2_cap < 2 * P || !c->d_x2) {
-        dev_free(c, c->d_x2);
-        emba_status st = dev_alloc(c, &c->d_x2, std::max<size_t>(2 * P, 2));
-        if (st) return st;
-        c->x2_cap = std::max<size_t>(2 * P, 2);
-    }
-    return EMBA_OK;
+    return ensure<double>(c, c->d_x2, std::max<size_t>(2 * P, 2));
 }
 // src_kind: 0 host pointer, 1 device pointer, 2 the x2 the last solve left in d_x2
 emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double damping)
@@ -1258,22 +1257,19 @@ emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double 
     if (st) return st;
     if (src_kind == 2 && c->P && c->x2_resident_P != c->P) return fail(c, EMBA_ERR_STATE, "x2 NULL: no solve of the current normal equations has left its x2 on the device");
     if (src_kind != 2 && c->P && !x2) return fail(c, EMBA_ERR_INVALID_ARG, "x2 NULL");
-    if (!c->d_Gx_trial) {
-        if ((st = dev_alloc(c, &c->d_Gx_trial, c->npix))) return st;
-        if ((st = dev_alloc(c, &c->d_Gy_trial, c->npix))) return st;
-    }
+    if ((st = ensure<double>(c, c->d_Gx_trial, c->npix)) || (st = ensure<double>(c, c->d_Gy_trial, c->npix))) return st;
     if ((st = ensure_x2(c, c->P))) return st;
     hipStream_t s = c->stream;
     if ((st = ensure_compact(c))) return st;
     if (c->P && src_kind != 2) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_x2, x2, 2 * c->P * sizeof(double), src_kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), x2, 2 * c->P * sizeof(double), src_kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
         c->x2_resident_P = (size_t)-1;      // (whatever a solve left there is overwritten)
     }
-    hipLaunchKernelGGL(emba_update_map_kernel, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, s, c->d_Gx_cur, c->d_Gy_cur, c->d_compact,
-                       c->d_x2, damping, (long)c->npix, c->d_Gx_trial, c->d_Gy_trial);
+    hipLaunchKernelGGL(emba_update_map_kernel, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, s, c->d_Gx_cur, c->d_Gy_cur, c->d_compact.as<int32_t>(),
+                       c->d_x2.as<double>(), damping, (long)c->npix, c->d_Gx_trial.as<double>(), c->d_Gy_trial.as<double>());
     HIP_TRY(c, hipGetLastError());
     if (src_kind == 0) HIP_TRY(c, hipStreamSynchronize(s));   // x2_host may be freed by the caller
-    c->d_Gx = c->d_Gx_trial; c->d_Gy = c->d_Gy_trial;
+    c->d_Gx = c->d_Gx_trial.as<double>(); c->d_Gy = c->d_Gy_trial.as<double>();
     c->map_is_trial = true;
     return EMBA_OK;
 }
@@ -1282,7 +1278,7 @@ emba_status keep_x2(emba_ctx* c, const double* d_src, size_t P)
 {
     emba_status st = ensure_x2(c, P);
     if (st) return st;
-    if (P) HIP_TRY(c, hipMemcpyAsync(c->d_x2, d_src, 2 * P * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (P) HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), d_src, 2 * P * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     c->x2_resident_P = P;
     return EMBA_OK;
 }
@@ -1295,12 +1291,10 @@ emba_status emba_map_accept(emba_ctx* c)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     if (!c->map_is_trial) return fail(c, EMBA_ERR_STATE, "no trial map (call emba_update_map first)");
-    // the trial buffers become the current map; the previous current buffers (if ours) become the next trial buffers
-    double* old_x = (c->d_Gx_cur == c->d_Gx_own) ? c->d_Gx_own : nullptr;
-    double* old_y = (c->d_Gy_cur == c->d_Gy_own) ? c->d_Gy_own : nullptr;
-    c->d_Gx_own = c->d_Gx_trial; c->d_Gy_own = c->d_Gy_trial;
-    c->d_Gx_cur = c->d_Gx = c->d_Gx_own; c->d_Gy_cur = c->d_Gy = c->d_Gy_own;
-    c->d_Gx_trial = old_x; c->d_Gy_trial = old_y;
+    // the trial buffers become the current map; our previous buffers become the next trial buffers (nothing reads them: the current map was either
+    // they or a bound one)
+    std::swap(c->d_Gx_own, c->d_Gx_trial); std::swap(c->d_Gy_own, c->d_Gy_trial);
+    c->d_Gx_cur = c->d_Gx = c->d_Gx_own.as<double>(); c->d_Gy_cur = c->d_Gy = c->d_Gy_own.as<double>();
     c->map_is_trial = false;
     return EMBA_OK;
 }
@@ -1313,9 +1307,7 @@ emba_status emba_trial_reject(emba_ctx* c)
     // (a trial that was only launched: its compacted residual vector and inlier numbers will never be asked for — nothing to resolve)
     if (c->ep_deferred && !c->P_pending && !c->inl_pending) c->ep_deferred = false;
     else if (c->P_pending || c->inl_pending || c->ep_deferred) { emba_status st = resolve_pending(c); if (st) return st; }
-    std::swap(c->d_rec, c->d_rec2); std::swap(c->d_tag, c->d_tag2); std::swap(c->set_stamp, c->set_stamp2);
-    std::swap(c->caps[reinterpret_cast<void**>(&c->d_rec)], c->caps[reinterpret_cast<void**>(&c->d_rec2)]);
-    std::swap(c->caps[reinterpret_cast<void**>(&c->d_tag)], c->caps[reinterpret_cast<void**>(&c->d_tag2)]);
+    std::swap(c->work, c->alt);
     c->eq_in_alt = false;
     c->active_done = c->eq_saved.active_done; c->accum_done = c->eq_saved.accum_done; c->finish_done = c->eq_saved.finish_done;
     c->compact_valid = c->eq_saved.compact_valid; c->l2_fused = c->eq_saved.l2_fused; c->P = c->eq_saved.P; c->pack_len = c->eq_saved.pack_len;
@@ -1358,9 +1350,9 @@ emba_status emba_get_map_active(emba_ctx* c, double* gxy_host, size_t cap_P)
     if (st) return st;
     if (cap_P < c->P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, c->P);
     if (!c->P) return EMBA_OK;
-    double* d_out = nullptr;
-    if ((st = ws_get(c, 15, 2 * c->P * sizeof(double), (void**)&d_out))) return st;
-    hipLaunchKernelGGL(emba_map_active_kernel, dim3(nblocks(c->P)), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->d_active, (long)c->P, d_out);
+    if ((st = ensure<double>(c, c->dl.out, 2 * c->P))) return st;
+    double* d_out = c->dl.out.as<double>();
+    hipLaunchKernelGGL(emba_map_active_kernel, dim3(nblocks(c->P)), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->d_active.as<uint32_t>(), (long)c->P, d_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(gxy_host, d_out, 2 * c->P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1370,12 +1362,12 @@ emba_status emba_get_map_active(emba_ctx* c, double* gxy_host, size_t cap_P)
 emba_status emba_bind_exchange_buffers(emba_ctx* c, int32_t* count_map_dev, double* pack_dev, size_t pack_cap)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    c->d_count = count_map_dev ? count_map_dev : c->d_count_own;
+    c->d_count = count_map_dev ? count_map_dev : c->d_count_own.as<int32_t>();
     c->count_stamp = 0;
     c->pix_dirty_all = true;   // the new count buffer says nothing about which pixacc lines are dirty
     c->pixacc_clean = false;
     if (pack_dev) { c->d_pack = pack_dev; c->pack_cap = pack_cap; c->pack_bound = true; }
-    else { c->pack_bound = false; c->d_pack = c->d_pack_own; c->pack_cap = c->pack_own_cap; }
+    else { c->pack_bound = false; c->d_pack = c->d_pack_own.as<double>(); c->pack_cap = c->d_pack_own.bytes / sizeof(double); }
     return EMBA_OK;
 }
 
@@ -1385,8 +1377,8 @@ emba_status emba_count_compress(emba_ctx* c, uint8_t* u8_dev, int32_t cap)
     if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
     if (c->counts_raw) {      // markers -> this rank's counts AND their saturated bytes in one sweep (ensure_counts + the compression below)
         c->counts_raw = false;
-        c->count_stamp = (c->d_count == c->d_count_own) ? c->set_stamp : 0u;
-        hipLaunchKernelGGL(emba_count_materialise_compress_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc, (long)c->npix,
+        c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
+        hipLaunchKernelGGL(emba_count_materialise_compress_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix,
                            c->count_mark, (int)cap, u8_dev);
     } else {
         hipLaunchKernelGGL(emba_count_compress_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, c->d_count, (long)c->npix, (int)cap, u8_dev);
@@ -1413,16 +1405,7 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
-    if (c->knots_cap < K) {
-        dev_free(c, c->d_knots);
-        if ((st = dev_alloc(c, &c->d_knots, (size_t)4 * K))) return st;
-        c->knots_cap = K;
-    }
-    if (c->seg_cap < K) {
-        dev_free(c, c->d_seg);
-        if ((st = dev_alloc(c, &c->d_seg, (size_t)kSegStride * K))) return st;
-        c->seg_cap = K;
-    }
+    if ((st = ensure<double>(c, c->d_knots, (size_t)4 * K)) || (st = ensure<double>(c, c->d_seg, (size_t)kSegStride * K))) return st;
     if ((st = prepare_order(c, knots, t0_ns, dt_ns, K))) return st;
     if ((st = ensure_pack(c, K))) return st;
     if (c->h_knots_cap < K) {
@@ -1436,18 +1419,11 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         // The working record set is what the current normal equations were formed from: this evaluation (an LM trial, or simply the next
         // step) writes the OTHER set, so that a rejection can go back to untouched equations (emba_trial_reject).
         if (c->P_pending || c->inl_pending) { if ((st = resolve_pending(c, true))) return st; }
-        if (!c->d_rec2) {
-            const size_t nrec = (std::max<size_t>(c->n_cand, 1) + kGramPad) * kRecStride, ntag = c->n_cand + kGramPad;
-            if ((st = dev_alloc(c, &c->d_rec2, nrec)) || (st = dev_alloc(c, &c->d_tag2, ntag))) return st;
-            HIP_TRY(c, hipMemsetAsync(c->d_rec2, 0, nrec * sizeof(double), s));     // (new memory: no record may look valid)
-            HIP_TRY(c, hipMemsetAsync(c->d_tag2, 0, ntag * sizeof(double), s));
-        }
+        if (!c->alt.rec.p && (st = size_record_set(c, c->alt, c->n_cand))) return st;
         c->eq_saved.active_done = c->active_done; c->eq_saved.accum_done = c->accum_done; c->eq_saved.finish_done = c->finish_done;
         c->eq_saved.compact_valid = c->compact_valid; c->eq_saved.l2_fused = c->l2_fused; c->eq_saved.P = c->P; c->eq_saved.pack_len = c->pack_len;
         c->eq_saved.K = c->K; c->eq_saved.thres = c->thres; c->eq_saved.irls = c->irls; c->eq_saved.eta = c->eta;
-        std::swap(c->d_rec, c->d_rec2); std::swap(c->d_tag, c->d_tag2); std::swap(c->set_stamp, c->set_stamp2);
-        std::swap(c->caps[reinterpret_cast<void**>(&c->d_rec)], c->caps[reinterpret_cast<void**>(&c->d_rec2)]);
-        std::swap(c->caps[reinterpret_cast<void**>(&c->d_tag)], c->caps[reinterpret_cast<void**>(&c->d_tag2)]);
+        std::swap(c->work, c->alt);
         c->eq_in_alt = true;
     }
     c->K = K;
@@ -1457,11 +1433,11 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
     c->ep_valid = false; c->ep_in_gram = false; c->ep_after_gram = false;
     if (c->pix_dirty_all) {   // first use of these buffers: num_ev_map.setTo(0), model.cpp:85 (+ every per-pixel accumulator line)
         HIP_TRY(c, hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int32_t), s));
-        HIP_TRY(c, hipMemsetAsync(c->d_pixacc, 0, c->npix * kPixAccStride * sizeof(double), s));
+        HIP_TRY(c, hipMemsetAsync(c->d_pixacc.as<double>(), 0, c->npix * kPixAccStride * sizeof(double), s));
         c->pix_dirty_all = false;
         c->pixacc_clean = true;
     }
-    int* rect_cur = c->d_rect;
+    int* rect_cur = c->d_rect.as<int>();
     // the clearing pass over count map + accumulator lines is only needed when the previous evaluation's sums are still in their lines (it was
     // never formed by the resident step, whose gather clears them behind itself); the count map's entries are stamped and need no clearing
     // (... and only when a warp kernel follows to re-mark it — an EMPTY window launches none, so its count map and active set would be the
@@ -1476,10 +1452,10 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         InlineKnots kn;
         const int nb = (int)c->n_batch;
         ++c->eval_seq;
-        c->d_err = c->d_err2 + (c->eval_seq & 1u);
-        q.count = c->d_count; q.npix = (long)c->npix; q.pixacc = c->d_pixacc; q.W = c->W; q.H = c->H; q.n_prep = n_prep_blk;
-        q.batch_t_ns = c->d_batch_t; q.nb = nb; q.K = (int)K; q.t0_ns = t0_ns; q.dt_ns = dt_ns; q.pose = c->d_pose; q.err = c->d_err;
-        q.err_next = c->d_err2 + ((c->eval_seq + 1u) & 1u);
+        c->d_err = c->d_err2.as<int>() + (c->eval_seq & 1u);
+        q.count = c->d_count; q.npix = (long)c->npix; q.pixacc = c->d_pixacc.as<double>(); q.W = c->W; q.H = c->H; q.n_prep = n_prep_blk;
+        q.batch_t_ns = c->d_batch_t.as<int64_t>(); q.nb = nb; q.K = (int)K; q.t0_ns = t0_ns; q.dt_ns = dt_ns; q.pose = c->d_pose.as<double>(); q.err = c->d_err;
+        q.err_next = c->d_err2.as<int>() + ((c->eval_seq + 1u) & 1u);
         // pixel order: per-event pose from the segment records too (warp_lane SEGPOSE; round 4, late) instead of one 112-B pose record per batch gathered by
         // every event — 7 x 16-B gathers over 64 different lines per wave, and past ~7 M events a table that no longer fits the L2s.  Measured, same box,
         // step time: 1 M events 101.2 -> 98.2 us, 1.5 M 150.8 -> 143.5, 10 M on 640x480 (city shape) 779 -> 714 (warp 0.60 -> 0.68 of the roofline),
@@ -1488,42 +1464,42 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         c->segpose = !c->tile_order && (c->segpose_mode ? c->segpose_mode == 2 : true);
         const bool seg_records = c->tile_order || c->segpose;
         q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
-        q.seg = seg_records ? c->d_seg : nullptr;
-        q.knots_dev = c->d_knots; q.knots_out = c->d_knots;
+        q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
+        q.knots_dev = c->d_knots.as<double>(); q.knots_out = c->d_knots.as<double>();
         q.inline_knots = (K <= kInlineKnots) ? 1 : 0;
         if (q.inline_knots) memcpy(kn.q, knots, (size_t)4 * K * sizeof(double));       // by value in the kernel arguments: no staging copy at all
         else {
             if (c->knots_in_flight) HIP_TRY(c, hipStreamSynchronize(s));               // the previous copy must have consumed the pinned staging buffer
             memcpy(c->h_knots, knots, (size_t)4 * K * sizeof(double));
-            HIP_TRY(c, hipMemcpyAsync(c->d_knots, c->h_knots, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), c->h_knots, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
             c->knots_in_flight = true;   // cleared by the next host synchronisation
         }
         q.n_tex = (c->use_texel == 3) ? 1024 : 0;
-        q.Gx = c->d_Gx; q.Gy = c->d_Gy; q.rect = rect_cur; q.texel = c->d_texel;
+        q.Gx = c->d_Gx; q.Gy = c->d_Gy; q.rect = rect_cur; q.texel = c->d_texel.as<double>();
         if (q.n_pose + q.n_tex + q.n_prep == 0) q.n_prep = 1;   // (an empty window on clean lines: block 0 still clears the next status word)
         if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }
         hipLaunchKernelGGL(emba_prep_pose_texel_kernel, dim3((unsigned)(q.n_pose + q.n_tex + q.n_prep)), dim3(256), 0, s, q, kn);
     }
     if (c->use_texel == 1)
         hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, s, c->d_Gx, c->d_Gy, c->H, c->W,
-                           c->d_texel);
+                           c->d_texel.as<double>());
     if (c->n_sorted) {
         WarpParams p{};
-        p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot; p.ev_pm = c->tile_order ? c->d_ev_pm : nullptr; p.n_sorted = (long)c->n_sorted;
-        p.ev_u = c->d_ev_u; p.ev_seg = c->d_ev_seg;      // per entry, in both orders
-        p.nblk = c->nblk; p.pose = c->d_pose; p.seg = c->d_seg; p.lut = c->d_lut; p.texel = c->use_texel ? c->d_texel : nullptr; p.W = c->W; p.H = c->H;
+        p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)c->n_sorted;
+        p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
+        p.nblk = c->nblk; p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = c->use_texel ? c->d_texel.as<double>() : nullptr; p.W = c->W; p.H = c->H;
         p.rect_acc = (c->use_texel == 3) ? rect_cur : nullptr;
-        p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc;
+        p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc.as<double>();
         p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px;
-        p.count = c->d_count; p.rec = c->d_rec; p.tag = (c->use_tags && !c->tile_order) ? c->d_tag : nullptr; p.e_sorted = c->d_e_sorted; p.flag = c->d_flag;
+        p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.tag = (c->use_tags && !c->tile_order) ? c->work.tag.as<double>() : nullptr; p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
         p.err = c->d_err;
         p.ablate = c->ablate;
         p.rec_nt = (c->tile_order || c->n_cand * (size_t)(kRecStride * 8) > ((size_t)144 << 20)) ? 1 : 0;      // (1 M slots = 128 MB: kept in the Infinity Cache for the Gram kernel)
         p.irls = c->cost_irls; p.eta = c->cost_eta;
-        p.stamp = ++c->rec_stamp; c->set_stamp = p.stamp;
+        p.stamp = ++c->rec_stamp; c->work.stamp = p.stamp;
         p.marker = c->count_mark = count_marker(p.stamp);
         c->pixacc_clean = false; c->pixacc_consumed = false;
-        p.chunks = c->d_chunks; p.n_chunks = c->n_chunks; p.chunks_linear = c->chunks_lpt ? 1 : 0;
+        p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->n_chunks; p.chunks_linear = c->chunks_lpt ? 1 : 0;
         if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
         if (c->tile_order) launch_warp_tiled(c->tile_shape, dim3((unsigned)grid8(c->n_chunks)), s, p);
         else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
@@ -1549,7 +1525,7 @@ emba_status emba_eval_finish(emba_ctx* c, double* ep_out, size_t* n_inliers, int
     emba_status st = resolve_pending(c);
     if (st) return st;
     if (n_inliers) *n_inliers = c->n_inliers;
-    if (ep_out && c->n_inliers) { HIP_TRY(c, hipStreamSynchronize(c->stream)); if ((st = d2h_pageable(c, ep_out, c->d_ep, c->n_inliers * sizeof(double)))) return st; }
+    if (ep_out && c->n_inliers) { HIP_TRY(c, hipStreamSynchronize(c->stream)); if ((st = d2h_pageable(c, ep_out, c->d_ep.as<double>(), c->n_inliers * sizeof(double)))) return st; }
     if (num_ev_map_out) {
         { emba_status st0 = ensure_counts(c); if (st0) return st0; }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1579,9 +1555,9 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
     const long npix = (long)c->npix;
     const long head = (long)9 * c->K * c->K + (long)3 * c->K;
     ActiveWriteParams aw{};
-    aw.count = c->d_count; aw.npix = npix; aw.thres = thres; aw.blk_off = c->d_ablk_off; aw.compact = nullptr; aw.active_idx = c->d_active; aw.pixacc = c->d_pixacc;
+    aw.count = c->d_count; aw.npix = npix; aw.thres = thres; aw.blk_off = c->d_ablk_off.as<uint32_t>(); aw.compact = nullptr; aw.active_idx = c->d_active.as<uint32_t>(); aw.pixacc = c->d_pixacc.as<double>();
     aw.A22b2 = pack_A22b2(c); aw.pack_head = c->d_pack; aw.head_len = head; aw.alpha = c->fused_alpha; aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
-    aw.active_bits = c->d_active_bits; aw.max_P = (long)((c->pack_cap - (size_t)head) / 5); aw.n_ablk = (long)c->n_ablk; aw.ablate = c->ablate;
+    aw.active_bits = c->d_active_bits.as<uint8_t>(); aw.max_P = (long)((c->pack_cap - (size_t)head) / 5); aw.n_ablk = (long)c->n_ablk; aw.ablate = c->ablate;
     // the resident step cleared this evaluation's per-pixel sums behind its gather: a second formNormalEq on the same evaluation takes A22 | b2
     // from the records (the generic path of emba_form_accumulate), and its L2 term from emba_form_finish
     c->force_generic_a22 = c->pixacc_consumed;
@@ -1599,15 +1575,15 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
     if (c->ep_deferred && c->n_sorted) {
         c->ep_deferred = false;
         PostWarpParams q{};
-        q.count = c->d_count; q.npix = npix; q.thres = thres; q.ablk_cnt = c->d_ablk_cnt; q.ablk_off = c->d_ablk_off; q.n_ablk = (long)c->n_ablk;
-        q.total_P = c->d_total + 1; q.total_P_host = c->h_pinned_dev + 2;
-        q.fblk_cnt = c->d_fblk_cnt; q.fblk_off = c->d_fblk_off; q.n_fblk = c->n_fblk; q.perm = nullptr; q.n_pm = (long)c->n_pm;
-        q.total_inl = c->d_total; q.total_inl_host = c->h_pinned_dev;
+        q.count = c->d_count; q.npix = npix; q.thres = thres; q.ablk_cnt = c->d_ablk_cnt.as<uint32_t>(); q.ablk_off = c->d_ablk_off.as<uint32_t>(); q.n_ablk = (long)c->n_ablk;
+        q.total_P = c->d_total.as<uint32_t>() + 1; q.total_P_host = c->h_pinned_dev + 2;
+        q.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); q.fblk_off = c->d_fblk_off.as<uint32_t>(); q.n_fblk = c->n_fblk; q.perm = nullptr; q.n_pm = (long)c->n_pm;
+        q.total_inl = c->d_total.as<uint32_t>(); q.total_inl_host = c->h_pinned_dev;
         q.err_dev = c->d_err; q.err_host = c->h_pinned_dev + 1;
-        q.e_sorted = c->d_e_sorted; q.flag = c->d_flag; q.ep = c->d_ep; q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
+        q.e_sorted = c->d_e_sorted.as<double>(); q.flag = c->d_flag.as<uint8_t>(); q.ep = c->d_ep.as<double>(); q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
         q.seq = ++c->seq; q.seq_host = c->h_pinned_dev + 3; c->seq_armed = true;
-        if (c->counts_raw) { q.raw_count = c->d_count; q.pixacc = c->d_pixacc; q.marker = c->count_mark; c->counts_raw = false;      // launch A turns the markers into counts
-                             c->count_stamp = (c->d_count == c->d_count_own) ? c->set_stamp : 0u; }
+        if (c->counts_raw) { q.raw_count = c->d_count; q.pixacc = c->d_pixacc.as<double>(); q.marker = c->count_mark; c->counts_raw = false;      // launch A turns the markers into counts
+                             c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u; }
         const bool consume = c->step_consume && c->step_fast && !c->force_generic_a22;    // this gather is the per-pixel sums' only reader: lines are zeroed behind it
         // list-driven gather: it rides in the head of the Gram kernel (as a kernel of its own it is no faster than the sweeping write: 109.6 vs
         // 108.5 us per step at 1 M events; option step_gather = 1 forces that form for comparison, 0 the sweeping kernel)
@@ -1620,8 +1596,8 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
         // with it / with the sweeping launch — 1 M 92.6 / 96.4 us, 1.5 M 134.7 / 143.8, 2 M (tile order) 193.4 / 208.5, 3 M 274.4 / 280.9, 10 M on
         // 640x480 (pixel order) 612.5 / 626.1, on 2048x4096 766.7 / 776.3; but 5 M (tile) 436.0 / 432.2, 40 M 3137 / 3014: a bandwidth-bound stream
         // misses the four waves more than it gains from the launch — pixel order everywhere, tile order up to 3.5 M candidates)
-        if (consume) { aw.clear_pixacc = c->d_pixacc; c->pixacc_clean = true; c->pixacc_consumed = true; }
-        if (lists) { q.seg = c->d_seg_act; aw.seg = c->d_seg_act; if (consume) q.clear_inactive = c->d_pixacc; }
+        if (consume) { aw.clear_pixacc = c->d_pixacc.as<double>(); c->pixacc_clean = true; c->pixacc_consumed = true; }
+        if (lists) { q.seg = c->d_seg_act.as<uint16_t>(); aw.seg = c->d_seg_act.as<uint16_t>(); if (consume) q.clear_inactive = c->d_pixacc.as<double>(); }
         // launch A: {active counts (+ markers -> counts, activity bits, cleared A11 | b1) || inlier-flag counts}; launch B: the active-set write,
         // whose blocks take their own prefix over launch A's per-block counts and whose last block publishes P, the inlier total, the status
         // word and the sequence words the host polls.  (Nothing on the device reads the compacted residual vector `ep` — costs, Gram and solvers
@@ -1631,11 +1607,11 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
         // and "sum every predecessor"): 38-270 us against 6.3 + 11.2 — the eight XCDs' L2s are not coherent with each other, so every flag is a
         // round trip to the memory side (and a release / acquire pair writes back / invalidates a whole L2); a kernel boundary is cheaper.
         c->fsup_half ^= 1;
-        q.fsup = c->d_fsup + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride; q.fsup_next = c->d_fsup + (size_t)(c->fsup_half ^ 1) * c->n_fsup * kFlagSupStride; q.n_sup = c->n_fsup;
-        q.active_bits = c->d_active_bits; q.pack_head = c->d_pack; q.head_len = head; aw.bits_head_done = 1;
-        q.blk_rect = c->d_blk_rect; q.W = c->W; aw.blk_rect = c->d_blk_rect; aw.rect_out = c->d_rect;   // the texel rectangle of the NEXT evaluation
+        q.fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride; q.fsup_next = c->d_fsup.as<uint32_t>() + (size_t)(c->fsup_half ^ 1) * c->n_fsup * kFlagSupStride; q.n_sup = c->n_fsup;
+        q.active_bits = c->d_active_bits.as<uint8_t>(); q.pack_head = c->d_pack; q.head_len = head; aw.bits_head_done = 1;
+        q.blk_rect = c->d_blk_rect.as<int>(); q.W = c->W; aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the texel rectangle of the NEXT evaluation
         hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->n_fblk)), dim3(256), 0, s, q);
-        aw.blk_cnt = c->d_ablk_cnt; aw.fblk_cnt = c->d_fblk_cnt; aw.n_fblk = c->n_fblk; aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
+        aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->n_fblk; aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
         aw.total_inl = q.total_inl; aw.total_inl_host = q.total_inl_host; aw.err_dev = q.err_dev; aw.err_host = q.err_host; aw.seq = q.seq; aw.seq_host = q.seq_host;
         // (round 4, measured and dropped: this write on a side stream beside the Gram kernel — both only depend on launch A — costs more than it
         // hides: each cross-stream event edge opens a 7-12 us bubble on this stack, 114.5 vs 107.6 us per step)
@@ -1653,8 +1629,8 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
     } else {
         { emba_status st0 = launch_ep_compaction(c); if (st0) return st0; }
         { emba_status st0 = ensure_counts(c); if (st0) return st0; }
-        hipLaunchKernelGGL(emba_active_count_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, c->d_count, npix, (int)thres, c->d_ablk_cnt);
-        hipLaunchKernelGGL(emba_scan_kernel, dim3(1), dim3(256), 0, s, c->d_ablk_cnt, c->d_ablk_off, (long)c->n_ablk, c->d_total + 1,
+        hipLaunchKernelGGL(emba_active_count_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, c->d_count, npix, (int)thres, c->d_ablk_cnt.as<uint32_t>());
+        hipLaunchKernelGGL(emba_scan_kernel, dim3(1), dim3(256), 0, s, c->d_ablk_cnt.as<uint32_t>(), c->d_ablk_off.as<uint32_t>(), (long)c->n_ablk, c->d_total.as<uint32_t>() + 1,
                            c->h_pinned_dev + 2, (const int*)nullptr, (int*)nullptr);
         hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
     }
@@ -1694,9 +1670,9 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
     if (generic_a22) { emba_status st = resolve_pending(c); if (st) return st; }   // needs n_inliers / P on the host (rare path)
     if (ep_host && c->n_inliers) {
         { emba_status st = ensure_inl_idx(c); if (st) return st; }
-        HIP_TRY(c, hipMemcpyAsync(c->d_ep, ep_host, c->n_inliers * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep, c->d_flag,
-                           c->d_inl_idx, c->d_ev_slot, c->d_ev_pix, c->tile_order ? c->d_ev_pm : nullptr, (long)c->n_sorted, c->d_rec, c->d_e_sorted);
+        HIP_TRY(c, hipMemcpyAsync(c->d_ep.as<double>(), ep_host, c->n_inliers * sizeof(double), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep.as<double>(), c->d_flag.as<uint8_t>(),
+                           c->d_inl_idx.as<int32_t>(), c->d_ev_slot.as<uint32_t>(), c->d_ev_pix, c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr, (long)c->n_sorted, c->work.rec.as<double>(), c->d_e_sorted.as<double>());
     }
     // A11 = Zero, b1 = Zero (model.cpp:357-361).  A22/b2 of the active pixels were gathered from the per-pixel
     // accumulator by emba_form_active (quadratic cost, device-resident residuals); with IRLS weights or a
@@ -1707,16 +1683,16 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         { emba_status st = ensure_compact(c); if (st) return st; }
         HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->P * sizeof(double), s));
         if (c->n_cand)
-            hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->d_rec,
-                               (long)c->n_cand, c->d_count, c->d_compact, c->thres, irls, eta, pack_A22b2(c), c->set_stamp);
+            hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
+                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->thres, irls, eta, pack_A22b2(c), c->work.stamp);
     }
     if (c->n_cand) {
         GramParams p{};
-        p.rec = c->d_rec; p.slot_key = c->d_slot_key; p.n_slots = (long)c->n_cand; p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits);
-        p.irls = irls; p.eta = eta; p.stamp = c->set_stamp; p.A11 = pack_A11(c); p.b1 = pack_b1(c);
+        p.rec = c->work.rec.as<double>(); p.slot_key = c->d_slot_key.as<uint32_t>(); p.n_slots = (long)c->n_cand; p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits.as<uint8_t>());
+        p.irls = irls; p.eta = eta; p.stamp = c->work.stamp; p.A11 = pack_A11(c); p.b1 = pack_b1(c);
         // the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime:
         // nearly every slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
-        p.tag = gram_uses_tags(c, ep_host != nullptr) ? c->d_tag : nullptr;
+        p.tag = gram_uses_tags(c, ep_host != nullptr) ? c->work.tag.as<double>() : nullptr;
         p.dim = 3 * c->K;
         p.ablate = c->ablate;
         // slots per wave: whole rounds of one 16-wave block per CU with equal shares (1 M events: one round of 236 slots per wave),
@@ -1740,8 +1716,8 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         p.n_gram_blocks = (int)grid;
         const bool ep_tail = c->ep_in_gram && !ep_host && c->n_pm;
         if (ep_tail) {
-            p.ep_flag = c->d_flag; p.ep_e = c->d_e_sorted; p.ep_out = c->d_ep; p.ep_fblk_cnt = c->d_fblk_cnt; p.ep_n_pm = (long)c->n_pm; p.ep_n_fblk = c->n_fblk;
-            p.ep_fsup = c->d_fsup + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride;
+            p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>(); p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_pm = (long)c->n_pm; p.ep_n_fblk = c->n_fblk;
+            p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride;
             grid += (unsigned)((c->n_pm + kEpTailBlk - 1) / kEpTailBlk);
         }
         c->ep_in_gram = false;
@@ -1767,9 +1743,9 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }
     }
     if (c->ep_after_gram && !ep_host && c->n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
-        { emba_status st = dev_scan(c, c->d_fblk_cnt, c->d_fblk_off, (size_t)c->n_fblk, c->d_total + 2); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted, c->d_flag, (const uint32_t*)nullptr, c->d_fblk_off, (long)c->n_pm,
-                           c->d_ep, (int32_t*)nullptr);
+        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>() + 2); if (st) return st; }
+        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->n_pm,
+                           c->d_ep.as<double>(), (int32_t*)nullptr);
         c->ep_valid = true;
     }
     c->ep_after_gram = false;
@@ -1790,8 +1766,8 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
         // P may still be unresolved on the host: the kernel reads it from device memory, the grid covers the bound
         const size_t bound = c->P_pending ? c->npix : c->P;
         if (bound)
-            hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), c->d_active,
-                               c->d_total + 1, alpha, c->d_Gx, c->d_Gy);
+            hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), c->d_active.as<uint32_t>(),
+                               c->d_total.as<uint32_t>() + 1, alpha, c->d_Gx, c->d_Gy);
     }
     HIP_TRY(c, hipGetLastError());
     const bool download = A11 || b1 || active_idx || A22 || b2 || A12_dense;
@@ -1803,13 +1779,13 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
     if ((A22 || b2 || A12_dense || active_idx) && cap_P < P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, P);
     if (A11) HIP_TRY(c, hipMemcpyAsync(A11, pack_A11(c), (size_t)dim * dim * sizeof(double), hipMemcpyDeviceToHost, s));
     if (b1) HIP_TRY(c, hipMemcpyAsync(b1, pack_b1(c), (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (active_idx && P) HIP_TRY(c, hipMemcpyAsync(active_idx, c->d_active, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    double* d_A22 = nullptr; double* d_b2 = nullptr; double* d_A12 = nullptr;
+    if (active_idx && P) HIP_TRY(c, hipMemcpyAsync(active_idx, c->d_active.as<uint32_t>(), P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DevBuf A12_tmp;
     if ((A22 || b2) && P) {
         // (round 6) the unpacked blocks sit in a workspace (a hipMalloc / hipFree pair per call until then) and travel through the pinned pipeline + the copy helpers
         // like ep: the drop-in downloads them twice per accepted step (formNormalEq, applyL2Reg), 23 MB each at config 2's shape
-        if ((st = ws_get(c, 43, 6 * P * sizeof(double), (void**)&d_A22))) return st;
-        d_b2 = d_A22 + 4 * P;
+        if ((st = ensure<double>(c, c->dl.A22b2, 6 * P))) return st;
+        double *d_A22 = c->dl.A22b2.as<double>(), *d_b2 = d_A22 + 4 * P;
         hipLaunchKernelGGL(emba_unpack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), (long)P, d_A22, d_b2);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -1819,16 +1795,16 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
     if (A12_dense && P) {
         if ((st = ensure_compact(c))) return st;
         const size_t n12 = (size_t)dim * 2 * P;
-        if ((st = dev_alloc(c, &d_A12, n12))) return st;
+        if ((st = ensure<double>(c, A12_tmp, n12))) return st;
+        double* d_A12 = A12_tmp.as<double>();
         (void)hipMemsetAsync(d_A12, 0, n12 * sizeof(double), s);
         if (c->n_cand)
-            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->d_rec, c->d_slot_key,
-                               (long)c->n_cand, c->d_count, c->d_compact, c->thres, c->irls, c->eta, dim, d_A12, c->set_stamp);
+            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
+                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->thres, c->irls, c->eta, dim, d_A12, c->work.stamp);
         (void)hipMemcpyAsync(A12_dense, d_A12, n12 * sizeof(double), hipMemcpyDeviceToHost, s);
     }
     hipError_t e = hipStreamSynchronize(s);
     c->knots_in_flight = false;
-    dev_free(c, d_A12);
     if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "form_finish: %s", hipGetErrorString(e));
     HIP_TRY(c, hipGetLastError());
     c->finish_done = true;
@@ -1854,17 +1830,16 @@ emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     const size_t M = c->n_cand;
     if (!M) return EMBA_OK;
-    int32_t *d_c = nullptr, *d_p = nullptr, *d_x = nullptr; double *d_w = nullptr, *d_jc = nullptr, *d_jp = nullptr, *d_dp = nullptr;
+    DevBuf b_c, b_p, b_x, b_w, b_jc, b_jp, b_dp;      // (per call)
     emba_status st;
-    if ((st = dev_alloc(c, &d_c, M)) || (st = dev_alloc(c, &d_p, M)) || (st = dev_alloc(c, &d_x, M)) || (st = dev_alloc(c, &d_w, M)) ||
-        (st = dev_alloc(c, &d_jc, 6 * M)) || (st = dev_alloc(c, &d_jp, 6 * M)) || (st = dev_alloc(c, &d_dp, 2 * M))) {
-        dev_free(c, d_c); dev_free(c, d_p); dev_free(c, d_x); dev_free(c, d_w); dev_free(c, d_jc); dev_free(c, d_jp); dev_free(c, d_dp);
+    if ((st = ensure<int32_t>(c, b_c, M)) || (st = ensure<int32_t>(c, b_p, M)) || (st = ensure<int32_t>(c, b_x, M)) || (st = ensure<double>(c, b_w, M)) ||
+        (st = ensure<double>(c, b_jc, 6 * M)) || (st = ensure<double>(c, b_jp, 6 * M)) || (st = ensure<double>(c, b_dp, 2 * M)) || (st = ensure_compact(c)))
         return st;
-    }
+    int32_t *d_c = b_c.as<int32_t>(), *d_p = b_p.as<int32_t>(), *d_x = b_x.as<int32_t>();
+    double *d_w = b_w.as<double>(), *d_jc = b_jc.as<double>(), *d_jp = b_jp.as<double>(), *d_dp = b_dp.as<double>();
     hipStream_t s = c->stream;
-    if ((st = ensure_compact(c))) { dev_free(c, d_c); dev_free(c, d_p); dev_free(c, d_x); dev_free(c, d_w); dev_free(c, d_jc); dev_free(c, d_jp); dev_free(c, d_dp); return st; }
-    hipLaunchKernelGGL(emba_export_a12_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c->d_rec, c->d_slot_key, (long)M,
-                       c->d_count, c->d_compact, c->thres, c->irls, c->eta, d_c, d_p, d_x, d_w, d_jc, d_jp, d_dp, c->set_stamp);
+    hipLaunchKernelGGL(emba_export_a12_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(), (long)M,
+                       c->d_count, c->d_compact.as<int32_t>(), c->thres, c->irls, c->eta, d_c, d_p, d_x, d_w, d_jc, d_jp, d_dp, c->work.stamp);
     if (cp_c) (void)hipMemcpyAsync(cp_c, d_c, M * 4, hipMemcpyDeviceToHost, s);
     if (cp_p) (void)hipMemcpyAsync(cp_p, d_p, M * 4, hipMemcpyDeviceToHost, s);
     if (pix) (void)hipMemcpyAsync(pix, d_x, M * 4, hipMemcpyDeviceToHost, s);
@@ -1873,7 +1848,6 @@ emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32
     if (jp) (void)hipMemcpyAsync(jp, d_jp, 6 * M * 8, hipMemcpyDeviceToHost, s);
     if (dp) (void)hipMemcpyAsync(dp, d_dp, 2 * M * 8, hipMemcpyDeviceToHost, s);
     hipError_t e = hipStreamSynchronize(s);
-    dev_free(c, d_c); dev_free(c, d_p); dev_free(c, d_x); dev_free(c, d_w); dev_free(c, d_jc); dev_free(c, d_jp); dev_free(c, d_dp);
     if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "get_A12_sparse: %s", hipGetErrorString(e));
     return EMBA_OK;
 }
@@ -1899,7 +1873,7 @@ emba_status emba_get_ep(emba_ctx* c, double* ep_host, size_t cap, size_t* n_inli
     if (n_inliers) *n_inliers = c->n_inliers;
     if (cap < c->n_inliers) return fail(c, EMBA_ERR_CAPACITY, "cap=%zu < inliers=%zu", cap, c->n_inliers);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->n_inliers && (st = d2h_pageable(c, ep_host, c->d_ep, c->n_inliers * sizeof(double)))) return st;
+    if (c->n_inliers && (st = d2h_pageable(c, ep_host, c->d_ep.as<double>(), c->n_inliers * sizeof(double)))) return st;
     return EMBA_OK;
 }
 
@@ -1911,9 +1885,9 @@ emba_status emba_get_inlier_pixels(emba_ctx* c, uint32_t* pix_host)
     emba_status st;
     if ((st = resolve_pending(c)) || (st = ensure_inl_idx(c))) return st;
     if (!c->n_inliers) return EMBA_OK;
-    uint32_t* d_out = nullptr;
-    if ((st = ws_get(c, 15, c->n_inliers * 4, (void**)&d_out))) return st;
-    hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix, c->d_flag, c->d_inl_idx, (long)c->n_pm, d_out);
+    if ((st = ensure<uint32_t>(c, c->dl.out, c->n_inliers))) return st;
+    uint32_t* d_out = c->dl.out.as<uint32_t>();
+    hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->n_pm, d_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(pix_host, d_out, c->n_inliers * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1928,9 +1902,9 @@ emba_status emba_get_inlier_pixel_starts(emba_ctx* c, uint32_t* starts_host)
     emba_status st;
     if ((st = resolve_pending(c)) || (st = ensure_inl_idx(c))) return st;
     const uint32_t S = (uint32_t)((size_t)c->sw * c->sh);
-    uint32_t *d_px = nullptr, *d_starts = nullptr;
-    if ((st = ws_get(c, 15, std::max<size_t>(c->n_inliers, 1) * 4, (void**)&d_px)) || (st = ws_get(c, 42, ((size_t)S + 1) * 4, (void**)&d_starts))) return st;
-    if (c->n_inliers) hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix, c->d_flag, c->d_inl_idx, (long)c->n_pm, d_px);
+    if ((st = ensure<uint32_t>(c, c->dl.out, std::max<size_t>(c->n_inliers, 1))) || (st = ensure<uint32_t>(c, c->dl.pix_starts, (size_t)S + 1))) return st;
+    uint32_t *d_px = c->dl.out.as<uint32_t>(), *d_starts = c->dl.pix_starts.as<uint32_t>();
+    if (c->n_inliers) hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->n_pm, d_px);
     hipLaunchKernelGGL(emba_pix_starts_kernel, dim3(nblocks(c->n_inliers + 1)), dim3(256), 0, c->stream, d_px, (long)c->n_inliers, S, d_starts);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(starts_host, d_starts, ((size_t)S + 1) * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1957,7 +1931,7 @@ emba_status emba_get_ep_by_pixel(emba_ctx* c, double* ep_out, const uint64_t* ds
     const uint32_t* starts = c->h_pix_starts.data();
     if ((size_t)starts[S] != c->n_inliers) return fail(c, EMBA_ERR_STATE, "the pixel starts do not belong to this evaluation (%u residuals there, %zu here)", starts[S], c->n_inliers);
     size_t p = 0;      // the pixel cursor only moves forward: the chunks arrive in ep order
-    return d2h_chunks(c, c->d_ep, c->n_inliers * sizeof(double), [&](const void* chunk, size_t off, size_t len) {
+    return d2h_chunks(c, c->d_ep.as<double>(), c->n_inliers * sizeof(double), [&](const void* chunk, size_t off, size_t len) {
         const size_t a = off / sizeof(double), b = (off + len) / sizeof(double);
         while (p < S && (size_t)starts[p + 1] <= a) ++p;
         for (size_t q = p; q < S && (size_t)starts[q] < b; ++q) {
@@ -1974,14 +1948,14 @@ emba_status emba_data_cost(emba_ctx* c, int32_t irls, double eta, double* cost)
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_scalar, 0, sizeof(double), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_scalar.as<double>(), 0, sizeof(double), s));
     if (c->n_sorted) {
         const unsigned grid = (unsigned)std::min<size_t>((c->n_pm + 255) / 256, 2048);
-        hipLaunchKernelGGL(emba_data_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_e_sorted, c->d_flag, (long)c->n_pm, (int)irls, eta,
-                           c->d_scalar);
+        hipLaunchKernelGGL(emba_data_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (long)c->n_pm, (int)irls, eta,
+                           c->d_scalar.as<double>());
     }
     double v = 0;
-    HIP_TRY(c, hipMemcpyAsync(&v, c->d_scalar, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&v, c->d_scalar.as<double>(), sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (irls == 0) v *= 0.5;
     else if (irls == 2) v *= 0.5 / eta;
@@ -2006,17 +1980,17 @@ emba_status emba_costs_launch(emba_ctx* c, int32_t irls, double eta, int32_t wit
         HIP_TRY(c, hipHostMalloc((void**)&c->h_cost, 4 * sizeof(double), hipHostMallocDefault));
         memset(c->h_cost, 0, 4 * sizeof(double));
         HIP_TRY(c, hipHostGetDevicePointer((void**)&c->h_cost_dev, c->h_cost, 0));
-        HIP_TRY(c, hipMalloc((void**)&c->d_cost_acc, 4 * sizeof(double)));
-        HIP_TRY(c, hipMemsetAsync(c->d_cost_acc, 0, 4 * sizeof(double), c->stream));      // (on the kernels' stream: a hipMemset on the default stream is not ordered in front of them)
+        if (emba_status st = ensure<double>(c, c->d_cost_acc, 4)) return st;
+        HIP_TRY(c, hipMemsetAsync(c->d_cost_acc.as<double>(), 0, 4 * sizeof(double), c->stream));      // (on the kernels' stream: a hipMemset on the default stream is not ordered in front of them)
     }
     hipStream_t s = c->stream;
     CostsParams p{};
-    p.e_sorted = c->d_e_sorted; p.flag = c->d_flag; p.n_pm = c->n_sorted ? (long)c->n_pm : 0L; p.irls = (int)irls; p.eta = eta;
+    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>(); p.n_pm = c->n_sorted ? (long)c->n_pm : 0L; p.irls = (int)irls; p.eta = eta;
     p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.npix = with_reg ? (long)c->npix : 0L;
     // (a few hundred blocks: every block ends with two same-address atomics — its sum and its ticket —, and 4096 of them on one word serialise for longer than the sums take)
     p.nb_data = (int)std::max<size_t>(1, std::min<size_t>(((size_t)p.n_pm + 255) / 256, (size_t)c->n_cu));
     p.nb_reg = with_reg ? (int)std::max<size_t>(1, std::min<size_t>((c->npix + 255) / 256, (size_t)2 * c->n_cu)) : 0;
-    p.acc = c->d_cost_acc; p.ticket = reinterpret_cast<unsigned int*>(c->d_cost_acc + 2); p.err_dev = c->d_err;
+    p.acc = c->d_cost_acc.as<double>(); p.ticket = reinterpret_cast<unsigned int*>(c->d_cost_acc.as<double>() + 2); p.err_dev = c->d_err;
     p.host_out = c->h_cost_dev; p.seq = ++c->cost_seq;
     hipLaunchKernelGGL(emba_costs_kernel, dim3((unsigned)(p.nb_data + p.nb_reg)), dim3(256), 0, s, p);
     HIP_TRY(c, hipGetLastError());
@@ -2055,11 +2029,11 @@ emba_status emba_reg_cost(emba_ctx* c, double alpha, double* cost)
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_scalar + 1, 0, sizeof(double), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_scalar.as<double>() + 1, 0, sizeof(double), s));
     const unsigned grid = (unsigned)std::min<size_t>((c->npix + 255) / 256, 2048);
-    hipLaunchKernelGGL(emba_reg_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_Gx, c->d_Gy, (long)c->npix, c->d_scalar + 1);
+    hipLaunchKernelGGL(emba_reg_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_Gx, c->d_Gy, (long)c->npix, c->d_scalar.as<double>() + 1);
     double v = 0;
-    HIP_TRY(c, hipMemcpyAsync(&v, c->d_scalar + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&v, c->d_scalar.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     *cost = 0.5 * alpha * v;
     return EMBA_OK;
@@ -2078,25 +2052,24 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     hipStream_t s = c->stream;
     // device and host staging only for what was asked for (a 100 M-event pm dump is 1.6 GB, the full state 17 GB)
     const bool w_pm = pm, w_D = D, w_dp = dp, w_G = Gpm, w_t = temp, w_pi = pm_int, w_inl = inlier_idx, w_flag = inlier_idx || pm_int || Gpm || temp;
-    double *d_pm = nullptr, *d_D = nullptr, *d_dp = nullptr, *d_G = nullptr, *d_t = nullptr; int32_t* d_pi = nullptr;
-    auto free_all = [&]() { dev_free(c, d_pm); dev_free(c, d_D); dev_free(c, d_dp); dev_free(c, d_G); dev_free(c, d_t); dev_free(c, d_pi); };
+    DevBuf b_pm, b_D, b_dp, b_G, b_t, b_pi;      // (per call)
     emba_status st = EMBA_OK;
-    if ((w_pm && (st = dev_alloc(c, &d_pm, 2 * ns))) || (w_D && (st = dev_alloc(c, &d_D, 12 * ns))) || (w_dp && (st = dev_alloc(c, &d_dp, 2 * ns))) ||
-        (w_G && (st = dev_alloc(c, &d_G, 2 * ns))) || (w_t && (st = dev_alloc(c, &d_t, 2 * ns))) || (w_pi && (st = dev_alloc(c, &d_pi, 2 * ns)))) {
-        free_all();
+    if ((w_pm && (st = ensure<double>(c, b_pm, 2 * ns))) || (w_D && (st = ensure<double>(c, b_D, 12 * ns))) || (w_dp && (st = ensure<double>(c, b_dp, 2 * ns))) ||
+        (w_G && (st = ensure<double>(c, b_G, 2 * ns))) || (w_t && (st = ensure<double>(c, b_t, 2 * ns))) || (w_pi && (st = ensure<int32_t>(c, b_pi, 2 * ns))))
         return st;
-    }
+    double *d_pm = b_pm.as<double>(), *d_D = b_D.as<double>(), *d_dp = b_dp.as<double>(), *d_G = b_G.as<double>(), *d_t = b_t.as<double>();
+    int32_t* d_pi = b_pi.as<int32_t>();
     if (w_dp) (void)hipMemsetAsync(d_dp, 0, 2 * ns * 8, s);
     if (w_G) (void)hipMemsetAsync(d_G, 0, 2 * ns * 8, s);
     if (w_t) (void)hipMemsetAsync(d_t, 0, 2 * ns * 8, s);
     if (w_pi) (void)hipMemsetAsync(d_pi, 0xFF, 2 * ns * 4, s);
     WarpParams p{};
-    p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot; p.ev_pm = c->tile_order ? c->d_ev_pm : nullptr; p.n_sorted = (long)ns; p.nblk = c->nblk;
-    p.ev_u = c->d_ev_u; p.ev_seg = c->d_ev_seg;
-    p.pose = c->d_pose; p.seg = c->d_seg; p.lut = c->d_lut; p.texel = nullptr; p.rect_acc = nullptr; p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc;
+    p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)ns; p.nblk = c->nblk;
+    p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();
+    p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = nullptr; p.rect_acc = nullptr; p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc.as<double>();
     p.W = c->W; p.H = c->H; p.fx = c->fx; p.fy = c->fy; p.cx = c->cx;
-    p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px; p.count = c->d_count; p.rec = c->d_rec; p.e_sorted = c->d_e_sorted;
-    p.flag = c->d_flag; p.d_pm = d_pm; p.d_D = d_D; p.d_dp = d_dp; p.d_Gpm = d_G; p.d_temp = d_t; p.d_pm_int = d_pi;
+    p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px; p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.e_sorted = c->d_e_sorted.as<double>();
+    p.flag = c->d_flag.as<uint8_t>(); p.d_pm = d_pm; p.d_D = d_D; p.d_dp = d_dp; p.d_Gpm = d_G; p.d_temp = d_t; p.d_pm_int = d_pi;
     if (c->tile_order) hipLaunchKernelGGL((emba_warp_residual_kernel<true, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
     else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<true, false, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);   // (the last evaluation left segment records, not a pose table)
     else hipLaunchKernelGGL((emba_warp_residual_kernel<true, false>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
@@ -2110,11 +2083,10 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     if (w_G) (void)hipMemcpyAsync(h_G.data(), d_G, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_t) (void)hipMemcpyAsync(h_t.data(), d_t, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_pi) (void)hipMemcpyAsync(h_pi.data(), d_pi, 2 * ns * 4, hipMemcpyDeviceToHost, s);
-    if (w_inl) (void)hipMemcpyAsync(h_inl.data(), c->d_inl_idx, c->n_pm * 4, hipMemcpyDeviceToHost, s);
-    if (w_flag) (void)hipMemcpyAsync(h_flag.data(), c->d_flag, c->n_pm, hipMemcpyDeviceToHost, s);
-    if (cp_idx) (void)hipMemcpyAsync(h_cp.data(), c->d_cp, h_cp.size() * 2, hipMemcpyDeviceToHost, s);
+    if (w_inl) (void)hipMemcpyAsync(h_inl.data(), c->d_inl_idx.as<int32_t>(), c->n_pm * 4, hipMemcpyDeviceToHost, s);
+    if (w_flag) (void)hipMemcpyAsync(h_flag.data(), c->d_flag.as<uint8_t>(), c->n_pm, hipMemcpyDeviceToHost, s);
+    if (cp_idx) (void)hipMemcpyAsync(h_cp.data(), c->d_cp.as<uint16_t>(), h_cp.size() * 2, hipMemcpyDeviceToHost, s);
     hipError_t e = hipStreamSynchronize(s);
-    free_all();
     if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "dump_state: %s", hipGetErrorString(e));
     // pure re-indexing (pixel-major -> original time order); no arithmetic on the host
     if (cp_idx) for (size_t k = 0; k < n; ++k) cp_idx[k] = -1;
@@ -2129,8 +2101,8 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     std::vector<uint32_t> h_evpix(ns), h_evbatch(cp_idx ? ns : 0), h_evpm(c->have_ev_pm ? ns : 0), h_pmorig(c->n_pm);
     HIP_TRY(c, hipMemcpy(h_evpix.data(), c->d_ev_pix, ns * 4, hipMemcpyDeviceToHost));
     if (cp_idx) HIP_TRY(c, hipMemcpy(h_evbatch.data(), c->d_ev_batch, ns * 4, hipMemcpyDeviceToHost));
-    if (c->have_ev_pm) HIP_TRY(c, hipMemcpy(h_evpm.data(), c->d_ev_pm, ns * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(h_pmorig.data(), c->d_pm_orig, c->n_pm * 4, hipMemcpyDeviceToHost));
+    if (c->have_ev_pm) HIP_TRY(c, hipMemcpy(h_evpm.data(), c->d_ev_pm.as<uint32_t>(), ns * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h_pmorig.data(), c->d_pm_orig.as<uint32_t>(), c->n_pm * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ns; ++i) {
         if (h_evpix[i] & kEvLead) continue;                        // lead-in copy / halo
         const size_t f = c->have_ev_pm ? h_evpm[i] : i;           // pm-order index: where flag / inlier number of this entry live
@@ -2370,7 +2342,7 @@ emba_status emba_bracket_overhead_us(emba_ctx* c, int32_t reps, float* us)
     double sum = 0.0;
     for (int r = 0; r < reps; ++r) {
         // the bracket sits BEHIND queued work, like the brackets of a step: a busy kernel first, then event | empty kernel | event
-        hipLaunchKernelGGL(emba_clock_probe_kernel, dim3(1), dim3(64), 0, s, c->d_probe + 4, 256);
+        hipLaunchKernelGGL(emba_clock_probe_kernel, dim3(1), dim3(64), 0, s, c->d_probe.as<unsigned long long>() + 4, 256);
         HIP_TRY(c, hipEventRecord(c->cal_ev[0], s));
         hipLaunchKernelGGL(emba_empty_kernel, dim3(1), dim3(64), 0, s);
         HIP_TRY(c, hipEventRecord(c->cal_ev[1], s));
@@ -2399,11 +2371,11 @@ emba_status emba_clock_probe(emba_ctx* c, double* sclk_mhz_est, double* probe_us
     // every SIMD of the chip busy with one wave's dependent chain of kClockProbeOps fp32 adds (4 cycles each on a 16-lane SIMD, issued back to back)
     const int loops = 1024;
     HIP_TRY(c, hipEventRecord(c->cal_ev[0], s));
-    hipLaunchKernelGGL(emba_clock_probe_kernel, dim3((unsigned)c->n_cu), dim3(256), 0, s, c->d_probe, loops);
+    hipLaunchKernelGGL(emba_clock_probe_kernel, dim3((unsigned)c->n_cu), dim3(256), 0, s, c->d_probe.as<unsigned long long>(), loops);
     HIP_TRY(c, hipEventRecord(c->cal_ev[1], s));
     HIP_TRY(c, hipGetLastError());
     unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(h, c->d_probe, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h, c->d_probe.as<unsigned long long>(), sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     c->spun = false;
     float ms = 0.f;
@@ -2441,40 +2413,81 @@ emba_status pose_vector_lds(emba_ctx* c, const void* kernel, size_t bytes, const
     return EMBA_OK;
 }
 
+// The cached lists (lists.off, lists.sorted) as a SolveLists.
+SolveLists cached_lists(const emba_ctx* c)
+{
+    SolveLists L;
+    L.off = c->lists.off.as<uint32_t>();
+    L.sorted.rec = c->lists.sorted.as<const double>(); L.sorted.packed = 1; L.sorted.pix_base = 0;
+    return L;
+}
+
+// Hands the solve scratch (sv) and the lists cache to a solve.  A CG session (emba_cg_shard_*) holds them from begin to end: it ends here.
+emba_ctx::Solve& take_solve_scratch(emba_ctx* c)
+{
+    c->cg.active = false;
+    return c->sv;
+}
+
+// The CG vectors in the solve scratch: x, r, p, z, t, the inverse diagonal (n doubles each) and the device scalars
+struct CgVecs { double *x, *r, *p, *z, *t, *invd, *sc; };
+CgVecs cg_vectors(const emba_ctx* c)
+{
+    const auto& v = c->sv;
+    return {v.S_or_x.as<double>(), v.rhs_or_r.as<double>(), v.U_or_p.as<double>(), v.y_or_z.as<double>(), v.cf_or_t.as<double>(), v.x2_or_invd.as<double>(),
+            v.info_or_sc.as<double>()};
+}
+emba_status ensure_cg_vectors(emba_ctx* c, size_t n)
+{
+    auto& v = take_solve_scratch(c);
+    emba_status st;
+    for (DevBuf* b : {&v.S_or_x, &v.rhs_or_r, &v.U_or_p, &v.y_or_z, &v.cf_or_t, &v.x2_or_invd})
+        if ((st = ensure<double>(c, *b, n))) return st;
+    return ensure<double>(c, v.info_or_sc, 8);
+}
+
+// An emba_cg_shard_* call after begin: the session must still hold the solve scratch.  The call releases it and takes it back when it succeeds, so that a
+// failure ends the session.
+emba_status cg_resume(emba_ctx* c)
+{
+    if (!c->cg.active) return fail(c, EMBA_ERR_STATE, "no CG session: call emba_cg_shard_begin (a solve on this context, or a failed emba_cg_shard_* call, ends one)");
+    c->cg.active = false;
+    return EMBA_OK;
+}
+
 // per-pixel record lists over `n_pix` pixels of `view` (n_rec records): counts from the records themselves, exclusive scan, fill.
-// Workspaces 0 (off), 1 (cursor), 33 (the records in pixel order).
+// Into the lists cache: off, cursor, sorted (the records in pixel order).
 emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n_pix, SolveLists* out)
 {
     hipStream_t s = c->stream;
-    uint32_t *d_off = nullptr, *d_cursor = nullptr; double* d_sorted = nullptr;
     emba_status st;
-    const uint32_t key_stamp = view.packed ? c->set_stamp : view.stamp;
-    if (c->lists_valid && c->lists_packed == (view.packed != 0) && c->lists_stamp == key_stamp && c->lists_P == n_pix && c->lists_nrec == n_rec && c->ws[0].p && c->ws[33].p &&
+    const uint32_t key_stamp = view.packed ? c->work.stamp : view.stamp;
+    if (c->lists_valid && c->lists_packed == (view.packed != 0) && c->lists_stamp == key_stamp && c->lists_P == n_pix && c->lists_nrec == n_rec &&
         (!view.packed || c->lists_lo == view.pix_base)) {
-        out->off = (uint32_t*)c->ws[0].p;
-        out->sorted = RecView{};
-        out->sorted.rec = (const double*)c->ws[33].p; out->sorted.packed = 1; out->sorted.pix_base = 0;
+        *out = cached_lists(c);
         return EMBA_OK;
     }
     if (view.packed && !view.rec) return fail(c, EMBA_ERR_STATE, "the received records of these equations are not cached on this rank: run the record exchange (emba_solve_shard_cached says when it can be skipped)");
     c->lists_valid = false; c->perm_valid = false;
-    if ((st = ws_get(c, 0, (n_pix + 2) * 4, (void**)&d_off)) || (st = ws_get(c, 1, (n_pix + 1) * 4, (void**)&d_cursor)) ||
-        (st = ws_get(c, 33, (n_rec + 1) * kRecStride * sizeof(double), (void**)&d_sorted)))
+    if ((st = ensure<uint32_t>(c, c->lists.off, n_pix + 2)) || (st = ensure<uint32_t>(c, c->lists.cursor, n_pix + 1)) ||
+        (st = ensure<double>(c, c->lists.sorted, (n_rec + 1) * kRecStride)))
         return st;
+    uint32_t *d_off = c->lists.off.as<uint32_t>(), *d_cursor = c->lists.cursor.as<uint32_t>();
+    double* d_sorted = c->lists.sorted.as<double>();
     // list lengths: from the context's own count map while it still belongs to the evaluation that wrote these records (count_stamp), else counted
     // from the records (all-reduced / saturated / externally bound counts, a trial evaluation since, the sharded solve's received records)
     const int cmap_env = c->opt_solve_counts;      // option solve_counts — 0: always from the records; 2: both, compared (diagnostic)
-    const bool from_map = cmap_env != 0 && !view.packed && c->count_stamp != 0 && c->count_stamp == view.stamp && c->d_count == c->d_count_own && n_pix == c->P && n_pix;
+    const bool from_map = cmap_env != 0 && !view.packed && c->count_stamp != 0 && c->count_stamp == view.stamp && c->d_count == c->d_count_own.as<int32_t>() && n_pix == c->P && n_pix;
     if (from_map && cmap_env != 2) {
-        hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active, c->d_count, (long)n_pix, d_cursor);
+        hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_count, (long)n_pix, d_cursor);
     } else {
         HIP_TRY(c, hipMemsetAsync(d_cursor, 0, (n_pix + 1) * 4, s));
         if (n_rec) hipLaunchKernelGGL(emba_csr_count_kernel, dim3(nblocks(n_rec)), dim3(256), 0, s, view, (long)n_rec, d_cursor);
         if (from_map) {      // diagnostic: the two must agree
             std::vector<uint32_t> a(n_pix), b(n_pix);
-            uint32_t* d_tmp = nullptr;
-            if ((st = ws_get(c, 38, n_pix * 4, (void**)&d_tmp))) return st;
-            hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active, c->d_count, (long)n_pix, d_tmp);
+            if ((st = ensure<uint32_t>(c, c->lists.tmp, n_pix))) return st;
+            uint32_t* d_tmp = c->lists.tmp.as<uint32_t>();
+            hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_count, (long)n_pix, d_tmp);
             HIP_TRY(c, hipMemcpyAsync(a.data(), d_cursor, n_pix * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipMemcpyAsync(b.data(), d_tmp, n_pix * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(c, hipStreamSynchronize(s));
@@ -2488,15 +2501,13 @@ emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n
     // the participating records, copied into pixel order (the passes over them — U build, x2, every CG iteration — then stream)
     if (n_rec) hipLaunchKernelGGL(emba_csr_fill_sorted_kernel, dim3(nblocks(n_rec, 32)), dim3(256), 0, s, view, (long)n_rec, d_off, d_cursor, d_sorted);
     HIP_TRY(c, hipGetLastError());
-    out->off = d_off;
-    out->sorted = RecView{};
-    out->sorted.rec = d_sorted; out->sorted.packed = 1; out->sorted.pix_base = 0;
+    *out = cached_lists(c);
     c->lists_valid = true; c->lists_packed = view.packed != 0; c->lists_stamp = key_stamp; c->lists_P = n_pix; c->lists_nrec = n_rec; c->lists_lo = view.pix_base;
     return EMBA_OK;
 }
 
 // S_aug (lds x (n+1), zero or pre-initialised) -= U_aug U_aug^T over the pixels [0, n_pix) of the lists; A22b2 points at the first of
-// those pixels' {xx xy yy bx by}.  Also leaves y = C^-1 b2 (d_y) and the 2x2 Cholesky factors (d_cf).  Workspaces 8 (U), 12 (slabs).
+// those pixels' {xx xy yy bx by}.  Also leaves y = C^-1 b2 (d_y) and the 2x2 Cholesky factors (d_cf).  Scratch: sv.U_or_p (U), sv.slab, the SYRK lists.
 bool axis_path(const emba_ctx* c, double* path_az_out, double* path_el_out);
 
 emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists& L, size_t n_pix, const double* A22b2, double lambda, int n,
@@ -2509,9 +2520,10 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::max<size_t>(n_pix, 1), (size_t)(6ull << 30) / (16ull * (size_t)lds_)));   // <= 6 GB of U
     const int nb64 = (n + 63) / 64, nbp = nb64 * (nb64 + 1) / 2;
     const int nks_max = std::max(1, (4 * c->n_cu + nbp - 1) / nbp);   // enough (tile pair, K slab) blocks to fill the chip ...
-    double *d_U = nullptr, *d_slab = nullptr;
+    auto& sv = c->sv;
     emba_status st;
-    if ((st = ws_get(c, 8, (size_t)lds_ * 2 * chunk * 8, (void**)&d_U)) || (st = ws_get(c, 12, (size_t)nks_max * nbp * 4096 * 8, (void**)&d_slab))) return st;
+    if ((st = ensure<double>(c, sv.U_or_p, (size_t)lds_ * 2 * chunk)) || (st = ensure<double>(c, sv.slab, (size_t)nks_max * nbp * 4096))) return st;
+    double* d_U = sv.U_or_p.as<double>();
     SchurBuildParams bp{};
     bp.view = view; bp.off = L.off; bp.A22b2 = A22b2; bp.lambda = lambda;
     bp.irls = c->irls; bp.eta = c->eta; bp.n = n; bp.U = d_U; bp.ldu = lds_; bp.yv = d_y; bp.cfac = d_cf; bp.info = d_info;
@@ -2529,13 +2541,14 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
         bp.p0 = (long)p0; bp.p1 = (long)p1;
         const long kc = (long)(2 * (p1 - p0));
         const int n_slices = (int)((p1 - p0 + kSyrkSlicePix - 1) / kSyrkSlicePix);
-        unsigned long long* d_mask = nullptr; uint32_t *d_list = nullptr, *d_cnt = nullptr; uint16_t* d_range = nullptr;
-        if ((st = ws_get(c, 32, (p1 - p0 + 8) * 2, (void**)&d_range))) return st;
+        if ((st = ensure<uint16_t>(c, sv.range, p1 - p0 + 8))) return st;
+        uint16_t* d_range = sv.range.as<uint16_t>();
         bp.range = d_range;
+        unsigned long long* d_mask = nullptr; uint32_t *d_list = nullptr, *d_cnt = nullptr;
         if (sparse) {
-            if ((st = ws_get(c, 3, (size_t)n_slices * 8, (void**)&d_mask)) || (st = ws_get(c, 4, (size_t)nbp * n_slices * 4, (void**)&d_list)) ||
-                (st = ws_get(c, 5, (size_t)nbp * 4, (void**)&d_cnt)))
+            if ((st = ensure<unsigned long long>(c, sv.mask, n_slices)) || (st = ensure<uint32_t>(c, sv.list, (size_t)nbp * n_slices)) || (st = ensure<uint32_t>(c, sv.cnt, nbp)))
                 return st;
+            d_mask = sv.mask.as<unsigned long long>(); d_list = sv.list.as<uint32_t>(); d_cnt = sv.cnt.as<uint32_t>();
             HIP_TRY(c, hipMemsetAsync(d_mask, 0, (size_t)n_slices * 8, s));
         }
         bp.slice_mask = d_mask;
@@ -2544,7 +2557,7 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
         // ... and whole rounds of one block per CU: 268 blocks of 512 columns on 256 CUs (K = 21, 137 k columns) took 57 us, 255 blocks of 536 columns 44 us
         if ((long)nbp * nks > c->n_cu) nks = (int)std::max<long>(1, ((long)nbp * nks / c->n_cu) * c->n_cu / nbp);
         SyrkParams sp{};
-        sp.A = d_U; sp.lda = lds_; sp.n = n; sp.k = kc; sp.C = d_S; sp.ldc = lds_; sp.slab = d_slab; sp.nbp = nbp; sp.range = d_range;
+        sp.A = d_U; sp.lda = lds_; sp.n = n; sp.k = kc; sp.C = d_S; sp.ldc = lds_; sp.slab = sv.slab.as<double>(); sp.nbp = nbp; sp.range = d_range;
         // Where it pays: a BANDED U — a pixel is in view for the fraction fov / (path of the optical axis over the window) of the control poses, and an operand block
         // is read once per pair of its band.  With a dense band (every pixel sees the whole window: 1 s at any K) there is nothing to re-use that the lists form does
         // not get from its longer runs (measured: 10 M events / K = 97 over 1 s 3.14 vs 3.38 ms per solve, 1 M / K = 201 over 1 s 2.5 vs 2.75; config 2's shape, 10 s:
@@ -2568,11 +2581,11 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
             item_chunk = (int)std::min<long>(64, std::max<long>(4, ((long)n_slices * pairs_est * 3 / 2 + 2999) / 3000));
             n_item_chunks = (n_slices + item_chunk - 1) / item_chunk;
             if (n_item_chunks > 65535 || nbp > 65535) return fail(c, EMBA_ERR_CAPACITY, "too many slice chunks for the item form of the block-sparse product");
-            double* d_slab2 = nullptr;
-            if ((st = ws_get(c, 12, std::max<size_t>((size_t)nks_max * nbp, item_cap) * 4096 * 8, (void**)&d_slab2)) ||
-                (st = ws_get(c, 37, (size_t)nbp * n_item_chunks * 4, (void**)&d_pair_items)) || (st = ws_get(c, 39, ((size_t)nbp * n_item_chunks + 2) * 4, (void**)&d_items)))
+            if ((st = ensure<double>(c, sv.slab, std::max<size_t>((size_t)nks_max * nbp, item_cap) * 4096)) ||
+                (st = ensure<uint32_t>(c, sv.pair_items, (size_t)nbp * n_item_chunks)) || (st = ensure<uint32_t>(c, sv.items, (size_t)nbp * n_item_chunks + 2)))
                 return st;
-            sp.slab = d_slab2;
+            d_pair_items = sv.pair_items.as<uint32_t>(); d_items = sv.items.as<uint32_t>();
+            sp.slab = sv.slab.as<double>();
         }
         sp.direct = (nks == 1);
         if (c->opt_solve_debug) {      // diagnostic: how sparse is this chunk?  (products = (block pair, slice) pairs the SYRK forms)
@@ -2613,7 +2626,7 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
         hipLaunchKernelGGL(emba_syrk_kernel, dim3(nbp, nks), dim3(256), 0, s, sp);
         if (nks > 1)
             hipLaunchKernelGGL(emba_syrk_reduce_kernel, dim3((unsigned)(((size_t)nbp * 4096 + 255) / 256), (unsigned)((nks + kSyrkReduceGroup - 1) / kSyrkReduceGroup)),
-                               dim3(256), 0, s, d_slab, nks, nbp, n, d_S, lds_);
+                               dim3(256), 0, s, sp.slab, nks, nbp, n, d_S, lds_);
     }
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
@@ -2651,7 +2664,7 @@ emba_status schur_factor_solve(emba_ctx* c, double* d_S, long lds_, int n, int s
 }
 
 // The column order of U for the local solve (emba_perm_keys_kernel): panorama columns first when the camera mostly pans (azimuth path of the optical axis
-// over the control poses >= its elevation path), the compact order (nullptr) otherwise.  Built once per list build; workspaces 34-36.
+// over the control poses >= its elevation path), the compact order (nullptr) otherwise.  Built once per list build; scratch sv.perm_cnt, perm_tick, perm.
 // azimuth / elevation path length (rad) of the optical axis over the control poses of the last evaluation (the host's pinned copy)
 bool axis_path(const emba_ctx* c, double* path_az_out, double* path_el_out)
 {
@@ -2676,31 +2689,32 @@ emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo =
     // 10 M events over 10 s) 3.96 / 4.16 ms — SYRK 1.25 / 1.52, 5.8 / 7.9 products per slice —; 10 M events at K = 97: 2.81 / 2.79; 1 M events over 1 s at
     // K = 201 (every pixel sees the whole window: nothing to gain) 2.27 / 2.24.  From six row blocks (K >= 128) up, unless option solve_perm forces it.
     if (c->solve_perm_mode == 0 || P < 4 * (size_t)kSyrkSlicePix || (c->solve_perm_mode < 0 && 3 * c->K < 384) || 3 * c->K < 256) return EMBA_OK;
-    if (c->perm_valid && c->perm_lo == lo && c->perm_n == P) { *perm = c->d_perm; return EMBA_OK; }
+    if (c->perm_valid && c->perm_lo == lo && c->perm_n == P) { *perm = c->sv.perm.as<uint32_t>(); return EMBA_OK; }
     if (c->solve_perm_mode < 0) {
         double path_az = 0.0, path_el = 0.0;
         if (!axis_path(c, &path_az, &path_el)) return EMBA_OK;
         if (path_az < path_el) return EMBA_OK;      // mostly tilting: a panorama row is the better slice already
     }
     hipStream_t s = c->stream;
-    uint32_t *d_cnt = nullptr, *d_tick = nullptr, *d_pm = nullptr;
+    auto& sv = c->sv;
     emba_status st;
-    if ((st = ws_get(c, 34, ((size_t)c->W + 2) * 4, (void**)&d_cnt)) || (st = ws_get(c, 35, P * 4, (void**)&d_tick)) || (st = ws_get(c, 36, P * 4, (void**)&d_pm))) return st;
+    c->perm_valid = false;
+    if ((st = ensure<uint32_t>(c, sv.perm_cnt, (size_t)c->W + 2)) || (st = ensure<uint32_t>(c, sv.perm_tick, P)) || (st = ensure<uint32_t>(c, sv.perm, P))) return st;
+    uint32_t *d_cnt = sv.perm_cnt.as<uint32_t>(), *d_tick = sv.perm_tick.as<uint32_t>(), *d_pm = sv.perm.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, ((size_t)c->W + 1) * 4, s));
-    hipLaunchKernelGGL(emba_perm_ticket_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active + lo, (long)P, c->W, d_cnt, d_tick);
+    hipLaunchKernelGGL(emba_perm_ticket_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active.as<uint32_t>() + lo, (long)P, c->W, d_cnt, d_tick);
     if ((st = dev_scan(c, d_cnt, d_cnt, (size_t)c->W, nullptr))) return st;
-    hipLaunchKernelGGL(emba_perm_place_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active + lo, (long)P, c->W, d_cnt, d_tick, d_pm);
+    hipLaunchKernelGGL(emba_perm_place_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active.as<uint32_t>() + lo, (long)P, c->W, d_cnt, d_tick, d_pm);
     HIP_TRY(c, hipGetLastError());
-    uint32_t* v0 = d_pm;
-    c->d_perm = v0; c->perm_valid = true; c->perm_lo = lo; c->perm_n = P;
-    *perm = v0;
+    c->perm_valid = true; c->perm_lo = lo; c->perm_n = P;
+    *perm = d_pm;
     return EMBA_OK;
 }
 
 RecView local_view(emba_ctx* c)
 {
     RecView v{};
-    v.rec = c->d_rec; v.slot_key = c->d_slot_key; v.compact = c->d_compact; v.stamp = c->set_stamp; v.packed = 0; v.pix_base = 0;
+    v.rec = c->work.rec.as<double>(); v.slot_key = c->d_slot_key.as<uint32_t>(); v.compact = c->d_compact.as<int32_t>(); v.stamp = c->work.stamp; v.packed = 0; v.pix_base = 0;
     return v;
 }
 
@@ -2721,11 +2735,12 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
     if (n - skip <= 0) return fail(c, EMBA_ERR_INVALID_ARG, "nothing to solve for");
     const int na = n + 1;                              // augmented: row n carries y / the right-hand side
     const long lds_ = (na + 15) / 16 * 16;             // leading dimension of S_aug and of U
-    double *d_S = nullptr, *d_rhs = nullptr, *d_y = nullptr, *d_cf = nullptr, *d_x2 = nullptr;
-    int* d_info = nullptr;
-    if ((st = ws_get(c, 6, (size_t)lds_ * na * 8, (void**)&d_S)) || (st = ws_get(c, 7, (size_t)n * 8, (void**)&d_rhs)) || (st = ws_get(c, 9, 2 * (P + 1) * 8, (void**)&d_y)) ||
-        (st = ws_get(c, 10, 3 * (P + 1) * 8, (void**)&d_cf)) || (st = ws_get(c, 11, 2 * (P + 1) * 8, (void**)&d_x2)) || (st = ws_get(c, 13, 4, (void**)&d_info)))
+    auto& sv = take_solve_scratch(c);
+    if ((st = ensure<double>(c, sv.S_or_x, (size_t)lds_ * na)) || (st = ensure<double>(c, sv.rhs_or_r, n)) || (st = ensure<double>(c, sv.y_or_z, 2 * (P + 1))) ||
+        (st = ensure<double>(c, sv.cf_or_t, 3 * (P + 1))) || (st = ensure<double>(c, sv.x2_or_invd, 2 * (P + 1))) || (st = ensure<int>(c, sv.info_or_sc, 1)))
         return st;
+    double *d_S = sv.S_or_x.as<double>(), *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>(), *d_x2 = sv.x2_or_invd.as<double>();
+    int* d_info = sv.info_or_sc.as<int>();
     if ((st = ensure_compact(c))) return st;
     HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
     HIP_TRY(c, hipMemsetAsync(d_S, 0, (size_t)lds_ * na * sizeof(double), s));
@@ -2786,8 +2801,9 @@ extern "C" emba_status emba_solve_shard_count(emba_ctx* c, int32_t n_ranks, size
     if (st) return st;
     if ((st = ensure_compact(c))) return st;
     hipStream_t s = c->stream;
-    unsigned long long* d_cnt = nullptr;
-    if ((st = ws_get(c, 14, (size_t)3 * n_ranks * 8 + 8, (void**)&d_cnt))) return st;
+    auto& sv = take_solve_scratch(c);
+    if ((st = ensure<unsigned long long>(c, sv.shard_cnt, (size_t)3 * n_ranks + 1))) return st;
+    unsigned long long* d_cnt = sv.shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, (size_t)3 * n_ranks * 8 + 8, s));
     if (c->n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->P, (int)n_ranks, d_cnt);
     std::vector<unsigned long long> h(n_ranks);
@@ -2804,10 +2820,10 @@ extern "C" emba_status emba_solve_shard_count(emba_ctx* c, int32_t n_ranks, size
 extern "C" emba_status emba_solve_shard_pack(emba_ctx* c, int32_t n_ranks, double* send_dev)
 {
     if (!c || n_ranks < 1 || n_ranks > kShardMaxRanks) return EMBA_ERR_INVALID_ARG;
-    if (!c->ws[14].p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_count first");
+    if (!c->sv.shard_cnt.p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_count first");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    unsigned long long* d_cnt = (unsigned long long*)c->ws[14].p;
+    unsigned long long* d_cnt = take_solve_scratch(c).shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt + 2 * n_ranks, 0, (size_t)n_ranks * 8, s));
     if (c->n_cand && send_dev)
         hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->P, (int)n_ranks, d_cnt + n_ranks,
@@ -2827,8 +2843,8 @@ extern "C" emba_status emba_solve_shard_cached(emba_ctx* c, int32_t rank, int32_
     if (!c || !cached || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_cached: bad arguments") : EMBA_ERR_INVALID_ARG;
     size_t lo, hi;
     shard_range(c->P, rank, n_ranks, &lo, &hi);
-    *cached = (c->finish_done && !c->eq_in_alt && c->lists_valid && c->lists_packed && c->lists_stamp == c->set_stamp && c->lists_P == hi - lo && c->lists_lo == (long)lo &&
-               c->ws[0].p && c->ws[33].p && c->ws[9].p) ? 1 : 0;
+    *cached = (c->finish_done && !c->eq_in_alt && c->lists_valid && c->lists_packed && c->lists_stamp == c->work.stamp && c->lists_P == hi - lo && c->lists_lo == (long)lo &&
+               c->sv.y_or_z.p) ? 1 : 0;
     if (n_recv) *n_recv = *cached ? c->lists_nrec : 0;
     return EMBA_OK;
 }
@@ -2845,9 +2861,11 @@ extern "C" emba_status emba_solve_shard_partial(emba_ctx* c, int32_t rank, int32
     size_t lo, hi;
     shard_range(c->P, rank, n_ranks, &lo, &hi);
     const size_t n_pix = hi - lo;
-    double *d_y = nullptr, *d_cf = nullptr; int* d_info = nullptr;
+    auto& sv = take_solve_scratch(c);
     emba_status st;
-    if ((st = ws_get(c, 9, 2 * (n_pix + 1) * 8, (void**)&d_y)) || (st = ws_get(c, 10, 3 * (n_pix + 1) * 8, (void**)&d_cf)) || (st = ws_get(c, 13, 64, (void**)&d_info))) return st;
+    if ((st = ensure<double>(c, sv.y_or_z, 2 * (n_pix + 1))) || (st = ensure<double>(c, sv.cf_or_t, 3 * (n_pix + 1))) || (st = ensure<int>(c, sv.info_or_sc, 16))) return st;
+    double *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
+    int* d_info = sv.info_or_sc.as<int>();
     HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
     HIP_TRY(c, hipMemsetAsync(S_part_dev, 0, (size_t)lds_ * na * sizeof(double), s));
     RecView view{};
@@ -2863,7 +2881,7 @@ extern "C" emba_status emba_solve_shard_finish(emba_ctx* c, int32_t rank, int32_
                                                int32_t fix_first_pose, double* S_dev, double* x1_host, double* x2_full_dev)
 {
     if (!c || !S_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_finish: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->ws[0].p || !c->ws[9].p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_partial first");
+    if (!c->lists.off.p || !c->sv.y_or_z.p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_partial first");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int n = 3 * c->K, na = n + 1, skip = fix_first_pose ? 3 : 0;
@@ -2871,20 +2889,19 @@ extern "C" emba_status emba_solve_shard_finish(emba_ctx* c, int32_t rank, int32_
     size_t lo, hi;
     shard_range(c->P, rank, n_ranks, &lo, &hi);
     const size_t n_pix = hi - lo;
-    double* d_rhs = nullptr;
+    auto& sv = take_solve_scratch(c);
     emba_status st;
-    if ((st = ws_get(c, 7, (size_t)n * 8, (void**)&d_rhs))) return st;
-    int* d_info = (int*)c->ws[13].p;
-    double* d_y = (double*)c->ws[9].p; double* d_cf = (double*)c->ws[10].p;
+    if ((st = ensure<double>(c, sv.rhs_or_r, n))) return st;
+    double *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
+    int* d_info = sv.info_or_sc.as<int>();
     hipLaunchKernelGGL(emba_schur_add_a11_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, S_dev, lds_);
     if ((st = schur_factor_solve(c, S_dev, lds_, n, skip, d_rhs, d_info))) return st;
     if (x2_full_dev) {
         HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->P * sizeof(double), s));
-        RecView view{};       // the received records in pixel order, as emba_solve_shard_partial's build_lists left them
-        view.rec = (const double*)c->ws[33].p; view.packed = 1; view.pix_base = 0;
+        const SolveLists L = cached_lists(c);      // the received records in pixel order, as emba_solve_shard_partial's build_lists left them
         if ((st = pose_vector_lds(c, (const void*)emba_schur_x2_kernel, (size_t)n * sizeof(double), "solveNormalEq (x2)"))) return st;
         if (n_pix)
-            hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), s, view, (const uint32_t*)c->ws[0].p,
+            hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), s, L.sorted, L.off,
                                d_y, d_cf, d_rhs, c->irls, c->eta, (long)n_pix, x2_full_dev + 2 * lo, n);
     }
     HIP_TRY(c, hipGetLastError());
@@ -2913,11 +2930,9 @@ extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32
     const size_t P = c->P, M = c->n_cand, N = (size_t)n + 2 * P;
     if (max_iter <= 0) max_iter = 100;     // model.cpp:823-824
     if (!(tol > 0)) tol = 1e-6;
-    double *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_z = nullptr, *d_t = nullptr, *d_invd = nullptr, *d_sc = nullptr;
-    if ((st = ws_get(c, 6, N * 8, (void**)&d_x)) || (st = ws_get(c, 7, N * 8, (void**)&d_r)) || (st = ws_get(c, 8, N * 8, (void**)&d_p)) ||
-        (st = ws_get(c, 9, N * 8, (void**)&d_z)) || (st = ws_get(c, 10, N * 8, (void**)&d_t)) || (st = ws_get(c, 11, N * 8, (void**)&d_invd)) ||
-        (st = ws_get(c, 13, 64, (void**)&d_sc)))
-        return st;
+    if ((st = ensure_cg_vectors(c, N))) return st;
+    const CgVecs v = cg_vectors(c);
+    double *d_x = v.x, *d_r = v.r, *d_p = v.p, *d_z = v.z, *d_t = v.t, *d_invd = v.invd, *d_sc = v.sc;
     if ((st = ensure_compact(c))) return st;
     const RecView view = local_view(c);
     SolveLists L;
@@ -3012,23 +3027,21 @@ extern "C" emba_status emba_cg_shard_begin(emba_ctx* c, int32_t rank, int32_t n_
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     auto& g = c->cg;
-    g.active = false;
     g.rank = rank; g.n_ranks = n_ranks; g.n = 3 * c->K; g.skip = fix_first_pose ? 3 : 0; g.lambda = lambda;
     size_t lo, hi;
     shard_range(c->P, rank, n_ranks, &lo, &hi);
     g.lo = lo; g.npix = hi - lo; g.Nl = (size_t)g.n + 2 * g.npix;
     emba_status st;
-    if ((st = ws_get(c, 6, g.Nl * 8, (void**)&g.x)) || (st = ws_get(c, 7, g.Nl * 8, (void**)&g.r)) || (st = ws_get(c, 8, g.Nl * 8, (void**)&g.p)) ||
-        (st = ws_get(c, 9, g.Nl * 8, (void**)&g.z)) || (st = ws_get(c, 10, g.Nl * 8, (void**)&g.t)) || (st = ws_get(c, 11, g.Nl * 8, (void**)&g.invd)) ||
-        (st = ws_get(c, 13, 64, (void**)&g.sc)))
-        return st;
+    if ((st = ensure_cg_vectors(c, g.Nl))) return st;
+    const CgVecs v = cg_vectors(c);
     RecView view{};
     view.rec = recv_dev; view.packed = 1; view.pix_base = (long)lo;
-    if ((st = build_lists(c, view, n_recv, g.npix, &g.L))) return st;
+    SolveLists L;
+    if ((st = build_lists(c, view, n_recv, g.npix, &L))) return st;
     if ((st = pose_vector_lds(c, (const void*)emba_cg_pixel_kernel, (size_t)g.n * 16, "solveNormalEqCG", 48))) return st;
     HIP_TRY(c, hipMemsetAsync(red_dev, 0, ((size_t)g.n + 2) * 8, s));
     const unsigned grid = (unsigned)std::min<size_t>(nblocks(g.Nl), 1024);
-    hipLaunchKernelGGL(emba_cg_init_kernel, dim3(grid), dim3(256), 0, s, pack_A11(c), pack_b1(c), pack_A22b2(c) + 5 * lo, g.n, g.skip, (long)g.npix, lambda, g.x, g.r, g.p, g.invd,
+    hipLaunchKernelGGL(emba_cg_init_kernel, dim3(grid), dim3(256), 0, s, pack_A11(c), pack_b1(c), pack_A22b2(c) + 5 * lo, g.n, g.skip, (long)g.npix, lambda, v.x, v.r, v.p, v.invd,
                        red_dev + g.n, (long)(rank == 0 ? 0 : g.n));
     HIP_TRY(c, hipGetLastError());
     g.active = true;
@@ -3039,20 +3052,23 @@ extern "C" emba_status emba_cg_shard_apply(emba_ctx* c, double* red_dev)
 {
     if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
     auto& g = c->cg;
-    if (!g.active) return fail(c, EMBA_ERR_STATE, "call emba_cg_shard_begin first");
+    if (emba_status st = cg_resume(c)) return st;
+    const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int n = g.n;
-    if (g.rank == 0) hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, g.lambda, g.skip, g.p, g.t);
-    else HIP_TRY(c, hipMemsetAsync(g.t, 0, (size_t)n * 8, s));
+    if (g.rank == 0) hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, g.lambda, g.skip, v.p, v.t);
+    else HIP_TRY(c, hipMemsetAsync(v.t, 0, (size_t)n * 8, s));
     CgPixParams pp{};
-    pp.view = g.L.sorted; pp.off = g.L.off; pp.A22b2 = pack_A22b2(c) + 5 * g.lo; pp.lambda = g.lambda; pp.irls = c->irls; pp.eta = c->eta; pp.n = n; pp.skip = g.skip;
-    pp.P = (long)g.npix; pp.v = g.p; pp.y = g.t;
+    const SolveLists L = cached_lists(c);
+    pp.view = L.sorted; pp.off = L.off; pp.A22b2 = pack_A22b2(c) + 5 * g.lo; pp.lambda = g.lambda; pp.irls = c->irls; pp.eta = c->eta; pp.n = n; pp.skip = g.skip;
+    pp.P = (long)g.npix; pp.v = v.p; pp.y = v.t;
     if (g.npix) hipLaunchKernelGGL(emba_cg_pixel_kernel, dim3((unsigned)std::min<size_t>((g.npix + 3) / 4, (size_t)8 * c->n_cu)), dim3(256), (size_t)n * 16, s, pp);
-    HIP_TRY(c, hipMemcpyAsync(red_dev, g.t, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(red_dev, v.t, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemsetAsync(red_dev + n, 0, 16, s));
-    if (g.npix) hipLaunchKernelGGL(emba_cg_dot_kernel, dim3((unsigned)std::min<size_t>(nblocks(2 * g.npix), 1024)), dim3(256), 0, s, g.p + n, g.t + n, (long)(2 * g.npix), red_dev + n);
+    if (g.npix) hipLaunchKernelGGL(emba_cg_dot_kernel, dim3((unsigned)std::min<size_t>(nblocks(2 * g.npix), 1024)), dim3(256), 0, s, v.p + n, v.t + n, (long)(2 * g.npix), red_dev + n);
     HIP_TRY(c, hipGetLastError());
+    g.active = true;
     return EMBA_OK;
 }
 
@@ -3060,18 +3076,20 @@ extern "C" emba_status emba_cg_shard_pt(emba_ctx* c, const double* red_dev, doub
 {
     if (!c || !red_dev || !pt) return EMBA_ERR_INVALID_ARG;
     auto& g = c->cg;
-    if (!g.active) return fail(c, EMBA_ERR_STATE, "call emba_cg_shard_begin first");
+    if (emba_status st = cg_resume(c)) return st;
+    const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int n = g.n;
-    HIP_TRY(c, hipMemcpyAsync(g.t, red_dev, (size_t)n * 8, hipMemcpyDeviceToDevice, s));      // the reduced t1, identical on every rank
-    HIP_TRY(c, hipMemsetAsync(g.sc, 0, 16, s));
-    hipLaunchKernelGGL(emba_cg_dot_kernel, dim3(1), dim3(256), 0, s, g.p, g.t, (long)n, g.sc);     // (one block: the same summation order on every rank)
+    HIP_TRY(c, hipMemcpyAsync(v.t, red_dev, (size_t)n * 8, hipMemcpyDeviceToDevice, s));      // the reduced t1, identical on every rank
+    HIP_TRY(c, hipMemsetAsync(v.sc, 0, 16, s));
+    hipLaunchKernelGGL(emba_cg_dot_kernel, dim3(1), dim3(256), 0, s, v.p, v.t, (long)n, v.sc);     // (one block: the same summation order on every rank)
     double h[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(&h[0], g.sc, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&h[0], v.sc, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&h[1], red_dev + n, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     *pt = h[0] + h[1];
+    g.active = true;
     return EMBA_OK;
 }
 
@@ -3079,15 +3097,17 @@ extern "C" emba_status emba_cg_shard_update(emba_ctx* c, double alpha, double* r
 {
     if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
     auto& g = c->cg;
-    if (!g.active) return fail(c, EMBA_ERR_STATE, "call emba_cg_shard_begin first");
+    if (emba_status st = cg_resume(c)) return st;
+    const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const long from = g.rank == 0 ? 0 : g.n;
     const unsigned grid = (unsigned)std::min<size_t>(nblocks(g.Nl), 1024);
     HIP_TRY(c, hipMemsetAsync(red_dev + g.n, 0, 16, s));
-    hipLaunchKernelGGL(emba_cg_xr_kernel, dim3(grid), dim3(256), 0, s, alpha, g.p, g.t, (long)g.Nl, g.x, g.r, red_dev + g.n, from);
-    hipLaunchKernelGGL(emba_cg_z_kernel, dim3(grid), dim3(256), 0, s, g.invd, g.r, (long)g.Nl, g.z, red_dev + g.n + 1, from);
+    hipLaunchKernelGGL(emba_cg_xr_kernel, dim3(grid), dim3(256), 0, s, alpha, v.p, v.t, (long)g.Nl, v.x, v.r, red_dev + g.n, from);
+    hipLaunchKernelGGL(emba_cg_z_kernel, dim3(grid), dim3(256), 0, s, v.invd, v.r, (long)g.Nl, v.z, red_dev + g.n + 1, from);
     HIP_TRY(c, hipGetLastError());
+    g.active = true;
     return EMBA_OK;
 }
 
@@ -3095,10 +3115,12 @@ extern "C" emba_status emba_cg_shard_direction(emba_ctx* c, double beta)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     auto& g = c->cg;
-    if (!g.active) return fail(c, EMBA_ERR_STATE, "call emba_cg_shard_begin first");
+    if (emba_status st = cg_resume(c)) return st;
+    const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(emba_cg_p_kernel, dim3(nblocks(g.Nl)), dim3(256), 0, c->stream, beta, g.z, (long)g.Nl, g.p);
+    hipLaunchKernelGGL(emba_cg_p_kernel, dim3(nblocks(g.Nl)), dim3(256), 0, c->stream, beta, v.z, (long)g.Nl, v.p);
     HIP_TRY(c, hipGetLastError());
+    g.active = true;
     return EMBA_OK;
 }
 
@@ -3106,16 +3128,16 @@ extern "C" emba_status emba_cg_shard_end(emba_ctx* c, double* x1_host, double* x
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     auto& g = c->cg;
-    if (!g.active) return fail(c, EMBA_ERR_STATE, "call emba_cg_shard_begin first");
+    if (emba_status st = cg_resume(c)) return st;
+    const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     if (x2_full_dev) {
         HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->P * sizeof(double), s));
-        if (g.npix) HIP_TRY(c, hipMemcpyAsync(x2_full_dev + 2 * g.lo, g.x + g.n, 2 * g.npix * 8, hipMemcpyDeviceToDevice, s));
+        if (g.npix) HIP_TRY(c, hipMemcpyAsync(x2_full_dev + 2 * g.lo, v.x + g.n, 2 * g.npix * 8, hipMemcpyDeviceToDevice, s));
     }
-    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, g.x, (size_t)g.n * 8, hipMemcpyDeviceToHost, s));
+    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, v.x, (size_t)g.n * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    g.active = false;
     return EMBA_OK;
 }
 
@@ -3133,42 +3155,43 @@ extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_
     // option poisson = 1 (dense): both axes by sine-matrix products (four GEMMs: the round-1/2 form, kept for comparison); default: Fourier analysis
     // along H only + tridiagonal solves along W (poisson_kernels.h) — a third of the arithmetic, same solution to rounding.
     const bool dense = c->opt_poisson == 1;      // option poisson: 1 dense sine transforms, 2 no folding (comparison forms)
-    if (!c->d_SH) {   // first use: S_H, its eigenvalues, two scratch planes
-        if ((st = dev_alloc(c, &c->d_SH, (size_t)H * H)) || (st = dev_alloc(c, &c->d_lamH, (size_t)H)) || (st = dev_alloc(c, &c->d_pF, npix)) || (st = dev_alloc(c, &c->d_pT, npix))) {
-            dev_free(c, c->d_SH); dev_free(c, c->d_lamH); dev_free(c, c->d_pF); dev_free(c, c->d_pT);
-            return st;
-        }
-        hipLaunchKernelGGL(emba_sine_matrix_kernel, dim3((unsigned)(((size_t)H * H + 255) / 256)), dim3(256), 0, s, H, c->d_SH);
-        hipLaunchKernelGGL(emba_dirichlet_eigen_kernel, dim3((H + 255) / 256), dim3(256), 0, s, H, c->d_lamH);
+    // first use: S_H, its eigenvalues, two scratch planes (each set of constants is computed when the buffer it ends with is new)
+    bool fresh = false;
+    if ((st = ensure<double>(c, c->d_lamH, (size_t)H)) || (st = ensure<double>(c, c->d_pF, npix)) || (st = ensure<double>(c, c->d_pT, npix)) ||
+        (st = ensure<double>(c, c->d_SH, (size_t)H * H, &fresh)))
+        return st;
+    if (fresh) {
+        hipLaunchKernelGGL(emba_sine_matrix_kernel, dim3((unsigned)(((size_t)H * H + 255) / 256)), dim3(256), 0, s, H, c->d_SH.as<double>());
+        hipLaunchKernelGGL(emba_dirichlet_eigen_kernel, dim3((H + 255) / 256), dim3(256), 0, s, H, c->d_lamH.as<double>());
     }
-    if (dense && !c->d_SW) {
-        if ((st = dev_alloc(c, &c->d_SW, (size_t)W * W)) || (st = dev_alloc(c, &c->d_lamW, (size_t)W))) { dev_free(c, c->d_SW); dev_free(c, c->d_lamW); return st; }
-        hipLaunchKernelGGL(emba_sine_matrix_kernel, dim3((unsigned)(((size_t)W * W + 255) / 256)), dim3(256), 0, s, W, c->d_SW);
-        hipLaunchKernelGGL(emba_dirichlet_eigen_kernel, dim3((W + 255) / 256), dim3(256), 0, s, W, c->d_lamW);
+    if (dense && ((st = ensure<double>(c, c->d_lamW, (size_t)W)) || (st = ensure<double>(c, c->d_SW, (size_t)W * W, &fresh)))) return st;
+    if (dense && fresh) {
+        hipLaunchKernelGGL(emba_sine_matrix_kernel, dim3((unsigned)(((size_t)W * W + 255) / 256)), dim3(256), 0, s, W, c->d_SW.as<double>());
+        hipLaunchKernelGGL(emba_dirichlet_eigen_kernel, dim3((W + 255) / 256), dim3(256), 0, s, W, c->d_lamW.as<double>());
     }
-    if (!dense && !c->d_thomas) {   // Thomas factors of T_W + lambda1[i] I for every H-frequency i: W x H doubles, once
-        if ((st = dev_alloc(c, &c->d_thomas, npix))) return st;
-        hipLaunchKernelGGL(emba_thomas_coef_kernel, dim3((H + 63) / 64), dim3(64), 0, s, c->d_lamH, H, W, c->d_thomas);
+    if (!dense && (st = ensure<double>(c, c->d_thomas, npix, &fresh))) return st;
+    if (!dense && fresh) {   // Thomas factors of T_W + lambda1[i] I for every H-frequency i: W x H doubles, once
+        hipLaunchKernelGGL(emba_thomas_coef_kernel, dim3((H + 63) / 64), dim3(64), 0, s, c->d_lamH.as<double>(), H, W, c->d_thomas.as<double>());
     }
     const bool fold = !dense && (H % 2 == 0) && H >= 64 && c->opt_poisson != 2;
-    if (fold && !c->d_Sfold) {
-        if ((st = dev_alloc(c, &c->d_Sfold, (size_t)H * H / 2))) return st;
-        hipLaunchKernelGGL(emba_sine_folded_kernel, dim3((unsigned)(((size_t)H * H / 2 + 255) / 256)), dim3(256), 0, s, H, c->d_Sfold);
+    if (fold && (st = ensure<double>(c, c->d_Sfold, (size_t)H * H / 2, &fresh))) return st;
+    if (fold && fresh) {
+        hipLaunchKernelGGL(emba_sine_folded_kernel, dim3((unsigned)(((size_t)H * H / 2 + 255) / 256)), dim3(256), 0, s, H, c->d_Sfold.as<double>());
     }
     const double *gx = c->d_Gx, *gy = c->d_Gy;
     if (Gx_host) {
-        if (!c->d_pGx) { if ((st = dev_alloc(c, &c->d_pGx, npix)) || (st = dev_alloc(c, &c->d_pGy, npix))) { dev_free(c, c->d_pGx); return st; } }
-        HIP_TRY(c, hipMemcpyAsync(c->d_pGx, Gx_host, npix * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->d_pGy, Gy_host, npix * sizeof(double), hipMemcpyHostToDevice, s));
-        gx = c->d_pGx; gy = c->d_pGy;
+        if ((st = ensure<double>(c, c->d_pGx, npix)) || (st = ensure<double>(c, c->d_pGy, npix))) return st;
+        HIP_TRY(c, hipMemcpyAsync(c->d_pGx.as<double>(), Gx_host, npix * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_pGy.as<double>(), Gy_host, npix * sizeof(double), hipMemcpyHostToDevice, s));
+        gx = c->d_pGx.as<double>(); gy = c->d_pGy.as<double>();
     }
-    if (dense) hipLaunchKernelGGL(emba_divergence_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, gx, gy, H, W, c->d_pF);
+    if (dense) hipLaunchKernelGGL(emba_divergence_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, gx, gy, H, W, c->d_pF.as<double>());
     auto gemm = [&](const double* A, const double* B, double* C, int M, int N, int K, int epilogue, double inv_norm, long lda = 0, int a_kstride = 1, int a_koff = 0) {
         GemmParams p{};
         p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda ? lda : K; p.ldb = N; p.ldc = N;
         p.a_kstride = a_kstride; p.a_koff = a_koff;
         p.epilogue = epilogue; p.inv_norm = inv_norm;
-        p.lam1 = c->d_lamH; p.lam2 = c->d_lamW;
+        p.lam1 = c->d_lamH.as<double>(); p.lam2 = c->d_lamW.as<double>();
         p.vec = ((K & 1) == 0 && (N & 1) == 0) ? 1 : 0;
         const long tm = (M + kGemmBM - 1) / kGemmBM, wide = tm * ((N + 127) / 128), narrow = tm * ((N + 63) / 64);
         const long big = ((M + kGemmBM2 - 1) / kGemmBM2) * ((N + kGemmBN2 - 1) / kGemmBN2);
@@ -3180,40 +3203,40 @@ extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_
     if (dense) {
         // rhs -> eigenvector space, solve, back (laplace.cpp:633-758):  M = S_H ((S_H F S_W) o C) S_W
         const double inv_norm = 1.0 / (4.0 * ((double)(H + 1) * (double)(W + 1)));   // fft_norm, laplace.cpp:648
-        gemm(c->d_pF, c->d_SW, c->d_pT, H, W, W, 0, 1.0);            // T = F S_W
-        gemm(c->d_SH, c->d_pT, c->d_pF, H, W, H, 1, inv_norm);       // U = (S_H T / fft_norm) / (lambda1 + lambda2)
-        gemm(c->d_pF, c->d_SW, c->d_pT, H, W, W, 0, 1.0);            // T = U S_W
-        gemm(c->d_SH, c->d_pT, c->d_pF, H, W, H, 0, 1.0);            // M = S_H T
+        gemm(c->d_pF.as<double>(), c->d_SW.as<double>(), c->d_pT.as<double>(), H, W, W, 0, 1.0);            // T = F S_W
+        gemm(c->d_SH.as<double>(), c->d_pT.as<double>(), c->d_pF.as<double>(), H, W, H, 1, inv_norm);       // U = (S_H T / fft_norm) / (lambda1 + lambda2)
+        gemm(c->d_pF.as<double>(), c->d_SW.as<double>(), c->d_pT.as<double>(), H, W, W, 0, 1.0);            // T = U S_W
+        gemm(c->d_SH.as<double>(), c->d_pT.as<double>(), c->d_pF.as<double>(), H, W, H, 0, 1.0);            // M = S_H T
     } else {
         const dim3 tg((W + 31) / 32, (H + 31) / 32), tgT((H + 31) / 32, (W + 31) / 32);
         // DST-I along H of every row of the transposed plane: src (W x H) -> dst (W x H), times scale.  Folded (even H): two half-size products on
         // the even- and odd-indexed inputs + a butterfly; tmp holds [E | O] (W x H/2 each).
         // transposed_out: dst receives the result TRANSPOSED (H x W) — the folded form's butterfly writes it that way, saving the last transpose pass
         auto dst_rows = [&](const double* src, double* dst, double* tmp, double scale, bool transposed_out) -> bool {
-            if (!fold) { gemm(src, c->d_SH, dst, W, H, H, 2, scale); return false; }
+            if (!fold) { gemm(src, c->d_SH.as<double>(), dst, W, H, H, 2, scale); return false; }
             const int h = H / 2;
             double* E = tmp; double* O = tmp + (size_t)W * h;
-            gemm(src, c->d_Sfold, E, W, h, h, 0, 1.0, H, 2, 0);
-            gemm(src, c->d_Sfold + (size_t)h * h, O, W, h, h, 0, 1.0, H, 2, 1);
+            gemm(src, c->d_Sfold.as<double>(), E, W, h, h, 0, 1.0, H, 2, 0);
+            gemm(src, c->d_Sfold.as<double>() + (size_t)h * h, O, W, h, h, 0, 1.0, H, 2, 1);
             if (transposed_out) hipLaunchKernelGGL(emba_dst_butterfly_T_kernel, dim3((h + 31) / 32, (W + 31) / 32), dim3(256), 0, s, E, O, W, H, scale, dst);
             else hipLaunchKernelGGL(emba_dst_butterfly_kernel, dim3((unsigned)(((size_t)W * h + 255) / 256)), dim3(256), 0, s, E, O, W, H, scale, dst);
             return transposed_out;
         };
-        if (fold && !c->d_pE) { if ((st = dev_alloc(c, &c->d_pE, npix))) return st; }
-        hipLaunchKernelGGL(emba_divergence_T_kernel, tg, dim3(256), 0, s, gx, gy, H, W, c->d_pT);                     // F^T  (W x H), straight from the gradient maps
-        dst_rows(c->d_pT, c->d_pF, c->d_pE, 1.0, false);                                                                 // (S_H F)^T = F^T S_H
+        if (fold && (st = ensure<double>(c, c->d_pE, npix))) return st;
+        hipLaunchKernelGGL(emba_divergence_T_kernel, tg, dim3(256), 0, s, gx, gy, H, W, c->d_pT.as<double>());                     // F^T  (W x H), straight from the gradient maps
+        dst_rows(c->d_pT.as<double>(), c->d_pF.as<double>(), c->d_pE.as<double>(), 1.0, false);                                                                 // (S_H F)^T = F^T S_H
         const unsigned tb = (unsigned)((H + kTriSys - 1) / kTriSys);
-        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas, c->d_lamH, c->d_pF, H, W);   // (T_W + lambda1[i] I) x = g, per i
-        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas, c->d_lamH, c->d_pF, H, W);
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, W);   // (T_W + lambda1[i] I) x = g, per i
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, W);
         // M^T = X^T S_H / (2 (H+1)).  Folded: the butterfly writes M itself into d_pF (its input X^T is dead once E and O exist)
-        if (fold) dst_rows(c->d_pF, c->d_pF, c->d_pE, 1.0 / (2.0 * (double)(H + 1)), true);
+        if (fold) dst_rows(c->d_pF.as<double>(), c->d_pF.as<double>(), c->d_pE.as<double>(), 1.0 / (2.0 * (double)(H + 1)), true);
         else {
-            dst_rows(c->d_pF, c->d_pT, c->d_pE, 1.0 / (2.0 * (double)(H + 1)), false);
-            hipLaunchKernelGGL(emba_transpose_kernel, tgT, dim3(256), 0, s, c->d_pT, W, H, c->d_pF);                  // M
+            dst_rows(c->d_pF.as<double>(), c->d_pT.as<double>(), c->d_pE.as<double>(), 1.0 / (2.0 * (double)(H + 1)), false);
+            hipLaunchKernelGGL(emba_transpose_kernel, tgT, dim3(256), 0, s, c->d_pT.as<double>(), W, H, c->d_pF.as<double>());                  // M
         }
     }
     HIP_TRY(c, hipGetLastError());
-    if (M_host) HIP_TRY(c, hipMemcpyAsync(M_host, c->d_pF, npix * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (M_host) HIP_TRY(c, hipMemcpyAsync(M_host, c->d_pF.as<double>(), npix * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     c->spun = false; c->knots_in_flight = false;
     return EMBA_OK;
@@ -3233,26 +3256,26 @@ void robust_ranks(size_t n, double pct, unsigned int k[2])
 }
 
 // rmin / rmax of every plane (n values each, device memory) by the radix select of render_kernels.h — 6 launches, no host round trip; with hsv
-// (planes = Gx, Gy) also the min / max of 0.5*angle and of the magnitude.  Results stay in c->d_rstate.
+// (planes = Gx, Gy) also the min / max of 0.5*angle and of the magnitude.  Results stay in c->d_rstate.as<RenderState>().
 emba_status robust_select(emba_ctx* c, const double* const* planes, int nplanes, size_t n, double pct, bool hsv)
 {
     hipStream_t s = c->stream;
     emba_status st;
     bool fresh_st = false, fresh_h = false;
-    if ((st = dev_alloc(c, &c->d_rstate, 1, &fresh_st)) || (st = dev_alloc(c, &c->d_rhist, (size_t)kRselSlots * kRselBins, &fresh_h)) ||
-        (st = dev_alloc(c, &c->d_rcand, (size_t)nplanes * n)))
+    if ((st = ensure<RenderState>(c, c->d_rstate, 1, &fresh_st)) || (st = ensure<unsigned int>(c, c->d_rhist, (size_t)kRselSlots * kRselBins, &fresh_h)) ||
+        (st = ensure<unsigned long long>(c, c->d_rcand, (size_t)nplanes * n)))
         return st;
     if (fresh_st) {
         RenderState init{};
         init.mm[0] = init.mm[2] = ~0ull;
-        HIP_TRY(c, hipMemcpyAsync(c->d_rstate, &init, sizeof init, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_rstate.as<RenderState>(), &init, sizeof init, hipMemcpyHostToDevice, s));
     }
-    if (fresh_h) HIP_TRY(c, hipMemsetAsync(c->d_rhist, 0, (size_t)kRselSlots * kRselBins * sizeof(unsigned int), s));
+    if (fresh_h) HIP_TRY(c, hipMemsetAsync(c->d_rhist.as<unsigned int>(), 0, (size_t)kRselSlots * kRselBins * sizeof(unsigned int), s));
     RselParams p{};
     p.src[0] = planes[0]; p.src[1] = nplanes > 1 ? planes[1] : nullptr;
     p.n = (unsigned int)n; p.nplanes = nplanes; p.hsv = hsv ? 1 : 0;
     robust_ranks(n, pct, p.k);
-    p.hist = c->d_rhist; p.cand = c->d_rcand; p.st = c->d_rstate;
+    p.hist = c->d_rhist.as<unsigned int>(); p.cand = c->d_rcand.as<unsigned long long>(); p.st = c->d_rstate.as<RenderState>();
     const unsigned g_full = (unsigned)std::min<size_t>(nblocks(n, kRselThreads * 8), 1024);
     hipLaunchKernelGGL(emba_rsel_stats_kernel, dim3(g_full), dim3(kRselThreads), 0, s, p);
     hipLaunchKernelGGL(emba_rsel_compact_kernel, dim3((unsigned)std::min<size_t>(nblocks(n, 256 * 8), 2048)), dim3(256), 0, s, p);
@@ -3267,7 +3290,7 @@ inline size_t img_off(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// Device layout of the images in c->d_img: [Gx_u8 | Gy_u8 | RGB (3 n) | Poisson_u8], each part 256-byte aligned.
+// Device layout of the images in c->d_img.as<uint8_t>(): [Gx_u8 | Gy_u8 | RGB (3 n) | Poisson_u8], each part 256-byte aligned.
 extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
@@ -3278,28 +3301,28 @@ extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, u
     const size_t n = c->npix, o1 = img_off(n), o2 = o1 + img_off(n), o3 = o2 + img_off(3 * n);
     if (n >= ((size_t)1 << 31)) return fail(c, EMBA_ERR_CAPACITY, "%zu pixels: the select counts in 32 bits", n);
     emba_status st;
-    if ((st = dev_alloc(c, &c->d_img, o3 + img_off(n)))) return st;
+    if ((st = ensure<uint8_t>(c, c->d_img, o3 + img_off(n)))) return st;
     if (gx_u8 || gy_u8 || rgb_u8) {
         const double* planes[2] = {c->d_Gx, c->d_Gy};
         if ((st = robust_select(c, planes, 2, n, pct_discard, rgb_u8 != nullptr))) return st;
         const int vec = (((uintptr_t)c->d_Gx | (uintptr_t)c->d_Gy) & 15) == 0;
-        hipLaunchKernelGGL(emba_render_kernel, dim3(nblocks(n, 1024)), dim3(256), 0, s, c->d_Gx, c->d_Gy, (unsigned int)n, (const RenderState*)c->d_rstate,
-                           gx_u8 ? c->d_img : nullptr, gy_u8 ? c->d_img + o1 : nullptr, rgb_u8 ? c->d_img + o2 : nullptr, vec);
+        hipLaunchKernelGGL(emba_render_kernel, dim3(nblocks(n, 1024)), dim3(256), 0, s, c->d_Gx, c->d_Gy, (unsigned int)n, (const RenderState*)c->d_rstate.as<RenderState>(),
+                           gx_u8 ? c->d_img.as<uint8_t>() : nullptr, gy_u8 ? c->d_img.as<uint8_t>() + o1 : nullptr, rgb_u8 ? c->d_img.as<uint8_t>() + o2 : nullptr, vec);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(s));
-        if (gx_u8 && (st = d2h_pageable(c, gx_u8, c->d_img, n))) return st;
-        if (gy_u8 && (st = d2h_pageable(c, gy_u8, c->d_img + o1, n))) return st;
-        if (rgb_u8 && (st = d2h_pageable(c, rgb_u8, c->d_img + o2, 3 * n))) return st;
+        if (gx_u8 && (st = d2h_pageable(c, gx_u8, c->d_img.as<uint8_t>(), n))) return st;
+        if (gy_u8 && (st = d2h_pageable(c, gy_u8, c->d_img.as<uint8_t>() + o1, n))) return st;
+        if (rgb_u8 && (st = d2h_pageable(c, rgb_u8, c->d_img.as<uint8_t>() + o2, 3 * n))) return st;
     }
     if (poisson_u8) {
-        if ((st = emba_reconstruct_intensity(c, nullptr, nullptr, nullptr))) return st;      // M stays in c->d_pF
-        const double* planes[1] = {c->d_pF};
+        if ((st = emba_reconstruct_intensity(c, nullptr, nullptr, nullptr))) return st;      // M stays in c->d_pF.as<double>()
+        const double* planes[1] = {c->d_pF.as<double>()};
         if ((st = robust_select(c, planes, 1, n, pct_discard, false))) return st;
-        hipLaunchKernelGGL(emba_robust_u8_kernel, dim3((unsigned)std::min<size_t>(nblocks(n), 4096)), dim3(256), 0, s, (const double*)c->d_pF, (unsigned int)n,
-                           (const RenderState*)c->d_rstate, 0, c->d_img + o3);
+        hipLaunchKernelGGL(emba_robust_u8_kernel, dim3((unsigned)std::min<size_t>(nblocks(n), 4096)), dim3(256), 0, s, (const double*)c->d_pF.as<double>(), (unsigned int)n,
+                           (const RenderState*)c->d_rstate.as<RenderState>(), 0, c->d_img.as<uint8_t>() + o3);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(s));
-        if ((st = d2h_pageable(c, poisson_u8, c->d_img + o3, n))) return st;
+        if ((st = d2h_pageable(c, poisson_u8, c->d_img.as<uint8_t>() + o3, n))) return st;
     }
     c->spun = false; c->knots_in_flight = false;
     return EMBA_OK;
@@ -3314,20 +3337,20 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     emba_status st;
-    if ((st = dev_alloc(c, &c->d_nsrc, n)) || (st = dev_alloc(c, &c->d_img, img_off(n)))) return st;
-    HIP_TRY(c, hipMemcpyAsync(c->d_nsrc, src_host, n * sizeof(double), hipMemcpyHostToDevice, s));
-    const double* planes[1] = {c->d_nsrc};
+    if ((st = ensure<double>(c, c->d_nsrc, n)) || (st = ensure<uint8_t>(c, c->d_img, img_off(n)))) return st;
+    HIP_TRY(c, hipMemcpyAsync(c->d_nsrc.as<double>(), src_host, n * sizeof(double), hipMemcpyHostToDevice, s));
+    const double* planes[1] = {c->d_nsrc.as<double>()};
     if ((st = robust_select(c, planes, 1, n, pct_discard, false))) return st;
     if (dst_host) {
-        hipLaunchKernelGGL(emba_robust_u8_kernel, dim3((unsigned)std::min<size_t>(nblocks(n), 4096)), dim3(256), 0, s, (const double*)c->d_nsrc, (unsigned int)n,
-                           (const RenderState*)c->d_rstate, 0, c->d_img);
+        hipLaunchKernelGGL(emba_robust_u8_kernel, dim3((unsigned)std::min<size_t>(nblocks(n), 4096)), dim3(256), 0, s, (const double*)c->d_nsrc.as<double>(), (unsigned int)n,
+                           (const RenderState*)c->d_rstate.as<RenderState>(), 0, c->d_img.as<uint8_t>());
         HIP_TRY(c, hipGetLastError());
     }
     double r[2];
-    HIP_TRY(c, hipMemcpyAsync(&r[0], &c->d_rstate->slot[0].value, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&r[1], &c->d_rstate->slot[1].value, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&r[0], &c->d_rstate.as<RenderState>()->slot[0].value, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&r[1], &c->d_rstate.as<RenderState>()->slot[1].value, sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (dst_host && (st = d2h_pageable(c, dst_host, c->d_img, n))) return st;
+    if (dst_host && (st = d2h_pageable(c, dst_host, c->d_img.as<uint8_t>(), n))) return st;
     if (rmin) *rmin = r[0];
     if (rmax) *rmax = r[1];
     c->spun = false; c->knots_in_flight = false;

@@ -161,18 +161,18 @@ struct emba_group {
     std::vector<hipEvent_t> ev_side, ev_side0;   // ordering between a rank's stream and its side stream / among the side streams
     std::string err;
     size_t npix = 0; int sw = 0;
-    // exchange buffers, per rank, on the rank's device
-    std::vector<int32_t*> count; std::vector<uint8_t*> count_u8; std::vector<double*> pack; size_t pack_cap = 0; int pack_K = 0;
+    // per rank, on the rank's device: the exchange buffers (count map, its saturated bytes, the pack) and the grow-only scratch of the sharded solve
+    // (an LM loop solves every iteration): records sent / received, S (also the CG reduction), x2
+    struct RankBufs { DevBuf count, count_u8, pack, send, recv, S, x2; };
+    std::vector<RankBufs> buf;
     // per-iteration results
     size_t P = 0, n_inliers = 0; int K = 0;
     std::vector<size_t> n_local;
     std::vector<size_t> lo;              // first global event of every rank's range
     bool x1_done = false;                // the count maps of the last evaluation have been all-reduced already (emba_group_eval returned num_ev_map)
     int decl_irls = 0; double decl_eta = 0.0;   // robust cost declared for the evaluations (emba_group_set_cost)
-    // grow-only scratch of the sharded solve, per rank (an LM loop calls it every iteration)
-    std::vector<double*> sv_send, sv_recv, sv_S, sv_x2; std::vector<size_t> cap_send, cap_recv, cap_S, cap_x2;
     bool last_solve_exchanged = true;   // the last sharded solve ran the record exchange (false: every rank had its received records cached)
-    bool x2_on_ranks = false;   // sv_x2[r] holds the all-reduced x2 of the last emba_group_solve (emba_group_update_map with x2_host == NULL)
+    bool x2_on_ranks = false;   // buf[r].x2 holds the all-reduced x2 of the last emba_group_solve (emba_group_update_map with x2_host == NULL)
     RankPool pool;
     int sw_ = 0;
     std::vector<uint16_t> ev_x, ev_y;    // sensor coordinates of the window's events (host copy): the merged residual vector of emba_group_eval is ordered by sensor pixel
@@ -205,16 +205,22 @@ emba_status gpool(emba_group* g, const std::function<emba_status(int)>& f)
     return gfail(g, st, "rank %d: %s", bad, emba_last_error(g->ctx[bad]));
 }
 
-template <typename T>
-emba_status grow(emba_group* g, int r, T** p, size_t* cap, size_t count)
+// a rank's scratch holds at least `count` doubles: grows by 1/8 more, after the rank's stream has drained
+emba_status grow(emba_group* g, int r, DevBuf& b, size_t count)
 {
-    if (*p && *cap >= count) return EMBA_OK;
+    if (b.p && b.bytes >= count * sizeof(double)) return EMBA_OK;
     G_HIP(g, hipSetDevice(g->dev[r]));
-    if (*p) { G_HIP(g, hipStreamSynchronize(g->ctx[r]->stream)); (void)hipFree(*p); *p = nullptr; }
-    const size_t want = std::max<size_t>(count + count / 8, 16);
-    G_HIP(g, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
+    if (b.p) G_HIP(g, hipStreamSynchronize(g->ctx[r]->stream));
+    G_HIP(g, b.ensure(std::max<size_t>(count + count / 8, 16) * sizeof(double)));
     return EMBA_OK;
+}
+
+// every rank's pointer to its buffer m
+std::vector<double*> rank_ptrs(emba_group* g, DevBuf emba_group::RankBufs::*m)
+{
+    std::vector<double*> v(g->n);
+    for (int r = 0; r < g->n; ++r) v[r] = (g->buf[r].*m).as<double>();
+    return v;
 }
 
 enum class XType { U8, I32, F64 };
@@ -303,22 +309,21 @@ emba_status group_alltoall(emba_group* g, double* const* send, double* const* re
 emba_status group_ensure_buffers(emba_group* g, int K)
 {
     const size_t need = (size_t)9 * K * K + (size_t)3 * K + 5 * g->npix;
-    if (g->pack_cap >= need && !g->pack.empty()) return EMBA_OK;
     for (int r = 0; r < g->n; ++r) {
+        auto& b = g->buf[r];
+        if (b.pack.bytes >= need * sizeof(double)) continue;
         G_HIP(g, hipSetDevice(g->dev[r]));
         G_HIP(g, hipStreamSynchronize(g->ctx[r]->stream));
-        if (g->pack[r]) (void)hipFree(g->pack[r]);
-        g->pack[r] = nullptr;
-        G_HIP(g, hipMalloc((void**)&g->pack[r], need * sizeof(double)));
-        if (!g->count[r]) {
-            G_HIP(g, hipMalloc((void**)&g->count[r], g->npix * sizeof(int32_t)));
-            G_HIP(g, hipMalloc((void**)&g->count_u8[r], g->npix));
-            G_HIP(g, hipMemset(g->count[r], 0, g->npix * sizeof(int32_t)));
+        G_HIP(g, b.pack.ensure(need * sizeof(double)));
+        bool fresh = false;
+        G_HIP(g, b.count_u8.ensure(g->npix));
+        G_HIP(g, b.count.ensure(g->npix * sizeof(int32_t), &fresh));
+        if (fresh) {
+            G_HIP(g, hipMemset(b.count.p, 0, g->npix * sizeof(int32_t)));
             G_HIP(g, hipDeviceSynchronize());      // (default stream: not ordered in front of the rank's non-blocking stream)
         }
-        G_TRY(g, r, emba_bind_exchange_buffers(g->ctx[r], g->count[r], g->pack[r], need));
+        G_TRY(g, r, emba_bind_exchange_buffers(g->ctx[r], b.count.as<int32_t>(), b.pack.as<double>(), need));
     }
-    g->pack_cap = need; g->pack_K = K;
     return EMBA_OK;
 }
 
@@ -340,11 +345,9 @@ emba_status emba_group_create_flags(const emba_cfg* cfg, const int32_t* devices,
     g->n = n_ranks;
     g->npix = (size_t)cfg->pano_w * cfg->pano_h; g->sw = cfg->sensor_w;
     g->ctx.assign(n_ranks, nullptr); g->dev.assign(devices, devices + n_ranks); g->comm.assign(n_ranks, nullptr); g->ev.assign(n_ranks, nullptr);
-    g->count.assign(n_ranks, nullptr); g->count_u8.assign(n_ranks, nullptr); g->pack.assign(n_ranks, nullptr); g->n_local.assign(n_ranks, 0);
+    g->buf.resize(n_ranks); g->n_local.assign(n_ranks, 0);
     g->side.assign(n_ranks, nullptr); g->ev_side.assign(n_ranks, nullptr); g->ev_side0.assign(n_ranks + 1, nullptr);
     g->lo.assign(n_ranks, 0); g->sw_ = cfg->sensor_w;
-    g->sv_send.assign(n_ranks, nullptr); g->sv_recv.assign(n_ranks, nullptr); g->sv_S.assign(n_ranks, nullptr); g->sv_x2.assign(n_ranks, nullptr);
-    g->cap_send.assign(n_ranks, 0); g->cap_recv.assign(n_ranks, 0); g->cap_S.assign(n_ranks, 0); g->cap_x2.assign(n_ranks, 0);
     auto bail = [&](emba_status st, const std::string& msg) { fail(nullptr, st, "%s", msg.c_str()); emba_group_destroy(g); return st; };
     for (int r = 0; r < n_ranks; ++r) {
         emba_cfg c2 = *cfg;
@@ -385,14 +388,12 @@ void emba_group_destroy(emba_group* g)
     g->pool.shutdown();
     for (int r = 0; r < g->n; ++r) {
         if (g->ctx[r]) { (void)hipSetDevice(g->dev[r]); (void)hipStreamSynchronize(g->ctx[r]->stream); }
-        for (double* p : {g->sv_send[r], g->sv_recv[r], g->sv_S[r], g->sv_x2[r]}) if (p) (void)hipFree(p);
+        for (DevBuf* b : {&g->buf[r].send, &g->buf[r].recv, &g->buf[r].S, &g->buf[r].x2}) b->reset();
     }
     for (int r = 0; r < g->n; ++r) {
         if (g->ctx[r]) { (void)hipSetDevice(g->dev[r]); (void)hipStreamSynchronize(g->ctx[r]->stream); }
         if (g->use_rccl && g->comm[r]) (void)g_rccl.CommDestroy(g->comm[r]);
-        if (g->count[r]) (void)hipFree(g->count[r]);
-        if (g->count_u8[r]) (void)hipFree(g->count_u8[r]);
-        if (g->pack[r]) (void)hipFree(g->pack[r]);
+        for (DevBuf* b : {&g->buf[r].count, &g->buf[r].count_u8, &g->buf[r].pack}) b->reset();
         if (g->ev[r]) (void)hipEventDestroy(g->ev[r]);
         if (g->side[r]) { (void)hipStreamSynchronize(g->side[r]); (void)hipStreamDestroy(g->side[r]); }
         if (g->ev_side[r]) (void)hipEventDestroy(g->ev_side[r]);
@@ -467,14 +468,14 @@ emba_status group_exchange_counts(emba_group* g, int thres, bool exact, const st
     if (g->x1_done) { if (after) return gpool(g, *after); return EMBA_OK; }
     const int cap = 255 / g->n;
     if (!exact && thres >= 1 && thres <= cap) {   // sum_i min(c_i, cap) >= thres <=> sum_i c_i >= thres, and world * cap <= 255 cannot wrap
-        { emba_status st = gpool(g, [&](int r) { return emba_count_compress(g->ctx[r], g->count_u8[r], cap); }); if (st) return st; }
-        { emba_status st = group_allreduce(g, (void* const*)g->count_u8.data(), g->npix, XType::U8); if (st) return st; }
-        { emba_status st = gpool(g, [&](int r) { emba_status s1 = emba_count_expand(g->ctx[r], g->count_u8[r]); return (s1 || !after) ? s1 : (*after)(r); }); if (st) return st; }
+        { emba_status st = gpool(g, [&](int r) { return emba_count_compress(g->ctx[r], g->buf[r].count_u8.as<uint8_t>(), cap); }); if (st) return st; }
+        { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::count_u8).data(), g->npix, XType::U8); if (st) return st; }
+        { emba_status st = gpool(g, [&](int r) { emba_status s1 = emba_count_expand(g->ctx[r], g->buf[r].count_u8.as<uint8_t>()); return (s1 || !after) ? s1 : (*after)(r); }); if (st) return st; }
         g->x1_done = true;
         return EMBA_OK;
     } else {
         { emba_status st = gpool(g, [&](int r) { return emba_count_map_ready(g->ctx[r]); }); if (st) return st; }
-        { emba_status st = group_allreduce(g, (void* const*)g->count.data(), g->npix, XType::I32); if (st) return st; }
+        { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::count).data(), g->npix, XType::I32); if (st) return st; }
     }
     g->x1_done = true;
     if (after) return gpool(g, *after);
@@ -508,7 +509,7 @@ emba_status emba_group_eval(emba_group* g, const double* knots, int32_t K, int64
         { emba_status st = group_exchange_counts(g, 0, /*exact=*/true); if (st) return st; }                                              // X1
         G_HIP(g, hipSetDevice(g->dev[0]));
         G_HIP(g, hipStreamSynchronize(g->ctx[0]->stream));
-        G_HIP(g, hipMemcpy(num_ev_map_out, g->count[0], g->npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+        G_HIP(g, hipMemcpy(num_ev_map_out, g->buf[0].count.as<int32_t>(), g->npix * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     if (!ep_out && !n_inliers)      // nothing asked for: E2 is enqueued only (the costs / formNormalEq that follow find an evaluation to work on)
         for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_eval_finish(g->ctx[r], nullptr, nullptr, nullptr));
@@ -600,16 +601,16 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
         for (int r = 0; r < g->n; ++r) fast = fast && (irls == g->ctx[r]->acc_irls) && (irls == 0 || eta == g->ctx[r]->acc_eta) && g->ctx[r]->eval_launched;
         if (fast) {
             const int cap = 255 / g->n;
-            { emba_status st = gpool(g, [&](int r) { return emba_count_compress(g->ctx[r], g->count_u8[r], cap); }); if (st) return st; }
-            { emba_status st = group_allreduce(g, (void* const*)g->count_u8.data(), g->npix, XType::U8); if (st) return st; }                      // X1
+            { emba_status st = gpool(g, [&](int r) { return emba_count_compress(g->ctx[r], g->buf[r].count_u8.as<uint8_t>(), cap); }); if (st) return st; }
+            { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::count_u8).data(), g->npix, XType::U8); if (st) return st; }                      // X1
             { emba_status st = gpool(g, [&](int r) {                                                                                              // E2, F1, F2
-                  emba_status s1 = emba_step_form_active(g->ctx[r], thres, g->count_u8[r]);
+                  emba_status s1 = emba_step_form_active(g->ctx[r], thres, g->buf[r].count_u8.as<uint8_t>());
                   return s1 ? s1 : emba_form_accumulate(g->ctx[r], nullptr, irls, eta); });
               if (st) return st; }
             size_t ni0 = 0;
             G_TRY(g, 0, emba_last_counts(g->ctx[0], &ni0, &g->P));          // the gather's first block publishes P: polled, the Gram kernels still run
             const size_t pl = g->ctx[0]->pack_len;
-            { emba_status st = group_allreduce(g, (void* const*)g->pack.data(), pl, XType::F64); if (st) return st; }                             // X2
+            { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::pack).data(), pl, XType::F64); if (st) return st; }                             // X2
             std::vector<size_t> ni(g->n, 0), pp(g->n, 0);
             { emba_status st = gpool(g, [&](int r) {                                                                                              // F3
                   emba_status s1 = emba_form_finish(g->ctx[r], alpha, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
@@ -653,19 +654,19 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
     split = split && rows_final;
     if (!split) {
         { emba_status st = gpool(g, [&](int r) { return emba_form_accumulate(g->ctx[r], nullptr, irls, eta); }); if (st) return st; }      // F2
-        { emba_status st = group_allreduce(g, (void* const*)g->pack.data(), pl, XType::F64); if (st) return st; }                          // X2
+        { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::pack).data(), pl, XType::F64); if (st) return st; }                          // X2
     } else {
         const size_t head = pl - 5 * g->P;
         std::vector<void*> rows(g->n, nullptr);
         for (int r = 0; r < g->n; ++r) {
-            rows[r] = g->pack[r] + head;
+            rows[r] = g->buf[r].pack.as<double>() + head;
             G_HIP(g, hipSetDevice(g->dev[r]));
             G_HIP(g, hipEventRecord(g->ev_side[r], g->ctx[r]->stream));          // the active-set write of this rank
             G_HIP(g, hipStreamWaitEvent(g->side[r], g->ev_side[r], 0));
         }
         { emba_status st = group_allreduce(g, rows.data(), 5 * g->P, XType::F64, /*on_side=*/true); if (st) return st; }                    // X2b
         { emba_status st = gpool(g, [&](int r) { return emba_form_accumulate(g->ctx[r], nullptr, irls, eta); }); if (st) return st; }      // F2
-        { emba_status st = group_allreduce(g, (void* const*)g->pack.data(), head, XType::F64); if (st) return st; }                        // X2a
+        { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::pack).data(), head, XType::F64); if (st) return st; }                        // X2a
         for (int r = 0; r < g->n; ++r) {
             G_HIP(g, hipSetDevice(g->dev[r]));
             G_HIP(g, hipEventRecord(g->ev_side[r], g->side[r]));
@@ -757,13 +758,13 @@ static emba_status group_exchange_records(emba_group* g, std::vector<size_t>* n_
     // grow-only scratch (an LM loop solves every iteration: no hipMalloc / hipFree per call)
     for (int r = 0; r < n; ++r) {
         emba_status st;
-        if ((st = grow(g, r, &g->sv_send[r], &g->cap_send[r], std::max<size_t>(n_send[r], 1) * 16)) || (st = grow(g, r, &g->sv_recv[r], &g->cap_recv[r], std::max<size_t>(n_recv[r], 1) * 16)))
+        if ((st = grow(g, r, g->buf[r].send, std::max<size_t>(n_send[r], 1) * 16)) || (st = grow(g, r, g->buf[r].recv, std::max<size_t>(n_recv[r], 1) * 16)))
             return st;
     }
     stage("grow");
-    { emba_status st = gpool(g, [&](int r) { return emba_solve_shard_pack(g->ctx[r], n, g->sv_send[r]); }); if (st) return st; }
+    { emba_status st = gpool(g, [&](int r) { return emba_solve_shard_pack(g->ctx[r], n, g->buf[r].send.as<double>()); }); if (st) return st; }
     stage("shard_pack");
-    { emba_status st = group_alltoall(g, g->sv_send.data(), g->sv_recv.data(), cnt16); if (st) return st; }
+    { emba_status st = group_alltoall(g, rank_ptrs(g, &emba_group::RankBufs::send).data(), rank_ptrs(g, &emba_group::RankBufs::recv).data(), cnt16); if (st) return st; }
     stage("alltoall (enqueue)");
     *n_recv_out = n_recv;
     return EMBA_OK;
@@ -792,24 +793,24 @@ emba_status emba_group_solve(emba_group* g, double lambda, int32_t fix_first_pos
     G_TRY(g, 0, emba_solve_shard_size(g->ctx[0], &s_doubles));
     for (int r = 0; r < n; ++r) {
         emba_status st;
-        if ((st = grow(g, r, &g->sv_S[r], &g->cap_S[r], s_doubles)) || (st = grow(g, r, &g->sv_x2[r], &g->cap_x2[r], std::max<size_t>(2 * g->P, 2)))) return st;
+        if ((st = grow(g, r, g->buf[r].S, s_doubles)) || (st = grow(g, r, g->buf[r].x2, std::max<size_t>(2 * g->P, 2)))) return st;
     }
     stage("grow S, x2");
-    { emba_status st = gpool(g, [&](int r) { return emba_solve_shard_partial(g->ctx[r], r, n, cached ? nullptr : g->sv_recv[r], n_recv[r], lambda, g->sv_S[r]); }); if (st) return st; }
+    { emba_status st = gpool(g, [&](int r) { return emba_solve_shard_partial(g->ctx[r], r, n, cached ? nullptr : g->buf[r].recv.as<double>(), n_recv[r], lambda, g->buf[r].S.as<double>()); }); if (st) return st; }
     stage("shard_partial");
-    { emba_status st = group_allreduce(g, (void* const*)g->sv_S.data(), s_doubles, XType::F64); if (st) return st; }
+    { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::S).data(), s_doubles, XType::F64); if (st) return st; }
     stage("allreduce S (enqueue)");
     // a 2x2 block that is not positive definite shows up on its pixel's owner only: every rank finishes (x2 exchange included) and the
     // failure is reported once, for the group
     std::vector<emba_status> fin(n, EMBA_OK);
     (void)g->pool.run([&](int r) {
-        fin[r] = emba_solve_shard_finish(g->ctx[r], r, n, cached ? nullptr : g->sv_recv[r], n_recv[r], lambda, fix_first_pose, g->sv_S[r], r == 0 ? x1_host : nullptr, g->sv_x2[r]);
+        fin[r] = emba_solve_shard_finish(g->ctx[r], r, n, cached ? nullptr : g->buf[r].recv.as<double>(), n_recv[r], lambda, fix_first_pose, g->buf[r].S.as<double>(), r == 0 ? x1_host : nullptr, g->buf[r].x2.as<double>());
         return EMBA_OK; });
     stage("shard_finish");
     for (int r = 0; r < n; ++r) if (fin[r] && fin[r] != EMBA_ERR_NUMERIC) return gfail(g, fin[r], "rank %d: %s", r, emba_last_error(g->ctx[r]));
-    { emba_status st = group_allreduce(g, (void* const*)g->sv_x2.data(), 2 * g->P, XType::F64); if (st) return st; }
+    { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::x2).data(), 2 * g->P, XType::F64); if (st) return st; }
     G_HIP(g, hipSetDevice(g->dev[0]));
-    if (x2_host && g->P) G_HIP(g, hipMemcpyAsync(x2_host, g->sv_x2[0], 2 * g->P * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
+    if (x2_host && g->P) G_HIP(g, hipMemcpyAsync(x2_host, g->buf[0].x2.as<double>(), 2 * g->P * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
     for (int r = 0; r < n; ++r) { G_HIP(g, hipSetDevice(g->dev[r])); G_HIP(g, hipStreamSynchronize(g->ctx[r]->stream)); }
     stage("x2 allreduce + sync");
     for (int r = 0; r < n; ++r) if (fin[r]) return gfail(g, fin[r], "rank %d: %s", r, emba_last_error(g->ctx[r]));
@@ -840,21 +841,21 @@ emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_
     G_TRY(g, 0, emba_cg_shard_size(g->ctx[0], &red_len));
     const size_t nn = red_len - 2;
     for (int r = 0; r < n; ++r) {
-        emba_status st;      // (sv_S doubles as the reduce buffer: (3K+1)^2 doubles when the Schur solve has grown it, at least 3K + 2 here)
-        if ((st = grow(g, r, &g->sv_S[r], &g->cap_S[r], red_len)) || (st = grow(g, r, &g->sv_x2[r], &g->cap_x2[r], std::max<size_t>(2 * g->P, 2)))) return st;
+        emba_status st;      // (buf[r].S doubles as the reduce buffer: (3K+1)^2 doubles when the Schur solve has grown it, at least 3K + 2 here)
+        if ((st = grow(g, r, g->buf[r].S, red_len)) || (st = grow(g, r, g->buf[r].x2, std::max<size_t>(2 * g->P, 2)))) return st;
     }
     // the two scalars behind the pose part of every rank's reduce buffer, read from rank 0's copy (identical everywhere)
     auto read2 = [&](double* a, double* b) -> emba_status {
         double h[2] = {0, 0};
         G_HIP(g, hipSetDevice(g->dev[0]));
-        G_HIP(g, hipMemcpyAsync(h, g->sv_S[0] + nn, 16, hipMemcpyDeviceToHost, g->ctx[0]->stream));
+        G_HIP(g, hipMemcpyAsync(h, g->buf[0].S.as<double>() + nn, 16, hipMemcpyDeviceToHost, g->ctx[0]->stream));
         G_HIP(g, hipStreamSynchronize(g->ctx[0]->stream));
         if (a) *a = h[0];
         if (b) *b = h[1];
         return EMBA_OK;
     };
-    { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_begin(g->ctx[r], r, n, cached ? nullptr : g->sv_recv[r], n_recv[r], lambda, fix_first_pose, g->sv_S[r]); }); if (st) return st; }
-    { emba_status st = group_allreduce(g, (void* const*)g->sv_S.data(), red_len, XType::F64); if (st) return st; }
+    { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_begin(g->ctx[r], r, n, cached ? nullptr : g->buf[r].recv.as<double>(), n_recv[r], lambda, fix_first_pose, g->buf[r].S.as<double>()); }); if (st) return st; }
+    { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::S).data(), red_len, XType::F64); if (st) return st; }
     double rhs2 = 0, absNew = 0;
     { emba_status st = read2(&rhs2, &absNew); if (st) return st; }
     int it = 0;
@@ -864,14 +865,14 @@ emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_
         double rn2 = rhs2;
         if (rn2 >= thr) {
             while (it < max_iter) {
-                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_apply(g->ctx[r], g->sv_S[r]); }); if (st) return st; }
-                { emba_status st = group_allreduce(g, (void* const*)g->sv_S.data(), red_len, XType::F64); if (st) return st; }
+                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_apply(g->ctx[r], g->buf[r].S.as<double>()); }); if (st) return st; }
+                { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::S).data(), red_len, XType::F64); if (st) return st; }
                 std::vector<double> pt(n, 0.0);
-                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_pt(g->ctx[r], g->sv_S[r], &pt[r]); }); if (st) return st; }
+                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_pt(g->ctx[r], g->buf[r].S.as<double>(), &pt[r]); }); if (st) return st; }
                 const double alpha = absNew / pt[0];      // (pt[r] are equal: the same reduced values, the same one-block dot)
-                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_update(g->ctx[r], alpha, g->sv_S[r]); }); if (st) return st; }
+                { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_update(g->ctx[r], alpha, g->buf[r].S.as<double>()); }); if (st) return st; }
                 std::vector<void*> tail(n);
-                for (int r = 0; r < n; ++r) tail[r] = g->sv_S[r] + nn;
+                for (int r = 0; r < n; ++r) tail[r] = g->buf[r].S.as<double>() + nn;
                 { emba_status st = group_allreduce(g, tail.data(), 2, XType::F64); if (st) return st; }
                 double absNext = 0;
                 { emba_status st = read2(&rn2, &absNext); if (st) return st; }
@@ -884,10 +885,10 @@ emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_
         }
         err = std::sqrt(rn2 / rhs2);
     }
-    { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_end(g->ctx[r], r == 0 ? x1_host : nullptr, g->sv_x2[r]); }); if (st) return st; }
-    { emba_status st = group_allreduce(g, (void* const*)g->sv_x2.data(), 2 * g->P, XType::F64); if (st) return st; }
+    { emba_status st = gpool(g, [&](int r) { return emba_cg_shard_end(g->ctx[r], r == 0 ? x1_host : nullptr, g->buf[r].x2.as<double>()); }); if (st) return st; }
+    { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::x2).data(), 2 * g->P, XType::F64); if (st) return st; }
     G_HIP(g, hipSetDevice(g->dev[0]));
-    if (x2_host && g->P) G_HIP(g, hipMemcpyAsync(x2_host, g->sv_x2[0], 2 * g->P * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
+    if (x2_host && g->P) G_HIP(g, hipMemcpyAsync(x2_host, g->buf[0].x2.as<double>(), 2 * g->P * 8, hipMemcpyDeviceToHost, g->ctx[0]->stream));
     for (int r = 0; r < n; ++r) { G_HIP(g, hipSetDevice(g->dev[r])); G_HIP(g, hipStreamSynchronize(g->ctx[r]->stream)); }
     g->x2_on_ranks = true;
     if (iterations) *iterations = it;
@@ -910,7 +911,7 @@ emba_status emba_group_update_map(emba_group* g, const double* x2_host, double d
     // to the host and back, and not once per rank
     if (!x2_host && (g->n > 1 || g->use_rccl)) {
         if (!g->x2_on_ranks) return gfail(g, EMBA_ERR_STATE, "x2 NULL: no emba_group_solve / emba_group_solve_cg has left an x2 on the ranks");
-        for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_update_map_dev(g->ctx[r], g->sv_x2[r], damping));
+        for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_update_map_dev(g->ctx[r], g->buf[r].x2.as<double>(), damping));
         return EMBA_OK;
     }
     for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_update_map(g->ctx[r], x2_host, damping));

@@ -501,3 +501,34 @@ def test_group_ep_is_merged_pixel_block_by_pixel_block(oracle_mod):
         assert np.array_equal(out2, ep)
     finally:
         m.close()
+
+
+def test_cg_session_ends_when_a_solve_takes_the_scratch():
+    """A CG session (emba_cg_shard_*) keeps its vectors and record lists in the context's solve scratch.  A solve on the same context between
+    emba_cg_shard_begin and the next step takes that scratch (the session's vectors could be re-allocated under it): the session has
+    ended, and its next step fails with EMBA_ERR_STATE before it launches anything.  One rank on one context, called as _sharded_solve_cg does."""
+    import torch
+    from emba_amd import LEGM
+    from emba_amd._lib import ERR_STATE, EmbaError
+    w = small_workload(n_events=20000)
+    m = LEGM(w.sensor_w, w.sensor_h, w.lut, w.C_th, w.pano_w, w.pano_h, device=0)
+    m.set_events(w.events)
+    nem = np.zeros((w.pano_h, w.pano_w), dtype=np.int32)
+    ep = m.evaluateDataError(w.traj, w.Gx, w.Gy, None, True, nem)
+    m.formNormalEq(ep, w.K, nem, w.thres_valid_pixel)
+    m.applyL2Reg(w.alpha)
+    lam = 1e-3
+    m.solveNormalEq(lam)                  # (sizes the scratch: the solve below regrows nothing)
+    dev = torch.device("cuda", 0)
+    n_recv = int(m.solve_shard_count(1).sum())      # one rank: the records it sends to itself are the records it receives
+    recv = torch.zeros(max(n_recv, 1) * 16, dtype=torch.float64, device=dev)
+    red = torch.zeros(m.cg_shard_size(), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    m.solve_shard_pack(1, recv.data_ptr())
+    m.cg_shard_begin(0, 1, recv.data_ptr(), n_recv, lam, False, red.data_ptr())
+    m.sync()
+    m.solveNormalEq(lam)
+    with pytest.raises(EmbaError) as err:
+        m.cg_shard_apply(red.data_ptr())
+    assert err.value.status == ERR_STATE
+    m.close()
