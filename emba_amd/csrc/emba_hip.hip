@@ -70,6 +70,44 @@ struct RecordSet { DevBuf rec, tag; uint32_t stamp = 0; };
 
 struct SolveLists { uint32_t* off = nullptr; emba::RecView sorted{}; };   // per-pixel record lists of a solve — sorted: the participating records in pixel order; off[i]: first record of pixel i
 
+// The normal equations currently in the pack, as the host knows them.  One value: an evaluation that sets the equations aside copies it (eq_saved), a
+// rejection copies it back — whatever describes "the equations in the pack" belongs here, so that it cannot be forgotten in one of the two directions.
+struct EqState {
+    bool active_done = false, accum_done = false;   // emba_form_active (and its count P resolved) / emba_form_accumulate ran
+    bool finish_done = false;         // emba_form_finish ran (L2 applied): the state the solvers work on
+    bool compact_valid = false;       // d_compact matches the active set (built on demand)
+    bool l2_fused = false;            // applyL2Reg has been applied to these blocks (by the gather of emba_step, or by emba_form_finish)
+    bool force_generic_a22 = false;   // decided by form_active, read by emba_form_accumulate: the per-pixel sums were consumed, A22 | b2 come from the records
+    size_t P = 0, pack_len = 0;
+    int K = 0, thres = 0, irls = 0; double eta = 0;
+};
+
+// The evaluation in flight: what is known on the host about the last emba_eval_launch and the products derived from it.  begin_evaluation() is the one reset.
+struct EvalState {
+    bool launched = false, done = false;   // emba_eval_launch ran / its inlier count and status word have reached the host
+    bool ep_deferred = false;     // residual compaction not launched yet (it rides along with the active-set kernels)
+    bool inl_pending = false, P_pending = false;   // counters enqueued for readback but not yet resolved (no host sync yet)
+    bool seq_armed = false;       // the pending counts come from kernels that publish the sequence number
+    bool inl_idx_valid = false;   // the per-event inlier numbers are produced on demand (dumps, caller-supplied ep): 4 B/event the step does not write
+    bool ep_valid = false;        // d_ep holds this evaluation's residuals in the reference's order (the resident step's Gram launch compacts them in its tail blocks)
+    bool ep_in_gram = false;      // ... the Gram launch of the equations being formed will do that (set by form_active's fused branch)
+    bool ep_after_gram = false;   // ... or, for windows too long for the tail form, the scan + compaction launches behind it
+    bool pix_starts_valid = false;   // h_pix_starts is emba_get_inlier_pixel_starts of this evaluation (for emba_get_ep_by_pixel)
+    uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
+    int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
+    bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
+};
+
+// Call options of the internal eval_launch / form_active (the extern "C" entry points pass the defaults).  irls, eta: the robust cost the per-pixel sums are
+// weighted with; keep_alt_set: the caller re-forms the equations itself, nothing of the previous ones can be gone back to — no second record set (ADVICE r3:
+// +12.8 GB at 100 M events for callers that can never reject)
+struct EvalOpts { int irls = 0; double eta = 0.0; bool keep_alt_set = false; };
+struct FormOpts {
+    bool consume = false, wants_ep = false;   // the resident step: this gather is the per-pixel sums' only reader; ... and ep is compacted with its Gram launch
+    const uint8_t* global_u8 = nullptr;       // emba_step_form_active: the all-reduced saturated byte counts activity is decided from
+    double fused_alpha = 0.0;                 // A22 | b2 come from the accumulator lines: applyL2Reg rides along with the gather
+};
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -98,7 +136,6 @@ struct emba_ctx {
     // emba_cg_shard_*: the session's sizes; its vectors are the solve scratch (sv), its lists the lists cache.  active: begin succeeded, and since then neither
     // another solve nor a failed emba_cg_shard_* call has taken the scratch
     struct CgShard { bool active = false; int rank = 0, n_ranks = 1, n = 0, skip = 0; size_t lo = 0, npix = 0, Nl = 0; double lambda = 0; } cg;
-    uint32_t count_stamp = 0;   // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
     size_t perm_lo = 0, perm_n = 0;   // ... of the pixels [perm_lo, perm_lo + perm_n) of the active set (a rank's owned range in the sharded solve)
     bool perm_valid = false;   // sv.perm holds the column order of U for the local Schur solve (solve_perm), valid with the lists
     int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
@@ -110,8 +147,6 @@ struct emba_ctx {
     DevBuf d_pixacc; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
     bool pixacc_clean = false;     // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
     bool pixacc_consumed = false;  // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
-    bool step_consume = false;     // set by emba_step around its emba_form_active: this gather is the sums' only reader
-    bool force_generic_a22 = false;
     int32_t count_mark = 0;        // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
     int use_texel = 0;    // what the current evaluation uses: 0 fly, 1 full pack, 3 rectangle
@@ -128,11 +163,10 @@ struct emba_ctx {
     uint32_t eval_seq = 0;
     DevBuf d_total;                 // [0] inliers, [1] active pixels
     DevBuf d_scalar;                // cost reductions
-    std::vector<uint32_t> h_pix_starts; uint32_t pix_starts_seq = 0;   // emba_get_inlier_pixel_starts of evaluation number pix_starts_seq (eval_seq), for emba_get_ep_by_pixel
+    std::vector<uint32_t> h_pix_starts;   // emba_get_inlier_pixel_starts of the current evaluation (ev.pix_starts_valid), for emba_get_ep_by_pixel
     void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
     int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3] step sequence number
     int seq = 0;                    // sequence number of the last step whose post-warp kernels publish [3]
-    bool seq_armed = false;         // the pending counts come from kernels that publish the sequence number
     bool spun = false;              // counts were taken by polling: later kernels of the stream may still be running
     int* h_pinned_dev = nullptr;    // the same memory through its device pointer
     double* h_knots_dev = nullptr;  // device pointer of the pinned control-pose staging buffer
@@ -163,32 +197,26 @@ struct emba_ctx {
     DevBuf d_seg_act;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
     bool aw_in_gram = false; ActiveWriteParams aw_saved{};   // the gather of the running step, to be issued with its Gram launch (emba_form_accumulate)
     int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
-    bool no_alt_set = false;   // set by emba_step around its evaluation: the step re-forms the equations itself, nothing of the previous ones can be gone back to —
-                               // no second record set (+12.8 GB at 100 M events for callers that can never reject)
     int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
     int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
     DevBuf d_slot_key; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
     // Two record sets (a rejected LM trial must not cost a re-evaluation).  `work` is the WORKING set: what
     // the last evaluation wrote and what formNormalEq and the solvers read.  An evaluation that would overwrite records the current normal
-    // equations were formed from (accum_done) first swaps in the other set; emba_map_reject / emba_trial_reject swaps back, so the solver can be
-    // called again with a larger lambda on untouched equations (solver.cpp:340-352 reuses A, b).  Nothing else needs a second copy: the
-    // pack, the active set and the compact index are written by formNormalEq only, which never runs on a rejected trial.
+    // equations were formed from (eq.accum_done) first sets them aside — eq_saved = eq, and the other record set is swapped in; emba_map_reject /
+    // emba_trial_reject swaps back and takes eq = eq_saved, so the solver can be called again with a larger lambda on untouched equations
+    // (solver.cpp:340-352 reuses A, b).  Nothing else needs a second copy: the pack, the active set and the compact index are written by
+    // formNormalEq only, which never runs on a rejected trial.
     RecordSet work, alt;
-    bool eq_in_alt = false;                      // the equations in the pack belong to the OTHER set (a trial evaluation has been written since)
-    struct EqState { bool active_done = false, accum_done = false, finish_done = false, compact_valid = false, l2_fused = false; size_t P = 0, pack_len = 0; int K = 0, thres = 0, irls = 0; double eta = 0; } eq_saved;
+    bool eq_in_alt = false;   // the equations in the pack (eq_saved) belong to the OTHER set: a trial evaluation has been written since
+    EqState eq, eq_saved;     // the equations in the pack; ... as they were when a trial evaluation set them aside (eq_in_alt)
+    EvalState ev;             // the evaluation in flight
     DevBuf d_e_sorted, d_flag, d_inl_idx;
     size_t n_outside_tile = 0; int n_rebin = 0; uint32_t last_rebin_stamp = 0;   // tile order: inliers found outside their tile in the last evaluation; how often the window was re-binned
-    bool inl_idx_valid = false;   // the per-event inlier numbers are produced on demand (dumps, caller-supplied ep): 4 B/event the step does not write
-    bool ep_valid = false;        // d_ep holds the current evaluation's residuals in the reference's order (the resident step's Gram launch compacts them in its tail blocks)
-    bool ep_in_gram = false;      // ... the Gram launch of the equations being formed will do that (set by emba_form_active's fused branch)
-    bool ep_after_gram = false;   // ... or, for windows too long for the tail form, the scan + compaction launches behind it
     int opt_poison = 0;          // option poison = 1 (tests): every NEW device allocation of the context is filled with 0xFF bytes
     int opt_tile_reserve = 2, opt_tile_shape = -1, opt_tile_fine = -1, opt_tile_min_events = 1650000, opt_tile_chunk = 0;   // emba_set_option: the tile order's window rule (prepare_order)
     int tile_shape = 0; bool tile_fine = false;   // ... and what the current order uses: index into kTileShapes, its finer pitch grid
     int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
     int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
-    bool step_wants_ep = false;   // set by emba_step around its emba_form_active
-    const uint8_t* global_u8 = nullptr;   // set by emba_step_form_active around its emba_form_active: the all-reduced saturated byte counts activity is decided from
     DevBuf d_fblk_cnt, d_fblk_off; long n_fblk = 0;   // inlier-flag counts per kFlagBlk pm-order entries
     DevBuf d_fsup; long n_fsup = 0; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (two arrays used alternately; fsup_half: the one the last launch A filled)
     DevBuf d_ep;
@@ -197,18 +225,10 @@ struct emba_ctx {
     double set_events_ms = 0, prepare_ms = 0;   // wall time of the last emba_set_events[_dev] / order preparation (diagnostics)
 
     // per-iteration state
-    int K = 0;
-    bool eval_launched = false, eval_done = false, active_done = false, accum_done = false;
-    size_t n_inliers = 0, P = 0, pack_len = 0;
+    size_t n_inliers = 0;
     size_t P_prev = 0;                                      // active pixels of the last equations whose count the host has seen (this window): the Gram kernel's form is chosen by it
-    bool compact_valid = false;   // d_compact matches the current active set (built on demand)
     int cost_irls = 0; double cost_eta = 0.0;   // robust cost declared with emba_set_cost: what the NEXT evaluation weights its per-pixel sums with
-    int acc_irls = 0; double acc_eta = 0.0;     // ... and what the per-pixel sums of the LAST evaluation were weighted with
-    double fused_alpha = 0.0; bool l2_fused = false;   // emba_step on one GPU folds applyL2Reg into the active-set gather
-    bool ep_deferred = false;   // residual compaction not launched yet (it rides along with the active-set kernels)
-    bool inl_pending = false, P_pending = false;   // counters enqueued for readback but not yet resolved (no host sync yet)
     double* h_knots = nullptr; int h_knots_cap = 0; hipEvent_t knots_copied = nullptr; bool knots_in_flight = false;   // pinned staging for the control poses
-    int thres = 0, irls = 0; double eta = 0;
 
     // timing
     hipEvent_t ev_start[8]{}, ev_stop[8]{};
@@ -221,7 +241,6 @@ struct emba_ctx {
     bool kt_warp_valid = false, kt_accum_valid = false;
     int n_cu = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
     int ablate = 0;  // diagnostics builds only (-DEMBA_DIAG): EMBA_ABLATE bit mask; always 0 in the shipped library
-    bool finish_done = false;   // emba_form_finish ran (L2 applied): the state emba_solve_normal_eq works on
     int solve_info = 0;         // last Schur solve: bit 0 a 2x2 block not positive definite (error), bit 1 a pivot of S vanished (zero update, like Eigen's ldlt)
     // ---- grow-only scratch, by phase.  A buffer named for two roles serves both (no phase holds it while the other runs): sharing keeps the peak down.
     struct {   // once-per-window order preparation (set_events_core, prepare_order) and the device scan / sort
@@ -293,13 +312,16 @@ emba_status ensure(emba_ctx* c, DevBuf& b, size_t count, bool* fresh = nullptr)
     return EMBA_OK;
 }
 
+// A new evaluation begins, or the last one can no longer be asked about (its window is gone, its trial was rejected): nothing that was derived from it —
+// pending counters, the residual vector, inlier numbers, the pixel-starts table, the count map's stamp — outlives this.
+void begin_evaluation(emba_ctx* c) { c->ev = EvalState{}; }
 void free_window(emba_ctx* c)
 {   // (the buffers stay: the next window reuses them, see DevBuf)
     c->d_ev_pix = nullptr; c->d_ev_batch = nullptr;
     c->have_events = false; c->keys_ready = false; c->tile_order = false; c->have_ev_pm = false; c->n_chunks = 0; c->n_lead = 0; c->P_prev = 0;
-    c->eval_launched = c->eval_done = c->active_done = c->accum_done = false;
+    c->eq.active_done = c->eq.accum_done = false;
     // (counters of the previous window that were never resolved must not be read as this window's)
-    c->inl_pending = c->P_pending = false; c->ep_deferred = false; c->ep_valid = false; c->inl_idx_valid = false; c->seq_armed = false;
+    begin_evaluation(c);
 }
 
 // ros::Time/Duration midpoint of a batch (model.cpp:116-119; rostime semantics per SURVEY Appendix A):
@@ -659,8 +681,8 @@ emba_status ensure_pack(emba_ctx* c, int K)
 }
 
 inline double* pack_A11(emba_ctx* c) { return c->d_pack; }
-inline double* pack_b1(emba_ctx* c) { return c->d_pack + (size_t)9 * c->K * c->K; }
-inline double* pack_A22b2(emba_ctx* c) { return c->d_pack + (size_t)9 * c->K * c->K + (size_t)3 * c->K; }
+inline double* pack_b1(emba_ctx* c) { return c->d_pack + (size_t)9 * c->eq.K * c->eq.K; }
+inline double* pack_A22b2(emba_ctx* c) { return c->d_pack + (size_t)9 * c->eq.K * c->eq.K + (size_t)3 * c->eq.K; }
 
 long grid8(long n) { return (n + 7) / 8 * 8; }
 
@@ -668,14 +690,14 @@ long grid8(long n) { return (n + 7) / 8 * 8; }
 // so it is produced when one of them asks (8 MB less traffic on every ordinary step).
 emba_status ensure_compact(emba_ctx* c)
 {
-    if (c->compact_valid) return EMBA_OK;
+    if (c->eq.compact_valid) return EMBA_OK;
     hipStream_t s = c->stream;
     HIP_TRY(c, hipMemsetAsync(c->d_compact.as<int32_t>(), 0xFF, c->npix * sizeof(int32_t), s));
-    const size_t bound = c->P_pending ? c->npix : c->P;
+    const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
     if (bound)
         hipLaunchKernelGGL(emba_compact_map_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_total.as<uint32_t>() + 1, c->d_compact.as<int32_t>());
     HIP_TRY(c, hipGetLastError());
-    c->compact_valid = true;
+    c->eq.compact_valid = true;
     return EMBA_OK;
 }
 
@@ -686,7 +708,7 @@ emba_status ensure_counts(emba_ctx* c)
 {
     if (!c->counts_raw) return EMBA_OK;
     c->counts_raw = false;
-    c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
+    c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
     hipLaunchKernelGGL(emba_count_materialise_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix, c->count_mark);
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
@@ -696,8 +718,8 @@ emba_status ensure_counts(emba_ctx* c)
 // ep / counts before the active-set kernels run; otherwise emba_form_active launches it fused with its own stages.
 emba_status launch_ep_compaction(emba_ctx* c)
 {
-    if (!c->ep_deferred) return EMBA_OK;
-    c->ep_deferred = false;
+    if (!c->ev.ep_deferred) return EMBA_OK;
+    c->ev.ep_deferred = false;
     hipStream_t s = c->stream;
     if (c->n_pm) {
         const uint32_t* perm = nullptr;    // (flags and residuals are stored in pm-order by both warp kernels)
@@ -706,14 +728,14 @@ emba_status launch_ep_compaction(emba_ctx* c)
         { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
         hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
                            (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
-        c->inl_idx_valid = true; c->ep_valid = true;
+        c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
         HIP_TRY(c, hipGetLastError());
     } else {
         HIP_TRY(c, hipMemsetAsync(c->d_total.as<uint32_t>(), 0, sizeof(uint32_t), s));
         HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[0], c->d_total.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
     }
-    c->inl_pending = true;
+    c->ev.inl_pending = true;
     return EMBA_OK;
 }
 
@@ -721,13 +743,13 @@ emba_status launch_ep_compaction(emba_ctx* c)
 emba_status ensure_inl_idx(emba_ctx* c)
 {
     { emba_status st = launch_ep_compaction(c); if (st) return st; }
-    if (c->inl_idx_valid || !c->n_pm) return EMBA_OK;
+    if (c->ev.inl_idx_valid || !c->n_pm) return EMBA_OK;
     // (the fused step leaves the per-block inlier counts of this evaluation in d_fblk_cnt, not their prefix)
     { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>()); if (st) return st; }
     hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
                        (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
     HIP_TRY(c, hipGetLastError());
-    c->inl_idx_valid = true; c->ep_valid = true;
+    c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
     return EMBA_OK;
 }
 
@@ -741,12 +763,12 @@ emba_status ensure_inl_idx(emba_ctx* c)
 emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
 {
     { emba_status st = launch_ep_compaction(c); if (st) return st; }
-    if (!c->inl_pending && !c->P_pending) {
+    if (!c->ev.inl_pending && !c->ev.P_pending) {
         if (c->spun && !counts_only) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; c->knots_in_flight = false; }
         return EMBA_OK;
     }
     bool polled = false;
-    if (counts_only && c->seq_armed && c->inl_pending && c->P_pending) {
+    if (counts_only && c->ev.seq_armed && c->ev.inl_pending && c->ev.P_pending) {
         volatile int* w = c->h_pinned + 3;                   // [3] behind the active-pixel count, [4] behind the inlier count
         for (long spin = 0; spin < 50000000L; ++spin) {      // bounded: a faulted kernel never publishes; fall back to the stream
             if (w[0] == c->seq && w[1] == c->seq) { polled = true; break; }
@@ -756,10 +778,10 @@ emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
     }
     if (polled) c->spun = true;
     else { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; }
-    c->seq_armed = false;
+    c->ev.seq_armed = false;
     c->knots_in_flight = false;   // (the prep kernel that reads the pinned knot buffer precedes the post-warp kernels)
-    if (c->inl_pending) {
-        c->inl_pending = false;
+    if (c->ev.inl_pending) {
+        c->ev.inl_pending = false;
         if (c->h_pinned[1] & 1) return fail(c, EMBA_ERR_TIME_RANGE, "a batch midpoint lies outside the spline's knots");
         c->n_inliers = (size_t)(uint32_t)c->h_pinned[0];
         c->n_outside_tile = (size_t)((uint32_t)c->h_pinned[1] >> 1);
@@ -770,16 +792,16 @@ emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
         if (c->tile_order && c->n_inliers && c->n_outside_tile * 5 > c->n_inliers && c->rec_stamp - c->last_rebin_stamp >= 3) {
             c->keys_ready = false; ++c->n_rebin; c->last_rebin_stamp = c->rec_stamp;
         }
-        c->eval_done = true;
+        c->ev.done = true;
     }
-    if (c->P_pending) {
-        c->P_pending = false;
-        c->P = (size_t)(uint32_t)c->h_pinned[2];
-        c->P_prev = c->P;
-        c->pack_len = (size_t)9 * c->K * c->K + (size_t)3 * c->K + 5 * c->P;
-        if (c->pack_len > c->pack_cap)
-            return fail(c, EMBA_ERR_CAPACITY, "pack buffer too small: need %zu doubles, have %zu", c->pack_len, c->pack_cap);
-        c->active_done = true;
+    if (c->ev.P_pending) {
+        c->ev.P_pending = false;
+        c->eq.P = (size_t)(uint32_t)c->h_pinned[2];
+        c->P_prev = c->eq.P;
+        c->eq.pack_len = (size_t)9 * c->eq.K * c->eq.K + (size_t)3 * c->eq.K + 5 * c->eq.P;
+        if (c->eq.pack_len > c->pack_cap)
+            return fail(c, EMBA_ERR_CAPACITY, "pack buffer too small: need %zu doubles, have %zu", c->eq.pack_len, c->pack_cap);
+        c->eq.active_done = true;
     }
     return EMBA_OK;
 }
@@ -1251,18 +1273,18 @@ emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double 
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map resident");
-    if (!c->active_done && !c->P_pending) return fail(c, EMBA_ERR_STATE, "updateMap needs the active set of formNormalEq");
+    if (!c->eq.active_done && !c->ev.P_pending) return fail(c, EMBA_ERR_STATE, "updateMap needs the active set of formNormalEq");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st = resolve_pending(c);
     if (st) return st;
-    if (src_kind == 2 && c->P && c->x2_resident_P != c->P) return fail(c, EMBA_ERR_STATE, "x2 NULL: no solve of the current normal equations has left its x2 on the device");
-    if (src_kind != 2 && c->P && !x2) return fail(c, EMBA_ERR_INVALID_ARG, "x2 NULL");
+    if (src_kind == 2 && c->eq.P && c->x2_resident_P != c->eq.P) return fail(c, EMBA_ERR_STATE, "x2 NULL: no solve of the current normal equations has left its x2 on the device");
+    if (src_kind != 2 && c->eq.P && !x2) return fail(c, EMBA_ERR_INVALID_ARG, "x2 NULL");
     if ((st = ensure<double>(c, c->d_Gx_trial, c->npix)) || (st = ensure<double>(c, c->d_Gy_trial, c->npix))) return st;
-    if ((st = ensure_x2(c, c->P))) return st;
+    if ((st = ensure_x2(c, c->eq.P))) return st;
     hipStream_t s = c->stream;
     if ((st = ensure_compact(c))) return st;
-    if (c->P && src_kind != 2) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), x2, 2 * c->P * sizeof(double), src_kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if (c->eq.P && src_kind != 2) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), x2, 2 * c->eq.P * sizeof(double), src_kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
         c->x2_resident_P = (size_t)-1;      // (whatever a solve left there is overwritten)
     }
     hipLaunchKernelGGL(emba_update_map_kernel, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, s, c->d_Gx_cur, c->d_Gy_cur, c->d_compact.as<int32_t>(),
@@ -1305,16 +1327,13 @@ emba_status emba_trial_reject(emba_ctx* c)
     if (!c->eq_in_alt) return EMBA_OK;     // nothing was evaluated since the equations were formed (or they have been re-formed)
     HIP_TRY(c, hipSetDevice(c->device));
     // (a trial that was only launched: its compacted residual vector and inlier numbers will never be asked for — nothing to resolve)
-    if (c->ep_deferred && !c->P_pending && !c->inl_pending) c->ep_deferred = false;
-    else if (c->P_pending || c->inl_pending || c->ep_deferred) { emba_status st = resolve_pending(c); if (st) return st; }
+    if (c->ev.ep_deferred && !c->ev.P_pending && !c->ev.inl_pending) c->ev.ep_deferred = false;
+    else if (c->ev.P_pending || c->ev.inl_pending || c->ev.ep_deferred) { emba_status st = resolve_pending(c); if (st) return st; }
     std::swap(c->work, c->alt);
+    c->eq = c->eq_saved;
     c->eq_in_alt = false;
-    c->active_done = c->eq_saved.active_done; c->accum_done = c->eq_saved.accum_done; c->finish_done = c->eq_saved.finish_done;
-    c->compact_valid = c->eq_saved.compact_valid; c->l2_fused = c->eq_saved.l2_fused; c->P = c->eq_saved.P; c->pack_len = c->eq_saved.pack_len;
-    c->K = c->eq_saved.K; c->thres = c->eq_saved.thres; c->irls = c->eq_saved.irls; c->eta = c->eq_saved.eta;
     // the per-event residuals, the count map and the per-pixel sums are the rejected trial's: formNormalEq needs a new evaluation
-    c->eval_launched = c->eval_done = false; c->inl_pending = c->P_pending = false; c->ep_deferred = false; c->inl_idx_valid = false;
-    c->ep_valid = false; c->ep_in_gram = false;
+    begin_evaluation(c);
     return EMBA_OK;
 }
 
@@ -1342,19 +1361,19 @@ emba_status emba_get_map_active(emba_ctx* c, double* gxy_host, size_t cap_P)
 {
     if (!c || !gxy_host) return c ? fail(c, EMBA_ERR_INVALID_ARG, "gxy_host NULL") : EMBA_ERR_INVALID_ARG;
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map resident");
-    if (!c->active_done && !c->P_pending) return fail(c, EMBA_ERR_STATE, "no active set (formNormalEq) yet");
+    if (!c->eq.active_done && !c->ev.P_pending) return fail(c, EMBA_ERR_STATE, "no active set (formNormalEq) yet");
     // (only a trial map — emba_update_map's output — is zero outside the active set it was built from; an uploaded or accepted map is not)
     if (!c->map_is_trial) return fail(c, EMBA_ERR_STATE, "emba_get_map_active returns the trial map emba_update_map built; no trial map is resident");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st = resolve_pending(c);
     if (st) return st;
-    if (cap_P < c->P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, c->P);
-    if (!c->P) return EMBA_OK;
-    if ((st = ensure<double>(c, c->dl.out, 2 * c->P))) return st;
+    if (cap_P < c->eq.P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, c->eq.P);
+    if (!c->eq.P) return EMBA_OK;
+    if ((st = ensure<double>(c, c->dl.out, 2 * c->eq.P))) return st;
     double* d_out = c->dl.out.as<double>();
-    hipLaunchKernelGGL(emba_map_active_kernel, dim3(nblocks(c->P)), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->d_active.as<uint32_t>(), (long)c->P, d_out);
+    hipLaunchKernelGGL(emba_map_active_kernel, dim3(nblocks(c->eq.P)), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->d_active.as<uint32_t>(), (long)c->eq.P, d_out);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(gxy_host, d_out, 2 * c->P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(gxy_host, d_out, 2 * c->eq.P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return EMBA_OK;
 }
@@ -1363,7 +1382,7 @@ emba_status emba_bind_exchange_buffers(emba_ctx* c, int32_t* count_map_dev, doub
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     c->d_count = count_map_dev ? count_map_dev : c->d_count_own.as<int32_t>();
-    c->count_stamp = 0;
+    c->ev.count_stamp = 0;
     c->pix_dirty_all = true;   // the new count buffer says nothing about which pixacc lines are dirty
     c->pixacc_clean = false;
     if (pack_dev) { c->d_pack = pack_dev; c->pack_cap = pack_cap; c->pack_bound = true; }
@@ -1374,10 +1393,10 @@ emba_status emba_bind_exchange_buffers(emba_ctx* c, int32_t* count_map_dev, doub
 emba_status emba_count_compress(emba_ctx* c, uint8_t* u8_dev, int32_t cap)
 {
     if (!c || !u8_dev || cap < 1 || cap > 255) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_compress: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
     if (c->counts_raw) {      // markers -> this rank's counts AND their saturated bytes in one sweep (ensure_counts + the compression below)
         c->counts_raw = false;
-        c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
+        c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
         hipLaunchKernelGGL(emba_count_materialise_compress_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix,
                            c->count_mark, (int)cap, u8_dev);
     } else {
@@ -1390,16 +1409,16 @@ emba_status emba_count_compress(emba_ctx* c, uint8_t* u8_dev, int32_t cap)
 emba_status emba_count_expand(emba_ctx* c, const uint8_t* u8_dev)
 {
     if (!c || !u8_dev) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_expand: NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
-    c->count_stamp = 0;      // (exchanged counts: no longer this context's own)
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    c->ev.count_stamp = 0;      // (exchanged counts: no longer this context's own)
     hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, u8_dev, (long)c->npix, c->d_count);
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
 }
 
-emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
+namespace {
+emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const EvalOpts& opt)
 {
-    if (!c) return EMBA_ERR_INVALID_ARG;
     if (!knots) return fail(c, EMBA_ERR_INVALID_ARG, "knots NULL");
     if (!c->have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
@@ -1415,22 +1434,18 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         c->h_knots_cap = K;
     }
     hipStream_t s = c->stream;
-    if (c->accum_done && !c->no_alt_set) {
+    if (c->eq.accum_done && !opt.keep_alt_set) {
         // The working record set is what the current normal equations were formed from: this evaluation (an LM trial, or simply the next
         // step) writes the OTHER set, so that a rejection can go back to untouched equations (emba_trial_reject).
-        if (c->P_pending || c->inl_pending) { if ((st = resolve_pending(c, true))) return st; }
+        if (c->ev.P_pending || c->ev.inl_pending) { if ((st = resolve_pending(c, true))) return st; }
         if (!c->alt.rec.p && (st = size_record_set(c, c->alt, c->n_cand))) return st;
-        c->eq_saved.active_done = c->active_done; c->eq_saved.accum_done = c->accum_done; c->eq_saved.finish_done = c->finish_done;
-        c->eq_saved.compact_valid = c->compact_valid; c->eq_saved.l2_fused = c->l2_fused; c->eq_saved.P = c->P; c->eq_saved.pack_len = c->pack_len;
-        c->eq_saved.K = c->K; c->eq_saved.thres = c->thres; c->eq_saved.irls = c->irls; c->eq_saved.eta = c->eta;
         std::swap(c->work, c->alt);
+        c->eq_saved = c->eq;
         c->eq_in_alt = true;
     }
-    c->K = K;
-    c->count_stamp = 0;      // (the warp kernels are about to mark the count map for a new evaluation)
-    c->eval_launched = c->eval_done = c->active_done = c->accum_done = false;
-    c->inl_pending = c->P_pending = false; c->ep_deferred = false; c->inl_idx_valid = false;
-    c->ep_valid = false; c->ep_in_gram = false; c->ep_after_gram = false;
+    c->eq.K = K;
+    c->eq.active_done = c->eq.accum_done = false;
+    begin_evaluation(c);      // (with it count_stamp: the warp kernels are about to mark the count map for a new evaluation)
     if (c->pix_dirty_all) {   // first use of these buffers: num_ev_map.setTo(0), model.cpp:85 (+ every per-pixel accumulator line)
         HIP_TRY(c, hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int32_t), s));
         HIP_TRY(c, hipMemsetAsync(c->d_pixacc.as<double>(), 0, c->npix * kPixAccStride * sizeof(double), s));
@@ -1495,7 +1510,7 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         p.err = c->d_err;
         p.ablate = c->ablate;
         p.rec_nt = (c->tile_order || c->n_cand * (size_t)(kRecStride * 8) > ((size_t)144 << 20)) ? 1 : 0;      // (1 M slots = 128 MB: kept in the Infinity Cache for the Gram kernel)
-        p.irls = c->cost_irls; p.eta = c->cost_eta;
+        p.irls = opt.irls; p.eta = opt.eta;
         p.stamp = ++c->rec_stamp; c->work.stamp = p.stamp;
         p.marker = c->count_mark = count_marker(p.stamp);
         c->pixacc_clean = false; c->pixacc_consumed = false;
@@ -1510,17 +1525,23 @@ emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_
         c->counts_raw = false;
     }
     HIP_TRY(c, hipGetLastError());
-    c->acc_irls = c->cost_irls; c->acc_eta = c->cost_eta;
-    c->eval_launched = true;
+    c->ev.acc_irls = opt.irls; c->ev.acc_eta = opt.eta;
+    c->ev.launched = true;
     return EMBA_OK;
+}
+}  // namespace
+
+emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
+{   // (weighted with the cost declared with emba_set_cost)
+    return c ? eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{c->cost_irls, c->cost_eta, false}) : EMBA_ERR_INVALID_ARG;
 }
 
 emba_status emba_eval_finish(emba_ctx* c, double* ep_out, size_t* n_inliers, int32_t* num_ev_map_out)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->ep_deferred = true;
+    c->ev.ep_deferred = true;
     if (!ep_out && !n_inliers && !num_ev_map_out) return EMBA_OK;   // fully asynchronous: the compaction rides with the next phase
     emba_status st = resolve_pending(c);
     if (st) return st;
@@ -1546,34 +1567,35 @@ emba_status emba_eval_data_error(emba_ctx* c, const double* knots, int32_t K, in
     return emba_eval_finish(c, ep_out, n_inliers, num_ev_map_out);
 }
 
-emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len)
+namespace {
+emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len, const FormOpts& opt)
 {
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_done && !c->inl_pending && !c->ep_deferred) return fail(c, EMBA_ERR_STATE, "formNormalEq needs the state of evaluateDataError (solver.cpp:99-102)");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "formNormalEq needs the state of evaluateDataError (solver.cpp:99-102)");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const long npix = (long)c->npix;
-    const long head = (long)9 * c->K * c->K + (long)3 * c->K;
+    const long head = (long)9 * c->eq.K * c->eq.K + (long)3 * c->eq.K;
     ActiveWriteParams aw{};
     aw.count = c->d_count; aw.npix = npix; aw.thres = thres; aw.blk_off = c->d_ablk_off.as<uint32_t>(); aw.compact = nullptr; aw.active_idx = c->d_active.as<uint32_t>(); aw.pixacc = c->d_pixacc.as<double>();
-    aw.A22b2 = pack_A22b2(c); aw.pack_head = c->d_pack; aw.head_len = head; aw.alpha = c->fused_alpha; aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
+    aw.A22b2 = pack_A22b2(c); aw.pack_head = c->d_pack; aw.head_len = head; aw.alpha = opt.fused_alpha; aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
     aw.active_bits = c->d_active_bits.as<uint8_t>(); aw.max_P = (long)((c->pack_cap - (size_t)head) / 5); aw.n_ablk = (long)c->n_ablk; aw.ablate = c->ablate;
     // the resident step cleared this evaluation's per-pixel sums behind its gather: a second formNormalEq on the same evaluation takes A22 | b2
     // from the records (the generic path of emba_form_accumulate), and its L2 term from emba_form_finish
-    c->force_generic_a22 = c->pixacc_consumed;
-    if (c->force_generic_a22) { aw.A22b2 = nullptr; aw.alpha = 0.0; c->fused_alpha = 0.0; }
+    c->eq.force_generic_a22 = c->pixacc_consumed;
+    if (c->eq.force_generic_a22) { aw.A22b2 = nullptr; aw.alpha = 0.0; }
     // a sharded window's rank in resident-step mode (emba_step_form_active): activity from the exchanged byte counts, which launch A reads beside this rank's
     // own counts — where the list-driven gather cannot be used the bytes are expanded into the count map first and the sweeping forms below see global counts
-    const bool lists_ok = c->step_consume && c->step_gather && !c->force_generic_a22 && (long)c->n_ablk <= kGatherMaxUnits && c->n_cand &&
+    const bool lists_ok = opt.consume && c->step_gather && !c->eq.force_generic_a22 && (long)c->n_ablk <= kGatherMaxUnits && c->n_cand &&
                           (c->step_gather == 3 || !c->tile_order || c->n_cand <= 3500000);
-    if (c->global_u8 && !(lists_ok && c->ep_deferred && c->n_sorted && !c->counts_raw)) {
+    const uint8_t* global_u8 = opt.global_u8;
+    if (global_u8 && !(lists_ok && c->ev.ep_deferred && c->n_sorted && !c->counts_raw)) {
         { emba_status st0 = ensure_counts(c); if (st0) return st0; }
-        c->count_stamp = 0;
-        hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, s, c->global_u8, npix, c->d_count);
-        c->global_u8 = nullptr;
+        c->ev.count_stamp = 0;
+        hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, s, global_u8, npix, c->d_count);
+        global_u8 = nullptr;      // (the count map holds them now)
     }
-    if (c->ep_deferred && c->n_sorted) {
-        c->ep_deferred = false;
+    if (c->ev.ep_deferred && c->n_sorted) {
+        c->ev.ep_deferred = false;
         PostWarpParams q{};
         q.count = c->d_count; q.npix = npix; q.thres = thres; q.ablk_cnt = c->d_ablk_cnt.as<uint32_t>(); q.ablk_off = c->d_ablk_off.as<uint32_t>(); q.n_ablk = (long)c->n_ablk;
         q.total_P = c->d_total.as<uint32_t>() + 1; q.total_P_host = c->h_pinned_dev + 2;
@@ -1581,16 +1603,16 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
         q.total_inl = c->d_total.as<uint32_t>(); q.total_inl_host = c->h_pinned_dev;
         q.err_dev = c->d_err; q.err_host = c->h_pinned_dev + 1;
         q.e_sorted = c->d_e_sorted.as<double>(); q.flag = c->d_flag.as<uint8_t>(); q.ep = c->d_ep.as<double>(); q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
-        q.seq = ++c->seq; q.seq_host = c->h_pinned_dev + 3; c->seq_armed = true;
+        q.seq = ++c->seq; q.seq_host = c->h_pinned_dev + 3; c->ev.seq_armed = true;
         if (c->counts_raw) { q.raw_count = c->d_count; q.pixacc = c->d_pixacc.as<double>(); q.marker = c->count_mark; c->counts_raw = false;      // launch A turns the markers into counts
-                             c->count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u; }
-        const bool consume = c->step_consume && c->step_fast && !c->force_generic_a22;    // this gather is the per-pixel sums' only reader: lines are zeroed behind it
+                             c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u; }
+        const bool consume = opt.consume && c->step_fast && !c->eq.force_generic_a22;    // this gather is the per-pixel sums' only reader: lines are zeroed behind it
         // list-driven gather: it rides in the head of the Gram kernel (as a kernel of its own it is no faster than the sweeping write: 109.6 vs
         // 108.5 us per step at 1 M events; option step_gather = 1 forces that form for comparison, 0 the sweeping kernel)
         // Where it paid as a HEAD in front of the stream (same box, step time with the head vs with the sweeping kernel): 1 M events 101.2 vs 105.7 us,
         // the 1 M-event shard of the 8 M-event stream 121.8 vs 127, scene-driven 1.17 M events 121 vs 135 — but 1.5 M events 161 vs 154, 3 M (tile order)
         // 289 vs 281, 10 M 833 vs 817: with more active pixels per block the head's dependent trips grew past what the launch saved.
-        q.global_u8 = c->global_u8;
+        q.global_u8 = global_u8;
         const bool lists = lists_ok && (q.raw_count || q.global_u8);      // (step_gather = 3: everywhere, for comparison)
         // (round 4, late: the gather is now the work of 4 of a Gram block's 16 waves BESIDE the record stream, not a head in front of it: step time
         // with it / with the sweeping launch — 1 M 92.6 / 96.4 us, 1.5 M 134.7 / 143.8, 2 M (tile order) 193.4 / 208.5, 3 M 274.4 / 280.9, 10 M on
@@ -1620,12 +1642,12 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
         c->aw_in_gram = false;
         // the residual vector ep of this evaluation: compacted by tail blocks of the Gram launch that follows (kernels.h: ep_tail_block) — launch A has just
         // left the per-block inlier-flag counts they need
-        c->ep_in_gram = c->step_wants_ep && c->step_ep != 2 && c->n_cand;
-        c->ep_after_gram = c->step_wants_ep && !c->ep_in_gram;
+        c->ev.ep_in_gram = opt.wants_ep && c->step_ep != 2 && c->n_cand;
+        c->ev.ep_after_gram = opt.wants_ep && !c->ev.ep_in_gram;
         if (lists && c->step_gather >= 2) { c->aw_saved = aw; c->aw_in_gram = true; }
         else if (lists) hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, aw);
         else hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
-        c->inl_pending = true;
+        c->ev.inl_pending = true;
     } else {
         { emba_status st0 = launch_ep_compaction(c); if (st0) return st0; }
         { emba_status st0 = ensure_counts(c); if (st0) return st0; }
@@ -1635,34 +1657,36 @@ emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack
         hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
     }
     HIP_TRY(c, hipGetLastError());
-    c->compact_valid = false;
-    c->l2_fused = (c->fused_alpha != 0.0);
-    c->fused_alpha = 0.0;
-    c->thres = thres;
+    c->eq.compact_valid = false;
+    c->eq.l2_fused = (aw.alpha != 0.0);
+    c->eq.thres = thres;
     c->eq_in_alt = false;   // new equations are being formed from the working set: the other set's are obsolete
-    c->P_pending = true; c->active_done = false; c->accum_done = false;
-    c->finish_done = false;          // (the head of the pack has just been cleared: what a solve would read is no set of equations — found by the call-order pair test)
+    c->ev.P_pending = true; c->eq.active_done = false; c->eq.accum_done = false;
+    c->eq.finish_done = false;          // (the head of the pack has just been cleared: what a solve would read is no set of equations — found by the call-order pair test)
     c->x2_resident_P = (size_t)-1;   // (a solve of the PREVIOUS equations may have left its x2 on the device)
     c->lists_valid = false; c->perm_valid = false;          // (new active set)
     if (!P && !pack_len) return EMBA_OK;   // asynchronous: P is read from device memory by the kernels that need it
     emba_status st = resolve_pending(c, true);   // counts only: a sharded host sizes exchange 2 from P while the gather still runs
     if (st) return st;
-    if (P) *P = c->P;
-    if (pack_len) *pack_len = c->pack_len;
+    if (P) *P = c->eq.P;
+    if (pack_len) *pack_len = c->eq.pack_len;
     return EMBA_OK;
 }
+}  // namespace
+
+emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len) { return c ? form_active(c, thres, P, pack_len, FormOpts{}) : EMBA_ERR_INVALID_ARG; }
 
 emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irls, double eta)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->active_done && !c->P_pending) return fail(c, EMBA_ERR_STATE, "emba_form_active has not been called");
-    if (c->accum_done) return fail(c, EMBA_ERR_STATE, "these equations have been accumulated already: A11 | b1 are cleared by emba_form_active only (a second pass would add the sums again)");
+    if (!c->eq.active_done && !c->ev.P_pending) return fail(c, EMBA_ERR_STATE, "emba_form_active has not been called");
+    if (c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "these equations have been accumulated already: A11 | b1 are cleared by emba_form_active only (a second pass would add the sums again)");
     if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     // the per-pixel sums of the evaluation already carry this cost's weights (emba_set_cost / emba_step)?  Then they ARE A22/b2.
-    const bool acc_matches = (irls == c->acc_irls) && (irls == 0 || eta == c->acc_eta);
-    const bool generic_a22 = !acc_matches || (ep_host != nullptr) || c->force_generic_a22;
+    const bool acc_matches = (irls == c->ev.acc_irls) && (irls == 0 || eta == c->ev.acc_eta);
+    const bool generic_a22 = !acc_matches || (ep_host != nullptr) || c->eq.force_generic_a22;
     if (c->aw_in_gram && (generic_a22 || !c->n_cand)) {   // (not what emba_step does: the deferred gather as a launch of its own after all)
         hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, c->aw_saved);
         c->aw_in_gram = false;
@@ -1678,13 +1702,13 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
     // accumulator by emba_form_active (quadratic cost, device-resident residuals); with IRLS weights or a
     // caller-supplied ep they are rebuilt from the records instead.
     // (the head of the pack, A11 | b1, was zeroed by emba_form_active's write kernel)
-    c->irls = irls; c->eta = eta;
-    if (generic_a22 && c->P) {
+    c->eq.irls = irls; c->eq.eta = eta;
+    if (generic_a22 && c->eq.P) {
         { emba_status st = ensure_compact(c); if (st) return st; }
-        HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->P * sizeof(double), s));
+        HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->eq.P * sizeof(double), s));
         if (c->n_cand)
             hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
-                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->thres, irls, eta, pack_A22b2(c), c->work.stamp);
+                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, irls, eta, pack_A22b2(c), c->work.stamp);
     }
     if (c->n_cand) {
         GramParams p{};
@@ -1693,14 +1717,14 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         // the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime:
         // nearly every slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
         p.tag = gram_uses_tags(c, ep_host != nullptr) ? c->work.tag.as<double>() : nullptr;
-        p.dim = 3 * c->K;
+        p.dim = 3 * c->eq.K;
         p.ablate = c->ablate;
         // slots per wave: whole rounds of one 16-wave block per CU with equal shares (1 M events: one round of 236 slots per wave),
         // between kGramChunkMin and kGramChunk slots
         // Sparse slot streams (pixel order on a large panorama: most inliers fall on pixels that stay inactive): stages of 128 tags, only the live records fetched (180 -> 78 us at 10 M events on 2048 x 4096, K = 256).
         // Which form: option gram_sparse (0 / 1), else by the LAST formed equations of this context — at least thres records per active pixel are live, and where
         // 4 thres P is still below a quarter of the slots the stream is sparse (BASELINE: 5 x 68.6 k of 1 M slots = 0.34 -> dense; 10 M events on 2048 x 4096: 0.055)
-        const bool sparse = p.tag && (c->opt_gram_sparse == 1 || (c->opt_gram_sparse < 0 && c->P_prev > 0 && c->n_cand >= (2u << 20) && 16ull * (size_t)c->thres * c->P_prev < c->n_cand));
+        const bool sparse = p.tag && (c->opt_gram_sparse == 1 || (c->opt_gram_sparse < 0 && c->P_prev > 0 && c->n_cand >= (2u << 20) && 16ull * (size_t)c->eq.thres * c->P_prev < c->n_cand));
         // (sparse form: up to four times the slots per wave — a wave's pipeline takes three stages to fill; option gram_sparse_chunk: 1 ... 8, no difference from 2 up)
         const long chunk_cap = sparse ? (long)c->opt_gram_sparse_chunk * kGramChunk : kGramChunk;
         const long per_round = (long)c->n_cu * (kGramBlock / 64);
@@ -1714,13 +1738,13 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         constexpr long wpb = kGramBlock / 64;
         unsigned grid = (unsigned)((waves + wpb - 1) / wpb);
         p.n_gram_blocks = (int)grid;
-        const bool ep_tail = c->ep_in_gram && !ep_host && c->n_pm;
+        const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->n_pm;
         if (ep_tail) {
             p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>(); p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_pm = (long)c->n_pm; p.ep_n_fblk = c->n_fblk;
             p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride;
             grid += (unsigned)((c->n_pm + kEpTailBlk - 1) / kEpTailBlk);
         }
-        c->ep_in_gram = false;
+        c->ev.ep_in_gram = false;
         const ActiveWriteParams aw = c->aw_in_gram ? c->aw_saved : ActiveWriteParams{};
         {   // gather waves per Gram block (option gather_waves = 1|2|4 overrides)
             const int gw_env = c->opt_gather_waves;
@@ -1739,18 +1763,18 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
             else hipLaunchKernelGGL((emba_gram_kernel<false, false>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
         }
         c->aw_in_gram = false;
-        if (ep_tail) c->ep_valid = true;
+        if (ep_tail) c->ev.ep_valid = true;
         if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }
     }
-    if (c->ep_after_gram && !ep_host && c->n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
+    if (c->ev.ep_after_gram && !ep_host && c->n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
         { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>() + 2); if (st) return st; }
         hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->n_pm,
                            c->d_ep.as<double>(), (int32_t*)nullptr);
-        c->ep_valid = true;
+        c->ev.ep_valid = true;
     }
-    c->ep_after_gram = false;
+    c->ev.ep_after_gram = false;
     HIP_TRY(c, hipGetLastError());
-    c->accum_done = true; c->finish_done = false;
+    c->eq.accum_done = true; c->eq.finish_done = false;
     return EMBA_OK;
 }
 
@@ -1758,13 +1782,13 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
                              double* b2, double* A12_dense)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->accum_done) return fail(c, EMBA_ERR_STATE, "emba_form_accumulate has not been called");
+    if (!c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "emba_form_accumulate has not been called");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (alpha != 0.0 && !c->l2_fused) {   // (l2_fused doubles as "already applied to this set of blocks": applyL2Reg acts once)
-        c->l2_fused = true;
+    if (alpha != 0.0 && !c->eq.l2_fused) {   // (l2_fused doubles as "already applied to this set of blocks": applyL2Reg acts once)
+        c->eq.l2_fused = true;
         // P may still be unresolved on the host: the kernel reads it from device memory, the grid covers the bound
-        const size_t bound = c->P_pending ? c->npix : c->P;
+        const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
         if (bound)
             hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), c->d_active.as<uint32_t>(),
                                c->d_total.as<uint32_t>() + 1, alpha, c->d_Gx, c->d_Gy);
@@ -1773,9 +1797,9 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
     const bool download = A11 || b1 || active_idx || A22 || b2 || A12_dense;
     emba_status st = resolve_pending(c, !download);   // the step's one host wait when nothing was resolved earlier
     if (st) return st;
-    if (!download) { c->finish_done = true; return EMBA_OK; }
-    const size_t P = c->P;
-    const int dim = 3 * c->K;
+    if (!download) { c->eq.finish_done = true; return EMBA_OK; }
+    const size_t P = c->eq.P;
+    const int dim = 3 * c->eq.K;
     if ((A22 || b2 || A12_dense || active_idx) && cap_P < P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, P);
     if (A11) HIP_TRY(c, hipMemcpyAsync(A11, pack_A11(c), (size_t)dim * dim * sizeof(double), hipMemcpyDeviceToHost, s));
     if (b1) HIP_TRY(c, hipMemcpyAsync(b1, pack_b1(c), (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1800,14 +1824,14 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
         (void)hipMemsetAsync(d_A12, 0, n12 * sizeof(double), s);
         if (c->n_cand)
             hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
-                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->thres, c->irls, c->eta, dim, d_A12, c->work.stamp);
+                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, dim, d_A12, c->work.stamp);
         (void)hipMemcpyAsync(A12_dense, d_A12, n12 * sizeof(double), hipMemcpyDeviceToHost, s);
     }
     hipError_t e = hipStreamSynchronize(s);
     c->knots_in_flight = false;
     if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "form_finish: %s", hipGetErrorString(e));
     HIP_TRY(c, hipGetLastError());
-    c->finish_done = true;
+    c->eq.finish_done = true;
     return EMBA_OK;
 }
 
@@ -1825,7 +1849,7 @@ emba_status emba_form_normal_eq(emba_ctx* c, const double* ep, int32_t thres, in
 emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32_t* pix, double* w, double* jc, double* jp, double* dp)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->accum_done) return fail(c, EMBA_ERR_STATE, "no normal equations formed yet");
+    if (!c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "no normal equations formed yet");
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     const size_t M = c->n_cand;
@@ -1839,7 +1863,7 @@ emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32
     double *d_w = b_w.as<double>(), *d_jc = b_jc.as<double>(), *d_jp = b_jp.as<double>(), *d_dp = b_dp.as<double>();
     hipStream_t s = c->stream;
     hipLaunchKernelGGL(emba_export_a12_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(), (long)M,
-                       c->d_count, c->d_compact.as<int32_t>(), c->thres, c->irls, c->eta, d_c, d_p, d_x, d_w, d_jc, d_jp, d_dp, c->work.stamp);
+                       c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, d_c, d_p, d_x, d_w, d_jc, d_jp, d_dp, c->work.stamp);
     if (cp_c) (void)hipMemcpyAsync(cp_c, d_c, M * 4, hipMemcpyDeviceToHost, s);
     if (cp_p) (void)hipMemcpyAsync(cp_p, d_p, M * 4, hipMemcpyDeviceToHost, s);
     if (pix) (void)hipMemcpyAsync(pix, d_x, M * 4, hipMemcpyDeviceToHost, s);
@@ -1855,21 +1879,21 @@ emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32
 emba_status emba_compact_ep(emba_ctx* c)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->ep_valid) return EMBA_OK;      // (the resident step's Gram launch has produced it already)
-    c->inl_idx_valid = false;      // (asked for explicitly: produce it for THIS call)
+    if (c->ev.ep_valid) return EMBA_OK;      // (the resident step's Gram launch has produced it already)
+    c->ev.inl_idx_valid = false;      // (asked for explicitly: produce it for THIS call)
     return ensure_inl_idx(c);
 }
 
 emba_status emba_get_ep(emba_ctx* c, double* ep_host, size_t cap, size_t* n_inliers)
 {
     if (!c || (!ep_host && cap)) return c ? fail(c, EMBA_ERR_INVALID_ARG, "ep_host NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched || (!c->eval_done && !c->inl_pending && !c->ep_deferred)) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
     if ((st = resolve_pending(c))) return st;
-    if (!c->ep_valid && (st = ensure_inl_idx(c))) return st;      // (not produced by a resident step: the stand-alone compaction)
+    if (!c->ev.ep_valid && (st = ensure_inl_idx(c))) return st;      // (not produced by a resident step: the stand-alone compaction)
     if (n_inliers) *n_inliers = c->n_inliers;
     if (cap < c->n_inliers) return fail(c, EMBA_ERR_CAPACITY, "cap=%zu < inliers=%zu", cap, c->n_inliers);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1880,7 +1904,7 @@ emba_status emba_get_ep(emba_ctx* c, double* ep_host, size_t cap, size_t* n_inli
 emba_status emba_get_inlier_pixels(emba_ctx* c, uint32_t* pix_host)
 {
     if (!c || !pix_host) return c ? fail(c, EMBA_ERR_INVALID_ARG, "pix_host NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_done && !c->inl_pending && !c->ep_deferred) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
     if ((st = resolve_pending(c)) || (st = ensure_inl_idx(c))) return st;
@@ -1897,7 +1921,7 @@ emba_status emba_get_inlier_pixels(emba_ctx* c, uint32_t* pix_host)
 emba_status emba_get_inlier_pixel_starts(emba_ctx* c, uint32_t* starts_host)
 {
     if (!c || !starts_host) return c ? fail(c, EMBA_ERR_INVALID_ARG, "starts_host NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched || (!c->eval_done && !c->inl_pending && !c->ep_deferred)) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
     if ((st = resolve_pending(c)) || (st = ensure_inl_idx(c))) return st;
@@ -1910,23 +1934,23 @@ emba_status emba_get_inlier_pixel_starts(emba_ctx* c, uint32_t* starts_host)
     HIP_TRY(c, hipMemcpyAsync(starts_host, d_starts, ((size_t)S + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->h_pix_starts.assign(starts_host, starts_host + S + 1);
-    c->pix_starts_seq = c->eval_seq;
+    c->ev.pix_starts_valid = true;
     return EMBA_OK;
 }
 
 emba_status emba_get_ep_by_pixel(emba_ctx* c, double* ep_out, const uint64_t* dst)
 {
     if (!c || !ep_out || !dst) return c ? fail(c, EMBA_ERR_INVALID_ARG, "ep_out / dst NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched || (!c->eval_done && !c->inl_pending && !c->ep_deferred)) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
     if ((st = resolve_pending(c))) return st;
     const size_t S = (size_t)c->sw * c->sh;
-    if (c->pix_starts_seq != c->eval_seq || c->h_pix_starts.size() != S + 1) {
+    if (!c->ev.pix_starts_valid || c->h_pix_starts.size() != S + 1) {
         std::vector<uint32_t> tmp(S + 1);
         if ((st = emba_get_inlier_pixel_starts(c, tmp.data()))) return st;
     }
-    if (!c->ep_valid && (st = ensure_inl_idx(c))) return st;
+    if (!c->ev.ep_valid && (st = ensure_inl_idx(c))) return st;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const uint32_t* starts = c->h_pix_starts.data();
     if ((size_t)starts[S] != c->n_inliers) return fail(c, EMBA_ERR_STATE, "the pixel starts do not belong to this evaluation (%u residuals there, %zu here)", starts[S], c->n_inliers);
@@ -1944,7 +1968,7 @@ emba_status emba_get_ep_by_pixel(emba_ctx* c, double* ep_out, const uint64_t* ds
 emba_status emba_data_cost(emba_ctx* c, int32_t irls, double eta, double* cost)
 {
     if (!c || !cost) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_done && !c->inl_pending && !c->ep_deferred) return fail(c, EMBA_ERR_STATE, "no residuals yet");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no residuals yet");
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     hipStream_t s = c->stream;
@@ -1969,13 +1993,13 @@ emba_status emba_data_cost(emba_ctx* c, int32_t irls, double eta, double* cost)
 emba_status emba_costs_launch(emba_ctx* c, int32_t irls, double eta, int32_t with_reg)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_done && !c->inl_pending && !c->ep_deferred) return fail(c, EMBA_ERR_STATE, "no residuals yet");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no residuals yet");
     if (with_reg && !c->have_map) return fail(c, EMBA_ERR_STATE, "no map");
     HIP_TRY(c, hipSetDevice(c->device));
     // An evaluation that has only been launched stays that way: the reductions read the per-event residuals and flags the warp kernel wrote,
     // not the compacted vector — so the formNormalEq that follows an accepted trial still finds the post-warp work fused (emba_form_active), and
     // a rejected trial never pays for a residual vector nobody asks for.  The step's status word comes back with the sums (emba_costs_finish).
-    if (!c->ep_deferred) { emba_status st0 = resolve_pending(c); if (st0) return st0; }
+    if (!c->ev.ep_deferred) { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     if (!c->h_cost) {
         HIP_TRY(c, hipHostMalloc((void**)&c->h_cost, 4 * sizeof(double), hipHostMallocDefault));
         memset(c->h_cost, 0, 4 * sizeof(double));
@@ -2043,7 +2067,7 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
                             double* Gpm, double* temp)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_done && !c->inl_pending && !c->ep_deferred) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state to dump");
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state to dump");
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     if (inlier_idx) { emba_status st0 = ensure_inl_idx(c); if (st0) return st0; }
@@ -2127,40 +2151,31 @@ emba_status emba_step(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns
     if (!c) return EMBA_ERR_INVALID_ARG;
     if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
     emba_status st;
-    {   // the evaluation weights its per-pixel sums with THIS step's cost (whatever emba_set_cost declared for other callers)
-        const int keep_irls = c->cost_irls; const double keep_eta = c->cost_eta;
-        c->cost_irls = irls; c->cost_eta = irls ? eta : 0.0;
-        c->no_alt_set = (c->step_one_set != 0);
-        st = emba_eval_launch(c, knots, K, t0_ns, dt_ns);
-        c->no_alt_set = false;
-        c->cost_irls = keep_irls; c->cost_eta = keep_eta;
-        if (st) return st;
-    }
+    // the evaluation weights its per-pixel sums with THIS step's cost (whatever emba_set_cost declared for other callers)
+    if ((st = eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{irls, irls ? eta : 0.0, c->step_one_set != 0}))) return st;
     if ((st = emba_eval_finish(c, nullptr, nullptr, nullptr))) return st;
-    c->fused_alpha = alpha;   // A22/b2 come from the accumulator, so applyL2Reg rides along with the gather
-    c->step_consume = (c->step_fast != 0);   // ... which is their only reader: it zeroes the lines behind itself and the next evaluation needs no clearing pass
-    c->step_wants_ep = (c->step_ep != 0);    // the step returns what evaluateDataError returns: ep, compacted in the tail of its Gram launch
-    st = emba_form_active(c, thres, nullptr, nullptr);
-    c->step_consume = false; c->step_wants_ep = false;
-    if (st) return st;
+    FormOpts fo;
+    fo.fused_alpha = alpha;               // A22/b2 come from the accumulator, so applyL2Reg rides along with the gather
+    fo.consume = (c->step_fast != 0);     // ... which is their only reader: it zeroes the lines behind itself and the next evaluation needs no clearing pass
+    fo.wants_ep = (c->step_ep != 0);      // the step returns what evaluateDataError returns: ep, compacted in the tail of its Gram launch
+    if ((st = form_active(c, thres, nullptr, nullptr, fo))) return st;
     if ((st = emba_form_accumulate(c, nullptr, irls, eta))) return st;
     if ((st = emba_form_finish(c, alpha, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr))) return st;
     if (n_inliers) *n_inliers = c->n_inliers;
-    if (P) *P = c->P;
+    if (P) *P = c->eq.P;
     return EMBA_OK;
 }
 
 emba_status emba_step_form_active(emba_ctx* c, int32_t thres, const uint8_t* global_counts_u8_dev)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eval_launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
     emba_status st;
     if ((st = emba_eval_finish(c, nullptr, nullptr, nullptr))) return st;
-    c->step_consume = (c->step_fast != 0);
-    c->global_u8 = global_counts_u8_dev;
-    st = emba_form_active(c, thres, nullptr, nullptr);
-    c->step_consume = false; c->global_u8 = nullptr;
-    return st;
+    FormOpts fo;
+    fo.consume = (c->step_fast != 0);
+    fo.global_u8 = global_counts_u8_dev;
+    return form_active(c, thres, nullptr, nullptr, fo);
 }
 
 emba_status emba_count_map_ready(emba_ctx* c)
@@ -2228,7 +2243,7 @@ emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
 emba_status emba_get_option(emba_ctx* c, const char* name, int32_t* value)
 {
     if (!c || !name || !value) return EMBA_ERR_INVALID_ARG;
-    if (!strcmp(name, "ep_valid")) { *value = c->ep_valid ? 1 : 0; return EMBA_OK; }      // read-only: the device holds the last evaluation's ep (a step produced it, or a compaction)
+    if (!strcmp(name, "ep_valid")) { *value = c->ev.ep_valid ? 1 : 0; return EMBA_OK; }      // read-only: the device holds the last evaluation's ep (a step produced it, or a compaction)
     for (const OptionRef& o : kOptions)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
@@ -2241,7 +2256,7 @@ emba_status emba_last_counts(emba_ctx* c, size_t* n_inliers, size_t* P)
     emba_status st = resolve_pending(c, true);
     if (st) return st;
     if (n_inliers) *n_inliers = c->n_inliers;
-    if (P) *P = c->P;
+    if (P) *P = c->eq.P;
     return EMBA_OK;
 }
 
@@ -2477,7 +2492,7 @@ emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n
     // list lengths: from the context's own count map while it still belongs to the evaluation that wrote these records (count_stamp), else counted
     // from the records (all-reduced / saturated / externally bound counts, a trial evaluation since, the sharded solve's received records)
     const int cmap_env = c->opt_solve_counts;      // option solve_counts — 0: always from the records; 2: both, compared (diagnostic)
-    const bool from_map = cmap_env != 0 && !view.packed && c->count_stamp != 0 && c->count_stamp == view.stamp && c->d_count == c->d_count_own.as<int32_t>() && n_pix == c->P && n_pix;
+    const bool from_map = cmap_env != 0 && !view.packed && c->ev.count_stamp != 0 && c->ev.count_stamp == view.stamp && c->d_count == c->d_count_own.as<int32_t>() && n_pix == c->eq.P && n_pix;
     if (from_map && cmap_env != 2) {
         hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_count, (long)n_pix, d_cursor);
     } else {
@@ -2526,7 +2541,7 @@ emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists&
     double* d_U = sv.U_or_p.as<double>();
     SchurBuildParams bp{};
     bp.view = view; bp.off = L.off; bp.A22b2 = A22b2; bp.lambda = lambda;
-    bp.irls = c->irls; bp.eta = c->eta; bp.n = n; bp.U = d_U; bp.ldu = lds_; bp.yv = d_y; bp.cfac = d_cf; bp.info = d_info;
+    bp.irls = c->eq.irls; bp.eta = c->eq.eta; bp.n = n; bp.U = d_U; bp.ldu = lds_; bp.yv = d_y; bp.cfac = d_cf; bp.info = d_info;
     bp.rhs_row = d_S + n; bp.lds = lds_; bp.perm = perm;
     const size_t lds_bytes = (size_t)(2 * kBuildWaves + 1) * n * sizeof(double);
     if (lds_bytes > 160 * 1024) return fail(c, EMBA_ERR_CAPACITY, "K=%d too large for the per-wave column staging in LDS", n / 3);
@@ -2668,9 +2683,9 @@ emba_status schur_factor_solve(emba_ctx* c, double* d_S, long lds_, int n, int s
 // azimuth / elevation path length (rad) of the optical axis over the control poses of the last evaluation (the host's pinned copy)
 bool axis_path(const emba_ctx* c, double* path_az_out, double* path_el_out)
 {
-    if (!c->h_knots || c->K < 2) return false;
+    if (!c->h_knots || c->eq.K < 2) return false;
     double path_az = 0.0, path_el = 0.0, az0 = 0.0, el0 = 0.0;
-    for (int i = 0; i < c->K; ++i) {
+    for (int i = 0; i < c->eq.K; ++i) {
         const double x = c->h_knots[4 * i], y = c->h_knots[4 * i + 1], z = c->h_knots[4 * i + 2], w = c->h_knots[4 * i + 3];
         const double ax = 2.0 * (x * z + w * y), ay = 2.0 * (y * z - w * x), az_ = 1.0 - 2.0 * (x * x + y * y);      // R (0, 0, 1)
         const double az = atan2(ax, az_), el = asin(std::max(-1.0, std::min(1.0, ay)));
@@ -2688,7 +2703,7 @@ emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo =
     // Measured (device time of one solve, with / without; the U build reads its pixels' records out of sequence and pays 5 % for it): config 2's shape (K = 201,
     // 10 M events over 10 s) 3.96 / 4.16 ms — SYRK 1.25 / 1.52, 5.8 / 7.9 products per slice —; 10 M events at K = 97: 2.81 / 2.79; 1 M events over 1 s at
     // K = 201 (every pixel sees the whole window: nothing to gain) 2.27 / 2.24.  From six row blocks (K >= 128) up, unless option solve_perm forces it.
-    if (c->solve_perm_mode == 0 || P < 4 * (size_t)kSyrkSlicePix || (c->solve_perm_mode < 0 && 3 * c->K < 384) || 3 * c->K < 256) return EMBA_OK;
+    if (c->solve_perm_mode == 0 || P < 4 * (size_t)kSyrkSlicePix || (c->solve_perm_mode < 0 && 3 * c->eq.K < 384) || 3 * c->eq.K < 256) return EMBA_OK;
     if (c->perm_valid && c->perm_lo == lo && c->perm_n == P) { *perm = c->sv.perm.as<uint32_t>(); return EMBA_OK; }
     if (c->solve_perm_mode < 0) {
         double path_az = 0.0, path_el = 0.0;
@@ -2718,32 +2733,78 @@ RecView local_view(emba_ctx* c)
     return v;
 }
 
+// the records a rank received as the owner of the active pixels from `lo` on (the sharded solves)
+RecView packed_view(const double* recv_dev, size_t lo) { RecView v{}; v.rec = recv_dev; v.packed = 1; v.pix_base = (long)lo; return v; }
+
+// Are the equations in the pack finished, and formed from the working record set?  What every solver asks first.
+emba_status equations_current(emba_ctx* c, const char* what)
+{
+    if (!c->eq.finish_done) return fail(c, EMBA_ERR_STATE, "%s needs formNormalEq + applyL2Reg (emba_form_finish) first", what);
+    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
+    return EMBA_OK;
+}
+
+// the pose block and the augmented Schur matrix S_aug of the current equations
+struct SchurDims {
+    int n, na, skip; long lds;   // n = 3K; na = n + 1: row n carries y / the right-hand side; lds: leading dimension of S_aug and of U; skip: the fixed first pose's rows
+    SchurDims(const emba_ctx* c, int fix_first_pose = 0) : n(3 * c->eq.K), na(n + 1), skip(fix_first_pose ? 3 : 0), lds((na + 15) / 16 * 16) {}
+    size_t size() const { return (size_t)lds * na; }
+};
+
+// The info word of a Schur solve.  bit 0: a 2x2 block A22m_i is not positive definite — the reference's A22m_i.inverse() (model.cpp:750) returns inf / nan there and
+// the step is lost (NaN cost: rejected); reported as EMBA_ERR_NUMERIC.  bit 1: a pivot of S vanished — handled like Eigen's ldlt (zero update), not an error.
+emba_status solve_status(emba_ctx* c, int info)
+{
+    c->solve_info = info;
+    if (info & 1) return fail(c, EMBA_ERR_NUMERIC, "a 2x2 block of A22 + lambda*diag(A22) is not positive definite (the reference's inverse() gives inf/nan)");
+    if (info & 4) return fail(c, EMBA_ERR_NUMERIC, "the Schur complement is indefinite or not finite (a pivot clearly below zero, or NaN): no update is returned");
+    return EMBA_OK;
+}
+
+// x2 = A22m^-1 (b2 - A12^T x1) of the n_pix pixels of the lists L, straight from the records of each pixel
+emba_status launch_schur_x2(emba_ctx* c, const SolveLists& L, size_t n_pix, int n, const double* d_y, const double* d_cf, const double* d_x1, double* d_x2)
+{
+    if (emba_status st = pose_vector_lds(c, (const void*)emba_schur_x2_kernel, (size_t)n * sizeof(double), "solveNormalEq (x2)")) return st;
+    if (n_pix)
+        hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), c->stream, L.sorted, L.off, d_y,
+                           d_cf, d_x1, c->eq.irls, c->eq.eta, (long)n_pix, d_x2, n);
+    return EMBA_OK;
+}
+
+// the pixels' part of y = [A11m A12; A12^T A22m] v: the n_pix pixels of the lists L, whose A22 | b2 rows start at pixel `lo` of the pack
+void launch_cg_pixels(emba_ctx* c, const SolveLists& L, size_t lo, size_t n_pix, double lambda, int n, int skip, const double* v, double* y)
+{
+    if (!n_pix) return;
+    CgPixParams pp{};
+    pp.view = L.sorted; pp.off = L.off; pp.A22b2 = pack_A22b2(c) + 5 * lo; pp.lambda = lambda; pp.irls = c->eq.irls; pp.eta = c->eq.eta; pp.n = n; pp.skip = skip;
+    pp.P = (long)n_pix; pp.v = v; pp.y = y;
+    hipLaunchKernelGGL(emba_cg_pixel_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, (size_t)8 * c->n_cu)), dim3(256), (size_t)n * 16, c->stream, pp);
+}
+
 }  // namespace
 
 extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t fix_first_pose, double* x1_host, double* x2_host)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->finish_done) return fail(c, EMBA_ERR_STATE, "solveNormalEq needs formNormalEq + applyL2Reg (emba_form_finish) first");
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
-    HIP_TRY(c, hipSetDevice(c->device));
-    emba_status st = resolve_pending(c);
+    emba_status st = equations_current(c, "solveNormalEq");
     if (st) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((st = resolve_pending(c))) return st;
     hipStream_t s = c->stream;
-    const int n = 3 * c->K;
-    const int skip = fix_first_pose ? 3 : 0;
-    const size_t P = c->P, M = c->n_cand;
+    const SchurDims d(c, fix_first_pose);
+    const int n = d.n, skip = d.skip;
+    const long lds_ = d.lds;
+    const size_t P = c->eq.P, M = c->n_cand;
     if (n - skip <= 0) return fail(c, EMBA_ERR_INVALID_ARG, "nothing to solve for");
-    const int na = n + 1;                              // augmented: row n carries y / the right-hand side
-    const long lds_ = (na + 15) / 16 * 16;             // leading dimension of S_aug and of U
     auto& sv = take_solve_scratch(c);
-    if ((st = ensure<double>(c, sv.S_or_x, (size_t)lds_ * na)) || (st = ensure<double>(c, sv.rhs_or_r, n)) || (st = ensure<double>(c, sv.y_or_z, 2 * (P + 1))) ||
+    if ((st = ensure<double>(c, sv.S_or_x, d.size())) || (st = ensure<double>(c, sv.rhs_or_r, n)) || (st = ensure<double>(c, sv.y_or_z, 2 * (P + 1))) ||
         (st = ensure<double>(c, sv.cf_or_t, 3 * (P + 1))) || (st = ensure<double>(c, sv.x2_or_invd, 2 * (P + 1))) || (st = ensure<int>(c, sv.info_or_sc, 1)))
         return st;
     double *d_S = sv.S_or_x.as<double>(), *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>(), *d_x2 = sv.x2_or_invd.as<double>();
     int* d_info = sv.info_or_sc.as<int>();
     if ((st = ensure_compact(c))) return st;
     HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
-    HIP_TRY(c, hipMemsetAsync(d_S, 0, (size_t)lds_ * na * sizeof(double), s));
+    HIP_TRY(c, hipMemsetAsync(d_S, 0, d.size() * sizeof(double), s));
     const RecView view = local_view(c);
     SolveLists L;
     if ((st = build_lists(c, view, M, P, &L))) return st;
@@ -2752,12 +2813,7 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
     if ((st = solve_perm(c, P, &perm))) return st;
     if ((st = schur_accumulate(c, L.sorted, L, P, pack_A22b2(c), lambda, n, d_S, lds_, d_y, d_cf, d_info, perm))) return st;
     if ((st = schur_factor_solve(c, d_S, lds_, n, skip, d_rhs, d_info))) return st;
-    // x2 = A22m^-1 (b2 - A12^T x1), straight from the records of each pixel
-    if (P) {
-        if ((st = pose_vector_lds(c, (const void*)emba_schur_x2_kernel, (size_t)n * sizeof(double), "solveNormalEq (x2)"))) return st;
-        hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((P + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), s, L.sorted, L.off, d_y,
-                           d_cf, d_rhs, c->irls, c->eta, (long)P, d_x2, n);
-    }
+    if (P && (st = launch_schur_x2(c, L, P, n, d_y, d_cf, d_rhs, d_x2))) return st;
     HIP_TRY(c, hipGetLastError());
     int info = 0;
     HIP_TRY(c, hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2765,13 +2821,7 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
     if (x2_host && P) HIP_TRY(c, hipMemcpyAsync(x2_host, d_x2, 2 * P * sizeof(double), hipMemcpyDeviceToHost, s));
     if ((st = keep_x2(c, d_x2, P))) return st;
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->solve_info = info;
-    // bit 0: a 2x2 block A22m_i is not positive definite — the reference's A22m_i.inverse() (model.cpp:750) returns inf / nan there and the
-    // step is lost (NaN cost: rejected); reported as EMBA_ERR_NUMERIC.  bit 1: a pivot of S vanished — handled like Eigen's ldlt (zero
-    // update in that component), not an error.
-    if (info & 1) return fail(c, EMBA_ERR_NUMERIC, "a 2x2 block of A22 + lambda*diag(A22) is not positive definite (the reference's inverse() gives inf/nan)");
-    if (info & 4) return fail(c, EMBA_ERR_NUMERIC, "the Schur complement is indefinite or not finite (a pivot clearly below zero, or NaN): no update is returned");
-    return EMBA_OK;
+    return solve_status(c, info);
 }
 
 extern "C" emba_status emba_last_solve_info(const emba_ctx* c, int32_t* info)
@@ -2785,27 +2835,23 @@ extern "C" emba_status emba_last_solve_info(const emba_ctx* c, int32_t* info)
 extern "C" emba_status emba_solve_shard_size(emba_ctx* c, size_t* s_doubles)
 {
     if (!c || !s_doubles) return EMBA_ERR_INVALID_ARG;
-    const int na = 3 * c->K + 1;
-    const long lds_ = (na + 15) / 16 * 16;
-    *s_doubles = (size_t)lds_ * na;
+    *s_doubles = SchurDims(c).size();
     return EMBA_OK;
 }
 
 extern "C" emba_status emba_solve_shard_count(emba_ctx* c, int32_t n_ranks, size_t* counts_host)
 {
     if (!c || !counts_host || n_ranks < 1 || n_ranks > 1024) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_count: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->finish_done) return fail(c, EMBA_ERR_STATE, "the sharded solve needs formNormalEq + applyL2Reg (emba_form_finish) first");
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
-    HIP_TRY(c, hipSetDevice(c->device));
-    emba_status st = resolve_pending(c);
+    emba_status st = equations_current(c, "the sharded solve");
     if (st) return st;
-    if ((st = ensure_compact(c))) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((st = resolve_pending(c)) || (st = ensure_compact(c))) return st;
     hipStream_t s = c->stream;
     auto& sv = take_solve_scratch(c);
     if ((st = ensure<unsigned long long>(c, sv.shard_cnt, (size_t)3 * n_ranks + 1))) return st;
     unsigned long long* d_cnt = sv.shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, (size_t)3 * n_ranks * 8 + 8, s));
-    if (c->n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->P, (int)n_ranks, d_cnt);
+    if (c->n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->eq.P, (int)n_ranks, d_cnt);
     std::vector<unsigned long long> h(n_ranks);
     HIP_TRY(c, hipMemcpyAsync(h.data(), d_cnt, (size_t)n_ranks * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -2826,7 +2872,7 @@ extern "C" emba_status emba_solve_shard_pack(emba_ctx* c, int32_t n_ranks, doubl
     unsigned long long* d_cnt = take_solve_scratch(c).shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt + 2 * n_ranks, 0, (size_t)n_ranks * 8, s));
     if (c->n_cand && send_dev)
-        hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->P, (int)n_ranks, d_cnt + n_ranks,
+        hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->eq.P, (int)n_ranks, d_cnt + n_ranks,
                            d_cnt + 2 * n_ranks, send_dev);
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
@@ -2842,8 +2888,8 @@ extern "C" emba_status emba_solve_shard_cached(emba_ctx* c, int32_t rank, int32_
 {
     if (!c || !cached || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_cached: bad arguments") : EMBA_ERR_INVALID_ARG;
     size_t lo, hi;
-    shard_range(c->P, rank, n_ranks, &lo, &hi);
-    *cached = (c->finish_done && !c->eq_in_alt && c->lists_valid && c->lists_packed && c->lists_stamp == c->work.stamp && c->lists_P == hi - lo && c->lists_lo == (long)lo &&
+    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
+    *cached = (c->eq.finish_done && !c->eq_in_alt && c->lists_valid && c->lists_packed && c->lists_stamp == c->work.stamp && c->lists_P == hi - lo && c->lists_lo == (long)lo &&
                c->sv.y_or_z.p) ? 1 : 0;
     if (n_recv) *n_recv = *cached ? c->lists_nrec : 0;
     return EMBA_OK;
@@ -2852,29 +2898,25 @@ extern "C" emba_status emba_solve_shard_cached(emba_ctx* c, int32_t rank, int32_
 extern "C" emba_status emba_solve_shard_partial(emba_ctx* c, int32_t rank, int32_t n_ranks, const double* recv_dev, size_t n_recv, double lambda, double* S_part_dev)
 {
     if (!c || !S_part_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_partial: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->finish_done) return fail(c, EMBA_ERR_STATE, "the sharded solve needs formNormalEq + applyL2Reg (emba_form_finish) first");
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
+    emba_status st = equations_current(c, "the sharded solve");
+    if (st) return st;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int n = 3 * c->K, na = n + 1;
-    const long lds_ = (na + 15) / 16 * 16;
+    const SchurDims d(c);
     size_t lo, hi;
-    shard_range(c->P, rank, n_ranks, &lo, &hi);
+    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
     const size_t n_pix = hi - lo;
     auto& sv = take_solve_scratch(c);
-    emba_status st;
     if ((st = ensure<double>(c, sv.y_or_z, 2 * (n_pix + 1))) || (st = ensure<double>(c, sv.cf_or_t, 3 * (n_pix + 1))) || (st = ensure<int>(c, sv.info_or_sc, 16))) return st;
     double *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
     int* d_info = sv.info_or_sc.as<int>();
     HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
-    HIP_TRY(c, hipMemsetAsync(S_part_dev, 0, (size_t)lds_ * na * sizeof(double), s));
-    RecView view{};
-    view.rec = recv_dev; view.packed = 1; view.pix_base = (long)lo;
+    HIP_TRY(c, hipMemsetAsync(S_part_dev, 0, d.size() * sizeof(double), s));
     SolveLists L;
-    if ((st = build_lists(c, view, n_recv, n_pix, &L))) return st;
+    if ((st = build_lists(c, packed_view(recv_dev, lo), n_recv, n_pix, &L))) return st;
     const uint32_t* perm = nullptr;
     if ((st = solve_perm(c, n_pix, &perm, lo))) return st;
-    return schur_accumulate(c, L.sorted, L, n_pix, pack_A22b2(c) + 5 * lo, lambda, n, S_part_dev, lds_, d_y, d_cf, d_info, perm);
+    return schur_accumulate(c, L.sorted, L, n_pix, pack_A22b2(c) + 5 * lo, lambda, d.n, S_part_dev, d.lds, d_y, d_cf, d_info, perm);
 }
 
 extern "C" emba_status emba_solve_shard_finish(emba_ctx* c, int32_t rank, int32_t n_ranks, const double* recv_dev, size_t n_recv, double lambda,
@@ -2884,35 +2926,29 @@ extern "C" emba_status emba_solve_shard_finish(emba_ctx* c, int32_t rank, int32_
     if (!c->lists.off.p || !c->sv.y_or_z.p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_partial first");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int n = 3 * c->K, na = n + 1, skip = fix_first_pose ? 3 : 0;
-    const long lds_ = (na + 15) / 16 * 16;
+    const SchurDims d(c, fix_first_pose);
+    const int n = d.n;
     size_t lo, hi;
-    shard_range(c->P, rank, n_ranks, &lo, &hi);
+    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
     const size_t n_pix = hi - lo;
     auto& sv = take_solve_scratch(c);
     emba_status st;
     if ((st = ensure<double>(c, sv.rhs_or_r, n))) return st;
     double *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
     int* d_info = sv.info_or_sc.as<int>();
-    hipLaunchKernelGGL(emba_schur_add_a11_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, S_dev, lds_);
-    if ((st = schur_factor_solve(c, S_dev, lds_, n, skip, d_rhs, d_info))) return st;
+    hipLaunchKernelGGL(emba_schur_add_a11_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, S_dev, d.lds);
+    if ((st = schur_factor_solve(c, S_dev, d.lds, n, d.skip, d_rhs, d_info))) return st;
     if (x2_full_dev) {
-        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->P * sizeof(double), s));
-        const SolveLists L = cached_lists(c);      // the received records in pixel order, as emba_solve_shard_partial's build_lists left them
-        if ((st = pose_vector_lds(c, (const void*)emba_schur_x2_kernel, (size_t)n * sizeof(double), "solveNormalEq (x2)"))) return st;
-        if (n_pix)
-            hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), s, L.sorted, L.off,
-                               d_y, d_cf, d_rhs, c->irls, c->eta, (long)n_pix, x2_full_dev + 2 * lo, n);
+        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->eq.P * sizeof(double), s));
+        // the received records in pixel order, as emba_solve_shard_partial's build_lists left them
+        if ((st = launch_schur_x2(c, cached_lists(c), n_pix, n, d_y, d_cf, d_rhs, x2_full_dev + 2 * lo))) return st;
     }
     HIP_TRY(c, hipGetLastError());
     int info = 0;
     HIP_TRY(c, hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s));
     if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, d_rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->solve_info = info;
-    if (info & 1) return fail(c, EMBA_ERR_NUMERIC, "a 2x2 block of A22 + lambda*diag(A22) is not positive definite (the reference's inverse() gives inf/nan)");
-    if (info & 4) return fail(c, EMBA_ERR_NUMERIC, "the Schur complement is indefinite or not finite (a pivot clearly below zero, or NaN): no update is returned");
-    return EMBA_OK;
+    return solve_status(c, info);
 }
 
 // LEGM::solveNormalEqCG (model.cpp:794-840)
@@ -2920,14 +2956,13 @@ extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32
                                                double* x2_host, int32_t* iterations, double* error)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->finish_done) return fail(c, EMBA_ERR_STATE, "solveNormalEqCG needs formNormalEq + applyL2Reg (emba_form_finish) first");
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
-    HIP_TRY(c, hipSetDevice(c->device));
-    emba_status st = resolve_pending(c);
+    emba_status st = equations_current(c, "solveNormalEqCG");
     if (st) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((st = resolve_pending(c))) return st;
     hipStream_t s = c->stream;
-    const int n = 3 * c->K, skip = fix_first_pose ? 3 : 0;
-    const size_t P = c->P, M = c->n_cand, N = (size_t)n + 2 * P;
+    const int n = 3 * c->eq.K, skip = fix_first_pose ? 3 : 0;
+    const size_t P = c->eq.P, M = c->n_cand, N = (size_t)n + 2 * P;
     if (max_iter <= 0) max_iter = 100;     // model.cpp:823-824
     if (!(tol > 0)) tol = 1e-6;
     if ((st = ensure_cg_vectors(c, N))) return st;
@@ -2948,13 +2983,9 @@ extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32
         return EMBA_OK;
     };
     if ((st = pose_vector_lds(c, (const void*)emba_cg_pixel_kernel, (size_t)n * 16, "solveNormalEqCG", 48))) return st;
-    CgPixParams pp{};
-    pp.view = L.sorted; pp.off = L.off; pp.A22b2 = pack_A22b2(c); pp.lambda = lambda; pp.irls = c->irls; pp.eta = c->eta; pp.n = n; pp.skip = skip;
-    pp.P = (long)P;
     auto apply = [&](const double* v, double* y) {   // y = [A11m A12; A12^T A22m] v
         hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, lambda, skip, v, y);
-        pp.v = v; pp.y = y;
-        if (P) hipLaunchKernelGGL(emba_cg_pixel_kernel, dim3((unsigned)std::min<size_t>((P + 3) / 4, (size_t)8 * c->n_cu)), dim3(256), (size_t)n * 16, s, pp);
+        launch_cg_pixels(c, L, 0, P, lambda, n, skip, v, y);
     };
     // Eigen/src/IterativeLinearSolvers/ConjugateGradient.h:28-88 (zero initial guess: residual = rhs)
     HIP_TRY(c, hipMemsetAsync(d_sc, 0, 64, s));
@@ -3014,7 +3045,7 @@ extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32
 extern "C" emba_status emba_cg_shard_size(emba_ctx* c, size_t* red_doubles)
 {
     if (!c || !red_doubles) return EMBA_ERR_INVALID_ARG;
-    *red_doubles = (size_t)3 * c->K + 2;
+    *red_doubles = (size_t)3 * c->eq.K + 2;
     return EMBA_OK;
 }
 
@@ -3022,22 +3053,19 @@ extern "C" emba_status emba_cg_shard_begin(emba_ctx* c, int32_t rank, int32_t n_
                                            double* red_dev)
 {
     if (!c || !red_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "cg_shard_begin: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->finish_done) return fail(c, EMBA_ERR_STATE, "solveNormalEqCG needs formNormalEq + applyL2Reg (emba_form_finish) first");
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed: report the LM decision first");
+    emba_status st = equations_current(c, "solveNormalEqCG");
+    if (st) return st;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     auto& g = c->cg;
-    g.rank = rank; g.n_ranks = n_ranks; g.n = 3 * c->K; g.skip = fix_first_pose ? 3 : 0; g.lambda = lambda;
+    g.rank = rank; g.n_ranks = n_ranks; g.n = 3 * c->eq.K; g.skip = fix_first_pose ? 3 : 0; g.lambda = lambda;
     size_t lo, hi;
-    shard_range(c->P, rank, n_ranks, &lo, &hi);
+    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
     g.lo = lo; g.npix = hi - lo; g.Nl = (size_t)g.n + 2 * g.npix;
-    emba_status st;
     if ((st = ensure_cg_vectors(c, g.Nl))) return st;
     const CgVecs v = cg_vectors(c);
-    RecView view{};
-    view.rec = recv_dev; view.packed = 1; view.pix_base = (long)lo;
     SolveLists L;
-    if ((st = build_lists(c, view, n_recv, g.npix, &L))) return st;
+    if ((st = build_lists(c, packed_view(recv_dev, lo), n_recv, g.npix, &L))) return st;
     if ((st = pose_vector_lds(c, (const void*)emba_cg_pixel_kernel, (size_t)g.n * 16, "solveNormalEqCG", 48))) return st;
     HIP_TRY(c, hipMemsetAsync(red_dev, 0, ((size_t)g.n + 2) * 8, s));
     const unsigned grid = (unsigned)std::min<size_t>(nblocks(g.Nl), 1024);
@@ -3059,11 +3087,7 @@ extern "C" emba_status emba_cg_shard_apply(emba_ctx* c, double* red_dev)
     const int n = g.n;
     if (g.rank == 0) hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, g.lambda, g.skip, v.p, v.t);
     else HIP_TRY(c, hipMemsetAsync(v.t, 0, (size_t)n * 8, s));
-    CgPixParams pp{};
-    const SolveLists L = cached_lists(c);
-    pp.view = L.sorted; pp.off = L.off; pp.A22b2 = pack_A22b2(c) + 5 * g.lo; pp.lambda = g.lambda; pp.irls = c->irls; pp.eta = c->eta; pp.n = n; pp.skip = g.skip;
-    pp.P = (long)g.npix; pp.v = v.p; pp.y = v.t;
-    if (g.npix) hipLaunchKernelGGL(emba_cg_pixel_kernel, dim3((unsigned)std::min<size_t>((g.npix + 3) / 4, (size_t)8 * c->n_cu)), dim3(256), (size_t)n * 16, s, pp);
+    launch_cg_pixels(c, cached_lists(c), g.lo, g.npix, g.lambda, n, g.skip, v.p, v.t);
     HIP_TRY(c, hipMemcpyAsync(red_dev, v.t, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemsetAsync(red_dev + n, 0, 16, s));
     if (g.npix) hipLaunchKernelGGL(emba_cg_dot_kernel, dim3((unsigned)std::min<size_t>(nblocks(2 * g.npix), 1024)), dim3(256), 0, s, v.p + n, v.t + n, (long)(2 * g.npix), red_dev + n);
@@ -3133,7 +3157,7 @@ extern "C" emba_status emba_cg_shard_end(emba_ctx* c, double* x1_host, double* x
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     if (x2_full_dev) {
-        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->P * sizeof(double), s));
+        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->eq.P * sizeof(double), s));
         if (g.npix) HIP_TRY(c, hipMemcpyAsync(x2_full_dev + 2 * g.lo, v.x + g.n, 2 * g.npix * 8, hipMemcpyDeviceToDevice, s));
     }
     if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, v.x, (size_t)g.n * 8, hipMemcpyDeviceToHost, s));

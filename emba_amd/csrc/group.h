@@ -580,9 +580,10 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
     if (g->n == 1 && !g->use_rccl) {
         emba_ctx* c = g->ctx[0];
         G_TRY(g, 0, emba_eval_finish(c, nullptr, nullptr, nullptr));
-        const bool fuse = (irls == c->acc_irls) && (irls == 0 || eta == c->acc_eta);
-        if (fuse) c->fused_alpha = alpha;   // A22 / b2 come from the accumulator lines: applyL2Reg rides along with the gather (as in emba_step)
-        G_TRY(g, 0, emba_form_active(c, thres, nullptr, nullptr));
+        const bool fuse = (irls == c->ev.acc_irls) && (irls == 0 || eta == c->ev.acc_eta);
+        FormOpts fo;
+        if (fuse) fo.fused_alpha = alpha;   // A22 / b2 come from the accumulator lines: applyL2Reg rides along with the gather (as in emba_step)
+        G_TRY(g, 0, form_active(c, thres, nullptr, nullptr, fo));
         G_TRY(g, 0, emba_form_accumulate(c, nullptr, irls, eta));
         G_TRY(g, 0, emba_form_finish(c, alpha, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
         G_TRY(g, 0, emba_last_counts(c, &g->n_inliers, &g->P));
@@ -598,7 +599,7 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
         size_t n_max = 0;
         for (int r = 0; r < g->n; ++r) n_max = std::max(n_max, g->n_local[r]);
         bool fast = !g->x1_done && thres >= 1 && thres <= 255 / g->n && n_max < 3000000 && g->opt_x2_split <= 0 && g->opt_step_fast != 0;
-        for (int r = 0; r < g->n; ++r) fast = fast && (irls == g->ctx[r]->acc_irls) && (irls == 0 || eta == g->ctx[r]->acc_eta) && g->ctx[r]->eval_launched;
+        for (int r = 0; r < g->n; ++r) fast = fast && (irls == g->ctx[r]->ev.acc_irls) && (irls == 0 || eta == g->ctx[r]->ev.acc_eta) && g->ctx[r]->ev.launched;
         if (fast) {
             const int cap = 255 / g->n;
             { emba_status st = gpool(g, [&](int r) { return emba_count_compress(g->ctx[r], g->buf[r].count_u8.as<uint8_t>(), cap); }); if (st) return st; }
@@ -609,7 +610,7 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
               if (st) return st; }
             size_t ni0 = 0;
             G_TRY(g, 0, emba_last_counts(g->ctx[0], &ni0, &g->P));          // the gather's first block publishes P: polled, the Gram kernels still run
-            const size_t pl = g->ctx[0]->pack_len;
+            const size_t pl = g->ctx[0]->eq.pack_len;
             { emba_status st = group_allreduce(g, (void* const*)rank_ptrs(g, &emba_group::RankBufs::pack).data(), pl, XType::F64); if (st) return st; }                             // X2
             std::vector<size_t> ni(g->n, 0), pp(g->n, 0);
             { emba_status st = gpool(g, [&](int r) {                                                                                              // F3
@@ -636,7 +637,7 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
     g->x1_done = false;   // (consumed: the next evaluation starts a new count map)
     // the active set comes from the GLOBAL counts: identical on every rank, so rank 0's P sizes exchange 2 (one host wait instead of N)
     size_t pl = 0;
-    { size_t ni = 0; G_TRY(g, 0, emba_last_counts(g->ctx[0], &ni, &g->P)); pl = g->ctx[0]->pack_len; }
+    { size_t ni = 0; G_TRY(g, 0, emba_last_counts(g->ctx[0], &ni, &g->P)); pl = g->ctx[0]->eq.pack_len; }
     // X2 in two parts.  The A22 | b2 rows (5 doubles per active pixel: the bulk of the exchange) are final once the active set has been
     // written — when the cost was declared before the evaluation, form_accumulate only adds the A11 | b1 head — and their all-reduce runs
     // on the ranks' SIDE streams while the Gram kernels form the head on the ranks' own streams; the small head follows.
@@ -648,7 +649,7 @@ emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double e
     // not from the cost last declared: a cost declared after the evaluation (the IRLS form's first iteration) leaves gathered rows that
     // emba_form_accumulate is about to rebuild from the records — they must not be on their way through a collective meanwhile.
     bool rows_final = true;
-    for (int r = 0; r < g->n; ++r) rows_final = rows_final && (irls == g->ctx[r]->acc_irls) && (irls == 0 || eta == g->ctx[r]->acc_eta);
+    for (int r = 0; r < g->n; ++r) rows_final = rows_final && (irls == g->ctx[r]->ev.acc_irls) && (irls == 0 || eta == g->ctx[r]->ev.acc_eta);
     bool split = n_max >= 3000000;
     if (g->opt_x2_split >= 0) split = g->opt_x2_split != 0;      // emba_group_set_option("x2_split")
     split = split && rows_final;

@@ -503,6 +503,64 @@ def test_group_ep_is_merged_pixel_block_by_pixel_block(oracle_mod):
         m.close()
 
 
+@pytest.mark.gpu
+def test_ep_by_pixel_takes_no_pixel_starts_across_a_rejected_trial(oracle_mod):
+    """emba_get_ep_by_pixel places the residuals with the pixel starts the context kept from emba_get_inlier_pixel_starts.  That table belongs to
+    ONE evaluation: a rejected trial ends the evaluation (EMBA_ERR_STATE until the next one), and the next evaluation takes its own starts even when
+    nobody fetched them first.  The two trajectories are chosen so that a table kept across the rejection would go unnoticed by every size check:
+    the same number of inliers (13793, on plateaus of the yaw rate four search steps of 2e-4 wide), but other runs per sensor pixel — asserted
+    below on the oracle."""
+    import ctypes as C
+    from emba_amd import LEGM, _lib
+    from emba_amd.synth import make_trajectory
+    L = _lib.load()
+    w = small_workload(n_events=20000)
+    ev = w.events
+    S = w.sensor_w * w.sensor_h
+    traj_a, traj_b = make_trajectory(w.K, 0.05, 0.1, 1.9976), make_trajectory(w.K, 0.05, 0.1, -1.9838)
+    o = oracle_mod.OracleLEGM(w.sensor_w, w.sensor_h, w.pano_w, w.pano_h, w.lut, w.C_th)
+    pix = ev.y.astype(np.int64) * w.sensor_w + ev.x
+
+    def oracle_starts(traj):
+        r = o.evaluate_data_error(traj.knots_xyzw, traj.t0_ns, traj.dt_ns, w.Gx, w.Gy, ev.x, ev.y, ev.polarity, ev.t_ns, dump=True)
+        return np.concatenate([[0], np.cumsum(np.bincount(pix[r[2]["inlier_idx"] >= 0], minlength=S))]).astype(np.uint32)
+
+    starts_a_o, starts_b_o = oracle_starts(traj_a), oracle_starts(traj_b)
+    assert starts_a_o[S] == starts_b_o[S] > 0 and np.count_nonzero(starts_a_o != starts_b_o) > S // 2     # same size, other runs
+
+    def fetch_starts():
+        s = np.zeros(S + 1, np.uint32)
+        assert L.emba_get_inlier_pixel_starts(m._ctx, s.ctypes.data_as(_lib._u32p)) == 0
+        return s
+
+    m = LEGM(w.sensor_w, w.sensor_h, w.lut, w.C_th, w.pano_w, w.pano_h, device=0)
+    try:
+        m.set_events(ev); m.upload_map(w.Gx, w.Gy)
+        m.eval_launch(traj_a); m.eval_finish(sync=False)
+        assert np.array_equal(fetch_starts(), starts_a_o)              # 1. the table of A is kept
+        m.form_active(w.thres_valid_pixel); m.form_accumulate(); m.form_finish(w.alpha)      # 2.
+        m.eval_launch(traj_b); m.eval_finish(sync=False)               # 3. a trial
+        m.rejectTrial()                                                # 4.
+        # the runs of B, pixel by pixel in REVERSE order: a placement that is not the identity
+        runs = np.diff(starts_b_o.astype(np.int64))
+        dst = np.ascontiguousarray((np.cumsum(runs[::-1])[::-1] - runs).astype(np.uint64))
+        out = np.full(int(starts_b_o[S]), np.nan)
+        by_pixel = lambda: L.emba_get_ep_by_pixel(m._ctx, out.ctypes.data_as(_lib._dp), dst.ctypes.data_as(C.POINTER(C.c_uint64)))
+        assert by_pixel() == _lib.ERR_STATE
+        assert np.isnan(out).all()
+        m.eval_launch(traj_b); m.eval_finish(sync=False)               # 5. B again, and the placement without fetching the starts first
+        assert by_pixel() == 0, L.emba_last_error(m._ctx)
+        starts_b = fetch_starts()
+        assert np.array_equal(starts_b, starts_b_o)
+        ep = m.get_ep()
+        want = np.full(ep.size, np.nan)
+        for q in np.flatnonzero(runs):
+            want[int(dst[q]): int(dst[q]) + runs[q]] = ep[starts_b[q]: starts_b[q + 1]]
+        assert not np.isnan(want).any() and np.array_equal(out, want)
+    finally:
+        m.close()
+
+
 def test_cg_session_ends_when_a_solve_takes_the_scratch():
     """A CG session (emba_cg_shard_*) keeps its vectors and record lists in the context's solve scratch.  A solve on the same context between
     emba_cg_shard_begin and the next step takes that scratch (the session's vectors could be re-allocated under it): the session has
