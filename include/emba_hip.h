@@ -388,8 +388,9 @@ emba_status emba_step(emba_ctx* ctx, const double* knots_xyzw_host, int32_t K, i
 emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
 
 /* Tuning and A/B switches: options by name, integer values, part of the ABI (EMBA_ABI_VERSION 2); an unknown name or a value out
- * of range is EMBA_ERR_INVALID_ARG.  Every option changes SPEED or the internal form only — results are the same under all of them (tests/test_gpu_parity.py
- * runs the parity cases under the non-default values).  Defaults are what the measurements under profiles/ chose.
+ * of range is EMBA_ERR_INVALID_ARG.  Every option changes SPEED or the internal form only — results are the same under all of them (tests/test_gpu_variants.py
+ * runs every kernel variant they select against the oracle; tests/option_matrix.py lists which test covers each option and value, or why none has to).
+ * Defaults are what the measurements under profiles/ chose.
  *   order          0 auto | 1 pixel order | 2 tile order of the device's event stream (takes effect at the next evaluation: the order is rebuilt)
  *   texel          0 auto | 1 pack every texel | 2 3x3 stencil on the fly | 3 pack inside the previous footprint's rectangle
  *   segpose        0 auto (= 2) | 1 per-batch pose table in pixel order | 2 per-event pose from the K-1 segment records
