@@ -89,6 +89,14 @@ SIGNATURES = {
     "emba_reconstruct_intensity": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "emba_render_map_images": (C.c_int, [C.c_void_p, C.c_double, _u8p, _u8p, _u8p, _u8p]),
     "emba_normalize_robust": (C.c_int, [C.c_void_p, _dp, C.c_size_t, C.c_double, _u8p, _dp, _dp]),
+    "emba_seq_upload": (C.c_int, [C.c_void_p, _u16p, _u16p, _u8p, _i64p, C.c_size_t, C.c_int32, _szp]),
+    "emba_seq_size": (C.c_int, [C.c_void_p, _szp]),
+    "emba_seq_free": (C.c_int, [C.c_void_p]),
+    "emba_seq_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _szp, _szp]),
+    "emba_set_events_seq": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]),
+    "emba_seq_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _u8p, _i64p]),
+    "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
+    "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "emba_count_map_ready": (C.c_int, [C.c_void_p]),
     "emba_count_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

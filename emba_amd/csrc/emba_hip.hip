@@ -29,6 +29,7 @@
 #include "solve_kernels.h"
 #include "poisson_kernels.h"
 #include "render_kernels.h"
+#include "sequence_kernels.h"
 
 using namespace emba;
 
@@ -279,6 +280,10 @@ struct emba_ctx {
     // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload
     DevBuf d_rstate, d_rhist, d_rcand;
     DevBuf d_img, d_nsrc;
+    // the whole (down-sampled) event sequence of a sliding-window run (sequence_kernels.h): uploaded once by emba_seq_upload, registered window by window by
+    // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload
+    struct { DevBuf x, y, pol, t, raw, status; size_t n = 0; } evseq;
+    DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 
 namespace {
@@ -878,15 +883,23 @@ void populate_pages_parallel(void* p, size_t bytes)
     copy_pool()->run([&](int h) { size_t lo, hi; CopyPool::piece(h, bytes, lo, hi); if (hi > lo) populate_pages((char*)p + lo, hi - lo); });
 }
 
+// the context's two pinned staging buffers (8 MB each) and the events that say when a transfer through one of them has completed
+constexpr size_t kStageBytes = (size_t)8 << 20;
+emba_status ensure_stage(emba_ctx* c)
+{
+    for (int k = 0; k < 2; ++k)
+        if (!c->h_stage[k]) { HIP_TRY(c, hipHostMalloc(&c->h_stage[k], kStageBytes, hipHostMallocDefault)); HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming)); }
+    return EMBA_OK;
+}
+
 // device -> host in pipelined chunks through the context's two pinned buffers: the DMA of chunk i + 1 runs while `consume(chunk, byte offset, bytes)` works on chunk i.
 // The stream must have been drained up to `src`'s producer.
 emba_status d2h_chunks(emba_ctx* c, const void* src, size_t bytes, const std::function<void(const void*, size_t, size_t)>& consume,
                        const std::function<void()>& while_first_chunk_travels = nullptr)
 {
     if (!bytes) return EMBA_OK;
-    constexpr size_t kChunk = (size_t)8 << 20;
-    for (int k = 0; k < 2; ++k)
-        if (!c->h_stage[k]) { HIP_TRY(c, hipHostMalloc(&c->h_stage[k], kChunk, hipHostMallocDefault)); HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming)); }
+    constexpr size_t kChunk = kStageBytes;
+    if (emba_status st = ensure_stage(c)) return st;
     hipStream_t s = c->stream;
     const size_t n = (bytes + kChunk - 1) / kChunk;
     auto len = [&](size_t i) { return std::min(kChunk, bytes - i * kChunk); };
@@ -3379,6 +3392,178 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
     if (rmax) *rmax = r[1];
     c->spun = false; c->knots_in_flight = false;
     return EMBA_OK;
+}
+
+// ---- the resident event sequence of a sliding-window run (sequence_kernels.h) ---------------------------------------------------
+// Raw events per upload chunk: 8 B + 2 B + 2 B + 1 B each, laid out [t | x | y | pol] in a pinned staging buffer (6.5 of its 8 MB).
+namespace {
+constexpr size_t kSeqChunk = (size_t)1 << 19;
+constexpr size_t kSeqOffX = kSeqChunk * 8, kSeqOffY = kSeqOffX + kSeqChunk * 2, kSeqOffPol = kSeqOffY + kSeqChunk * 2, kSeqRawBytes = kSeqOffPol + kSeqChunk;
+static_assert(kSeqRawBytes <= kStageBytes, "an upload chunk must fit a staging buffer");
+}  // namespace
+
+extern "C" emba_status emba_seq_free(emba_ctx* c)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->evseq.x.reset(); c->evseq.y.reset(); c->evseq.pol.reset(); c->evseq.t.reset(); c->evseq.raw.reset();
+    c->evseq.n = 0;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_seq_size(const emba_ctx* c, size_t* n)
+{
+    if (!c || !n) return EMBA_ERR_INVALID_ARG;
+    *n = c->evseq.n;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n, int32_t sampling_rate,
+                                       size_t* n_kept_out)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (n && (!x || !y || !pol || !t_ns)) return fail(c, EMBA_ERR_INVALID_ARG, "event arrays are NULL");
+    if (n >= 0xFFFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events for 32-bit indices");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const size_t rate = sampling_rate >= 2 ? (size_t)sampling_rate : 1;      // emba.cpp:282
+    const size_t n_kept = n / rate;
+    c->evseq.n = 0;      // (a second upload replaces the first; a failed one leaves none)
+    emba_status st;
+    if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRawBytes)) || (st = ensure<uint32_t>(c, c->evseq.status, 16)) ||
+        (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
+        (st = ensure<uint8_t>(c, c->evseq.pol, std::max<size_t>(n_kept, 1))) || (st = ensure<int64_t>(c, c->evseq.t, std::max<size_t>(n_kept, 1))))
+        return st;
+    uint32_t* d_err = c->evseq.status.as<uint32_t>();
+    HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
+    uint8_t* raw = c->evseq.raw.as<uint8_t>();
+    for (size_t k0 = 0, i = 0; k0 < n; k0 += kSeqChunk, ++i) {
+        const size_t m = std::min(kSeqChunk, n - k0);
+        uint8_t* h = static_cast<uint8_t*>(c->h_stage[i & 1]);
+        HIP_TRY(c, hipEventSynchronize(c->stage_ev[i & 1]));      // the transfer that last used this staging buffer has completed
+        std::memcpy(h, t_ns + k0, m * 8); std::memcpy(h + kSeqOffX, x + k0, m * 2); std::memcpy(h + kSeqOffY, y + k0, m * 2); std::memcpy(h + kSeqOffPol, pol + k0, m);
+        // (one stream: the copy of chunk i + 1 into `raw` is ordered behind the kernel that reads chunk i)
+        HIP_TRY(c, hipMemcpyAsync(raw, h, m * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffX, h + kSeqOffX, m * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffY, h + kSeqOffY, m * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffPol, h + kSeqOffPol, m, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipEventRecord(c->stage_ev[i & 1], s));
+        hipLaunchKernelGGL(emba_seq_ingest_kernel, dim3(nblocks(m)), dim3(256), 0, s, reinterpret_cast<const int64_t*>(raw), reinterpret_cast<const uint16_t*>(raw + kSeqOffX),
+                           reinterpret_cast<const uint16_t*>(raw + kSeqOffY), (const uint8_t*)(raw + kSeqOffPol), (long)m, (long)k0, k0 ? t_ns[k0 - 1] : (int64_t)0, c->sw, c->sh,
+                           (long)rate, (long)n_kept, c->evseq.x.as<uint16_t>(), c->evseq.y.as<uint16_t>(), c->evseq.pol.as<uint8_t>(), c->evseq.t.as<int64_t>(), d_err);
+        HIP_TRY(c, hipGetLastError());
+    }
+    uint32_t h_err[2];
+    HIP_TRY(c, hipMemcpyAsync(h_err, d_err, sizeof h_err, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (h_err[0] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[0], c->sw, c->sh);
+    if (h_err[1] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[1]);
+    c->evseq.n = n_kept;
+    if (n_kept_out) *n_kept_out = n_kept;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_seq_window(emba_ctx* c, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg_out, size_t* end_out)
+{
+    if (!c || !beg_out || !end_out) return c ? fail(c, EMBA_ERR_INVALID_ARG, "beg/end NULL") : EMBA_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = c->evseq.n, m = (n + kSeqProbe - 1) / kSeqProbe;
+    const int64_t a = t_beg_ns + 1000000, b = t_end_ns - 1000000;      // t_epsilon = ros::Duration(1e-3), emba.cpp:476-478
+    uint32_t h_res[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (m) {
+        emba_status st;
+        if ((st = ensure<uint32_t>(c, c->evseq.status, 16))) return st;
+        uint32_t* d_res = c->evseq.status.as<uint32_t>();
+        HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, 8, s));
+        hipLaunchKernelGGL(emba_seq_window_kernel, dim3((unsigned)std::min<size_t>(nblocks(m), 1024)), dim3(256), 0, s, (const int64_t*)c->evseq.t.as<int64_t>(), (long)n, a, b, d_res);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(h_res, d_res, sizeof h_res, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    // head: the first probe past a, or the first multiple of 100 >= n (emba.cpp:483-491)
+    const size_t jb = h_res[0] != 0xFFFFFFFFu ? h_res[0] : m, beg = kSeqProbe * jb;
+    size_t end = n;                                                      // no probe past b: the loop runs off the sequence, :504-505
+    if (jb < m && h_res[1] != 0xFFFFFFFFu) {
+        // tail: the first probe >= beg past b (every probe from beg on is past a; where b < a the search stops at beg itself)
+        const size_t je = std::max<size_t>(h_res[1], jb);
+        if (je == jb) return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (the tail search stops at its first probe, event %zu)", beg);
+        end = kSeqProbe * je - kSeqProbe;                                  // :500
+    }
+    if (beg > end) return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (it begins behind the last event)");
+    *beg_out = beg; *end_out = end;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_set_events_seq(emba_ctx* c, size_t beg, size_t end)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (beg > end || end > c->evseq.n) return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
+    return emba_set_events_dev(c, c->evseq.x.as<uint16_t>() + beg, c->evseq.y.as<uint16_t>() + beg, c->evseq.pol.as<uint8_t>() + beg, c->evseq.t.as<int64_t>() + beg, end - beg,
+                               nullptr, nullptr, nullptr, 0);
+}
+
+extern "C" emba_status emba_seq_get(emba_ctx* c, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (beg > end || end > c->evseq.n) return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t m = end - beg;
+    emba_status st;
+    if (x && (st = d2h_pageable(c, x, c->evseq.x.as<uint16_t>() + beg, m * 2))) return st;
+    if (y && (st = d2h_pageable(c, y, c->evseq.y.as<uint16_t>() + beg, m * 2))) return st;
+    if (pol && (st = d2h_pageable(c, pol, c->evseq.pol.as<uint8_t>() + beg, m))) return st;
+    if (t_ns && (st = d2h_pageable(c, t_ns, c->evseq.t.as<int64_t>() + beg, m * 8))) return st;
+    return EMBA_OK;
+}
+
+// ---- 3x3 median blur of the initial map (emba.cpp:357-364) -----------------------------------------------------------------------
+namespace {
+void launch_median3(emba_ctx* c, const double* src, int h, int w, double* dst)
+{
+    hipLaunchKernelGGL(emba_median3_kernel, dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)), dim3(256), 0, c->stream, src, h, w, dst);
+}
+}  // namespace
+
+extern "C" emba_status emba_median_blur3_map(emba_ctx* c)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map resident");
+    if (c->map_is_trial) return fail(c, EMBA_ERR_STATE, "a trial map is pending (emba_map_accept / emba_map_reject first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    emba_status st;
+    if ((st = ensure<double>(c, c->d_blur, c->npix))) return st;
+    // a map the caller bound (emba_bind_map_dev) is the caller's memory: the blurred map then becomes the context's own
+    const bool own = c->d_Gx_cur == c->d_Gx_own.as<double>() && c->d_Gy_cur == c->d_Gy_own.as<double>();
+    if (!own && ((st = ensure<double>(c, c->d_Gx_own, c->npix)) || (st = ensure<double>(c, c->d_Gy_own, c->npix)))) return st;
+    const double* src[2] = {c->d_Gx_cur, c->d_Gy_cur};
+    double* dst[2] = {c->d_Gx_own.as<double>(), c->d_Gy_own.as<double>()};
+    for (int k = 0; k < 2; ++k) {
+        launch_median3(c, src[k], c->H, c->W, c->d_blur.as<double>());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(dst[k], c->d_blur.as<double>(), c->npix * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    c->d_Gx = c->d_Gx_cur = dst[0]; c->d_Gy = c->d_Gy_cur = dst[1];
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_median_blur3(emba_ctx* c, const double* src_host, int32_t h, int32_t w, double* dst_host)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!src_host || !dst_host || h <= 0 || w <= 0 || h > 4 * 65535 || (size_t)h * (size_t)w >= 0x7FFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "src / dst NULL or bad size %d x %d", h, w);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)h * (size_t)w;
+    emba_status st;
+    if ((st = ensure<double>(c, c->d_nsrc, n)) || (st = ensure<double>(c, c->d_blur, n))) return st;
+    HIP_TRY(c, hipMemcpyAsync(c->d_nsrc.as<double>(), src_host, n * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_median3(c, c->d_nsrc.as<double>(), h, w, c->d_blur.as<double>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return d2h_pageable(c, dst_host, c->d_blur.as<double>(), n * sizeof(double));
 }
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------

@@ -1,0 +1,88 @@
+// emba_amd/csrc/sequence_kernels.h — the whole event sequence resident in HBM, and the 3x3 median blur of the initial map (gfx950, wave64).
+//
+// What EMBA::EMBA / EMBA::Run do to their inputs before and between time windows (reference src/emba/emba.cpp):
+//   * emba_seq_ingest_kernel   validation of a chunk of the raw sequence + the down-sampling of emba.cpp:281-304 as a strided gather
+//   * emba_seq_window_kernel   getEventSubset (emba.cpp:473-510): both cursors as min-reductions over every 100th timestamp
+//   * emba_median3_kernel      cv::medianBlur(., ., 3) on a float32 copy of a plane (emba.cpp:357-364)
+// All of it is bandwidth-bound, once-per-run or once-per-window work: one thread per element, coalesced loads, no tuning.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace emba {
+
+constexpr int kSeqProbe = 100;   // getEventSubset probes every 100th event (emba.cpp:485, 496)
+
+// One chunk of the raw sequence (n_chunk events, the first of them has the original index k0; t_prev: the timestamp in front of the chunk).
+// err[0] = smallest original index of an event outside the sensor, err[1] = smallest original index of an event earlier than its predecessor
+// (0xFFFFFFFF each when clean) — every raw event is checked, kept or not.  rate <= 1: every event is kept; otherwise the events with original
+// index rate-1, 2 rate-1, ... (sampling_count reaches the rate at the rate-th event, emba.cpp:287-298) go to slot (index + 1) / rate - 1.
+__global__ void emba_seq_ingest_kernel(const int64_t* __restrict__ t, const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, const uint8_t* __restrict__ pol,
+                                       long n_chunk, long k0, int64_t t_prev, int sw, int sh, long rate, long n_kept,
+                                       uint16_t* __restrict__ ox, uint16_t* __restrict__ oy, uint8_t* __restrict__ opol, int64_t* __restrict__ ot, uint32_t* __restrict__ err)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_chunk) return;
+    const long g = k0 + i;
+    const uint16_t xi = x[i], yi = y[i];
+    const int64_t ti = t[i];
+    if (xi >= sw || yi >= sh) atomicMin(err + 0, (uint32_t)g);
+    if (g > 0 && ti < (i > 0 ? t[i - 1] : t_prev)) atomicMin(err + 1, (uint32_t)g);
+    long dst = g;
+    if (rate > 1) {
+        if ((g + 1) % rate) return;
+        dst = (g + 1) / rate - 1;
+    }
+    if (dst >= n_kept) return;
+    ox[dst] = xi; oy[dst] = yi; opol[dst] = pol[i]; ot[dst] = ti;
+}
+
+// res[0] = smallest j with t[100 j] > a, res[1] = smallest j with t[100 j] > b, over the probes 100 j < n (0xFFFFFFFF each: none).  The
+// timestamps are sorted, so the first probe past a cursor IS the smallest one: a min-reduction, one atomic per wave that found any.
+__global__ __launch_bounds__(256) void emba_seq_window_kernel(const int64_t* __restrict__ t, long n, int64_t a, int64_t b, uint32_t* __restrict__ res)
+{
+    const long m = (n + kSeqProbe - 1) / kSeqProbe;
+    uint32_t ja = 0xFFFFFFFFu, jb = 0xFFFFFFFFu;
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (long)gridDim.x * blockDim.x) {
+        const int64_t tj = t[kSeqProbe * j];
+        if (tj > a) ja = min(ja, (uint32_t)j);
+        if (tj > b) jb = min(jb, (uint32_t)j);
+    }
+    for (int o = 32; o; o >>= 1) { ja = min(ja, (uint32_t)__shfl_xor((int)ja, o)); jb = min(jb, (uint32_t)__shfl_xor((int)jb, o)); }
+    if ((threadIdx.x & 63) == 0) {
+        if (ja != 0xFFFFFFFFu) atomicMin(res + 0, ja);
+        if (jb != 0xFFFFFFFFu) atomicMin(res + 1, jb);
+    }
+}
+
+// a <- min, b <- max: one exchange of the median network (no branch on data)
+__device__ __forceinline__ void med_exchange(float& a, float& b)
+{
+    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    a = lo; b = hi;
+}
+
+// dst = f64(median3x3(f32(src))) with replicated borders (cv::BORDER_REPLICATE: SURVEY Appendix A), h x w row-major; dst must not be src.
+// convertTo(CV_32F) rounds to nearest even, which is what the conversion below does; the median SELECTS one of the nine floats (19 exchanges:
+// the classic minimum-exchange network for nine values), so the result is exact.  NaN input is undefined, as in OpenCV.
+__global__ __launch_bounds__(256) void emba_median3_kernel(const double* __restrict__ src, int h, int w, double* __restrict__ dst)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    const int xm = max(x - 1, 0), xp = min(x + 1, w - 1);
+    const size_t r0 = (size_t)max(y - 1, 0) * w, r1 = (size_t)y * w, r2 = (size_t)min(y + 1, h - 1) * w;
+    float p0 = (float)src[r0 + xm], p1 = (float)src[r0 + x], p2 = (float)src[r0 + xp];
+    float p3 = (float)src[r1 + xm], p4 = (float)src[r1 + x], p5 = (float)src[r1 + xp];
+    float p6 = (float)src[r2 + xm], p7 = (float)src[r2 + x], p8 = (float)src[r2 + xp];
+    med_exchange(p1, p2); med_exchange(p4, p5); med_exchange(p7, p8);
+    med_exchange(p0, p1); med_exchange(p3, p4); med_exchange(p6, p7);
+    med_exchange(p1, p2); med_exchange(p4, p5); med_exchange(p7, p8);
+    med_exchange(p0, p3); med_exchange(p5, p8); med_exchange(p4, p7);
+    med_exchange(p3, p6); med_exchange(p1, p4); med_exchange(p2, p5);
+    med_exchange(p4, p7); med_exchange(p4, p2); med_exchange(p6, p4);
+    med_exchange(p4, p2);
+    dst[r1 + x] = (double)p4;
+}
+
+}  // namespace emba

@@ -1,0 +1,136 @@
+"""The caller of solve_time_window: EMBA::EMBA's preparation of its inputs and EMBA::Run, the sliding-window loop (reference src/emba/emba.cpp:281-304,
+309-323, 357-364, 400-532), without ROS.  A recording longer than one time window is cut into windows of `time_window_size` that advance by
+`sliding_window_stride`; the trajectory grows window by window, the map is carried from one window to the next on the device.
+
+With a device model (emba_amd.LEGM) the whole event sequence crosses to the device once (LEGM.set_sequence: checked and down-sampled there), every window
+is a range of it (LEGM.sequence_window -> EventWindow -> emba_set_events_seq) and the median blur of the initial map runs on the resident map.  Models
+without a resident sequence (the sharded host, the test suite's oracle model) get the same windows as host slices, through the numpy forms in emba_amd.io.
+
+Time cursors are integer nanoseconds by the rostime rules of SURVEY.md Appendix A (ros::Time(double) / ros::Duration(double): io.ros_time_ns)."""
+import dataclasses
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import io as emba_io
+from . import so3
+from .legm import EventWindow, LinearTrajectory
+from .solver import BASettings, LMSettings, solve_time_window
+
+
+@dataclass
+class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/parameters.md; t_start / t_end: start_time_s / stop_time_s + the time offset, emba.cpp:244-249
+    time_window_size: float
+    sliding_window_stride: float
+    dt_knots: float = 0.05
+    event_sampling_rate: int = 1
+    t_start: float = 0.0
+    t_end: float = 0.0
+    median_blur: bool = True    # emba.cpp:357-364 is unconditional in the reference; False keeps the initial map as given
+
+
+@dataclass
+class WindowResult:
+    index: int                  # count_window_
+    t_beg_ns: int
+    t_end_ns: int
+    beg: int                    # event subset [beg, end) of the (down-sampled) sequence
+    end: int
+    idx_cp_beg: int             # idx_cp_traj_beg_: first control pose of the whole trajectory this window refines
+    traj_init: LinearTrajectory     # the segment handed to solve_time_window
+    result: object              # its LMResult
+    setup_ms: float = float("nan")  # emba_last_setup_ms of the window's registration (device models)
+
+
+@dataclass
+class SequenceResult:
+    traj: LinearTrajectory      # the whole trajectory (traj_ptr_)
+    windows: list = field(default_factory=list)
+    n_events: int = 0           # events of the sequence after down-sampling
+
+
+def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm=LMSettings(), runtime_log=None, map_recorder=None, resident=True,
+                 resident_sequence=None, verbose=False):
+    """model: emba_amd.LEGM (or anything solve_time_window drives).  events: the whole recording (EventPacket, sorted).  pose_t [n] seconds, pose_q [n,4]
+    xyzw: the raw front-end poses (io.load_poses).  Gx, Gy: the initial map.  runtime_log / map_recorder: ONE object for the run — their counters run over
+    the windows like the reference's function statics.  resident: as in solve_time_window.  resident_sequence: keep the sequence on the device (default:
+    wherever the model can); False registers every window from a host slice (emba_set_events) instead."""
+    if resident_sequence is None:
+        resident_sequence = hasattr(model, "set_sequence")
+    pose_t = np.asarray(pose_t, dtype=np.float64)
+    pose_q = np.asarray(pose_q, dtype=np.float64).reshape(-1, 4)
+    pose_t_ns = np.array([emba_io.ros_time_ns(t) for t in pose_t], dtype=np.int64)      # std::map<ros::Time, SO3d>, pose_manager.cpp:41-80
+
+    # event down-sampling, emba.cpp:281-304
+    if resident_sequence:
+        n_seq = model.set_sequence(events, seq.event_sampling_rate)
+    else:
+        events = emba_io.downsample_events(events, seq.event_sampling_rate)
+        n_seq = events.size()
+
+    # time cursors, emba.cpp:309-323
+    win_size = emba_io.ros_time_ns(seq.time_window_size)
+    win_stride = emba_io.ros_time_ns(seq.sliding_window_stride)
+    t_BA_end = emba_io.ros_time_ns(seq.t_end)
+    t_win_beg = emba_io.ros_time_ns(seq.t_start)
+    t_win_end = t_win_beg + win_size
+    t_pose_beg, t_pose_end = t_win_beg, t_win_end
+    first_time_window = True
+    count_window = 0
+    cp_stride = int(round(seq.sliding_window_stride / seq.dt_knots))                     # :322 (std::round of a positive number)
+    # the whole trajectory: LinearTrajectory(config) keeps t_beg.toSec() and t_beg.toNSec(), dt_ns = int64(1e9 dt_knots)   trajectory.cpp:24-39
+    traj_t_beg = (t_win_beg // 1_000_000_000) + 1e-9 * (t_win_beg % 1_000_000_000)
+    traj_t0_ns, traj_dt_ns = t_win_beg, int(1e9 * seq.dt_knots)
+    knots = np.zeros((0, 4))
+    pose_latest = None
+
+    # median blur of the initial map, emba.cpp:357-364
+    if seq.median_blur:
+        if hasattr(model, "median_blur_map"):
+            model.upload_map(Gx, Gy)
+            model.median_blur_map()
+            Gx = Gy = None                                                              # "the resident map"
+        else:
+            Gx, Gy = emba_io.median_blur3(Gx), emba_io.median_blur3(Gy)
+
+    out = SequenceResult(None, [], n_seq)
+    while t_win_end < t_BA_end + 1_000_000:                                             # :406
+        # :409 getEventSubset
+        if resident_sequence:
+            beg, end = model.sequence_window(t_win_beg, t_win_end)
+            ev_win = EventWindow(beg, end)
+        else:
+            beg, end = emba_io.event_window(events.t_ns, t_win_beg, t_win_end)
+            ev_win = emba_io.slice_events(events, beg, end)
+        # :412-413 getPoseSubset: upper_bound(t_pose_beg) ... lower_bound(t_pose_end)
+        sel = (pose_t_ns > t_pose_beg) & (pose_t_ns < t_pose_end)
+        # :416-417 generateCtrlPosesLong over one-knot sub-intervals
+        new = emba_io.generate_ctrl_poses_long(pose_t[sel], pose_q[sel], t_pose_beg * 1e-9, t_pose_end * 1e-9, seq.dt_knots, seq.dt_knots)
+        if not first_time_window:                                                       # :420-428 align to the tail of the current trajectory
+            R0_inv = so3.inverse(new[0])
+            new = np.array([so3.mul(pose_latest, so3.mul(R0_inv, q)) for q in new])
+            new = new[1:]                                                               # :441
+        idx_cp_beg = count_window * cp_stride                                           # :432
+        knots = np.concatenate([knots, new])                                            # :444 pushbackCtrlPoses
+        # :447 cloneSegment(idx_cp_beg, size): start = int64(1e9 (t_beg + idx dt))   trajectory.cpp:61-70, 317-330
+        if not idx_cp_beg < len(knots):
+            raise ValueError(f"window {count_window}: no control poses behind index {idx_cp_beg}")      # CHECK_GT, trajectory.cpp:319
+        seg = LinearTrajectory.from_seconds(traj_t_beg + idx_cp_beg * seq.dt_knots, seq.dt_knots, knots[idx_cp_beg:].copy())
+        # :450 solveTimeWindow; the map of windows 1, 2, ... is the one the previous window left on the device
+        ba_win = dataclasses.replace(ba, first_time_window=first_time_window)
+        res = solve_time_window(model, seg, ev_win, Gx, Gy, ba_win, lm, verbose=verbose, resident=resident, runtime_log=runtime_log, map_recorder=map_recorder)
+        Gx = Gy = None
+        knots[idx_cp_beg:] = res.traj.knots_xyzw                                        # :453 replaceWith
+        setup_ms = model.setup_info()["set_events_ms"] if hasattr(model, "setup_info") else float("nan")
+        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms))
+        # :459-460 the latest pose: the whole trajectory 1 us before the window's end
+        pose_latest = so3.spline_evaluate(knots, traj_t0_ns, traj_dt_ns, t_win_end - 1000)
+        # :512-532 slideWindow
+        t_win_beg += win_stride
+        t_pose_beg = t_win_end
+        t_win_end += win_stride
+        t_pose_end = t_win_end
+        count_window += 1
+        first_time_window = False
+    out.traj = LinearTrajectory(knots, traj_t0_ns, traj_dt_ns)
+    return out

@@ -13,6 +13,10 @@
   normalize_robust / save_pgm    image_util::normalizeRobust          src/utils/image_utils.cpp:13-38   (8-bit display images of maps and of the
                                                                       Poisson-reconstructed panorama, solver.cpp:417-425; PGM instead of PNG)
   save_png                       cv::imwrite of an 8-bit image         solver.cpp:381-479 (record_data's map images; grey or RGB, standard-library zlib)
+  ros_time_ns                    ros::Time(double) / ros::Duration(double) -> toNSec()  (rostime, SURVEY Appendix A)
+  downsample_events              the event down-sampling of EMBA::EMBA   src/emba/emba.cpp:281-304
+  event_window                   EMBA::getEventSubset                 src/emba/emba.cpp:473-510
+  median_blur3                   convertTo(CV_32F) + cv::medianBlur(3) + convertTo(CV_64F) of the initial map   src/emba/emba.cpp:357-364
   save_events / load_events      a flat .npz replacing the rosbag of src/utils/rosbag_loading.cpp (x, y u16; polarity u8; t_ns i64, sorted)
 
 Host-side, O(K) or file-sized work; the per-event path is emba_amd.LEGM.
@@ -225,3 +229,55 @@ def load_events(path, t_min_ns=None, t_max_ns=None):
     if t_max_ns is not None:
         sel &= t <= t_max_ns
     return EventPacket(x[sel], y[sel], p[sel], t[sel])
+
+
+# ---- the sequence-level steps of EMBA::EMBA / EMBA::Run (numpy forms; the device forms are LEGM.set_sequence / sequence_window / median_blur_map) ------
+def ros_time_ns(t_sec):
+    """ros::Time(double) / ros::Duration(double) as integer nanoseconds (fromSec: sec = floor(t), nsec = round((t - sec) * 1e9), carried)."""
+    sec = int(np.floor(t_sec))
+    return sec * 1_000_000_000 + int(np.round((t_sec - sec) * 1e9))
+
+
+def downsample_events(events, rate):
+    """emba.cpp:281-304: with rate >= 2 exactly the events with index rate-1, 2 rate-1, ... survive (n // rate of them); otherwise all."""
+    rate = int(rate)
+    if rate < 2:
+        return events
+    sl = slice(rate - 1, None, rate)
+    return EventPacket(events.x[sl], events.y[sl], events.polarity[sl], events.t_ns[sl])
+
+
+def event_window(t_ns, t_beg_ns, t_end_ns):
+    """EMBA::getEventSubset (emba.cpp:473-510) on sorted timestamps: (beg, end) of the subset, both cursors moving 100 events at a time behind the
+    1-ms margins.  Raises ValueError where the reference's tail search stops at its first probe (its `-= 100` underflows size_t) or the subset would be a
+    reversed range — "window holds no events", as emba_seq_window reports it."""
+    t = np.asarray(t_ns, dtype=np.int64)
+    n = t.size
+    a, b = int(t_beg_ns) + 1_000_000, int(t_end_ns) - 1_000_000              # :476-478
+    probes = t[::100]
+    m = probes.size
+    jb = int(np.searchsorted(probes, a, side="right"))                       # :483-491: the first probe later than a
+    beg, end = 100 * jb, n
+    if jb < m:
+        je = max(int(np.searchsorted(probes, b, side="right")), jb)          # :494-503, starting from the head
+        if je < m:
+            if je == jb:
+                raise ValueError(f"window holds no events (the tail search stops at its first probe, event {beg})")
+            end = 100 * je - 100
+    if beg > end:
+        raise ValueError("window holds no events (it begins behind the last event)")
+    return beg, end
+
+
+def slice_events(events, beg, end):
+    return EventPacket(events.x[beg:end], events.y[beg:end], events.polarity[beg:end], events.t_ns[beg:end])
+
+
+def median_blur3(plane):
+    """emba.cpp:357-364 for one plane: float32 copy (round to nearest even), 3x3 median with replicated borders (cv::BORDER_REPLICATE, SURVEY Appendix A),
+    back to float64.  The median is one of the nine values, so the device form (emba_median_blur3) gives the same numbers."""
+    a = np.asarray(plane, dtype=np.float64).astype(np.float32)
+    h, w = a.shape
+    p = np.pad(a, 1, mode="edge")
+    nine = np.stack([p[dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3)])
+    return np.sort(nine, axis=0)[4].astype(np.float64)

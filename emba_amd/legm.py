@@ -47,6 +47,11 @@ class LinearTrajectory:
     def size(self):
         return self.knots_xyzw.shape[0]
 
+    def evaluate(self, t_ns):
+        """LinearTrajectory::evaluate (trajectory.cpp:122-147) on the host: the linear SO(3) spline at an integer-nanosecond time (so3.spline_evaluate)."""
+        from . import so3
+        return so3.spline_evaluate(self.knots_xyzw, self.t0_ns, self.dt_ns, t_ns)
+
 
 @dataclass
 class EventPacket:
@@ -58,6 +63,17 @@ class EventPacket:
 
     def size(self):
         return int(self.x.size)
+
+
+@dataclass
+class EventWindow:
+    """event_subset_ = events_[beg, end) (emba.cpp:508-509) of the sequence LEGM.set_sequence left on the device: what set_events takes instead of an
+    EventPacket in a sliding-window run (emba_set_events_seq)."""
+    beg: int
+    end: int
+
+    def size(self):
+        return int(self.end - self.beg)
 
 
 class LEGM:
@@ -97,7 +113,14 @@ class LEGM:
 
     # -- events (once per window) --------------------------------------------------------------
     def set_events(self, events, halo=None):
-        """events: EventPacket sorted by time.  halo: optional (x, y, batch_t_ns) arrays (multi-GPU shards)."""
+        """events: EventPacket sorted by time, or an EventWindow of the resident sequence (set_sequence).  halo: optional (x, y, batch_t_ns) arrays
+        (multi-GPU shards)."""
+        if isinstance(events, EventWindow):
+            if halo is not None:
+                raise ValueError("a window of the resident sequence takes no halo")
+            self._check(self._L.emba_set_events_seq(self._ctx, int(events.beg), int(events.end)))
+            self.n_events = events.size()
+            return
         x = np.ascontiguousarray(events.x, dtype=np.uint16)
         y = np.ascontiguousarray(events.y, dtype=np.uint16)
         pol = np.ascontiguousarray(events.polarity, dtype=np.uint8)
@@ -125,6 +148,55 @@ class LEGM:
         self._check(self._L.emba_set_events_dev(self._ctx, C.c_void_p(x_ptr), C.c_void_p(y_ptr), C.c_void_p(pol_ptr), C.c_void_p(t_ptr), int(n),
                                                 hx, hy, ht, nh))
         self.n_events = int(n)
+
+    # -- the whole sequence of a sliding-window run, resident on the device (emba.cpp:281-304, 473-510) ---------------------------
+    def set_sequence(self, events, sampling_rate=1):
+        """The whole recording to the device, once (emba_seq_upload): checked there and down-sampled as emba.cpp:281-304 does.  Returns the number of
+        events kept (n // rate)."""
+        x = np.ascontiguousarray(events.x, dtype=np.uint16)
+        y = np.ascontiguousarray(events.y, dtype=np.uint16)
+        pol = np.ascontiguousarray(events.polarity, dtype=np.uint8)
+        t = np.ascontiguousarray(events.t_ns, dtype=np.int64)
+        if not (x.size == y.size == pol.size == t.size):
+            raise ValueError("event arrays differ in length")
+        n = C.c_size_t(0)
+        self._check(self._L.emba_seq_upload(self._ctx, _p(x, _u16p), _p(y, _u16p), _p(pol, _u8p), _p(t, _i64p), x.size, int(sampling_rate), C.byref(n)))
+        return n.value
+
+    def sequence_size(self):
+        n = C.c_size_t(0)
+        self._check(self._L.emba_seq_size(self._ctx, C.byref(n)))
+        return n.value
+
+    def sequence_window(self, t_beg_ns, t_end_ns):
+        """EMBA::getEventSubset (emba.cpp:473-510) on the resident sequence: (beg, end).  Raises EmbaError where the window holds no events."""
+        b, e = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._L.emba_seq_window(self._ctx, int(t_beg_ns), int(t_end_ns), C.byref(b), C.byref(e)))
+        return b.value, e.value
+
+    def sequence_events(self, beg, end):
+        """[beg, end) of the resident sequence as an EventPacket (a download: tests, diagnostics)."""
+        n = int(end) - int(beg)
+        x, y = np.empty(max(n, 0), np.uint16), np.empty(max(n, 0), np.uint16)
+        pol, t = np.empty(max(n, 0), np.uint8), np.empty(max(n, 0), np.int64)
+        self._check(self._L.emba_seq_get(self._ctx, int(beg), int(end), _p(x, _u16p), _p(y, _u16p), _p(pol, _u8p), _p(t, _i64p)))
+        return EventPacket(x, y, pol, t)
+
+    def free_sequence(self):
+        self._check(self._L.emba_seq_free(self._ctx))
+
+    def median_blur_map(self):
+        """emba.cpp:357-364 on the map resident on the device, both planes (emba_median_blur3_map)."""
+        self._check(self._L.emba_median_blur3_map(self._ctx))
+
+    def medianBlur3(self, plane):
+        """The same 3x3 median (float32, replicated borders) of any 2-D float64 plane on the device: bit for bit io.median_blur3."""
+        a = np.ascontiguousarray(plane, dtype=np.float64)
+        if a.ndim != 2:
+            raise ValueError("medianBlur3 takes a 2-D plane")
+        out = np.empty_like(a)
+        self._check(self._L.emba_median_blur3(self._ctx, _p(a, _dp), a.shape[0], a.shape[1], _p(out, _dp)))
+        return out
 
     def setup_info(self):
         """Diagnostics of the once-per-window work (emba_last_setup_ms)."""

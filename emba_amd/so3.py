@@ -44,3 +44,18 @@ def log(q):
         n = np.sqrt(n2)
         f = (np.pi / n if w > 0 else -np.pi / n) if abs(w) < EPS else 2.0 * np.arctan(n / w) / n
     return f * q[:3]
+
+
+def spline_evaluate(knots_xyzw, t0_ns, dt_ns, t_ns):
+    """basalt::So3Spline<2>::evaluate (so3_spline.h:218-274) without the Jacobian, as LinearTrajectory::evaluate calls it (trajectory.cpp:122-147):
+    s = (t - t0) / dt and u = ((t - t0) % dt) / dt in integer nanoseconds, R(t) = R_s exp(u log(R_s^-1 R_s+1)).  Raises outside the knots, where the
+    reference asserts (so3_spline.h:221-230)."""
+    st = int(t_ns) - int(t0_ns)
+    if st < 0:
+        raise ValueError(f"t = {t_ns} ns lies before the spline's start {t0_ns} ns")
+    s, r = divmod(st, int(dt_ns))
+    if s + 2 > len(knots_xyzw):
+        raise ValueError(f"t = {t_ns} ns lies behind the last knot interval (s = {s}, {len(knots_xyzw)} knots)")
+    u = float(r) / float(dt_ns)
+    p0, p1 = knots_xyzw[s], knots_xyzw[s + 1]
+    return mul(p0, exp(u * log(mul(inverse(p0), p1))))

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Event-based mosaicing bundle adjustment of one time window on an MI355X, without ROS: the job of the reference's
+"""Event-based mosaicing bundle adjustment of one time window — or, with --window-size, of a whole recording in sliding windows — on an MI355X, without ROS: the job of the reference's
 `roslaunch emba <seq>.launch` back-end (src/emba/emba.cpp:29-330 + solver.cpp:11-368) for data already on disk.
 
   python examples/run_ba.py --demo out/                       # simulate a scene, perturb the trajectory, refine, write results
+  python examples/run_ba.py --demo out/ --window-size 0.3 --window-stride 0.1   # the same in sliding time windows (EMBA::Run, emba.cpp:400-532)
   python examples/run_ba.py --events ev.npz --poses init_traj.txt --map-dir init_map/ --calib calib.npz --out out/
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
@@ -43,6 +44,11 @@ def main():
     ap.add_argument("--runtime-log", action="store_true", help="write the reference's run-time records under <out>/final_results (every timed phase then ends in a host synchronisation)")
     ap.add_argument("--record-data", action="store_true", help="write the reference's record_data map images (PNG, rendered on the device) under <out>/ "
                     "at every LM iteration and at the end (rank 0)")
+    ap.add_argument("--window-size", type=float, help="time_window_size in seconds: refine the recording in sliding windows (EMBA::Run, emba.cpp:400-532); "
+                    "the event sequence then stays on the device and the map is carried from window to window")
+    ap.add_argument("--window-stride", type=float, help="sliding_window_stride in seconds (default: the window size)")
+    ap.add_argument("--sampling-rate", type=int, default=1, help="event_sampling_rate: keep every n-th event (emba.cpp:281-304; with --window-size)")
+    ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
     a = ap.parse_args()
     if a.alpha is None:
@@ -57,6 +63,10 @@ def main():
             knots[i] = so3.mul(so3.exp(rng.normal(size=3) * 0.01), knots[i])
         traj, truth = LinearTrajectory(knots, w.traj.t0_ns, w.traj.dt_ns), w.traj
         events, Gx, Gy, lut, sw, sh, C_th = w.events, w.Gx, w.Gy, w.lut, w.sensor_w, w.sensor_h, w.C_th
+        # the front end's raw poses of a sliding-window run: the perturbed trajectory sampled every 5 ms (9 poses inside every knot interval)
+        t_raw_ns = traj.t0_ns + 5_000_000 * np.arange((traj.dt_ns * (traj.size() - 1)) // 5_000_000, dtype=np.int64)
+        t, qs = t_raw_ns * 1e-9, np.array([traj.evaluate(int(tn)) for tn in t_raw_ns])
+        t_beg, t_end = traj.t0_ns * 1e-9, (traj.t0_ns + traj.dt_ns * (traj.size() - 1)) * 1e-9
     else:
         cal = np.load(a.calib)
         sw, sh = int(cal["width"]), int(cal["height"])
@@ -69,6 +79,7 @@ def main():
         sel = (t >= t_beg) & (t <= t_end)
         traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, eio.fit_ctrl_poses(t[sel], qs[sel], t_beg, a.dt_knots, num_cps))
         events = eio.load_events(a.events, int(t_beg * 1e9), traj.t0_ns + traj.dt_ns * (num_cps - 1) - 1)
+        t_end = t_beg + a.dt_knots * (num_cps - 1)
         truth, C_th = None, a.C_th
 
     H, W = Gx.shape
@@ -101,8 +112,23 @@ def main():
     # the reference's run-time records (final_results/runtime_{formEqs,solveEqs,objFuncs}.txt, iterations.txt: solver.cpp:105-151, 170-178, 205-223, 271-291)
     rlog = RuntimeLog(a.out) if (a.runtime_log and rank == 0) else None
     mrec = MapRecorder(a.out) if (a.record_data and rank == 0) else None
-    res = solve_time_window(model, traj, events, Gx, Gy, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True, runtime_log=rlog,
-                            map_recorder=mrec)
+    if a.window_size:
+        from emba_amd.driver import SequenceSettings, run_sequence
+        seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
+                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur)
+        sres = run_sequence(model, events, t, qs, Gx, Gy, seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
+                            verbose=a.verbose)
+        if rank == 0:
+            for wr in sres.windows:
+                print(f"window {wr.index}: [{wr.t_beg_ns * 1e-9:.3f}, {wr.t_end_ns * 1e-9:.3f}] s, events [{wr.beg}, {wr.end}), control poses from {wr.idx_cp_beg}, "
+                      f"{wr.result.iterations} LM iterations ({wr.result.reason or 'converged'}), cost {wr.result.cost_min:.6e}, set-up {wr.setup_ms:.2f} ms")
+        res = sres.windows[-1].result
+        res = type(res)(sres.traj, res.cost_min, sum(wr.result.iterations for wr in sres.windows), all(wr.result.converged for wr in sres.windows), res.log, res.reason)
+        if truth is not None:
+            traj = LinearTrajectory(traj.knots_xyzw[:sres.traj.size()], traj.t0_ns, traj.dt_ns)
+    else:
+        res = solve_time_window(model, traj, events, Gx, Gy, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True, runtime_log=rlog,
+                                map_recorder=mrec)
     dt = time.time() - t0
     if mrec is not None:
         mrec.close()

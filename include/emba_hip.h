@@ -258,6 +258,41 @@ emba_status emba_render_map_images(emba_ctx* ctx, double pct_discard, uint8_t* g
  * Needs a context only (no map, no events). */
 emba_status emba_normalize_robust(emba_ctx* ctx, const double* src_host, size_t n, double pct_discard, uint8_t* dst_host, double* rmin, double* rmax);
 
+/* ---- A whole recording refined in sliding windows: what EMBA::EMBA + EMBA::Run do around solveTimeWindow (emba.cpp:281-304, 357-364, 400-532) ----
+ * The event sequence crosses to the device ONCE and stays there; every time window is then registered from a range of it (overlapping windows
+ * re-read HBM, not host memory).  The library keeps no host copy of the sequence.  emba_amd/driver.py: run_sequence is the caller.
+ *
+ * emba_seq_upload: the event down-sampling of emba.cpp:281-304 and the checks of emba_set_events, on the device.  Host arrays of the WHOLE sequence (sorted
+ * by time) go through the context's pinned staging buffers in chunks; every raw event is checked (a pixel outside the sensor or a timestamp earlier than its
+ * predecessor anywhere in the sequence: EMBA_ERR_INVALID_ARG, and no sequence is resident afterwards).  sampling_rate <= 1 keeps every event; otherwise
+ * exactly the events with original index rate-1, 2 rate-1, ... survive (sampling_count reaches the rate at every rate-th event), *n_kept = n / rate
+ * (may be NULL).  A second upload replaces the first.  emba_seq_size: events resident (0: none).  emba_seq_free releases the memory (emba_destroy does too). */
+emba_status emba_seq_upload(emba_ctx* ctx, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n,
+                            int32_t sampling_rate, size_t* n_kept);
+emba_status emba_seq_size(const emba_ctx* ctx, size_t* n);
+emba_status emba_seq_free(emba_ctx* ctx);
+/* EMBA::getEventSubset (emba.cpp:473-510) on the resident sequence of length n, one launch: with a = t_beg_ns + 1 000 000 and b = t_end_ns - 1 000 000
+ * (t_epsilon = ros::Duration(1e-3); ros::Time comparison is integer comparison), *beg = the smallest multiple of 100 below n with t[beg] > a, or the first
+ * multiple of 100 >= n if there is none; end0 = the smallest multiple of 100 in [beg, n) with t[end0] > b; *end = end0 - 100 if it exists, else n.
+ * Where the reference's tail search stops at its first probe (end0 == beg) its `idx_ev_subset_end -= 100` underflows size_t (beg == 0: the subset silently
+ * becomes the whole sequence) or leaves end < beg, and where no event lies behind a and n is no multiple of 100 it also ends with end < beg: a vector
+ * built from a reversed iterator range, undefined behaviour.  Both are EMBA_ERR_INVALID_ARG ("window holds no events") here. */
+emba_status emba_seq_window(emba_ctx* ctx, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end);
+/* event_subset_ = events_[beg, end) (emba.cpp:508-509) handed to solveTimeWindow: registers that range of the resident sequence as the context's window,
+ * exactly as emba_set_events_dev does with pointers into it — no copy, no halo; emba_last_setup_ms reports it like any other registration.  The sequence
+ * stays valid across windows and across emba_set_events* calls. */
+emba_status emba_set_events_seq(emba_ctx* ctx, size_t beg, size_t end);
+/* [beg, end) of the resident sequence back to the host (tests, diagnostics): capacity end - beg each; any pointer may be NULL. */
+emba_status emba_seq_get(emba_ctx* ctx, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns);
+
+/* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
+ * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
+ * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
+ * the context's own).  EMBA_ERR_STATE without a resident map or while a trial map is pending.  emba_median_blur3: the same for any h x w host plane
+ * (row-major doubles; dst_host may be src_host); needs a context only. */
+emba_status emba_median_blur3_map(emba_ctx* ctx);
+emba_status emba_median_blur3(emba_ctx* ctx, const double* src_host, int32_t h, int32_t w, double* dst_host);
+
 /* Schur-complement solve: LEGM::solveNormalEq(A11, A12, A22_blocks, b1, b2, lambda, x1, x2), model.cpp:721-792,
  * on the device-resident normal equations of the last emba_form_finish (so after applyL2Reg, as in solver.cpp:130,190-202),
  * consuming the SPARSE A12 factors: S = A11m - A12 A22m^-1 A12^T is formed chunk-wise from per-pixel column pairs built from the
