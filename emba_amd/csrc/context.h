@@ -1,0 +1,326 @@
+// emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
+// the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
+// Included by emba_hip.hip and group.h; host code only.
+#pragma once
+#include "../../include/emba_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "solve_kernels.h"
+
+// Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
+// (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
+// The memory goes with the buffer (move-only); the context frees its buffers after draining its stream, the group each rank's with the rank's device current.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;     // capacity
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+    ~DevBuf() { reset(); }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    // at least n bytes (8 at the least); *fresh: the memory is new — uninitialised, or 0xFF bytes (written on `s`) with poison
+    hipError_t ensure(size_t n, bool* fresh = nullptr, bool poison = false, hipStream_t s = nullptr)
+    {
+        n = std::max<size_t>(n, 8);
+        if (fresh) *fresh = false;
+        if (p && bytes >= n) return hipSuccess;
+        reset();
+        hipError_t e = hipMalloc(&p, n);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        bytes = n;
+        if (fresh) *fresh = true;
+        return poison ? hipMemsetAsync(p, 0xFF, n, s) : hipSuccess;
+    }
+};
+
+// a record set: what one evaluation wrote, per candidate slot (records_valid: stamped with the evaluation number `stamp`)
+struct RecordSet { DevBuf rec, tag; uint32_t stamp = 0; };
+
+struct SolveLists { uint32_t* off = nullptr; emba::RecView sorted{}; };   // per-pixel record lists of a solve — sorted: the participating records in pixel order; off[i]: first record of pixel i
+
+// The normal equations currently in the pack, as the host knows them.  One value: an evaluation that sets the equations aside copies it (eq_saved), a
+// rejection copies it back — whatever describes "the equations in the pack" belongs here, so that it cannot be forgotten in one of the two directions.
+struct EqState {
+    bool active_done = false, accum_done = false;   // emba_form_active (and its count P resolved) / emba_form_accumulate ran
+    bool finish_done = false;         // emba_form_finish ran (L2 applied): the state the solvers work on
+    bool compact_valid = false;       // d_compact matches the active set (built on demand)
+    bool l2_fused = false;            // applyL2Reg has been applied to these blocks (by the gather of emba_step, or by emba_form_finish)
+    bool force_generic_a22 = false;   // decided by form_active, read by emba_form_accumulate: the per-pixel sums were consumed, A22 | b2 come from the records
+    size_t P = 0, pack_len = 0;
+    int K = 0, thres = 0, irls = 0; double eta = 0;
+};
+
+// The evaluation in flight: what is known on the host about the last emba_eval_launch and the products derived from it.  begin_evaluation() is the one reset.
+struct EvalState {
+    bool launched = false, done = false;   // emba_eval_launch ran / its inlier count and status word have reached the host
+    bool ep_deferred = false;     // residual compaction not launched yet (it rides along with the active-set kernels)
+    bool inl_pending = false, P_pending = false;   // counters enqueued for readback but not yet resolved (no host sync yet)
+    bool seq_armed = false;       // the pending counts come from kernels that publish the sequence number
+    bool inl_idx_valid = false;   // the per-event inlier numbers are produced on demand (dumps, caller-supplied ep): 4 B/event the step does not write
+    bool ep_valid = false;        // d_ep holds this evaluation's residuals in the reference's order (the resident step's Gram launch compacts them in its tail blocks)
+    bool ep_in_gram = false;      // ... the Gram launch of the equations being formed will do that (set by form_active's fused branch)
+    bool ep_after_gram = false;   // ... or, for windows too long for the tail form, the scan + compaction launches behind it
+    bool pix_starts_valid = false;   // h_pix_starts is emba_get_inlier_pixel_starts of this evaluation (for emba_get_ep_by_pixel)
+    uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
+    int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
+    bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
+};
+
+// Call options of the internal eval_launch / form_active (the extern "C" entry points pass the defaults).  irls, eta: the robust cost the per-pixel sums are
+// weighted with; keep_alt_set: the caller re-forms the equations itself, nothing of the previous ones can be gone back to — no second record set (ADVICE r3:
+// +12.8 GB at 100 M events for callers that can never reject)
+struct EvalOpts { int irls = 0; double eta = 0.0; bool keep_alt_set = false; };
+struct FormOpts {
+    bool consume = false, wants_ep = false;   // the resident step: this gather is the per-pixel sums' only reader; ... and ep is compacted with its Gram launch
+    const uint8_t* global_u8 = nullptr;       // emba_step_form_active: the all-reduced saturated byte counts activity is decided from
+    double fused_alpha = 0.0;                 // A22 | b2 come from the accumulator lines: applyL2Reg rides along with the gather
+};
+
+// What the host knows about the registered window (emba_set_events*).  free_window() is the one reset: a fresh value, less what it names as carried over.
+struct WindowState {
+    bool have_events = false;
+    size_t n_in = 0, n_used = 0, n_halo = 0, n_pm = 0, n_sorted = 0, n_batch = 0, n_cand = 0;   // n_pm: pm-order entries (events + halo); n_sorted: entries of the device order
+    long nblk = 0;                    // waves of the pixel-order warp kernel over the device order
+    long n_fblk = 0, n_fsup = 0;      // inlier-flag blocks of kFlagBlk pm-order entries; ... summed per kFlagSup of those
+    size_t P_prev = 0;                // active pixels of the last equations whose count the host has seen (this window): the Gram kernel's form is chosen by it
+    // tile order: inliers found outside their tile in the last evaluation; how often a window of this context was re-binned; the evaluation that did it last
+    size_t n_outside_tile = 0; int n_rebin = 0; uint32_t last_rebin_stamp = 0;
+};
+
+// The device order of the window and the decision that led to it (prepare_order).  new_order() is the one reset, at a new window and at every re-ordering.
+struct OrderState {
+    bool keys_ready = false; int64_t key_t0 = 0, key_dt = 0; int key_K = 0;   // the order is built, for this spline timing
+    uint32_t* d_ev_pix = nullptr; uint32_t* d_ev_batch = nullptr;   // borrowed — pixel order: the pm-order arrays; tile order: d_ev_pix_own / d_ev_batch_own
+    bool tile_order = false, have_ev_pm = false;
+    long n_chunks = 0;                // tile order: workgroups of the tiled warp kernel
+    size_t n_lead = 0;                // lead-in copies the tile order added
+    bool chunks_lpt = false;          // the chunk list is sorted longest first and walked in grid order (no XCD-contiguous remapping)
+    int tile_shape = 0; bool tile_fine = false;   // what the last tile search chose: index into kTileShapes, its finer pitch grid
+    double order_per_px = 0.0, order_lead_frac = 0.0;   // what the last order decision saw (diagnostics: emba_last_order_stats)
+    double order_inl_pred = 0.0;      // ... and the inlier fraction the predicted pixels give (the rule's estimate of what the pixel order pays per event)
+};
+
+// The key of the lists cache: whose records (packed: the ones this rank RECEIVED as the owner of the pixels [lo, lo + P), keyed by its own working set's stamp —
+// the ranks evaluate and form in lockstep; else the local ones, lo = 0), of which evaluation, over how many pixels and records.
+struct ListsKey {
+    bool packed = false; uint32_t stamp = 0; size_t P = 0, nrec = 0; long lo = 0;
+    bool operator==(const ListsKey& o) const { return packed == o.packed && stamp == o.stamp && P == o.P && nrec == o.nrec && lo == o.lo; }
+};
+
+// What the last solve left behind for the next one.
+struct SolveCache {
+    // the per-pixel record lists + pixel-ordered records of the last solve (lists.off, lists.sorted): a re-solve of the same equations with another
+    // lambda (a rejected LM trial, solver.cpp:340-352) reuses them; round 6: so does the SHARDED solve — a re-solve skips count, pack and the all-to-all
+    bool lists_valid = false; ListsKey key;
+    bool perm_valid = false;   // sv.perm holds the column order of U for the local Schur solve (solve_perm), valid with the lists
+    size_t perm_lo = 0, perm_n = 0;   // ... of the pixels [perm_lo, perm_lo + perm_n) of the active set (a rank's owned range in the sharded solve)
+    size_t x2_resident_P = (size_t)-1;   // d_x2 holds the x2 of the last solve on this context (for that many pixels)
+    int info = 0;              // last Schur solve: bit 0 a 2x2 block not positive definite (error), bit 1 a pivot of S vanished (zero update, like Eigen's ldlt)
+    // emba_cg_shard_*: the session's sizes; its vectors are the solve scratch (sv), its lists the lists cache.  active: begin succeeded, and since then neither
+    // another solve nor a failed emba_cg_shard_* call has taken the scratch
+    struct CgShard { bool active = false; int rank = 0, n_ranks = 1, n = 0, skip = 0; size_t lo = 0, npix = 0, Nl = 0; double lambda = 0; } cg;
+    void invalidate() { lists_valid = false; perm_valid = false; }   // the records or the active set changed: neither the lists nor the column order hold
+};
+
+struct emba_ctx {
+    emba_cfg cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string err;
+
+    int sw = 0, sh = 0, W = 0, H = 0;
+    size_t S = 0, npix = 0;
+    double fx = 0, fy = 0, cx = 0, cy = 0, C_th = 0, outlier_px = 10.0;
+    double fov_x = M_PI, fov_y = M_PI;    // the sensor's field of view (rad), from the bearing LUT
+
+    // persistent device buffers
+    DevBuf d_lut;
+    DevBuf d_texel;
+    DevBuf d_Gx_own, d_Gy_own;
+    const double* d_Gx = nullptr; const double* d_Gy = nullptr;   // the map planes the next evaluation reads (current or trial)
+    const double* d_Gx_cur = nullptr; const double* d_Gy_cur = nullptr;   // current (accepted) map: own upload, bound, or accepted trial
+    DevBuf d_Gx_trial, d_Gy_trial; bool map_is_trial = false;
+    SolveCache solve;         // what the last solve left behind
+    int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
+    double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of emba_costs, written by the kernel itself
+    double* h_cost_dev = nullptr; DevBuf d_cost_acc; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
+    DevBuf d_x2;              // the x2 of the last solve on this context (solve.x2_resident_P)
+    DevBuf d_count_own; int32_t* d_count = nullptr;
+    bool counts_raw = false;   // the count map holds the warp kernel's markers, not yet the counts (see ensure_counts)
+    DevBuf d_pixacc; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
+    bool pixacc_clean = false;     // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
+    bool pixacc_consumed = false;  // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
+    int32_t count_mark = 0;        // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
+    int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
+    int use_texel = 0;    // what the current evaluation uses: 0 fly, 1 full pack, 3 rectangle
+    DevBuf d_rect;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
+    DevBuf d_blk_rect;   // per prep-block boxes
+    DevBuf d_compact, d_active_bits;   // 1 bit per pixel: count >= thres of the current active set
+    DevBuf d_active;
+    DevBuf d_ablk_cnt, d_ablk_off; size_t n_ablk = 0;
+    DevBuf d_pack_own;
+    double* d_pack = nullptr; size_t pack_cap = 0; bool pack_bound = false;   // d_pack_own, or the caller's buffer (emba_bind_exchange_buffers)
+    DevBuf d_knots;
+    int* d_err = nullptr;           // status word of the CURRENT evaluation: one of the two words of d_err2 (they alternate: an evaluation's first launch
+    DevBuf d_err2;                  // clears the NEXT evaluation's word while its own pose threads may already be setting bits of the current one)
+    uint32_t eval_seq = 0;
+    DevBuf d_total;                 // [0] inliers, [1] active pixels
+    DevBuf d_scalar;                // cost reductions
+    std::vector<uint32_t> h_pix_starts;   // emba_get_inlier_pixel_starts of the current evaluation (ev.pix_starts_valid), for emba_get_ep_by_pixel
+    void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
+    int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3] step sequence number
+    int seq = 0;                    // sequence number of the last step whose post-warp kernels publish [3]
+    bool spun = false;              // counts were taken by polling: later kernels of the stream may still be running
+    int* h_pinned_dev = nullptr;    // the same memory through its device pointer
+    double* h_knots_dev = nullptr;  // device pointer of the pinned control-pose staging buffer
+
+    // per-window (set_events) state — all of it lives on the device (order_kernels.h); the buffers outlive the window, what the host knows of it is win / order
+    WindowState win;
+    OrderState order;
+    bool have_map = false;
+    DevBuf d_pm_pix, d_pm_batch, d_pm_orig;                                                         // pm-order = (sensor pixel, time): the reference's per-pixel vectors laid end to end
+    DevBuf d_ev_slot;                                                                               // device order: record slot per entry
+    DevBuf d_ev_pix_own, d_ev_batch_own;                                                            // tile order: the arrays order.d_ev_pix / d_ev_batch point to
+    DevBuf d_ev_pm;                                                                                 // tile order only: entry -> pm index (order.have_ev_pm)
+    DevBuf d_cp, d_batch_u;                                                                         // control-pose index (= spline segment) and spline parameter per batch
+    DevBuf d_ev_u, d_ev_seg;                                                                        // tile order: the same per entry of the device order
+    DevBuf d_chunks;                                                                                // tile order: one per workgroup of the tiled warp kernel (order.n_chunks)
+    int segpose_mode = 0;      // option segpose (A/B; 0 auto = yes, 1 no, 2 yes): pixel order evaluates the pose per event from segment records (default: yes)
+    bool segpose = false;      // ... in the current evaluation
+    int order_mode = 0;        // option order: 0 auto, 1 pixel, 2 tile
+    DevBuf d_batch_t, d_pose;   // pose table: 112 B per batch (pixel order; the tile order only uses it to predict the bins)
+    DevBuf d_seg;                                             // tile order: per-segment constants the tiled kernel evaluates each event's pose from (12 doubles per segment)
+    int step_gather = 2;    // option step_gather: how emba_step writes its active set + A22 | b2 rows — 0 the sweeping kernel (emba_active_write_kernel), 1 the list-driven
+                            // gather as a kernel of its own, 2 (default) the list-driven gather as the head of the compact Gram kernel
+    DevBuf d_seg_act;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
+    bool aw_in_gram = false; emba::ActiveWriteParams aw_saved{};   // the gather of the running step, to be issued with its Gram launch (emba_form_accumulate)
+    int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
+    int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
+    int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
+    DevBuf d_slot_key; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
+    // Two record sets (a rejected LM trial must not cost a re-evaluation).  `work` is the WORKING set: what
+    // the last evaluation wrote and what formNormalEq and the solvers read.  An evaluation that would overwrite records the current normal
+    // equations were formed from (eq.accum_done) first sets them aside — eq_saved = eq, and the other record set is swapped in; emba_map_reject /
+    // emba_trial_reject swaps back and takes eq = eq_saved, so the solver can be called again with a larger lambda on untouched equations
+    // (solver.cpp:340-352 reuses A, b).  Nothing else needs a second copy: the pack, the active set and the compact index are written by
+    // formNormalEq only, which never runs on a rejected trial.
+    RecordSet work, alt;
+    bool eq_in_alt = false;   // the equations in the pack (eq_saved) belong to the OTHER set: a trial evaluation has been written since
+    EqState eq, eq_saved;     // the equations in the pack; ... as they were when a trial evaluation set them aside (eq_in_alt)
+    EvalState ev;             // the evaluation in flight
+    DevBuf d_e_sorted, d_flag, d_inl_idx;
+    int opt_poison = 0;          // option poison = 1 (tests): every NEW device allocation of the context is filled with 0xFF bytes
+    int opt_tile_reserve = 2, opt_tile_shape = -1, opt_tile_fine = -1, opt_tile_min_events = 1650000, opt_tile_chunk = 0;   // emba_set_option: the tile order's window rule (prepare_order)
+    int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
+    int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
+    DevBuf d_fblk_cnt, d_fblk_off;   // inlier-flag counts per kFlagBlk pm-order entries (win.n_fblk)
+    DevBuf d_fsup; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (win.n_fsup; two arrays used alternately; fsup_half: the one the last launch A filled)
+    DevBuf d_ep;
+    double set_events_ms = 0, prepare_ms = 0;   // wall time of the last emba_set_events[_dev] / order preparation (diagnostics)
+
+    // per-iteration state
+    size_t n_inliers = 0;
+    int cost_irls = 0; double cost_eta = 0.0;   // robust cost declared with emba_set_cost: what the NEXT evaluation weights its per-pixel sums with
+    double* h_knots = nullptr; int h_knots_cap = 0; hipEvent_t knots_copied = nullptr; bool knots_in_flight = false;   // pinned staging for the control poses
+
+    // timing
+    hipEvent_t ev_start[8]{}, ev_stop[8]{};
+    bool kernel_timing = false;
+    hipEvent_t kt_sets[16][5]{}; hipEvent_t* kt = kt_sets[0]; int kt_slot = 0;  // per slot: warp start/stop, accum start/stop (emba_enable_kernel_timing), [4]: in front of the step's first launch
+    bool kt_valid[16][3]{};
+    bool kt_all = false;        // emba_kernel_timing_all: also record [4], so that the four intervals [4]->[0]->[1]->[2]->[3] tile the whole step (prep | warp | post-warp | Gram)
+    hipEvent_t cal_ev[2]{};     // emba_bracket_overhead_us / emba_clock_probe
+    DevBuf d_probe;
+    bool kt_warp_valid = false, kt_accum_valid = false;
+    int n_cu = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+    int ablate = 0;  // diagnostics builds only (-DEMBA_DIAG): EMBA_ABLATE bit mask; always 0 in the shipped library
+    // ---- grow-only scratch, by phase.  A buffer named for two roles serves both (no phase holds it while the other runs): sharing keeps the peak down.
+    struct {   // once-per-window order preparation (set_events_core, prepare_order) and the device scan / sort
+        DevBuf scan_sums, scan_offs;   // dev_scan
+        DevBuf sort_hist;              // dev_sort
+        DevBuf status;                 // 64 B of status words: set_events_core, prepare_order
+        DevBuf keys[2], vals[2];       // radix-sort pairs: set_events_core (pm-order), prepare_order (tile order, record slots)
+        DevBuf flags;                  // set_events_core: candidate flags; prepare_order: chain-head flags, the tile binning's emit flags, candidate flags
+        DevBuf pos;                    // set_events_core: candidate positions; prepare_order: head / emit positions, candidate positions
+        DevBuf bin, used;              // prepare_order: tile of every entry, occupied bins
+        DevBuf bin_start_or_x;         // prepare_order: first entry of every tile; emba_set_events: upload of x
+        DevBuf pred_or_y;              // prepare_order: predicted pixels; emba_set_events: upload of y
+        DevBuf heads_or_pol;           // prepare_order: chain heads; emba_set_events: upload of the polarities
+        DevBuf halo;                   // emba_set_events: upload of the halo (times, x, y)
+    } ord;
+    struct Solve {   // the solvers (an LM loop solves every iteration).  Schur: emba_solve_normal_eq, emba_solve_shard_*; CG: emba_solve_normal_eq_cg, emba_cg_shard_*
+        DevBuf S_or_x, rhs_or_r, U_or_p, y_or_z, cf_or_t, x2_or_invd;   // Schur: S_aug, x1, U block, y, 2x2 factors, x2; CG: x, r, p, z, t, inverse diagonal
+        DevBuf info_or_sc;             // Schur: status word; CG: device scalars
+        DevBuf slab, mask, list, cnt, range, pair_items, items;         // schur_accumulate: the block-sparse SYRK
+        DevBuf perm_cnt, perm_tick, perm;   // solve_perm (perm: the column order, valid with solve.perm_valid)
+        DevBuf shard_cnt;              // emba_solve_shard_count -> emba_solve_shard_pack: counts, offsets, cursors per rank
+    } sv;
+    struct {   // build_lists.  off / sorted are the lists cache (solve.lists_valid) that a re-solve, emba_solve_shard_cached / _finish and a CG session read
+        DevBuf off, cursor, sorted, tmp;
+    } lists;
+    struct {   // downloads
+        DevBuf out;          // emba_get_map_active, emba_get_inlier_pixels, the pixel list of emba_get_inlier_pixel_starts
+        DevBuf pix_starts;   // emba_get_inlier_pixel_starts
+        DevBuf A22b2;        // emba_form_finish: unpacked A22 | b2
+    } dl;
+    // f3 (Poisson reconstruction): sine matrices and eigenvalues of the two transform lengths, scratch planes
+    DevBuf d_SH, d_SW, d_lamH, d_lamW, d_pF, d_pT, d_pGx, d_pGy;
+    DevBuf d_thomas;              // Thomas factors of T_W + lambda1[i] I (W x H)
+    DevBuf d_Sfold;               // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
+    DevBuf d_pE;                  // [E | O] of the folded transform (W x H/2 each)
+    // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload
+    DevBuf d_rstate, d_rhist, d_rcand;
+    DevBuf d_img, d_nsrc;
+    // the whole (down-sampled) event sequence of a sliding-window run (sequence_kernels.h): uploaded once by emba_seq_upload, registered window by window by
+    // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload
+    struct { DevBuf x, y, pol, t, raw, status; size_t n = 0; } evseq;
+    DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
+};
+
+namespace {
+
+thread_local std::string g_create_error;   // the message of a failure that has no context to keep it (emba_create)
+
+emba_status fail(emba_ctx* c, emba_status st, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf; else g_create_error = buf;
+    return st;
+}
+
+#define HIP_TRY(c, call)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail((c), EMBA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                     \
+    } while (0)
+
+// a grow-only buffer of the context (DevBuf) holds at least `count` elements of T.  Option poison (tests): new memory reads as NaN / 0xFFFFFFFF, so that a
+// read of never-written memory shows.
+template <typename T>
+emba_status ensure(emba_ctx* c, DevBuf& b, size_t count, bool* fresh = nullptr)
+{
+    const hipError_t e = b.ensure(count * sizeof(T), fresh, c->opt_poison != 0, c->stream);
+    if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
+    return EMBA_OK;
+}
+
+inline unsigned nblocks(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>((n + per - 1) / per, 1); }
+
+}  // namespace

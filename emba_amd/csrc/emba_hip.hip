@@ -30,300 +30,36 @@
 #include "poisson_kernels.h"
 #include "render_kernels.h"
 #include "sequence_kernels.h"
+#include "context.h"
 
 using namespace emba;
 
 namespace {
 
-thread_local std::string g_create_error;
-
-}  // namespace
-
-// Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
-// (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
-// The memory goes with the buffer (move-only); the context frees its buffers after draining its stream, the group each rank's with the rank's device current.
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;     // capacity
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
-    ~DevBuf() { reset(); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    // at least n bytes (8 at the least); *fresh: the memory is new — uninitialised, or 0xFF bytes (written on `s`) with poison
-    hipError_t ensure(size_t n, bool* fresh = nullptr, bool poison = false, hipStream_t s = nullptr)
-    {
-        n = std::max<size_t>(n, 8);
-        if (fresh) *fresh = false;
-        if (p && bytes >= n) return hipSuccess;
-        reset();
-        hipError_t e = hipMalloc(&p, n);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        bytes = n;
-        if (fresh) *fresh = true;
-        return poison ? hipMemsetAsync(p, 0xFF, n, s) : hipSuccess;
-    }
-};
-
-// a record set: what one evaluation wrote, per candidate slot (records_valid: stamped with the evaluation number `stamp`)
-struct RecordSet { DevBuf rec, tag; uint32_t stamp = 0; };
-
-struct SolveLists { uint32_t* off = nullptr; emba::RecView sorted{}; };   // per-pixel record lists of a solve — sorted: the participating records in pixel order; off[i]: first record of pixel i
-
-// The normal equations currently in the pack, as the host knows them.  One value: an evaluation that sets the equations aside copies it (eq_saved), a
-// rejection copies it back — whatever describes "the equations in the pack" belongs here, so that it cannot be forgotten in one of the two directions.
-struct EqState {
-    bool active_done = false, accum_done = false;   // emba_form_active (and its count P resolved) / emba_form_accumulate ran
-    bool finish_done = false;         // emba_form_finish ran (L2 applied): the state the solvers work on
-    bool compact_valid = false;       // d_compact matches the active set (built on demand)
-    bool l2_fused = false;            // applyL2Reg has been applied to these blocks (by the gather of emba_step, or by emba_form_finish)
-    bool force_generic_a22 = false;   // decided by form_active, read by emba_form_accumulate: the per-pixel sums were consumed, A22 | b2 come from the records
-    size_t P = 0, pack_len = 0;
-    int K = 0, thres = 0, irls = 0; double eta = 0;
-};
-
-// The evaluation in flight: what is known on the host about the last emba_eval_launch and the products derived from it.  begin_evaluation() is the one reset.
-struct EvalState {
-    bool launched = false, done = false;   // emba_eval_launch ran / its inlier count and status word have reached the host
-    bool ep_deferred = false;     // residual compaction not launched yet (it rides along with the active-set kernels)
-    bool inl_pending = false, P_pending = false;   // counters enqueued for readback but not yet resolved (no host sync yet)
-    bool seq_armed = false;       // the pending counts come from kernels that publish the sequence number
-    bool inl_idx_valid = false;   // the per-event inlier numbers are produced on demand (dumps, caller-supplied ep): 4 B/event the step does not write
-    bool ep_valid = false;        // d_ep holds this evaluation's residuals in the reference's order (the resident step's Gram launch compacts them in its tail blocks)
-    bool ep_in_gram = false;      // ... the Gram launch of the equations being formed will do that (set by form_active's fused branch)
-    bool ep_after_gram = false;   // ... or, for windows too long for the tail form, the scan + compaction launches behind it
-    bool pix_starts_valid = false;   // h_pix_starts is emba_get_inlier_pixel_starts of this evaluation (for emba_get_ep_by_pixel)
-    uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
-    int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
-    bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
-};
-
-// Call options of the internal eval_launch / form_active (the extern "C" entry points pass the defaults).  irls, eta: the robust cost the per-pixel sums are
-// weighted with; keep_alt_set: the caller re-forms the equations itself, nothing of the previous ones can be gone back to — no second record set (ADVICE r3:
-// +12.8 GB at 100 M events for callers that can never reject)
-struct EvalOpts { int irls = 0; double eta = 0.0; bool keep_alt_set = false; };
-struct FormOpts {
-    bool consume = false, wants_ep = false;   // the resident step: this gather is the per-pixel sums' only reader; ... and ep is compacted with its Gram launch
-    const uint8_t* global_u8 = nullptr;       // emba_step_form_active: the all-reduced saturated byte counts activity is decided from
-    double fused_alpha = 0.0;                 // A22 | b2 come from the accumulator lines: applyL2Reg rides along with the gather
-};
-
-struct emba_ctx {
-    emba_cfg cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-
-    int sw = 0, sh = 0, W = 0, H = 0;
-    size_t S = 0, npix = 0;
-    double fx = 0, fy = 0, cx = 0, cy = 0, C_th = 0, outlier_px = 10.0;
-    double fov_x = M_PI, fov_y = M_PI;    // the sensor's field of view (rad), from the bearing LUT
-
-    // persistent device buffers
-    DevBuf d_lut;
-    DevBuf d_texel;
-    DevBuf d_Gx_own, d_Gy_own;
-    const double* d_Gx = nullptr; const double* d_Gy = nullptr;   // the map planes the next evaluation reads (current or trial)
-    const double* d_Gx_cur = nullptr; const double* d_Gy_cur = nullptr;   // current (accepted) map: own upload, bound, or accepted trial
-    DevBuf d_Gx_trial, d_Gy_trial; bool map_is_trial = false;
-    // the per-pixel record lists + pixel-ordered records of the last LOCAL solve (lists.off, lists.sorted): a re-solve of the same equations with another
-    // lambda (a rejected LM trial, solver.cpp:340-352) reuses them
-    bool lists_valid = false; uint32_t lists_stamp = 0; size_t lists_P = 0, lists_nrec = 0;
-    // round 6: ... and so does the SHARDED solve — lists_packed: the workspaces hold the records this rank RECEIVED as the owner of the pixels
-    // [lists_lo, lists_lo + lists_P), keyed by its own working set's stamp (the ranks evaluate and form in lockstep); a re-solve skips count, pack and the all-to-all
-    bool lists_packed = false; long lists_lo = 0;
-    // emba_cg_shard_*: the session's sizes; its vectors are the solve scratch (sv), its lists the lists cache.  active: begin succeeded, and since then neither
-    // another solve nor a failed emba_cg_shard_* call has taken the scratch
-    struct CgShard { bool active = false; int rank = 0, n_ranks = 1, n = 0, skip = 0; size_t lo = 0, npix = 0, Nl = 0; double lambda = 0; } cg;
-    size_t perm_lo = 0, perm_n = 0;   // ... of the pixels [perm_lo, perm_lo + perm_n) of the active set (a rank's owned range in the sharded solve)
-    bool perm_valid = false;   // sv.perm holds the column order of U for the local Schur solve (solve_perm), valid with the lists
-    int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
-    double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of emba_costs, written by the kernel itself
-    double* h_cost_dev = nullptr; DevBuf d_cost_acc; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
-    DevBuf d_x2; size_t x2_resident_P = (size_t)-1;   // x2_resident_P: d_x2 holds the x2 of the last solve on this context (for that many pixels)
-    DevBuf d_count_own; int32_t* d_count = nullptr;
-    bool counts_raw = false;   // the count map holds the warp kernel's markers, not yet the counts (see ensure_counts)
-    DevBuf d_pixacc; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
-    bool pixacc_clean = false;     // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
-    bool pixacc_consumed = false;  // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
-    int32_t count_mark = 0;        // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
-    int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
-    int use_texel = 0;    // what the current evaluation uses: 0 fly, 1 full pack, 3 rectangle
-    DevBuf d_rect;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
-    DevBuf d_blk_rect;   // per prep-block boxes
-    DevBuf d_compact, d_active_bits;   // 1 bit per pixel: count >= thres of the current active set
-    DevBuf d_active;
-    DevBuf d_ablk_cnt, d_ablk_off; size_t n_ablk = 0;
-    DevBuf d_pack_own;
-    double* d_pack = nullptr; size_t pack_cap = 0; bool pack_bound = false;   // d_pack_own, or the caller's buffer (emba_bind_exchange_buffers)
-    DevBuf d_knots;
-    int* d_err = nullptr;           // status word of the CURRENT evaluation: one of the two words of d_err2 (they alternate: an evaluation's first launch
-    DevBuf d_err2;                  // clears the NEXT evaluation's word while its own pose threads may already be setting bits of the current one)
-    uint32_t eval_seq = 0;
-    DevBuf d_total;                 // [0] inliers, [1] active pixels
-    DevBuf d_scalar;                // cost reductions
-    std::vector<uint32_t> h_pix_starts;   // emba_get_inlier_pixel_starts of the current evaluation (ev.pix_starts_valid), for emba_get_ep_by_pixel
-    void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
-    int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3] step sequence number
-    int seq = 0;                    // sequence number of the last step whose post-warp kernels publish [3]
-    bool spun = false;              // counts were taken by polling: later kernels of the stream may still be running
-    int* h_pinned_dev = nullptr;    // the same memory through its device pointer
-    double* h_knots_dev = nullptr;  // device pointer of the pinned control-pose staging buffer
-
-    // per-window (set_events) state — all of it lives on the device (order_kernels.h)
-    bool have_events = false, have_map = false;
-    size_t n_in = 0, n_used = 0, n_halo = 0, n_pm = 0, n_sorted = 0, n_batch = 0, n_cand = 0;   // n_pm: pm-order entries (events + halo); n_sorted: entries of the device order
-    long nblk = 0;
-    DevBuf d_pm_pix, d_pm_batch, d_pm_orig;                                                         // pm-order = (sensor pixel, time): the reference's per-pixel vectors laid end to end
-    uint32_t* d_ev_pix = nullptr; uint32_t* d_ev_batch = nullptr; DevBuf d_ev_slot;                 // device order (== pm-order arrays in pixel order; own arrays in tile order)
-    DevBuf d_ev_pix_own, d_ev_batch_own;                                                            // tile order: the arrays d_ev_pix / d_ev_batch point to
-    DevBuf d_ev_pm;                                                                                 // tile order only: entry -> pm index
-    bool have_ev_pm = false;
-    DevBuf d_cp, d_batch_u;                                                                         // control-pose index (= spline segment) and spline parameter per batch
-    DevBuf d_ev_u, d_ev_seg;                                                                        // tile order: the same per entry of the device order
-    DevBuf d_chunks; long n_chunks = 0;                                                             // tile order: one per workgroup of the tiled warp kernel
-    int segpose_mode = 0;      // option segpose (A/B; 0 auto = yes, 1 no, 2 yes): pixel order evaluates the pose per event from segment records (default: yes)
-    bool segpose = false;      // ... in the current evaluation
-    bool chunks_lpt = false;   // the chunk list is sorted longest first and walked in grid order (no XCD-contiguous remapping)
-    double order_inl_pred = 0.0;   // ... and the inlier fraction the predicted pixels give (the rule's estimate of what the pixel order pays per event)
-    double order_per_px = 0.0, order_lead_frac = 0.0;   // what the last order decision saw (diagnostics: emba_last_order_stats)
-    bool tile_order = false; int order_mode = 0;   // option order: 0 auto, 1 pixel, 2 tile
-    size_t n_lead = 0;                             // lead-in copies the tile order added
-    DevBuf d_batch_t, d_pose;   // pose table: 112 B per batch (pixel order; the tile order only uses it to predict the bins)
-    DevBuf d_seg;                                             // tile order: per-segment constants the tiled kernel evaluates each event's pose from (12 doubles per segment)
-    int step_gather = 2;    // option step_gather: how emba_step writes its active set + A22 | b2 rows — 0 the sweeping kernel (emba_active_write_kernel), 1 the list-driven
-                            // gather as a kernel of its own, 2 (default) the list-driven gather as the head of the compact Gram kernel
-    DevBuf d_seg_act;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
-    bool aw_in_gram = false; ActiveWriteParams aw_saved{};   // the gather of the running step, to be issued with its Gram launch (emba_form_accumulate)
-    int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
-    int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
-    int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
-    DevBuf d_slot_key; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
-    // Two record sets (a rejected LM trial must not cost a re-evaluation).  `work` is the WORKING set: what
-    // the last evaluation wrote and what formNormalEq and the solvers read.  An evaluation that would overwrite records the current normal
-    // equations were formed from (eq.accum_done) first sets them aside — eq_saved = eq, and the other record set is swapped in; emba_map_reject /
-    // emba_trial_reject swaps back and takes eq = eq_saved, so the solver can be called again with a larger lambda on untouched equations
-    // (solver.cpp:340-352 reuses A, b).  Nothing else needs a second copy: the pack, the active set and the compact index are written by
-    // formNormalEq only, which never runs on a rejected trial.
-    RecordSet work, alt;
-    bool eq_in_alt = false;   // the equations in the pack (eq_saved) belong to the OTHER set: a trial evaluation has been written since
-    EqState eq, eq_saved;     // the equations in the pack; ... as they were when a trial evaluation set them aside (eq_in_alt)
-    EvalState ev;             // the evaluation in flight
-    DevBuf d_e_sorted, d_flag, d_inl_idx;
-    size_t n_outside_tile = 0; int n_rebin = 0; uint32_t last_rebin_stamp = 0;   // tile order: inliers found outside their tile in the last evaluation; how often the window was re-binned
-    int opt_poison = 0;          // option poison = 1 (tests): every NEW device allocation of the context is filled with 0xFF bytes
-    int opt_tile_reserve = 2, opt_tile_shape = -1, opt_tile_fine = -1, opt_tile_min_events = 1650000, opt_tile_chunk = 0;   // emba_set_option: the tile order's window rule (prepare_order)
-    int tile_shape = 0; bool tile_fine = false;   // ... and what the current order uses: index into kTileShapes, its finer pitch grid
-    int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
-    int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
-    DevBuf d_fblk_cnt, d_fblk_off; long n_fblk = 0;   // inlier-flag counts per kFlagBlk pm-order entries
-    DevBuf d_fsup; long n_fsup = 0; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (two arrays used alternately; fsup_half: the one the last launch A filled)
-    DevBuf d_ep;
-    // order / key cache
-    bool keys_ready = false; int64_t key_t0 = 0, key_dt = 0; int key_K = 0;
-    double set_events_ms = 0, prepare_ms = 0;   // wall time of the last emba_set_events[_dev] / order preparation (diagnostics)
-
-    // per-iteration state
-    size_t n_inliers = 0;
-    size_t P_prev = 0;                                      // active pixels of the last equations whose count the host has seen (this window): the Gram kernel's form is chosen by it
-    int cost_irls = 0; double cost_eta = 0.0;   // robust cost declared with emba_set_cost: what the NEXT evaluation weights its per-pixel sums with
-    double* h_knots = nullptr; int h_knots_cap = 0; hipEvent_t knots_copied = nullptr; bool knots_in_flight = false;   // pinned staging for the control poses
-
-    // timing
-    hipEvent_t ev_start[8]{}, ev_stop[8]{};
-    bool kernel_timing = false;
-    hipEvent_t kt_sets[16][5]{}; hipEvent_t* kt = kt_sets[0]; int kt_slot = 0;  // per slot: warp start/stop, accum start/stop (emba_enable_kernel_timing), [4]: in front of the step's first launch
-    bool kt_valid[16][3]{};
-    bool kt_all = false;        // emba_kernel_timing_all: also record [4], so that the four intervals [4]->[0]->[1]->[2]->[3] tile the whole step (prep | warp | post-warp | Gram)
-    hipEvent_t cal_ev[2]{};     // emba_bracket_overhead_us / emba_clock_probe
-    DevBuf d_probe;
-    bool kt_warp_valid = false, kt_accum_valid = false;
-    int n_cu = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    int ablate = 0;  // diagnostics builds only (-DEMBA_DIAG): EMBA_ABLATE bit mask; always 0 in the shipped library
-    int solve_info = 0;         // last Schur solve: bit 0 a 2x2 block not positive definite (error), bit 1 a pivot of S vanished (zero update, like Eigen's ldlt)
-    // ---- grow-only scratch, by phase.  A buffer named for two roles serves both (no phase holds it while the other runs): sharing keeps the peak down.
-    struct {   // once-per-window order preparation (set_events_core, prepare_order) and the device scan / sort
-        DevBuf scan_sums, scan_offs;   // dev_scan
-        DevBuf sort_hist;              // dev_sort
-        DevBuf status;                 // 64 B of status words: set_events_core, prepare_order
-        DevBuf keys[2], vals[2];       // radix-sort pairs: set_events_core (pm-order), prepare_order (tile order, record slots)
-        DevBuf flags;                  // set_events_core: candidate flags; prepare_order: chain-head flags, the tile binning's emit flags, candidate flags
-        DevBuf pos;                    // set_events_core: candidate positions; prepare_order: head / emit positions, candidate positions
-        DevBuf bin, used;              // prepare_order: tile of every entry, occupied bins
-        DevBuf bin_start_or_x;         // prepare_order: first entry of every tile; emba_set_events: upload of x
-        DevBuf pred_or_y;              // prepare_order: predicted pixels; emba_set_events: upload of y
-        DevBuf heads_or_pol;           // prepare_order: chain heads; emba_set_events: upload of the polarities
-        DevBuf halo;                   // emba_set_events: upload of the halo (times, x, y)
-    } ord;
-    struct Solve {   // the solvers (an LM loop solves every iteration).  Schur: emba_solve_normal_eq, emba_solve_shard_*; CG: emba_solve_normal_eq_cg, emba_cg_shard_*
-        DevBuf S_or_x, rhs_or_r, U_or_p, y_or_z, cf_or_t, x2_or_invd;   // Schur: S_aug, x1, U block, y, 2x2 factors, x2; CG: x, r, p, z, t, inverse diagonal
-        DevBuf info_or_sc;             // Schur: status word; CG: device scalars
-        DevBuf slab, mask, list, cnt, range, pair_items, items;         // schur_accumulate: the block-sparse SYRK
-        DevBuf perm_cnt, perm_tick, perm;   // solve_perm (perm: the column order, valid with perm_valid)
-        DevBuf shard_cnt;              // emba_solve_shard_count -> emba_solve_shard_pack: counts, offsets, cursors per rank
-    } sv;
-    struct {   // build_lists.  off / sorted are the lists cache (lists_valid) that a re-solve, emba_solve_shard_cached / _finish and a CG session read
-        DevBuf off, cursor, sorted, tmp;
-    } lists;
-    struct {   // downloads
-        DevBuf out;          // emba_get_map_active, emba_get_inlier_pixels, the pixel list of emba_get_inlier_pixel_starts
-        DevBuf pix_starts;   // emba_get_inlier_pixel_starts
-        DevBuf A22b2;        // emba_form_finish: unpacked A22 | b2
-    } dl;
-    // f3 (Poisson reconstruction): sine matrices and eigenvalues of the two transform lengths, scratch planes
-    DevBuf d_SH, d_SW, d_lamH, d_lamW, d_pF, d_pT, d_pGx, d_pGy;
-    DevBuf d_thomas;              // Thomas factors of T_W + lambda1[i] I (W x H)
-    DevBuf d_Sfold;               // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
-    DevBuf d_pE;                  // [E | O] of the folded transform (W x H/2 each)
-    // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload
-    DevBuf d_rstate, d_rhist, d_rcand;
-    DevBuf d_img, d_nsrc;
-    // the whole (down-sampled) event sequence of a sliding-window run (sequence_kernels.h): uploaded once by emba_seq_upload, registered window by window by
-    // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload
-    struct { DevBuf x, y, pol, t, raw, status; size_t n = 0; } evseq;
-    DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
-};
-
-namespace {
-
-emba_status fail(emba_ctx* c, emba_status st, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf; else g_create_error = buf;
-    return st;
-}
-
-#define HIP_TRY(c, call)                                                                         \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail((c), EMBA_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                     \
-    } while (0)
-
-// a grow-only buffer of the context (DevBuf) holds at least `count` elements of T.  Option poison (tests): new memory reads as NaN / 0xFFFFFFFF, so that a
-// read of never-written memory shows.
-template <typename T>
-emba_status ensure(emba_ctx* c, DevBuf& b, size_t count, bool* fresh = nullptr)
-{
-    const hipError_t e = b.ensure(count * sizeof(T), fresh, c->opt_poison != 0, c->stream);
-    if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-    return EMBA_OK;
-}
-
 // A new evaluation begins, or the last one can no longer be asked about (its window is gone, its trial was rejected): nothing that was derived from it —
 // pending counters, the residual vector, inlier numbers, the pixel-starts table, the count map's stamp — outlives this.
 void begin_evaluation(emba_ctx* c) { c->ev = EvalState{}; }
+// A new device order (a new window, or the window is ordered again): nothing of the previous one is kept but the shape and grid of the last tile search,
+// which emba_last_tile_geometry reports until another search runs.
+OrderState new_order(const OrderState& prev)
+{
+    OrderState o{};
+    o.tile_shape = prev.tile_shape; o.tile_fine = prev.tile_fine;
+    return o;
+}
 void free_window(emba_ctx* c)
 {   // (the buffers stay: the next window reuses them, see DevBuf)
-    c->d_ev_pix = nullptr; c->d_ev_batch = nullptr;
-    c->have_events = false; c->keys_ready = false; c->tile_order = false; c->have_ev_pm = false; c->n_chunks = 0; c->n_lead = 0; c->P_prev = 0;
+    WindowState w{};
+    w.last_rebin_stamp = c->rec_stamp - 3;   // a new window may be re-binned at its first drifted evaluation
+    w.n_rebin = c->win.n_rebin;              // emba_last_tile_drift counts the re-binnings of the context, not of a window
+    // until set_events_core takes the next window (a registration may fail before): emba_event_counts, emba_last_setup_ms and emba_last_tile_drift go on
+    // reporting the last one's sizes and drift
+    w.n_used = c->win.n_used; w.n_cand = c->win.n_cand; w.n_sorted = c->win.n_sorted; w.n_outside_tile = c->win.n_outside_tile;
+    c->win = w;
+    OrderState o = new_order(c->order);
+    // until the window's first evaluation orders it: emba_last_order_stats and emba_last_order_inlier_estimate go on reporting the last decision
+    o.order_per_px = c->order.order_per_px; o.order_lead_frac = c->order.order_lead_frac; o.order_inl_pred = c->order.order_inl_pred;
+    c->order = o;
     c->eq.active_done = c->eq.accum_done = false;
     // (counters of the previous window that were never resolved must not be read as this window's)
     begin_evaluation(c);
@@ -345,7 +81,6 @@ int64_t batch_mid_ns(int64_t t_first, int64_t t_last)
 }
 
 // ---- device-side helpers of the once-per-window structure (order_kernels.h) ----------------------------------------------------
-inline unsigned nblocks(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>((n + per - 1) / per, 1); }
 
 // out[i] = sum_{j<i} in[j]; total_dev[0] = sum of all (may be nullptr).  Scratch: ord.scan_sums, ord.scan_offs.
 emba_status dev_scan(emba_ctx* c, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total_dev, int* total_host = nullptr, const int* err_dev = nullptr, int* err_host = nullptr)
@@ -395,23 +130,16 @@ emba_status ensure_sort_pairs(emba_ctx* c, size_t n)
 
 int bits_for(size_t n_values) { int b = 1; while (((size_t)1 << b) < n_values) ++b; return b; }
 
-// At the first evaluation of a window (and again whenever the spline timing changes): the control-pose pair of every measurement,
-// the device order (pixel order, or tile order from the panorama positions the given control poses predict) and the record slots
-// sorted by pair.  Pose-independent except for the tile binning, which only affects speed.
-emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int64_t dt, int K)
+constexpr size_t kTileRound = (size_t)kWarpNew * kTileWaves;   // entries one round of a tiled workgroup's waves takes
+
+// ---- prepare_order, phase by phase.  The host arithmetic that decides the order is order_rule.h (tested on the CPU); here: the launches that feed it. ----
+
+// control-pose index per batch; a batch outside the knots is an error (BASALT_ASSERT_STREAM at so3_spline.h:221-229)
+emba_status order_batch_segments(emba_ctx* c, int64_t t0, int64_t dt, int K)
 {
-    if (c->keys_ready && c->key_t0 == t0 && c->key_dt == dt && c->key_K == K) return EMBA_OK;
-    if (dt <= 0 || K < 2 || K > 65535) return fail(c, EMBA_ERR_INVALID_ARG, "bad spline: dt_ns=%lld K=%d", (long long)dt, K);
-    const auto t_begin = std::chrono::steady_clock::now();
     hipStream_t s = c->stream;
     emba_status st;
-    const size_t ns = c->n_pm, nbatch = c->n_batch;
-    // (a previous order of this window goes away; its buffers are reused)
-    c->d_ev_pix = nullptr; c->d_ev_batch = nullptr;
-    c->tile_order = false; c->have_ev_pm = false; c->n_chunks = 0; c->n_lead = 0;
-    c->order_per_px = 0.0; c->order_lead_frac = 0.0; c->order_inl_pred = 0.0;
-
-    // control-pose index per batch; a batch outside the knots is an error (BASALT_ASSERT_STREAM at so3_spline.h:221-229)
+    const size_t nbatch = c->win.n_batch;
     if ((st = ensure<uint32_t>(c, c->ord.status, 16))) return st;
     uint32_t* d_err = c->ord.status.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
@@ -426,249 +154,233 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
         return fail(c, EMBA_ERR_TIME_RANGE, "batch %u midpoint %lld ns outside spline [%lld, %lld) (K=%d)", h_err[0], (long long)tb, (long long)t0,
                     (long long)(t0 + dt * (K - 1)), K);
     }
+    return EMBA_OK;
+}
 
-    // ---- which order?  Tile order pays when many events share a panorama pixel (the per-pixel sums are then combined in LDS) and the
-    // chains of a sensor pixel stay in a tile for a while (every tile entry costs one extra warp of the predecessor).
-    // Round 6: WHICH tile (order_kernels.h: the window rule).  The 1152-pixel LDS tile comes in four shapes (kernels.h: kTileShapes); every chain is cut into the
-    // longest segments that fit a tile of the shape on its pitch grid, and the shape with the fewest entries + chunks wins — a fast pan wants wide tiles, a
-    // trajectory that pitches wants tall ones (scripts/lead_in_sim.py: 5 M events over 4.8 s at 0.5 rad/s: 19.5 % lead-ins at 48 x 24, 11.5 % at 72 x 16).
-    BinGeom g{};
-    uint32_t *d_bin = nullptr, *d_emit = nullptr, *d_pos = nullptr, *d_pred = nullptr; uint8_t* d_used = nullptr; unsigned long long* d_breaks = nullptr;
-    bool tile = false;
-    size_t n_break = 0, n_used_bins = 0, nbins = 1;
-    // (auto on a window below tile_min_events never takes the tile order: nothing to analyse — 1.2 -> 0.3 ms of a 1 M-event window's first evaluation)
-    if (c->order_mode != 1 && ns && knots_host && (c->order_mode == 2 || c->n_used >= (size_t)c->opt_tile_min_events)) {
-        const size_t max_bins = (size_t)((c->W + 7) / 8) * ((c->H + 1) / 2) + 1;      // (the finest pitch any candidate uses is 8 x 2)
-        if ((st = ensure<uint32_t>(c, c->ord.bin, ns)) || (st = ensure<uint32_t>(c, c->ord.flags, ns)) || (st = ensure<uint32_t>(c, c->ord.pos, ns)) ||
-            (st = ensure<uint8_t>(c, c->ord.used, max_bins + 8)) || (st = ensure<uint32_t>(c, c->ord.pred_or_y, ns)) || (st = ensure<uint32_t>(c, c->ord.heads_or_pol, ns)))
-            return st;
-        d_bin = c->ord.bin.as<uint32_t>(); d_emit = c->ord.flags.as<uint32_t>(); d_pos = c->ord.pos.as<uint32_t>(); d_used = c->ord.used.as<uint8_t>(); d_pred = c->ord.pred_or_y.as<uint32_t>();
-        d_breaks = reinterpret_cast<unsigned long long*>(d_err + 8);
-        // the poses the caller starts from (staged through the pinned buffer like every evaluation's)
-        HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), knots_host, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(emba_pose_kernel, dim3(nblocks(nbatch, 64)), dim3(64), 0, s, c->d_batch_t.as<int64_t>(), (int)nbatch, c->d_knots.as<double>(), K, t0, dt, c->d_pose.as<double>(), c->d_err);
-        hipLaunchKernelGGL(emba_predict_pixel_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_pose.as<double>(), kPoseStride, c->d_lut.as<double>(),
-                           c->fx, c->fy, c->cx, c->cy, c->W, c->H, d_pred);
-        // the chains of the pm-order: heads -> list (one wave of the assignment kernel per chain)
-        uint32_t *d_hflag = d_emit, *d_hpos = d_pos, *d_heads = c->ord.heads_or_pol.as<uint32_t>(), *d_nheads = d_err + 6;
-        hipLaunchKernelGGL(emba_head_flag_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), (long)ns, d_hflag);
-        if ((st = dev_scan(c, d_hflag, d_hpos, ns, d_nheads))) return st;
-        hipLaunchKernelGGL(emba_head_list_kernel, dim3(nblocks(ns)), dim3(256), 0, s, d_hflag, d_hpos, (long)ns, d_heads);
-        uint32_t h_nheads = 0;
-        HIP_TRY(c, hipMemcpyAsync(&h_nheads, d_nheads, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const long n_heads = (long)h_nheads;
-        double f_pred = 1.0;
-        {
-            HIP_TRY(c, hipMemsetAsync(d_breaks, 0, 8, s));
-            hipLaunchKernelGGL(emba_count_pred_inliers_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_pred, (long)ns, c->outlier_px, d_breaks);
-            unsigned long long hi = 0;
-            HIP_TRY(c, hipMemcpyAsync(&hi, d_breaks, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            f_pred = c->n_used ? (double)hi / (double)c->n_used : 0.0;
-        }
-        c->order_inl_pred = f_pred;
-        const bool hopeless = c->order_mode == 0 && 83.0 * f_pred <= 41.0;      // the rule below cannot hold even without a single lead-in: skip the search for a tile
-        const int r = std::max(0, std::min(c->opt_tile_reserve, 5));
-        std::vector<uint8_t> h_used(max_bins);
-        auto geom = [&](int shape, bool fine) {
-            BinGeom q{};
-            const TileShape& ts = kTileShapes[shape];
-            q.W = c->W; q.H = c->H; q.tw = ts.tw; q.th = ts.th; q.r = r;
-            q.bw = fine ? ts.fine_pw : ts.pw; q.bh = fine ? ts.fine_ph : ts.ph;
-            q.bw = std::min(q.bw, ts.tw - 2 * r); q.bh = std::min(q.bh, ts.th - 2 * r);     // (a single pixel must fit wherever it lies in its pitch cell)
-            q.nbx = (c->W + q.bw - 1) / q.bw; q.nby = (c->H + q.bh - 1) / q.bh;
-            return q;
-        };
-        // lead-ins and occupied tiles of one candidate; leaves its assignment in d_bin / d_emit
-        auto evaluate = [&](const BinGeom& q, size_t* breaks, size_t* used) -> emba_status {
-            const size_t nb_ = (size_t)q.nbx * q.nby + 1;
-            HIP_TRY(c, hipMemsetAsync(d_used, 0, nb_, s));
-            HIP_TRY(c, hipMemsetAsync(d_breaks, 0, 8, s));
-            hipLaunchKernelGGL(emba_assign_tiles_kernel, dim3((unsigned)((n_heads + 3) / 4)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_pred, d_heads, n_heads, (long)ns, q, d_bin, d_used);
-            hipLaunchKernelGGL(emba_expand_count_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_bin, (long)ns, d_emit);
-            hipLaunchKernelGGL(emba_count_breaks_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, d_emit, (long)ns, d_breaks);
-            unsigned long long hb = 0;
-            HIP_TRY(c, hipMemcpyAsync(h_used.data(), d_used, nb_, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(&hb, d_breaks, 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            *breaks = (size_t)hb; *used = 0;
-            for (size_t b = 0; b + 1 < nb_; ++b) *used += h_used[b];
-            return EMBA_OK;
-        };
-        // what a candidate costs the warp kernel, in entries: every lead-in is a full warp, every chunk zeroes and flushes an LDS tile (~ 256 entries' worth:
-        // 3 M events, round 3: 902 -> 2520 entries per chunk took the kernel from 191 to 174 us)
-        auto cost = [&](size_t breaks, size_t used) {
-            const double entries = (double)c->n_used + (double)breaks;
-            const double chunks = std::max((double)used, entries / (double)(kWarpNew * kTileWaves * 8));
-            return entries + 256.0 * chunks;
-        };
-        if (!hopeless) {
-        int best = -1; bool best_fine = false; double best_cost = 0; size_t best_breaks = 0, best_used = 0; int last = -1; bool last_fine = false;
-        // (the tall shape first, the others have to beat it by 2 %: at equal lead-ins 36 x 32 measured 3-5 % faster than 48 x 24 — 3 M events 155 vs 161 us, config 4's
-        // shard 245 vs 260, 2 M 111 vs 115, city 463 vs 465; profiles/r06_regime_sweep.txt)
-        static const int kShapeOrder[kNumTileShapes] = {3, 0, 1, 2};
-        for (int si = 0; si < kNumTileShapes; ++si) {
-            const int sh = kShapeOrder[si];
-            if (c->opt_tile_shape >= 0 && sh != c->opt_tile_shape) continue;
-            size_t br = 0, us = 0;
-            if ((st = evaluate(geom(sh, false), &br, &us))) return st;
-            last = sh; last_fine = false;
-            const double cc = cost(br, us);
-            if (best < 0 || cc < 0.98 * best_cost) { best = sh; best_fine = false; best_cost = cc; best_breaks = br; best_used = us; }
-        }
-        // dense tiles can afford a finer grid of tile origins (segments end closer to the tile's far edge, and a tile's entries spread over more chunks): config 4's
-        // shard (11.7 k entries per tile) 258 -> 229 us; at 3-5 k entries per tile it loses (3 M: 162 -> 173, 5 M: 236 -> 271)
-        // (... and only below 16 M events: the finer grid doubles the chunks — 40 M events 1749 -> 1879 us, config 5's shard 566 -> 655, 100 M + 2 % per step;
-        // profiles/r06_large_window_ab.txt)
-        if (best >= 0 && c->opt_tile_fine != 0 &&
-            (c->opt_tile_fine == 1 || (c->n_used < (size_t)16000000 && (double)c->n_used / std::max<size_t>(best_used, 1) >= 2.0 * kWarpNew * kTileWaves * 8))) {
-            size_t br = 0, us = 0;
-            if ((st = evaluate(geom(best, true), &br, &us))) return st;
-            last_fine = true; last = best;
-            const double cc = cost(br, us);
-            if (cc < best_cost || c->opt_tile_fine == 1) { best_fine = true; best_cost = cc; best_breaks = br; best_used = us; }
-        }
-        if (best < 0) return fail(c, EMBA_ERR_INVALID_ARG, "option tile_shape %d: no such shape", c->opt_tile_shape);
-        g = geom(best, best_fine);
-        if (last != best || last_fine != best_fine) { size_t br = 0, us = 0; if ((st = evaluate(g, &br, &us))) return st; }   // d_bin / d_emit of the winner
-        c->tile_shape = best; c->tile_fine = best_fine;
-        nbins = (size_t)g.nbx * g.nby + 1;
-        n_break = best_breaks; n_used_bins = best_used;
-        const double per_px = n_used_bins ? (double)c->n_used / ((double)n_used_bins * g.bw * g.bh) : 0.0;     // events per panorama pixel of the occupied pitch cells
-        const double lead_frac = c->n_used ? (double)n_break / (double)c->n_used : 1.0;
-        // Measured (profiles/r02c_order_sweep.txt): the tile order wins once the working set has left the Infinity Cache (3 M events, 1024x2048:
-        // 374 vs 394 us per step; 5 M / K=97: 558 vs 618; 100 M: 4.8 vs 8.7 ms warp) and loses below it (1 M events, 24 per pixel: 82 vs 52 us
-        // — every entry of the tile order is a warp, lead-ins included, and a workgroup's LDS tile is zeroed and flushed for a handful of groups).
-        // (round 3, with at least 5 groups per wave and chunk: 2 M events 220 vs 246 us per step, 1.5 M 188 vs 155 — the pixel order falls off a cliff
-        // between 1.5 M and 2 M events: twice the events on the same footprint are twice as close along a chain, nearly all of them inliers — 3 x the atomic requests)
-        // (round 5: a slow pan over a big sensor — the city shape at 0.1 rad/s: 10 M events on 640x480, 50 events per panorama pixel — is
-        // atomic-request bound in pixel order (7.3 M requests on 155 k lines); the tile order's LDS sums win there in spite of the extra entries: step 867 vs
-        // 946-995 us.  Hence the second clause: very dense tiles tolerate more lead-ins.)
-        // Round 6: the rule prices both orders.  Per million events, fitted to profiles/r06_regime_sweep.txt and r06_sparse_order_ab.txt (warp + Gram kernels, us):
-        // pixel order 20 + 93 f (it pays per INLIER: an atomic request, a record, a live slot of the Gram kernel's tag stream; f = inlier fraction), tile order
-        // 31 (1 + lead) + 10 f + 30 (it pays per ENTRY, lead-in copies included, and its Gram kernel reads every candidate's slot).  The tile order wins where
-        // 83 f > 41 + 31 lead.  f is estimated from the predicted pixels (emba_count_pred_inliers_kernel).  (Rounds 2-5 asked for lead <= 0.35 only: with the window
-        // rule's fewer lead-ins that sent a 34 %-inlier stream — 10 M events on 640x480 at 0.5 rad/s — to the tile order: 850 us per step against 636 in pixel order.)
-        tile = (c->order_mode == 2) || (c->n_used >= (size_t)c->opt_tile_min_events && per_px >= 8.0 && 83.0 * f_pred > 41.0 + 31.0 * lead_frac);
-        c->order_per_px = per_px; c->order_lead_frac = lead_frac;
-        }
-    }
+// The order scratch as the tile search and the tile order built from it use it.  status words (ord.status, cleared by order_batch_segments): [4] entries of the
+// expanded list, [6] chain heads, [8..9] a 64-bit counter (predicted inliers, then a candidate's lead-ins).
+struct TileSearch {
+    uint32_t *bin, *emit, *pos, *pred, *heads, *status; uint8_t* used;
+    long n_heads = 0;
+    std::vector<uint8_t> h_used;
+    unsigned long long* breaks() const { return reinterpret_cast<unsigned long long*>(status + 8); }
+};
 
-    if (!tile) {
-        c->d_ev_pix = c->d_pm_pix.as<uint32_t>(); c->d_ev_batch = c->d_pm_batch.as<uint32_t>();
-        c->n_sorted = ns;
-        // per entry the spline parameter and segment of its batch (the warp kernel's per-event pose: 10 B per entry, streamed with the event words)
-        if ((st = ensure<double>(c, c->d_ev_u, std::max<size_t>(ns, 1))) || (st = ensure<uint16_t>(c, c->d_ev_seg, std::max<size_t>(ns, 1)))) return st;
-        if (ns) hipLaunchKernelGGL(emba_entry_pose_args_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>());
-    } else {
-        // expanded list: every event, plus a lead-in copy of its predecessor where its chain enters a tile -> stable sort by tile
-        uint32_t* d_tot = d_err + 4;
-        if ((st = dev_scan(c, d_emit, d_pos, ns, d_tot))) return st;
-        uint32_t nd32 = 0;
-        HIP_TRY(c, hipMemcpyAsync(&nd32, d_tot, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const size_t nd = nd32;
-        if ((st = ensure_sort_pairs(c, nd)) || (st = ensure<uint32_t>(c, c->ord.bin_start_or_x, nbins + 1))) return st;
-        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
-        uint32_t* d_bin_start = c->ord.bin_start_or_x.as<uint32_t>();
-        hipLaunchKernelGGL(emba_expand_write_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_bin, d_emit, d_pos, (long)ns, k0, v0);
-        if ((st = dev_sort(c, &k0, &v0, &k1, &v1, nd, bits_for(nbins)))) return st;
-        if ((st = ensure<uint32_t>(c, c->d_ev_pix_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_batch_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_pm, nd)) ||
-            (st = ensure<double>(c, c->d_ev_u, nd)) || (st = ensure<uint16_t>(c, c->d_ev_seg, nd)))
-            return st;
-        c->d_ev_pix = c->d_ev_pix_own.as<uint32_t>(); c->d_ev_batch = c->d_ev_batch_own.as<uint32_t>(); c->have_ev_pm = true;
-        HIP_TRY(c, hipMemsetAsync(d_bin_start, 0xFF, (nbins + 1) * 4, s));
-        uint32_t* d_cf = d_emit;    // (emit is dead: its buffer now takes the candidate flags of the device order — nd <= 2 ns may exceed it)
-        if (nd > ns) { if ((st = ensure<uint32_t>(c, c->ord.flags, nd))) return st; d_cf = c->ord.flags.as<uint32_t>(); }
-        hipLaunchKernelGGL(emba_dev_gather_kernel, dim3(nblocks(nd)), dim3(256), 0, s, k0, v0, (long)nd, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), c->d_ev_pix, c->d_ev_batch,
-                           c->d_ev_pm.as<uint32_t>(), c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>(), d_cf, d_bin_start);
-        // chunks: every occupied tile is cut into workgroup-sized pieces (host: <= 32 k tiles)
-        std::vector<uint32_t> h_start(nbins + 1);
-        HIP_TRY(c, hipMemcpyAsync(h_start.data(), d_bin_start, (nbins + 1) * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        std::vector<std::pair<uint32_t, uint32_t>> occ;   // (bin, start)
-        for (size_t b = 0; b < nbins; ++b) if (h_start[b] != 0xFFFFFFFFu) occ.emplace_back((uint32_t)b, h_start[b]);
-        std::vector<ChunkDesc> h_chunks;
-        const size_t slots = (size_t)c->n_cu * 2;      // workgroups of the tiled kernel the chip holds at a time
-        {
-        // chunk size: enough workgroups for ~8 rounds of the chip, at most 16 groups of 63 entries per wave
-        size_t chunk = (nd + slots * 8 - 1) / (slots * 8);
-        // (at least 5 groups per wave: a workgroup zeroes and flushes its 55-KB LDS tile whatever it has to do — 3 M events: 902 -> 2520 entries per
-        // chunk, warp kernel 191 -> 174 us; 5 M: 280 -> 271; from 10 M on the first rule gives more than that anyway)
-        // round 4, with the chunks dispatched longest first: 8 groups per wave up to ~8 M entries (3 M events: 1339 chunks, warp kernel 160 -> 153 us;
-        // 5 M: 257 -> 242), 5 beyond (10 M: 8 groups 493 us, 5 groups 464 — there the first rule decides most chunks anyway)
-        const size_t min_groups = nd < (size_t)8000000 ? 8 : 5;
-        chunk = std::min<size_t>(std::max<size_t>(chunk, (size_t)kWarpNew * kTileWaves * min_groups), (size_t)kWarpNew * kTileWaves * 16);
-        if (c->opt_tile_chunk > 0) chunk = (size_t)c->opt_tile_chunk;
-        for (size_t k = 0; k < occ.size(); ++k) {
-            const uint32_t b = occ[k].first, b0 = occ[k].second, b1 = (k + 1 < occ.size()) ? occ[k + 1].second : (uint32_t)nd;
-            // (pieces in whole ROUNDS of the workgroup's waves: a piece of G groups takes ceil(G / 8) rounds whatever it holds, so only a tile's last piece may be ragged)
-            constexpr size_t kRound = (size_t)kWarpNew * kTileWaves;
-            const size_t cnt = b1 - b0, nch = (cnt + chunk - 1) / chunk, per = ((cnt + nch - 1) / nch + kRound - 1) / kRound * kRound;
-            const int bx = (int)(b % (uint32_t)g.nbx), by = (int)(b / (uint32_t)g.nbx);
-            for (size_t q = 0; q < nch; ++q) {
-                ChunkDesc d;
-                d.begin = b0 + (uint32_t)(q * per); d.end = (uint32_t)std::min<size_t>(b0 + (q + 1) * per, b1);
-                d.x0 = bx * g.bw - g.r; d.y0 = by * g.bh - g.r;
-                if (d.begin < d.end) h_chunks.push_back(d);
-            }
-        }
-        // Chunk sizes differ (every bin is cut on its own) and the grid is a few rounds of the chip's workgroup slots: with the longest chunks FIRST the
-        // last round is made of the short ones (longest-processing-time order; workgroups are dispatched in grid order as slots free up).
-        // Option chunk_order_bin keeps the bins' order (neighbouring chunks on one XCD).
-        c->chunks_lpt = !c->opt_chunk_order_bin;
-        if (c->chunks_lpt) std::stable_sort(h_chunks.begin(), h_chunks.end(), [](const ChunkDesc& a, const ChunkDesc& b) { return a.end - a.begin > b.end - b.begin; });
-        }
-        c->n_chunks = (long)h_chunks.size();
-        if ((st = ensure<ChunkDesc>(c, c->d_chunks, h_chunks.size()))) return st;
-        HIP_TRY(c, hipMemcpyAsync(c->d_chunks.as<ChunkDesc>(), h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        c->n_sorted = nd; c->n_lead = nd - c->n_used; c->tile_order = true;
-        d_emit = d_cf;
-    }
-    const size_t nd = c->n_sorted;
-    c->nblk = (long)((nd + kWarpNew - 1) / kWarpNew);
+// the pixels the caller's poses predict for every pm-order entry, the chains of the pm-order, and the inlier fraction f_pred the predicted pixels give
+emba_status tile_search_begin(emba_ctx* c, const double* knots_host, int64_t t0, int64_t dt, int K, TileSearch* ts, double* f_pred)
+{
+    hipStream_t s = c->stream;
+    emba_status st;
+    const size_t ns = c->win.n_pm, nbatch = c->win.n_batch;
+    const size_t max_bins = (size_t)((c->W + 7) / 8) * ((c->H + 1) / 2) + 1;      // (the finest pitch any candidate uses is 8 x 2)
+    if ((st = ensure<uint32_t>(c, c->ord.bin, ns)) || (st = ensure<uint32_t>(c, c->ord.flags, ns)) || (st = ensure<uint32_t>(c, c->ord.pos, ns)) ||
+        (st = ensure<uint8_t>(c, c->ord.used, max_bins + 8)) || (st = ensure<uint32_t>(c, c->ord.pred_or_y, ns)) || (st = ensure<uint32_t>(c, c->ord.heads_or_pol, ns)))
+        return st;
+    ts->bin = c->ord.bin.as<uint32_t>(); ts->emit = c->ord.flags.as<uint32_t>(); ts->pos = c->ord.pos.as<uint32_t>(); ts->used = c->ord.used.as<uint8_t>();
+    ts->pred = c->ord.pred_or_y.as<uint32_t>(); ts->heads = c->ord.heads_or_pol.as<uint32_t>(); ts->status = c->ord.status.as<uint32_t>();
+    ts->h_used.resize(max_bins);
+    // the poses the caller starts from (staged through the pinned buffer like every evaluation's)
+    HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), knots_host, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(emba_pose_kernel, dim3(nblocks(nbatch, 64)), dim3(64), 0, s, c->d_batch_t.as<int64_t>(), (int)nbatch, c->d_knots.as<double>(), K, t0, dt, c->d_pose.as<double>(), c->d_err);
+    hipLaunchKernelGGL(emba_predict_pixel_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_pose.as<double>(), kPoseStride, c->d_lut.as<double>(),
+                       c->fx, c->fy, c->cx, c->cy, c->W, c->H, ts->pred);
+    // the chains of the pm-order: heads -> list (one wave of the assignment kernel per chain)
+    uint32_t *d_hflag = ts->emit, *d_hpos = ts->pos, *d_nheads = ts->status + 6;
+    hipLaunchKernelGGL(emba_head_flag_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), (long)ns, d_hflag);
+    if ((st = dev_scan(c, d_hflag, d_hpos, ns, d_nheads))) return st;
+    hipLaunchKernelGGL(emba_head_list_kernel, dim3(nblocks(ns)), dim3(256), 0, s, d_hflag, d_hpos, (long)ns, ts->heads);
+    uint32_t h_nheads = 0;
+    HIP_TRY(c, hipMemcpyAsync(&h_nheads, d_nheads, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    ts->n_heads = (long)h_nheads;
+    HIP_TRY(c, hipMemsetAsync(ts->breaks(), 0, 8, s));
+    hipLaunchKernelGGL(emba_count_pred_inliers_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), ts->pred, (long)ns, c->outlier_px, ts->breaks());
+    unsigned long long hi = 0;
+    HIP_TRY(c, hipMemcpyAsync(&hi, ts->breaks(), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    *f_pred = c->win.n_used ? (double)hi / (double)c->win.n_used : 0.0;
+    return EMBA_OK;
+}
 
-    // record slots sorted by control-pose pair: candidates of the device order -> (key, entry) -> stable sort -> slot
-    {
-        const size_t M = c->n_cand;
-        if ((st = ensure<uint32_t>(c, c->ord.pos, std::max<size_t>(nd, 1)))) return st;
-        uint32_t *d_cf = d_emit, *d_cpos = c->ord.pos.as<uint32_t>();
-        if (!tile) {
-            if ((st = ensure<uint32_t>(c, c->ord.flags, std::max<size_t>(nd, 1)))) return st;
-            d_cf = c->ord.flags.as<uint32_t>();
-            if (nd) hipLaunchKernelGGL(emba_cand_flag_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->d_ev_pix, (long)nd, d_cf);
-        }
-        if ((st = dev_scan(c, d_cf, d_cpos, nd, nullptr))) return st;
-        if ((st = ensure_sort_pairs(c, std::max<size_t>(M, 1)))) return st;
-        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
-        if ((st = ensure<uint32_t>(c, c->d_ev_slot, nd))) return st;
-        HIP_TRY(c, hipMemsetAsync(c->d_ev_slot.as<uint32_t>(), 0xFF, std::max<size_t>(nd, 1) * 4, s));
-        if (nd) hipLaunchKernelGGL(emba_cand_keys_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->d_ev_pix, c->d_ev_batch, c->d_cp.as<uint16_t>(), (long)nd, d_cpos, k0, v0);
-        // the key's low half is cp_p, the high half cp_c, both < K: sort on the bits they really use
-        const int kb = bits_for((size_t)K);
-        if (kb <= 8) {   // fold the two halves into one 16-bit key for the sort (two passes instead of four)
-            if (M) hipLaunchKernelGGL(emba_fold_keys_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, (long)M, 1);
-            if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 16))) return st;
-            if (M) hipLaunchKernelGGL(emba_fold_keys_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, (long)M, 0);
-        } else if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 32))) return st;
-        if (M) hipLaunchKernelGGL(emba_slot_assign_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, v0, (long)M, c->d_ev_slot.as<uint32_t>(), c->d_slot_key.as<uint32_t>());
+// lead-ins and occupied tiles of one candidate; leaves its assignment in ts.bin / ts.emit
+emba_status tile_search_evaluate(emba_ctx* c, TileSearch& ts, const BinGeom& q, size_t* breaks, size_t* used)
+{
+    hipStream_t s = c->stream;
+    const size_t ns = c->win.n_pm, nb_ = (size_t)q.nbx * q.nby + 1;
+    HIP_TRY(c, hipMemsetAsync(ts.used, 0, nb_, s));
+    HIP_TRY(c, hipMemsetAsync(ts.breaks(), 0, 8, s));
+    hipLaunchKernelGGL(emba_assign_tiles_kernel, dim3((unsigned)((ts.n_heads + 3) / 4)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), ts.pred, ts.heads, ts.n_heads, (long)ns, q, ts.bin, ts.used);
+    hipLaunchKernelGGL(emba_expand_count_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), ts.bin, (long)ns, ts.emit);
+    hipLaunchKernelGGL(emba_count_breaks_kernel, dim3((unsigned)std::min<size_t>(nblocks(ns), 1024)), dim3(256), 0, s, ts.emit, (long)ns, ts.breaks());
+    unsigned long long hb = 0;
+    HIP_TRY(c, hipMemcpyAsync(ts.h_used.data(), ts.used, nb_, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&hb, ts.breaks(), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    *breaks = (size_t)hb; *used = 0;
+    for (size_t b = 0; b + 1 < nb_; ++b) *used += ts.h_used[b];
+    return EMBA_OK;
+}
+
+// ---- which order?  Tile order pays when many events share a panorama pixel (the per-pixel sums are then combined in LDS) and the
+// chains of a sensor pixel stay in a tile for a while (every tile entry costs one extra warp of the predecessor).
+// Round 6: WHICH tile (order_kernels.h: the window rule).  The 1152-pixel LDS tile comes in four shapes (kernels.h: kTileShapes); every chain is cut into the
+// longest segments that fit a tile of the shape on its pitch grid, and the shape with the fewest entries + chunks wins — a fast pan wants wide tiles, a
+// trajectory that pitches wants tall ones (scripts/lead_in_sim.py: 5 M events over 4.8 s at 0.5 rad/s: 19.5 % lead-ins at 48 x 24, 11.5 % at 72 x 16).
+// tile: the tile order it is, with the winner's assignment left in ord.bin / ord.flags; g, nbins: its pitch grid; breaks, used: its lead-ins and occupied tiles.
+struct TileOrderChoice { bool tile = false; BinGeom g{}; size_t nbins = 1, breaks = 0, used = 0; };
+
+emba_status choose_tile_order(emba_ctx* c, const double* knots_host, int64_t t0, int64_t dt, int K, TileOrderChoice* out)
+{
+    *out = TileOrderChoice{};
+    const size_t n_used = c->win.n_used;
+    if (!c->win.n_pm || !knots_host || !order_considers_tiles(c->order_mode, n_used, c->opt_tile_min_events)) return EMBA_OK;
+    emba_status st;
+    TileSearch ts{};
+    double f_pred = 1.0;
+    if ((st = tile_search_begin(c, knots_host, t0, dt, K, &ts, &f_pred))) return st;
+    c->order.order_inl_pred = f_pred;
+    if (order_hopeless(c->order_mode, f_pred)) return EMBA_OK;
+    const int r = clamp_tile_reserve(c->opt_tile_reserve);
+    TileChoice best{kTileRound};
+    int last = -1; bool last_fine = false;      // the candidate whose assignment the scratch holds
+    size_t br = 0, us = 0;
+    // (the tall shape first, the others have to beat it by 2 %: at equal lead-ins 36 x 32 measured 3-5 % faster than 48 x 24 — 3 M events 155 vs 161 us, config 4's
+    // shard 245 vs 260, 2 M 111 vs 115, city 463 vs 465; profiles/r06_regime_sweep.txt)
+    static const int kShapeOrder[kNumTileShapes] = {3, 0, 1, 2};
+    for (int si = 0; si < kNumTileShapes; ++si) {
+        const int sh = kShapeOrder[si];
+        if (c->opt_tile_shape >= 0 && sh != c->opt_tile_shape) continue;
+        if ((st = tile_search_evaluate(c, ts, tile_geometry(c->W, c->H, kTileShapes[sh], false, r), &br, &us))) return st;
+        last = sh; last_fine = false;
+        best.offer(sh, n_used, br, us);
     }
-    // per-entry outputs of the evaluations
+    if (best.wants_fine(c->opt_tile_fine, n_used)) {
+        if ((st = tile_search_evaluate(c, ts, tile_geometry(c->W, c->H, kTileShapes[best.shape], true, r), &br, &us))) return st;
+        last = best.shape; last_fine = true;
+        best.offer_fine(c->opt_tile_fine, n_used, br, us);
+    }
+    if (best.shape < 0) return fail(c, EMBA_ERR_INVALID_ARG, "option tile_shape %d: no such shape", c->opt_tile_shape);
+    out->g = tile_geometry(c->W, c->H, kTileShapes[best.shape], best.fine, r);
+    if (last != best.shape || last_fine != best.fine) { if ((st = tile_search_evaluate(c, ts, out->g, &br, &us))) return st; }   // ord.bin / ord.flags of the winner
+    c->order.tile_shape = best.shape; c->order.tile_fine = best.fine;
+    out->nbins = (size_t)out->g.nbx * out->g.nby + 1; out->breaks = best.breaks; out->used = best.used;
+    c->order.order_per_px = events_per_pano_px(n_used, best.used, out->g); c->order.order_lead_frac = lead_in_fraction(n_used, best.breaks);
+    out->tile = tile_order_wins(c->order_mode, n_used, c->opt_tile_min_events, c->order.order_per_px, f_pred, c->order.order_lead_frac);
+    return EMBA_OK;
+}
+
+// pixel order: the device order is the pm-order
+emba_status build_pixel_order(emba_ctx* c)
+{
+    hipStream_t s = c->stream;
+    emba_status st;
+    const size_t ns = c->win.n_pm;
+    c->order.d_ev_pix = c->d_pm_pix.as<uint32_t>(); c->order.d_ev_batch = c->d_pm_batch.as<uint32_t>();
+    c->win.n_sorted = ns;
+    // per entry the spline parameter and segment of its batch (the warp kernel's per-event pose: 10 B per entry, streamed with the event words)
+    if ((st = ensure<double>(c, c->d_ev_u, std::max<size_t>(ns, 1))) || (st = ensure<uint16_t>(c, c->d_ev_seg, std::max<size_t>(ns, 1)))) return st;
+    if (ns) hipLaunchKernelGGL(emba_entry_pose_args_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_batch.as<uint32_t>(), (long)ns, c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>());
+    // the candidate flags of the device order
+    if ((st = ensure<uint32_t>(c, c->ord.flags, std::max<size_t>(ns, 1)))) return st;
+    if (ns) hipLaunchKernelGGL(emba_cand_flag_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->order.d_ev_pix, (long)ns, c->ord.flags.as<uint32_t>());
+    return EMBA_OK;
+}
+
+// tile order — expanded list: every event, plus a lead-in copy of its predecessor where its chain enters a tile -> stable sort by tile -> chunks.
+// Leaves the candidate flags of the device order in ord.flags.
+emba_status build_tile_order(emba_ctx* c, const TileOrderChoice& ch)
+{
+    hipStream_t s = c->stream;
+    emba_status st;
+    const size_t ns = c->win.n_pm, nbins = ch.nbins;
+    uint32_t *d_bin = c->ord.bin.as<uint32_t>(), *d_emit = c->ord.flags.as<uint32_t>(), *d_pos = c->ord.pos.as<uint32_t>(), *d_tot = c->ord.status.as<uint32_t>() + 4;
+    if ((st = dev_scan(c, d_emit, d_pos, ns, d_tot))) return st;
+    uint32_t nd32 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nd32, d_tot, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const size_t nd = nd32;
+    if ((st = ensure_sort_pairs(c, nd)) || (st = ensure<uint32_t>(c, c->ord.bin_start_or_x, nbins + 1))) return st;
+    uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+    uint32_t* d_bin_start = c->ord.bin_start_or_x.as<uint32_t>();
+    hipLaunchKernelGGL(emba_expand_write_kernel, dim3(nblocks(ns)), dim3(256), 0, s, c->d_pm_pix.as<uint32_t>(), d_bin, d_emit, d_pos, (long)ns, k0, v0);
+    if ((st = dev_sort(c, &k0, &v0, &k1, &v1, nd, bits_for(nbins)))) return st;
+    if ((st = ensure<uint32_t>(c, c->d_ev_pix_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_batch_own, nd)) || (st = ensure<uint32_t>(c, c->d_ev_pm, nd)) ||
+        (st = ensure<double>(c, c->d_ev_u, nd)) || (st = ensure<uint16_t>(c, c->d_ev_seg, nd)))
+        return st;
+    c->order.d_ev_pix = c->d_ev_pix_own.as<uint32_t>(); c->order.d_ev_batch = c->d_ev_batch_own.as<uint32_t>(); c->order.have_ev_pm = true;
+    HIP_TRY(c, hipMemsetAsync(d_bin_start, 0xFF, (nbins + 1) * 4, s));
+    uint32_t* d_cf = d_emit;    // (emit is dead: its buffer now takes the candidate flags of the device order — nd <= 2 ns may exceed it)
+    if (nd > ns) { if ((st = ensure<uint32_t>(c, c->ord.flags, nd))) return st; d_cf = c->ord.flags.as<uint32_t>(); }
+    hipLaunchKernelGGL(emba_dev_gather_kernel, dim3(nblocks(nd)), dim3(256), 0, s, k0, v0, (long)nd, c->d_pm_pix.as<uint32_t>(), c->d_pm_batch.as<uint32_t>(), c->order.d_ev_pix, c->order.d_ev_batch,
+                       c->d_ev_pm.as<uint32_t>(), c->d_cp.as<uint16_t>(), c->d_batch_u.as<double>(), c->d_ev_seg.as<uint16_t>(), c->d_ev_u.as<double>(), d_cf, d_bin_start);
+    std::vector<uint32_t> h_start(nbins + 1);
+    HIP_TRY(c, hipMemcpyAsync(h_start.data(), d_bin_start, (nbins + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->order.chunks_lpt = !c->opt_chunk_order_bin;
+    const std::vector<ChunkDesc> h_chunks = cut_chunks(kTileRound, h_start.data(), nbins, nd, ch.g, c->n_cu, c->opt_tile_chunk, c->order.chunks_lpt);
+    c->order.n_chunks = (long)h_chunks.size();
+    if ((st = ensure<ChunkDesc>(c, c->d_chunks, h_chunks.size()))) return st;
+    HIP_TRY(c, hipMemcpyAsync(c->d_chunks.as<ChunkDesc>(), h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->win.n_sorted = nd; c->order.n_lead = nd - c->win.n_used; c->order.tile_order = true;
+    return EMBA_OK;
+}
+
+// record slots sorted by control-pose pair: candidates of the device order (flags in ord.flags) -> (key, entry) -> stable sort -> slot
+emba_status assign_record_slots(emba_ctx* c, int K)
+{
+    hipStream_t s = c->stream;
+    emba_status st;
+    const size_t nd = c->win.n_sorted, M = c->win.n_cand;
+    if ((st = ensure<uint32_t>(c, c->ord.pos, std::max<size_t>(nd, 1)))) return st;
+    uint32_t *d_cf = c->ord.flags.as<uint32_t>(), *d_cpos = c->ord.pos.as<uint32_t>();
+    if ((st = dev_scan(c, d_cf, d_cpos, nd, nullptr))) return st;
+    if ((st = ensure_sort_pairs(c, std::max<size_t>(M, 1)))) return st;
+    uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+    if ((st = ensure<uint32_t>(c, c->d_ev_slot, nd))) return st;
+    HIP_TRY(c, hipMemsetAsync(c->d_ev_slot.as<uint32_t>(), 0xFF, std::max<size_t>(nd, 1) * 4, s));
+    if (nd) hipLaunchKernelGGL(emba_cand_keys_kernel, dim3(nblocks(nd)), dim3(256), 0, s, c->order.d_ev_pix, c->order.d_ev_batch, c->d_cp.as<uint16_t>(), (long)nd, d_cpos, k0, v0);
+    // the key's low half is cp_p, the high half cp_c, both < K: sort on the bits they really use
+    const int kb = bits_for((size_t)K);
+    if (kb <= 8) {   // fold the two halves into one 16-bit key for the sort (two passes instead of four)
+        if (M) hipLaunchKernelGGL(emba_fold_keys_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, (long)M, 1);
+        if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 16))) return st;
+        if (M) hipLaunchKernelGGL(emba_fold_keys_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, (long)M, 0);
+    } else if ((st = dev_sort(c, &k0, &v0, &k1, &v1, M, 32))) return st;
+    if (M) hipLaunchKernelGGL(emba_slot_assign_kernel, dim3(nblocks(M)), dim3(256), 0, s, k0, v0, (long)M, c->d_ev_slot.as<uint32_t>(), c->d_slot_key.as<uint32_t>());
+    return EMBA_OK;
+}
+
+// At the first evaluation of a window (and again whenever the spline timing changes): the control-pose pair of every measurement,
+// the device order (pixel order, or tile order from the panorama positions the given control poses predict) and the record slots
+// sorted by pair.  Pose-independent except for the tile binning, which only affects speed.
+emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int64_t dt, int K)
+{
+    if (c->order.keys_ready && c->order.key_t0 == t0 && c->order.key_dt == dt && c->order.key_K == K) return EMBA_OK;
+    if (dt <= 0 || K < 2 || K > 65535) return fail(c, EMBA_ERR_INVALID_ARG, "bad spline: dt_ns=%lld K=%d", (long long)dt, K);
+    const auto t_begin = std::chrono::steady_clock::now();
+    hipStream_t s = c->stream;
+    emba_status st;
+    const size_t ns = c->win.n_pm;
+    c->order = new_order(c->order);      // (a previous order of this window goes away; its buffers are reused)
+    TileOrderChoice choice;
+    if ((st = order_batch_segments(c, t0, dt, K)) || (st = choose_tile_order(c, knots_host, t0, dt, K, &choice))) return st;
+    if ((st = choice.tile ? build_tile_order(c, choice) : build_pixel_order(c))) return st;
+    c->win.nblk = (long)((c->win.n_sorted + kWarpNew - 1) / kWarpNew);
+    if ((st = assign_record_slots(c, K))) return st;
     // per-event outputs of the evaluations, indexed in pm-order in both orders
     if ((st = ensure<double>(c, c->d_e_sorted, ns)) || (st = ensure<uint8_t>(c, c->d_flag, ns)) || (st = ensure<int32_t>(c, c->d_inl_idx, ns))) return st;
     HIP_TRY(c, hipMemsetAsync(c->d_flag.as<uint8_t>(), 0, std::max<size_t>(ns, 1), s));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->keys_ready = true; c->key_t0 = t0; c->key_dt = dt; c->key_K = K;
+    c->order.keys_ready = true; c->order.key_t0 = t0; c->order.key_dt = dt; c->order.key_K = K;
     c->prepare_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return EMBA_OK;
 }
 
 // the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime: nearly every
 // slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
-bool gram_uses_tags(const emba_ctx* c, bool ep_host) { return c->use_tags && !c->tile_order && !ep_host; }
+bool gram_uses_tags(const emba_ctx* c, bool ep_host) { return c->use_tags && !c->order.tile_order && !ep_host; }
 
 emba_status ensure_pack(emba_ctx* c, int K)
 {
@@ -726,13 +438,13 @@ emba_status launch_ep_compaction(emba_ctx* c)
     if (!c->ev.ep_deferred) return EMBA_OK;
     c->ev.ep_deferred = false;
     hipStream_t s = c->stream;
-    if (c->n_pm) {
+    if (c->win.n_pm) {
         const uint32_t* perm = nullptr;    // (flags and residuals are stored in pm-order by both warp kernels)
-        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_flag.as<uint8_t>(), perm, (long)c->n_pm, c->d_fblk_cnt.as<uint32_t>());
+        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_flag.as<uint8_t>(), perm, (long)c->win.n_pm, c->d_fblk_cnt.as<uint32_t>());
         // (round 6: the block counts by the three-launch scan — one 256-thread block walked all of them before: 101 us for 97 k counts at 100 M events)
-        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
-                           (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
+        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
+        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
+                           (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
         c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
         HIP_TRY(c, hipGetLastError());
     } else {
@@ -748,11 +460,11 @@ emba_status launch_ep_compaction(emba_ctx* c)
 emba_status ensure_inl_idx(emba_ctx* c)
 {
     { emba_status st = launch_ep_compaction(c); if (st) return st; }
-    if (c->ev.inl_idx_valid || !c->n_pm) return EMBA_OK;
+    if (c->ev.inl_idx_valid || !c->win.n_pm) return EMBA_OK;
     // (the fused step leaves the per-block inlier counts of this evaluation in d_fblk_cnt, not their prefix)
-    { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>()); if (st) return st; }
-    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
-                       (long)c->n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
+    { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>()); if (st) return st; }
+    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
+                       (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
     HIP_TRY(c, hipGetLastError());
     c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
     return EMBA_OK;
@@ -789,20 +501,20 @@ emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
         c->ev.inl_pending = false;
         if (c->h_pinned[1] & 1) return fail(c, EMBA_ERR_TIME_RANGE, "a batch midpoint lies outside the spline's knots");
         c->n_inliers = (size_t)(uint32_t)c->h_pinned[0];
-        c->n_outside_tile = (size_t)((uint32_t)c->h_pinned[1] >> 1);
+        c->win.n_outside_tile = (size_t)((uint32_t)c->h_pinned[1] >> 1);
         // Tile order: the bins were predicted with the trajectory of the window's first evaluation.  Events that have since left their
         // tile (+ margin) are still handled correctly, but one by one through HBM atomics; once that is a fifth of the inliers the order
         // is rebuilt from the CURRENT trajectory at the next evaluation (an LM loop that starts far from its solution).
         // (not again within three evaluations: a loop whose every trial moves the events further than the margin would re-bin each time)
-        if (c->tile_order && c->n_inliers && c->n_outside_tile * 5 > c->n_inliers && c->rec_stamp - c->last_rebin_stamp >= 3) {
-            c->keys_ready = false; ++c->n_rebin; c->last_rebin_stamp = c->rec_stamp;
+        if (c->order.tile_order && c->n_inliers && c->win.n_outside_tile * 5 > c->n_inliers && c->rec_stamp - c->win.last_rebin_stamp >= 3) {
+            c->order.keys_ready = false; ++c->win.n_rebin; c->win.last_rebin_stamp = c->rec_stamp;
         }
         c->ev.done = true;
     }
     if (c->ev.P_pending) {
         c->ev.P_pending = false;
         c->eq.P = (size_t)(uint32_t)c->h_pinned[2];
-        c->P_prev = c->eq.P;
+        c->win.P_prev = c->eq.P;
         c->eq.pack_len = (size_t)9 * c->eq.K * c->eq.K + (size_t)3 * c->eq.K + 5 * c->eq.P;
         if (c->eq.pack_len > c->pack_cap)
             return fail(c, EMBA_ERR_CAPACITY, "pack buffer too small: need %zu doubles, have %zu", c->eq.pack_len, c->pack_cap);
@@ -1081,20 +793,20 @@ emba_status set_events_core(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
                             size_t n, const uint16_t* hx, const uint16_t* hy, const int64_t* hbt, size_t n_halo)
 {
     hipStream_t s = c->stream;
-    c->last_rebin_stamp = c->rec_stamp - 3; c->n_outside_tile = 0;   // a new window may be re-binned at its first drifted evaluation
+    c->win.n_outside_tile = 0;
     const size_t n_used = (n / 100) * 100;   // quirk Q1: std::ceil of an integer division (model.cpp:79)
     const size_t nb = n_used / 100;
     if (n_used + n_halo >= 0x3FFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events for 32-bit indices");
-    c->n_in = n; c->n_used = n_used; c->n_halo = n_halo; c->n_batch = nb + n_halo;
+    c->win.n_in = n; c->win.n_used = n_used; c->win.n_halo = n_halo; c->win.n_batch = nb + n_halo;
     const size_t ns = n_used + n_halo;
-    c->n_pm = ns; c->n_sorted = ns;
+    c->win.n_pm = ns; c->win.n_sorted = ns;
     emba_status st;
     if ((st = ensure<uint32_t>(c, c->ord.status, 16))) return st;
     uint32_t* d_err = c->ord.status.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
     hipLaunchKernelGGL(emba_validate_events_kernel, dim3(nblocks(std::max(n_used, n_halo))), dim3(256), 0, s, x, y, t_dev, (long)n_used, c->sw, c->sh, hx, hy,
                        (long)n_halo, d_err);
-    if ((st = ensure<int64_t>(c, c->d_batch_t, c->n_batch))) return st;
+    if ((st = ensure<int64_t>(c, c->d_batch_t, c->win.n_batch))) return st;
     if (t_dev) { if (nb) hipLaunchKernelGGL(emba_batch_mid_kernel, dim3(nblocks(nb)), dim3(256), 0, s, t_dev, (long)nb, c->d_batch_t.as<int64_t>()); }
     else if (nb) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t.as<int64_t>(), batch_t_host, nb * 8, hipMemcpyHostToDevice, s));
     if (n_halo) HIP_TRY(c, hipMemcpyAsync(c->d_batch_t.as<int64_t>() + nb, hbt, n_halo * 8, hipMemcpyDeviceToDevice, s));
@@ -1117,23 +829,23 @@ emba_status set_events_core(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
     if (h_err[0] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[0], c->sw, c->sh);
     if (h_err[1] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[1]);
     if (h_err[2] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "halo event %u outside the sensor", h_err[2]);
-    c->n_cand = ns ? h_err[4] : 0;
-    const size_t n_cand = c->n_cand;
+    c->win.n_cand = ns ? h_err[4] : 0;
+    const size_t n_cand = c->win.n_cand;
 
-    if ((st = ensure<double>(c, c->d_pose, c->n_batch * kPoseStride))) return st;
+    if ((st = ensure<double>(c, c->d_pose, c->win.n_batch * kPoseStride))) return st;
     if ((st = size_record_set(c, c->work, n_cand))) return st;
     if ((st = ensure<uint32_t>(c, c->d_slot_key, n_cand))) return st;
-    c->n_fblk = (long)std::max<size_t>((ns + kFlagBlk - 1) / kFlagBlk, 1);
-    if ((st = ensure<uint32_t>(c, c->d_fblk_cnt, (size_t)c->n_fblk)) || (st = ensure<uint32_t>(c, c->d_fblk_off, (size_t)c->n_fblk))) return st;
-    c->n_fsup = (c->n_fblk + kFlagSup - 1) / kFlagSup;
-    if ((st = ensure<uint32_t>(c, c->d_fsup, (size_t)2 * c->n_fsup * kFlagSupStride))) return st;
-    HIP_TRY(c, hipMemsetAsync(c->d_fsup.as<uint32_t>(), 0, (size_t)2 * c->n_fsup * kFlagSupStride * sizeof(uint32_t), c->stream));      // (both halves: launch A adds into one and zeroes the other for the next step)
+    c->win.n_fblk = (long)std::max<size_t>((ns + kFlagBlk - 1) / kFlagBlk, 1);
+    if ((st = ensure<uint32_t>(c, c->d_fblk_cnt, (size_t)c->win.n_fblk)) || (st = ensure<uint32_t>(c, c->d_fblk_off, (size_t)c->win.n_fblk))) return st;
+    c->win.n_fsup = (c->win.n_fblk + kFlagSup - 1) / kFlagSup;
+    if ((st = ensure<uint32_t>(c, c->d_fsup, (size_t)2 * c->win.n_fsup * kFlagSupStride))) return st;
+    HIP_TRY(c, hipMemsetAsync(c->d_fsup.as<uint32_t>(), 0, (size_t)2 * c->win.n_fsup * kFlagSupStride * sizeof(uint32_t), c->stream));      // (both halves: launch A adds into one and zeroes the other for the next step)
     if ((st = ensure<double>(c, c->d_ep, ns))) return st;
     c->eq_in_alt = false;
     if (c->alt.rec.p && (st = size_record_set(c, c->alt, n_cand))) return st;   // the second record set (if an LM loop has made one) follows the window's size
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->nblk = (long)((ns + kWarpNew - 1) / kWarpNew);
-    c->have_events = true;
+    c->win.nblk = (long)((ns + kWarpNew - 1) / kWarpNew);
+    c->win.have_events = true;
     return EMBA_OK;
 }
 
@@ -1201,8 +913,8 @@ emba_status emba_set_events_dev(emba_ctx* c, const uint16_t* x_dev, const uint16
 emba_status emba_last_tile_drift(const emba_ctx* c, size_t* n_outside, int32_t* n_rebin)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (n_outside) *n_outside = c->n_outside_tile;
-    if (n_rebin) *n_rebin = c->n_rebin;
+    if (n_outside) *n_outside = c->win.n_outside_tile;
+    if (n_rebin) *n_rebin = c->win.n_rebin;
     return EMBA_OK;
 }
 
@@ -1211,45 +923,44 @@ emba_status emba_last_setup_ms(const emba_ctx* c, double* set_events_ms, double*
     if (!c) return EMBA_ERR_INVALID_ARG;
     if (set_events_ms) *set_events_ms = c->set_events_ms;
     if (prepare_ms) *prepare_ms = c->prepare_ms;
-    if (tile_order) *tile_order = c->tile_order ? 1 : 0;
-    if (n_entries) *n_entries = c->n_sorted;
-    if (n_chunks) *n_chunks = (size_t)c->n_chunks;
+    if (tile_order) *tile_order = c->order.tile_order ? 1 : 0;
+    if (n_entries) *n_entries = c->win.n_sorted;
+    if (n_chunks) *n_chunks = (size_t)c->order.n_chunks;
     return EMBA_OK;
 }
 
 emba_status emba_last_order_stats(const emba_ctx* c, double* events_per_pano_px, double* lead_in_frac)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (events_per_pano_px) *events_per_pano_px = c->order_per_px;
-    if (lead_in_frac) *lead_in_frac = c->order_lead_frac;
+    if (events_per_pano_px) *events_per_pano_px = c->order.order_per_px;
+    if (lead_in_frac) *lead_in_frac = c->order.order_lead_frac;
     return EMBA_OK;
 }
 
 emba_status emba_last_order_inlier_estimate(const emba_ctx* c, double* inlier_frac)
 {
     if (!c || !inlier_frac) return EMBA_ERR_INVALID_ARG;
-    *inlier_frac = c->order_inl_pred;
+    *inlier_frac = c->order.order_inl_pred;
     return EMBA_OK;
 }
 
 emba_status emba_last_tile_geometry(const emba_ctx* c, int32_t* tile_w, int32_t* tile_h, int32_t* pitch_x, int32_t* pitch_y, int32_t* reserve)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    const TileShape& ts = kTileShapes[c->tile_shape];
-    const int r = std::max(0, std::min(c->opt_tile_reserve, 5));
-    if (tile_w) *tile_w = ts.tw;
-    if (tile_h) *tile_h = ts.th;
-    if (pitch_x) *pitch_x = std::min(c->tile_fine ? ts.fine_pw : ts.pw, ts.tw - 2 * r);
-    if (pitch_y) *pitch_y = std::min(c->tile_fine ? ts.fine_ph : ts.ph, ts.th - 2 * r);
-    if (reserve) *reserve = r;
+    const BinGeom g = tile_geometry(c->W, c->H, kTileShapes[c->order.tile_shape], c->order.tile_fine, clamp_tile_reserve(c->opt_tile_reserve));
+    if (tile_w) *tile_w = g.tw;
+    if (tile_h) *tile_h = g.th;
+    if (pitch_x) *pitch_x = g.bw;
+    if (pitch_y) *pitch_y = g.bh;
+    if (reserve) *reserve = g.r;
     return EMBA_OK;
 }
 
 emba_status emba_event_counts(const emba_ctx* c, size_t* n_used, size_t* n_cand)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (n_used) *n_used = c->n_used;
-    if (n_cand) *n_cand = c->n_cand;
+    if (n_used) *n_used = c->win.n_used;
+    if (n_cand) *n_cand = c->win.n_cand;
     return EMBA_OK;
 }
 
@@ -1290,7 +1001,7 @@ emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double 
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st = resolve_pending(c);
     if (st) return st;
-    if (src_kind == 2 && c->eq.P && c->x2_resident_P != c->eq.P) return fail(c, EMBA_ERR_STATE, "x2 NULL: no solve of the current normal equations has left its x2 on the device");
+    if (src_kind == 2 && c->eq.P && c->solve.x2_resident_P != c->eq.P) return fail(c, EMBA_ERR_STATE, "x2 NULL: no solve of the current normal equations has left its x2 on the device");
     if (src_kind != 2 && c->eq.P && !x2) return fail(c, EMBA_ERR_INVALID_ARG, "x2 NULL");
     if ((st = ensure<double>(c, c->d_Gx_trial, c->npix)) || (st = ensure<double>(c, c->d_Gy_trial, c->npix))) return st;
     if ((st = ensure_x2(c, c->eq.P))) return st;
@@ -1298,7 +1009,7 @@ emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double 
     if ((st = ensure_compact(c))) return st;
     if (c->eq.P && src_kind != 2) {
         HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), x2, 2 * c->eq.P * sizeof(double), src_kind == 0 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-        c->x2_resident_P = (size_t)-1;      // (whatever a solve left there is overwritten)
+        c->solve.x2_resident_P = (size_t)-1;      // (whatever a solve left there is overwritten)
     }
     hipLaunchKernelGGL(emba_update_map_kernel, dim3((unsigned)((c->npix + 255) / 256)), dim3(256), 0, s, c->d_Gx_cur, c->d_Gy_cur, c->d_compact.as<int32_t>(),
                        c->d_x2.as<double>(), damping, (long)c->npix, c->d_Gx_trial.as<double>(), c->d_Gy_trial.as<double>());
@@ -1314,7 +1025,7 @@ emba_status keep_x2(emba_ctx* c, const double* d_src, size_t P)
     emba_status st = ensure_x2(c, P);
     if (st) return st;
     if (P) HIP_TRY(c, hipMemcpyAsync(c->d_x2.as<double>(), d_src, 2 * P * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->x2_resident_P = P;
+    c->solve.x2_resident_P = P;
     return EMBA_OK;
 }
 }  // namespace
@@ -1433,7 +1144,7 @@ namespace {
 emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const EvalOpts& opt)
 {
     if (!knots) return fail(c, EMBA_ERR_INVALID_ARG, "knots NULL");
-    if (!c->have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
+    if (!c->win.have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
     if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
     HIP_TRY(c, hipSetDevice(c->device));
     emba_status st;
@@ -1451,7 +1162,7 @@ emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_
         // The working record set is what the current normal equations were formed from: this evaluation (an LM trial, or simply the next
         // step) writes the OTHER set, so that a rejection can go back to untouched equations (emba_trial_reject).
         if (c->ev.P_pending || c->ev.inl_pending) { if ((st = resolve_pending(c, true))) return st; }
-        if (!c->alt.rec.p && (st = size_record_set(c, c->alt, c->n_cand))) return st;
+        if (!c->alt.rec.p && (st = size_record_set(c, c->alt, c->win.n_cand))) return st;
         std::swap(c->work, c->alt);
         c->eq_saved = c->eq;
         c->eq_in_alt = true;
@@ -1470,15 +1181,15 @@ emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_
     // never formed by the resident step, whose gather clears them behind itself); the count map's entries are stamped and need no clearing
     // (... and only when a warp kernel follows to re-mark it — an EMPTY window launches none, so its count map and active set would be the
     // previous window's; the reference clears, model.cpp:85, and finds P = 0)
-    const int n_prep_blk = (c->pixacc_clean && c->n_sorted) ? 0 : (int)((c->npix + 1023) / 1024);
+    const int n_prep_blk = (c->pixacc_clean && c->win.n_sorted) ? 0 : (int)((c->npix + 1023) / 1024);
     // Hessian source: with several events per panorama pixel (measured break-even: ~4) the full texel pack (one 48-B gather per
     // measurement instead of an 18-load stencil) pays for itself; otherwise texels are packed only inside the bounding box of the pixels an
     // earlier evaluation touched, and the warp kernel falls back to the stencil outside it.
-    c->use_texel = c->texel_mode == 1 ? 1 : c->texel_mode == 2 ? 0 : c->texel_mode == 3 ? 3 : (c->n_sorted > 4 * c->npix ? 1 : 3);
+    c->use_texel = c->texel_mode == 1 ? 1 : c->texel_mode == 2 ? 0 : c->texel_mode == 3 ? 3 : (c->win.n_sorted > 4 * c->npix ? 1 : 3);
     {   // ONE launch in front of the warp kernel: prep || pose table (or segment records) || texel rectangle — independent of each other
         PrepPoseTexelParams q{};
         InlineKnots kn;
-        const int nb = (int)c->n_batch;
+        const int nb = (int)c->win.n_batch;
         ++c->eval_seq;
         c->d_err = c->d_err2.as<int>() + (c->eval_seq & 1u);
         q.count = c->d_count; q.npix = (long)c->npix; q.pixacc = c->d_pixacc.as<double>(); q.W = c->W; q.H = c->H; q.n_prep = n_prep_blk;
@@ -1489,8 +1200,8 @@ emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_
         // step time: 1 M events 101.2 -> 98.2 us, 1.5 M 150.8 -> 143.5, 10 M on 640x480 (city shape) 779 -> 714 (warp 0.60 -> 0.68 of the roofline),
         // 10 M on 2048x4096 / K = 256 940 -> 861.  (Round 1 had measured the opposite at 1 M events, + 6 us, on a kernel that was then VALU-heavier in
         // other places; option segpose = 1 keeps the per-batch table for comparison.)
-        c->segpose = !c->tile_order && (c->segpose_mode ? c->segpose_mode == 2 : true);
-        const bool seg_records = c->tile_order || c->segpose;
+        c->segpose = !c->order.tile_order && (c->segpose_mode ? c->segpose_mode == 2 : true);
+        const bool seg_records = c->order.tile_order || c->segpose;
         q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
         q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
         q.knots_dev = c->d_knots.as<double>(); q.knots_out = c->d_knots.as<double>();
@@ -1511,27 +1222,27 @@ emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_
     if (c->use_texel == 1)
         hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, s, c->d_Gx, c->d_Gy, c->H, c->W,
                            c->d_texel.as<double>());
-    if (c->n_sorted) {
+    if (c->win.n_sorted) {
         WarpParams p{};
-        p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)c->n_sorted;
+        p.ev_pix = c->order.d_ev_pix; p.ev_batch = c->order.d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)c->win.n_sorted;
         p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
-        p.nblk = c->nblk; p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = c->use_texel ? c->d_texel.as<double>() : nullptr; p.W = c->W; p.H = c->H;
+        p.nblk = c->win.nblk; p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = c->use_texel ? c->d_texel.as<double>() : nullptr; p.W = c->W; p.H = c->H;
         p.rect_acc = (c->use_texel == 3) ? rect_cur : nullptr;
         p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc.as<double>();
         p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px;
-        p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.tag = (c->use_tags && !c->tile_order) ? c->work.tag.as<double>() : nullptr; p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
+        p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.tag = (c->use_tags && !c->order.tile_order) ? c->work.tag.as<double>() : nullptr; p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
         p.err = c->d_err;
         p.ablate = c->ablate;
-        p.rec_nt = (c->tile_order || c->n_cand * (size_t)(kRecStride * 8) > ((size_t)144 << 20)) ? 1 : 0;      // (1 M slots = 128 MB: kept in the Infinity Cache for the Gram kernel)
+        p.rec_nt = (c->order.tile_order || c->win.n_cand * (size_t)(kRecStride * 8) > ((size_t)144 << 20)) ? 1 : 0;      // (1 M slots = 128 MB: kept in the Infinity Cache for the Gram kernel)
         p.irls = opt.irls; p.eta = opt.eta;
         p.stamp = ++c->rec_stamp; c->work.stamp = p.stamp;
         p.marker = c->count_mark = count_marker(p.stamp);
         c->pixacc_clean = false; c->pixacc_consumed = false;
-        p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->n_chunks; p.chunks_linear = c->chunks_lpt ? 1 : 0;
+        p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->order.n_chunks; p.chunks_linear = c->order.chunks_lpt ? 1 : 0;
         if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
-        if (c->tile_order) launch_warp_tiled(c->tile_shape, dim3((unsigned)grid8(c->n_chunks)), s, p);
-        else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
-        else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
+        if (c->order.tile_order) launch_warp_tiled(c->order.tile_shape, dim3((unsigned)grid8(c->order.n_chunks)), s, p);
+        else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
+        else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
         if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[1], s)); c->kt_warp_valid = true; c->kt_valid[c->kt_slot][0] = true; }
         c->counts_raw = true;
     } else {
@@ -1598,21 +1309,21 @@ emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len,
     if (c->eq.force_generic_a22) { aw.A22b2 = nullptr; aw.alpha = 0.0; }
     // a sharded window's rank in resident-step mode (emba_step_form_active): activity from the exchanged byte counts, which launch A reads beside this rank's
     // own counts — where the list-driven gather cannot be used the bytes are expanded into the count map first and the sweeping forms below see global counts
-    const bool lists_ok = opt.consume && c->step_gather && !c->eq.force_generic_a22 && (long)c->n_ablk <= kGatherMaxUnits && c->n_cand &&
-                          (c->step_gather == 3 || !c->tile_order || c->n_cand <= 3500000);
+    const bool lists_ok = opt.consume && c->step_gather && !c->eq.force_generic_a22 && (long)c->n_ablk <= kGatherMaxUnits && c->win.n_cand &&
+                          (c->step_gather == 3 || !c->order.tile_order || c->win.n_cand <= 3500000);
     const uint8_t* global_u8 = opt.global_u8;
-    if (global_u8 && !(lists_ok && c->ev.ep_deferred && c->n_sorted && !c->counts_raw)) {
+    if (global_u8 && !(lists_ok && c->ev.ep_deferred && c->win.n_sorted && !c->counts_raw)) {
         { emba_status st0 = ensure_counts(c); if (st0) return st0; }
         c->ev.count_stamp = 0;
         hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, s, global_u8, npix, c->d_count);
         global_u8 = nullptr;      // (the count map holds them now)
     }
-    if (c->ev.ep_deferred && c->n_sorted) {
+    if (c->ev.ep_deferred && c->win.n_sorted) {
         c->ev.ep_deferred = false;
         PostWarpParams q{};
         q.count = c->d_count; q.npix = npix; q.thres = thres; q.ablk_cnt = c->d_ablk_cnt.as<uint32_t>(); q.ablk_off = c->d_ablk_off.as<uint32_t>(); q.n_ablk = (long)c->n_ablk;
         q.total_P = c->d_total.as<uint32_t>() + 1; q.total_P_host = c->h_pinned_dev + 2;
-        q.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); q.fblk_off = c->d_fblk_off.as<uint32_t>(); q.n_fblk = c->n_fblk; q.perm = nullptr; q.n_pm = (long)c->n_pm;
+        q.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); q.fblk_off = c->d_fblk_off.as<uint32_t>(); q.n_fblk = c->win.n_fblk; q.perm = nullptr; q.n_pm = (long)c->win.n_pm;
         q.total_inl = c->d_total.as<uint32_t>(); q.total_inl_host = c->h_pinned_dev;
         q.err_dev = c->d_err; q.err_host = c->h_pinned_dev + 1;
         q.e_sorted = c->d_e_sorted.as<double>(); q.flag = c->d_flag.as<uint8_t>(); q.ep = c->d_ep.as<double>(); q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
@@ -1642,11 +1353,11 @@ emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len,
         // and "sum every predecessor"): 38-270 us against 6.3 + 11.2 — the eight XCDs' L2s are not coherent with each other, so every flag is a
         // round trip to the memory side (and a release / acquire pair writes back / invalidates a whole L2); a kernel boundary is cheaper.
         c->fsup_half ^= 1;
-        q.fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride; q.fsup_next = c->d_fsup.as<uint32_t>() + (size_t)(c->fsup_half ^ 1) * c->n_fsup * kFlagSupStride; q.n_sup = c->n_fsup;
+        q.fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->win.n_fsup * kFlagSupStride; q.fsup_next = c->d_fsup.as<uint32_t>() + (size_t)(c->fsup_half ^ 1) * c->win.n_fsup * kFlagSupStride; q.n_sup = c->win.n_fsup;
         q.active_bits = c->d_active_bits.as<uint8_t>(); q.pack_head = c->d_pack; q.head_len = head; aw.bits_head_done = 1;
         q.blk_rect = c->d_blk_rect.as<int>(); q.W = c->W; aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the texel rectangle of the NEXT evaluation
-        hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->n_fblk)), dim3(256), 0, s, q);
-        aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->n_fblk; aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
+        hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->win.n_fblk)), dim3(256), 0, s, q);
+        aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->win.n_fblk; aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
         aw.total_inl = q.total_inl; aw.total_inl_host = q.total_inl_host; aw.err_dev = q.err_dev; aw.err_host = q.err_host; aw.seq = q.seq; aw.seq_host = q.seq_host;
         // (round 4, measured and dropped: this write on a side stream beside the Gram kernel — both only depend on launch A — costs more than it
         // hides: each cross-stream event edge opens a 7-12 us bubble on this stack, 114.5 vs 107.6 us per step)
@@ -1655,7 +1366,7 @@ emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len,
         c->aw_in_gram = false;
         // the residual vector ep of this evaluation: compacted by tail blocks of the Gram launch that follows (kernels.h: ep_tail_block) — launch A has just
         // left the per-block inlier-flag counts they need
-        c->ev.ep_in_gram = opt.wants_ep && c->step_ep != 2 && c->n_cand;
+        c->ev.ep_in_gram = opt.wants_ep && c->step_ep != 2 && c->win.n_cand;
         c->ev.ep_after_gram = opt.wants_ep && !c->ev.ep_in_gram;
         if (lists && c->step_gather >= 2) { c->aw_saved = aw; c->aw_in_gram = true; }
         else if (lists) hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, aw);
@@ -1676,8 +1387,8 @@ emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len,
     c->eq_in_alt = false;   // new equations are being formed from the working set: the other set's are obsolete
     c->ev.P_pending = true; c->eq.active_done = false; c->eq.accum_done = false;
     c->eq.finish_done = false;          // (the head of the pack has just been cleared: what a solve would read is no set of equations — found by the call-order pair test)
-    c->x2_resident_P = (size_t)-1;   // (a solve of the PREVIOUS equations may have left its x2 on the device)
-    c->lists_valid = false; c->perm_valid = false;          // (new active set)
+    c->solve.x2_resident_P = (size_t)-1;   // (a solve of the PREVIOUS equations may have left its x2 on the device)
+    c->solve.invalidate();                 // (new active set)
     if (!P && !pack_len) return EMBA_OK;   // asynchronous: P is read from device memory by the kernels that need it
     emba_status st = resolve_pending(c, true);   // counts only: a sharded host sizes exchange 2 from P while the gather still runs
     if (st) return st;
@@ -1700,7 +1411,7 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
     // the per-pixel sums of the evaluation already carry this cost's weights (emba_set_cost / emba_step)?  Then they ARE A22/b2.
     const bool acc_matches = (irls == c->ev.acc_irls) && (irls == 0 || eta == c->ev.acc_eta);
     const bool generic_a22 = !acc_matches || (ep_host != nullptr) || c->eq.force_generic_a22;
-    if (c->aw_in_gram && (generic_a22 || !c->n_cand)) {   // (not what emba_step does: the deferred gather as a launch of its own after all)
+    if (c->aw_in_gram && (generic_a22 || !c->win.n_cand)) {   // (not what emba_step does: the deferred gather as a launch of its own after all)
         hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, c->aw_saved);
         c->aw_in_gram = false;
     }
@@ -1708,8 +1419,8 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
     if (ep_host && c->n_inliers) {
         { emba_status st = ensure_inl_idx(c); if (st) return st; }
         HIP_TRY(c, hipMemcpyAsync(c->d_ep.as<double>(), ep_host, c->n_inliers * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep.as<double>(), c->d_flag.as<uint8_t>(),
-                           c->d_inl_idx.as<int32_t>(), c->d_ev_slot.as<uint32_t>(), c->d_ev_pix, c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr, (long)c->n_sorted, c->work.rec.as<double>(), c->d_e_sorted.as<double>());
+        hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->win.n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep.as<double>(), c->d_flag.as<uint8_t>(),
+                           c->d_inl_idx.as<int32_t>(), c->d_ev_slot.as<uint32_t>(), c->order.d_ev_pix, c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr, (long)c->win.n_sorted, c->work.rec.as<double>(), c->d_e_sorted.as<double>());
     }
     // A11 = Zero, b1 = Zero (model.cpp:357-361).  A22/b2 of the active pixels were gathered from the per-pixel
     // accumulator by emba_form_active (quadratic cost, device-resident residuals); with IRLS weights or a
@@ -1719,13 +1430,13 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
     if (generic_a22 && c->eq.P) {
         { emba_status st = ensure_compact(c); if (st) return st; }
         HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->eq.P * sizeof(double), s));
-        if (c->n_cand)
-            hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
-                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, irls, eta, pack_A22b2(c), c->work.stamp);
+        if (c->win.n_cand)
+            hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
+                               (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, irls, eta, pack_A22b2(c), c->work.stamp);
     }
-    if (c->n_cand) {
+    if (c->win.n_cand) {
         GramParams p{};
-        p.rec = c->work.rec.as<double>(); p.slot_key = c->d_slot_key.as<uint32_t>(); p.n_slots = (long)c->n_cand; p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits.as<uint8_t>());
+        p.rec = c->work.rec.as<double>(); p.slot_key = c->d_slot_key.as<uint32_t>(); p.n_slots = (long)c->win.n_cand; p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits.as<uint8_t>());
         p.irls = irls; p.eta = eta; p.stamp = c->work.stamp; p.A11 = pack_A11(c); p.b1 = pack_b1(c);
         // the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime:
         // nearly every slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
@@ -1737,25 +1448,25 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         // Sparse slot streams (pixel order on a large panorama: most inliers fall on pixels that stay inactive): stages of 128 tags, only the live records fetched (180 -> 78 us at 10 M events on 2048 x 4096, K = 256).
         // Which form: option gram_sparse (0 / 1), else by the LAST formed equations of this context — at least thres records per active pixel are live, and where
         // 4 thres P is still below a quarter of the slots the stream is sparse (BASELINE: 5 x 68.6 k of 1 M slots = 0.34 -> dense; 10 M events on 2048 x 4096: 0.055)
-        const bool sparse = p.tag && (c->opt_gram_sparse == 1 || (c->opt_gram_sparse < 0 && c->P_prev > 0 && c->n_cand >= (2u << 20) && 16ull * (size_t)c->eq.thres * c->P_prev < c->n_cand));
+        const bool sparse = p.tag && (c->opt_gram_sparse == 1 || (c->opt_gram_sparse < 0 && c->win.P_prev > 0 && c->win.n_cand >= (2u << 20) && 16ull * (size_t)c->eq.thres * c->win.P_prev < c->win.n_cand));
         // (sparse form: up to four times the slots per wave — a wave's pipeline takes three stages to fill; option gram_sparse_chunk: 1 ... 8, no difference from 2 up)
         const long chunk_cap = sparse ? (long)c->opt_gram_sparse_chunk * kGramChunk : kGramChunk;
         const long per_round = (long)c->n_cu * (kGramBlock / 64);
-        const long rounds = std::max<long>(1, ((long)c->n_cand + per_round * chunk_cap - 1) / (per_round * chunk_cap));
-        long chunk = ((long)c->n_cand + per_round * rounds - 1) / (per_round * rounds);
+        const long rounds = std::max<long>(1, ((long)c->win.n_cand + per_round * chunk_cap - 1) / (per_round * chunk_cap));
+        long chunk = ((long)c->win.n_cand + per_round * rounds - 1) / (per_round * rounds);
         chunk = (chunk + 7) & ~7L;
         chunk = std::min<long>(std::max<long>(chunk, kGramChunkMin), chunk_cap);
         p.chunk = (int)chunk;
-        const long waves = ((long)c->n_cand + chunk - 1) / chunk;
+        const long waves = ((long)c->win.n_cand + chunk - 1) / chunk;
         if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[2], s));
         constexpr long wpb = kGramBlock / 64;
         unsigned grid = (unsigned)((waves + wpb - 1) / wpb);
         p.n_gram_blocks = (int)grid;
-        const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->n_pm;
+        const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->win.n_pm;
         if (ep_tail) {
-            p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>(); p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_pm = (long)c->n_pm; p.ep_n_fblk = c->n_fblk;
-            p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->n_fsup * kFlagSupStride;
-            grid += (unsigned)((c->n_pm + kEpTailBlk - 1) / kEpTailBlk);
+            p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>(); p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_pm = (long)c->win.n_pm; p.ep_n_fblk = c->win.n_fblk;
+            p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->win.n_fsup * kFlagSupStride;
+            grid += (unsigned)((c->win.n_pm + kEpTailBlk - 1) / kEpTailBlk);
         }
         c->ev.ep_in_gram = false;
         const ActiveWriteParams aw = c->aw_in_gram ? c->aw_saved : ActiveWriteParams{};
@@ -1779,9 +1490,9 @@ emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irl
         if (ep_tail) c->ev.ep_valid = true;
         if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }
     }
-    if (c->ev.ep_after_gram && !ep_host && c->n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
-        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->n_fblk, c->d_total.as<uint32_t>() + 2); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->n_pm,
+    if (c->ev.ep_after_gram && !ep_host && c->win.n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
+        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>() + 2); if (st) return st; }
+        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->win.n_pm,
                            c->d_ep.as<double>(), (int32_t*)nullptr);
         c->ev.ep_valid = true;
     }
@@ -1835,9 +1546,9 @@ emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1,
         if ((st = ensure<double>(c, A12_tmp, n12))) return st;
         double* d_A12 = A12_tmp.as<double>();
         (void)hipMemsetAsync(d_A12, 0, n12 * sizeof(double), s);
-        if (c->n_cand)
-            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
-                               (long)c->n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, dim, d_A12, c->work.stamp);
+        if (c->win.n_cand)
+            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
+                               (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, dim, d_A12, c->work.stamp);
         (void)hipMemcpyAsync(A12_dense, d_A12, n12 * sizeof(double), hipMemcpyDeviceToHost, s);
     }
     hipError_t e = hipStreamSynchronize(s);
@@ -1865,7 +1576,7 @@ emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32
     if (!c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "no normal equations formed yet");
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
-    const size_t M = c->n_cand;
+    const size_t M = c->win.n_cand;
     if (!M) return EMBA_OK;
     DevBuf b_c, b_p, b_x, b_w, b_jc, b_jp, b_dp;      // (per call)
     emba_status st;
@@ -1924,7 +1635,7 @@ emba_status emba_get_inlier_pixels(emba_ctx* c, uint32_t* pix_host)
     if (!c->n_inliers) return EMBA_OK;
     if ((st = ensure<uint32_t>(c, c->dl.out, c->n_inliers))) return st;
     uint32_t* d_out = c->dl.out.as<uint32_t>();
-    hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->n_pm, d_out);
+    hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->win.n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->win.n_pm, d_out);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(pix_host, d_out, c->n_inliers * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1941,7 +1652,7 @@ emba_status emba_get_inlier_pixel_starts(emba_ctx* c, uint32_t* starts_host)
     const uint32_t S = (uint32_t)((size_t)c->sw * c->sh);
     if ((st = ensure<uint32_t>(c, c->dl.out, std::max<size_t>(c->n_inliers, 1))) || (st = ensure<uint32_t>(c, c->dl.pix_starts, (size_t)S + 1))) return st;
     uint32_t *d_px = c->dl.out.as<uint32_t>(), *d_starts = c->dl.pix_starts.as<uint32_t>();
-    if (c->n_inliers) hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->n_pm, d_px);
+    if (c->n_inliers) hipLaunchKernelGGL(emba_inlier_pix_kernel, dim3(nblocks(c->win.n_pm)), dim3(256), 0, c->stream, c->d_pm_pix.as<uint32_t>(), c->d_flag.as<uint8_t>(), c->d_inl_idx.as<int32_t>(), (long)c->win.n_pm, d_px);
     hipLaunchKernelGGL(emba_pix_starts_kernel, dim3(nblocks(c->n_inliers + 1)), dim3(256), 0, c->stream, d_px, (long)c->n_inliers, S, d_starts);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(starts_host, d_starts, ((size_t)S + 1) * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1986,9 +1697,9 @@ emba_status emba_data_cost(emba_ctx* c, int32_t irls, double eta, double* cost)
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     hipStream_t s = c->stream;
     HIP_TRY(c, hipMemsetAsync(c->d_scalar.as<double>(), 0, sizeof(double), s));
-    if (c->n_sorted) {
-        const unsigned grid = (unsigned)std::min<size_t>((c->n_pm + 255) / 256, 2048);
-        hipLaunchKernelGGL(emba_data_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (long)c->n_pm, (int)irls, eta,
+    if (c->win.n_sorted) {
+        const unsigned grid = (unsigned)std::min<size_t>((c->win.n_pm + 255) / 256, 2048);
+        hipLaunchKernelGGL(emba_data_cost_kernel, dim3(grid), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (long)c->win.n_pm, (int)irls, eta,
                            c->d_scalar.as<double>());
     }
     double v = 0;
@@ -2022,7 +1733,7 @@ emba_status emba_costs_launch(emba_ctx* c, int32_t irls, double eta, int32_t wit
     }
     hipStream_t s = c->stream;
     CostsParams p{};
-    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>(); p.n_pm = c->n_sorted ? (long)c->n_pm : 0L; p.irls = (int)irls; p.eta = eta;
+    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>(); p.n_pm = c->win.n_sorted ? (long)c->win.n_pm : 0L; p.irls = (int)irls; p.eta = eta;
     p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.npix = with_reg ? (long)c->npix : 0L;
     // (a few hundred blocks: every block ends with two same-address atomics — its sum and its ticket —, and 4096 of them on one word serialise for longer than the sums take)
     p.nb_data = (int)std::max<size_t>(1, std::min<size_t>(((size_t)p.n_pm + 255) / 256, (size_t)c->n_cu));
@@ -2084,7 +1795,7 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     HIP_TRY(c, hipSetDevice(c->device));
     { emba_status st0 = resolve_pending(c); if (st0) return st0; }
     if (inlier_idx) { emba_status st0 = ensure_inl_idx(c); if (st0) return st0; }
-    const size_t ns = c->n_sorted, n = c->n_in;
+    const size_t ns = c->win.n_sorted, n = c->win.n_in;
     if (!ns) return EMBA_OK;
     hipStream_t s = c->stream;
     // device and host staging only for what was asked for (a 100 M-event pm dump is 1.6 GB, the full state 17 GB)
@@ -2101,27 +1812,27 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     if (w_t) (void)hipMemsetAsync(d_t, 0, 2 * ns * 8, s);
     if (w_pi) (void)hipMemsetAsync(d_pi, 0xFF, 2 * ns * 4, s);
     WarpParams p{};
-    p.ev_pix = c->d_ev_pix; p.ev_batch = c->d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)ns; p.nblk = c->nblk;
+    p.ev_pix = c->order.d_ev_pix; p.ev_batch = c->order.d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)ns; p.nblk = c->win.nblk;
     p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();
     p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = nullptr; p.rect_acc = nullptr; p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc.as<double>();
     p.W = c->W; p.H = c->H; p.fx = c->fx; p.fy = c->fy; p.cx = c->cx;
     p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px; p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.e_sorted = c->d_e_sorted.as<double>();
     p.flag = c->d_flag.as<uint8_t>(); p.d_pm = d_pm; p.d_D = d_D; p.d_dp = d_dp; p.d_Gpm = d_G; p.d_temp = d_t; p.d_pm_int = d_pi;
-    if (c->tile_order) hipLaunchKernelGGL((emba_warp_residual_kernel<true, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
-    else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<true, false, true>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);   // (the last evaluation left segment records, not a pose table)
-    else hipLaunchKernelGGL((emba_warp_residual_kernel<true, false>), dim3((unsigned)grid8(c->nblk)), dim3(kWarpBlock), 0, s, p);
+    if (c->order.tile_order) hipLaunchKernelGGL((emba_warp_residual_kernel<true, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
+    else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<true, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);   // (the last evaluation left segment records, not a pose table)
+    else hipLaunchKernelGGL((emba_warp_residual_kernel<true, false>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
     std::vector<double> h_pm(w_pm ? 2 * ns : 0), h_D(w_D ? 12 * ns : 0), h_dp(w_dp ? 2 * ns : 0), h_G(w_G ? 2 * ns : 0), h_t(w_t ? 2 * ns : 0);
-    std::vector<uint16_t> h_cp(cp_idx ? c->n_batch : 0);
-    std::vector<int32_t> h_pi(w_pi ? 2 * ns : 0), h_inl(w_inl ? c->n_pm : 0);     // (inlier numbers and flags are indexed in pm-order)
-    std::vector<uint8_t> h_flag(w_flag ? c->n_pm : 0);
+    std::vector<uint16_t> h_cp(cp_idx ? c->win.n_batch : 0);
+    std::vector<int32_t> h_pi(w_pi ? 2 * ns : 0), h_inl(w_inl ? c->win.n_pm : 0);     // (inlier numbers and flags are indexed in pm-order)
+    std::vector<uint8_t> h_flag(w_flag ? c->win.n_pm : 0);
     if (w_pm) (void)hipMemcpyAsync(h_pm.data(), d_pm, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_D) (void)hipMemcpyAsync(h_D.data(), d_D, 12 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_dp) (void)hipMemcpyAsync(h_dp.data(), d_dp, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_G) (void)hipMemcpyAsync(h_G.data(), d_G, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_t) (void)hipMemcpyAsync(h_t.data(), d_t, 2 * ns * 8, hipMemcpyDeviceToHost, s);
     if (w_pi) (void)hipMemcpyAsync(h_pi.data(), d_pi, 2 * ns * 4, hipMemcpyDeviceToHost, s);
-    if (w_inl) (void)hipMemcpyAsync(h_inl.data(), c->d_inl_idx.as<int32_t>(), c->n_pm * 4, hipMemcpyDeviceToHost, s);
-    if (w_flag) (void)hipMemcpyAsync(h_flag.data(), c->d_flag.as<uint8_t>(), c->n_pm, hipMemcpyDeviceToHost, s);
+    if (w_inl) (void)hipMemcpyAsync(h_inl.data(), c->d_inl_idx.as<int32_t>(), c->win.n_pm * 4, hipMemcpyDeviceToHost, s);
+    if (w_flag) (void)hipMemcpyAsync(h_flag.data(), c->d_flag.as<uint8_t>(), c->win.n_pm, hipMemcpyDeviceToHost, s);
     if (cp_idx) (void)hipMemcpyAsync(h_cp.data(), c->d_cp.as<uint16_t>(), h_cp.size() * 2, hipMemcpyDeviceToHost, s);
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "dump_state: %s", hipGetErrorString(e));
@@ -2135,14 +1846,14 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     if (Gpm) memset(Gpm, 0, 2 * n * 8);
     if (temp) memset(temp, 0, 2 * n * 8);
     // entry of the device order -> pm-order index -> original event (lead-in copies and halo entries map to nothing)
-    std::vector<uint32_t> h_evpix(ns), h_evbatch(cp_idx ? ns : 0), h_evpm(c->have_ev_pm ? ns : 0), h_pmorig(c->n_pm);
-    HIP_TRY(c, hipMemcpy(h_evpix.data(), c->d_ev_pix, ns * 4, hipMemcpyDeviceToHost));
-    if (cp_idx) HIP_TRY(c, hipMemcpy(h_evbatch.data(), c->d_ev_batch, ns * 4, hipMemcpyDeviceToHost));
-    if (c->have_ev_pm) HIP_TRY(c, hipMemcpy(h_evpm.data(), c->d_ev_pm.as<uint32_t>(), ns * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(h_pmorig.data(), c->d_pm_orig.as<uint32_t>(), c->n_pm * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> h_evpix(ns), h_evbatch(cp_idx ? ns : 0), h_evpm(c->order.have_ev_pm ? ns : 0), h_pmorig(c->win.n_pm);
+    HIP_TRY(c, hipMemcpy(h_evpix.data(), c->order.d_ev_pix, ns * 4, hipMemcpyDeviceToHost));
+    if (cp_idx) HIP_TRY(c, hipMemcpy(h_evbatch.data(), c->order.d_ev_batch, ns * 4, hipMemcpyDeviceToHost));
+    if (c->order.have_ev_pm) HIP_TRY(c, hipMemcpy(h_evpm.data(), c->d_ev_pm.as<uint32_t>(), ns * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h_pmorig.data(), c->d_pm_orig.as<uint32_t>(), c->win.n_pm * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ns; ++i) {
         if (h_evpix[i] & kEvLead) continue;                        // lead-in copy / halo
-        const size_t f = c->have_ev_pm ? h_evpm[i] : i;           // pm-order index: where flag / inlier number of this entry live
+        const size_t f = c->order.have_ev_pm ? h_evpm[i] : i;           // pm-order index: where flag / inlier number of this entry live
         const uint32_t k = h_pmorig[f];
         if (k == 0xFFFFFFFFu) continue;
         const bool cand = (h_evpix[i] & kEvHasPred) != 0;
@@ -2247,7 +1958,7 @@ emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
         if (!strcmp(o.name, name)) {
             if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
             c->*(o.field) = (int)value;
-            if (!strcmp(name, "order") || !strcmp(name, "chunk_order_bin") || !strncmp(name, "tile_", 5)) c->keys_ready = false;      // the device order is rebuilt at the next evaluation
+            if (!strcmp(name, "order") || !strcmp(name, "chunk_order_bin") || !strncmp(name, "tile_", 5)) c->order.keys_ready = false;      // the device order is rebuilt at the next evaluation
             return EMBA_OK;
         }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
@@ -2453,7 +2164,7 @@ SolveLists cached_lists(const emba_ctx* c)
 // Hands the solve scratch (sv) and the lists cache to a solve.  A CG session (emba_cg_shard_*) holds them from begin to end: it ends here.
 emba_ctx::Solve& take_solve_scratch(emba_ctx* c)
 {
-    c->cg.active = false;
+    c->solve.cg.active = false;
     return c->sv;
 }
 
@@ -2478,8 +2189,8 @@ emba_status ensure_cg_vectors(emba_ctx* c, size_t n)
 // failure ends the session.
 emba_status cg_resume(emba_ctx* c)
 {
-    if (!c->cg.active) return fail(c, EMBA_ERR_STATE, "no CG session: call emba_cg_shard_begin (a solve on this context, or a failed emba_cg_shard_* call, ends one)");
-    c->cg.active = false;
+    if (!c->solve.cg.active) return fail(c, EMBA_ERR_STATE, "no CG session: call emba_cg_shard_begin (a solve on this context, or a failed emba_cg_shard_* call, ends one)");
+    c->solve.cg.active = false;
     return EMBA_OK;
 }
 
@@ -2489,14 +2200,13 @@ emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n
 {
     hipStream_t s = c->stream;
     emba_status st;
-    const uint32_t key_stamp = view.packed ? c->work.stamp : view.stamp;
-    if (c->lists_valid && c->lists_packed == (view.packed != 0) && c->lists_stamp == key_stamp && c->lists_P == n_pix && c->lists_nrec == n_rec &&
-        (!view.packed || c->lists_lo == view.pix_base)) {
+    const ListsKey key{view.packed != 0, view.packed ? c->work.stamp : view.stamp, n_pix, n_rec, view.packed ? (long)view.pix_base : 0L};
+    if (c->solve.lists_valid && c->solve.key == key) {
         *out = cached_lists(c);
         return EMBA_OK;
     }
     if (view.packed && !view.rec) return fail(c, EMBA_ERR_STATE, "the received records of these equations are not cached on this rank: run the record exchange (emba_solve_shard_cached says when it can be skipped)");
-    c->lists_valid = false; c->perm_valid = false;
+    c->solve.invalidate();
     if ((st = ensure<uint32_t>(c, c->lists.off, n_pix + 2)) || (st = ensure<uint32_t>(c, c->lists.cursor, n_pix + 1)) ||
         (st = ensure<double>(c, c->lists.sorted, (n_rec + 1) * kRecStride)))
         return st;
@@ -2530,7 +2240,7 @@ emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n
     if (n_rec) hipLaunchKernelGGL(emba_csr_fill_sorted_kernel, dim3(nblocks(n_rec, 32)), dim3(256), 0, s, view, (long)n_rec, d_off, d_cursor, d_sorted);
     HIP_TRY(c, hipGetLastError());
     *out = cached_lists(c);
-    c->lists_valid = true; c->lists_packed = view.packed != 0; c->lists_stamp = key_stamp; c->lists_P = n_pix; c->lists_nrec = n_rec; c->lists_lo = view.pix_base;
+    c->solve.lists_valid = true; c->solve.key = key;
     return EMBA_OK;
 }
 
@@ -2717,7 +2427,7 @@ emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo =
     // 10 M events over 10 s) 3.96 / 4.16 ms — SYRK 1.25 / 1.52, 5.8 / 7.9 products per slice —; 10 M events at K = 97: 2.81 / 2.79; 1 M events over 1 s at
     // K = 201 (every pixel sees the whole window: nothing to gain) 2.27 / 2.24.  From six row blocks (K >= 128) up, unless option solve_perm forces it.
     if (c->solve_perm_mode == 0 || P < 4 * (size_t)kSyrkSlicePix || (c->solve_perm_mode < 0 && 3 * c->eq.K < 384) || 3 * c->eq.K < 256) return EMBA_OK;
-    if (c->perm_valid && c->perm_lo == lo && c->perm_n == P) { *perm = c->sv.perm.as<uint32_t>(); return EMBA_OK; }
+    if (c->solve.perm_valid && c->solve.perm_lo == lo && c->solve.perm_n == P) { *perm = c->sv.perm.as<uint32_t>(); return EMBA_OK; }
     if (c->solve_perm_mode < 0) {
         double path_az = 0.0, path_el = 0.0;
         if (!axis_path(c, &path_az, &path_el)) return EMBA_OK;
@@ -2726,7 +2436,7 @@ emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo =
     hipStream_t s = c->stream;
     auto& sv = c->sv;
     emba_status st;
-    c->perm_valid = false;
+    c->solve.perm_valid = false;
     if ((st = ensure<uint32_t>(c, sv.perm_cnt, (size_t)c->W + 2)) || (st = ensure<uint32_t>(c, sv.perm_tick, P)) || (st = ensure<uint32_t>(c, sv.perm, P))) return st;
     uint32_t *d_cnt = sv.perm_cnt.as<uint32_t>(), *d_tick = sv.perm_tick.as<uint32_t>(), *d_pm = sv.perm.as<uint32_t>();
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, ((size_t)c->W + 1) * 4, s));
@@ -2734,7 +2444,7 @@ emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo =
     if ((st = dev_scan(c, d_cnt, d_cnt, (size_t)c->W, nullptr))) return st;
     hipLaunchKernelGGL(emba_perm_place_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active.as<uint32_t>() + lo, (long)P, c->W, d_cnt, d_tick, d_pm);
     HIP_TRY(c, hipGetLastError());
-    c->perm_valid = true; c->perm_lo = lo; c->perm_n = P;
+    c->solve.perm_valid = true; c->solve.perm_lo = lo; c->solve.perm_n = P;
     *perm = d_pm;
     return EMBA_OK;
 }
@@ -2768,7 +2478,7 @@ struct SchurDims {
 // the step is lost (NaN cost: rejected); reported as EMBA_ERR_NUMERIC.  bit 1: a pivot of S vanished — handled like Eigen's ldlt (zero update), not an error.
 emba_status solve_status(emba_ctx* c, int info)
 {
-    c->solve_info = info;
+    c->solve.info = info;
     if (info & 1) return fail(c, EMBA_ERR_NUMERIC, "a 2x2 block of A22 + lambda*diag(A22) is not positive definite (the reference's inverse() gives inf/nan)");
     if (info & 4) return fail(c, EMBA_ERR_NUMERIC, "the Schur complement is indefinite or not finite (a pivot clearly below zero, or NaN): no update is returned");
     return EMBA_OK;
@@ -2807,7 +2517,7 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
     const SchurDims d(c, fix_first_pose);
     const int n = d.n, skip = d.skip;
     const long lds_ = d.lds;
-    const size_t P = c->eq.P, M = c->n_cand;
+    const size_t P = c->eq.P, M = c->win.n_cand;
     if (n - skip <= 0) return fail(c, EMBA_ERR_INVALID_ARG, "nothing to solve for");
     auto& sv = take_solve_scratch(c);
     if ((st = ensure<double>(c, sv.S_or_x, d.size())) || (st = ensure<double>(c, sv.rhs_or_r, n)) || (st = ensure<double>(c, sv.y_or_z, 2 * (P + 1))) ||
@@ -2840,7 +2550,7 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
 extern "C" emba_status emba_last_solve_info(const emba_ctx* c, int32_t* info)
 {
     if (!c || !info) return EMBA_ERR_INVALID_ARG;
-    *info = c->solve_info;
+    *info = c->solve.info;
     return EMBA_OK;
 }
 
@@ -2864,7 +2574,7 @@ extern "C" emba_status emba_solve_shard_count(emba_ctx* c, int32_t n_ranks, size
     if ((st = ensure<unsigned long long>(c, sv.shard_cnt, (size_t)3 * n_ranks + 1))) return st;
     unsigned long long* d_cnt = sv.shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt, 0, (size_t)3 * n_ranks * 8 + 8, s));
-    if (c->n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->eq.P, (int)n_ranks, d_cnt);
+    if (c->win.n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->win.n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->win.n_cand, (long)c->eq.P, (int)n_ranks, d_cnt);
     std::vector<unsigned long long> h(n_ranks);
     HIP_TRY(c, hipMemcpyAsync(h.data(), d_cnt, (size_t)n_ranks * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -2884,8 +2594,8 @@ extern "C" emba_status emba_solve_shard_pack(emba_ctx* c, int32_t n_ranks, doubl
     hipStream_t s = c->stream;
     unsigned long long* d_cnt = take_solve_scratch(c).shard_cnt.as<unsigned long long>();
     HIP_TRY(c, hipMemsetAsync(d_cnt + 2 * n_ranks, 0, (size_t)n_ranks * 8, s));
-    if (c->n_cand && send_dev)
-        hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->n_cand, (long)c->eq.P, (int)n_ranks, d_cnt + n_ranks,
+    if (c->win.n_cand && send_dev)
+        hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->win.n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->win.n_cand, (long)c->eq.P, (int)n_ranks, d_cnt + n_ranks,
                            d_cnt + 2 * n_ranks, send_dev);
     HIP_TRY(c, hipGetLastError());
     return EMBA_OK;
@@ -2902,9 +2612,9 @@ extern "C" emba_status emba_solve_shard_cached(emba_ctx* c, int32_t rank, int32_
     if (!c || !cached || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_cached: bad arguments") : EMBA_ERR_INVALID_ARG;
     size_t lo, hi;
     shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
-    *cached = (c->eq.finish_done && !c->eq_in_alt && c->lists_valid && c->lists_packed && c->lists_stamp == c->work.stamp && c->lists_P == hi - lo && c->lists_lo == (long)lo &&
-               c->sv.y_or_z.p) ? 1 : 0;
-    if (n_recv) *n_recv = *cached ? c->lists_nrec : 0;
+    const ListsKey key{true, c->work.stamp, hi - lo, c->solve.key.nrec, (long)lo};   // (how many records it received is what the cache tells the caller)
+    *cached = (c->eq.finish_done && !c->eq_in_alt && c->solve.lists_valid && c->solve.key == key && c->sv.y_or_z.p) ? 1 : 0;
+    if (n_recv) *n_recv = *cached ? c->solve.key.nrec : 0;
     return EMBA_OK;
 }
 
@@ -2975,7 +2685,7 @@ extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32
     if ((st = resolve_pending(c))) return st;
     hipStream_t s = c->stream;
     const int n = 3 * c->eq.K, skip = fix_first_pose ? 3 : 0;
-    const size_t P = c->eq.P, M = c->n_cand, N = (size_t)n + 2 * P;
+    const size_t P = c->eq.P, M = c->win.n_cand, N = (size_t)n + 2 * P;
     if (max_iter <= 0) max_iter = 100;     // model.cpp:823-824
     if (!(tol > 0)) tol = 1e-6;
     if ((st = ensure_cg_vectors(c, N))) return st;
@@ -3070,7 +2780,7 @@ extern "C" emba_status emba_cg_shard_begin(emba_ctx* c, int32_t rank, int32_t n_
     if (st) return st;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     g.rank = rank; g.n_ranks = n_ranks; g.n = 3 * c->eq.K; g.skip = fix_first_pose ? 3 : 0; g.lambda = lambda;
     size_t lo, hi;
     shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
@@ -3092,7 +2802,7 @@ extern "C" emba_status emba_cg_shard_begin(emba_ctx* c, int32_t rank, int32_t n_
 extern "C" emba_status emba_cg_shard_apply(emba_ctx* c, double* red_dev)
 {
     if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     if (emba_status st = cg_resume(c)) return st;
     const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3112,7 +2822,7 @@ extern "C" emba_status emba_cg_shard_apply(emba_ctx* c, double* red_dev)
 extern "C" emba_status emba_cg_shard_pt(emba_ctx* c, const double* red_dev, double* pt)
 {
     if (!c || !red_dev || !pt) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     if (emba_status st = cg_resume(c)) return st;
     const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3133,7 +2843,7 @@ extern "C" emba_status emba_cg_shard_pt(emba_ctx* c, const double* red_dev, doub
 extern "C" emba_status emba_cg_shard_update(emba_ctx* c, double alpha, double* red_dev)
 {
     if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     if (emba_status st = cg_resume(c)) return st;
     const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3151,7 +2861,7 @@ extern "C" emba_status emba_cg_shard_update(emba_ctx* c, double alpha, double* r
 extern "C" emba_status emba_cg_shard_direction(emba_ctx* c, double beta)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     if (emba_status st = cg_resume(c)) return st;
     const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3164,7 +2874,7 @@ extern "C" emba_status emba_cg_shard_direction(emba_ctx* c, double beta)
 extern "C" emba_status emba_cg_shard_end(emba_ctx* c, double* x1_host, double* x2_full_dev)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->cg;
+    auto& g = c->solve.cg;
     if (emba_status st = cg_resume(c)) return st;
     const CgVecs v = cg_vectors(c);
     HIP_TRY(c, hipSetDevice(c->device));

@@ -22,6 +22,8 @@
 #include <set>
 #include <thread>
 
+#include "context.h"
+
 namespace emba {
 
 __global__ void emba_add_f64_kernel(double* __restrict__ dst, const double* __restrict__ src, long n)

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "device_math.h"
+#include "order_rule.h"   // ChunkDesc, TileShape
 
 // Development ablations (EMBA_ABLATE bit mask: parts of a kernel switched off to see what they cost; results are WRONG when non-zero)
 // exist only in a diagnostics build (-DEMBA_DIAG, scripts/ablate*.sh build one under build_variants/): the shipped library has none of
@@ -261,12 +262,9 @@ __global__ __launch_bounds__(256) void emba_texel_kernel(const double* __restric
 //   emba_warp_tiled_kernel     tile order (order_kernels.h): a workgroup owns one panorama tile's worth of events and keeps the
 //                              per-pixel sums of the tile (+ margin) in LDS; one atomic request per touched pixel at the end
 // ------------------------------------------------------------------------------------------------
-struct ChunkDesc { uint32_t begin, end; int32_t x0, y0; };   // entries [begin, end) of the device order; LDS tile origin (panorama px)
-
 // LDS accumulator tile of the tiled kernel: 1152 panorama pixels x 6 doubles = 54 KB, two workgroups per CU.  Round 6: four shapes of that budget, one kernel
 // instantiation each; a window takes the shape that cuts its chains into the fewest segments (order_kernels.h: the window rule; emba_hip.hip: prepare_order).
 // {tile w, h, pitch of the tile-origin grid, its finer variant for very dense windows}
-struct TileShape { int tw, th, pw, ph, fine_pw, fine_ph; };
 constexpr int kNumTileShapes = 4;
 constexpr TileShape kTileShapes[kNumTileShapes] = {
     {48, 24, 32, 8, 16, 4},      // the shape of rounds 2-5 (then: a 32 x 8 bin + 8 px of margin)

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "device_math.h"
+#include "order_rule.h"   // BinGeom
 
 namespace emba {
 
@@ -234,7 +235,6 @@ __global__ void emba_batch_cp_kernel(const int64_t* __restrict__ batch_t, long n
 // and it may grow while xmax - floor(xmin / px) px < tw - 2 r (same in y).  Greedy longest segments are optimal for a sequence (feasibility is hereditary).
 // scripts/lead_in_sim.py: lead-in copies 31.5 -> 12.8 % at 2 M events, 23.1 -> 9.1 % at 3 M, 40.5 -> 17.3 % on the city shape, 16.1 -> 4.6 % on config 4's shard.
 // Speed only, as before: whatever the trial poses move out of a tile goes to HBM directly (and is counted: emba_last_tile_drift).
-struct BinGeom { int W, H, bw, bh, nbx, nby, tw, th, r; };   // pitch grid of tile origins: bw x bh panorama pixels, nbx x nby of them; LDS tile tw x th; reserve r
 
 constexpr uint32_t kNoPixel = 0xFFFFFFFFu;
 

@@ -82,6 +82,18 @@ def test_cpp_sharded_host_matches_oracle(tmp_path, hip_lib, oracle_mod, devices,
     assert f"world={len(devices.split(','))} rccl={int(force_rccl)}" in last
 
 
+def test_order_rule_on_the_cpu(tmp_path):
+    """emba_amd/csrc/order_rule.h (plain C++17, no HIP): tests/cpp/order_rule_test.cpp cuts a few hundred start tables into chunks — every occupied tile
+    covered exactly once, no empty piece, whole rounds except a tile's last piece, origins, longest-first order stable — and checks the order rule on
+    hand-computed cases."""
+    import option_matrix as OM
+    exe = str(tmp_path / "order_rule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-DTILE_ROUND=%d" % OM.tile_round(), os.path.join(ROOT, "tests", "cpp", "order_rule_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "OK order_rule", r.stdout + r.stderr
+
+
 ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "adapter_test")
 
 
