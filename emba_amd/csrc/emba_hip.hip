@@ -1,4 +1,5 @@
-// emba_amd/csrc/emba_hip.hip — context, HBM residency and the C ABI of include/emba_hip.h.
+// emba_amd/csrc/emba_hip.hip — context, HBM residency and the C ABI of include/emba_hip.h: the window and its order, the evaluation, the normal equations,
+// f3 and the downloads.  The context itself is context.h, the solvers (f1) are solve_host.h, the multi-GPU group is group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
 // (emba_set_events: pose-independent structure), launches kernels and moves bytes.
@@ -2138,755 +2139,7 @@ emba_status emba_device_pci_bus_id(emba_ctx* c, char* buf, size_t len)
 
 }  // extern "C"
 
-// ---- f1: the solvers (solve_kernels.h) ------------------------------------------------------------------------------------------
-namespace {
-
-
-// A kernel that keeps the 3K-vector x1 (or the pose part of a CG vector) in dynamic LDS: above 64 KB (K > 2730) the launch needs the attribute raised, above the
-// CU's 160 KB there is no such launch — say so instead of a generic launch failure
-emba_status pose_vector_lds(emba_ctx* c, const void* kernel, size_t bytes, const char* what, size_t per_pose = 24)
-{
-    if (bytes > (size_t)160 * 1024)
-        return fail(c, EMBA_ERR_CAPACITY, "%s: K = %zu control poses need %zu bytes of LDS for the pose vector (limit 160 KB: K <= %zu)", what, bytes / per_pose, bytes, (size_t)160 * 1024 / per_pose);
-    if (bytes > (size_t)64 * 1024) HIP_TRY(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return EMBA_OK;
-}
-
-// The cached lists (lists.off, lists.sorted) as a SolveLists.
-SolveLists cached_lists(const emba_ctx* c)
-{
-    SolveLists L;
-    L.off = c->lists.off.as<uint32_t>();
-    L.sorted.rec = c->lists.sorted.as<const double>(); L.sorted.packed = 1; L.sorted.pix_base = 0;
-    return L;
-}
-
-// Hands the solve scratch (sv) and the lists cache to a solve.  A CG session (emba_cg_shard_*) holds them from begin to end: it ends here.
-emba_ctx::Solve& take_solve_scratch(emba_ctx* c)
-{
-    c->solve.cg.active = false;
-    return c->sv;
-}
-
-// The CG vectors in the solve scratch: x, r, p, z, t, the inverse diagonal (n doubles each) and the device scalars
-struct CgVecs { double *x, *r, *p, *z, *t, *invd, *sc; };
-CgVecs cg_vectors(const emba_ctx* c)
-{
-    const auto& v = c->sv;
-    return {v.S_or_x.as<double>(), v.rhs_or_r.as<double>(), v.U_or_p.as<double>(), v.y_or_z.as<double>(), v.cf_or_t.as<double>(), v.x2_or_invd.as<double>(),
-            v.info_or_sc.as<double>()};
-}
-emba_status ensure_cg_vectors(emba_ctx* c, size_t n)
-{
-    auto& v = take_solve_scratch(c);
-    emba_status st;
-    for (DevBuf* b : {&v.S_or_x, &v.rhs_or_r, &v.U_or_p, &v.y_or_z, &v.cf_or_t, &v.x2_or_invd})
-        if ((st = ensure<double>(c, *b, n))) return st;
-    return ensure<double>(c, v.info_or_sc, 8);
-}
-
-// An emba_cg_shard_* call after begin: the session must still hold the solve scratch.  The call releases it and takes it back when it succeeds, so that a
-// failure ends the session.
-emba_status cg_resume(emba_ctx* c)
-{
-    if (!c->solve.cg.active) return fail(c, EMBA_ERR_STATE, "no CG session: call emba_cg_shard_begin (a solve on this context, or a failed emba_cg_shard_* call, ends one)");
-    c->solve.cg.active = false;
-    return EMBA_OK;
-}
-
-// per-pixel record lists over `n_pix` pixels of `view` (n_rec records): counts from the records themselves, exclusive scan, fill.
-// Into the lists cache: off, cursor, sorted (the records in pixel order).
-emba_status build_lists(emba_ctx* c, const RecView& view, size_t n_rec, size_t n_pix, SolveLists* out)
-{
-    hipStream_t s = c->stream;
-    emba_status st;
-    const ListsKey key{view.packed != 0, view.packed ? c->work.stamp : view.stamp, n_pix, n_rec, view.packed ? (long)view.pix_base : 0L};
-    if (c->solve.lists_valid && c->solve.key == key) {
-        *out = cached_lists(c);
-        return EMBA_OK;
-    }
-    if (view.packed && !view.rec) return fail(c, EMBA_ERR_STATE, "the received records of these equations are not cached on this rank: run the record exchange (emba_solve_shard_cached says when it can be skipped)");
-    c->solve.invalidate();
-    if ((st = ensure<uint32_t>(c, c->lists.off, n_pix + 2)) || (st = ensure<uint32_t>(c, c->lists.cursor, n_pix + 1)) ||
-        (st = ensure<double>(c, c->lists.sorted, (n_rec + 1) * kRecStride)))
-        return st;
-    uint32_t *d_off = c->lists.off.as<uint32_t>(), *d_cursor = c->lists.cursor.as<uint32_t>();
-    double* d_sorted = c->lists.sorted.as<double>();
-    // list lengths: from the context's own count map while it still belongs to the evaluation that wrote these records (count_stamp), else counted
-    // from the records (all-reduced / saturated / externally bound counts, a trial evaluation since, the sharded solve's received records)
-    const int cmap_env = c->opt_solve_counts;      // option solve_counts — 0: always from the records; 2: both, compared (diagnostic)
-    const bool from_map = cmap_env != 0 && !view.packed && c->ev.count_stamp != 0 && c->ev.count_stamp == view.stamp && c->d_count == c->d_count_own.as<int32_t>() && n_pix == c->eq.P && n_pix;
-    if (from_map && cmap_env != 2) {
-        hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_count, (long)n_pix, d_cursor);
-    } else {
-        HIP_TRY(c, hipMemsetAsync(d_cursor, 0, (n_pix + 1) * 4, s));
-        if (n_rec) hipLaunchKernelGGL(emba_csr_count_kernel, dim3(nblocks(n_rec)), dim3(256), 0, s, view, (long)n_rec, d_cursor);
-        if (from_map) {      // diagnostic: the two must agree
-            std::vector<uint32_t> a(n_pix), b(n_pix);
-            if ((st = ensure<uint32_t>(c, c->lists.tmp, n_pix))) return st;
-            uint32_t* d_tmp = c->lists.tmp.as<uint32_t>();
-            hipLaunchKernelGGL(emba_csr_count_from_map_kernel, dim3(nblocks(n_pix)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_count, (long)n_pix, d_tmp);
-            HIP_TRY(c, hipMemcpyAsync(a.data(), d_cursor, n_pix * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(b.data(), d_tmp, n_pix * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            size_t bad = 0; for (size_t i = 0; i < n_pix; ++i) bad += a[i] != b[i];
-            fprintf(stderr, "[solve counts] P %zu: %zu pixels where the count map and the records disagree\n", n_pix, bad);
-            if (bad) return fail(c, EMBA_ERR_STATE, "count map and record counts disagree on %zu pixels", bad);
-        }
-    }
-    if ((st = dev_scan(c, d_cursor, d_off, n_pix, d_off + n_pix))) return st;
-    HIP_TRY(c, hipMemsetAsync(d_cursor, 0, (n_pix + 1) * 4, s));
-    // the participating records, copied into pixel order (the passes over them — U build, x2, every CG iteration — then stream)
-    if (n_rec) hipLaunchKernelGGL(emba_csr_fill_sorted_kernel, dim3(nblocks(n_rec, 32)), dim3(256), 0, s, view, (long)n_rec, d_off, d_cursor, d_sorted);
-    HIP_TRY(c, hipGetLastError());
-    *out = cached_lists(c);
-    c->solve.lists_valid = true; c->solve.key = key;
-    return EMBA_OK;
-}
-
-// S_aug (lds x (n+1), zero or pre-initialised) -= U_aug U_aug^T over the pixels [0, n_pix) of the lists; A22b2 points at the first of
-// those pixels' {xx xy yy bx by}.  Also leaves y = C^-1 b2 (d_y) and the 2x2 Cholesky factors (d_cf).  Scratch: sv.U_or_p (U), sv.slab, the SYRK lists.
-bool axis_path(const emba_ctx* c, double* path_az_out, double* path_el_out);
-
-emba_status schur_accumulate(emba_ctx* c, const RecView& view, const SolveLists& L, size_t n_pix, const double* A22b2, double lambda, int n,
-                             double* d_S, long lds_, double* d_y, double* d_cf, int* d_info, const uint32_t* perm = nullptr)
-{
-    hipStream_t s = c->stream;
-    // (the SYRK covers the n rows of S; row n of the augmented matrix, the right-hand side b1 - U y, is accumulated by the build kernel itself)
-    // (round 6, measured and dropped: chunk i + 1's U build on this stream beside chunk i's product on a second one — every chunk count was slower than one after
-    // the other, 3.87 -> 4.2 / 4.6 / 5.3 ms for 2 / 4 / 8 chunks at config 2's shape: profiles/r06_schur_pipe_ab.txt)
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::max<size_t>(n_pix, 1), (size_t)(6ull << 30) / (16ull * (size_t)lds_)));   // <= 6 GB of U
-    const int nb64 = (n + 63) / 64, nbp = nb64 * (nb64 + 1) / 2;
-    const int nks_max = std::max(1, (4 * c->n_cu + nbp - 1) / nbp);   // enough (tile pair, K slab) blocks to fill the chip ...
-    auto& sv = c->sv;
-    emba_status st;
-    if ((st = ensure<double>(c, sv.U_or_p, (size_t)lds_ * 2 * chunk)) || (st = ensure<double>(c, sv.slab, (size_t)nks_max * nbp * 4096))) return st;
-    double* d_U = sv.U_or_p.as<double>();
-    SchurBuildParams bp{};
-    bp.view = view; bp.off = L.off; bp.A22b2 = A22b2; bp.lambda = lambda;
-    bp.irls = c->eq.irls; bp.eta = c->eq.eta; bp.n = n; bp.U = d_U; bp.ldu = lds_; bp.yv = d_y; bp.cfac = d_cf; bp.info = d_info;
-    bp.rhs_row = d_S + n; bp.lds = lds_; bp.perm = perm;
-    const size_t lds_bytes = (size_t)(2 * kBuildWaves + 1) * n * sizeof(double);
-    if (lds_bytes > 160 * 1024) return fail(c, EMBA_ERR_CAPACITY, "K=%d too large for the per-wave column staging in LDS", n / 3);
-    if (lds_bytes > 64 * 1024) HIP_TRY(c, hipFuncSetAttribute((const void*)emba_schur_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    // Block-sparse SYRK (>= 4 row blocks, i.e. K >= 64): the columns of a slice of kSyrkSlicePix consecutive active pixels — a piece of a
-    // panorama row — are non-zero only in the rows of the control poses in view while the camera looked there; over a long window
-    // (config 2: 10 s, K = 201) that is a band, and only the (row-block pair, slice) products with both blocks populated are formed.
-    // Option syrk_dense switches it off (comparison).
-    const bool sparse = nb64 >= 4 && nb64 <= 64 && !c->opt_syrk_dense;
-    for (size_t p0 = 0; p0 < n_pix; p0 += chunk) {
-        const size_t p1 = std::min(n_pix, p0 + chunk);
-        bp.p0 = (long)p0; bp.p1 = (long)p1;
-        const long kc = (long)(2 * (p1 - p0));
-        const int n_slices = (int)((p1 - p0 + kSyrkSlicePix - 1) / kSyrkSlicePix);
-        if ((st = ensure<uint16_t>(c, sv.range, p1 - p0 + 8))) return st;
-        uint16_t* d_range = sv.range.as<uint16_t>();
-        bp.range = d_range;
-        unsigned long long* d_mask = nullptr; uint32_t *d_list = nullptr, *d_cnt = nullptr;
-        if (sparse) {
-            if ((st = ensure<unsigned long long>(c, sv.mask, n_slices)) || (st = ensure<uint32_t>(c, sv.list, (size_t)nbp * n_slices)) || (st = ensure<uint32_t>(c, sv.cnt, nbp)))
-                return st;
-            d_mask = sv.mask.as<unsigned long long>(); d_list = sv.list.as<uint32_t>(); d_cnt = sv.cnt.as<uint32_t>();
-            HIP_TRY(c, hipMemsetAsync(d_mask, 0, (size_t)n_slices * 8, s));
-        }
-        bp.slice_mask = d_mask;
-        hipLaunchKernelGGL(emba_schur_build_kernel, dim3((unsigned)std::min<size_t>((p1 - p0 + kBuildWaves - 1) / kBuildWaves, 4096)), dim3(64 * kBuildWaves), lds_bytes, s, bp);
-        int nks = (int)std::max<long>(1, std::min<long>(nks_max, kc / c->opt_syrk_min_cols));   // ... but >= 512 columns each (option syrk_min_cols): a block pays a fixed LDS combine + 32-KB slab write
-        // ... and whole rounds of one block per CU: 268 blocks of 512 columns on 256 CUs (K = 21, 137 k columns) took 57 us, 255 blocks of 536 columns 44 us
-        if ((long)nbp * nks > c->n_cu) nks = (int)std::max<long>(1, ((long)nbp * nks / c->n_cu) * c->n_cu / nbp);
-        SyrkParams sp{};
-        sp.A = d_U; sp.lda = lds_; sp.n = n; sp.k = kc; sp.C = d_S; sp.ldc = lds_; sp.slab = sv.slab.as<double>(); sp.nbp = nbp; sp.range = d_range;
-        // Where it pays: a BANDED U — a pixel is in view for the fraction fov / (path of the optical axis over the window) of the control poses, and an operand block
-        // is read once per pair of its band.  With a dense band (every pixel sees the whole window: 1 s at any K) there is nothing to re-use that the lists form does
-        // not get from its longer runs (measured: 10 M events / K = 97 over 1 s 3.14 vs 3.38 ms per solve, 1 M / K = 201 over 1 s 2.5 vs 2.75; config 2's shape, 10 s:
-        // 4.15 vs 3.93).  Option syrk_lists: 0 auto, 1 the lists form always, 2 the item form always.
-        double paz = 0.0, pel = 0.0, in_view = 1.0;
-        if (axis_path(c, &paz, &pel)) in_view = std::min(1.0, (paz >= pel ? c->fov_x : c->fov_y) / std::max(std::max(paz, pel), 1e-9));
-        const int band_blocks = std::min(nb64, (int)std::ceil(in_view * nb64) + 1);
-        const bool items_form = sparse && (c->opt_syrk_lists == 2 || (c->opt_syrk_lists == 0 && 2 * band_blocks <= nb64));
-        if (sparse) {
-            if (!items_form || c->opt_solve_debug) hipLaunchKernelGGL(emba_syrk_lists_kernel, dim3((unsigned)nbp), dim3(64), 0, s, d_mask, n_slices, nbp, d_list, d_cnt);
-            sp.list = d_list; sp.count = d_cnt; sp.n_slices = n_slices;
-            nks = std::max(1, std::min(nks_max, n_slices));
-        }
-        // ITEM form of the block-sparse product (round 5, SyrkParams::items): workgroups = (block pair, chunk of slices) in chunk-major order.  Option syrk_lists = 1
-        // keeps the round-3/4 form (a workgroup per (pair, part) walking every nks-th slice of the pair's list).
-        int item_chunk = 0, n_item_chunks = 0;
-        uint32_t* d_pair_items = nullptr; uint32_t* d_items = nullptr;
-        const uint32_t item_cap = (uint32_t)c->opt_syrk_item_cap;      // slabs of the item form: items beyond them add to S by global atomics (option syrk_item_cap: 4096; tests force the overflow branch with 8)
-        if (items_form) {
-            const long pairs_est = (long)band_blocks * (band_blocks + 1) / 2;
-            item_chunk = (int)std::min<long>(64, std::max<long>(4, ((long)n_slices * pairs_est * 3 / 2 + 2999) / 3000));
-            n_item_chunks = (n_slices + item_chunk - 1) / item_chunk;
-            if (n_item_chunks > 65535 || nbp > 65535) return fail(c, EMBA_ERR_CAPACITY, "too many slice chunks for the item form of the block-sparse product");
-            if ((st = ensure<double>(c, sv.slab, std::max<size_t>((size_t)nks_max * nbp, item_cap) * 4096)) ||
-                (st = ensure<uint32_t>(c, sv.pair_items, (size_t)nbp * n_item_chunks)) || (st = ensure<uint32_t>(c, sv.items, (size_t)nbp * n_item_chunks + 2)))
-                return st;
-            d_pair_items = sv.pair_items.as<uint32_t>(); d_items = sv.items.as<uint32_t>();
-            sp.slab = sv.slab.as<double>();
-        }
-        sp.direct = (nks == 1);
-        if (c->opt_solve_debug) {      // diagnostic: how sparse is this chunk?  (products = (block pair, slice) pairs the SYRK forms)
-            (void)hipStreamSynchronize(s);
-            std::vector<uint16_t> hr(p1 - p0); (void)hipMemcpy(hr.data(), d_range, (p1 - p0) * 2, hipMemcpyDeviceToHost);
-            long w16 = 0, w64 = 0, hist[9] = {0};
-            for (uint16_t r : hr) { const int lo = r & 255, hi = r >> 8; if (lo > hi) continue; w16 += hi - lo + 1; const int b = (hi >> 2) - (lo >> 2) + 1; w64 += b; hist[b < 8 ? b : 8]++; }
-            long prod = 0, prod_diag = 0;
-            if (sparse) { std::vector<uint32_t> hc(nbp); (void)hipMemcpy(hc.data(), d_cnt, nbp * 4, hipMemcpyDeviceToHost); for (int b = 0; b < nbp; ++b) { prod += hc[b]; int I, J; I = (int)((sqrt(8.0 * b + 1.0) - 1.0) * 0.5); while ((long)I * (I + 1) / 2 > b) --I; while ((long)(I + 1) * (I + 2) / 2 <= b) ++I; J = b - I * (I + 1) / 2; if (I == J) prod_diag += hc[b]; } }
-            for (int R : {1, 2, 4, 8, 16}) {      // union band (16-row groups) of runs of R slices: what a band-resident product would have to hold
-                const size_t per = (size_t)R * kSyrkSlicePix; long ng = 0, fit12 = 0, fit16 = 0, wsum = 0; long fit16_pix = 0;
-                for (size_t g0 = 0; g0 < hr.size(); g0 += per) {
-                    int lo = 999, hi = -1;
-                    for (size_t i = g0; i < std::min(hr.size(), g0 + per); ++i) { const int l = hr[i] & 255, h = hr[i] >> 8; if (l > h) continue; lo = std::min(lo, l); hi = std::max(hi, h); }
-                    if (hi < 0) continue;
-                    ++ng; const int w = hi - lo + 1; wsum += w; if (w <= 12) ++fit12; if (w <= 16) { ++fit16; fit16_pix += (long)std::min(hr.size(), g0 + per) - (long)g0; }
-                }
-                fprintf(stderr, "[solve debug] runs of %2d slices: %ld runs, mean union band %.1f groups, <= 12 groups: %.1f %%, <= 16 groups: %.1f %% (%.1f %% of the pixels)\n", R, ng,
-                        (double)wsum / std::max(1L, ng), 100.0 * fit12 / std::max(1L, ng), 100.0 * fit16 / std::max(1L, ng), 100.0 * fit16_pix / std::max<size_t>(1, hr.size()));
-            }
-            fprintf(stderr, "[solve debug] pixels %ld slices %d nbp %d nks %d: mean 16-row groups per pixel %.2f, mean 64-row blocks written %.2f (hist 1..8+: %ld %ld %ld %ld %ld %ld %ld %ld), products %ld (diag %ld) = %.2f per slice; U written %.1f MB\n",
-                    (long)(p1 - p0), n_slices, nbp, nks, (double)w16 / (p1 - p0), (double)w64 / (p1 - p0), hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8], prod, prod_diag,
-                    (double)prod / n_slices, w64 * 64.0 * 2 * 8 / 1e6);
-        }
-        if (items_form) {
-            int32_t* d_ord = reinterpret_cast<int32_t*>(d_list);                  // (nbp * n_slices words >= nbp * n_item_chunks)
-            uint32_t* d_n_items = d_items + (size_t)nbp * n_item_chunks;
-            hipLaunchKernelGGL(emba_syrk_item_flag_kernel, dim3((unsigned)n_item_chunks), dim3(256), 0, s, d_mask, n_slices, nbp, item_chunk, d_ord);
-            hipLaunchKernelGGL(emba_syrk_item_ord_kernel, dim3((unsigned)((nbp + 63) / 64)), dim3(64), 0, s, nbp, n_item_chunks, d_ord, d_cnt);
-            hipLaunchKernelGGL(emba_syrk_item_list_kernel, dim3(1), dim3(1024), 0, s, d_ord, nbp, n_item_chunks, d_items, d_pair_items, d_n_items);
-            sp.list = nullptr; sp.count = nullptr; sp.n_slices = n_slices; sp.direct = 0;
-            sp.items = d_items; sp.n_items = d_n_items; sp.slice_mask = d_mask; sp.item_chunk = item_chunk; sp.item_cap = item_cap;
-            hipLaunchKernelGGL(emba_syrk_kernel, dim3((unsigned)((size_t)nbp * n_item_chunks)), dim3(256), 0, s, sp);
-            hipLaunchKernelGGL(emba_syrk_item_reduce_kernel, dim3((unsigned)(((size_t)nbp * 4096 + 255) / 256)), dim3(256), 0, s, sp.slab, d_pair_items, d_cnt, n_item_chunks, item_cap,
-                               nbp, n, d_S, lds_);
-            continue;
-        }
-        hipLaunchKernelGGL(emba_syrk_kernel, dim3(nbp, nks), dim3(256), 0, s, sp);
-        if (nks > 1)
-            hipLaunchKernelGGL(emba_syrk_reduce_kernel, dim3((unsigned)(((size_t)nbp * 4096 + 255) / 256), (unsigned)((nks + kSyrkReduceGroup - 1) / kSyrkReduceGroup)),
-                               dim3(256), 0, s, sp.slab, nks, nbp, n, d_S, lds_);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-// blocked Cholesky of S[skip:n, skip:n] and the two triangular solves: d_rhs <- x1 (zeros in front of skip).  The reference calls
-// Eigen's ldlt (model.cpp:789).
-emba_status schur_factor_solve(emba_ctx* c, double* d_S, long lds_, int n, int skip, double* d_rhs, int* d_info)
-{
-    // The right-hand side sits in S as row n (schur kernels: the augmented block).  The panel loop carries it along as one more row below
-    // the matrix — its triangular solve and trailing updates ARE the forward substitution — so only L^T x = z is left for the solve kernel.
-    hipStream_t s = c->stream;
-    const int m = n - skip;
-    double* Sm = d_S + (size_t)lds_ * skip + skip;
-    if (m + 1 <= 64 && skip <= 64) {                         // K <= 21: factor + both substitutions in one launch
-        hipLaunchKernelGGL(emba_chol_small_kernel, dim3(1), dim3(256), 0, s, Sm, lds_, m, skip, d_rhs, d_info);
-        HIP_TRY(c, hipGetLastError());
-        return EMBA_OK;
-    }
-    // per panel: [diagonal factor — a launch of its own for the first panel only] / panel solve / trailing update + the next panel's diagonal factor
-    hipLaunchKernelGGL(emba_chol_diag_kernel, dim3(1), dim3(256), 0, s, Sm, lds_, 0, std::min(64, m), d_info);
-    for (int jb = 0; jb < m; jb += 64) {
-        const int nb = std::min(64, m - jb);
-        const int below = m - jb - nb;                      // matrix rows under the panel; the rhs row (index m) comes on top of them
-        hipLaunchKernelGGL(emba_chol_trsm_kernel, dim3((below + 1 + 4 * kTrsmRows - 1) / (4 * kTrsmRows)), dim3(256), 0, s, Sm, lds_, m + 1, jb, nb);
-        if (below > 0) {
-            const int tb = (below + 1 + 63) / 64;
-            hipLaunchKernelGGL(emba_chol_trail_kernel, dim3(tb * (tb + 1) / 2), dim3(256), 0, s, Sm, lds_, jb, nb, below + 1, std::min(64, below), d_info);
-        }
-    }
-    hipLaunchKernelGGL(emba_schur_rhs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_S, lds_, n, skip, d_rhs);   // z = row n of the factor
-    hipLaunchKernelGGL(emba_chol_trsv_kernel, dim3(1), dim3(kTrsvThreads), 0, s, Sm, lds_, m, d_rhs + skip);
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-// The column order of U for the local solve (emba_perm_keys_kernel): panorama columns first when the camera mostly pans (azimuth path of the optical axis
-// over the control poses >= its elevation path), the compact order (nullptr) otherwise.  Built once per list build; scratch sv.perm_cnt, perm_tick, perm.
-// azimuth / elevation path length (rad) of the optical axis over the control poses of the last evaluation (the host's pinned copy)
-bool axis_path(const emba_ctx* c, double* path_az_out, double* path_el_out)
-{
-    if (!c->h_knots || c->eq.K < 2) return false;
-    double path_az = 0.0, path_el = 0.0, az0 = 0.0, el0 = 0.0;
-    for (int i = 0; i < c->eq.K; ++i) {
-        const double x = c->h_knots[4 * i], y = c->h_knots[4 * i + 1], z = c->h_knots[4 * i + 2], w = c->h_knots[4 * i + 3];
-        const double ax = 2.0 * (x * z + w * y), ay = 2.0 * (y * z - w * x), az_ = 1.0 - 2.0 * (x * x + y * y);      // R (0, 0, 1)
-        const double az = atan2(ax, az_), el = asin(std::max(-1.0, std::min(1.0, ay)));
-        if (i) { double d = az - az0; while (d > M_PI) d -= 2.0 * M_PI; while (d < -M_PI) d += 2.0 * M_PI; path_az += fabs(d); path_el += fabs(el - el0); }
-        az0 = az; el0 = el;
-    }
-    *path_az_out = path_az; *path_el_out = path_el;
-    return true;
-}
-
-emba_status solve_perm(emba_ctx* c, size_t P, const uint32_t** perm, size_t lo = 0)
-{   // the pixels [lo, lo + P) of the active set (round 6: a rank's owned range in the sharded solve too — without the order its half of the product took 1.45 ms where
-    // the whole single-rank product takes 0.96); perm[j] is relative to lo
-    *perm = nullptr;
-    // Measured (device time of one solve, with / without; the U build reads its pixels' records out of sequence and pays 5 % for it): config 2's shape (K = 201,
-    // 10 M events over 10 s) 3.96 / 4.16 ms — SYRK 1.25 / 1.52, 5.8 / 7.9 products per slice —; 10 M events at K = 97: 2.81 / 2.79; 1 M events over 1 s at
-    // K = 201 (every pixel sees the whole window: nothing to gain) 2.27 / 2.24.  From six row blocks (K >= 128) up, unless option solve_perm forces it.
-    if (c->solve_perm_mode == 0 || P < 4 * (size_t)kSyrkSlicePix || (c->solve_perm_mode < 0 && 3 * c->eq.K < 384) || 3 * c->eq.K < 256) return EMBA_OK;
-    if (c->solve.perm_valid && c->solve.perm_lo == lo && c->solve.perm_n == P) { *perm = c->sv.perm.as<uint32_t>(); return EMBA_OK; }
-    if (c->solve_perm_mode < 0) {
-        double path_az = 0.0, path_el = 0.0;
-        if (!axis_path(c, &path_az, &path_el)) return EMBA_OK;
-        if (path_az < path_el) return EMBA_OK;      // mostly tilting: a panorama row is the better slice already
-    }
-    hipStream_t s = c->stream;
-    auto& sv = c->sv;
-    emba_status st;
-    c->solve.perm_valid = false;
-    if ((st = ensure<uint32_t>(c, sv.perm_cnt, (size_t)c->W + 2)) || (st = ensure<uint32_t>(c, sv.perm_tick, P)) || (st = ensure<uint32_t>(c, sv.perm, P))) return st;
-    uint32_t *d_cnt = sv.perm_cnt.as<uint32_t>(), *d_tick = sv.perm_tick.as<uint32_t>(), *d_pm = sv.perm.as<uint32_t>();
-    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, ((size_t)c->W + 1) * 4, s));
-    hipLaunchKernelGGL(emba_perm_ticket_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active.as<uint32_t>() + lo, (long)P, c->W, d_cnt, d_tick);
-    if ((st = dev_scan(c, d_cnt, d_cnt, (size_t)c->W, nullptr))) return st;
-    hipLaunchKernelGGL(emba_perm_place_kernel, dim3(nblocks(P)), dim3(256), 0, s, c->d_active.as<uint32_t>() + lo, (long)P, c->W, d_cnt, d_tick, d_pm);
-    HIP_TRY(c, hipGetLastError());
-    c->solve.perm_valid = true; c->solve.perm_lo = lo; c->solve.perm_n = P;
-    *perm = d_pm;
-    return EMBA_OK;
-}
-
-RecView local_view(emba_ctx* c)
-{
-    RecView v{};
-    v.rec = c->work.rec.as<double>(); v.slot_key = c->d_slot_key.as<uint32_t>(); v.compact = c->d_compact.as<int32_t>(); v.stamp = c->work.stamp; v.packed = 0; v.pix_base = 0;
-    return v;
-}
-
-// the records a rank received as the owner of the active pixels from `lo` on (the sharded solves)
-RecView packed_view(const double* recv_dev, size_t lo) { RecView v{}; v.rec = recv_dev; v.packed = 1; v.pix_base = (long)lo; return v; }
-
-// Are the equations in the pack finished, and formed from the working record set?  What every solver asks first.
-emba_status equations_current(emba_ctx* c, const char* what)
-{
-    if (!c->eq.finish_done) return fail(c, EMBA_ERR_STATE, "%s needs formNormalEq + applyL2Reg (emba_form_finish) first", what);
-    if (c->eq_in_alt) return fail(c, EMBA_ERR_STATE, "an evaluation has been written since these equations were formed (its records are the working set): report the LM decision first — emba_map_reject / emba_trial_reject to go back to them, or form the new ones");
-    return EMBA_OK;
-}
-
-// the pose block and the augmented Schur matrix S_aug of the current equations
-struct SchurDims {
-    int n, na, skip; long lds;   // n = 3K; na = n + 1: row n carries y / the right-hand side; lds: leading dimension of S_aug and of U; skip: the fixed first pose's rows
-    SchurDims(const emba_ctx* c, int fix_first_pose = 0) : n(3 * c->eq.K), na(n + 1), skip(fix_first_pose ? 3 : 0), lds((na + 15) / 16 * 16) {}
-    size_t size() const { return (size_t)lds * na; }
-};
-
-// The info word of a Schur solve.  bit 0: a 2x2 block A22m_i is not positive definite — the reference's A22m_i.inverse() (model.cpp:750) returns inf / nan there and
-// the step is lost (NaN cost: rejected); reported as EMBA_ERR_NUMERIC.  bit 1: a pivot of S vanished — handled like Eigen's ldlt (zero update), not an error.
-emba_status solve_status(emba_ctx* c, int info)
-{
-    c->solve.info = info;
-    if (info & 1) return fail(c, EMBA_ERR_NUMERIC, "a 2x2 block of A22 + lambda*diag(A22) is not positive definite (the reference's inverse() gives inf/nan)");
-    if (info & 4) return fail(c, EMBA_ERR_NUMERIC, "the Schur complement is indefinite or not finite (a pivot clearly below zero, or NaN): no update is returned");
-    return EMBA_OK;
-}
-
-// x2 = A22m^-1 (b2 - A12^T x1) of the n_pix pixels of the lists L, straight from the records of each pixel
-emba_status launch_schur_x2(emba_ctx* c, const SolveLists& L, size_t n_pix, int n, const double* d_y, const double* d_cf, const double* d_x1, double* d_x2)
-{
-    if (emba_status st = pose_vector_lds(c, (const void*)emba_schur_x2_kernel, (size_t)n * sizeof(double), "solveNormalEq (x2)")) return st;
-    if (n_pix)
-        hipLaunchKernelGGL(emba_schur_x2_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, 8192)), dim3(256), (size_t)n * sizeof(double), c->stream, L.sorted, L.off, d_y,
-                           d_cf, d_x1, c->eq.irls, c->eq.eta, (long)n_pix, d_x2, n);
-    return EMBA_OK;
-}
-
-// the pixels' part of y = [A11m A12; A12^T A22m] v: the n_pix pixels of the lists L, whose A22 | b2 rows start at pixel `lo` of the pack
-void launch_cg_pixels(emba_ctx* c, const SolveLists& L, size_t lo, size_t n_pix, double lambda, int n, int skip, const double* v, double* y)
-{
-    if (!n_pix) return;
-    CgPixParams pp{};
-    pp.view = L.sorted; pp.off = L.off; pp.A22b2 = pack_A22b2(c) + 5 * lo; pp.lambda = lambda; pp.irls = c->eq.irls; pp.eta = c->eq.eta; pp.n = n; pp.skip = skip;
-    pp.P = (long)n_pix; pp.v = v; pp.y = y;
-    hipLaunchKernelGGL(emba_cg_pixel_kernel, dim3((unsigned)std::min<size_t>((n_pix + 3) / 4, (size_t)8 * c->n_cu)), dim3(256), (size_t)n * 16, c->stream, pp);
-}
-
-}  // namespace
-
-extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t fix_first_pose, double* x1_host, double* x2_host)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    emba_status st = equations_current(c, "solveNormalEq");
-    if (st) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((st = resolve_pending(c))) return st;
-    hipStream_t s = c->stream;
-    const SchurDims d(c, fix_first_pose);
-    const int n = d.n, skip = d.skip;
-    const long lds_ = d.lds;
-    const size_t P = c->eq.P, M = c->win.n_cand;
-    if (n - skip <= 0) return fail(c, EMBA_ERR_INVALID_ARG, "nothing to solve for");
-    auto& sv = take_solve_scratch(c);
-    if ((st = ensure<double>(c, sv.S_or_x, d.size())) || (st = ensure<double>(c, sv.rhs_or_r, n)) || (st = ensure<double>(c, sv.y_or_z, 2 * (P + 1))) ||
-        (st = ensure<double>(c, sv.cf_or_t, 3 * (P + 1))) || (st = ensure<double>(c, sv.x2_or_invd, 2 * (P + 1))) || (st = ensure<int>(c, sv.info_or_sc, 1)))
-        return st;
-    double *d_S = sv.S_or_x.as<double>(), *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>(), *d_x2 = sv.x2_or_invd.as<double>();
-    int* d_info = sv.info_or_sc.as<int>();
-    if ((st = ensure_compact(c))) return st;
-    HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
-    HIP_TRY(c, hipMemsetAsync(d_S, 0, d.size() * sizeof(double), s));
-    const RecView view = local_view(c);
-    SolveLists L;
-    if ((st = build_lists(c, view, M, P, &L))) return st;
-    hipLaunchKernelGGL(emba_schur_init_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, d_S, lds_);
-    const uint32_t* perm = nullptr;
-    if ((st = solve_perm(c, P, &perm))) return st;
-    if ((st = schur_accumulate(c, L.sorted, L, P, pack_A22b2(c), lambda, n, d_S, lds_, d_y, d_cf, d_info, perm))) return st;
-    if ((st = schur_factor_solve(c, d_S, lds_, n, skip, d_rhs, d_info))) return st;
-    if (P && (st = launch_schur_x2(c, L, P, n, d_y, d_cf, d_rhs, d_x2))) return st;
-    HIP_TRY(c, hipGetLastError());
-    int info = 0;
-    HIP_TRY(c, hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, d_rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (x2_host && P) HIP_TRY(c, hipMemcpyAsync(x2_host, d_x2, 2 * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    if ((st = keep_x2(c, d_x2, P))) return st;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return solve_status(c, info);
-}
-
-extern "C" emba_status emba_last_solve_info(const emba_ctx* c, int32_t* info)
-{
-    if (!c || !info) return EMBA_ERR_INVALID_ARG;
-    *info = c->solve.info;
-    return EMBA_OK;
-}
-
-// ---- sharded Schur solve (f1 on N GPUs): count / pack / [all-to-all] / partial / [all-reduce] / finish ----------------------------
-extern "C" emba_status emba_solve_shard_size(emba_ctx* c, size_t* s_doubles)
-{
-    if (!c || !s_doubles) return EMBA_ERR_INVALID_ARG;
-    *s_doubles = SchurDims(c).size();
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_solve_shard_count(emba_ctx* c, int32_t n_ranks, size_t* counts_host)
-{
-    if (!c || !counts_host || n_ranks < 1 || n_ranks > 1024) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_count: bad arguments") : EMBA_ERR_INVALID_ARG;
-    emba_status st = equations_current(c, "the sharded solve");
-    if (st) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((st = resolve_pending(c)) || (st = ensure_compact(c))) return st;
-    hipStream_t s = c->stream;
-    auto& sv = take_solve_scratch(c);
-    if ((st = ensure<unsigned long long>(c, sv.shard_cnt, (size_t)3 * n_ranks + 1))) return st;
-    unsigned long long* d_cnt = sv.shard_cnt.as<unsigned long long>();
-    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, (size_t)3 * n_ranks * 8 + 8, s));
-    if (c->win.n_cand) hipLaunchKernelGGL(emba_shard_count_kernel, dim3((unsigned)std::min<size_t>(nblocks(c->win.n_cand), (size_t)4 * c->n_cu)), dim3(256), 0, s, local_view(c), (long)c->win.n_cand, (long)c->eq.P, (int)n_ranks, d_cnt);
-    std::vector<unsigned long long> h(n_ranks);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), d_cnt, (size_t)n_ranks * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    unsigned long long run = 0;
-    std::vector<unsigned long long> off(n_ranks);
-    for (int r = 0; r < n_ranks; ++r) { counts_host[r] = (size_t)h[r]; off[r] = run; run += h[r]; }
-    HIP_TRY(c, hipMemcpyAsync(d_cnt + n_ranks, off.data(), (size_t)n_ranks * 8, hipMemcpyHostToDevice, s));   // [n, 2n): offsets; [2n, 3n): cursors (zero)
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_solve_shard_pack(emba_ctx* c, int32_t n_ranks, double* send_dev)
-{
-    if (!c || n_ranks < 1 || n_ranks > kShardMaxRanks) return EMBA_ERR_INVALID_ARG;
-    if (!c->sv.shard_cnt.p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_count first");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    unsigned long long* d_cnt = take_solve_scratch(c).shard_cnt.as<unsigned long long>();
-    HIP_TRY(c, hipMemsetAsync(d_cnt + 2 * n_ranks, 0, (size_t)n_ranks * 8, s));
-    if (c->win.n_cand && send_dev)
-        hipLaunchKernelGGL(emba_shard_pack_kernel, dim3(nblocks(c->win.n_cand, kShardPackRec)), dim3(256), 0, s, local_view(c), (long)c->win.n_cand, (long)c->eq.P, (int)n_ranks, d_cnt + n_ranks,
-                           d_cnt + 2 * n_ranks, send_dev);
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-namespace {
-void shard_range(size_t P, int rank, int n_ranks, size_t* lo, size_t* hi) { *lo = (P * (size_t)rank) / n_ranks; *hi = (P * ((size_t)rank + 1)) / n_ranks; }
-}
-
-// Does this rank still hold, in pixel order, the records it received as the owner of its pixel range for the CURRENT equations (a re-solve with another lambda after a
-// rejected trial, solver.cpp:340-352)?  Then emba_solve_shard_count / _pack and the all-to-all can be skipped and emba_solve_shard_partial / _finish take recv_dev = NULL.
-extern "C" emba_status emba_solve_shard_cached(emba_ctx* c, int32_t rank, int32_t n_ranks, int32_t* cached, size_t* n_recv)
-{
-    if (!c || !cached || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_cached: bad arguments") : EMBA_ERR_INVALID_ARG;
-    size_t lo, hi;
-    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
-    const ListsKey key{true, c->work.stamp, hi - lo, c->solve.key.nrec, (long)lo};   // (how many records it received is what the cache tells the caller)
-    *cached = (c->eq.finish_done && !c->eq_in_alt && c->solve.lists_valid && c->solve.key == key && c->sv.y_or_z.p) ? 1 : 0;
-    if (n_recv) *n_recv = *cached ? c->solve.key.nrec : 0;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_solve_shard_partial(emba_ctx* c, int32_t rank, int32_t n_ranks, const double* recv_dev, size_t n_recv, double lambda, double* S_part_dev)
-{
-    if (!c || !S_part_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_partial: bad arguments") : EMBA_ERR_INVALID_ARG;
-    emba_status st = equations_current(c, "the sharded solve");
-    if (st) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const SchurDims d(c);
-    size_t lo, hi;
-    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
-    const size_t n_pix = hi - lo;
-    auto& sv = take_solve_scratch(c);
-    if ((st = ensure<double>(c, sv.y_or_z, 2 * (n_pix + 1))) || (st = ensure<double>(c, sv.cf_or_t, 3 * (n_pix + 1))) || (st = ensure<int>(c, sv.info_or_sc, 16))) return st;
-    double *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
-    int* d_info = sv.info_or_sc.as<int>();
-    HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
-    HIP_TRY(c, hipMemsetAsync(S_part_dev, 0, d.size() * sizeof(double), s));
-    SolveLists L;
-    if ((st = build_lists(c, packed_view(recv_dev, lo), n_recv, n_pix, &L))) return st;
-    const uint32_t* perm = nullptr;
-    if ((st = solve_perm(c, n_pix, &perm, lo))) return st;
-    return schur_accumulate(c, L.sorted, L, n_pix, pack_A22b2(c) + 5 * lo, lambda, d.n, S_part_dev, d.lds, d_y, d_cf, d_info, perm);
-}
-
-extern "C" emba_status emba_solve_shard_finish(emba_ctx* c, int32_t rank, int32_t n_ranks, const double* recv_dev, size_t n_recv, double lambda,
-                                               int32_t fix_first_pose, double* S_dev, double* x1_host, double* x2_full_dev)
-{
-    if (!c || !S_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "solve_shard_finish: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->lists.off.p || !c->sv.y_or_z.p) return fail(c, EMBA_ERR_STATE, "call emba_solve_shard_partial first");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const SchurDims d(c, fix_first_pose);
-    const int n = d.n;
-    size_t lo, hi;
-    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
-    const size_t n_pix = hi - lo;
-    auto& sv = take_solve_scratch(c);
-    emba_status st;
-    if ((st = ensure<double>(c, sv.rhs_or_r, n))) return st;
-    double *d_rhs = sv.rhs_or_r.as<double>(), *d_y = sv.y_or_z.as<double>(), *d_cf = sv.cf_or_t.as<double>();
-    int* d_info = sv.info_or_sc.as<int>();
-    hipLaunchKernelGGL(emba_schur_add_a11_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, S_dev, d.lds);
-    if ((st = schur_factor_solve(c, S_dev, d.lds, n, d.skip, d_rhs, d_info))) return st;
-    if (x2_full_dev) {
-        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->eq.P * sizeof(double), s));
-        // the received records in pixel order, as emba_solve_shard_partial's build_lists left them
-        if ((st = launch_schur_x2(c, cached_lists(c), n_pix, n, d_y, d_cf, d_rhs, x2_full_dev + 2 * lo))) return st;
-    }
-    HIP_TRY(c, hipGetLastError());
-    int info = 0;
-    HIP_TRY(c, hipMemcpyAsync(&info, d_info, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, d_rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return solve_status(c, info);
-}
-
-// LEGM::solveNormalEqCG (model.cpp:794-840)
-extern "C" emba_status emba_solve_normal_eq_cg(emba_ctx* c, double lambda, int32_t fix_first_pose, int32_t max_iter, double tol, double* x1_host,
-                                               double* x2_host, int32_t* iterations, double* error)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    emba_status st = equations_current(c, "solveNormalEqCG");
-    if (st) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((st = resolve_pending(c))) return st;
-    hipStream_t s = c->stream;
-    const int n = 3 * c->eq.K, skip = fix_first_pose ? 3 : 0;
-    const size_t P = c->eq.P, M = c->win.n_cand, N = (size_t)n + 2 * P;
-    if (max_iter <= 0) max_iter = 100;     // model.cpp:823-824
-    if (!(tol > 0)) tol = 1e-6;
-    if ((st = ensure_cg_vectors(c, N))) return st;
-    const CgVecs v = cg_vectors(c);
-    double *d_x = v.x, *d_r = v.r, *d_p = v.p, *d_z = v.z, *d_t = v.t, *d_invd = v.invd, *d_sc = v.sc;
-    if ((st = ensure_compact(c))) return st;
-    const RecView view = local_view(c);
-    SolveLists L;
-    if ((st = build_lists(c, view, M, P, &L))) return st;
-    const unsigned gridN = (unsigned)std::min<size_t>(nblocks(N), 1024);
-    auto read2 = [&](double* a, double* b) -> emba_status {   // device scalars d_sc[0], d_sc[1] -> host, then cleared
-        double h[2] = {0, 0};
-        HIP_TRY(c, hipMemcpyAsync(h, d_sc, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipMemsetAsync(d_sc, 0, 16, s));
-        if (a) *a = h[0];
-        if (b) *b = h[1];
-        return EMBA_OK;
-    };
-    if ((st = pose_vector_lds(c, (const void*)emba_cg_pixel_kernel, (size_t)n * 16, "solveNormalEqCG", 48))) return st;
-    auto apply = [&](const double* v, double* y) {   // y = [A11m A12; A12^T A22m] v
-        hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, lambda, skip, v, y);
-        launch_cg_pixels(c, L, 0, P, lambda, n, skip, v, y);
-    };
-    // Eigen/src/IterativeLinearSolvers/ConjugateGradient.h:28-88 (zero initial guess: residual = rhs)
-    HIP_TRY(c, hipMemsetAsync(d_sc, 0, 64, s));
-    hipLaunchKernelGGL(emba_cg_init_kernel, dim3(gridN), dim3(256), 0, s, pack_A11(c), pack_b1(c), pack_A22b2(c), n, skip, (long)P, lambda, d_x, d_r, d_p, d_invd, d_sc);
-    double rhs2 = 0, absNew = 0;
-    if ((st = read2(&rhs2, &absNew))) return st;
-    int it = 0;
-    double err = 0;
-    if (rhs2 != 0) {
-        const double thr = std::max(tol * tol * rhs2, std::numeric_limits<double>::min());
-        double rn2 = rhs2;
-        if (rn2 >= thr) {
-            while (it < max_iter) {
-                apply(d_p, d_t);
-                hipLaunchKernelGGL(emba_cg_dot_kernel, dim3(gridN), dim3(256), 0, s, d_p, d_t, (long)N, d_sc);
-                double pt = 0;
-                if ((st = read2(&pt, nullptr))) return st;
-                const double alpha = absNew / pt;
-                hipLaunchKernelGGL(emba_cg_xr_kernel, dim3(gridN), dim3(256), 0, s, alpha, d_p, d_t, (long)N, d_x, d_r, d_sc);
-                hipLaunchKernelGGL(emba_cg_z_kernel, dim3(gridN), dim3(256), 0, s, d_invd, d_r, (long)N, d_z, d_sc + 1);
-                double absNext = 0;
-                if ((st = read2(&rn2, &absNext))) return st;
-                if (rn2 < thr) break;
-                const double beta = absNext / absNew;
-                absNew = absNext;
-                hipLaunchKernelGGL(emba_cg_p_kernel, dim3(nblocks(N)), dim3(256), 0, s, beta, d_z, (long)N, d_p);
-                ++it;
-            }
-        }
-        err = std::sqrt(rn2 / rhs2);
-    } else {
-        HIP_TRY(c, hipMemsetAsync(d_x, 0, N * 8, s));
-    }
-    HIP_TRY(c, hipGetLastError());
-    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (x2_host && P) HIP_TRY(c, hipMemcpyAsync(x2_host, d_x + n, 2 * P * sizeof(double), hipMemcpyDeviceToHost, s));
-    if ((st = keep_x2(c, d_x + n, P))) return st;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (iterations) *iterations = it;
-    if (error) *error = err;
-    return EMBA_OK;
-}
-
-// ---- LEGM::solveNormalEqCG over a sharded window (round 6, VERDICT r5 missing #3: a launch file with use_CG = true on several GPUs, solver.cpp:190-202) --------------
-// The system [A11m A12; A12^T A22m] is applied matrix-free with the PIXELS sharded: rank r owns the active pixels [P r / n, P (r+1) / n) and — after the same
-// record exchange as the sharded Schur solve (cached across re-solves) — every record of those pixels.  A CG vector is [pose part, 3K, REPLICATED | this rank's
-// 2 x (its pixels) map entries]; the map part of M v is local, the pose part is a sum over the ranks' pixels: ONE all-reduce of 3K + 2 doubles per application
-// (the rank's share of t1 and of p.t), one of 2 doubles per iteration for r.r and r.z.  Every rank takes the same scalars from the reduced sums, so the
-// replicated pose parts stay bit-identical.  The loop itself (Eigen's ConjugateGradient.h:28-88) is driven by the host: emba_group_solve_cg, emba_amd/sharded.py.
-//   begin     lists of the owned pixels' records, x = 0, r = b, p = invd r;  red[n] = r.r, red[n+1] = r.p (partial)      -> all-reduce red (n + 2)
-//   apply     t = M p on this rank's pixels;  red[0..n) = its share of t1 (rank 0 adds A11m p1), red[n] = p2.t2          -> all-reduce red (n + 2)
-//   pt        t1 = red[0..n);  *pt = p1.t1 + red[n]
-//   update    x += alpha p, r -= alpha t, z = invd r;  red[n] = r.r, red[n+1] = r.z (partial)                             -> all-reduce red + n (2)
-//   direction p = z + beta p
-//   end       x1 -> host, this rank's x2 into x2_full_dev (zeros elsewhere)                                               -> all-reduce x2_full (2P)
-// Partial sums count the replicated pose part on rank 0 only.
-extern "C" emba_status emba_cg_shard_size(emba_ctx* c, size_t* red_doubles)
-{
-    if (!c || !red_doubles) return EMBA_ERR_INVALID_ARG;
-    *red_doubles = (size_t)3 * c->eq.K + 2;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_begin(emba_ctx* c, int32_t rank, int32_t n_ranks, const double* recv_dev, size_t n_recv, double lambda, int32_t fix_first_pose,
-                                           double* red_dev)
-{
-    if (!c || !red_dev || rank < 0 || rank >= n_ranks) return c ? fail(c, EMBA_ERR_INVALID_ARG, "cg_shard_begin: bad arguments") : EMBA_ERR_INVALID_ARG;
-    emba_status st = equations_current(c, "solveNormalEqCG");
-    if (st) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    auto& g = c->solve.cg;
-    g.rank = rank; g.n_ranks = n_ranks; g.n = 3 * c->eq.K; g.skip = fix_first_pose ? 3 : 0; g.lambda = lambda;
-    size_t lo, hi;
-    shard_range(c->eq.P, rank, n_ranks, &lo, &hi);
-    g.lo = lo; g.npix = hi - lo; g.Nl = (size_t)g.n + 2 * g.npix;
-    if ((st = ensure_cg_vectors(c, g.Nl))) return st;
-    const CgVecs v = cg_vectors(c);
-    SolveLists L;
-    if ((st = build_lists(c, packed_view(recv_dev, lo), n_recv, g.npix, &L))) return st;
-    if ((st = pose_vector_lds(c, (const void*)emba_cg_pixel_kernel, (size_t)g.n * 16, "solveNormalEqCG", 48))) return st;
-    HIP_TRY(c, hipMemsetAsync(red_dev, 0, ((size_t)g.n + 2) * 8, s));
-    const unsigned grid = (unsigned)std::min<size_t>(nblocks(g.Nl), 1024);
-    hipLaunchKernelGGL(emba_cg_init_kernel, dim3(grid), dim3(256), 0, s, pack_A11(c), pack_b1(c), pack_A22b2(c) + 5 * lo, g.n, g.skip, (long)g.npix, lambda, v.x, v.r, v.p, v.invd,
-                       red_dev + g.n, (long)(rank == 0 ? 0 : g.n));
-    HIP_TRY(c, hipGetLastError());
-    g.active = true;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_apply(emba_ctx* c, double* red_dev)
-{
-    if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->solve.cg;
-    if (emba_status st = cg_resume(c)) return st;
-    const CgVecs v = cg_vectors(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int n = g.n;
-    if (g.rank == 0) hipLaunchKernelGGL(emba_cg_a11_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pack_A11(c), n, g.lambda, g.skip, v.p, v.t);
-    else HIP_TRY(c, hipMemsetAsync(v.t, 0, (size_t)n * 8, s));
-    launch_cg_pixels(c, cached_lists(c), g.lo, g.npix, g.lambda, n, g.skip, v.p, v.t);
-    HIP_TRY(c, hipMemcpyAsync(red_dev, v.t, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(red_dev + n, 0, 16, s));
-    if (g.npix) hipLaunchKernelGGL(emba_cg_dot_kernel, dim3((unsigned)std::min<size_t>(nblocks(2 * g.npix), 1024)), dim3(256), 0, s, v.p + n, v.t + n, (long)(2 * g.npix), red_dev + n);
-    HIP_TRY(c, hipGetLastError());
-    g.active = true;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_pt(emba_ctx* c, const double* red_dev, double* pt)
-{
-    if (!c || !red_dev || !pt) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->solve.cg;
-    if (emba_status st = cg_resume(c)) return st;
-    const CgVecs v = cg_vectors(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int n = g.n;
-    HIP_TRY(c, hipMemcpyAsync(v.t, red_dev, (size_t)n * 8, hipMemcpyDeviceToDevice, s));      // the reduced t1, identical on every rank
-    HIP_TRY(c, hipMemsetAsync(v.sc, 0, 16, s));
-    hipLaunchKernelGGL(emba_cg_dot_kernel, dim3(1), dim3(256), 0, s, v.p, v.t, (long)n, v.sc);     // (one block: the same summation order on every rank)
-    double h[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(&h[0], v.sc, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&h[1], red_dev + n, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    *pt = h[0] + h[1];
-    g.active = true;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_update(emba_ctx* c, double alpha, double* red_dev)
-{
-    if (!c || !red_dev) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->solve.cg;
-    if (emba_status st = cg_resume(c)) return st;
-    const CgVecs v = cg_vectors(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const long from = g.rank == 0 ? 0 : g.n;
-    const unsigned grid = (unsigned)std::min<size_t>(nblocks(g.Nl), 1024);
-    HIP_TRY(c, hipMemsetAsync(red_dev + g.n, 0, 16, s));
-    hipLaunchKernelGGL(emba_cg_xr_kernel, dim3(grid), dim3(256), 0, s, alpha, v.p, v.t, (long)g.Nl, v.x, v.r, red_dev + g.n, from);
-    hipLaunchKernelGGL(emba_cg_z_kernel, dim3(grid), dim3(256), 0, s, v.invd, v.r, (long)g.Nl, v.z, red_dev + g.n + 1, from);
-    HIP_TRY(c, hipGetLastError());
-    g.active = true;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_direction(emba_ctx* c, double beta)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->solve.cg;
-    if (emba_status st = cg_resume(c)) return st;
-    const CgVecs v = cg_vectors(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(emba_cg_p_kernel, dim3(nblocks(g.Nl)), dim3(256), 0, c->stream, beta, v.z, (long)g.Nl, v.p);
-    HIP_TRY(c, hipGetLastError());
-    g.active = true;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_cg_shard_end(emba_ctx* c, double* x1_host, double* x2_full_dev)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    auto& g = c->solve.cg;
-    if (emba_status st = cg_resume(c)) return st;
-    const CgVecs v = cg_vectors(c);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (x2_full_dev) {
-        HIP_TRY(c, hipMemsetAsync(x2_full_dev, 0, 2 * c->eq.P * sizeof(double), s));
-        if (g.npix) HIP_TRY(c, hipMemcpyAsync(x2_full_dev + 2 * g.lo, v.x + g.n, 2 * g.npix * 8, hipMemcpyDeviceToDevice, s));
-    }
-    if (x1_host) HIP_TRY(c, hipMemcpyAsync(x1_host, v.x, (size_t)g.n * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return EMBA_OK;
-}
+#include "solve_host.h"   // f1: the solvers
 
 // ---- f3: intensity panorama from the gradient map ---------------------------------------------------------------------------
 extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_host, const double* Gy_host, double* M_host)

@@ -94,6 +94,22 @@ def test_order_rule_on_the_cpu(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "OK order_rule", r.stdout + r.stderr
 
 
+def test_solve_rule_on_the_cpu(tmp_path):
+    """emba_amd/csrc/solve_rule.h (plain C++17, no HIP): tests/cpp/solve_rule_test.cpp checks the sizes of the Schur matrix, the ranks' pixel ranges, the path
+    of the optical axis, who gets the panorama column order and the plan of the block-sparse product on hand-computed cases, and sweeps the plan over
+    K = 1 ... 1400, every value of the syrk_* options and two chip sizes against the expressions schur_accumulate held before they moved there."""
+    import option_matrix as OM
+    consts = OM.parse_constants(os.path.join(ROOT, "emba_amd", "csrc", "solve_kernels.h"))
+    exe = str(tmp_path / "solve_rule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-DSYRK_SLICE_PIX=%d" % consts["kSyrkSlicePix"], "-DSCHUR_BUILD_WAVES=%d" % consts["kBuildWaves"],
+                           os.path.join(ROOT, "tests", "cpp", "solve_rule_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "OK solve_rule", r.stdout + r.stderr
+    for opt, values in (("syrk_dense", (1,)), ("syrk_lists", (1, 2)), ("syrk_min_cols", (64,)), ("syrk_item_cap", (8,))):      # what the sweep's option values are taken from
+        assert tuple(OM.REQUIRED[opt]) == values, opt
+
+
 ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "adapter_test")
 
 
