@@ -94,6 +94,8 @@ SIGNATURES = {
     "emba_seq_free": (C.c_int, [C.c_void_p]),
     "emba_seq_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _szp, _szp]),
     "emba_set_events_seq": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]),
+    "emba_set_events_seq_shard": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "emba_seq_halo": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _i64p, C.c_size_t, _szp]),
     "emba_seq_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _u8p, _i64p]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
@@ -133,6 +135,12 @@ SIGNATURES = {
     "emba_group_uses_rccl": (C.c_int32, [C.c_void_p]),
     "emba_group_ctx": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "emba_group_set_events": (C.c_int, [C.c_void_p, _u16p, _u16p, _u8p, _i64p, C.c_size_t]),
+    "emba_group_seq_upload": (C.c_int, [C.c_void_p, _u16p, _u16p, _u8p, _i64p, C.c_size_t, C.c_int32, _szp]),
+    "emba_group_seq_size": (C.c_int, [C.c_void_p, _szp]),
+    "emba_group_seq_free": (C.c_int, [C.c_void_p]),
+    "emba_group_seq_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _szp, _szp]),
+    "emba_group_set_events_seq": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]),
+    "emba_group_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_group_upload_map": (C.c_int, [C.c_void_p, _dp, _dp]),
     "emba_group_step": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, _szp, _szp]),
     "emba_group_eval": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp, _szp, _i32p]),

@@ -283,8 +283,9 @@ struct emba_ctx {
     DevBuf d_rstate, d_rhist, d_rcand;
     DevBuf d_img, d_nsrc;
     // the whole (down-sampled) event sequence of a sliding-window run (sequence_kernels.h): uploaded once by emba_seq_upload, registered window by window by
-    // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload
-    struct { DevBuf x, y, pol, t, raw, status; size_t n = 0; } evseq;
+    // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload;
+    // halo_*: emba_set_events_seq_shard's passes — last event per sensor pixel, halo flags and positions per event in front of the shard
+    struct { DevBuf x, y, pol, t, raw, status, halo_last, halo_flag, halo_pos; size_t n = 0; } evseq;
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

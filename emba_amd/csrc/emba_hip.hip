@@ -2371,6 +2371,7 @@ extern "C" emba_status emba_seq_free(emba_ctx* c)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->evseq.x.reset(); c->evseq.y.reset(); c->evseq.pol.reset(); c->evseq.t.reset(); c->evseq.raw.reset();
+    c->evseq.halo_last.reset(); c->evseq.halo_flag.reset(); c->evseq.halo_pos.reset();
     c->evseq.n = 0;
     return EMBA_OK;
 }
@@ -2466,6 +2467,90 @@ extern "C" emba_status emba_set_events_seq(emba_ctx* c, size_t beg, size_t end)
     if (beg > end || end > c->evseq.n) return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
     return emba_set_events_dev(c, c->evseq.x.as<uint16_t>() + beg, c->evseq.y.as<uint16_t>() + beg, c->evseq.pol.as<uint8_t>() + beg, c->evseq.t.as<int64_t>() + beg, end - beg,
                                nullptr, nullptr, nullptr, 0);
+}
+
+namespace {
+// The halo of the time shard that begins at `lo` of the window that begins at win_beg (sequence_kernels.h: emba_halo_*), into ord.halo in the layout
+// emba_set_events stages — [hbt (8 B) | hx (2 B) | hy (2 B)] x *n_halo.  The sequence was checked at its upload: every pixel lies inside the sensor, so
+// inside the table.  One small read: the count, which places hx / hy behind the times.  Scratch of its own (evseq) + dev_scan's.
+emba_status build_seq_halo(emba_ctx* c, size_t win_beg, size_t lo, size_t* n_halo)
+{
+    hipStream_t s = c->stream;
+    const size_t m = lo - win_beg;
+    *n_halo = 0;
+    if (!m) return EMBA_OK;
+    if (m > 0x7FFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events in front of the shard for 32-bit indices");
+    emba_status st;
+    if ((st = ensure<int32_t>(c, c->evseq.halo_last, c->S)) || (st = ensure<uint32_t>(c, c->evseq.halo_flag, m)) || (st = ensure<uint32_t>(c, c->evseq.halo_pos, m)) ||
+        (st = ensure<uint32_t>(c, c->evseq.status, 16)))
+        return st;
+    const uint16_t *x = c->evseq.x.as<uint16_t>() + win_beg, *y = c->evseq.y.as<uint16_t>() + win_beg;
+    const int64_t* t = c->evseq.t.as<int64_t>() + win_beg;
+    int32_t* last = c->evseq.halo_last.as<int32_t>();
+    uint32_t *flag = c->evseq.halo_flag.as<uint32_t>(), *pos = c->evseq.halo_pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + 4;
+    HIP_TRY(c, hipMemsetAsync(last, 0xFF, c->S * sizeof(int32_t), s));      // -1: no event of this pixel
+    hipLaunchKernelGGL(emba_halo_last_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, last);
+    hipLaunchKernelGGL(emba_halo_flag_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, (const int32_t*)last, flag);
+    if ((st = dev_scan(c, flag, pos, m, d_tot))) return st;
+    uint32_t h_tot = 0;
+    HIP_TRY(c, hipMemcpyAsync(&h_tot, d_tot, sizeof h_tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (h_tot > c->S) return fail(c, EMBA_ERR_STATE, "halo of %u entries on a sensor of %zu pixels", h_tot, c->S);
+    const size_t n = h_tot;
+    if ((st = ensure<uint8_t>(c, c->ord.halo, std::max<size_t>(n, 1) * 12))) return st;
+    int64_t* hbt = c->ord.halo.as<int64_t>();
+    uint16_t *hx = reinterpret_cast<uint16_t*>(hbt + n), *hy = hx + n;
+    hipLaunchKernelGGL(emba_halo_gather_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, t, (long)m, (const uint32_t*)flag, (const uint32_t*)pos, hx, hy, hbt);
+    HIP_TRY(c, hipGetLastError());
+    *n_halo = n;
+    return EMBA_OK;
+}
+
+emba_status check_seq_shard(emba_ctx* c, size_t win_beg, size_t lo, size_t hi)
+{
+    if (win_beg > lo || lo > hi || hi > c->evseq.n)
+        return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) of the window at %zu is not a range of the resident sequence of %zu events", lo, hi, win_beg, c->evseq.n);
+    if ((lo - win_beg) % 100) return fail(c, EMBA_ERR_INVALID_ARG, "the shard begins %zu events behind its window: not on the window's batch grid", lo - win_beg);
+    return EMBA_OK;
+}
+}  // namespace
+
+extern "C" emba_status emba_set_events_seq_shard(emba_ctx* c, size_t win_beg, size_t lo, size_t hi)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    emba_status st;
+    if ((st = check_seq_shard(c, win_beg, lo, hi))) return st;      // (before anything of the registered window is touched)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    size_t n_halo = 0;
+    if ((st = build_seq_halo(c, win_beg, lo, &n_halo))) return st;
+    int64_t* hbt = c->ord.halo.as<int64_t>();
+    uint16_t *hx = reinterpret_cast<uint16_t*>(hbt + n_halo), *hy = hx + n_halo;
+    st = emba_set_events_dev(c, c->evseq.x.as<uint16_t>() + lo, c->evseq.y.as<uint16_t>() + lo, c->evseq.pol.as<uint8_t>() + lo, c->evseq.t.as<int64_t>() + lo, hi - lo,
+                             n_halo ? hx : nullptr, n_halo ? hy : nullptr, n_halo ? hbt : nullptr, n_halo);
+    c->set_events_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();      // the halo passes included
+    return st;
+}
+
+extern "C" emba_status emba_seq_halo(emba_ctx* c, size_t win_beg, size_t lo, uint16_t* hx, uint16_t* hy, int64_t* hbt, size_t cap, size_t* n_halo)
+{
+    if (!c || !n_halo) return c ? fail(c, EMBA_ERR_INVALID_ARG, "n_halo NULL") : EMBA_ERR_INVALID_ARG;
+    emba_status st;
+    if ((st = check_seq_shard(c, win_beg, lo, lo))) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    size_t n = 0;
+    if ((st = build_seq_halo(c, win_beg, lo, &n))) return st;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_halo = n;
+    if (!hx && !hy && !hbt) return EMBA_OK;
+    if (cap < n) return fail(c, EMBA_ERR_CAPACITY, "the halo has %zu entries, the arrays hold %zu", n, cap);
+    const int64_t* dhb = c->ord.halo.as<int64_t>();
+    const uint16_t *dhx = reinterpret_cast<const uint16_t*>(dhb + n), *dhy = dhx + n;
+    if (n && hbt && (st = d2h_pageable(c, hbt, dhb, n * 8))) return st;
+    if (n && hx && (st = d2h_pageable(c, hx, dhx, n * 2))) return st;
+    if (n && hy && (st = d2h_pageable(c, hy, dhy, n * 2))) return st;
+    return EMBA_OK;
 }
 
 extern "C" emba_status emba_seq_get(emba_ctx* c, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns)

@@ -447,6 +447,62 @@ emba_status emba_group_set_events(emba_group* g, const uint16_t* x, const uint16
     return EMBA_OK;
 }
 
+// ---- the resident sequence of a sliding-window run, on every rank (emba_seq_*): each context holds its own copy, also where ranks share a device ----
+emba_status emba_group_seq_upload(emba_group* g, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n, int32_t sampling_rate, size_t* n_kept)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    std::vector<size_t> kept(g->n, 0);
+    { emba_status st = gpool(g, [&](int r) { return emba_seq_upload(g->ctx[r], x, y, pol, t_ns, n, sampling_rate, &kept[r]); }); if (st) return st; }
+    if (n_kept) *n_kept = kept[0];
+    return EMBA_OK;
+}
+
+emba_status emba_group_seq_size(const emba_group* g, size_t* n) { return g ? emba_seq_size(g->ctx[0], n) : EMBA_ERR_INVALID_ARG; }
+
+emba_status emba_group_seq_free(emba_group* g)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_seq_free(g->ctx[r]));
+    return EMBA_OK;
+}
+
+// (every rank holds the same sequence and the search is deterministic: rank 0's answer is everybody's)
+emba_status emba_group_seq_window(emba_group* g, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    G_TRY(g, 0, emba_seq_window(g->ctx[0], t_beg_ns, t_end_ns, beg, end));
+    return EMBA_OK;
+}
+
+// emba_group_set_events on the window [beg, end) of the resident sequence: the same rank ranges on the WINDOW's batch grid, every rank's halo built on its
+// own device from its own copy (emba_set_events_seq_shard), the registrations issued side by side from the ranks' threads.  No event crosses PCIe.
+emba_status emba_group_set_events_seq(emba_group* g, size_t beg, size_t end)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    if (beg > end || end > g->ctx[0]->evseq.n) return gfail(g, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, g->ctx[0]->evseq.n);
+    const size_t nb = (end - beg) / 100;
+    std::vector<size_t> lo(g->n), hi(g->n);
+    size_t b = 0;
+    for (int r = 0; r < g->n; ++r) {
+        const size_t cnt = nb / g->n + ((size_t)r < nb % g->n ? 1 : 0);
+        lo[r] = beg + b * 100; hi[r] = beg + (b + cnt) * 100;
+        b += cnt;
+    }
+    // the last rank also receives the n % 100 tail the reference drops (quirk Q1), as in emba_group_set_events
+    { emba_status st = gpool(g, [&](int r) { return emba_set_events_seq_shard(g->ctx[r], beg, lo[r], r == g->n - 1 ? end : hi[r]); }); if (st) return st; }
+    for (int r = 0; r < g->n; ++r) { g->n_local[r] = hi[r] - lo[r]; g->lo[r] = lo[r] - beg; }
+    g->x1_done = false;
+    return EMBA_OK;
+}
+
+// emba.cpp:357-364 on every replica of the resident map
+emba_status emba_group_median_blur3_map(emba_group* g)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_median_blur3_map(g->ctx[r]));
+    return EMBA_OK;
+}
+
 emba_status emba_group_upload_map(emba_group* g, const double* Gx, const double* Gy)
 {
     if (!g) return EMBA_ERR_INVALID_ARG;

@@ -4,10 +4,14 @@
 //   * emba_seq_ingest_kernel   validation of a chunk of the raw sequence + the down-sampling of emba.cpp:281-304 as a strided gather
 //   * emba_seq_window_kernel   getEventSubset (emba.cpp:473-510): both cursors as min-reductions over every 100th timestamp
 //   * emba_median3_kernel      cv::medianBlur(., ., 3) on a float32 copy of a plane (emba.cpp:357-364)
+//   * emba_halo_*_kernel       the per-pixel halo of a time shard of a window: for every sensor pixel the last event in front of the
+//                              rank's range, in three passes — last event per pixel (atomicMax), flags + scan (order_kernels.h), gather
 // All of it is bandwidth-bound, once-per-run or once-per-window work: one thread per element, coalesced loads, no tuning.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "order_kernels.h"   // batch_mid_ns_dev
 
 namespace emba {
 
@@ -53,6 +57,35 @@ __global__ __launch_bounds__(256) void emba_seq_window_kernel(const int64_t* __r
         if (ja != 0xFFFFFFFFu) atomicMin(res + 0, ja);
         if (jb != 0xFFFFFFFFu) atomicMin(res + 1, jb);
     }
+}
+
+// ---- the halo of a time shard: the events [0, m) handed in are [win_beg, lo) of the sequence, m a multiple of 100 (the WINDOW's batch grid) ----
+// Pass 1: last[p] = the largest i with pixel(i) == p (last preset to -1: "none", below offset 0).  One 32-bit atomic per event on a table of sensor size.
+__global__ void emba_halo_last_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, long m, int sw, int32_t* __restrict__ last)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) atomicMax(last + ((size_t)y[i] * sw + x[i]), (int32_t)i);
+}
+
+// Pass 2: flag[i] = 1 iff event i is its pixel's last one; the exclusive scan of the flags (dev_scan) then numbers the halo entries in index = time order.
+__global__ void emba_halo_flag_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, long m, int sw, const int32_t* __restrict__ last,
+                                      uint32_t* __restrict__ flag)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) flag[i] = last[(size_t)y[i] * sw + x[i]] == (int32_t)i;
+}
+
+// Pass 3: entry pos[i] of the halo = (x, y, midpoint of the window batch i / 100) of every flagged event; t: the window's timestamps (t[0] is win_beg's).
+__global__ void emba_halo_gather_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, const int64_t* __restrict__ t, long m,
+                                        const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, uint16_t* __restrict__ hx, uint16_t* __restrict__ hy,
+                                        int64_t* __restrict__ hbt)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m || !flag[i]) return;
+    const long b = i / 100;
+    const uint32_t j = pos[i];
+    hx[j] = x[i]; hy[j] = y[i];
+    hbt[j] = batch_mid_ns_dev(t[100 * b], t[100 * b + 99]);
 }
 
 // a <- min, b <- max: one exchange of the median network (no branch on data)

@@ -3,8 +3,10 @@
 `sliding_window_stride`; the trajectory grows window by window, the map is carried from one window to the next on the device.
 
 With a device model (emba_amd.LEGM) the whole event sequence crosses to the device once (LEGM.set_sequence: checked and down-sampled there), every window
-is a range of it (LEGM.sequence_window -> EventWindow -> emba_set_events_seq) and the median blur of the initial map runs on the resident map.  Models
-without a resident sequence (the sharded host, the test suite's oracle model) get the same windows as host slices, through the numpy forms in emba_amd.io.
+is a range of it (LEGM.sequence_window -> EventWindow -> emba_set_events_seq) and the median blur of the initial map runs on the resident map.  The sharded
+host (sharded.ShardedModel over HipEngine) does the same on every rank: each holds the whole sequence and registers its time shard of the window from it, the
+per-pixel halo built on the device (emba_set_events_seq_shard).  Models without a resident sequence (the test suite's oracle model, a sharded host over an
+engine that has none) get the same windows as host slices, through the numpy forms in emba_amd.io.
 
 Time cursors are integer nanoseconds by the rostime rules of SURVEY.md Appendix A (ros::Time(double) / ros::Duration(double): io.ros_time_ns)."""
 import dataclasses
@@ -49,6 +51,12 @@ class SequenceResult:
     n_events: int = 0           # events of the sequence after down-sampling
 
 
+def keeps_sequence(model):
+    """Can `model` hold the whole sequence on the device and register windows as ranges of it?  emba_amd.LEGM can; a sharded.ShardedModel says so itself
+    (has_resident_sequence: only where its engine can); anything without set_sequence cannot."""
+    return hasattr(model, "set_sequence") and bool(getattr(model, "has_resident_sequence", True))
+
+
 def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm=LMSettings(), runtime_log=None, map_recorder=None, resident=True,
                  resident_sequence=None, verbose=False):
     """model: emba_amd.LEGM (or anything solve_time_window drives).  events: the whole recording (EventPacket, sorted).  pose_t [n] seconds, pose_q [n,4]
@@ -56,7 +64,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
     the windows like the reference's function statics.  resident: as in solve_time_window.  resident_sequence: keep the sequence on the device (default:
     wherever the model can); False registers every window from a host slice (emba_set_events) instead."""
     if resident_sequence is None:
-        resident_sequence = hasattr(model, "set_sequence")
+        resident_sequence = keeps_sequence(model)
     pose_t = np.asarray(pose_t, dtype=np.float64)
     pose_q = np.asarray(pose_q, dtype=np.float64).reshape(-1, 4)
     pose_t_ns = np.array([emba_io.ros_time_ns(t) for t in pose_t], dtype=np.int64)      # std::map<ros::Time, SO3d>, pose_manager.cpp:41-80
@@ -86,7 +94,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
 
     # median blur of the initial map, emba.cpp:357-364
     if seq.median_blur:
-        if hasattr(model, "median_blur_map"):
+        if hasattr(model, "median_blur_map") and getattr(model, "has_resident_sequence", True):      # (a ShardedModel over an engine without one: numpy)
             model.upload_map(Gx, Gy)
             model.median_blur_map()
             Gx = Gy = None                                                              # "the resident map"

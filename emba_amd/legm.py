@@ -174,6 +174,21 @@ class LEGM:
         self._check(self._L.emba_seq_window(self._ctx, int(t_beg_ns), int(t_end_ns), C.byref(b), C.byref(e)))
         return b.value, e.value
 
+    def set_events_seq_shard(self, win_beg, lo, hi):
+        """This rank's part [lo, hi) of the window that begins at win_beg of the resident sequence (emba_set_events_seq_shard): the per-pixel halo of
+        [win_beg, lo) is built on the device, nothing is sliced or sent from the host.  (lo - win_beg) % 100 == 0."""
+        self._check(self._L.emba_set_events_seq_shard(self._ctx, int(win_beg), int(lo), int(hi)))
+        self.n_events = int(hi) - int(lo)
+
+    def sequence_halo(self, win_beg, lo):
+        """The halo that registration builds, as (x, y, batch_t_ns) arrays (a download: tests, diagnostics) — what sharded.shard_events returns for the rank
+        that begins at lo - win_beg of the slice [win_beg, ...)."""
+        n = C.c_size_t(0)
+        self._check(self._L.emba_seq_halo(self._ctx, int(win_beg), int(lo), None, None, None, 0, C.byref(n)))
+        hx, hy, hbt = np.empty(n.value, np.uint16), np.empty(n.value, np.uint16), np.empty(n.value, np.int64)
+        self._check(self._L.emba_seq_halo(self._ctx, int(win_beg), int(lo), _p(hx, _u16p), _p(hy, _u16p), _p(hbt, _i64p), n.value, C.byref(n)))
+        return hx, hy, hbt
+
     def sequence_events(self, beg, end):
         """[beg, end) of the resident sequence as an EventPacket (a download: tests, diagnostics)."""
         n = int(end) - int(beg)

@@ -25,7 +25,7 @@ import math
 import numpy as np
 
 from ._lib import ERR_NUMERIC as _ERR_NUMERIC, EmbaError
-from .legm import EventPacket
+from .legm import EventPacket, EventWindow
 
 BATCH = 100  # model.cpp:78
 
@@ -52,6 +52,14 @@ def batch_ranges(n_events, world_size):
         cnt = base + (1 if r < rem else 0)
         out.append((b * BATCH, (b + cnt) * BATCH))
         b += cnt
+    return out
+
+
+def window_shard_ranges(beg, end, world_size):
+    """[(lo, hi)] per rank of the window [beg, end) of a resident sequence: batch_ranges on the WINDOW's batch grid shifted by beg; the last rank's hi is
+    `end`, so it carries the (end - beg) % 100 tail the library ignores (as emba_group_set_events hands it out)."""
+    out = [(beg + lo, beg + hi) for lo, hi in batch_ranges(end - beg, world_size)]
+    out[-1] = (out[-1][0], end)
     return out
 
 
@@ -117,6 +125,14 @@ class ShardedLEGM:
         self.force_collectives = False   # rehearse the exchanges with a single rank
 
     def set_events(self, events):
+        """events: the window's EventPacket (sliced on the host: shard_events), or an EventWindow of the sequence set_sequence left on the device — this
+        rank's range of it is then registered there, halo included (emba_set_events_seq_shard)."""
+        if isinstance(events, EventWindow):
+            lo, hi = window_shard_ranges(events.beg, events.end, self.world)[self.rank]
+            self.engine.set_events_seq_shard(events.beg, lo, hi)
+            sizes = [h - l for l, h in batch_ranges(events.size(), self.world)]
+            self.n_local, self.n_max = sizes[self.rank], max(sizes)      # (whole batches, as below; n_max is rank-invariant)
+            return EventWindow(lo, hi)
         local, halo = shard_events(events, self.sensor_w, self.rank, self.world)
         self.engine.set_events(local, halo)
         self.n_local = local.size()
@@ -125,6 +141,17 @@ class ShardedLEGM:
         # different collectives
         self.n_max = max(hi - lo for lo, hi in batch_ranges(events.size(), self.world))
         return local
+
+    # the whole sequence of a sliding-window run: EVERY rank holds all of it (a window's halo reaches back to the window's first event)
+    def set_sequence(self, events, sampling_rate=1):
+        return self.engine.set_sequence(events, sampling_rate)
+
+    def sequence_window(self, t_beg_ns, t_end_ns):
+        """(beg, end) of EMBA::getEventSubset — a deterministic search on equal copies: the same on every rank, no collective."""
+        return self.engine.sequence_window(t_beg_ns, t_end_ns)
+
+    def median_blur_map(self):
+        self.engine.median_blur_map()
 
     def iteration(self, traj, thres_valid_pixel, alpha, cost_type="quadratic", a=0.0, download=False):
         """One evaluateDataError + formNormalEq[IRLS] + applyL2Reg over all ranks.  Map must be resident (upload_map)."""
@@ -343,6 +370,23 @@ class ShardedModel:
     def set_events(self, events):
         self.sh.set_events(events)
 
+    @property
+    def has_resident_sequence(self):
+        """driver.run_sequence: can the windows be ranges of a sequence on the device?  (Not with an engine that has no such thing: host slices then.)"""
+        return hasattr(self.sh.engine, "set_sequence")
+
+    def set_sequence(self, events, sampling_rate=1):
+        return self.sh.set_sequence(events, sampling_rate)
+
+    def sequence_window(self, t_beg_ns, t_end_ns):
+        return self.sh.sequence_window(t_beg_ns, t_end_ns)
+
+    def median_blur_map(self):
+        self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
+
+    def setup_info(self):
+        return self.m.setup_info() if hasattr(self.m, "setup_info") else dict(set_events_ms=float("nan"))
+
     def set_cost(self, cost_type="quadratic", a=0.0):
         self.cost = (cost_type, a)
 
@@ -442,6 +486,18 @@ class HipEngine:
 
     def set_events(self, events, halo):
         self.m.set_events(events, halo)
+
+    def set_events_seq_shard(self, win_beg, lo, hi):
+        self.m.set_events_seq_shard(win_beg, lo, hi)
+
+    def set_sequence(self, events, sampling_rate=1):
+        return self.m.set_sequence(events, sampling_rate)
+
+    def sequence_window(self, t_beg_ns, t_end_ns):
+        return self.m.sequence_window(t_beg_ns, t_end_ns)
+
+    def median_blur_map(self):
+        self.m.median_blur_map()
 
     def upload_map(self, Gx, Gy):
         self.m.upload_map(Gx, Gy)

@@ -279,9 +279,20 @@ emba_status emba_seq_free(emba_ctx* ctx);
  * built from a reversed iterator range, undefined behaviour.  Both are EMBA_ERR_INVALID_ARG ("window holds no events") here. */
 emba_status emba_seq_window(emba_ctx* ctx, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end);
 /* event_subset_ = events_[beg, end) (emba.cpp:508-509) handed to solveTimeWindow: registers that range of the resident sequence as the context's window,
- * exactly as emba_set_events_dev does with pointers into it — no copy, no halo; emba_last_setup_ms reports it like any other registration.  The sequence
- * stays valid across windows and across emba_set_events* calls. */
+ * exactly as emba_set_events_dev does with pointers into it — no copy, no halo (a rank of a time-sharded window: emba_set_events_seq_shard below);
+ * emba_last_setup_ms reports it like any other registration.  The sequence stays valid across windows and across emba_set_events* calls. */
 emba_status emba_set_events_seq(emba_ctx* ctx, size_t beg, size_t end);
+/* A time shard of a window (the window is the event_subset_ of emba.cpp:473-510): this rank's part [lo, hi) of the window that begins at win_beg of
+ * the resident sequence.  The halo — for every sensor pixel with an event in [win_beg, lo) its last such event k, in ascending k, as (x[k], y[k], midpoint of
+ * the WINDOW's batch (k - win_beg) / 100, model.cpp:116-119) — is built on the device from the resident arrays (three passes: last event per pixel, flags +
+ * scan, gather; one small read for the count), then the range is registered exactly as emba_set_events_dev(x + lo, ..., hi - lo, halo ...) would: what
+ * emba_group_set_events / emba_amd.sharded.shard_events compute on the host from a slice, bit for bit.  lo == win_beg: identical to
+ * emba_set_events_seq(lo, hi).  emba_last_setup_ms includes the halo passes.  EMBA_ERR_INVALID_ARG: not win_beg <= lo <= hi <= n, or
+ * (lo - win_beg) % 100 != 0 — the registered window is then left as it was. */
+emba_status emba_set_events_seq_shard(emba_ctx* ctx, size_t win_beg, size_t lo, size_t hi);
+/* The halo that call builds, to the host (tests, diagnostics): capacity cap entries each (EMBA_ERR_CAPACITY below *n_halo, which is set);
+ * array pointers may be NULL to ask for the count only.  Leaves the registered window as it is. */
+emba_status emba_seq_halo(emba_ctx* ctx, size_t win_beg, size_t lo, uint16_t* hx, uint16_t* hy, int64_t* hbt, size_t cap, size_t* n_halo);
 /* [beg, end) of the resident sequence back to the host (tests, diagnostics): capacity end - beg each; any pointer may be NULL. */
 emba_status emba_seq_get(emba_ctx* ctx, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns);
 
@@ -516,6 +527,20 @@ int32_t     emba_group_uses_rccl(const emba_group* g);
 emba_ctx*   emba_group_ctx(emba_group* g, int32_t rank);
 emba_status emba_group_set_events(emba_group* g, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n);
 emba_status emba_group_upload_map(emba_group* g, const double* Gx, const double* Gy);
+/* The sliding-window run of emba.cpp:400-532 on a group: emba_seq_upload on EVERY rank's context — each holds its own copy of the sequence, also
+ * where ranks share a device; *n_kept = n / rate.  emba_group_seq_size / _seq_free: emba_seq_size of rank 0 / emba_seq_free on every rank. */
+emba_status emba_group_seq_upload(emba_group* g, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n,
+                                  int32_t sampling_rate, size_t* n_kept);
+emba_status emba_group_seq_size(const emba_group* g, size_t* n);
+emba_status emba_group_seq_free(emba_group* g);
+/* EMBA::getEventSubset (emba.cpp:473-510): emba_seq_window on rank 0 (the search is deterministic and the copies are equal: every rank's answer). */
+emba_status emba_group_seq_window(emba_group* g, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end);
+/* emba_group_set_events for the window [beg, end) of the resident sequence (emba.cpp:508-509 -> solveTimeWindow): with nb = (end - beg) / 100, rank r
+ * registers the window's batches [nb r / N, nb (r + 1) / N) (the remainder on the first ranks; the last rank's range runs to `end` and so carries the
+ * (end - beg) % 100 tail the library ignores) through emba_set_events_seq_shard — its halo is built on its own device, no event crosses the host. */
+emba_status emba_group_set_events_seq(emba_group* g, size_t beg, size_t end);
+/* The median blur of the initial map (emba.cpp:357-364): emba_median_blur3_map on every rank's replica. */
+emba_status emba_group_median_blur3_map(emba_group* g);
 /* evaluateDataError + formNormalEq[IRLS] + applyL2Reg over all ranks; n_inliers = total over the ranks, P = active pixels */
 emba_status emba_group_step(emba_group* g, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t thres_valid_pixel,
                             int32_t irls, double eta, double alpha, size_t* n_inliers, size_t* P);
