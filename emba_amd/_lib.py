@@ -63,6 +63,8 @@ SIGNATURES = {
     "emba_upload_map": (C.c_int, [C.c_void_p, _dp, _dp]),
     "emba_bind_map_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "emba_solve_normal_eq": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, _dp, _dp]),
+    "emba_solve_map_only": (C.c_int, [C.c_void_p, C.c_double, _dp]),
+    "emba_solve_poses_only": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, _dp]),
     "emba_last_solve_info": (C.c_int, [C.c_void_p, _i32p]),
     "emba_solve_shard_size": (C.c_int, [C.c_void_p, _szp]),
     "emba_solve_shard_count": (C.c_int, [C.c_void_p, C.c_int32, _szp]),
@@ -154,6 +156,8 @@ SIGNATURES = {
     "emba_group_download": (C.c_int, [C.c_void_p, _dp, _dp, _u32p, C.c_size_t, _dp, _dp]),
     "emba_group_costs": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, _dp, _dp]),
     "emba_group_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, _dp, _dp]),
+    "emba_group_solve_map_only": (C.c_int, [C.c_void_p, C.c_double, _dp]),
+    "emba_group_solve_poses_only": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, _dp]),
     "emba_group_update_map": (C.c_int, [C.c_void_p, _dp, C.c_double]),
     "emba_group_map_accept": (C.c_int, [C.c_void_p]),
     "emba_group_map_reject": (C.c_int, [C.c_void_p]),

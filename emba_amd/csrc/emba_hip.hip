@@ -1065,7 +1065,7 @@ emba_status emba_trial_reject(emba_ctx* c)
 emba_status emba_map_reject(emba_ctx* c)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->map_is_trial) return fail(c, EMBA_ERR_STATE, "no trial map (call emba_update_map first)");
+    // (no trial map: a step that moved the poses only — emba_solve_poses_only, no emba_update_map — was rejected; the map stays, the equations come back)
     c->d_Gx = c->d_Gx_cur; c->d_Gy = c->d_Gy_cur;
     c->map_is_trial = false;
     return emba_trial_reject(c);           // and the normal equations the trial evaluation set aside are current again

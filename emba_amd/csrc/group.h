@@ -174,6 +174,7 @@ struct emba_group {
     bool x1_done = false;                // the count maps of the last evaluation have been all-reduced already (emba_group_eval returned num_ev_map)
     int decl_irls = 0; double decl_eta = 0.0;   // robust cost declared for the evaluations (emba_group_set_cost)
     bool last_solve_exchanged = true;   // the last sharded solve ran the record exchange (false: every rank had its received records cached)
+    bool x2_in_ctx = false;     // every rank's context keeps the x2 of the last emba_group_solve_map_only (emba_group_update_map with x2_host == NULL)
     bool x2_on_ranks = false;   // buf[r].x2 holds the all-reduced x2 of the last emba_group_solve (emba_group_update_map with x2_host == NULL)
     RankPool pool;
     int sw_ = 0;
@@ -634,7 +635,7 @@ emba_status emba_group_get_ep(emba_group* g, double* ep_out, size_t cap, size_t*
 emba_status emba_group_form(emba_group* g, int32_t thres, int32_t irls, double eta, double alpha, size_t* n_inliers, size_t* P)
 {
     if (!g) return EMBA_ERR_INVALID_ARG;
-    g->x2_on_ranks = false;     // (what a solve of the previous equations left on the ranks)
+    g->x2_on_ranks = g->x2_in_ctx = false;     // (what a solve of the previous equations left on the ranks)
     if (g->n == 1 && !g->use_rccl) {
         emba_ctx* c = g->ctx[0];
         G_TRY(g, 0, emba_eval_finish(c, nullptr, nullptr, nullptr));
@@ -834,8 +835,8 @@ extern "C" {
 // Cholesky, x2 exchanged.  x1_host: 3K, x2_host: 2P (either may be NULL).
 emba_status emba_group_solve(emba_group* g, double lambda, int32_t fix_first_pose, double* x1_host, double* x2_host)
 {
-    if (g) g->x2_on_ranks = false;
     if (!g) return EMBA_ERR_INVALID_ARG;
+    g->x2_on_ranks = g->x2_in_ctx = false;
     if (g->n == 1 && !g->use_rccl) { G_TRY(g, 0, emba_solve_normal_eq(g->ctx[0], lambda, fix_first_pose, x1_host, x2_host)); return EMBA_OK; }
     const int n = g->n;
     const auto t_dbg0 = std::chrono::steady_clock::now(); auto t_dbg = t_dbg0;
@@ -885,7 +886,7 @@ emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_
                                 int32_t* iterations, double* error)
 {
     if (!g) return EMBA_ERR_INVALID_ARG;
-    g->x2_on_ranks = false;
+    g->x2_on_ranks = g->x2_in_ctx = false;
     if (g->n == 1 && !g->use_rccl) {
         G_TRY(g, 0, emba_solve_normal_eq_cg(g->ctx[0], lambda, fix_first_pose, max_iter, tol, x1_host, x2_host, iterations, error));
         return EMBA_OK;
@@ -955,6 +956,25 @@ emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_
     return EMBA_OK;
 }
 
+// emba_solve_map_only / emba_solve_poses_only over the group: every rank's pack is a replica after exchange 2 (emba_group_form), so each rank solves on its own
+// context — no record exchange, no collective, identical results on every rank
+emba_status emba_group_solve_map_only(emba_group* g, double lambda, double* x2_host)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    g->x2_on_ranks = g->x2_in_ctx = false;
+    g->last_solve_exchanged = false;
+    { emba_status st = gpool(g, [&](int r) { return emba_solve_map_only(g->ctx[r], lambda, r == 0 ? x2_host : nullptr); }); if (st) return st; }
+    g->x2_in_ctx = true;
+    return EMBA_OK;
+}
+emba_status emba_group_solve_poses_only(emba_group* g, double lambda, int32_t fix_first_pose, double* x1_host)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    g->x2_on_ranks = g->x2_in_ctx = false;
+    g->last_solve_exchanged = false;
+    return gpool(g, [&](int r) { return emba_solve_poses_only(g->ctx[r], lambda, fix_first_pose, r == 0 ? x1_host : nullptr); });
+}
+
 emba_status emba_group_last_solve_exchanged(const emba_group* g, int32_t* exchanged)
 {
     if (!g || !exchanged) return EMBA_ERR_INVALID_ARG;
@@ -969,6 +989,7 @@ emba_status emba_group_update_map(emba_group* g, const double* x2_host, double d
     // x2_host == NULL: every rank applies the x2 the last emba_group_solve left in ITS device memory (the all-reduced vector) — nothing crosses
     // to the host and back, and not once per rank
     if (!x2_host && (g->n > 1 || g->use_rccl)) {
+        if (g->x2_in_ctx) { for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_update_map(g->ctx[r], nullptr, damping)); return EMBA_OK; }
         if (!g->x2_on_ranks) return gfail(g, EMBA_ERR_STATE, "x2 NULL: no emba_group_solve / emba_group_solve_cg has left an x2 on the ranks");
         for (int r = 0; r < g->n; ++r) G_TRY(g, r, emba_update_map_dev(g->ctx[r], g->buf[r].x2.as<double>(), damping));
         return EMBA_OK;

@@ -1,5 +1,5 @@
-// emba_amd/csrc/solve_host.h — f1, the solvers, as host code over the kernels of solve_kernels.h: the Schur solve (emba_solve_normal_eq), its sharded form
-// (emba_solve_shard_*), conjugate gradients (emba_solve_normal_eq_cg) and their sharded session (emba_cg_shard_*).  What is plain arithmetic — sizes, a rank's
+// emba_amd/csrc/solve_host.h — f1, the solvers, as host code over the kernels of solve_kernels.h: the Schur solve (emba_solve_normal_eq), its two halves
+// (emba_solve_map_only, emba_solve_poses_only), its sharded form (emba_solve_shard_*), conjugate gradients (emba_solve_normal_eq_cg) and their sharded session (emba_cg_shard_*).  What is plain arithmetic — sizes, a rank's
 // pixel range, the shape of the block-sparse product — is decided in solve_rule.h; here are the scratch, the launches and the C ABI.
 // Part of emba_hip.hip's translation unit, included by it below the helpers this file needs from it (declared first, so that the order is stated once).
 #pragma once
@@ -438,6 +438,52 @@ extern "C" emba_status emba_solve_normal_eq(emba_ctx* c, double lambda, int32_t 
     if ((st = schur_factor_solve(c, v.S, d.lds, n, d.skip, v.x1, v.info))) return st;
     if (P && (st = launch_schur_x2(c, L, P, n, v.y, v.cf, v.x1, v.x2))) return st;
     return finish_solve(c, v.info, v.x1, n, x1_host, v.x2, P, x2_host);
+}
+
+// Mapping with known poses: with x1 = 0 the map block of the normal equations is block diagonal, x2_i = A22m_i^-1 b2_i (the Schur path's 2x2 rule, block2_*).
+// Reads the A22 | b2 rows of the pack only: no record lists, no Schur matrix, the records and the lists cache are left alone.  x2 stays on the device for
+// updateMap (keep_x2), as after a joint solve.
+extern "C" emba_status emba_solve_map_only(emba_ctx* c, double lambda, double* x2_host)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    emba_status st = equations_current(c, "solveMapOnly");
+    if (st) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((st = resolve_pending(c))) return st;
+    hipStream_t s = c->stream;
+    const size_t P = c->eq.P;
+    if (!P) { c->solve.info = 0; return keep_x2(c, nullptr, 0); }      // no active pixel: nothing to solve for, nothing written
+    auto& sv = take_solve_scratch(c);
+    if ((st = ensure<double>(c, sv.x2_or_invd, 2 * (P + 1))) || (st = ensure<int>(c, sv.info_or_sc, 16))) return st;
+    double* d_x2 = sv.x2_or_invd.as<double>();
+    int* d_info = sv.info_or_sc.as<int>();
+    HIP_TRY(c, hipMemsetAsync(d_info, 0, sizeof(int), s));
+    hipLaunchKernelGGL(emba_map_only_kernel, dim3(nblocks(P)), dim3(256), 0, s, pack_A22b2(c), lambda, (long)P, d_x2, d_info);
+    return finish_solve(c, d_info, nullptr, 0, nullptr, d_x2, P, x2_host);
+}
+
+// Pose refinement against a map that is held fixed: the pose block alone, (A11 + lambda diag A11) x1 = b1, through the Schur solve's Cholesky (the same
+// first-pose trim, the same treatment of a vanishing pivot).  Leaves no x2, and whatever x2 an earlier solve kept is no longer an answer to the last solve:
+// emba_update_map(NULL) fails until the next solve that has one.
+extern "C" emba_status emba_solve_poses_only(emba_ctx* c, double lambda, int32_t fix_first_pose, double* x1_host)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    emba_status st = equations_current(c, "solvePosesOnly");
+    if (st) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((st = resolve_pending(c))) return st;
+    hipStream_t s = c->stream;
+    const SchurDims d = schur_dims(c, fix_first_pose);
+    const int n = d.n;
+    if (n - d.skip <= 0) return fail(c, EMBA_ERR_INVALID_ARG, "nothing to solve for");
+    c->solve.x2_resident_P = (size_t)-1;
+    if ((st = ensure_schur_vectors(c, d, 0, kSchurFactor | kSchurLocal)) || (st = ensure<int>(c, c->sv.info_or_sc, 16))) return st;
+    const SchurVecs v = schur_vectors(c);
+    HIP_TRY(c, hipMemsetAsync(v.info, 0, sizeof(int), s));
+    HIP_TRY(c, hipMemsetAsync(v.S, 0, d.size() * sizeof(double), s));
+    hipLaunchKernelGGL(emba_schur_init_kernel, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, pack_A11(c), pack_b1(c), n, lambda, v.S, d.lds);
+    if ((st = schur_factor_solve(c, v.S, d.lds, n, d.skip, v.x1, v.info))) return st;
+    return finish_solve(c, v.info, v.x1, n, x1_host);
 }
 
 extern "C" emba_status emba_last_solve_info(const emba_ctx* c, int32_t* info)

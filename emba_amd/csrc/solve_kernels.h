@@ -121,6 +121,36 @@ __device__ __forceinline__ double rsqrt_nr(double d)
     return y;
 }
 
+// ---- the damped 2x2 block of one active pixel: ONE rule for every solver that inverts it -------------------------------------------
+// C C^T = A22_i + lambda diag(A22_i) (model.cpp:748) by reciprocal square roots (v_rsq_f64 + two Newton steps, rsqrt_nr): two square roots, three
+// divisions and two reciprocals per pixel were ~150 fp64 VALU instructions that every lane of a wave of the U build executed (round 5); the factor agrees
+// with sqrt / divide to an ulp or two (x2 is compared at 1e-7).  pd: the block is positive definite — where it is not the reference's A22m_i.inverse()
+// (model.cpp:750) gives inf / nan, and the caller sets bit 0 of the solve's info word.
+struct Block2 { double rs0, rs1, c00, c10, c11; bool pd; };      // C = {c00, c10, c11}; rs0 = 1 / c00, rs1 = 1 / c11
+__device__ __forceinline__ Block2 block2_factor(double xx, double xy, double yy, double lambda)
+{
+    Block2 f;
+    const double mxx = xx + lambda * xx, mxy = xy, myy = yy + lambda * yy;
+    f.rs0 = rsqrt_nr(mxx);
+    f.c00 = mxx * f.rs0; f.c10 = mxy * f.rs0;
+    const double dd = myy - f.c10 * f.c10;
+    f.rs1 = rsqrt_nr(dd);
+    f.c11 = dd * f.rs1;
+    f.pd = (mxx > 0.0) && (dd > 0.0);
+    return f;
+}
+// y = C^-1 b
+__device__ __forceinline__ void block2_forward(const Block2& f, double b0, double b1, double& y0, double& y1)
+{
+    y0 = b0 * f.rs0; y1 = (b1 - f.c10 * y0) * f.rs1;
+}
+// x = C^-T t
+__device__ __forceinline__ void block2_back(double c00, double c10, double c11, double t0, double t1, double& x0, double& x1)
+{
+    x1 = t1 / c11;
+    x0 = (t0 - c10 * x1) / c00;
+}
+
 // ---- U chunk: one wave per active pixel ---------------------------------------------------------------------------------
 // Column slices of the block-sparse SYRK: kSyrkSlicePix consecutive active pixels (ascending panorama index = a piece of a panorama row).
 // The control poses a pixel's measurements involve are those in view while the camera looks at it, so over a long window (config 2:
@@ -197,15 +227,11 @@ __global__ __launch_bounds__(64 * kBuildWaves) void emba_schur_build_kernel(Schu
     for (long i = i_first; i < p.p1; i += nwaves) {
         load_hdr(i + 2 * nwaves, h_nn);
         load_grp(h_nxt.b0, (int)(h_nxt.b1 - h_nxt.b0), 0, g_nxt);
-        const double mxx = h_cur.q0 + p.lambda * h_cur.q0, mxy = h_cur.q1, myy = h_cur.q2 + p.lambda * h_cur.q2;   // model.cpp:748
-        // 2x2 Cholesky by reciprocal square roots (v_rsq_f64 + two Newton steps, rsqrt_nr): two square roots, three divisions and two reciprocals per pixel were
-        // ~150 fp64 VALU instructions that every lane of the wave executed (round 5); the factor agrees with sqrt / divide to an ulp or two (x2 is compared at 1e-7)
-        const double rs0 = rsqrt_nr(mxx);
-        const double c00 = mxx * rs0, c10 = mxy * rs0, dd = myy - c10 * c10;
-        const double rs1 = rsqrt_nr(dd);
-        const double c11 = dd * rs1;
-        if (!(mxx > 0.0) || !(dd > 0.0)) { if (lane == 0) atomicOr(p.info, 1); }
-        const double y0 = h_cur.q3 * rs0, y1 = (h_cur.q4 - c10 * y0) * rs1;
+        const Block2 f2 = block2_factor(h_cur.q0, h_cur.q1, h_cur.q2, p.lambda);      // C C^T = A22m_i: the pixel's 2x2 Cholesky factor
+        const double rs0 = f2.rs0, rs1 = f2.rs1, c00 = f2.c00, c10 = f2.c10, c11 = f2.c11;
+        if (!f2.pd) { if (lane == 0) atomicOr(p.info, 1); }
+        double y0, y1;
+        block2_forward(f2, h_cur.q3, h_cur.q4, y0, y1);
         if (lane == 0) { const long k = h_cur.k; p.yv[2 * k] = y0; p.yv[2 * k + 1] = y1; p.cfac[3 * k] = c00; p.cfac[3 * k + 1] = c10; p.cfac[3 * k + 2] = c11; }
         const uint32_t b0 = h_cur.b0, b1 = h_cur.b1;
         unsigned long long rows_mask = 0ull;
@@ -941,12 +967,32 @@ __global__ __launch_bounds__(256) void emba_schur_x2_kernel(RecView view, const 
             const double c00 = cfac[3 * i], c10 = cfac[3 * i + 1], c11 = cfac[3 * i + 2];
             const double z0 = a0 / c00, z1 = (a1 - c10 * z0) / c11;          // z = C^-1 (A12_i^T x1)
             const double t0 = yv[2 * i] - z0, t1 = yv[2 * i + 1] - z1;
-            const double bq = t1 / c11;                                      // x2 = C^-T t
-            x2[2 * i + 1] = bq;
-            x2[2 * i] = (t0 - c10 * bq) / c00;
+            double q0, q1;
+            block2_back(c00, c10, c11, t0, t1, q0, q1);                      // x2 = C^-T t
+            x2[2 * i + 1] = q1;
+            x2[2 * i] = q0;
         }
         cb0 = nb0; cb1 = nb1;
     }
+}
+
+
+// Mapping with known poses: x2_i = (A22_i + lambda diag(A22_i))^-1 b2_i of every active pixel, from the A22 | b2 rows of the pack alone (emba_solve_map_only).
+// With the poses held fixed the map block of the normal equations is block diagonal — an event touches one panorama pixel, through a dp that does not
+// depend on the map — so no record is read.  The factor, the two substitutions and the positive-definite test are the Schur path's (block2_*): x2 = C^-T C^-1 b2.
+// One thread per pixel.
+__global__ __launch_bounds__(256) void emba_map_only_kernel(const double* __restrict__ A22b2, double lambda, long P, double* __restrict__ x2, int* __restrict__ info)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const double* q = A22b2 + 5 * i;
+    const Block2 f = block2_factor(q[0], q[1], q[2], lambda);
+    if (!f.pd) atomicOr(info, 1);
+    double y0, y1, x0, x1;
+    block2_forward(f, q[3], q[4], y0, y1);
+    block2_back(f.c00, f.c10, f.c11, y0, y1, x0, x1);
+    x2[2 * i] = x0;
+    x2[2 * i + 1] = x1;
 }
 
 

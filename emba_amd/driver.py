@@ -29,6 +29,9 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     t_start: float = 0.0
     t_end: float = 0.0
     median_blur: bool = True    # emba.cpp:357-364 is unconditional in the reference; False keeps the initial map as given
+    init_map: str = "given"     # "given": Gx, Gy are the front end's map.  "events": there is none (the reference's init_map_available = false, emba.cpp:333-355,
+                                # fills the map with noise there) — the run starts from a zero map, and the first window is first solved for the map alone from
+                                # its initial control poses (BASettings.refine = "map": well posed where the joint system with G = 0 is singular)
 
 
 @dataclass
@@ -42,6 +45,7 @@ class WindowResult:
     traj_init: LinearTrajectory     # the segment handed to solve_time_window
     result: object              # its LMResult
     setup_ms: float = float("nan")  # emba_last_setup_ms of the window's registration (device models)
+    map_init: object = None     # SequenceSettings.init_map = "events", first window only: the LMResult of the map-only pass that preceded `result`
 
 
 @dataclass
@@ -60,9 +64,17 @@ def keeps_sequence(model):
 def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm=LMSettings(), runtime_log=None, map_recorder=None, resident=True,
                  resident_sequence=None, verbose=False):
     """model: emba_amd.LEGM (or anything solve_time_window drives).  events: the whole recording (EventPacket, sorted).  pose_t [n] seconds, pose_q [n,4]
-    xyzw: the raw front-end poses (io.load_poses).  Gx, Gy: the initial map.  runtime_log / map_recorder: ONE object for the run — their counters run over
+    xyzw: the raw front-end poses (io.load_poses).  Gx, Gy: the initial map (both None with seq.init_map = "events").  runtime_log / map_recorder: ONE object for the run — their counters run over
     the windows like the reference's function statics.  resident: as in solve_time_window.  resident_sequence: keep the sequence on the device (default:
     wherever the model can); False registers every window from a host slice (emba_set_events) instead."""
+    if seq.init_map not in ("given", "events"):
+        raise ValueError(f"SequenceSettings.init_map must be 'given' or 'events', not {seq.init_map!r}")
+    if (Gx is None) != (Gy is None):
+        raise ValueError("pass both Gx and Gy, or neither")
+    if seq.init_map == "given" and Gx is None:
+        raise ValueError("no initial map: pass Gx, Gy or set SequenceSettings.init_map = 'events'")
+    if seq.init_map == "events" and ba.use_CG:
+        raise ValueError("init_map = 'events' starts with a map-only solve, which use_CG cannot do")
     if resident_sequence is None:
         resident_sequence = keeps_sequence(model)
     pose_t = np.asarray(pose_t, dtype=np.float64)
@@ -93,7 +105,9 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
     pose_latest = None
 
     # median blur of the initial map, emba.cpp:357-364
-    if seq.median_blur:
+    if seq.init_map == "events":
+        Gx, Gy = np.zeros((model.H, model.W)), np.zeros((model.H, model.W))            # (no blur: the blur of zeros is zeros)
+    elif seq.median_blur:
         if hasattr(model, "median_blur_map") and getattr(model, "has_resident_sequence", True):      # (a ShardedModel over an engine without one: numpy)
             model.upload_map(Gx, Gy)
             model.median_blur_map()
@@ -126,11 +140,16 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         seg = LinearTrajectory.from_seconds(traj_t_beg + idx_cp_beg * seq.dt_knots, seq.dt_knots, knots[idx_cp_beg:].copy())
         # :450 solveTimeWindow; the map of windows 1, 2, ... is the one the previous window left on the device
         ba_win = dataclasses.replace(ba, first_time_window=first_time_window)
+        map_init = None
+        if first_time_window and seq.init_map == "events":
+            # mapping with known poses from the zero map, at the window's initial control poses; the joint solve below then starts from the resident map
+            map_init = solve_time_window(model, seg, ev_win, Gx, Gy, dataclasses.replace(ba_win, refine="map"), lm, verbose=verbose, resident=resident)
+            Gx = Gy = None
         res = solve_time_window(model, seg, ev_win, Gx, Gy, ba_win, lm, verbose=verbose, resident=resident, runtime_log=runtime_log, map_recorder=map_recorder)
         Gx = Gy = None
         knots[idx_cp_beg:] = res.traj.knots_xyzw                                        # :453 replaceWith
         setup_ms = model.setup_info()["set_events_ms"] if hasattr(model, "setup_info") else float("nan")
-        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms))
+        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init))
         # :459-460 the latest pose: the whole trajectory 1 us before the window's end
         pose_latest = so3.spline_evaluate(knots, traj_t0_ns, traj_dt_ns, t_win_end - 1000)
         # :512-532 slideWindow

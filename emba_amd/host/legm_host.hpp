@@ -123,6 +123,20 @@ public:
     // applyL2Reg(A22_blocks, b2, active, alpha, Gx, Gy)   model.cpp:689-719 (on the device-resident blocks; call once)
     void applyL2Reg(NormalEquations& ne, double alpha) { finish(ne, alpha, false); }
 
+    // The two halves of solveNormalEq on the device-resident equations (after applyL2Reg), each with the other unknown held fixed — the reference's LEGM has
+    // neither.  solveMapOnly: mapping with known poses, x2_i = (A22_i + lambda diag A22_i)^-1 b2_i per active pixel (well posed from a zero map); x2 also
+    // stays on the device for emba_update_map(ctx(), nullptr, damping).  solvePosesOnly: (A11 + lambda diag A11) x1 = b1; leaves no x2.
+    void solveMapOnly(double lambda, std::vector<double>& x2)
+    {
+        x2.assign(2 * P_, 0.0);
+        check(emba_solve_map_only(ctx_, lambda, P_ ? x2.data() : nullptr));
+    }
+    void solvePosesOnly(double lambda, bool fix_first_pose, std::vector<double>& x1)
+    {
+        x1.assign(3 * (size_t)K_, 0.0);
+        check(emba_solve_poses_only(ctx_, lambda, fix_first_pose ? 1 : 0, x1.data()));
+    }
+
     // record_data's map images (EMBA::saveEvoData / saveOptData, solver.cpp:370-479) of the map the next evaluation would use, rendered on the device:
     // pano_height*pano_width bytes each (rgb: x3, interleaved R, G, B); nullptr skips an image (poisson: also the Poisson solve).  Writes no file.
     void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson)

@@ -144,6 +144,23 @@ public:
         x1.assign(3 * (size_t)K_, 0.0);
         check(emba_group_solve(g_, lambda, fix_first_pose ? 1 : 0, x1.data(), nullptr));
     }
+    // The two halves of that solve, each with the other unknown held fixed (emba_group_solve_map_only / _poses_only: every rank solves its replica of the pack,
+    // no collective).  solveMapOnlyResident: x1 = 0, x2 left on every rank's device for updateMapResident; solvePosesOnly: x1 to the host, no x2.
+    void solveMapOnlyResident(double lambda, std::vector<double>& x1)
+    {
+        x1.assign(3 * (size_t)K_, 0.0);
+        check(emba_group_solve_map_only(g_, lambda, nullptr));
+    }
+    void solveMapOnly(double lambda, std::vector<double>& x1, std::vector<double>& x2)
+    {
+        x1.assign(3 * (size_t)K_, 0.0); x2.assign(2 * P_, 0.0);
+        check(emba_group_solve_map_only(g_, lambda, P_ ? x2.data() : nullptr));
+    }
+    void solvePosesOnly(double lambda, bool fix_first_pose, std::vector<double>& x1)
+    {
+        x1.assign(3 * (size_t)K_, 0.0);
+        check(emba_group_solve_poses_only(g_, lambda, fix_first_pose ? 1 : 0, x1.data()));
+    }
     // both cost terms of the last evaluation, one host synchronisation (solver.cpp:88-91, 257-268)
     void costs(const std::string& cost_type, double a, double alpha, double& data_cost, double& reg_cost)
     {

@@ -48,6 +48,9 @@ struct BASettings {               // include/emba/params.h:14-61, values of laun
     double damping_factor = 1.0;
     bool first_time_window = true;      // the first control pose is held fixed (solver.cpp:156-165, 227-230)
     bool use_CG = false;                // solveNormalEqCG instead of the Schur solve (solver.cpp:190-202)
+    enum Refine { Both, Map, Poses };
+    Refine refine = Both;               // what a step moves: Both (the reference's joint solve); Map: mapping with known poses (solveMapOnly, the control poses are
+                                        // held); Poses: solvePosesOnly against the map as it is — no updateMap (it zeroes every inactive pixel), the map is never touched
 };
 
 struct LMLogEntry { int iter; double log10_lambda, cost_min, cost_new; bool accepted; size_t num_active; int cg_iter; };
@@ -157,6 +160,7 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
 {
     using clock = std::chrono::steady_clock;
     auto secs = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
+    if (ba.use_CG && ba.refine != BASettings::Both) throw std::invalid_argument("use_CG solves the joint system: it cannot be combined with refine = Map / Poses");
     const int K = traj0.num_ctrl_poses;
     std::vector<double> knots(traj0.knots_xyzw, traj0.knots_xyzw + 4 * (size_t)K), knots_new;
     auto view = [&](const std::vector<double>& k) { return TrajectoryView{k.data(), K, traj0.t0_ns, traj0.dt_ns}; };
@@ -199,7 +203,11 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
         {
             const auto t0 = clock::now();
             try {
-                if (ba.use_CG) {                                                                                // :196-202
+                if (ba.refine == BASettings::Map) {
+                    model.solveMapOnlyResident(lambda, x1);                                                     // x1 = 0; x2 stays on the device
+                } else if (ba.refine == BASettings::Poses) {
+                    model.solvePosesOnly(lambda, ba.first_time_window, x1);
+                } else if (ba.use_CG) {                                                                         // :196-202
                     std::vector<double> x2;
                     const std::pair<int, double> r = model.solveNormalEqCG(lambda, ba.first_time_window, x1, x2);
                     cg_it = r.first;
@@ -227,8 +235,8 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
             continue;
         }
         knots_new = knots;                                                                                      // :226-234
-        incrementalUpdate(knots_new, x1, ba.first_time_window);
-        { const auto t0 = clock::now(); if (!ba.use_CG) model.updateMapResident(ba.damping_factor); res.update_ms += secs(t0) * 1e3; }   // :237-240
+        if (ba.refine != BASettings::Map) incrementalUpdate(knots_new, x1, ba.first_time_window);               // (Map: the knots stay bit-identical)
+        { const auto t0 = clock::now(); if (!ba.use_CG && ba.refine != BASettings::Poses) model.updateMapResident(ba.damping_factor); res.update_ms += secs(t0) * 1e3; }   // :237-240
         const size_t n_active = model.numActivePixels();
         {
             const auto t0 = clock::now();
@@ -241,7 +249,7 @@ inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0,
         if (accepted) {                                                                                         // :299-339
             cost_has_decreased = true;
             knots.swap(knots_new);
-            model.acceptMap();
+            if (ba.refine != BASettings::Poses) model.acceptMap();      // (Poses: there is no trial map, the map is held)
             lambda /= 10;
             cost_min_old = cost_min; cost_min = cost_new; cost_data = cost_data_new; cost_reg = cost_reg_new;
             if (std::fabs(1 - cost_min / (cost_min_old + 1e-10)) < lm.tol_fun) {

@@ -334,6 +334,22 @@ class LEGM:
         self._check(self._L.emba_solve_normal_eq(self._ctx, float(lam), 1 if fix_first_pose else 0, _p(x1, _dp), None if resident_x2 else _p(x2, _dp)))
         return x1, (None if resident_x2 else x2[:2 * self._P])
 
+    def solveMapOnly(self, lam, resident_x2=False):
+        """Mapping with known poses (emba_solve_map_only): x1 = 0 and, per active pixel, x2_i = (A22_i + lam diag A22_i)^-1 b2_i — the map block of the
+        normal equations is block diagonal once the poses are held fixed, and well posed from an all-zero map.  Returns (zeros(3K), x2 [2P]);
+        resident_x2 as in solveNormalEq: x2 is returned as None and updateMap(None, damping) applies the device copy."""
+        self.last_counts()
+        x2 = None if resident_x2 else np.zeros(2 * max(self._P, 1))
+        self._check(self._L.emba_solve_map_only(self._ctx, float(lam), None if resident_x2 else _p(x2, _dp)))
+        return np.zeros(3 * self.K), (None if resident_x2 else x2[:2 * self._P])
+
+    def solvePosesOnly(self, lam, fix_first_pose=False):
+        """Pose refinement against the map as it is (emba_solve_poses_only): (A11 + lam diag A11) x1 = b1.  Returns (x1 [3K], None): there is no map
+        update, and updateMap(None, ...) raises until another solve leaves one."""
+        x1 = np.zeros(3 * self.K)
+        self._check(self._L.emba_solve_poses_only(self._ctx, float(lam), 1 if fix_first_pose else 0, _p(x1, _dp)))
+        return x1, None
+
     def last_solve_info(self):
         """bit 0: a 2x2 block was not positive definite (the solve raised EMBA_ERR_NUMERIC); bit 1: a pivot of S vanished (zero update)."""
         v = C.c_int32(0)

@@ -299,6 +299,20 @@ class ShardedLEGM:
         x1 = x2[n2 + 1:].cpu().numpy().copy()
         return x1, (x2[: 2 * self.P] if resident_x2 else x2[: 2 * self.P].cpu().numpy())
 
+    def solveMapOnly(self, lam, resident_x2=False):
+        """Mapping with known poses over all ranks, after iteration(): the pack every rank holds after exchange 2 is a replica, so each rank solves its own
+        copy (engine.solve_map_only: x2_i = (A22_i + lam diag A22_i)^-1 b2_i) — no record exchange, no collective, identical results.  A block that is not
+        positive definite is the same block on every rank: all of them raise together.  Returns (zeros(3K), x2 [2P]); resident_x2: x2 is None and stays with
+        the engine for ShardedModel.updateMap(None, ...)."""
+        self.last_solve_exchanged = False
+        x2 = self.engine.solve_map_only(lam, resident_x2)
+        return np.zeros(3 * int(self.engine.K)), x2
+
+    def solvePosesOnly(self, lam, fix_first_pose=False):
+        """(A11 + lam diag A11) x1 = b1 on every rank's replica of the pack (engine.solve_poses_only): no collective.  Returns (x1 [3K], None)."""
+        self.last_solve_exchanged = False
+        return self.engine.solve_poses_only(lam, fix_first_pose), None
+
 
     # (method of ShardedLEGM, defined below the class body's other solvers for readability)
 
@@ -429,6 +443,12 @@ class ShardedModel:
     def solveNormalEqCG(self, lam, fix_first_pose=False, resident_x2=False):
         x1, x2, _, _ = self.sh.solveNormalEqCG(lam, fix_first_pose, resident_x2=resident_x2)
         return x1, x2
+
+    def solveMapOnly(self, lam, resident_x2=False):
+        return self.sh.solveMapOnly(lam, resident_x2=resident_x2)
+
+    def solvePosesOnly(self, lam, fix_first_pose=False):
+        return self.sh.solvePosesOnly(lam, fix_first_pose)
 
     def updateMap(self, x2, damping):
         if hasattr(x2, "data_ptr"):            # the tensor of solveNormalEq(resident_x2=True)
@@ -586,6 +606,12 @@ class HipEngine:
 
     def cg_shard_end(self, x2):
         return self.m.cg_shard_end(x2.data_ptr())
+
+    def solve_map_only(self, lam, resident_x2=False):
+        return self.m.solveMapOnly(lam, resident_x2=resident_x2)[1]
+
+    def solve_poses_only(self, lam, fix_first_pose=False):
+        return self.m.solvePosesOnly(lam, fix_first_pose)[0]
 
     def solve_shard_partial(self, rank, n_ranks, recv, n_recv, lam, S):      # recv None: the rank's cached records (solve_shard_cached)
         self.m.solve_shard_partial(rank, n_ranks, recv.data_ptr() if recv is not None else None, n_recv, lam, S.data_ptr())

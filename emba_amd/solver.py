@@ -28,6 +28,8 @@ class BASettings:               # include/emba/params.h:14-61, values of launch/
     damping_factor: float = 1.0
     first_time_window: bool = True      # the first control pose is held fixed (solver.cpp:156-165, 227-230)
     use_CG: bool = False                # solveNormalEqCG instead of the Schur solve (solver.cpp:190-202; launch default false)
+    refine: str = "both"                # what a step moves: "both" (the reference's joint solve), "map" (mapping with known poses: solveMapOnly, the
+                                        # trajectory is held) or "poses" (solvePosesOnly against the map as it is: no updateMap, the map is never touched)
 
 
 @dataclass
@@ -199,8 +201,14 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
     runtime_log: a RuntimeLog — the reference's runtime_*.txt / iterations.txt records (each timed phase then ends in a host synchronisation,
     as it does in the reference's synchronous calls).
     map_recorder: a MapRecorder — record_data's map images at the reference's three points: an evo set every loop iteration (solver.cpp:173),
-    evo + opt at convergence (:332-336) and at forced termination (:360-364)."""
+    evo + opt at convergence (:332-336) and at forced termination (:360-364).
+    ba.refine = "map" / "poses": every step solves for the map alone (model.solveMapOnly; the trajectory object is carried through untouched) or for the poses
+    alone (model.solvePosesOnly; no updateMap, the map is never touched) — the rest of the loop is the same.  "map" is well posed from an all-zero map."""
     import time
+    if ba.refine not in ("both", "map", "poses"):
+        raise ValueError(f"BASettings.refine must be 'both', 'map' or 'poses', not {ba.refine!r}")
+    if ba.use_CG and ba.refine != "both":
+        raise ValueError("use_CG solves the joint system: it cannot be combined with refine = 'map' / 'poses'")
     rl = runtime_log
     mr = map_recorder
     if rl is not None:
@@ -238,7 +246,11 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
         # x2 goes from the solver to updateMap and nowhere else (solver.cpp:193-239): a device model keeps it in HBM (x2 is None here)
         rkw = dict(resident_x2=True) if getattr(model, "supports_resident_x2", False) else {}
         try:
-            if ba.use_CG:
+            if ba.refine == "map":
+                x1, x2 = timed("solveEqs", it, lambda: model.solveMapOnly(lam, **rkw))
+            elif ba.refine == "poses":
+                x1, x2 = timed("solveEqs", it, lambda: model.solvePosesOnly(lam, fix_first_pose=ba.first_time_window))
+            elif ba.use_CG:
                 res = timed("solveEqs", it, lambda: model.solveNormalEqCG(lam, fix_first_pose=ba.first_time_window, **rkw))   # :196-202
                 x1, x2 = res[:2]
                 if rl is not None and len(res) >= 4:
@@ -258,8 +270,11 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
             lam *= 10
             count_tol = 0
             continue
-        traj_new = emba_io.incremental_update(traj, x1, ba.first_time_window)        # :226-234
-        model.updateMap(x2, ba.damping_factor)                                       # :237-240 (trial map, on the device)
+        # refine = "map": the trajectory OBJECT is carried through (bit-identical knots); refine = "poses": no updateMap — it zeroes every inactive
+        # pixel, so it would change the map even with a zero update
+        traj_new = traj if ba.refine == "map" else emba_io.incremental_update(traj, x1, ba.first_time_window)        # :226-234
+        if ba.refine != "poses":
+            model.updateMap(x2, ba.damping_factor)                                   # :237-240 (trial map, on the device)
         n_act = (lambda: model.last_counts()[1]) if hasattr(model, "last_counts") else None
         cost_new = timed("obj_func", it + 1, lambda: ph.evaluate(traj_new), n_act)   # :251-268 (+ :271-291 runtime_objFuncs.txt, after iter += 1)
         cost_parts_new = ph.last_costs
@@ -271,7 +286,8 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
         if accepted:                                                                 # :299-339
             decreased = True
             traj = traj_new
-            model.acceptMap()
+            if ba.refine != "poses":         # (no trial map to accept: the map is held)
+                model.acceptMap()
             lam /= 10
             cost_min_old, cost_min = cost_min, cost_new
             cost_parts = cost_parts_new

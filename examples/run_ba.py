@@ -5,6 +5,8 @@
   python examples/run_ba.py --demo out/                       # simulate a scene, perturb the trajectory, refine, write results
   python examples/run_ba.py --demo out/ --window-size 0.3 --window-stride 0.1   # the same in sliding time windows (EMBA::Run, emba.cpp:400-532)
   python examples/run_ba.py --events ev.npz --poses init_traj.txt --map-dir init_map/ --calib calib.npz --out out/
+  python examples/run_ba.py --demo out/ --init-map events     # no front-end map: start from a zero map, solved for the map alone first
+  python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... --window-size 0.3 --window-stride 0.1
@@ -52,10 +54,16 @@ def main():
     ap.add_argument("--window-stride", type=float, help="sliding_window_stride in seconds (default: the window size)")
     ap.add_argument("--sampling-rate", type=int, default=1, help="event_sampling_rate: keep every n-th event (emba.cpp:281-304; with --window-size)")
     ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
+    ap.add_argument("--init-map", default="given", choices=["given", "events"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
+                    "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size")
+    ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
+    ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
     a = ap.parse_args()
     if a.alpha is None:
         a.alpha = 0.0 if a.demo else 5.0
+    if not a.demo and a.init_map == "given" and not a.map_dir:
+        ap.error("--map-dir is required unless --init-map events is given")
     os.makedirs(a.out, exist_ok=True)
 
     if a.demo:
@@ -74,7 +82,7 @@ def main():
         cal = np.load(a.calib)
         sw, sh = int(cal["width"]), int(cal["height"])
         lut = eio.bearing_lut_from_calibration(cal["K"], cal["D"], sw, sh)
-        Gx, Gy = eio.load_map(a.map_dir)
+        Gx, Gy = eio.load_map(a.map_dir) if a.init_map == "given" else (np.zeros((a.pano_h, 2 * a.pano_h)), np.zeros((a.pano_h, 2 * a.pano_h)))
         t, qs = eio.load_poses(a.poses)
         t_beg = a.t_beg if a.t_beg is not None else t[0]
         t_end = a.t_end if a.t_end is not None else t[-1]
@@ -86,6 +94,8 @@ def main():
         truth, C_th = None, a.C_th
 
     H, W = Gx.shape
+    if a.init_map == "events":
+        Gx, Gy = np.zeros((H, W)), np.zeros((H, W))
     world, rank, local_rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     legm = None
     if world > 1 or a.sharded:
@@ -108,7 +118,7 @@ def main():
     else:
         model = legm = LEGM(sw, sh, lut, C_th, W, H)
     ba = BASettings(use_IRLS=a.cost != "quadratic", cost_type=a.cost, eta=a.eta, thres_valid_pixel=a.thres_valid_pixel, alpha=a.alpha,
-                    damping_factor=a.damping_factor)
+                    damping_factor=a.damping_factor, refine=a.refine)
     if rank == 0:
         print(f"{events.size()} events, {traj.size()} control poses, panorama {H}x{W}" + (f", {world} rank(s) through the sharded host" if legm is not model else ""))
     t0 = time.time()
@@ -118,11 +128,13 @@ def main():
     if a.window_size:
         from emba_amd.driver import SequenceSettings, run_sequence
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
-                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur)
-        sres = run_sequence(model, events, t, qs, Gx, Gy, seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
+                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map)
+        sres = run_sequence(model, events, t, qs, *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0:
             for wr in sres.windows:
+                if wr.map_init is not None:
+                    print(f"window {wr.index}: map-only start from a zero map, {wr.map_init.iterations} LM iterations ({wr.map_init.reason}), cost {wr.map_init.cost_min:.6e}")
                 print(f"window {wr.index}: [{wr.t_beg_ns * 1e-9:.3f}, {wr.t_end_ns * 1e-9:.3f}] s, events [{wr.beg}, {wr.end}), control poses from {wr.idx_cp_beg}, "
                       f"{wr.result.iterations} LM iterations ({wr.result.reason or 'converged'}), cost {wr.result.cost_min:.6e}, set-up {wr.setup_ms:.2f} ms")
         res = sres.windows[-1].result
@@ -130,6 +142,12 @@ def main():
         if truth is not None:
             traj = LinearTrajectory(traj.knots_xyzw[:sres.traj.size()], traj.t0_ns, traj.dt_ns)
     else:
+        if a.init_map == "events":      # mapping with known poses from the zero map, then the window as usual from the resident map
+            import dataclasses
+            mres = solve_time_window(model, traj, events, Gx, Gy, dataclasses.replace(ba, refine="map"), LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True)
+            Gx = Gy = None
+            if rank == 0:
+                print(f"map-only start from a zero map: {mres.iterations} LM iterations ({mres.reason}), cost {mres.cost_min:.6e}")
         res = solve_time_window(model, traj, events, Gx, Gy, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True, runtime_log=rlog,
                                 map_recorder=mrec)
     dt = time.time() - t0

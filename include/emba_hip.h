@@ -213,7 +213,7 @@ emba_status emba_bind_map_dev(emba_ctx* ctx, const double* Gx_dev, const double*
  * the device-resident map with the active set of the last emba_form_active: trial = current; trial[active_i] += damping*x2[2i],
  * x2[2i+1]; trial[every other pixel] = 0.  From then on evaluations use the TRIAL map (pass Gx = Gy = NULL to
  * emba_eval_data_error, or call emba_eval_launch) until the caller reports the LM decision: emba_map_accept makes the trial map
- * current (solver.cpp:299-339), emba_map_reject drops it (:340-352).  x2_host: 2P doubles, or NULL: the x2 the last
+ * current (solver.cpp:299-339), emba_map_reject drops it (:340-352; with no trial map pending it is emba_trial_reject).  x2_host: 2P doubles, or NULL: the x2 the last
  * emba_solve_normal_eq[_cg] on this context left on the device (the reference hands x2 from the solver straight to updateMap,
  * solver.cpp:193-239 — 2P doubles that need not cross to the host and back).  emba_update_map_dev: x2 in device memory (a sharded
  * host's all-reduced x2), NULL as above.  emba_download_map copies the map the next evaluation would use. */
@@ -315,7 +315,21 @@ emba_status emba_median_blur3(emba_ctx* ctx, const double* src_host, int32_t h, 
  * be NULL).  Works on this context's own records: with a sharded window use emba_solve_shard_* (a pixel's A12 columns are sums over all
  * ranks' records, so the records are first re-distributed by pixel owner). */
 emba_status emba_solve_normal_eq(emba_ctx* ctx, double lambda, int32_t fix_first_pose, double* x1_host, double* x2_host);
-/* Diagnostics of the last Schur solve of this context: bit 0 = a 2x2 block was not positive definite (EMBA_ERR_NUMERIC was returned),
+/* The two halves of that solve, each with the other unknown held fixed.  Same preconditions (after emba_form_finish, no trial evaluation pending), same damping.
+ *   emba_solve_map_only    mapping with known poses, x1 = 0: the residual is linear in the map and an event touches one panorama pixel, so the map block is
+ *                          block diagonal — x2_i = (A22_i + lambda diag A22_i)^-1 b2_i per active pixel, by the Schur solve's own 2x2 rule (a block that is not
+ *                          positive definite: info bit 0, EMBA_ERR_NUMERIC).  Well posed from an all-zero map, where the joint system is singular (every pose
+ *                          Jacobian vanishes with G = 0): the way to start a run without a front-end map.  Reads the A22 | b2 rows of the pack only — no record
+ *                          lists, no Schur matrix.  x2_host: 2P doubles or NULL; x2 stays on the device for emba_update_map(ctx, NULL, damping) either way.
+ *                          P = 0: EMBA_OK, nothing written.
+ *   emba_solve_poses_only  the pose block alone, (A11 + lambda diag A11) x1 = b1, by the same Cholesky: fix_first_pose as above (x1[0..2] = 0), a vanishing pivot
+ *                          is a zero update (info bit 1), an indefinite or NaN matrix info bit 2 (EMBA_ERR_NUMERIC).  x1_host: 3K doubles.  Keeps no x2 and
+ *                          drops a kept one: emba_update_map(ctx, NULL, ...) is EMBA_ERR_STATE until another solve leaves one.  A rejected trial of such a step
+ *                          is reported with emba_map_reject / emba_trial_reject as usual (there is no trial map: only the equations come back).
+ * Neither changes what a later emba_solve_normal_eq[_cg] on the same equations returns. */
+emba_status emba_solve_map_only(emba_ctx* ctx, double lambda, double* x2_host);
+emba_status emba_solve_poses_only(emba_ctx* ctx, double lambda, int32_t fix_first_pose, double* x1_host);
+/* Diagnostics of the last Schur solve of this context (emba_solve_map_only / _poses_only included): bit 0 = a 2x2 block was not positive definite (EMBA_ERR_NUMERIC was returned),
  * bit 1 = a pivot of S vanished and its component got a zero update (what ldlt.info() == NumericalIssue is in the reference: never read). */
 emba_status emba_last_solve_info(const emba_ctx* ctx, int32_t* info);
 
@@ -567,6 +581,11 @@ emba_status emba_group_solve(emba_group* g, double lambda, int32_t fix_first_pos
  * application of the matrix and one of 2 doubles per iteration; emba_cg_shard_* below are the per-rank steps). */
 emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_pose, int32_t max_iter, double tol, double* x1_host, double* x2_host,
                                 int32_t* iterations, double* error);
+/* emba_solve_map_only / emba_solve_poses_only over the group.  After emba_group_form every rank's pack is a replica, so each rank runs the call on its own
+ * context: no record exchange, no collective, and the results are identical on every rank (x2_host / x1_host are rank 0's).  emba_group_update_map(g, NULL, ...)
+ * follows emba_group_solve_map_only as it follows emba_group_solve; emba_group_last_solve_exchanged reports 0 after either. */
+emba_status emba_group_solve_map_only(emba_group* g, double lambda, double* x2_host);
+emba_status emba_group_solve_poses_only(emba_group* g, double lambda, int32_t fix_first_pose, double* x1_host);
 /* Did the last emba_group_solve / _solve_cg run the record exchange (1), or did every rank still hold the records it had received for these equations (0)? */
 emba_status emba_group_last_solve_exchanged(const emba_group* g, int32_t* exchanged);
 /* x2_host == NULL: every rank applies the (all-reduced) x2 the last emba_group_solve / _solve_cg left in its own device memory. */
