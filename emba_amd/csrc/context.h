@@ -1,6 +1,6 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
-// Included by emba_hip.hip and group.h; host code only.
+// Included by emba_hip.hip, step_host.h, solve_host.h and group.h; host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -73,7 +73,36 @@ struct EvalState {
     bool pix_starts_valid = false;   // h_pix_starts is emba_get_inlier_pixel_starts of this evaluation (for emba_get_ep_by_pixel)
     uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
     int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
+    int use_texel = 0;            // the Hessian source this evaluation uses: 0 fly, 1 full pack, 3 rectangle (step_rule.h: hessian_source)
+    bool segpose = false;         // pixel order: this evaluation takes the pose per event from segment records (option segpose); emba_dump_state re-warps the same way
     bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
+};
+
+// What the host knows about the count map (d_count) and the per-pixel accumulator lines (d_pixacc): whether they have been cleared at all, whether the lines
+// are zero, and whether the count map holds counts or the last warp kernel's markers.  The members change through the transitions only.
+struct PixAccState {
+    bool first_use() const { return dirty_all_; }     // num_ev_map.setTo(0), model.cpp:85 (+ every accumulator line) is still to be done
+    bool lines_clean() const { return clean_; }       // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
+    bool lines_consumed() const { return consumed_; } // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
+    bool counts_raw() const { return raw_; }          // the count map holds the warp kernel's markers, not yet the counts (see ensure_counts)
+    int32_t marker() const { return mark_; }          // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
+    void bound() { dirty_all_ = true; clean_ = false; }              // another count buffer: it says nothing about which lines are dirty
+    void first_use_cleared() { dirty_all_ = false; clean_ = true; }  // both have just been zeroed
+    void marked(int32_t marker) { mark_ = marker; clean_ = false; consumed_ = false; raw_ = true; }   // a warp launch marks the touched pixels and adds into their lines
+    void not_marked() { raw_ = false; }                // an evaluation of an empty window: no warp launch
+    void materialised() { raw_ = false; }              // a dense pass turned the markers into counts
+    void consumed_by_gather() { clean_ = true; consumed_ = true; }   // the resident step's gather is the lines' only reader and zeroes them behind itself
+private:
+    bool dirty_all_ = true, clean_ = false, consumed_ = false, raw_ = false;
+    int32_t mark_ = 0;
+};
+
+// What the fused branch of form_active leaves for the Gram launch of the same equations (emba_form_accumulate).  Neither an evaluation nor a trial resets it:
+// the halves of d_fsup alternate from step to step.
+struct PostWarpState {
+    bool gather_deferred = false; emba::ActiveWriteParams gather{};   // the gather of the running step, to be issued with its Gram launch
+    int fsup_half = 0;                                                // the half of d_fsup the last launch A filled
+    void defer(const emba::ActiveWriteParams& aw) { gather = aw; gather_deferred = true; }
 };
 
 // Call options of the internal eval_launch / form_active (the extern "C" entry points pass the defaults).  irls, eta: the robust cost the per-pixel sums are
@@ -157,13 +186,9 @@ struct emba_ctx {
     double* h_cost_dev = nullptr; DevBuf d_cost_acc; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
     DevBuf d_x2;              // the x2 of the last solve on this context (solve.x2_resident_P)
     DevBuf d_count_own; int32_t* d_count = nullptr;
-    bool counts_raw = false;   // the count map holds the warp kernel's markers, not yet the counts (see ensure_counts)
-    DevBuf d_pixacc; bool pix_dirty_all = true;   // per-pixel A22/b2 accumulator lines (64 B each)
-    bool pixacc_clean = false;     // every accumulator line is zero: the last evaluation's sums were gathered AND cleared by the resident step (no prep blocks needed)
-    bool pixacc_consumed = false;  // ... so a second formNormalEq on the same evaluation rebuilds A22 | b2 from the records instead
-    int32_t count_mark = 0;        // count_marker(stamp) of the last evaluation: what its touched pixels hold in a raw count map
+    DevBuf d_pixacc;          // per-pixel A22/b2 accumulator lines (64 B each)
+    PixAccState pix;          // what the host knows about the count map and the lines
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
-    int use_texel = 0;    // what the current evaluation uses: 0 fly, 1 full pack, 3 rectangle
     DevBuf d_rect;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
     DevBuf d_blk_rect;   // per prep-block boxes
     DevBuf d_compact, d_active_bits;   // 1 bit per pixel: count >= thres of the current active set
@@ -196,15 +221,14 @@ struct emba_ctx {
     DevBuf d_cp, d_batch_u;                                                                         // control-pose index (= spline segment) and spline parameter per batch
     DevBuf d_ev_u, d_ev_seg;                                                                        // tile order: the same per entry of the device order
     DevBuf d_chunks;                                                                                // tile order: one per workgroup of the tiled warp kernel (order.n_chunks)
-    int segpose_mode = 0;      // option segpose (A/B; 0 auto = yes, 1 no, 2 yes): pixel order evaluates the pose per event from segment records (default: yes)
-    bool segpose = false;      // ... in the current evaluation
+    int segpose_mode = 0;      // option segpose (A/B; 0 auto = yes, 1 no, 2 yes): pixel order evaluates the pose per event from segment records (default: yes; ev.segpose)
     int order_mode = 0;        // option order: 0 auto, 1 pixel, 2 tile
     DevBuf d_batch_t, d_pose;   // pose table: 112 B per batch (pixel order; the tile order only uses it to predict the bins)
     DevBuf d_seg;                                             // tile order: per-segment constants the tiled kernel evaluates each event's pose from (12 doubles per segment)
     int step_gather = 2;    // option step_gather: how emba_step writes its active set + A22 | b2 rows — 0 the sweeping kernel (emba_active_write_kernel), 1 the list-driven
                             // gather as a kernel of its own, 2 (default) the list-driven gather as the head of the compact Gram kernel
     DevBuf d_seg_act;   // launch A's per-unit active lists (offsets inside the unit), n_ablk * kActivePix entries
-    bool aw_in_gram = false; emba::ActiveWriteParams aw_saved{};   // the gather of the running step, to be issued with its Gram launch (emba_form_accumulate)
+    PostWarpState post;   // the deferred gather and the flag sums a fused form_active leaves for its Gram launch
     int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
     int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
     int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
@@ -225,7 +249,7 @@ struct emba_ctx {
     int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
     int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
     DevBuf d_fblk_cnt, d_fblk_off;   // inlier-flag counts per kFlagBlk pm-order entries (win.n_fblk)
-    DevBuf d_fsup; int fsup_half = 0;                    // ... summed per kFlagSup of those by launch A (win.n_fsup; two arrays used alternately; fsup_half: the one the last launch A filled)
+    DevBuf d_fsup;                   // ... summed per kFlagSup of those by launch A (win.n_fsup; two arrays used alternately: post.fsup_half)
     DevBuf d_ep;
     double set_events_ms = 0, prepare_ms = 0;   // wall time of the last emba_set_events[_dev] / order preparation (diagnostics)
 

@@ -1,5 +1,6 @@
-// emba_amd/csrc/emba_hip.hip — context, HBM residency and the C ABI of include/emba_hip.h: the window and its order, the evaluation, the normal equations,
-// f3 and the downloads.  The context itself is context.h, the solvers (f1) are solve_host.h, the multi-GPU group is group.h: all one translation unit.
+// emba_amd/csrc/emba_hip.hip — context, HBM residency and the C ABI of include/emba_hip.h: the window and its order, the map, f3, the downloads, costs, dumps,
+// options and timers.  The context itself is context.h, the step path (the evaluation and the normal equations) is step_host.h, the solvers (f1) are solve_host.h,
+// the multi-GPU group is group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
 // (emba_set_events: pose-independent structure), launches kernels and moves bytes.
@@ -379,150 +380,7 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     return EMBA_OK;
 }
 
-// the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime: nearly every
-// slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
-bool gram_uses_tags(const emba_ctx* c, bool ep_host) { return c->use_tags && !c->order.tile_order && !ep_host; }
-
-emba_status ensure_pack(emba_ctx* c, int K)
-{
-    const size_t need = (size_t)9 * K * K + (size_t)3 * K + 5 * c->npix;
-    if (c->pack_bound) {
-        if (c->pack_cap < (size_t)9 * K * K + (size_t)3 * K)
-            return fail(c, EMBA_ERR_CAPACITY, "bound pack buffer too small for K=%d", K);
-        return EMBA_OK;
-    }
-    emba_status st = ensure<double>(c, c->d_pack_own, need);
-    if (st) return st;
-    c->d_pack = c->d_pack_own.as<double>();
-    c->pack_cap = c->d_pack_own.bytes / sizeof(double);
-    return EMBA_OK;
-}
-
-inline double* pack_A11(emba_ctx* c) { return c->d_pack; }
-inline double* pack_b1(emba_ctx* c) { return c->d_pack + (size_t)9 * c->eq.K * c->eq.K; }
-inline double* pack_A22b2(emba_ctx* c) { return c->d_pack + (size_t)9 * c->eq.K * c->eq.K + (size_t)3 * c->eq.K; }
-
 long grid8(long n) { return (n + 7) / 8 * 8; }
-
-// The pano -> compact index map is only read by the generic (weighted / external-ep) A22 path, the A12 exports and the Schur solve,
-// so it is produced when one of them asks (8 MB less traffic on every ordinary step).
-emba_status ensure_compact(emba_ctx* c)
-{
-    if (c->eq.compact_valid) return EMBA_OK;
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_compact.as<int32_t>(), 0xFF, c->npix * sizeof(int32_t), s));
-    const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
-    if (bound)
-        hipLaunchKernelGGL(emba_compact_map_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_total.as<uint32_t>() + 1, c->d_compact.as<int32_t>());
-    HIP_TRY(c, hipGetLastError());
-    c->eq.compact_valid = true;
-    return EMBA_OK;
-}
-
-// The warp kernel only MARKS touched pixels in the int32 count map (the count itself is accumulated next to the A22/b2 sums, one
-// atomic request per measurement).  The first post-warp launch of the resident step turns the markers into counts as a side
-// effect of its dense pass; whoever needs num_ev_map before that (download, exchange 1, the non-fused active-set path) calls this.
-emba_status ensure_counts(emba_ctx* c)
-{
-    if (!c->counts_raw) return EMBA_OK;
-    c->counts_raw = false;
-    c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
-    hipLaunchKernelGGL(emba_count_materialise_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix, c->count_mark);
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-// Standalone residual compaction (scan of the per-wave inlier counts, then the compaction): used when the host asks for
-// ep / counts before the active-set kernels run; otherwise emba_form_active launches it fused with its own stages.
-emba_status launch_ep_compaction(emba_ctx* c)
-{
-    if (!c->ev.ep_deferred) return EMBA_OK;
-    c->ev.ep_deferred = false;
-    hipStream_t s = c->stream;
-    if (c->win.n_pm) {
-        const uint32_t* perm = nullptr;    // (flags and residuals are stored in pm-order by both warp kernels)
-        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_flag.as<uint8_t>(), perm, (long)c->win.n_pm, c->d_fblk_cnt.as<uint32_t>());
-        // (round 6: the block counts by the three-launch scan — one 256-thread block walked all of them before: 101 us for 97 k counts at 100 M events)
-        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
-                           (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
-        c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
-        HIP_TRY(c, hipGetLastError());
-    } else {
-        HIP_TRY(c, hipMemsetAsync(c->d_total.as<uint32_t>(), 0, sizeof(uint32_t), s));
-        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[0], c->d_total.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    c->ev.inl_pending = true;
-    return EMBA_OK;
-}
-
-// Per-event inlier numbers (index into ep), for the consumers that need them: the fused post-warp launches skip them.
-emba_status ensure_inl_idx(emba_ctx* c)
-{
-    { emba_status st = launch_ep_compaction(c); if (st) return st; }
-    if (c->ev.inl_idx_valid || !c->win.n_pm) return EMBA_OK;
-    // (the fused step leaves the per-block inlier counts of this evaluation in d_fblk_cnt, not their prefix)
-    { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>()); if (st) return st; }
-    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
-                       (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
-    HIP_TRY(c, hipGetLastError());
-    c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
-    return EMBA_OK;
-}
-
-// Synchronize the stream and turn the counters that were read back asynchronously (inlier count, device error
-// word, active-pixel count) into host state.  Called only where the host really needs a value.
-// counts_only: the caller needs the inlier / active-pixel counts and nothing else from the device.  When they were produced by
-// the fused post-warp kernels, the host polls the sequence word those kernels publish after the counts instead of waiting for
-// the whole stream: it returns while the later kernels of the step (active-set gather, Gram) still run, so the next step's
-// launches queue up behind them and the GPU never idles for a host round trip.  Everything that reads device data on the
-// host goes through the full form (counts_only = false), which drains the stream.
-emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
-{
-    { emba_status st = launch_ep_compaction(c); if (st) return st; }
-    if (!c->ev.inl_pending && !c->ev.P_pending) {
-        if (c->spun && !counts_only) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; c->knots_in_flight = false; }
-        return EMBA_OK;
-    }
-    bool polled = false;
-    if (counts_only && c->ev.seq_armed && c->ev.inl_pending && c->ev.P_pending) {
-        volatile int* w = c->h_pinned + 3;                   // [3] behind the active-pixel count, [4] behind the inlier count
-        for (long spin = 0; spin < 50000000L; ++spin) {      // bounded: a faulted kernel never publishes; fall back to the stream
-            if (w[0] == c->seq && w[1] == c->seq) { polled = true; break; }
-            __builtin_ia32_pause();
-        }
-        if (polled) std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (polled) c->spun = true;
-    else { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; }
-    c->ev.seq_armed = false;
-    c->knots_in_flight = false;   // (the prep kernel that reads the pinned knot buffer precedes the post-warp kernels)
-    if (c->ev.inl_pending) {
-        c->ev.inl_pending = false;
-        if (c->h_pinned[1] & 1) return fail(c, EMBA_ERR_TIME_RANGE, "a batch midpoint lies outside the spline's knots");
-        c->n_inliers = (size_t)(uint32_t)c->h_pinned[0];
-        c->win.n_outside_tile = (size_t)((uint32_t)c->h_pinned[1] >> 1);
-        // Tile order: the bins were predicted with the trajectory of the window's first evaluation.  Events that have since left their
-        // tile (+ margin) are still handled correctly, but one by one through HBM atomics; once that is a fifth of the inliers the order
-        // is rebuilt from the CURRENT trajectory at the next evaluation (an LM loop that starts far from its solution).
-        // (not again within three evaluations: a loop whose every trial moves the events further than the margin would re-bin each time)
-        if (c->order.tile_order && c->n_inliers && c->win.n_outside_tile * 5 > c->n_inliers && c->rec_stamp - c->win.last_rebin_stamp >= 3) {
-            c->order.keys_ready = false; ++c->win.n_rebin; c->win.last_rebin_stamp = c->rec_stamp;
-        }
-        c->ev.done = true;
-    }
-    if (c->ev.P_pending) {
-        c->ev.P_pending = false;
-        c->eq.P = (size_t)(uint32_t)c->h_pinned[2];
-        c->win.P_prev = c->eq.P;
-        c->eq.pack_len = (size_t)9 * c->eq.K * c->eq.K + (size_t)3 * c->eq.K + 5 * c->eq.P;
-        if (c->eq.pack_len > c->pack_cap)
-            return fail(c, EMBA_ERR_CAPACITY, "pack buffer too small: need %zu doubles, have %zu", c->eq.pack_len, c->pack_cap);
-        c->eq.active_done = true;
-    }
-    return EMBA_OK;
-}
 
 // Device -> host into memory the CALLER owns (pageable: an Eigen vector, a cv::Mat, a numpy array).  hipMemcpy stages such a copy through the runtime's own bounce
 // buffers one chunk after the other; here the DMA of chunk i + 1 into one pinned buffer runs while the CPU copies chunk i out of the other — the two halves of the
@@ -852,6 +710,10 @@ emba_status set_events_core(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
 
 }  // namespace
 
+// evaluateDataError + formNormalEq + applyL2Reg: the step path.  Here, above the map calls and the downloads that wait for its counters — and above emba_dump_state:
+// kernel templates are emitted in the order of their first use, and the device code keeps its order when the step's warp and Gram forms come first.
+#include "step_host.h"
+
 extern "C" {
 
 emba_status emba_set_events(emba_ctx* c, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns,
@@ -1103,474 +965,6 @@ emba_status emba_get_map_active(emba_ctx* c, double* gxy_host, size_t cap_P)
     return EMBA_OK;
 }
 
-emba_status emba_bind_exchange_buffers(emba_ctx* c, int32_t* count_map_dev, double* pack_dev, size_t pack_cap)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    c->d_count = count_map_dev ? count_map_dev : c->d_count_own.as<int32_t>();
-    c->ev.count_stamp = 0;
-    c->pix_dirty_all = true;   // the new count buffer says nothing about which pixacc lines are dirty
-    c->pixacc_clean = false;
-    if (pack_dev) { c->d_pack = pack_dev; c->pack_cap = pack_cap; c->pack_bound = true; }
-    else { c->pack_bound = false; c->d_pack = c->d_pack_own.as<double>(); c->pack_cap = c->d_pack_own.bytes / sizeof(double); }
-    return EMBA_OK;
-}
-
-emba_status emba_count_compress(emba_ctx* c, uint8_t* u8_dev, int32_t cap)
-{
-    if (!c || !u8_dev || cap < 1 || cap > 255) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_compress: bad arguments") : EMBA_ERR_INVALID_ARG;
-    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
-    if (c->counts_raw) {      // markers -> this rank's counts AND their saturated bytes in one sweep (ensure_counts + the compression below)
-        c->counts_raw = false;
-        c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
-        hipLaunchKernelGGL(emba_count_materialise_compress_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix,
-                           c->count_mark, (int)cap, u8_dev);
-    } else {
-        hipLaunchKernelGGL(emba_count_compress_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, c->d_count, (long)c->npix, (int)cap, u8_dev);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-emba_status emba_count_expand(emba_ctx* c, const uint8_t* u8_dev)
-{
-    if (!c || !u8_dev) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_expand: NULL") : EMBA_ERR_INVALID_ARG;
-    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
-    c->ev.count_stamp = 0;      // (exchanged counts: no longer this context's own)
-    hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, u8_dev, (long)c->npix, c->d_count);
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
-}
-
-namespace {
-emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const EvalOpts& opt)
-{
-    if (!knots) return fail(c, EMBA_ERR_INVALID_ARG, "knots NULL");
-    if (!c->win.have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
-    if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
-    HIP_TRY(c, hipSetDevice(c->device));
-    emba_status st;
-    if ((st = ensure<double>(c, c->d_knots, (size_t)4 * K)) || (st = ensure<double>(c, c->d_seg, (size_t)kSegStride * K))) return st;
-    if ((st = prepare_order(c, knots, t0_ns, dt_ns, K))) return st;
-    if ((st = ensure_pack(c, K))) return st;
-    if (c->h_knots_cap < K) {
-        if (c->h_knots) (void)hipHostFree(c->h_knots);
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_knots, (size_t)4 * K * sizeof(double), hipHostMallocMapped));
-        HIP_TRY(c, hipHostGetDevicePointer((void**)&c->h_knots_dev, c->h_knots, 0));
-        c->h_knots_cap = K;
-    }
-    hipStream_t s = c->stream;
-    if (c->eq.accum_done && !opt.keep_alt_set) {
-        // The working record set is what the current normal equations were formed from: this evaluation (an LM trial, or simply the next
-        // step) writes the OTHER set, so that a rejection can go back to untouched equations (emba_trial_reject).
-        if (c->ev.P_pending || c->ev.inl_pending) { if ((st = resolve_pending(c, true))) return st; }
-        if (!c->alt.rec.p && (st = size_record_set(c, c->alt, c->win.n_cand))) return st;
-        std::swap(c->work, c->alt);
-        c->eq_saved = c->eq;
-        c->eq_in_alt = true;
-    }
-    c->eq.K = K;
-    c->eq.active_done = c->eq.accum_done = false;
-    begin_evaluation(c);      // (with it count_stamp: the warp kernels are about to mark the count map for a new evaluation)
-    if (c->pix_dirty_all) {   // first use of these buffers: num_ev_map.setTo(0), model.cpp:85 (+ every per-pixel accumulator line)
-        HIP_TRY(c, hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int32_t), s));
-        HIP_TRY(c, hipMemsetAsync(c->d_pixacc.as<double>(), 0, c->npix * kPixAccStride * sizeof(double), s));
-        c->pix_dirty_all = false;
-        c->pixacc_clean = true;
-    }
-    int* rect_cur = c->d_rect.as<int>();
-    // the clearing pass over count map + accumulator lines is only needed when the previous evaluation's sums are still in their lines (it was
-    // never formed by the resident step, whose gather clears them behind itself); the count map's entries are stamped and need no clearing
-    // (... and only when a warp kernel follows to re-mark it — an EMPTY window launches none, so its count map and active set would be the
-    // previous window's; the reference clears, model.cpp:85, and finds P = 0)
-    const int n_prep_blk = (c->pixacc_clean && c->win.n_sorted) ? 0 : (int)((c->npix + 1023) / 1024);
-    // Hessian source: with several events per panorama pixel (measured break-even: ~4) the full texel pack (one 48-B gather per
-    // measurement instead of an 18-load stencil) pays for itself; otherwise texels are packed only inside the bounding box of the pixels an
-    // earlier evaluation touched, and the warp kernel falls back to the stencil outside it.
-    c->use_texel = c->texel_mode == 1 ? 1 : c->texel_mode == 2 ? 0 : c->texel_mode == 3 ? 3 : (c->win.n_sorted > 4 * c->npix ? 1 : 3);
-    {   // ONE launch in front of the warp kernel: prep || pose table (or segment records) || texel rectangle — independent of each other
-        PrepPoseTexelParams q{};
-        InlineKnots kn;
-        const int nb = (int)c->win.n_batch;
-        ++c->eval_seq;
-        c->d_err = c->d_err2.as<int>() + (c->eval_seq & 1u);
-        q.count = c->d_count; q.npix = (long)c->npix; q.pixacc = c->d_pixacc.as<double>(); q.W = c->W; q.H = c->H; q.n_prep = n_prep_blk;
-        q.batch_t_ns = c->d_batch_t.as<int64_t>(); q.nb = nb; q.K = (int)K; q.t0_ns = t0_ns; q.dt_ns = dt_ns; q.pose = c->d_pose.as<double>(); q.err = c->d_err;
-        q.err_next = c->d_err2.as<int>() + ((c->eval_seq + 1u) & 1u);
-        // pixel order: per-event pose from the segment records too (warp_lane SEGPOSE; round 4, late) instead of one 112-B pose record per batch gathered by
-        // every event — 7 x 16-B gathers over 64 different lines per wave, and past ~7 M events a table that no longer fits the L2s.  Measured, same box,
-        // step time: 1 M events 101.2 -> 98.2 us, 1.5 M 150.8 -> 143.5, 10 M on 640x480 (city shape) 779 -> 714 (warp 0.60 -> 0.68 of the roofline),
-        // 10 M on 2048x4096 / K = 256 940 -> 861.  (Round 1 had measured the opposite at 1 M events, + 6 us, on a kernel that was then VALU-heavier in
-        // other places; option segpose = 1 keeps the per-batch table for comparison.)
-        c->segpose = !c->order.tile_order && (c->segpose_mode ? c->segpose_mode == 2 : true);
-        const bool seg_records = c->order.tile_order || c->segpose;
-        q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
-        q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
-        q.knots_dev = c->d_knots.as<double>(); q.knots_out = c->d_knots.as<double>();
-        q.inline_knots = (K <= kInlineKnots) ? 1 : 0;
-        if (q.inline_knots) memcpy(kn.q, knots, (size_t)4 * K * sizeof(double));       // by value in the kernel arguments: no staging copy at all
-        else {
-            if (c->knots_in_flight) HIP_TRY(c, hipStreamSynchronize(s));               // the previous copy must have consumed the pinned staging buffer
-            memcpy(c->h_knots, knots, (size_t)4 * K * sizeof(double));
-            HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), c->h_knots, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
-            c->knots_in_flight = true;   // cleared by the next host synchronisation
-        }
-        q.n_tex = (c->use_texel == 3) ? 1024 : 0;
-        q.Gx = c->d_Gx; q.Gy = c->d_Gy; q.rect = rect_cur; q.texel = c->d_texel.as<double>();
-        if (q.n_pose + q.n_tex + q.n_prep == 0) q.n_prep = 1;   // (an empty window on clean lines: block 0 still clears the next status word)
-        if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }
-        hipLaunchKernelGGL(emba_prep_pose_texel_kernel, dim3((unsigned)(q.n_pose + q.n_tex + q.n_prep)), dim3(256), 0, s, q, kn);
-    }
-    if (c->use_texel == 1)
-        hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, s, c->d_Gx, c->d_Gy, c->H, c->W,
-                           c->d_texel.as<double>());
-    if (c->win.n_sorted) {
-        WarpParams p{};
-        p.ev_pix = c->order.d_ev_pix; p.ev_batch = c->order.d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>(); p.ev_pm = c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr; p.n_sorted = (long)c->win.n_sorted;
-        p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
-        p.nblk = c->win.nblk; p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>(); p.texel = c->use_texel ? c->d_texel.as<double>() : nullptr; p.W = c->W; p.H = c->H;
-        p.rect_acc = (c->use_texel == 3) ? rect_cur : nullptr;
-        p.Gx = c->d_Gx; p.Gy = c->d_Gy; p.pixacc = c->d_pixacc.as<double>();
-        p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px;
-        p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.tag = (c->use_tags && !c->order.tile_order) ? c->work.tag.as<double>() : nullptr; p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
-        p.err = c->d_err;
-        p.ablate = c->ablate;
-        p.rec_nt = (c->order.tile_order || c->win.n_cand * (size_t)(kRecStride * 8) > ((size_t)144 << 20)) ? 1 : 0;      // (1 M slots = 128 MB: kept in the Infinity Cache for the Gram kernel)
-        p.irls = opt.irls; p.eta = opt.eta;
-        p.stamp = ++c->rec_stamp; c->work.stamp = p.stamp;
-        p.marker = c->count_mark = count_marker(p.stamp);
-        c->pixacc_clean = false; c->pixacc_consumed = false;
-        p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->order.n_chunks; p.chunks_linear = c->order.chunks_lpt ? 1 : 0;
-        if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
-        if (c->order.tile_order) launch_warp_tiled(c->order.tile_shape, dim3((unsigned)grid8(c->order.n_chunks)), s, p);
-        else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
-        else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
-        if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[1], s)); c->kt_warp_valid = true; c->kt_valid[c->kt_slot][0] = true; }
-        c->counts_raw = true;
-    } else {
-        c->counts_raw = false;
-    }
-    HIP_TRY(c, hipGetLastError());
-    c->ev.acc_irls = opt.irls; c->ev.acc_eta = opt.eta;
-    c->ev.launched = true;
-    return EMBA_OK;
-}
-}  // namespace
-
-emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
-{   // (weighted with the cost declared with emba_set_cost)
-    return c ? eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{c->cost_irls, c->cost_eta, false}) : EMBA_ERR_INVALID_ARG;
-}
-
-emba_status emba_eval_finish(emba_ctx* c, double* ep_out, size_t* n_inliers, int32_t* num_ev_map_out)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->ev.ep_deferred = true;
-    if (!ep_out && !n_inliers && !num_ev_map_out) return EMBA_OK;   // fully asynchronous: the compaction rides with the next phase
-    emba_status st = resolve_pending(c);
-    if (st) return st;
-    if (n_inliers) *n_inliers = c->n_inliers;
-    if (ep_out && c->n_inliers) { HIP_TRY(c, hipStreamSynchronize(c->stream)); if ((st = d2h_pageable(c, ep_out, c->d_ep.as<double>(), c->n_inliers * sizeof(double)))) return st; }
-    if (num_ev_map_out) {
-        { emba_status st0 = ensure_counts(c); if (st0) return st0; }
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if ((st = d2h_pageable(c, num_ev_map_out, c->d_count, c->npix * sizeof(int32_t)))) return st;
-    }
-    return EMBA_OK;
-}
-
-emba_status emba_eval_data_error(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const double* Gx,
-                                 const double* Gy, int32_t eval_deriv, double* ep_out, size_t* n_inliers,
-                                 int32_t* num_ev_map_out)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!eval_deriv) return fail(c, EMBA_ERR_INVALID_ARG, "eval_deriv=false is never used by the reference (solver.cpp:75,251) and is not provided");
-    emba_status st;
-    if (Gx || Gy) { if ((st = emba_upload_map(c, Gx, Gy))) return st; }   // both NULL: evaluate on the resident (current or trial) map
-    if ((st = emba_eval_launch(c, knots, K, t0_ns, dt_ns))) return st;
-    return emba_eval_finish(c, ep_out, n_inliers, num_ev_map_out);
-}
-
-namespace {
-emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len, const FormOpts& opt)
-{
-    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "formNormalEq needs the state of evaluateDataError (solver.cpp:99-102)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const long npix = (long)c->npix;
-    const long head = (long)9 * c->eq.K * c->eq.K + (long)3 * c->eq.K;
-    ActiveWriteParams aw{};
-    aw.count = c->d_count; aw.npix = npix; aw.thres = thres; aw.blk_off = c->d_ablk_off.as<uint32_t>(); aw.compact = nullptr; aw.active_idx = c->d_active.as<uint32_t>(); aw.pixacc = c->d_pixacc.as<double>();
-    aw.A22b2 = pack_A22b2(c); aw.pack_head = c->d_pack; aw.head_len = head; aw.alpha = opt.fused_alpha; aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
-    aw.active_bits = c->d_active_bits.as<uint8_t>(); aw.max_P = (long)((c->pack_cap - (size_t)head) / 5); aw.n_ablk = (long)c->n_ablk; aw.ablate = c->ablate;
-    // the resident step cleared this evaluation's per-pixel sums behind its gather: a second formNormalEq on the same evaluation takes A22 | b2
-    // from the records (the generic path of emba_form_accumulate), and its L2 term from emba_form_finish
-    c->eq.force_generic_a22 = c->pixacc_consumed;
-    if (c->eq.force_generic_a22) { aw.A22b2 = nullptr; aw.alpha = 0.0; }
-    // a sharded window's rank in resident-step mode (emba_step_form_active): activity from the exchanged byte counts, which launch A reads beside this rank's
-    // own counts — where the list-driven gather cannot be used the bytes are expanded into the count map first and the sweeping forms below see global counts
-    const bool lists_ok = opt.consume && c->step_gather && !c->eq.force_generic_a22 && (long)c->n_ablk <= kGatherMaxUnits && c->win.n_cand &&
-                          (c->step_gather == 3 || !c->order.tile_order || c->win.n_cand <= 3500000);
-    const uint8_t* global_u8 = opt.global_u8;
-    if (global_u8 && !(lists_ok && c->ev.ep_deferred && c->win.n_sorted && !c->counts_raw)) {
-        { emba_status st0 = ensure_counts(c); if (st0) return st0; }
-        c->ev.count_stamp = 0;
-        hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, s, global_u8, npix, c->d_count);
-        global_u8 = nullptr;      // (the count map holds them now)
-    }
-    if (c->ev.ep_deferred && c->win.n_sorted) {
-        c->ev.ep_deferred = false;
-        PostWarpParams q{};
-        q.count = c->d_count; q.npix = npix; q.thres = thres; q.ablk_cnt = c->d_ablk_cnt.as<uint32_t>(); q.ablk_off = c->d_ablk_off.as<uint32_t>(); q.n_ablk = (long)c->n_ablk;
-        q.total_P = c->d_total.as<uint32_t>() + 1; q.total_P_host = c->h_pinned_dev + 2;
-        q.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); q.fblk_off = c->d_fblk_off.as<uint32_t>(); q.n_fblk = c->win.n_fblk; q.perm = nullptr; q.n_pm = (long)c->win.n_pm;
-        q.total_inl = c->d_total.as<uint32_t>(); q.total_inl_host = c->h_pinned_dev;
-        q.err_dev = c->d_err; q.err_host = c->h_pinned_dev + 1;
-        q.e_sorted = c->d_e_sorted.as<double>(); q.flag = c->d_flag.as<uint8_t>(); q.ep = c->d_ep.as<double>(); q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
-        q.seq = ++c->seq; q.seq_host = c->h_pinned_dev + 3; c->ev.seq_armed = true;
-        if (c->counts_raw) { q.raw_count = c->d_count; q.pixacc = c->d_pixacc.as<double>(); q.marker = c->count_mark; c->counts_raw = false;      // launch A turns the markers into counts
-                             c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u; }
-        const bool consume = opt.consume && c->step_fast && !c->eq.force_generic_a22;    // this gather is the per-pixel sums' only reader: lines are zeroed behind it
-        // list-driven gather: it rides in the head of the Gram kernel (as a kernel of its own it is no faster than the sweeping write: 109.6 vs
-        // 108.5 us per step at 1 M events; option step_gather = 1 forces that form for comparison, 0 the sweeping kernel)
-        // Where it paid as a HEAD in front of the stream (same box, step time with the head vs with the sweeping kernel): 1 M events 101.2 vs 105.7 us,
-        // the 1 M-event shard of the 8 M-event stream 121.8 vs 127, scene-driven 1.17 M events 121 vs 135 — but 1.5 M events 161 vs 154, 3 M (tile order)
-        // 289 vs 281, 10 M 833 vs 817: with more active pixels per block the head's dependent trips grew past what the launch saved.
-        q.global_u8 = global_u8;
-        const bool lists = lists_ok && (q.raw_count || q.global_u8);      // (step_gather = 3: everywhere, for comparison)
-        // (round 4, late: the gather is now the work of 4 of a Gram block's 16 waves BESIDE the record stream, not a head in front of it: step time
-        // with it / with the sweeping launch — 1 M 92.6 / 96.4 us, 1.5 M 134.7 / 143.8, 2 M (tile order) 193.4 / 208.5, 3 M 274.4 / 280.9, 10 M on
-        // 640x480 (pixel order) 612.5 / 626.1, on 2048x4096 766.7 / 776.3; but 5 M (tile) 436.0 / 432.2, 40 M 3137 / 3014: a bandwidth-bound stream
-        // misses the four waves more than it gains from the launch — pixel order everywhere, tile order up to 3.5 M candidates)
-        if (consume) { aw.clear_pixacc = c->d_pixacc.as<double>(); c->pixacc_clean = true; c->pixacc_consumed = true; }
-        if (lists) { q.seg = c->d_seg_act.as<uint16_t>(); aw.seg = c->d_seg_act.as<uint16_t>(); if (consume) q.clear_inactive = c->d_pixacc.as<double>(); }
-        // launch A: {active counts (+ markers -> counts, activity bits, cleared A11 | b1) || inlier-flag counts}; launch B: the active-set write,
-        // whose blocks take their own prefix over launch A's per-block counts and whose last block publishes P, the inlier total, the status
-        // word and the sequence words the host polls.  (Nothing on the device reads the compacted residual vector `ep` — costs, Gram and solvers
-        // work from the records and the per-event residuals — so it is produced when the host asks for it: resolve_pending / ensure_inl_idx
-        // run the standalone compaction from the per-block flag counts left here.  100 M events: 0.65 -> 0.2 ms.)
-        // Tried and dropped (round 3, 1 M events): both launches as ONE kernel with the per-block counts published through flags (look-back,
-        // and "sum every predecessor"): 38-270 us against 6.3 + 11.2 — the eight XCDs' L2s are not coherent with each other, so every flag is a
-        // round trip to the memory side (and a release / acquire pair writes back / invalidates a whole L2); a kernel boundary is cheaper.
-        c->fsup_half ^= 1;
-        q.fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->win.n_fsup * kFlagSupStride; q.fsup_next = c->d_fsup.as<uint32_t>() + (size_t)(c->fsup_half ^ 1) * c->win.n_fsup * kFlagSupStride; q.n_sup = c->win.n_fsup;
-        q.active_bits = c->d_active_bits.as<uint8_t>(); q.pack_head = c->d_pack; q.head_len = head; aw.bits_head_done = 1;
-        q.blk_rect = c->d_blk_rect.as<int>(); q.W = c->W; aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the texel rectangle of the NEXT evaluation
-        hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->win.n_fblk)), dim3(256), 0, s, q);
-        aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->win.n_fblk; aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
-        aw.total_inl = q.total_inl; aw.total_inl_host = q.total_inl_host; aw.err_dev = q.err_dev; aw.err_host = q.err_host; aw.seq = q.seq; aw.seq_host = q.seq_host;
-        // (round 4, measured and dropped: this write on a side stream beside the Gram kernel — both only depend on launch A — costs more than it
-        // hides: each cross-stream event edge opens a 7-12 us bubble on this stack, 114.5 vs 107.6 us per step)
-        // The resident one-GPU step (lists): the write is list-driven and balanced (active_gather_block) and rides in the head of the compact Gram
-        // kernel — emba_form_accumulate issues it — or runs as a kernel of its own (step_gather = 1, or where the Gram kernel is another form)
-        c->aw_in_gram = false;
-        // the residual vector ep of this evaluation: compacted by tail blocks of the Gram launch that follows (kernels.h: ep_tail_block) — launch A has just
-        // left the per-block inlier-flag counts they need
-        c->ev.ep_in_gram = opt.wants_ep && c->step_ep != 2 && c->win.n_cand;
-        c->ev.ep_after_gram = opt.wants_ep && !c->ev.ep_in_gram;
-        if (lists && c->step_gather >= 2) { c->aw_saved = aw; c->aw_in_gram = true; }
-        else if (lists) hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, aw);
-        else hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
-        c->ev.inl_pending = true;
-    } else {
-        { emba_status st0 = launch_ep_compaction(c); if (st0) return st0; }
-        { emba_status st0 = ensure_counts(c); if (st0) return st0; }
-        hipLaunchKernelGGL(emba_active_count_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, c->d_count, npix, (int)thres, c->d_ablk_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(emba_scan_kernel, dim3(1), dim3(256), 0, s, c->d_ablk_cnt.as<uint32_t>(), c->d_ablk_off.as<uint32_t>(), (long)c->n_ablk, c->d_total.as<uint32_t>() + 1,
-                           c->h_pinned_dev + 2, (const int*)nullptr, (int*)nullptr);
-        hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
-    }
-    HIP_TRY(c, hipGetLastError());
-    c->eq.compact_valid = false;
-    c->eq.l2_fused = (aw.alpha != 0.0);
-    c->eq.thres = thres;
-    c->eq_in_alt = false;   // new equations are being formed from the working set: the other set's are obsolete
-    c->ev.P_pending = true; c->eq.active_done = false; c->eq.accum_done = false;
-    c->eq.finish_done = false;          // (the head of the pack has just been cleared: what a solve would read is no set of equations — found by the call-order pair test)
-    c->solve.x2_resident_P = (size_t)-1;   // (a solve of the PREVIOUS equations may have left its x2 on the device)
-    c->solve.invalidate();                 // (new active set)
-    if (!P && !pack_len) return EMBA_OK;   // asynchronous: P is read from device memory by the kernels that need it
-    emba_status st = resolve_pending(c, true);   // counts only: a sharded host sizes exchange 2 from P while the gather still runs
-    if (st) return st;
-    if (P) *P = c->eq.P;
-    if (pack_len) *pack_len = c->eq.pack_len;
-    return EMBA_OK;
-}
-}  // namespace
-
-emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len) { return c ? form_active(c, thres, P, pack_len, FormOpts{}) : EMBA_ERR_INVALID_ARG; }
-
-emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irls, double eta)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eq.active_done && !c->ev.P_pending) return fail(c, EMBA_ERR_STATE, "emba_form_active has not been called");
-    if (c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "these equations have been accumulated already: A11 | b1 are cleared by emba_form_active only (a second pass would add the sums again)");
-    if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    // the per-pixel sums of the evaluation already carry this cost's weights (emba_set_cost / emba_step)?  Then they ARE A22/b2.
-    const bool acc_matches = (irls == c->ev.acc_irls) && (irls == 0 || eta == c->ev.acc_eta);
-    const bool generic_a22 = !acc_matches || (ep_host != nullptr) || c->eq.force_generic_a22;
-    if (c->aw_in_gram && (generic_a22 || !c->win.n_cand)) {   // (not what emba_step does: the deferred gather as a launch of its own after all)
-        hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, s, c->aw_saved);
-        c->aw_in_gram = false;
-    }
-    if (generic_a22) { emba_status st = resolve_pending(c); if (st) return st; }   // needs n_inliers / P on the host (rare path)
-    if (ep_host && c->n_inliers) {
-        { emba_status st = ensure_inl_idx(c); if (st) return st; }
-        HIP_TRY(c, hipMemcpyAsync(c->d_ep.as<double>(), ep_host, c->n_inliers * sizeof(double), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->win.n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep.as<double>(), c->d_flag.as<uint8_t>(),
-                           c->d_inl_idx.as<int32_t>(), c->d_ev_slot.as<uint32_t>(), c->order.d_ev_pix, c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr, (long)c->win.n_sorted, c->work.rec.as<double>(), c->d_e_sorted.as<double>());
-    }
-    // A11 = Zero, b1 = Zero (model.cpp:357-361).  A22/b2 of the active pixels were gathered from the per-pixel
-    // accumulator by emba_form_active (quadratic cost, device-resident residuals); with IRLS weights or a
-    // caller-supplied ep they are rebuilt from the records instead.
-    // (the head of the pack, A11 | b1, was zeroed by emba_form_active's write kernel)
-    c->eq.irls = irls; c->eq.eta = eta;
-    if (generic_a22 && c->eq.P) {
-        { emba_status st = ensure_compact(c); if (st) return st; }
-        HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->eq.P * sizeof(double), s));
-        if (c->win.n_cand)
-            hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
-                               (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, irls, eta, pack_A22b2(c), c->work.stamp);
-    }
-    if (c->win.n_cand) {
-        GramParams p{};
-        p.rec = c->work.rec.as<double>(); p.slot_key = c->d_slot_key.as<uint32_t>(); p.n_slots = (long)c->win.n_cand; p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits.as<uint8_t>());
-        p.irls = irls; p.eta = eta; p.stamp = c->work.stamp; p.A11 = pack_A11(c); p.b1 = pack_b1(c);
-        // the tag stream pays where slots are dead (pixel order: about half of them at the BASELINE workload); in the tile order (dense regime:
-        // nearly every slot is live) the warp kernel's scattered 8-B tag stores cost more than the Gram kernel saves (40 M events: +370 vs -180 us)
-        p.tag = gram_uses_tags(c, ep_host != nullptr) ? c->work.tag.as<double>() : nullptr;
-        p.dim = 3 * c->eq.K;
-        p.ablate = c->ablate;
-        // slots per wave: whole rounds of one 16-wave block per CU with equal shares (1 M events: one round of 236 slots per wave),
-        // between kGramChunkMin and kGramChunk slots
-        // Sparse slot streams (pixel order on a large panorama: most inliers fall on pixels that stay inactive): stages of 128 tags, only the live records fetched (180 -> 78 us at 10 M events on 2048 x 4096, K = 256).
-        // Which form: option gram_sparse (0 / 1), else by the LAST formed equations of this context — at least thres records per active pixel are live, and where
-        // 4 thres P is still below a quarter of the slots the stream is sparse (BASELINE: 5 x 68.6 k of 1 M slots = 0.34 -> dense; 10 M events on 2048 x 4096: 0.055)
-        const bool sparse = p.tag && (c->opt_gram_sparse == 1 || (c->opt_gram_sparse < 0 && c->win.P_prev > 0 && c->win.n_cand >= (2u << 20) && 16ull * (size_t)c->eq.thres * c->win.P_prev < c->win.n_cand));
-        // (sparse form: up to four times the slots per wave — a wave's pipeline takes three stages to fill; option gram_sparse_chunk: 1 ... 8, no difference from 2 up)
-        const long chunk_cap = sparse ? (long)c->opt_gram_sparse_chunk * kGramChunk : kGramChunk;
-        const long per_round = (long)c->n_cu * (kGramBlock / 64);
-        const long rounds = std::max<long>(1, ((long)c->win.n_cand + per_round * chunk_cap - 1) / (per_round * chunk_cap));
-        long chunk = ((long)c->win.n_cand + per_round * rounds - 1) / (per_round * rounds);
-        chunk = (chunk + 7) & ~7L;
-        chunk = std::min<long>(std::max<long>(chunk, kGramChunkMin), chunk_cap);
-        p.chunk = (int)chunk;
-        const long waves = ((long)c->win.n_cand + chunk - 1) / chunk;
-        if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[2], s));
-        constexpr long wpb = kGramBlock / 64;
-        unsigned grid = (unsigned)((waves + wpb - 1) / wpb);
-        p.n_gram_blocks = (int)grid;
-        const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->win.n_pm;
-        if (ep_tail) {
-            p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>(); p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_pm = (long)c->win.n_pm; p.ep_n_fblk = c->win.n_fblk;
-            p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->fsup_half * c->win.n_fsup * kFlagSupStride;
-            grid += (unsigned)((c->win.n_pm + kEpTailBlk - 1) / kEpTailBlk);
-        }
-        c->ev.ep_in_gram = false;
-        const ActiveWriteParams aw = c->aw_in_gram ? c->aw_saved : ActiveWriteParams{};
-        {   // gather waves per Gram block (option gather_waves = 1|2|4 overrides)
-            const int gw_env = c->opt_gather_waves;
-            // (measured, scripts/r04_exp15.sh: with ONE gather wave the gather outlasts the stream at every size — Gram kernel 57 vs 36 us at 1 M events,
-            // 1288 vs 1047 at 40 M —, two are within noise of four or of the sweeping launch from 5 M events up: four wherever the lists are used)
-            p.gather_waves = (gw_env == 1 || gw_env == 2 || gw_env == 4) ? gw_env : 4;
-        }
-        if (p.tag && sparse) {
-            if (c->aw_in_gram) hipLaunchKernelGGL((emba_gram_kernel<true, true, true>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-            else hipLaunchKernelGGL((emba_gram_kernel<true, false, true>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-        } else if (p.tag) {
-            if (c->aw_in_gram) hipLaunchKernelGGL((emba_gram_kernel<true, true>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-            else hipLaunchKernelGGL((emba_gram_kernel<true, false>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-        } else {
-            if (c->aw_in_gram) hipLaunchKernelGGL((emba_gram_kernel<false, true>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-            else hipLaunchKernelGGL((emba_gram_kernel<false, false>), dim3(grid), dim3(kGramBlock), 0, s, p, aw);
-        }
-        c->aw_in_gram = false;
-        if (ep_tail) c->ev.ep_valid = true;
-        if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }
-    }
-    if (c->ev.ep_after_gram && !ep_host && c->win.n_pm) {      // option step_ep = 2 (A/B): the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
-        { emba_status st = dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>() + 2); if (st) return st; }
-        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->win.n_pm,
-                           c->d_ep.as<double>(), (int32_t*)nullptr);
-        c->ev.ep_valid = true;
-    }
-    c->ev.ep_after_gram = false;
-    HIP_TRY(c, hipGetLastError());
-    c->eq.accum_done = true; c->eq.finish_done = false;
-    return EMBA_OK;
-}
-
-emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1, uint32_t* active_idx, size_t cap_P, double* A22,
-                             double* b2, double* A12_dense)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "emba_form_accumulate has not been called");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (alpha != 0.0 && !c->eq.l2_fused) {   // (l2_fused doubles as "already applied to this set of blocks": applyL2Reg acts once)
-        c->eq.l2_fused = true;
-        // P may still be unresolved on the host: the kernel reads it from device memory, the grid covers the bound
-        const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
-        if (bound)
-            hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), c->d_active.as<uint32_t>(),
-                               c->d_total.as<uint32_t>() + 1, alpha, c->d_Gx, c->d_Gy);
-    }
-    HIP_TRY(c, hipGetLastError());
-    const bool download = A11 || b1 || active_idx || A22 || b2 || A12_dense;
-    emba_status st = resolve_pending(c, !download);   // the step's one host wait when nothing was resolved earlier
-    if (st) return st;
-    if (!download) { c->eq.finish_done = true; return EMBA_OK; }
-    const size_t P = c->eq.P;
-    const int dim = 3 * c->eq.K;
-    if ((A22 || b2 || A12_dense || active_idx) && cap_P < P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, P);
-    if (A11) HIP_TRY(c, hipMemcpyAsync(A11, pack_A11(c), (size_t)dim * dim * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (b1) HIP_TRY(c, hipMemcpyAsync(b1, pack_b1(c), (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (active_idx && P) HIP_TRY(c, hipMemcpyAsync(active_idx, c->d_active.as<uint32_t>(), P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    DevBuf A12_tmp;
-    if ((A22 || b2) && P) {
-        // (round 6) the unpacked blocks sit in a workspace (a hipMalloc / hipFree pair per call until then) and travel through the pinned pipeline + the copy helpers
-        // like ep: the drop-in downloads them twice per accepted step (formNormalEq, applyL2Reg), 23 MB each at config 2's shape
-        if ((st = ensure<double>(c, c->dl.A22b2, 6 * P))) return st;
-        double *d_A22 = c->dl.A22b2.as<double>(), *d_b2 = d_A22 + 4 * P;
-        hipLaunchKernelGGL(emba_unpack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), (long)P, d_A22, d_b2);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (A22 && (st = d2h_pageable(c, A22, d_A22, 4 * P * sizeof(double)))) return st;
-        if (b2 && (st = d2h_pageable(c, b2, d_b2, 2 * P * sizeof(double)))) return st;
-    }
-    if (A12_dense && P) {
-        if ((st = ensure_compact(c))) return st;
-        const size_t n12 = (size_t)dim * 2 * P;
-        if ((st = ensure<double>(c, A12_tmp, n12))) return st;
-        double* d_A12 = A12_tmp.as<double>();
-        (void)hipMemsetAsync(d_A12, 0, n12 * sizeof(double), s);
-        if (c->win.n_cand)
-            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
-                               (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, dim, d_A12, c->work.stamp);
-        (void)hipMemcpyAsync(A12_dense, d_A12, n12 * sizeof(double), hipMemcpyDeviceToHost, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    c->knots_in_flight = false;
-    if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "form_finish: %s", hipGetErrorString(e));
-    HIP_TRY(c, hipGetLastError());
-    c->eq.finish_done = true;
-    return EMBA_OK;
-}
-
-emba_status emba_form_normal_eq(emba_ctx* c, const double* ep, int32_t thres, int32_t irls, double eta, double alpha, double* A11,
-                                double* b1, size_t* P, uint32_t* active_idx, size_t cap_P, double* A22, double* b2, double* A12_dense)
-{
-    emba_status st;
-    size_t Pl = 0, pl = 0;
-    if ((st = emba_form_active(c, thres, &Pl, &pl))) return st;
-    if (P) *P = Pl;
-    if ((st = emba_form_accumulate(c, ep, irls, eta))) return st;
-    return emba_form_finish(c, alpha, A11, b1, active_idx, cap_P, A22, b2, A12_dense);
-}
-
 emba_status emba_get_A12_sparse(emba_ctx* c, int32_t* cp_c, int32_t* cp_p, int32_t* pix, double* w, double* jc, double* jp, double* dp)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
@@ -1820,7 +1214,7 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     p.cy = c->cy; p.C_th = c->C_th; p.outlier_px = c->outlier_px; p.count = c->d_count; p.rec = c->work.rec.as<double>(); p.e_sorted = c->d_e_sorted.as<double>();
     p.flag = c->d_flag.as<uint8_t>(); p.d_pm = d_pm; p.d_D = d_D; p.d_dp = d_dp; p.d_Gpm = d_G; p.d_temp = d_t; p.d_pm_int = d_pi;
     if (c->order.tile_order) hipLaunchKernelGGL((emba_warp_residual_kernel<true, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
-    else if (c->segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<true, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);   // (the last evaluation left segment records, not a pose table)
+    else if (c->ev.segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<true, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);   // (the last evaluation left segment records, not a pose table)
     else hipLaunchKernelGGL((emba_warp_residual_kernel<true, false>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
     std::vector<double> h_pm(w_pm ? 2 * ns : 0), h_D(w_D ? 12 * ns : 0), h_dp(w_dp ? 2 * ns : 0), h_G(w_G ? 2 * ns : 0), h_t(w_t ? 2 * ns : 0);
     std::vector<uint16_t> h_cp(cp_idx ? c->win.n_batch : 0);
@@ -1867,54 +1261,6 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
         if (Gpm && h_flag[f]) { Gpm[2 * k] = h_G[2 * i]; Gpm[2 * k + 1] = h_G[2 * i + 1]; }
         if (temp && h_flag[f]) { temp[2 * k] = h_t[2 * i]; temp[2 * k + 1] = h_t[2 * i + 1]; }
     }
-    return EMBA_OK;
-}
-
-emba_status emba_step(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t thres, int32_t irls, double eta,
-                      double alpha, size_t* n_inliers, size_t* P)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
-    emba_status st;
-    // the evaluation weights its per-pixel sums with THIS step's cost (whatever emba_set_cost declared for other callers)
-    if ((st = eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{irls, irls ? eta : 0.0, c->step_one_set != 0}))) return st;
-    if ((st = emba_eval_finish(c, nullptr, nullptr, nullptr))) return st;
-    FormOpts fo;
-    fo.fused_alpha = alpha;               // A22/b2 come from the accumulator, so applyL2Reg rides along with the gather
-    fo.consume = (c->step_fast != 0);     // ... which is their only reader: it zeroes the lines behind itself and the next evaluation needs no clearing pass
-    fo.wants_ep = (c->step_ep != 0);      // the step returns what evaluateDataError returns: ep, compacted in the tail of its Gram launch
-    if ((st = form_active(c, thres, nullptr, nullptr, fo))) return st;
-    if ((st = emba_form_accumulate(c, nullptr, irls, eta))) return st;
-    if ((st = emba_form_finish(c, alpha, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr))) return st;
-    if (n_inliers) *n_inliers = c->n_inliers;
-    if (P) *P = c->eq.P;
-    return EMBA_OK;
-}
-
-emba_status emba_step_form_active(emba_ctx* c, int32_t thres, const uint8_t* global_counts_u8_dev)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
-    emba_status st;
-    if ((st = emba_eval_finish(c, nullptr, nullptr, nullptr))) return st;
-    FormOpts fo;
-    fo.consume = (c->step_fast != 0);
-    fo.global_u8 = global_counts_u8_dev;
-    return form_active(c, thres, nullptr, nullptr, fo);
-}
-
-emba_status emba_count_map_ready(emba_ctx* c)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    return ensure_counts(c);
-}
-
-emba_status emba_set_cost(emba_ctx* c, int32_t irls, double eta)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
-    c->cost_irls = irls; c->cost_eta = irls ? eta : 0.0;
     return EMBA_OK;
 }
 

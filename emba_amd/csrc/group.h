@@ -311,7 +311,7 @@ emba_status group_alltoall(emba_group* g, double* const* send, double* const* re
 
 emba_status group_ensure_buffers(emba_group* g, int K)
 {
-    const size_t need = (size_t)9 * K * K + (size_t)3 * K + 5 * g->npix;
+    const size_t need = PackLayout(K).need(g->npix);
     for (int r = 0; r < g->n; ++r) {
         auto& b = g->buf[r];
         if (b.pack.bytes >= need * sizeof(double)) continue;

@@ -1,0 +1,798 @@
+// emba_amd/csrc/step_host.h — the step path, evaluateDataError + formNormalEq + applyL2Reg, as host code over the kernels of kernels.h: the evaluation
+// (emba_eval_launch / _finish), the active set (emba_form_active), the Gram launch (emba_form_accumulate), emba_form_finish, the resident emba_step, the count-map
+// exchange of a sharded window and the counters an evaluation leaves pending.  What is plain arithmetic — the pack's layout, which source, form and plan a
+// launch takes — is decided in step_rule.h; here are the buffers, the launches, the state and the C ABI.
+// Part of emba_hip.hip's translation unit, included by it below the helpers this file needs from it (prepare_order, size_record_set, dev_scan, d2h_pageable,
+// begin_evaluation, grid8) and above the map calls, downloads and solvers that wait for its counters (resolve_pending).
+#pragma once
+#include "context.h"
+#include "step_rule.h"
+
+using namespace emba;
+
+namespace {
+
+#define STEP_TRY(call) do { if (const emba_status st_ = (call)) return st_; } while (0)
+
+constexpr GramSizes kGramSizes{kGramBlock, kGramChunk, kGramChunkMin, kEpTailBlk};
+
+emba_status check_irls(emba_ctx* c, int32_t irls)
+{
+    if (irls < 0 || irls > 2) return fail(c, EMBA_ERR_INVALID_ARG, "irls must be 0 (quadratic), 1 (huber) or 2 (cauchy)");
+    return EMBA_OK;
+}
+
+bool gram_uses_tags(const emba_ctx* c, bool ep_host) { return gram_tags(c->use_tags, c->order.tile_order, ep_host); }
+
+emba_status ensure_pack(emba_ctx* c, int K)
+{
+    const PackLayout pack(K);
+    if (c->pack_bound) {
+        if (c->pack_cap < pack.head)
+            return fail(c, EMBA_ERR_CAPACITY, "bound pack buffer too small for K=%d", K);
+        return EMBA_OK;
+    }
+    STEP_TRY(ensure<double>(c, c->d_pack_own, pack.need(c->npix)));
+    c->d_pack = c->d_pack_own.as<double>();
+    c->pack_cap = c->d_pack_own.bytes / sizeof(double);
+    return EMBA_OK;
+}
+
+double* pack_A11(emba_ctx* c) { return c->d_pack; }
+double* pack_b1(emba_ctx* c) { return c->d_pack + PackLayout(c->eq.K).b1; }
+double* pack_A22b2(emba_ctx* c) { return c->d_pack + PackLayout(c->eq.K).A22b2; }
+
+// The pano -> compact index map is only read by the generic (weighted / external-ep) A22 path, the A12 exports and the Schur solve,
+// so it is produced when one of them asks (8 MB less traffic on every ordinary step).
+emba_status ensure_compact(emba_ctx* c)
+{
+    if (c->eq.compact_valid) return EMBA_OK;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->d_compact.as<int32_t>(), 0xFF, c->npix * sizeof(int32_t), s));
+    const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
+    if (bound)
+        hipLaunchKernelGGL(emba_compact_map_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, s, c->d_active.as<uint32_t>(), c->d_total.as<uint32_t>() + 1, c->d_compact.as<int32_t>());
+    HIP_TRY(c, hipGetLastError());
+    c->eq.compact_valid = true;
+    return EMBA_OK;
+}
+
+// a dense pass is about to turn the count map's markers into counts: this context's own (count_stamp) unless the map is a bound exchange buffer
+void counts_materialised(emba_ctx* c)
+{
+    c->pix.materialised();
+    c->ev.count_stamp = (c->d_count == c->d_count_own.as<int32_t>()) ? c->work.stamp : 0u;
+}
+
+// The warp kernel only MARKS touched pixels in the int32 count map (the count itself is accumulated next to the A22/b2 sums, one
+// atomic request per measurement).  The first post-warp launch of the resident step turns the markers into counts as a side
+// effect of its dense pass; whoever needs num_ev_map before that (download, exchange 1, the non-fused active-set path) calls this.
+emba_status ensure_counts(emba_ctx* c)
+{
+    if (!c->pix.counts_raw()) return EMBA_OK;
+    counts_materialised(c);
+    hipLaunchKernelGGL(emba_count_materialise_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix, c->pix.marker());
+    HIP_TRY(c, hipGetLastError());
+    return EMBA_OK;
+}
+
+// Standalone residual compaction (scan of the per-wave inlier counts, then the compaction): used when the host asks for
+// ep / counts before the active-set kernels run; otherwise emba_form_active launches it fused with its own stages.
+emba_status launch_ep_compaction(emba_ctx* c)
+{
+    if (!c->ev.ep_deferred) return EMBA_OK;
+    c->ev.ep_deferred = false;
+    hipStream_t s = c->stream;
+    if (c->win.n_pm) {
+        const uint32_t* perm = nullptr;    // (flags and residuals are stored in pm-order by both warp kernels)
+        hipLaunchKernelGGL(emba_flag_count_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_flag.as<uint8_t>(), perm, (long)c->win.n_pm, c->d_fblk_cnt.as<uint32_t>());
+        // (round 6: the block counts by the three-launch scan — one 256-thread block walked all of them before: 101 us for 97 k counts at 100 M events)
+        STEP_TRY(dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>(), c->h_pinned_dev, c->d_err, c->h_pinned_dev + 1));
+        hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, s, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), perm, c->d_fblk_off.as<uint32_t>(),
+                           (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());
+        c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        HIP_TRY(c, hipMemsetAsync(c->d_total.as<uint32_t>(), 0, sizeof(uint32_t), s));
+        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[0], c->d_total.as<uint32_t>(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&c->h_pinned[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    c->ev.inl_pending = true;
+    return EMBA_OK;
+}
+
+// Per-event inlier numbers (index into ep), for the consumers that need them: the fused post-warp launches skip them.
+emba_status ensure_inl_idx(emba_ctx* c)
+{
+    STEP_TRY(launch_ep_compaction(c));
+    if (c->ev.inl_idx_valid || !c->win.n_pm) return EMBA_OK;
+    // (the fused step leaves the per-block inlier counts of this evaluation in d_fblk_cnt, not their prefix)
+    STEP_TRY(dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>()));
+    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(),
+                       (long)c->win.n_pm, c->d_ep.as<double>(), c->d_inl_idx.as<int32_t>());   // (ep is rewritten with the same values)
+    HIP_TRY(c, hipGetLastError());
+    c->ev.inl_idx_valid = true; c->ev.ep_valid = true;
+    return EMBA_OK;
+}
+
+// The host waits for the pending counters.  counts_only and both counts published by the fused post-warp kernels: it polls the sequence words those kernels
+// write behind the counts instead of draining the stream; everything else synchronises.
+emba_status wait_for_counts(emba_ctx* c, bool counts_only)
+{
+    bool polled = false;
+    if (counts_only && c->ev.seq_armed && c->ev.inl_pending && c->ev.P_pending) {
+        volatile int* w = c->h_pinned + 3;                   // [3] behind the active-pixel count, [4] behind the inlier count
+        for (long spin = 0; spin < 50000000L; ++spin) {      // bounded: a faulted kernel never publishes; fall back to the stream
+            if (w[0] == c->seq && w[1] == c->seq) { polled = true; break; }
+            __builtin_ia32_pause();
+        }
+        if (polled) std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    if (polled) c->spun = true;
+    else { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; }
+    c->ev.seq_armed = false;
+    c->knots_in_flight = false;   // (the prep kernel that reads the pinned knot buffer precedes the post-warp kernels)
+    return EMBA_OK;
+}
+
+// Synchronize the stream and turn the counters that were read back asynchronously (inlier count, device error
+// word, active-pixel count) into host state.  Called only where the host really needs a value.
+// counts_only: the caller needs the inlier / active-pixel counts and nothing else from the device.  When they were produced by
+// the fused post-warp kernels, the host polls the sequence word those kernels publish after the counts instead of waiting for
+// the whole stream: it returns while the later kernels of the step (active-set gather, Gram) still run, so the next step's
+// launches queue up behind them and the GPU never idles for a host round trip.  Everything that reads device data on the
+// host goes through the full form (counts_only = false), which drains the stream.
+emba_status resolve_pending(emba_ctx* c, bool counts_only = false)
+{
+    STEP_TRY(launch_ep_compaction(c));
+    if (!c->ev.inl_pending && !c->ev.P_pending) {
+        if (c->spun && !counts_only) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->spun = false; c->knots_in_flight = false; }
+        return EMBA_OK;
+    }
+    STEP_TRY(wait_for_counts(c, counts_only));
+    if (c->ev.inl_pending) {
+        c->ev.inl_pending = false;
+        if (c->h_pinned[1] & 1) return fail(c, EMBA_ERR_TIME_RANGE, "a batch midpoint lies outside the spline's knots");
+        c->n_inliers = (size_t)(uint32_t)c->h_pinned[0];
+        c->win.n_outside_tile = (size_t)((uint32_t)c->h_pinned[1] >> 1);
+        if (tile_rebin_due(c->order.tile_order, c->n_inliers, c->win.n_outside_tile, c->rec_stamp, c->win.last_rebin_stamp)) {
+            c->order.keys_ready = false; ++c->win.n_rebin; c->win.last_rebin_stamp = c->rec_stamp;
+        }
+        c->ev.done = true;
+    }
+    if (c->ev.P_pending) {
+        c->ev.P_pending = false;
+        c->eq.P = (size_t)(uint32_t)c->h_pinned[2];
+        c->win.P_prev = c->eq.P;
+        c->eq.pack_len = PackLayout(c->eq.K).len(c->eq.P);
+        if (c->eq.pack_len > c->pack_cap)
+            return fail(c, EMBA_ERR_CAPACITY, "pack buffer too small: need %zu doubles, have %zu", c->eq.pack_len, c->pack_cap);
+        c->eq.active_done = true;
+    }
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_bind_exchange_buffers(emba_ctx* c, int32_t* count_map_dev, double* pack_dev, size_t pack_cap)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    c->d_count = count_map_dev ? count_map_dev : c->d_count_own.as<int32_t>();
+    c->ev.count_stamp = 0;
+    c->pix.bound();
+    if (pack_dev) { c->d_pack = pack_dev; c->pack_cap = pack_cap; c->pack_bound = true; }
+    else { c->pack_bound = false; c->d_pack = c->d_pack_own.as<double>(); c->pack_cap = c->d_pack_own.bytes / sizeof(double); }
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_count_compress(emba_ctx* c, uint8_t* u8_dev, int32_t cap)
+{
+    if (!c || !u8_dev || cap < 1 || cap > 255) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_compress: bad arguments") : EMBA_ERR_INVALID_ARG;
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    if (c->pix.counts_raw()) {      // markers -> this rank's counts AND their saturated bytes in one sweep (ensure_counts + the compression below)
+        counts_materialised(c);
+        hipLaunchKernelGGL(emba_count_materialise_compress_kernel, dim3((unsigned)((c->npix + 2047) / 2048)), dim3(256), 0, c->stream, c->d_count, c->d_pixacc.as<double>(), (long)c->npix,
+                           c->pix.marker(), (int)cap, u8_dev);
+    } else {
+        hipLaunchKernelGGL(emba_count_compress_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, c->d_count, (long)c->npix, (int)cap, u8_dev);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_count_expand(emba_ctx* c, const uint8_t* u8_dev)
+{
+    if (!c || !u8_dev) return c ? fail(c, EMBA_ERR_INVALID_ARG, "count_expand: NULL") : EMBA_ERR_INVALID_ARG;
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    c->ev.count_stamp = 0;      // (exchanged counts: no longer this context's own)
+    hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, u8_dev, (long)c->npix, c->d_count);
+    HIP_TRY(c, hipGetLastError());
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_count_map_ready(emba_ctx* c)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return ensure_counts(c);
+}
+
+// ---- the evaluation (evaluateDataError), phase by phase ----------------------------------------------------------------------------------------
+
+namespace {
+
+// what an evaluation needs before anything is launched: a window, a map, the device order for this spline, the pack and the knots' buffers
+emba_status eval_checks_and_buffers(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
+{
+    if (!knots) return fail(c, EMBA_ERR_INVALID_ARG, "knots NULL");
+    if (!c->win.have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
+    if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
+    HIP_TRY(c, hipSetDevice(c->device));
+    STEP_TRY(ensure<double>(c, c->d_knots, (size_t)4 * K));
+    STEP_TRY(ensure<double>(c, c->d_seg, (size_t)kSegStride * K));
+    STEP_TRY(prepare_order(c, knots, t0_ns, dt_ns, K));
+    STEP_TRY(ensure_pack(c, K));
+    if (c->h_knots_cap < K) {
+        if (c->h_knots) (void)hipHostFree(c->h_knots);
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_knots, (size_t)4 * K * sizeof(double), hipHostMallocMapped));
+        HIP_TRY(c, hipHostGetDevicePointer((void**)&c->h_knots_dev, c->h_knots, 0));
+        c->h_knots_cap = K;
+    }
+    return EMBA_OK;
+}
+
+// The working record set is what the current normal equations were formed from: this evaluation (an LM trial, or simply the next
+// step) writes the OTHER set, so that a rejection can go back to untouched equations (emba_trial_reject).
+emba_status set_equations_aside(emba_ctx* c)
+{
+    if (c->ev.P_pending || c->ev.inl_pending) STEP_TRY(resolve_pending(c, true));
+    if (!c->alt.rec.p) STEP_TRY(size_record_set(c, c->alt, c->win.n_cand));
+    std::swap(c->work, c->alt);
+    c->eq_saved = c->eq;
+    c->eq_in_alt = true;
+    return EMBA_OK;
+}
+
+// first use of these buffers: num_ev_map.setTo(0), model.cpp:85 (+ every per-pixel accumulator line)
+emba_status clear_on_first_use(emba_ctx* c)
+{
+    if (!c->pix.first_use()) return EMBA_OK;
+    HIP_TRY(c, hipMemsetAsync(c->d_count, 0, c->npix * sizeof(int32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_pixacc.as<double>(), 0, c->npix * kPixAccStride * sizeof(double), c->stream));
+    c->pix.first_use_cleared();
+    return EMBA_OK;
+}
+
+// the control poses reach the kernel: by value in its arguments (no staging copy at all), or through the pinned staging buffer
+emba_status stage_knots(emba_ctx* c, const double* knots, int32_t K, PrepPoseTexelParams& q, InlineKnots& kn)
+{
+    hipStream_t s = c->stream;
+    q.knots_dev = c->d_knots.as<double>();
+    q.knots_out = c->d_knots.as<double>();
+    q.inline_knots = (K <= kInlineKnots) ? 1 : 0;
+    if (q.inline_knots) { memcpy(kn.q, knots, (size_t)4 * K * sizeof(double)); return EMBA_OK; }
+    if (c->knots_in_flight) HIP_TRY(c, hipStreamSynchronize(s));               // the previous copy must have consumed the pinned staging buffer
+    memcpy(c->h_knots, knots, (size_t)4 * K * sizeof(double));
+    HIP_TRY(c, hipMemcpyAsync(c->d_knots.as<double>(), c->h_knots, (size_t)4 * K * sizeof(double), hipMemcpyHostToDevice, s));
+    c->knots_in_flight = true;   // cleared by the next host synchronisation
+    return EMBA_OK;
+}
+
+// ONE launch in front of the warp kernel: prep || pose table (or segment records) || texel rectangle — independent of each other.  Decides the evaluation's
+// Hessian source and pose source (step_rule.h) and takes the evaluation's status word.
+emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
+{
+    hipStream_t s = c->stream;
+    const int n_prep_blk = prep_blocks(c->pix.lines_clean(), c->win.n_sorted, c->npix);
+    c->ev.use_texel = hessian_source(c->texel_mode, c->win.n_sorted, c->npix);
+    PrepPoseTexelParams q{};
+    InlineKnots kn;
+    const int nb = (int)c->win.n_batch;
+    ++c->eval_seq;
+    c->d_err = c->d_err2.as<int>() + (c->eval_seq & 1u);
+    q.count = c->d_count; q.npix = (long)c->npix; q.pixacc = c->d_pixacc.as<double>();
+    q.W = c->W; q.H = c->H;
+    q.n_prep = n_prep_blk;
+    q.batch_t_ns = c->d_batch_t.as<int64_t>(); q.nb = nb;
+    q.K = (int)K; q.t0_ns = t0_ns; q.dt_ns = dt_ns;
+    q.pose = c->d_pose.as<double>();
+    q.err = c->d_err;
+    q.err_next = c->d_err2.as<int>() + ((c->eval_seq + 1u) & 1u);
+    c->ev.segpose = segpose_in_pixel_order(c->order.tile_order, c->segpose_mode);
+    const bool seg_records = c->order.tile_order || c->ev.segpose;
+    q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
+    q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
+    STEP_TRY(stage_knots(c, knots, K, q, kn));
+    q.n_tex = (c->ev.use_texel == 3) ? 1024 : 0;
+    q.Gx = c->d_Gx; q.Gy = c->d_Gy;
+    q.rect = c->d_rect.as<int>();
+    q.texel = c->d_texel.as<double>();
+    if (q.n_pose + q.n_tex + q.n_prep == 0) q.n_prep = 1;   // (an empty window on clean lines: block 0 still clears the next status word)
+    if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }
+    hipLaunchKernelGGL(emba_prep_pose_texel_kernel, dim3((unsigned)(q.n_pose + q.n_tex + q.n_prep)), dim3(256), 0, s, q, kn);
+    return EMBA_OK;
+}
+
+// the warp kernel of the window's order: it stamps the working record set, marks the count map and adds into the accumulator lines
+emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
+{
+    hipStream_t s = c->stream;
+    const bool tile = c->order.tile_order;
+    WarpParams p{};
+    p.ev_pix = c->order.d_ev_pix; p.ev_batch = c->order.d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>();
+    p.ev_pm = tile ? c->d_ev_pm.as<uint32_t>() : nullptr;
+    p.n_sorted = (long)c->win.n_sorted; p.nblk = c->win.nblk;
+    p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
+    p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>();
+    p.texel = c->ev.use_texel ? c->d_texel.as<double>() : nullptr;
+    p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() : nullptr;
+    p.W = c->W; p.H = c->H;
+    p.Gx = c->d_Gx; p.Gy = c->d_Gy;
+    p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy;
+    p.C_th = c->C_th; p.outlier_px = c->outlier_px;
+    p.count = c->d_count; p.pixacc = c->d_pixacc.as<double>();
+    p.rec = c->work.rec.as<double>();
+    p.tag = (c->use_tags && !tile) ? c->work.tag.as<double>() : nullptr;
+    p.rec_nt = records_non_temporal(tile, c->win.n_cand, kRecStride) ? 1 : 0;
+    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
+    p.err = c->d_err;
+    p.ablate = c->ablate;
+    p.irls = opt.irls; p.eta = opt.eta;
+    p.stamp = ++c->rec_stamp;
+    c->work.stamp = p.stamp;
+    p.marker = count_marker(p.stamp);
+    c->pix.marked(p.marker);
+    p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->order.n_chunks; p.chunks_linear = c->order.chunks_lpt ? 1 : 0;
+    if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
+    if (tile) launch_warp_tiled(c->order.tile_shape, dim3((unsigned)grid8(c->order.n_chunks)), s, p);
+    else if (c->ev.segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
+    else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
+    if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[1], s)); c->kt_warp_valid = true; c->kt_valid[c->kt_slot][0] = true; }
+    return EMBA_OK;
+}
+
+emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const EvalOpts& opt)
+{
+    STEP_TRY(eval_checks_and_buffers(c, knots, K, t0_ns, dt_ns));
+    if (c->eq.accum_done && !opt.keep_alt_set) STEP_TRY(set_equations_aside(c));
+    c->eq.K = K;
+    c->eq.active_done = c->eq.accum_done = false;
+    begin_evaluation(c);      // (with it count_stamp: the warp kernels are about to mark the count map for a new evaluation)
+    STEP_TRY(clear_on_first_use(c));
+    STEP_TRY(launch_prep_pose_texel(c, knots, K, t0_ns, dt_ns));
+    if (c->ev.use_texel == 1)
+        hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->H, c->W, c->d_texel.as<double>());
+    if (c->win.n_sorted) STEP_TRY(launch_warp(c, opt));
+    else c->pix.not_marked();
+    HIP_TRY(c, hipGetLastError());
+    c->ev.acc_irls = opt.irls; c->ev.acc_eta = opt.eta;
+    c->ev.launched = true;
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns)
+{   // (weighted with the cost declared with emba_set_cost)
+    return c ? eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{c->cost_irls, c->cost_eta, false}) : EMBA_ERR_INVALID_ARG;
+}
+
+extern "C" emba_status emba_eval_finish(emba_ctx* c, double* ep_out, size_t* n_inliers, int32_t* num_ev_map_out)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->ev.ep_deferred = true;
+    if (!ep_out && !n_inliers && !num_ev_map_out) return EMBA_OK;   // fully asynchronous: the compaction rides with the next phase
+    STEP_TRY(resolve_pending(c));
+    if (n_inliers) *n_inliers = c->n_inliers;
+    if (ep_out && c->n_inliers) { HIP_TRY(c, hipStreamSynchronize(c->stream)); STEP_TRY(d2h_pageable(c, ep_out, c->d_ep.as<double>(), c->n_inliers * sizeof(double))); }
+    if (num_ev_map_out) {
+        STEP_TRY(ensure_counts(c));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        STEP_TRY(d2h_pageable(c, num_ev_map_out, c->d_count, c->npix * sizeof(int32_t)));
+    }
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_eval_data_error(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, const double* Gx,
+                                            const double* Gy, int32_t eval_deriv, double* ep_out, size_t* n_inliers,
+                                            int32_t* num_ev_map_out)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!eval_deriv) return fail(c, EMBA_ERR_INVALID_ARG, "eval_deriv=false is never used by the reference (solver.cpp:75,251) and is not provided");
+    if (Gx || Gy) STEP_TRY(emba_upload_map(c, Gx, Gy));   // both NULL: evaluate on the resident (current or trial) map
+    STEP_TRY(emba_eval_launch(c, knots, K, t0_ns, dt_ns));
+    return emba_eval_finish(c, ep_out, n_inliers, num_ev_map_out);
+}
+
+// ---- the active set (formNormalEq, first half), phase by phase -----------------------------------------------------------------------------------
+
+namespace {
+
+// the active-set write as every form of it starts out: the sweeping kernel's arguments (the fused branch adds what launch A hands over)
+void fill_active_write(emba_ctx* c, int32_t thres, const FormOpts& opt, ActiveWriteParams& aw)
+{
+    const PackLayout pack(c->eq.K);
+    aw.count = c->d_count; aw.npix = (long)c->npix; aw.thres = thres;
+    aw.blk_off = c->d_ablk_off.as<uint32_t>(); aw.n_ablk = (long)c->n_ablk;
+    aw.compact = nullptr;
+    aw.active_idx = c->d_active.as<uint32_t>(); aw.active_bits = c->d_active_bits.as<uint8_t>();
+    aw.pixacc = c->d_pixacc.as<double>();
+    aw.A22b2 = pack_A22b2(c); aw.alpha = opt.fused_alpha;
+    aw.pack_head = c->d_pack; aw.head_len = (long)pack.head;
+    aw.max_P = (long)pack.max_P(c->pack_cap);
+    aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
+    aw.ablate = c->ablate;
+    // the resident step cleared this evaluation's per-pixel sums behind its gather: a second formNormalEq on the same evaluation takes A22 | b2
+    // from the records (the generic path of emba_form_accumulate), and its L2 term from emba_form_finish
+    if (c->eq.force_generic_a22) { aw.A22b2 = nullptr; aw.alpha = 0.0; }
+}
+
+// a sharded window's rank whose exchanged byte counts launch A cannot read: they go into the count map, and the forms below see global counts
+emba_status expand_global_counts(emba_ctx* c, const uint8_t* global_u8)
+{
+    STEP_TRY(ensure_counts(c));
+    c->ev.count_stamp = 0;
+    hipLaunchKernelGGL(emba_count_expand_kernel, dim3((unsigned)((c->npix + 1023) / 1024)), dim3(256), 0, c->stream, global_u8, (long)c->npix, c->d_count);
+    return EMBA_OK;
+}
+
+// launch A: {active counts (+ markers -> counts, activity bits, cleared A11 | b1) || inlier-flag counts}; launch B: the active-set write,
+// whose blocks take their own prefix over launch A's per-block counts and whose last block publishes P, the inlier total, the status
+// word and the sequence words the host polls.  (Nothing on the device reads the compacted residual vector `ep` — costs, Gram and solvers
+// work from the records and the per-event residuals — so it is produced when the host asks for it: resolve_pending / ensure_inl_idx
+// run the standalone compaction from the per-block flag counts left here.  100 M events: 0.65 -> 0.2 ms.)
+// Tried and dropped (round 3, 1 M events): both launches as ONE kernel with the per-block counts published through flags (look-back,
+// and "sum every predecessor"): 38-270 us against 6.3 + 11.2 — the eight XCDs' L2s are not coherent with each other, so every flag is a
+// round trip to the memory side (and a release / acquire pair writes back / invalidates a whole L2); a kernel boundary is cheaper.
+// Returns (*lists) whether it wrote the per-unit active lists the list-driven gather reads; hands `aw` what launch B takes over from it.
+void launch_post_warp_a(emba_ctx* c, int32_t thres, const FormOpts& opt, const uint8_t* global_u8, bool lists_ok, ActiveWriteParams& aw, bool* lists)
+{
+    PostWarpParams q{};
+    q.count = c->d_count; q.npix = (long)c->npix; q.thres = thres;
+    q.ablk_cnt = c->d_ablk_cnt.as<uint32_t>(); q.ablk_off = c->d_ablk_off.as<uint32_t>(); q.n_ablk = (long)c->n_ablk;
+    q.total_P = c->d_total.as<uint32_t>() + 1; q.total_P_host = c->h_pinned_dev + 2;
+    q.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); q.fblk_off = c->d_fblk_off.as<uint32_t>(); q.n_fblk = c->win.n_fblk;
+    q.perm = nullptr; q.n_pm = (long)c->win.n_pm;
+    q.total_inl = c->d_total.as<uint32_t>(); q.total_inl_host = c->h_pinned_dev;
+    q.err_dev = c->d_err; q.err_host = c->h_pinned_dev + 1;
+    q.e_sorted = c->d_e_sorted.as<double>(); q.flag = c->d_flag.as<uint8_t>(); q.ep = c->d_ep.as<double>();
+    q.inl_idx = nullptr;   // (inlier numbers: on demand, ensure_inl_idx)
+    q.seq = ++c->seq; q.seq_host = c->h_pinned_dev + 3;
+    c->ev.seq_armed = true;
+    if (c->pix.counts_raw()) {      // launch A turns the markers into counts
+        q.raw_count = c->d_count; q.pixacc = c->d_pixacc.as<double>(); q.marker = c->pix.marker();
+        counts_materialised(c);
+    }
+    const bool consume = opt.consume && c->step_fast && !c->eq.force_generic_a22;    // this gather is the per-pixel sums' only reader: lines are zeroed behind it
+    q.global_u8 = global_u8;
+    *lists = gather_uses_lists(lists_ok, q.raw_count != nullptr, q.global_u8 != nullptr);      // (step_gather = 3: everywhere, for comparison)
+    if (consume) { aw.clear_pixacc = c->d_pixacc.as<double>(); c->pix.consumed_by_gather(); }
+    if (*lists) {
+        q.seg = c->d_seg_act.as<uint16_t>(); aw.seg = c->d_seg_act.as<uint16_t>();
+        if (consume) q.clear_inactive = c->d_pixacc.as<double>();
+    }
+    const size_t fsup_len = (size_t)c->win.n_fsup * kFlagSupStride;
+    c->post.fsup_half ^= 1;
+    q.fsup = c->d_fsup.as<uint32_t>() + (size_t)c->post.fsup_half * fsup_len;
+    q.fsup_next = c->d_fsup.as<uint32_t>() + (size_t)(c->post.fsup_half ^ 1) * fsup_len;
+    q.n_sup = c->win.n_fsup;
+    q.active_bits = c->d_active_bits.as<uint8_t>(); q.pack_head = c->d_pack; q.head_len = aw.head_len;
+    aw.bits_head_done = 1;
+    q.blk_rect = c->d_blk_rect.as<int>(); q.W = c->W;
+    aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the texel rectangle of the NEXT evaluation
+    hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->win.n_fblk)), dim3(256), 0, c->stream, q);
+    aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->win.n_fblk;
+    aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;
+    aw.total_inl = q.total_inl; aw.total_inl_host = q.total_inl_host;
+    aw.err_dev = q.err_dev; aw.err_host = q.err_host;
+    aw.seq = q.seq; aw.seq_host = q.seq_host;
+}
+
+// Launch B, in one of three forms.  The resident one-GPU step (lists): the write is list-driven and balanced (active_gather_block) and rides in the compact Gram
+// kernel — emba_form_accumulate issues it — or runs as a kernel of its own (step_gather = 1, or where the Gram kernel is another form): as a kernel of its own it
+// is no faster than the sweeping write (109.6 vs 108.5 us per step at 1 M events; option step_gather = 1 forces that form for comparison, 0 the sweeping kernel).
+// (round 4, measured and dropped: this write on a side stream beside the Gram kernel — both only depend on launch A — costs more than it
+// hides: each cross-stream event edge opens a 7-12 us bubble on this stack, 114.5 vs 107.6 us per step)
+void launch_or_defer_active_set(emba_ctx* c, const FormOpts& opt, bool lists, const ActiveWriteParams& aw)
+{
+    c->post.gather_deferred = false;
+    // the residual vector ep of this evaluation: compacted by tail blocks of the Gram launch that follows (kernels.h: ep_tail_block) — launch A has just
+    // left the per-block inlier-flag counts they need
+    c->ev.ep_in_gram = opt.wants_ep && c->step_ep != 2 && c->win.n_cand;
+    c->ev.ep_after_gram = opt.wants_ep && !c->ev.ep_in_gram;
+    if (gather_rides_in_gram(lists, c->step_gather)) c->post.defer(aw);
+    else if (lists) hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, c->stream, aw);
+    else hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, c->stream, aw);
+    c->ev.inl_pending = true;
+}
+
+// the sweeping branch: the residual compaction and the counts on their own, then count / scan / write
+emba_status launch_active_set_sweeping(emba_ctx* c, int32_t thres, const ActiveWriteParams& aw)
+{
+    hipStream_t s = c->stream;
+    STEP_TRY(launch_ep_compaction(c));
+    STEP_TRY(ensure_counts(c));
+    hipLaunchKernelGGL(emba_active_count_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, c->d_count, (long)c->npix, (int)thres, c->d_ablk_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(emba_scan_kernel, dim3(1), dim3(256), 0, s, c->d_ablk_cnt.as<uint32_t>(), c->d_ablk_off.as<uint32_t>(), (long)c->n_ablk, c->d_total.as<uint32_t>() + 1,
+                       c->h_pinned_dev + 2, (const int*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(emba_active_write_kernel, dim3((unsigned)c->n_ablk), dim3(256), 0, s, aw);
+    return EMBA_OK;
+}
+
+// new equations are being formed from the working set: whatever described the previous ones no longer holds
+void equations_restarted(emba_ctx* c, int32_t thres, bool l2_fused)
+{
+    c->eq.compact_valid = false;
+    c->eq.l2_fused = l2_fused;
+    c->eq.thres = thres;
+    c->eq_in_alt = false;   // the other set's equations are obsolete
+    c->ev.P_pending = true; c->eq.active_done = false; c->eq.accum_done = false;
+    c->eq.finish_done = false;          // (the head of the pack has just been cleared: what a solve would read is no set of equations — found by the call-order pair test)
+    c->solve.x2_resident_P = (size_t)-1;   // (a solve of the PREVIOUS equations may have left its x2 on the device)
+    c->solve.invalidate();                 // (new active set)
+}
+
+emba_status form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len, const FormOpts& opt)
+{
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "formNormalEq needs the state of evaluateDataError (solver.cpp:99-102)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->eq.force_generic_a22 = c->pix.lines_consumed();
+    ActiveWriteParams aw{};
+    fill_active_write(c, thres, opt, aw);
+    const bool lists_ok = gather_lists_ok(opt.consume, c->step_gather, c->eq.force_generic_a22, (long)c->n_ablk, kGatherMaxUnits, c->win.n_cand, c->order.tile_order);
+    const uint8_t* global_u8 = opt.global_u8;
+    if (global_u8 && global_counts_need_expanding(lists_ok, c->ev.ep_deferred, c->win.n_sorted, c->pix.counts_raw())) {
+        STEP_TRY(expand_global_counts(c, global_u8));
+        global_u8 = nullptr;      // (the count map holds them now)
+    }
+    if (c->ev.ep_deferred && c->win.n_sorted) {      // the fused branch
+        c->ev.ep_deferred = false;
+        bool lists = false;
+        launch_post_warp_a(c, thres, opt, global_u8, lists_ok, aw, &lists);
+        launch_or_defer_active_set(c, opt, lists, aw);
+    } else {
+        STEP_TRY(launch_active_set_sweeping(c, thres, aw));
+    }
+    HIP_TRY(c, hipGetLastError());
+    equations_restarted(c, thres, aw.alpha != 0.0);
+    if (!P && !pack_len) return EMBA_OK;   // asynchronous: P is read from device memory by the kernels that need it
+    STEP_TRY(resolve_pending(c, true));    // counts only: a sharded host sizes exchange 2 from P while the gather still runs
+    if (P) *P = c->eq.P;
+    if (pack_len) *pack_len = c->eq.pack_len;
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_form_active(emba_ctx* c, int32_t thres, size_t* P, size_t* pack_len) { return c ? form_active(c, thres, P, pack_len, FormOpts{}) : EMBA_ERR_INVALID_ARG; }
+
+// ---- the Gram launch (formNormalEq, second half), phase by phase ---------------------------------------------------------------------------------
+
+namespace {
+
+// the caller's ep replaces the evaluation's residuals: in d_ep, in the per-event residuals and in the records
+emba_status override_ep(emba_ctx* c, const double* ep_host)
+{
+    hipStream_t s = c->stream;
+    STEP_TRY(ensure_inl_idx(c));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ep.as<double>(), ep_host, c->n_inliers * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(emba_override_ep_kernel, dim3((unsigned)((c->win.n_sorted + 255) / 256)), dim3(256), 0, s, c->d_ep.as<double>(), c->d_flag.as<uint8_t>(),
+                       c->d_inl_idx.as<int32_t>(), c->d_ev_slot.as<uint32_t>(), c->order.d_ev_pix, c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr, (long)c->win.n_sorted, c->work.rec.as<double>(), c->d_e_sorted.as<double>());
+    return EMBA_OK;
+}
+
+// A22/b2 of the active pixels were gathered from the per-pixel accumulator by emba_form_active (quadratic cost, device-resident residuals); with IRLS
+// weights or a caller-supplied ep they are rebuilt from the records instead.
+emba_status rebuild_a22_from_records(emba_ctx* c, int32_t irls, double eta)
+{
+    hipStream_t s = c->stream;
+    STEP_TRY(ensure_compact(c));
+    HIP_TRY(c, hipMemsetAsync(pack_A22b2(c), 0, 5 * c->eq.P * sizeof(double), s));
+    if (c->win.n_cand)
+        hipLaunchKernelGGL(emba_a22_from_records_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(),
+                           (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, irls, eta, pack_A22b2(c), c->work.stamp);
+    return EMBA_OK;
+}
+
+// the six forms of the Gram kernel: with or without the tag stream, with the gather in four of its waves, over a sparse slot stream (tags only)
+void launch_gram_form(bool tags, bool gather, bool sparse, unsigned grid, hipStream_t s, const GramParams& p, const ActiveWriteParams& aw)
+{
+#define GRAM_FORM(...) hipLaunchKernelGGL((emba_gram_kernel<__VA_ARGS__>), dim3(grid), dim3(kGramBlock), 0, s, p, aw)
+    if (tags && sparse) { if (gather) GRAM_FORM(true, true, true); else GRAM_FORM(true, false, true); }
+    else if (tags) { if (gather) GRAM_FORM(true, true); else GRAM_FORM(true, false); }
+    else { if (gather) GRAM_FORM(false, true); else GRAM_FORM(false, false); }
+#undef GRAM_FORM
+}
+
+// A11 | b1 from the records of the working set (the head of the pack was zeroed by emba_form_active's write kernel); with it the deferred gather, in four
+// waves of every block, and the residual vector ep, in tail blocks
+emba_status launch_gram(emba_ctx* c, bool ep_host, int32_t irls, double eta)
+{
+    hipStream_t s = c->stream;
+    GramParams p{};
+    p.rec = c->work.rec.as<double>(); p.slot_key = c->d_slot_key.as<uint32_t>(); p.n_slots = (long)c->win.n_cand;
+    p.active_bits = reinterpret_cast<const uint32_t*>(c->d_active_bits.as<uint8_t>());
+    p.irls = irls; p.eta = eta;
+    p.stamp = c->work.stamp;
+    p.A11 = pack_A11(c); p.b1 = pack_b1(c); p.dim = 3 * c->eq.K;
+    p.tag = gram_uses_tags(c, ep_host) ? c->work.tag.as<double>() : nullptr;
+    p.ablate = c->ablate;
+    const bool sparse = gram_sparse(p.tag != nullptr, c->opt_gram_sparse, c->win.P_prev, c->win.n_cand, c->eq.thres);
+    const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->win.n_pm;
+    const GramPlan plan = gram_plan(c->win.n_cand, sparse, c->opt_gram_sparse_chunk, c->n_cu, ep_tail, c->win.n_pm, c->opt_gather_waves, kGramSizes);
+    p.chunk = plan.chunk;
+    p.n_gram_blocks = plan.n_gram_blocks;
+    p.gather_waves = plan.gather_waves;
+    if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[2], s));
+    if (ep_tail) {
+        p.ep_flag = c->d_flag.as<uint8_t>(); p.ep_e = c->d_e_sorted.as<double>(); p.ep_out = c->d_ep.as<double>();
+        p.ep_fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); p.ep_n_fblk = c->win.n_fblk;
+        p.ep_n_pm = (long)c->win.n_pm;
+        p.ep_fsup = c->d_fsup.as<uint32_t>() + (size_t)c->post.fsup_half * c->win.n_fsup * kFlagSupStride;
+    }
+    c->ev.ep_in_gram = false;
+    const ActiveWriteParams aw = c->post.gather_deferred ? c->post.gather : ActiveWriteParams{};
+    launch_gram_form(p.tag != nullptr, c->post.gather_deferred, sparse, plan.grid, s, p, aw);
+    c->post.gather_deferred = false;
+    if (ep_tail) c->ev.ep_valid = true;
+    if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }
+    return EMBA_OK;
+}
+
+// option step_ep = 2 (A/B), and windows without candidates: the step's ep by launches of its own behind the Gram kernel: launch A's per-block flag counts -> offsets -> compaction
+emba_status launch_ep_after_gram(emba_ctx* c)
+{
+    STEP_TRY(dev_scan(c, c->d_fblk_cnt.as<uint32_t>(), c->d_fblk_off.as<uint32_t>(), (size_t)c->win.n_fblk, c->d_total.as<uint32_t>() + 2));
+    hipLaunchKernelGGL(emba_compact_ep_kernel, dim3((unsigned)c->win.n_fblk), dim3(256), 0, c->stream, c->d_e_sorted.as<double>(), c->d_flag.as<uint8_t>(), (const uint32_t*)nullptr, c->d_fblk_off.as<uint32_t>(), (long)c->win.n_pm,
+                       c->d_ep.as<double>(), (int32_t*)nullptr);
+    c->ev.ep_valid = true;
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_form_accumulate(emba_ctx* c, const double* ep_host, int32_t irls, double eta)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->eq.active_done && !c->ev.P_pending) return fail(c, EMBA_ERR_STATE, "emba_form_active has not been called");
+    if (c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "these equations have been accumulated already: A11 | b1 are cleared by emba_form_active only (a second pass would add the sums again)");
+    STEP_TRY(check_irls(c, irls));
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the per-pixel sums of the evaluation already carry this cost's weights (emba_set_cost / emba_step)?  Then they ARE A22/b2.
+    const bool acc_matches = (irls == c->ev.acc_irls) && (irls == 0 || eta == c->ev.acc_eta);
+    const bool generic_a22 = !acc_matches || (ep_host != nullptr) || c->eq.force_generic_a22;
+    if (c->post.gather_deferred && (generic_a22 || !c->win.n_cand)) {   // (not what emba_step does: the deferred gather as a launch of its own after all)
+        hipLaunchKernelGGL(emba_active_gather_kernel, dim3(1024), dim3(256), 0, c->stream, c->post.gather);
+        c->post.gather_deferred = false;
+    }
+    if (generic_a22) STEP_TRY(resolve_pending(c));   // needs n_inliers / P on the host (rare path)
+    if (ep_host && c->n_inliers) STEP_TRY(override_ep(c, ep_host));
+    // A11 = Zero, b1 = Zero (model.cpp:357-361): the head of the pack was zeroed by emba_form_active's write kernel
+    c->eq.irls = irls; c->eq.eta = eta;
+    if (generic_a22 && c->eq.P) STEP_TRY(rebuild_a22_from_records(c, irls, eta));
+    if (c->win.n_cand) STEP_TRY(launch_gram(c, ep_host != nullptr, irls, eta));
+    if (c->ev.ep_after_gram && !ep_host && c->win.n_pm) STEP_TRY(launch_ep_after_gram(c));
+    c->ev.ep_after_gram = false;
+    HIP_TRY(c, hipGetLastError());
+    c->eq.accum_done = true; c->eq.finish_done = false;
+    return EMBA_OK;
+}
+
+namespace {
+
+// device -> host of whatever emba_form_finish was asked for, then the one synchronisation
+emba_status download_equations(emba_ctx* c, double* A11, double* b1, uint32_t* active_idx, size_t cap_P, double* A22, double* b2, double* A12_dense)
+{
+    hipStream_t s = c->stream;
+    const size_t P = c->eq.P;
+    const int dim = 3 * c->eq.K;
+    if ((A22 || b2 || A12_dense || active_idx) && cap_P < P) return fail(c, EMBA_ERR_CAPACITY, "cap_P=%zu < P=%zu", cap_P, P);
+    if (A11) HIP_TRY(c, hipMemcpyAsync(A11, pack_A11(c), (size_t)dim * dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (b1) HIP_TRY(c, hipMemcpyAsync(b1, pack_b1(c), (size_t)dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (active_idx && P) HIP_TRY(c, hipMemcpyAsync(active_idx, c->d_active.as<uint32_t>(), P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DevBuf A12_tmp;
+    if ((A22 || b2) && P) {
+        // (round 6) the unpacked blocks sit in a workspace (a hipMalloc / hipFree pair per call until then) and travel through the pinned pipeline + the copy helpers
+        // like ep: the drop-in downloads them twice per accepted step (formNormalEq, applyL2Reg), 23 MB each at config 2's shape
+        STEP_TRY(ensure<double>(c, c->dl.A22b2, 6 * P));
+        double *d_A22 = c->dl.A22b2.as<double>(), *d_b2 = d_A22 + 4 * P;
+        hipLaunchKernelGGL(emba_unpack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, pack_A22b2(c), (long)P, d_A22, d_b2);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (A22) STEP_TRY(d2h_pageable(c, A22, d_A22, 4 * P * sizeof(double)));
+        if (b2) STEP_TRY(d2h_pageable(c, b2, d_b2, 2 * P * sizeof(double)));
+    }
+    if (A12_dense && P) {
+        STEP_TRY(ensure_compact(c));
+        const size_t n12 = (size_t)dim * 2 * P;
+        STEP_TRY(ensure<double>(c, A12_tmp, n12));
+        double* d_A12 = A12_tmp.as<double>();
+        (void)hipMemsetAsync(d_A12, 0, n12 * sizeof(double), s);
+        if (c->win.n_cand)
+            hipLaunchKernelGGL(emba_dense_a12_kernel, dim3((unsigned)((c->win.n_cand + 255) / 256)), dim3(256), 0, s, c->work.rec.as<double>(), c->d_slot_key.as<uint32_t>(),
+                               (long)c->win.n_cand, c->d_count, c->d_compact.as<int32_t>(), c->eq.thres, c->eq.irls, c->eq.eta, dim, d_A12, c->work.stamp);
+        (void)hipMemcpyAsync(A12_dense, d_A12, n12 * sizeof(double), hipMemcpyDeviceToHost, s);
+    }
+    hipError_t e = hipStreamSynchronize(s);
+    c->knots_in_flight = false;
+    if (e != hipSuccess) return fail(c, EMBA_ERR_HIP, "form_finish: %s", hipGetErrorString(e));
+    HIP_TRY(c, hipGetLastError());
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, double* b1, uint32_t* active_idx, size_t cap_P, double* A22,
+                                        double* b2, double* A12_dense)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->eq.accum_done) return fail(c, EMBA_ERR_STATE, "emba_form_accumulate has not been called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (alpha != 0.0 && !c->eq.l2_fused) {   // (l2_fused doubles as "already applied to this set of blocks": applyL2Reg acts once)
+        c->eq.l2_fused = true;
+        // P may still be unresolved on the host: the kernel reads it from device memory, the grid covers the bound
+        const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
+        if (bound)
+            hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, c->stream, pack_A22b2(c), c->d_active.as<uint32_t>(),
+                               c->d_total.as<uint32_t>() + 1, alpha, c->d_Gx, c->d_Gy);
+    }
+    HIP_TRY(c, hipGetLastError());
+    const bool download = A11 || b1 || active_idx || A22 || b2 || A12_dense;
+    STEP_TRY(resolve_pending(c, !download));   // the step's one host wait when nothing was resolved earlier
+    if (download) STEP_TRY(download_equations(c, A11, b1, active_idx, cap_P, A22, b2, A12_dense));
+    c->eq.finish_done = true;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_form_normal_eq(emba_ctx* c, const double* ep, int32_t thres, int32_t irls, double eta, double alpha, double* A11,
+                                           double* b1, size_t* P, uint32_t* active_idx, size_t cap_P, double* A22, double* b2, double* A12_dense)
+{
+    size_t Pl = 0, pl = 0;
+    STEP_TRY(emba_form_active(c, thres, &Pl, &pl));
+    if (P) *P = Pl;
+    STEP_TRY(emba_form_accumulate(c, ep, irls, eta));
+    return emba_form_finish(c, alpha, A11, b1, active_idx, cap_P, A22, b2, A12_dense);
+}
+
+extern "C" emba_status emba_step(emba_ctx* c, const double* knots, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t thres, int32_t irls, double eta,
+                                 double alpha, size_t* n_inliers, size_t* P)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    STEP_TRY(check_irls(c, irls));
+    // the evaluation weights its per-pixel sums with THIS step's cost (whatever emba_set_cost declared for other callers)
+    STEP_TRY(eval_launch(c, knots, K, t0_ns, dt_ns, EvalOpts{irls, irls ? eta : 0.0, c->step_one_set != 0}));
+    STEP_TRY(emba_eval_finish(c, nullptr, nullptr, nullptr));
+    FormOpts fo;
+    fo.fused_alpha = alpha;               // A22/b2 come from the accumulator, so applyL2Reg rides along with the gather
+    fo.consume = (c->step_fast != 0);     // ... which is their only reader: it zeroes the lines behind itself and the next evaluation needs no clearing pass
+    fo.wants_ep = (c->step_ep != 0);      // the step returns what evaluateDataError returns: ep, compacted in the tail of its Gram launch
+    STEP_TRY(form_active(c, thres, nullptr, nullptr, fo));
+    STEP_TRY(emba_form_accumulate(c, nullptr, irls, eta));
+    STEP_TRY(emba_form_finish(c, alpha, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+    if (n_inliers) *n_inliers = c->n_inliers;
+    if (P) *P = c->eq.P;
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_step_form_active(emba_ctx* c, int32_t thres, const uint8_t* global_counts_u8_dev)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->ev.launched) return fail(c, EMBA_ERR_STATE, "emba_eval_launch has not been called");
+    STEP_TRY(emba_eval_finish(c, nullptr, nullptr, nullptr));
+    FormOpts fo;
+    fo.consume = (c->step_fast != 0);
+    fo.global_u8 = global_counts_u8_dev;
+    return form_active(c, thres, nullptr, nullptr, fo);
+}
+
+extern "C" emba_status emba_set_cost(emba_ctx* c, int32_t irls, double eta)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    STEP_TRY(check_irls(c, irls));
+    c->cost_irls = irls; c->cost_eta = irls ? eta : 0.0;
+    return EMBA_OK;
+}
+
+#undef STEP_TRY

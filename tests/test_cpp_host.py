@@ -110,6 +110,28 @@ def test_solve_rule_on_the_cpu(tmp_path):
         assert tuple(OM.REQUIRED[opt]) == values, opt
 
 
+def test_step_rule_on_the_cpu(tmp_path):
+    """emba_amd/csrc/step_rule.h (plain C++17, no HIP): tests/cpp/step_rule_test.cpp checks the layout of the pack, every boolean rule of the step path on
+    both sides of its size threshold and under the option values the GPU tests set, sweeps the Gram launch's plan (1 ... 2.1e9 candidates, both forms,
+    gram_sparse_chunk 1 ... 8, four chip sizes, with and without the ep tail) over its properties, and compares it at the BASELINE shape and the shapes
+    of DESIGN.md §6 with what emba_form_accumulate's own expressions gave before they moved there."""
+    import re
+    import option_matrix as OM
+    consts = OM.parse_constants()
+    with open(OM.KERNELS_H) as f:
+        consts["kEpTailBlk"] = OM._eval_int(re.search(r"constexpr\s+int\s+kEpTailBlk\s*=\s*([^;]+);", f.read()).group(1), consts)      # (= 4 * kFlagBlk)
+    defs = dict(GRAM_BLOCK="kGramBlock", GRAM_CHUNK="kGramChunk", GRAM_CHUNK_MIN="kGramChunkMin", EP_TAIL_BLK="kEpTailBlk", REC_STRIDE="kRecStride", GATHER_MAX_UNITS="kGatherMaxUnits")
+    exe = str(tmp_path / "step_rule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror"] + ["-D%s=%d" % (k, consts[v]) for k, v in defs.items()] +
+                          [os.path.join(ROOT, "tests", "cpp", "step_rule_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "OK step_rule", r.stdout + r.stderr
+    # what the rule test's option values are taken from
+    for opt, values in (("texel", (1, 2, 3)), ("segpose", (1, 2)), ("step_gather", (0, 1, 3)), ("gram_sparse", (0, 1)), ("gram_tags", (0,)), ("gather_waves", (1, 2, 4))):
+        assert tuple(OM.REQUIRED[opt]) == values, opt
+
+
 ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "adapter_test")
 
 
