@@ -74,6 +74,8 @@ struct EvalState {
     uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
     int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
     int use_texel = 0;            // the Hessian source this evaluation uses: 0 fly, 1 full pack, 3 rectangle (step_rule.h: hessian_source)
+    bool prep_in_warp = false;    // no launch in front of the warp kernel: its workgroup 0 formed the segment records (step_rule.h: prep_inside_warp)
+    bool texels_packed = false;   // the launch in front of the warp kernel carried texel blocks (source 3: only when the texels were stale)
     bool segpose = false;         // pixel order: this evaluation takes the pose per event from segment records (option segpose); emba_dump_state re-warps the same way
     bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
 };
@@ -189,7 +191,13 @@ struct emba_ctx {
     DevBuf d_pixacc;          // per-pixel A22/b2 accumulator lines (64 B each)
     PixAccState pix;          // what the host knows about the count map and the lines
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
-    DevBuf d_rect;       // {xmin,ymin,xmax,ymax} of the pixels the previous evaluation touched
+    DevBuf d_rect;       // [0..3] {xmin,ymin,xmax,ymax} of the pixels the last formed evaluation touched; [4..7] the box the texels are PACKED for (what the warp kernel trusts)
+    bool map_bound = false;   // the current map was bound with emba_bind_map_dev: the caller's memory, which may change without a call (the trial map is always the context's own)
+    uint32_t seg_seq = 0;     // the flag value of the last in-warp hand-off of segment records (never 0: the flag word starts at 0)
+    uint32_t map_version = 1, packed_version = 0;   // counts the calls that change or rebind the map planes (map_changed); the count the last texel pack read
+    int step_prep = 0, step_prep_polls = 1024;   // option step_prep (A/B): 0 (default) the launch in front of the warp kernel always, 1 none where its work fits the warp launch; option step_prep_polls: the consumers' poll budget (0: none)
+    emba::InlineSegParams seg_inline{}; emba::InlineKnots seg_knots{};   // what launch_prep_pose_texel leaves for the warp launch of the same evaluation (ev.prep_in_warp)
+    DevBuf d_seg_flag;   // [0] the segment records' flag (a line of its own), [32] waves that formed their records themselves (diagnostics)
     DevBuf d_blk_rect;   // per prep-block boxes
     DevBuf d_compact, d_active_bits;   // 1 bit per pixel: count >= thres of the current active set
     DevBuf d_active;
@@ -204,7 +212,7 @@ struct emba_ctx {
     DevBuf d_scalar;                // cost reductions
     std::vector<uint32_t> h_pix_starts;   // emba_get_inlier_pixel_starts of the current evaluation (ev.pix_starts_valid), for emba_get_ep_by_pixel
     void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
-    int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3] step sequence number
+    int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3], [4] step sequence number [5] the packed texels still cover the step's box (the step's number, else 0)
     int seq = 0;                    // sequence number of the last step whose post-warp kernels publish [3]
     bool spun = false;              // counts were taken by polling: later kernels of the stream may still be running
     int* h_pinned_dev = nullptr;    // the same memory through its device pointer

@@ -41,6 +41,9 @@ namespace {
 // A new evaluation begins, or the last one can no longer be asked about (its window is gone, its trial was rejected): nothing that was derived from it —
 // pending counters, the residual vector, inlier numbers, the pixel-starts table, the count map's stamp — outlives this.
 void begin_evaluation(emba_ctx* c) { c->ev = EvalState{}; }
+// The planes the next evaluation reads have changed or been rebound (upload, bind, trial update, accept, reject, blur — the map-only start goes through the trial
+// update): the packed texels describe another map (step_rule.h: texels_stale).
+void map_changed(emba_ctx* c) { ++c->map_version; }
 // A new device order (a new window, or the window is ordered again): nothing of the previous one is kept but the shape and grid of the last tile search,
 // which emba_last_tile_geometry reports until another search runs.
 OrderState new_order(const OrderState& prev)
@@ -589,8 +592,10 @@ emba_status emba_create(const emba_cfg* cfg, emba_ctx** out)
     CREATE_TRY(c->d_err2.ensure(2 * sizeof(int)));
     CREATE_TRY(hipMemset(c->d_err2.as<int>(), 0, 2 * sizeof(int)));
     c->d_err = c->d_err2.as<int>();
-    CREATE_TRY(c->d_rect.ensure(4 * sizeof(int)));
-    { const int init[4] = {0x7FFFFFFF, 0x7FFFFFFF, -1, -1}; CREATE_TRY(hipMemcpy(c->d_rect.as<int>(), init, sizeof init, hipMemcpyHostToDevice)); }
+    CREATE_TRY(c->d_rect.ensure(8 * sizeof(int)));
+    { const int init[8] = {0x7FFFFFFF, 0x7FFFFFFF, -1, -1, 0x7FFFFFFF, 0x7FFFFFFF, -1, -1}; CREATE_TRY(hipMemcpy(c->d_rect.as<int>(), init, sizeof init, hipMemcpyHostToDevice)); }
+    CREATE_TRY(c->d_seg_flag.ensure(256));
+    CREATE_TRY(hipMemset(c->d_seg_flag.as<unsigned>(), 0, 256));
     CREATE_TRY(c->d_blk_rect.ensure(c->n_ablk * 4 * sizeof(int)));   // per active-count block: box of the touched pixels
     CREATE_TRY(c->d_total.ensure(4 * sizeof(uint32_t)));   // [0] inliers [1] P [2] scratch total
     CREATE_TRY(c->d_scalar.ensure(2 * sizeof(double)));
@@ -836,8 +841,9 @@ emba_status emba_upload_map(emba_ctx* c, const double* Gx, const double* Gy)
     HIP_TRY(c, hipMemcpyAsync(c->d_Gx_own.as<double>(), Gx, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_Gy_own.as<double>(), Gy, c->npix * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->d_Gx = c->d_Gx_cur = c->d_Gx_own.as<double>(); c->d_Gy = c->d_Gy_cur = c->d_Gy_own.as<double>();
-    c->map_is_trial = false;
+    c->map_is_trial = false; c->map_bound = false;
     c->have_map = true;
+    map_changed(c);
     return EMBA_OK;
 }
 
@@ -845,8 +851,9 @@ emba_status emba_bind_map_dev(emba_ctx* c, const double* Gx_dev, const double* G
 {
     if (!c || !Gx_dev || !Gy_dev) return c ? fail(c, EMBA_ERR_INVALID_ARG, "Gx/Gy NULL") : EMBA_ERR_INVALID_ARG;
     c->d_Gx = c->d_Gx_cur = Gx_dev; c->d_Gy = c->d_Gy_cur = Gy_dev;
-    c->map_is_trial = false;
+    c->map_is_trial = false; c->map_bound = true;
     c->have_map = true;
+    map_changed(c);
     return EMBA_OK;
 }
 
@@ -880,6 +887,7 @@ emba_status update_map_impl(emba_ctx* c, const double* x2, int src_kind, double 
     if (src_kind == 0) HIP_TRY(c, hipStreamSynchronize(s));   // x2_host may be freed by the caller
     c->d_Gx = c->d_Gx_trial.as<double>(); c->d_Gy = c->d_Gy_trial.as<double>();
     c->map_is_trial = true;
+    map_changed(c);
     return EMBA_OK;
 }
 // the solvers leave their x2 in d_x2 (device to device: 2P doubles), so that updateMap needs no trip through the host
@@ -904,7 +912,8 @@ emba_status emba_map_accept(emba_ctx* c)
     // they or a bound one)
     std::swap(c->d_Gx_own, c->d_Gx_trial); std::swap(c->d_Gy_own, c->d_Gy_trial);
     c->d_Gx_cur = c->d_Gx = c->d_Gx_own.as<double>(); c->d_Gy_cur = c->d_Gy = c->d_Gy_own.as<double>();
-    c->map_is_trial = false;
+    c->map_is_trial = false; c->map_bound = false;
+    map_changed(c);      // (the same values at the same addresses as the trial map's; counted all the same: every rebinding is)
     return EMBA_OK;
 }
 
@@ -928,6 +937,7 @@ emba_status emba_map_reject(emba_ctx* c)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     // (no trial map: a step that moved the poses only — emba_solve_poses_only, no emba_update_map — was rejected; the map stays, the equations come back)
+    if (c->d_Gx != c->d_Gx_cur || c->d_Gy != c->d_Gy_cur) map_changed(c);
     c->d_Gx = c->d_Gx_cur; c->d_Gy = c->d_Gy_cur;
     c->map_is_trial = false;
     return emba_trial_reject(c);           // and the normal equations the trial evaluation set aside are current again
@@ -1296,6 +1306,12 @@ const OptionRef kOptions[] = {
     {"poisson", &emba_ctx::opt_poisson, 0, 2},
     {"gemm64", &emba_ctx::opt_gemm64, 0, 1},
 };
+// the hand-off of the segment records inside the warp launch (step_rule.h: prep_inside_warp); tests/test_gpu_step_prep.py runs every value that selects a branch
+// (tests/test_step_prep_rule_cpu.py checks that it does)
+const OptionRef kStepPrepOptions[] = {
+    {"step_prep", &emba_ctx::step_prep, 0, 1},
+    {"step_prep_polls", &emba_ctx::step_prep_polls, 0, 1 << 16},
+};
 }  // namespace
 
 emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
@@ -1308,14 +1324,35 @@ emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
             if (!strcmp(name, "order") || !strcmp(name, "chunk_order_bin") || !strncmp(name, "tile_", 5)) c->order.keys_ready = false;      // the device order is rebuilt at the next evaluation
             return EMBA_OK;
         }
+    for (const OptionRef& o : kStepPrepOptions)
+        if (!strcmp(o.name, name)) {
+            if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
+            c->*(o.field) = (int)value;
+            return EMBA_OK;
+        }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 emba_status emba_get_option(emba_ctx* c, const char* name, int32_t* value)
 {
     if (!c || !name || !value) return EMBA_ERR_INVALID_ARG;
+    // read-only, the last evaluation: no launch in front of its warp kernel; that launch carried texel blocks; waves that formed their segment records themselves
+    // (all evaluations of the context; drains the stream)
+    if (!strcmp(name, "prep_in_warp")) { *value = c->ev.prep_in_warp ? 1 : 0; return EMBA_OK; }
+    if (!strcmp(name, "texels_packed")) { *value = c->ev.texels_packed ? 1 : 0; return EMBA_OK; }
+    if (!strcmp(name, "step_prep_fallbacks")) {
+        unsigned n = 0;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->spun = false; c->knots_in_flight = false;
+        HIP_TRY(c, hipMemcpy(&n, c->d_seg_flag.as<unsigned>() + 32, sizeof n, hipMemcpyDeviceToHost));
+        *value = (int32_t)std::min<unsigned>(n, 0x7FFFFFFFu);
+        return EMBA_OK;
+    }
     if (!strcmp(name, "ep_valid")) { *value = c->ev.ep_valid ? 1 : 0; return EMBA_OK; }      // read-only: the device holds the last evaluation's ep (a step produced it, or a compaction)
     for (const OptionRef& o : kOptions)
+        if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
+    for (const OptionRef& o : kStepPrepOptions)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
@@ -1941,6 +1978,8 @@ extern "C" emba_status emba_median_blur3_map(emba_ctx* c)
         HIP_TRY(c, hipMemcpyAsync(dst[k], c->d_blur.as<double>(), c->npix * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     c->d_Gx = c->d_Gx_cur = dst[0]; c->d_Gy = c->d_Gy_cur = dst[1];
+    c->map_bound = false;
+    map_changed(c);
     return EMBA_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "device_math.h"
 #include "order_rule.h"   // ChunkDesc, TileShape
+#include "step_rule.h"    // kRectMargin, rect_contained
 
 // Development ablations (EMBA_ABLATE bit mask: parts of a kernel switched off to see what they cost; results are WRONG when non-zero)
 // exist only in a diagnostics build (-DEMBA_DIAG, scripts/ablate*.sh build one under build_variants/): the shipped library has none of
@@ -143,13 +144,22 @@ __device__ __forceinline__ void pose_thread(int b, const int64_t* __restrict__ b
 
 // Tile order: per-SEGMENT constants instead (device_math.h: segment_consts / spline2_event); thread s fills segment s of seg[12 s].
 constexpr int kSegStride = 12;
-__device__ __forceinline__ void seg_thread(int sidx, const double* __restrict__ knots, int K, double* __restrict__ seg)
+// (the record of segment sidx as VALUES: whoever forms it — the prep launch, workgroup 0 of the warp launch, a wave that gave up waiting for that one — gets the
+// same bits, and nothing downstream is contracted into the chain: the values pass through registers the compiler cannot see into)
+__device__ __forceinline__ void seg_record(int sidx, const double* __restrict__ knots, double* __restrict__ o)
 {
-    if (sidx >= K - 1) return;
-    double p0[4], p1[4], o[kSegStride];
+    double p0[4], p1[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { p0[i] = knots[4 * sidx + i]; p1[i] = knots[4 * (sidx + 1) + i]; }
     segment_consts(p0, p1, o);
+#pragma unroll
+    for (int i = 0; i < kSegStride; ++i) __asm__ volatile("" : "+v"(o[i]));
+}
+__device__ __forceinline__ void seg_thread(int sidx, const double* __restrict__ knots, int K, double* __restrict__ seg)
+{
+    if (sidx >= K - 1) return;
+    double o[kSegStride];
+    seg_record(sidx, knots, o);
 #pragma unroll
     for (int i = 0; i < kSegStride; ++i) seg[(size_t)kSegStride * sidx + i] = o[i];
 }
@@ -193,11 +203,11 @@ __device__ __forceinline__ void hessian_at(const double* __restrict__ Gx, const 
     gyy_o = 0.125 * gyy;
 }
 
-// Texel rectangle: the bounding box (+ margin) of the pixels the PREVIOUS evaluation touched, accumulated by the prep kernel.
+// Texel rectangle: the bounding box (+ kRectMargin, step_rule.h) of the pixels an EARLIER formed evaluation touched, reduced by its active-set write.
 // Inside it the warp kernel gathers one 48-B texel (3 cache accesses); outside it falls back to the 3x3 stencil on the Gx/Gy
 // planes (18 accesses).  Consecutive LM trial points move the footprint by a few pixels, so almost every gather is a texel.
-// rect = {x0, y0, x1, y1} inclusive; empty if x1 < x0.  acc = raw {xmin, ymin, xmax, ymax} from the prep kernel.
-constexpr int kRectMargin = 24;
+// rect = {x0, y0, x1, y1} inclusive; empty if x1 < x0.  acc = raw {xmin, ymin, xmax, ymax}: the box the texels were last PACKED for (the pack's
+// block 0 copies it from the newest box; texels are packed when they are stale, not in every evaluation: step_rule.h, texels_stale).
 __device__ __forceinline__ void texel_rect(const int* __restrict__ acc, int W, int H, int& x0, int& y0, int& x1, int& y1)
 {
     const int ax0 = acc[0], ay0 = acc[1], ax1 = acc[2], ay1 = acc[3];
@@ -312,6 +322,68 @@ __device__ __forceinline__ double dpp_shl1(double v)
     return __hiloint2double(dpp_shl1(__double2hiint(v)), dpp_shl1(__double2loint(v)));
 }
 
+// The control poses of a spline with K <= kInlineKnots travel BY VALUE in the kernel arguments (emba_prep_pose_texel_kernel, emba_warp_residual_inline_kernel)
+constexpr int kInlineKnots = 104;
+struct InlineKnots { double q[4 * kInlineKnots]; };
+
+// ---- the segment records INSIDE the pixel-order warp launch (step_rule.h: prep_inside_warp) -----------------------------------------------------------------
+// What is left of the launch in front of the warp kernel on clean lines and fresh texels is one block that writes K - 1 records of 96 B.  Here workgroup 0 — the
+// first dispatched — forms them from the control poses in the kernel arguments (seg_record: the prep launch's own chain, the same bits) and hands them to every
+// other workgroup of the launch; it also takes over block 0's other duties (the next evaluation's status word, the device copy of the control poses).
+// The hand-off (MI355X: eight XCDs with private L2s, an L1 per CU that no other CU's store refreshes):
+//   producer   the records go out as write-through 8-B agent-scope stores, the wave drains them (vmcnt(0)), then ONE lane stores the flag — the number of this
+//              hand-off on the context (it skips 0, the word's first value), which no earlier evaluation has written, so nothing is cleared between
+//              evaluations — as an agent-scope store.  The number and the control poses are kernel ARGUMENTS: a captured graph would replay both frozen, and
+//              the step is not captured (its poses change with every call).  Every shared word is reached through a global (address space 1) pointer
+//   consumers  issue the loads that do not depend on the records (event words, spline parameter, segment, slot), then poll the flag with agent-scope loads and read
+//              the records with 16-B sc1 buffer loads, EVERY load of them: a line an earlier evaluation left in this CU's L1 is never looked at.  No acquire: an
+//              acquire per one-wave workgroup would be 15.9 k invalidations per launch at 1 M events
+//   bounded    after `polls` polls a wave turns producer itself: it forms all K - 1 records (seg_record again: the same bits) and stores them the same way — the same
+//              values to the same addresses, whoever else is writing them —, drains, counts itself in `fallbacks` and reads them back like everybody else (in front of
+//              the per-event part, where few registers are live: the chain inlined into that part cost 36 VGPRs and a wave per SIMD); workgroup 0 waits for nobody;
+//              no spin without a bound
+struct InlineSegParams {
+    double* seg; unsigned seg_bytes;      // the K - 1 records, and their extent (the buffer loads' bound)
+    unsigned* flag; unsigned seq;         // a word on a line of its own; this hand-off's number (never 0)
+    int K, polls;                         // a poll and its s_sleep(8) take about 0.25 us: the default 1024 bounds the wait at a quarter of a millisecond.
+                                          // polls = 0: nobody waits (tests: every wave but workgroup 0's takes the bounded path's exit)
+    unsigned* fallbacks;                  // diagnostics: waves that formed their records themselves, summed over the context's life
+    int* err_next; double* knots_out;     // block 0's other duties
+};
+typedef __attribute__((address_space(1))) unsigned gu32;
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+// how a lane of the inline form reads its segment record
+struct InlineSegLane { __amdgpu_buffer_rsrc_t rsrc; };
+
+// duties: workgroup 0 (the flag, and block 0's other duties of the launch this replaces); a wave that gave up waiting writes the records only
+__device__ __forceinline__ void inline_seg_produce(const InlineSegParams& h, const double* __restrict__ knots, int t, bool duties)
+{
+    for (int sidx = t; sidx < h.K - 1; sidx += kWarpBlock) {
+        double o[kSegStride];
+        seg_record(sidx, knots, o);
+        gu64* dst = (gu64*)(h.seg + (size_t)kSegStride * sidx);
+#pragma unroll
+        for (int i = 0; i < kSegStride; ++i) __hip_atomic_store(dst + i, (unsigned long long)__double_as_longlong(o[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing lane is in this one wave: drained before the flag
+    if (!duties) return;
+    if (t == 0) __hip_atomic_store((gu32*)h.flag, h.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 63) h.err_next[0] = 0;
+    if (h.knots_out) for (int i = t; i < 4 * h.K; i += kWarpBlock) h.knots_out[i] = knots[i];   // (for whoever reads the device copy later)
+}
+// true: the records are published; false: the poll budget ran out (wave-uniform either way)
+__device__ __forceinline__ bool inline_seg_wait(const InlineSegParams& h)
+{
+    bool ready = false;
+    for (int n = 0; n < h.polls; ++n) {
+        const unsigned f = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load((gu32*)h.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (f == h.seq) { ready = true; break; }
+        __builtin_amdgcn_s_sleep(8);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // (no instruction: the record loads stay behind the poll)
+    return ready;
+}
+
 // What one lane knows about its measurement after the shared part.
 #ifndef WARP_LATE_EP
 #define WARP_LATE_EP 0     // pixel-order kernel: residual / flag stores issued after the record stores and atomics instead of in the middle
@@ -351,8 +423,8 @@ struct NoPrefetch { __device__ __forceinline__ void operator()() const {} };
 // SEGPOSE (round 4; pixel order with a LARGE window): the pose is evaluated per event from its batch's spline parameter and segment record, as in the tile
 // order, instead of gathered from the per-batch table — at 10 M events that table is 11 MB of 112-B records, every event pulls one or two 128-B lines of it
 // past the L2 (counters: 1.37x the algorithmic bytes); u and the segment travel per entry with the event words (10 B, streamed), the K-1 segment records are a few KB.
-template <bool DUMP, bool COMPACT = false, class PF = NoPrefetch, bool LATE_EP = false, bool SEGPOSE = false>
-__device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const LaneIn& in, int t, LaneOut& o, PF prefetch = PF())
+template <bool DUMP, bool COMPACT = false, class PF = NoPrefetch, bool LATE_EP = false, bool SEGPOSE = false, bool INLINE_SEG = false>
+__device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const LaneIn& in, int t, LaneOut& o, PF prefetch = PF(), const InlineSegLane* is = nullptr)
 {
     const bool valid = in.valid;
     double pm[2] = {0, 0};
@@ -374,9 +446,22 @@ __device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const Lan
             // (the K-1 segment records are cache-resident and fetched here, next to the bearing-vector gather whose latency is paid anyway:
             // prefetched with the event words they cost 24 VGPRs per pipeline stage)
             const uint32_t sg = bi; const double uu = in.u;
-            const double2* S2 = reinterpret_cast<const double2*>(p.seg + (size_t)kSegStride * (EMBA_ABL(p.ablate, 16) ? (sg & 1u) : sg));
-            const double2 s0 = S2[0], s1 = S2[1], s2 = S2[2], s3 = S2[3], s4 = S2[4], s5 = S2[5];
-            const double seg[kSegStride] = {s0.x, s0.y, s1.x, s1.y, s2.x, s2.y, s3.x, s3.y, s4.x, s4.y, s5.x, s5.y};
+            double seg[kSegStride];
+            if (INLINE_SEG) {   // the records were written inside this launch (inline_seg_*): sc1 loads only
+                typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+                typedef double v2d __attribute__((ext_vector_type(2)));
+                const int off = (int)(sg * (uint32_t)(kSegStride * sizeof(double)));
+#pragma unroll
+                for (int k = 0; k < kSegStride / 2; ++k) {
+                    const v2d v = __builtin_bit_cast(v2d, (v4u)__builtin_amdgcn_raw_buffer_load_b128(is->rsrc, off + 16 * k, 0, 16));   // aux 16 = sc1
+                    seg[2 * k] = v.x; seg[2 * k + 1] = v.y;
+                }
+            } else {
+                const double2* S2 = reinterpret_cast<const double2*>(p.seg + (size_t)kSegStride * (EMBA_ABL(p.ablate, 16) ? (sg & 1u) : sg));
+                const double2 s0 = S2[0], s1 = S2[1], s2 = S2[2], s3 = S2[3], s4 = S2[4], s5 = S2[5];
+                seg[0] = s0.x; seg[1] = s0.y; seg[2] = s1.x; seg[3] = s1.y; seg[4] = s2.x; seg[5] = s2.y;
+                seg[6] = s3.x; seg[7] = s3.y; seg[8] = s4.x; seg[9] = s4.y; seg[10] = s5.x; seg[11] = s5.y;
+            }
             double q[4];
             spline2_event<!DUMP>(seg, uu, q, J1);
             quat_to_matrix(q, R);     // rot.matrix() per event, event_pano_warper.cpp:55
@@ -561,8 +646,8 @@ __device__ __forceinline__ void store_records(const WarpParams& p, int t, const 
 #ifndef WARP_OCC
 #define WARP_OCC
 #endif
-template <bool DUMP, bool COMPACT = false, bool SEGPOSE = false>
-__global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel(WarpParams p)
+template <bool DUMP, bool COMPACT, bool SEGPOSE, bool INLINE_SEG>
+__device__ __forceinline__ void warp_residual_body(const WarpParams& p, const InlineSegParams* h, const double* knots)
 {
     // One wave per workgroup, LDS operations complete in order: the record staging tile (first) and the run sums (afterwards) share
     // the same bytes, so that LDS (160 KB per CU) does not cap the resident waves below what the registers allow.
@@ -572,15 +657,26 @@ __global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel
     uint32_t* const s_q = reinterpret_cast<uint32_t*>(s_tile + 64 * 6);     // ... and their panorama pixels (256 B)
     __shared__ uint32_t s_slot[32];                                         // record slots of the staged half's inliers
 
+    const int t = threadIdx.x;   // == lane
+    if (INLINE_SEG && blockIdx.x == 0) inline_seg_produce(*h, knots, t, true);   // before anything else, and whether or not this workgroup has entries of its own
     const long b = xcd_contiguous_block(blockIdx.x, gridDim.x);
     if (b >= p.nblk) return;  // the whole wave exits together
-    const int t = threadIdx.x;   // == lane
     const long i = b * kWarpNew + t - 1;
     const bool valid = (i >= 0) && (i < p.n_sorted);
     LaneOut o;
     LaneIn in;
     load_event_words<COMPACT, SEGPOSE>(p, i, valid, in);
-    warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE>(p, i, in, t, o);
+    if (INLINE_SEG) {
+        InlineSegLane is;
+        is.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)h->seg, 0, (int)h->seg_bytes, 0x00020000);    // raw buffer, 32-bit data format; loads past seg_bytes return 0
+        if (blockIdx.x != 0 && !inline_seg_wait(*h)) {       // (workgroup 0 has returned from inline_seg_produce: its own stores are drained)
+            inline_seg_produce(*h, knots, t, false);
+            if (t == 0) atomicAdd(h->fallbacks, 1u);
+        }
+        warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE, true>(p, i, in, t, o, NoPrefetch(), &is);
+    } else {
+        warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE>(p, i, in, t, o);
+    }
     if (DUMP) return;
     const bool inl = o.inl;
     const uint32_t pi = o.pi;
@@ -650,6 +746,22 @@ __global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel
         if (inl) { if (EP_NT_STORE) __builtin_nontemporal_store(o.e, &p.e_sorted[in.pm]); else p.e_sorted[in.pm] = o.e; }
         if (o.wr_flag) { if (EP_NT_STORE) __builtin_nontemporal_store((uint8_t)(inl ? 1 : 0), &p.flag[in.pm]); else p.flag[in.pm] = inl ? 1 : 0; }
     }
+}
+
+template <bool DUMP, bool COMPACT = false, bool SEGPOSE = false>
+__global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel(WarpParams p)
+{
+    warp_residual_body<DUMP, COMPACT, SEGPOSE, false>(p, nullptr, nullptr);
+}
+// pixel order, pose per event, the segment records formed by workgroup 0 of this launch (inline_seg_*)
+// (five waves per SIMD like the form it replaces: the producer's chain — so3_log, sin, cos: 128 VGPRs on its own — spills 144 B per lane in the two places that run
+// it; the per-event part fits as before)
+#ifndef EMBA_INLINE_WARP_OCC
+#define EMBA_INLINE_WARP_OCC __attribute__((amdgpu_waves_per_eu(5, 5)))
+#endif
+__global__ __launch_bounds__(kWarpBlock) EMBA_INLINE_WARP_OCC void emba_warp_residual_inline_kernel(WarpParams p, InlineSegParams h, InlineKnots kn)
+{
+    warp_residual_body<false, false, true, true>(p, &h, kn.q);
 }
 
 // Tile order: blockIdx -> chunk of one panorama bin's events (ChunkDesc).  The workgroup's waves take the chunk's 63-entry groups
@@ -1149,7 +1261,16 @@ struct ActiveWriteParams {
     double* clear_pixacc; // non-null (the resident one-GPU step): the per-pixel sums have one reader, this gather — every touched line is zeroed behind it,
                           // so that the next evaluation starts on clean lines without a clearing pass (emba_prep_pose_texel_kernel: no prep blocks)
     const int* blk_rect; int* rect_out;   // non-null: launch A's per-block boxes; the last block reduces them into rect_out = {xmin, ymin, xmax, ymax}
+    const int* rect_packed; int* fresh_host;   // with them: the box the texels are packed for; the verdict "the new box lies inside it" (seq, else 0), published in front of the sequence words
 };
+
+// the last block's verdict on the packed texels (step_rule.h: rect_contained), in pinned host memory: the host reads it behind the sequence words
+__device__ __forceinline__ void publish_texel_verdict(const ActiveWriteParams& a, int xmin, int ymin, int xmax, int ymax)
+{
+    if (!a.fresh_host) return;
+    const bool in = rect_contained(xmin, ymin, xmax, ymax, a.rect_packed[0], a.rect_packed[1], a.rect_packed[2], a.rect_packed[3], kRectFreshSlack);
+    a.fresh_host[0] = in ? a.seq : 0;
+}
 
 __global__ __launch_bounds__(256) void emba_post_warp_a_kernel(PostWarpParams p)
 {
@@ -1241,10 +1362,10 @@ __device__ __forceinline__ void active_write_block(long blk, const ActiveWritePa
             if (lane == 0) { int* bx = s_bx[wv]; bx[0] = xmin; bx[1] = ymin; bx[2] = xmax; bx[3] = ymax; }
             __syncthreads();
             if (threadIdx.x == 0) {
-                a.rect_out[0] = min(min(s_bx[0][0], s_bx[1][0]), min(s_bx[2][0], s_bx[3][0]));
-                a.rect_out[1] = min(min(s_bx[0][1], s_bx[1][1]), min(s_bx[2][1], s_bx[3][1]));
-                a.rect_out[2] = max(max(s_bx[0][2], s_bx[1][2]), max(s_bx[2][2], s_bx[3][2]));
-                a.rect_out[3] = max(max(s_bx[0][3], s_bx[1][3]), max(s_bx[2][3], s_bx[3][3]));
+                const int bx0 = min(min(s_bx[0][0], s_bx[1][0]), min(s_bx[2][0], s_bx[3][0])), by0 = min(min(s_bx[0][1], s_bx[1][1]), min(s_bx[2][1], s_bx[3][1]));
+                const int bx1 = max(max(s_bx[0][2], s_bx[1][2]), max(s_bx[2][2], s_bx[3][2])), by1 = max(max(s_bx[0][3], s_bx[1][3]), max(s_bx[2][3], s_bx[3][3]));
+                a.rect_out[0] = bx0; a.rect_out[1] = by0; a.rect_out[2] = bx1; a.rect_out[3] = by1;
+                publish_texel_verdict(a, bx0, by0, bx1, by1);
             }
         }
         if (threadIdx.x == 0) {
@@ -1395,7 +1516,7 @@ __device__ __forceinline__ uint32_t active_gather_prefix(const ActiveWriteParams
     if (blk == 0 && tid == 0) {
         uint32_t ni = 0; int xmin = 0x7FFFFFFF, ymin = 0x7FFFFFFF, xmax = -1, ymax = -1;
         for (int w = 0; w < NW; ++w) { ni += (uint32_t)s_pub[w][0]; xmin = min(xmin, s_pub[w][1]); ymin = min(ymin, s_pub[w][2]); xmax = max(xmax, s_pub[w][3]); ymax = max(ymax, s_pub[w][4]); }
-        if (a.blk_rect) { a.rect_out[0] = xmin; a.rect_out[1] = ymin; a.rect_out[2] = xmax; a.rect_out[3] = ymax; }
+        if (a.blk_rect) { a.rect_out[0] = xmin; a.rect_out[1] = ymin; a.rect_out[2] = xmax; a.rect_out[3] = ymax; publish_texel_verdict(a, xmin, ymin, xmax, ymax); }
         a.total_P[0] = P; a.total_inl[0] = ni;
         if (a.total_P_host) a.total_P_host[0] = (int)P;
         if (a.total_inl_host) a.total_inl_host[0] = (int)ni;
@@ -1556,13 +1677,12 @@ __device__ __forceinline__ void prep_block(long blk, int32_t* __restrict__ count
 // The control poses travel BY VALUE in the kernel arguments (K <= kInlineKnots: no staging copy, no dependency on another block);
 // larger K reads them from `knots_dev`, which the host has copied there before the launch.
 // err_next: the status word of the NEXT evaluation, cleared here (this launch's pose threads may already be setting bits of err).
-constexpr int kInlineKnots = 104;
-struct InlineKnots { double q[4 * kInlineKnots]; };
 struct PrepPoseTexelParams {
     int32_t* count; long npix; double* pixacc; int W, H; int n_prep;
     const int64_t* batch_t_ns; int nb; int K; int64_t t0_ns, dt_ns; double* pose; int* err; int* err_next; int n_pose; double* seg;
     const double* knots_dev; double* knots_out; int inline_knots;
     int n_tex; const double* Gx; const double* Gy; const int* rect; double* texel;
+    int* rect_packed;   // n_tex != 0: the box the texels are packed for from now on (= rect), what the warp kernel trusts
 };
 
 __global__ __launch_bounds__(256) void emba_prep_pose_texel_kernel(PrepPoseTexelParams p, InlineKnots kn)
@@ -1572,6 +1692,7 @@ __global__ __launch_bounds__(256) void emba_prep_pose_texel_kernel(PrepPoseTexel
     const int b = (int)blockIdx.x;
     if (b == 0) {   // (whatever block 0's role is; none of the roles below has a barrier)
         if (threadIdx.x == 255) p.err_next[0] = 0;
+        if (p.n_tex && threadIdx.x >= 248 && threadIdx.x < 252) p.rect_packed[threadIdx.x - 248] = p.rect[threadIdx.x - 248];   // (the texel blocks read rect, the warp kernel rect_packed)
         if (p.inline_knots && p.knots_out) for (int i = (int)threadIdx.x - 64; i >= 0 && i < 4 * p.K; i += 192) p.knots_out[i] = kn.q[i];   // (for whoever reads the device copy later)
     }
     if (b < p.n_pose) {

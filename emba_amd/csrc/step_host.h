@@ -302,13 +302,31 @@ emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, 
     const bool seg_records = c->order.tile_order || c->ev.segpose;
     q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
     q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
-    STEP_TRY(stage_knots(c, knots, K, q, kn));
-    q.n_tex = (c->ev.use_texel == 3) ? 1024 : 0;
+    // texels are packed when they are stale, not in every evaluation: another map, or the last formed box has left the packed one (h_pinned[5]: the verdict of
+    // the active-set write that reduced it — it precedes the sequence words, so once c->seq is there it is this step's)
+    const bool map_owned = c->map_is_trial || !c->map_bound;
+    const bool stale = texels_stale(map_owned, c->map_version, c->packed_version, ((volatile int*)c->h_pinned)[5], c->seq);
+    q.n_tex = texel_blocks(c->ev.use_texel, stale);
+    if (q.n_tex) c->packed_version = c->map_version;
+    c->ev.texels_packed = q.n_tex != 0;
     q.Gx = c->d_Gx; q.Gy = c->d_Gy;
-    q.rect = c->d_rect.as<int>();
+    q.rect = c->d_rect.as<int>(); q.rect_packed = c->d_rect.as<int>() + 4;
     q.texel = c->d_texel.as<double>();
+    if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }   // (no launch in front: an empty first interval)
+    c->ev.prep_in_warp = prep_inside_warp(c->step_prep, c->order.tile_order, c->ev.segpose, (int)K, kInlineKnots, c->win.n_sorted, n_prep_blk, q.n_tex, c->ev.use_texel);
+    if (c->ev.prep_in_warp) {      // workgroup 0 of the warp launch forms the segment records and takes over block 0's duties
+        memcpy(c->seg_knots.q, knots, (size_t)4 * K * sizeof(double));
+        InlineSegParams& h = c->seg_inline;
+        h.seg = c->d_seg.as<double>(); h.seg_bytes = (unsigned)((size_t)kSegStride * (K - 1) * sizeof(double));
+        if (++c->seg_seq == 0) ++c->seg_seq;      // (0 is what the flag word starts at)
+        h.flag = c->d_seg_flag.as<unsigned>(); h.seq = c->seg_seq;
+        h.K = (int)K; h.polls = c->step_prep_polls;
+        h.fallbacks = c->d_seg_flag.as<unsigned>() + 32;
+        h.err_next = q.err_next; h.knots_out = c->d_knots.as<double>();
+        return EMBA_OK;
+    }
+    STEP_TRY(stage_knots(c, knots, K, q, kn));
     if (q.n_pose + q.n_tex + q.n_prep == 0) q.n_prep = 1;   // (an empty window on clean lines: block 0 still clears the next status word)
-    if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }
     hipLaunchKernelGGL(emba_prep_pose_texel_kernel, dim3((unsigned)(q.n_pose + q.n_tex + q.n_prep)), dim3(256), 0, s, q, kn);
     return EMBA_OK;
 }
@@ -325,7 +343,7 @@ emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
     p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
     p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>();
     p.texel = c->ev.use_texel ? c->d_texel.as<double>() : nullptr;
-    p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() : nullptr;
+    p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() + 4 : nullptr;      // the box the texels are packed for
     p.W = c->W; p.H = c->H;
     p.Gx = c->d_Gx; p.Gy = c->d_Gy;
     p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy;
@@ -345,6 +363,7 @@ emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
     p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->order.n_chunks; p.chunks_linear = c->order.chunks_lpt ? 1 : 0;
     if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
     if (tile) launch_warp_tiled(c->order.tile_shape, dim3((unsigned)grid8(c->order.n_chunks)), s, p);
+    else if (c->ev.prep_in_warp) hipLaunchKernelGGL(emba_warp_residual_inline_kernel, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p, c->seg_inline, c->seg_knots);
     else if (c->ev.segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
     else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
     if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[1], s)); c->kt_warp_valid = true; c->kt_valid[c->kt_slot][0] = true; }
@@ -481,7 +500,8 @@ void launch_post_warp_a(emba_ctx* c, int32_t thres, const FormOpts& opt, const u
     q.active_bits = c->d_active_bits.as<uint8_t>(); q.pack_head = c->d_pack; q.head_len = aw.head_len;
     aw.bits_head_done = 1;
     q.blk_rect = c->d_blk_rect.as<int>(); q.W = c->W;
-    aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the texel rectangle of the NEXT evaluation
+    aw.blk_rect = c->d_blk_rect.as<int>(); aw.rect_out = c->d_rect.as<int>();   // the box of this evaluation's pixels: what the next pack of the texels covers
+    aw.rect_packed = c->d_rect.as<int>() + 4; aw.fresh_host = c->h_pinned_dev + 5;   // ... and whether the packed texels still cover it (step_rule.h: texels_stale)
     hipLaunchKernelGGL(emba_post_warp_a_kernel, dim3((unsigned)(c->n_ablk + c->win.n_fblk)), dim3(256), 0, c->stream, q);
     aw.blk_cnt = c->d_ablk_cnt.as<uint32_t>(); aw.fblk_cnt = c->d_fblk_cnt.as<uint32_t>(); aw.n_fblk = c->win.n_fblk;
     aw.total_P = q.total_P; aw.total_P_host = q.total_P_host;

@@ -10,6 +10,13 @@
 
 #include <algorithm>
 
+// (the containment rule below is also what the active-set write evaluates on the device)
+#if defined(__HIPCC__)
+#define EMBA_RULE_HD __host__ __device__
+#else
+#define EMBA_RULE_HD
+#endif
+
 namespace emba {
 
 // The pack of K control poses: [A11 (3K)^2 | b1 (3K) | 5 doubles per active pixel (A22 | b2)] — what formNormalEq leaves, the solvers read and exchange 2 carries.
@@ -36,6 +43,42 @@ inline int hessian_source(int texel_mode, size_t n_sorted, size_t npix)
 // 10 M on 2048x4096 / K = 256 940 -> 861.  (Round 1 had measured the opposite at 1 M events, + 6 us, on a kernel that was then VALU-heavier in
 // other places; option segpose = 1 keeps the per-batch table for comparison.)  segpose_mode: option segpose — 0 auto = yes, 1 no, 2 yes.
 inline bool segpose_in_pixel_order(bool tile_order, int segpose_mode) { return !tile_order && (segpose_mode ? segpose_mode == 2 : true); }
+
+// The packed texels (source 3) describe ONE map and ONE rectangle.  They are packed again when either no longer holds, not in every evaluation: on the same map and
+// inside the same rectangle the pack writes the same bytes (a poses-only refinement, every re-evaluation on one map, the benchmark).
+//   the map: the host counts every call that changes or rebinds the planes (map_version) and remembers which count the last pack read.  A map the caller bound is the
+//   caller's memory and may change without a call: it is never taken for unchanged.
+//   the rectangle: the pack covers the last formed evaluation's box grown by kRectMargin, and the warp kernel trusts the PACKED rectangle only (outside it: the
+//   stencil, slow, never wrong).  The active-set write's last block, which reduces the new box, compares it on the device with the packed one and publishes the
+//   verdict beside the counts the host waits for anyway (no round trip; the host never reads a rectangle): fresh while the new box stays inside the packed box grown
+//   by kRectFreshSlack — half the margin, so that the next evaluation's pixels may move as far again before one of them meets the stencil.
+constexpr int kRectMargin = 24;
+constexpr int kRectFreshSlack = 12;
+static_assert(kRectFreshSlack <= kRectMargin, "texels exist only inside the packed box grown by kRectMargin");
+// boxes {xmin, ymin, xmax, ymax}, inclusive, empty if max < min.  An empty new box needs no texels; nothing lies inside an empty packed box.
+EMBA_RULE_HD inline bool rect_contained(int nx0, int ny0, int nx1, int ny1, int px0, int py0, int px1, int py1, int slack)
+{
+    if (nx1 < nx0 || ny1 < ny0) return true;
+    if (px1 < px0 || py1 < py0) return false;
+    return nx0 >= px0 - slack && ny0 >= py0 - slack && nx1 <= px1 + slack && ny1 <= py1 + slack;
+}
+// verdict_seq: the word the last block publishes — the step's sequence number where the new box is contained, 0 where it is not; step_seq: the host's number of the
+// last step that reduced a box.  They differ while that step's verdict has not arrived (or no step has run): not known to be fresh.
+inline bool texels_stale(bool map_owned, uint32_t map_version, uint32_t packed_version, int verdict_seq, int step_seq)
+{
+    return !map_owned || map_version != packed_version || step_seq == 0 || verdict_seq != step_seq;
+}
+// The texel blocks of the launch in front of the warp kernel: 1024 for source 3 with stale texels, none otherwise
+inline int texel_blocks(int hessian_src, bool stale) { return (hessian_src == 3 && stale) ? 1024 : 0; }
+
+// No launch in front of the warp kernel at all (option step_prep: 0, the default, the launch always; 1 where this rule allows — measured at 1 M events: the hand-off
+// costs the warp kernel what the launch cost): what is left of it once the lines are clean and the texels fresh is
+// one block that writes K - 1 segment records; workgroup 0 of the warp kernel writes them instead and hands them to the others (kernels.h: inline_seg_*).  Pixel order
+// with segment records, the control poses in the kernel arguments, a window with entries, and nothing else for the launch to do.
+inline bool prep_inside_warp(int step_prep, bool tile_order, bool segpose, int K, int inline_knots, size_t n_sorted, int n_prep_blk, int n_tex_blk, int hessian_src)
+{
+    return step_prep != 0 && !tile_order && segpose && K <= inline_knots && n_sorted > 0 && n_prep_blk == 0 && n_tex_blk == 0 && hessian_src != 1;
+}
 
 // Blocks of the clearing pass over count map + accumulator lines in front of an evaluation.  It is only needed when the previous evaluation's sums are still
 // in their lines (it was never formed by the resident step, whose gather clears them behind itself); the count map's entries are stamped and need no clearing

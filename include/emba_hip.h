@@ -453,6 +453,8 @@ emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
  * Defaults are what the measurements under profiles/ chose.
  *   order          0 auto | 1 pixel order | 2 tile order of the device's event stream (takes effect at the next evaluation: the order is rebuilt)
  *   texel          0 auto | 1 pack every texel | 2 3x3 stencil on the fly | 3 pack inside the previous footprint's rectangle
+ *                  (3: packed when the map has changed — upload, bind, update, accept, reject, blur — or the footprint has left the packed rectangle, not in every
+ *                  evaluation; a map bound with emba_bind_map_dev is the caller's memory and counts as changed at every evaluation)
  *   segpose        0 auto (= 2) | 1 per-batch pose table in pixel order | 2 per-event pose from the K-1 segment records
  *   gram_tags      1 the pixel order's 8-B tag stream lets the Gram kernel skip dead slots | 0 decide from the records
  *   step_ep        1 emba_step compacts the residuals into ep (what evaluateDataError returns): in the tail of its Gram launch, or for windows of more than
@@ -460,6 +462,11 @@ emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
  *   step_fast      1 emba_step zeroes the per-pixel sums behind their reader (no clearing pass) | 0 keeps the clearing pass
  *   step_gather    0 sweeping active-set write | 1 list-driven gather as a launch | 2 (default) inside the Gram kernel | 3 inside it at every size
  *   step_one_set   1 emba_step keeps one record set | 0 alternates between two like an LM loop
+ *   step_prep      0 (default) the launch in front of the warp kernel always | 1 none on clean accumulator lines and fresh texels (pixel order, segpose, K <= 104):
+ *                  workgroup 0 of the warp kernel forms the K-1 segment records and hands them to the others inside the launch (measured: no faster).  step_prep_polls (1024; 0 ... 65536): polls a wave waits for
+ *                  the records before it forms its own (0: every wave does; same bits).
+ *                  emba_get_option, read-only, of the last evaluation: "prep_in_warp" (no launch in front), "texels_packed"
+ *                  (its launch packed texels); "step_prep_fallbacks": waves that formed their own records since the context was created (drains the stream)
  *   gram_sparse    -1 auto (by the active-pixel count of the window's last equations) | 0 | 1 the Gram kernel's form for slot streams with few live records (pixel
  *                  order on a large panorama): stages of 128 tags, the live slots compacted, only their records fetched;  gram_sparse_chunk 1 ... 8 (4): its slots per wave, x 1024
  *   gather_waves   0 auto (4) | 1 | 2 | 4 waves of a Gram workgroup do its slice of the gather
