@@ -99,6 +99,8 @@ SIGNATURES = {
     "emba_set_events_seq_shard": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "emba_seq_halo": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _i64p, C.c_size_t, _szp]),
     "emba_seq_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _u8p, _i64p]),
+    "emba_seq_filter": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_uint64)]),
+    "emba_seq_hot_pixels": (C.c_int, [C.c_void_p, _u8p]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -141,6 +143,7 @@ SIGNATURES = {
     "emba_group_seq_size": (C.c_int, [C.c_void_p, _szp]),
     "emba_group_seq_free": (C.c_int, [C.c_void_p]),
     "emba_group_seq_window": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _szp, _szp]),
+    "emba_group_seq_filter": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_uint64)]),
     "emba_group_set_events_seq": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t]),
     "emba_group_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_group_upload_map": (C.c_int, [C.c_void_p, _dp, _dp]),

@@ -316,8 +316,14 @@ struct emba_ctx {
     DevBuf d_img, d_nsrc;
     // the whole (down-sampled) event sequence of a sliding-window run (sequence_kernels.h): uploaded once by emba_seq_upload, registered window by window by
     // emba_set_events_seq, which builds the window's structure from [beg, end) of these arrays and keeps no pointer into them.  raw: one chunk of the upload;
-    // halo_*: emba_set_events_seq_shard's passes — last event per sensor pixel, halo flags and positions per event in front of the shard
-    struct { DevBuf x, y, pol, t, raw, status, halo_last, halo_flag, halo_pos; size_t n = 0; } evseq;
+    // halo_*: emba_set_events_seq_shard's passes — last event per sensor pixel, halo flags and positions per event in front of the shard.
+    // emba_seq_filter: x2 ... t2 take the survivors and are swapped with x ... t (never compacted in place); f_start: per-pixel starts of the pixel-sorted
+    // sequence (S + 1), f_hot: the last filter's hot-pixel mask (S bytes, have_hot), f_sums: its eight 64-bit counters.  have: a sequence is resident (an
+    // upload succeeded, also one of no events, and no filter has removed every event since)
+    struct {
+        DevBuf x, y, pol, t, raw, status, halo_last, halo_flag, halo_pos; size_t n = 0;
+        DevBuf x2, y2, pol2, t2, f_start, f_hot, f_sums; bool have = false, have_hot = false;
+    } evseq;
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

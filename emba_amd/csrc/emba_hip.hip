@@ -1755,7 +1755,9 @@ extern "C" emba_status emba_seq_free(emba_ctx* c)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->evseq.x.reset(); c->evseq.y.reset(); c->evseq.pol.reset(); c->evseq.t.reset(); c->evseq.raw.reset();
     c->evseq.halo_last.reset(); c->evseq.halo_flag.reset(); c->evseq.halo_pos.reset();
-    c->evseq.n = 0;
+    c->evseq.x2.reset(); c->evseq.y2.reset(); c->evseq.pol2.reset(); c->evseq.t2.reset();
+    c->evseq.f_start.reset(); c->evseq.f_hot.reset(); c->evseq.f_sums.reset();
+    c->evseq.n = 0; c->evseq.have = false; c->evseq.have_hot = false;
     return EMBA_OK;
 }
 
@@ -1777,7 +1779,7 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     HIP_TRY(c, hipStreamSynchronize(s));
     const size_t rate = sampling_rate >= 2 ? (size_t)sampling_rate : 1;      // emba.cpp:282
     const size_t n_kept = n / rate;
-    c->evseq.n = 0;      // (a second upload replaces the first; a failed one leaves none)
+    c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
     emba_status st;
     if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRawBytes)) || (st = ensure<uint32_t>(c, c->evseq.status, 16)) ||
         (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
@@ -1807,7 +1809,7 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h_err[0] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[0], c->sw, c->sh);
     if (h_err[1] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[1]);
-    c->evseq.n = n_kept;
+    c->evseq.n = n_kept; c->evseq.have = true;
     if (n_kept_out) *n_kept_out = n_kept;
     return EMBA_OK;
 }
@@ -1949,6 +1951,124 @@ extern "C" emba_status emba_seq_get(emba_ctx* c, size_t beg, size_t end, uint16_
     if (pol && (st = d2h_pageable(c, pol, c->evseq.pol.as<uint8_t>() + beg, m))) return st;
     if (t_ns && (st = d2h_pageable(c, t_ns, c->evseq.t.as<int64_t>() + beg, m * 8))) return st;
     return EMBA_OK;
+}
+
+// ---- sensor-noise filters on the resident sequence (sequence_kernels.h: emba_filter_*; the rule: include/emba_hip.h) ------------------------------
+namespace {
+// thr = mean + sigma sqrt(var) over the pixels with events, from the exact integer sums: every operation rounded on its own (no contraction), so that
+// the host form (emba_amd.io.filter_events) and the loop reference of the tests get the same bits.
+double hot_threshold(uint64_t s1, uint64_t m, uint64_t s2, double sigma)
+{
+#pragma clang fp contract(off)
+    const double mean = (double)s1 / (double)m;
+    const double msq = (double)s2 / (double)m;
+    const double mean2 = mean * mean;
+    double var = msq - mean2;
+    if (var < 0.0) var = 0.0;
+    const double sd = std::sqrt(var);
+    const double spread = sigma * sd;
+    return mean + spread;
+}
+}  // namespace
+
+// Scratch: the sort pairs, flags and positions of the order preparation (ord.keys / vals / flags / pos, + dev_scan's and dev_sort's) — a registered window
+// keeps nothing in them: set_events_core copies what it sorted into the pm-order arrays, prepare_order into the device order and the record slots, and a
+// re-binning rebuilds all of it from the pm-order.  What has to outlive the call (starts, hot mask, counters, the fresh arrays) is evseq's own.
+extern "C" emba_status emba_seq_filter(emba_ctx* c, double hot_sigma, int64_t refractory_ns, int64_t support_ns, int32_t sampling_rate, uint64_t* stats)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->evseq.have) return fail(c, EMBA_ERR_STATE, "no resident sequence (emba_seq_upload first)");
+    if (std::isnan(hot_sigma)) return fail(c, EMBA_ERR_INVALID_ARG, "hot_sigma is NaN");
+    const size_t n = c->evseq.n, S = c->S;
+    if (n >= 0x100000000ull) return fail(c, EMBA_ERR_INVALID_ARG, "emba_seq_filter: %zu events are too many for the 32-bit event indices of its sort (limit 2^32 - 1)", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const bool hot_on = hot_sigma > 0.0, filters_on = hot_on || refractory_ns > 0 || support_ns > 0;
+    const size_t rate = sampling_rate >= 2 ? (size_t)sampling_rate : 1;
+    const bool sorts = filters_on && n, rewrites = filters_on || rate > 1;      // (neither: the sequence stays exactly as it is)
+    // Everything that can fail for want of memory comes first — the scratch of the sort and of the scans included, and the fresh arrays at their upper bound
+    // n / rate — so that a failure leaves the sequence AND the previous filter's hot mask as they were.
+    emba_status st;
+    if ((st = ensure<uint8_t>(c, c->evseq.f_hot, S)) || (st = ensure<uint64_t>(c, c->evseq.f_sums, 8)) || (st = ensure<uint32_t>(c, c->evseq.status, 16))) return st;
+    if (sorts) {
+        const size_t ntiles = (n + kSortTile - 1) / kSortTile, n_scan = std::max(n, 256 * ntiles);
+        if ((st = ensure_sort_pairs(c, n)) || (st = ensure<uint32_t>(c, c->ord.flags, n)) || (st = ensure<uint32_t>(c, c->ord.pos, n)) ||
+            (st = ensure<uint32_t>(c, c->evseq.f_start, S + 1)) || (st = ensure<uint32_t>(c, c->ord.sort_hist, 256 * ntiles)) ||
+            (st = ensure<uint32_t>(c, c->ord.scan_sums, (n_scan + kScanTile - 1) / kScanTile + 1)) ||
+            (st = ensure<uint32_t>(c, c->ord.scan_offs, (n_scan + kScanTile - 1) / kScanTile + 2)))
+            return st;
+    }
+    const size_t n_fresh = std::max<size_t>(n / rate, 1);
+    if (rewrites && ((st = ensure<uint16_t>(c, c->evseq.x2, n_fresh)) || (st = ensure<uint16_t>(c, c->evseq.y2, n_fresh)) ||
+                     (st = ensure<uint8_t>(c, c->evseq.pol2, n_fresh)) || (st = ensure<int64_t>(c, c->evseq.t2, n_fresh))))
+        return st;
+    uint8_t* d_hot = c->evseq.f_hot.as<uint8_t>();
+    unsigned long long* d_sums = c->evseq.f_sums.as<unsigned long long>();   // [0] pixels with events [1] sum c^2 [2] hot pixels [3] their events [4] refractory [5] support
+    uint32_t* d_tot = c->evseq.status.as<uint32_t>() + 8;
+    c->evseq.have_hot = false;     // (from here on the mask is this filter's: all zero unless the hot test below runs)
+    HIP_TRY(c, hipMemsetAsync(d_hot, 0, S, s));
+    HIP_TRY(c, hipMemsetAsync(d_sums, 0, 64, s));
+    unsigned long long h_sums[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t n_surv = n;
+    const uint16_t *x = c->evseq.x.as<uint16_t>(), *y = c->evseq.y.as<uint16_t>();
+    const uint8_t* pol = c->evseq.pol.as<uint8_t>();
+    const int64_t* t = c->evseq.t.as<int64_t>();
+    const uint32_t *d_keep = nullptr, *d_pos = nullptr;
+    if (sorts) {
+        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
+        uint32_t *keep = c->ord.flags.as<uint32_t>(), *pos = c->ord.pos.as<uint32_t>(), *start = c->evseq.f_start.as<uint32_t>();
+        hipLaunchKernelGGL(emba_pixel_keys_kernel, dim3(nblocks(n)), dim3(256), 0, s, x, y, (long)n, c->sw, (const uint16_t*)nullptr, (const uint16_t*)nullptr, 0L, k0, v0);
+        if ((st = dev_sort(c, &k0, &v0, &k1, &v1, n, bits_for(S)))) return st;
+        hipLaunchKernelGGL(emba_filter_starts_kernel, dim3(nblocks(n)), dim3(256), 0, s, (const uint32_t*)k0, (long)n, (long)S, start);
+        if (hot_on) {
+            const unsigned grid = (unsigned)std::min<size_t>(nblocks(S), 1024);
+            hipLaunchKernelGGL(emba_filter_pixel_sums_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)start, (long)S, d_sums);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(h_sums, d_sums, 16, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            if (!h_sums[0]) return fail(c, EMBA_ERR_STATE, "emba_seq_filter: %zu events on no pixel", n);
+            const double thr = hot_threshold(n, h_sums[0], h_sums[1], hot_sigma);
+            hipLaunchKernelGGL(emba_filter_hot_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)start, (long)S, thr, d_hot, d_sums);
+        }
+        hipLaunchKernelGGL(emba_filter_flags_kernel, dim3(nblocks(n)), dim3(256), 0, s, (const uint32_t*)k0, (const uint32_t*)v0, t, (long)n, c->sw, c->sh,
+                           (const uint32_t*)start, (const uint8_t*)d_hot, refractory_ns, support_ns, keep, d_sums);
+        HIP_TRY(c, hipGetLastError());
+        if ((st = dev_scan(c, keep, pos, n, d_tot))) return st;
+        uint32_t h_tot = 0;
+        HIP_TRY(c, hipMemcpyAsync(&h_tot, d_tot, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(h_sums, d_sums, 64, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (h_tot > n) return fail(c, EMBA_ERR_STATE, "emba_seq_filter: %u survivors of %zu events", h_tot, n);
+        n_surv = h_tot; d_keep = keep; d_pos = pos;
+    }
+    const size_t n_kept = n_surv / rate;
+    if (rewrites) {
+        if (n_kept) {
+            hipLaunchKernelGGL(emba_filter_gather_kernel, dim3(nblocks(n)), dim3(256), 0, s, x, y, pol, t, (long)n, d_keep, d_pos, (long)rate, (long)n_kept,
+                               c->evseq.x2.as<uint16_t>(), c->evseq.y2.as<uint16_t>(), c->evseq.pol2.as<uint8_t>(), c->evseq.t2.as<int64_t>());
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(s));
+            std::swap(c->evseq.x, c->evseq.x2); std::swap(c->evseq.y, c->evseq.y2); std::swap(c->evseq.pol, c->evseq.pol2); std::swap(c->evseq.t, c->evseq.t2);
+        }
+        c->evseq.n = n_kept;
+        if (!n_kept) c->evseq.have = false;      // every event removed: emba_seq_filter finds no sequence until the next upload (the other calls see n = 0)
+    }
+    c->evseq.have_hot = true;
+    if (stats) {
+        stats[0] = n; stats[1] = h_sums[2]; stats[2] = h_sums[3]; stats[3] = h_sums[4]; stats[4] = h_sums[5]; stats[5] = n_kept;
+    }
+    return EMBA_OK;
+}
+
+extern "C" emba_status emba_seq_hot_pixels(emba_ctx* c, uint8_t* mask_host)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!mask_host) return fail(c, EMBA_ERR_INVALID_ARG, "mask NULL");
+    if (!c->evseq.have_hot) return fail(c, EMBA_ERR_STATE, "no filter has run on this context (emba_seq_filter first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return d2h_pageable(c, mask_host, c->evseq.f_hot.as<uint8_t>(), c->S);
 }
 
 // ---- 3x3 median blur of the initial map (emba.cpp:357-364) -----------------------------------------------------------------------

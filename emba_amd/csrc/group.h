@@ -467,6 +467,16 @@ emba_status emba_group_seq_free(emba_group* g)
     return EMBA_OK;
 }
 
+// emba_seq_filter on every rank's own copy, side by side (equal copies and a deterministic rule: equal results; the statistics are rank 0's)
+emba_status emba_group_seq_filter(emba_group* g, double hot_sigma, int64_t refractory_ns, int64_t support_ns, int32_t sampling_rate, uint64_t* stats)
+{
+    if (!g) return EMBA_ERR_INVALID_ARG;
+    std::vector<uint64_t> st6((size_t)g->n * 6, 0);
+    { emba_status st = gpool(g, [&](int r) { return emba_seq_filter(g->ctx[r], hot_sigma, refractory_ns, support_ns, sampling_rate, &st6[(size_t)r * 6]); }); if (st) return st; }
+    if (stats) std::copy(st6.begin(), st6.begin() + 6, stats);
+    return EMBA_OK;
+}
+
 // (every rank holds the same sequence and the search is deterministic: rank 0's answer is everybody's)
 emba_status emba_group_seq_window(emba_group* g, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end)
 {

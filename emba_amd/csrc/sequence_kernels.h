@@ -6,6 +6,8 @@
 //   * emba_median3_kernel      cv::medianBlur(., ., 3) on a float32 copy of a plane (emba.cpp:357-364)
 //   * emba_halo_*_kernel       the per-pixel halo of a time shard of a window: for every sensor pixel the last event in front of the
 //                              rank's range, in three passes — last event per pixel (atomicMax), flags + scan (order_kernels.h), gather
+//   * emba_filter_*_kernel     hot-pixel, refractory and neighbour-support filters on the raw sequence (no counterpart in the reference): one stable
+//                              sort by sensor pixel (order_kernels.h), per-pixel starts, keep-flags per event, scan, gather into fresh arrays
 // All of it is bandwidth-bound, once-per-run or once-per-window work: one thread per element, coalesced loads, no tuning.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -86,6 +88,122 @@ __global__ void emba_halo_gather_kernel(const uint16_t* __restrict__ x, const ui
     const uint32_t j = pos[i];
     hx[j] = x[i]; hy[j] = y[i];
     hbt[j] = batch_mid_ns_dev(t[100 * b], t[100 * b + 99]);
+}
+
+// ---- sensor-noise filters on the raw resident sequence (emba_seq_filter; the rule: include/emba_hip.h) -------------------------------
+// The sequence is sorted by (sensor pixel, index) with the radix sort of order_kernels.h (keys p = y sw + x, values k); everything below works on that
+// order.  Every event is judged from the RAW sequence, so the three tests are independent of each other and of the order in which they run.
+
+// start[p], p in [0, S]: the first sorted entry of pixel p (start[S] = n); c[p] = start[p + 1] - start[p].  One coalesced pass over the n >= 1 sorted keys:
+// the head of a pixel's chain (entry i whose predecessor has a smaller key) writes i to every pixel in (keys[i - 1], keys[i]] — the pixels without events in
+// between begin where the next chain begins — and the last entry writes n to every pixel behind its own.  Every p in [0, S] is written exactly once.
+__global__ void emba_filter_starts_kernel(const uint32_t* __restrict__ keys, long n, long S, uint32_t* __restrict__ start)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long key = keys[i], prev = i > 0 ? (long)keys[i - 1] : -1L;
+    for (long p = prev + 1; p <= key && p <= S; ++p) start[p] = (uint32_t)i;
+    if (i == n - 1)
+        for (long p = key + 1; p <= S; ++p) start[p] = (uint32_t)n;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// sums[0] += pixels with c > 0, sums[1] += sum of c^2 (exact: c < 2^32, the sum <= n^2 < 2^64).  One atomic pair per wave.
+__global__ __launch_bounds__(256) void emba_filter_pixel_sums_kernel(const uint32_t* __restrict__ start, long S, unsigned long long* __restrict__ sums)
+{
+    unsigned long long m = 0, s2 = 0;
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < S; p += (long)gridDim.x * 256) {
+        const unsigned long long c = start[p + 1] - start[p];
+        m += c ? 1ull : 0ull;
+        s2 += c * c;
+    }
+    m = wave_sum_u64(m); s2 = wave_sum_u64(s2);
+    if ((threadIdx.x & 63) == 0) { atomicAdd(sums + 0, m); atomicAdd(sums + 1, s2); }
+}
+
+// hot[p] = double(c[p]) > thr (thr: computed by the host from the exact sums, one rounding per operation); sums[2] += hot pixels, sums[3] += their events.
+__global__ __launch_bounds__(256) void emba_filter_hot_kernel(const uint32_t* __restrict__ start, long S, double thr, uint8_t* __restrict__ hot,
+                                                              unsigned long long* __restrict__ sums)
+{
+    unsigned long long np = 0, ne = 0;
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < S; p += (long)gridDim.x * 256) {
+        const uint32_t c = start[p + 1] - start[p];
+        const bool h = (double)c > thr;
+        hot[p] = h ? 1 : 0;
+        if (h) { np += 1; ne += c; }
+    }
+    np = wave_sum_u64(np); ne = wave_sum_u64(ne);
+    if ((threadIdx.x & 63) == 0 && np) { atomicAdd(sums + 2, np); atomicAdd(sums + 3, ne); }
+}
+
+// One thread per SORTED entry r (pixel p = keys[r], event k = vals[r]; a pixel's entries are its events in index order, the sort is stable).
+//   hot         hot[p]
+//   refractory  entry r - 1 is prev(k) when it has the same pixel: fails iff t[k] - t[prev] < refr_ns                     (refr_ns <= 0: off)
+//   support     per neighbouring pixel q inside the sensor and not hot: the largest entry of q's chain with index < k (binary search in vals over
+//               [start[q], start[q + 1])), passes iff t[k] - t[that] <= supp_ns for some q                                     (supp_ns <= 0: off)
+// Neighbouring lanes hold neighbouring entries of one chain: they search the same ranges, so the probes hit the same cache lines.
+// keep[k] (the event's ORIGINAL index) = 1 iff it fails none; sums[4] += events failing refractory, sums[5] += events failing support (one atomic per wave).
+__global__ __launch_bounds__(256) void emba_filter_flags_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, const int64_t* __restrict__ t,
+                                                                long n, int sw, int sh, const uint32_t* __restrict__ start, const uint8_t* __restrict__ hot,
+                                                                int64_t refr_ns, int64_t supp_ns, uint32_t* __restrict__ keep, unsigned long long* __restrict__ sums)
+{
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    bool f_ref = false, f_sup = false;
+    if (r < n) {
+        const uint32_t p = keys[r], k = vals[r];
+        const int64_t tk = t[k];
+        if (refr_ns > 0 && r > 0 && keys[r - 1] == p) f_ref = tk - t[vals[r - 1]] < refr_ns;
+        if (supp_ns > 0) {
+            const int px = (int)(p % (uint32_t)sw), py = (int)(p / (uint32_t)sw);
+            bool ok = false;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int qx = px + dx, qy = py + dy;
+                    if (ok || (!dx && !dy) || qx < 0 || qx >= sw || qy < 0 || qy >= sh) continue;
+                    const size_t q = (size_t)qy * sw + qx;
+                    if (hot[q]) continue;
+                    const uint32_t base = start[q];
+                    uint32_t lo = base, hi = start[q + 1];
+                    while (lo < hi) {
+                        const uint32_t mid = lo + ((hi - lo) >> 1);
+                        if (vals[mid] < k) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo > base && tk - t[vals[lo - 1]] <= supp_ns) ok = true;
+                }
+            f_sup = !ok;
+        }
+        keep[k] = (hot[p] || f_ref || f_sup) ? 0u : 1u;
+    }
+    const unsigned long long b_ref = __ballot(f_ref), b_sup = __ballot(f_sup);
+    if ((threadIdx.x & 63) == 0) {
+        if (b_ref) atomicAdd(sums + 4, (unsigned long long)__popcll(b_ref));
+        if (b_sup) atomicAdd(sums + 5, (unsigned long long)__popcll(b_sup));
+    }
+}
+
+// The survivors (keep == nullptr: every event), in their order, into FRESH arrays: survivor of rank r = pos[k] (the exclusive scan of keep) goes to slot r, or,
+// with rate > 1, to slot (r + 1) / rate - 1 iff (r + 1) % rate == 0 — the counting loop of emba.cpp:281-304 over the survivors.  cap: slots of the fresh arrays.
+__global__ void emba_filter_gather_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y, const uint8_t* __restrict__ pol, const int64_t* __restrict__ t,
+                                          long n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos, long rate, long cap,
+                                          uint16_t* __restrict__ ox, uint16_t* __restrict__ oy, uint8_t* __restrict__ opol, int64_t* __restrict__ ot)
+{
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    long r = k;
+    if (keep) { if (!keep[k]) return; r = pos[k]; }
+    long dst = r;
+    if (rate > 1) {
+        if ((r + 1) % rate) return;
+        dst = (r + 1) / rate - 1;
+    }
+    if (dst >= cap) return;
+    ox[dst] = x[k]; oy[dst] = y[k]; opol[dst] = pol[k]; ot[dst] = t[k];
 }
 
 // a <- min, b <- max: one exchange of the median network (no branch on data)

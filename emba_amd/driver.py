@@ -32,6 +32,11 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     init_map: str = "given"     # "given": Gx, Gy are the front end's map.  "events": there is none (the reference's init_map_available = false, emba.cpp:333-355,
                                 # fills the map with noise there) — the run starts from a zero map, and the first window is first solved for the map alone from
                                 # its initial control poses (BASettings.refine = "map": well posed where the joint system with G = 0 is singular)
+    # Sensor noise (no counterpart in the reference; the rule: include/emba_hip.h, emba_seq_filter).  All off by default; with any of them on the recording
+    # is filtered once, BEFORE the down-sampling, on the device wherever the sequence is resident (LEGM.filter_sequence), else by io.filter_events.
+    hot_pixel_sigma: float = 0.0    # a pixel is hot when its event count exceeds mean + sigma * std over the pixels that have events
+    refractory_period: float = 0.0  # seconds: an event closer than this behind its pixel's previous event is dropped
+    support_time: float = 0.0       # seconds: an event is kept only if one of its eight neighbours fired at most this long before it
 
 
 @dataclass
@@ -53,6 +58,7 @@ class SequenceResult:
     traj: LinearTrajectory      # the whole trajectory (traj_ptr_)
     windows: list = field(default_factory=list)
     n_events: int = 0           # events of the sequence after down-sampling
+    filter_stats: object = None # with a noise filter on: uint64[6] — events in, hot pixels, events failing hot / refractory / support, events kept
 
 
 def keeps_sequence(model):
@@ -82,7 +88,23 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
     pose_t_ns = np.array([emba_io.ros_time_ns(t) for t in pose_t], dtype=np.int64)      # std::map<ros::Time, SO3d>, pose_manager.cpp:41-80
 
     # event down-sampling, emba.cpp:281-304
-    if resident_sequence:
+    filter_stats = None
+    if seq.hot_pixel_sigma > 0 or seq.refractory_period > 0 or seq.support_time > 0:
+        # sensor noise first, then the down-sampling over the survivors
+        refr_ns, supp_ns = emba_io.ros_time_ns(seq.refractory_period), emba_io.ros_time_ns(seq.support_time)
+        if resident_sequence:
+            model.set_sequence(events, 1)
+            filter_stats = model.filter_sequence(seq.hot_pixel_sigma, refr_ns, supp_ns, seq.event_sampling_rate)
+            n_seq = int(filter_stats[5])
+        else:
+            # (a model that does not know its sensor: any size that holds every event gives the same survivors — a pixel without events supports nobody)
+            sw = getattr(model, "sensor_w", None) or int(np.max(events.x, initial=0)) + 1
+            sh = getattr(model, "sensor_h", None) or int(np.max(events.y, initial=0)) + 1
+            events, filter_stats, _ = emba_io.filter_events(events, sw, sh, seq.hot_pixel_sigma, refr_ns, supp_ns)
+            events = emba_io.downsample_events(events, seq.event_sampling_rate)
+            n_seq = events.size()
+            filter_stats[5] = n_seq
+    elif resident_sequence:
         n_seq = model.set_sequence(events, seq.event_sampling_rate)
     else:
         events = emba_io.downsample_events(events, seq.event_sampling_rate)
@@ -115,7 +137,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         else:
             Gx, Gy = emba_io.median_blur3(Gx), emba_io.median_blur3(Gy)
 
-    out = SequenceResult(None, [], n_seq)
+    out = SequenceResult(None, [], n_seq, filter_stats)
     while t_win_end < t_BA_end + 1_000_000:                                             # :406
         # :409 getEventSubset
         if resident_sequence:

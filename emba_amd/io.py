@@ -281,3 +281,72 @@ def median_blur3(plane):
     p = np.pad(a, 1, mode="edge")
     nine = np.stack([p[dy:dy + h, dx:dx + w] for dy in range(3) for dx in range(3)])
     return np.sort(nine, axis=0)[4].astype(np.float64)
+
+
+# ---- sensor noise (numpy form of emba_seq_filter, include/emba_hip.h; the device form is LEGM.filter_sequence) --------------------------------------
+def hot_pixel_threshold(counts, hot_sigma):
+    """mean + hot_sigma * sqrt(var) of the event counts of the pixels that have events, from exact integer sums; python floats: every operation is
+    rounded on its own, as the rule demands."""
+    c = np.asarray(counts)
+    c = c[c > 0].astype(np.uint64)
+    m, s1, s2 = int(c.size), int(c.sum(dtype=np.uint64)), int((c * c).sum(dtype=np.uint64))
+    mean = float(s1) / float(m)
+    var = float(s2) / float(m) - mean * mean
+    if var < 0.0:
+        var = 0.0
+    return mean + float(hot_sigma) * float(np.sqrt(var))
+
+
+def filter_events(events, sensor_w, sensor_h, hot_sigma=0.0, refractory_ns=0, support_ns=0):
+    """Hot-pixel, refractory and neighbour-support filters on a whole recording (sorted by time), each event judged from the RAW sequence: the rule of
+    emba_seq_filter, vectorised — one stable sort by sensor pixel, then one searchsorted per neighbouring pixel.  Returns (events, stats, hot_mask):
+    the survivors in their order (the SAME packet when every filter is off), stats = uint64[6] (events in, hot pixels, events failing hot, failing
+    refractory, failing support, survivors) and hot_mask = uint8[sensor_w * sensor_h].  No down-sampling here: downsample_events of the result."""
+    sw, sh = int(sensor_w), int(sensor_h)
+    S = sw * sh
+    hot_sigma, refractory_ns, support_ns = float(hot_sigma), int(refractory_ns), int(support_ns)
+    if np.isnan(hot_sigma):
+        raise ValueError("hot_sigma is NaN")
+    x, y = np.asarray(events.x, dtype=np.int64), np.asarray(events.y, dtype=np.int64)
+    t = np.asarray(events.t_ns, dtype=np.int64)
+    n = t.size
+    stats = np.zeros(6, dtype=np.uint64)
+    stats[0] = stats[5] = n
+    hot = np.zeros(S, dtype=bool)
+    if n == 0 or not (hot_sigma > 0 or refractory_ns > 0 or support_ns > 0):
+        return events, stats, hot.astype(np.uint8)
+    if (x >= sw).any() or (y >= sh).any():
+        raise ValueError(f"an event lies outside the {sw}x{sh} sensor")
+    pix = y * sw + x
+    order = np.argsort(pix, kind="stable")                     # (pixel, index): every pixel's events in index order, end to end
+    sp = pix[order]
+    counts = np.bincount(pix, minlength=S)
+    start = np.concatenate([[0], np.cumsum(counts)])
+    if hot_sigma > 0:
+        hot = counts.astype(np.float64) > hot_pixel_threshold(counts, hot_sigma)
+    fail_hot = hot[pix]
+    fail_ref = np.zeros(n, dtype=bool)
+    if refractory_ns > 0:
+        f = (sp[1:] == sp[:-1]) & (t[order[1:]] - t[order[:-1]] < refractory_ns)
+        fail_ref[order[1:][f]] = True
+    fail_sup = np.zeros(n, dtype=bool)
+    if support_ns > 0:
+        comp = sp * n + order                                  # ascending: (pixel, index) as one integer
+        k = np.arange(n, dtype=np.int64)
+        ok = np.zeros(n, dtype=bool)
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if dx == 0 and dy == 0:
+                    continue
+                qx, qy = x + dx, y + dy
+                valid = (qx >= 0) & (qx < sw) & (qy >= 0) & (qy < sh)
+                q = np.where(valid, qy * sw + qx, 0)
+                valid &= ~hot[q]
+                j = np.searchsorted(comp, q * n + k) - 1      # the last entry of (pixel q, index < k), if it lies in q's chain
+                valid &= j >= start[q]
+                ok |= valid & (t - t[order[np.maximum(j, 0)]] <= support_ns)
+        fail_sup = ~ok
+    keep = ~(fail_hot | fail_ref | fail_sup)
+    stats[1], stats[2], stats[3], stats[4], stats[5] = int(hot.sum()), int(fail_hot.sum()), int(fail_ref.sum()), int(fail_sup.sum()), int(keep.sum())
+    out = EventPacket(np.asarray(events.x)[keep], np.asarray(events.y)[keep], np.asarray(events.polarity)[keep], np.asarray(events.t_ns)[keep])
+    return out, stats, hot.astype(np.uint8)

@@ -197,6 +197,21 @@ class LEGM:
         self._check(self._L.emba_seq_get(self._ctx, int(beg), int(end), _p(x, _u16p), _p(y, _u16p), _p(pol, _u8p), _p(t, _i64p)))
         return EventPacket(x, y, pol, t)
 
+    def filter_sequence(self, hot_sigma=0.0, refractory_ns=0, support_ns=0, sampling_rate=1):
+        """Sensor noise out of the resident sequence, on the device (emba_seq_filter: hot pixels, refractory period, neighbour support — each event judged
+        from the raw sequence; then the down-sampling of emba.cpp:281-304 over the survivors).  Returns stats = uint64[6]: events in, hot pixels, events
+        failing hot / refractory / support, events kept.  io.filter_events is the same rule in numpy."""
+        stats = np.zeros(6, np.uint64)
+        self._check(self._L.emba_seq_filter(self._ctx, float(hot_sigma), int(refractory_ns), int(support_ns), int(sampling_rate),
+                                            stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def sequence_hot_pixels(self):
+        """The hot pixels of the last filter_sequence: uint8[sensor_h * sensor_w], 1 = hot."""
+        mask = np.zeros(self.sensor_w * self.sensor_h, np.uint8)
+        self._check(self._L.emba_seq_hot_pixels(self._ctx, _p(mask, _u8p)))
+        return mask
+
     def free_sequence(self):
         self._check(self._L.emba_seq_free(self._ctx))
 

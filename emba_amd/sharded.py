@@ -150,6 +150,13 @@ class ShardedLEGM:
         """(beg, end) of EMBA::getEventSubset — a deterministic search on equal copies: the same on every rank, no collective."""
         return self.engine.sequence_window(t_beg_ns, t_end_ns)
 
+    def filter_sequence(self, hot_sigma=0.0, refractory_ns=0, support_ns=0, sampling_rate=1):
+        """emba_seq_filter on this rank's copy — a deterministic rule on equal copies: the same survivors and statistics on every rank, no collective."""
+        return self.engine.filter_sequence(hot_sigma, refractory_ns, support_ns, sampling_rate)
+
+    def sequence_hot_pixels(self):
+        return self.engine.sequence_hot_pixels()
+
     def median_blur_map(self):
         self.engine.median_blur_map()
 
@@ -395,6 +402,12 @@ class ShardedModel:
     def sequence_window(self, t_beg_ns, t_end_ns):
         return self.sh.sequence_window(t_beg_ns, t_end_ns)
 
+    def filter_sequence(self, hot_sigma=0.0, refractory_ns=0, support_ns=0, sampling_rate=1):
+        return self.sh.filter_sequence(hot_sigma, refractory_ns, support_ns, sampling_rate)
+
+    def sequence_hot_pixels(self):
+        return self.sh.sequence_hot_pixels()
+
     def median_blur_map(self):
         self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
 
@@ -515,6 +528,12 @@ class HipEngine:
 
     def sequence_window(self, t_beg_ns, t_end_ns):
         return self.m.sequence_window(t_beg_ns, t_end_ns)
+
+    def filter_sequence(self, hot_sigma=0.0, refractory_ns=0, support_ns=0, sampling_rate=1):
+        return self.m.filter_sequence(hot_sigma, refractory_ns, support_ns, sampling_rate)
+
+    def sequence_hot_pixels(self):
+        return self.m.sequence_hot_pixels()
 
     def median_blur_map(self):
         self.m.median_blur_map()

@@ -201,3 +201,29 @@ def make_scene_stream(n_target, pano_h=1024, K=21, sensor=(240, 180), focal=200.
     w = make_scene_workload(pano_h=pano_h, K=K, sensor=sensor, focal=focal, C_th=C_th, amp=amp, n_steps=n_steps, seed=seed,
                             n_terms=8, max_freq=(40, 20), **kw)
     return w
+
+
+# ---- the three kinds of noise a DVS / DAVIS recording carries, to test the filters of emba_seq_filter / io.filter_events with ----------------------
+def add_sensor_noise(events, sensor, n_hot=0, hot_events_each=0, n_background=0, seed=SEED):
+    """events (sorted) + n_hot hot pixels (distinct, drawn uniformly) that fire hot_events_each times each at uniformly spaced times over the recording
+    + n_background events uniform in pixel and time, merged STABLY into the time order (at equal timestamps: the recording's events first, then the hot
+    pixels', then the background).  Polarities are drawn uniformly.  A pure function of its arguments.  Returns (EventPacket, hot pixel indices
+    y * sensor_w + x, ascending)."""
+    sw, sh = sensor
+    rng = np.random.default_rng(seed)
+    t = np.asarray(events.t_ns, dtype=np.int64)
+    t0, t1 = (int(t[0]), int(t[-1])) if t.size else (0, 0)
+    hot = np.sort(rng.choice(sw * sh, size=int(n_hot), replace=False)).astype(np.int64)
+    E = int(hot_events_each)
+    hot_t = t0 + (np.arange(E, dtype=np.int64) * (t1 - t0)) // max(E, 1)
+    hp = np.repeat(hot, E)
+    ht = np.tile(hot_t, hot.size)
+    nb = int(n_background)
+    bp = rng.integers(0, sw * sh, size=nb)
+    bt = rng.integers(t0, t1 + 1, size=nb) if nb else np.zeros(0, np.int64)
+    pix = np.concatenate([np.asarray(events.y, np.int64) * sw + np.asarray(events.x, np.int64), hp, bp])
+    pol = np.concatenate([np.asarray(events.polarity, np.uint8), rng.integers(0, 2, size=hp.size + nb).astype(np.uint8)])
+    tt = np.concatenate([t, ht, bt.astype(np.int64)])
+    order = np.argsort(tt, kind="stable")
+    pix = pix[order]
+    return EventPacket((pix % sw).astype(np.uint16), (pix // sw).astype(np.uint16), pol[order], tt[order]), hot

@@ -53,6 +53,11 @@ def main():
                     "the event sequence then stays on the device and the map is carried from window to window")
     ap.add_argument("--window-stride", type=float, help="sliding_window_stride in seconds (default: the window size)")
     ap.add_argument("--sampling-rate", type=int, default=1, help="event_sampling_rate: keep every n-th event (emba.cpp:281-304; with --window-size)")
+    ap.add_argument("--hot-pixel-sigma", type=float, default=0.0, help="drop every event of a pixel whose event count exceeds mean + SIGMA * std over the pixels "
+                    "that fired (0: off; with --window-size; the filters run on the device before the down-sampling)")
+    ap.add_argument("--refractory", type=float, default=0.0, help="seconds: drop an event closer than this behind the previous event of its pixel (0: off)")
+    ap.add_argument("--support-time", type=float, default=0.0, help="seconds: keep an event only if one of its eight neighbouring pixels fired at most this long "
+                    "before it (0: off)")
     ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
     ap.add_argument("--init-map", default="given", choices=["given", "events"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
                     "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size")
@@ -128,9 +133,13 @@ def main():
     if a.window_size:
         from emba_amd.driver import SequenceSettings, run_sequence
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
-                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map)
+                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
+                               hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time)
         sres = run_sequence(model, events, t, qs, *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
+        if rank == 0 and sres.filter_stats is not None:
+            fs = [int(v) for v in sres.filter_stats]
+            print(f"noise filters: {fs[0]} events in, {fs[1]} hot pixels ({fs[2]} events), {fs[3]} inside the refractory period, {fs[4]} without support, {fs[5]} kept")
         if rank == 0:
             for wr in sres.windows:
                 if wr.map_init is not None:

@@ -296,6 +296,33 @@ emba_status emba_seq_halo(emba_ctx* ctx, size_t win_beg, size_t lo, uint16_t* hx
 /* [beg, end) of the resident sequence back to the host (tests, diagnostics): capacity end - beg each; any pointer may be NULL. */
 emba_status emba_seq_get(emba_ctx* ctx, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns);
 
+/* ---- Sensor noise (no counterpart in the reference, whose only defence is outlier_px): hot pixels, bursts at one pixel and isolated background-activity
+ * events of a DVS / DAVIS recording are removed from the resident sequence on the device, once per recording, before any window is cut from it.
+ * Every event is judged from the RAW resident sequence (sorted by time; "earlier" = smaller index, which also orders equal timestamps), with
+ * p(k) = y[k] * sensor_w + x[k], so the three tests are independent:
+ *   hot pixels   (hot_sigma > 0)       c[p] = events of pixel p, m = pixels with c > 0, s1 = sum c = n, s2 = sum c^2 (exact, uint64); in double, one rounding per
+ *                                      operation (no fused multiply-add): mean = s1 / m, var = s2 / m - mean * mean (0 if negative), thr = mean + hot_sigma * sqrt(var).
+ *                                      Pixel p is hot iff double(c[p]) > thr; every event of a hot pixel fails.
+ *   refractory   (refractory_ns > 0)   prev(k) = the latest earlier event of the same pixel, surviving or not; k fails iff it exists and t[k] - t[prev(k)] < refractory_ns.
+ *   support      (support_ns > 0)      k passes iff an earlier event j at one of the up to eight neighbouring pixels inside the sensor (not the pixel itself),
+ *                                      that pixel not hot, has t[k] - t[j] <= support_ns (only the latest earlier event of each neighbour matters).
+ * The survivors — the events that fail no enabled test — keep their order; the down-sampling of emba.cpp:281-304 then runs over the SURVIVORS: with
+ * sampling_rate >= 2 the survivor of rank r (from 0) is kept iff (r + 1) % sampling_rate == 0.  stats (6 values, may be NULL): events in, hot pixels, events
+ * failing hot, failing refractory, failing support (each counted over all events on its own: overlaps count in each), events kept.
+ * With every test off and sampling_rate <= 1 the sequence is left exactly as it is.  The survivors are gathered into fresh arrays that replace the resident
+ * ones; a registered window is not disturbed (emba_set_events_seq keeps no pointer into the sequence), ranges taken from emba_seq_window before the call no
+ * longer apply.  EMBA_ERR_STATE: no sequence resident.  EMBA_ERR_INVALID_ARG: hot_sigma is NaN, or 2^32 events or more (the sort carries 32-bit event
+ * indices) — the sequence is then left as it was.  Every event removed: EMBA_OK with stats[5] = 0, and no sequence is resident afterwards (emba_seq_size: 0).
+ * "Resident" is asked by emba_seq_filter and emba_group_seq_filter alone: a successful emba_seq_upload makes a sequence resident, also one of no events (the
+ * filter of it is EMBA_OK with all-zero statistics); emba_seq_free, a failed upload and a filter that removes every event end that, and a further filter
+ * is then EMBA_ERR_STATE until the next upload.  Every other emba_seq_* call and emba_set_events_seq* go by the event count, as before: they see a
+ * sequence of 0 events (emba_seq_window: the empty range; emba_seq_get and emba_set_events_seq: the range [0, 0) only).  Lack of memory: EMBA_ERR_HIP, with
+ * the sequence and the previous filter's hot mask left as they were (every allocation precedes the first write).
+ * emba_amd.io.filter_events is the same rule in numpy.  Launches and timings: DESIGN.md §10. */
+emba_status emba_seq_filter(emba_ctx* ctx, double hot_sigma, int64_t refractory_ns, int64_t support_ns, int32_t sampling_rate, uint64_t* stats);
+/* The hot pixels of the last emba_seq_filter on this context: sensor_w * sensor_h bytes, 1 = hot (all 0 where hot_sigma was off).  EMBA_ERR_STATE before any. */
+emba_status emba_seq_hot_pixels(emba_ctx* ctx, uint8_t* mask_host);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
@@ -556,6 +583,9 @@ emba_status emba_group_seq_size(const emba_group* g, size_t* n);
 emba_status emba_group_seq_free(emba_group* g);
 /* EMBA::getEventSubset (emba.cpp:473-510): emba_seq_window on rank 0 (the search is deterministic and the copies are equal: every rank's answer). */
 emba_status emba_group_seq_window(emba_group* g, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg, size_t* end);
+/* emba_seq_filter on EVERY rank's copy of the sequence (equal copies, a deterministic rule: equal results); stats are rank 0's.  Rank r's hot pixels:
+ * emba_seq_hot_pixels(emba_group_ctx(g, r), .). */
+emba_status emba_group_seq_filter(emba_group* g, double hot_sigma, int64_t refractory_ns, int64_t support_ns, int32_t sampling_rate, uint64_t* stats);
 /* emba_group_set_events for the window [beg, end) of the resident sequence (emba.cpp:508-509 -> solveTimeWindow): with nb = (end - beg) / 100, rank r
  * registers the window's batches [nb r / N, nb (r + 1) / N) (the remainder on the first ranks; the last rank's range runs to `end` and so carries the
  * (end - beg) % 100 tail the library ignores) through emba_set_events_seq_shard — its halo is built on its own device, no event crosses the host. */
