@@ -1,6 +1,6 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
-// Included by emba_hip.hip, step_host.h, solve_host.h and group.h; host code only.
+// Included by emba_hip.hip, step_host.h, solve_host.h, sequence_host.h and group.h; host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -319,10 +319,15 @@ struct emba_ctx {
     // halo_*: emba_set_events_seq_shard's passes — last event per sensor pixel, halo flags and positions per event in front of the shard.
     // emba_seq_filter: x2 ... t2 take the survivors and are swapped with x ... t (never compacted in place); f_start: per-pixel starts of the pixel-sorted
     // sequence (S + 1), f_hot: the last filter's hot-pixel mask (S bytes, have_hot), f_sums: its eight 64-bit counters.  have: a sequence is resident (an
-    // upload succeeded, also one of no events, and no filter has removed every event since)
+    // upload succeeded, also one of no events, and no filter has removed every event since).  The host code: sequence_host.h.
     struct {
         DevBuf x, y, pol, t, raw, status, halo_last, halo_flag, halo_pos; size_t n = 0;
         DevBuf x2, y2, pol2, t2, f_start, f_hot, f_sums; bool have = false, have_hot = false;
+        void reset()      // emba_seq_free: every buffer above, and what the host knows about them
+        {
+            for (DevBuf* b : {&x, &y, &pol, &t, &raw, &status, &halo_last, &halo_flag, &halo_pos, &x2, &y2, &pol2, &t2, &f_start, &f_hot, &f_sums}) b->reset();
+            n = 0; have = have_hot = false;
+        }
     } evseq;
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };

@@ -33,6 +33,7 @@
 #include "render_kernels.h"
 #include "sequence_kernels.h"
 #include "context.h"
+#include "sequence_rule.h"
 
 using namespace emba;
 
@@ -87,13 +88,30 @@ int64_t batch_mid_ns(int64_t t_first, int64_t t_last)
 
 // ---- device-side helpers of the once-per-window structure (order_kernels.h) ----------------------------------------------------
 
+// The scratch of a dev_scan over n elements / of a dev_sort of n entries (its histogram, and the scan over it).  dev_scan and dev_sort reserve it themselves;
+// a caller that must not fail for want of memory later on (emba_seq_filter) reserves it up front through the same two functions.
+size_t scan_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
+size_t sort_tiles(size_t n) { return (n + kSortTile - 1) / kSortTile; }
+emba_status ensure_scan_scratch(emba_ctx* c, size_t n)
+{
+    emba_status st;
+    if ((st = ensure<uint32_t>(c, c->ord.scan_sums, scan_tiles(n) + 1)) || (st = ensure<uint32_t>(c, c->ord.scan_offs, scan_tiles(n) + 2))) return st;
+    return EMBA_OK;
+}
+emba_status ensure_sort_scratch(emba_ctx* c, size_t n)
+{
+    emba_status st;
+    if ((st = ensure<uint32_t>(c, c->ord.sort_hist, 256 * sort_tiles(n))) || (st = ensure_scan_scratch(c, 256 * sort_tiles(n)))) return st;
+    return EMBA_OK;
+}
+
 // out[i] = sum_{j<i} in[j]; total_dev[0] = sum of all (may be nullptr).  Scratch: ord.scan_sums, ord.scan_offs.
 emba_status dev_scan(emba_ctx* c, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total_dev, int* total_host = nullptr, const int* err_dev = nullptr, int* err_host = nullptr)
 {   // (total_host / err_host: pinned, device-visible words the middle launch writes the total and the evaluation's status word to — no copy node)
     hipStream_t s = c->stream;
-    const size_t ntiles = (n + kScanTile - 1) / kScanTile;
+    const size_t ntiles = scan_tiles(n);
     emba_status st;
-    if ((st = ensure<uint32_t>(c, c->ord.scan_sums, ntiles + 1)) || (st = ensure<uint32_t>(c, c->ord.scan_offs, ntiles + 2))) return st;
+    if ((st = ensure_scan_scratch(c, n))) return st;
     uint32_t *sums = c->ord.scan_sums.as<uint32_t>(), *offs = c->ord.scan_offs.as<uint32_t>();
     uint32_t* tot = total_dev ? total_dev : offs + ntiles + 1;
     if (!n) { HIP_TRY(c, hipMemsetAsync(tot, 0, 4, s)); return EMBA_OK; }
@@ -110,9 +128,9 @@ emba_status dev_sort(emba_ctx* c, uint32_t** keys, uint32_t** vals, uint32_t** k
 {
     if (n < 2 || bits <= 0) return EMBA_OK;
     hipStream_t s = c->stream;
-    const size_t ntiles = (n + kSortTile - 1) / kSortTile;
+    const size_t ntiles = sort_tiles(n);
     emba_status st;
-    if ((st = ensure<uint32_t>(c, c->ord.sort_hist, 256 * ntiles))) return st;
+    if ((st = ensure_sort_scratch(c, n))) return st;
     uint32_t* hist = c->ord.sort_hist.as<uint32_t>();
     for (int shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(emba_sort_hist_kernel, dim3(nblocks(ntiles, 4)), dim3(256), 0, s, *keys, (long)n, shift, (long)ntiles, hist);
@@ -740,14 +758,15 @@ emba_status emba_set_events(emba_ctx* c, const uint16_t* x, const uint16_t* y, c
     for (size_t b = 0; b < nb; ++b) bt[b] = batch_mid_ns(t_ns[100 * b], t_ns[100 * b + 99]);
     // x, y, polarity (5 B per event) and the halo go to the device as they are
     hipStream_t s = c->stream;
+    const HaloLayout halo(n_halo);
     emba_status st;
     if ((st = ensure<uint16_t>(c, c->ord.bin_start_or_x, std::max<size_t>(n_used, 1))) || (st = ensure<uint16_t>(c, c->ord.pred_or_y, std::max<size_t>(n_used, 1))) ||
-        (st = ensure<uint8_t>(c, c->ord.heads_or_pol, std::max<size_t>(n_used, 1))) || (st = ensure<uint8_t>(c, c->ord.halo, std::max<size_t>(n_halo, 1) * 12)))
+        (st = ensure<uint8_t>(c, c->ord.heads_or_pol, std::max<size_t>(n_used, 1))) || (st = ensure<uint8_t>(c, c->ord.halo, halo.bytes)))
         return st;
     uint16_t *dx = c->ord.bin_start_or_x.as<uint16_t>(), *dy = c->ord.pred_or_y.as<uint16_t>();
     uint8_t* dp = c->ord.heads_or_pol.as<uint8_t>();
-    int64_t* dhb = c->ord.halo.as<int64_t>();
-    uint16_t *dhx = reinterpret_cast<uint16_t*>(dhb + n_halo), *dhy = dhx + n_halo;
+    int64_t* dhb = halo.hbt_in(c->ord.halo.p);
+    uint16_t *dhx = halo.hx_in(c->ord.halo.p), *dhy = halo.hy_in(c->ord.halo.p);
     if (n_used) {
         HIP_TRY(c, hipMemcpyAsync(dx, x, n_used * 2, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(dy, y, n_used * 2, hipMemcpyHostToDevice, s));
@@ -1740,336 +1759,7 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
     return EMBA_OK;
 }
 
-// ---- the resident event sequence of a sliding-window run (sequence_kernels.h) ---------------------------------------------------
-// Raw events per upload chunk: 8 B + 2 B + 2 B + 1 B each, laid out [t | x | y | pol] in a pinned staging buffer (6.5 of its 8 MB).
-namespace {
-constexpr size_t kSeqChunk = (size_t)1 << 19;
-constexpr size_t kSeqOffX = kSeqChunk * 8, kSeqOffY = kSeqOffX + kSeqChunk * 2, kSeqOffPol = kSeqOffY + kSeqChunk * 2, kSeqRawBytes = kSeqOffPol + kSeqChunk;
-static_assert(kSeqRawBytes <= kStageBytes, "an upload chunk must fit a staging buffer");
-}  // namespace
-
-extern "C" emba_status emba_seq_free(emba_ctx* c)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->evseq.x.reset(); c->evseq.y.reset(); c->evseq.pol.reset(); c->evseq.t.reset(); c->evseq.raw.reset();
-    c->evseq.halo_last.reset(); c->evseq.halo_flag.reset(); c->evseq.halo_pos.reset();
-    c->evseq.x2.reset(); c->evseq.y2.reset(); c->evseq.pol2.reset(); c->evseq.t2.reset();
-    c->evseq.f_start.reset(); c->evseq.f_hot.reset(); c->evseq.f_sums.reset();
-    c->evseq.n = 0; c->evseq.have = false; c->evseq.have_hot = false;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_seq_size(const emba_ctx* c, size_t* n)
-{
-    if (!c || !n) return EMBA_ERR_INVALID_ARG;
-    *n = c->evseq.n;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n, int32_t sampling_rate,
-                                       size_t* n_kept_out)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (n && (!x || !y || !pol || !t_ns)) return fail(c, EMBA_ERR_INVALID_ARG, "event arrays are NULL");
-    if (n >= 0xFFFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events for 32-bit indices");
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const size_t rate = sampling_rate >= 2 ? (size_t)sampling_rate : 1;      // emba.cpp:282
-    const size_t n_kept = n / rate;
-    c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
-    emba_status st;
-    if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRawBytes)) || (st = ensure<uint32_t>(c, c->evseq.status, 16)) ||
-        (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
-        (st = ensure<uint8_t>(c, c->evseq.pol, std::max<size_t>(n_kept, 1))) || (st = ensure<int64_t>(c, c->evseq.t, std::max<size_t>(n_kept, 1))))
-        return st;
-    uint32_t* d_err = c->evseq.status.as<uint32_t>();
-    HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
-    uint8_t* raw = c->evseq.raw.as<uint8_t>();
-    for (size_t k0 = 0, i = 0; k0 < n; k0 += kSeqChunk, ++i) {
-        const size_t m = std::min(kSeqChunk, n - k0);
-        uint8_t* h = static_cast<uint8_t*>(c->h_stage[i & 1]);
-        HIP_TRY(c, hipEventSynchronize(c->stage_ev[i & 1]));      // the transfer that last used this staging buffer has completed
-        std::memcpy(h, t_ns + k0, m * 8); std::memcpy(h + kSeqOffX, x + k0, m * 2); std::memcpy(h + kSeqOffY, y + k0, m * 2); std::memcpy(h + kSeqOffPol, pol + k0, m);
-        // (one stream: the copy of chunk i + 1 into `raw` is ordered behind the kernel that reads chunk i)
-        HIP_TRY(c, hipMemcpyAsync(raw, h, m * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffX, h + kSeqOffX, m * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffY, h + kSeqOffY, m * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(raw + kSeqOffPol, h + kSeqOffPol, m, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipEventRecord(c->stage_ev[i & 1], s));
-        hipLaunchKernelGGL(emba_seq_ingest_kernel, dim3(nblocks(m)), dim3(256), 0, s, reinterpret_cast<const int64_t*>(raw), reinterpret_cast<const uint16_t*>(raw + kSeqOffX),
-                           reinterpret_cast<const uint16_t*>(raw + kSeqOffY), (const uint8_t*)(raw + kSeqOffPol), (long)m, (long)k0, k0 ? t_ns[k0 - 1] : (int64_t)0, c->sw, c->sh,
-                           (long)rate, (long)n_kept, c->evseq.x.as<uint16_t>(), c->evseq.y.as<uint16_t>(), c->evseq.pol.as<uint8_t>(), c->evseq.t.as<int64_t>(), d_err);
-        HIP_TRY(c, hipGetLastError());
-    }
-    uint32_t h_err[2];
-    HIP_TRY(c, hipMemcpyAsync(h_err, d_err, sizeof h_err, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (h_err[0] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[0], c->sw, c->sh);
-    if (h_err[1] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[1]);
-    c->evseq.n = n_kept; c->evseq.have = true;
-    if (n_kept_out) *n_kept_out = n_kept;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_seq_window(emba_ctx* c, int64_t t_beg_ns, int64_t t_end_ns, size_t* beg_out, size_t* end_out)
-{
-    if (!c || !beg_out || !end_out) return c ? fail(c, EMBA_ERR_INVALID_ARG, "beg/end NULL") : EMBA_ERR_INVALID_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t n = c->evseq.n, m = (n + kSeqProbe - 1) / kSeqProbe;
-    const int64_t a = t_beg_ns + 1000000, b = t_end_ns - 1000000;      // t_epsilon = ros::Duration(1e-3), emba.cpp:476-478
-    uint32_t h_res[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-    if (m) {
-        emba_status st;
-        if ((st = ensure<uint32_t>(c, c->evseq.status, 16))) return st;
-        uint32_t* d_res = c->evseq.status.as<uint32_t>();
-        HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, 8, s));
-        hipLaunchKernelGGL(emba_seq_window_kernel, dim3((unsigned)std::min<size_t>(nblocks(m), 1024)), dim3(256), 0, s, (const int64_t*)c->evseq.t.as<int64_t>(), (long)n, a, b, d_res);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(h_res, d_res, sizeof h_res, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    // head: the first probe past a, or the first multiple of 100 >= n (emba.cpp:483-491)
-    const size_t jb = h_res[0] != 0xFFFFFFFFu ? h_res[0] : m, beg = kSeqProbe * jb;
-    size_t end = n;                                                      // no probe past b: the loop runs off the sequence, :504-505
-    if (jb < m && h_res[1] != 0xFFFFFFFFu) {
-        // tail: the first probe >= beg past b (every probe from beg on is past a; where b < a the search stops at beg itself)
-        const size_t je = std::max<size_t>(h_res[1], jb);
-        if (je == jb) return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (the tail search stops at its first probe, event %zu)", beg);
-        end = kSeqProbe * je - kSeqProbe;                                  // :500
-    }
-    if (beg > end) return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (it begins behind the last event)");
-    *beg_out = beg; *end_out = end;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_set_events_seq(emba_ctx* c, size_t beg, size_t end)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (beg > end || end > c->evseq.n) return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
-    return emba_set_events_dev(c, c->evseq.x.as<uint16_t>() + beg, c->evseq.y.as<uint16_t>() + beg, c->evseq.pol.as<uint8_t>() + beg, c->evseq.t.as<int64_t>() + beg, end - beg,
-                               nullptr, nullptr, nullptr, 0);
-}
-
-namespace {
-// The halo of the time shard that begins at `lo` of the window that begins at win_beg (sequence_kernels.h: emba_halo_*), into ord.halo in the layout
-// emba_set_events stages — [hbt (8 B) | hx (2 B) | hy (2 B)] x *n_halo.  The sequence was checked at its upload: every pixel lies inside the sensor, so
-// inside the table.  One small read: the count, which places hx / hy behind the times.  Scratch of its own (evseq) + dev_scan's.
-emba_status build_seq_halo(emba_ctx* c, size_t win_beg, size_t lo, size_t* n_halo)
-{
-    hipStream_t s = c->stream;
-    const size_t m = lo - win_beg;
-    *n_halo = 0;
-    if (!m) return EMBA_OK;
-    if (m > 0x7FFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events in front of the shard for 32-bit indices");
-    emba_status st;
-    if ((st = ensure<int32_t>(c, c->evseq.halo_last, c->S)) || (st = ensure<uint32_t>(c, c->evseq.halo_flag, m)) || (st = ensure<uint32_t>(c, c->evseq.halo_pos, m)) ||
-        (st = ensure<uint32_t>(c, c->evseq.status, 16)))
-        return st;
-    const uint16_t *x = c->evseq.x.as<uint16_t>() + win_beg, *y = c->evseq.y.as<uint16_t>() + win_beg;
-    const int64_t* t = c->evseq.t.as<int64_t>() + win_beg;
-    int32_t* last = c->evseq.halo_last.as<int32_t>();
-    uint32_t *flag = c->evseq.halo_flag.as<uint32_t>(), *pos = c->evseq.halo_pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + 4;
-    HIP_TRY(c, hipMemsetAsync(last, 0xFF, c->S * sizeof(int32_t), s));      // -1: no event of this pixel
-    hipLaunchKernelGGL(emba_halo_last_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, last);
-    hipLaunchKernelGGL(emba_halo_flag_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, (const int32_t*)last, flag);
-    if ((st = dev_scan(c, flag, pos, m, d_tot))) return st;
-    uint32_t h_tot = 0;
-    HIP_TRY(c, hipMemcpyAsync(&h_tot, d_tot, sizeof h_tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (h_tot > c->S) return fail(c, EMBA_ERR_STATE, "halo of %u entries on a sensor of %zu pixels", h_tot, c->S);
-    const size_t n = h_tot;
-    if ((st = ensure<uint8_t>(c, c->ord.halo, std::max<size_t>(n, 1) * 12))) return st;
-    int64_t* hbt = c->ord.halo.as<int64_t>();
-    uint16_t *hx = reinterpret_cast<uint16_t*>(hbt + n), *hy = hx + n;
-    hipLaunchKernelGGL(emba_halo_gather_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, t, (long)m, (const uint32_t*)flag, (const uint32_t*)pos, hx, hy, hbt);
-    HIP_TRY(c, hipGetLastError());
-    *n_halo = n;
-    return EMBA_OK;
-}
-
-emba_status check_seq_shard(emba_ctx* c, size_t win_beg, size_t lo, size_t hi)
-{
-    if (win_beg > lo || lo > hi || hi > c->evseq.n)
-        return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) of the window at %zu is not a range of the resident sequence of %zu events", lo, hi, win_beg, c->evseq.n);
-    if ((lo - win_beg) % 100) return fail(c, EMBA_ERR_INVALID_ARG, "the shard begins %zu events behind its window: not on the window's batch grid", lo - win_beg);
-    return EMBA_OK;
-}
-}  // namespace
-
-extern "C" emba_status emba_set_events_seq_shard(emba_ctx* c, size_t win_beg, size_t lo, size_t hi)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    emba_status st;
-    if ((st = check_seq_shard(c, win_beg, lo, hi))) return st;      // (before anything of the registered window is touched)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const auto t_begin = std::chrono::steady_clock::now();
-    size_t n_halo = 0;
-    if ((st = build_seq_halo(c, win_beg, lo, &n_halo))) return st;
-    int64_t* hbt = c->ord.halo.as<int64_t>();
-    uint16_t *hx = reinterpret_cast<uint16_t*>(hbt + n_halo), *hy = hx + n_halo;
-    st = emba_set_events_dev(c, c->evseq.x.as<uint16_t>() + lo, c->evseq.y.as<uint16_t>() + lo, c->evseq.pol.as<uint8_t>() + lo, c->evseq.t.as<int64_t>() + lo, hi - lo,
-                             n_halo ? hx : nullptr, n_halo ? hy : nullptr, n_halo ? hbt : nullptr, n_halo);
-    c->set_events_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();      // the halo passes included
-    return st;
-}
-
-extern "C" emba_status emba_seq_halo(emba_ctx* c, size_t win_beg, size_t lo, uint16_t* hx, uint16_t* hy, int64_t* hbt, size_t cap, size_t* n_halo)
-{
-    if (!c || !n_halo) return c ? fail(c, EMBA_ERR_INVALID_ARG, "n_halo NULL") : EMBA_ERR_INVALID_ARG;
-    emba_status st;
-    if ((st = check_seq_shard(c, win_beg, lo, lo))) return st;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    size_t n = 0;
-    if ((st = build_seq_halo(c, win_beg, lo, &n))) return st;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *n_halo = n;
-    if (!hx && !hy && !hbt) return EMBA_OK;
-    if (cap < n) return fail(c, EMBA_ERR_CAPACITY, "the halo has %zu entries, the arrays hold %zu", n, cap);
-    const int64_t* dhb = c->ord.halo.as<int64_t>();
-    const uint16_t *dhx = reinterpret_cast<const uint16_t*>(dhb + n), *dhy = dhx + n;
-    if (n && hbt && (st = d2h_pageable(c, hbt, dhb, n * 8))) return st;
-    if (n && hx && (st = d2h_pageable(c, hx, dhx, n * 2))) return st;
-    if (n && hy && (st = d2h_pageable(c, hy, dhy, n * 2))) return st;
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_seq_get(emba_ctx* c, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (beg > end || end > c->evseq.n) return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t m = end - beg;
-    emba_status st;
-    if (x && (st = d2h_pageable(c, x, c->evseq.x.as<uint16_t>() + beg, m * 2))) return st;
-    if (y && (st = d2h_pageable(c, y, c->evseq.y.as<uint16_t>() + beg, m * 2))) return st;
-    if (pol && (st = d2h_pageable(c, pol, c->evseq.pol.as<uint8_t>() + beg, m))) return st;
-    if (t_ns && (st = d2h_pageable(c, t_ns, c->evseq.t.as<int64_t>() + beg, m * 8))) return st;
-    return EMBA_OK;
-}
-
-// ---- sensor-noise filters on the resident sequence (sequence_kernels.h: emba_filter_*; the rule: include/emba_hip.h) ------------------------------
-namespace {
-// thr = mean + sigma sqrt(var) over the pixels with events, from the exact integer sums: every operation rounded on its own (no contraction), so that
-// the host form (emba_amd.io.filter_events) and the loop reference of the tests get the same bits.
-double hot_threshold(uint64_t s1, uint64_t m, uint64_t s2, double sigma)
-{
-#pragma clang fp contract(off)
-    const double mean = (double)s1 / (double)m;
-    const double msq = (double)s2 / (double)m;
-    const double mean2 = mean * mean;
-    double var = msq - mean2;
-    if (var < 0.0) var = 0.0;
-    const double sd = std::sqrt(var);
-    const double spread = sigma * sd;
-    return mean + spread;
-}
-}  // namespace
-
-// Scratch: the sort pairs, flags and positions of the order preparation (ord.keys / vals / flags / pos, + dev_scan's and dev_sort's) — a registered window
-// keeps nothing in them: set_events_core copies what it sorted into the pm-order arrays, prepare_order into the device order and the record slots, and a
-// re-binning rebuilds all of it from the pm-order.  What has to outlive the call (starts, hot mask, counters, the fresh arrays) is evseq's own.
-extern "C" emba_status emba_seq_filter(emba_ctx* c, double hot_sigma, int64_t refractory_ns, int64_t support_ns, int32_t sampling_rate, uint64_t* stats)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!c->evseq.have) return fail(c, EMBA_ERR_STATE, "no resident sequence (emba_seq_upload first)");
-    if (std::isnan(hot_sigma)) return fail(c, EMBA_ERR_INVALID_ARG, "hot_sigma is NaN");
-    const size_t n = c->evseq.n, S = c->S;
-    if (n >= 0x100000000ull) return fail(c, EMBA_ERR_INVALID_ARG, "emba_seq_filter: %zu events are too many for the 32-bit event indices of its sort (limit 2^32 - 1)", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const bool hot_on = hot_sigma > 0.0, filters_on = hot_on || refractory_ns > 0 || support_ns > 0;
-    const size_t rate = sampling_rate >= 2 ? (size_t)sampling_rate : 1;
-    const bool sorts = filters_on && n, rewrites = filters_on || rate > 1;      // (neither: the sequence stays exactly as it is)
-    // Everything that can fail for want of memory comes first — the scratch of the sort and of the scans included, and the fresh arrays at their upper bound
-    // n / rate — so that a failure leaves the sequence AND the previous filter's hot mask as they were.
-    emba_status st;
-    if ((st = ensure<uint8_t>(c, c->evseq.f_hot, S)) || (st = ensure<uint64_t>(c, c->evseq.f_sums, 8)) || (st = ensure<uint32_t>(c, c->evseq.status, 16))) return st;
-    if (sorts) {
-        const size_t ntiles = (n + kSortTile - 1) / kSortTile, n_scan = std::max(n, 256 * ntiles);
-        if ((st = ensure_sort_pairs(c, n)) || (st = ensure<uint32_t>(c, c->ord.flags, n)) || (st = ensure<uint32_t>(c, c->ord.pos, n)) ||
-            (st = ensure<uint32_t>(c, c->evseq.f_start, S + 1)) || (st = ensure<uint32_t>(c, c->ord.sort_hist, 256 * ntiles)) ||
-            (st = ensure<uint32_t>(c, c->ord.scan_sums, (n_scan + kScanTile - 1) / kScanTile + 1)) ||
-            (st = ensure<uint32_t>(c, c->ord.scan_offs, (n_scan + kScanTile - 1) / kScanTile + 2)))
-            return st;
-    }
-    const size_t n_fresh = std::max<size_t>(n / rate, 1);
-    if (rewrites && ((st = ensure<uint16_t>(c, c->evseq.x2, n_fresh)) || (st = ensure<uint16_t>(c, c->evseq.y2, n_fresh)) ||
-                     (st = ensure<uint8_t>(c, c->evseq.pol2, n_fresh)) || (st = ensure<int64_t>(c, c->evseq.t2, n_fresh))))
-        return st;
-    uint8_t* d_hot = c->evseq.f_hot.as<uint8_t>();
-    unsigned long long* d_sums = c->evseq.f_sums.as<unsigned long long>();   // [0] pixels with events [1] sum c^2 [2] hot pixels [3] their events [4] refractory [5] support
-    uint32_t* d_tot = c->evseq.status.as<uint32_t>() + 8;
-    c->evseq.have_hot = false;     // (from here on the mask is this filter's: all zero unless the hot test below runs)
-    HIP_TRY(c, hipMemsetAsync(d_hot, 0, S, s));
-    HIP_TRY(c, hipMemsetAsync(d_sums, 0, 64, s));
-    unsigned long long h_sums[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t n_surv = n;
-    const uint16_t *x = c->evseq.x.as<uint16_t>(), *y = c->evseq.y.as<uint16_t>();
-    const uint8_t* pol = c->evseq.pol.as<uint8_t>();
-    const int64_t* t = c->evseq.t.as<int64_t>();
-    const uint32_t *d_keep = nullptr, *d_pos = nullptr;
-    if (sorts) {
-        uint32_t *k0 = c->ord.keys[0].as<uint32_t>(), *v0 = c->ord.vals[0].as<uint32_t>(), *k1 = c->ord.keys[1].as<uint32_t>(), *v1 = c->ord.vals[1].as<uint32_t>();
-        uint32_t *keep = c->ord.flags.as<uint32_t>(), *pos = c->ord.pos.as<uint32_t>(), *start = c->evseq.f_start.as<uint32_t>();
-        hipLaunchKernelGGL(emba_pixel_keys_kernel, dim3(nblocks(n)), dim3(256), 0, s, x, y, (long)n, c->sw, (const uint16_t*)nullptr, (const uint16_t*)nullptr, 0L, k0, v0);
-        if ((st = dev_sort(c, &k0, &v0, &k1, &v1, n, bits_for(S)))) return st;
-        hipLaunchKernelGGL(emba_filter_starts_kernel, dim3(nblocks(n)), dim3(256), 0, s, (const uint32_t*)k0, (long)n, (long)S, start);
-        if (hot_on) {
-            const unsigned grid = (unsigned)std::min<size_t>(nblocks(S), 1024);
-            hipLaunchKernelGGL(emba_filter_pixel_sums_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)start, (long)S, d_sums);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(h_sums, d_sums, 16, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            if (!h_sums[0]) return fail(c, EMBA_ERR_STATE, "emba_seq_filter: %zu events on no pixel", n);
-            const double thr = hot_threshold(n, h_sums[0], h_sums[1], hot_sigma);
-            hipLaunchKernelGGL(emba_filter_hot_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)start, (long)S, thr, d_hot, d_sums);
-        }
-        hipLaunchKernelGGL(emba_filter_flags_kernel, dim3(nblocks(n)), dim3(256), 0, s, (const uint32_t*)k0, (const uint32_t*)v0, t, (long)n, c->sw, c->sh,
-                           (const uint32_t*)start, (const uint8_t*)d_hot, refractory_ns, support_ns, keep, d_sums);
-        HIP_TRY(c, hipGetLastError());
-        if ((st = dev_scan(c, keep, pos, n, d_tot))) return st;
-        uint32_t h_tot = 0;
-        HIP_TRY(c, hipMemcpyAsync(&h_tot, d_tot, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(h_sums, d_sums, 64, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (h_tot > n) return fail(c, EMBA_ERR_STATE, "emba_seq_filter: %u survivors of %zu events", h_tot, n);
-        n_surv = h_tot; d_keep = keep; d_pos = pos;
-    }
-    const size_t n_kept = n_surv / rate;
-    if (rewrites) {
-        if (n_kept) {
-            hipLaunchKernelGGL(emba_filter_gather_kernel, dim3(nblocks(n)), dim3(256), 0, s, x, y, pol, t, (long)n, d_keep, d_pos, (long)rate, (long)n_kept,
-                               c->evseq.x2.as<uint16_t>(), c->evseq.y2.as<uint16_t>(), c->evseq.pol2.as<uint8_t>(), c->evseq.t2.as<int64_t>());
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipStreamSynchronize(s));
-            std::swap(c->evseq.x, c->evseq.x2); std::swap(c->evseq.y, c->evseq.y2); std::swap(c->evseq.pol, c->evseq.pol2); std::swap(c->evseq.t, c->evseq.t2);
-        }
-        c->evseq.n = n_kept;
-        if (!n_kept) c->evseq.have = false;      // every event removed: emba_seq_filter finds no sequence until the next upload (the other calls see n = 0)
-    }
-    c->evseq.have_hot = true;
-    if (stats) {
-        stats[0] = n; stats[1] = h_sums[2]; stats[2] = h_sums[3]; stats[3] = h_sums[4]; stats[4] = h_sums[5]; stats[5] = n_kept;
-    }
-    return EMBA_OK;
-}
-
-extern "C" emba_status emba_seq_hot_pixels(emba_ctx* c, uint8_t* mask_host)
-{
-    if (!c) return EMBA_ERR_INVALID_ARG;
-    if (!mask_host) return fail(c, EMBA_ERR_INVALID_ARG, "mask NULL");
-    if (!c->evseq.have_hot) return fail(c, EMBA_ERR_STATE, "no filter has run on this context (emba_seq_filter first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return d2h_pageable(c, mask_host, c->evseq.f_hot.as<uint8_t>(), c->S);
-}
+#include "sequence_host.h"   // the resident event sequence of a sliding-window run: upload, windows, time shards and their halos, noise filters
 
 // ---- 3x3 median blur of the initial map (emba.cpp:357-364) -----------------------------------------------------------------------
 namespace {

@@ -23,6 +23,7 @@
 #include <thread>
 
 #include "context.h"
+#include "sequence_rule.h"
 
 namespace emba {
 
@@ -413,20 +414,19 @@ int32_t emba_group_size(const emba_group* g) { return g ? g->n : 0; }
 int32_t emba_group_uses_rccl(const emba_group* g) { return (g && g->use_rccl) ? 1 : 0; }
 emba_ctx* emba_group_ctx(emba_group* g, int32_t rank) { return (g && rank >= 0 && rank < g->n) ? g->ctx[rank] : nullptr; }
 
-// Events sorted by time, the reference's EventPacket.  Rank r gets the whole global batches [nb r / N, nb (r+1) / N) and, per sensor
+// Events sorted by time, the reference's EventPacket.  Rank r gets whole global batches (sequence_rule.h: rank_batches) and, per sensor
 // pixel, the last event before its range with the midpoint time of the (global) batch that event belongs to (emba_set_events).
 emba_status emba_group_set_events(emba_group* g, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n)
 {
     if (!g || (n && (!x || !y || !pol || !t_ns))) return g ? gfail(g, EMBA_ERR_INVALID_ARG, "event arrays are NULL") : EMBA_ERR_INVALID_ARG;
-    const size_t nb = n / 100;
+    const size_t nb = n / kBatch;
     const size_t S = (size_t)g->ctx[0]->sw * g->ctx[0]->sh;
-    for (size_t k = 0; k < nb * 100; ++k)
+    for (size_t k = 0; k < nb * kBatch; ++k)
         if (x[k] >= g->ctx[0]->sw || y[k] >= g->ctx[0]->sh) return gfail(g, EMBA_ERR_INVALID_ARG, "event %zu lies outside the sensor", k);
     std::vector<int64_t> last(S, -1);
-    size_t k = 0, b = 0;
+    size_t k = 0;
     for (int r = 0; r < g->n; ++r) {
-        const size_t cnt = nb / g->n + ((size_t)r < nb % g->n ? 1 : 0);
-        const size_t lo = b * 100, hi = (b + cnt) * 100;
+        const auto [lo, hi] = rank_batches(n, g->n, r);
         for (; k < lo; ++k) last[(size_t)y[k] * g->sw + x[k]] = (int64_t)k;      // events before this rank's range
         std::vector<uint16_t> hx, hy; std::vector<int64_t> hbt;
         if (lo) {
@@ -434,15 +434,14 @@ emba_status emba_group_set_events(emba_group* g, const uint16_t* x, const uint16
             for (size_t p = 0; p < S; ++p) if (last[p] >= 0) idx.push_back(last[p]);
             std::sort(idx.begin(), idx.end());                                      // time order
             for (int64_t i : idx) {
-                const size_t bb = (size_t)i / 100;
-                hx.push_back(x[i]); hy.push_back(y[i]); hbt.push_back(batch_mid_ns(t_ns[100 * bb], t_ns[100 * bb + 99]));
+                const size_t bb = (size_t)i / kBatch;
+                hx.push_back(x[i]); hy.push_back(y[i]); hbt.push_back(batch_mid_ns(t_ns[kBatch * bb], t_ns[kBatch * bb + kBatch - 1]));
             }
         }
         // the last rank also receives the n % 100 tail the reference drops (quirk Q1): emba_set_events ignores it the same way
         const size_t n_r = (r == g->n - 1) ? n - lo : hi - lo;
         G_TRY(g, r, emba_set_events(g->ctx[r], x + lo, y + lo, pol + lo, t_ns + lo, n_r, hx.data(), hy.data(), hbt.data(), hx.size()));
         g->n_local[r] = hi - lo; g->lo[r] = lo;
-        b += cnt;
     }
     g->x1_done = false;
     return EMBA_OK;
@@ -491,13 +490,10 @@ emba_status emba_group_set_events_seq(emba_group* g, size_t beg, size_t end)
 {
     if (!g) return EMBA_ERR_INVALID_ARG;
     if (beg > end || end > g->ctx[0]->evseq.n) return gfail(g, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, g->ctx[0]->evseq.n);
-    const size_t nb = (end - beg) / 100;
     std::vector<size_t> lo(g->n), hi(g->n);
-    size_t b = 0;
     for (int r = 0; r < g->n; ++r) {
-        const size_t cnt = nb / g->n + ((size_t)r < nb % g->n ? 1 : 0);
-        lo[r] = beg + b * 100; hi[r] = beg + (b + cnt) * 100;
-        b += cnt;
+        const EventRange b = rank_batches(end - beg, g->n, r);
+        lo[r] = beg + b.lo; hi[r] = beg + b.hi;
     }
     // the last rank also receives the n % 100 tail the reference drops (quirk Q1), as in emba_group_set_events
     { emba_status st = gpool(g, [&](int r) { return emba_set_events_seq_shard(g->ctx[r], beg, lo[r], r == g->n - 1 ? end : hi[r]); }); if (st) return st; }

@@ -132,6 +132,35 @@ def test_step_rule_on_the_cpu(tmp_path):
         assert tuple(OM.REQUIRED[opt]) == values, opt
 
 
+def test_sequence_rule_on_the_cpu(tmp_path):
+    """emba_amd/csrc/sequence_rule.h (plain C++17, no HIP): tests/cpp/sequence_rule_test.cpp checks the event window behind the probe kernel against the loops of
+    getEventSubset on a few thousand random sequences and on hand cases, the layouts of a halo and of an upload chunk, the shard check, the hot-pixel
+    threshold bit for bit against Python floats and the plan of a filter call; the ranks' batches it prints are compared here with
+    emba_amd.sharded.window_shard_ranges — the C++ rule of emba_group_set_events[_seq] against the Python one, window by window."""
+    import option_matrix as OM
+    from emba_amd.sharded import window_shard_ranges
+    from test_sequence_sharded_cpu import WINDOWS
+    consts = OM.parse_constants(os.path.join(ROOT, "emba_amd", "csrc", "sequence_kernels.h"))
+    exe = str(tmp_path / "sequence_rule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-ffp-contract=off", "-DSEQ_PROBE=%d" % consts["kSeqProbe"],
+                           os.path.join(ROOT, "tests", "cpp", "sequence_rule_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-3000:], r.stderr)
+    lines = r.stdout.strip().splitlines()
+    assert r.returncode == 0 and lines[-1] == "OK sequence_rule", r.stdout[-3000:] + r.stderr
+    got = {}
+    for l in lines:
+        if l.startswith("RANK "):
+            beg, end, world, rank, lo, hi = (int(v) for v in l.split()[1:])
+            assert rank == len(got.setdefault((beg, end, world), []))
+            got[(beg, end, world)].append((beg + lo, beg + hi))
+    assert sorted(got) == sorted((beg, end, world) for beg, end in WINDOWS for world in (1, 2, 3, 8))
+    for (beg, end, world), ranges in got.items():
+        want = window_shard_ranges(beg, end, world)
+        want[-1] = (want[-1][0], end - (end - beg) % 100)      # without the tail the last rank carries: emba_group_set_events[_seq] adds it at the call
+        assert ranges == want, (beg, end, world)
+
+
 ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "adapter_test")
 
 
