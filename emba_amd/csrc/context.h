@@ -1,6 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
-// Included by emba_hip.hip, step_host.h, solve_host.h, sequence_host.h and group.h; host code only.
+// Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, solve_host.h,
+// sequence_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -15,6 +16,7 @@
 
 #include "kernels.h"
 #include "solve_kernels.h"
+#include "map_rule.h"
 
 // Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
 // (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
@@ -99,6 +101,33 @@ private:
     int32_t mark_ = 0;
 };
 
+// The map planes in HBM and what the host knows about them (map_rule.h: MapState).  own, trial: the context's buffers, grown by the calls that fill them
+// (map_host.h).  The current (accepted) planes are own's, or the caller's memory (emba_bind_map_dev); the planes the next evaluation reads are the current
+// ones, or the trial's (emba_update_map).  The pointers and the state move together, through the functions below only.  The buffers are public so that
+// ensure() can grow them: map_host.h alone writes them, and only immediately before the transition that announces what it wrote (uploaded, trial_built,
+// blurred) — a filled buffer without its transition is never read.
+struct MapPlanes {
+    DevBuf own_x, own_y, trial_x, trial_y;
+    const double* Gx() const { return x_; }           // the planes the next evaluation reads (current or trial)
+    const double* Gy() const { return y_; }
+    const double* cur_Gx() const { return cur_x_; }   // current (accepted) map: own upload, bound, or accepted trial
+    const double* cur_Gy() const { return cur_y_; }
+    const emba::MapState& state() const { return st_; }
+    void uploaded() { to_own(); st_.uploaded(); }     // own_x / own_y have been filled
+    void bound(const double* gx, const double* gy) { x_ = cur_x_ = gx; y_ = cur_y_ = gy; st_.bound(); }
+    void trial_built() { x_ = trial_x.as<double>(); y_ = trial_y.as<double>(); st_.trial_built(); }   // trial_x / trial_y have been filled from the current planes
+    // the trial buffers become the current map; our previous buffers become the next trial buffers (nothing reads them: the current map was either
+    // they or a bound one)
+    void accepted() { std::swap(own_x, trial_x); std::swap(own_y, trial_y); to_own(); st_.accepted(); }
+    void rejected() { x_ = cur_x_; y_ = cur_y_; st_.rejected(); }
+    void blurred() { to_own(); st_.blurred(); }       // own_x / own_y have been filled with the blurred current planes
+    void texels_packed() { st_.texels_packed(); }
+private:
+    void to_own() { x_ = cur_x_ = own_x.as<double>(); y_ = cur_y_ = own_y.as<double>(); }
+    const double *x_ = nullptr, *y_ = nullptr, *cur_x_ = nullptr, *cur_y_ = nullptr;
+    emba::MapState st_;
+};
+
 // What the fused branch of form_active leaves for the Gram launch of the same equations (emba_form_accumulate).  Neither an evaluation nor a trial resets it:
 // the halves of d_fsup alternate from step to step.
 struct PostWarpState {
@@ -141,6 +170,19 @@ struct OrderState {
     double order_inl_pred = 0.0;      // ... and the inlier fraction the predicted pixels give (the rule's estimate of what the pixel order pays per event)
 };
 
+// The words of a 64-byte status block (ord.status of the window registration and the order preparation; evseq.status of the resident sequence uses the
+// same words, and two of its own in emba_seq_window).  The validation words hold the smallest offending index, 0xFFFFFFFF when clean.
+enum StatusWord : int {
+    kStFirstBad = 0,      // the first event outside the sensor (emba_validate_events_kernel, emba_seq_ingest_kernel); order_batch_segments: the first batch outside the knots
+    kStUnsorted = 1,      // the first event earlier than its predecessor
+    kStProbeA = 0, kStProbeB = 1,   // emba_seq_window only: the first probe past either cursor (kNoProbe = 0xFFFFFFFF: none)
+    kStBadHalo = 2,       // a halo event outside the sensor
+    kStTotal = 4,         // the total of a scan: measurement candidates, entries of the expanded list, halo entries
+    kStHeads = 6,         // the tile search: chain heads of the pm-order
+    kStCounter = 8,       // [8..9] a 64-bit counter (the tile search: predicted inliers, then a candidate's lead-ins); emba_seq_filter: the survivors' number
+    kStatusWords = 16
+};
+
 // The key of the lists cache: whose records (packed: the ones this rank RECEIVED as the owner of the pixels [lo, lo + P), keyed by its own working set's stamp —
 // the ranks evaluate and form in lockstep; else the local ones, lo = 0), of which evaluation, over how many pixels and records.
 struct ListsKey {
@@ -178,10 +220,7 @@ struct emba_ctx {
     // persistent device buffers
     DevBuf d_lut;
     DevBuf d_texel;
-    DevBuf d_Gx_own, d_Gy_own;
-    const double* d_Gx = nullptr; const double* d_Gy = nullptr;   // the map planes the next evaluation reads (current or trial)
-    const double* d_Gx_cur = nullptr; const double* d_Gy_cur = nullptr;   // current (accepted) map: own upload, bound, or accepted trial
-    DevBuf d_Gx_trial, d_Gy_trial; bool map_is_trial = false;
+    MapPlanes map;            // the map planes and what the host knows about them
     SolveCache solve;         // what the last solve left behind
     int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
     double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of emba_costs, written by the kernel itself
@@ -192,9 +231,7 @@ struct emba_ctx {
     PixAccState pix;          // what the host knows about the count map and the lines
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
     DevBuf d_rect;       // [0..3] {xmin,ymin,xmax,ymax} of the pixels the last formed evaluation touched; [4..7] the box the texels are PACKED for (what the warp kernel trusts)
-    bool map_bound = false;   // the current map was bound with emba_bind_map_dev: the caller's memory, which may change without a call (the trial map is always the context's own)
     uint32_t seg_seq = 0;     // the flag value of the last in-warp hand-off of segment records (never 0: the flag word starts at 0)
-    uint32_t map_version = 1, packed_version = 0;   // counts the calls that change or rebind the map planes (map_changed); the count the last texel pack read
     int step_prep = 0, step_prep_polls = 1024;   // option step_prep (A/B): 0 (default) the launch in front of the warp kernel always, 1 none where its work fits the warp launch; option step_prep_polls: the consumers' poll budget (0: none)
     emba::InlineSegParams seg_inline{}; emba::InlineKnots seg_knots{};   // what launch_prep_pose_texel leaves for the warp launch of the same evaluation (ev.prep_in_warp)
     DevBuf d_seg_flag;   // [0] the segment records' flag (a line of its own), [32] waves that formed their records themselves (diagnostics)
@@ -221,7 +258,6 @@ struct emba_ctx {
     // per-window (set_events) state — all of it lives on the device (order_kernels.h); the buffers outlive the window, what the host knows of it is win / order
     WindowState win;
     OrderState order;
-    bool have_map = false;
     DevBuf d_pm_pix, d_pm_batch, d_pm_orig;                                                         // pm-order = (sensor pixel, time): the reference's per-pixel vectors laid end to end
     DevBuf d_ev_slot;                                                                               // device order: record slot per entry
     DevBuf d_ev_pix_own, d_ev_batch_own;                                                            // tile order: the arrays order.d_ev_pix / d_ev_batch point to
@@ -281,7 +317,7 @@ struct emba_ctx {
     struct {   // once-per-window order preparation (set_events_core, prepare_order) and the device scan / sort
         DevBuf scan_sums, scan_offs;   // dev_scan
         DevBuf sort_hist;              // dev_sort
-        DevBuf status;                 // 64 B of status words: set_events_core, prepare_order
+        DevBuf status;                 // 64 B of status words (StatusWord): set_events_core, prepare_order
         DevBuf keys[2], vals[2];       // radix-sort pairs: set_events_core (pm-order), prepare_order (tile order, record slots)
         DevBuf flags;                  // set_events_core: candidate flags; prepare_order: chain-head flags, the tile binning's emit flags, candidate flags
         DevBuf pos;                    // set_events_core: candidate positions; prepare_order: head / emit positions, candidate positions
@@ -365,6 +401,11 @@ emba_status ensure(emba_ctx* c, DevBuf& b, size_t count, bool* fresh = nullptr)
     return EMBA_OK;
 }
 
+// A new evaluation begins, or the last one can no longer be asked about (its window is gone, its trial was rejected): nothing that was derived from it —
+// pending counters, the residual vector, inlier numbers, the pixel-starts table, the count map's stamp — outlives this (EvalState).
+void begin_evaluation(emba_ctx* c) { c->ev = EvalState{}; }
+
 inline unsigned nblocks(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>((n + per - 1) / per, 1); }
+long grid8(long n) { return (n + 7) / 8 * 8; }   // a grid of whole rounds over the chip's eight XCDs
 
 }  // namespace

@@ -886,7 +886,7 @@ emba_status emba_group_solve(emba_group* g, double lambda, int32_t fix_first_pos
 
 // LEGM::solveNormalEqCG (model.cpp:794-840) over the group.  One rank: the single-context solver.  Several (round 6): the pixels are sharded as in the Schur
 // solve (same record exchange, cached across re-solves) and Eigen's loop (ConjugateGradient.h:28-88) runs here on scalars that every rank reads from the same
-// all-reduced sums — emba_cg_shard_* (emba_hip.hip) are the per-rank steps, the collectives are one all-reduce of 3K + 2 doubles per matrix application and one
+// all-reduced sums — emba_cg_shard_* (solve_host.h) are the per-rank steps, the collectives are one all-reduce of 3K + 2 doubles per matrix application and one
 // of 2 doubles per iteration.
 emba_status emba_group_solve_cg(emba_group* g, double lambda, int32_t fix_first_pose, int32_t max_iter, double tol, double* x1_host, double* x2_host,
                                 int32_t* iterations, double* error)

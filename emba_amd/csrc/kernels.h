@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void emba_texel_kernel(const double* __restric
 //                              per-pixel sums of the tile (+ margin) in LDS; one atomic request per touched pixel at the end
 // ------------------------------------------------------------------------------------------------
 // LDS accumulator tile of the tiled kernel: 1152 panorama pixels x 6 doubles = 54 KB, two workgroups per CU.  Round 6: four shapes of that budget, one kernel
-// instantiation each; a window takes the shape that cuts its chains into the fewest segments (order_kernels.h: the window rule; emba_hip.hip: prepare_order).
+// instantiation each; a window takes the shape that cuts its chains into the fewest segments (order_kernels.h: the window rule; order_host.h: prepare_order).
 // {tile w, h, pitch of the tile-origin grid, its finer variant for very dense windows}
 constexpr int kNumTileShapes = 4;
 constexpr TileShape kTileShapes[kNumTileShapes] = {

@@ -157,7 +157,7 @@ __global__ void emba_validate_events_kernel(const uint16_t* __restrict__ x, cons
 }
 
 // ros::Time/Duration midpoint of a batch (model.cpp:116-119; rostime semantics per SURVEY Appendix A): the host function
-// batch_mid_ns of emba_hip.hip operation for operation (no contraction: the double scale-and-round must give the same integer).
+// batch_mid_ns of order_host.h operation for operation (no contraction: the double scale-and-round must give the same integer).
 #pragma clang fp contract(off)
 __device__ __forceinline__ int64_t batch_mid_ns_dev(int64_t t_first, int64_t t_last)
 {

@@ -3,8 +3,8 @@
 // (emba_set_events_seq[_shard], emba_seq_halo), the sensor-noise filters (emba_seq_filter, emba_seq_hot_pixels) and the downloads.  What is plain arithmetic —
 // the layouts of a chunk and of a halo, the window behind the probes, the hot-pixel threshold, what a filter call has to do — is decided in sequence_rule.h;
 // here are the buffers, the launches, the state (emba_ctx::evseq) and the C ABI.
-// Part of emba_hip.hip's translation unit, included by it below the helpers this file needs from it (dev_scan, dev_sort and their scratch, ensure_stage,
-// d2h_pageable, emba_set_events_dev) and above the group host, which calls it on every rank.
+// Part of emba_hip.hip's translation unit, included by it below the helpers this file needs (order_host.h: dev_scan, dev_sort and their scratch,
+// emba_set_events_dev; transfer_host.h: ensure_stage, d2h_pageable) and above the group host, which calls it on every rank.
 #pragma once
 #include "context.h"
 #include "sequence_kernels.h"
@@ -49,12 +49,12 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     const size_t rate = sampling_stride(sampling_rate), n_kept = sampled_count(n, sampling_rate);
     c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
     emba_status st;
-    if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRaw.bytes)) || (st = ensure<uint32_t>(c, c->evseq.status, 16)) ||
+    if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRaw.bytes)) || (st = ensure<uint32_t>(c, c->evseq.status, kStatusWords)) ||
         (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
         (st = ensure<uint8_t>(c, c->evseq.pol, std::max<size_t>(n_kept, 1))) || (st = ensure<int64_t>(c, c->evseq.t, std::max<size_t>(n_kept, 1))))
         return st;
-    uint32_t* d_err = c->evseq.status.as<uint32_t>();
-    HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, 64, s));
+    uint32_t* d_err = c->evseq.status.as<uint32_t>();      // (the ingest kernel writes kStFirstBad, kStUnsorted)
+    HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, kStatusWords * 4, s));
     uint8_t* raw = c->evseq.raw.as<uint8_t>();
     for (size_t k0 = 0, i = 0; k0 < n; k0 += kSeqChunk, ++i) {
         const size_t m = std::min(kSeqChunk, n - k0);
@@ -75,8 +75,8 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     uint32_t h_err[2];
     HIP_TRY(c, hipMemcpyAsync(h_err, d_err, sizeof h_err, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (h_err[0] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[0], c->sw, c->sh);
-    if (h_err[1] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[1]);
+    if (h_err[kStFirstBad] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[kStFirstBad], c->sw, c->sh);
+    if (h_err[kStUnsorted] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[kStUnsorted]);
     c->evseq.n = n_kept; c->evseq.have = true;
     if (n_kept_out) *n_kept_out = n_kept;
     return EMBA_OK;
@@ -92,15 +92,15 @@ extern "C" emba_status emba_seq_window(emba_ctx* c, int64_t t_beg_ns, int64_t t_
     const SeqCursors cur = seq_window_cursors(t_beg_ns, t_end_ns);
     uint32_t h_res[2] = {kNoProbe, kNoProbe};
     if (m) {
-        SEQ_TRY(ensure<uint32_t>(c, c->evseq.status, 16));
+        SEQ_TRY(ensure<uint32_t>(c, c->evseq.status, kStatusWords));
         uint32_t* d_res = c->evseq.status.as<uint32_t>();
-        HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, 8, s));
+        HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, sizeof h_res, s));      // kStProbeA, kStProbeB
         hipLaunchKernelGGL(emba_seq_window_kernel, dim3((unsigned)std::min<size_t>(nblocks(m), 1024)), dim3(256), 0, s, (const int64_t*)c->evseq.t.as<int64_t>(), (long)n, cur.a, cur.b, d_res);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(h_res, d_res, sizeof h_res, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    const SeqWindow w = seq_window(n, h_res[0], h_res[1], kSeqProbe);
+    const SeqWindow w = seq_window(n, h_res[kStProbeA], h_res[kStProbeB], kSeqProbe);
     if (w.status == SeqWindowStatus::stops_at_first_probe)
         return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (the tail search stops at its first probe, event %zu)", w.beg);
     if (w.status == SeqWindowStatus::begins_behind_last) return fail(c, EMBA_ERR_INVALID_ARG, "window holds no events (it begins behind the last event)");
@@ -129,12 +129,12 @@ emba_status build_seq_halo(emba_ctx* c, size_t win_beg, size_t lo, size_t* n_hal
     if (m > 0x7FFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events in front of the shard for 32-bit indices");
     emba_status st;
     if ((st = ensure<int32_t>(c, c->evseq.halo_last, c->S)) || (st = ensure<uint32_t>(c, c->evseq.halo_flag, m)) || (st = ensure<uint32_t>(c, c->evseq.halo_pos, m)) ||
-        (st = ensure<uint32_t>(c, c->evseq.status, 16)))
+        (st = ensure<uint32_t>(c, c->evseq.status, kStatusWords)))
         return st;
     const uint16_t *x = c->evseq.x.as<uint16_t>() + win_beg, *y = c->evseq.y.as<uint16_t>() + win_beg;
     const int64_t* t = c->evseq.t.as<int64_t>() + win_beg;
     int32_t* last = c->evseq.halo_last.as<int32_t>();
-    uint32_t *flag = c->evseq.halo_flag.as<uint32_t>(), *pos = c->evseq.halo_pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + 4;
+    uint32_t *flag = c->evseq.halo_flag.as<uint32_t>(), *pos = c->evseq.halo_pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + kStTotal;
     HIP_TRY(c, hipMemsetAsync(last, 0xFF, c->S * sizeof(int32_t), s));      // -1: no event of this pixel
     hipLaunchKernelGGL(emba_halo_last_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, last);
     hipLaunchKernelGGL(emba_halo_flag_kernel, dim3(nblocks(m)), dim3(256), 0, s, x, y, (long)m, c->sw, (const int32_t*)last, flag);
@@ -239,7 +239,7 @@ emba_status filter_reserve(emba_ctx* c, const FilterPlan& plan)
 {
     SEQ_TRY(ensure<uint8_t>(c, c->evseq.f_hot, plan.S));
     SEQ_TRY(ensure<uint64_t>(c, c->evseq.f_sums, 8));
-    SEQ_TRY(ensure<uint32_t>(c, c->evseq.status, 16));
+    SEQ_TRY(ensure<uint32_t>(c, c->evseq.status, kStatusWords));
     if (plan.sorts) {
         SEQ_TRY(ensure_sort_pairs(c, plan.n));
         SEQ_TRY(ensure<uint32_t>(c, c->ord.flags, plan.n));
@@ -293,7 +293,7 @@ emba_status filter_flag_and_count(emba_ctx* c, const FilterPlan& plan, int64_t r
 {
     hipStream_t s = c->stream;
     const size_t n = plan.n;
-    uint32_t *keep = c->ord.flags.as<uint32_t>(), *pos = c->ord.pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + 8;
+    uint32_t *keep = c->ord.flags.as<uint32_t>(), *pos = c->ord.pos.as<uint32_t>(), *d_tot = c->evseq.status.as<uint32_t>() + kStCounter;
     unsigned long long* d_sums = c->evseq.f_sums.as<unsigned long long>();
     hipLaunchKernelGGL(emba_filter_flags_kernel, dim3(nblocks(n)), dim3(256), 0, s, f->keys, f->vals, (const int64_t*)c->evseq.t.as<int64_t>(), (long)n, c->sw, c->sh,
                        (const uint32_t*)c->evseq.f_start.as<uint32_t>(), (const uint8_t*)c->evseq.f_hot.as<uint8_t>(), refractory_ns, support_ns, keep, d_sums);

@@ -2,8 +2,9 @@
 // (emba_eval_launch / _finish), the active set (emba_form_active), the Gram launch (emba_form_accumulate), emba_form_finish, the resident emba_step, the count-map
 // exchange of a sharded window and the counters an evaluation leaves pending.  What is plain arithmetic — the pack's layout, which source, form and plan a
 // launch takes — is decided in step_rule.h; here are the buffers, the launches, the state and the C ABI.
-// Part of emba_hip.hip's translation unit, included by it below the helpers this file needs from it (prepare_order, size_record_set, dev_scan, d2h_pageable,
-// begin_evaluation, grid8) and above the map calls, downloads and solvers that wait for its counters (resolve_pending).
+// Part of emba_hip.hip's translation unit, included by it below the helpers this file needs (order_host.h: prepare_order, size_record_set, dev_scan;
+// transfer_host.h: d2h_pageable; context.h: begin_evaluation, grid8) and above the map calls (map_host.h), downloads and solvers that wait for its counters
+// (resolve_pending).
 #pragma once
 #include "context.h"
 #include "step_rule.h"
@@ -226,7 +227,7 @@ emba_status eval_checks_and_buffers(emba_ctx* c, const double* knots, int32_t K,
 {
     if (!knots) return fail(c, EMBA_ERR_INVALID_ARG, "knots NULL");
     if (!c->win.have_events) return fail(c, EMBA_ERR_STATE, "emba_set_events has not been called");
-    if (!c->have_map) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
+    if (!c->map.state().resident()) return fail(c, EMBA_ERR_STATE, "no map: call emba_upload_map or emba_bind_map_dev");
     HIP_TRY(c, hipSetDevice(c->device));
     STEP_TRY(ensure<double>(c, c->d_knots, (size_t)4 * K));
     STEP_TRY(ensure<double>(c, c->d_seg, (size_t)kSegStride * K));
@@ -304,12 +305,12 @@ emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, 
     q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
     // texels are packed when they are stale, not in every evaluation: another map, or the last formed box has left the packed one (h_pinned[5]: the verdict of
     // the active-set write that reduced it — it precedes the sequence words, so once c->seq is there it is this step's)
-    const bool map_owned = c->map_is_trial || !c->map_bound;
-    const bool stale = texels_stale(map_owned, c->map_version, c->packed_version, ((volatile int*)c->h_pinned)[5], c->seq);
+    const MapState& map = c->map.state();
+    const bool stale = texels_stale(map.reads_own_memory(), map.version(), map.packed_version(), ((volatile int*)c->h_pinned)[5], c->seq);
     q.n_tex = texel_blocks(c->ev.use_texel, stale);
-    if (q.n_tex) c->packed_version = c->map_version;
+    if (q.n_tex) c->map.texels_packed();
     c->ev.texels_packed = q.n_tex != 0;
-    q.Gx = c->d_Gx; q.Gy = c->d_Gy;
+    q.Gx = c->map.Gx(); q.Gy = c->map.Gy();
     q.rect = c->d_rect.as<int>(); q.rect_packed = c->d_rect.as<int>() + 4;
     q.texel = c->d_texel.as<double>();
     if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }   // (no launch in front: an empty first interval)
@@ -345,7 +346,7 @@ emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
     p.texel = c->ev.use_texel ? c->d_texel.as<double>() : nullptr;
     p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() + 4 : nullptr;      // the box the texels are packed for
     p.W = c->W; p.H = c->H;
-    p.Gx = c->d_Gx; p.Gy = c->d_Gy;
+    p.Gx = c->map.Gx(); p.Gy = c->map.Gy();
     p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy;
     p.C_th = c->C_th; p.outlier_px = c->outlier_px;
     p.count = c->d_count; p.pixacc = c->d_pixacc.as<double>();
@@ -380,7 +381,7 @@ emba_status eval_launch(emba_ctx* c, const double* knots, int32_t K, int64_t t0_
     STEP_TRY(clear_on_first_use(c));
     STEP_TRY(launch_prep_pose_texel(c, knots, K, t0_ns, dt_ns));
     if (c->ev.use_texel == 1)
-        hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, c->stream, c->d_Gx, c->d_Gy, c->H, c->W, c->d_texel.as<double>());
+        hipLaunchKernelGGL(emba_texel_kernel, dim3((c->W + 255) / 256, c->H), dim3(256), 0, c->stream, c->map.Gx(), c->map.Gy(), c->H, c->W, c->d_texel.as<double>());
     if (c->win.n_sorted) STEP_TRY(launch_warp(c, opt));
     else c->pix.not_marked();
     HIP_TRY(c, hipGetLastError());
@@ -441,7 +442,7 @@ void fill_active_write(emba_ctx* c, int32_t thres, const FormOpts& opt, ActiveWr
     aw.A22b2 = pack_A22b2(c); aw.alpha = opt.fused_alpha;
     aw.pack_head = c->d_pack; aw.head_len = (long)pack.head;
     aw.max_P = (long)pack.max_P(c->pack_cap);
-    aw.Gx = c->d_Gx; aw.Gy = c->d_Gy;
+    aw.Gx = c->map.Gx(); aw.Gy = c->map.Gy();
     aw.ablate = c->ablate;
     // the resident step cleared this evaluation's per-pixel sums behind its gather: a second formNormalEq on the same evaluation takes A22 | b2
     // from the records (the generic path of emba_form_accumulate), and its L2 term from emba_form_finish
@@ -756,7 +757,7 @@ extern "C" emba_status emba_form_finish(emba_ctx* c, double alpha, double* A11, 
         const size_t bound = c->ev.P_pending ? c->npix : c->eq.P;
         if (bound)
             hipLaunchKernelGGL(emba_l2reg_kernel, dim3((unsigned)((bound + 255) / 256)), dim3(256), 0, c->stream, pack_A22b2(c), c->d_active.as<uint32_t>(),
-                               c->d_total.as<uint32_t>() + 1, alpha, c->d_Gx, c->d_Gy);
+                               c->d_total.as<uint32_t>() + 1, alpha, c->map.Gx(), c->map.Gy());
     }
     HIP_TRY(c, hipGetLastError());
     const bool download = A11 || b1 || active_idx || A22 || b2 || A12_dense;

@@ -46,7 +46,7 @@ inline bool segpose_in_pixel_order(bool tile_order, int segpose_mode) { return !
 
 // The packed texels (source 3) describe ONE map and ONE rectangle.  They are packed again when either no longer holds, not in every evaluation: on the same map and
 // inside the same rectangle the pack writes the same bytes (a poses-only refinement, every re-evaluation on one map, the benchmark).
-//   the map: the host counts every call that changes or rebinds the planes (map_version) and remembers which count the last pack read.  A map the caller bound is the
+//   the map: the host counts every call that changes or rebinds the planes (map_rule.h: MapState) and remembers which count the last pack read.  A map the caller bound is the
 //   caller's memory and may change without a call: it is never taken for unchanged.
 //   the rectangle: the pack covers the last formed evaluation's box grown by kRectMargin, and the warp kernel trusts the PACKED rectangle only (outside it: the
 //   stencil, slow, never wrong).  The active-set write's last block, which reduces the new box, compares it on the device with the packed one and publishes the

@@ -161,6 +161,18 @@ def test_sequence_rule_on_the_cpu(tmp_path):
         assert ranges == want, (beg, end, world)
 
 
+def test_map_rule_on_the_cpu(tmp_path):
+    """emba_amd/csrc/map_rule.h (plain C++17, no HIP): tests/cpp/map_rule_test.cpp walks every sequence of MapState's transitions up to length 6, from the created
+    state and from an uploaded one, beside the loose context fields and hand-written assignments MapState replaced — every query, both versions, what the
+    state refuses and the verdict of texels_stale (both outcomes of each of its clauses occur) agree after every step; the version never decreases and
+    stays only across a reject without a pending trial and across a texel pack."""
+    exe = str(tmp_path / "map_rule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "map_rule_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-3000:], r.stderr)
+    assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "OK map_rule", r.stdout[-3000:] + r.stderr
+
+
 ADAPTER_EXE = os.path.join(ROOT, "tests", "cpp", "_build", "adapter_test")
 
 

@@ -229,6 +229,64 @@ def test_a_bound_map_is_never_taken_for_unchanged(gpu, contexts):
     same(r, fresh(contexts, w, w.traj, 0.5 * w.Gx, w.Gy), "bound map changed in place")
 
 
+def test_the_planes_follow_every_transition(gpu, contexts, oracle_mod):
+    """The PLANES after each call that changes or rebinds them (the tests above see them through the texels only): one context walks upload, bind, the blur of
+    a bound map, a trial update, a second update before an accept, accept, a reject without a trial, another update, its reject; after each,
+    emba_download_map against an expectation kept in numpy.  What only rebinds or copies is compared bit for bit, the blur with its restatement
+    (emba_amd.io.median_blur3, exact), an update as test_gpu_parity.test_lm_loop_map_residency does: oracle update_map of the active set, at its tolerance.
+    (The dampings are powers of two: damping * x2 is then exact, so that a fused multiply-add gives the bits of a multiply and an add.)"""
+    import torch
+    from emba_amd import io as eio
+    w = workload(5)
+
+    def planes(want, what, exact=True):
+        got = m.downloadMap()
+        for g, e, n in zip(got, want, ("Gx", "Gy")):
+            if exact:
+                assert np.array_equal(g, e), f"{n} after {what}"
+            else:
+                assert np.allclose(g, e, rtol=0, atol=1e-16), f"{n} after {what}"
+        return got
+
+    def solved_step():
+        """step + solve on the planes the next evaluation reads: the active set and x2 an update is built from"""
+        m.step(w.traj, w.thres_valid_pixel, w.alpha)
+        ne = m._finish(w.alpha, False)
+        _, x2 = m.solveNormalEq(1e-2, fix_first_pose=True)
+        assert 0 < ne["P"] < w.Gx.size and x2.any(), "the window has active and inactive pixels, and the solve moves the map"
+        return ne["active"], x2
+
+    m = contexts(w)                                                                        # 1. upload
+    cur = planes((w.Gx, w.Gy), "emba_upload_map")
+    bound = (np.ascontiguousarray(0.5 * w.Gx), np.ascontiguousarray(0.5 * w.Gy + 0.25 * w.Gx))
+    gx, gy = (torch.from_numpy(a.copy()).cuda() for a in bound)
+    m.bind_map_dev(gx.data_ptr(), gy.data_ptr())                                           # 2. bind, other values
+    cur = planes(bound, "emba_bind_map_dev")
+    m.median_blur_map()                                                                    # 3. the blur of a bound map: the result is the context's own
+    cur = planes((eio.median_blur3(bound[0]), eio.median_blur3(bound[1])), "emba_median_blur3_map on a bound map")
+    assert not np.array_equal(cur[0], bound[0])
+    torch.cuda.synchronize()
+    assert np.array_equal(gx.cpu().numpy(), bound[0]) and np.array_equal(gy.cpu().numpy(), bound[1]), "the blur wrote the caller's tensors"
+    active, x2 = solved_step()                                                             # 4. step, solve, update
+    m.updateMap(x2, 0.5)
+    first = planes(oracle_mod.update_map(active, x2, 0.5, *cur), "emba_update_map", exact=False)
+    assert (first[0].ravel()[np.setdiff1d(np.arange(first[0].size), active)] == 0).all()
+    m.updateMap(x2, 0.25)                                                                  # 5. again, another damping, no accept: from the CURRENT planes
+    second = planes(oracle_mod.update_map(active, x2, 0.25, *cur), "a second emba_update_map before an accept", exact=False)
+    from_first = oracle_mod.update_map(active, x2, 0.25, *first)
+    assert not np.allclose(second[0], from_first[0], rtol=0, atol=1e-16), "the case cannot tell the current planes from the first trial"
+    m.acceptMap()                                                                          # 6. accept: the trial's values
+    cur = planes(second, "emba_map_accept")
+    m.rejectMap()                                                                          # 7. reject with no trial pending: nothing moves
+    planes(cur, "emba_map_reject without a trial")
+    active, x2 = solved_step()                                                             # 8. step, solve, update
+    m.updateMap(x2, 0.5)
+    trial = planes(oracle_mod.update_map(active, x2, 0.5, *cur), "emba_update_map on the accepted map", exact=False)
+    assert not np.array_equal(trial[0], cur[0])
+    m.rejectMap()                                                                          # 9. reject: the accepted planes again
+    planes(cur, "emba_map_reject")
+
+
 def test_a_footprint_that_leaves_the_packed_rectangle(gpu, contexts):
     """A trajectory whose pixels leave the packed rectangle: that step meets the stencil outside it (same values), the next one packs the new rectangle."""
     w = workload(5)
