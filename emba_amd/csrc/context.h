@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, solve_host.h,
-// sequence_host.h, group.h); host code only.
+// sequence_host.h, cmax_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "solve_kernels.h"
 #include "map_rule.h"
+#include "cmax_rule.h"
 
 // Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
 // (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
@@ -205,6 +206,10 @@ struct SolveCache {
     void invalidate() { lists_valid = false; perm_valid = false; }   // the records or the active set changed: neither the lists nor the column order hold
 };
 
+// Grow-only buffers of contrast maximisation (cmax_host.h): the per-slice results of emba_seq_cmax (t_ref: one entry more than slices), and the
+// candidates of emba_seq_cmax_objective with their J and their images.
+struct CmaxBuffers { DevBuf omega, t_ref, j0, j, evals, cand, cand_j, cand_iwe; };
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -365,6 +370,11 @@ struct emba_ctx {
             n = 0; have = have_hot = false;
         }
     } evseq;
+    // contrast maximisation on that sequence (cmax_host.h): the pinhole of the image plane, fitted to the bearing LUT by emba_create (ok: there is one);
+    // the per-slice results of emba_seq_cmax (t_ref: one entry more, the last estimated event's time); the candidates of emba_seq_cmax_objective, their J
+    // and their images.
+    emba::CmaxPinhole cmax_pin;
+    CmaxBuffers cmax;
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -2,7 +2,8 @@
 // step's counters, emba_dump_state, the option tables, the timers and probes, f3 and the record_data images.  Every path with state of its own is a host header
 // with a HIP-free rule header beside it: the context is context.h, copies into the caller's pageable memory transfer_host.h, the window and its order
 // order_host.h / order_rule.h, the step path (the evaluation and the normal equations) step_host.h / step_rule.h, the map map_host.h / map_rule.h, the solvers
-// (f1) solve_host.h / solve_rule.h, the resident event sequence sequence_host.h / sequence_rule.h, the multi-GPU group group.h: all one translation unit.
+// (f1) solve_host.h / solve_rule.h, the resident event sequence sequence_host.h / sequence_rule.h, contrast maximisation on it
+// cmax_host.h / cmax_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
 // (emba_set_events: pose-independent structure), launches kernels and moves bytes.
@@ -109,6 +110,7 @@ emba_status emba_create(const emba_cfg* cfg, emba_ctx** out)
         }
         c->fov_x = x1 > x0 ? x1 - x0 : M_PI; c->fov_y = y1 > y0 ? y1 - y0 : M_PI;
     }
+    c->cmax_pin = cmax_pinhole_fit(cfg->bearing_lut, c->sw, c->sh);   // the image plane of contrast maximisation (cmax_rule.h); asked for by emba_seq_cmax* only
     c->cfg.bearing_lut = nullptr;  // not retained
     CREATE_TRY(c->d_texel.ensure(c->npix * kTexelStride * sizeof(double)));
     CREATE_TRY(c->d_count_own.ensure(c->npix * sizeof(int32_t)));
@@ -958,6 +960,7 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
 }
 
 #include "sequence_host.h"   // the resident event sequence of a sliding-window run: upload, windows, time shards and their halos, noise filters
+#include "cmax_host.h"       // contrast maximisation on it: the angular velocity of every slice of events, from the events alone
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

@@ -37,6 +37,21 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     hot_pixel_sigma: float = 0.0    # a pixel is hot when its event count exceeds mean + sigma * std over the pixels that have events
     refractory_period: float = 0.0  # seconds: an event closer than this behind its pixel's previous event is dropped
     support_time: float = 0.0       # seconds: an event is kept only if one of its eight neighbours fired at most this long before it
+    # The raw poses.  "given": pose_t, pose_q are a front end's.  "events": there is no front end — the angular velocity of every slice of cmax_slice_events
+    # events is estimated from the events alone by contrast maximisation (the rule: include/emba_hip.h, emba_seq_cmax) after the filters and
+    # the down-sampling, on the device where the sequence is resident (LEGM.estimate_angular_velocity), else by io.estimate_angular_velocity, and integrated
+    # from the identity (io.integrate_angular_velocity); pose_t, pose_q may then be None.
+    init_poses: str = "given"
+    cmax_slice_events: int = 10000
+    cmax_omega_max: float = 8.0
+
+    def __post_init__(self):
+        if self.init_poses not in ("given", "events"):
+            raise ValueError(f"SequenceSettings.init_poses must be 'given' or 'events', not {self.init_poses!r}")
+        if int(self.cmax_slice_events) < 1:
+            raise ValueError(f"SequenceSettings.cmax_slice_events = {self.cmax_slice_events}: a slice has at least one event")
+        if not (np.isfinite(self.cmax_omega_max) and self.cmax_omega_max > 0):
+            raise ValueError("SequenceSettings.cmax_omega_max must be finite and positive")
 
 
 @dataclass
@@ -59,6 +74,8 @@ class SequenceResult:
     windows: list = field(default_factory=list)
     n_events: int = 0           # events of the sequence after down-sampling
     filter_stats: object = None # with a noise filter on: uint64[6] — events in, hot pixels, events failing hot / refractory / support, events kept
+    cmax: object = None         # SequenceSettings.init_poses = "events": what estimate_angular_velocity returned (omega, t_ref_ns, J0, J, evals) + the raw
+                                # poses made of it (pose_t, pose_q)
 
 
 def keeps_sequence(model):
@@ -67,10 +84,31 @@ def keeps_sequence(model):
     return hasattr(model, "set_sequence") and bool(getattr(model, "has_resident_sequence", True))
 
 
+def estimate_raw_poses(model, events, seq, resident_sequence):
+    """SequenceSettings.init_poses = "events": the raw poses of a run from its events alone.  events: the recording as the windows will see it (a model with
+    a resident sequence asks its device instead; a ShardedModel every rank's own context — every rank holds the same sequence and the rule is deterministic
+    integer arithmetic, so all get the same estimate without a collective).  The integrated trajectory is
+    sampled every dt_knots / 10 over [t_start, t_end], so that every knot interval has poses to fit whatever the slices' length.  Returns the dict of the
+    estimate + pose_t, pose_q."""
+    m, wmax = int(seq.cmax_slice_events), float(seq.cmax_omega_max)
+    if resident_sequence and hasattr(model, "estimate_angular_velocity"):
+        est = model.estimate_angular_velocity(m, wmax)
+    else:
+        lut, sw, sh = getattr(model, "bearing_lut", None), getattr(model, "sensor_w", None), getattr(model, "sensor_h", None)
+        if lut is None or not sw or not sh:
+            raise ValueError("init_poses = 'events' without a resident sequence needs the camera: model.bearing_lut, model.sensor_w, model.sensor_h")
+        est = emba_io.estimate_angular_velocity(events, lut, sw, sh, m, wmax)
+    if not len(est["omega"]):
+        raise ValueError(f"init_poses = 'events': the sequence is shorter than one slice of {m} events")
+    t0, t1, step = emba_io.ros_time_ns(seq.t_start), emba_io.ros_time_ns(seq.t_end), max(int(1e9 * seq.dt_knots) // 10, 1)
+    pose_t, pose_q = emba_io.integrate_angular_velocity(est["omega"], est["t_ref_ns"], np.arange(t0, t1 + step, step, dtype=np.int64))
+    return dict(est, pose_t=pose_t, pose_q=pose_q)
+
+
 def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm=LMSettings(), runtime_log=None, map_recorder=None, resident=True,
                  resident_sequence=None, verbose=False):
     """model: emba_amd.LEGM (or anything solve_time_window drives).  events: the whole recording (EventPacket, sorted).  pose_t [n] seconds, pose_q [n,4]
-    xyzw: the raw front-end poses (io.load_poses).  Gx, Gy: the initial map (both None with seq.init_map = "events").  runtime_log / map_recorder: ONE object for the run — their counters run over
+    xyzw: the raw front-end poses (io.load_poses; both None with seq.init_poses = "events": they are estimated from the events, SequenceResult.cmax).  Gx, Gy: the initial map (both None with seq.init_map = "events").  runtime_log / map_recorder: ONE object for the run — their counters run over
     the windows like the reference's function statics.  resident: as in solve_time_window.  resident_sequence: keep the sequence on the device (default:
     wherever the model can); False registers every window from a host slice (emba_set_events) instead."""
     if seq.init_map not in ("given", "events"):
@@ -81,11 +119,10 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         raise ValueError("no initial map: pass Gx, Gy or set SequenceSettings.init_map = 'events'")
     if seq.init_map == "events" and ba.use_CG:
         raise ValueError("init_map = 'events' starts with a map-only solve, which use_CG cannot do")
+    if seq.init_poses == "given" and (pose_t is None or pose_q is None):
+        raise ValueError("no raw poses: pass pose_t, pose_q or set SequenceSettings.init_poses = 'events'")
     if resident_sequence is None:
         resident_sequence = keeps_sequence(model)
-    pose_t = np.asarray(pose_t, dtype=np.float64)
-    pose_q = np.asarray(pose_q, dtype=np.float64).reshape(-1, 4)
-    pose_t_ns = np.array([emba_io.ros_time_ns(t) for t in pose_t], dtype=np.int64)      # std::map<ros::Time, SO3d>, pose_manager.cpp:41-80
 
     # event down-sampling, emba.cpp:281-304
     filter_stats = None
@@ -109,6 +146,14 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
     else:
         events = emba_io.downsample_events(events, seq.event_sampling_rate)
         n_seq = events.size()
+
+    cmax = None
+    if seq.init_poses == "events":
+        cmax = estimate_raw_poses(model, events, seq, resident_sequence)
+        pose_t, pose_q = cmax["pose_t"], cmax["pose_q"]
+    pose_t = np.asarray(pose_t, dtype=np.float64)
+    pose_q = np.asarray(pose_q, dtype=np.float64).reshape(-1, 4)
+    pose_t_ns = np.array([emba_io.ros_time_ns(t) for t in pose_t], dtype=np.int64)      # std::map<ros::Time, SO3d>, pose_manager.cpp:41-80
 
     # time cursors, emba.cpp:309-323
     win_size = emba_io.ros_time_ns(seq.time_window_size)
@@ -137,7 +182,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         else:
             Gx, Gy = emba_io.median_blur3(Gx), emba_io.median_blur3(Gy)
 
-    out = SequenceResult(None, [], n_seq, filter_stats)
+    out = SequenceResult(None, [], n_seq, filter_stats, cmax)
     while t_win_end < t_BA_end + 1_000_000:                                             # :406
         # :409 getEventSubset
         if resident_sequence:

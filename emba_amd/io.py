@@ -350,3 +350,195 @@ def filter_events(events, sensor_w, sensor_h, hot_sigma=0.0, refractory_ns=0, su
     stats[1], stats[2], stats[3], stats[4], stats[5] = int(hot.sum()), int(fail_hot.sum()), int(fail_ref.sum()), int(fail_sup.sum()), int(keep.sum())
     out = EventPacket(np.asarray(events.x)[keep], np.asarray(events.y)[keep], np.asarray(events.polarity)[keep], np.asarray(events.t_ns)[keep])
     return out, stats, hot.astype(np.uint8)
+
+
+# ---- angular velocity from the events alone: contrast maximisation (numpy form of emba_seq_cmax / emba_seq_cmax_objective, include/emba_hip.h; the
+# device forms are LEGM.estimate_angular_velocity / LEGM.cmax_objective).  The rule — grid, pinhole, warp, votes, search — is emba_amd/csrc/cmax_rule.h's
+# and cmax_kernels.h's, operation for operation: J and the image are integers, so both forms give the same bits.
+CMAX_GRID_CELLS = (64 << 10) // 4        # kCmaxMaxCells: the uint32 cells that fit 64 KiB
+CMAX_MAX_RANGE = (1 << 24) - 1           # kCmaxMaxRange: events a 32-bit cell counts exactly
+CMAX_MAX_ITER = 64                       # kCmaxMaxIter
+
+
+def cmax_grid(sensor_w, sensor_h):
+    """(shift, grid_w, grid_h): cells of 2^shift sensor pixels, shift the smallest for which the grid of uint32 cells fits 64 KiB (cmax_rule.h: cmax_grid)."""
+    s = 0
+    while True:
+        gw, gh = (int(sensor_w) + (1 << s) - 1) >> s, (int(sensor_h) + (1 << s) - 1) >> s
+        if gw * gh <= CMAX_GRID_CELLS:
+            return s, gw, gh
+        s += 1
+
+
+def _cmax_fit_line(lut, first, stride, count, comp):
+    """cmax_rule.h: cmax_fit_line — python floats, every operation rounded on its own, the sums in index order."""
+    pts = []
+    for i in range(count):
+        b = lut[first + i * stride]
+        if not float(b[2]) > 0.0:
+            continue
+        pts.append((float(i), float(b[comp]) / float(b[2])))
+    if not pts:
+        return 0.0, 0.0, 0.0, False
+    sp = sr = 0.0
+    for p, r in pts:
+        sp = sp + p
+        sr = sr + r
+    m_pos, m_ratio = sp / float(len(pts)), sr / float(len(pts))
+    spr = srr = 0.0
+    for p, r in pts:
+        dp, dr = p - m_pos, r - m_ratio
+        spr = spr + dp * dr
+        srr = srr + dr * dr
+    if len(pts) < 2 or not srr > 0.0:
+        return m_pos, m_ratio, 0.0, False
+    slope = spr / srr
+    return m_pos, m_ratio, slope, bool(np.isfinite(slope) and slope > 0.0)
+
+
+def cmax_pinhole_fit(lut, sensor_w, sensor_h):
+    """(f, cu, cv) of the ideal pinhole u = f b'x / b'z + cu, v = f b'y / b'z + cv behind the image of warped events: least squares of x over b.x / b.z
+    along the LUT's centre row and of y over b.y / b.z along its centre column (cmax_rule.h: cmax_pinhole_fit, the same operations in the same order).
+    Raises ValueError where neither line has a positive slope."""
+    sw, sh = int(sensor_w), int(sensor_h)
+    lut = np.asarray(lut, dtype=np.float64).reshape(sw * sh, 3)
+    rp, rr, rs, rok = _cmax_fit_line(lut, (sh // 2) * sw, 1, sw, 0)
+    cp, cr, cs, cok = _cmax_fit_line(lut, sw // 2, sw, sh, 1)
+    if not rok and not cok:
+        raise ValueError("the bearing LUT has no pinhole fit")
+    f = (rs + cs) * 0.5 if (rok and cok) else (rs if rok else cs)
+    cu, cv = rp - f * rr, cp - f * cr
+    if not (np.isfinite(f) and np.isfinite(cu) and np.isfinite(cv)):
+        raise ValueError("the bearing LUT has no pinhole fit")
+    return f, cu, cv
+
+
+def cmax_objective(events, lut, sensor_w, sensor_h, omega, beg=0, end=None, want_iwe=True, pinhole=None):
+    """J(w) = sum of I^2 over the image of warped events of events[beg:end], t_ref = t[beg], for every candidate of omega [M, 3]: (J uint64 [M],
+    iwe uint32 [M, grid_h, grid_w] or None).  The rule of emba_seq_cmax_objective (include/emba_hip.h), vectorised over the events."""
+    sw, sh = int(sensor_w), int(sensor_h)
+    shift, gw, gh = cmax_grid(sw, sh)
+    f, cu, cv = pinhole if pinhole is not None else cmax_pinhole_fit(lut, sw, sh)
+    lut = np.asarray(lut, dtype=np.float64).reshape(sw * sh, 3)
+    omega = np.asarray(omega, dtype=np.float64).reshape(-1, 3)
+    if not np.isfinite(omega).all():
+        raise ValueError("omega is not finite")
+    n = int(np.asarray(events.t_ns).size)
+    end = n if end is None else int(end)
+    beg = int(beg)
+    if not 0 <= beg <= end <= n:
+        raise ValueError(f"[{beg}, {end}) is not a range of the sequence of {n} events")
+    if end - beg > CMAX_MAX_RANGE:
+        raise ValueError(f"[{beg}, {end}): the 32-bit cells of the image count at most {CMAX_MAX_RANGE} events exactly")
+    M, cells = omega.shape[0], gw * gh
+    J = np.zeros(M, dtype=np.uint64)
+    iwe = np.zeros((M, gh, gw), dtype=np.uint32) if want_iwe else None
+    if beg == end:
+        return J, iwe
+    t = np.asarray(events.t_ns, dtype=np.int64)[beg:end]
+    p = np.asarray(events.y, dtype=np.int64)[beg:end] * sw + np.asarray(events.x, dtype=np.int64)[beg:end]
+    b0, b1, b2 = lut[p, 0], lut[p, 1], lut[p, 2]
+    hdt = ((t - t[0]).astype(np.float64) * 1e-9) * 0.5
+    inv = 1.0 / float(1 << shift)
+    for j in range(M):
+        a0, a1, a2 = omega[j, 0] * hdt, omega[j, 1] * hdt, omega[j, 2] * hdt
+        aa = (a0 * a0 + a1 * a1) + a2 * a2
+        c0, c1, c2 = a1 * b2 - a2 * b1, a2 * b0 - a0 * b2, a0 * b1 - a1 * b0
+        d0, d1, d2 = a1 * c2 - a2 * c1, a2 * c0 - a0 * c2, a0 * c1 - a1 * c0
+        s = 1.0 + aa
+        r0, r1, r2 = s * b0 + 2.0 * (c0 + d0), s * b1 + 2.0 * (c1 + d1), s * b2 + 2.0 * (c2 + d2)
+        with np.errstate(all="ignore"):
+            front = r2 > 0.0
+            r2s = np.where(front, r2, 1.0)
+            gx, gy = (f * (r0 / r2s) + cu) * inv, (f * (r1 / r2s) + cv) * inv
+            ok = front & (gx >= -1.0) & (gx < float(gw)) & (gy >= -1.0) & (gy < float(gh))
+        gx, gy = gx[ok], gy[ok]
+        fx, fy = np.floor(gx), np.floor(gy)
+        ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+        wx, wy = ((gx - fx) * 16.0).astype(np.int64), ((gy - fy) * 16.0).astype(np.int64)
+        acc = np.zeros(cells, dtype=np.float64)         # (sums of integers below 2^32: exact in a double)
+        for dx, dy, v in ((0, 0, (16 - wx) * (16 - wy)), (1, 0, wx * (16 - wy)), (0, 1, (16 - wx) * wy), (1, 1, wx * wy)):
+            cx, cy = ix + dx, iy + dy
+            ins = (cx >= 0) & (cx < gw) & (cy >= 0) & (cy < gh)
+            acc += np.bincount((cy * gw + cx)[ins], weights=v[ins].astype(np.float64), minlength=cells)
+        I = acc.astype(np.uint64)
+        J[j] = (I * I).sum(dtype=np.uint64)
+        if want_iwe:
+            iwe[j] = I.astype(np.uint32).reshape(gh, gw)
+    return J, iwe
+
+
+def cmax_search(J_of, omega_max):
+    """The compass search of one slice (cmax_rule.h: CmaxSearch) over J_of(omega [6, 3]) -> six integers: (omega [3], J0, J, evaluations); J_of is first
+    asked for omega = 0 alone.  same_instant slices are the caller's."""
+    w = [0.0, 0.0, 0.0]
+    J0 = J = int(J_of(np.zeros((1, 3)))[0])
+    step, min_step, it, evals = omega_max * 0.5, omega_max * (1.0 / 4096.0), 0, 1
+    while it < CMAX_MAX_ITER and not step < min_step:
+        cand = np.array([w] * 6)
+        for c in range(6):
+            cand[c, c >> 1] = w[c >> 1] + (-1.0 if c & 1 else 1.0) * step
+        Jc = [int(v) for v in J_of(cand)]
+        evals += 6
+        best = max(range(6), key=lambda c: (Jc[c], -c))      # ties: the earlier candidate
+        if Jc[best] > J:
+            w, J = [float(v) for v in cand[best]], Jc[best]
+        else:
+            step = step * 0.5
+        it += 1
+    return w, J0, J, evals
+
+
+def estimate_angular_velocity(events, lut, sensor_w, sensor_h, slice_events, omega_max):
+    """The angular velocity of every slice of slice_events events by contrast maximisation: the rule of emba_seq_cmax (include/emba_hip.h) in numpy, for
+    models without a resident sequence and for the tests.  Returns a dict: omega float64 [n_slices, 3] (rad/s, body frame), t_ref_ns int64 [n_slices + 1]
+    (every slice's first timestamp, then the last estimated event's; empty where n_slices = 0), J0, J uint64 [n_slices], evals int32 [n_slices]."""
+    m, omega_max = int(slice_events), float(omega_max)
+    if m < 1:
+        raise ValueError(f"slice_events = {m}: a slice has at least one event")
+    if not (np.isfinite(omega_max) and omega_max > 0.0):
+        raise ValueError("omega_max must be finite and positive")
+    if m > CMAX_MAX_RANGE:
+        raise ValueError(f"slice_events = {m}: the 32-bit cells of the image count at most {CMAX_MAX_RANGE} events exactly")
+    t = np.asarray(events.t_ns, dtype=np.int64)
+    ns = t.size // m
+    out = dict(omega=np.zeros((ns, 3)), t_ref_ns=np.zeros(ns + 1 if ns else 0, np.int64), J0=np.zeros(ns, np.uint64), J=np.zeros(ns, np.uint64),
+               evals=np.zeros(ns, np.int32))
+    if not ns:
+        return out
+    pin = cmax_pinhole_fit(lut, sensor_w, sensor_h)
+    out["t_ref_ns"][:ns], out["t_ref_ns"][ns] = t[0:ns * m:m], t[ns * m - 1]
+    for s in range(ns):
+        beg, end = s * m, (s + 1) * m
+        J_of = lambda w: cmax_objective(events, lut, sensor_w, sensor_h, w, beg, end, want_iwe=False, pinhole=pin)[0]
+        if t[end - 1] == t[beg]:
+            w, J0, evals = [0.0, 0.0, 0.0], int(J_of(np.zeros((1, 3)))[0]), 1
+            J = J0
+        else:
+            w, J0, J, evals = cmax_search(J_of, omega_max)
+        out["omega"][s], out["J0"][s], out["J"][s], out["evals"][s] = w, J0, J, evals
+    return out
+
+
+def integrate_angular_velocity(omega, t_ref_ns, t_query_ns=None):
+    """The rotation that per-slice angular velocities describe: q_0 = identity, q_{s+1} = q_s * exp(omega_s (t_ref(s+1) - t_ref(s))) (so3.exp; body frame,
+    the convention of warpEventToMap's R * bearing), t_ref_ns [n_slices + 1] as estimate_angular_velocity returns it — the last interval ends at the last
+    estimated event and uses the last omega.  Returns (pose_t [n_slices + 1] seconds, pose_q [n_slices + 1, 4] xyzw): what load_poses returns, what
+    generate_ctrl_poses_long consumes.  With t_query_ns: (t seconds, q) at those times instead, slice s = the last one beginning at or before t (the first /
+    last slice's velocity outside the estimated span)."""
+    omega = np.asarray(omega, dtype=np.float64).reshape(-1, 3)
+    t_ref = np.asarray(t_ref_ns, dtype=np.int64)
+    ns = omega.shape[0]
+    if ns == 0:
+        raise ValueError("no slice was estimated")
+    if t_ref.size != ns + 1:
+        raise ValueError(f"{ns} slices need {ns + 1} reference times, not {t_ref.size}")
+    q = np.zeros((ns + 1, 4))
+    q[0] = (0.0, 0.0, 0.0, 1.0)
+    for s in range(ns):
+        q[s + 1] = so3.mul(q[s], so3.exp(omega[s] * (float(t_ref[s + 1] - t_ref[s]) * 1e-9)))
+    if t_query_ns is None:
+        return t_ref * 1e-9, q
+    tq = np.asarray(t_query_ns, dtype=np.int64)
+    sl = np.clip(np.searchsorted(t_ref[:ns], tq, side="right") - 1, 0, ns - 1)
+    return tq * 1e-9, np.array([so3.mul(q[s], so3.exp(omega[s] * (float(tk - t_ref[s]) * 1e-9))) for s, tk in zip(sl, tq)]).reshape(-1, 4)

@@ -89,6 +89,7 @@ class LEGM:
         if st != _lib.OK:
             self._ctx = C.c_void_p()
             raise EmbaError(st, self._L.emba_last_error(None).decode())
+        self.bearing_lut = lut                           # (host copy: the numpy forms of emba_amd.io that need the camera, e.g. cmax_objective)
         self.stream = int(stream) if stream else None   # the caller's HIP stream (None: the library made its own)
         self.n_events = 0
         self.K = 0
@@ -211,6 +212,37 @@ class LEGM:
         mask = np.zeros(self.sensor_w * self.sensor_h, np.uint8)
         self._check(self._L.emba_seq_hot_pixels(self._ctx, _p(mask, _u8p)))
         return mask
+
+    def estimate_angular_velocity(self, slice_events, omega_max):
+        """The angular velocity of every slice of slice_events events of the resident sequence by contrast maximisation, one launch (emba_seq_cmax; the
+        rule: include/emba_hip.h).  Returns what io.estimate_angular_velocity returns, bit for bit: a dict of omega float64 [n_slices, 3], t_ref_ns int64
+        [n_slices + 1] (empty where n_slices = 0), J0, J uint64 [n_slices], evals int32 [n_slices]."""
+        u64p = C.POINTER(C.c_uint64)
+        n = C.c_size_t(0)
+        self._check(self._L.emba_seq_cmax(self._ctx, int(slice_events), float(omega_max), None, None, None, None, None, 0, C.byref(n)))
+        ns = n.value
+        out = dict(omega=np.zeros((ns, 3)), t_ref_ns=np.zeros(ns + 1 if ns else 0, np.int64), J0=np.zeros(ns, np.uint64), J=np.zeros(ns, np.uint64),
+                   evals=np.zeros(ns, np.int32))
+        if ns:
+            self._check(self._L.emba_seq_cmax(self._ctx, int(slice_events), float(omega_max), _p(out["omega"], _dp), _p(out["t_ref_ns"], _i64p), _p(out["J0"], u64p),
+                                              _p(out["J"], u64p), _p(out["evals"], _i32p), ns, C.byref(n)))
+        return out
+
+    def cmax_grid(self):
+        """(shift, grid_w, grid_h) of the image of warped events on this sensor (io.cmax_grid)."""
+        gw, gh, sh = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._L.emba_seq_cmax_objective(self._ctx, 0, 0, None, 0, None, None, C.byref(gw), C.byref(gh), C.byref(sh)))
+        return sh.value, gw.value, gh.value
+
+    def cmax_objective(self, omega, beg, end, want_iwe=True):
+        """J of every candidate of omega [M, 3] over the events [beg, end) of the resident sequence, and their images of warped events
+        (emba_seq_cmax_objective): (J uint64 [M], iwe uint32 [M, grid_h, grid_w] or None) — io.cmax_objective, bit for bit."""
+        w = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1, 3)
+        _, gw, gh = self.cmax_grid()
+        J = np.zeros(w.shape[0], np.uint64)
+        iwe = np.zeros((w.shape[0], gh, gw), np.uint32) if want_iwe else None
+        self._check(self._L.emba_seq_cmax_objective(self._ctx, int(beg), int(end), _p(w, _dp), w.shape[0], _p(J, C.POINTER(C.c_uint64)), _p(iwe, _u32p), None, None, None))
+        return J, iwe
 
     def free_sequence(self):
         self._check(self._L.emba_seq_free(self._ctx))

@@ -157,6 +157,11 @@ class ShardedLEGM:
     def sequence_hot_pixels(self):
         return self.engine.sequence_hot_pixels()
 
+    def estimate_angular_velocity(self, slice_events, omega_max):
+        """emba_seq_cmax on this rank's copy — a deterministic rule in integer arithmetic on equal copies: the same estimate on every rank, no collective
+        (slices over the ranks: not yet)."""
+        return self.engine.estimate_angular_velocity(slice_events, omega_max)
+
     def median_blur_map(self):
         self.engine.median_blur_map()
 
@@ -387,6 +392,8 @@ class ShardedModel:
         self.cost = ("quadratic", 0.0)
         self._thres = None
         self.H, self.W = legm.H, legm.W
+        # the camera, where the rank's model knows it: what driver.estimate_raw_poses needs over an engine without a resident sequence (numpy path)
+        self.bearing_lut, self.sensor_w, self.sensor_h = getattr(legm, "bearing_lut", None), getattr(legm, "sensor_w", None), getattr(legm, "sensor_h", None)
 
     def set_events(self, events):
         self.sh.set_events(events)
@@ -407,6 +414,9 @@ class ShardedModel:
 
     def sequence_hot_pixels(self):
         return self.sh.sequence_hot_pixels()
+
+    def estimate_angular_velocity(self, slice_events, omega_max):
+        return self.sh.estimate_angular_velocity(slice_events, omega_max)
 
     def median_blur_map(self):
         self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
@@ -534,6 +544,9 @@ class HipEngine:
 
     def sequence_hot_pixels(self):
         return self.m.sequence_hot_pixels()
+
+    def estimate_angular_velocity(self, slice_events, omega_max):
+        return self.m.estimate_angular_velocity(slice_events, omega_max)
 
     def median_blur_map(self):
         self.m.median_blur_map()

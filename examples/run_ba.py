@@ -6,6 +6,8 @@
   python examples/run_ba.py --demo out/ --window-size 0.3 --window-stride 0.1   # the same in sliding time windows (EMBA::Run, emba.cpp:400-532)
   python examples/run_ba.py --events ev.npz --poses init_traj.txt --map-dir init_map/ --calib calib.npz --out out/
   python examples/run_ba.py --demo out/ --init-map events     # no front-end map: start from a zero map, solved for the map alone first
+  python examples/run_ba.py --demo out/ --init-poses events --init-map events --window-size 0.3 --window-stride 0.1   # no front end at all: the raw poses
+                                                  # come from the events by contrast maximisation on the device; --events E --calib C likewise
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
@@ -61,6 +63,10 @@ def main():
     ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
     ap.add_argument("--init-map", default="given", choices=["given", "events"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
                     "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size")
+    ap.add_argument("--init-poses", default="given", choices=["given", "events"], help="events: no --poses is needed — the angular velocity of every slice of events is "
+                    "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
+    ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
+    ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
@@ -69,6 +75,10 @@ def main():
         a.alpha = 0.0 if a.demo else 5.0
     if not a.demo and a.init_map == "given" and not a.map_dir:
         ap.error("--map-dir is required unless --init-map events is given")
+    if not a.demo and a.init_poses == "given" and not a.poses:
+        ap.error("--poses is required unless --init-poses events is given")
+    if a.init_poses == "events" and not a.window_size:
+        ap.error("--init-poses events needs --window-size (the estimate runs on the resident sequence of a sliding-window run)")
     os.makedirs(a.out, exist_ok=True)
 
     if a.demo:
@@ -88,13 +98,27 @@ def main():
         sw, sh = int(cal["width"]), int(cal["height"])
         lut = eio.bearing_lut_from_calibration(cal["K"], cal["D"], sw, sh)
         Gx, Gy = eio.load_map(a.map_dir) if a.init_map == "given" else (np.zeros((a.pano_h, 2 * a.pano_h)), np.zeros((a.pano_h, 2 * a.pano_h)))
-        t, qs = eio.load_poses(a.poses)
+        if a.init_poses == "events":
+            # no front end: the span is the recording's, and the trajectory below only carries the timing (run_sequence makes the poses)
+            whole = eio.load_events(a.events)
+            t, qs = np.array([whole.t_ns[0] * 1e-9, whole.t_ns[-1] * 1e-9]), None
+        else:
+            t, qs = eio.load_poses(a.poses)
         t_beg = a.t_beg if a.t_beg is not None else t[0]
         t_end = a.t_end if a.t_end is not None else t[-1]
         num_cps = int(round((t_end - t_beg) / a.dt_knots)) + 1                      # trajectory.cpp:231-245
         sel = (t >= t_beg) & (t <= t_end)
-        traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, eio.fit_ctrl_poses(t[sel], qs[sel], t_beg, a.dt_knots, num_cps))
-        events = eio.load_events(a.events, int(t_beg * 1e9), traj.t0_ns + traj.dt_ns * (num_cps - 1) - 1)
+        if a.init_poses == "events":
+            num_cps = int(np.floor((t_end - t_beg) / a.dt_knots)) + 1               # whole knot intervals inside the recording
+            traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, np.tile([0.0, 0.0, 0.0, 1.0], (num_cps, 1)))
+        else:
+            traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, eio.fit_ctrl_poses(t[sel], qs[sel], t_beg, a.dt_knots, num_cps))
+        ev_lo, ev_hi = int(t_beg * 1e9), traj.t0_ns + traj.dt_ns * (num_cps - 1) - 1
+        if a.init_poses == "events":                                               # (the file was read above: cut the same span from it)
+            keep = (whole.t_ns >= ev_lo) & (whole.t_ns <= ev_hi)
+            events = type(whole)(whole.x[keep], whole.y[keep], whole.polarity[keep], whole.t_ns[keep])
+        else:
+            events = eio.load_events(a.events, ev_lo, ev_hi)
         t_end = t_beg + a.dt_knots * (num_cps - 1)
         truth, C_th = None, a.C_th
 
@@ -134,12 +158,21 @@ def main():
         from emba_amd.driver import SequenceSettings, run_sequence
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
                                event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
-                               hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time)
-        sres = run_sequence(model, events, t, qs, *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
+                               hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
+                               init_poses=a.init_poses, cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max)
+        sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
             fs = [int(v) for v in sres.filter_stats]
             print(f"noise filters: {fs[0]} events in, {fs[1]} hot pixels ({fs[2]} events), {fs[3]} inside the refractory period, {fs[4]} without support, {fs[5]} kept")
+        if rank == 0 and sres.cmax is not None:
+            cm = sres.cmax
+            print(f"contrast maximisation: {len(cm['omega'])} slices of {a.cmax_slice_events} events, {int(cm['evals'].sum())} evaluations, "
+                  f"median |omega| {np.median(np.linalg.norm(cm['omega'], axis=1)):.3f} rad/s")
+            if truth is not None:
+                # the initial trajectory of the comparison at the end: the integrated estimate at the control poses' times
+                tq = truth.t0_ns + truth.dt_ns * np.arange(truth.size(), dtype=np.int64)
+                traj = LinearTrajectory(eio.integrate_angular_velocity(cm["omega"], cm["t_ref_ns"], tq)[1], truth.t0_ns, truth.dt_ns)
         if rank == 0:
             for wr in sres.windows:
                 if wr.map_init is not None:
@@ -171,7 +204,9 @@ def main():
         return
     print(f"{res.iterations} LM iterations in {dt * 1e3:.1f} ms ({'converged' if res.converged else 'stopped'}), cost {res.cost_min:.6e}")
     if truth is not None:
-        err = lambda tr: np.degrees(np.mean([np.linalg.norm(so3.log(so3.mul(so3.inverse(p), q))) for p, q in zip(tr.knots_xyzw, truth.knots_xyzw)]))
+        # (a run from the events alone starts at the identity, wherever the camera pointed: rotations relative to the first control pose are compared then)
+        rel = (lambda k: np.array([so3.mul(so3.inverse(k[0]), q) for q in k])) if a.init_poses == "events" else (lambda k: k)
+        err = lambda tr: np.degrees(np.mean([np.linalg.norm(so3.log(so3.mul(so3.inverse(p), q))) for p, q in zip(rel(tr.knots_xyzw), rel(truth.knots_xyzw))]))
         print(f"mean control-pose error vs ground truth: {err(traj):.4f} deg -> {err(res.traj):.4f} deg")
     eio.write_trajectory(os.path.join(a.out, "refined_traj.txt"), res.traj)
     eio.save_map(a.out, *model.downloadMap())

@@ -323,6 +323,40 @@ emba_status emba_seq_filter(emba_ctx* ctx, double hot_sigma, int64_t refractory_
 /* The hot pixels of the last emba_seq_filter on this context: sensor_w * sensor_h bytes, 1 = hot (all 0 where hot_sigma was off).  EMBA_ERR_STATE before any. */
 emba_status emba_seq_hot_pixels(emba_ctx* ctx, uint8_t* mask_host);
 
+/* ---- Angular velocity from the events alone: contrast maximisation (Gallego & Scaramuzza, RA-L 2017; no counterpart in the reference, which takes its raw
+ * poses from a front end) on the resident sequence as it stands (after any filter and down-sampling), n events.  For every slice of m = slice_events events,
+ * slice s = [s m, (s + 1) m), s < n_slices = n / m (the tail behind the last whole slice is not estimated), t_ref(s) = t[s m], the angular velocity w whose
+ * image of warped events is sharpest.  The objective is exact integer arithmetic, so emba_amd.io.cmax_objective / estimate_angular_velocity (numpy) give the
+ * same numbers bit for bit and the search takes the same decisions.  All floating point below: IEEE double, one rounding per operation (no fused
+ * multiply-add), in the order written.
+ *   warp of event k   dt = double(t[k] - t_ref) * 1e-9, a = w * (dt * 0.5), b = bearing_lut[y[k] * sensor_w + x[k]],
+ *                     aa = (ax ax + ay ay) + az az, c = a x b, d = a x c (cx = ay bz - az by, ...), b' = (1 + aa) * b + 2 * (c + d): the unnormalised Cayley
+ *                     rotation of b about w, by 2 atan(|w| dt / 2) rather than |w| dt (relative difference (|w| dt)^2 / 12: DESIGN.md §11).
+ *   image plane       an ideal pinhole fitted to the LUT alone: u = f * (b'x / b'z) + cu, v = f * (b'y / b'z) + cv; f, cu, cv by least squares over the
+ *                     LUT's centre row and centre column (the formula: emba_amd/csrc/cmax_rule.h, cmax_pinhole_fit).  b'z <= 0 votes nowhere.
+ *   votes             cells of 2^shift sensor pixels, shift the smallest for which ceil(w / 2^shift) x ceil(h / 2^shift) uint32 cells fit 64 KiB (240x180:
+ *                     shift 1, 120x90; 64x48: shift 0).  g = u / 2^shift (v likewise), i = floor(g), wx = floor((gx - ix) * 16), wy likewise; the cells
+ *                     (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) get (16 - wx)(16 - wy), wx (16 - wy), (16 - wx) wy, wx wy — 256 in all; a vote
+ *                     whose cell lies outside the grid is dropped.
+ *   objective         J(w) = sum over the cells of I^2, uint64, exact for fewer than 2^24 events.
+ *   search            per slice, from w = 0, step = omega_max / 2: an iteration evaluates w +- step e_i in the order +x -x +y -y +z -z and moves to the best of
+ *                     the six (ties: the earlier) iff its J is strictly greater than the centre's, else halves the step; it ends when step < omega_max 2^-12
+ *                     or after 64 iterations.  A slice whose first and last timestamps are equal gets w = 0 after the one evaluation of J(0).
+ * emba_seq_cmax: one workgroup per slice, the whole search inside one launch (emba_amd/csrc/cmax_kernels.h).  Per slice: omega_out [3] (rad/s, body frame: the
+ * pose of event k is R(t_ref) exp(w (t[k] - t_ref)), the convention of warpEventToMap's R * bearing), j0_out = J(0), j_out = J(w), evals_out = evaluations of J
+ * (1 + 6 per iteration); t_ref_ns_out: t_ref of every slice and, behind them, the timestamp of the last estimated event — cap_slices + 1 entries, the other
+ * arrays cap_slices (3 cap_slices doubles for omega_out).  Any of the arrays may be NULL; *n_slices (may be NULL) is always set, and with every array NULL
+ * nothing is launched.  EMBA_ERR_STATE: no sequence resident, or the LUT admits no pinhole fit.  EMBA_ERR_INVALID_ARG: slice_events < 1 or >= 2^24, omega_max
+ * not finite and positive.  EMBA_ERR_CAPACITY: cap_slices < n_slices.  n_slices = 0 (fewer events than one slice) is EMBA_OK.  Timings: DESIGN.md §11. */
+emba_status emba_seq_cmax(emba_ctx* ctx, int64_t slice_events, double omega_max, double* omega_out, int64_t* t_ref_ns_out, uint64_t* j0_out, uint64_t* j_out,
+                          int32_t* evals_out, size_t cap_slices, size_t* n_slices);
+/* The objective alone, for M given candidates omega [M, 3] over the events [beg, end) of the resident sequence, t_ref = t[beg] (tests, diagnostics; one
+ * workgroup per candidate): j_out [M] and, where iwe_out is not NULL, the images of warped events [M, grid_h, grid_w] (uint32, row-major).  *grid_w, *grid_h,
+ * *shift (each may be NULL) are always set, and with M = 0 or both outputs NULL nothing else happens — the grid of a context needs no sequence.  An empty range:
+ * J = 0, an empty image.  EMBA_ERR_STATE: no sequence resident.  EMBA_ERR_INVALID_ARG: not beg <= end <= n, 2^24 events or more, omega NULL or not finite. */
+emba_status emba_seq_cmax_objective(emba_ctx* ctx, size_t beg, size_t end, const double* omega, size_t M, uint64_t* j_out, uint32_t* iwe_out, int32_t* grid_w,
+                                    int32_t* grid_h, int32_t* shift);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
