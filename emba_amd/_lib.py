@@ -103,6 +103,8 @@ SIGNATURES = {
     "emba_seq_hot_pixels": (C.c_int, [C.c_void_p, _u8p]),
     "emba_seq_cmax": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, _dp, _i64p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i32p, C.c_size_t, _szp]),
     "emba_seq_cmax_objective": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _dp, C.c_size_t, C.POINTER(C.c_uint64), _u32p, _i32p, _i32p, _i32p]),
+    "emba_seq_event_panorama": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _i32p, C.POINTER(C.c_uint64), _i64p,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, solve_host.h,
-// sequence_host.h, cmax_host.h, group.h); host code only.
+// sequence_host.h, cmax_host.h, panorama_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -210,6 +210,11 @@ struct SolveCache {
 // candidates of emba_seq_cmax_objective with their J and their images.
 struct CmaxBuffers { DevBuf omega, t_ref, j0, j, evals, cand, cand_j, cand_iwe; };
 
+// Grow-only buffers of the panorama of warped events (panorama_host.h): the int32 image [H, W]; the midpoints and the pose table of the range's batches and
+// the control poses they were evaluated from (the call's own: the registered window's are left alone); one slot per wave of the reduction; out: J, sum,
+// non-zero cells, dropped votes and the pose stage's status word; pm: the projected events, where asked for.
+struct PanoBuffers { DevBuf image, batch_t, pose, knots, slots, out, pm; };
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -375,6 +380,7 @@ struct emba_ctx {
     // and their images.
     emba::CmaxPinhole cmax_pin;
     CmaxBuffers cmax;
+    PanoBuffers pano;             // the panorama of warped events on that sequence (panorama_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -961,6 +961,7 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
 
 #include "sequence_host.h"   // the resident event sequence of a sliding-window run: upload, windows, time shards and their halos, noise filters
 #include "cmax_host.h"       // contrast maximisation on it: the angular velocity of every slice of events, from the events alone
+#include "panorama_host.h"   // the panorama of warped events along a trajectory, and its contrast
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

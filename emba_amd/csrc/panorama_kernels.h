@@ -1,0 +1,106 @@
+// emba_amd/csrc/panorama_kernels.h — the panorama of warped events along a trajectory (gfx950, wave64): every event of a range of the resident sequence
+// warped through the linear SO(3) spline onto the equirectangular panorama, bilinear votes with exact integer weights, the image reduced to its contrast.
+// The rule: panorama_rule.h, include/emba_hip.h (emba_seq_event_panorama), DESIGN.md §12.  Three stages on one stream:
+//   * pose stage                    the batches' midpoints and rotations: emba_batch_mid_kernel (order_kernels.h) and emba_pose_kernel (kernels.h) as they
+//                                   are, on the range's own batches and into the panorama's own tables — the registered window's are not touched
+//   * emba_pano_vote_kernel         one lane per event: bearing, batch pose, pm by the evaluation path's own device_math.h functions, pano_vote, up to four
+//                                   return-less int32 atomic adds into the image in HBM
+//   * emba_pano_reduce_kernel,      J = sum I^2, sum I and the non-zero cells over the H W cells: per thread -> wave shuffle -> one slot per wave, then one
+//     emba_pano_reduce_final_kernel wave adds the slots in a fixed order
+// The atomics execute at the memory side (MI355X_MICROARCH.md, global atomics): an add leaves the XCD's L2 as an uncached 64-B request and nothing of the
+// image stays there, so neither the block shape nor the placement of the workgroups changes what an add costs, and events in time order are neighbours on
+// the panorama only as far as the scene makes them.  Plain 256-thread workgroups, one lane per event; measured, the kernel runs at the rate of those
+// requests (23 adds per ns at 1 M events) — what an LDS-tiled form would have to beat by merging votes before they leave the chip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "device_math.h"
+#include "kernels.h"      // kPoseStride, emba_pose_kernel
+#include "panorama_rule.h"
+
+namespace emba {
+
+constexpr int kPanoThreads = 256;
+constexpr int kPanoReduceBlocks = 256;                                   // at the most: one round over the compute units
+constexpr int kPanoReduceSlots = kPanoReduceBlocks * (kPanoThreads / 64);   // one per wave
+constexpr int kPanoSums = 3;                                             // per slot: J, sum (two's complement), non-zero cells
+
+struct PanoParams {
+    const uint16_t* x; const uint16_t* y; const uint8_t* pol;   // the resident sequence, from the range's first event
+    const double* lut;                                          // bearing vector per sensor pixel [S, 3]
+    const double* pose;                                         // pose table of the range's batches (kPoseStride doubles each; [0..3]: the quaternion)
+    long nn;                                                    // events used: whole batches
+    int sw, W, H;
+    double fx, fy, cx, cy;                                      // the equirectangular camera of the context
+    int signed_polarity;
+    int32_t* image;                                             // [H, W], zeroed on the stream in front of this launch
+    unsigned long long* dropped;                                // votes whose row lies outside the panorama (zeroed likewise)
+    double* pm_out;                                             // [nn, 2] or nullptr
+};
+
+// Event k of the range: pm = project(R(batch k / 100) * bearing) — quat_to_matrix, the three products and two sums of the warp kernels (kernels.h) and
+// project_chain, all of it compiled without contraction like everything that feeds an integer (device_math.h) — then pano_vote.
+#pragma clang fp contract(off)
+__global__ __launch_bounds__(kPanoThreads) void emba_pano_vote_kernel(PanoParams p)
+{
+    const long k = (long)blockIdx.x * kPanoThreads + threadIdx.x;
+    unsigned int lost = 0;
+    if (k < p.nn) {
+        const double* P = p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch);
+        const double q[4] = {P[0], P[1], P[2], P[3]};
+        double R[9];
+        quat_to_matrix(q, R);
+        const double* bv = p.lut + 3 * ((size_t)p.y[k] * (size_t)p.sw + (size_t)p.x[k]);      // (every event was checked at its upload: inside the LUT)
+        const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
+        double rb[3], pm[2], J23[6];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
+        project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);      // (the Jacobian is dead code here)
+        if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
+        const PanoVotes v = pano_vote(pm[0], pm[1], p.W, p.H);
+        const bool neg = p.signed_polarity && p.pol[k] == 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (!v.w[i]) continue;
+            if (v.cell[i] < 0) { ++lost; continue; }
+            atomicAdd(p.image + v.cell[i], neg ? -v.w[i] : v.w[i]);      // (the result is not used: a return-less global_atomic_add)
+        }
+    }
+    // the dropped votes of the wave in one add (every lane of the workgroup arrives here)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
+    if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
+}
+#pragma clang fp contract(fast)
+
+// Slot (blockIdx.x, wave) <- {sum I^2, sum I, cells != 0} over the cells the wave's lanes stride over.  Integers: every order gives the same sums; the order
+// is fixed all the same (a grid-stride sweep, the butterfly, then the final kernel's), like the reduction of cmax_kernels.h.
+__global__ __launch_bounds__(kPanoThreads) void emba_pano_reduce_kernel(const int32_t* __restrict__ image, long cells, unsigned long long* __restrict__ slots)
+{
+    unsigned long long j = 0, s = 0, nz = 0;
+    for (long i = (long)blockIdx.x * kPanoThreads + threadIdx.x; i < cells; i += (long)gridDim.x * kPanoThreads) {
+        const long long I = image[i];
+        j += (unsigned long long)(I * I);
+        s += (unsigned long long)I;
+        nz += I != 0;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { j += __shfl_xor(j, o); s += __shfl_xor(s, o); nz += __shfl_xor(nz, o); }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* o = slots + (size_t)kPanoSums * ((size_t)blockIdx.x * (kPanoThreads / 64) + (threadIdx.x >> 6));
+        o[0] = j; o[1] = s; o[2] = nz;
+    }
+}
+
+// One wave: lane l adds the slots l, l + 64, ... in that order, the butterfly adds the lanes.  out[0..2] = J, sum, non-zero cells.
+__global__ __launch_bounds__(64) void emba_pano_reduce_final_kernel(const unsigned long long* __restrict__ slots, int n_slots, unsigned long long* __restrict__ out)
+{
+    unsigned long long j = 0, s = 0, nz = 0;
+    for (int i = threadIdx.x; i < n_slots; i += 64) { j += slots[kPanoSums * i]; s += slots[kPanoSums * i + 1]; nz += slots[kPanoSums * i + 2]; }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { j += __shfl_xor(j, o); s += __shfl_xor(s, o); nz += __shfl_xor(nz, o); }
+    if (threadIdx.x == 0) { out[0] = j; out[1] = s; out[2] = nz; }
+}
+
+}  // namespace emba

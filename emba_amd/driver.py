@@ -44,6 +44,11 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     init_poses: str = "given"
     cmax_slice_events: int = 10000
     cmax_omega_max: float = 8.0
+    # The panorama of warped events (no counterpart in the reference's back end; the rule: include/emba_hip.h, emba_seq_event_panorama), on the
+    # device where the sequence is resident (LEGM.event_panorama), else by io.event_panorama.  Both off by default.
+    record_contrast: bool = False   # WindowResult.contrast_init / contrast_final: J, sum, nonzero of the window's events at the segment handed to
+                                    # solve_time_window and at the refined one — comparable between trajectories on the same events, which the LM cost is not
+    event_panorama: bool = False    # SequenceResult.event_panorama: the image of the events the final trajectory spans, at that trajectory
 
     def __post_init__(self):
         if self.init_poses not in ("given", "events"):
@@ -66,6 +71,8 @@ class WindowResult:
     result: object              # its LMResult
     setup_ms: float = float("nan")  # emba_last_setup_ms of the window's registration (device models)
     map_init: object = None     # SequenceSettings.init_map = "events", first window only: the LMResult of the map-only pass that preceded `result`
+    contrast_init: object = None    # SequenceSettings.record_contrast: {"J", "sum", "nonzero"} of the panorama of the window's events [beg, end) at traj_init
+    contrast_final: object = None   # ... and at result.traj
 
 
 @dataclass
@@ -76,6 +83,7 @@ class SequenceResult:
     filter_stats: object = None # with a noise filter on: uint64[6] — events in, hot pixels, events failing hot / refractory / support, events kept
     cmax: object = None         # SequenceSettings.init_poses = "events": what estimate_angular_velocity returned (omega, t_ref_ns, J0, J, evals) + the raw
                                 # poses made of it (pose_t, pose_q)
+    event_panorama: object = None   # SequenceSettings.event_panorama: int64 [H, W], the panorama of the events [windows[0].beg, windows[-1].end) warped along traj
 
 
 def keeps_sequence(model):
@@ -103,6 +111,21 @@ def estimate_raw_poses(model, events, seq, resident_sequence):
     t0, t1, step = emba_io.ros_time_ns(seq.t_start), emba_io.ros_time_ns(seq.t_end), max(int(1e9 * seq.dt_knots) // 10, 1)
     pose_t, pose_q = emba_io.integrate_angular_velocity(est["omega"], est["t_ref_ns"], np.arange(t0, t1 + step, step, dtype=np.int64))
     return dict(est, pose_t=pose_t, pose_q=pose_q)
+
+
+def panorama_of_events(model, events, traj, beg, end, resident_sequence, want_image=False):
+    """The panorama of warped events of [beg, end) of the run's (down-sampled) sequence along traj, as LEGM.event_panorama returns it: from the model's device
+    where the sequence is resident there, else by io.event_panorama on `events` with the camera and the panorama size the model knows."""
+    if resident_sequence and hasattr(model, "event_panorama"):
+        return model.event_panorama(traj, beg, end, want_image=want_image)
+    lut, sw, sh = getattr(model, "bearing_lut", None), getattr(model, "sensor_w", None), getattr(model, "sensor_h", None)
+    if lut is None or not sw or not sh:
+        raise ValueError("the panorama of warped events without a resident sequence needs the camera: model.bearing_lut, model.sensor_w, model.sensor_h")
+    return emba_io.event_panorama(events, lut, sw, sh, model.W, model.H, traj, beg, end)
+
+
+def _contrast(r):
+    return {k: r[k] for k in ("J", "sum", "nonzero")}
 
 
 def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm=LMSettings(), runtime_log=None, map_recorder=None, resident=True,
@@ -214,9 +237,13 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
             Gx = Gy = None
         res = solve_time_window(model, seg, ev_win, Gx, Gy, ba_win, lm, verbose=verbose, resident=resident, runtime_log=runtime_log, map_recorder=map_recorder)
         Gx = Gy = None
+        c_init = c_final = None
+        if seq.record_contrast:      # (after the solve: the calls leave the registered window and the evaluation alone, and need neither)
+            c_init = _contrast(panorama_of_events(model, events, seg, beg, end, resident_sequence))
+            c_final = _contrast(panorama_of_events(model, events, res.traj, beg, end, resident_sequence))
         knots[idx_cp_beg:] = res.traj.knots_xyzw                                        # :453 replaceWith
         setup_ms = model.setup_info()["set_events_ms"] if hasattr(model, "setup_info") else float("nan")
-        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init))
+        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init, c_init, c_final))
         # :459-460 the latest pose: the whole trajectory 1 us before the window's end
         pose_latest = so3.spline_evaluate(knots, traj_t0_ns, traj_dt_ns, t_win_end - 1000)
         # :512-532 slideWindow
@@ -227,4 +254,6 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         count_window += 1
         first_time_window = False
     out.traj = LinearTrajectory(knots, traj_t0_ns, traj_dt_ns)
+    if seq.event_panorama and out.windows:
+        out.event_panorama = panorama_of_events(model, events, out.traj, out.windows[0].beg, out.windows[-1].end, resident_sequence, want_image=True)["image"]
     return out

@@ -542,3 +542,96 @@ def integrate_angular_velocity(omega, t_ref_ns, t_query_ns=None):
     tq = np.asarray(t_query_ns, dtype=np.int64)
     sl = np.clip(np.searchsorted(t_ref[:ns], tq, side="right") - 1, 0, ns - 1)
     return tq * 1e-9, np.array([so3.mul(q[s], so3.exp(omega[s] * (float(tk - t_ref[s]) * 1e-9))) for s, tk in zip(sl, tq)]).reshape(-1, 4)
+
+
+# ---- the panorama of warped events along a trajectory and its contrast (numpy form of emba_seq_event_panorama, include/emba_hip.h; the device form is
+# LEGM.event_panorama).  The votes are emba_amd/csrc/panorama_rule.h's pano_vote, operation for operation: given the same pm both forms give the same integers.
+PANO_BATCH = 100                         # kPanoBatch: events per pose (model.cpp:100-119)
+PANO_MAX_EVENTS = 1 << 23                # kPanoMaxEvents: a range of this many used events or more is refused
+
+
+def pano_votes(pm, pano_w, pano_h):
+    """pano_vote (panorama_rule.h) of every row of pm [n, 2]: (cell int64 [n, 4], weight int64 [n, 4]) for the cells (ix, iy), (ix + 1, iy), (ix, iy + 1),
+    (ix + 1, iy + 1) — cell = row * pano_w + column with the column wrapped modulo pano_w, -1 where the row lies outside [0, pano_h); a pm that is not
+    finite (or |pm| >= 2^31) has every cell -1 and every weight 0."""
+    W, H = int(pano_w), int(pano_h)
+    pm = np.asarray(pm, dtype=np.float64).reshape(-1, 2)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(pm[:, 0]) < 2147483648.0) & (np.abs(pm[:, 1]) < 2147483648.0)
+    x, y = np.where(ok, pm[:, 0], 0.0), np.where(ok, pm[:, 1], 0.0)
+    fx, fy = np.floor(x), np.floor(y)
+    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    wx, wy = ((x - fx) * 16.0).astype(np.int64), ((y - fy) * 16.0).astype(np.int64)
+    c0 = ix % W
+    c1 = np.where(c0 + 1 == W, 0, c0 + 1)
+    r0, r1 = (iy >= 0) & (iy < H) & ok, (iy + 1 >= 0) & (iy + 1 < H) & ok
+    cell = np.stack([np.where(r0, iy * W + c0, -1), np.where(r0, iy * W + c1, -1), np.where(r1, (iy + 1) * W + c0, -1), np.where(r1, (iy + 1) * W + c1, -1)], axis=1)
+    w = np.stack([(16 - wx) * (16 - wy), wx * (16 - wy), (16 - wx) * wy, wx * wy], axis=1) * ok[:, None]
+    return cell, w
+
+
+def event_panorama_pm(events, lut, sensor_w, sensor_h, pano_w, pano_h, traj, beg=0, end=None):
+    """pm [nn, 2] of the used events of events[beg:end] (whole batches of 100) along traj: batch b of the range takes the spline pose at its midpoint
+    (sharded.batch_mid_ns of its first and last timestamp, model.cpp:116-119; so3.spline_evaluate), pm = project(R * bearing) with the equirectangular
+    projection of synth.project_equirect.  numpy's sin / atan2 / asin are not the device's: close to emba_seq_event_panorama's pm_out, not bit-equal.
+    Raises ValueError where a midpoint lies outside the knots."""
+    from . import synth
+    from .sharded import batch_mid_ns
+    sw = int(sensor_w)
+    lut = np.asarray(lut, dtype=np.float64).reshape(sw * int(sensor_h), 3)
+    t = np.asarray(events.t_ns, dtype=np.int64)
+    end = t.size if end is None else int(end)
+    beg = int(beg)
+    if not 0 <= beg <= end <= t.size:
+        raise ValueError(f"[{beg}, {end}) is not a range of the sequence of {t.size} events")
+    nb = (end - beg) // PANO_BATCH
+    nn = nb * PANO_BATCH
+    p = np.asarray(events.y, dtype=np.int64)[beg:beg + nn] * sw + np.asarray(events.x, dtype=np.int64)[beg:beg + nn]
+    pm = np.zeros((nn, 2))
+    for b in range(nb):
+        k0 = beg + PANO_BATCH * b
+        q = so3.spline_evaluate(traj.knots_xyzw, traj.t0_ns, traj.dt_ns, batch_mid_ns(t[k0], t[k0 + PANO_BATCH - 1]))
+        rb = lut[p[PANO_BATCH * b:PANO_BATCH * (b + 1)]] @ synth._quat_to_R(q).T
+        pm[PANO_BATCH * b:PANO_BATCH * (b + 1), 0], pm[PANO_BATCH * b:PANO_BATCH * (b + 1), 1] = synth.project_equirect(int(pano_w), int(pano_h), rb)
+    return pm
+
+
+def event_panorama(events, lut, sensor_w, sensor_h, pano_w, pano_h, traj, beg=0, end=None, signed=False, pm=None):
+    """The panorama of warped events of events[beg:end] along the linear SO(3) spline traj, and its contrast: the rule of emba_seq_event_panorama
+    (include/emba_hip.h) in numpy.  Returns a dict: image int64 [pano_h, pano_w], J = sum I^2, sum = sum I, nonzero = cells != 0, dropped = votes (non-zero
+    weights) whose row lies outside the panorama — python ints — and pm float64 [nn, 2], nn = ((end - beg) // 100) * 100.
+    Given pm [nn, 2] (the device's pm_out, an oracle's) the integer rule is applied to it exactly: the same image, bit for bit, as the device makes of the
+    same pm.  Without pm it is computed here (event_panorama_pm): numpy's sin / atan2 / asin differ from the device's in the last bits, so that image is
+    close to the device's but not bit-equal (DESIGN.md §12 has the measured distance).  traj may be None where pm is given."""
+    W, H = int(pano_w), int(pano_h)
+    n = int(np.asarray(events.t_ns).size)
+    end = n if end is None else int(end)
+    beg = int(beg)
+    if not 0 <= beg <= end <= n:
+        raise ValueError(f"[{beg}, {end}) is not a range of the sequence of {n} events")
+    nn = ((end - beg) // PANO_BATCH) * PANO_BATCH
+    if nn >= PANO_MAX_EVENTS:
+        raise ValueError(f"[{beg}, {end}): the 32-bit cells of the image count fewer than {PANO_MAX_EVENTS} events exactly")
+    if pm is None:
+        if traj is None or traj.size() < 2 or int(traj.dt_ns) <= 0:
+            raise ValueError("event_panorama needs a trajectory of at least two control poses with a positive knot spacing, or pm")
+        pm = event_panorama_pm(events, lut, sensor_w, sensor_h, W, H, traj, beg, end)
+    pm = np.asarray(pm, dtype=np.float64).reshape(-1, 2)
+    if pm.shape[0] != nn:
+        raise ValueError(f"pm has {pm.shape[0]} rows, the range uses {nn} events")
+    cell, w = pano_votes(pm, W, H)
+    if signed:
+        w = np.where((np.asarray(events.polarity)[beg:beg + nn] == 0)[:, None], -w, w)
+    inside = cell >= 0
+    acc = np.bincount(cell[inside], weights=w[inside].astype(np.float64), minlength=W * H)      # (sums of integers below 2^31: exact in a double)
+    image = acc.astype(np.int64).reshape(H, W)
+    return dict(pano_contrast(image), image=image, dropped=int(np.count_nonzero(~inside & (w != 0))), pm=pm)
+
+
+def pano_contrast(image):
+    """J = sum I^2, sum = sum I, nonzero = cells != 0 of an image of warped events, as python ints.  With sum |I| < 2^31 (one call's image) every sum is
+    exact in int64; the sum of several calls' images may exceed that, and its squares are then added as python ints."""
+    image = np.asarray(image, dtype=np.int64)
+    nz = image[image != 0]
+    J = int((nz * nz).sum()) if int(np.abs(nz).sum()) < (1 << 31) else sum(int(v) * int(v) for v in nz.tolist())
+    return dict(J=J, sum=int(image.sum()), nonzero=int(nz.size))

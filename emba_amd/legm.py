@@ -244,6 +244,48 @@ class LEGM:
         self._check(self._L.emba_seq_cmax_objective(self._ctx, int(beg), int(end), _p(w, _dp), w.shape[0], _p(J, C.POINTER(C.c_uint64)), _p(iwe, _u32p), None, None, None))
         return J, iwe
 
+    def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False, _chunk_events=None):
+        """The panorama of warped events of [beg, end) of the resident sequence (end = None: its end) along the linear SO(3) spline traj, and its contrast
+        (emba_seq_event_panorama; the rule: include/emba_hip.h): a dict of image int64 [pano_h, pano_w] (None with want_image=False), J = sum I^2, sum = sum I,
+        nonzero = cells != 0, dropped = votes whose row lies outside the panorama (python ints) and pm float64 [nn, 2] (None without want_pm) —
+        io.event_panorama given the same pm, bit for bit.  signed: events of polarity 0 vote negative.
+        One library call counts fewer than 2^23 events exactly, so a longer range is cut here into chunks of whole batches (the batches, and so their
+        midpoints and poses, are those of the uncut range), the chunks' int32 images are summed in int64, and J, sum and nonzero are then RECOMPUTED from
+        that sum on the host (io.pano_contrast) — the chunks' own J do not add up to it; dropped and pm are the chunks' concatenated.  A range cut into
+        chunks therefore always downloads the image, whatever want_image says about returning it."""
+        from . import io as emba_io
+        u64 = C.POINTER(C.c_uint64)
+        knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
+        end = self.sequence_size() if end is None else int(end)
+        beg = int(beg)
+        chunk = int(_chunk_events) if _chunk_events else (emba_io.PANO_MAX_EVENTS - 1) // emba_io.PANO_BATCH * emba_io.PANO_BATCH      # (private: the tests force small chunks)
+        if chunk < emba_io.PANO_BATCH or chunk % emba_io.PANO_BATCH:
+            raise ValueError("a chunk is a positive number of whole batches")
+        nn = max(end - beg, 0) // emba_io.PANO_BATCH * emba_io.PANO_BATCH
+        cuts = [(beg, end)] if nn <= chunk else [(b, min(b + chunk, beg + nn)) for b in range(beg, beg + nn, chunk)]
+        single = len(cuts) == 1
+        total = None if single else np.zeros((self.H, self.W), np.int64)
+        pms, dropped, res = [], 0, None
+        for b, e in cuts:
+            m = max(e - b, 0) // emba_io.PANO_BATCH * emba_io.PANO_BATCH
+            img = np.empty((self.H, self.W), np.int32) if (want_image or not single) else None
+            pm = np.empty((m, 2)) if want_pm else None
+            J, sm, nz, dr = C.c_uint64(0), C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+            self._check(self._L.emba_seq_event_panorama(self._ctx, b, e, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns), 1 if signed else 0,
+                                                        _p(img, _i32p), C.byref(J), C.byref(sm), C.byref(nz), C.byref(dr), _p(pm, _dp)))
+            dropped += dr.value
+            if want_pm:
+                pms.append(pm)
+            if single:
+                res = dict(image=None if img is None else img.astype(np.int64), J=J.value, sum=sm.value, nonzero=nz.value)
+            else:
+                total += img
+        if not single:
+            res = dict(emba_io.pano_contrast(total), image=total if want_image else None)
+        res["dropped"] = dropped
+        res["pm"] = (pms[0] if single else np.concatenate(pms)) if want_pm else None
+        return res
+
     def free_sequence(self):
         self._check(self._L.emba_seq_free(self._ctx))
 

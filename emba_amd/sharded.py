@@ -162,6 +162,11 @@ class ShardedLEGM:
         (slices over the ranks: not yet)."""
         return self.engine.estimate_angular_velocity(slice_events, omega_max)
 
+    def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
+        """emba_seq_event_panorama on this rank's copy of the sequence — exact integer votes on equal copies: what rank 0's context answers is what every
+        rank's answers, so each asks its own and no collective is needed (the events of the range over the ranks: out of scope)."""
+        return self.engine.event_panorama(traj, beg, end, signed, want_image, want_pm)
+
     def median_blur_map(self):
         self.engine.median_blur_map()
 
@@ -418,6 +423,9 @@ class ShardedModel:
     def estimate_angular_velocity(self, slice_events, omega_max):
         return self.sh.estimate_angular_velocity(slice_events, omega_max)
 
+    def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
+        return self.sh.event_panorama(traj, beg, end, signed, want_image, want_pm)
+
     def median_blur_map(self):
         self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
 
@@ -547,6 +555,9 @@ class HipEngine:
 
     def estimate_angular_velocity(self, slice_events, omega_max):
         return self.m.estimate_angular_velocity(slice_events, omega_max)
+
+    def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
+        return self.m.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
     def median_blur_map(self):
         self.m.median_blur_map()

@@ -67,6 +67,9 @@ def main():
                     "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
+    ap.add_argument("--record-contrast", action="store_true", help="print, per window, the contrast J = sum I^2 of the panorama of the window's warped events at its "
+                    "initial and at its refined control poses (with --window-size; DESIGN.md section 12)")
+    ap.add_argument("--event-panorama", action="store_true", help="write <out>/event_panorama.png: the events warped along the final trajectory (with --window-size)")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
@@ -79,6 +82,8 @@ def main():
         ap.error("--poses is required unless --init-poses events is given")
     if a.init_poses == "events" and not a.window_size:
         ap.error("--init-poses events needs --window-size (the estimate runs on the resident sequence of a sliding-window run)")
+    if (a.record_contrast or a.event_panorama) and not a.window_size:
+        ap.error("--record-contrast / --event-panorama need --window-size (they run on the resident sequence of a sliding-window run)")
     os.makedirs(a.out, exist_ok=True)
 
     if a.demo:
@@ -159,7 +164,8 @@ def main():
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
                                event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
                                hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
-                               init_poses=a.init_poses, cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max)
+                               init_poses=a.init_poses, cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
+                               record_contrast=a.record_contrast, event_panorama=a.event_panorama)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
@@ -179,6 +185,11 @@ def main():
                     print(f"window {wr.index}: map-only start from a zero map, {wr.map_init.iterations} LM iterations ({wr.map_init.reason}), cost {wr.map_init.cost_min:.6e}")
                 print(f"window {wr.index}: [{wr.t_beg_ns * 1e-9:.3f}, {wr.t_end_ns * 1e-9:.3f}] s, events [{wr.beg}, {wr.end}), control poses from {wr.idx_cp_beg}, "
                       f"{wr.result.iterations} LM iterations ({wr.result.reason or 'converged'}), cost {wr.result.cost_min:.6e}, set-up {wr.setup_ms:.2f} ms")
+                if wr.contrast_init is not None:
+                    j0, j1 = wr.contrast_init["J"], wr.contrast_final["J"]
+                    print(f"window {wr.index}: contrast of the warped events J = {j0:.6e} -> {j1:.6e} (x {j1 / max(j0, 1):.4f})")
+            if sres.event_panorama is not None:
+                eio.save_png(os.path.join(a.out, "event_panorama.png"), eio.normalize_robust(sres.event_panorama.astype(np.float64), 0.1))
         res = sres.windows[-1].result
         res = type(res)(sres.traj, res.cost_min, sum(wr.result.iterations for wr in sres.windows), all(wr.result.converged for wr in sres.windows), res.log, res.reason)
         if truth is not None:

@@ -357,6 +357,30 @@ emba_status emba_seq_cmax(emba_ctx* ctx, int64_t slice_events, double omega_max,
 emba_status emba_seq_cmax_objective(emba_ctx* ctx, size_t beg, size_t end, const double* omega, size_t M, uint64_t* j_out, uint32_t* iwe_out, int32_t* grid_w,
                                     int32_t* grid_h, int32_t* shift);
 
+/* ---- The panorama of warped events along a trajectory, and its contrast (no map, no ground truth: "is this trajectory better than that one, on these
+ * events?") on [beg, end) of the resident sequence as it stands.  The trajectory is a linear SO(3) spline as emba_eval_launch takes it: K
+ * control poses knots_xyzw [K, 4], t0_ns, dt_ns.
+ *   batches           nn = ((end - beg) / 100) * 100 events are used, the tail is ignored (quirk Q1).  Batch b of the range is [beg + 100 b, beg + 100 b + 100);
+ *                     its pose is the spline at the batch's midpoint by the rule of model.cpp:116-119 — the integer midpoint emba_set_events_seq(beg, end)
+ *                     gives that range — so the image is what the bundle adjustment sees.
+ *   warp              pm = project(R(midpoint) * bearing_lut[y[k] * sensor_w + x[k]]): the spline evaluation and the equirectangular projection of the
+ *                     evaluation path (emba_amd/csrc/device_math.h), no second formulation.  A pm that is not finite votes nowhere.
+ *   votes             ix = floor(pm_x), wx = floor((pm_x - ix) * 16), iy, wy likewise; the cells (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) get
+ *                     (16 - wx)(16 - wy), wx (16 - wy), (16 - wx) wy, wx wy — 256 per event in all, the convention of the cmax grid.  Columns wrap modulo
+ *                     pano_w (azimuth is periodic).  A vote — a non-zero weight — whose row lies outside [0, pano_h) is dropped and counted in *dropped_out
+ *                     (votes, not events).  signed_polarity != 0: events with pol == 0 vote negative; == 0: every event votes positive.
+ *   image, contrast   cells are int32, pano_h x pano_w, row-major; J = sum I^2 (uint64), sum = sum I (int64), nonzero = cells != 0.  Exact for fewer than
+ *                     2^23 events in the range (the formula: emba_amd/csrc/panorama_rule.h, pano_vote).
+ * Any output may be NULL, and with every output NULL nothing is launched.  image_out: host memory of pano_h * pano_w int32; pm_out: host memory of nn * 2
+ * doubles, pm of every used event in event order (the seam the tests pin, like iwe_out above).  The registered window, its order and the last evaluation
+ * are left as they are.  EMBA_ERR_STATE: no sequence resident.  EMBA_ERR_INVALID_ARG: not beg <= end <= n, K < 2, dt_ns <= 0, nn >= 2^23, knots NULL.
+ * EMBA_ERR_TIME_RANGE: a batch midpoint outside the knots (the outputs are then untouched).  An empty or sub-batch range is EMBA_OK with J = 0 and a zero image.
+ * emba_amd.io.event_panorama is the same rule in numpy (given pm: the same integers).  Launches and timings: DESIGN.md §12.  While emba_enable_kernel_timing
+ * is on, the call records timer slot 7 around its vote kernel: emba_timer_elapsed_ms(ctx, 7, &ms) afterwards is that kernel's time. */
+emba_status emba_seq_event_panorama(emba_ctx* ctx, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                    int32_t signed_polarity, int32_t* image_out, uint64_t* j_out, int64_t* sum_out, uint64_t* nonzero_out,
+                                    uint64_t* dropped_out, double* pm_out);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
