@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, solve_host.h,
-// sequence_host.h, cmax_host.h, panorama_host.h, group.h); host code only.
+// sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -215,6 +215,11 @@ struct CmaxBuffers { DevBuf omega, t_ref, j0, j, evals, cand, cand_j, cand_iwe; 
 // non-zero cells, dropped votes and the pose stage's status word; pm: the projected events, where asked for.
 struct PanoBuffers { DevBuf image, batch_t, pose, knots, slots, out, pm; };
 
+// Grow-only buffers of the smooth contrast and its gradient (contrast_host.h): the fp64 image [H, W]; the midpoints, the pose table and the control poses
+// of the call (its own, like the panorama's); one slot per wave of the reduction; out: J, dropped votes, the pose stage's status word and, behind them, the
+// gradient [3 K]; pm, D, cp: the projected events, their 2x6 Jacobians and their control-pose indices, where asked for.
+struct ContrastBuffers { DevBuf image, batch_t, pose, knots, slots, out, pm, D, cp; };
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -381,6 +386,7 @@ struct emba_ctx {
     emba::CmaxPinhole cmax_pin;
     CmaxBuffers cmax;
     PanoBuffers pano;             // the panorama of warped events on that sequence (panorama_host.h)
+    ContrastBuffers contrast;     // its smooth contrast and the gradient with respect to the control poses (contrast_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -1,0 +1,199 @@
+// emba_amd/csrc/contrast_kernels.h — the smooth contrast of the panorama of warped events and its gradient with respect to the control poses (gfx950,
+// wave64).  The rule: contrast_rule.h, include/emba_hip.h (emba_seq_contrast_gradient), DESIGN.md §13.  Stages on one stream:
+//   * pose stage                       emba_batch_mid_kernel (order_kernels.h) and emba_pose_kernel (kernels.h) as they are, on the range's own batches and into
+//                                      this call's own tables: the pose record holds q, J1 and cp
+//   * emba_contrast_vote_kernel        one lane per event: contrast_warp, up to four return-less fp64 atomic adds into the double image in HBM
+//   * emba_contrast_grad_kernel        one lane per event: contrast_warp again (the same cells), the four I gathered, ge = 2 s gp^T D; summed per
+//                                      workgroup in an LDS table over the control poses the workgroup spans, then one global fp64 add per touched component
+//   * emba_contrast_reduce_kernel,     J = sum I^2 in fp64 in a fixed order: per thread -> wave shuffle -> one slot per wave, then one wave adds the slots
+//     emba_contrast_reduce_final_kernel
+// The fp64 adds into the image and into g arrive in no fixed order: both depend on it in their last bits (compared by tolerance, never by bits).  Given the
+// image, J is deterministic.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "contrast_rule.h"
+#include "device_math.h"
+#include "kernels.h"      // kPoseStride, emba_pose_kernel
+
+namespace emba {
+
+constexpr int kContrastThreads = 256;
+constexpr int kContrastReduceBlocks = 256;                                          // at the most: one round over the compute units
+constexpr int kContrastReduceSlots = kContrastReduceBlocks * (kContrastThreads / 64);   // one per wave
+
+struct ContrastParams {
+    const uint16_t* x; const uint16_t* y; const uint8_t* pol;   // the resident sequence, from the range's first event
+    const double* lut;                                          // bearing vector per sensor pixel [S, 3]
+    const double* pose;                                         // pose table of the range's batches (kPoseStride doubles each: q[4] J1[9] cp)
+    long nn;                                                    // events used: whole batches
+    int sw, W, H, K;
+    double fx, fy, cx, cy;                                      // the equirectangular camera of the context
+    int signed_polarity;
+    double* image;                                              // [H, W], zeroed on the stream in front of the vote launch
+    unsigned long long* dropped;                                // votes whose row lies outside the panorama (zeroed likewise)
+    double* grad;                                               // [3 K], zeroed likewise (gradient pass)
+    double* pm_out;                                             // [nn, 2] or nullptr (vote pass)
+    double* d_out;                                              // [nn, 2, 6] or nullptr (gradient pass)
+    int32_t* cp_out;                                            // [nn] or nullptr (gradient pass)
+};
+
+// Everything below is compiled without contraction: the two passes must land in the same cells, and the rule header's functions are the CPU test's.
+#pragma clang fp contract(off)
+
+// Event k of the range: pm = project(R(batch k / 100) * bearing) and J23 = dpm / d(rotation increment) — quat_to_matrix, the three products and two sums of
+// the warp kernels (kernels.h) and project_chain — then contrast_vote.  The one formulation both passes call.
+__device__ __forceinline__ ContrastVotes contrast_warp(const ContrastParams& p, long k, const double* P, double* pm, double* J23)
+{
+    const double q[4] = {P[0], P[1], P[2], P[3]};
+    double R[9];
+    quat_to_matrix(q, R);
+    const double* bv = p.lut + 3 * ((size_t)p.y[k] * (size_t)p.sw + (size_t)p.x[k]);      // (every event was checked at its upload: inside the LUT)
+    const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
+    double rb[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
+    project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
+    return contrast_vote(pm[0], pm[1], p.W, p.H);
+}
+
+__global__ __launch_bounds__(kContrastThreads) void emba_contrast_vote_kernel(ContrastParams p)
+{
+    const long k = (long)blockIdx.x * kContrastThreads + threadIdx.x;
+    unsigned int lost = 0;
+    if (k < p.nn) {
+        double pm[2], J23[6];      // (the Jacobian is dead code here)
+        const ContrastVotes v = contrast_warp(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
+        if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
+        const bool neg = p.signed_polarity && p.pol[k] == 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (v.w[i] == 0.0) continue;
+            if (v.cell[i] < 0) { ++lost; continue; }
+            atomicAdd(p.image + v.cell[i], neg ? -v.w[i] : v.w[i]);      // (the result is not used: a return-less global_atomic_add_f64)
+        }
+    }
+    // the dropped votes of the wave in one add (every lane of the workgroup arrives here)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
+    if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
+}
+
+// g += the gradients of the workgroup's events.  Events are in time order, so the control-pose indices of a workgroup's 256 events are a short run
+// [cp_first, cp_last]; the workgroup sums into an LDS table over [cp_first, cp_last + 1] (contrast_span), a wave whose lanes all have one cp by a shuffle
+// reduction and one lane's six LDS adds, a wave across a knot boundary by LDS atomics per lane, and then adds each touched component to g once.  A span
+// longer than the table (kContrastTableCps control poses): the lanes add to g in HBM directly.  A lane whose pose record holds no control-pose index in
+// [0, K - 2] — a batch outside the knots leaves its record unwritten, and sets the call's status word — adds nothing anywhere.
+__global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(ContrastParams p)
+{
+    __shared__ double tab[3 * kContrastTableCps];
+    __shared__ int w_lo[kContrastThreads / 64], w_hi[kContrastThreads / 64];
+    const long k = (long)blockIdx.x * kContrastThreads + threadIdx.x;
+    const int wave = threadIdx.x >> 6;
+    bool live = false;
+    int cp = 0;
+    double ge[6] = {0, 0, 0, 0, 0, 0};
+    if (k < p.nn) {
+        const double* P = p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch);
+        const double cpd = P[13];
+        live = cpd >= 0.0 && cpd <= (double)(p.K - 2);      // (false for NaN)
+        double pm[2], J23[6];
+        const ContrastVotes v = contrast_warp(p, k, P, pm, J23);
+        // dpm_ddrot_cp = J23 * [I - J1 | J1]   (the warp kernels' D, kernels.h)
+        double D[12];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                double s0 = 0, s1 = 0;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const double j1 = P[4 + 3 * j + c];
+                    const double j0 = ((j == c) ? 1.0 : 0.0) - j1;
+                    s0 += J23[3 * r + j] * j0;
+                    s1 += J23[3 * r + j] * j1;
+                }
+                D[6 * r + c] = s0;
+                D[6 * r + c + 3] = s1;
+            }
+        if (p.d_out) {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) p.d_out[12 * k + j] = D[j];
+        }
+        if (p.cp_out) p.cp_out[k] = live ? (int32_t)cpd : -1;
+        if (live) {
+            cp = (int)cpd;
+            double I4[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) I4[i] = v.cell[i] >= 0 ? p.image[v.cell[i]] : 0.0;
+            contrast_event_grad(v, I4, D, (p.signed_polarity && p.pol[k] == 0) ? -1.0 : 1.0, ge);
+        }
+    }
+    // the wave's and the workgroup's run of control poses (every lane arrives here)
+    int lo = live ? cp : 0x7FFFFFFF, hi = live ? cp : -1;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+    if ((threadIdx.x & 63) == 0) { w_lo[wave] = lo; w_hi[wave] = hi; }
+    for (int i = threadIdx.x; i < 3 * kContrastTableCps; i += kContrastThreads) tab[i] = 0.0;
+    __syncthreads();
+    int b_lo = w_lo[0], b_hi = w_hi[0];
+#pragma unroll
+    for (int i = 1; i < kContrastThreads / 64; ++i) { b_lo = min(b_lo, w_lo[i]); b_hi = max(b_hi, w_hi[i]); }
+    const ContrastSpan span = contrast_span(b_lo, b_hi);
+    if (b_hi < b_lo) return;      // no event of the workgroup has a pose (uniform: after the only barrier every lane takes part in)
+    if (!span.fits) {             // the fallback: every lane adds its six components to g
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                if (ge[j] != 0.0) atomicAdd(p.grad + 3 * (size_t)cp + j, ge[j]);
+        }
+        return;
+    }
+    if (hi >= lo) {               // the wave has live lanes
+        if (lo == hi) {           // all at one control pose: the butterfly, then lane 0's six LDS adds
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) ge[j] += __shfl_xor(ge[j], o);
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int j = 0; j < 6; ++j) atomicAdd(&tab[3 * (lo - span.first) + j], ge[j]);
+            }
+        } else if (live) {        // a knot boundary inside the wave
+#pragma unroll
+            for (int j = 0; j < 6; ++j) atomicAdd(&tab[3 * (cp - span.first) + j], ge[j]);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < span.comps; i += kContrastThreads) {
+        const double v = tab[i];
+        if (v != 0.0) atomicAdd(p.grad + 3 * (size_t)span.first + i, v);
+    }
+}
+
+// Slot (blockIdx.x, wave) <- sum I^2 over the cells the wave's lanes stride over: a grid-stride sweep, the butterfly, then the final kernel's order.
+__global__ __launch_bounds__(kContrastThreads) void emba_contrast_reduce_kernel(const double* __restrict__ image, long cells, double* __restrict__ slots)
+{
+    double j = 0.0;
+    for (long i = (long)blockIdx.x * kContrastThreads + threadIdx.x; i < cells; i += (long)gridDim.x * kContrastThreads) {
+        const double I = image[i];
+        j += I * I;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) j += __shfl_xor(j, o);
+    if ((threadIdx.x & 63) == 0) slots[(size_t)blockIdx.x * (kContrastThreads / 64) + (threadIdx.x >> 6)] = j;
+}
+
+// One wave: lane l adds the slots l, l + 64, ... in that order, the butterfly adds the lanes.
+__global__ __launch_bounds__(64) void emba_contrast_reduce_final_kernel(const double* __restrict__ slots, int n_slots, double* __restrict__ out)
+{
+    double j = 0.0;
+    for (int i = threadIdx.x; i < n_slots; i += 64) j += slots[i];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) j += __shfl_xor(j, o);
+    if (threadIdx.x == 0) out[0] = j;
+}
+#pragma clang fp contract(fast)
+
+}  // namespace emba

@@ -3,7 +3,8 @@
 // with a HIP-free rule header beside it: the context is context.h, copies into the caller's pageable memory transfer_host.h, the window and its order
 // order_host.h / order_rule.h, the step path (the evaluation and the normal equations) step_host.h / step_rule.h, the map map_host.h / map_rule.h, the solvers
 // (f1) solve_host.h / solve_rule.h, the resident event sequence sequence_host.h / sequence_rule.h, contrast maximisation on it
-// cmax_host.h / cmax_rule.h, the multi-GPU group group.h: all one translation unit.
+// cmax_host.h / cmax_rule.h, the panorama of warped events panorama_host.h / panorama_rule.h and its smooth contrast and gradient
+// contrast_host.h / contrast_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
 // (emba_set_events: pose-independent structure), launches kernels and moves bytes.
@@ -962,6 +963,7 @@ extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host
 #include "sequence_host.h"   // the resident event sequence of a sliding-window run: upload, windows, time shards and their halos, noise filters
 #include "cmax_host.h"       // contrast maximisation on it: the angular velocity of every slice of events, from the events alone
 #include "panorama_host.h"   // the panorama of warped events along a trajectory, and its contrast
+#include "contrast_host.h"   // the smooth (fp64) contrast of that panorama and its gradient with respect to the control poses
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

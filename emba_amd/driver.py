@@ -49,6 +49,11 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     record_contrast: bool = False   # WindowResult.contrast_init / contrast_final: J, sum, nonzero of the window's events at the segment handed to
                                     # solve_time_window and at the refined one — comparable between trajectories on the same events, which the LM cost is not
     event_panorama: bool = False    # SequenceResult.event_panorama: the image of the events the final trajectory spans, at that trajectory
+    # Refinement of each window's initial control poses on the window's events alone, before solve_time_window: conjugate-gradient ascent on the smooth
+    # contrast of the panorama of warped events (io.refine_contrast over LEGM.contrast_gradient; the rule: include/emba_hip.h,
+    # emba_seq_contrast_gradient), the window's first pose held fixed.  Needs the sequence resident on the device.  Off by default.
+    refine_contrast: bool = False
+    contrast_iters: int = 60
 
     def __post_init__(self):
         if self.init_poses not in ("given", "events"):
@@ -73,6 +78,9 @@ class WindowResult:
     map_init: object = None     # SequenceSettings.init_map = "events", first window only: the LMResult of the map-only pass that preceded `result`
     contrast_init: object = None    # SequenceSettings.record_contrast: {"J", "sum", "nonzero"} of the panorama of the window's events [beg, end) at traj_init
     contrast_final: object = None   # ... and at result.traj
+    refine_J_before: object = None  # SequenceSettings.refine_contrast: the smooth contrast of the window's events at the control poses as generated ...
+    refine_J_after: object = None   # ... and at the refined ones, which became traj_init
+    refine_evals: object = None     # ... and the evaluations of the contrast the ascent took
 
 
 @dataclass
@@ -122,6 +130,26 @@ def panorama_of_events(model, events, traj, beg, end, resident_sequence, want_im
     if lut is None or not sw or not sh:
         raise ValueError("the panorama of warped events without a resident sequence needs the camera: model.bearing_lut, model.sensor_w, model.sensor_h")
     return emba_io.event_panorama(events, lut, sw, sh, model.W, model.H, traj, beg, end)
+
+
+def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter):
+    """The window's initial control poses moved uphill on the smooth contrast of the window's events [beg, end) (io.refine_contrast over the model's
+    contrast_gradient), the first pose held fixed: (trajectory, J before, J after, evaluations).  Only where the sequence is resident on the model's
+    device: a numpy form of pm and D of its own is out of scope (so3.spline_evaluate has no Jacobian).  The end of the ascent depends on the last bits of
+    J: a model that stands for several ranks brings its own refine_contrast, which leaves every rank with the same trajectory."""
+    if not (resident_sequence and hasattr(model, "contrast_gradient")):
+        raise ValueError("refine_contrast needs a model with the event sequence resident on its device (LEGM.set_sequence, contrast_gradient)")
+    if hasattr(model, "refine_contrast"):      # a host over several ranks: one rank's loop, its result on all of them (sharded.ShardedLEGM.refine_contrast)
+        return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter))
+
+    def J_and_grad(t):
+        r = model.contrast_gradient(t, beg, end)
+        return r["J"], r["grad"]
+
+    def J_only(t):
+        return model.contrast_gradient(t, beg, end, want_grad=False)["J"]
+    traj, hist, evals = emba_io.refine_contrast(J_and_grad, J_only, seg, fix_first_pose=True, max_iter=int(max_iter), pano_w=model.W)
+    return traj, hist[0], hist[-1], evals
 
 
 def _contrast(r):
@@ -231,6 +259,9 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         # :450 solveTimeWindow; the map of windows 1, 2, ... is the one the previous window left on the device
         ba_win = dataclasses.replace(ba, first_time_window=first_time_window)
         map_init = None
+        rJ0 = rJ1 = r_evals = None
+        if seq.refine_contrast:      # on the events alone, before any map is solved for
+            seg, rJ0, rJ1, r_evals = refine_window_poses(model, seg, beg, end, resident_sequence, seq.contrast_iters)
         if first_time_window and seq.init_map == "events":
             # mapping with known poses from the zero map, at the window's initial control poses; the joint solve below then starts from the resident map
             map_init = solve_time_window(model, seg, ev_win, Gx, Gy, dataclasses.replace(ba_win, refine="map"), lm, verbose=verbose, resident=resident)
@@ -243,7 +274,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
             c_final = _contrast(panorama_of_events(model, events, res.traj, beg, end, resident_sequence))
         knots[idx_cp_beg:] = res.traj.knots_xyzw                                        # :453 replaceWith
         setup_ms = model.setup_info()["set_events_ms"] if hasattr(model, "setup_info") else float("nan")
-        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init, c_init, c_final))
+        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init, c_init, c_final, rJ0, rJ1, r_evals))
         # :459-460 the latest pose: the whole trajectory 1 us before the window's end
         pose_latest = so3.spline_evaluate(knots, traj_t0_ns, traj_dt_ns, t_win_end - 1000)
         # :512-532 slideWindow

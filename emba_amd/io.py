@@ -635,3 +635,115 @@ def pano_contrast(image):
     nz = image[image != 0]
     J = int((nz * nz).sum()) if int(np.abs(nz).sum()) < (1 << 31) else sum(int(v) * int(v) for v in nz.tolist())
     return dict(J=J, sum=int(image.sum()), nonzero=int(nz.size))
+
+
+# ---- the smooth contrast of that panorama and its gradient with respect to the control poses (numpy form of emba_seq_contrast_gradient, include/emba_hip.h,
+# given pm, D and cp; the device form is LEGM.contrast_gradient).  The votes are emba_amd/csrc/contrast_rule.h's contrast_vote, operation for operation.
+def contrast_votes(pm, pano_w, pano_h):
+    """contrast_vote (contrast_rule.h) of every row of pm [n, 2]: (cell int64 [n, 4], w, dwx, dwy float64 [n, 4]) for the cells (ix, iy), (ix + 1, iy),
+    (ix, iy + 1), (ix + 1, iy + 1) — the bilinear weights (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay and their derivatives in pm_x and pm_y; cell =
+    row * pano_w + column with the column wrapped modulo pano_w, -1 where the row lies outside [0, pano_h); a pm that is not finite (or |pm| >= 2^31) has
+    every cell -1 and every weight and derivative 0."""
+    W, H = int(pano_w), int(pano_h)
+    pm = np.asarray(pm, dtype=np.float64).reshape(-1, 2)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(pm[:, 0]) < 2147483648.0) & (np.abs(pm[:, 1]) < 2147483648.0)
+    x, y = np.where(ok, pm[:, 0], 0.0), np.where(ok, pm[:, 1], 0.0)
+    fx, fy = np.floor(x), np.floor(y)
+    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    ax, ay = x - fx, y - fy
+    bx, by = 1.0 - ax, 1.0 - ay
+    c0 = ix % W
+    c1 = np.where(c0 + 1 == W, 0, c0 + 1)
+    r0, r1 = (iy >= 0) & (iy < H) & ok, (iy + 1 >= 0) & (iy + 1 < H) & ok
+    cell = np.stack([np.where(r0, iy * W + c0, -1), np.where(r0, iy * W + c1, -1), np.where(r1, (iy + 1) * W + c0, -1), np.where(r1, (iy + 1) * W + c1, -1)], axis=1)
+    m = ok[:, None]
+    w = np.stack([bx * by, ax * by, bx * ay, ax * ay], axis=1) * m
+    dwx = np.stack([-by, by, -ay, ay], axis=1) * m
+    dwy = np.stack([-bx, -ax, bx, ax], axis=1) * m
+    return cell, w, dwx, dwy
+
+
+def contrast_gradient(pm, D, cp, pol, K, pano_w, pano_h, signed=False):
+    """The smooth contrast of the panorama of warped events and its gradient, given what the warp produced: pm [n, 2], D [n, 2, 6] (dpm_ddrot_cp, J23
+    [I - J1 | J1]), cp [n] (the control pose the event's spline segment begins at) and pol [n] (None: every event votes positive).  Returns a dict: image
+    float64 [pano_h, pano_w], J = sum I^2, grad float64 [3 K] with respect to the increments of incremental_update (ge = 2 s gp^T D per event, gp = sum over
+    the kept cells of I(c) (dwx, dwy); ge[0:3] to control pose cp, ge[3:6] to cp + 1; a component that is not finite, or an event whose cp lies outside
+    [0, K - 2], adds nothing), dropped = votes (non-zero weights) whose row lies outside the panorama.  D and cp may be None: grad is then None."""
+    W, H, K = int(pano_w), int(pano_h), int(K)
+    cell, w, dwx, dwy = contrast_votes(pm, W, H)
+    n = cell.shape[0]
+    s = np.ones(n)
+    if signed and pol is not None:
+        s = np.where(np.asarray(pol).reshape(-1)[:n] == 0, -1.0, 1.0)
+    inside = cell >= 0
+    img = np.zeros(W * H)
+    np.add.at(img, cell[inside], (w * s[:, None])[inside])
+    out = dict(image=img.reshape(H, W), J=float((img * img).sum()), dropped=int(np.count_nonzero(~inside & (w != 0))), grad=None)
+    if D is None or cp is None:
+        return out
+    D = np.asarray(D, dtype=np.float64).reshape(n, 2, 6)
+    cp = np.asarray(cp, dtype=np.int64).reshape(n)
+    I4 = np.where(inside, img[np.where(inside, cell, 0)], 0.0)
+    gx, gy = (I4 * dwx).sum(axis=1), (I4 * dwy).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ge = (2.0 * s)[:, None] * (gx[:, None] * D[:, 0, :] + gy[:, None] * D[:, 1, :])
+    ge = np.where(np.isfinite(ge), ge, 0.0)
+    live = (cp >= 0) & (cp <= K - 2)
+    g = np.zeros((K, 3))
+    np.add.at(g, cp[live], ge[live, :3])
+    np.add.at(g, cp[live] + 1, ge[live, 3:])
+    out["grad"] = g.reshape(-1)
+    return out
+
+
+def refine_contrast(J_and_grad, J_only, traj, fix_first_pose=True, max_iter=60, step_px=2.0, tol=1e-6, *, pano_w):
+    """Polak-Ribiere+ conjugate-gradient ascent of the control poses of traj on a contrast J.  J_and_grad(traj) -> (J, g [3 K]) with g the gradient with
+    respect to the increments of incremental_update, J_only(traj) -> J (the line search asks for nothing else).  With fix_first_pose the first control
+    pose's three components of g are zeroed.  Per iteration: the direction d is scaled so that its largest component is 1; trial steps a d go through
+    incremental_update, a starting at step_px 2 pi / pano_w (step_px pixels of azimuth on the panorama); a is halved up to 10 times until J rises
+    strictly, and doubled after an accepted step, capped at 8 times the start; the loop restarts along g where d . g <= 0.  It stops when no halving
+    helps, when the relative gain falls below tol, or after max_iter iterations.  pano_w is required: the first step is in pixels.  Returns (trajectory, [J at the start, J after every accepted step],
+    evaluations of J)."""
+    def grad_at(t):
+        J, g = J_and_grad(t)
+        g = np.array(g, dtype=np.float64).reshape(-1)
+        if fix_first_pose:
+            g[:3] = 0.0
+        return float(J), g
+    a0 = float(step_px) * 2.0 * np.pi / float(pano_w)
+    a = a0
+    J, g = grad_at(traj)
+    evals, hist, d = 1, [J], g.copy()
+    for _ in range(int(max_iter)):
+        if float(d @ g) <= 0.0:
+            d = g.copy()
+        top = float(np.max(np.abs(d), initial=0.0))
+        if not (top > 0.0 and np.isfinite(top)):
+            break
+        dn = d / top
+        trial = Jt = None
+        for _ in range(11):                                   # a, then up to 10 halvings
+            cand = incremental_update(traj, a * dn, fix_first_pose)
+            Jc = float(J_only(cand))
+            evals += 1
+            if Jc > J:
+                trial, Jt = cand, Jc
+                break
+            a *= 0.5
+        if trial is None:
+            break
+        gain = (Jt - J) / abs(Jt)
+        traj = trial
+        a = min(2.0 * a, 8.0 * a0)
+        _, g_new = grad_at(traj)                               # (the next comparisons are made against J_only's value of this point: one form throughout)
+        evals += 1
+        hist.append(Jt)
+        gg = float(g @ g)
+        beta = max(0.0, float(g_new @ (g_new - g)) / gg) if gg > 0.0 else 0.0
+        d = g_new + beta * d
+        g = g_new
+        J = Jt
+        if gain < tol:
+            break
+    return traj, hist, evals

@@ -8,6 +8,8 @@
   python examples/run_ba.py --demo out/ --init-map events     # no front-end map: start from a zero map, solved for the map alone first
   python examples/run_ba.py --demo out/ --init-poses events --init-map events --window-size 0.3 --window-stride 0.1   # no front end at all: the raw poses
                                                   # come from the events by contrast maximisation on the device; --events E --calib C likewise
+  python examples/run_ba.py --demo out/ --init-poses events --init-map events --refine-contrast --window-size 0.3 --window-stride 0.1   # ... and each window's
+                                                  # initial control poses moved uphill on the contrast of its warped events first
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
@@ -70,6 +72,9 @@ def main():
     ap.add_argument("--record-contrast", action="store_true", help="print, per window, the contrast J = sum I^2 of the panorama of the window's warped events at its "
                     "initial and at its refined control poses (with --window-size; DESIGN.md section 12)")
     ap.add_argument("--event-panorama", action="store_true", help="write <out>/event_panorama.png: the events warped along the final trajectory (with --window-size)")
+    ap.add_argument("--refine-contrast", action="store_true", help="before each window's solve, move the window's initial control poses uphill on the smooth contrast of "
+                    "the panorama of the window's warped events — on the events alone, the window's first pose held fixed (with --window-size; DESIGN.md section 13)")
+    ap.add_argument("--contrast-iters", type=int, default=60, help="conjugate-gradient iterations of --refine-contrast per window, at the most")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
@@ -82,8 +87,8 @@ def main():
         ap.error("--poses is required unless --init-poses events is given")
     if a.init_poses == "events" and not a.window_size:
         ap.error("--init-poses events needs --window-size (the estimate runs on the resident sequence of a sliding-window run)")
-    if (a.record_contrast or a.event_panorama) and not a.window_size:
-        ap.error("--record-contrast / --event-panorama need --window-size (they run on the resident sequence of a sliding-window run)")
+    if (a.record_contrast or a.event_panorama or a.refine_contrast) and not a.window_size:
+        ap.error("--record-contrast / --event-panorama / --refine-contrast need --window-size (they run on the resident sequence of a sliding-window run)")
     os.makedirs(a.out, exist_ok=True)
 
     if a.demo:
@@ -165,7 +170,8 @@ def main():
                                event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
                                hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
                                init_poses=a.init_poses, cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
-                               record_contrast=a.record_contrast, event_panorama=a.event_panorama)
+                               record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
+                               contrast_iters=a.contrast_iters)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
@@ -185,6 +191,9 @@ def main():
                     print(f"window {wr.index}: map-only start from a zero map, {wr.map_init.iterations} LM iterations ({wr.map_init.reason}), cost {wr.map_init.cost_min:.6e}")
                 print(f"window {wr.index}: [{wr.t_beg_ns * 1e-9:.3f}, {wr.t_end_ns * 1e-9:.3f}] s, events [{wr.beg}, {wr.end}), control poses from {wr.idx_cp_beg}, "
                       f"{wr.result.iterations} LM iterations ({wr.result.reason or 'converged'}), cost {wr.result.cost_min:.6e}, set-up {wr.setup_ms:.2f} ms")
+                if wr.refine_J_before is not None:
+                    print(f"window {wr.index}: control poses refined on the events alone, smooth contrast J = {wr.refine_J_before:.6e} -> {wr.refine_J_after:.6e} "
+                          f"in {wr.refine_evals} evaluations")
                 if wr.contrast_init is not None:
                     j0, j1 = wr.contrast_init["J"], wr.contrast_final["J"]
                     print(f"window {wr.index}: contrast of the warped events J = {j0:.6e} -> {j1:.6e} (x {j1 / max(j0, 1):.4f})")

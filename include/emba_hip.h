@@ -381,6 +381,31 @@ emba_status emba_seq_event_panorama(emba_ctx* ctx, size_t beg, size_t end, const
                                     int32_t signed_polarity, int32_t* image_out, uint64_t* j_out, int64_t* sum_out, uint64_t* nonzero_out,
                                     uint64_t* dropped_out, double* pm_out);
 
+/* ---- The smooth contrast of that panorama and its gradient with respect to the control poses (what moves a trajectory uphill on the events alone;
+ * DESIGN.md §13).  The integer image above is piecewise constant in the poses; this one is fp64 with real bilinear weights.  Range, batches, midpoints, pm,
+ * column wrap and pole rows are exactly those of emba_seq_event_panorama.
+ *   votes             ix = floor(pm_x), ax = pm_x - ix, iy, ay likewise; the cells (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) get the weights
+ *                     (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay.  Their derivatives in pm_x are -(1 - ay), +(1 - ay), -ay, +ay, in pm_y
+ *                     -(1 - ax), -ax, +(1 - ax), +ax.  A cell whose row lies outside [0, pano_h) is dropped, and counted in *dropped_out where its weight
+ *                     is not zero.  A pm that is not finite votes nowhere.
+ *   image, contrast   I(c) = sum_k s_k w_kc with s_k = 1, or +-1 by polarity where signed_polarity != 0 (pol == 0: -1); J = sum_c I(c)^2, fp64.
+ *   gradient          with respect to the increments x of knot_i <- exp(x_i) knot_i (emba_amd.io.incremental_update): grad_out has 3 K entries.  For
+ *                     event k of a batch whose spline segment begins at control pose cp: gp = sum_i I(c_i) (dwx_i, dwy_i) over the kept cells,
+ *                     ge = 2 s_k gp^T D_k with D_k the 2x6 dpm_ddrot_cp of the evaluation path (J23 [I - J1 | J1]); ge[0:3] is added to g[3 cp ..],
+ *                     ge[3:6] to g[3 (cp + 1) ..].  A component of ge that is not finite adds nothing.
+ * The formula: emba_amd/csrc/contrast_rule.h; emba_amd.io.contrast_votes / contrast_gradient are the same rule in numpy given pm, D and cp.  The adds into
+ * the image and into g are fp64 atomics whose order is not fixed: both depend on it in their last bits, so results are compared by tolerance, not by bits
+ * (given the image, J is deterministic).  Any output may be NULL, and with every output NULL nothing is launched.  With grad_out, d_out and cp_out NULL
+ * the gradient pass is not launched (a line search asks for J alone).  image_out: pano_h * pano_w doubles; pm_out [nn, 2], d_out [nn, 2, 6], cp_out [nn]
+ * (-1: no pose): per used event in event order, the seam the tests pin.  Statuses and the empty range as emba_seq_event_panorama (J = 0, grad = 0, a zero
+ * image), without its limit of 2^23 events: fp64 cells do not overflow.  EMBA_ERR_TIME_RANGE leaves the outputs untouched.  The registered window, its
+ * order, the last evaluation and the integer panorama's buffers are left as they are.  While emba_enable_kernel_timing is on, timer slot 7 brackets the
+ * vote kernel and the gradient kernel together. */
+emba_status emba_seq_contrast_gradient(emba_ctx* ctx, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                       int32_t signed_polarity, double* j_out, double* grad_out /* 3K or NULL */, double* image_out /* H*W or NULL */,
+                                       uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */, double* d_out /* [nn,2,6] or NULL */,
+                                       int32_t* cp_out /* [nn] or NULL */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
