@@ -387,6 +387,8 @@ struct emba_ctx {
     CmaxBuffers cmax;
     PanoBuffers pano;             // the panorama of warped events on that sequence (panorama_host.h)
     ContrastBuffers contrast;     // its smooth contrast and the gradient with respect to the control poses (contrast_host.h)
+    int opt_contrast_vote = -1;   // option contrast_vote: the vote kernel of a level call — -1 by the image's size (contrast_rule.h: contrast_vote_plan), 0 HBM, 1 LDS where it fits
+    int contrast_vote_path = -1;  // the vote kernel the last contrast call launched: 0 HBM, 1 LDS; -1 none yet (emba_get_option "contrast_vote_path")
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

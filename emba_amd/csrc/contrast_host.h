@@ -1,6 +1,6 @@
 // emba_amd/csrc/contrast_host.h — the smooth contrast of the panorama of warped events and its gradient with respect to the control poses, as host code
-// over the kernels of contrast_kernels.h (emba_seq_contrast_gradient).  What is plain arithmetic — the argument checks, the votes of one event and their
-// derivatives, the gradient of one event, the span plan — is decided in contrast_rule.h; here are the buffers (emba_ctx::contrast), the launches and the
+// over the kernels of contrast_kernels.h (emba_seq_contrast_gradient, emba_seq_contrast_gradient_level).  What is plain arithmetic — the argument checks, the votes of one event and their
+// derivatives, the gradient of one event, the span plan, the grid of a level and the vote kernel it takes — is decided in contrast_rule.h; here are the buffers (emba_ctx::contrast), the launches and the
 // C ABI.
 // Part of emba_hip.hip's translation unit, included by it below panorama_host.h (SEQ_TRY, d2h_pageable, the sequence itself: emba_ctx::evseq).  Nothing of
 // the registered window or of the integer panorama is read or written: the batch times, the pose table, the control poses, the image and the status word
@@ -19,12 +19,24 @@ constexpr int kContrastTimerSlot = 7;      // with kernel timing on: the events 
 constexpr size_t kContrastHead = 3;        // 8-byte words in front of g in emba_ctx::contrast.out: J (a double), dropped votes, the pose stage's status word
 }
 
-extern "C" emba_status emba_seq_contrast_gradient(emba_ctx* c, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
-                                                  int32_t signed_polarity, double* j_out, double* grad_out, double* image_out, uint64_t* dropped_out,
-                                                  double* pm_out, double* d_out, int32_t* cp_out)
+// Both entry points.  level < 0: emba_seq_contrast_gradient — the panorama's own grid, the <false> instantiations of the vote and gradient kernels, the
+// votes in HBM: what it was before there were levels.  level >= 0: emba_seq_contrast_gradient_level — the level's grid (contrast_level_grid), the <true>
+// instantiations, and the vote kernel contrast_vote_plan names.
+static emba_status contrast_gradient_run(emba_ctx* c, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                         int32_t signed_polarity, int level, double* j_out, double* grad_out, double* image_out, uint64_t* dropped_out,
+                                         double* pm_out, double* d_out, int32_t* cp_out)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
     if (!c->evseq.have) return fail(c, EMBA_ERR_STATE, "no resident sequence (emba_seq_upload first)");
+    const bool leveled = level >= 0;
+    if (leveled)
+        switch (contrast_level_ok(c->W, c->H, level)) {
+        case ContrastLevelStatus::bad_level: return fail(c, EMBA_ERR_INVALID_ARG, "level %d: levels are 0 ... %d", level, kContrastMaxLevel);
+        case ContrastLevelStatus::not_divisible: return fail(c, EMBA_ERR_INVALID_ARG, "level %d: a panorama of %d x %d cells is not divisible by %d", level, c->W, c->H, 1 << level);
+        case ContrastLevelStatus::too_few_rows: return fail(c, EMBA_ERR_INVALID_ARG, "level %d: %d rows of %d leave fewer than two", level, c->H, 1 << level);
+        default: break;
+        }
+    const ContrastLevel lv = contrast_level_grid(c->W, c->H, leveled ? level : 0);
     switch (contrast_args_ok(beg, end, c->evseq.n, K, dt_ns)) {
     case PanoArgStatus::not_a_range: return fail(c, EMBA_ERR_INVALID_ARG, "[%zu, %zu) is not a range of the resident sequence of %zu events", beg, end, c->evseq.n);
     case PanoArgStatus::too_few_knots: return fail(c, EMBA_ERR_INVALID_ARG, "K = %d: a linear spline has at least two control poses", (int)K);
@@ -32,7 +44,7 @@ extern "C" emba_status emba_seq_contrast_gradient(emba_ctx* c, size_t beg, size_
     default: break;
     }
     if (!j_out && !grad_out && !image_out && !dropped_out && !pm_out && !d_out && !cp_out) return EMBA_OK;      // nothing asked for: nothing launched
-    const size_t nb = pano_batch_count(beg, end), nn = pano_events_used(beg, end), cells = c->npix, ng = 3 * (size_t)K;
+    const size_t nb = pano_batch_count(beg, end), nn = pano_events_used(beg, end), cells = (size_t)lv.W * (size_t)lv.H, ng = 3 * (size_t)K;
     if (!nn) {      // an empty or sub-batch range: no event votes
         if (j_out) *j_out = 0.0;
         if (grad_out) std::memset(grad_out, 0, ng * sizeof(double));
@@ -67,12 +79,20 @@ extern "C" emba_status emba_seq_contrast_gradient(emba_ctx* c, size_t beg, size_
     // votes, gradient.  (A batch outside the knots leaves its pose record unwritten and sets the status word: whatever that record holds, contrast_vote
     // keeps every add inside the image, the gradient kernel takes no control-pose index outside [0, K - 2], and the result is discarded below.)
     ContrastParams P{c->evseq.x.as<uint16_t>() + beg, c->evseq.y.as<uint16_t>() + beg, c->evseq.pol.as<uint8_t>() + beg, c->d_lut.as<double>(), B.pose.as<double>(), (long)nn,
-                     c->sw, c->W, c->H, (int)K, c->fx, c->fy, c->cx, c->cy, signed_polarity != 0, B.image.as<double>(),
+                     c->sw, lv.W, lv.H, (int)K, lv.scale, c->fx, c->fy, c->cx, c->cy, signed_polarity != 0, B.image.as<double>(),
                      reinterpret_cast<unsigned long long*>(d_head + 1), d_head + kContrastHead, pm_out ? B.pm.as<double>() : (double*)nullptr,
                      d_out ? B.D.as<double>() : (double*)nullptr, cp_out ? B.cp.as<int32_t>() : (int32_t*)nullptr};
     if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->ev_start[kContrastTimerSlot], s));
-    hipLaunchKernelGGL(emba_contrast_vote_kernel, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
-    if (grad_pass) hipLaunchKernelGGL(emba_contrast_grad_kernel, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
+    const ContrastVotePath path = leveled ? contrast_vote_plan(lv.W, lv.H, c->opt_contrast_vote) : ContrastVotePath::hbm;
+    c->contrast_vote_path = (int)path;
+    if (!leveled) {
+        hipLaunchKernelGGL(emba_contrast_vote_kernel<false>, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
+        if (grad_pass) hipLaunchKernelGGL(emba_contrast_grad_kernel<false>, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
+    } else {
+        if (path == ContrastVotePath::lds) hipLaunchKernelGGL(emba_contrast_vote_lds_kernel, dim3(contrast_lds_grid(c->n_cu)), dim3(kContrastLdsThreads), 0, s, P);
+        else hipLaunchKernelGGL(emba_contrast_vote_kernel<true>, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
+        if (grad_pass) hipLaunchKernelGGL(emba_contrast_grad_kernel<true>, dim3(nblocks(nn, kContrastThreads)), dim3(kContrastThreads), 0, s, P);
+    }
     if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->ev_stop[kContrastTimerSlot], s));
     // contrast
     const unsigned rblocks = std::min<unsigned>(nblocks(cells, kContrastThreads * 4), kContrastReduceBlocks);
@@ -93,4 +113,19 @@ extern "C" emba_status emba_seq_contrast_gradient(emba_ctx* c, size_t beg, size_
     if (d_out) SEQ_TRY(d2h_pageable(c, d_out, B.D.p, 12 * nn * sizeof(double)));
     if (cp_out) SEQ_TRY(d2h_pageable(c, cp_out, B.cp.p, nn * sizeof(int32_t)));
     return EMBA_OK;
+}
+
+extern "C" emba_status emba_seq_contrast_gradient(emba_ctx* c, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                                  int32_t signed_polarity, double* j_out, double* grad_out, double* image_out, uint64_t* dropped_out,
+                                                  double* pm_out, double* d_out, int32_t* cp_out)
+{
+    return contrast_gradient_run(c, beg, end, knots_xyzw, K, t0_ns, dt_ns, signed_polarity, -1, j_out, grad_out, image_out, dropped_out, pm_out, d_out, cp_out);
+}
+
+extern "C" emba_status emba_seq_contrast_gradient_level(emba_ctx* c, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                                        int32_t signed_polarity, int32_t level, double* j_out, double* grad_out, double* image_out,
+                                                        uint64_t* dropped_out, double* pm_out, double* d_out, int32_t* cp_out)
+{
+    if (c && level < 0) return fail(c, EMBA_ERR_INVALID_ARG, "level %d: levels are 0 ... %d", (int)level, kContrastMaxLevel);
+    return contrast_gradient_run(c, beg, end, knots_xyzw, K, t0_ns, dt_ns, signed_polarity, level, j_out, grad_out, image_out, dropped_out, pm_out, d_out, cp_out);
 }

@@ -7,6 +7,10 @@
 //                                      workgroup in an LDS table over the control poses the workgroup spans, then one global fp64 add per touched component
 //   * emba_contrast_reduce_kernel,     J = sum I^2 in fp64 in a fixed order: per thread -> wave shuffle -> one slot per wave, then one wave adds the slots
 //     emba_contrast_reduce_final_kernel
+// Levels (emba_seq_contrast_gradient_level, contrast_rule.h): the vote and gradient kernels' <true> instantiations vote at pm 2^-l on the
+// level's grid and multiply D by 2^-l; the <false> ones are the level-free entry point's, unchanged.  Where the level's image fits LDS:
+//   * emba_contrast_vote_lds_kernel    a fixed grid of persistent workgroups, each summing a contiguous share of the events into an image in LDS
+//                                      (ds_add_f64) and then adding its non-zero cells to the image in HBM
 // The fp64 adds into the image and into g arrive in no fixed order: both depend on it in their last bits (compared by tolerance, never by bits).  Given the
 // image, J is deterministic.
 #pragma once
@@ -28,7 +32,8 @@ struct ContrastParams {
     const double* lut;                                          // bearing vector per sensor pixel [S, 3]
     const double* pose;                                         // pose table of the range's batches (kPoseStride doubles each: q[4] J1[9] cp)
     long nn;                                                    // events used: whole batches
-    int sw, W, H, K;
+    int sw, W, H, K;                                            // (W, H: the grid voted on — the panorama, or the level's W_l, H_l)
+    double scale;                                               // 2^-level: read by the <true> instantiations and the LDS vote only
     double fx, fy, cx, cy;                                      // the equirectangular camera of the context
     int signed_polarity;
     double* image;                                              // [H, W], zeroed on the stream in front of the vote launch
@@ -43,7 +48,9 @@ struct ContrastParams {
 #pragma clang fp contract(off)
 
 // Event k of the range: pm = project(R(batch k / 100) * bearing) and J23 = dpm / d(rotation increment) — quat_to_matrix, the three products and two sums of
-// the warp kernels (kernels.h) and project_chain — then contrast_vote.  The one formulation both passes call.
+// the warp kernels (kernels.h) and project_chain — then contrast_vote (kScaled: at pm 2^-level on the level's grid; pm and J23 stay unscaled).  The one
+// formulation every pass calls.
+template <bool kScaled>
 __device__ __forceinline__ ContrastVotes contrast_warp(const ContrastParams& p, long k, const double* P, double* pm, double* J23)
 {
     const double q[4] = {P[0], P[1], P[2], P[3]};
@@ -55,16 +62,18 @@ __device__ __forceinline__ ContrastVotes contrast_warp(const ContrastParams& p, 
 #pragma unroll
     for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
     project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
-    return contrast_vote(pm[0], pm[1], p.W, p.H);
+    if constexpr (kScaled) return contrast_vote_level(pm[0], pm[1], ContrastLevel{p.W, p.H, p.scale});
+    else return contrast_vote(pm[0], pm[1], p.W, p.H);
 }
 
+template <bool kScaled>
 __global__ __launch_bounds__(kContrastThreads) void emba_contrast_vote_kernel(ContrastParams p)
 {
     const long k = (long)blockIdx.x * kContrastThreads + threadIdx.x;
     unsigned int lost = 0;
     if (k < p.nn) {
         double pm[2], J23[6];      // (the Jacobian is dead code here)
-        const ContrastVotes v = contrast_warp(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
+        const ContrastVotes v = contrast_warp<kScaled>(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
         if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
         const bool neg = p.signed_polarity && p.pol[k] == 0;
 #pragma unroll
@@ -80,11 +89,48 @@ __global__ __launch_bounds__(kContrastThreads) void emba_contrast_vote_kernel(Co
     if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
 }
 
+// The votes of a level whose image fits LDS (contrast_vote_plan).  gridDim.x persistent workgroups (contrast_lds_grid: a function of the chip, not of
+// nn); workgroup b zeroes the W x H cells of its LDS image, votes its share of the events (contrast_share: contiguous, so in time order a compact part of
+// the panorama) into it with LDS atomics, and after the barrier adds its cells that are not zero to the image in HBM, return-less.  A workgroup with an
+// empty share returns at once and adds nothing.  p.W * p.H <= kContrastLdsCells is the host's plan; contrast_vote keeps every cell index inside W x H.
+__global__ __launch_bounds__(kContrastLdsThreads) void emba_contrast_vote_lds_kernel(ContrastParams p)
+{
+    __shared__ double img[kContrastLdsCells];
+    const int cells = p.W * p.H;
+    const ContrastShare sh = contrast_share(p.nn, (int)gridDim.x, (int)blockIdx.x);
+    if (sh.end <= sh.beg) return;      // (uniform over the workgroup: in front of every barrier)
+    for (int i = threadIdx.x; i < cells; i += kContrastLdsThreads) img[i] = 0.0;
+    __syncthreads();
+    unsigned int lost = 0;
+    for (long k = sh.beg + threadIdx.x; k < sh.end; k += kContrastLdsThreads) {
+        double pm[2], J23[6];      // (the Jacobian is dead code here)
+        const ContrastVotes v = contrast_warp<true>(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
+        if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
+        const bool neg = p.signed_polarity && p.pol[k] == 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (v.w[i] == 0.0) continue;
+            if (v.cell[i] < 0) { ++lost; continue; }
+            atomicAdd(&img[v.cell[i]], neg ? -v.w[i] : v.w[i]);      // (the result is not used: ds_add_f64)
+        }
+    }
+    // the dropped votes of the wave in one add (the lanes have left the loop: every lane of the workgroup arrives here)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
+    if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += kContrastLdsThreads) {
+        const double v = img[i];
+        if (v != 0.0) atomicAdd(p.image + i, v);
+    }
+}
+
 // g += the gradients of the workgroup's events.  Events are in time order, so the control-pose indices of a workgroup's 256 events are a short run
 // [cp_first, cp_last]; the workgroup sums into an LDS table over [cp_first, cp_last + 1] (contrast_span), a wave whose lanes all have one cp by a shuffle
 // reduction and one lane's six LDS adds, a wave across a knot boundary by LDS atomics per lane, and then adds each touched component to g once.  A span
 // longer than the table (kContrastTableCps control poses): the lanes add to g in HBM directly.  A lane whose pose record holds no control-pose index in
 // [0, K - 2] — a batch outside the knots leaves its record unwritten, and sets the call's status word — adds nothing anywhere.
+template <bool kScaled>
 __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(ContrastParams p)
 {
     __shared__ double tab[3 * kContrastTableCps];
@@ -99,7 +145,7 @@ __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(Co
         const double cpd = P[13];
         live = cpd >= 0.0 && cpd <= (double)(p.K - 2);      // (false for NaN)
         double pm[2], J23[6];
-        const ContrastVotes v = contrast_warp(p, k, P, pm, J23);
+        const ContrastVotes v = contrast_warp<kScaled>(p, k, P, pm, J23);
         // dpm_ddrot_cp = J23 * [I - J1 | J1]   (the warp kernels' D, kernels.h)
         double D[12];
 #pragma unroll
@@ -122,6 +168,10 @@ __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(Co
             for (int j = 0; j < 12; ++j) p.d_out[12 * k + j] = D[j];
         }
         if (p.cp_out) p.cp_out[k] = live ? (int32_t)cpd : -1;
+        if constexpr (kScaled) {      // D_l = D 2^-level (d_out above stays the unscaled D)
+#pragma unroll
+            for (int j = 0; j < 12; ++j) D[j] *= p.scale;
+        }
         if (live) {
             cp = (int)cpd;
             double I4[4];

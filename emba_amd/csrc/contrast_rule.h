@@ -1,6 +1,7 @@
 // emba_amd/csrc/contrast_rule.h — the smooth contrast of the panorama of warped events and its gradient with respect to the control poses
 // (contrast_host.h, contrast_kernels.h), as functions of plain values: the argument checks, the bilinear votes of one projected event with their
-// derivatives, the gradient of one event, and the span of control poses a workgroup's LDS table covers.
+// derivatives, the gradient of one event, the span of control poses a workgroup's LDS table covers, and the levels of the coarse-to-fine refinement
+// (their grids, the scaled vote, the vote kernel a level takes, the shares of its persistent workgroups).
 // emba_amd.io.contrast_votes / contrast_gradient are the same rule in numpy; include/emba_hip.h (emba_seq_contrast_gradient) states it in words.
 //
 // The rule, once.  Range, batches, midpoints, pm, column wrap and pole rows are those of emba_seq_event_panorama (panorama_rule.h).  Event k projected to
@@ -94,6 +95,63 @@ EMBA_RULE_HD inline ContrastSpan contrast_span(int cp_first, int cp_last)
     s.fits = cps <= kContrastTableCps;
     s.comps = s.fits ? (int)(3 * cps) : 0;
     return s;
+}
+
+// ---- levels (coarse to fine).  Level l in [0, kContrastMaxLevel] is the rule above on a grid of W_l = pano_w >> l by H_l = pano_h >> l
+// cells: the vote coordinate is pm_l = pm 2^-l and the Jacobian D_l = D 2^-l (both exact scalings), everything else — floor, the four weights and their
+// derivatives, the column wrap modulo W_l, rows outside [0, H_l) dropped and counted, a pm that is not finite, the polarity signs, ge and where it is
+// added — is unchanged with W_l, H_l for W, H.  Level 0 is the rule above, bit for bit (a product with 1.0).  emba_amd.io.contrast_level is the numpy form.
+constexpr int kContrastMaxLevel = 8;
+enum class ContrastLevelStatus { ok, bad_level, not_divisible, too_few_rows };
+inline ContrastLevelStatus contrast_level_ok(int pano_w, int pano_h, int level)
+{
+    if (level < 0 || level > kContrastMaxLevel) return ContrastLevelStatus::bad_level;
+    const int m = (1 << level) - 1;
+    if ((pano_w & m) || (pano_h & m)) return ContrastLevelStatus::not_divisible;
+    if ((pano_h >> level) < 2) return ContrastLevelStatus::too_few_rows;
+    return ContrastLevelStatus::ok;
+}
+struct ContrastLevel {
+    int W, H;          // W_l, H_l
+    double scale;      // 2^-l
+};
+EMBA_RULE_HD inline ContrastLevel contrast_level_grid(int pano_w, int pano_h, int level)      // (of a level contrast_level_ok accepts)
+{
+    return ContrastLevel{pano_w >> level, pano_h >> level, 1.0 / (double)(1 << level)};
+}
+// the votes of one event at a level: contrast_vote of the scaled pm on the level's grid
+EMBA_RULE_HD inline ContrastVotes contrast_vote_level(double pm_x, double pm_y, const ContrastLevel& lv)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    return contrast_vote(pm_x * lv.scale, pm_y * lv.scale, lv.W, lv.H);
+}
+
+// ---- which vote kernel a level call takes.  An image of at most kContrastLdsCells cells (64 KiB of fp64: what one workgroup may declare as a static array,
+// and two fifths of a compute unit's 160 KiB) is summed in LDS by a fixed grid of persistent workgroups, each over a contiguous share of the events, and
+// only the non-zero cells of each workgroup's image go to HBM; a larger one takes the adds in HBM directly.  forced: option contrast_vote, -1 by the size,
+// 0 always HBM, 1 LDS wherever the image fits (never where it does not).
+constexpr int kContrastLdsCells = 8192;
+constexpr int kContrastLdsThreads = 1024;
+enum class ContrastVotePath { hbm = 0, lds = 1 };
+inline ContrastVotePath contrast_vote_plan(int W_l, int H_l, int forced)
+{
+    const bool fits = (int64_t)W_l * (int64_t)H_l <= kContrastLdsCells;
+    return fits && forced != 0 ? ContrastVotePath::lds : ContrastVotePath::hbm;
+}
+// the persistent grid: one workgroup per compute unit, whatever the number of events
+inline int contrast_lds_grid(int compute_units) { return compute_units > 0 ? compute_units : 1; }
+// the events [beg, end) of workgroup b of `blocks`: contiguous shares of ceil(nn / blocks) events, at least one round of the workgroup's lanes — any
+// partition is correct (every vote is an add); a workgroup behind the last event gets an empty share and adds nothing
+struct ContrastShare { long beg, end; };
+EMBA_RULE_HD inline ContrastShare contrast_share(long nn, int blocks, int b)
+{
+    long per = (nn + blocks - 1) / blocks;
+    if (per < kContrastLdsThreads) per = kContrastLdsThreads;
+    const long beg = (long)b * per < nn ? (long)b * per : nn;
+    const long end = beg + per < nn ? beg + per : nn;
+    return ContrastShare{beg, end};
 }
 
 }  // namespace emba

@@ -532,6 +532,11 @@ const OptionRef kStepPrepOptions[] = {
     {"step_prep", &emba_ctx::step_prep, 0, 1},
     {"step_prep_polls", &emba_ctx::step_prep_polls, 0, 1 << 16},
 };
+// the vote kernel of emba_seq_contrast_gradient_level (contrast_rule.h: contrast_vote_plan); tests/test_gpu_contrast_pyramid.py runs every value at a level
+// whose image fits LDS and at one whose image does not
+const OptionRef kContrastOptions[] = {
+    {"contrast_vote", &emba_ctx::opt_contrast_vote, -1, 1},
+};
 }  // namespace
 
 emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
@@ -545,6 +550,12 @@ emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
             return EMBA_OK;
         }
     for (const OptionRef& o : kStepPrepOptions)
+        if (!strcmp(o.name, name)) {
+            if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
+            c->*(o.field) = (int)value;
+            return EMBA_OK;
+        }
+    for (const OptionRef& o : kContrastOptions)
         if (!strcmp(o.name, name)) {
             if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
             c->*(o.field) = (int)value;
@@ -573,6 +584,9 @@ emba_status emba_get_option(emba_ctx* c, const char* name, int32_t* value)
     for (const OptionRef& o : kOptions)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     for (const OptionRef& o : kStepPrepOptions)
+        if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
+    if (!strcmp(name, "contrast_vote_path")) { *value = c->contrast_vote_path; return EMBA_OK; }      // read-only: the vote kernel of the last contrast call — 0 HBM, 1 LDS, -1 none yet
+    for (const OptionRef& o : kContrastOptions)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
 }

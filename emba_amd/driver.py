@@ -54,10 +54,14 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # emba_seq_contrast_gradient), the window's first pose held fixed.  Needs the sequence resident on the device.  Off by default.
     refine_contrast: bool = False
     contrast_iters: int = 60
+    # The schedule of that ascent, coarse to fine (io.refine_contrast_pyramid): level l climbs on a panorama of cells 2^l pixels wide
+    # (LEGM.contrast_gradient(level=l)), each level for up to contrast_iters iterations, strictly decreasing and ending at 0.  (0,): the panorama alone.
+    contrast_levels: tuple = (0,)
 
     def __post_init__(self):
         if self.init_poses not in ("given", "events"):
             raise ValueError(f"SequenceSettings.init_poses must be 'given' or 'events', not {self.init_poses!r}")
+        self.contrast_levels = emba_io.check_contrast_levels(self.contrast_levels, 1 << emba_io.CONTRAST_MAX_LEVEL)      # (the width: checked where it is known)
         if int(self.cmax_slice_events) < 1:
             raise ValueError(f"SequenceSettings.cmax_slice_events = {self.cmax_slice_events}: a slice has at least one event")
         if not (np.isfinite(self.cmax_omega_max) and self.cmax_omega_max > 0):
@@ -80,7 +84,7 @@ class WindowResult:
     contrast_final: object = None   # ... and at result.traj
     refine_J_before: object = None  # SequenceSettings.refine_contrast: the smooth contrast of the window's events at the control poses as generated ...
     refine_J_after: object = None   # ... and at the refined ones, which became traj_init
-    refine_evals: object = None     # ... and the evaluations of the contrast the ascent took
+    refine_evals: object = None     # ... and the evaluations of the contrast the ascent took (over all of SequenceSettings.contrast_levels; J before and after: at level 0)
 
 
 @dataclass
@@ -132,15 +136,23 @@ def panorama_of_events(model, events, traj, beg, end, resident_sequence, want_im
     return emba_io.event_panorama(events, lut, sw, sh, model.W, model.H, traj, beg, end)
 
 
-def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter):
+def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter, levels=(0,)):
     """The window's initial control poses moved uphill on the smooth contrast of the window's events [beg, end) (io.refine_contrast over the model's
     contrast_gradient), the first pose held fixed: (trajectory, J before, J after, evaluations).  Only where the sequence is resident on the model's
     device: a numpy form of pm and D of its own is out of scope (so3.spline_evaluate has no Jacobian).  The end of the ascent depends on the last bits of
-    J: a model that stands for several ranks brings its own refine_contrast, which leaves every rank with the same trajectory."""
+    J: a model that stands for several ranks brings its own refine_contrast, which leaves every rank with the same trajectory.
+    levels with more than one entry: coarse to fine (io.refine_contrast_pyramid) — J before and after at level 0, the evaluations over all
+    levels.  (0,) makes the calls it made before there were levels."""
     if not (resident_sequence and hasattr(model, "contrast_gradient")):
         raise ValueError("refine_contrast needs a model with the event sequence resident on its device (LEGM.set_sequence, contrast_gradient)")
+    levels = tuple(int(l) for l in levels)
+    pyramid = levels != (0,)
     if hasattr(model, "refine_contrast"):      # a host over several ranks: one rank's loop, its result on all of them (sharded.ShardedLEGM.refine_contrast)
+        if pyramid:
+            return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter), levels=levels)
         return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter))
+    if pyramid:
+        return emba_io.refine_contrast_levels(model, seg, beg, end, levels, pano_w=model.W, fix_first_pose=True, max_iter=int(max_iter))
 
     def J_and_grad(t):
         r = model.contrast_gradient(t, beg, end)
@@ -261,7 +273,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         map_init = None
         rJ0 = rJ1 = r_evals = None
         if seq.refine_contrast:      # on the events alone, before any map is solved for
-            seg, rJ0, rJ1, r_evals = refine_window_poses(model, seg, beg, end, resident_sequence, seq.contrast_iters)
+            seg, rJ0, rJ1, r_evals = refine_window_poses(model, seg, beg, end, resident_sequence, seq.contrast_iters, seq.contrast_levels)
         if first_time_window and seq.init_map == "events":
             # mapping with known poses from the zero map, at the window's initial control poses; the joint solve below then starts from the resident map
             map_init = solve_time_window(model, seg, ev_win, Gx, Gy, dataclasses.replace(ba_win, refine="map"), lm, verbose=verbose, resident=resident)

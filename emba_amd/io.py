@@ -747,3 +747,73 @@ def refine_contrast(J_and_grad, J_only, traj, fix_first_pose=True, max_iter=60, 
         if gain < tol:
             break
     return traj, hist, evals
+
+
+# ---- coarse to fine (numpy form of emba_seq_contrast_gradient_level, include/emba_hip.h): a level is the rule above on a coarser grid
+CONTRAST_MAX_LEVEL = 8      # kContrastMaxLevel (emba_amd/csrc/contrast_rule.h)
+
+
+def contrast_level(pm, D, pano_w, pano_h, level):
+    """Level `level` of the smooth contrast: (pm_l, D_l, W_l, H_l) with W_l = pano_w >> level, H_l = pano_h >> level, pm_l = pm 2^-level and D_l = D 2^-level
+    (exact scalings; D may be None) — contrast_gradient(pm_l, D_l, cp, pol, K, W_l, H_l) is then the rule of emba_seq_contrast_gradient_level.  Level 0
+    returns pm and D as they are.  ValueError, as the library refuses: a level outside [0, CONTRAST_MAX_LEVEL], a panorama not divisible by 2^level, fewer
+    than two rows left."""
+    W, H, l = int(pano_w), int(pano_h), int(level)
+    if not 0 <= l <= CONTRAST_MAX_LEVEL:
+        raise ValueError(f"level {level}: levels are 0 ... {CONTRAST_MAX_LEVEL}")
+    if W % (1 << l) or H % (1 << l):
+        raise ValueError(f"level {l}: a panorama of {W} x {H} cells is not divisible by {1 << l}")
+    if (H >> l) < 2:
+        raise ValueError(f"level {l}: {H} rows of {1 << l} leave fewer than two")
+    scale = 1.0 / (1 << l)
+    pm = np.asarray(pm, dtype=np.float64)
+    return pm * scale, (None if D is None else np.asarray(D, dtype=np.float64) * scale), W >> l, H >> l
+
+
+def check_contrast_levels(levels, pano_w):
+    """The schedule of a pyramid as a tuple of ints: strictly decreasing, ending at level 0, every level one the panorama's width is divisible by."""
+    lv = tuple(int(l) for l in levels)
+    if not lv or lv[-1] != 0:
+        raise ValueError(f"contrast levels {lv}: the schedule must end at level 0, the panorama itself")
+    for a, b in zip(lv, lv[1:]):
+        if not a > b:
+            raise ValueError(f"contrast levels {lv}: levels must be strictly decreasing, coarse to fine ({a} is followed by {b})")
+    if lv[0] > CONTRAST_MAX_LEVEL:
+        raise ValueError(f"contrast levels {lv}: levels are 0 ... {CONTRAST_MAX_LEVEL}")
+    if int(pano_w) % (1 << lv[0]):
+        raise ValueError(f"contrast levels {lv}: a panorama {int(pano_w)} cells wide is not divisible by {1 << lv[0]}")
+    return lv
+
+
+def refine_contrast_pyramid(J_and_grad_at, J_only_at, traj, levels, *, pano_w, **kw):
+    """refine_contrast coarse to fine.  J_and_grad_at(level) and J_only_at(level) return the two callables of refine_contrast for that level's contrast;
+    levels: strictly decreasing and ending at 0 (check_contrast_levels), e.g. (3, 2, 1, 0).  Each level runs refine_contrast with pano_w >> level — the
+    first trial step is step_px of THAT level's cells — and hands its trajectory to the next finer one; **kw goes to every level (fix_first_pose,
+    max_iter, step_px, tol).  Returns (trajectory, {level: [J at the level's start, J after every accepted step]}, evaluations of J over all levels).
+    A level's J are not comparable with another level's: the histories stay apart."""
+    lv = check_contrast_levels(levels, pano_w)
+    hists, evals = {}, 0
+    for l in lv:
+        traj, hist, n = refine_contrast(J_and_grad_at(l), J_only_at(l), traj, pano_w=int(pano_w) >> l, **kw)
+        hists[l] = hist
+        evals += n
+    return traj, hists, evals
+
+
+def refine_contrast_levels(model, traj, beg, end, levels, *, pano_w, fix_first_pose=True, max_iter=60):
+    """refine_contrast_pyramid over model.contrast_gradient(..., level=l) on the events [beg, end) of the model's resident sequence: (trajectory, J at
+    level 0 before, J at level 0 after, evaluations over all levels — the one of J before included where the schedule does not start at level 0)."""
+    lv = check_contrast_levels(levels, pano_w)
+
+    def J_and_grad_at(l):
+        def f(t):
+            r = model.contrast_gradient(t, beg, end, level=l)
+            return r["J"], r["grad"]
+        return f
+
+    def J_only_at(l):
+        return lambda t: model.contrast_gradient(t, beg, end, want_grad=False, level=l)["J"]
+    extra = 0 if lv[0] == 0 else 1
+    J_before = float(J_only_at(0)(traj)) if extra else None
+    out, hists, evals = refine_contrast_pyramid(J_and_grad_at, J_only_at, traj, lv, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
+    return out, (hists[0][0] if J_before is None else J_before), hists[0][-1], evals + extra

@@ -286,25 +286,34 @@ class LEGM:
         res["pm"] = (pms[0] if single else np.concatenate(pms)) if want_pm else None
         return res
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
         """The smooth (fp64, real bilinear weights) contrast J = sum I^2 of the panorama of warped events of [beg, end) of the resident sequence along the
         linear SO(3) spline traj, and its gradient with respect to the increments of io.incremental_update (emba_seq_contrast_gradient; the rule:
         include/emba_hip.h): a dict of J (float), grad float64 [3 K] (None with want_grad=False: the gradient pass is then not launched), dropped (int),
         image float64 [pano_h, pano_w] (None without want_image), pm float64 [nn, 2] (None without want_pm), D float64 [nn, 2, 6] and cp int32 [nn] (None
-        without want_D).  io.contrast_gradient given the same pm, D and cp gives the same J, image and grad to the rounding of the sums' order."""
+        without want_D).  io.contrast_gradient given the same pm, D and cp gives the same J, image and grad to the rounding of the sums' order.
+        level > 0: the same on the grid of pano_w >> level by pano_h >> level cells (emba_seq_contrast_gradient_level) — image has that
+        shape, pm and D stay the unscaled ones, and io.contrast_gradient on io.contrast_level(pm, D, pano_w, pano_h, level) is the numpy form.  level = 0
+        goes through emba_seq_contrast_gradient as before there were levels."""
         from . import io as emba_io
         knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
         end = self.sequence_size() if end is None else int(end)
-        beg = int(beg)
+        beg, level = int(beg), int(level)
+        if level < 0:
+            raise ValueError(f"level = {level}: levels are 0, 1, ...")
         nn = max(end - beg, 0) // emba_io.PANO_BATCH * emba_io.PANO_BATCH
         J, dr = C.c_double(0.0), C.c_uint64(0)
         grad = np.zeros(3 * knots.shape[0]) if want_grad else None
-        img = np.zeros((self.H, self.W)) if want_image else None
+        img = np.zeros((self.H >> level, self.W >> level)) if want_image else None
         pm = np.zeros((nn, 2)) if want_pm else None
         D = np.zeros((nn, 2, 6)) if want_D else None
         cp = np.zeros(nn, np.int32) if want_D else None
-        self._check(self._L.emba_seq_contrast_gradient(self._ctx, beg, end, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns), 1 if signed else 0,
-                                                       C.cast(C.byref(J), _dp), _p(grad, _dp), _p(img, _dp), C.byref(dr), _p(pm, _dp), _p(D, _dp), _p(cp, _i32p)))
+        head = (self._ctx, beg, end, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns), 1 if signed else 0)
+        outs = (C.cast(C.byref(J), _dp), _p(grad, _dp), _p(img, _dp), C.byref(dr), _p(pm, _dp), _p(D, _dp), _p(cp, _i32p))
+        if level == 0:
+            self._check(self._L.emba_seq_contrast_gradient(*head, *outs))
+        else:
+            self._check(self._L.emba_seq_contrast_gradient_level(*head, level, *outs))
         return dict(J=J.value, grad=grad, dropped=dr.value, image=img, pm=pm, D=D, cp=cp)
 
     def free_sequence(self):

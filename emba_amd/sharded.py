@@ -167,33 +167,41 @@ class ShardedLEGM:
         rank's answers, so each asks its own and no collective is needed (the events of the range over the ranks: out of scope)."""
         return self.engine.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
         """emba_seq_contrast_gradient on this rank's copy of the sequence: equal copies and equal control poses, so every rank asks its own context and no
         collective is needed.  The fp64 adds arrive in no fixed order: the ranks' answers are equal to rounding, not bit for bit — fine for one call, not
         for a loop over such calls that every rank must leave with the same result: refine_contrast below."""
+        if level:      # (level 0: the call as it was before there were levels)
+            return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
         return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
 
-    def refine_contrast(self, traj, beg, end, pano_w, fix_first_pose=True, max_iter=60):
+    def refine_contrast(self, traj, beg, end, pano_w, fix_first_pose=True, max_iter=60, levels=(0,)):
         """io.refine_contrast of the control poses of traj on the events [beg, end) of the resident sequence, ONE result on every rank: (trajectory, J before,
         J after, evaluations of J).  One contrast_gradient call is equal across the ranks to rounding only, and the ascent multiplies a difference in the
         last place about tenfold per accepted step: loops run rank by rank would end at different control poses, and every rank must enter
         the window's solve with the SAME trajectory or the replicas drift apart (as with x1 in solveNormalEq).  So rank 0 alone runs the loop, on its own
-        context, and its control poses, J and evaluation count reach the others in one all-reduce (zeros from them: the sum is rank 0's values, exactly)."""
+        context, and its control poses, J and evaluation count reach the others in one all-reduce (zeros from them: the sum is rank 0's values, exactly).
+        levels with more than one entry: rank 0 runs the whole pyramid (io.refine_contrast_pyramid), J before and after at level 0, the
+        evaluations over all levels; still one all-reduce."""
         import torch
         from . import io as emba_io
         from .legm import LinearTrajectory
         K = int(traj.size())
+        levels = tuple(int(l) for l in levels)
         buf = np.zeros(4 * K + 3)
         if self.rank == 0:
             e = self.engine
-
-            def J_and_grad(t):
-                r = e.contrast_gradient(t, beg, end)
-                return r["J"], r["grad"]
-            out, hist, evals = emba_io.refine_contrast(J_and_grad, lambda t: e.contrast_gradient(t, beg, end, want_grad=False)["J"], traj,
-                                                       fix_first_pose=fix_first_pose, max_iter=int(max_iter), pano_w=pano_w)
+            if levels == (0,):
+                def J_and_grad(t):
+                    r = e.contrast_gradient(t, beg, end)
+                    return r["J"], r["grad"]
+                out, hist, evals = emba_io.refine_contrast(J_and_grad, lambda t: e.contrast_gradient(t, beg, end, want_grad=False)["J"], traj,
+                                                           fix_first_pose=fix_first_pose, max_iter=int(max_iter), pano_w=pano_w)
+                J0, J1 = hist[0], hist[-1]
+            else:
+                out, J0, J1, evals = emba_io.refine_contrast_levels(e, traj, beg, end, levels, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
             buf[:4 * K] = np.asarray(out.knots_xyzw, dtype=np.float64).reshape(-1)
-            buf[4 * K:] = hist[0], hist[-1], float(evals)
+            buf[4 * K:] = J0, J1, float(evals)
         if self.world > 1 or self.force_collectives:
             dev = self.pack.device if self.pack is not None else "cpu"
             t = torch.from_numpy(buf).to(dev)
@@ -460,12 +468,14 @@ class ShardedModel:
     def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
         return self.sh.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
+        if level:      # (level 0: the call as it was before there were levels)
+            return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
         return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
 
-    def refine_contrast(self, traj, beg, end, fix_first_pose=True, max_iter=60):
+    def refine_contrast(self, traj, beg, end, fix_first_pose=True, max_iter=60, levels=(0,)):
         """The control poses of traj refined on the events [beg, end) alone — rank 0's result on every rank (ShardedLEGM.refine_contrast)."""
-        return self.sh.refine_contrast(traj, beg, end, self.W, fix_first_pose, max_iter)
+        return self.sh.refine_contrast(traj, beg, end, self.W, fix_first_pose, max_iter, levels)
 
     def median_blur_map(self):
         self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
@@ -600,7 +610,9 @@ class HipEngine:
     def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
         return self.m.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
+        if level:      # (level 0: the call as it was before there were levels)
+            return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
         return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
 
     def median_blur_map(self):

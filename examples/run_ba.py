@@ -8,6 +8,8 @@
   python examples/run_ba.py --demo out/ --init-map events     # no front-end map: start from a zero map, solved for the map alone first
   python examples/run_ba.py --demo out/ --init-poses events --init-map events --window-size 0.3 --window-stride 0.1   # no front end at all: the raw poses
                                                   # come from the events by contrast maximisation on the device; --events E --calib C likewise
+  python examples/run_ba.py --demo out/ --init-poses identity --init-map events --refine-contrast --contrast-levels 3,2,1,0 --window-size 0.3 --window-stride 0.1
+                                                                                             # identity raw poses, the ascent coarse to fine
   python examples/run_ba.py --demo out/ --init-poses events --init-map events --refine-contrast --window-size 0.3 --window-stride 0.1   # ... and each window's
                                                   # initial control poses moved uphill on the contrast of its warped events first
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
@@ -65,7 +67,8 @@ def main():
     ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
     ap.add_argument("--init-map", default="given", choices=["given", "events"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
                     "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size")
-    ap.add_argument("--init-poses", default="given", choices=["given", "events"], help="events: no --poses is needed — the angular velocity of every slice of events is "
+    ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity"], help="identity: no --poses is needed — every raw pose is the identity "
+                    "(what a run without a front end always has; with --window-size).  events: no --poses is needed — the angular velocity of every slice of events is "
                     "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
@@ -74,7 +77,9 @@ def main():
     ap.add_argument("--event-panorama", action="store_true", help="write <out>/event_panorama.png: the events warped along the final trajectory (with --window-size)")
     ap.add_argument("--refine-contrast", action="store_true", help="before each window's solve, move the window's initial control poses uphill on the smooth contrast of "
                     "the panorama of the window's warped events — on the events alone, the window's first pose held fixed (with --window-size; DESIGN.md section 13)")
-    ap.add_argument("--contrast-iters", type=int, default=60, help="conjugate-gradient iterations of --refine-contrast per window, at the most")
+    ap.add_argument("--contrast-iters", type=int, default=60, help="conjugate-gradient iterations of --refine-contrast per window (and per level), at the most")
+    ap.add_argument("--contrast-levels", default="0", help="the schedule of --refine-contrast, coarse to fine: comma-separated levels, strictly decreasing and ending "
+                    "at 0, e.g. 3,2,1,0 — level l climbs on a panorama of cells 2^l pixels wide (DESIGN.md section 14); 0: the panorama alone")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
@@ -84,9 +89,14 @@ def main():
     if not a.demo and a.init_map == "given" and not a.map_dir:
         ap.error("--map-dir is required unless --init-map events is given")
     if not a.demo and a.init_poses == "given" and not a.poses:
-        ap.error("--poses is required unless --init-poses events is given")
-    if a.init_poses == "events" and not a.window_size:
-        ap.error("--init-poses events needs --window-size (the estimate runs on the resident sequence of a sliding-window run)")
+        ap.error("--poses is required unless --init-poses events or identity is given")
+    if a.init_poses != "given" and not a.window_size:
+        ap.error("--init-poses events / identity needs --window-size (a sliding-window run makes its control poses from the raw ones)")
+    no_front_end = a.init_poses != "given"
+    try:
+        a.contrast_levels = eio.check_contrast_levels([int(v) for v in a.contrast_levels.split(",")], 1 << eio.CONTRAST_MAX_LEVEL)
+    except ValueError as e:
+        ap.error(f"--contrast-levels: {e}")
     if (a.record_contrast or a.event_panorama or a.refine_contrast) and not a.window_size:
         ap.error("--record-contrast / --event-panorama / --refine-contrast need --window-size (they run on the resident sequence of a sliding-window run)")
     os.makedirs(a.out, exist_ok=True)
@@ -108,7 +118,7 @@ def main():
         sw, sh = int(cal["width"]), int(cal["height"])
         lut = eio.bearing_lut_from_calibration(cal["K"], cal["D"], sw, sh)
         Gx, Gy = eio.load_map(a.map_dir) if a.init_map == "given" else (np.zeros((a.pano_h, 2 * a.pano_h)), np.zeros((a.pano_h, 2 * a.pano_h)))
-        if a.init_poses == "events":
+        if no_front_end:
             # no front end: the span is the recording's, and the trajectory below only carries the timing (run_sequence makes the poses)
             whole = eio.load_events(a.events)
             t, qs = np.array([whole.t_ns[0] * 1e-9, whole.t_ns[-1] * 1e-9]), None
@@ -118,13 +128,13 @@ def main():
         t_end = a.t_end if a.t_end is not None else t[-1]
         num_cps = int(round((t_end - t_beg) / a.dt_knots)) + 1                      # trajectory.cpp:231-245
         sel = (t >= t_beg) & (t <= t_end)
-        if a.init_poses == "events":
+        if no_front_end:
             num_cps = int(np.floor((t_end - t_beg) / a.dt_knots)) + 1               # whole knot intervals inside the recording
             traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, np.tile([0.0, 0.0, 0.0, 1.0], (num_cps, 1)))
         else:
             traj = LinearTrajectory.from_seconds(t_beg, a.dt_knots, eio.fit_ctrl_poses(t[sel], qs[sel], t_beg, a.dt_knots, num_cps))
         ev_lo, ev_hi = int(t_beg * 1e9), traj.t0_ns + traj.dt_ns * (num_cps - 1) - 1
-        if a.init_poses == "events":                                               # (the file was read above: cut the same span from it)
+        if no_front_end:                                                           # (the file was read above: cut the same span from it)
             keep = (whole.t_ns >= ev_lo) & (whole.t_ns <= ev_hi)
             events = type(whole)(whole.x[keep], whole.y[keep], whole.polarity[keep], whole.t_ns[keep])
         else:
@@ -132,6 +142,10 @@ def main():
         t_end = t_beg + a.dt_knots * (num_cps - 1)
         truth, C_th = None, a.C_th
 
+    if a.init_poses == "identity":      # identity raw poses every 5 ms over the span, and the identity as the trajectory the result is compared with
+        t = np.arange(int(round(t_beg * 1e9)) - 10_000_000, int(round(t_end * 1e9)) + 10_000_001, 5_000_000, dtype=np.int64) * 1e-9
+        qs = np.tile([0.0, 0.0, 0.0, 1.0], (len(t), 1))
+        traj = LinearTrajectory(np.tile([0.0, 0.0, 0.0, 1.0], (traj.size(), 1)), traj.t0_ns, traj.dt_ns)
     H, W = Gx.shape
     if a.init_map == "events":
         Gx, Gy = np.zeros((H, W)), np.zeros((H, W))
@@ -169,9 +183,9 @@ def main():
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
                                event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
                                hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
-                               init_poses=a.init_poses, cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
+                               init_poses="events" if a.init_poses == "events" else "given", cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
                                record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
-                               contrast_iters=a.contrast_iters)
+                               contrast_iters=a.contrast_iters, contrast_levels=a.contrast_levels)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
@@ -225,7 +239,7 @@ def main():
     print(f"{res.iterations} LM iterations in {dt * 1e3:.1f} ms ({'converged' if res.converged else 'stopped'}), cost {res.cost_min:.6e}")
     if truth is not None:
         # (a run from the events alone starts at the identity, wherever the camera pointed: rotations relative to the first control pose are compared then)
-        rel = (lambda k: np.array([so3.mul(so3.inverse(k[0]), q) for q in k])) if a.init_poses == "events" else (lambda k: k)
+        rel = (lambda k: np.array([so3.mul(so3.inverse(k[0]), q) for q in k])) if no_front_end else (lambda k: k)
         err = lambda tr: np.degrees(np.mean([np.linalg.norm(so3.log(so3.mul(so3.inverse(p), q))) for p, q in zip(rel(tr.knots_xyzw), rel(truth.knots_xyzw))]))
         print(f"mean control-pose error vs ground truth: {err(traj):.4f} deg -> {err(res.traj):.4f} deg")
     eio.write_trajectory(os.path.join(a.out, "refined_traj.txt"), res.traj)

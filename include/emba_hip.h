@@ -406,6 +406,23 @@ emba_status emba_seq_contrast_gradient(emba_ctx* ctx, size_t beg, size_t end, co
                                        uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */, double* d_out /* [nn,2,6] or NULL */,
                                        int32_t* cp_out /* [nn] or NULL */);
 
+/* ---- The same contrast and gradient on a coarser grid (coarse to fine: the ascent of the control poses climbs first where the objective's features are
+ * 2^level pixels wide).  Level l in [0, 8] is the rule of emba_seq_contrast_gradient on a grid of W_l = pano_w >> l by H_l = pano_h >> l
+ * cells with the vote coordinate pm_l = pm 2^-l and D_l = D 2^-l, both exact scalings: floor, the four weights and their derivatives, the column wrap
+ * (modulo W_l), the rows dropped and counted (outside [0, H_l)), a pm that is not finite, the polarity signs, ge and where it is added are those of that
+ * rule with W_l, H_l for pano_w, pano_h.  Level 0 is that rule.  A J of one level is not comparable with a J of another.
+ *   image_out         H_l * W_l doubles
+ *   pm_out, d_out     the UNSCALED pm and D of the evaluation path, as emba_seq_contrast_gradient gives them (the seam the tests pin): the numpy form is
+ *                     emba_amd.io.contrast_gradient on emba_amd.io.contrast_level(pm, D, pano_w, pano_h, level)
+ * EMBA_ERR_INVALID_ARG, outputs untouched: level outside [0, 8]; pano_w or pano_h not divisible by 2^level; H_l < 2.  Everything else — the other
+ * arguments, statuses, NULL outputs, the empty range, what is left alone, timer slot 7 — as emba_seq_contrast_gradient.  An image of at most 8 192 cells is
+ * summed in LDS by a fixed grid of persistent workgroups and only their non-zero cells are added in HBM; a larger one takes every add in HBM (option
+ * contrast_vote; emba_get_option "contrast_vote_path": what the last call took).  The formula and the plan: emba_amd/csrc/contrast_rule.h. */
+emba_status emba_seq_contrast_gradient_level(emba_ctx* ctx, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                             int32_t signed_polarity, int32_t level, double* j_out, double* grad_out /* 3K or NULL */,
+                                             double* image_out /* H_l*W_l or NULL */, uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */,
+                                             double* d_out /* [nn,2,6] or NULL */, int32_t* cp_out /* [nn] or NULL */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
@@ -591,6 +608,9 @@ emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
  *                  form (an item beyond them adds its tile to S by global atomics)
  *   poison         1 (tests) fills every NEW device allocation of the context with 0xFF bytes: a read of never-written workspace then shows as NaN / 0xFFFFFFFF
  *   solve_debug    1 prints the band statistics of a solve
+ *   contrast_vote  -1 auto | 0 | 1 the vote kernel of emba_seq_contrast_gradient_level: by the size of the level's image (at most 8 192 cells: in LDS) | every
+ *                  add in HBM | in LDS wherever the image fits.  emba_get_option "contrast_vote_path", read-only: the vote kernel of the last contrast call,
+ *                  0 HBM | 1 LDS | -1 none yet
  *   poisson        0 folded Fourier form | 1 dense sine transforms | 2 no folding;  gemm64 1 forces the 64-wide GEMM tiles */
 emba_status emba_set_option(emba_ctx* ctx, const char* name, int32_t value);
 emba_status emba_get_option(emba_ctx* ctx, const char* name, int32_t* value);
