@@ -169,6 +169,10 @@ struct OrderState {
     int tile_shape = 0; bool tile_fine = false;   // what the last tile search chose: index into kTileShapes, its finer pitch grid
     double order_per_px = 0.0, order_lead_frac = 0.0;   // what the last order decision saw (diagnostics: emba_last_order_stats)
     double order_inl_pred = 0.0;      // ... and the inlier fraction the predicted pixels give (the rule's estimate of what the pixel order pays per event)
+    // the runs of equal pair key among the record slots (sorted first slots; known unless the window has more than kGramMaxRuns), and what the pair-aligned
+    // Gram form has cut from them into d_gram_cuts: for how many streaming waves per block and which plan of gram_plan, into how many blocks (step_host.h: ensure_gram_cuts)
+    std::vector<uint32_t> run_start; bool runs_known = false;
+    int cuts_sw = 0, cuts_base_blocks = 0, cuts_blocks = 0;
 };
 
 // The words of a 64-byte status block (ord.status of the window registration and the order preparation; evseq.status of the resident sequence uses the
@@ -291,6 +295,7 @@ struct emba_ctx {
     int step_one_set = 1;      // option step_one_set = 0: emba_step alternates between two record sets like an LM loop's evaluations (A/B)
     int step_fast = 1;   // option step_fast = 0: emba_step keeps the clearing pass in front of every evaluation (A/B)
     int use_tags = 1;   // the records' tags (per slot {pano pixel, stamp}) let the Gram kernel skip dead slots without fetching them (option gram_tags = 0 disables)
+    DevBuf d_gram_cuts; std::vector<uint32_t> h_gram_cuts; bool last_gram_paired = false;   // the pair-aligned Gram form's wave ranges (OrderState); did the last Gram launch take that form
     DevBuf d_slot_key; uint32_t rec_stamp = 0;   // evaluation number stamped into the records (record_valid)
     // Two record sets (a rejected LM trial must not cost a re-evaluation).  `work` is the WORKING set: what
     // the last evaluation wrote and what formNormalEq and the solvers read.  An evaluation that would overwrite records the current normal
@@ -305,7 +310,7 @@ struct emba_ctx {
     DevBuf d_e_sorted, d_flag, d_inl_idx;
     int opt_poison = 0;          // option poison = 1 (tests): every NEW device allocation of the context is filled with 0xFF bytes
     int opt_tile_reserve = 2, opt_tile_shape = -1, opt_tile_fine = -1, opt_tile_min_events = 1650000, opt_tile_chunk = 0;   // emba_set_option: the tile order's window rule (prepare_order)
-    int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
+    int opt_gather_waves = 0, opt_chunk_order_bin = 0, opt_solve_counts = -1, opt_syrk_dense = 0, opt_syrk_lists = 0, opt_gram_sparse = -1, opt_gram_sparse_chunk = 4, opt_gram_multikey = 0, opt_syrk_min_cols = 512, opt_syrk_item_cap = 4096, opt_solve_debug = 0, opt_poisson = 0, opt_gemm64 = 0;   // emba_set_option
     int step_ep = 1;              // emba_step produces ep (what evaluateDataError returns, model.cpp:256) in every step; 0: on demand only (A/B, bench.py's no_ep block)
     DevBuf d_fblk_cnt, d_fblk_off;   // inlier-flag counts per kFlagBlk pm-order entries (win.n_fblk)
     DevBuf d_fsup;                   // ... summed per kFlagSup of those by launch A (win.n_fsup; two arrays used alternately: post.fsup_half)

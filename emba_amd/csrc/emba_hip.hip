@@ -537,6 +537,10 @@ const OptionRef kStepPrepOptions[] = {
 const OptionRef kContrastOptions[] = {
     {"contrast_vote", &emba_ctx::opt_contrast_vote, -1, 1},
 };
+// the form of the dense pixel-order Gram launch (step_rule.h: gram_paired); tests/test_gpu_gram_paired.py runs both values and asserts which form ran
+const OptionRef kGramOptions[] = {
+    {"gram_multikey", &emba_ctx::opt_gram_multikey, 0, 1},
+};
 }  // namespace
 
 emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
@@ -556,6 +560,12 @@ emba_status emba_set_option(emba_ctx* c, const char* name, int32_t value)
             return EMBA_OK;
         }
     for (const OptionRef& o : kContrastOptions)
+        if (!strcmp(o.name, name)) {
+            if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
+            c->*(o.field) = (int)value;
+            return EMBA_OK;
+        }
+    for (const OptionRef& o : kGramOptions)
         if (!strcmp(o.name, name)) {
             if (value < o.lo || value > o.hi) return fail(c, EMBA_ERR_INVALID_ARG, "option %s: %d outside [%d, %d]", name, (int)value, o.lo, o.hi);
             c->*(o.field) = (int)value;
@@ -587,6 +597,9 @@ emba_status emba_get_option(emba_ctx* c, const char* name, int32_t* value)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     if (!strcmp(name, "contrast_vote_path")) { *value = c->contrast_vote_path; return EMBA_OK; }      // read-only: the vote kernel of the last contrast call — 0 HBM, 1 LDS, -1 none yet
     for (const OptionRef& o : kContrastOptions)
+        if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
+    if (!strcmp(name, "gram_paired")) { *value = c->last_gram_paired ? 1 : 0; return EMBA_OK; }      // read-only: the last Gram launch took the pair-aligned form
+    for (const OptionRef& o : kGramOptions)
         if (!strcmp(o.name, name)) { *value = c->*(o.field); return EMBA_OK; }
     return fail(c, EMBA_ERR_INVALID_ARG, "unknown option '%s'", name);
 }

@@ -1733,6 +1733,7 @@ struct GramParams {
     int n_gram_blocks; // blocks [0, n_gram_blocks) of the grid form the Gram sums; the blocks behind them (the resident step, ep_out != nullptr) compact the
                        // residuals into the reference-order ep vector (ep_tail_block): no launch and no scan launch of their own
     const uint8_t* ep_flag; const double* ep_e; double* ep_out; const uint32_t* ep_fblk_cnt; long ep_n_pm, ep_n_fblk; const uint32_t* ep_fsup;
+    const uint32_t* wave_cuts;   // PAIRED form: [start, end) per wave slot (kGramBlock / 64 per block), each inside one pair's run of slots (step_rule.h: gram_pair_cuts)
 };
 
 // Global flush of one 16x16 tile value owned by (row, col) for the pair `key`.
@@ -1842,7 +1843,9 @@ __device__ __forceinline__ uint32_t rec_elem15_hi(double2 v)
 // GATHER (the resident one-GPU step): every block first does its slice of the list-driven active-set write + A22 | b2 gather (active_gather_*): it
 // only depends on launch A of the post-warp pair, like the Gram sums, and as a prologue it costs three short round trips instead of a launch of
 // its own with a pass over the count map (round 4, 1 M events: 27.5 + 15 us -> 34.5 us).
-template <bool TAGS, int kGramBlock, bool GATHER, bool SPARSE = false>   // TAGS: p.tag is the per-slot tag stream (pixel order); otherwise activity is decided from the records (tile order).  SPARSE (with TAGS): few slots live — stages of 128 tags, compacted
+// PAIRED (with TAGS, dense): every streaming wave has a slot range of its own inside ONE pair's run (p.wave_cuts) instead of a share of the block's window: no pair
+// change in mid-stream, so no flush but the wave's tile at its end, no key table, no LDS atomics; the block sums the tiles per pair in wave order.
+template <bool TAGS, int kGramBlock, bool GATHER, bool SPARSE = false, bool PAIRED = false>   // TAGS: p.tag is the per-slot tag stream (pixel order); otherwise activity is decided from the records (tile order).  SPARSE (with TAGS): few slots live — stages of 128 tags, compacted
 __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_blk, const ActiveWriteParams& aw)
 {
     __shared__ uint32_t s_tag[kGramKeys];
@@ -1851,8 +1854,11 @@ __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_b
     __shared__ uint32_t s_ws[kGramBlock / 64];
     __shared__ double s_wtile[(kGramBlock / 64) * 256];      // every wave's own 16 x 16 sum of its last pair (gram_wave_tile)
     __shared__ uint32_t s_wkey[kGramBlock / 64];
-    for (int i = threadIdx.x; i < kGramKeys * 256; i += kGramBlock) s_tile[i] = 0.0;
-    if (threadIdx.x < kGramKeys) s_tag[threadIdx.x] = 0xFFFFFFFFu;
+    static_assert(!PAIRED || (TAGS && !SPARSE && GRAM_WAVE_TILE), "the pair-aligned form is the dense tag-stream form with the waves' own tiles");
+    if constexpr (!PAIRED) {
+        for (int i = threadIdx.x; i < kGramKeys * 256; i += kGramBlock) s_tile[i] = 0.0;
+        if (threadIdx.x < kGramKeys) s_tag[threadIdx.x] = 0xFFFFFFFFu;
+    }
     if (threadIdx.x < kGramBlock / 64) s_wkey[threadIdx.x] = 0xFFFFFFFFu;
     // GATHER: the block's slice of the gather is the work of its first kGW waves ONLY; the others go straight to the record stream, which depends on
     // launch A's activity bits and on nothing the gather writes (round 4, late: with all 16 waves gathering first the head cost this kernel 9 us
@@ -1878,11 +1884,18 @@ __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_b
     constexpr int U = TAGS ? GRAM_U : GRAM_U_NT;   // independent 1-KiB loads (8 records each) per wave and stage
     constexpr int TS = GRAM_SPARSE_TS;             // SPARSE: tag loads (64 slots each) per wave and stage
     constexpr int kStage = SPARSE ? 64 * TS : 8 * U;
-    const int kStride = kSW * kStage;
-    const long start = gram_blk * (kGramBlock / 64) * p.chunk;
-    const long end = (start + (long)(kGramBlock / 64) * p.chunk < p.n_slots) ? start + (long)(kGramBlock / 64) * p.chunk : p.n_slots;
+    const int kStride = PAIRED ? kStage : kSW * kStage;
+    long start, end;
+    if constexpr (PAIRED) {      // the wave's own range (a gather wave reads slot 0's and does not use it)
+        const uint32_t* cut = p.wave_cuts + 2 * (gram_blk * (kGramBlock / 64) + (wv > 0 ? wv : 0));
+        start = (long)__builtin_amdgcn_readfirstlane((int)cut[0]);
+        end = (long)__builtin_amdgcn_readfirstlane((int)cut[1]);
+    } else {
+        start = gram_blk * (kGramBlock / 64) * p.chunk;
+        end = (start + (long)(kGramBlock / 64) * p.chunk < p.n_slots) ? start + (long)(kGramBlock / 64) * p.chunk : p.n_slots;
+    }
     const int len = (int)(end - start);                              // <= 16 * kGramChunk: stage offsets are 32-bit
-    const int off0 = wv * kStage;
+    const int off0 = PAIRED ? 0 : wv * kStage;
     const bool have_work = wv >= 0 && off0 < len;   // wave-uniform
     const int m = lane & 7, R = lane >> 3;
     if (have_work) {
@@ -1935,7 +1948,7 @@ __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_b
         return w;
     };
     auto consume = [&](int off, double2* x) {
-        if ((k_first == cur_key) && (k_last == cur_key)) {             // fast path: the whole stage belongs to the current pair
+        if (PAIRED || ((k_first == cur_key) && (k_last == cur_key))) {             // fast path: the whole stage belongs to the current pair
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool ok = act[u] & 1u;                               // model.cpp:396,409
@@ -2159,7 +2172,7 @@ __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_b
         };
         typedef const uint32_t __attribute__((address_space(4))) * const_u32_ptr;
         const_u32_ptr key_s = (const_u32_ptr)(uintptr_t)key0;
-        auto keys = [&](int off) { k_first = key_s[off]; k_last = key_s[(off + 8 * U < len ? off + 8 * U : len) - 1]; };
+        auto keys = [&](int off) { if constexpr (!PAIRED) { k_first = key_s[off]; k_last = key_s[(off + 8 * U < len ? off + 8 * U : len) - 1]; } };
         // iteration i: Tb = tags of stage i+1 (here), Tn = tags of stage i+2 (arriving), W = activity words of stage i+1 (arriving)
         static_assert(8 * U <= 64, "a stage's live mask is one wave ballot");
         unsigned long long Mc; uint32_t W;
@@ -2263,6 +2276,7 @@ __device__ __forceinline__ void gram_body(const GramParams& p, const long gram_b
     }  // have_work
     __syncthreads();
     // block-level flush of the combine table: entry (k, row, col) by thread k*256 + row*16 + col
+    if constexpr (!PAIRED)
     for (int i = threadIdx.x; i < kGramKeys * 256; i += kGramBlock) {
         const uint32_t key = s_tag[i >> 8];
         if (key != 0xFFFFFFFFu) gram_atomic_out(s_tile[i], (i >> 4) & 15, i & 15, key, p.A11, p.b1, p.dim, p.ablate);
@@ -2348,11 +2362,11 @@ __device__ __forceinline__ void ep_tail_block(long cb, const GramParams& p)
     // 100 M + 453 vs + 460: the compaction moves 17 B per event at 3.7-4 TB/s either way, next to a Gram kernel that is itself bandwidth-bound)
 }
 
-template <bool TAGS, bool GATHER, bool SPARSE = false>
+template <bool TAGS, bool GATHER, bool SPARSE = false, bool PAIRED = false>
 __global__ __launch_bounds__(kGramBlock) void emba_gram_kernel(GramParams p, ActiveWriteParams aw)
 {
     if ((int)blockIdx.x >= p.n_gram_blocks) { ep_tail_block((long)blockIdx.x - p.n_gram_blocks, p); return; }      // (block-uniform)
-    gram_body<TAGS, kGramBlock, GATHER, SPARSE>(p, blockIdx.x, aw);
+    gram_body<TAGS, kGramBlock, GATHER, SPARSE, PAIRED>(p, blockIdx.x, aw);
 }
 
 // A22 / b2 from the records, for the weighted (IRLS) or caller-supplied-ep cases (model.cpp:599-636); the quadratic

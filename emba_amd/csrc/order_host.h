@@ -344,6 +344,30 @@ emba_status assign_record_slots(emba_ctx* c, int K)
     return EMBA_OK;
 }
 
+// where the pair key changes among the sorted slots: the runs the pair-aligned Gram form cuts its wave ranges from (step_rule.h: gram_pair_cuts).  Once per
+// order, like the slots themselves; the starts come to the host (a few hundred words; the scan's position buffer is free again and takes them on the device).
+emba_status collect_pair_runs(emba_ctx* c)
+{
+    hipStream_t s = c->stream;
+    const size_t M = c->win.n_cand;
+    c->order.run_start.clear(); c->order.runs_known = false;
+    if (!M) return EMBA_OK;
+    emba_status st;
+    if ((st = ensure<uint32_t>(c, c->ord.pos, 1 + (size_t)kGramMaxRuns))) return st;
+    uint32_t* d_runs = c->ord.pos.as<uint32_t>();
+    HIP_TRY(c, hipMemsetAsync(d_runs, 0, 4, s));
+    hipLaunchKernelGGL(emba_pair_runs_kernel, dim3(nblocks(M)), dim3(256), 0, s, c->d_slot_key.as<uint32_t>(), (long)M, d_runs, kGramMaxRuns);
+    uint32_t n = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n, d_runs, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (!n || n > kGramMaxRuns) return EMBA_OK;
+    c->order.run_start.resize(n);
+    HIP_TRY(c, hipMemcpy(c->order.run_start.data(), d_runs + 1, (size_t)n * 4, hipMemcpyDeviceToHost));
+    std::sort(c->order.run_start.begin(), c->order.run_start.end());
+    c->order.runs_known = true;
+    return EMBA_OK;
+}
+
 // At the first evaluation of a window (and again whenever the spline timing changes): the control-pose pair of every measurement,
 // the device order (pixel order, or tile order from the panorama positions the given control poses predict) and the record slots
 // sorted by pair.  Pose-independent except for the tile binning, which only affects speed.
@@ -360,7 +384,7 @@ emba_status prepare_order(emba_ctx* c, const double* knots_host, int64_t t0, int
     if ((st = order_batch_segments(c, t0, dt, K)) || (st = choose_tile_order(c, knots_host, t0, dt, K, &choice))) return st;
     if ((st = choice.tile ? build_tile_order(c, choice) : build_pixel_order(c))) return st;
     c->win.nblk = (long)((c->win.n_sorted + kWarpNew - 1) / kWarpNew);
-    if ((st = assign_record_slots(c, K))) return st;
+    if ((st = assign_record_slots(c, K)) || (st = collect_pair_runs(c))) return st;
     // per-event outputs of the evaluations, indexed in pm-order in both orders
     if ((st = ensure<double>(c, c->d_e_sorted, ns)) || (st = ensure<uint8_t>(c, c->d_flag, ns)) || (st = ensure<int32_t>(c, c->d_inl_idx, ns))) return st;
     HIP_TRY(c, hipMemsetAsync(c->d_flag.as<uint8_t>(), 0, std::max<size_t>(ns, 1), s));

@@ -439,6 +439,15 @@ __global__ void emba_slot_assign_kernel(const uint32_t* __restrict__ keys, const
     slot_key[s] = keys[s];
 }
 
+// the slots at which the pair key changes (slot 0 included), in no order: out[0] counts them, out[1 + i] holds the first `cap` (the host sorts them; step_rule.h: gram_pair_cuts)
+__global__ void emba_pair_runs_kernel(const uint32_t* __restrict__ slot_key, long M, uint32_t* __restrict__ out, uint32_t cap)
+{
+    const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= M || (s && slot_key[s] == slot_key[s - 1])) return;
+    const uint32_t i = atomicAdd(out, 1u);
+    if (i < cap) out[1 + i] = (uint32_t)s;
+}
+
 __global__ void emba_fill_u32_kernel(uint32_t* __restrict__ p, long n, uint32_t v)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

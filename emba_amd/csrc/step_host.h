@@ -617,14 +617,31 @@ emba_status rebuild_a22_from_records(emba_ctx* c, int32_t irls, double eta)
     return EMBA_OK;
 }
 
-// the six forms of the Gram kernel: with or without the tag stream, with the gather in four of its waves, over a sparse slot stream (tags only)
-void launch_gram_form(bool tags, bool gather, bool sparse, unsigned grid, hipStream_t s, const GramParams& p, const ActiveWriteParams& aw)
+// the eight forms of the Gram kernel: with or without the tag stream, with the gather in four of its waves, over a sparse slot stream (tags only), pair-aligned (tags, dense)
+void launch_gram_form(bool tags, bool gather, bool sparse, bool paired, unsigned grid, hipStream_t s, const GramParams& p, const ActiveWriteParams& aw)
 {
 #define GRAM_FORM(...) hipLaunchKernelGGL((emba_gram_kernel<__VA_ARGS__>), dim3(grid), dim3(kGramBlock), 0, s, p, aw)
-    if (tags && sparse) { if (gather) GRAM_FORM(true, true, true); else GRAM_FORM(true, false, true); }
+    if (paired) { if (gather) GRAM_FORM(true, true, false, true); else GRAM_FORM(true, false, false, true); }
+    else if (tags && sparse) { if (gather) GRAM_FORM(true, true, true); else GRAM_FORM(true, false, true); }
     else if (tags) { if (gather) GRAM_FORM(true, true); else GRAM_FORM(true, false); }
     else { if (gather) GRAM_FORM(false, true); else GRAM_FORM(false, false); }
 #undef GRAM_FORM
+}
+
+// The wave ranges of the pair-aligned form, on the device: cut once per order and number of streaming waves (the first launch of a window; again if the
+// gather moves in or out of the launch), from the run starts prepare_order left on the host
+emba_status ensure_gram_cuts(emba_ctx* c, int n_sw, const GramPlan& base)
+{
+    OrderState& o = c->order;
+    if (o.cuts_sw == n_sw && o.cuts_base_blocks == base.n_gram_blocks) return EMBA_OK;
+    const GramPairPlan g = gram_pair_cuts(o.run_start.data(), o.run_start.size(), c->win.n_cand, n_sw, base, kGramSizes, c->h_gram_cuts);
+    emba_status st;
+    if ((st = ensure<uint32_t>(c, c->d_gram_cuts, c->h_gram_cuts.size()))) return st;
+    // (the previous table may still be read by a launch in flight, and h_gram_cuts is pageable: the copy returns when it is done)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_gram_cuts.as<uint32_t>(), c->h_gram_cuts.data(), c->h_gram_cuts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    o.cuts_sw = n_sw; o.cuts_base_blocks = base.n_gram_blocks; o.cuts_blocks = g.n_gram_blocks;
+    return EMBA_OK;
 }
 
 // A11 | b1 from the records of the working set (the head of the pack was zeroed by emba_form_active's write kernel); with it the deferred gather, in four
@@ -642,7 +659,15 @@ emba_status launch_gram(emba_ctx* c, bool ep_host, int32_t irls, double eta)
     p.ablate = c->ablate;
     const bool sparse = gram_sparse(p.tag != nullptr, c->opt_gram_sparse, c->win.P_prev, c->win.n_cand, c->eq.thres);
     const bool ep_tail = c->ev.ep_in_gram && !ep_host && c->win.n_pm;
-    const GramPlan plan = gram_plan(c->win.n_cand, sparse, c->opt_gram_sparse_chunk, c->n_cu, ep_tail, c->win.n_pm, c->opt_gather_waves, kGramSizes);
+    GramPlan plan = gram_plan(c->win.n_cand, sparse, c->opt_gram_sparse_chunk, c->n_cu, ep_tail, c->win.n_pm, c->opt_gather_waves, kGramSizes);
+    const bool paired = gram_paired(c->opt_gram_multikey, p.tag != nullptr, sparse, c->order.tile_order, c->order.runs_known, records_non_temporal(c->order.tile_order, c->win.n_cand, kRecStride));
+    if (paired) {
+        STEP_TRY(ensure_gram_cuts(c, kGramBlock / 64 - (c->post.gather_deferred ? plan.gather_waves : 0), plan));
+        p.wave_cuts = c->d_gram_cuts.as<uint32_t>();
+        plan.grid += (unsigned)(c->order.cuts_blocks - plan.n_gram_blocks);
+        plan.n_gram_blocks = c->order.cuts_blocks;
+    }
+    c->last_gram_paired = paired;
     p.chunk = plan.chunk;
     p.n_gram_blocks = plan.n_gram_blocks;
     p.gather_waves = plan.gather_waves;
@@ -655,7 +680,7 @@ emba_status launch_gram(emba_ctx* c, bool ep_host, int32_t irls, double eta)
     }
     c->ev.ep_in_gram = false;
     const ActiveWriteParams aw = c->post.gather_deferred ? c->post.gather : ActiveWriteParams{};
-    launch_gram_form(p.tag != nullptr, c->post.gather_deferred, sparse, plan.grid, s, p, aw);
+    launch_gram_form(p.tag != nullptr, c->post.gather_deferred, sparse, paired, plan.grid, s, p, aw);
     c->post.gather_deferred = false;
     if (ep_tail) c->ev.ep_valid = true;
     if (c->kernel_timing) { HIP_TRY(c, hipEventRecord(c->kt[3], s)); c->kt_accum_valid = true; c->kt_valid[c->kt_slot][1] = true; }

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <vector>
 
 // (the containment rule below is also what the active-set write evaluates on the device)
 #if defined(__HIPCC__)
@@ -155,6 +156,51 @@ inline GramPlan gram_plan(size_t n_cand, bool sparse, int opt_gram_sparse_chunk,
         g.grid += g.ep_tail_blocks;
     }
     g.gather_waves = gather_waves(opt_gather_waves);
+    return g;
+}
+
+// The pair-aligned form of the dense pixel-order Gram launch.  Slots are sorted by control-pose pair key; gram_plan's equal shares ignore where a pair's
+// run of slots starts, so a wave that meets such a start leaves the fast path (per-record keys, a flush through the block's CAS-keyed LDS table in mid-stream)
+// and a block may meet more pairs than that table holds.  Here every streaming wave is given a range inside ONE run: each wave's whole stream is the fast
+// path, its only flush is the plain-store tile at its end, and the block sums its waves' tiles per pair in wave order (a fixed order) — no LDS atomics, no
+// key table.  A window has more runs than knots (the pair of a measurement is the segment of the event AND of its predecessor on the pixel: at 1 M
+// uniform events on K = 21 158 runs, 68 of them shorter than a wave's share), which is why the unit of the cut is the wave and not the block: a tiny run costs one wave.
+// Every wave then streams a range of its own, not a share of the block's window — taken only while the records stay in the Infinity Cache
+// (records_non_temporal), and only for the dense tag-stream form in pixel order; everything else keeps the multi-key form.  opt_multikey: option gram_multikey.
+constexpr uint32_t kGramMaxRuns = 4096;   // run starts the order preparation keeps; a window with more keeps the multi-key form
+inline bool gram_paired(int opt_multikey, bool tags, bool sparse, bool tile_order, bool runs_known, bool records_nt)
+{
+    return !opt_multikey && tags && !sparse && !tile_order && runs_known && !records_nt;
+}
+// run_start: the n_runs sorted first slots of the runs (run_start[0] = 0); n_sw: streaming waves per block; base: gram_plan's plan of the same launch.
+// cuts: [start, end) per wave slot, block/64 slots per block of which the first n_sw are used.  The share is the smallest multiple of 8 with which the
+// waves fit base's blocks; past share_max (what a streaming wave of a full multi-key block walks) the grid grows instead.  A run's waves get equal shares.
+struct GramPairPlan { int share; long waves; int n_gram_blocks; };
+inline GramPairPlan gram_pair_cuts(const uint32_t* run_start, size_t n_runs, size_t n_cand, int n_sw, const GramPlan& base, const GramSizes& k, std::vector<uint32_t>& cuts)
+{
+    const long wpb = k.block / 64;
+    const long slots = (long)base.n_gram_blocks * n_sw;
+    const long share_max = ((wpb * k.chunk + n_sw - 1) / n_sw + 7) & ~7L;
+    auto run_len = [&](size_t r) { return (long)((r + 1 < n_runs ? run_start[r + 1] : (uint32_t)n_cand) - run_start[r]); };
+    auto waves_at = [&](long share) { long n = 0; for (size_t r = 0; r < n_runs; ++r) n += (run_len(r) + share - 1) / share; return n; };
+    long share = (((long)n_cand + slots - 1) / std::max<long>(slots, 1) + 7) & ~7L;
+    share = std::min(std::max<long>(share, k.chunk_min), share_max);
+    while (share < share_max && waves_at(share) > slots) share += 8;
+    GramPairPlan g{};
+    g.share = (int)share;
+    g.waves = waves_at(share);
+    g.n_gram_blocks = (int)std::max<long>(1, (g.waves + n_sw - 1) / n_sw);
+    cuts.assign((size_t)g.n_gram_blocks * wpb * 2, 0u);
+    long w = 0;
+    for (size_t r = 0; r < n_runs; ++r) {
+        const long len = run_len(r), n = (len + share - 1) / share;
+        const long each = n ? (((len + n - 1) / n + 7) & ~7L) : 0;      // (<= share: share is a multiple of 8)
+        for (long i = 0; i < n; ++i, ++w) {
+            const size_t at = (size_t)((w / n_sw) * wpb + w % n_sw) * 2;
+            cuts[at] = run_start[r] + (uint32_t)std::min(i * each, len);
+            cuts[at + 1] = run_start[r] + (uint32_t)std::min((i + 1) * each, len);
+        }
+    }
     return g;
 }
 

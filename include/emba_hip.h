@@ -597,6 +597,9 @@ emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
  *   gram_sparse    -1 auto (by the active-pixel count of the window's last equations) | 0 | 1 the Gram kernel's form for slot streams with few live records (pixel
  *                  order on a large panorama): stages of 128 tags, the live slots compacted, only their records fetched;  gram_sparse_chunk 1 ... 8 (4): its slots per wave, x 1024
  *   gather_waves   0 auto (4) | 1 | 2 | 4 waves of a Gram workgroup do its slice of the gather
+ *   gram_multikey  0 (default) the dense pixel-order Gram launch is pair-aligned while the records fit the Infinity Cache: every streaming wave's slot range lies
+ *                  inside one control-pose pair's run of slots, cut once per window | 1 the multi-key form always (equal shares of the slot range, pair changes
+ *                  in mid-stream go through the workgroup's keyed LDS table).  emba_get_option "gram_paired", read-only: the last Gram launch was pair-aligned
  *   chunk_order_bin 0 tile-order chunks longest first | 1 in bin order
  *   tile_shape     -1 auto (fewest entries + chunks) | 0 48x24 | 1 72x16 | 2 96x12 | 3 36x32: the tiled kernel's LDS tile;  tile_fine -1 auto | 0 | 1 the finer grid of tile origins;
  *                  tile_reserve 0 ... 5 (2): pixels kept free on every side of a tile when chains are cut into tile-sized segments;  tile_min_events (1650000): fewest
