@@ -214,15 +214,19 @@ struct SolveCache {
 // candidates of emba_seq_cmax_objective with their J and their images.
 struct CmaxBuffers { DevBuf omega, t_ref, j0, j, evals, cand, cand_j, cand_iwe; };
 
-// Grow-only buffers of the panorama of warped events (panorama_host.h): the int32 image [H, W]; the midpoints and the pose table of the range's batches and
-// the control poses they were evaluated from (the call's own: the registered window's are left alone); one slot per wave of the reduction; out: J, sum,
-// non-zero cells, dropped votes and the pose stage's status word; pm: the projected events, where asked for.
-struct PanoBuffers { DevBuf image, batch_t, pose, knots, slots, out, pm; };
+// Grow-only buffers of the pose stage of a range of the resident sequence (seq_range_poses, panorama_host.h): the midpoints and the pose table of the
+// range's batches and the control poses they were evaluated from (the registered window's are left alone).  One set for the panorama and the contrast
+// calls alike: each call rebuilds all three from its own arguments and synchronises the stream before it returns, so nothing in them outlives a call.
+struct SeqPoseBuffers { DevBuf batch_t, pose, knots; };
 
-// Grow-only buffers of the smooth contrast and its gradient (contrast_host.h): the fp64 image [H, W]; the midpoints, the pose table and the control poses
-// of the call (its own, like the panorama's); one slot per wave of the reduction; out: J, dropped votes, the pose stage's status word and, behind them, the
-// gradient [3 K]; pm, D, cp: the projected events, their 2x6 Jacobians and their control-pose indices, where asked for.
-struct ContrastBuffers { DevBuf image, batch_t, pose, knots, slots, out, pm, D, cp; };
+// Grow-only buffers of the panorama of warped events (panorama_host.h): the int32 image [H, W]; one slot per wave of the reduction; out: J, sum, non-zero
+// cells, dropped votes and the pose stage's status word; pm: the projected events, where asked for.
+struct PanoBuffers { DevBuf image, slots, out, pm; };
+
+// Grow-only buffers of the smooth contrast and its gradient (contrast_host.h): the fp64 image [H, W]; one slot per wave of the reduction; out: J, dropped
+// votes, the pose stage's status word and, behind them, the gradient [3 K]; pm, D, cp: the projected events, their 2x6 Jacobians and their control-pose
+// indices, where asked for.
+struct ContrastBuffers { DevBuf image, slots, out, pm, D, cp; };
 
 struct emba_ctx {
     emba_cfg cfg{};
@@ -390,6 +394,7 @@ struct emba_ctx {
     // and their images.
     emba::CmaxPinhole cmax_pin;
     CmaxBuffers cmax;
+    SeqPoseBuffers seq_pose;      // the pose stage of the two below (seq_range_poses)
     PanoBuffers pano;             // the panorama of warped events on that sequence (panorama_host.h)
     ContrastBuffers contrast;     // its smooth contrast and the gradient with respect to the control poses (contrast_host.h)
     int opt_contrast_vote = -1;   // option contrast_vote: the vote kernel of a level call — -1 by the image's size (contrast_rule.h: contrast_vote_plan), 0 HBM, 1 LDS where it fits

@@ -1,16 +1,16 @@
 // emba_amd/csrc/contrast_kernels.h — the smooth contrast of the panorama of warped events and its gradient with respect to the control poses (gfx950,
 // wave64).  The rule: contrast_rule.h, include/emba_hip.h (emba_seq_contrast_gradient), DESIGN.md §13.  Stages on one stream:
-//   * pose stage                       emba_batch_mid_kernel (order_kernels.h) and emba_pose_kernel (kernels.h) as they are, on the range's own batches and into
-//                                      this call's own tables: the pose record holds q, J1 and cp
-//   * emba_contrast_vote_kernel        one lane per event: contrast_warp, up to four return-less fp64 atomic adds into the double image in HBM
-//   * emba_contrast_grad_kernel        one lane per event: contrast_warp again (the same cells), the four I gathered, ge = 2 s gp^T D; summed per
+//   * pose stage                       seq_range_poses (panorama_host.h): the pose record of every batch of the range holds q, J1 and cp
+//   * emba_contrast_vote_kernel        one lane per event: seq_event_warp and seq_cast_votes (panorama_kernels.h) — up to four return-less fp64 atomic adds
+//                                      into the double image in HBM
+//   * emba_contrast_vote_lds_kernel    the same where the image fits LDS (contrast_vote_plan): a fixed grid of persistent workgroups, each summing a
+//                                      contiguous share of the events into an image in LDS (ds_add_f64) and then adding its non-zero cells to the image in HBM
+//   * emba_contrast_grad_kernel        one lane per event: seq_event_warp again (the same cells), the four I gathered, ge = 2 s gp^T D; summed per
 //                                      workgroup in an LDS table over the control poses the workgroup spans, then one global fp64 add per touched component
 //   * emba_contrast_reduce_kernel,     J = sum I^2 in fp64 in a fixed order: per thread -> wave shuffle -> one slot per wave, then one wave adds the slots
 //     emba_contrast_reduce_final_kernel
-// Levels (emba_seq_contrast_gradient_level, contrast_rule.h): the vote and gradient kernels' <true> instantiations vote at pm 2^-l on the
-// level's grid and multiply D by 2^-l; the <false> ones are the level-free entry point's, unchanged.  Where the level's image fits LDS:
-//   * emba_contrast_vote_lds_kernel    a fixed grid of persistent workgroups, each summing a contiguous share of the events into an image in LDS
-//                                      (ds_add_f64) and then adding its non-zero cells to the image in HBM
+// Levels (contrast_rule.h): every kernel exists once; it votes at pm 2^-l on the level's grid and multiplies D by 2^-l.  At level 0, and
+// for the level-free entry point, both are products with 1.0: exact.
 // The fp64 adds into the image and into g arrive in no fixed order: both depend on it in their last bits (compared by tolerance, never by bits).  Given the
 // image, J is deterministic.
 #pragma once
@@ -19,7 +19,7 @@
 
 #include "contrast_rule.h"
 #include "device_math.h"
-#include "kernels.h"      // kPoseStride, emba_pose_kernel
+#include "panorama_kernels.h"      // SeqEventParams, seq_event_warp, seq_cast_votes, seq_add_dropped
 
 namespace emba {
 
@@ -28,18 +28,11 @@ constexpr int kContrastReduceBlocks = 256;                                      
 constexpr int kContrastReduceSlots = kContrastReduceBlocks * (kContrastThreads / 64);   // one per wave
 
 struct ContrastParams {
-    const uint16_t* x; const uint16_t* y; const uint8_t* pol;   // the resident sequence, from the range's first event
-    const double* lut;                                          // bearing vector per sensor pixel [S, 3]
-    const double* pose;                                         // pose table of the range's batches (kPoseStride doubles each: q[4] J1[9] cp)
-    long nn;                                                    // events used: whole batches
-    int sw, W, H, K;                                            // (W, H: the grid voted on — the panorama, or the level's W_l, H_l)
-    double scale;                                               // 2^-level: read by the <true> instantiations and the LDS vote only
-    double fx, fy, cx, cy;                                      // the equirectangular camera of the context
-    int signed_polarity;
+    SeqEventParams ev;                                          // (panorama_kernels.h)
+    int W, H, K;                                                // (W, H: the grid voted on — the level's W_l, H_l)
+    double scale;                                               // 2^-level
     double* image;                                              // [H, W], zeroed on the stream in front of the vote launch
-    unsigned long long* dropped;                                // votes whose row lies outside the panorama (zeroed likewise)
     double* grad;                                               // [3 K], zeroed likewise (gradient pass)
-    double* pm_out;                                             // [nn, 2] or nullptr (vote pass)
     double* d_out;                                              // [nn, 2, 6] or nullptr (gradient pass)
     int32_t* cp_out;                                            // [nn] or nullptr (gradient pass)
 };
@@ -47,46 +40,22 @@ struct ContrastParams {
 // Everything below is compiled without contraction: the two passes must land in the same cells, and the rule header's functions are the CPU test's.
 #pragma clang fp contract(off)
 
-// Event k of the range: pm = project(R(batch k / 100) * bearing) and J23 = dpm / d(rotation increment) — quat_to_matrix, the three products and two sums of
-// the warp kernels (kernels.h) and project_chain — then contrast_vote (kScaled: at pm 2^-level on the level's grid; pm and J23 stay unscaled).  The one
-// formulation every pass calls.
-template <bool kScaled>
-__device__ __forceinline__ ContrastVotes contrast_warp(const ContrastParams& p, long k, const double* P, double* pm, double* J23)
+// The votes of an event projected to pm: at pm 2^-level on the level's grid (pm itself stays unscaled).  The one formulation every pass calls.
+__device__ __forceinline__ ContrastVotes contrast_votes_at(const ContrastParams& p, const double* pm)
 {
-    const double q[4] = {P[0], P[1], P[2], P[3]};
-    double R[9];
-    quat_to_matrix(q, R);
-    const double* bv = p.lut + 3 * ((size_t)p.y[k] * (size_t)p.sw + (size_t)p.x[k]);      // (every event was checked at its upload: inside the LUT)
-    const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
-    double rb[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
-    project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
-    if constexpr (kScaled) return contrast_vote_level(pm[0], pm[1], ContrastLevel{p.W, p.H, p.scale});
-    else return contrast_vote(pm[0], pm[1], p.W, p.H);
+    return contrast_vote_level(pm[0], pm[1], ContrastLevel{p.W, p.H, p.scale});
 }
 
-template <bool kScaled>
 __global__ __launch_bounds__(kContrastThreads) void emba_contrast_vote_kernel(ContrastParams p)
 {
     const long k = (long)blockIdx.x * kContrastThreads + threadIdx.x;
     unsigned int lost = 0;
-    if (k < p.nn) {
-        double pm[2], J23[6];      // (the Jacobian is dead code here)
-        const ContrastVotes v = contrast_warp<kScaled>(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
-        if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
-        const bool neg = p.signed_polarity && p.pol[k] == 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (v.w[i] == 0.0) continue;
-            if (v.cell[i] < 0) { ++lost; continue; }
-            atomicAdd(p.image + v.cell[i], neg ? -v.w[i] : v.w[i]);      // (the result is not used: a return-less global_atomic_add_f64)
-        }
+    if (k < p.ev.nn) {
+        double pm[2];
+        seq_event_pm(p.ev, k, pm);
+        lost = seq_cast_votes(p.ev, k, contrast_votes_at(p, pm), p.image);
     }
-    // the dropped votes of the wave in one add (every lane of the workgroup arrives here)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
-    if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
+    seq_add_dropped(p.ev, lost);
 }
 
 // The votes of a level whose image fits LDS (contrast_vote_plan).  gridDim.x persistent workgroups (contrast_lds_grid: a function of the chip, not of
@@ -97,27 +66,17 @@ __global__ __launch_bounds__(kContrastLdsThreads) void emba_contrast_vote_lds_ke
 {
     __shared__ double img[kContrastLdsCells];
     const int cells = p.W * p.H;
-    const ContrastShare sh = contrast_share(p.nn, (int)gridDim.x, (int)blockIdx.x);
+    const ContrastShare sh = contrast_share(p.ev.nn, (int)gridDim.x, (int)blockIdx.x);
     if (sh.end <= sh.beg) return;      // (uniform over the workgroup: in front of every barrier)
     for (int i = threadIdx.x; i < cells; i += kContrastLdsThreads) img[i] = 0.0;
     __syncthreads();
     unsigned int lost = 0;
     for (long k = sh.beg + threadIdx.x; k < sh.end; k += kContrastLdsThreads) {
-        double pm[2], J23[6];      // (the Jacobian is dead code here)
-        const ContrastVotes v = contrast_warp<true>(p, k, p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch), pm, J23);
-        if (p.pm_out) { p.pm_out[2 * k] = pm[0]; p.pm_out[2 * k + 1] = pm[1]; }
-        const bool neg = p.signed_polarity && p.pol[k] == 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (v.w[i] == 0.0) continue;
-            if (v.cell[i] < 0) { ++lost; continue; }
-            atomicAdd(&img[v.cell[i]], neg ? -v.w[i] : v.w[i]);      // (the result is not used: ds_add_f64)
-        }
+        double pm[2];
+        seq_event_pm(p.ev, k, pm);
+        lost += seq_cast_votes(p.ev, k, contrast_votes_at(p, pm), img);
     }
-    // the dropped votes of the wave in one add (the lanes have left the loop: every lane of the workgroup arrives here)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
-    if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped, (unsigned long long)lost);
+    seq_add_dropped(p.ev, lost);      // (the lanes have left the loop)
     __syncthreads();
     for (int i = threadIdx.x; i < cells; i += kContrastLdsThreads) {
         const double v = img[i];
@@ -130,7 +89,6 @@ __global__ __launch_bounds__(kContrastLdsThreads) void emba_contrast_vote_lds_ke
 // reduction and one lane's six LDS adds, a wave across a knot boundary by LDS atomics per lane, and then adds each touched component to g once.  A span
 // longer than the table (kContrastTableCps control poses): the lanes add to g in HBM directly.  A lane whose pose record holds no control-pose index in
 // [0, K - 2] — a batch outside the knots leaves its record unwritten, and sets the call's status word — adds nothing anywhere.
-template <bool kScaled>
 __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(ContrastParams p)
 {
     __shared__ double tab[3 * kContrastTableCps];
@@ -140,12 +98,12 @@ __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(Co
     bool live = false;
     int cp = 0;
     double ge[6] = {0, 0, 0, 0, 0, 0};
-    if (k < p.nn) {
-        const double* P = p.pose + (size_t)kPoseStride * (size_t)(k / (long)kPanoBatch);
+    if (k < p.ev.nn) {
+        double pm[2], J23[6];
+        const double* P = seq_event_warp(p.ev, k, pm, J23);
+        const ContrastVotes v = contrast_votes_at(p, pm);
         const double cpd = P[13];
         live = cpd >= 0.0 && cpd <= (double)(p.K - 2);      // (false for NaN)
-        double pm[2], J23[6];
-        const ContrastVotes v = contrast_warp<kScaled>(p, k, P, pm, J23);
         // dpm_ddrot_cp = J23 * [I - J1 | J1]   (the warp kernels' D, kernels.h)
         double D[12];
 #pragma unroll
@@ -168,16 +126,14 @@ __global__ __launch_bounds__(kContrastThreads) void emba_contrast_grad_kernel(Co
             for (int j = 0; j < 12; ++j) p.d_out[12 * k + j] = D[j];
         }
         if (p.cp_out) p.cp_out[k] = live ? (int32_t)cpd : -1;
-        if constexpr (kScaled) {      // D_l = D 2^-level (d_out above stays the unscaled D)
 #pragma unroll
-            for (int j = 0; j < 12; ++j) D[j] *= p.scale;
-        }
+        for (int j = 0; j < 12; ++j) D[j] *= p.scale;      // D_l = D 2^-level (d_out above stays the unscaled D)
         if (live) {
             cp = (int)cpd;
             double I4[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) I4[i] = v.cell[i] >= 0 ? p.image[v.cell[i]] : 0.0;
-            contrast_event_grad(v, I4, D, (p.signed_polarity && p.pol[k] == 0) ? -1.0 : 1.0, ge);
+            contrast_event_grad(v, I4, D, (p.ev.signed_polarity && p.ev.pol[k] == 0) ? -1.0 : 1.0, ge);
         }
     }
     // the wave's and the workgroup's run of control poses (every lane arrives here)

@@ -141,27 +141,14 @@ def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter, level
     contrast_gradient), the first pose held fixed: (trajectory, J before, J after, evaluations).  Only where the sequence is resident on the model's
     device: a numpy form of pm and D of its own is out of scope (so3.spline_evaluate has no Jacobian).  The end of the ascent depends on the last bits of
     J: a model that stands for several ranks brings its own refine_contrast, which leaves every rank with the same trajectory.
-    levels with more than one entry: coarse to fine (io.refine_contrast_pyramid) — J before and after at level 0, the evaluations over all
-    levels.  (0,) makes the calls it made before there were levels."""
+    levels: the schedule, coarse to fine (io.refine_contrast_levels, DESIGN.md §14) — J before and after at level 0, the evaluations over all levels;
+    (0,) is the ascent on the panorama itself."""
     if not (resident_sequence and hasattr(model, "contrast_gradient")):
         raise ValueError("refine_contrast needs a model with the event sequence resident on its device (LEGM.set_sequence, contrast_gradient)")
     levels = tuple(int(l) for l in levels)
-    pyramid = levels != (0,)
     if hasattr(model, "refine_contrast"):      # a host over several ranks: one rank's loop, its result on all of them (sharded.ShardedLEGM.refine_contrast)
-        if pyramid:
-            return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter), levels=levels)
-        return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter))
-    if pyramid:
-        return emba_io.refine_contrast_levels(model, seg, beg, end, levels, pano_w=model.W, fix_first_pose=True, max_iter=int(max_iter))
-
-    def J_and_grad(t):
-        r = model.contrast_gradient(t, beg, end)
-        return r["J"], r["grad"]
-
-    def J_only(t):
-        return model.contrast_gradient(t, beg, end, want_grad=False)["J"]
-    traj, hist, evals = emba_io.refine_contrast(J_and_grad, J_only, seg, fix_first_pose=True, max_iter=int(max_iter), pano_w=model.W)
-    return traj, hist[0], hist[-1], evals
+        return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter), levels=levels)
+    return emba_io.refine_contrast_levels(model, seg, beg, end, levels, pano_w=model.W, fix_first_pose=True, max_iter=int(max_iter))
 
 
 def _contrast(r):

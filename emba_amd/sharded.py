@@ -171,9 +171,7 @@ class ShardedLEGM:
         """emba_seq_contrast_gradient on this rank's copy of the sequence: equal copies and equal control poses, so every rank asks its own context and no
         collective is needed.  The fp64 adds arrive in no fixed order: the ranks' answers are equal to rounding, not bit for bit — fine for one call, not
         for a loop over such calls that every rank must leave with the same result: refine_contrast below."""
-        if level:      # (level 0: the call as it was before there were levels)
-            return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
-        return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
+        return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
 
     def refine_contrast(self, traj, beg, end, pano_w, fix_first_pose=True, max_iter=60, levels=(0,)):
         """io.refine_contrast of the control poses of traj on the events [beg, end) of the resident sequence, ONE result on every rank: (trajectory, J before,
@@ -190,16 +188,7 @@ class ShardedLEGM:
         levels = tuple(int(l) for l in levels)
         buf = np.zeros(4 * K + 3)
         if self.rank == 0:
-            e = self.engine
-            if levels == (0,):
-                def J_and_grad(t):
-                    r = e.contrast_gradient(t, beg, end)
-                    return r["J"], r["grad"]
-                out, hist, evals = emba_io.refine_contrast(J_and_grad, lambda t: e.contrast_gradient(t, beg, end, want_grad=False)["J"], traj,
-                                                           fix_first_pose=fix_first_pose, max_iter=int(max_iter), pano_w=pano_w)
-                J0, J1 = hist[0], hist[-1]
-            else:
-                out, J0, J1, evals = emba_io.refine_contrast_levels(e, traj, beg, end, levels, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
+            out, J0, J1, evals = emba_io.refine_contrast_levels(self.engine, traj, beg, end, levels, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
             buf[:4 * K] = np.asarray(out.knots_xyzw, dtype=np.float64).reshape(-1)
             buf[4 * K:] = J0, J1, float(evals)
         if self.world > 1 or self.force_collectives:
@@ -469,9 +458,7 @@ class ShardedModel:
         return self.sh.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
     def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
-        if level:      # (level 0: the call as it was before there were levels)
-            return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
-        return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
+        return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
 
     def refine_contrast(self, traj, beg, end, fix_first_pose=True, max_iter=60, levels=(0,)):
         """The control poses of traj refined on the events [beg, end) alone — rank 0's result on every rank (ShardedLEGM.refine_contrast)."""
@@ -611,9 +598,7 @@ class HipEngine:
         return self.m.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
     def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
-        if level:      # (level 0: the call as it was before there were levels)
-            return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
-        return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D)
+        return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
 
     def median_blur_map(self):
         self.m.median_blur_map()

@@ -251,7 +251,7 @@ def test_every_rank_gets_one_refined_trajectory():
         def set_sequence(self, events, sampling_rate=1):
             return 0
 
-        def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+        def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
             self.calls += 1
             w = np.array([so3.log(so3.mul(target, so3.inverse(q))) for q in traj.knots_xyzw])      # exp(x) q = target at x = w
             J = self.scale * float(np.exp(-50.0 * (w * w).sum(axis=1)).sum())
@@ -319,7 +319,7 @@ def test_sharded_hosts_forward_the_gradient():
         def bind_exchange(self, count, pack):
             pass
 
-        def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
+        def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
             calls.append((traj, beg, end, signed, want_grad, want_image, want_pm, want_D))
             return dict(J=7.0)
     dist = SimpleNamespace(get_rank=lambda: 0, get_world_size=lambda: 2)

@@ -201,53 +201,65 @@ def test_pyramid_arguments():
             SequenceSettings(0.15, 0.1, contrast_levels=bad)
 
 
-class CountingModel:
+class LevelModel:
     """A stand-in for LEGM with the sequence resident: a smooth bump around `target` for every control pose, the same at every level, and a record of the
-    calls.  Without `levels` its contrast_gradient has the signature of before there were levels."""
+    calls."""
     W, H = W, H
     target = so3.exp(np.array([0.02, -0.05, 0.01]))
 
     def __init__(self):
         self.calls = []
 
+    def bind_exchange(self, count, pack):
+        pass
+
     def _answer(self, traj, want_grad):
         w = np.array([so3.log(so3.mul(self.target, so3.inverse(q))) for q in traj.knots_xyzw])
         e = np.exp(-50.0 * (w * w).sum(axis=1))
         return dict(J=float(e.sum()), grad=(100.0 * w * e[:, None]).reshape(-1) if want_grad else None)
 
-
-class OldModel(CountingModel):
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False):
-        self.calls.append((beg, end, want_grad))
-        return self._answer(traj, want_grad)
-
-
-class LevelModel(CountingModel):
     def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
         self.calls.append((beg, end, want_grad, level))
         return self._answer(traj, want_grad)
 
 
+# What refine_window_poses(model, start, 10, 990, True, 20) and ShardedLEGM.refine_contrast(start, 10, 990, W, True, 20) asked this stand-in, and what both
+# returned, at the commit before the level-free branches went (recorded there, with no level argument in any call).  G: J and gradient, J: J alone.
+PARENT_CALLS = "GJGJGJJJGJJJJJJGJJJGJJJJG"
+PARENT_KNOTS = [[0.0, 0.0, 0.0, 1.0],
+                [0.010007971225612203, -0.02501992806403051, 0.005003985612806102, 0.9996243313563377],
+                [0.010007971225612203, -0.02501992806403051, 0.005003985612806102, 0.9996243313563377]]
+PARENT_J = (2.5821239292751734, 2.860707721143072)
+
+
 def test_the_default_schedule_makes_the_calls_it_made():
-    """Under contrast_levels = (0,) refine_window_poses asks the model exactly what io.refine_contrast over contrast_gradient asked before there were
-    levels — no level argument at all (a model whose contrast_gradient does not know the word still works), the same calls in the same order, the same
-    result.  With two levels: the level-0 J before, then level 1, then level 0; evaluations over both."""
+    """Under contrast_levels = (0,) driver.refine_window_poses and ShardedLEGM.refine_contrast ask the model what they asked before (0,) ran through
+    io.refine_contrast_levels — the same ranges and want_grad in the same order, now at level 0 — and return the same tuple: the recorded one, and bit
+    for bit what io.refine_contrast over contrast_gradient gives here.  With two levels: the level-0 J before, then level 1, then level 0; evaluations
+    over both."""
+    from types import SimpleNamespace
     from emba_amd.driver import SequenceSettings, refine_window_poses
+    from emba_amd.sharded import ShardedLEGM
     start = LinearTrajectory(np.tile([0.0, 0.0, 0.0, 1.0], (3, 1)), 0, 50_000_000)
-    old = OldModel()
-    traj, J0, J1, evals = refine_window_poses(old, start, 10, 990, True, 20, SequenceSettings(0.15, 0.1).contrast_levels)
-    ref = OldModel()
+    ref = LevelModel()
     t_ref, hist, n_ref = eio.refine_contrast(lambda t: (lambda r: (r["J"], r["grad"]))(ref.contrast_gradient(t, 10, 990)),
                                              lambda t: ref.contrast_gradient(t, 10, 990, want_grad=False)["J"], start, fix_first_pose=True, max_iter=20, pano_w=W)
-    assert old.calls == ref.calls and len(old.calls) == evals == n_ref and np.array_equal(traj.knots_xyzw, t_ref.knots_xyzw) and (J0, J1) == (hist[0], hist[-1])
-    assert np.array_equal(refine_window_poses(OldModel(), start, 10, 990, True, 20)[0].knots_xyzw, traj.knots_xyzw)      # (the argument's default)
+    one_rank = SimpleNamespace(get_rank=lambda: 0, get_world_size=lambda: 1)
+    for run in (lambda m: refine_window_poses(m, start, 10, 990, True, 20, SequenceSettings(0.15, 0.1).contrast_levels),
+                lambda m: refine_window_poses(m, start, 10, 990, True, 20),      # (the argument's default)
+                lambda m: ShardedLEGM(m, one_rank, None, None, 64).refine_contrast(start, 10, 990, W, True, 20, (0,))):
+        m = LevelModel()
+        traj, J0, J1, evals = run(m)
+        assert m.calls == [(10, 990, ch == "G", 0) for ch in PARENT_CALLS] and evals == len(PARENT_CALLS) == n_ref
+        assert np.array_equal(traj.knots_xyzw, t_ref.knots_xyzw) and (J0, J1) == (hist[0], hist[-1]) and (traj.t0_ns, traj.dt_ns) == (0, 50_000_000)
+        assert np.allclose(traj.knots_xyzw, PARENT_KNOTS, rtol=0, atol=1e-13) and (J0, J1) == pytest.approx(PARENT_J, rel=1e-13)
     m = LevelModel()
     traj2, K0, K1, evals2 = refine_window_poses(m, start, 10, 990, True, 20, (1, 0))
     levels = [c[3] for c in m.calls]
     assert len(m.calls) == evals2 and m.calls[0] == (10, 990, False, 0) and levels[1] == 1
     first0 = levels.index(0, 1)
     assert set(levels[1:first0]) == {1} and set(levels[first0:]) == {0} and first0 > 2
-    assert K0 == J0 and K1 > K0 and np.array_equal(traj2.knots_xyzw[0], start.knots_xyzw[0])
+    assert K0 == hist[0] and K1 > K0 and np.array_equal(traj2.knots_xyzw[0], start.knots_xyzw[0])
 
 
 def test_every_rank_gets_rank_0s_pyramid():
@@ -311,7 +323,7 @@ def test_every_rank_gets_rank_0s_pyramid():
 
 
 def test_sharded_hosts_forward_the_level():
-    """ShardedModel -> ShardedLEGM -> HipEngine -> the rank's model: a level arrives as it was given; level 0 is the call of before."""
+    """ShardedModel -> ShardedLEGM -> HipEngine -> the rank's model: a level arrives as it was given, level 0 like any other."""
     from types import SimpleNamespace
     from emba_amd.sharded import HipEngine, ShardedLEGM, ShardedModel
     calls = []
@@ -328,7 +340,7 @@ def test_sharded_hosts_forward_the_level():
     assert host.contrast_gradient("traj", 3, 900, True, False, True, True, True, level=2) == dict(J=7.0)
     assert calls[-1] == (("traj", 3, 900, True, False, True, True, True), dict(level=2))
     host.contrast_gradient("traj", 3, 900)
-    assert calls[-1] == (("traj", 3, 900, False, True, False, False, False), {})
+    assert calls[-1] == (("traj", 3, 900, False, True, False, False, False), dict(level=0))
     eng = HipEngine.__new__(HipEngine)
     eng.m = Device()
     eng.contrast_gradient("traj", 1, 2, level=3)

@@ -292,6 +292,35 @@ def test_poisoned_workspace(gpu, scene):
     m.close()
 
 
+@pytest.mark.parametrize("poison", [0, 1])
+def test_panorama_and_contrast_share_the_pose_stage(gpu, scene, poison):
+    """The batch times, the pose table and the control poses of the panorama and of the contrast gradient are one buffer set of the context, rebuilt by
+    every call: a contrast call with another K on a longer range that is not nested in the panorama's leaves nothing behind that a second panorama call
+    could read — it answers what the first answered, bit for bit — and what the first panorama call left does not reach the contrast call, whose pm is
+    a fresh context's.  With option poison: new memory reads as NaN, so a pose record or knot read before this call wrote it would show."""
+    ev, t6 = scene.events, scene.traj
+    t8 = turned(LinearTrajectory(np.concatenate([t6.knots_xyzw, t6.knots_xyzw[-1:], t6.knots_xyzw[-1:]]), t6.t0_ns, t6.dt_ns), [0.01, -0.02, 0.03])
+    assert t6.size() == 6 and t8.size() == 8
+    A, B = (1000, 6000), (3000, 12000)
+    m = make_legm(scene.lut)
+    m.set_option("poison", poison)
+    m.set_sequence(ev)
+    first = m.event_panorama(t6, *A, want_image=True, want_pm=True)
+    between = m.contrast_gradient(t8, *B, want_pm=True)
+    third = m.event_panorama(t6, *A, want_image=True, want_pm=True)
+    m.close()
+    assert first["J"] > 0 and first["pm"].shape == (5000, 2) and np.isfinite(first["pm"]).all()
+    for key in ("image", "pm", "J", "sum", "nonzero", "dropped"):
+        assert np.array_equal(third[key], first[key]), key
+    fresh = make_legm(scene.lut)
+    fresh.set_sequence(ev)
+    alone = fresh.contrast_gradient(t8, *B, want_pm=True)
+    fresh.close()
+    assert between["pm"].shape == (9000, 2) and np.array_equal(between["pm"], alone["pm"]) and between["dropped"] == alone["dropped"]
+    assert_close(np.array([between["J"]]), np.array([alone["J"]]), "J after a panorama call")
+    assert_close(between["grad"], alone["grad"], "grad after a panorama call")
+
+
 @pytest.fixture(scope="module")
 def device_ascent(gpu, const_rec):
     """io.refine_contrast over LEGM.contrast_gradient from the half-rate trajectory of the constant-rate recording: run once, shared."""
