@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
-// Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, solve_host.h,
-// sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, group.h); host code only.
+// Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -246,7 +246,7 @@ struct emba_ctx {
     MapPlanes map;            // the map planes and what the host knows about them
     SolveCache solve;         // what the last solve left behind
     int solve_perm_mode = -1;                               // option solve_perm (A/B): -1 auto, 0 off, 1 on
-    double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of emba_costs, written by the kernel itself
+    double* h_cost = nullptr;           // pinned: {data cost sum, reg cost sum, error word, sequence number} of the cost launch (cost_host.h), written by the kernel itself
     double* h_cost_dev = nullptr; DevBuf d_cost_acc; int cost_seq = 0;      // its device pointer; device: {data, reg} partial sums + the blocks' ticket counter (zero between calls)
     DevBuf d_x2;              // the x2 of the last solve on this context (solve.x2_resident_P)
     DevBuf d_count_own; int32_t* d_count = nullptr;
@@ -269,7 +269,6 @@ struct emba_ctx {
     DevBuf d_err2;                  // clears the NEXT evaluation's word while its own pose threads may already be setting bits of the current one)
     uint32_t eval_seq = 0;
     DevBuf d_total;                 // [0] inliers, [1] active pixels
-    DevBuf d_scalar;                // cost reductions
     std::vector<uint32_t> h_pix_starts;   // emba_get_inlier_pixel_starts of the current evaluation (ev.pix_starts_valid), for emba_get_ep_by_pixel
     void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stage_ev[2]{};   // two pinned 8-MB buffers: device -> PAGEABLE host memory in pipelined chunks (d2h_chunks)
     int* h_pinned = nullptr;        // pinned, device-visible status words the kernels write: [0] inliers [1] err [2] P [3], [4] step sequence number [5] the packed texels still cover the step's box (the step's number, else 0)

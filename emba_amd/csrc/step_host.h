@@ -332,28 +332,36 @@ emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, 
     return EMBA_OK;
 }
 
-// the warp kernel of the window's order: it stamps the working record set, marks the count map and adds into the accumulator lines
-emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
+// What every launch of a warp kernel is given: the window in its device order, the poses, the camera, the map, and where residuals, flags, records and
+// per-pixel sums live.  Everything else stays zero: launch_warp adds what one evaluation decides, emba_dump_state (readback_host.h) its dump pointers.
+WarpParams warp_params(emba_ctx* c)
 {
-    hipStream_t s = c->stream;
-    const bool tile = c->order.tile_order;
     WarpParams p{};
     p.ev_pix = c->order.d_ev_pix; p.ev_batch = c->order.d_ev_batch; p.ev_slot = c->d_ev_slot.as<uint32_t>();
-    p.ev_pm = tile ? c->d_ev_pm.as<uint32_t>() : nullptr;
+    p.ev_pm = c->order.tile_order ? c->d_ev_pm.as<uint32_t>() : nullptr;
     p.n_sorted = (long)c->win.n_sorted; p.nblk = c->win.nblk;
     p.ev_u = c->d_ev_u.as<double>(); p.ev_seg = c->d_ev_seg.as<uint16_t>();      // per entry, in both orders
     p.pose = c->d_pose.as<double>(); p.seg = c->d_seg.as<double>(); p.lut = c->d_lut.as<double>();
-    p.texel = c->ev.use_texel ? c->d_texel.as<double>() : nullptr;
-    p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() + 4 : nullptr;      // the box the texels are packed for
     p.W = c->W; p.H = c->H;
     p.Gx = c->map.Gx(); p.Gy = c->map.Gy();
     p.fx = c->fx; p.fy = c->fy; p.cx = c->cx; p.cy = c->cy;
     p.C_th = c->C_th; p.outlier_px = c->outlier_px;
     p.count = c->d_count; p.pixacc = c->d_pixacc.as<double>();
     p.rec = c->work.rec.as<double>();
+    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
+    return p;
+}
+
+// the warp kernel of the window's order: it stamps the working record set, marks the count map and adds into the accumulator lines
+emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
+{
+    hipStream_t s = c->stream;
+    const bool tile = c->order.tile_order;
+    WarpParams p = warp_params(c);
+    p.texel = c->ev.use_texel ? c->d_texel.as<double>() : nullptr;
+    p.rect_acc = (c->ev.use_texel == 3) ? c->d_rect.as<int>() + 4 : nullptr;      // the box the texels are packed for
     p.tag = (c->use_tags && !tile) ? c->work.tag.as<double>() : nullptr;
     p.rec_nt = records_non_temporal(tile, c->win.n_cand, kRecStride) ? 1 : 0;
-    p.e_sorted = c->d_e_sorted.as<double>(); p.flag = c->d_flag.as<uint8_t>();
     p.err = c->d_err;
     p.ablate = c->ablate;
     p.irls = opt.irls; p.eta = opt.eta;
@@ -831,6 +839,23 @@ extern "C" emba_status emba_step_form_active(emba_ctx* c, int32_t thres, const u
     fo.consume = (c->step_fast != 0);
     fo.global_u8 = global_counts_u8_dev;
     return form_active(c, thres, nullptr, nullptr, fo);
+}
+
+// The rejected trial wrote the other record set (set_equations_aside): back to the set and the equations it left untouched.
+extern "C" emba_status emba_trial_reject(emba_ctx* c)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->eq_in_alt) return EMBA_OK;     // nothing was evaluated since the equations were formed (or they have been re-formed)
+    HIP_TRY(c, hipSetDevice(c->device));
+    // (a trial that was only launched: its compacted residual vector and inlier numbers will never be asked for — nothing to resolve)
+    if (c->ev.ep_deferred && !c->ev.P_pending && !c->ev.inl_pending) c->ev.ep_deferred = false;
+    else if (c->ev.P_pending || c->ev.inl_pending || c->ev.ep_deferred) { emba_status st = resolve_pending(c); if (st) return st; }
+    std::swap(c->work, c->alt);
+    c->eq = c->eq_saved;
+    c->eq_in_alt = false;
+    // the per-event residuals, the count map and the per-pixel sums are the rejected trial's: formNormalEq needs a new evaluation
+    begin_evaluation(c);
+    return EMBA_OK;
 }
 
 extern "C" emba_status emba_set_cost(emba_ctx* c, int32_t irls, double eta)

@@ -9,11 +9,14 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP_SRC = os.path.join(ROOT, "emba_amd", "csrc", "emba_hip.hip")
+OPTIONS_SRC = os.path.join(ROOT, "emba_amd", "csrc", "options_host.h")
 KERNELS_H = os.path.join(ROOT, "emba_amd", "csrc", "kernels.h")
 
 _V = "test_gpu_variants.py::"
 _P = "test_gpu_parity.py::"
+_S = "test_gpu_step_prep.py::"
+_C = "test_gpu_contrast_pyramid.py::"
+_G = "test_gpu_gram_paired.py::"
 
 # option -> (values the GPU tests set, tests that set them)
 COVERED = {
@@ -42,6 +45,10 @@ COVERED = {
     "syrk_lists": ((1, 2), (_P + "test_schur_solve_under_every_form_of_the_syrk",)),
     "syrk_min_cols": ((64,), (_P + "test_schur_solve_under_every_form_of_the_syrk",)),
     "syrk_item_cap": ((8,), (_P + "test_schur_solve_under_every_form_of_the_syrk",)),
+    "step_prep": ((0, 1), (_S + "test_consecutive_steps_never_read_stale_records", _S + "test_both_forms_against_the_oracle")),
+    "step_prep_polls": ((0,), (_S + "test_waves_that_give_up_waiting_form_the_same_records",)),
+    "contrast_vote": ((-1, 0, 1), (_C + "test_forced_vote_kernel", _C + "test_wrap_and_pole_at_a_coarse_level")),
+    "gram_multikey": ((0, 1), (_G + "test_gram_forms_on_windows_that_stress_the_plan", _G + "test_window_without_candidates")),
 }
 
 # covered option -> the non-default values that select another kernel instantiation or host branch (read from the code that switches on them)
@@ -71,6 +78,10 @@ REQUIRED = {
     "syrk_lists": (1, 2),
     "syrk_min_cols": (64,),
     "syrk_item_cap": (8,),
+    "step_prep": (1,),                     # the segment records formed inside the warp launch (step_rule.h: prep_inside_warp); the library's default is 0
+    "step_prep_polls": (0,),               # nobody waits: the bounded wait's exit
+    "contrast_vote": (0, 1),               # the HBM vote forced where the image fits LDS; the LDS vote asked for where it does not (contrast_rule.h: contrast_vote_plan)
+    "gram_multikey": (1,),                 # the multi-key form of the dense pixel-order Gram launch instead of the pair-aligned one (step_rule.h: gram_paired)
 }
 
 EXEMPT = {
@@ -114,14 +125,14 @@ def tile_round(consts=None):
     return consts["kWarpNew"] * consts["kTileWaves"]
 
 
-def parse_options(path=HIP_SRC, consts=None):
-    """The kOptions table of emba_hip.hip: [{"name", "field", "lo", "hi"}] in source order."""
+def parse_options(path=OPTIONS_SRC, consts=None):
+    """The kOptions table of options_host.h: [{"name", "field", "lo", "hi", "reorders"}] in source order."""
     consts = parse_constants() if consts is None else consts
     with open(path) as f:
         block = _block(f.read(), "kOptions[] = {")
     out = []
-    for m in re.finditer(r'\{\s*"(\w+)"\s*,\s*&emba_ctx::(\w+)\s*,\s*([^,{}]+?)\s*,\s*([^,{}]+?)\s*\}', block):
-        out.append(dict(name=m.group(1), field=m.group(2), lo=_eval_int(m.group(3), consts), hi=_eval_int(m.group(4), consts)))
+    for m in re.finditer(r'\{\s*"(\w+)"\s*,\s*&emba_ctx::(\w+)\s*,\s*([^,{}]+?)\s*,\s*([^,{}]+?)\s*,\s*(true|false)\s*\}', block):
+        out.append(dict(name=m.group(1), field=m.group(2), lo=_eval_int(m.group(3), consts), hi=_eval_int(m.group(4), consts), reorders=m.group(5) == "true"))
     return out
 
 

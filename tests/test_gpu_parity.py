@@ -1000,6 +1000,47 @@ def test_costs_in_one_call(gpu, oracle_mod, cost):
     assert r == pytest.approx(oracle_mod.reg_cost(w.Gx, w.Gy, w.alpha), rel=1e-12)
 
 
+def test_cost_entry_points_share_one_launch(gpu, oracle_mod):
+    """emba_data_cost, emba_reg_cost and emba_costs are one kernel with three grids (data blocks only, regulariser blocks only, both) over one pair of device
+    accumulators and one ticket: called one after the other on one context, each value is the oracle's — a ticket or an accumulator that the launch before
+    did not put back to zero would show as a wrong or a missing answer.  regCost needs the map alone: it answers before any evaluation.  A window whose
+    evaluation has no inliers has a data term of exactly 0."""
+    w = small_workload(n_events=20000)
+    m = make_legm(w)
+    want_reg = oracle_mod.reg_cost(w.Gx, w.Gy, w.alpha)
+    m.upload_map(w.Gx, w.Gy)
+    assert m.regCost(w.alpha) == pytest.approx(want_reg, rel=1e-12)                  # no evaluation yet: nothing of a step is looked at
+    assert m.regCost(2.0 * w.alpha) == pytest.approx(2.0 * want_reg, rel=1e-12)
+    nem = np.zeros((w.pano_h, w.pano_w), dtype=np.int32)
+    ep = m.evaluateDataError(w.traj, w.Gx, w.Gy, w.events, True, nem)
+    assert ep.size > 0
+    for cost_type, a, irls in (("quadratic", 0.0, 0), ("huber", 0.1, 1), ("cauchy", 1.0, 2)):
+        want = oracle_mod.data_cost(ep, irls, a)
+        got = [m.dataCost(cost_type, a), m.costs(cost_type, a, w.alpha), m.regCost(w.alpha), m.costs(cost_type, a, w.alpha)]
+        print(cost_type, got, want, want_reg)
+        assert got[0] == pytest.approx(want, rel=1e-10)
+        assert got[2] == pytest.approx(want_reg, rel=1e-12)
+        for d, r in (got[1], got[3]):
+            assert d == pytest.approx(want, rel=1e-10) and r == pytest.approx(want_reg, rel=1e-12)
+            assert d == pytest.approx(got[0], rel=1e-12) and r == pytest.approx(got[2], rel=1e-12)
+    m.close()
+    # every event on a pixel of its own: entries to look at, no inlier among them
+    from emba_amd.legm import EventPacket
+    w = small_workload(n_events=2000)
+    i = np.arange(w.events.size())
+    w.events = EventPacket((i % w.sensor_w).astype(np.uint16), (i // w.sensor_w).astype(np.uint16), w.events.polarity, w.events.t_ns)
+    m = make_legm(w)
+    ep = m.evaluateDataError(w.traj, w.Gx, w.Gy, w.events, True, nem)
+    assert ep.size == 0
+    want_reg = oracle_mod.reg_cost(w.Gx, w.Gy, w.alpha)
+    for cost_type, a in (("quadratic", 0.0), ("huber", 0.1), ("cauchy", 1.0)):
+        assert m.dataCost(cost_type, a) == 0.0
+        d, r = m.costs(cost_type, a, w.alpha)
+        assert d == 0.0 and r == pytest.approx(want_reg, rel=1e-12)
+        assert m.regCost(w.alpha) == pytest.approx(want_reg, rel=1e-12)
+    m.close()
+
+
 @pytest.mark.parametrize("cfg", [
     dict(n_events=30000),                                       # small: 64 units of 2048 pixels over 27 Gram blocks
     dict(n_events=20000, pano_h=75, sensor=(48, 36), focal=45.0),   # 75 x 150 panorama: 11 250 pixels, neither a multiple of 2048 nor of 8

@@ -17,7 +17,7 @@ def table():
 
 
 def test_option_table_parses(table):
-    assert len(table) >= 27, sorted(table)
+    assert len(table) >= 31, sorted(table)
     for o in table.values():
         assert o["lo"] <= o["hi"], o
 
@@ -112,11 +112,11 @@ def test_tile_shapes_parse():
 
 def test_parser_names_a_new_option(tmp_path):
     """A new entry in the table (here a dummy one) is reported by name."""
-    with open(OM.HIP_SRC) as f:
+    with open(OM.OPTIONS_SRC) as f:
         src = f.read()
     head = "kOptions[] = {"
     assert src.count(head) == 1
-    p = tmp_path / "emba_hip.hip"
-    p.write_text(src.replace(head, head + '\n    {"foo", &emba_ctx::step_ep, 0, 1},'))
+    p = tmp_path / "options_host.h"
+    p.write_text(src.replace(head, head + '\n    {"foo", &emba_ctx::step_ep, 0, 1, false},'))
     names = {o["name"] for o in OM.parse_options(str(p))}
     assert "foo" in names and sorted(names - set(OM.COVERED) - set(OM.EXEMPT)) == ["foo"]

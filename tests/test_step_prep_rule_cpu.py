@@ -19,14 +19,15 @@ def test_step_prep_rules_on_the_cpu(tmp_path):
 
 
 def test_the_step_prep_options_have_their_gpu_tests():
-    """step_prep and step_prep_polls live in a table of their own (kStepPrepOptions of emba_hip.hip).  As for every option, the values that select another
-    kernel or host branch are run against a fresh context and the oracle: tests/test_gpu_step_prep.py must exist as a GPU module and set each of them."""
+    """step_prep and step_prep_polls are entries of the one option table (kOptions of options_host.h, read by tests/option_matrix.py).  As for every option,
+    the values that select another kernel or host branch are run against a fresh context and the oracle: tests/test_gpu_step_prep.py must exist as a GPU
+    module and set each of them."""
     import re
-    with open(os.path.join(ROOT, "emba_amd", "csrc", "emba_hip.hip")) as f:
-        src = f.read()
-    i = src.index("kStepPrepOptions[] = {")
-    names = re.findall(r'\{\s*"(\w+)"', src[i:src.index("};", i)])
+    import option_matrix as OM
+    names = [o["name"] for o in OM.parse_options() if o["name"].startswith("step_prep")]
     assert names == ["step_prep", "step_prep_polls"], names
+    for n in names:
+        assert all(t.startswith("test_gpu_step_prep.py::") for t in OM.COVERED[n][1]), OM.COVERED[n]
     with open(os.path.join(ROOT, "tests", "test_gpu_step_prep.py")) as f:
         text = f.read()
     assert re.search(r"\bpytest\.mark\.gpu\b", text)
