@@ -18,6 +18,7 @@
 #include "solve_kernels.h"
 #include "map_rule.h"
 #include "cmax_rule.h"
+#include "contrast_rule.h"
 
 // Owned device memory, grow-only: ensure() re-allocates only when the buffer has to grow, so that registering the next window of a sliding-window run
 // (same sizes) costs kernels, not hipMalloc / hipFree of gigabytes (measured at 100 M events: 270 ms of allocator time around 10 ms of kernels).
@@ -228,6 +229,16 @@ struct PanoBuffers { DevBuf image, slots, out, pm; };
 // indices, where asked for.
 struct ContrastBuffers { DevBuf image, slots, out, pm, D, cp; };
 
+// The priors of the smooth contrast (contrast_host.h): per level at most one image P_l [H_l, W_l] of what earlier events of the resident
+// sequence voted — present[l]: there is one; its buffer stays allocated when it is dropped (the sizes are the context's own).  out: the dropped votes per
+// level of one emba_seq_contrast_prior_add and, behind them, the pose stage's status word.  All levels together are at most 4/3 of one H x W fp64 image.
+struct ContrastPriors {
+    DevBuf image[emba::kContrastLevels], out;
+    bool present[emba::kContrastLevels] = {};
+    void drop() { for (bool& b : present) b = false; }      // the sequence was replaced or re-indexed, or emba_seq_contrast_prior_clear
+    void reset() { drop(); for (DevBuf& b : image) b.reset(); }      // emba_seq_free
+};
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -396,6 +407,7 @@ struct emba_ctx {
     SeqPoseBuffers seq_pose;      // the pose stage of the two below (seq_range_poses)
     PanoBuffers pano;             // the panorama of warped events on that sequence (panorama_host.h)
     ContrastBuffers contrast;     // its smooth contrast and the gradient with respect to the control poses (contrast_host.h)
+    ContrastPriors priors;        // what earlier events voted, per level: the image a call of emba_seq_contrast_gradient_prior starts from
     int opt_contrast_vote = -1;   // option contrast_vote: the vote kernel of a level call — -1 by the image's size (contrast_rule.h: contrast_vote_plan), 0 HBM, 1 LDS where it fits
     int contrast_vote_path = -1;  // the vote kernel the last contrast call launched: 0 HBM, 1 LDS; -1 none yet (emba_get_option "contrast_vote_path")
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)

@@ -9,6 +9,9 @@
 //                                      workgroup in an LDS table over the control poses the workgroup spans, then one global fp64 add per touched component
 //   * emba_contrast_reduce_kernel,     J = sum I^2 in fp64 in a fixed order: per thread -> wave shuffle -> one slot per wave, then one wave adds the slots
 //     emba_contrast_reduce_final_kernel
+//   * emba_contrast_prior_vote_kernel  the prior: one lane per event, ONE seq_event_warp, then the votes of every level of the call into that
+//                                      level's prior image in HBM (emba_seq_contrast_prior_add; its own launch, once per window)
+//   * emba_contrast_prior_init_kernel  image <- prior_weight P_l in the place of the zeroing, in front of either vote kernel (emba_seq_contrast_gradient_prior)
 // Levels (contrast_rule.h): every kernel exists once; it votes at pm 2^-l on the level's grid and multiplies D by 2^-l.  At level 0, and
 // for the level-free entry point, both are products with 1.0: exact.
 // The fp64 adds into the image and into g arrive in no fixed order: both depend on it in their last bits (compared by tolerance, never by bits).  Given the
@@ -82,6 +85,53 @@ __global__ __launch_bounds__(kContrastLdsThreads) void emba_contrast_vote_lds_ke
         const double v = img[i];
         if (v != 0.0) atomicAdd(p.image + i, v);
     }
+}
+
+// ---- the prior (contrast_rule.h)
+// The levels one emba_seq_contrast_prior_add votes at, by value: entry j is the j-th set level of the mask — its grid, its prior image P_l [H_l, W_l] in HBM
+// and dropped[j], the votes of that level whose row lies outside the grid (zeroed on the stream in front of the launch).  ev.dropped and ev.pm_out are not used.
+struct ContrastPriorParams {
+    SeqEventParams ev;
+    int n;                                                      // levels in use: 1 ... kContrastLevels
+    ContrastLevel lv[kContrastLevels];
+    double* image[kContrastLevels];
+    unsigned long long* dropped;                                // [n]
+};
+
+// P_l += the level-l votes of every event, for every level of the call: one lane per event, seq_event_warp ONCE per event (the spline pose, the LUT and the
+// projection are the expensive part), then per level the scaled vote (contrast_vote_level: what contrast_votes_at is) and seq_cast_votes into that level's
+// image — return-less fp64 atomics in HBM like emba_contrast_vote_kernel's.  The level loop is uniform: every lane of the wave takes part in every level's
+// count of dropped votes, one add per wave per level.
+__global__ __launch_bounds__(kContrastThreads) void emba_contrast_prior_vote_kernel(ContrastPriorParams p)
+{
+    const long k = (long)blockIdx.x * kContrastThreads + threadIdx.x;
+    const bool on = k < p.ev.nn;
+    double pm[2] = {0.0, 0.0}, J23[6];
+    if (on) seq_event_warp(p.ev, k, pm, J23);      // (the Jacobian is dead code)
+    for (int j = 0; j < p.n; ++j) {
+        unsigned int lost = 0;
+        if (on) lost = seq_cast_votes(p.ev, k, contrast_vote_level(pm[0], pm[1], p.lv[j]), p.image[j]);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) lost += __shfl_xor(lost, o);
+        if ((threadIdx.x & 63) == 0 && lost) atomicAdd(p.dropped + j, (unsigned long long)lost);
+    }
+}
+
+// image[c] = prior_weight * P_l[c]: what stands in the image in front of the votes of emba_seq_contrast_gradient_prior, in the place of the zeroing.
+// Grid-stride, two cells (16 bytes) per lane and round; an odd last cell by one lane.  Both arrays are the heads of device allocations: 16-byte aligned.
+__global__ __launch_bounds__(kContrastThreads) void emba_contrast_prior_init_kernel(const double* __restrict__ prior, double prior_weight, long cells,
+                                                                                    double* __restrict__ image)
+{
+    const long pairs = cells >> 1;
+    const double2* __restrict__ src = reinterpret_cast<const double2*>(prior);
+    double2* __restrict__ dst = reinterpret_cast<double2*>(image);
+    for (long i = (long)blockIdx.x * kContrastThreads + threadIdx.x; i < pairs; i += (long)gridDim.x * kContrastThreads) {
+        double2 v = src[i];
+        v.x = contrast_prior_cell(prior_weight, v.x);
+        v.y = contrast_prior_cell(prior_weight, v.y);
+        dst[i] = v;
+    }
+    if ((cells & 1) && blockIdx.x == 0 && threadIdx.x == 0) image[cells - 1] = contrast_prior_cell(prior_weight, prior[cells - 1]);
 }
 
 // g += the gradients of the workgroup's events.  Events are in time order, so the control-pose indices of a workgroup's 256 events are a short run

@@ -1,7 +1,8 @@
 // emba_amd/csrc/contrast_rule.h — the smooth contrast of the panorama of warped events and its gradient with respect to the control poses
 // (contrast_host.h, contrast_kernels.h), as functions of plain values: the argument checks, the bilinear votes of one projected event with their
-// derivatives, the gradient of one event, the span of control poses a workgroup's LDS table covers, and the levels of the coarse-to-fine refinement
-// (their grids, the scaled vote, the vote kernel a level takes, the shares of its persistent workgroups).
+// derivatives, the gradient of one event, the span of control poses a workgroup's LDS table covers, the levels of the coarse-to-fine refinement
+// (their grids, the scaled vote, the vote kernel a level takes, the shares of its persistent workgroups), and the prior (the level mask, the weight, the
+// cell an image starts from).
 // emba_amd.io.contrast_votes / contrast_gradient are the same rule in numpy; include/emba_hip.h (emba_seq_contrast_gradient) states it in words.
 //
 // The rule, once.  Range, batches, midpoints, pm, column wrap and pole rows are those of emba_seq_event_panorama (panorama_rule.h).  Event k projected to
@@ -152,6 +153,37 @@ EMBA_RULE_HD inline ContrastShare contrast_share(long nn, int blocks, int b)
     const long beg = (long)b * per < nn ? (long)b * per : nn;
     const long end = beg + per < nn ? beg + per : nn;
     return ContrastShare{beg, end};
+}
+
+// ---- the prior: per level at most one image P_l [H_l, W_l] of what earlier events voted.  With one, the image of a call starts as
+// prior_weight P_l instead of zero: I(c) = prior_weight P_l(c) + sum_k s_k w_kc, and J and the gradient are the rule above on that I — J = sum (lambda P + I_w)^2,
+// the window's own contrast plus twice its correlation with the prior plus a constant.  Everything about the votes is unchanged.
+constexpr int kContrastLevels = kContrastMaxLevel + 1;
+// a cell of the image in front of the votes
+EMBA_RULE_HD inline double contrast_prior_cell(double prior_weight, double p) { return prior_weight * p; }
+// the weight of a call: finite and not negative (false for NaN)
+inline bool contrast_prior_weight_ok(double prior_weight) { return prior_weight >= 0.0 && prior_weight <= 1.7976931348623157e308; }
+// the levels of emba_seq_contrast_prior_add: bit l of the mask is level l.  Refused: no bit, a bit at kContrastLevels or above, a set level the panorama
+// does not admit (*bad_level: the lowest such level; contrast_level_ok says what is wrong with it)
+enum class ContrastMaskStatus { ok, empty, bad_bit, bad_level };
+inline ContrastMaskStatus contrast_prior_mask_ok(int pano_w, int pano_h, uint32_t mask, int* bad_level = nullptr)
+{
+    if (!mask) return ContrastMaskStatus::empty;
+    if (mask >> kContrastLevels) return ContrastMaskStatus::bad_bit;
+    for (int l = 0; l < kContrastLevels; ++l) {
+        if (!((mask >> l) & 1u) || contrast_level_ok(pano_w, pano_h, l) == ContrastLevelStatus::ok) continue;
+        if (bad_level) *bad_level = l;
+        return ContrastMaskStatus::bad_level;
+    }
+    return ContrastMaskStatus::ok;
+}
+// the levels of a mask in the order the vote kernel takes them (ascending): levels[0 .. n), n returned
+inline int contrast_prior_levels(uint32_t mask, int* levels)
+{
+    int n = 0;
+    for (int l = 0; l < kContrastLevels; ++l)
+        if ((mask >> l) & 1u) levels[n++] = l;
+    return n;
 }
 
 }  // namespace emba

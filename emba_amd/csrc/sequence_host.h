@@ -27,6 +27,7 @@ extern "C" emba_status emba_seq_free(emba_ctx* c)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->evseq.reset();
+    c->priors.reset();      // (votes of that sequence's events)
     return EMBA_OK;
 }
 
@@ -48,6 +49,7 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     HIP_TRY(c, hipStreamSynchronize(s));
     const size_t rate = sampling_stride(sampling_rate), n_kept = sampled_count(n, sampling_rate);
     c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
+    c->priors.drop();                           // (the contrast priors are votes of the sequence that goes)
     emba_status st;
     if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRaw.bytes)) || (st = ensure<uint32_t>(c, c->evseq.status, kStatusWords)) ||
         (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
@@ -339,6 +341,7 @@ extern "C" emba_status emba_seq_filter(emba_ctx* c, double hot_sigma, int64_t re
     HIP_TRY(c, hipStreamSynchronize(s));
     const FilterPlan plan(n, c->S, hot_sigma, refractory_ns, support_ns, sampling_rate);
     SEQ_TRY(filter_reserve(c, plan));
+    c->priors.drop();              // (the events are re-indexed: the contrast priors are votes of the sequence as it was)
     c->evseq.have_hot = false;     // (from here on the mask is this filter's: all zero unless the hot test below runs)
     HIP_TRY(c, hipMemsetAsync(c->evseq.f_hot.p, 0, plan.S, s));
     HIP_TRY(c, hipMemsetAsync(c->evseq.f_sums.p, 0, 64, s));

@@ -57,11 +57,21 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # The schedule of that ascent, coarse to fine (io.refine_contrast_pyramid): level l climbs on a panorama of cells 2^l pixels wide
     # (LEGM.contrast_gradient(level=l)), each level for up to contrast_iters iterations, strictly decreasing and ending at 0.  (0,): the panorama alone.
     contrast_levels: tuple = (0,)
+    # The prior of that ascent (the rule: include/emba_hip.h, emba_seq_contrast_gradient_prior): before a window is refined, the events no
+    # later window will see again are voted, along the trajectory as refined so far, into the priors of every level of contrast_levels
+    # (LEGM.contrast_prior_add), and the window then climbs on the contrast of contrast_prior_weight times that prior plus its own events — what ties a window
+    # to the panorama the windows before it placed.  Needs refine_contrast.  Off by default; the first window has no prior.
+    contrast_prior: bool = False
+    contrast_prior_weight: float = 1.0
 
     def __post_init__(self):
         if self.init_poses not in ("given", "events"):
             raise ValueError(f"SequenceSettings.init_poses must be 'given' or 'events', not {self.init_poses!r}")
         self.contrast_levels = emba_io.check_contrast_levels(self.contrast_levels, 1 << emba_io.CONTRAST_MAX_LEVEL)      # (the width: checked where it is known)
+        if not (np.isfinite(self.contrast_prior_weight) and self.contrast_prior_weight >= 0):
+            raise ValueError(f"SequenceSettings.contrast_prior_weight = {self.contrast_prior_weight}: the weight of the prior is finite and not negative")
+        if self.contrast_prior and not self.refine_contrast:
+            raise ValueError("SequenceSettings.contrast_prior is the prior of the contrast refinement: it needs refine_contrast = True")
         if int(self.cmax_slice_events) < 1:
             raise ValueError(f"SequenceSettings.cmax_slice_events = {self.cmax_slice_events}: a slice has at least one event")
         if not (np.isfinite(self.cmax_omega_max) and self.cmax_omega_max > 0):
@@ -85,6 +95,8 @@ class WindowResult:
     refine_J_before: object = None  # SequenceSettings.refine_contrast: the smooth contrast of the window's events at the control poses as generated ...
     refine_J_after: object = None   # ... and at the refined ones, which became traj_init
     refine_evals: object = None     # ... and the evaluations of the contrast the ascent took (over all of SequenceSettings.contrast_levels; J before and after: at level 0)
+    prior_events: object = None     # SequenceSettings.contrast_prior: the events retired into the priors before this window was refined (0: it climbed without one;
+                                    # with one, refine_J_before / refine_J_after are the contrast against it)
 
 
 @dataclass
@@ -136,19 +148,29 @@ def panorama_of_events(model, events, traj, beg, end, resident_sequence, want_im
     return emba_io.event_panorama(events, lut, sw, sh, model.W, model.H, traj, beg, end)
 
 
-def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter, levels=(0,)):
+def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter, levels=(0,), prior_weight=None):
     """The window's initial control poses moved uphill on the smooth contrast of the window's events [beg, end) (io.refine_contrast over the model's
     contrast_gradient), the first pose held fixed: (trajectory, J before, J after, evaluations).  Only where the sequence is resident on the model's
     device: a numpy form of pm and D of its own is out of scope (so3.spline_evaluate has no Jacobian).  The end of the ascent depends on the last bits of
     J: a model that stands for several ranks brings its own refine_contrast, which leaves every rank with the same trajectory.
     levels: the schedule, coarse to fine (io.refine_contrast_levels, DESIGN.md §14) — J before and after at level 0, the evaluations over all levels;
-    (0,) is the ascent on the panorama itself."""
+    (0,) is the ascent on the panorama itself.  prior_weight: None, or the weight of the model's priors at those levels."""
     if not (resident_sequence and hasattr(model, "contrast_gradient")):
         raise ValueError("refine_contrast needs a model with the event sequence resident on its device (LEGM.set_sequence, contrast_gradient)")
     levels = tuple(int(l) for l in levels)
+    kw = {} if prior_weight is None else dict(prior_weight=float(prior_weight))      # (none: the calls made before there were priors)
     if hasattr(model, "refine_contrast"):      # a host over several ranks: one rank's loop, its result on all of them (sharded.ShardedLEGM.refine_contrast)
-        return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter), levels=levels)
-    return emba_io.refine_contrast_levels(model, seg, beg, end, levels, pano_w=model.W, fix_first_pose=True, max_iter=int(max_iter))
+        return model.refine_contrast(seg, beg, end, fix_first_pose=True, max_iter=int(max_iter), levels=levels, **kw)
+    return emba_io.refine_contrast_levels(model, seg, beg, end, levels, pano_w=model.W, fix_first_pose=True, max_iter=int(max_iter), **kw)
+
+
+def retire_events(model, knots, t0_ns, dt_ns, retired, beg, levels):
+    """SequenceSettings.contrast_prior: the events [retired, beg) of the resident sequence — those no later window sees again — voted into the model's priors
+    of `levels` along the WHOLE trajectory as it stands (the control poses refined so far, and the new window's as generated).  Returns the events added:
+    whole batches, so the rest of fewer than 100 events waits for the next window."""
+    if beg - retired < emba_io.PANO_BATCH:
+        return 0
+    return int(model.contrast_prior_add(LinearTrajectory(knots.copy(), t0_ns, dt_ns), retired, beg, levels=tuple(levels))["added"])
 
 
 def _contrast(r):
@@ -173,6 +195,10 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         raise ValueError("no raw poses: pass pose_t, pose_q or set SequenceSettings.init_poses = 'events'")
     if resident_sequence is None:
         resident_sequence = keeps_sequence(model)
+    if seq.contrast_prior and not seq.refine_contrast:
+        raise ValueError("contrast_prior is the prior of the contrast refinement: it needs refine_contrast")
+    if seq.contrast_prior and not (resident_sequence and hasattr(model, "contrast_prior_add")):
+        raise ValueError("contrast_prior needs a model with the event sequence resident on its device (LEGM.set_sequence, contrast_prior_add)")
 
     # event down-sampling, emba.cpp:281-304
     filter_stats = None
@@ -233,6 +259,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
             Gx, Gy = emba_io.median_blur3(Gx), emba_io.median_blur3(Gy)
 
     out = SequenceResult(None, [], n_seq, filter_stats, cmax)
+    retired_from = retired = None      # contrast_prior: the events [retired_from, retired) are in the priors
     while t_win_end < t_BA_end + 1_000_000:                                             # :406
         # :409 getEventSubset
         if resident_sequence:
@@ -258,9 +285,15 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
         # :450 solveTimeWindow; the map of windows 1, 2, ... is the one the previous window left on the device
         ba_win = dataclasses.replace(ba, first_time_window=first_time_window)
         map_init = None
-        rJ0 = rJ1 = r_evals = None
+        rJ0 = rJ1 = r_evals = prior_events = None
+        if seq.contrast_prior:       # what no later window sees again goes to the priors, along the whole trajectory as refined so far
+            if retired is None:
+                retired_from = retired = beg      # (nothing in front of the first window was ever placed)
+            retired += retire_events(model, knots, traj_t0_ns, traj_dt_ns, retired, beg, seq.contrast_levels)
+            prior_events = retired - retired_from
         if seq.refine_contrast:      # on the events alone, before any map is solved for
-            seg, rJ0, rJ1, r_evals = refine_window_poses(model, seg, beg, end, resident_sequence, seq.contrast_iters, seq.contrast_levels)
+            seg, rJ0, rJ1, r_evals = refine_window_poses(model, seg, beg, end, resident_sequence, seq.contrast_iters, seq.contrast_levels,
+                                                         seq.contrast_prior_weight if prior_events else None)
         if first_time_window and seq.init_map == "events":
             # mapping with known poses from the zero map, at the window's initial control poses; the joint solve below then starts from the resident map
             map_init = solve_time_window(model, seg, ev_win, Gx, Gy, dataclasses.replace(ba_win, refine="map"), lm, verbose=verbose, resident=resident)
@@ -273,7 +306,7 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
             c_final = _contrast(panorama_of_events(model, events, res.traj, beg, end, resident_sequence))
         knots[idx_cp_beg:] = res.traj.knots_xyzw                                        # :453 replaceWith
         setup_ms = model.setup_info()["set_events_ms"] if hasattr(model, "setup_info") else float("nan")
-        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init, c_init, c_final, rJ0, rJ1, r_evals))
+        out.windows.append(WindowResult(count_window, t_win_beg, t_win_end, beg, end, idx_cp_beg, seg, res, setup_ms, map_init, c_init, c_final, rJ0, rJ1, r_evals, prior_events))
         # :459-460 the latest pose: the whole trajectory 1 us before the window's end
         pose_latest = so3.spline_evaluate(knots, traj_t0_ns, traj_dt_ns, t_win_end - 1000)
         # :512-532 slideWindow

@@ -664,12 +664,14 @@ def contrast_votes(pm, pano_w, pano_h):
     return cell, w, dwx, dwy
 
 
-def contrast_gradient(pm, D, cp, pol, K, pano_w, pano_h, signed=False):
+def contrast_gradient(pm, D, cp, pol, K, pano_w, pano_h, signed=False, prior=None):
     """The smooth contrast of the panorama of warped events and its gradient, given what the warp produced: pm [n, 2], D [n, 2, 6] (dpm_ddrot_cp, J23
     [I - J1 | J1]), cp [n] (the control pose the event's spline segment begins at) and pol [n] (None: every event votes positive).  Returns a dict: image
     float64 [pano_h, pano_w], J = sum I^2, grad float64 [3 K] with respect to the increments of incremental_update (ge = 2 s gp^T D per event, gp = sum over
     the kept cells of I(c) (dwx, dwy); ge[0:3] to control pose cp, ge[3:6] to cp + 1; a component that is not finite, or an event whose cp lies outside
-    [0, K - 2], adds nothing), dropped = votes (non-zero weights) whose row lies outside the panorama.  D and cp may be None: grad is then None."""
+    [0, K - 2], adds nothing), dropped = votes (non-zero weights) whose row lies outside the panorama.  D and cp may be None: grad is then None.
+    prior: None, or an array [pano_h, pano_w] the image starts from instead of zeros — what earlier events voted, times its weight (the caller passes
+    lambda P: the numpy form of emba_seq_contrast_gradient_prior); J and the gradient are then those of that image."""
     W, H, K = int(pano_w), int(pano_h), int(K)
     cell, w, dwx, dwy = contrast_votes(pm, W, H)
     n = cell.shape[0]
@@ -677,7 +679,13 @@ def contrast_gradient(pm, D, cp, pol, K, pano_w, pano_h, signed=False):
     if signed and pol is not None:
         s = np.where(np.asarray(pol).reshape(-1)[:n] == 0, -1.0, 1.0)
     inside = cell >= 0
-    img = np.zeros(W * H)
+    if prior is None:
+        img = np.zeros(W * H)
+    else:
+        img = np.array(prior, dtype=np.float64)
+        if img.shape != (H, W):
+            raise ValueError(f"the prior has {img.shape} cells, the image {H} x {W}")
+        img = img.reshape(-1)
     np.add.at(img, cell[inside], (w * s[:, None])[inside])
     out = dict(image=img.reshape(H, W), J=float((img * img).sum()), dropped=int(np.count_nonzero(~inside & (w != 0))), grad=None)
     if D is None or cp is None:
@@ -800,19 +808,22 @@ def refine_contrast_pyramid(J_and_grad_at, J_only_at, traj, levels, *, pano_w, *
     return traj, hists, evals
 
 
-def refine_contrast_levels(model, traj, beg, end, levels, *, pano_w, fix_first_pose=True, max_iter=60):
+def refine_contrast_levels(model, traj, beg, end, levels, *, pano_w, fix_first_pose=True, max_iter=60, prior_weight=None):
     """refine_contrast_pyramid over model.contrast_gradient(..., level=l) on the events [beg, end) of the model's resident sequence: (trajectory, J at
-    level 0 before, J at level 0 after, evaluations over all levels — the one of J before included where the schedule does not start at level 0)."""
+    level 0 before, J at level 0 after, evaluations over all levels — the one of J before included where the schedule does not start at level 0).
+    prior_weight: None, or the weight of the model's priors — every call of every level then asks
+    model.contrast_gradient(..., prior_weight=prior_weight), J before and after included, and every level of the schedule needs a prior."""
     lv = check_contrast_levels(levels, pano_w)
+    kw = {} if prior_weight is None else dict(prior_weight=float(prior_weight))      # (none: the calls made before there were priors)
 
     def J_and_grad_at(l):
         def f(t):
-            r = model.contrast_gradient(t, beg, end, level=l)
+            r = model.contrast_gradient(t, beg, end, level=l, **kw)
             return r["J"], r["grad"]
         return f
 
     def J_only_at(l):
-        return lambda t: model.contrast_gradient(t, beg, end, want_grad=False, level=l)["J"]
+        return lambda t: model.contrast_gradient(t, beg, end, want_grad=False, level=l, **kw)["J"]
     extra = 0 if lv[0] == 0 else 1
     J_before = float(J_only_at(0)(traj)) if extra else None
     out, hists, evals = refine_contrast_pyramid(J_and_grad_at, J_only_at, traj, lv, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))

@@ -286,7 +286,7 @@ class LEGM:
         res["pm"] = (pms[0] if single else np.concatenate(pms)) if want_pm else None
         return res
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
         """The smooth (fp64, real bilinear weights) contrast J = sum I^2 of the panorama of warped events of [beg, end) of the resident sequence along the
         linear SO(3) spline traj, and its gradient with respect to the increments of io.incremental_update (emba_seq_contrast_gradient; the rule:
         include/emba_hip.h): a dict of J (float), grad float64 [3 K] (None with want_grad=False: the gradient pass is then not launched), dropped (int),
@@ -294,7 +294,9 @@ class LEGM:
         without want_D).  io.contrast_gradient given the same pm, D and cp gives the same J, image and grad to the rounding of the sums' order.
         level > 0: the same on the grid of pano_w >> level by pano_h >> level cells (emba_seq_contrast_gradient_level) — image has that
         shape, pm and D stay the unscaled ones, and io.contrast_gradient on io.contrast_level(pm, D, pano_w, pano_h, level) is the numpy form.  level = 0
-        goes through emba_seq_contrast_gradient as before there were levels."""
+        goes through emba_seq_contrast_gradient as before there were levels.
+        prior_weight = None: the calls above.  A number: the image starts as prior_weight times the level's prior (emba_seq_contrast_gradient_prior;
+        DESIGN.md §15; contrast_prior_add / contrast_prior_set put one there) — io.contrast_gradient(..., prior=prior_weight * P) is the numpy form."""
         from . import io as emba_io
         knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
         end = self.sequence_size() if end is None else int(end)
@@ -310,11 +312,55 @@ class LEGM:
         cp = np.zeros(nn, np.int32) if want_D else None
         head = (self._ctx, beg, end, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns), 1 if signed else 0)
         outs = (C.cast(C.byref(J), _dp), _p(grad, _dp), _p(img, _dp), C.byref(dr), _p(pm, _dp), _p(D, _dp), _p(cp, _i32p))
-        if level == 0:
+        if prior_weight is not None:
+            self._check(self._L.emba_seq_contrast_gradient_prior(*head, level, float(prior_weight), *outs))
+        elif level == 0:
             self._check(self._L.emba_seq_contrast_gradient(*head, *outs))
         else:
             self._check(self._L.emba_seq_contrast_gradient_level(*head, level, *outs))
         return dict(J=J.value, grad=grad, dropped=dr.value, image=img, pm=pm, D=D, cp=cp)
+
+    def contrast_prior_add(self, traj, beg=0, end=None, levels=(0,), signed=False):
+        """The votes of the used events of [beg, end) of the resident sequence along traj added to the priors of `levels`, one launch for all of them
+        (emba_seq_contrast_prior_add): {"added": events used, "dropped": {level: votes whose row lies outside that level's grid}}."""
+        from . import io as emba_io
+        knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
+        end = self.sequence_size() if end is None else int(end)
+        levels = tuple(int(l) for l in levels)
+        if any(not 0 <= l < 32 for l in levels):
+            raise ValueError(f"levels {levels}: levels are 0 ... {emba_io.CONTRAST_MAX_LEVEL}")
+        mask = 0
+        for l in levels:
+            mask |= 1 << l
+        added = C.c_size_t(0)
+        dropped = np.zeros(emba_io.CONTRAST_MAX_LEVEL + 1, np.uint64)
+        self._check(self._L.emba_seq_contrast_prior_add(self._ctx, int(beg), end, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns),
+                                                        1 if signed else 0, mask, C.byref(added), _p(dropped, C.POINTER(C.c_uint64))))
+        return dict(added=int(added.value), dropped={l: int(dropped[l]) for l in sorted(set(levels))})
+
+    def contrast_prior_set(self, level, image):
+        """The prior of `level` <- image [pano_h >> level, pano_w >> level]; None: no prior at that level (emba_seq_contrast_prior_set)."""
+        level = int(level)
+        if image is not None:
+            image = np.ascontiguousarray(image, dtype=np.float64)
+            if level < 0 or image.shape != (self.H >> level, self.W >> level):
+                raise ValueError(f"the prior of level {level} has {self.H >> max(level, 0)} x {self.W >> max(level, 0)} cells, not {image.shape}")
+        self._check(self._L.emba_seq_contrast_prior_set(self._ctx, level, _p(image, _dp)))
+
+    def contrast_prior_get(self, level):
+        """The prior of `level` as float64 [pano_h >> level, pano_w >> level], or None where there is none (emba_seq_contrast_prior_get)."""
+        level = int(level)
+        present = C.c_int32(0)
+        self._check(self._L.emba_seq_contrast_prior_get(self._ctx, level, None, C.byref(present)))
+        if not present.value:
+            return None
+        image = np.zeros((self.H >> level, self.W >> level))
+        self._check(self._L.emba_seq_contrast_prior_get(self._ctx, level, _p(image, _dp), C.byref(present)))
+        return image
+
+    def contrast_prior_clear(self):
+        """No prior at any level (emba_seq_contrast_prior_clear)."""
+        self._check(self._L.emba_seq_contrast_prior_clear(self._ctx))
 
     def free_sequence(self):
         self._check(self._L.emba_seq_free(self._ctx))

@@ -109,6 +109,11 @@ def _device_sync(dev):
         torch.cuda.synchronize(dev)
 
 
+def _prior_kw(prior_weight):
+    """The keyword a contrast call is forwarded with: none without a prior weight — the calls made before there were priors, argument for argument."""
+    return {} if prior_weight is None else dict(prior_weight=prior_weight)
+
+
 class ShardedLEGM:
     """LEGM over `dist` (a torch.distributed-like module: all_reduce, get_rank, get_world_size)."""
 
@@ -167,20 +172,34 @@ class ShardedLEGM:
         rank's answers, so each asks its own and no collective is needed (the events of the range over the ranks: out of scope)."""
         return self.engine.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
         """emba_seq_contrast_gradient on this rank's copy of the sequence: equal copies and equal control poses, so every rank asks its own context and no
         collective is needed.  The fp64 adds arrive in no fixed order: the ranks' answers are equal to rounding, not bit for bit — fine for one call, not
-        for a loop over such calls that every rank must leave with the same result: refine_contrast below."""
-        return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
+        for a loop over such calls that every rank must leave with the same result: refine_contrast below.  prior_weight: against this rank's own prior."""
+        return self.engine.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level, **_prior_kw(prior_weight))
 
-    def refine_contrast(self, traj, beg, end, pano_w, fix_first_pose=True, max_iter=60, levels=(0,)):
+    def contrast_prior_add(self, traj, beg=0, end=None, levels=(0,), signed=False):
+        """emba_seq_contrast_prior_add on this rank's context: every rank adds the same events along the same trajectory to its own prior (equal to
+        rounding across the ranks, like the image of one contrast_gradient call); no collective."""
+        return self.engine.contrast_prior_add(traj, beg, end, levels, signed)
+
+    def contrast_prior_set(self, level, image):
+        self.engine.contrast_prior_set(level, image)
+
+    def contrast_prior_get(self, level):
+        return self.engine.contrast_prior_get(level)
+
+    def contrast_prior_clear(self):
+        self.engine.contrast_prior_clear()
+
+    def refine_contrast(self, traj, beg, end, pano_w, fix_first_pose=True, max_iter=60, levels=(0,), prior_weight=None):
         """io.refine_contrast of the control poses of traj on the events [beg, end) of the resident sequence, ONE result on every rank: (trajectory, J before,
         J after, evaluations of J).  One contrast_gradient call is equal across the ranks to rounding only, and the ascent multiplies a difference in the
         last place about tenfold per accepted step: loops run rank by rank would end at different control poses, and every rank must enter
         the window's solve with the SAME trajectory or the replicas drift apart (as with x1 in solveNormalEq).  So rank 0 alone runs the loop, on its own
         context, and its control poses, J and evaluation count reach the others in one all-reduce (zeros from them: the sum is rank 0's values, exactly).
         levels with more than one entry: rank 0 runs the whole pyramid (io.refine_contrast_pyramid), J before and after at level 0, the
-        evaluations over all levels; still one all-reduce."""
+        evaluations over all levels; still one all-reduce.  prior_weight: rank 0's loop climbs against rank 0's prior."""
         import torch
         from . import io as emba_io
         from .legm import LinearTrajectory
@@ -188,7 +207,8 @@ class ShardedLEGM:
         levels = tuple(int(l) for l in levels)
         buf = np.zeros(4 * K + 3)
         if self.rank == 0:
-            out, J0, J1, evals = emba_io.refine_contrast_levels(self.engine, traj, beg, end, levels, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
+            out, J0, J1, evals = emba_io.refine_contrast_levels(self.engine, traj, beg, end, levels, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter),
+                                                                   **_prior_kw(prior_weight))
             buf[:4 * K] = np.asarray(out.knots_xyzw, dtype=np.float64).reshape(-1)
             buf[4 * K:] = J0, J1, float(evals)
         if self.world > 1 or self.force_collectives:
@@ -457,12 +477,24 @@ class ShardedModel:
     def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
         return self.sh.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
-        return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
+        return self.sh.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level, **_prior_kw(prior_weight))
 
-    def refine_contrast(self, traj, beg, end, fix_first_pose=True, max_iter=60, levels=(0,)):
+    def contrast_prior_add(self, traj, beg=0, end=None, levels=(0,), signed=False):
+        return self.sh.contrast_prior_add(traj, beg, end, levels, signed)
+
+    def contrast_prior_set(self, level, image):
+        self.sh.contrast_prior_set(level, image)
+
+    def contrast_prior_get(self, level):
+        return self.sh.contrast_prior_get(level)
+
+    def contrast_prior_clear(self):
+        self.sh.contrast_prior_clear()
+
+    def refine_contrast(self, traj, beg, end, fix_first_pose=True, max_iter=60, levels=(0,), prior_weight=None):
         """The control poses of traj refined on the events [beg, end) alone — rank 0's result on every rank (ShardedLEGM.refine_contrast)."""
-        return self.sh.refine_contrast(traj, beg, end, self.W, fix_first_pose, max_iter, levels)
+        return self.sh.refine_contrast(traj, beg, end, self.W, fix_first_pose, max_iter, levels, **_prior_kw(prior_weight))
 
     def median_blur_map(self):
         self.sh.median_blur_map()                            # every rank blurs its own replica: identical maps stay identical
@@ -597,8 +629,20 @@ class HipEngine:
     def event_panorama(self, traj, beg=0, end=None, signed=False, want_image=True, want_pm=False):
         return self.m.event_panorama(traj, beg, end, signed, want_image, want_pm)
 
-    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0):
-        return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level)
+    def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
+        return self.m.contrast_gradient(traj, beg, end, signed, want_grad, want_image, want_pm, want_D, level=level, **_prior_kw(prior_weight))
+
+    def contrast_prior_add(self, traj, beg=0, end=None, levels=(0,), signed=False):
+        return self.m.contrast_prior_add(traj, beg, end, levels, signed)
+
+    def contrast_prior_set(self, level, image):
+        self.m.contrast_prior_set(level, image)
+
+    def contrast_prior_get(self, level):
+        return self.m.contrast_prior_get(level)
+
+    def contrast_prior_clear(self):
+        self.m.contrast_prior_clear()
 
     def median_blur_map(self):
         self.m.median_blur_map()

@@ -12,6 +12,8 @@
                                                                                              # identity raw poses, the ascent coarse to fine
   python examples/run_ba.py --demo out/ --init-poses events --init-map events --refine-contrast --window-size 0.3 --window-stride 0.1   # ... and each window's
                                                   # initial control poses moved uphill on the contrast of its warped events first
+  python examples/run_ba.py --demo out/ --init-poses events --init-map events --refine-contrast --contrast-prior --window-size 0.3 --window-stride 0.1
+                                                  # ... against the panorama the earlier windows' events already placed
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
@@ -80,6 +82,9 @@ def main():
     ap.add_argument("--contrast-iters", type=int, default=60, help="conjugate-gradient iterations of --refine-contrast per window (and per level), at the most")
     ap.add_argument("--contrast-levels", default="0", help="the schedule of --refine-contrast, coarse to fine: comma-separated levels, strictly decreasing and ending "
                     "at 0, e.g. 3,2,1,0 — level l climbs on a panorama of cells 2^l pixels wide (DESIGN.md section 14); 0: the panorama alone")
+    ap.add_argument("--contrast-prior", action="store_true", help="with --refine-contrast: before a window is refined, the events no later window sees again are voted "
+                    "into a prior along the trajectory as refined so far, and the window climbs against it (DESIGN.md section 15)")
+    ap.add_argument("--contrast-prior-weight", type=float, default=1.0, help="the weight of that prior in the image (finite, not negative)")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
@@ -99,6 +104,10 @@ def main():
         ap.error(f"--contrast-levels: {e}")
     if (a.record_contrast or a.event_panorama or a.refine_contrast) and not a.window_size:
         ap.error("--record-contrast / --event-panorama / --refine-contrast need --window-size (they run on the resident sequence of a sliding-window run)")
+    if a.contrast_prior and not a.refine_contrast:
+        ap.error("--contrast-prior is the prior of --refine-contrast")
+    if not (np.isfinite(a.contrast_prior_weight) and a.contrast_prior_weight >= 0):
+        ap.error("--contrast-prior-weight is finite and not negative")
     os.makedirs(a.out, exist_ok=True)
 
     if a.demo:
@@ -185,7 +194,8 @@ def main():
                                hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
                                init_poses="events" if a.init_poses == "events" else "given", cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
                                record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
-                               contrast_iters=a.contrast_iters, contrast_levels=a.contrast_levels)
+                               contrast_iters=a.contrast_iters, contrast_levels=a.contrast_levels, contrast_prior=a.contrast_prior,
+                               contrast_prior_weight=a.contrast_prior_weight)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
@@ -207,7 +217,7 @@ def main():
                       f"{wr.result.iterations} LM iterations ({wr.result.reason or 'converged'}), cost {wr.result.cost_min:.6e}, set-up {wr.setup_ms:.2f} ms")
                 if wr.refine_J_before is not None:
                     print(f"window {wr.index}: control poses refined on the events alone, smooth contrast J = {wr.refine_J_before:.6e} -> {wr.refine_J_after:.6e} "
-                          f"in {wr.refine_evals} evaluations")
+                          f"in {wr.refine_evals} evaluations" + (f", against a prior of {wr.prior_events} earlier events" if wr.prior_events else ""))
                 if wr.contrast_init is not None:
                     j0, j1 = wr.contrast_init["J"], wr.contrast_final["J"]
                     print(f"window {wr.index}: contrast of the warped events J = {j0:.6e} -> {j1:.6e} (x {j1 / max(j0, 1):.4f})")

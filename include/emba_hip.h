@@ -423,6 +423,43 @@ emba_status emba_seq_contrast_gradient_level(emba_ctx* ctx, size_t beg, size_t e
                                              double* image_out /* H_l*W_l or NULL */, uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */,
                                              double* d_out /* [nn,2,6] or NULL */, int32_t* cp_out /* [nn] or NULL */);
 
+/* ---- The same contrast and gradient against what earlier events already voted: the prior (what ties a window of a sliding-window run to the panorama the
+ * windows before it placed).  A context holds, per level l in [0, 8], at most one prior image P_l of H_l x W_l doubles (H_l = pano_h >> l,
+ * W_l = pano_w >> l), absent until written.  The rule, once:
+ *   image             with a prior, the image of a call is I(c) = prior_weight * P_l(c) + sum_k s_k w_kc
+ *   contrast          J = sum_c I(c)^2: the window's own contrast, twice its correlation with prior_weight P_l, and a constant
+ *   gradient          the rule of emba_seq_contrast_gradient on that I (gp gathers I, so ge = 2 s (lambda P + I_w) . dw D)
+ * Votes, weights, derivatives, column wrap, rows dropped and counted, a pm that is not finite, polarity signs, batches of 100 and their midpoints are exactly
+ * those of emba_seq_contrast_gradient_level.  The priors are votes of the resident sequence's events: every call that replaces or re-indexes the sequence
+ * (emba_seq_upload, emba_seq_free, emba_seq_filter) drops all of them.  All levels together are at most 4/3 of one pano_h x pano_w fp64 image.
+ *
+ * emba_seq_contrast_prior_add: for every level whose bit is set in level_mask (bit l: level l), P_l += the level-l votes of the used events of [beg, end)
+ * along the trajectory — one launch, every event warped once and voted at every level; a prior that does not exist is created as zeros first (also by an
+ * empty or sub-batch range, which adds nothing).  *n_added = the events used, ((end - beg) / 100) * 100; dropped_out: NULL or 9 entries, entry l the votes of
+ * level l whose row lies outside [0, H_l) (0 for a level not in the mask).  EMBA_ERR_INVALID_ARG: level_mask 0, a bit at 9 or above, a set level the
+ * panorama does not admit (not divisible by 2^l, H_l < 2); the range, K and dt_ns checks and EMBA_ERR_STATE / EMBA_ERR_TIME_RANGE as the gradient entry
+ * points.  EMBA_ERR_TIME_RANGE, and every other refusal, leaves every prior bit for bit as it was: the pose stage's status is read before anything is voted,
+ * one synchronisation more than an evaluation takes.
+ * emba_seq_contrast_prior_set: P_level <- image_host (H_l * W_l doubles), or, with image_host NULL, no prior at that level.
+ * emba_seq_contrast_prior_get: *present = 1 / 0; where there is a prior and image_host is not NULL, its H_l * W_l doubles (else image_host is untouched).
+ * emba_seq_contrast_prior_clear: no prior at any level.  set and get: EMBA_ERR_STATE without a resident sequence, EMBA_ERR_INVALID_ARG for a level the
+ * panorama does not admit.
+ *
+ * emba_seq_contrast_gradient_prior: emba_seq_contrast_gradient_level with the rule above — every argument, output, status and the choice of the vote kernel
+ * (option contrast_vote, "contrast_vote_path") as there, timer slot 7 likewise.  EMBA_ERR_STATE, outputs untouched: no prior at that level.
+ * EMBA_ERR_INVALID_ARG: prior_weight not finite or negative.  An empty or sub-batch range is EMBA_OK with J = prior_weight^2 sum P^2, a zero gradient and
+ * image_out = prior_weight P (the image is still formed and reduced on the device).  prior_weight = 0 is the rule without a prior.  A call never changes a
+ * prior.  The numpy form: emba_amd.io.contrast_gradient(..., prior = prior_weight * P). */
+emba_status emba_seq_contrast_prior_add(emba_ctx* ctx, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                        int32_t signed_polarity, uint32_t level_mask, size_t* n_added, uint64_t* dropped_out /* [9] or NULL */);
+emba_status emba_seq_contrast_prior_set(emba_ctx* ctx, int32_t level, const double* image_host /* NULL: drop this level's prior */);
+emba_status emba_seq_contrast_prior_get(emba_ctx* ctx, int32_t level, double* image_host /* or NULL */, int32_t* present);
+emba_status emba_seq_contrast_prior_clear(emba_ctx* ctx);
+emba_status emba_seq_contrast_gradient_prior(emba_ctx* ctx, size_t beg, size_t end, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns,
+                                             int32_t signed_polarity, int32_t level, double prior_weight, double* j_out, double* grad_out /* 3K or NULL */,
+                                             double* image_out /* H_l*W_l or NULL */, uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */,
+                                             double* d_out /* [nn,2,6] or NULL */, int32_t* cp_out /* [nn] or NULL */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
