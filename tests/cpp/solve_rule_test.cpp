@@ -97,6 +97,15 @@ void check_plan()
     // ... the build's LDS, 72 n bytes: above 64 KB from n = 912 (K = 304: 65 664; K = 303: 65 448), above 160 KB from n = 2277 (K = 759: 163 944; K = 758: 163 728)
     CHECK(!syrk_plan(shape(303, 1000), 0).build_lds_raise && syrk_plan(shape(304, 1000), 0).build_lds_raise && syrk_plan(shape(304, 1000), 0).build_lds == 65664, "64 KB");
     CHECK(syrk_plan(shape(758, 1000), 0).status == kSyrkOk && syrk_plan(shape(758, 1000), 0).build_lds_raise && syrk_plan(shape(759, 1000), 0).status == kSyrkBuildLds, "160 KB");
+    // The shapes tests/test_gpu_solve_capacity.py runs on the device (tests/solve_edge_cases.py: about 1800 active pixels), with the K its constants derive from
+    // 72 x 3K bytes against 64 KB and 160 KB — one statement per edge, so that a failure names it
+    CHECK(!syrk_plan(shape(303, 1751), 0).build_lds_raise && syrk_plan(shape(303, 1751), 0).build_lds == 65448 && syrk_plan(shape(303, 1751), 0).status == kSyrkOk, "K = 303: no raise");
+    CHECK(syrk_plan(shape(304, 1751), 0).build_lds_raise && syrk_plan(shape(304, 1751), 0).status == kSyrkOk, "K = 304: the raise");
+    q = syrk_plan(shape(758, 1781), 0);      // n = 2274: 36 row blocks, 666 pairs, nks_max = (1024 + 665) / 666 = 2; 1781 pixels = 14 slices
+    CHECK(q.status == kSyrkOk && q.build_lds == 163728 && q.build_lds == 160 * 1024 - 112 && q.build_lds_raise, "K = 758: 112 bytes under the CU's LDS");
+    CHECK(q.nb64 == 36 && q.nbp == 666 && q.sparse && q.nks_max == 2 && q.n_slices == 14 && q.nks == 2 && !q.items_form, "K = 758: 36 row blocks, block-sparse");
+    CHECK(syrk_plan(shape(759, 1781), 0).status == kSyrkBuildLds && syrk_plan(shape(759, 1781), 0).build_lds == 163944, "K = 759: refused");
+    CHECK(solve_perm_size_ok(-1, 1751, 303, 128) && solve_perm_size_ok(-1, 1781, 758, 128) && !solve_perm_size_ok(-1, 511, 758, 128), "the column order's size rule decides by itself there");
 }
 
 void check_forms()
