@@ -90,6 +90,8 @@ SIGNATURES = {
     "emba_set_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "emba_reconstruct_intensity": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "emba_render_map_images": (C.c_int, [C.c_void_p, C.c_double, _u8p, _u8p, _u8p, _u8p]),
+    "emba_reconstruct_intensity_bc": (C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int32]),
+    "emba_render_map_images_bc": (C.c_int, [C.c_void_p, C.c_double, _u8p, _u8p, _u8p, _u8p, C.c_int32]),
     "emba_normalize_robust": (C.c_int, [C.c_void_p, _dp, C.c_size_t, C.c_double, _u8p, _dp, _dp]),
     "emba_seq_upload": (C.c_int, [C.c_void_p, _u16p, _u16p, _u8p, _i64p, C.c_size_t, C.c_int32, _szp]),
     "emba_seq_size": (C.c_int, [C.c_void_p, _szp]),

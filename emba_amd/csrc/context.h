@@ -379,6 +379,7 @@ struct emba_ctx {
     // f3 (Poisson reconstruction): sine matrices and eigenvalues of the two transform lengths, scratch planes
     DevBuf d_SH, d_SW, d_lamH, d_lamW, d_pF, d_pT, d_pGx, d_pGy;
     DevBuf d_thomas;              // Thomas factors of T_W + lambda1[i] I (W x H)
+    DevBuf d_wrapq;               // boundary EMBA_POISSON_WRAP_X: q = T_{W-1}^-1 (e_0 + e_{W-2}) per H-frequency (W x H, row W-1 zero; poisson_rule.h)
     DevBuf d_Sfold;               // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
     DevBuf d_pE;                  // [E | O] of the folded transform (W x H/2 each)
     // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload

@@ -3,7 +3,7 @@
 // header beside it: the context is context.h, copies into the caller's pageable memory transfer_host.h, the window and its order order_host.h / order_rule.h,
 // the step path (the evaluation and the normal equations) step_host.h / step_rule.h, the map map_host.h / map_rule.h, the downloads that wait on the step's
 // counters and emba_dump_state readback_host.h, the costs cost_host.h / cost_rule.h, the options options_host.h, the timers and probes timing_host.h, the
-// solvers (f1) solve_host.h / solve_rule.h, f3 and the record_data images render_host.h, the resident event sequence sequence_host.h / sequence_rule.h,
+// solvers (f1) solve_host.h / solve_rule.h, f3 and the record_data images render_host.h / poisson_rule.h, the resident event sequence sequence_host.h / sequence_rule.h,
 // contrast maximisation on it cmax_host.h / cmax_rule.h, the panorama of warped events panorama_host.h / panorama_rule.h and its smooth contrast and gradient
 // contrast_host.h / contrast_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "poisson_rule.h"
+
 namespace emba {
 
 typedef double pdouble4_t __attribute__((ext_vector_type(4)));
@@ -433,6 +435,57 @@ __global__ void emba_dst_butterfly_kernel(const double* __restrict__ E, const do
     const double e = E[idx], o = O[idx];
     y[row * n + k] = (e + o) * scale;
     y[row * n + (n - 1 - k)] = (e - o) * scale;
+}
+
+// ---- boundary EMBA_POISSON_WRAP_X: the columns wrap, the poles stay Dirichlet (poisson_rule.h states the rule) -----------------------------
+// Only the W direction differs from the solve above: the divergence gains its last column, and the tridiagonal systems become the cyclic ones
+// (C_W + lambda1[i] I) x = g.  Condensed on x[W-1] they are the SAME sweeps over the first W-1 rows of the transposed plane (the Thomas recurrence does
+// not depend on the length: the first W-1 rows of the factor table are T_{W-1}'s), then two small passes: the pivot t per system, and x = p - t q.
+
+// F^T with the wrapped column: emba_divergence_T_kernel's tiles, every column j < W live, its right neighbour (j + 1) mod W
+__global__ __launch_bounds__(256) void emba_divergence_T_wrap_kernel(const double* __restrict__ Gx, const double* __restrict__ Gy, int H, int W, double* __restrict__ FT)
+{
+    __shared__ double tile[32][33];
+    const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int r = ty; r < 32; r += 8) {
+        const int i = by + r, j = bx + tx;
+        double f = 0.0;
+        if (i < H - 1 && j < W) {
+            const size_t row = (size_t)i * W, idx = row + j;
+            f = poisson_divergence(Gx[row + poisson_wrap_right(j, W)], Gx[idx], Gy[idx + W], Gy[idx]);
+        }
+        tile[r][tx] = f;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) { const int j = bx + r, i = by + tx; if (j < W && i < H) FT[(size_t)j * H + i] = tile[tx][r]; }
+}
+
+// The right-hand side of q = T_{W-1}^-1 (e_0 + e_{W-2}) for every system i, on the transposed plane (W x H, every row written: row W-1, which no sweep
+// over W-1 rows touches and no pass reads, is 0).  The two sweeps above over its first W-1 rows make it q.  Once per context, like the Thomas factors.
+__global__ void emba_wrap_unit_kernel(int H, int W, double* __restrict__ q)
+{
+    const unsigned int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (unsigned int)H * (unsigned int)W) return;
+    const int j = (int)(idx / (unsigned int)H);
+    q[idx] = (j == 0 || j == W - 2) ? 1.0 : 0.0;
+}
+
+// t = x[W-1] of every system, from the gather p[0], p[W-2], g[W-1] (three coalesced rows of the swept plane) — written over g[W-1], which only this thread reads
+__global__ void emba_wrap_pivot_kernel(const double* __restrict__ q, const double* __restrict__ lam1, double* __restrict__ v, int H, int W)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H) return;
+    const size_t last = (size_t)(W - 2) * H + i, pivot = (size_t)(W - 1) * H + i;
+    v[pivot] = poisson_wrap_pivot(v[pivot], v[i], v[last], -2.0 + lam1[i], q[i], q[last]);
+}
+
+// x[j] = p[j] - t q[j] for j < W-1, in place (row W-1 holds t and is x[W-1] already): one coalesced pass over two planes
+__global__ __launch_bounds__(256) void emba_wrap_close_kernel(const double* __restrict__ q, double* __restrict__ v, int H, int W)
+{
+    const unsigned int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (unsigned int)H * (unsigned int)(W - 1)) return;
+    const unsigned int i = idx % (unsigned int)H;
+    v[idx] = poisson_wrap_close(v[idx], v[(size_t)(W - 1) * H + i], q[idx]);
 }
 
 }  // namespace emba

@@ -1,5 +1,5 @@
 // emba_amd/csrc/render_host.h — f3, the intensity panorama from the gradient map (poisson_kernels.h), and the reference's record_data map images
-// (render_kernels.h): emba_reconstruct_intensity, emba_render_map_images, emba_normalize_robust.
+// (render_kernels.h): emba_reconstruct_intensity[_bc], emba_render_map_images[_bc], emba_normalize_robust.  The boundary rule: poisson_rule.h.
 // Part of emba_hip.hip's translation unit, included below solve_host.h (the device code keeps the order of first use) and transfer_host.h (d2h_pageable).
 #pragma once
 #include "context.h"
@@ -7,16 +7,37 @@
 using namespace emba;
 
 // ---- f3: intensity panorama from the gradient map ---------------------------------------------------------------------------
-extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_host, const double* Gy_host, double* M_host)
+namespace {
+
+// the boundary argument of the _bc entry points (poisson_rule.h): refused before anything is allocated, launched or written
+emba_status poisson_boundary_check(emba_ctx* c, int boundary)
+{
+    switch (poisson_boundary_ok(boundary, c->W)) {
+    case PoissonBoundaryStatus::unknown:
+        return fail(c, EMBA_ERR_INVALID_ARG, "boundary=%d: EMBA_POISSON_DIRICHLET (%d) or EMBA_POISSON_WRAP_X (%d)", boundary, EMBA_POISSON_DIRICHLET, EMBA_POISSON_WRAP_X);
+    case PoissonBoundaryStatus::too_narrow:
+        return fail(c, EMBA_ERR_INVALID_ARG, "boundary EMBA_POISSON_WRAP_X needs pano_w >= %d (pano_w=%d)", kPoissonWrapMinW, c->W);
+    case PoissonBoundaryStatus::ok: break;
+    }
+    if (boundary == EMBA_POISSON_WRAP_X && c->opt_poisson == 1)
+        return fail(c, EMBA_ERR_STATE, "boundary EMBA_POISSON_WRAP_X with option poisson = 1: the dense sine transforms along W have no wrapped form");
+    return EMBA_OK;
+}
+
+}  // namespace
+
+extern "C" emba_status emba_reconstruct_intensity_bc(emba_ctx* c, const double* Gx_host, const double* Gy_host, double* M_host, int boundary)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
+    emba_status st;
+    if ((st = poisson_boundary_check(c, boundary))) return st;
+    const bool wrap = boundary == EMBA_POISSON_WRAP_X;
     if ((Gx_host == nullptr) != (Gy_host == nullptr)) return fail(c, EMBA_ERR_INVALID_ARG, "pass both Gx and Gy, or neither");
     if (!Gx_host && !c->map.state().resident()) return fail(c, EMBA_ERR_STATE, "no map resident");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int H = c->H, W = c->W;
     const size_t npix = c->npix;
-    emba_status st;
     // option poisson = 1 (dense): both axes by sine-matrix products (four GEMMs: the round-1/2 form, kept for comparison); default: Fourier analysis
     // along H only + tridiagonal solves along W (poisson_kernels.h) — a third of the arithmetic, same solution to rounding.
     const bool dense = c->opt_poisson == 1;      // option poisson: 1 dense sine transforms, 2 no folding (comparison forms)
@@ -37,6 +58,14 @@ extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_
     if (!dense && (st = ensure<double>(c, c->d_thomas, npix, &fresh))) return st;
     if (!dense && fresh) {   // Thomas factors of T_W + lambda1[i] I for every H-frequency i: W x H doubles, once
         hipLaunchKernelGGL(emba_thomas_coef_kernel, dim3((H + 63) / 64), dim3(64), 0, s, c->d_lamH.as<double>(), H, W, c->d_thomas.as<double>());
+    }
+    // boundary EMBA_POISSON_WRAP_X: q = T_{W-1}^-1 (e_0 + e_{W-2}) for every H-frequency i (W x H doubles, once) by the sweeps of the solve itself
+    if (wrap && (st = ensure<double>(c, c->d_wrapq, npix, &fresh))) return st;
+    if (wrap && fresh) {
+        const unsigned tb = (unsigned)((H + kTriSys - 1) / kTriSys);
+        hipLaunchKernelGGL(emba_wrap_unit_kernel, dim3(nblocks(npix)), dim3(256), 0, s, H, W, c->d_wrapq.as<double>());
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_wrapq.as<double>(), H, W - 1);
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_wrapq.as<double>(), H, W - 1);
     }
     const bool fold = !dense && (H % 2 == 0) && H >= 64 && c->opt_poisson != 2;
     if (fold && (st = ensure<double>(c, c->d_Sfold, (size_t)H * H / 2, &fresh))) return st;
@@ -88,11 +117,18 @@ extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_
             return transposed_out;
         };
         if (fold && (st = ensure<double>(c, c->d_pE, npix))) return st;
-        hipLaunchKernelGGL(emba_divergence_T_kernel, tg, dim3(256), 0, s, gx, gy, H, W, c->d_pT.as<double>());                     // F^T  (W x H), straight from the gradient maps
+        if (wrap) hipLaunchKernelGGL(emba_divergence_T_wrap_kernel, tg, dim3(256), 0, s, gx, gy, H, W, c->d_pT.as<double>());      // F^T with the wrapped column
+        else hipLaunchKernelGGL(emba_divergence_T_kernel, tg, dim3(256), 0, s, gx, gy, H, W, c->d_pT.as<double>());                // F^T  (W x H), straight from the gradient maps
         dst_rows(c->d_pT.as<double>(), c->d_pF.as<double>(), c->d_pE.as<double>(), 1.0, false);                                                                 // (S_H F)^T = F^T S_H
         const unsigned tb = (unsigned)((H + kTriSys - 1) / kTriSys);
-        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, W);   // (T_W + lambda1[i] I) x = g, per i
-        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, W);
+        // wrapped: the cyclic systems condensed on x[W-1] (poisson_rule.h) — the same sweeps over the first W-1 rows give p, then t per system and x = p - t q
+        const int Wt = wrap ? W - 1 : W;
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, Wt);   // (T_W + lambda1[i] I) x = g, per i
+        hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_pF.as<double>(), H, Wt);
+        if (wrap) {
+            hipLaunchKernelGGL(emba_wrap_pivot_kernel, dim3((H + 255) / 256), dim3(256), 0, s, (const double*)c->d_wrapq.as<double>(), (const double*)c->d_lamH.as<double>(), c->d_pF.as<double>(), H, W);
+            hipLaunchKernelGGL(emba_wrap_close_kernel, dim3(nblocks((size_t)H * (W - 1))), dim3(256), 0, s, (const double*)c->d_wrapq.as<double>(), c->d_pF.as<double>(), H, W);
+        }
         // M^T = X^T S_H / (2 (H+1)).  Folded: the butterfly writes M itself into d_pF (its input X^T is dead once E and O exist)
         if (fold) dst_rows(c->d_pF.as<double>(), c->d_pF.as<double>(), c->d_pE.as<double>(), 1.0 / (2.0 * (double)(H + 1)), true);
         else {
@@ -105,6 +141,11 @@ extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_
     HIP_TRY(c, hipStreamSynchronize(s));
     c->spun = false; c->knots_in_flight = false;
     return EMBA_OK;
+}
+
+extern "C" emba_status emba_reconstruct_intensity(emba_ctx* c, const double* Gx_host, const double* Gy_host, double* M_host)
+{
+    return emba_reconstruct_intensity_bc(c, Gx_host, Gy_host, M_host, EMBA_POISSON_DIRICHLET);
 }
 
 // ---- record_data map images (render_kernels.h) --------------------------------------------------------------------------------
@@ -156,16 +197,17 @@ inline size_t img_off(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 }  // namespace
 
 // Device layout of the images in c->d_img.as<uint8_t>(): [Gx_u8 | Gy_u8 | RGB (3 n) | Poisson_u8], each part 256-byte aligned.
-extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8)
+extern "C" emba_status emba_render_map_images_bc(emba_ctx* c, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8, int boundary)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;
+    emba_status st;
+    if ((st = poisson_boundary_check(c, boundary))) return st;      // (before the first image is written)
     if (!(pct_discard >= 0.0 && pct_discard <= 100.0)) return fail(c, EMBA_ERR_INVALID_ARG, "pct_discard=%g outside [0, 100]", pct_discard);
     if (!c->map.state().resident()) return fail(c, EMBA_ERR_STATE, "no map resident");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t n = c->npix, o1 = img_off(n), o2 = o1 + img_off(n), o3 = o2 + img_off(3 * n);
     if (n >= ((size_t)1 << 31)) return fail(c, EMBA_ERR_CAPACITY, "%zu pixels: the select counts in 32 bits", n);
-    emba_status st;
     if ((st = ensure<uint8_t>(c, c->d_img, o3 + img_off(n)))) return st;
     if (gx_u8 || gy_u8 || rgb_u8) {
         const double* planes[2] = {c->map.Gx(), c->map.Gy()};
@@ -180,7 +222,7 @@ extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, u
         if (rgb_u8 && (st = d2h_pageable(c, rgb_u8, c->d_img.as<uint8_t>() + o2, 3 * n))) return st;
     }
     if (poisson_u8) {
-        if ((st = emba_reconstruct_intensity(c, nullptr, nullptr, nullptr))) return st;      // M stays in c->d_pF.as<double>()
+        if ((st = emba_reconstruct_intensity_bc(c, nullptr, nullptr, nullptr, boundary))) return st;      // M stays in c->d_pF.as<double>()
         const double* planes[1] = {c->d_pF.as<double>()};
         if ((st = robust_select(c, planes, 1, n, pct_discard, false))) return st;
         hipLaunchKernelGGL(emba_robust_u8_kernel, dim3((unsigned)std::min<size_t>(nblocks(n), 4096)), dim3(256), 0, s, (const double*)c->d_pF.as<double>(), (unsigned int)n,
@@ -191,6 +233,11 @@ extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, u
     }
     c->spun = false; c->knots_in_flight = false;
     return EMBA_OK;
+}
+
+extern "C" emba_status emba_render_map_images(emba_ctx* c, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8)
+{
+    return emba_render_map_images_bc(c, pct_discard, gx_u8, gy_u8, rgb_u8, poisson_u8, EMBA_POISSON_DIRICHLET);
 }
 
 extern "C" emba_status emba_normalize_robust(emba_ctx* c, const double* src_host, size_t n, double pct_discard, uint8_t* dst_host, double* rmin, double* rmax)

@@ -139,9 +139,10 @@ public:
 
     // record_data's map images (EMBA::saveEvoData / saveOptData, solver.cpp:370-479) of the map the next evaluation would use, rendered on the device:
     // pano_height*pano_width bytes each (rgb: x3, interleaved R, G, B); nullptr skips an image (poisson: also the Poisson solve).  Writes no file.
-    void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson)
+    // boundary: that of the Poisson image (EMBA_POISSON_DIRICHLET, the reference's, or EMBA_POISSON_WRAP_X: include/emba_hip.h).
+    void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson, int boundary = EMBA_POISSON_DIRICHLET)
     {
-        check(emba_render_map_images(ctx_, pct_discard, gx, gy, rgb, poisson));
+        check(emba_render_map_images_bc(ctx_, pct_discard, gx, gy, rgb, poisson, boundary));
     }
 
     emba_ctx* ctx() { return ctx_; }

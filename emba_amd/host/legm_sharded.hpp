@@ -216,10 +216,11 @@ public:
     void mapAtActive(std::vector<double>& gxy) { gxy.assign(P_ ? 2 * P_ : 1, 0.0); check(emba_group_get_map_active(g_, gxy.data(), P_)); gxy.resize(2 * P_); }
 
     // record_data's map images (LEGM::render_map_images) through rank 0's context: the map is replicated, no collective is involved
-    void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson)
+    // boundary: that of the Poisson image (EMBA_POISSON_DIRICHLET, the reference's, or EMBA_POISSON_WRAP_X: include/emba_hip.h)
+    void render_map_images(double pct_discard, uint8_t* gx, uint8_t* gy, uint8_t* rgb, uint8_t* poisson, int boundary = EMBA_POISSON_DIRICHLET)
     {
         emba_ctx* c = emba_group_ctx(g_, 0);
-        const emba_status st = emba_render_map_images(c, pct_discard, gx, gy, rgb, poisson);
+        const emba_status st = emba_render_map_images_bc(c, pct_discard, gx, gy, rgb, poisson, boundary);
         if (st != EMBA_OK) throw StatusError(st, emba_last_error(c));
     }
 

@@ -51,6 +51,7 @@ struct BASettings {               // include/emba/params.h:14-61, values of laun
     enum Refine { Both, Map, Poses };
     Refine refine = Both;               // what a step moves: Both (the reference's joint solve); Map: mapping with known poses (solveMapOnly, the control poses are
                                         // held); Poses: solvePosesOnly against the map as it is — no updateMap (it zeroes every inactive pixel), the map is never touched
+    int panorama_boundary = EMBA_POISSON_DIRICHLET;   // the boundary of the recorded Poisson images: what a record callback hands to model.render_map_images
 };
 
 struct LMLogEntry { int iter; double log10_lambda, cost_min, cost_new; bool accepted; size_t num_active; int cg_iter; };
@@ -153,7 +154,7 @@ inline void incrementalUpdate(std::vector<double>& knots_xyzw, const std::vector
 // rl: optional run-time records.  Returns the refined poses, the final cost and the iteration log; model.downloadMap() gives the refined map.
 // record: optional record_data callback (iter, final) at the reference's three points — every loop iteration (solver.cpp:173, final = false),
 // convergence (:332-336) and forced termination (:360-364) (final = true: saveEvoData + saveOptData).  The map resident when it is called is the
-// accepted one (model.render_map_images renders it); the caller writes the files.
+// accepted one (model.render_map_images renders it, its Poisson image at ba.panorama_boundary); the caller writes the files.
 inline LMResult solveTimeWindow(ShardedLEGM& model, const TrajectoryView& traj0, const EventPacket& events, const double* Gx, const double* Gy,
                                 const BASettings& ba = BASettings(), const LMSettings& lm = LMSettings(), RuntimeLog* rl = nullptr,
                                 const std::function<void(int, bool)>& record = nullptr)

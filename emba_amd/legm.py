@@ -25,6 +25,14 @@ _dp, _i32p, _u32p = _lib._dp, _lib._i32p, _lib._u32p
 _u16p, _u8p, _i64p = _lib._u16p, _lib._u8p, _lib._i64p
 
 COST_TYPES = {"quadratic": 0, "huber": 1, "cauchy": 2}
+POISSON_BOUNDARIES = {"dirichlet": 0, "wrap": 1}      # EMBA_POISSON_DIRICHLET, EMBA_POISSON_WRAP_X
+
+
+def poisson_boundary(boundary):
+    """The boundary argument of reconstructIntensity / renderMapImages as the C ABI's integer."""
+    if boundary not in POISSON_BOUNDARIES:
+        raise ValueError(f"boundary must be 'dirichlet' or 'wrap', not {boundary!r}")
+    return POISSON_BOUNDARIES[boundary]
 
 
 def _p(a, ty):
@@ -622,9 +630,12 @@ class LEGM:
         per-pixel sums directly (speed only; see emba_set_cost)."""
         self._check(self._L.emba_set_cost(self._ctx, COST_TYPES[cost_type], float(a)))
 
-    def reconstructIntensity(self, Gx=None, Gy=None, download=True):
+    def reconstructIntensity(self, Gx=None, Gy=None, download=True, boundary="dirichlet"):
         """poisson_reconstruction::reconstructFromGradient (poisson_reconstruction.cpp:9-50; solver.cpp:417,471): the intensity
-        panorama whose gradient is (Gx, Gy) — or the device-resident map when both are None."""
+        panorama whose gradient is (Gx, Gy) — or the device-resident map when both are None.  boundary: "dirichlet", the reference's flat rectangle
+        with intensity 0 all round, or "wrap": column W-1 is the neighbour of column 0, the rows beyond the poles stay 0 (include/emba_hip.h,
+        EMBA_POISSON_WRAP_X) — no seam, and a map rolled by k columns gives the same panorama rolled."""
+        bc = poisson_boundary(boundary)
         if (Gx is None) != (Gy is None):
             raise ValueError("pass both Gx and Gy, or neither")
         if Gx is not None:
@@ -632,19 +643,20 @@ class LEGM:
             if Gx.shape != (self.H, self.W) or Gy.shape != (self.H, self.W):
                 raise ValueError("Gx/Gy must be pano_height x pano_width float64")
         M = np.empty((self.H, self.W)) if download else None
-        self._check(self._L.emba_reconstruct_intensity(self._ctx, _p(Gx, _dp), _p(Gy, _dp), _p(M, _dp)))
+        self._check(self._L.emba_reconstruct_intensity_bc(self._ctx, _p(Gx, _dp), _p(Gy, _dp), _p(M, _dp), bc))
         return M
 
-    def renderMapImages(self, pct=0.1, poisson=True):
+    def renderMapImages(self, pct=0.1, poisson=True, boundary="dirichlet"):
         """The images EMBA::saveEvoData / saveOptData write (solver.cpp:370-479), rendered on the device from the map the next evaluation would
         use (the one downloadMap returns): {"Gx", "Gy": normalizeRobust(G, pct), "G_hsv": H x W x 3 RGB (hue = orientation, value = magnitude),
-        "map_poisson": normalizeRobust(reconstructIntensity(), pct) or None with poisson=False}, all uint8.  Synchronous: the images are in host
-        memory when it returns."""
+        "map_poisson": normalizeRobust(reconstructIntensity(boundary=boundary), pct) or None with poisson=False}, all uint8.  Synchronous: the
+        images are in host memory when it returns."""
+        bc = poisson_boundary(boundary)
         H, W = self.H, self.W
         gx, gy = np.empty((H, W), np.uint8), np.empty((H, W), np.uint8)
         rgb = np.empty((H, W, 3), np.uint8)
         mp = np.empty((H, W), np.uint8) if poisson else None
-        self._check(self._L.emba_render_map_images(self._ctx, float(pct), _p(gx, _u8p), _p(gy, _u8p), _p(rgb, _u8p), _p(mp, _u8p)))
+        self._check(self._L.emba_render_map_images_bc(self._ctx, float(pct), _p(gx, _u8p), _p(gy, _u8p), _p(rgb, _u8p), _p(mp, _u8p), bc))
         return {"Gx": gx, "Gy": gy, "G_hsv": rgb, "map_poisson": mp}
 
     def normalizeRobust(self, img, pct=0.1, with_range=False):

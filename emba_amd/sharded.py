@@ -571,8 +571,8 @@ class ShardedModel:
         return self.m.downloadMap()
 
     # the map is replicated: the record_data images of this rank's LEGM are every rank's (no collective; only the recording rank calls these)
-    def renderMapImages(self, pct=0.1, poisson=True):
-        return self.m.renderMapImages(pct, poisson)
+    def renderMapImages(self, pct=0.1, poisson=True, boundary="dirichlet"):
+        return self.m.renderMapImages(pct, poisson, boundary=boundary)
 
     def normalizeRobust(self, img, pct=0.1, with_range=False):
         return self.m.normalizeRobust(img, pct, with_range)

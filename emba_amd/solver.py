@@ -30,6 +30,7 @@ class BASettings:               # include/emba/params.h:14-61, values of launch/
     use_CG: bool = False                # solveNormalEqCG instead of the Schur solve (solver.cpp:190-202; launch default false)
     refine: str = "both"                # what a step moves: "both" (the reference's joint solve), "map" (mapping with known poses: solveMapOnly, the
                                         # trajectory is held) or "poses" (solvePosesOnly against the map as it is: no updateMap, the map is never touched)
+    panorama_boundary: str = "dirichlet"  # the boundary of the recorded map_poisson images: "dirichlet" (the reference's) or "wrap" (LEGM.reconstructIntensity)
 
 
 @dataclass
@@ -116,14 +117,15 @@ class MapRecorder:
     def new_window(self):
         self.window += 1
 
-    def record(self, model, it, final=False):
-        """saveEvoData(Gx, Gy, win, it), and saveOptData too with final=True (one render serves both sets)."""
+    def record(self, model, it, final=False, boundary="dirichlet"):
+        """saveEvoData(Gx, Gy, win, it), and saveOptData too with final=True (one render serves both sets).  boundary: that of map_poisson
+        (BASettings.panorama_boundary); a model is asked for it only where it is not the reference's."""
         import os
         import time
         if self.window < 0:
             self.window = 0
         t0 = time.perf_counter()
-        imgs = model.renderMapImages(self.pct, poisson=True)
+        imgs = model.renderMapImages(self.pct, poisson=True, **({} if boundary == "dirichlet" else dict(boundary=boundary)))
         self.render_s += time.perf_counter() - t0
         win = "win_%04d_" % self.window
         for table in ((self.EVO, self.OPT) if final else (self.EVO,)):
@@ -207,6 +209,8 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
     import time
     if ba.refine not in ("both", "map", "poses"):
         raise ValueError(f"BASettings.refine must be 'both', 'map' or 'poses', not {ba.refine!r}")
+    if ba.panorama_boundary not in ("dirichlet", "wrap"):
+        raise ValueError(f"BASettings.panorama_boundary must be 'dirichlet' or 'wrap', not {ba.panorama_boundary!r}")
     if ba.use_CG and ba.refine != "both":
         raise ValueError("use_CG solves the joint system: it cannot be combined with refine = 'map' / 'poses'")
     rl = runtime_log
@@ -242,7 +246,7 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
         if rl is not None:                                                           # :170-178
             rl.iteration(it, lam, cost_min, cost_new, *cost_parts)
         if mr is not None:                                                           # :173 saveEvoData
-            mr.record(model, it)
+            mr.record(model, it, boundary=ba.panorama_boundary)
         # x2 goes from the solver to updateMap and nowhere else (solver.cpp:193-239): a device model keeps it in HBM (x2 is None here)
         rkw = dict(resident_x2=True) if getattr(model, "supports_resident_x2", False) else {}
         try:
@@ -295,7 +299,7 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
                 count_tol += 1
                 if count_tol >= lm.num_times_tol_fun_sat:
                     if mr is not None:                                               # :332-336 saveEvoData + saveOptData
-                        mr.record(model, it, final=True)
+                        mr.record(model, it, final=True, boundary=ba.panorama_boundary)
                     return LMResult(traj, cost_min, it, True, log, "tolerance")
         else:                                                                        # :340-352
             decreased = False
@@ -312,5 +316,5 @@ def solve_time_window(model, traj, events, Gx, Gy, ba=BASettings(), lm=LMSetting
             count_tol = 0
     reason = "max_iter" if it > lm.max_num_iter else ("cost" if cost_min <= 1e-16 else "lambda")
     if mr is not None:                                                               # :360-364 forced termination
-        mr.record(model, it, final=True)
+        mr.record(model, it, final=True, boundary=ba.panorama_boundary)
     return LMResult(traj, cost_min, it, False, log, reason)

@@ -87,6 +87,8 @@ def main():
     ap.add_argument("--contrast-prior-weight", type=float, default=1.0, help="the weight of that prior in the image (finite, not negative)")
     ap.add_argument("--pano-h", type=int, default=1024, help="panorama height H (the map is H x 2H) where no map is read (--init-map events without --demo)")
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
+    ap.add_argument("--panorama-boundary", default="dirichlet", choices=["dirichlet", "wrap"], help="the boundary of the intensity panorama (map_poisson_opt.pgm and the "
+                    "recorded map_poisson images): dirichlet, the reference's flat rectangle with a dark frame, or wrap: column W-1 is the neighbour of column 0 (DESIGN.md section 16)")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
     a = ap.parse_args()
     if a.alpha is None:
@@ -180,7 +182,7 @@ def main():
     else:
         model = legm = LEGM(sw, sh, lut, C_th, W, H)
     ba = BASettings(use_IRLS=a.cost != "quadratic", cost_type=a.cost, eta=a.eta, thres_valid_pixel=a.thres_valid_pixel, alpha=a.alpha,
-                    damping_factor=a.damping_factor, refine=a.refine)
+                    damping_factor=a.damping_factor, refine=a.refine, panorama_boundary=a.panorama_boundary)
     if rank == 0:
         print(f"{events.size()} events, {traj.size()} control poses, panorama {H}x{W}" + (f", {world} rank(s) through the sharded host" if legm is not model else ""))
     t0 = time.time()
@@ -255,7 +257,7 @@ def main():
     eio.write_trajectory(os.path.join(a.out, "refined_traj.txt"), res.traj)
     eio.save_map(a.out, *model.downloadMap())
     # intensity panorama from the refined gradient map (solver.cpp:417-425 / 471-479), reconstructed on the device
-    eio.save_pgm(os.path.join(a.out, "map_poisson_opt.pgm"), eio.normalize_robust(legm.reconstructIntensity(), 0.1))
+    eio.save_pgm(os.path.join(a.out, "map_poisson_opt.pgm"), eio.normalize_robust(legm.reconstructIntensity(boundary=a.panorama_boundary), 0.1))
     if legm is not model:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()

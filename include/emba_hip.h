@@ -242,6 +242,22 @@ emba_status emba_get_map_active(emba_ctx* ctx, double* gxy_host, size_t cap_P);
  * matrix on the fp64 matrix cores (the transform lengths 2(n+1) have large prime factors); the matrices are built on first
  * use and kept (8 (H^2 + W^2) bytes). */
 emba_status emba_reconstruct_intensity(emba_ctx* ctx, const double* Gx_host, const double* Gy_host, double* M_host);
+/* The same reconstruction under a boundary rule.  The panorama is equirectangular: column W-1 is the neighbour of column 0.
+ *   EMBA_POISSON_DIRICHLET  the reference's rule, above: the image is a flat rectangle with intensity 0 all round; the last row and the last column of the
+ *                           divergence are 0.  emba_reconstruct_intensity and emba_render_map_images are the _bc forms at this boundary, bit for bit.
+ *   EMBA_POISSON_WRAP_X     wrap in x, and the reference's zero Dirichlet rows beyond the poles.  Divergence, for every row i < H-1 and EVERY column j:
+ *                               F[i][j] = Gx[i][(j+1) mod W] - Gx[i][j] + Gy[i+1][j] - Gy[i][j]            (row H-1 of F is 0, as in the reference)
+ *                           M solves  M[i-1][j] + M[i+1][j] + M[i][(j-1) mod W] + M[i][(j+1) mod W] - 4 M[i][j] = F[i][j]  with M[-1][:] = M[H][:] = 0, i.e.
+ *                               M = DST-I_H( FFT_W^-1( FFT_W(DST-I_H(F)) / (lambda1[i] + mu[k]) ) ) / (2 (H+1)),
+ *                               lambda1[i] = -4 sin^2(pi (i+1) / (2 (H+1))),  mu[k] = -4 sin^2(pi k / W).
+ *                           lambda1[i] + mu[k] <= lambda1[0] < 0: never singular, no null space, no mean to fix.  Rolling Gx, Gy by k columns rolls M.
+ *                           On the device: the DST-I along H as above, and per H-frequency the cyclic system along W, condensed on its last unknown.
+ * Refused, with the outputs and the context as they were: a boundary that is neither (EMBA_ERR_INVALID_ARG); EMBA_POISSON_WRAP_X on a panorama of fewer than 3
+ * columns (EMBA_ERR_INVALID_ARG) or with option poisson = 1, whose dense sine transforms along W have no wrapped meaning (EMBA_ERR_STATE).  Options poisson = 2
+ * and gemm64 keep their meaning.  emba_render_map_images_bc checks the boundary whether or not poisson_u8 is given. */
+#define EMBA_POISSON_DIRICHLET 0
+#define EMBA_POISSON_WRAP_X 1
+emba_status emba_reconstruct_intensity_bc(emba_ctx* ctx, const double* Gx_host, const double* Gy_host, double* M_host, int boundary);
 
 /* The map images of the reference's record_data output (EMBA::saveEvoData / saveOptData, solver.cpp:370-479), rendered on the device from the map the
  * next evaluation would use (the one emba_download_map copies).  Host pointers, H x W bytes each (rgb_u8: H x W x 3, interleaved R, G, B); a NULL pointer
@@ -254,6 +270,8 @@ emba_status emba_reconstruct_intensity(emba_ctx* ctx, const double* Gx_host, con
  *   poisson_u8      emba_reconstruct_intensity of the resident map, robust-normalised as above
  * The images come back through the context's pinned staging buffers; the call returns when they are in host memory. */
 emba_status emba_render_map_images(emba_ctx* ctx, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8);
+/* poisson_u8 from emba_reconstruct_intensity_bc at `boundary`; everything else as above. */
+emba_status emba_render_map_images_bc(emba_ctx* ctx, double pct_discard, uint8_t* gx_u8, uint8_t* gy_u8, uint8_t* rgb_u8, uint8_t* poisson_u8, int boundary);
 /* The same robust normalisation of any plane of n doubles (host memory): dst_host (n bytes, or NULL) and the order statistics rmin / rmax (or NULL).
  * Needs a context only (no map, no events). */
 emba_status emba_normalize_robust(emba_ctx* ctx, const double* src_host, size_t n, double pct_discard, uint8_t* dst_host, double* rmin, double* rmax);
