@@ -118,6 +118,9 @@ SIGNATURES = {
     "emba_seq_contrast_prior_clear": (C.c_int, [C.c_void_p]),
     "emba_seq_contrast_gradient_prior": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double,
                                                    _dp, _dp, _dp, C.POINTER(C.c_uint64), _dp, _dp, _i32p]),
+    "emba_render_views": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                    _dp, _u8p, C.POINTER(C.c_uint64), _dp]),
+    "emba_seq_event_frames": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _i64p, C.c_size_t, C.c_int32, _i32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

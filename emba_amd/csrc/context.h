@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -239,6 +239,11 @@ struct ContrastPriors {
     void reset() { drop(); for (DevBuf& b : image) b.reset(); }      // emba_seq_free
 };
 
+// Grow-only buffers of the sensor views (view_host.h).  emba_render_views: a caller's source plane [H, W]; the frame times, their pose table and the control
+// poses they were evaluated from (this stage's own: emba_ctx::seq_pose is left alone); head: the pose stage's status word; one chunk of frames as fp64,
+// as bytes and as pm; outside: the count per frame.  emba_seq_event_frames: the edges, one chunk of int32 frames, ends: the events before and after.
+struct ViewBuffers { DevBuf plane, t, pose, knots, head, frames, u8, pm, outside, edge, counts, ends; };
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -411,6 +416,7 @@ struct emba_ctx {
     ContrastPriors priors;        // what earlier events voted, per level: the image a call of emba_seq_contrast_gradient_prior starts from
     int opt_contrast_vote = -1;   // option contrast_vote: the vote kernel of a level call — -1 by the image's size (contrast_rule.h: contrast_vote_plan), 0 HBM, 1 LDS where it fits
     int contrast_vote_path = -1;  // the vote kernel the last contrast call launched: 0 HBM, 1 LDS; -1 none yet (emba_get_option "contrast_vote_path")
+    ViewBuffers view;             // sensor views along the trajectory: predicted frames and event frames (view_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -63,8 +63,17 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # to the panorama the windows before it placed.  Needs refine_contrast.  Off by default; the first window has no prior.
     contrast_prior: bool = False
     contrast_prior_weight: float = 1.0
+    # Sensor views along the final trajectory (no counterpart in the reference; the rules: include/emba_hip.h, emba_render_views and emba_seq_event_frames;
+    # DESIGN.md §17): after the last window, what the camera would have seen at views_hz frames per second over the time the trajectory covers, sampled
+    # from the intensity panorama of the refined map under BASettings.panorama_boundary (SequenceResult.views) — on the device where the model has one
+    # (LEGM.render_views), else by io.render_views; with view_events also the signed event counts between consecutive frames (LEGM.event_frames where the
+    # sequence is resident, else io.event_frames).  0: off.
+    views_hz: float = 0.0
+    view_events: bool = False
 
     def __post_init__(self):
+        if not (np.isfinite(self.views_hz) and self.views_hz >= 0):
+            raise ValueError(f"SequenceSettings.views_hz = {self.views_hz}: frames per second, finite and not negative (0: off)")
         if self.init_poses not in ("given", "events"):
             raise ValueError(f"SequenceSettings.init_poses must be 'given' or 'events', not {self.init_poses!r}")
         self.contrast_levels = emba_io.check_contrast_levels(self.contrast_levels, 1 << emba_io.CONTRAST_MAX_LEVEL)      # (the width: checked where it is known)
@@ -108,6 +117,7 @@ class SequenceResult:
     cmax: object = None         # SequenceSettings.init_poses = "events": what estimate_angular_velocity returned (omega, t_ref_ns, J0, J, evals) + the raw
                                 # poses made of it (pose_t, pose_q)
     event_panorama: object = None   # SequenceSettings.event_panorama: int64 [H, W], the panorama of the events [windows[0].beg, windows[-1].end) warped along traj
+    views: object = None        # SequenceSettings.views_hz: what sequence_views returned — t_ns [F], views [F, sh, sw], u8, outside [F], lo, hi, event_frames
 
 
 def keeps_sequence(model):
@@ -146,6 +156,57 @@ def panorama_of_events(model, events, traj, beg, end, resident_sequence, want_im
     if lut is None or not sw or not sh:
         raise ValueError("the panorama of warped events without a resident sequence needs the camera: model.bearing_lut, model.sensor_w, model.sensor_h")
     return emba_io.event_panorama(events, lut, sw, sh, model.W, model.H, traj, beg, end)
+
+
+def view_frame_times(traj, views_hz):
+    """The frame times of views_hz frames per second over the time traj covers: t0, t0 + p, t0 + 2 p, ... with p = round(1e9 / views_hz) ns (at least 1),
+    up to the last time the spline accepts, t0 + (K - 1) dt - 1."""
+    period = max(int(round(1e9 / float(views_hz))), 1)
+    t_last = int(traj.t0_ns) + (traj.size() - 1) * int(traj.dt_ns) - 1
+    return np.arange(int(traj.t0_ns), t_last + 1, period, dtype=np.int64)
+
+
+def sequence_views(model, events, traj, views_hz, view_events=False, boundary="dirichlet", resident_sequence=True, panorama=None):
+    """Sensor views along traj: the frames the camera would have seen at view_frame_times(traj, views_hz), sampled from the intensity
+    panorama of the model's resident map under `boundary` (or from `panorama` [H, W] where given), their 8-bit form with the tone of
+    normalize_robust(panorama, 0.1) — constant across frames — and, with view_events, the signed event counts of the whole (down-sampled) sequence between
+    consecutive frames.  On the device where the model (or the rank's model behind a sharded host) has render_views / event_frames and, for the counts, the
+    sequence is resident; else by the numpy forms of emba_amd.io with the camera the model names, which need `panorama` or a model that reconstructs one.
+    Returns a dict: t_ns [F], views float64 [F, sh, sw], u8 uint8 [F, sh, sw], outside int64 [F], lo, hi, event_frames int32 [F - 1, sh, sw] or None."""
+    ts = view_frame_times(traj, views_hz)
+    dev = model if hasattr(model, "render_views") else getattr(model, "m", None)
+    if not hasattr(dev, "render_views"):
+        dev = None
+    if dev is not None:
+        M = None if panorama is None else np.ascontiguousarray(panorama, dtype=np.float64)
+        src = dev.reconstructIntensity(boundary=boundary) if M is None else M
+        lo, hi = dev.normalizeRobust(src, 0.1, with_range=True)[1]
+        r = dev.render_views(ts, traj.knots_xyzw, traj.t0_ns, traj.dt_ns, plane=M, boundary=boundary, lo=lo, hi=hi, want_u8=True)
+        out = dict(t_ns=ts, views=r["views"], u8=r["u8"], outside=r["outside"], lo=lo, hi=hi, event_frames=None)
+    else:
+        lut, sw, sh = getattr(model, "bearing_lut", None), getattr(model, "sensor_w", None), getattr(model, "sensor_h", None)
+        if lut is None or not sw or not sh:
+            raise ValueError("sensor views without the device need the camera: model.bearing_lut, model.sensor_w, model.sensor_h")
+        if panorama is None:
+            if not hasattr(model, "reconstructIntensity"):
+                raise ValueError("sensor views without the device need the intensity panorama: pass panorama, or a model with reconstructIntensity")
+            panorama = model.reconstructIntensity(boundary=boundary)
+        M = np.asarray(panorama, dtype=np.float64)
+        lo, hi = emba_io.robust_range(M, 0.1)
+        pm = emba_io.view_pm(lut, traj.knots_xyzw, traj.t0_ns, traj.dt_ns, ts, M.shape[1], M.shape[0])
+        v, outside = emba_io.render_views(M, pm, with_outside=True)
+        shape = (ts.size, int(sh), int(sw))
+        out = dict(t_ns=ts, views=v.reshape(shape), u8=emba_io.view_u8(v, lo, hi, outside=outside).reshape(shape), outside=outside.sum(axis=1).astype(np.int64),
+                   lo=lo, hi=hi, event_frames=None)
+    if view_events and ts.size >= 1:
+        if dev is not None and resident_sequence and hasattr(dev, "event_frames"):
+            out["event_frames"] = dev.event_frames(0, None, ts)[0]
+        else:
+            sw, sh = getattr(model, "sensor_w", None), getattr(model, "sensor_h", None)
+            if events is None or not sw or not sh:
+                raise ValueError("event frames without a resident sequence need the events and the sensor's size: model.sensor_w, model.sensor_h")
+            out["event_frames"] = emba_io.event_frames(events.x, events.y, events.polarity, events.t_ns, ts, sw, sh)[0]
+    return out
 
 
 def refine_window_poses(model, seg, beg, end, resident_sequence, max_iter, levels=(0,), prior_weight=None):
@@ -319,4 +380,6 @@ def run_sequence(model, events, pose_t, pose_q, Gx, Gy, seq, ba=BASettings(), lm
     out.traj = LinearTrajectory(knots, traj_t0_ns, traj_dt_ns)
     if seq.event_panorama and out.windows:
         out.event_panorama = panorama_of_events(model, events, out.traj, out.windows[0].beg, out.windows[-1].end, resident_sequence, want_image=True)["image"]
+    if seq.views_hz > 0 and out.windows:
+        out.views = sequence_views(model, events, out.traj, seq.views_hz, seq.view_events, ba.panorama_boundary, resident_sequence)
     return out

@@ -170,13 +170,20 @@ def normalize_robust(img, percentage_pixels_to_discard=0.1):
     """image_util::normalizeRobust: scale [robust min, robust max] (order statistics after discarding the given percentage of
     pixels, float32 index arithmetic like the reference) to [0, 255]; cv::Mat::convertTo(CV_8UC1) = round half to even, saturate."""
     a = np.asarray(img, dtype=np.float64)
+    rmin, rmax = robust_range(a, percentage_pixels_to_discard)
+    scale = 255.0 / (rmax - rmin) if rmax != rmin else 1.0
+    return np.clip(np.rint(scale * (a - rmin)), 0, 255).astype(np.uint8)
+
+
+def robust_range(img, percentage_pixels_to_discard=0.1):
+    """image_util::minMaxLocRobust (image_utils.cpp:22-23): the order statistics normalize_robust scales between, (rmin, rmax) — what
+    LEGM.normalizeRobust(with_range=True) returns beside the image."""
+    a = np.asarray(img, dtype=np.float64)
     srt = np.sort(a, axis=None)
     n = a.size
     i_min = int(np.float32(np.float32(0.5) * np.float32(percentage_pixels_to_discard) / np.float32(100.0)) * np.float32(n))
     i_max = int(np.float32(np.float32(1.0) - np.float32(0.5) * np.float32(percentage_pixels_to_discard) / np.float32(100.0)) * np.float32(n))
-    rmin, rmax = srt[i_min], srt[min(i_max, n - 1)]
-    scale = 255.0 / (rmax - rmin) if rmax != rmin else 1.0
-    return np.clip(np.rint(scale * (a - rmin)), 0, 255).astype(np.uint8)
+    return float(srt[i_min]), float(srt[min(i_max, n - 1)])
 
 
 def save_pgm(path, img_u8):
@@ -828,3 +835,74 @@ def refine_contrast_levels(model, traj, beg, end, levels, *, pano_w, fix_first_p
     J_before = float(J_only_at(0)(traj)) if extra else None
     out, hists, evals = refine_contrast_pyramid(J_and_grad_at, J_only_at, traj, lv, pano_w=pano_w, fix_first_pose=fix_first_pose, max_iter=int(max_iter))
     return out, (hists[0][0] if J_before is None else J_before), hists[0][-1], evals + extra
+
+
+# ---- sensor views along the trajectory (numpy forms of emba_render_views and emba_seq_event_frames, include/emba_hip.h; the device forms are
+# LEGM.render_views and LEGM.event_frames).  The sample and the tone are emba_amd/csrc/view_rule.h's view_sample and view_u8, operation for
+# operation: given the same pm both forms give the same bits.  The event frames are integers.
+def view_pm(lut, knots, t0_ns, dt_ns, frame_t_ns, W, H):
+    """pm [F, S, 2] of every sensor pixel (S rows of the bearing LUT) at every frame time: the spline pose by so3.spline_evaluate, pm = project(R * bearing)
+    with the equirectangular projection of synth.project_equirect on a panorama of W x H.  numpy's sin / atan2 / asin are not the device's: close to
+    emba_render_views' pm_out, not bit-equal.  Raises ValueError where a frame time lies outside the knots (so3.spline_evaluate)."""
+    from . import synth
+    lut = np.asarray(lut, dtype=np.float64).reshape(-1, 3)
+    knots = np.asarray(knots, dtype=np.float64).reshape(-1, 4)
+    ts = np.asarray(frame_t_ns, dtype=np.int64).reshape(-1)
+    pm = np.zeros((ts.size, lut.shape[0], 2))
+    for f, t in enumerate(ts.tolist()):
+        rb = lut @ synth._quat_to_R(so3.spline_evaluate(knots, int(t0_ns), int(dt_ns), t)).T
+        pm[f, :, 0], pm[f, :, 1] = synth.project_equirect(int(W), int(H), rb)
+    return pm
+
+
+def render_views(plane, pm, fill=0.0, with_outside=False):
+    """view_sample (view_rule.h) of plane [H, W] at every pm [..., 2]: ix = floor(pm_x), ax = pm_x - ix, iy, ay likewise; the columns ix, ix + 1 wrap modulo
+    W; iy < 0 or iy + 1 > H - 1 (or a pm that is not finite, or |pm| >= 2^31) is outside and reads `fill`; otherwise
+    (1 - ay) ((1 - ax) P[iy][ix] + ax P[iy][ix + 1]) + ay ((1 - ax) P[iy + 1][ix] + ax P[iy + 1][ix + 1]), in this order.  Returns the views, shaped
+    pm.shape[:-1]; with_outside also the boolean mask of the outside pixels."""
+    P = np.asarray(plane, dtype=np.float64)
+    H, W = P.shape
+    pm = np.asarray(pm, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(pm[..., 0]) < 2147483648.0) & (np.abs(pm[..., 1]) < 2147483648.0)
+    x, y = np.where(ok, pm[..., 0], 0.0), np.where(ok, pm[..., 1], -1.0)
+    fx, fy = np.floor(x), np.floor(y)
+    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    inside = ok & (iy >= 0) & (iy + 1 <= H - 1)
+    ax, ay = x - fx, y - fy
+    c0 = ix % W
+    c1 = np.where(c0 + 1 == W, 0, c0 + 1)
+    r0 = np.where(inside, iy, 0)
+    r1 = np.where(inside, iy + 1, 0)
+    top = (1.0 - ax) * P[r0, c0] + ax * P[r0, c1]
+    bot = (1.0 - ax) * P[r1, c0] + ax * P[r1, c1]
+    views = np.where(inside, (1.0 - ay) * top + ay * bot, float(fill))
+    return (views, ~inside) if with_outside else views
+
+
+def view_u8(views, lo, hi, outside=None):
+    """view_u8 (view_rule.h): sat(rint(scale (v - lo))) with scale = 255 / (hi - lo), or 1 where hi == lo — the arithmetic of normalize_robust with the
+    caller's limits; a NaN is 0, and so is every pixel of the mask `outside`."""
+    v = np.asarray(views, dtype=np.float64)
+    scale = 255.0 / (float(hi) - float(lo)) if hi != lo else 1.0
+    with np.errstate(invalid="ignore"):
+        r = np.rint(scale * (v - float(lo)))
+        u8 = np.where(r > 0.0, np.minimum(r, 255.0), 0.0).astype(np.uint8)
+    return u8 if outside is None else np.where(outside, np.uint8(0), u8)
+
+
+def event_frames(x, y, pol, t, edges, sw, sh, signed_polarity=True):
+    """The rule of emba_seq_event_frames: F = len(edges) - 1 frames int32 [F, sh, sw]; event k belongs to frame f when edges[f] <= t[k] < edges[f + 1] and
+    adds +1 to its pixel there, or -1 for polarity 0 with signed_polarity.  Returns (frames, before, after): the events before edges[0] and at or after
+    edges[F].  Every event counts (no batches).  The edges must be strictly increasing."""
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1)
+    if edges.size < 1 or (np.diff(edges) <= 0).any():
+        raise ValueError("the edges must be strictly increasing (F + 1 of them)")
+    F, sw, sh = edges.size - 1, int(sw), int(sh)
+    t = np.asarray(t, dtype=np.int64).reshape(-1)
+    f = np.searchsorted(edges, t, side="right") - 1
+    keep = (f >= 0) & (f < F)
+    cell = (f[keep] * sh + np.asarray(y, dtype=np.int64).reshape(-1)[keep]) * sw + np.asarray(x, dtype=np.int64).reshape(-1)[keep]
+    w = np.where(np.asarray(pol).reshape(-1)[keep] == 0, -1.0, 1.0) if signed_polarity else np.ones(cell.size)
+    frames = np.bincount(cell, weights=w, minlength=F * sh * sw).astype(np.int32).reshape(F, sh, sw)      # (sums of +-1: exact in a double)
+    return frames, int((f < 0).sum()), int((f >= F).sum())

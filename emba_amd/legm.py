@@ -294,6 +294,49 @@ class LEGM:
         res["pm"] = (pms[0] if single else np.concatenate(pms)) if want_pm else None
         return res
 
+    def render_views(self, frame_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", fill=0.0, lo=None, hi=None, want_u8=False, want_pm=False):
+        """What the camera would have seen at the times frame_t_ns [F] along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns): frames at sensor
+        resolution sampled from `plane` [pano_h, pano_w], or, with plane=None, from the intensity panorama of the resident map under `boundary`
+        (emba_render_views; the rule: include/emba_hip.h).  A dict of views float64 [F, sensor_h, sensor_w] (`fill` where a pixel looks past a pole row),
+        outside int64 [F] (those pixels per frame), u8 uint8 [F, sensor_h, sensor_w] (None without want_u8) and pm float64 [F, sensor_h * sensor_w, 2] (None
+        without want_pm) — io.render_views given the same pm, bit for bit.  The tone of u8 is sat(rint(255 / (hi - lo) (v - lo))); lo / hi default to the
+        order statistics of normalizeRobust on the source plane (pct 0.1), so the tone is the panorama's own and constant across frames."""
+        bc = poisson_boundary(boundary)
+        knots = np.ascontiguousarray(knots, dtype=np.float64).reshape(-1, 4)
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float64)
+            if plane.shape != (self.H, self.W):
+                raise ValueError("plane must be pano_height x pano_width float64")
+        if want_u8 and (lo is None or hi is None):
+            rmin, rmax = self.normalizeRobust(self.reconstructIntensity(boundary=boundary) if plane is None else plane, with_range=True)[1]
+            lo, hi = (rmin if lo is None else lo), (rmax if hi is None else hi)
+        views = np.empty((F, self.sensor_h, self.sensor_w))
+        u8 = np.empty((F, self.sensor_h, self.sensor_w), np.uint8) if want_u8 else None
+        outside = np.zeros(F, np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        self._check(self._L.emba_render_views(self._ctx, _p(plane, _dp), bc, _p(ts, _i64p), F, _p(knots, _dp), knots.shape[0], int(t0_ns), int(dt_ns), float(fill),
+                                              float(lo) if want_u8 else 0.0, float(hi) if want_u8 else 1.0, _p(views, _dp), _p(u8, _u8p),
+                                              _p(outside, C.POINTER(C.c_uint64)), _p(pm, _dp)))
+        return dict(views=views, outside=outside.astype(np.int64), u8=u8, pm=pm)
+
+    def event_frames(self, beg, end, edge_t_ns, signed_polarity=True):
+        """What the camera reported: the per-pixel event counts of the events [beg, end) of the resident sequence (end = None: its end) in the F frames whose
+        edges are edge_t_ns [F + 1], strictly increasing (emba_seq_event_frames) — event k belongs to frame f when edge[f] <= t[k] < edge[f + 1], +1, or -1
+        for polarity 0 with signed_polarity.  Every event counts, not whole batches of 100.  Returns (frames int32 [F, sensor_h, sensor_w], before, after):
+        the events before edge[0] and at or after edge[F].  io.event_frames gives the same bits."""
+        edges = np.ascontiguousarray(edge_t_ns, dtype=np.int64).reshape(-1)
+        if edges.size < 1:
+            raise ValueError("F frames have F + 1 edges: at least one")
+        F = edges.size - 1
+        end = self.sequence_size() if end is None else int(end)
+        frames = np.zeros((F, self.sensor_h, self.sensor_w), np.int32)
+        before, after = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.emba_seq_event_frames(self._ctx, int(beg), end, _p(edges, _i64p), F, 1 if signed_polarity else 0, _p(frames, _i32p), C.byref(before),
+                                                  C.byref(after)))
+        return frames, before.value, after.value
+
     def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
         """The smooth (fp64, real bilinear weights) contrast J = sum I^2 of the panorama of warped events of [beg, end) of the resident sequence along the
         linear SO(3) spline traj, and its gradient with respect to the increments of io.incremental_update (emba_seq_contrast_gradient; the rule:

@@ -24,7 +24,9 @@
 Inputs: events (.npz: x, y u16; polarity u8; t_ns i64), initial poses ("t tx ty tz qx qy qz qw" per line), initial map
 (Gx.bin / Gy.bin raw float64, H x 2H), calibration (.npz: K [3,3], D [<=5] plumb_bob, width, height).
 Outputs: <out>/refined_traj.txt, <out>/Gx.bin, <out>/Gy.bin (the files emba.cpp:300-330 writes), <out>/map_poisson_opt.pgm; with --record-data
-also the reference's record_data map images (solver.cpp:173-179, 332-336, 360-364): <out>/{Gx_evo,Gy_evo,G_hsv_evo,map_poisson_evo,map_opt}/*.png."""
+also the reference's record_data map images (solver.cpp:173-179, 332-336, 360-364): <out>/{Gx_evo,Gy_evo,G_hsv_evo,map_poisson_evo,map_opt}/*.png; with
+--views-hz (and --window-size) <out>/views/frame_%06d.pgm and times.txt, what the camera would have seen along the final trajectory, and with --view-events
+<out>/views/event_frames.npy."""
 import argparse
 import os
 import sys
@@ -89,6 +91,11 @@ def main():
     ap.add_argument("--refine", default="both", choices=["both", "map", "poses"], help="what the LM steps move: map and poses (the reference), the map only, or the poses only")
     ap.add_argument("--panorama-boundary", default="dirichlet", choices=["dirichlet", "wrap"], help="the boundary of the intensity panorama (map_poisson_opt.pgm and the "
                     "recorded map_poisson images): dirichlet, the reference's flat rectangle with a dark frame, or wrap: column W-1 is the neighbour of column 0 (DESIGN.md section 16)")
+    ap.add_argument("--views-hz", type=float, default=0.0, help="write <out>/views/frame_%%06d.pgm and views/times.txt: what the camera would have seen along the final "
+                    "trajectory at this many frames per second, sampled from the intensity panorama under --panorama-boundary with the panorama's own tone "
+                    "(with --window-size; DESIGN.md section 17; rank 0).  0: off")
+    ap.add_argument("--view-events", action="store_true", help="with --views-hz: also <out>/views/event_frames.npy, the signed event counts per sensor pixel between "
+                    "consecutive frames")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
     a = ap.parse_args()
     if a.alpha is None:
@@ -108,6 +115,12 @@ def main():
         ap.error("--record-contrast / --event-panorama / --refine-contrast need --window-size (they run on the resident sequence of a sliding-window run)")
     if a.contrast_prior and not a.refine_contrast:
         ap.error("--contrast-prior is the prior of --refine-contrast")
+    if not (np.isfinite(a.views_hz) and a.views_hz >= 0):
+        ap.error("--views-hz is finite and not negative")
+    if a.views_hz > 0 and not a.window_size:
+        ap.error("--views-hz needs --window-size (the views follow the trajectory of a sliding-window run)")
+    if a.view_events and not a.views_hz > 0:
+        ap.error("--view-events counts the events between the frames of --views-hz")
     if not (np.isfinite(a.contrast_prior_weight) and a.contrast_prior_weight >= 0):
         ap.error("--contrast-prior-weight is finite and not negative")
     os.makedirs(a.out, exist_ok=True)
@@ -197,7 +210,7 @@ def main():
                                init_poses="events" if a.init_poses == "events" else "given", cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
                                record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
                                contrast_iters=a.contrast_iters, contrast_levels=a.contrast_levels, contrast_prior=a.contrast_prior,
-                               contrast_prior_weight=a.contrast_prior_weight)
+                               contrast_prior_weight=a.contrast_prior_weight, views_hz=a.views_hz if rank == 0 else 0.0, view_events=a.view_events)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:
@@ -225,6 +238,23 @@ def main():
                     print(f"window {wr.index}: contrast of the warped events J = {j0:.6e} -> {j1:.6e} (x {j1 / max(j0, 1):.4f})")
             if sres.event_panorama is not None:
                 eio.save_png(os.path.join(a.out, "event_panorama.png"), eio.normalize_robust(sres.event_panorama.astype(np.float64), 0.1))
+            if sres.views is not None:
+                vw = sres.views
+                os.makedirs(os.path.join(a.out, "views"), exist_ok=True)
+                for f, img in enumerate(vw["u8"]):
+                    eio.save_pgm(os.path.join(a.out, "views", "frame_%06d.pgm" % f), img)
+                with open(os.path.join(a.out, "views", "times.txt"), "w") as fh:
+                    fh.write("".join("%d %d.%09d\n" % (f, tn // 1_000_000_000, tn % 1_000_000_000) for f, tn in enumerate(vw["t_ns"].tolist())))
+                if vw["event_frames"] is not None:
+                    np.save(os.path.join(a.out, "views", "event_frames.npy"), vw["event_frames"])
+                print(f"views: {len(vw['t_ns'])} frames at {a.views_hz:g} Hz under {a.out}/views, tone [{vw['lo']:.4g}, {vw['hi']:.4g}], "
+                      f"{int(vw['outside'].sum())} pixels past a pole row"
+                      + (f", {int(np.abs(vw['event_frames']).sum())} net events in {len(vw['event_frames'])} event frames" if vw["event_frames"] is not None else ""))
+                if vw["event_frames"] is not None and len(vw["event_frames"]) and vw["event_frames"].any():
+                    # the generative model: the brightness change between two predicted frames, over C_th, is the event count it expects at that pixel
+                    dv = np.diff(vw["views"], axis=0).ravel()
+                    print(f"views: correlation between V[f+1] - V[f] and the signed event frames {np.corrcoef(dv, vw['event_frames'].ravel().astype(np.float64))[0, 1]:+.4f} "
+                          f"(mean |dV| {np.abs(dv).mean():.4g}, C_th {C_th:g})")
         res = sres.windows[-1].result
         res = type(res)(sres.traj, res.cost_min, sum(wr.result.iterations for wr in sres.windows), all(wr.result.converged for wr in sres.windows), res.log, res.reason)
         if truth is not None:

@@ -478,6 +478,45 @@ emba_status emba_seq_contrast_gradient_prior(emba_ctx* ctx, size_t beg, size_t e
                                              double* image_out /* H_l*W_l or NULL */, uint64_t* dropped_out, double* pm_out /* [nn,2] or NULL */,
                                              double* d_out /* [nn,2,6] or NULL */, int32_t* cp_out /* [nn] or NULL */);
 
+/* ---- Sensor views along the trajectory: what the camera would have seen at a time t, a frame at sensor resolution sampled from a panorama
+ * plane, and what it reported between two times, the per-pixel event count of the resident sequence.  The brightness change between two predicted frames,
+ * over C_th, is the event count the generative model expects at that sensor pixel.
+ *
+ * emba_render_views: F frames at the times frame_t_ns [F] along the linear SO(3) spline (knots_xyzw [K, 4], t0_ns, dt_ns, as emba_eval_launch takes it).
+ *   source plane      plane_host: pano_h * pano_w doubles, any plane (an intensity panorama, a 0/1 coverage mask), uploaded into a buffer of the call's own.
+ *                     plane_host NULL: the intensity panorama of the resident map under `boundary` (EMBA_POISSON_DIRICHLET / EMBA_POISSON_WRAP_X), which the
+ *                     call reconstructs itself, as emba_render_map_images_bc does; `boundary` is read in that case only.
+ *   poses             the spline at every frame time (the pose kernel of the evaluation path, all F at once, into a table of this call's own).
+ *   warp              per frame and sensor pixel s = y * sensor_w + x: pm = project(R(frame) * bearing_lut[s]), the functions of emba_seq_event_panorama.
+ *   sample            ix = floor(pm_x), ax = pm_x - ix, iy, ay likewise.  The columns ix, ix + 1 wrap modulo pano_w, always (whatever `boundary` was).
+ *                     iy < 0 or iy + 1 > pano_h - 1 (and a pm that is not finite): the pixel is outside — views_out = fill, views_u8 = 0, counted in
+ *                     outside_out[f].  Otherwise v = (1 - ay) ((1 - ax) P[iy][ix] + ax P[iy][ix + 1]) + ay ((1 - ax) P[iy + 1][ix] + ax P[iy + 1][ix + 1]),
+ *                     in this order, without contraction (emba_amd/csrc/view_rule.h: view_sample).  No occlusion, no exposure model.
+ *   tone              views_u8 = sat(rint(scale (v - lo))), scale = 255 / (hi - lo), or 1 where hi == lo: the arithmetic of emba_normalize_robust.  A caller
+ *                     takes lo / hi from that call on the panorama, so the tone is constant across frames.  lo, hi are read with views_u8 only.
+ * Outputs, each may be NULL (with all of them NULL, or F = 0, nothing is launched): views_out [F, sensor_h, sensor_w] doubles, views_u8 the same in bytes,
+ * outside_out [F], pm_out [F, sensor_h * sensor_w, 2] (the seam the tests pin: emba_amd.io.render_views(plane, pm, fill) gives views_out bit for bit).
+ * Frames are rendered in chunks of at most 65 535 frames and 32 MiB of doubles (one frame at the least); F < 2^31.  The registered window, its order, the
+ * last evaluation and the buffers of the panorama and contrast calls are left as they are; with plane_host NULL the Poisson workspace is rewritten.
+ * EMBA_ERR_INVALID_ARG: knots or frame_t_ns NULL, K < 2, dt_ns <= 0, F >= 2^31, lo / hi not finite with views_u8; with plane_host NULL also the refusals of
+ * emba_reconstruct_intensity_bc's boundary.  EMBA_ERR_STATE: plane_host NULL and no map resident.  EMBA_ERR_TIME_RANGE: a frame time outside the knots
+ * (t < t0_ns or t >= t0_ns + (K - 1) dt_ns).  A refused call leaves every output untouched.  While emba_enable_kernel_timing is on, timer slot 7 brackets the
+ * view kernel of the first chunk.
+ *
+ * emba_seq_event_frames: F frames of signed event counts with the edges edge_t_ns [F + 1], strictly increasing.  EVERY event k of [beg, end) of the resident
+ * sequence counts — not whole batches of 100: no pose is involved.  Event k belongs to frame f when edge[f] <= t[k] < edge[f + 1]; its pixel of frame f
+ * gets +1, or -1 for polarity 0 where signed_polarity != 0.  Events before edge[0] are counted in *before_out, events at or after edge[F] in *after_out.
+ * frames_out: [F, sensor_h, sensor_w] int32; each output may be NULL.  Exact integers: emba_amd.io.event_frames gives the same bits.  Chunks of frames as
+ * above (32 MiB of int32); every chunk's launch sweeps the events of the range.  EMBA_ERR_STATE: no sequence resident.  EMBA_ERR_INVALID_ARG: not
+ * beg <= end <= n, edge_t_ns NULL or not strictly increasing, F >= 2^31 - 1.  A refused call leaves every output untouched.  Nothing else of the context
+ * is read or written.  Timer slot 7 as above. */
+emba_status emba_render_views(emba_ctx* ctx, const double* plane_host /* H*W or NULL */, int boundary, const int64_t* frame_t_ns, size_t F,
+                              const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, double fill, double lo, double hi,
+                              double* views_out /* [F, sh, sw] or NULL */, uint8_t* views_u8 /* [F, sh, sw] or NULL */, uint64_t* outside_out /* [F] or NULL */,
+                              double* pm_out /* [F, sh*sw, 2] or NULL */);
+emba_status emba_seq_event_frames(emba_ctx* ctx, size_t beg, size_t end, const int64_t* edge_t_ns /* F+1, strictly increasing */, size_t F,
+                                  int32_t signed_polarity, int32_t* frames_out /* [F, sh, sw] */, uint64_t* before_out, uint64_t* after_out);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
