@@ -68,7 +68,7 @@ struct GemmParams {
     int a_kstride, a_koff;   // A's reduction index k reads column a_koff + a_kstride * k (1, 0: plain; 2, parity: every other column — the folded DST)
 };
 
-constexpr int kGemmBM = 64, kGemmBK = 16;
+// (the block tiles kGemmBM, kGemmBK, kGemmBM2, kGemmBN2 and the rule that picks a kernel: poisson_rule.h)
 constexpr int kGemmLdA = kGemmBM + 16;   // k-major rows padded to 16 (mod 32) words: the 4 k-slices of an
                                                                   // MFMA operand read fall on disjoint bank halves
 
@@ -180,7 +180,6 @@ __global__ __launch_bounds__(256) void emba_dgemm_kernel(GemmParams p)
 // The same product with a 128 x 128 x 16 block tile and 512 threads (8 waves, 4 x 2, wave tile 32 x 64 as above): a third less operand traffic
 // from L2 per flop (the 64 x 128 tile above moves 0.8 GB through L2 for the 8.6 GFLOP of one folded DST product at 2048 x 4096 — 4 TB/s at its
 // 200 us).  Used when the output gives every CU a tile of this size.
-constexpr int kGemmBM2 = 128, kGemmBN2 = 128;
 __global__ __launch_bounds__(512) void emba_dgemm128_kernel(GemmParams p)
 {
     constexpr int LdA = kGemmBM2 + 16, LdB = kGemmBN2 + 16, NB = 4;
@@ -353,8 +352,8 @@ __global__ void emba_thomas_coef_kernel(const double* __restrict__ lam1, int H, 
 // Both are first-order linear recurrences  y_j = a_j y_prev + b_j  (a_j = -cp_j; b_j = cp_j g_j resp. y_j): a workgroup takes kTriSys
 // systems and cuts the j range into kTriChunks chunks — (A) every thread composes its chunk's affine map, (B) one thread per system
 // chains the chunks' maps, (C) every thread replays its chunk from the now known start value and writes the result.
-constexpr int kTriSys = 8, kTriChunks = 128;
-constexpr int kTriMaxQ = 32;    // elements per chunk the recomputing backward replay supports (W <= kTriChunks * kTriMaxQ = 4096; wider planes read the table)
+// kTriSys = 8, kTriChunks = 128 and kTriMaxQ = 32, the elements per chunk the recomputing backward replay supports (W <= kTriChunks * kTriMaxQ = 4096; wider
+// planes read the table), are poisson_rule.h's, with tri_chunk_len and tri_replay_from_table.
 // The Thomas factors are RECOMPUTED inside a chunk from the chunk's first stored one (c_j = 1 / (beta_i - c_{j-1}): one division per element,
 // on an otherwise idle VALU) instead of being streamed: a sweep read cp and the plane twice each — 335 MB at 2048 x 4096 — now 67 x 2 + 67 MB
 // of plane traffic and 128 factors per system.  (Same values: the table itself was filled by this recurrence, emba_thomas_coef_kernel.)
@@ -365,7 +364,7 @@ __global__ __launch_bounds__(kTriSys * kTriChunks) void emba_tridiag_sweep_kerne
     __shared__ double sA[kTriChunks][kTriSys], sB[kTriChunks][kTriSys], sY[kTriChunks][kTriSys];
     const int s = threadIdx.x % kTriSys, ch = threadIdx.x / kTriSys;
     const int i = blockIdx.x * kTriSys + s;
-    const int q = (W + kTriChunks - 1) / kTriChunks;
+    const int q = tri_chunk_len(W);
     const int j0 = ch * q, j1 = (j0 + q < W) ? j0 + q : W;
     const bool live = i < H && j0 < W;
     const double beta = live ? -2.0 + lam1[i] : -3.0;
@@ -398,7 +397,7 @@ __global__ __launch_bounds__(kTriSys * kTriChunks) void emba_tridiag_sweep_kerne
         for (int j = j0; j < j1; ++j) { c = 1.0 / (beta - c); const double g = v[(size_t)j * H + i]; y = c * (g - y); v[(size_t)j * H + i] = y; }
     } else {
         // descending replay needs c_j descending: the chunk's factors are kept from one ascending pass (q <= kTriMaxQ of them; longer chunks read the table)
-        if (q <= kTriMaxQ) {
+        if (!tri_replay_from_table(W)) {
             double cs[kTriMaxQ];
             double c = c_in;
 #pragma unroll

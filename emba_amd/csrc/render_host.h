@@ -67,7 +67,7 @@ extern "C" emba_status emba_reconstruct_intensity_bc(emba_ctx* c, const double* 
         hipLaunchKernelGGL(emba_tridiag_sweep_kernel<false>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_wrapq.as<double>(), H, W - 1);
         hipLaunchKernelGGL(emba_tridiag_sweep_kernel<true>, dim3(tb), dim3(kTriSys * kTriChunks), 0, s, c->d_thomas.as<double>(), c->d_lamH.as<double>(), c->d_wrapq.as<double>(), H, W - 1);
     }
-    const bool fold = !dense && (H % 2 == 0) && H >= 64 && c->opt_poisson != 2;
+    const bool fold = poisson_folds(H, c->opt_poisson);      // poisson_rule.h
     if (fold && (st = ensure<double>(c, c->d_Sfold, (size_t)H * H / 2, &fresh))) return st;
     if (fold && fresh) {
         hipLaunchKernelGGL(emba_sine_folded_kernel, dim3((unsigned)(((size_t)H * H / 2 + 255) / 256)), dim3(256), 0, s, H, c->d_Sfold.as<double>());
@@ -86,13 +86,14 @@ extern "C" emba_status emba_reconstruct_intensity_bc(emba_ctx* c, const double* 
         p.a_kstride = a_kstride; p.a_koff = a_koff;
         p.epilogue = epilogue; p.inv_norm = inv_norm;
         p.lam1 = c->d_lamH.as<double>(); p.lam2 = c->d_lamW.as<double>();
-        p.vec = ((K & 1) == 0 && (N & 1) == 0) ? 1 : 0;
-        const long tm = (M + kGemmBM - 1) / kGemmBM, wide = tm * ((N + 127) / 128), narrow = tm * ((N + 63) / 64);
-        const long big = ((M + kGemmBM2 - 1) / kGemmBM2) * ((N + kGemmBN2 - 1) / kGemmBN2);
-        const bool use_big = big >= (long)c->n_cu && !c->opt_gemm64;
-        if (use_big) hipLaunchKernelGGL(emba_dgemm128_kernel, dim3((unsigned)grid8(big)), dim3(512), 0, s, p);
-        else if (wide >= 2L * c->n_cu) hipLaunchKernelGGL(emba_dgemm_kernel<128>, dim3((unsigned)grid8(wide)), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(emba_dgemm_kernel<64>, dim3((unsigned)grid8(narrow)), dim3(256), 0, s, p);
+        p.vec = gemm_vec(K, N);
+        const GemmForm form = gemm_form(M, N, c->n_cu, c->opt_gemm64);      // poisson_rule.h
+        const dim3 grid((unsigned)grid8(gemm_tiles(M, N, form)));
+        switch (form) {
+        case GemmForm::k128x128: hipLaunchKernelGGL(emba_dgemm128_kernel, grid, dim3(512), 0, s, p); break;
+        case GemmForm::k64x128: hipLaunchKernelGGL(emba_dgemm_kernel<128>, grid, dim3(256), 0, s, p); break;
+        case GemmForm::k64x64: hipLaunchKernelGGL(emba_dgemm_kernel<64>, grid, dim3(256), 0, s, p); break;
+        }
     };
     if (dense) {
         // rhs -> eigenvector space, solve, back (laplace.cpp:633-758):  M = S_H ((S_H F S_W) o C) S_W
