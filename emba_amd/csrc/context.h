@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -244,6 +244,22 @@ struct ContrastPriors {
 // as bytes and as pm; outside: the count per frame.  emba_seq_event_frames: the edges, one chunk of int32 frames, ends: the events before and after.
 struct ViewBuffers { DevBuf plane, t, pose, knots, head, frames, u8, pm, outside, edge, counts, ends; };
 
+// Grow-only buffers of the intensity panorama (poisson_host.h).  The tables are made once per context, each when its buffer is new; the planes are scratch
+// of one solve.  Forms: dense (option poisson = 1) and Fourier (every other), the latter folded (poisson_folds) or not, under either boundary.
+struct PoissonBuffers {
+    DevBuf SH;        // table: the sine matrix S_H (H x H); every form makes it with lamH, the dense and the unfolded Fourier form multiply by it
+    DevBuf lamH;      // table: the eigenvalues lambda_H (H); every form
+    DevBuf SW;        // table: the sine matrix S_W (W x W); dense
+    DevBuf lamW;      // table: the eigenvalues lambda_W (W); dense
+    DevBuf thomas;    // table: the Thomas factors of T_W + lambda1[i] I (W x H); Fourier
+    DevBuf wrapq;     // table: q = T_{W-1}^-1 (e_0 + e_{W-2}) per H-frequency (W x H, row W-1 zero; poisson_rule.h); Fourier under EMBA_POISSON_WRAP_X
+    DevBuf Sfold;     // table: S_H folded by its symmetry, two (H/2 x H/2) blocks; folded Fourier
+    DevBuf Gx, Gy;    // planes: the caller's gradient maps, where the solve is given host planes and not the resident map; every form
+    DevBuf F;         // plane: the divergence and every second intermediate, and at the end of a solve the panorama M (H x W); every form
+    DevBuf T;         // plane: the other intermediate (Fourier: the transposed plane, W x H); every form
+    DevBuf EO;        // plane: [E | O] of a folded transform (W x H/2 each); folded Fourier
+};
+
 struct emba_ctx {
     emba_cfg cfg{};
     int device = 0;
@@ -381,12 +397,7 @@ struct emba_ctx {
         DevBuf pix_starts;   // emba_get_inlier_pixel_starts
         DevBuf A22b2;        // emba_form_finish: unpacked A22 | b2
     } dl;
-    // f3 (Poisson reconstruction): sine matrices and eigenvalues of the two transform lengths, scratch planes
-    DevBuf d_SH, d_SW, d_lamH, d_lamW, d_pF, d_pT, d_pGx, d_pGy;
-    DevBuf d_thomas;              // Thomas factors of T_W + lambda1[i] I (W x H)
-    DevBuf d_wrapq;               // boundary EMBA_POISSON_WRAP_X: q = T_{W-1}^-1 (e_0 + e_{W-2}) per H-frequency (W x H, row W-1 zero; poisson_rule.h)
-    DevBuf d_Sfold;               // the sine matrix folded by its symmetry: two (H/2 x H/2) blocks (even H)
-    DevBuf d_pE;                  // [E | O] of the folded transform (W x H/2 each)
+    PoissonBuffers poisson;       // f3, the intensity panorama from the gradient map (poisson_host.h)
     // record_data images (render_kernels.h): radix-select state, its histograms (zero between uses) and candidates, the 8-bit images, a host plane's upload
     DevBuf d_rstate, d_rhist, d_rcand;
     DevBuf d_img, d_nsrc;

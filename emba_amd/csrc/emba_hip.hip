@@ -3,7 +3,7 @@
 // header beside it: the context is context.h, copies into the caller's pageable memory transfer_host.h, the window and its order order_host.h / order_rule.h,
 // the step path (the evaluation and the normal equations) step_host.h / step_rule.h, the map map_host.h / map_rule.h, the downloads that wait on the step's
 // counters and emba_dump_state readback_host.h, the costs cost_host.h / cost_rule.h, the options options_host.h, the timers and probes timing_host.h, the
-// solvers (f1) solve_host.h / solve_rule.h, f3 and the record_data images render_host.h / poisson_rule.h, the resident event sequence sequence_host.h / sequence_rule.h,
+// solvers (f1) solve_host.h / solve_rule.h, f3 poisson_host.h / poisson_rule.h, the record_data images render_host.h, the resident event sequence sequence_host.h / sequence_rule.h,
 // contrast maximisation on it cmax_host.h / cmax_rule.h, the panorama of warped events panorama_host.h / panorama_rule.h and its smooth contrast and gradient
 // contrast_host.h / contrast_rule.h, the sensor views along the trajectory view_host.h / view_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
@@ -182,7 +182,8 @@ void emba_destroy(emba_ctx* c)
 #include "options_host.h"    // emba_set_option / emba_get_option: the one table
 #include "timing_host.h"     // the timers, kernel timing, the bracket overhead, the clock probe
 #include "solve_host.h"      // f1: the solvers
-#include "render_host.h"     // f3: the intensity panorama; the record_data map images
+#include "poisson_host.h"    // f3: the intensity panorama from the gradient map
+#include "render_host.h"     // the record_data map images (the panorama among them)
 #include "sequence_host.h"   // the resident event sequence of a sliding-window run: upload, windows, time shards and their halos, noise filters
 #include "cmax_host.h"       // contrast maximisation on it: the angular velocity of every slice of events, from the events alone
 #include "panorama_host.h"   // the panorama of warped events along a trajectory, and its contrast

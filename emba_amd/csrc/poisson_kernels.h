@@ -11,6 +11,8 @@
 // The transform lengths 2(n+1) = 2050 / 4098 have large prime factors (41, 683), so an FFT is the wrong tool here: the DST is
 // applied as a dense product with the symmetric sine matrix S_n[k][j] = 2 sin(pi (j+1)(k+1)/(n+1)) — a GEMM-shaped fp64 job,
 // the one place on this code path where MFMA is the bound:  M = S_H ((S_H F S_W) o C) S_W,  25.8 GFLOP at 1024 x 2048.
+// The host code that launches these is poisson_host.h; what both sides must agree on — the boundary rule, the divergence, the GEMM's block tiles, the
+// sweeps' chunks — is poisson_rule.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,22 +30,28 @@ __global__ void emba_divergence_kernel(const double* __restrict__ Gx, const doub
     if (idx >= (long)H * W) return;
     const int i = (int)(idx / W), j = (int)(idx % W);
     double f = 0.0;
-    if (i < H - 1 && j < W - 1) f = Gx[idx + 1] - Gx[idx] + Gy[idx + W] - Gy[idx];   // same association as the reference
+    if (i < H - 1 && j < W - 1) f = poisson_divergence(Gx[idx + 1], Gx[idx], Gy[idx + W], Gy[idx]);   // the reference's association (poisson_rule.h)
     F[idx] = f;
 }
 
-// S[k][j] = 2 sin(pi (j+1)(k+1) / (n+1)), row-major n x n (symmetric).  The argument is reduced in exact integer arithmetic
-// (period 2(n+1)) and folded to [0, (n+1)/2] before the sine, so every entry is accurate to the last bits.
+// 2 sin(pi p / m) for an integer product p >= 0.  The argument is reduced in exact integer arithmetic (period 2 m) and folded to [0, m/2] before the
+// sine, so every entry of the sine matrices is accurate to the last bits.
+__device__ inline double sine_entry(long p, long m)
+{
+    long r = p % (2 * m);
+    double sgn = 2.0;
+    if (r >= m) { r -= m; sgn = -2.0; }          // sin(x + pi) = -sin(x)
+    if (2 * r > m) r = m - r;                     // sin(pi - x) = sin(x)
+    return sgn * sin(3.14159265358979323846 * (double)r / (double)m);
+}
+
+// S[k][j] = 2 sin(pi (j+1)(k+1) / (n+1)), row-major n x n (symmetric)
 __global__ void emba_sine_matrix_kernel(int n, double* __restrict__ S)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)n * n) return;
-    const long k = idx / n, j = idx % n, m = n + 1;
-    long r = ((j + 1) * (k + 1)) % (2 * m);
-    double sgn = 2.0;
-    if (r >= m) { r -= m; sgn = -2.0; }          // sin(x + pi) = -sin(x)
-    if (2 * r > m) r = m - r;                     // sin(pi - x) = sin(x)
-    S[idx] = sgn * sin(3.14159265358979323846 * (double)r / (double)m);
+    const long k = idx / n, j = idx % n;
+    S[idx] = sine_entry((j + 1) * (k + 1), n + 1);
 }
 
 // lambda[k] = -4 sin^2(pi (k+1) / (2 (n+1)))   (laplace.cpp:700-704)
@@ -55,8 +63,8 @@ __global__ void emba_dirichlet_eigen_kernel(int n, double* __restrict__ lam)
     lam[k] = -4.0 * (s * s);
 }
 
-// C (M x N) = A (M x K) * B (K x N), all row-major fp64, on v_mfma_f64_16x16x4_f64.
-// Block tile 64 x 128 x 16, 256 threads = 4 waves in a 2 x 2 arrangement, each wave 32 x 64 = 2 x 4 MFMA tiles (32 accumulator
+// C (M x N) = A (M x K) * B (K x N), all row-major fp64, on v_mfma_f64_16x16x4_f64: one kernel, three block tiles (GemmForm / gemm_tile, poisson_rule.h).
+// At 64 x 128 x 16: 256 threads = 4 waves in a 2 x 2 arrangement, each wave 32 x 64 = 2 x 4 MFMA tiles (32 accumulator
 // doubles per lane).  A and B tiles go global -> registers -> LDS (k-major, so that the operand reads of the MFMA layout — lane l
 // holds element (l&15) at k = l>>4 — are consecutive 8-B words), double-buffered: the next tile's global loads are in flight
 // while the current tile's 4 k-steps x 8 MFMAs run.  12 FLOP per byte loaded from L2; MFMA-bound (fp64 matrix peak 78.6 TFLOP/s).
@@ -68,21 +76,28 @@ struct GemmParams {
     int a_kstride, a_koff;   // A's reduction index k reads column a_koff + a_kstride * k (1, 0: plain; 2, parity: every other column — the folded DST)
 };
 
-// (the block tiles kGemmBM, kGemmBK, kGemmBM2, kGemmBN2 and the rule that picks a kernel: poisson_rule.h)
-constexpr int kGemmLdA = kGemmBM + 16;   // k-major rows padded to 16 (mod 32) words: the 4 k-slices of an
-                                                                  // MFMA operand read fall on disjoint bank halves
-
-// BN = 128 (wave tile 32 x 64) or 64 (wave tile 32 x 32: twice the blocks, for outputs too small to give every CU two of the wide ones)
-template <int kGemmBN>
-__global__ __launch_bounds__(256) void emba_dgemm_kernel(GemmParams p)
+// The block tile BM x BN x 16 on THREADS threads; everything else follows.  The waves stand WM x WN (rows x columns), each on a wave tile of
+// 32 x BN / WN = 2 x NB MFMA tiles; a thread stages 4 doubles of A and BQ of B per k-tile.  The instantiations (gemm_tile, poisson_rule.h):
+//   64 x 64, 256 threads    waves 2 x 2, wave tile 32 x 32, BQ 4: twice the blocks, for outputs too small to give every CU two of the wide ones
+//   64 x 128, 256 threads   waves 2 x 2, wave tile 32 x 64, BQ 8
+//   128 x 128, 512 threads  waves 4 x 2, wave tile 32 x 64, BQ 4: a third less operand traffic from L2 per flop (the 64 x 128 tile moves 0.8 GB through L2
+//                           for the 8.6 GFLOP of one folded DST product at 2048 x 4096 — 4 TB/s at its 200 us); where the output gives every CU such a tile
+template <int BM, int BN, int THREADS>
+__global__ __launch_bounds__(THREADS) void emba_dgemm_kernel(GemmParams p)
 {
-    constexpr int kGemmLdB = kGemmBN + 16, NB = kGemmBN / 32, BQ = kGemmBN / 16;   // MFMA column tiles per wave; B doubles staged per thread
+    constexpr int WM = BM / 32, WN = THREADS / 64 / WM, NB = BN / WN / 16;   // rows and columns of waves; MFMA column tiles per wave
+    constexpr int BQ = kGemmBK * BN / THREADS, BT = BN / BQ;                  // B doubles staged per thread; threads per row of the B tile
+    constexpr int kGemmLdA = BM + 16, kGemmLdB = BN + 16;   // k-major rows padded to 16 (mod 32) words: the 4 k-slices of an MFMA operand read fall on disjoint bank halves
+    static_assert(BM % 32 == 0 && THREADS % 64 == 0 && WM * WN * 64 == THREADS, "the waves tile the block in rows of 32");
+    static_assert(BN % (16 * WN) == 0 && NB >= 1, "a wave tile is whole MFMA tiles wide");
+    static_assert(4 * BM == THREADS, "A staging: a thread takes 4 of a row's 16 k");
+    static_assert(BQ * THREADS == kGemmBK * BN && BQ % 2 == 0 && BN % BQ == 0, "B staging: a thread takes BQ consecutive columns of one k, in 16-B pairs");
     __shared__ __attribute__((aligned(16))) double sA[2][kGemmBK * kGemmLdA];
     __shared__ __attribute__((aligned(16))) double sB[2][kGemmBK * kGemmLdB];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const int el = lane & 15, kk = lane >> 4;
     // XCD-aware tile order: the 8 XCDs take contiguous runs of tile rows, so the B panels an XCD streams stay in its own L2
-    const int tiles_n = (p.N + kGemmBN - 1) / kGemmBN, tiles_m = (p.M + kGemmBM - 1) / kGemmBM;
+    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
     const long n_tiles = (long)tiles_m * tiles_n;
     long bid = blockIdx.x;
     {
@@ -90,12 +105,12 @@ __global__ __launch_bounds__(256) void emba_dgemm_kernel(GemmParams p)
         bid = (bid & 7) * per + (bid >> 3);
         if (bid >= n_tiles) return;   // (whole block; before any barrier)
     }
-    const int m0 = (int)(bid / tiles_n) * kGemmBM, n0 = (int)(bid % tiles_n) * kGemmBN;
-    const int wm = (wv & 1) * 32, wn = (wv >> 1) * (kGemmBN / 2);
+    const int m0 = (int)(bid / tiles_n) * BM, n0 = (int)(bid % tiles_n) * BN;
+    const int wm = (wv % WM) * 32, wn = (wv / WM) * (BN / WN);
 
-    // global -> register staging: A tile 64 x 16 (4 doubles per thread: row t/4, k (t%4)*4..+3), B tile 16 x 128 (8 per thread: k t/16, cols (t%16)*8..+7)
+    // global -> register staging: A tile BM x 16 (4 doubles per thread: row t/4, k (t%4)*4..+3), B tile 16 x BN (BQ per thread: k t/BT, cols (t%BT)*BQ..+BQ-1)
     const int a_row = t >> 2, a_k = (t & 3) * 4;
-    const int b_k = t >> 4, b_col = (t & 15) * BQ;
+    const int b_k = t / BT, b_col = (t % BT) * BQ;
     double ra[4], rb[BQ];
     auto load_tile = [&](int k0) {
         const int gr = m0 + a_row;
@@ -177,106 +192,6 @@ __global__ __launch_bounds__(256) void emba_dgemm_kernel(GemmParams p)
             }
 }
 
-// The same product with a 128 x 128 x 16 block tile and 512 threads (8 waves, 4 x 2, wave tile 32 x 64 as above): a third less operand traffic
-// from L2 per flop (the 64 x 128 tile above moves 0.8 GB through L2 for the 8.6 GFLOP of one folded DST product at 2048 x 4096 — 4 TB/s at its
-// 200 us).  Used when the output gives every CU a tile of this size.
-__global__ __launch_bounds__(512) void emba_dgemm128_kernel(GemmParams p)
-{
-    constexpr int LdA = kGemmBM2 + 16, LdB = kGemmBN2 + 16, NB = 4;
-    __shared__ __attribute__((aligned(16))) double sA[2][kGemmBK * LdA];
-    __shared__ __attribute__((aligned(16))) double sB[2][kGemmBK * LdB];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int el = lane & 15, kk = lane >> 4;
-    const int tiles_n = (p.N + kGemmBN2 - 1) / kGemmBN2, tiles_m = (p.M + kGemmBM2 - 1) / kGemmBM2;
-    const long n_tiles = (long)tiles_m * tiles_n;
-    long bid = blockIdx.x;
-    {
-        const long per = (n_tiles + 7) / 8;
-        bid = (bid & 7) * per + (bid >> 3);
-        if (bid >= n_tiles) return;
-    }
-    const int m0 = (int)(bid / tiles_n) * kGemmBM2, n0 = (int)(bid % tiles_n) * kGemmBN2;
-    const int wm = (wv & 3) * 32, wn = (wv >> 2) * 64;
-    // staging: A tile 128 x 16 (4 doubles per thread: row t/4, k (t%4)*4..+3), B tile 16 x 128 (4 per thread: k t/32, cols (t%32)*4..+3)
-    const int a_row = t >> 2, a_k = (t & 3) * 4;
-    const int b_k = t >> 5, b_col = (t & 31) * 4;
-    double ra[4], rb[4];
-    auto load_tile = [&](int k0) {
-        const int gr = m0 + a_row;
-        if (p.vec && p.a_kstride == 1 && gr < p.M && k0 + a_k + 3 < p.K) {
-            const double2* q2 = reinterpret_cast<const double2*>(p.A + (size_t)p.lda * gr + k0 + a_k);
-            const double2 v0 = q2[0], v1 = q2[1];
-            ra[0] = v0.x; ra[1] = v0.y; ra[2] = v1.x; ra[3] = v1.y;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int gk = k0 + a_k + q;
-                ra[q] = (gr < p.M && gk < p.K) ? p.A[(size_t)p.lda * gr + p.a_koff + (size_t)p.a_kstride * gk] : 0.0;
-            }
-        }
-        const int gk = k0 + b_k;
-        if (p.vec && gk < p.K && n0 + b_col + 3 < p.N) {
-            const double2* q2 = reinterpret_cast<const double2*>(p.B + (size_t)p.ldb * gk + n0 + b_col);
-            const double2 v0 = q2[0], v1 = q2[1];
-            rb[0] = v0.x; rb[1] = v0.y; rb[2] = v1.x; rb[3] = v1.y;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int gc = n0 + b_col + q;
-                rb[q] = (gk < p.K && gc < p.N) ? p.B[(size_t)p.ldb * gk + gc] : 0.0;
-            }
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sA[buf][(a_k + q) * LdA + a_row] = ra[q];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sB[buf][b_k * LdB + b_col + q] = rb[q];
-    };
-    pdouble4_t acc[2][NB];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[a][b] = pdouble4_t{0.0, 0.0, 0.0, 0.0};
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = 0; k0 < p.K; k0 += kGemmBK) {
-        const bool more = k0 + kGemmBK < p.K;
-        if (more) load_tile(k0 + kGemmBK);
-#pragma unroll
-        for (int ks = 0; ks < kGemmBK; ks += 4) {
-            double av[2], bv[NB];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) av[a] = sA[buf][(ks + kk) * LdA + wm + 16 * a + el];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) bv[b] = sB[buf][(ks + kk) * LdB + wn + 16 * b + el];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        if (more) store_tile(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wm + 16 * a + kk + 4 * r, col = n0 + wn + 16 * b + el;
-                if (row < p.M && col < p.N) {
-                    double v = acc[a][b][r];
-                    if (p.epilogue == 1) v = (v * p.inv_norm) / (p.lam1[row] + p.lam2[col]);
-                    else if (p.epilogue == 2) v = v * p.inv_norm;
-                    p.C[(size_t)p.ldc * row + col] = v;
-                }
-            }
-}
-
 // ---- Fourier analysis along ONE axis + tridiagonal solves along the other ------------------------------------------------------------
 // The Dirichlet solve of laplace.cpp:587-797 is  M = S_H ((S_H F S_W) o C) S_W,  C[i][k] = 1 / (4 (H+1)(W+1) (lambda1[i] + lambda2[k])).
 // S_W / sqrt(2 (W+1)) is the orthogonal eigenbasis of the 1-D second-difference operator T_W = tridiag(1, -2, 1), eigenvalues lambda2, so
@@ -294,7 +209,9 @@ __global__ __launch_bounds__(256) void emba_transpose_kernel(const double* __res
     for (int r = ty; r < 32; r += 8) { const int y = bx + r, x = by + tx; if (y < cols && x < rows) dst[(size_t)y * rows + x] = tile[tx][r]; }
 }
 
-// F^T straight from the gradient maps (the divergence of emba_divergence_kernel, written transposed: one pass instead of two)
+// F^T straight from the gradient maps (the divergence of emba_divergence_kernel, written transposed: one pass instead of two).  WRAP (boundary
+// EMBA_POISSON_WRAP_X, poisson_rule.h): every column j < W is live and its right neighbour is (j + 1) mod W; else the last column is 0 like the last row.
+template <bool WRAP>
 __global__ __launch_bounds__(256) void emba_divergence_T_kernel(const double* __restrict__ Gx, const double* __restrict__ Gy, int H, int W, double* __restrict__ FT)
 {
     __shared__ double tile[32][33];
@@ -302,7 +219,10 @@ __global__ __launch_bounds__(256) void emba_divergence_T_kernel(const double* __
     for (int r = ty; r < 32; r += 8) {
         const int i = by + r, j = bx + tx;
         double f = 0.0;
-        if (i < H - 1 && j < W - 1) { const size_t idx = (size_t)i * W + j; f = Gx[idx + 1] - Gx[idx] + Gy[idx + W] - Gy[idx]; }   // same association as the reference
+        if (i < H - 1 && j < (WRAP ? W : W - 1)) {
+            const size_t row = (size_t)i * W, idx = row + j;
+            f = poisson_divergence(Gx[WRAP ? row + poisson_wrap_right(j, W) : idx + 1], Gx[idx], Gy[idx + W], Gy[idx]);
+        }
         tile[r][tx] = f;
     }
     __syncthreads();
@@ -418,12 +338,8 @@ __global__ void emba_sine_folded_kernel(int n, double* __restrict__ Sf)
 {
     const long h = n / 2, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= 2 * h * h) return;
-    const long parity = idx / (h * h), rem = idx % (h * h), jp = rem / h, k = rem % h, m = n + 1;
-    long r = ((2 * jp + parity + 1) * (k + 1)) % (2 * m);
-    double sgn = 2.0;
-    if (r >= m) { r -= m; sgn = -2.0; }
-    if (2 * r > m) r = m - r;
-    Sf[idx] = sgn * sin(3.14159265358979323846 * (double)r / (double)m);
+    const long parity = idx / (h * h), rem = idx % (h * h), jp = rem / h, k = rem % h;
+    Sf[idx] = sine_entry((2 * jp + parity + 1) * (k + 1), n + 1);
 }
 // y[row][k] = (E + O) * scale, y[row][n-1-k] = (E - O) * scale from EO = [E (rows x n/2) | O (rows x n/2)] stored as two planes
 __global__ void emba_dst_butterfly_kernel(const double* __restrict__ E, const double* __restrict__ O, int rows, int n, double scale, double* __restrict__ y)
@@ -437,27 +353,9 @@ __global__ void emba_dst_butterfly_kernel(const double* __restrict__ E, const do
 }
 
 // ---- boundary EMBA_POISSON_WRAP_X: the columns wrap, the poles stay Dirichlet (poisson_rule.h states the rule) -----------------------------
-// Only the W direction differs from the solve above: the divergence gains its last column, and the tridiagonal systems become the cyclic ones
+// Only the W direction differs from the solve above: the divergence gains its last column (emba_divergence_T_kernel<true>), and the tridiagonal systems become the cyclic ones
 // (C_W + lambda1[i] I) x = g.  Condensed on x[W-1] they are the SAME sweeps over the first W-1 rows of the transposed plane (the Thomas recurrence does
 // not depend on the length: the first W-1 rows of the factor table are T_{W-1}'s), then two small passes: the pivot t per system, and x = p - t q.
-
-// F^T with the wrapped column: emba_divergence_T_kernel's tiles, every column j < W live, its right neighbour (j + 1) mod W
-__global__ __launch_bounds__(256) void emba_divergence_T_wrap_kernel(const double* __restrict__ Gx, const double* __restrict__ Gy, int H, int W, double* __restrict__ FT)
-{
-    __shared__ double tile[32][33];
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8) {
-        const int i = by + r, j = bx + tx;
-        double f = 0.0;
-        if (i < H - 1 && j < W) {
-            const size_t row = (size_t)i * W, idx = row + j;
-            f = poisson_divergence(Gx[row + poisson_wrap_right(j, W)], Gx[idx], Gy[idx + W], Gy[idx]);
-        }
-        tile[r][tx] = f;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) { const int j = bx + r, i = by + tx; if (j < W && i < H) FT[(size_t)j * H + i] = tile[tx][r]; }
-}
 
 // The right-hand side of q = T_{W-1}^-1 (e_0 + e_{W-2}) for every system i, on the transposed plane (W x H, every row written: row W-1, which no sweep
 // over W-1 rows touches and no pass reads, is 0).  The two sweeps above over its first W-1 rows make it q.  Once per context, like the Thomas factors.

@@ -1,4 +1,4 @@
-// emba_amd/csrc/poisson_rule.h — the boundary rules of the intensity panorama (render_host.h, poisson_kernels.h) as functions of plain values: the boundary
+// emba_amd/csrc/poisson_rule.h — the boundary rules of the intensity panorama (poisson_host.h, poisson_kernels.h) as functions of plain values: the boundary
 // argument's check, the smallest width a wrapped panorama may have, the divergence of a panorama whose columns wrap, and the closing step of the cyclic
 // systems along W.  tests/poisson_wrap_ref.py is the same rule in numpy (its spectral form); include/emba_hip.h (EMBA_POISSON_WRAP_X) states it in words.
 // Below them the launch plan of the solve: the fold of the DST, the GEMM kernel of a product and its loads, the chunks of the Thomas sweeps.
@@ -57,7 +57,7 @@ EMBA_RULE_HD inline double poisson_wrap_close(double p, double t, double q)
     return p - t * q;
 }
 
-// ---- the launch plan of the Fourier form (render_host.h): whether the DST along H folds, which GEMM kernel a product runs on and how it loads its
+// ---- the launch plan of the Fourier form (poisson_host.h): whether the DST along H folds, which GEMM kernel a product runs on and how it loads its
 // operands, how the Thomas sweeps cut the W direction and how the backward sweep replays a chunk.  tests/poisson_edge_cases.py states the same in Python.
 
 // The DST-I of even length H as two half-size products and a butterfly (poisson_kernels.h, emba_sine_folded_kernel).  Option poisson: 1 dense sine
@@ -69,30 +69,34 @@ inline bool poisson_folds(int H, int opt_poisson)
     return !dense && (H % 2 == 0) && H >= kPoissonFoldMinH && opt_poisson != 2;
 }
 
-// Block tiles of the three fp64 MFMA GEMM kernels: 64 x 64 and 64 x 128 (emba_dgemm_kernel<64>, <128>), 128 x 128 (emba_dgemm128_kernel), all k-tile 16.
-constexpr int kGemmBM = 64, kGemmBK = 16;
-constexpr int kGemmBM2 = 128, kGemmBN2 = 128;
+// The three forms of the fp64 MFMA GEMM kernel (poisson_kernels.h, emba_dgemm_kernel<BM, BN, THREADS>) and the block tile of each, stated here once:
+// the kernel's instantiations, the choice of a form and the grid all read gemm_tile.  The k-tile is 16 for all; a thread stages 16 BN / THREADS doubles of B.
+constexpr int kGemmBK = 16;
 enum class GemmForm { k64x64, k64x128, k128x128 };
-// The 128 x 128 kernel where the output gives every CU a tile of that size (a third less operand traffic per flop); else the 64 x 128 kernel where it
-// gives every CU two; else twice the blocks of 64 x 64.  Option gemm64 keeps the 64-row kernels (comparison form).
-inline GemmForm gemm_form(int M, int N, int n_cu, int opt_gemm64)
+struct GemmTile { int bm, bn, threads, b_per_thread; };      // block rows, block columns, threads, B doubles a thread stages per k-tile
+constexpr GemmTile gemm_tile_of(int bm, int bn, int threads) { return GemmTile{bm, bn, threads, kGemmBK * bn / threads}; }
+constexpr GemmTile gemm_tile(GemmForm f)
 {
-    const long tm = (M + kGemmBM - 1) / kGemmBM, wide = tm * ((N + 127) / 128);
-    const long big = (long)((M + kGemmBM2 - 1) / kGemmBM2) * ((N + kGemmBN2 - 1) / kGemmBN2);
-    if (big >= (long)n_cu && !opt_gemm64) return GemmForm::k128x128;
-    if (wide >= 2L * n_cu) return GemmForm::k64x128;
-    return GemmForm::k64x64;
+    return f == GemmForm::k128x128 ? gemm_tile_of(128, 128, 512) : f == GemmForm::k64x128 ? gemm_tile_of(64, 128, 256) : gemm_tile_of(64, 64, 256);
 }
 // tiles a form's launch covers (the grid is this, rounded up to the 8 XCDs)
 inline long gemm_tiles(int M, int N, GemmForm f)
 {
-    const int bm = f == GemmForm::k128x128 ? kGemmBM2 : kGemmBM, bn = f == GemmForm::k64x64 ? 64 : 128;
-    return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+    const GemmTile t = gemm_tile(f);
+    return (long)((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
+}
+// The 128 x 128 form where the output gives every CU a tile of that size (a third less operand traffic per flop); else the 64 x 128 form where it
+// gives every CU two; else twice the blocks of 64 x 64.  Option gemm64 keeps the 64-row forms (comparison form).
+inline GemmForm gemm_form(int M, int N, int n_cu, int opt_gemm64)
+{
+    if (gemm_tiles(M, N, GemmForm::k128x128) >= (long)n_cu && !opt_gemm64) return GemmForm::k128x128;
+    if (gemm_tiles(M, N, GemmForm::k64x128) >= 2L * n_cu) return GemmForm::k64x128;
+    return GemmForm::k64x64;
 }
 // 16-B operand loads on interior tiles: every row of A (lda = K or an even multiple of it) and of B (ldb = N) then starts 16-B aligned
 inline int gemm_vec(int K, int N) { return ((K & 1) == 0 && (N & 1) == 0) ? 1 : 0; }
 
-// The products of one solve in launch order, as render_host.h writes them out with their operands: C (M x N) = A (M x K) B (K x N), A's rows lda apart and
+// The products of one solve in launch order, as poisson_host.h writes them out with their operands: C (M x N) = A (M x K) B (K x N), A's rows lda apart and
 // its reduction index reading every a_kstride-th column.  Dense: S_H and S_W products on the plane itself.  Otherwise everything runs on the transposed
 // plane (W x H): two DSTs along H, each one product, or folded two half-size products on the even- and odd-indexed columns.  Returns how many.
 struct PoissonProduct { int M, N, K; long lda; int a_kstride; };

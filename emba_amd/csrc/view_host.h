@@ -2,7 +2,7 @@
 // given times, sampled from a panorama plane (emba_render_views), and the per-pixel event counts of the resident sequence between given times
 // (emba_seq_event_frames).  What is plain arithmetic — the sample, the tone, the frame of a timestamp, the chunks — is decided in view_rule.h; here are the
 // buffers (emba_ctx::view), the launches and the C ABI.
-// Part of emba_hip.hip's translation unit, included by it below render_host.h (emba_reconstruct_intensity_bc, poisson_boundary_check), sequence_host.h
+// Part of emba_hip.hip's translation unit, included by it below poisson_host.h (poisson_boundary_check, poisson_solve), sequence_host.h
 // (SEQ_TRY; the sequence itself: emba_ctx::evseq) and transfer_host.h (d2h_pageable).  Nothing of the registered window, of the pose stage of the panorama
 // calls (emba_ctx::seq_pose) or of their buffers is read or written.
 #pragma once
@@ -50,15 +50,13 @@ extern "C" emba_status emba_render_views(emba_ctx* c, const double* plane_host, 
     HIP_TRY(c, hipStreamSynchronize(s));      // (the caller's knots and frame times have been read; a frame outside the knots is refused before anything is rendered)
     if ((int)(word & 0xFFFFFFFFull) & 1) return fail(c, EMBA_ERR_TIME_RANGE, "a frame time lies outside the spline's knots");
     // source plane
-    const double* plane;
+    const double* plane = nullptr;
     if (plane_host) {
         SEQ_TRY(ensure<double>(c, B.plane, c->npix));
         HIP_TRY(c, hipMemcpyAsync(B.plane.p, plane_host, c->npix * sizeof(double), hipMemcpyHostToDevice, s));
         plane = B.plane.as<double>();
-    } else {
-        SEQ_TRY(emba_reconstruct_intensity_bc(c, nullptr, nullptr, nullptr, boundary));      // M stays in c->d_pF
-        plane = c->d_pF.as<double>();
-    }
+    } else SEQ_TRY(poisson_solve(c, nullptr, nullptr, nullptr, boundary, &plane));      // the panorama of the resident map, on the device
+
     // frames, chunk by chunk
     const size_t per = view_chunk_frames(S, sizeof(double)), chunks = view_chunk_count(F, per), cap = std::min(per, F) * S;
     if (views_out) SEQ_TRY(ensure<double>(c, B.frames, cap));

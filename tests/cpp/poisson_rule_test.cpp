@@ -2,7 +2,8 @@
 // the closing step of the cyclic systems (C_W + (beta + 2) I) x = g — Thomas sweeps of T_{W-1} by the recurrence the kernels use (c_j = 1 / (beta - c_{j-1})),
 // then poisson_wrap_pivot and poisson_wrap_close — against dense Gaussian elimination with partial pivoting.
 // Built and run by tests/test_poisson_wrap_cpu.py.  Also the launch plan at its thresholds (the fold, the GEMM kernel and its loads, the sweeps' chunks
-// and replay), and, with the argument `plan`, the plan of every case on stdin: tests/test_poisson_edge_cases_cpu.py compares it with its Python statement.
+// and replay), and, with the argument `plan`, the plan of every case on stdin: tests/test_poisson_edge_cases_cpu.py compares it with its Python statement,
+// as it does the GEMM forms' tile table, printed with the argument `tiles`.
 //
 // The bound.  The cyclic matrix is symmetric with eigenvalues beta + 2 cos(2 pi k / W), all in [beta - 2, beta + 2] and negative: its condition number is at
 // most cond = (|beta| + 2) / (|beta| - 2).  Elimination with pivoting and the condensed Thomas solve are each backward stable to a few W eps on these
@@ -104,6 +105,17 @@ static int print_plans()
     return 0;
 }
 
+// `tiles`: per GEMM form `name block_rows block_columns threads b_doubles_per_thread`, from the one table the kernel's instantiations, gemm_form and
+// gemm_tiles read.  tests/test_poisson_edge_cases_cpu.py compares it with TILE and THREAD_COLS of tests/poisson_edge_cases.py.
+static int print_tiles()
+{
+    for (GemmForm f : {GemmForm::k64x64, GemmForm::k64x128, GemmForm::k128x128}) {
+        const GemmTile t = gemm_tile(f);
+        std::printf("%s %d %d %d %d\n", form_name(f), t.bm, t.bn, t.threads, t.b_per_thread);
+    }
+    return 0;
+}
+
 // ---- the launch plan at its thresholds
 static void check_plan()
 {
@@ -151,6 +163,7 @@ static void check_plan()
 int main(int argc, char** argv)
 {
     if (argc > 1 && std::string(argv[1]) == "plan") return print_plans();
+    if (argc > 1 && std::string(argv[1]) == "tiles") return print_tiles();
     check_plan();
 
     // ---- the boundary argument

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE (no HIP in here): the intensity panorama (emba_amd/csrc/render_host.h, poisson_kernels.h) at every tile, fold and sweep-chunk edge —
+"""TEST INFRASTRUCTURE (no HIP in here): the intensity panorama (emba_amd/csrc/poisson_host.h, poisson_kernels.h) at every tile, fold and sweep-chunk edge —
 the launch plan of emba_amd/csrc/poisson_rule.h restated in Python, the case table tests/test_poisson_edge_cases_cpu.py (the plan, its coverage, the numpy
 references) and tests/test_gpu_poisson_edges.py (the device) share, and the suite's random planes.
 

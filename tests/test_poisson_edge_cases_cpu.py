@@ -44,6 +44,18 @@ def test_the_python_plan_is_the_rule_headers(rule_exe):
     print(cpp_plans(rule_exe, [f"{c.H} {c.W} {E.N_CU} {c.options.get('gemm64', 0)} {c.options.get('poisson', 0)} {int(c.boundary == E.WRAP)}\n" for c in E.CASES]))
 
 
+def test_the_python_tiles_are_the_rule_headers(rule_exe):
+    """TILE and THREAD_COLS against the one tile table of poisson_rule.h (gemm_tile), which the kernel's instantiations, gemm_form and gemm_tiles read."""
+    r = subprocess.run([rule_exe, "tiles"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr
+    print(r.stdout)
+    rows = {f[0]: tuple(int(v) for v in f[1:]) for f in (line.split() for line in r.stdout.splitlines())}
+    assert set(rows) == set(FORMS) == set(E.TILE) == set(E.THREAD_COLS)
+    for form, (bm, bn, threads, b_per_thread) in rows.items():
+        assert (bm, bn) == E.TILE[form] and b_per_thread == E.THREAD_COLS[form], form
+        assert b_per_thread * threads == E.GEMM_BK * bn and 4 * bm == threads, form      # the staging: a B tile of 16 x bn, an A tile of bm x 16 in fours
+
+
 def test_every_case_takes_the_form_its_row_names():
     for c in E.CASES:
         assert {p[6] for p in c.plan()["products"]} == set(c.forms), c
