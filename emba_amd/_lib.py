@@ -121,6 +121,11 @@ SIGNATURES = {
     "emba_render_views": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
                                     _dp, _u8p, C.POINTER(C.c_uint64), _dp]),
     "emba_seq_event_frames": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _i64p, C.c_size_t, C.c_int32, _i32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "emba_simulate_events": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32,
+                                       C.c_uint64, C.POINTER(C.c_uint64)]),
+    "emba_sim_size": (C.c_int, [C.c_void_p, _szp]),
+    "emba_sim_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _u8p, _i64p]),
+    "emba_seq_from_sim": (C.c_int, [C.c_void_p, C.c_int32, _szp]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

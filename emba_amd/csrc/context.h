@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, sim_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -244,6 +244,17 @@ struct ContrastPriors {
 // as bytes and as pm; outside: the count per frame.  emba_seq_event_frames: the edges, one chunk of int32 frames, ends: the events before and after.
 struct ViewBuffers { DevBuf plane, t, pose, knots, head, frames, u8, pm, outside, edge, counts, ends; };
 
+// The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
+// the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
+// [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
+// chunk of samples and the frame in front of it; outside: the view kernel's count per frame (the simulator counts for itself); cells: events per (step,
+// pixel) of a chunk, then their offsets; ref / armed: the pixels' state in front of and behind a chunk; sums: positive events, capped and outside cells;
+// total: the chunk's number of events; ev_t, ev_sp: a chunk's events as emitted (the sort pairs are the order preparation's, as emba_seq_filter's are).
+struct SimState {
+    DevBuf x, y, pol, t, x2, y2, pol2, t2; size_t n = 0; bool have = false; uint64_t stats[4] = {0, 0, 0, 0};
+    DevBuf plane, step_t, pose, knots, head, frames, outside, cells, ref[2], armed[2], sums, total, ev_t, ev_sp;
+};
+
 // Grow-only buffers of the intensity panorama (poisson_host.h).  The tables are made once per context, each when its buffer is new; the planes are scratch
 // of one solve.  Forms: dense (option poisson = 1) and Fourier (every other), the latter folded (poisson_folds) or not, under either boundary.
 struct PoissonBuffers {
@@ -428,6 +439,7 @@ struct emba_ctx {
     int opt_contrast_vote = -1;   // option contrast_vote: the vote kernel of a level call — -1 by the image's size (contrast_rule.h: contrast_vote_plan), 0 HBM, 1 LDS where it fits
     int contrast_vote_path = -1;  // the vote kernel the last contrast call launched: 0 HBM, 1 LDS; -1 none yet (emba_get_option "contrast_vote_path")
     ViewBuffers view;             // sensor views along the trajectory: predicted frames and event frames (view_host.h)
+    SimState sim;                 // the event simulator: the simulated recording and the scratch of a call (sim_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

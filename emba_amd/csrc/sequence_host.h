@@ -38,6 +38,39 @@ extern "C" emba_status emba_seq_size(const emba_ctx* c, size_t* n)
     return EMBA_OK;
 }
 
+namespace {
+// The two ends of an ingest of n raw events into the resident sequence, whatever memory they come from (emba_seq_upload: the caller's; emba_seq_from_sim:
+// the simulator's).  Begin: the stream drained, the sequence that goes and its contrast priors dropped, the arrays of the n_kept events and the status
+// words ready (0xFF: clean).  Finish: the ingest kernel's two words read; the sequence is resident when both are clean.
+emba_status seq_ingest_begin(emba_ctx* c, size_t n_kept)
+{
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
+    c->priors.drop();                           // (the contrast priors are votes of the sequence that goes)
+    emba_status st;
+    if ((st = ensure<uint32_t>(c, c->evseq.status, kStatusWords)) ||
+        (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
+        (st = ensure<uint8_t>(c, c->evseq.pol, std::max<size_t>(n_kept, 1))) || (st = ensure<int64_t>(c, c->evseq.t, std::max<size_t>(n_kept, 1))))
+        return st;
+    HIP_TRY(c, hipMemsetAsync(c->evseq.status.p, 0xFF, kStatusWords * 4, s));      // (the ingest kernel writes kStFirstBad, kStUnsorted)
+    return EMBA_OK;
+}
+
+emba_status seq_ingest_finish(emba_ctx* c, size_t n_kept, size_t* n_kept_out)
+{
+    hipStream_t s = c->stream;
+    uint32_t h_err[2];
+    HIP_TRY(c, hipMemcpyAsync(h_err, c->evseq.status.p, sizeof h_err, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (h_err[kStFirstBad] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[kStFirstBad], c->sw, c->sh);
+    if (h_err[kStUnsorted] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[kStUnsorted]);
+    c->evseq.n = n_kept; c->evseq.have = true;
+    if (n_kept_out) *n_kept_out = n_kept;
+    return EMBA_OK;
+}
+}  // namespace
+
 extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uint16_t* y, const uint8_t* pol, const int64_t* t_ns, size_t n, int32_t sampling_rate,
                                        size_t* n_kept_out)
 {
@@ -46,17 +79,11 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
     if (n >= 0xFFFFFFFFull) return fail(c, EMBA_ERR_INVALID_ARG, "too many events for 32-bit indices");
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipStreamSynchronize(s));
     const size_t rate = sampling_stride(sampling_rate), n_kept = sampled_count(n, sampling_rate);
-    c->evseq.n = 0; c->evseq.have = false;      // (a second upload replaces the first; a failed one leaves none)
-    c->priors.drop();                           // (the contrast priors are votes of the sequence that goes)
-    emba_status st;
-    if ((st = ensure_stage(c)) || (st = ensure<uint8_t>(c, c->evseq.raw, kSeqRaw.bytes)) || (st = ensure<uint32_t>(c, c->evseq.status, kStatusWords)) ||
-        (st = ensure<uint16_t>(c, c->evseq.x, std::max<size_t>(n_kept, 1))) || (st = ensure<uint16_t>(c, c->evseq.y, std::max<size_t>(n_kept, 1))) ||
-        (st = ensure<uint8_t>(c, c->evseq.pol, std::max<size_t>(n_kept, 1))) || (st = ensure<int64_t>(c, c->evseq.t, std::max<size_t>(n_kept, 1))))
-        return st;
-    uint32_t* d_err = c->evseq.status.as<uint32_t>();      // (the ingest kernel writes kStFirstBad, kStUnsorted)
-    HIP_TRY(c, hipMemsetAsync(d_err, 0xFF, kStatusWords * 4, s));
+    SEQ_TRY(seq_ingest_begin(c, n_kept));
+    SEQ_TRY(ensure_stage(c));
+    SEQ_TRY(ensure<uint8_t>(c, c->evseq.raw, kSeqRaw.bytes));
+    uint32_t* d_err = c->evseq.status.as<uint32_t>();
     uint8_t* raw = c->evseq.raw.as<uint8_t>();
     for (size_t k0 = 0, i = 0; k0 < n; k0 += kSeqChunk, ++i) {
         const size_t m = std::min(kSeqChunk, n - k0);
@@ -74,14 +101,7 @@ extern "C" emba_status emba_seq_upload(emba_ctx* c, const uint16_t* x, const uin
                            (long)rate, (long)n_kept, c->evseq.x.as<uint16_t>(), c->evseq.y.as<uint16_t>(), c->evseq.pol.as<uint8_t>(), c->evseq.t.as<int64_t>(), d_err);
         HIP_TRY(c, hipGetLastError());
     }
-    uint32_t h_err[2];
-    HIP_TRY(c, hipMemcpyAsync(h_err, d_err, sizeof h_err, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (h_err[kStFirstBad] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "event %u lies outside the %dx%d sensor", h_err[kStFirstBad], c->sw, c->sh);
-    if (h_err[kStUnsorted] != 0xFFFFFFFFu) return fail(c, EMBA_ERR_INVALID_ARG, "timestamps not sorted at event %u", h_err[kStUnsorted]);
-    c->evseq.n = n_kept; c->evseq.have = true;
-    if (n_kept_out) *n_kept_out = n_kept;
-    return EMBA_OK;
+    return seq_ingest_finish(c, n_kept, n_kept_out);
 }
 
 // getEventSubset: the kernel finds the first probe past either cursor, sequence_rule.h (seq_window) makes the window of them

@@ -906,3 +906,87 @@ def event_frames(x, y, pol, t, edges, sw, sh, signed_polarity=True):
     w = np.where(np.asarray(pol).reshape(-1)[keep] == 0, -1.0, 1.0) if signed_polarity else np.ones(cell.size)
     frames = np.bincount(cell, weights=w, minlength=F * sh * sw).astype(np.int32).reshape(F, sh, sw)      # (sums of +-1: exact in a double)
     return frames, int((f < 0).sum()), int((f >= F).sum())
+
+
+# ---- the event simulator (numpy form of emba_simulate_events, include/emba_hip.h; the device form is LEGM.simulate_events).  The rule is
+# emba_amd/csrc/sim_rule.h's sim_frame / sim_step, operation for operation: given the same samples both forms give the same events in the same order.
+SIM_MAX_PER_STEP = 255
+SIM_MAX_SPAN_NS = 1 << 52
+
+
+def simulate_events(views, outside, step_t_ns, sensor_w, c_on, c_off=None, max_per_step=255):
+    """The events of the samples views [F + 1, S] (S = sensor_h * sensor_w, any shape that reshapes to it) with the mask outside [F + 1, S] at the step times
+    step_t_ns [F + 1], strictly increasing over less than 2^52 ns.  Every pixel s, over f = 0 ... F: V_f outside disarms it; V_f inside and the pixel not
+    armed: ref = V_f, armed, no event; V_f inside and armed: prev = V_{f-1}, cur = V_f, d = step_t[f] - step_t[f-1], and while |cur - ref| >= C (C = c_on,
+    sgn = +1 where cur - ref > 0, else C = c_off, sgn = -1), at most max_per_step times: ref = ref + sgn C; frac = (ref - prev) / (cur - prev), 0 where it
+    is not >= 0, 1 where it is > 1; off = int64(frac * float(d)) truncated, at most d - 1; the event (x = s % sensor_w, y = s // sensor_w, polarity = sgn > 0,
+    t = step_t[f-1] + off).  What the cap leaves over is carried in ref.  Order: ascending t, among equal t ascending s, among those the order of emission.
+    Returns (EventPacket, stats uint64 [4]): events, positive events, (pixel, step) pairs where the condition still held after max_per_step events,
+    (pixel, frame) pairs outside."""
+    ts = np.asarray(step_t_ns, dtype=np.int64).reshape(-1)
+    F = ts.size - 1
+    if F < 1 or (np.diff(ts) <= 0).any() or int(ts[-1]) - int(ts[0]) >= SIM_MAX_SPAN_NS:
+        raise ValueError("the step times must be strictly increasing over less than 2^52 ns (F + 1 of them, F >= 1)")
+    c_on = float(c_on)
+    c_off = c_on if c_off is None else float(c_off)
+    if not (np.isfinite(c_on) and c_on > 0.0 and np.isfinite(c_off) and c_off > 0.0):
+        raise ValueError("the thresholds must be positive and finite")
+    max_per_step, sw = int(max_per_step), int(sensor_w)
+    if not 1 <= max_per_step <= SIM_MAX_PER_STEP:
+        raise ValueError(f"max_per_step must be 1 ... {SIM_MAX_PER_STEP}")
+    V = np.asarray(views, dtype=np.float64).reshape(F + 1, -1)
+    out = np.asarray(outside, dtype=bool).reshape(F + 1, -1)
+    if out.shape != V.shape or V.shape[1] % sw:
+        raise ValueError("views and outside must both be [F + 1, sensor_h * sensor_w]")
+    armed = ~out[0]
+    ref = np.where(armed, V[0], 0.0)
+    n_cap = 0
+    ev_s, ev_pol, ev_t = [], [], []
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for f in range(1, F + 1):
+            inside = ~out[f]
+            idx = np.flatnonzero(inside & armed)
+            t_prev, d = int(ts[f - 1]), int(ts[f] - ts[f - 1])
+            r, p, c = ref[idx], V[f - 1][idx], V[f][idx]
+            s_f, k_f, pol_f, t_f = [], [], [], []
+            k = 0
+            while idx.size:
+                diff = c - r
+                up = diff > 0.0
+                C = np.where(up, c_on, c_off)
+                go = np.abs(diff) >= C
+                idx, r, p, c, up, C = idx[go], r[go], p[go], c[go], up[go], C[go]
+                if k == max_per_step:
+                    n_cap += idx.size
+                    break
+                if not idx.size:
+                    break
+                r = r + np.where(up, 1.0, -1.0) * C
+                frac = (r - p) / (c - p)
+                frac = np.where(frac >= 0.0, frac, 0.0)
+                frac = np.where(frac > 1.0, 1.0, frac)
+                off = np.minimum((frac * float(d)).astype(np.int64), d - 1)
+                ref[idx] = r
+                s_f.append(idx); k_f.append(np.full(idx.size, k)); pol_f.append(up); t_f.append(t_prev + off)
+                k += 1
+            if s_f:
+                s_f, k_f, pol_f, t_f = np.concatenate(s_f), np.concatenate(k_f), np.concatenate(pol_f), np.concatenate(t_f)
+                order = np.lexsort((k_f, s_f, t_f))      # by t, then pixel, then emission
+                ev_s.append(s_f[order]); ev_pol.append(pol_f[order]); ev_t.append(t_f[order])
+            fresh = inside & ~armed
+            ref[fresh] = V[f][fresh]
+            armed = inside
+    s_all = np.concatenate(ev_s) if ev_s else np.zeros(0, np.int64)
+    pol = (np.concatenate(ev_pol) if ev_pol else np.zeros(0, bool)).astype(np.uint8)
+    t = np.concatenate(ev_t).astype(np.int64) if ev_t else np.zeros(0, np.int64)
+    stats = np.array([t.size, int(pol.sum()), n_cap, int(out.sum())], dtype=np.uint64)
+    return EventPacket((s_all % sw).astype(np.uint16), (s_all // sw).astype(np.uint16), pol, t), stats
+
+
+def simulate_from_plane(plane, lut, knots, t0_ns, dt_ns, step_t_ns, sensor, c_on, c_off=None, max_per_step=255):
+    """A recording without the device: the samples of `plane` [H, W] at the step times along the spline (view_pm, then render_views), then simulate_events.
+    sensor = (sensor_w, sensor_h).  numpy's pm is close to the device's, not bit-equal: so are the samples, and an event near a threshold may differ."""
+    P = np.asarray(plane, dtype=np.float64)
+    pm = view_pm(lut, knots, t0_ns, dt_ns, step_t_ns, P.shape[1], P.shape[0])
+    views, outside = render_views(P, pm, with_outside=True)
+    return simulate_events(views, outside, step_t_ns, int(sensor[0]), c_on, c_off, max_per_step)

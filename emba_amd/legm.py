@@ -90,7 +90,8 @@ class LEGM:
         self._ctx = C.c_void_p()
         self.sensor_w, self.sensor_h = int(sensor_w), int(sensor_h)
         self.W, self.H = int(pano_width), int(pano_height)
-        lut = np.ascontiguousarray(bearing_lut, dtype=np.float64).reshape(self.sensor_w * self.sensor_h, 3)
+        self.C_th = float(C_th)
+        lut =np.ascontiguousarray(bearing_lut, dtype=np.float64).reshape(self.sensor_w * self.sensor_h, 3)
         cfg = EmbaCfg(self.sensor_w, self.sensor_h, self.W, self.H, _p(lut, _dp), float(C_th), 100, 10.0, int(device),
                       C.c_void_p(stream) if stream else None)
         st = self._L.emba_create(C.byref(cfg), C.byref(self._ctx))
@@ -336,6 +337,54 @@ class LEGM:
         self._check(self._L.emba_seq_event_frames(self._ctx, int(beg), end, _p(edges, _i64p), F, 1 if signed_polarity else 0, _p(frames, _i32p), C.byref(before),
                                                   C.byref(after)))
         return frames, before.value, after.value
+
+    def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
+        """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
+        F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives
+        at those times of `plane` [pano_h, pano_w], or, with plane=None, of the intensity panorama of the resident map under `boundary`.  c_on defaults to
+        the model's C_th, c_off to c_on.  The recording stays on the device (simulated_events downloads it, sequence_from_simulation makes it the resident
+        sequence).  Returns stats uint64 [4]: events, positive events, (pixel, step) pairs the cap cut short, (pixel, frame) pairs outside —
+        io.simulate_events given the same samples, bit for bit.  More than max_events events (0: 2^32 - 2) raises EmbaError with status 6, and
+        EmbaError.needed is the number that would have been needed."""
+        bc = poisson_boundary(boundary)
+        knots = np.ascontiguousarray(knots, dtype=np.float64).reshape(-1, 4)
+        ts = np.ascontiguousarray(step_t_ns, dtype=np.int64).reshape(-1)
+        if ts.size < 2:
+            raise ValueError("F steps have F + 1 step times: at least two")
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float64)
+            if plane.shape != (self.H, self.W):
+                raise ValueError("plane must be pano_height x pano_width float64")
+        c_on = float(self.C_th if c_on is None else c_on)
+        c_off = c_on if c_off is None else float(c_off)
+        stats = np.zeros(4, np.uint64)
+        st = self._L.emba_simulate_events(self._ctx, _p(plane, _dp), bc, _p(ts, _i64p), ts.size - 1, _p(knots, _dp), knots.shape[0], int(t0_ns), int(dt_ns), c_on, c_off,
+                                          int(max_per_step), int(max_events), stats.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if st != _lib.OK:
+            err = EmbaError(st, self._L.emba_last_error(self._ctx).decode())
+            err.needed = int(stats[0]) if st == _lib.ERR_CAPACITY else None
+            raise err
+        return stats
+
+    def simulated_size(self):
+        n = C.c_size_t(0)
+        self._check(self._L.emba_sim_size(self._ctx, C.byref(n)))
+        return n.value
+
+    def simulated_events(self, beg=0, end=None):
+        """[beg, end) of the simulated recording (end = None: its end) as an EventPacket (emba_sim_get): time order, ties by pixel index."""
+        end = self.simulated_size() if end is None else int(end)
+        n = max(end - int(beg), 0)
+        x, y, pol, t = np.empty(n, np.uint16), np.empty(n, np.uint16), np.empty(n, np.uint8), np.empty(n, np.int64)
+        self._check(self._L.emba_sim_get(self._ctx, int(beg), end, _p(x, _u16p), _p(y, _u16p), _p(pol, _u8p), _p(t, _i64p)))
+        return EventPacket(x, y, pol, t)
+
+    def sequence_from_simulation(self, sampling_rate=1):
+        """The simulated recording becomes the resident sequence, device to device (emba_seq_from_sim): what set_sequence of simulated_events() with the same
+        rate leaves.  Returns the number of events kept."""
+        n = C.c_size_t(0)
+        self._check(self._L.emba_seq_from_sim(self._ctx, int(sampling_rate), C.byref(n)))
+        return n.value
 
     def contrast_gradient(self, traj, beg=0, end=None, signed=False, want_grad=True, want_image=False, want_pm=False, want_D=False, level=0, prior_weight=None):
         """The smooth (fp64, real bilinear weights) contrast J = sum I^2 of the panorama of warped events of [beg, end) of the resident sequence along the

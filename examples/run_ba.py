@@ -15,6 +15,8 @@
   python examples/run_ba.py --demo out/ --init-poses events --init-map events --refine-contrast --contrast-prior --window-size 0.3 --window-stride 0.1
                                                   # ... against the panorama the earlier windows' events already placed
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
+  python examples/run_ba.py out/ --simulate plane.npy --poses traj.txt --calib calib.npz --sim-hz 2000 --events-out ev.npz   # panorama to events: a recording
+                                                  # of the log-intensity plane along the trajectory, simulated on the device; with --demo the BA then runs on it
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... --window-size 0.3 --window-stride 0.1
@@ -39,6 +41,95 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from emba_amd import LEGM, io as eio, so3, synth                      # noqa: E402
 from emba_amd.legm import LinearTrajectory                            # noqa: E402
 from emba_amd.solver import BASettings, LMSettings, MapRecorder, RuntimeLog, solve_time_window  # noqa: E402
+
+
+def load_plane(path):
+    """A log-intensity plane: a .npy of doubles, or a binary .pgm read as log(1 + v)."""
+    if path.endswith(".npy"):
+        return np.ascontiguousarray(np.load(path), dtype=np.float64)
+    with open(path, "rb") as f:
+        raw = f.read()
+    tok, pos = [], 0
+    while len(tok) < 4:                                                # magic, width, height, maxval: whitespace-separated, '#' comments
+        while raw[pos:pos + 1].isspace():
+            pos += 1
+        if raw[pos:pos + 1] == b"#":
+            pos = raw.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while not raw[end:end + 1].isspace():
+            end += 1
+        tok.append(raw[pos:end]); pos = end
+    if tok[0] != b"P5":
+        raise ValueError(f"{path}: not a binary PGM")
+    w, h, maxval = int(tok[1]), int(tok[2]), int(tok[3])
+    v = np.frombuffer(raw, dtype=np.uint8 if maxval < 256 else ">u2", count=w * h, offset=pos + 1).reshape(h, w)
+    return np.log1p(v.astype(np.float64))
+
+
+def simulate(a, ap):
+    """--simulate: a recording from a log-intensity plane and a trajectory, on the device; with --demo, then the BA on it."""
+    if not (np.isfinite(a.sim_hz) and a.sim_hz > 0):
+        ap.error("--simulate needs --sim-hz, the steps per second (finite, positive)")
+    if not a.events_out:
+        ap.error("--simulate needs --events-out FILE")
+    plane = load_plane(a.simulate)
+    H, W = plane.shape
+    if a.demo:      # the demo's camera and, without --poses, its trajectory
+        sw, sh, dt_knots = 128, 96, 0.05
+        lut = synth.pinhole_bearing_lut(sw, sh, 120.0, 120.0, 0.5 * (sw - 1), 0.5 * (sh - 1))
+        truth = synth.make_trajectory(11, dt_knots=dt_knots) if not a.poses else None
+    else:
+        if not a.poses or not a.calib:
+            ap.error("--simulate needs --poses and --calib (or --demo)")
+        cal = np.load(a.calib)
+        sw, sh, dt_knots, truth = int(cal["width"]), int(cal["height"]), a.dt_knots, None
+        lut = eio.bearing_lut_from_calibration(cal["K"], cal["D"], sw, sh)
+    if truth is None:
+        t, qs = eio.load_poses(a.poses)
+        t_beg = a.t_beg if a.t_beg is not None else t[0]
+        t_end = a.t_end if a.t_end is not None else t[-1]
+        num_cps = int(round((t_end - t_beg) / dt_knots)) + 1
+        sel = (t >= t_beg) & (t <= t_end)
+        truth = LinearTrajectory.from_seconds(t_beg, dt_knots, eio.fit_ctrl_poses(t[sel], qs[sel], t_beg, dt_knots, num_cps))
+    # step times t0, t0 + p, ... up to t0 + (K - 1) dt - 1: the rule of --views-hz
+    period = max(int(round(1e9 / a.sim_hz)), 1)
+    ts = np.arange(truth.t0_ns, truth.t0_ns + truth.dt_ns * (truth.size() - 1), period, dtype=np.int64)
+    if ts.size < 2:
+        ap.error("--sim-hz gives fewer than two step times on this trajectory")
+    c_on = a.sim_c_on if a.sim_c_on is not None else a.C_th
+    c_off = a.sim_c_off if a.sim_c_off is not None else c_on
+    legm = LEGM(sw, sh, lut, c_on, W, H)
+    t0 = time.time()
+    stats = legm.simulate_events(ts, truth.knots_xyzw, truth.t0_ns, truth.dt_ns, plane=plane, c_on=c_on, c_off=c_off)
+    dt = time.time() - t0
+    ev = legm.simulated_events()
+    eio.save_events(a.events_out, ev)
+    print(f"simulated {int(stats[0])} events ({int(stats[1])} positive) on {sw}x{sh} from a {H}x{W} plane over {ts.size - 1} steps at {a.sim_hz:g} Hz in {dt * 1e3:.1f} ms: "
+          f"{int(stats[2])} (pixel, step) pairs capped, {int(stats[3])} (pixel, frame) pairs outside; written to {a.events_out}")
+    if not a.demo:
+        return
+    # the BA on the simulated recording: device to device into the resident sequence; from a zero map (map only first) and a perturbed trajectory
+    n = legm.sequence_from_simulation(a.sampling_rate)
+    from emba_amd.legm import EventWindow
+    import dataclasses
+    rng = np.random.default_rng(5)
+    knots = truth.knots_xyzw.copy()
+    for i in range(1, len(knots)):
+        knots[i] = so3.mul(so3.exp(rng.normal(size=3) * 0.01), knots[i])
+    traj = LinearTrajectory(knots, truth.t0_ns, truth.dt_ns)
+    ba = BASettings(use_IRLS=a.cost != "quadratic", cost_type=a.cost, eta=a.eta, thres_valid_pixel=a.thres_valid_pixel, alpha=a.alpha,
+                    damping_factor=a.damping_factor, refine=a.refine, panorama_boundary=a.panorama_boundary)
+    zero = np.zeros((H, W))
+    mres = solve_time_window(legm, traj, EventWindow(0, n), zero, zero, dataclasses.replace(ba, refine="map"), LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True)
+    print(f"{n} simulated events resident; map-only start from a zero map: {mres.iterations} LM iterations ({mres.reason}), cost {mres.cost_min:.6e}")
+    res = solve_time_window(legm, traj, EventWindow(0, n), None, None, ba, LMSettings(max_num_iter=a.max_iter), verbose=a.verbose, resident=True)
+    err = lambda tr: np.degrees(np.mean([np.linalg.norm(so3.log(so3.mul(so3.inverse(p), q))) for p, q in zip(tr.knots_xyzw, truth.knots_xyzw)]))
+    print(f"{res.iterations} LM iterations ({'converged' if res.converged else 'stopped'}), cost {res.cost_min:.6e}; "
+          f"mean control-pose error vs the simulated trajectory: {err(traj):.4f} deg -> {err(res.traj):.4f} deg")
+    eio.write_trajectory(os.path.join(a.out, "refined_traj.txt"), res.traj)
+    eio.save_map(a.out, *legm.downloadMap())
+    eio.save_pgm(os.path.join(a.out, "map_poisson_opt.pgm"), eio.normalize_robust(legm.reconstructIntensity(boundary=a.panorama_boundary), 0.1))
 
 
 def main():
@@ -97,9 +188,19 @@ def main():
     ap.add_argument("--view-events", action="store_true", help="with --views-hz: also <out>/views/event_frames.npy, the signed event counts per sensor pixel between "
                     "consecutive frames")
     ap.add_argument("--sharded", action="store_true", help="go through the multi-GPU host (ShardedLEGM / ShardedModel) even with one rank")
+    ap.add_argument("--simulate", metavar="PLANE", help="simulate a recording on the device from a log-intensity plane (.npy of doubles, H x W, or a binary .pgm read as "
+                    "log(1 + v)) along the trajectory of --poses (with --calib; --demo: the demo's camera and, without --poses, its trajectory), write it to "
+                    "--events-out and print its stats; with --demo the BA then runs on the simulated recording (DESIGN.md section 18)")
+    ap.add_argument("--sim-hz", type=float, default=0.0, help="steps per second of --simulate: step times t0, t0 + p, ... up to t0 + (K - 1) dt - 1")
+    ap.add_argument("--sim-c-on", type=float, help="the threshold of positive events (default: --C-th)")
+    ap.add_argument("--sim-c-off", type=float, help="the threshold of negative events (default: the positive one)")
+    ap.add_argument("--events-out", help="the file --simulate writes, in the flat event format of --events")
     a = ap.parse_args()
     if a.alpha is None:
         a.alpha = 0.0 if a.demo else 5.0
+    if a.simulate:
+        os.makedirs(a.out, exist_ok=True)
+        return simulate(a, ap)
     if not a.demo and a.init_map == "given" and not a.map_dir:
         ap.error("--map-dir is required unless --init-map events is given")
     if not a.demo and a.init_poses == "given" and not a.poses:

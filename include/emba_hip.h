@@ -517,6 +517,53 @@ emba_status emba_render_views(emba_ctx* ctx, const double* plane_host /* H*W or 
 emba_status emba_seq_event_frames(emba_ctx* ctx, size_t beg, size_t end, const int64_t* edge_t_ns /* F+1, strictly increasing */, size_t F,
                                   int32_t signed_polarity, int32_t* frames_out /* [F, sh, sw] */, uint64_t* before_out, uint64_t* after_out);
 
+/* ---- The event simulator: a recording from a log-intensity panorama plane and a trajectory — the events a sensor would report whose pixels see
+ * the samples of emba_render_views change.  No noise, no refractory period, no exposure model; inside a step the brightness of a pixel is linear in time.
+ *
+ * emba_simulate_events: F >= 1 steps between the F + 1 step times step_t_ns, strictly increasing, step_t_ns[F] - step_t_ns[0] < 2^52.
+ *   samples      V_f[s], f = 0 ... F, s = y * sensor_w + x: exactly what emba_render_views gives for the frame time step_t_ns[f] — the same source plane
+ *                (plane_host, or with NULL the intensity panorama of the resident map under `boundary`), poses, warp and sample, and the same pixels outside.
+ *   per pixel    a state machine over f = 0 ... F, independent of the other pixels, every operation in fp64, in this order, without contraction
+ *                (emba_amd/csrc/sim_rule.h: sim_frame, sim_step):
+ *                  V_f outside: the pixel is disarmed.
+ *                  V_f inside, the pixel not armed: ref = V_f, the pixel is armed; no event in the step that ends at f.
+ *                  V_f inside, the pixel armed (so V_{f-1} was inside): prev = V_{f-1}, cur = V_f, d = step_t_ns[f] - step_t_ns[f-1].  While
+ *                  fabs(cur - ref) >= C — C = c_on and sgn = +1 where cur - ref > 0, otherwise C = c_off and sgn = -1 — and at most max_per_step times:
+ *                    ref = ref + sgn * C;  frac = (ref - prev) / (cur - prev), 0 where it is not >= 0 (a NaN too), 1 where it is > 1;
+ *                    off = (int64)(frac * (double)d) truncated, at most d - 1;  the event (x, y, polarity = sgn > 0, t = step_t_ns[f-1] + off).
+ *                  What the cap leaves over is carried: ref stays behind and the next step goes on from it.
+ *                Every event of the step that ends at f has step_t_ns[f-1] <= t <= step_t_ns[f] - 1: the steps are disjoint in time.
+ *   order        ascending t; among equal t ascending pixel index s; among those the order of emission.
+ *   stats        uint64 [4] or NULL: [0] events, [1] positive events, [2] (pixel, step) pairs where the condition still held after max_per_step events,
+ *                [3] (pixel, f) pairs with V_f outside, f = 0 ... F.
+ *   thresholds   c_on, c_off > 0 and finite; max_per_step 1 ... 255; max_events: 0 stands for 2^32 - 2, the limit of the 32-bit scan and sort (and the most any
+ *                value allows).
+ * The recording stays on the device, in buffers of the simulator's own, and replaces the one before only when the call succeeds.  The steps go in chunks of at
+ * most 32 MiB of samples and 65 534 steps (one step at the least): per chunk the view kernel of emba_render_views, a count pass, a scan, an emit pass and the
+ * stable 32-bit sort.  (The simulator knows an outside sample by the bits of one quiet NaN, 0x7FF8000053494D31, which it passes to the view kernel as its
+ * fill: a plane that holds these very bits reads as outside there.)  EMBA_ERR_INVALID_ARG: knots or step_t_ns NULL, K < 2, dt_ns <= 0, F = 0 or F >= 2^31 - 1,
+ * step times not strictly increasing or spanning 2^52 ns or more, a threshold not positive or not finite, max_per_step outside 1 ... 255, a sensor of more
+ * than (2^32 - 2) / 255 pixels; with plane_host NULL also the refusals of emba_reconstruct_intensity_bc's boundary.  EMBA_ERR_STATE: plane_host NULL and no map
+ * resident.  EMBA_ERR_TIME_RANGE: a step time outside the knots; the pose stage's status word is read before anything else runs.  These refusals leave the
+ * previous simulated recording, stats, the resident sequence, the registered window and the last evaluation untouched.  EMBA_ERR_CAPACITY: more than
+ * max_events events — stats[0] is the number that would have been needed, the rest of stats is untouched, nothing is emitted and the previous recording is
+ * kept.  No events at all is a success with stats[0] = 0.  The sort pairs of the order preparation are scratch here as in emba_seq_filter; with plane_host
+ * NULL the Poisson workspace is rewritten.  While emba_enable_kernel_timing is on, the timer slots 3 ... 7 bracket the first chunk's views, count, scan, emit
+ * and sort.  The numpy form, given the samples: emba_amd.io.simulate_events.
+ *
+ * emba_sim_size, emba_sim_get: the number of events of the simulated recording, and [beg, end) of it; any of the four pointers may be NULL, as in
+ * emba_seq_get.  EMBA_ERR_STATE before the first successful simulation; EMBA_ERR_INVALID_ARG: not beg <= end <= n.
+ *
+ * emba_seq_from_sim: the simulated recording becomes the resident sequence, device to device: what emba_seq_upload of the same four arrays with the same
+ * sampling_rate leaves, bit for bit — the same checks, the same down-sampling, the same effect on the contrast priors, the filter's hot mask and the
+ * registered window.  The simulated recording itself stays.  EMBA_ERR_STATE before the first successful simulation. */
+emba_status emba_simulate_events(emba_ctx* ctx, const double* plane_host /* H*W or NULL */, int boundary, const int64_t* step_t_ns /* F+1 */, size_t F,
+                                 const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, double c_on, double c_off, int32_t max_per_step,
+                                 uint64_t max_events, uint64_t* stats /* [4] or NULL */);
+emba_status emba_sim_size(const emba_ctx* ctx, size_t* n);
+emba_status emba_sim_get(emba_ctx* ctx, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns);
+emba_status emba_seq_from_sim(emba_ctx* ctx, int32_t sampling_rate, size_t* n_kept);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
