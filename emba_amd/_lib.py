@@ -121,6 +121,11 @@ SIGNATURES = {
     "emba_render_views": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
                                     _dp, _u8p, C.POINTER(C.c_uint64), _dp]),
     "emba_seq_event_frames": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _i64p, C.c_size_t, C.c_int32, _i32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "emba_mosaic_frames": (C.c_int, [C.c_void_p, _u8p, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), _dp]),
+    "emba_mosaic_get": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp, _u8p, C.POINTER(C.c_uint64)]),
+    "emba_mosaic_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int32, _dp, _dp, _dp, C.c_int32]),
+    "emba_mosaic_clear": (C.c_int, [C.c_void_p]),
     "emba_simulate_events": (C.c_int, [C.c_void_p, _dp, C.c_int32, _i64p, C.c_size_t, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32,
                                        C.c_uint64, C.POINTER(C.c_uint64)]),
     "emba_sim_size": (C.c_int, [C.c_void_p, _szp]),

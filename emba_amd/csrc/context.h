@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, sim_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -244,6 +244,16 @@ struct ContrastPriors {
 // as bytes and as pm; outside: the count per frame.  emba_seq_event_frames: the edges, one chunk of int32 frames, ends: the events before and after.
 struct ViewBuffers { DevBuf plane, t, pose, knots, head, frames, u8, pm, outside, edge, counts, ends; };
 
+// The mosaic of intensity frames (mosaic_host.h).  sum_w, sum_v: the two uint64 sums per cell [H, W], resident between calls; votes: the frame pixels
+// accumulated into them since they were last zeroed (0: nothing accumulated; below 2^36: mosaic_rule.h).  Scratch of one call: the frame times, their pose
+// table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; one chunk of frames as bytes and as pm;
+// counters: [0] dropped votes, [1] skipped pixels, [2] covered cells; the mean and its covered bytes; the log-intensity plane, the bytes of the cells that
+// stay covered under it, and the two gradient planes.
+struct MosaicBuffers {
+    DevBuf sum_w, sum_v; uint64_t votes = 0;
+    DevBuf t, pose, knots, head, frames, pm, counters, mean, covered, L, covered_log, gx, gy;
+};
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -440,6 +450,7 @@ struct emba_ctx {
     int contrast_vote_path = -1;  // the vote kernel the last contrast call launched: 0 HBM, 1 LDS; -1 none yet (emba_get_option "contrast_vote_path")
     ViewBuffers view;             // sensor views along the trajectory: predicted frames and event frames (view_host.h)
     SimState sim;                 // the event simulator: the simulated recording and the scratch of a call (sim_host.h)
+    MosaicBuffers mosaic;         // the mosaic of intensity frames: the resident sums and the scratch of a call (mosaic_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -5,7 +5,7 @@
 // counters and emba_dump_state readback_host.h, the costs cost_host.h / cost_rule.h, the options options_host.h, the timers and probes timing_host.h, the
 // solvers (f1) solve_host.h / solve_rule.h, f3 poisson_host.h / poisson_rule.h, the record_data images render_host.h, the resident event sequence sequence_host.h / sequence_rule.h,
 // contrast maximisation on it cmax_host.h / cmax_rule.h, the panorama of warped events panorama_host.h / panorama_rule.h and its smooth contrast and gradient
-// contrast_host.h / contrast_rule.h, the sensor views along the trajectory view_host.h / view_rule.h, the event simulator on them
+// contrast_host.h / contrast_rule.h, the sensor views along the trajectory view_host.h / view_rule.h, the mosaic of intensity frames mosaic_host.h / mosaic_rule.h, the event simulator
 // sim_host.h / sim_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
@@ -190,6 +190,7 @@ void emba_destroy(emba_ctx* c)
 #include "panorama_host.h"   // the panorama of warped events along a trajectory, and its contrast
 #include "contrast_host.h"   // the smooth (fp64) contrast of that panorama and its gradient with respect to the control poses
 #include "view_host.h"       // sensor views along the trajectory: the frames the camera would have seen, the event counts it reported
+#include "mosaic_host.h"     // the way back: intensity frames stitched into the panorama along the trajectory, and the gradient map made from the mosaic
 #include "sim_host.h"        // the event simulator: a recording from a panorama plane and a trajectory, and its way into the resident sequence
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------

@@ -193,6 +193,30 @@ def save_pgm(path, img_u8):
         f.write(img_u8.tobytes())
 
 
+def load_pgm(path):
+    """A binary PGM (P5) as an array [h, w]: uint8 where maxval < 256, else big-endian uint16.  The header is magic, width, height, maxval, separated by
+    whitespace, with '#' comments; one whitespace byte in front of the raster.  What save_pgm writes, read back."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    tok, pos = [], 0
+    while len(tok) < 4:
+        while raw[pos:pos + 1].isspace():
+            pos += 1
+        if raw[pos:pos + 1] == b"#":
+            pos = raw.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while end < len(raw) and not raw[end:end + 1].isspace():
+            end += 1
+        if end == pos:
+            raise ValueError(f"{path}: the PGM header ends early")
+        tok.append(raw[pos:end]); pos = end
+    if tok[0] != b"P5":
+        raise ValueError(f"{path}: not a binary PGM")
+    w, h, maxval = int(tok[1]), int(tok[2]), int(tok[3])
+    return np.frombuffer(raw, dtype=np.uint8 if maxval < 256 else ">u2", count=w * h, offset=pos + 1).reshape(h, w)
+
+
 def save_png(path, img_u8, level=1):
     """8-bit greyscale (H x W) or RGB (H x W x 3) PNG: filter type 0 on every row, deflated with the standard library's zlib at `level`."""
     import struct
@@ -906,6 +930,72 @@ def event_frames(x, y, pol, t, edges, sw, sh, signed_polarity=True):
     w = np.where(np.asarray(pol).reshape(-1)[keep] == 0, -1.0, 1.0) if signed_polarity else np.ones(cell.size)
     frames = np.bincount(cell, weights=w, minlength=F * sh * sw).astype(np.int32).reshape(F, sh, sw)      # (sums of +-1: exact in a double)
     return frames, int((f < 0).sum()), int((f >= F).sum())
+
+
+# ---- the mosaic of intensity frames (numpy forms of emba_mosaic_frames, emba_mosaic_get and emba_mosaic_map, include/emba_hip.h; the device forms are
+# LEGM.mosaic_frames, LEGM.mosaic and LEGM.mosaic_map).  The rules are emba_amd/csrc/mosaic_rule.h's, operation for operation: given the same
+# pm the sums are the same integers, given the same sums the mean has the same bits, given the same L the gradients have the same bits.  view_pm above
+# gives numpy's own pm.
+MOSAIC_MAX_VOTES = 1 << 36               # kMosaicMaxVotes: the frame pixels accumulated stay below this, so that both sums convert to double exactly
+
+
+def mosaic_votes(frames_u8, pm, pano_w, pano_h, skip_zero=False):
+    """The votes of the frame pixels frames_u8 [F, S] (any shape of F * S bytes) projected to pm [F, S, 2]: every pixel votes through pano_votes, cell c gets
+    w into sum_w[c] and w * v into sum_v[c].  With skip_zero a pixel whose byte is 0 casts no vote and is counted.  Returns (sum_w uint64 [pano_h, pano_w],
+    sum_v likewise, dropped, skipped): dropped the non-zero weights whose row lies outside the panorama, as python ints."""
+    W, H = int(pano_w), int(pano_h)
+    v = np.asarray(frames_u8, dtype=np.uint8).reshape(-1).astype(np.int64)
+    if v.size >= MOSAIC_MAX_VOTES:
+        raise ValueError(f"{v.size} frame pixels: the sums are exact below {MOSAIC_MAX_VOTES} votes")
+    cell, w = pano_votes(pm, W, H)
+    if cell.shape[0] != v.size:
+        raise ValueError(f"pm has {cell.shape[0]} rows, the frames have {v.size} pixels")
+    votes = (v != 0) if skip_zero else np.ones(v.size, dtype=bool)
+    w = w * votes[:, None]
+    inside = cell >= 0
+    # (sums of integers below 2^53: exact in the doubles bincount adds)
+    sum_w = np.bincount(cell[inside], weights=w[inside].astype(np.float64), minlength=W * H).astype(np.uint64).reshape(H, W)
+    sum_v = np.bincount(cell[inside], weights=(w * v[:, None])[inside].astype(np.float64), minlength=W * H).astype(np.uint64).reshape(H, W)
+    return sum_w, sum_v, int(np.count_nonzero(~inside & (w != 0))), int(np.count_nonzero(~votes))
+
+
+def mosaic_mean(sum_w, sum_v, min_weight=256, fill=0.0):
+    """mosaic_mean (mosaic_rule.h): covered = sum_w >= min_weight (min_weight >= 1); mean = double(sum_v) / double(sum_w) where covered, else `fill`.
+    Returns (mean float64, covered bool)."""
+    if int(min_weight) < 1:
+        raise ValueError("min_weight is 1 at the least")
+    sum_w, sum_v = np.asarray(sum_w, dtype=np.uint64), np.asarray(sum_v, dtype=np.uint64)
+    covered = sum_w >= np.uint64(min_weight)
+    mean = np.where(covered, sum_v.astype(np.float64) / np.where(covered, sum_w, np.uint64(1)).astype(np.float64), float(fill))
+    return mean, covered
+
+
+def mosaic_log(mean, covered, lo=0.0, hi=1.0, eps=1.0 / 255.0, take_log=True):
+    """mosaic_log (mosaic_rule.h): I = lo + mean * (hi - lo) / 255 in this order, the inverse of view_u8's tone; L = I without take_log, else log(I + eps),
+    and a cell whose I + eps is not positive becomes uncovered.  Returns (L float64, 0 where uncovered; covered bool)."""
+    lo, hi, eps = float(lo), float(hi), float(eps)
+    if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(eps) and hi > lo):
+        raise ValueError("lo, hi, eps are finite and hi > lo")
+    covered = np.asarray(covered).astype(bool)
+    inten = lo + np.asarray(mean, dtype=np.float64) * (hi - lo) / 255.0
+    if not take_log:
+        return np.where(covered, inten, 0.0), covered
+    a = inten + eps
+    with np.errstate(invalid="ignore"):
+        covered = covered & (a > 0.0)
+    return np.where(covered, np.log(np.where(covered, a, 1.0)), 0.0), covered
+
+
+def gradient_from_plane(L, covered):
+    """mosaic_gradient (mosaic_rule.h): backward differences of the plane L [H, W] with holes — Gx[i][j] = L[i][j] - L[i][(j - 1) mod W] where both cells
+    are covered, Gy[i][j] = L[i][j] - L[i - 1][j] where both are covered and i >= 1, 0 elsewhere: the field whose divergence in reconstruct_intensity is the
+    5-point operator.  Returns (Gx, Gy)."""
+    L = np.asarray(L, dtype=np.float64)
+    cov = np.asarray(covered).astype(bool)
+    Gx = np.where(cov & np.roll(cov, 1, axis=1), L - np.roll(L, 1, axis=1), 0.0)
+    Gy = np.zeros_like(L)
+    Gy[1:] = np.where(cov[1:] & cov[:-1], L[1:] - L[:-1], 0.0)
+    return Gx, Gy
 
 
 # ---- the event simulator (numpy form of emba_simulate_events, include/emba_hip.h; the device form is LEGM.simulate_events; DESIGN.md §18).  The rule is

@@ -338,6 +338,50 @@ class LEGM:
                                                   C.byref(after)))
         return frames, before.value, after.value
 
+    def mosaic_frames(self, frames, frame_t_ns, traj, skip_zero=False, accumulate=False, want_pm=False):
+        """Frames -> panorama (emba_mosaic_frames; the rule: include/emba_hip.h): the bytes frames [F, sensor_h, sensor_w] taken at the times frame_t_ns [F]
+        are voted into the context's mosaic along traj (a LinearTrajectory) — every pixel bilinearly into four cells, its weight into sum_w, weight times
+        byte into sum_v.  skip_zero: a byte of 0 casts no vote (the frames of render_views hold 0 outside the panorama).  accumulate: add to the sums that
+        are there instead of starting from zero, so that frames can be streamed in pieces.  A dict of dropped (votes whose row lies outside the panorama),
+        skipped (pixels skip_zero left out) and pm float64 [F, sensor_h * sensor_w, 2] (None without want_pm) — io.mosaic_votes given the same pm, the same
+        integers."""
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
+        dropped, skipped = C.c_uint64(0), C.c_uint64(0)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        self._check(self._L.emba_mosaic_frames(self._ctx, _p(frames, _u8p), _p(ts, _i64p), F, _p(knots, _dp), knots.shape[0], int(traj.t0_ns), int(traj.dt_ns),
+                                               1 if skip_zero else 0, 1 if accumulate else 0, C.byref(dropped), C.byref(skipped), _p(pm, _dp)))
+        return dict(dropped=dropped.value, skipped=skipped.value, pm=pm)
+
+    def mosaic(self, min_weight=256, fill=0.0):
+        """The mosaic as it stands (emba_mosaic_get): a dict of sum_w, sum_v uint64 [pano_h, pano_w], covered bool (sum_w >= min_weight; 256 is one whole
+        pixel's worth), mean float64 (sum_v / sum_w in byte units where covered, else `fill`) and n_covered — io.mosaic_mean of the sums, bit for bit."""
+        shape = (self.H, self.W)
+        sum_w, sum_v = np.empty(shape, np.uint64), np.empty(shape, np.uint64)
+        mean, covered, n = np.empty(shape), np.empty(shape, np.uint8), C.c_uint64(0)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_mosaic_get(self._ctx, int(min_weight), float(fill), _p(sum_w, u64p), _p(sum_v, u64p), _p(mean, _dp), _p(covered, _u8p), C.byref(n)))
+        return dict(sum_w=sum_w, sum_v=sum_v, mean=mean, covered=covered.astype(bool), n_covered=n.value)
+
+    def mosaic_map(self, min_weight=256, lo=0.0, hi=1.0, eps=1.0 / 255.0, take_log=True, resident=False):
+        """The log-intensity plane of the mosaic and the gradient map made from it (emba_mosaic_map): I = lo + mean (hi - lo) / 255, the inverse of
+        render_views' tone; L = log(I + eps), or I itself without take_log (bytes that are log intensity already); Gx, Gy the backward differences of L
+        between covered cells, 0 elsewhere — io.mosaic_log and io.gradient_from_plane.  resident: Gx, Gy also become the resident map, device to device, as
+        upload_map of them would leave it.  A dict of L, Gx, Gy float64 [pano_h, pano_w]."""
+        shape = (self.H, self.W)
+        L, Gx, Gy = np.empty(shape), np.empty(shape), np.empty(shape)
+        self._check(self._L.emba_mosaic_map(self._ctx, int(min_weight), float(lo), float(hi), float(eps), 1 if take_log else 0, _p(L, _dp), _p(Gx, _dp), _p(Gy, _dp),
+                                            1 if resident else 0))
+        return dict(L=L, Gx=Gx, Gy=Gy)
+
+    def mosaic_clear(self):
+        """Zero sums, nothing accumulated (emba_mosaic_clear)."""
+        self._check(self._L.emba_mosaic_clear(self._ctx))
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

@@ -17,6 +17,9 @@
   python examples/run_ba.py --demo out/ --refine poses        # move the poses only, against the map as given (or --refine map: the map only)
   python examples/run_ba.py out/ --simulate plane.npy --poses traj.txt --calib calib.npz --sim-hz 2000 --events-out ev.npz   # panorama to events: a recording
                                                   # of the log-intensity plane along the trajectory, simulated on the device; with --demo the BA then runs on it
+  python examples/run_ba.py --demo out2/ --frames out1/views --init-map frames --frames-log 0 --frames-skip-zero --frames-lo LO --frames-hi HI
+                                                  # frames to panorama: the initial map is the mosaic of intensity frames along the raw trajectory (DESIGN.md
+                                                  # section 19); here the frames another run wrote with --views-hz, whose tone LO HI is in out1/views/tone.txt
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... --window-size 0.3 --window-stride 0.1
@@ -28,7 +31,8 @@ Inputs: events (.npz: x, y u16; polarity u8; t_ns i64), initial poses ("t tx ty 
 Outputs: <out>/refined_traj.txt, <out>/Gx.bin, <out>/Gy.bin (the files emba.cpp:300-330 writes), <out>/map_poisson_opt.pgm; with --record-data
 also the reference's record_data map images (solver.cpp:173-179, 332-336, 360-364): <out>/{Gx_evo,Gy_evo,G_hsv_evo,map_poisson_evo,map_opt}/*.png; with
 --views-hz (and --window-size) <out>/views/frame_%06d.pgm and times.txt, what the camera would have seen along the final trajectory, and with --view-events
-<out>/views/event_frames.npy."""
+<out>/views/event_frames.npy; with --frames <out>/frame_mosaic.pgm and <out>/frame_mosaic_covered.pgm, the frames stitched along
+the final trajectory."""
 import argparse
 import os
 import sys
@@ -47,24 +51,36 @@ def load_plane(path):
     """A log-intensity plane: a .npy of doubles, or a binary .pgm read as log(1 + v)."""
     if path.endswith(".npy"):
         return np.ascontiguousarray(np.load(path), dtype=np.float64)
-    with open(path, "rb") as f:
-        raw = f.read()
-    tok, pos = [], 0
-    while len(tok) < 4:                                                # magic, width, height, maxval: whitespace-separated, '#' comments
-        while raw[pos:pos + 1].isspace():
-            pos += 1
-        if raw[pos:pos + 1] == b"#":
-            pos = raw.index(b"\n", pos) + 1
-            continue
-        end = pos
-        while not raw[end:end + 1].isspace():
-            end += 1
-        tok.append(raw[pos:end]); pos = end
-    if tok[0] != b"P5":
-        raise ValueError(f"{path}: not a binary PGM")
-    w, h, maxval = int(tok[1]), int(tok[2]), int(tok[3])
-    v = np.frombuffer(raw, dtype=np.uint8 if maxval < 256 else ">u2", count=w * h, offset=pos + 1).reshape(h, w)
-    return np.log1p(v.astype(np.float64))
+    return np.log1p(eio.load_pgm(path).astype(np.float64))
+
+
+def load_frames(frames_dir, sw, sh):
+    """--frames DIR: times.txt ('index seconds.nanoseconds' per line) and frame_%06d.pgm of sensor size, as --views-hz writes them.  Returns (frames
+    uint8 [F, sh, sw], t_ns int64 [F])."""
+    idx, t_ns = [], []
+    with open(os.path.join(frames_dir, "times.txt")) as fh:
+        for line in fh:
+            if not line.strip():
+                continue
+            i, stamp = line.split()
+            sec, _, frac = stamp.partition(".")
+            idx.append(int(i)); t_ns.append(int(sec) * 1_000_000_000 + int((frac + "000000000")[:9]))
+    frames = np.zeros((len(idx), sh, sw), np.uint8)
+    for k, i in enumerate(idx):
+        img = eio.load_pgm(os.path.join(frames_dir, "frame_%06d.pgm" % i))
+        if img.shape != (sh, sw) or img.dtype != np.uint8:
+            raise ValueError(f"{frames_dir}/frame_{i:06d}.pgm: {img.shape[1]}x{img.shape[0]} {img.dtype}, the sensor is {sw}x{sh} in bytes")
+        frames[k] = img
+    return frames, np.array(t_ns, dtype=np.int64)
+
+
+def frame_mosaic(legm, frames, t_ns, traj, skip_zero):
+    """The frames whose times the trajectory covers, voted into the context's mosaic on the device.  Returns how many those were."""
+    keep = (t_ns >= traj.t0_ns) & (t_ns < traj.t0_ns + traj.dt_ns * (traj.size() - 1))
+    if not keep.any():
+        raise SystemExit("--frames: no frame time lies inside the trajectory's knots")
+    legm.mosaic_frames(frames[keep], t_ns[keep], traj, skip_zero=skip_zero)
+    return int(keep.sum())
 
 
 def simulate(a, ap):
@@ -160,8 +176,17 @@ def main():
     ap.add_argument("--support-time", type=float, default=0.0, help="seconds: keep an event only if one of its eight neighbouring pixels fired at most this long "
                     "before it (0: off)")
     ap.add_argument("--median-blur", action="store_true", help="3x3 median blur of the initial map (emba.cpp:357-364; with --window-size)")
-    ap.add_argument("--init-map", default="given", choices=["given", "events"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
-                    "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size")
+    ap.add_argument("--init-map", default="given", choices=["given", "events", "frames"], help="events: no --map-dir is needed — the run starts from a zero map, which is first "
+                    "solved for alone at the initial poses (mapping with known poses), then refined jointly; --pano-h gives its size.  frames: no --map-dir is "
+                    "needed — the intensity frames of --frames are stitched into the panorama along the raw trajectory on the device, and the backward "
+                    "differences of that mosaic's log intensity are the initial map (DESIGN.md section 19)")
+    ap.add_argument("--frames", metavar="DIR", help="intensity frames beside the events: DIR/frame_%%06d.pgm at sensor size and DIR/times.txt, exactly what --views-hz "
+                    "writes.  With it <out>/frame_mosaic.pgm and <out>/frame_mosaic_covered.pgm are written: the frames stitched along the final trajectory")
+    ap.add_argument("--frames-lo", type=float, default=0.0, help="the intensity a byte of 0 stands for (the tone the frames were written with)")
+    ap.add_argument("--frames-hi", type=float, default=1.0, help="the intensity a byte of 255 stands for")
+    ap.add_argument("--frames-eps", type=float, default=1.0 / 255.0, help="L = log(I + eps)")
+    ap.add_argument("--frames-log", type=int, default=1, choices=[0, 1], help="0: the bytes are log intensity already (the frames of --views-hz): no logarithm is taken")
+    ap.add_argument("--frames-skip-zero", action="store_true", help="a byte of 0 is no measurement (--views-hz writes 0 where a pixel looks past the panorama)")
     ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity"], help="identity: no --poses is needed — every raw pose is the identity "
                     "(what a run without a front end always has; with --window-size).  events: no --poses is needed — the angular velocity of every slice of events is "
                     "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
@@ -202,7 +227,14 @@ def main():
         os.makedirs(a.out, exist_ok=True)
         return simulate(a, ap)
     if not a.demo and a.init_map == "given" and not a.map_dir:
-        ap.error("--map-dir is required unless --init-map events is given")
+        ap.error("--map-dir is required unless --init-map events or frames is given")
+    if a.init_map == "frames" and not a.frames:
+        ap.error("--init-map frames needs --frames DIR")
+    if a.init_map == "frames" and a.init_poses != "given":
+        ap.error("--init-map frames stitches the frames along the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity, "
+                 "whose trajectory at that point carries the timing only")
+    if a.frames and not (np.isfinite(a.frames_lo) and np.isfinite(a.frames_hi) and np.isfinite(a.frames_eps) and a.frames_hi > a.frames_lo):
+        ap.error("--frames-lo, --frames-hi and --frames-eps are finite, and --frames-hi is above --frames-lo")
     if not a.demo and a.init_poses == "given" and not a.poses:
         ap.error("--poses is required unless --init-poses events or identity is given")
     if a.init_poses != "given" and not a.window_size:
@@ -299,6 +331,15 @@ def main():
                     damping_factor=a.damping_factor, refine=a.refine, panorama_boundary=a.panorama_boundary)
     if rank == 0:
         print(f"{events.size()} events, {traj.size()} control poses, panorama {H}x{W}" + (f", {world} rank(s) through the sharded host" if legm is not model else ""))
+    if a.frames:
+        frames, frames_t_ns = load_frames(a.frames, sw, sh)
+    if a.init_map == "frames":      # the mosaic of the frames along the raw trajectory, on the device; its gradient map is handed on as the given map
+        used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero)
+        fm = legm.mosaic_map(lo=a.frames_lo, hi=a.frames_hi, eps=a.frames_eps, take_log=bool(a.frames_log))
+        Gx, Gy = fm["Gx"], fm["Gy"]
+        if rank == 0:
+            print(f"initial map from {used} of {len(frames_t_ns)} frames along the raw trajectory: {legm.mosaic()['n_covered']} of {H * W} cells covered, "
+                  f"mean |G| {0.5 * (np.abs(Gx).mean() + np.abs(Gy).mean()):.4g}")
     t0 = time.time()
     # the reference's run-time records (final_results/runtime_{formEqs,solveEqs,objFuncs}.txt, iterations.txt: solver.cpp:105-151, 170-178, 205-223, 271-291)
     rlog = RuntimeLog(a.out) if (a.runtime_log and rank == 0) else None
@@ -306,7 +347,8 @@ def main():
     if a.window_size:
         from emba_amd.driver import SequenceSettings, run_sequence
         seq = SequenceSettings(time_window_size=a.window_size, sliding_window_stride=a.window_stride or a.window_size, dt_knots=traj.dt_ns * 1e-9 if a.demo else a.dt_knots,
-                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur, init_map=a.init_map,
+                               event_sampling_rate=a.sampling_rate, t_start=t_beg, t_end=t_end, median_blur=a.median_blur,
+                               init_map="events" if a.init_map == "events" else "given",      # (frames: the mosaic's map is a given map)
                                hot_pixel_sigma=a.hot_pixel_sigma, refractory_period=a.refractory, support_time=a.support_time,
                                init_poses="events" if a.init_poses == "events" else "given", cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
                                record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
@@ -346,6 +388,8 @@ def main():
                     eio.save_pgm(os.path.join(a.out, "views", "frame_%06d.pgm" % f), img)
                 with open(os.path.join(a.out, "views", "times.txt"), "w") as fh:
                     fh.write("".join("%d %d.%09d\n" % (f, tn // 1_000_000_000, tn % 1_000_000_000) for f, tn in enumerate(vw["t_ns"].tolist())))
+                with open(os.path.join(a.out, "views", "tone.txt"), "w") as fh:      # the tone of the bytes, in full: --frames-lo / --frames-hi of a run on these frames
+                    fh.write("%r %r\n" % (float(vw["lo"]), float(vw["hi"])))
                 if vw["event_frames"] is not None:
                     np.save(os.path.join(a.out, "views", "event_frames.npy"), vw["event_frames"])
                 print(f"views: {len(vw['t_ns'])} frames at {a.views_hz:g} Hz under {a.out}/views, tone [{vw['lo']:.4g}, {vw['hi']:.4g}], "
@@ -389,6 +433,12 @@ def main():
     eio.save_map(a.out, *model.downloadMap())
     # intensity panorama from the refined gradient map (solver.cpp:417-425 / 471-479), reconstructed on the device
     eio.save_pgm(os.path.join(a.out, "map_poisson_opt.pgm"), eio.normalize_robust(legm.reconstructIntensity(boundary=a.panorama_boundary), 0.1))
+    if a.frames:      # the frames along the FINAL trajectory: an independent picture of the scene, to set against map_poisson_opt.pgm
+        used = frame_mosaic(legm, frames, frames_t_ns, res.traj, a.frames_skip_zero)
+        mo = legm.mosaic()
+        eio.save_pgm(os.path.join(a.out, "frame_mosaic.pgm"), np.clip(np.rint(mo["mean"]), 0, 255).astype(np.uint8))
+        eio.save_pgm(os.path.join(a.out, "frame_mosaic_covered.pgm"), np.where(mo["covered"], 255, 0).astype(np.uint8))
+        print(f"frame mosaic: {used} of {len(frames_t_ns)} frames along the final trajectory, {mo['n_covered']} of {H * W} cells covered")
     if legm is not model:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()

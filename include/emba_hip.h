@@ -517,6 +517,57 @@ emba_status emba_render_views(emba_ctx* ctx, const double* plane_host /* H*W or 
 emba_status emba_seq_event_frames(emba_ctx* ctx, size_t beg, size_t end, const int64_t* edge_t_ns /* F+1, strictly increasing */, size_t F,
                                   int32_t signed_polarity, int32_t* frames_out /* [F, sh, sw] */, uint64_t* before_out, uint64_t* after_out);
 
+/* ---- The mosaic of intensity frames: frames -> panorama, the way back from emba_render_views.  Frames of bytes at sensor resolution
+ * (a DAVIS sensor's intensity frames, or what emba_render_views wrote) are stitched into the panorama along a trajectory; the mosaic's log-intensity
+ * plane and its backward differences are a gradient map that does not depend on the events at all.
+ *
+ * emba_mosaic_frames: F frames [F, sensor_h, sensor_w] of bytes at the times frame_t_ns [F] along the linear SO(3) spline (knots_xyzw [K, 4], t0_ns, dt_ns).
+ *   vote              pixel s = y * sensor_w + x of frame f has the byte v.  pm = project(R(frame_t[f]) * bearing_lut[s]), the pose stage and the warp of
+ *                     emba_render_views, unchanged.  The pixel votes as an event of emba_seq_event_panorama does (emba_amd/csrc/panorama_rule.h:
+ *                     pano_vote): the four cells around pm, weights in 256ths, 256 in all, columns wrapped modulo pano_w.  A row outside [0, pano_h) has no
+ *                     cell: its non-zero weight is a dropped vote.  Cell c receives w into sum_w[c] and w * v into sum_v[c], both uint64.  Integer sums do
+ *                     not depend on the order of the adds: emba_amd.io.mosaic_votes gives the same integers from the same pm.
+ *   skip_zero         non-zero: a pixel whose byte is 0 casts no vote and is counted in *skipped_out.  emba_render_views writes 0 for the pixels outside
+ *                     the panorama, so its frames need this flag; a real frame does not.
+ *   accumulate        0: both sums are zeroed first.  Otherwise the call adds to what is there: frames can be streamed in pieces.  The sums stay on the
+ *                     device; the frames go up in chunks of at most 65 535 frames and 32 MiB of bytes (one frame at the least).
+ *   exactness         the votes accumulated since the sums were last zeroed number F * sensor_h * sensor_w (skipped pixels count); they stay below 2^36, so
+ *                     that 65 280 * votes < 2^53 and both sums convert to double exactly.  A call that would reach 2^36 is refused.
+ * *dropped_out, *skipped_out: this call's dropped votes and skipped pixels; pm_out [F, sensor_h * sensor_w, 2] or NULL, the seam the tests pin.  F = 0 votes
+ * nothing (and without `accumulate` leaves zero sums with nothing accumulated).  EMBA_ERR_INVALID_ARG: frames, frame_t_ns or knots NULL with F > 0, K < 2,
+ * dt_ns <= 0, F >= 2^31, the 2^36 bound.  EMBA_ERR_TIME_RANGE: a frame time outside the knots, decided before anything is voted or zeroed.  A refused call
+ * leaves every output and the sums untouched.  A call that FAILS (EMBA_ERR_HIP: an allocation, a copy or a launch, possibly in a later chunk) is not a
+ * refusal: some chunks may have been voted, dropped_out / skipped_out are unwritten, and the mosaic is undefined until emba_mosaic_clear (or a call
+ * without `accumulate`).  While emba_enable_kernel_timing is on, timer slot 7 brackets the vote kernel of the first chunk.
+ *
+ * emba_mosaic_get: the sums and their mean.  covered[c] = sum_w[c] >= min_weight (min_weight >= 1; 256 is one whole pixel's worth);
+ * mean[c] = double(sum_v[c]) / double(sum_w[c]) where covered, else `fill` — one IEEE division of two exactly converted integers
+ * (emba_amd.io.mosaic_mean: the same bits); *n_covered_out the number of covered cells.  Each output may be NULL.
+ *
+ * emba_mosaic_map: the log-intensity plane and the gradient map (emba_amd/csrc/mosaic_rule.h: mosaic_log, mosaic_gradient).
+ *   plane             I = lo + mean * (hi - lo) / 255, in this order and without contraction: the inverse of emba_render_views' tone.  take_log == 0: L = I (the
+ *                     frames of run_ba.py --views-hz are log intensity already).  Otherwise L = log(I + eps), and a cell with I + eps <= 0 becomes
+ *                     uncovered.  L_out holds 0 in uncovered cells.
+ *   map               Gx[i][j] = L[i][j] - L[i][(j - 1) mod pano_w] where both cells are covered, else 0; Gy[i][j] = L[i][j] - L[i - 1][j] where both
+ *                     are covered and i >= 1, else 0: backward differences, the field whose divergence in emba_reconstruct_intensity is the 5-point operator.
+ *                     Given the device's L and the covered cells, emba_amd.io.gradient_from_plane gives the same bits.
+ *   make_resident     non-zero: Gx, Gy become the context's resident map, device to device, exactly as emba_upload_map of the same planes would leave it
+ *                     (a pending trial map is dropped).
+ * L_out, Gx_out, Gy_out: pano_h * pano_w doubles each, or NULL.
+ *
+ * emba_mosaic_clear: zero sums, nothing accumulated.
+ * EMBA_ERR_INVALID_ARG (get, map): min_weight < 1; fill, lo, hi or eps not finite; hi <= lo.  EMBA_ERR_STATE (get, map): nothing accumulated.  A refused call
+ * leaves every output, the sums and the resident map untouched.  The registered window, its order, the last evaluation, the resident sequence and the
+ * buffers of every other stage are left as they are by all four calls; without make_resident so is the resident map. */
+emba_status emba_mosaic_frames(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, const int64_t* frame_t_ns, size_t F,
+                               const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t skip_zero, int32_t accumulate,
+                               uint64_t* dropped_out, uint64_t* skipped_out, double* pm_out /* [F, sh*sw, 2] or NULL */);
+emba_status emba_mosaic_get(emba_ctx* ctx, uint64_t min_weight, double fill, uint64_t* sum_w_out, uint64_t* sum_v_out, double* mean_out,
+                            uint8_t* covered_out, uint64_t* n_covered_out);
+emba_status emba_mosaic_map(emba_ctx* ctx, uint64_t min_weight, double lo, double hi, double eps, int32_t take_log,
+                            double* L_out, double* Gx_out, double* Gy_out /* each H*W or NULL */, int32_t make_resident);
+emba_status emba_mosaic_clear(emba_ctx* ctx);
+
 /* ---- The event simulator: a recording from a log-intensity panorama plane and a trajectory — the events a sensor would report whose pixels see
  * the samples of emba_render_views change.  No noise, no refractory period, no exposure model; inside a step the brightness of a pixel is linear in time.
  *
