@@ -29,6 +29,11 @@ class EmbaCfg(C.Structure):
                 ("device", C.c_int32), ("stream", C.c_void_p)]
 
 
+class EmbaAlignSettings(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("min_pixels", C.c_int32), ("lambda0", C.c_double), ("lambda_up", C.c_double), ("lambda_down", C.c_double),
+                ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("tol_rot", C.c_double), ("huber_k", C.c_double)]
+
+
 # symbol -> (restype, argtypes); exactly the entry points include/emba_hip.h declares
 SIGNATURES = {
     "emba_abi_version": (C.c_int, []),
@@ -131,6 +136,10 @@ SIGNATURES = {
     "emba_sim_size": (C.c_int, [C.c_void_p, _szp]),
     "emba_sim_get": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, _u16p, _u16p, _u8p, _i64p]),
     "emba_seq_from_sim": (C.c_int, [C.c_void_p, C.c_int32, _szp]),
+    "emba_frames_align_eval": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _dp, _dp, _u8p, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                         C.c_double, _dp, C.POINTER(C.c_uint64), _dp, _dp]),
+    "emba_frames_align": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _dp, _dp, _u8p, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                    C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), _i32p, _i32p, _dp, C.POINTER(C.c_uint64)]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -192,6 +192,7 @@ void emba_destroy(emba_ctx* c)
 #include "view_host.h"       // sensor views along the trajectory: the frames the camera would have seen, the event counts it reported
 #include "mosaic_host.h"     // the way back: intensity frames stitched into the panorama along the trajectory, and the gradient map made from the mosaic
 #include "sim_host.h"        // the event simulator: a recording from a panorama plane and a trajectory, and its way into the resident sequence
+#include "align_host.h"      // poses from frames: each intensity frame's rotation aligned to a panorama plane (the mosaic's mean, or a caller's)
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

@@ -1080,3 +1080,210 @@ def simulate_from_plane(plane, lut, knots, t0_ns, dt_ns, step_t_ns, sensor, c_on
     pm = view_pm(lut, knots, t0_ns, dt_ns, step_t_ns, P.shape[1], P.shape[0])
     views, outside = render_views(P, pm, with_outside=True)
     return simulate_events(views, outside, step_t_ns, int(sensor[0]), c_on, c_off, max_per_step)
+
+
+# ---- intensity frames aligned to a panorama plane (numpy forms of emba_frames_align_eval and emba_frames_align, include/emba_hip.h; the device forms are
+# LEGM.align_frames_eval and LEGM.align_frames).  The rule is emba_amd/csrc/align_rule.h's, operation for operation where bits are promised:
+# given the same pm, the sample, its gradient, the classes and the residual have the same bits.  rb and J23 are numpy's own.
+ALIGN_CONVERGED, ALIGN_STALLED, ALIGN_ITERATIONS, ALIGN_DEGENERATE = 1, 2, 3, 4      # EMBA_ALIGN_*
+ALIGN_STATUS_NAMES = {1: "converged", 2: "stalled", 3: "iterations", 4: "degenerate"}
+ALIGN_USED, ALIGN_OUTSIDE, ALIGN_MASKED, ALIGN_SKIPPED = 0, 1, 2, 3                  # the classes of a pixel, in the order of counts
+ALIGN_DEFAULTS = dict(max_iters=30, lambda0=1e-3, lambda_up=10.0, lambda_down=10.0, lambda_min=1e-9, lambda_max=1e6, tol_rot=1e-6, min_pixels=16, huber_k=0.0)
+
+
+def align_settings(**kw):
+    """ALIGN_DEFAULTS with the given members replaced; the refusals of emba_frames_align's settings as ValueError."""
+    unknown = set(kw) - set(ALIGN_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)}")
+    s = dict(ALIGN_DEFAULTS, **kw)
+    ok = (int(s["max_iters"]) >= 0 and np.isfinite(s["lambda_up"]) and np.isfinite(s["lambda_down"]) and s["lambda_up"] > 1.0 and s["lambda_down"] > 1.0
+          and np.isfinite(s["lambda0"]) and s["lambda0"] > 0.0 and 0.0 <= s["lambda_min"] <= s["lambda_max"] and s["lambda_max"] > 0.0 and s["tol_rot"] >= 0.0
+          and int(s["min_pixels"]) >= 3 and not np.isnan(s["huber_k"]))
+    if not ok:
+        raise ValueError(f"settings out of range: {s}")
+    return s
+
+
+def _align_cell(shape, pm):
+    """view_sample's cell of every pm [..., 2] on a plane of `shape`: (inside, r0, r1, c0, c1, ax, ay); the rows of an outside pixel are 0."""
+    H, W = shape
+    pm = np.asarray(pm, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(pm[..., 0]) < 2147483648.0) & (np.abs(pm[..., 1]) < 2147483648.0)
+    x, y = np.where(ok, pm[..., 0], 0.0), np.where(ok, pm[..., 1], -1.0)
+    fx, fy = np.floor(x), np.floor(y)
+    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    inside = ok & (iy >= 0) & (iy + 1 <= H - 1)
+    c0 = ix % W
+    c1 = np.where(c0 + 1 == W, 0, c0 + 1)
+    return inside, np.where(inside, iy, 0), np.where(inside, iy + 1, 0), c0, c1, x - fx, y - fy
+
+
+def align_sample(plane, pm):
+    """align_sample (align_rule.h) of plane [H, W] at every pm [..., 2]: (val, gx, gy, outside).  The cell and the outside test are render_views'; val is its
+    value, gx = (1 - ay) (P[iy][c1] - P[iy][c0]) + ay (P[iy+1][c1] - P[iy+1][c0]), gy = (1 - ax) (P[iy+1][c0] - P[iy][c0]) + ax (P[iy+1][c1] - P[iy][c1]),
+    in this order.  All three are 0 where the pixel is outside."""
+    P = np.asarray(plane, dtype=np.float64)
+    inside, r0, r1, c0, c1, ax, ay = _align_cell(P.shape, pm)
+    p00, p01, p10, p11 = P[r0, c0], P[r0, c1], P[r1, c0], P[r1, c1]
+    top = (1.0 - ax) * p00 + ax * p01
+    bot = (1.0 - ax) * p10 + ax * p11
+    val = (1.0 - ay) * top + ay * bot
+    gx = (1.0 - ay) * (p01 - p00) + ay * (p11 - p10)
+    gy = (1.0 - ax) * (p10 - p00) + ax * (p11 - p01)
+    return np.where(inside, val, 0.0), np.where(inside, gx, 0.0), np.where(inside, gy, 0.0), ~inside
+
+
+def align_warp(lut, q, W, H):
+    """numpy's own warp of one frame with the rotation q (xyzw): rb = R(q) lut [S, 3], pm [S, 2] by synth.project_equirect and J23 [S, 2, 3] = d pm / d delta
+    for the left perturbation R <- exp(delta) R (the equirectangular projection's Jacobian times -[rb]x)."""
+    from . import synth
+    lut = np.asarray(lut, dtype=np.float64).reshape(-1, 3)
+    rb = lut @ synth._quat_to_R(np.asarray(q, dtype=np.float64)).T
+    px, py = synth.project_equirect(int(W), int(H), rb)
+    x, y, z = rb[:, 0], rb[:, 1], rb[:, 2]
+    fx, fy = W / (2.0 * np.pi), H / np.pi
+    d2 = x * x + z * z
+    rho2 = d2 + y * y
+    s = fy / (np.sqrt(d2) * rho2)
+    zero = np.zeros_like(x)
+    Jp = np.stack([np.stack([fx * z / d2, zero, -fx * x / d2], axis=1), np.stack([-s * x * y, s * d2, -s * y * z], axis=1)], axis=1)      # [S, 2, 3]
+    M = np.stack([np.stack([zero, z, -y], axis=1), np.stack([-z, zero, x], axis=1), np.stack([y, -x, zero], axis=1)], axis=1)               # -[rb]x
+    return rb, np.stack([px, py], axis=1), Jp @ M
+
+
+def align_huber(r, huber_k):
+    """(w, rho) of the residuals r: huber_k <= 0 quadratic; else w = 1, rho = r^2 for |r| <= k and w = k / |r|, rho = 2 k |r| - k^2 beyond."""
+    r = np.asarray(r, dtype=np.float64)
+    k = float(huber_k)
+    a = np.abs(r)
+    if not k > 0.0:
+        return np.ones_like(r), r * r
+    far = a > k
+    return np.where(far, k / np.where(far, a, 1.0), 1.0), np.where(far, 2.0 * k * a - k * k, r * r)
+
+
+def align_terms(frame_u8, pm, lut, q, plane, valid=None, lo=0.0, hi=255.0, skip_zero=False, huber_k=0.0):
+    """The terms of one frame's pixels (align_pixel, align_rule.h) from a given pm [S, 2] (the device's pm_out, or align_warp's) and numpy's own J23 of q: a
+    dict of cls int [S] (ALIGN_USED / OUTSIDE / MASKED / SKIPPED, in this precedence), r [S] (val - I with I = lo + v (hi - lo) / 255; 0 where the pixel is
+    not used), w, rho [S] and g [S, 3] = gx J23[0,:] + gy J23[1,:]."""
+    P = np.asarray(plane, dtype=np.float64)
+    H, W = P.shape
+    v = np.asarray(frame_u8, dtype=np.uint8).reshape(-1)
+    pm = np.asarray(pm, dtype=np.float64).reshape(-1, 2)
+    if pm.shape[0] != v.size:
+        raise ValueError(f"pm has {pm.shape[0]} rows, the frame has {v.size} pixels")
+    val, gx, gy, outside = align_sample(P, pm)
+    cls = np.full(v.size, ALIGN_USED, dtype=np.int64)
+    if skip_zero:
+        cls[v == 0] = ALIGN_SKIPPED
+    if valid is not None:
+        ok = np.asarray(valid).astype(bool)
+        _, r0, r1, c0, c1, _, _ = _align_cell(P.shape, pm)
+        cls[~(ok[r0, c0] & ok[r0, c1] & ok[r1, c0] & ok[r1, c1])] = ALIGN_MASKED
+    cls[outside] = ALIGN_OUTSIDE
+    used = cls == ALIGN_USED
+    inten = float(lo) + v.astype(np.float64) * (float(hi) - float(lo)) / 255.0
+    r = np.where(used, val - inten, 0.0)
+    w, rho = align_huber(r, huber_k)
+    J23 = align_warp(lut, q, W, H)[2]
+    g = gx[:, None] * J23[:, 0, :] + gy[:, None] * J23[:, 1, :]
+    return dict(cls=cls, r=r, w=np.where(used, w, 0.0), rho=np.where(used, rho, 0.0), g=np.where(used[:, None], g, 0.0))
+
+
+def align_sum_terms(terms):
+    """The ten terms of every pixel [S, 10] (H 00 01 02 11 12 22, b 0 1 2, rho), zero where the pixel is not used."""
+    g, w, r = terms["g"], terms["w"], terms["r"]
+    wg = w[:, None] * g
+    return np.stack([wg[:, 0] * g[:, 0], wg[:, 0] * g[:, 1], wg[:, 0] * g[:, 2], wg[:, 1] * g[:, 1], wg[:, 1] * g[:, 2], wg[:, 2] * g[:, 2],
+                     wg[:, 0] * r, wg[:, 1] * r, wg[:, 2] * r, terms["rho"]], axis=1)
+
+
+def align_sums(terms, with_scale=False):
+    """The ten sums and the four counts of one frame's terms: (sums float64 [10], counts int64 [4]: used, outside, masked, skipped), accumulated in
+    np.longdouble and returned as doubles.  with_scale also sum |term| per sum, what a bound on a sum's rounding error is relative to."""
+    t = align_sum_terms(terms)
+    sums = t.astype(np.longdouble).sum(axis=0).astype(np.float64)
+    counts = np.bincount(terms["cls"], minlength=4).astype(np.int64)
+    return (sums, counts, np.abs(t).astype(np.longdouble).sum(axis=0).astype(np.float64)) if with_scale else (sums, counts)
+
+
+def align_step(Hm, b, lam):
+    """align_solve (align_rule.h): delta [3] of (H + lam diag H) delta = -b by a Cholesky, H [3, 3] symmetric (or its six entries 00 01 02 11 12 22); None where a
+    pivot is not positive."""
+    Hm = np.asarray(Hm, dtype=np.float64)
+    if Hm.size == 6:
+        h = Hm.reshape(6)
+        Hm = np.array([[h[0], h[1], h[2]], [h[1], h[3], h[4]], [h[2], h[4], h[5]]])
+    A = Hm + float(lam) * np.diag(np.diag(Hm))
+    L = np.zeros((3, 3))
+    for j in range(3):
+        d = A[j, j] - L[j, :j] @ L[j, :j]
+        if not d > 0.0:
+            return None
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 3):
+            L[i, j] = (A[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
+    y = np.zeros(3)
+    rhs = -np.asarray(b, dtype=np.float64).reshape(3)
+    for i in range(3):
+        y[i] = (rhs[i] - L[i, :i] @ y[:i]) / L[i, i]
+    x = np.zeros(3)
+    for i in (2, 1, 0):
+        x[i] = (y[i] - L[i + 1:, i] @ x[i + 1:]) / L[i, i]
+    return x if np.isfinite(x).all() else None
+
+
+def align_frames(frames_u8, q_xyzw, lut, plane, valid=None, lo=0.0, hi=255.0, skip_zero=False, **settings):
+    """The loop of emba_frames_align in numpy, with numpy's own pm: per frame (frames_u8 [F, S], q_xyzw [F, 4]) the Levenberg-Marquardt iteration of
+    align_step (align_rule.h) — solve, trial q' = normalise(exp(delta) q), accepted when n' >= min_pixels and cost' / n' < cost / n, lambda down on accept and
+    up on reject; a frame ends converged (|delta| < tol_rot on an accepted step), stalled (lambda > lambda_max), out of iterations or degenerate.  A dict of q
+    [F, 4], sums [F, 10], counts [F, 4], status, iters, cost0, n0 [F]."""
+    s = align_settings(**settings)
+    P = np.asarray(plane, dtype=np.float64)
+    H, W = P.shape
+    q_in = np.asarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+    F = q_in.shape[0]
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)
+
+    def evaluate(f, q):
+        return align_sums(align_terms(frames[f], align_warp(lut, q, W, H)[1], lut, q, P, valid, lo, hi, skip_zero, s["huber_k"]))
+
+    out = dict(q=q_in.copy(), sums=np.zeros((F, 10)), counts=np.zeros((F, 4), np.int64), status=np.zeros(F, np.int32), iters=np.zeros(F, np.int32),
+               cost0=np.zeros(F), n0=np.zeros(F, np.int64))
+    for f in range(F):
+        q = q_in[f].copy()
+        sums, counts = evaluate(f, q)
+        out["cost0"][f], out["n0"][f] = sums[9], counts[0]
+        lam, iters = float(s["lambda0"]), 0
+        while True:
+            delta = align_step(sums[:6], sums[6:9], lam) if counts[0] >= s["min_pixels"] else None
+            if delta is None:
+                status = ALIGN_DEGENERATE
+                break
+            if iters >= s["max_iters"]:
+                status = ALIGN_ITERATIONS
+                break
+            trial = so3.mul(so3.exp(delta), q)
+            tsums, tcounts = evaluate(f, trial)
+            iters += 1
+            if tcounts[0] >= s["min_pixels"] and tsums[9] / tcounts[0] < sums[9] / counts[0]:
+                q, sums, counts = trial, tsums, tcounts
+                lam = max(lam / s["lambda_down"], s["lambda_min"])
+                if np.linalg.norm(delta) < s["tol_rot"]:
+                    status = ALIGN_CONVERGED
+                    break
+            else:
+                lam *= s["lambda_up"]
+                if lam > s["lambda_max"]:
+                    status = ALIGN_STALLED
+                    break
+        out["q"][f], out["sums"][f], out["counts"][f], out["status"][f], out["iters"][f] = q, sums, counts, status, iters
+    return out
+
+
+def rotation_angle_between(qa, qb):
+    """The angle (rad) of the rotation from qa to qb, quaternions xyzw [..., 4]."""
+    qa, qb = np.asarray(qa, dtype=np.float64).reshape(-1, 4), np.asarray(qb, dtype=np.float64).reshape(-1, 4)
+    return np.array([np.linalg.norm(so3.log(so3.mul(b, so3.inverse(a)))) for a, b in zip(qa, qb)])

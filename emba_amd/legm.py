@@ -382,6 +382,58 @@ class LEGM:
         """Zero sums, nothing accumulated (emba_mosaic_clear)."""
         self._check(self._L.emba_mosaic_clear(self._ctx))
 
+    def _align_args(self, frames, q_xyzw, plane, valid, use_mosaic):
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+        F, S = q.shape[0], self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        if plane is None and not use_mosaic:
+            raise ValueError("a plane [pano_height, pano_width], or use_mosaic")
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float64)
+            if plane.shape != (self.H, self.W):
+                raise ValueError("plane must be pano_height x pano_width float64")
+            if valid is not None:
+                valid = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+                if valid.shape != (self.H, self.W):
+                    raise ValueError("valid must be pano_height x pano_width")
+        return frames, q, F, S, plane, (valid if plane is not None else None)
+
+    def align_frames_eval(self, frames, q_xyzw, plane=None, valid=None, use_mosaic=False, min_weight=256, fill=0.0, lo=0.0, hi=255.0, skip_zero=False,
+                          huber_k=0.0, want_pm=False, want_resid=False):
+        """One evaluation of the photometric alignment of the bytes frames [F, sensor_h, sensor_w] at the rotations q_xyzw [F, 4] against `plane`
+        [pano_h, pano_w] under the optional mask `valid`, or, with plane=None and use_mosaic, against the mosaic's mean under its covered cells
+        (emba_frames_align_eval; the rule: include/emba_hip.h).  The frames' bytes mean I = lo + v (hi - lo) / 255 in the plane's units (the mosaic's mean
+        is in byte units: lo = 0, hi = 255).  A dict of sums float64 [F, 10] (H's six entries 00 01 02 11 12 22, b's three, the cost), counts int64 [F, 4]
+        (used, outside, masked, skipped), pm [F, S, 2] and resid [F, S] (None unless asked for) — io.align_terms and io.align_sums given the same pm."""
+        frames, q, F, S, plane, valid = self._align_args(frames, q_xyzw, plane, valid, use_mosaic)
+        sums, counts = np.zeros((F, 10)), np.zeros((F, 4), np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        resid = np.empty((F, S)) if want_resid else None
+        self._check(self._L.emba_frames_align_eval(self._ctx, _p(frames, _u8p), F, _p(q, _dp), _p(plane, _dp), _p(valid, _u8p), 1 if use_mosaic else 0,
+                                                   int(min_weight), float(fill), float(lo), float(hi), 1 if skip_zero else 0, float(huber_k), _p(sums, _dp),
+                                                   _p(counts, C.POINTER(C.c_uint64)), _p(pm, _dp), _p(resid, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), pm=pm, resid=resid)
+
+    def align_frames(self, frames, q_xyzw, plane=None, valid=None, use_mosaic=False, min_weight=256, fill=0.0, lo=0.0, hi=255.0, skip_zero=False, **settings):
+        """Poses from frames (emba_frames_align): every frame's own rotation refined by a 3-DoF Levenberg-Marquardt on its photometric error against the
+        plane (arguments as align_frames_eval; settings: the members of io.ALIGN_DEFAULTS).  A dict of q [F, 4], sums [F, 10] and counts [F, 4] at q,
+        status int32 [F] (io.ALIGN_CONVERGED / STALLED / ITERATIONS / DEGENERATE), iters [F] (trials evaluated), cost0 and n0 [F] (cost and used pixels
+        at q_xyzw).  io.align_frames is the same loop in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        frames, q, F, S, plane, valid = self._align_args(frames, q_xyzw, plane, valid, use_mosaic)
+        cs = _lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                    float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]), float(s["huber_k"]))
+        q_out, sums, counts = q.copy(), np.zeros((F, 10)), np.zeros((F, 4), np.uint64)
+        status, iters, cost0, n0 = np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F), np.zeros(F, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_align(self._ctx, _p(frames, _u8p), F, _p(q, _dp), _p(plane, _dp), _p(valid, _u8p), 1 if use_mosaic else 0,
+                                              int(min_weight), float(fill), float(lo), float(hi), 1 if skip_zero else 0, C.addressof(cs), _p(q_out, _dp),
+                                              _p(sums, _dp), _p(counts, u64p), _p(status, _i32p), _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p)))
+        return dict(q=q_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64))
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

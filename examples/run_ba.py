@@ -83,6 +83,36 @@ def frame_mosaic(legm, frames, t_ns, traj, skip_zero):
     return int(keep.sum())
 
 
+def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_zero, log=print):
+    """--refine-frames N: poses from frames.  Per round: the frames are stitched along the current raw trajectory, every frame is
+    aligned to that mosaic's mean under its covered cells on the device, and io.fit_ctrl_poses of the aligned rotations at the frame times, merged with the
+    raw poses outside the frames' span, becomes the raw trajectory.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the aligned
+    rotation, the status and the mean cost before and after, of the last round."""
+    keep = (t_ns >= traj.t0_ns) & (t_ns < traj.t0_ns + traj.dt_ns * (traj.size() - 1))
+    if not keep.any():
+        raise SystemExit("--frames: no frame time lies inside the trajectory's knots")
+    fr, ts = frames[keep], t_ns[keep]
+    t_beg, dt = traj.t0_ns * 1e-9, traj.dt_ns * 1e-9
+    rows = []
+    for rnd in range(1, rounds + 1):
+        legm.mosaic_frames(fr, ts, traj, skip_zero=skip_zero)
+        q0 = np.array([traj.evaluate(int(tn)) for tn in ts])
+        r = legm.align_frames(fr, q0, use_mosaic=True, lo=0.0, hi=255.0, skip_zero=skip_zero, huber_k=huber_k)
+        before, after = r["cost0"] / np.maximum(r["n0"], 1), r["sums"][:, 9] / np.maximum(r["counts"][:, 0], 1)
+        tf = ts * 1e-9
+        outside = (t_raw < tf[0]) | (t_raw > tf[-1])
+        t_all, q_all = np.concatenate([t_raw[outside], tf]), np.concatenate([q_raw[outside], r["q"]])
+        order = np.argsort(t_all, kind="stable")
+        t_raw, q_raw = t_all[order], q_all[order]
+        traj = LinearTrajectory(eio.fit_ctrl_poses(t_raw, q_raw, t_beg, dt, traj.size()), traj.t0_ns, traj.dt_ns)
+        moved = eio.rotation_angle_between(q0, r["q"])
+        names = ", ".join(f"{int((r['status'] == k).sum())} {v}" for k, v in eio.ALIGN_STATUS_NAMES.items())
+        log(f"refine-frames round {rnd}: {len(ts)} frames aligned to their mosaic ({names}); mean cost {before.mean():.4g} -> {after.mean():.4g}, "
+            f"mean turn {moved.mean():.3e} rad, up to {int(r['iters'].max())} trials")
+        rows = [(tn, q, int(st), b, a_) for tn, q, st, b, a_ in zip(ts, r["q"], r["status"], before, after)]
+    return traj, t_raw, q_raw, rows
+
+
 def simulate(a, ap):
     """--simulate: a recording from a log-intensity plane and a trajectory, on the device; with --demo, then the BA on it."""
     if not (np.isfinite(a.sim_hz) and a.sim_hz > 0):
@@ -187,6 +217,10 @@ def main():
     ap.add_argument("--frames-eps", type=float, default=1.0 / 255.0, help="L = log(I + eps)")
     ap.add_argument("--frames-log", type=int, default=1, choices=[0, 1], help="0: the bytes are log intensity already (the frames of --views-hz): no logarithm is taken")
     ap.add_argument("--frames-skip-zero", action="store_true", help="a byte of 0 is no measurement (--views-hz writes 0 where a pixel looks past the panorama)")
+    ap.add_argument("--refine-frames", type=int, default=0, metavar="N", help="with --frames and given poses: N rounds before the BA, each stitching the frames along "
+                    "the current raw trajectory, aligning every frame's rotation to that mosaic on the device and fitting the raw trajectory to the aligned "
+                    "rotations (DESIGN.md section 20); writes <out>/frames_aligned.txt")
+    ap.add_argument("--frames-huber", type=float, default=0.0, metavar="K", help="with --refine-frames: the Huber threshold of the alignment, in byte units (0: quadratic)")
     ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity"], help="identity: no --poses is needed — every raw pose is the identity "
                     "(what a run without a front end always has; with --window-size).  events: no --poses is needed — the angular velocity of every slice of events is "
                     "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
@@ -233,6 +267,12 @@ def main():
     if a.init_map == "frames" and a.init_poses != "given":
         ap.error("--init-map frames stitches the frames along the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity, "
                  "whose trajectory at that point carries the timing only")
+    if a.refine_frames < 0 or (a.refine_frames and not a.frames):
+        ap.error("--refine-frames N (N >= 0) aligns the frames of --frames DIR")
+    if a.refine_frames and a.init_poses != "given":
+        ap.error("--refine-frames aligns the frames from the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity")
+    if not (np.isfinite(a.frames_huber) and a.frames_huber >= 0.0):
+        ap.error("--frames-huber is finite and not negative")
     if a.frames and not (np.isfinite(a.frames_lo) and np.isfinite(a.frames_hi) and np.isfinite(a.frames_eps) and a.frames_hi > a.frames_lo):
         ap.error("--frames-lo, --frames-hi and --frames-eps are finite, and --frames-hi is above --frames-lo")
     if not a.demo and a.init_poses == "given" and not a.poses:
@@ -333,6 +373,14 @@ def main():
         print(f"{events.size()} events, {traj.size()} control poses, panorama {H}x{W}" + (f", {world} rank(s) through the sharded host" if legm is not model else ""))
     if a.frames:
         frames, frames_t_ns = load_frames(a.frames, sw, sh)
+    if a.refine_frames:      # poses from frames: the raw trajectory is refitted to the frames' aligned rotations before anything else reads it
+        traj, t, qs, rows = refine_frames(legm, frames, frames_t_ns, traj, np.asarray(t, dtype=np.float64), np.asarray(qs, dtype=np.float64), a.refine_frames,
+                                          a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None))
+        if rank == 0:
+            with open(os.path.join(a.out, "frames_aligned.txt"), "w") as fh:
+                fh.write("# t[s] qx qy qz qw status(1 converged, 2 stalled, 3 iterations, 4 degenerate) mean_cost_before mean_cost_after\n")
+                for tn, q, st, b, a_ in rows:
+                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {b:.9g} {a_:.9g}\n")
     if a.init_map == "frames":      # the mosaic of the frames along the raw trajectory, on the device; its gradient map is handed on as the given map
         used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero)
         fm = legm.mosaic_map(lo=a.frames_lo, hi=a.frames_hi, eps=a.frames_eps, take_log=bool(a.frames_log))

@@ -615,6 +615,68 @@ emba_status emba_sim_size(const emba_ctx* ctx, size_t* n);
 emba_status emba_sim_get(emba_ctx* ctx, size_t beg, size_t end, uint16_t* x, uint16_t* y, uint8_t* pol, int64_t* t_ns);
 emba_status emba_seq_from_sim(emba_ctx* ctx, int32_t sampling_rate, size_t* n_kept);
 
+/* ---- Intensity frames aligned to the panorama: poses from frames.  The mosaic stitches frames along a GIVEN trajectory; here each frame's
+ * own rotation is refined by direct photometric alignment against a panorama plane — a 3-DoF Levenberg-Marquardt per frame, the frames independent.  The
+ * rule lives in emba_amd/csrc/align_rule.h; emba_amd.io.align_sample / align_terms / align_sums / align_step / align_frames are the same rule in numpy.
+ *
+ * Frame f has the rotation q_xyzw[f] (xyzw, unit; a per-frame input, not a spline); pixel s = y * sensor_w + x of it has the byte v.
+ *   warp              rb = R(q_f) * bearing_lut[s]; pm and J23 = d pm / d delta for the left perturbation R <- exp(delta) R, by the projection of the step
+ *                     path with its Jacobian.  pm is computed without contraction, as in emba_render_views: it feeds floor().
+ *   sample            ix, iy, ax, ay, the wrapped columns c0, c1 and the outside test are emba_render_views' (view_sample).  val is its value;
+ *                     gx = (1 - ay) (P[iy][c1] - P[iy][c0]) + ay (P[iy+1][c1] - P[iy+1][c0]), gy = (1 - ax) (P[iy+1][c0] - P[iy][c0]) + ax (P[iy+1][c1] - P[iy][c1]),
+ *                     in this order, without contraction: numpy gives the same bits from the same pm.
+ *   which pixels      outside: as in emba_render_views.  masked: a `valid` plane is there and any of the four cells holds 0.  skipped: skip_zero != 0 and
+ *                     v == 0.  Counted per frame in this precedence; every other pixel is used (n).
+ *   residual          I = lo + v * (hi - lo) / 255, in this order, without contraction (the inverse tone of emba_mosaic_map); r = val - I.  The plane and
+ *                     the frames are in the same units; whether that is intensity or its logarithm is the caller's business.
+ *   weight            huber_k <= 0: w = 1, rho = r^2.  Otherwise the same for |r| <= huber_k, and w = huber_k / |r|, rho = 2 huber_k |r| - huber_k^2 beyond.
+ *   sums              g = gx J23[0,:] + gy J23[1,:].  Per frame H = sum w g^T g (six entries: 00 01 02 11 12 22), b = sum w g^T r (three), cost = sum rho,
+ *                     and n.  The sums of a frame are reduced in a fixed order: the same call on the same inputs returns the same bits.
+ *   plane             plane_host: pano_h * pano_w doubles, uploaded into a buffer of this stage's own, with valid_host (pano_h * pano_w bytes, or NULL: no
+ *                     mask).  plane_host NULL and use_mosaic != 0: the mean of the mosaic as it stands (emba_mosaic_get's, under min_weight and fill, in byte
+ *                     units: lo = 0, hi = 255 make I = v) with its covered cells as the mask, device to device; valid_host is not read.  min_weight and
+ *                     fill are read in that case only, use_mosaic only where plane_host is NULL.
+ *
+ * emba_frames_align_eval: one evaluation.  Outputs, each may be NULL: sums_out [F, 10] (H's six, b's three, cost), counts_out [F, 4] (used, outside, masked,
+ * skipped), pm_out [F, sensor_h * sensor_w, 2] (the seam the tests pin) and resid_out [F, sensor_h * sensor_w] (r, 0 where the pixel is not used).
+ *
+ * emba_frames_align: the loop, per frame, the frames and their rotations resident on the device between iterations.
+ *   step              (H + lambda diag H) delta = -b by a 3 x 3 Cholesky.  A frame is degenerate when a pivot is not positive or n < min_pixels: it is frozen.
+ *                     The trial is q' = normalise(exp(delta) (x) q); it is accepted when n' >= min_pixels and cost' / n' < cost / n (the means: pixels enter
+ *                     and leave the panorama and the mask).  Accepted: q <- q', lambda <- max(lambda / lambda_down, lambda_min).  Rejected:
+ *                     lambda <- lambda * lambda_up.  The sums of an accepted trial are the next iteration's: an iteration costs one evaluation.
+ *   a frame ends      EMBA_ALIGN_CONVERGED: |delta| < tol_rot on an accepted step; EMBA_ALIGN_STALLED: lambda > lambda_max; EMBA_ALIGN_ITERATIONS: max_iters
+ *                     trials were evaluated; EMBA_ALIGN_DEGENERATE.
+ * Outputs, each may be NULL: q_out [F, 4]; sums_out, counts_out as above, at q_out (bit for bit what emba_frames_align_eval gives there); status_out [F];
+ * iters_out [F] (trials evaluated); cost0_out, n0_out [F]: cost and n at q_xyzw.
+ *
+ * Both calls cut F into chunks of at most 65 535 frames and 32 MiB of bytes (one frame at the least); a chunk's bytes go up once.  F = 0 launches nothing.
+ * Refusals are decided before anything is uploaded and leave every output untouched.  EMBA_ERR_INVALID_ARG: frames or q_xyzw NULL with F > 0; F >= 2^31; lo or
+ * hi not finite, hi <= lo; huber_k a NaN; a q that is not finite or has zero norm; neither plane_host nor use_mosaic; with use_mosaic min_weight < 1 or fill
+ * not finite; settings NULL, max_iters < 0, lambda_up or lambda_down <= 1, lambda0 <= 0, not 0 <= lambda_min <= lambda_max, tol_rot < 0, min_pixels < 3.
+ * EMBA_ERR_STATE: use_mosaic with nothing accumulated.  The registered window, its order, the last evaluation, the resident sequence, the mosaic's sums, the
+ * resident map and every other stage's buffers are left as they are (use_mosaic rewrites the mosaic's mean and covered scratch, as emba_mosaic_get does).
+ * While emba_enable_kernel_timing is on, timer slot 7 brackets the first evaluation kernel of the first chunk. */
+#define EMBA_ALIGN_RUNNING 0      /* (never reported) */
+#define EMBA_ALIGN_CONVERGED 1
+#define EMBA_ALIGN_STALLED 2
+#define EMBA_ALIGN_ITERATIONS 3
+#define EMBA_ALIGN_DEGENERATE 4
+typedef struct {
+    int32_t max_iters, min_pixels;
+    double lambda0, lambda_up, lambda_down, lambda_min, lambda_max, tol_rot, huber_k;
+} emba_align_settings;
+emba_status emba_frames_align_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                                   const double* plane_host /* H*W or NULL */, const uint8_t* valid_host /* H*W or NULL */, int32_t use_mosaic,
+                                   uint64_t min_weight, double fill, double lo, double hi, int32_t skip_zero, double huber_k,
+                                   double* sums_out /* [F, 10] */, uint64_t* counts_out /* [F, 4] */, double* pm_out /* [F, sh*sw, 2] */,
+                                   double* resid_out /* [F, sh*sw] */);
+emba_status emba_frames_align(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                              const double* plane_host /* H*W or NULL */, const uint8_t* valid_host /* H*W or NULL */, int32_t use_mosaic,
+                              uint64_t min_weight, double fill, double lo, double hi, int32_t skip_zero, const emba_align_settings* settings,
+                              double* q_out /* [F, 4] */, double* sums_out /* [F, 10] */, uint64_t* counts_out /* [F, 4] */, int32_t* status_out /* [F] */,
+                              int32_t* iters_out /* [F] */, double* cost0_out /* [F] */, uint64_t* n0_out /* [F] */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
