@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, align_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, align_host.h, track_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -263,6 +263,18 @@ struct AlignBuffers {
     DevBuf q, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
 };
 
+// Intensity frames tracked against their own growing mosaic (track_host.h).  lw, lv: the two uint64 sums per cell of the levels 1 ... 7 [H_l, W_l], resident
+// between calls (level 0's are the mosaic's sum_w, sum_v); voted: bit l is set when the last successful emba_frames_track voted into level l.  Scratch of one
+// call, over its F frames: the frame times, every frame's rotation, status, iterations per level, cost, counts and overlap; counters: [0] dropped votes,
+// [1] skipped pixels.  Over one batch (or one chunk of emba_track_eval): pred, the predicted starts; pm and resid; the rest is what AlignBuffers holds for
+// emba_frames_align's loop, here for this stage's own.  frames: one chunk of bytes.
+struct TrackBuffers {
+    DevBuf lw[8], lv[8]; uint32_t voted = 0;
+    DevBuf t, q_all, status_all, iters_all, cost_all, overlap_all, counts_all, counters;
+    DevBuf frames, pred, pm, resid, partial, q_trial, esums, ecounts;
+    DevBuf q, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
+};
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -461,6 +473,7 @@ struct emba_ctx {
     SimState sim;                 // the event simulator: the simulated recording and the scratch of a call (sim_host.h)
     MosaicBuffers mosaic;         // the mosaic of intensity frames: the resident sums and the scratch of a call (mosaic_host.h)
     AlignBuffers align;           // intensity frames aligned to a panorama plane: the scratch of a call (align_host.h)
+    TrackBuffers track;           // intensity frames tracked against their own growing mosaic: the level planes and the scratch of a call (track_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -193,6 +193,7 @@ void emba_destroy(emba_ctx* c)
 #include "mosaic_host.h"     // the way back: intensity frames stitched into the panorama along the trajectory, and the gradient map made from the mosaic
 #include "sim_host.h"        // the event simulator: a recording from a panorama plane and a trajectory, and its way into the resident sequence
 #include "align_host.h"      // poses from frames: each intensity frame's rotation aligned to a panorama plane (the mosaic's mean, or a caller's)
+#include "track_host.h"      // poses from the frames alone: each frame aligned to the growing mosaic of the frames before it, then voted into it
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

@@ -1283,6 +1283,163 @@ def align_frames(frames_u8, q_xyzw, lut, plane, valid=None, lo=0.0, hi=255.0, sk
     return out
 
 
+# ---- intensity frames tracked against their own growing mosaic (numpy forms of emba_frames_track, emba_track_eval and emba_track_level_get,
+# include/emba_hip.h; the device forms are LEGM.track_frames, LEGM.track_eval and LEGM.track_level).  The rule is
+# emba_amd/csrc/track_rule.h's: given the same level-0 pm the level sums are the same integers; given the same sums and the same level pm the classes are
+# the same and the residuals have the same bits.
+TRACK_ANCHOR, TRACK_TRACKED, TRACK_LOST = 1, 2, 3      # EMBA_TRACK_*
+TRACK_STATUS_NAMES = {1: "anchor", 2: "tracked", 3: "lost"}
+TRACK_MAX_LEVEL = 7
+
+
+def track_level_shape(pano_w, pano_h, level):
+    """track_level (track_rule.h): (W_l, H_l, 2^-level) of level 0 ... 7; ValueError where W or H is not divisible by 2^level or fewer than 2 rows are left."""
+    W, H, l = int(pano_w), int(pano_h), int(level)
+    if not 0 <= l <= TRACK_MAX_LEVEL:
+        raise ValueError(f"level = {l}: levels are 0 ... {TRACK_MAX_LEVEL}")
+    if W % (1 << l) or H % (1 << l):
+        raise ValueError(f"level = {l}: the panorama {W} x {H} is not divisible by {1 << l}")
+    if (H >> l) < 2:
+        raise ValueError(f"level = {l} leaves {H >> l} rows: a sample needs two")
+    return W >> l, H >> l, 1.0 / (1 << l)
+
+
+def track_level_pm(pm, level):
+    """pm_l = pm * 2^-level (exact)."""
+    return np.asarray(pm, dtype=np.float64) * (1.0 / (1 << int(level)))
+
+
+def track_vote_levels(levels):
+    """The planes a tracked frame votes into: the schedule's levels in their order, each once, then level 0 where the schedule does not name it."""
+    out = []
+    for l in levels:
+        if int(l) not in out:
+            out.append(int(l))
+    return out if 0 in out else out + [0]
+
+
+def track_votes(frames_u8, pm, status, pano_w, pano_h, levels, skip_zero=False):
+    """Every level's integer sums from the level-0 pm [F, S, 2] the frames voted with: the frames whose status is TRACK_ANCHOR or TRACK_TRACKED vote through
+    mosaic_votes at pm * 2^-l on (W_l, H_l), for every level of track_vote_levels(levels).  A dict of planes {level: (sum_w, sum_v)}, dropped (over every
+    plane) and skipped."""
+    status = np.asarray(status).reshape(-1)
+    F = status.size
+    votes = (status == TRACK_ANCHOR) | (status == TRACK_TRACKED)
+    fr = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)[votes]
+    pm = np.asarray(pm, dtype=np.float64).reshape(F, -1, 2)[votes]
+    planes, dropped, skipped = {}, 0, 0
+    for l in track_vote_levels(levels):
+        Wl, Hl, _ = track_level_shape(pano_w, pano_h, l)
+        sw, sv, d, skipped = mosaic_votes(fr, track_level_pm(pm, l).reshape(-1, 2), Wl, Hl, skip_zero)
+        planes[l] = (sw, sv)
+        dropped += d
+    return dict(planes=planes, dropped=dropped, skipped=skipped)
+
+
+def track_terms(frame_u8, pm_l, lut, q, sum_w, sum_v, min_weight=256, skip_zero=False, huber_k=0.0):
+    """The terms of one frame's pixels against a level's two sums [H_l, W_l] (track_pixel, track_rule.h) from the level's pm [S, 2]: the plane is
+    mosaic_mean of the sums, a pixel is masked when any of its four cells has sum_w < min_weight, the frame's byte is in the plane's units (I = v), and
+    J23 is numpy's own on the level's grid.  A dict as align_terms'."""
+    mean, covered = mosaic_mean(sum_w, sum_v, min_weight, 0.0)
+    return align_terms(frame_u8, pm_l, lut, q, mean, covered, 0.0, 255.0, skip_zero, huber_k)
+
+
+def track_predict(q_a, t_a, q_b, t_b, t, predict=True):
+    """track_predict (track_rule.h): the start of the frame at time t from the last two tracked frames a < b — normalise(exp(omega (t - t_b) / (t_b - t_a))
+    (x) q_b), omega = log(q_b (x) q_a^-1); q_b where predict is off or q_a is None."""
+    q_b = np.asarray(q_b, dtype=np.float64)
+    if not predict or q_a is None:
+        return q_b.copy()
+    omega = so3.log(so3.mul(q_b, so3.inverse(np.asarray(q_a, dtype=np.float64))))
+    u = float(int(t) - int(t_b)) / float(int(t_b) - int(t_a))
+    return so3.mul(so3.exp(omega * u), q_b)
+
+
+def track_frames(frames_u8, frame_t_ns, lut, pano_w, pano_h, q0=(0.0, 0.0, 0.0, 1.0), levels=(0,), batch=1, predict=True, skip_zero=False, min_weight=256,
+                 min_overlap=0.5, **settings):
+    """The whole tracker of emba_frames_track in numpy, with numpy's own pm: frame 0 is voted at normalise(q0); behind it the frames [f0, f0 + batch) are each
+    aligned from their own prediction against the level sums of the frames tracked before f0, level by level through `levels` with align_frames' loop, and
+    the tracked ones among them are then voted at every level.  A dict of q [F, 4], status [F], iters [F, len(levels)], cost, overlap [F], counts [F, 4],
+    pm [F, S, 2] (the level-0 pm voted with, NaN for a lost frame) and planes {level: (sum_w, sum_v)}.  One difference from the device: batches are cut by
+    `batch` alone, not at the device's chunk edges (65 535 frames or 32 MiB of bytes, track_batch_frames of track_rule.h), which calls of this form's size
+    do not reach."""
+    s = align_settings(**settings)
+    W, H = int(pano_w), int(pano_h)
+    ts = np.asarray(frame_t_ns, dtype=np.int64).reshape(-1)
+    F = ts.size
+    if (np.diff(ts) <= 0).any():
+        raise ValueError("the frame times must be strictly increasing")
+    if int(batch) < 1 or not 0.0 <= float(min_overlap) <= 1.0 or int(min_weight) < 1 or not 1 <= len(levels) <= 8:
+        raise ValueError("batch >= 1, 0 <= min_overlap <= 1, min_weight >= 1, 1 ... 8 levels")
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)
+    S = frames.shape[1]
+    shapes = {l: track_level_shape(W, H, l) for l in track_vote_levels(levels)}
+    planes = {l: (np.zeros((Hl, Wl), np.uint64), np.zeros((Hl, Wl), np.uint64)) for l, (Wl, Hl, _) in shapes.items()}
+    out = dict(q=np.zeros((F, 4)), status=np.zeros(F, np.int32), iters=np.zeros((F, len(levels)), np.int32), cost=np.zeros(F), overlap=np.zeros(F),
+               counts=np.zeros((F, 4), np.int64), pm=np.full((F, S, 2), np.nan), planes=planes)
+
+    def vote(f):
+        pm = align_warp(lut, out["q"][f], W, H)[1]
+        out["pm"][f] = pm
+        for l, (Wl, Hl, scale) in shapes.items():
+            sw, sv, _, _ = mosaic_votes(frames[f], pm * scale, Wl, Hl, skip_zero)
+            planes[l][0][...] += sw
+            planes[l][1][...] += sv
+
+    def evaluate(f, q, l):
+        Wl, Hl, scale = shapes[l]
+        return align_sums(track_terms(frames[f], align_warp(lut, q, W, H)[1] * scale, lut, q, planes[l][0], planes[l][1], min_weight, skip_zero, s["huber_k"]))
+
+    def align_level(f, q, l):      # align_frames' loop for one frame against one level: (q, sums, counts, status, iters)
+        sums, counts = evaluate(f, q, l)
+        lam, iters = float(s["lambda0"]), 0
+        while True:
+            delta = align_step(sums[:6], sums[6:9], lam) if counts[0] >= s["min_pixels"] else None
+            if delta is None:
+                return q, sums, counts, ALIGN_DEGENERATE, iters
+            if iters >= s["max_iters"]:
+                return q, sums, counts, ALIGN_ITERATIONS, iters
+            trial = so3.mul(so3.exp(delta), q)
+            tsums, tcounts = evaluate(f, trial, l)
+            iters += 1
+            if tcounts[0] >= s["min_pixels"] and tsums[9] / tcounts[0] < sums[9] / counts[0]:
+                q, sums, counts = trial, tsums, tcounts
+                lam = max(lam / s["lambda_down"], s["lambda_min"])
+                if np.linalg.norm(delta) < s["tol_rot"]:
+                    return q, sums, counts, ALIGN_CONVERGED, iters
+            else:
+                lam *= s["lambda_up"]
+                if lam > s["lambda_max"]:
+                    return q, sums, counts, ALIGN_STALLED, iters
+
+    if not F:
+        return out
+    out["q"][0], out["status"][0] = so3.normalize(np.asarray(q0, dtype=np.float64)), TRACK_ANCHOR
+    vote(0)
+    tracked = [0]
+    f0 = 1
+    while f0 < F:
+        nf = min(int(batch), F - f0)
+        b = tracked[-1]
+        a = tracked[-2] if len(tracked) > 1 else None
+        for f in range(f0, f0 + nf):
+            pred = track_predict(None if a is None else out["q"][a], None if a is None else ts[a], out["q"][b], ts[b], ts[f], predict)
+            q = pred
+            for k, l in enumerate(levels):
+                q, sums, counts, status, out["iters"][f, k] = align_level(f, q, int(l))
+            denom = S - counts[3]
+            overlap = counts[0] / denom if denom > 0 else 0.0
+            ok = status != ALIGN_DEGENERATE and overlap >= float(min_overlap)
+            out["q"][f], out["status"][f] = (q if ok else pred), (TRACK_TRACKED if ok else TRACK_LOST)
+            out["cost"][f], out["overlap"][f], out["counts"][f] = sums[9], overlap, counts
+        for f in range(f0, f0 + nf):
+            if out["status"][f] == TRACK_TRACKED:
+                vote(f)
+                tracked.append(f)
+        f0 += nf
+    return out
+
+
 def rotation_angle_between(qa, qb):
     """The angle (rad) of the rotation from qa to qb, quaternions xyzw [..., 4]."""
     qa, qb = np.asarray(qa, dtype=np.float64).reshape(-1, 4), np.asarray(qb, dtype=np.float64).reshape(-1, 4)

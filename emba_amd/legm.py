@@ -434,6 +434,63 @@ class LEGM:
                                               _p(sums, _dp), _p(counts, u64p), _p(status, _i32p), _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p)))
         return dict(q=q_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64))
 
+    def track_frames(self, frames, frame_t_ns, q0=(0.0, 0.0, 0.0, 1.0), levels=(0,), batch=1, predict=True, skip_zero=False, min_weight=256, min_overlap=0.5,
+                     want_pm=False, **settings):
+        """Poses from the frames alone (emba_frames_track; the rule: include/emba_hip.h): frame 0 is put at q0, every later frame of frames
+        [F, sensor_h, sensor_w] (taken at frame_t_ns [F], strictly increasing) is aligned to the mosaic of the frames tracked before it — level by level
+        through `levels`, from a start predicted from the last two tracked frames — and then voted into it.  `batch` frames are aligned at once; settings:
+        the members of io.ALIGN_DEFAULTS.  The mosaic the call leaves is the context's (mosaic, mosaic_map).  A dict of q [F, 4], status int32 [F]
+        (io.TRACK_ANCHOR / TRACKED / LOST), iters [F, len(levels)], cost [F], counts [F, 4], overlap [F], tracked, lost, dropped, skipped and pm
+        [F, S, 2] (None without want_pm; NaN for a lost frame).  io.track_frames is the same tracker in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        levels = [int(l) for l in levels]
+        if not 1 <= len(levels) <= 8:
+            raise ValueError("a schedule names 1 ... 8 levels")
+        q0 = np.ascontiguousarray(q0, dtype=np.float64).reshape(4)
+        cs = _lib.EmbaTrackSettings(len(levels), (C.c_int32 * 8)(*levels), int(batch), 1 if predict else 0, 1 if skip_zero else 0, int(min_weight), float(min_overlap),
+                                    _lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                                           float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]), float(s["huber_k"])))
+        q, status, iters = np.zeros((F, 4)), np.zeros(F, np.int32), np.zeros((F, len(levels)), np.int32)
+        cost, counts, overlap, stats = np.zeros(F), np.zeros((F, 4), np.uint64), np.zeros(F), np.zeros(4, np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_track(self._ctx, _p(frames, _u8p), _p(ts, _i64p), F, _p(q0, _dp), C.addressof(cs), _p(q, _dp), _p(status, _i32p),
+                                              _p(iters, _i32p), _p(cost, _dp), _p(counts, u64p), _p(overlap, _dp), _p(stats, u64p), _p(pm, _dp)))
+        return dict(q=q, status=status, iters=iters, cost=cost, counts=counts.astype(np.int64), overlap=overlap, tracked=int(stats[0]), lost=int(stats[1]),
+                    dropped=int(stats[2]), skipped=int(stats[3]), pm=pm)
+
+    def track_eval(self, frames, q_xyzw, level=0, min_weight=256, skip_zero=False, huber_k=0.0, want_pm=False, want_resid=False):
+        """One evaluation of the frames [F, sensor_h, sensor_w] at the rotations q_xyzw [F, 4] against the two integer sums of `level` as the last
+        track_frames left them (emba_track_eval).  A dict as align_frames_eval's; pm is the level's — io.track_terms and io.align_sums given the same pm."""
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+        F, S = q.shape[0], self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        sums, counts = np.zeros((F, 10)), np.zeros((F, 4), np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        resid = np.empty((F, S)) if want_resid else None
+        self._check(self._L.emba_track_eval(self._ctx, _p(frames, _u8p), F, _p(q, _dp), int(level), int(min_weight), 1 if skip_zero else 0, float(huber_k),
+                                            _p(sums, _dp), _p(counts, C.POINTER(C.c_uint64)), _p(pm, _dp), _p(resid, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), pm=pm, resid=resid)
+
+    def track_level(self, level):
+        """The two integer sums of a level as the last track_frames left them (emba_track_level_get): (sum_w, sum_v) uint64 [pano_h >> level, pano_w >> level]."""
+        level = int(level)
+        if not 0 <= level <= 7:
+            raise ValueError("levels are 0 ... 7")
+        shape = (self.H >> level, self.W >> level)
+        sum_w, sum_v = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_track_level_get(self._ctx, level, _p(sum_w, u64p), _p(sum_v, u64p)))
+        return sum_w, sum_v
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

@@ -20,6 +20,7 @@
   python examples/run_ba.py --demo out2/ --frames out1/views --init-map frames --frames-log 0 --frames-skip-zero --frames-lo LO --frames-hi HI
                                                   # frames to panorama: the initial map is the mosaic of intensity frames along the raw trajectory (DESIGN.md
                                                   # section 19); here the frames another run wrote with --views-hz, whose tone LO HI is in out1/views/tone.txt
+  python examples/run_ba.py --demo out4/ --frames out1/views --init-poses frames --init-map frames --track-levels 3,2,1 --window-size 0.5 --frames-log 0 --frames-skip-zero --frames-lo LO --frames-hi HI   # poses from the frames alone
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... # the window's events time-sharded
                                                   # over the GPUs of one node (RCCL); every rank runs the same LM loop, rank 0 writes
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_ba.py ... --window-size 0.3 --window-stride 0.1
@@ -110,6 +111,28 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
         log(f"refine-frames round {rnd}: {len(ts)} frames aligned to their mosaic ({names}); mean cost {before.mean():.4g} -> {after.mean():.4g}, "
             f"mean turn {moved.mean():.3e} rad, up to {int(r['iters'].max())} trials")
         rows = [(tn, q, int(st), b, a_) for tn, q, st, b, a_ in zip(ts, r["q"], r["status"], before, after)]
+    return traj, t_raw, q_raw, rows
+
+
+def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
+    """--init-poses frames: poses from the frames alone.  The frames are tracked against their own growing mosaic on the device; the
+    tracked frames' (t, q), sampled on a 5 ms grid over the span and held at both ends where the frames do not reach them, are the raw poses, and
+    io.fit_ctrl_poses of them the trajectory.
+    Lost frames are left out.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the rotation, the status, the overlap and the cost."""
+    r = legm.track_frames(frames, t_ns, q0=a.track_q0, levels=a.track_levels, batch=a.track_batch, predict=bool(a.track_predict), skip_zero=a.frames_skip_zero,
+                          min_overlap=a.track_min_overlap, huber_k=a.frames_huber)
+    ok = r["status"] != eio.TRACK_LOST
+    tf, qf = t_ns[ok] * 1e-9, r["q"][ok]
+    # the raw poses a sliding-window run reads: the tracked rotations on a 5 ms grid over the trajectory's span (io.pose_at: interpolated between tracked
+    # frames, held before the first and behind the last), so that there are more raw poses than control poses however few frames there are
+    t_raw_ns = traj.t0_ns + 5_000_000 * np.arange((traj.dt_ns * (traj.size() - 1)) // 5_000_000, dtype=np.int64)
+    t_raw = t_raw_ns * 1e-9
+    q_raw = np.array([eio.pose_at(tf, qf, tq) for tq in t_raw])
+    traj = LinearTrajectory(eio.fit_ctrl_poses(t_raw, q_raw, traj.t0_ns * 1e-9, traj.dt_ns * 1e-9, traj.size()), traj.t0_ns, traj.dt_ns)
+    log(f"init-poses frames: {r['tracked']} of {len(t_ns)} frames tracked through levels {a.track_levels} (batch {a.track_batch}), {r['lost']} lost; "
+        f"overlap >= {r['overlap'][1:].min() if len(t_ns) > 1 else 0.0:.3f}, up to {int(r['iters'].max()) if r['iters'].size else 0} trials per level, "
+        f"{r['dropped']} votes dropped, {r['skipped']} pixels skipped")
+    rows = [(int(tn), q, int(st), float(ov), float(c)) for tn, q, st, ov, c in zip(t_ns, r["q"], r["status"], r["overlap"], r["cost"])]
     return traj, t_raw, q_raw, rows
 
 
@@ -221,9 +244,16 @@ def main():
                     "the current raw trajectory, aligning every frame's rotation to that mosaic on the device and fitting the raw trajectory to the aligned "
                     "rotations (DESIGN.md section 20); writes <out>/frames_aligned.txt")
     ap.add_argument("--frames-huber", type=float, default=0.0, metavar="K", help="with --refine-frames: the Huber threshold of the alignment, in byte units (0: quadratic)")
-    ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity"], help="identity: no --poses is needed — every raw pose is the identity "
+    ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity", "frames"], help="frames: no --poses is needed — the intensity frames of "
+                    "--frames are tracked against their own growing mosaic on the device from --track-q0 on, and the tracked frames' rotations are the raw poses "
+                    "(with --window-size; DESIGN.md section 21; writes <out>/frames_tracked.txt).  identity: no --poses is needed — every raw pose is the identity "
                     "(what a run without a front end always has; with --window-size).  events: no --poses is needed — the angular velocity of every slice of events is "
                     "estimated from the events alone by contrast maximisation and integrated (with --window-size; --t-beg / --t-end default to the recording's span)")
+    ap.add_argument("--track-levels", default="2,1,0", help="--init-poses frames: the schedule of levels, coarse to fine, comma-separated (level l has cells 2^l pixels wide).  A level whose cells are finer than the sensor's pixels stays under-covered and loses every frame: the demo's 128 x 96 sensor on 512 x 1024 needs 3,2,1")
+    ap.add_argument("--track-batch", type=int, default=1, metavar="B", help="--init-poses frames: frames aligned at once against the mosaic of the frames before them")
+    ap.add_argument("--track-predict", type=int, default=1, choices=[0, 1], help="--init-poses frames: start a frame from the last two tracked frames' angular velocity")
+    ap.add_argument("--track-min-overlap", type=float, default=0.3, metavar="X", help="--init-poses frames: a frame whose used pixels fall below this share is lost")
+    ap.add_argument("--track-q0", default="0,0,0,1", metavar="x,y,z,w", help="--init-poses frames: the rotation of the first frame")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
     ap.add_argument("--record-contrast", action="store_true", help="print, per window, the contrast J = sum I^2 of the panorama of the window's warped events at its "
@@ -264,12 +294,12 @@ def main():
         ap.error("--map-dir is required unless --init-map events or frames is given")
     if a.init_map == "frames" and not a.frames:
         ap.error("--init-map frames needs --frames DIR")
-    if a.init_map == "frames" and a.init_poses != "given":
+    if a.init_map == "frames" and a.init_poses not in ("given", "frames"):
         ap.error("--init-map frames stitches the frames along the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity, "
                  "whose trajectory at that point carries the timing only")
     if a.refine_frames < 0 or (a.refine_frames and not a.frames):
         ap.error("--refine-frames N (N >= 0) aligns the frames of --frames DIR")
-    if a.refine_frames and a.init_poses != "given":
+    if a.refine_frames and a.init_poses not in ("given", "frames"):
         ap.error("--refine-frames aligns the frames from the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity")
     if not (np.isfinite(a.frames_huber) and a.frames_huber >= 0.0):
         ap.error("--frames-huber is finite and not negative")
@@ -277,6 +307,16 @@ def main():
         ap.error("--frames-lo, --frames-hi and --frames-eps are finite, and --frames-hi is above --frames-lo")
     if not a.demo and a.init_poses == "given" and not a.poses:
         ap.error("--poses is required unless --init-poses events or identity is given")
+    if a.init_poses == "frames":
+        if not a.frames or not a.window_size:
+            ap.error("--init-poses frames tracks the frames of --frames DIR and needs --window-size (a sliding-window run makes its control poses from the raw ones)")
+        try:
+            a.track_levels = [int(v) for v in a.track_levels.split(",")]
+            a.track_q0 = [float(v) for v in a.track_q0.split(",")]
+        except ValueError:
+            ap.error("--track-levels is a list of integers, --track-q0 four numbers x,y,z,w")
+        if not 1 <= len(a.track_levels) <= 8 or len(a.track_q0) != 4 or a.track_batch < 1 or not 0.0 <= a.track_min_overlap <= 1.0:
+            ap.error("--track-levels names 1 ... 8 levels, --track-q0 has four numbers, --track-batch >= 1, 0 <= --track-min-overlap <= 1")
     if a.init_poses != "given" and not a.window_size:
         ap.error("--init-poses events / identity needs --window-size (a sliding-window run makes its control poses from the raw ones)")
     no_front_end = a.init_poses != "given"
@@ -373,6 +413,15 @@ def main():
         print(f"{events.size()} events, {traj.size()} control poses, panorama {H}x{W}" + (f", {world} rank(s) through the sharded host" if legm is not model else ""))
     if a.frames:
         frames, frames_t_ns = load_frames(a.frames, sw, sh)
+    tracked_mosaic = False
+    if a.init_poses == "frames":      # poses from the frames alone: the tracked frames' rotations are the raw poses, the tracker's mosaic stays in the context
+        traj, t, qs, rows = track_frames(legm, frames, frames_t_ns, traj, t_beg, t_end, a, log=print if rank == 0 else (lambda *_: None))
+        tracked_mosaic = True
+        if rank == 0:
+            with open(os.path.join(a.out, "frames_tracked.txt"), "w") as fh:
+                fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost\n")
+                for tn, q, st, ov, cost in rows:
+                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {ov:.9g} {cost:.9g}\n")
     if a.refine_frames:      # poses from frames: the raw trajectory is refitted to the frames' aligned rotations before anything else reads it
         traj, t, qs, rows = refine_frames(legm, frames, frames_t_ns, traj, np.asarray(t, dtype=np.float64), np.asarray(qs, dtype=np.float64), a.refine_frames,
                                           a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None))
@@ -382,7 +431,10 @@ def main():
                 for tn, q, st, b, a_ in rows:
                     fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {b:.9g} {a_:.9g}\n")
     if a.init_map == "frames":      # the mosaic of the frames along the raw trajectory, on the device; its gradient map is handed on as the given map
-        used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero)
+        if tracked_mosaic and not a.refine_frames:      # the mosaic the tracker left: no second stitch
+            used = int(sum(1 for row in rows if row[2] != eio.TRACK_LOST))
+        else:
+            used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero)
         fm = legm.mosaic_map(lo=a.frames_lo, hi=a.frames_hi, eps=a.frames_eps, take_log=bool(a.frames_log))
         Gx, Gy = fm["Gx"], fm["Gy"]
         if rank == 0:

@@ -677,6 +677,68 @@ emba_status emba_frames_align(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw
                               double* q_out /* [F, 4] */, double* sums_out /* [F, 10] */, uint64_t* counts_out /* [F, 4] */, int32_t* status_out /* [F] */,
                               int32_t* iters_out /* [F] */, double* cost0_out /* [F] */, uint64_t* n0_out /* [F] */);
 
+/* ---- Intensity frames tracked against their own growing mosaic: poses from the frames alone.  The alignment above needs a finished plane
+ * and a start for every frame; here there is no trajectory at all.  Frame 0 is put at q0, every later frame is aligned to the mosaic of the frames tracked
+ * before it and then voted into it.  The rule lives in emba_amd/csrc/track_rule.h; emba_amd.io.track_level_pm / track_votes / track_terms / track_predict /
+ * track_frames are the same rule in numpy.
+ *
+ * Frames f = 0 ... F - 1 of bytes, taken at frame_t_ns (strictly increasing).
+ *   levels            level l (0 ... 7) is the panorama with cells 2^l pixels wide: W_l = W >> l, H_l = H >> l, pm_l = pm * 2^-l, J23_l = J23 * 2^-l (exact).
+ *                     Per level the context holds two uint64 planes sum_w_l, sum_v_l [H_l, W_l]; level 0's are the mosaic's sums themselves, so that
+ *                     emba_mosaic_get / emba_mosaic_map work on the tracked mosaic as they stand.  settings.levels[0 ... n_levels) is the schedule, coarse to
+ *                     fine as the caller orders it.
+ *   vote              a tracked frame (and the anchor) is warped once and votes at every level of the schedule, and at level 0 whether the schedule names
+ *                     it or not: emba_mosaic_frames' vote (four cells, 256 units, columns wrapped, rows outside dropped and counted, w into sum_w_l and w * v
+ *                     into sum_v_l by integer atomics) on the grid (W_l, H_l) at pm_l.  With skip_zero a byte of 0 casts no vote and is counted.  Integer
+ *                     sums: numpy gives the same sums from the same pm.
+ *   sample            P_l[c] = sum_v_l[c] / sum_w_l[c], one IEEE division, formed for the four cells of emba_render_views' cell of pm_l on (W_l, H_l); no
+ *                     mean plane is written.  A pixel is masked when any of its four cells has sum_w_l < min_weight (the same min_weight at every level).
+ *                     Everything else is emba_frames_align's with lo = 0, hi = 255 (I = v): outside / masked / skipped in this precedence, the value and
+ *                     the gradient, the weight, g = gx J23_l[0,:] + gy J23_l[1,:], the ten sums, reduced in a fixed order.
+ *   prediction        a < b the last two tracked frames (the anchor counts).  predict != 0 and both there: the start of frame f is
+ *                     normalise(exp(omega (t_f - t_b) / (t_b - t_a)) (x) q_b), omega = log(q_b (x) q_a^-1).  Otherwise q_b.
+ *   batches           frame 0 is the anchor: voted at normalise(q0), never aligned.  Behind it the frames [f0, f0 + batch) are aligned at once against the
+ *                     mosaic of the frames tracked before f0, each from its own prediction, and the tracked ones among them are then voted in one launch.
+ *                     batch = 1 is pure frame-to-mosaic tracking.  A batch ends at the end of its chunk (below).
+ *   per frame         for each level of the schedule in order emba_frames_align's loop under settings.align, started where the previous level ended; a
+ *                     level that ends degenerate leaves q as it was.  Behind the last level overlap = used / (S - skipped) at q_out (0 where every pixel
+ *                     was skipped).  The frame is EMBA_TRACK_TRACKED when the last level did not end degenerate and overlap >= min_overlap; otherwise
+ *                     EMBA_TRACK_LOST: q_out is its prediction, it casts no vote, and later predictions skip it.
+ *
+ * emba_frames_track zeroes the mosaic and every level plane first (tracking against a mosaic that is there is not built).  Outputs, each may be NULL: q_out
+ * [F, 4]; status_out [F]; iters_out [F, n_levels] (trials evaluated per level); cost_out [F] and counts_out [F, 4] (used, outside, masked, skipped) of the
+ * last level at the rotation it ended at; overlap_out [F]; stats_out [4]: tracked frames (the anchor among them), lost frames, dropped votes (over every
+ * plane), skipped pixels (of the voted frames); pm_out [F, sensor_h * sensor_w, 2]: the level-0 pm each voted frame voted with, NaN for a lost frame (the seam
+ * the tests pin; asking for it makes every batch wait for its download).  The anchor reports 0 iterations, cost 0, counts 0 and overlap 0.
+ * emba_track_eval: one evaluation of F frames at q_xyzw against the planes of `level` as they stand; outputs as emba_frames_align_eval's, pm_out the level's pm.
+ * emba_track_level_get: the two planes of a level [H_l, W_l], each may be NULL.
+ *
+ * The frames go up in chunks of at most 65 535 frames and 32 MiB; a chunk boundary is a batch boundary.  Rotations and statuses stay on the device between
+ * batches.  F = 0 zeroes the planes and launches nothing else.  Refusals are decided before anything is zeroed and leave every output, the mosaic and the
+ * level planes untouched.  EMBA_ERR_INVALID_ARG: frames or frame_t_ns NULL with F > 0; q0 or settings NULL; F >= 2^31; n_levels not 1 ... 8; a level not
+ * 0 ... 7, W or H not divisible by 2^level, H_l < 2; batch < 1; min_overlap not in [0, 1]; min_weight < 1; frame times not strictly increasing; q0 not finite
+ * or of zero norm; settings.align refused as emba_frames_align refuses it (huber_k a NaN among it); F * S >= 2^36 votes.  emba_track_eval: frames or q_xyzw
+ * NULL with F > 0, F >= 2^31, the level as above, min_weight < 1, huber_k a NaN, a q not finite or of zero norm.  EMBA_ERR_STATE: emba_track_eval or
+ * emba_track_level_get at a level that the last successful emba_frames_track did not vote into.  The registered window, its order, the last evaluation, the
+ * resident sequence and the resident map are left as they are.  While emba_enable_kernel_timing is on, timer slot 7 brackets the first evaluation kernel. */
+#define EMBA_TRACK_ANCHOR 1
+#define EMBA_TRACK_TRACKED 2
+#define EMBA_TRACK_LOST 3
+typedef struct {
+    int32_t n_levels, levels[8], batch, predict, skip_zero;
+    uint64_t min_weight;
+    double min_overlap;
+    emba_align_settings align;
+} emba_track_settings;
+emba_status emba_frames_track(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, const int64_t* frame_t_ns /* [F] */, size_t F, const double* q0_xyzw /* [4] */,
+                              const emba_track_settings* settings, double* q_out /* [F, 4] */, int32_t* status_out /* [F] */, int32_t* iters_out /* [F, n_levels] */,
+                              double* cost_out /* [F] */, uint64_t* counts_out /* [F, 4] */, double* overlap_out /* [F] */, uint64_t* stats_out /* [4] */,
+                              double* pm_out /* [F, sh*sw, 2] */);
+emba_status emba_track_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */, int32_t level, uint64_t min_weight,
+                            int32_t skip_zero, double huber_k, double* sums_out /* [F, 10] */, uint64_t* counts_out /* [F, 4] */, double* pm_out /* [F, sh*sw, 2] */,
+                            double* resid_out /* [F, sh*sw] */);
+emba_status emba_track_level_get(emba_ctx* ctx, int32_t level, uint64_t* sum_w_out /* [H_l, W_l] */, uint64_t* sum_v_out /* [H_l, W_l] */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
