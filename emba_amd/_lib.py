@@ -39,6 +39,10 @@ class EmbaTrackSettings(C.Structure):
                 ("min_weight", C.c_uint64), ("min_overlap", C.c_double), ("align", EmbaAlignSettings)]
 
 
+class EmbaExposureSettings(C.Structure):
+    _fields_ = [("align", EmbaAlignSettings), ("gain_min", C.c_double), ("gain_max", C.c_double)]
+
+
 # symbol -> (restype, argtypes); exactly the entry points include/emba_hip.h declares
 SIGNATURES = {
     "emba_abi_version": (C.c_int, []),
@@ -148,6 +152,12 @@ SIGNATURES = {
     "emba_frames_track": (C.c_int, [C.c_void_p, _u8p, _i64p, C.c_size_t, _dp, C.c_void_p, _dp, _i32p, _i32p, _dp, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint64), _dp]),
     "emba_track_eval": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _dp, C.c_int32, C.c_uint64, C.c_int32, C.c_double, _dp, C.POINTER(C.c_uint64), _dp, _dp]),
     "emba_track_level_get": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "emba_frames_exposure_eval": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _dp, _dp, _dp, _dp, _u8p, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double,
+                                            C.c_int32, C.c_double, _dp, C.POINTER(C.c_uint64), _dp, _dp]),
+    "emba_frames_exposure_align": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _dp, _dp, _dp, C.c_int32, _dp, _u8p, C.c_int32, C.c_uint64, C.c_double, C.c_double,
+                                             C.c_double, C.c_int32, C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), _i32p, _i32p, _dp, C.POINTER(C.c_uint64)]),
+    "emba_mosaic_frames_exposure": (C.c_int, [C.c_void_p, _u8p, _i64p, C.c_size_t, _dp, _dp, _dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _dp]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

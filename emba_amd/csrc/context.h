@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, align_host.h, track_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, align_host.h, track_host.h, exposure_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -275,6 +275,17 @@ struct TrackBuffers {
     DevBuf q, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
 };
 
+// Per-frame exposure (exposure_host.h); all of it scratch of one call.  One chunk of frames as bytes, as pm and as residuals; partial: the evaluation kernel's
+// sums per (frame, workgroup); q_trial, gain_trial, bias_trial, esums, ecounts: where every frame of the chunk is evaluated and what the evaluation gave
+// there; q ... n0: the members of exposure_rule.h's ExposureFrame, one array each, with the first evaluation's cost and n; running: the frames a step left
+// running.  vote_gain, vote_bias: all F gains and biases of emba_mosaic_frames_exposure.  (The plane and its mask are AlignBuffers'; the pose table, the
+// bytes and the counters of the vote are MosaicBuffers'.)
+struct ExposureBuffers {
+    DevBuf frames, pm, resid, partial, q_trial, gain_trial, bias_trial, esums, ecounts;
+    DevBuf q, gain, bias, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
+    DevBuf vote_gain, vote_bias;
+};
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -474,6 +485,7 @@ struct emba_ctx {
     MosaicBuffers mosaic;         // the mosaic of intensity frames: the resident sums and the scratch of a call (mosaic_host.h)
     AlignBuffers align;           // intensity frames aligned to a panorama plane: the scratch of a call (align_host.h)
     TrackBuffers track;           // intensity frames tracked against their own growing mosaic: the level planes and the scratch of a call (track_host.h)
+    ExposureBuffers exposure;     // per-frame exposure: the scratch of a call (exposure_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -194,6 +194,7 @@ void emba_destroy(emba_ctx* c)
 #include "sim_host.h"        // the event simulator: a recording from a panorama plane and a trajectory, and its way into the resident sequence
 #include "align_host.h"      // poses from frames: each intensity frame's rotation aligned to a panorama plane (the mosaic's mean, or a caller's)
 #include "track_host.h"      // poses from the frames alone: each frame aligned to the growing mosaic of the frames before it, then voted into it
+#include "exposure_host.h"   // per-frame exposure: a gain and a bias estimated with each frame's rotation, and applied when the frames are stitched
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

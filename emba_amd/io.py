@@ -1283,6 +1283,220 @@ def align_frames(frames_u8, q_xyzw, lut, plane, valid=None, lo=0.0, hi=255.0, sk
     return out
 
 
+# ---- per-frame exposure (numpy forms of emba_frames_exposure_eval, emba_frames_exposure_align and emba_mosaic_frames_exposure, include/emba_hip.h; the
+# device forms are LEGM.exposure_eval, LEGM.align_frames_exposure and LEGM.mosaic_frames_exposure).  The rule is
+# emba_amd/csrc/exposure_rule.h's: frame f carries (q_f, a_f, b_f), its compensated intensity is a_f * I0 + b_f.  Given the same pm, the classes are the same
+# and the residuals have the same bits; given the same pm, io.mosaic_votes of exposure_bytes gives the same integer sums.
+EXPOSURE_GAIN, EXPOSURE_BIAS = 1, 2                                  # EMBA_EXPOSURE_*: the bits of `estimate`
+EXPOSURE_SUMS, EXPOSURE_RHS, EXPOSURE_COST = 21, 15, 20
+EXPOSURE_SHARED = (0, 1, 2, 5, 6, 9, 15, 16, 17, 20)                 # where align_sums' ten lie among the 21 (exposure_shared_index)
+EXPOSURE_COLLINEAR = 1e-9                                            # kExposureCollinear
+EXPOSURE_BOUNDS = dict(gain_min=0.25, gain_max=4.0)
+
+
+def exposure_h_index(i, j):
+    """The place of H[i][j], i <= j, among the 15 entries of the upper triangle in row-major order over (delta0, delta1, delta2, a, b)."""
+    return i * 5 - i * (i - 1) // 2 + (j - i)
+
+
+def exposure_bounds(gain_min=None, gain_max=None):
+    """(gain_min, gain_max), EXPOSURE_BOUNDS where None; the refusal of emba_frames_exposure_align's bounds as ValueError."""
+    lo = float(EXPOSURE_BOUNDS["gain_min"] if gain_min is None else gain_min)
+    hi = float(EXPOSURE_BOUNDS["gain_max"] if gain_max is None else gain_max)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= 1.0 <= hi):
+        raise ValueError(f"gain_min = {lo}, gain_max = {hi}: finite, 0 < gain_min <= 1 <= gain_max")
+    return lo, hi
+
+
+def exposure_check(gain, bias, F):
+    """gain, bias as float64 [F]; the refusals of the entry points as ValueError: not finite, a gain <= 0."""
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64), (F,)))
+    b = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (F,)))
+    if not (np.isfinite(a).all() and np.isfinite(b).all() and (a > 0.0).all()):
+        raise ValueError("every gain is finite and positive, every bias finite")
+    return a, b
+
+
+def exposure_terms(frame_u8, pm, lut, q, plane, gain=1.0, bias=0.0, valid=None, lo=0.0, hi=255.0, skip_zero=False, huber_k=0.0):
+    """The terms of one frame's pixels (exposure_pixel, exposure_rule.h) from a given pm [S, 2] and numpy's own J23 of q: align_terms' dict — cls in
+    align_terms' precedence (skipped tests the raw byte), r = val - (gain * I0 + bias) with I0 = lo + v (hi - lo) / 255 (multiply, then add), w, rho, g —
+    and I0 [S] (0 where the pixel is not used).  The Jacobian row of r is (g, -I0, -1)."""
+    P = np.asarray(plane, dtype=np.float64)
+    H, W = P.shape
+    v = np.asarray(frame_u8, dtype=np.uint8).reshape(-1)
+    pm = np.asarray(pm, dtype=np.float64).reshape(-1, 2)
+    if pm.shape[0] != v.size:
+        raise ValueError(f"pm has {pm.shape[0]} rows, the frame has {v.size} pixels")
+    val, gx, gy, outside = align_sample(P, pm)
+    cls = np.full(v.size, ALIGN_USED, dtype=np.int64)
+    if skip_zero:
+        cls[v == 0] = ALIGN_SKIPPED
+    if valid is not None:
+        ok = np.asarray(valid).astype(bool)
+        _, r0, r1, c0, c1, _, _ = _align_cell(P.shape, pm)
+        cls[~(ok[r0, c0] & ok[r0, c1] & ok[r1, c0] & ok[r1, c1])] = ALIGN_MASKED
+    cls[outside] = ALIGN_OUTSIDE
+    used = cls == ALIGN_USED
+    I0 = float(lo) + v.astype(np.float64) * (float(hi) - float(lo)) / 255.0
+    scaled = float(gain) * I0
+    r = np.where(used, val - (scaled + float(bias)), 0.0)
+    w, rho = align_huber(r, huber_k)
+    J23 = align_warp(lut, q, W, H)[2]
+    g = gx[:, None] * J23[:, 0, :] + gy[:, None] * J23[:, 1, :]
+    return dict(cls=cls, r=r, w=np.where(used, w, 0.0), rho=np.where(used, rho, 0.0), g=np.where(used[:, None], g, 0.0), I0=np.where(used, I0, 0.0))
+
+
+def exposure_sum_terms(terms):
+    """The 21 terms of every pixel [S, 21]: w J^T J's upper triangle in row-major order, w J^T r, rho, with J = (g, -I0, -1); zero where the pixel is not
+    used.  The columns EXPOSURE_SHARED are align_sum_terms', by the same operations."""
+    g, w, r = terms["g"], terms["w"], terms["r"]
+    J = np.concatenate([g, -terms["I0"][:, None], np.where(terms["cls"] == ALIGN_USED, -1.0, 0.0)[:, None]], axis=1)
+    wJ = w[:, None] * J
+    cols = [wJ[:, i] * J[:, j] for i in range(5) for j in range(i, 5)] + [wJ[:, i] * r for i in range(5)] + [terms["rho"]]
+    return np.stack(cols, axis=1)
+
+
+def exposure_sums(terms, with_scale=False):
+    """The 21 sums and the four counts of one frame's terms, as align_sums gives its ten: (sums float64 [21], counts int64 [4]) and, with_scale, sum |term|
+    per sum."""
+    t = exposure_sum_terms(terms)
+    sums = t.astype(np.longdouble).sum(axis=0).astype(np.float64)
+    counts = np.bincount(terms["cls"], minlength=4).astype(np.int64)
+    return (sums, counts, np.abs(t).astype(np.longdouble).sum(axis=0).astype(np.float64)) if with_scale else (sums, counts)
+
+
+def exposure_collinear(sums):
+    """exposure_collinear (exposure_rule.h): the undamped pivot of the bias behind the gain, H44 - H34^2 / H33, is at most EXPOSURE_COLLINEAR of H44."""
+    h33, h34, h44 = (float(sums[k]) for k in (12, 13, 14))
+    if not (h33 > 0.0 and h44 > 0.0):
+        return True
+    return not (h44 - h34 * h34 / h33 > EXPOSURE_COLLINEAR * h44)
+
+
+def exposure_step(sums, lam, estimate):
+    """exposure_solve (exposure_rule.h): x [5] = (delta, x_a, x_b) of (H + lam diag H) x = -b on the active rows of the 21 sums by a Cholesky, zero where a
+    parameter is not estimated (estimate: EXPOSURE_GAIN | EXPOSURE_BIAS).  estimate = 0 is align_step itself.  None where the frame is degenerate: a pivot
+    is not positive, or gain and bias are both estimated and their columns collinear."""
+    sums = np.asarray(sums, dtype=np.float64).reshape(EXPOSURE_SUMS)
+    estimate = int(estimate)
+    if not 0 <= estimate <= 3:
+        raise ValueError("estimate is a mask of EXPOSURE_GAIN and EXPOSURE_BIAS")
+    x = np.zeros(5)
+    if estimate == 0:
+        ten = sums[list(EXPOSURE_SHARED)]
+        delta = align_step(ten[:6], ten[6:9], lam)
+        if delta is None:
+            return None
+        x[:3] = delta
+        return x
+    if estimate == 3 and exposure_collinear(sums):
+        return None
+    idx = [0, 1, 2] + ([3] if estimate & EXPOSURE_GAIN else []) + ([4] if estimate & EXPOSURE_BIAS else [])
+    n = len(idx)
+    A = np.array([[sums[exposure_h_index(min(i, j), max(i, j))] for j in idx] for i in idx])
+    A = A + float(lam) * np.diag(np.diag(A))
+    L = np.zeros((n, n))
+    for j in range(n):
+        d = A[j, j] - L[j, :j] @ L[j, :j]
+        if not d > 0.0:
+            return None
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, n):
+            L[i, j] = (A[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
+    rhs = -sums[[EXPOSURE_RHS + i for i in idx]]
+    y = np.zeros(n)
+    for i in range(n):
+        y[i] = (rhs[i] - L[i, :i] @ y[:i]) / L[i, i]
+    z = np.zeros(n)
+    for i in range(n - 1, -1, -1):
+        z[i] = (y[i] - L[i + 1:, i] @ z[i + 1:]) / L[i, i]
+    if not np.isfinite(z).all():
+        return None
+    x[idx] = z
+    return x
+
+
+def align_frames_exposure(frames_u8, q_xyzw, lut, plane, gain=1.0, bias=0.0, estimate=3, valid=None, lo=0.0, hi=255.0, skip_zero=False, gain_min=None,
+                          gain_max=None, **settings):
+    """The loop of emba_frames_exposure_align in numpy, with numpy's own pm: align_frames with (a, b) beside q — the trial is q' = normalise(exp(delta) q),
+    a' = a + x_a, b' = b + x_b; accepted as align_frames accepts, and rejected when its estimated gain lies outside [gain_min, gain_max]; converged tests
+    |delta| < tol_rot.  A dict of q [F, 4], gain, bias [F], sums [F, 21], counts [F, 4], status, iters, cost0, n0 [F]."""
+    s = align_settings(**settings)
+    g_lo, g_hi = exposure_bounds(gain_min, gain_max)
+    estimate = int(estimate)
+    if not 0 <= estimate <= 3:
+        raise ValueError("estimate is a mask of EXPOSURE_GAIN and EXPOSURE_BIAS")
+    P = np.asarray(plane, dtype=np.float64)
+    H, W = P.shape
+    q_in = np.asarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+    F = q_in.shape[0]
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)
+    a_in, b_in = exposure_check(gain, bias, F)
+
+    def evaluate(f, q, a, b):
+        return exposure_sums(exposure_terms(frames[f], align_warp(lut, q, W, H)[1], lut, q, P, a, b, valid, lo, hi, skip_zero, s["huber_k"]))
+
+    out = dict(q=q_in.copy(), gain=a_in.copy(), bias=b_in.copy(), sums=np.zeros((F, EXPOSURE_SUMS)), counts=np.zeros((F, 4), np.int64),
+               status=np.zeros(F, np.int32), iters=np.zeros(F, np.int32), cost0=np.zeros(F), n0=np.zeros(F, np.int64))
+    for f in range(F):
+        q, a, b = q_in[f].copy(), float(a_in[f]), float(b_in[f])
+        sums, counts = evaluate(f, q, a, b)
+        out["cost0"][f], out["n0"][f] = sums[EXPOSURE_COST], counts[0]
+        lam, iters = float(s["lambda0"]), 0
+        while True:
+            x = exposure_step(sums, lam, estimate) if counts[0] >= s["min_pixels"] else None
+            if x is None:
+                status = ALIGN_DEGENERATE
+                break
+            if iters >= s["max_iters"]:
+                status = ALIGN_ITERATIONS
+                break
+            trial, ta, tb = so3.mul(so3.exp(x[:3]), q), a + x[3], b + x[4]
+            tsums, tcounts = evaluate(f, trial, ta, tb)
+            iters += 1
+            take = tcounts[0] >= s["min_pixels"] and tsums[EXPOSURE_COST] / tcounts[0] < sums[EXPOSURE_COST] / counts[0]
+            if (estimate & EXPOSURE_GAIN) and not g_lo <= ta <= g_hi:
+                take = False
+            if take:
+                q, a, b, sums, counts = trial, ta, tb, tsums, tcounts
+                lam = max(lam / s["lambda_down"], s["lambda_min"])
+                if np.linalg.norm(x[:3]) < s["tol_rot"]:
+                    status = ALIGN_CONVERGED
+                    break
+            else:
+                lam *= s["lambda_up"]
+                if lam > s["lambda_max"]:
+                    status = ALIGN_STALLED
+                    break
+        out["q"][f], out["gain"][f], out["bias"][f], out["sums"][f], out["counts"][f], out["status"][f], out["iters"][f] = q, a, b, sums, counts, status, iters
+    return out
+
+
+def exposure_bytes(frames_u8, gain, bias):
+    """exposure_byte (exposure_rule.h) of every byte of frames_u8 [F, S] under its frame's (gain, bias): clamp(rint(a * v + b), 0, 255), ties to even, in
+    fp64 — what a compensated frame votes into the mosaic.  uint8 [F, S]."""
+    v = np.asarray(frames_u8, dtype=np.uint8)
+    F = v.shape[0]
+    a, b = exposure_check(gain, bias, F)
+    v2 = v.reshape(F, -1).astype(np.float64)
+    scaled = a[:, None] * v2
+    return np.clip(np.rint(scaled + b[:, None]), 0.0, 255.0).astype(np.uint8)
+
+
+def exposure_gauge(gain, bias, ok=None):
+    """exposure_gauge (exposure_rule.h): the common affine tone of frames aligned to their own mosaic, fixed — alpha = mean a, beta = mean b over the frames
+    with ok (all of them where None), a <- a / alpha, b <- (b - beta) / alpha for every frame.  Returns (gain, bias), unchanged copies where no frame is
+    ok or alpha is not positive."""
+    a, b = np.array(gain, dtype=np.float64).reshape(-1), np.array(bias, dtype=np.float64).reshape(-1)
+    sel = np.ones(a.size, bool) if ok is None else np.asarray(ok).astype(bool).reshape(-1)
+    if not sel.any():
+        return a, b
+    alpha, beta = float(np.sum(a[sel])) / int(sel.sum()), float(np.sum(b[sel])) / int(sel.sum())
+    if not (alpha > 0.0 and np.isfinite(alpha) and np.isfinite(beta)):
+        return a, b
+    return a / alpha, (b - beta) / alpha
+
+
 # ---- intensity frames tracked against their own growing mosaic (numpy forms of emba_frames_track, emba_track_eval and emba_track_level_get,
 # include/emba_hip.h; the device forms are LEGM.track_frames, LEGM.track_eval and LEGM.track_level; DESIGN.md §21).  The rule is
 # emba_amd/csrc/track_rule.h's: given the same level-0 pm the level sums are the same integers; given the same sums and the same level pm the classes are

@@ -357,6 +357,31 @@ class LEGM:
                                                1 if skip_zero else 0, 1 if accumulate else 0, C.byref(dropped), C.byref(skipped), _p(pm, _dp)))
         return dict(dropped=dropped.value, skipped=skipped.value, pm=pm)
 
+    def mosaic_frames_exposure(self, frames, frame_t_ns, traj, gain=None, bias=None, skip_zero=False, accumulate=False, want_pm=False):
+        """mosaic_frames with a gain and a bias per frame (emba_mosaic_frames_exposure; the rule: include/emba_hip.h): frame f votes its compensated bytes
+        clamp(rint(gain[f] v + bias[f]), 0, 255) in the place of v — io.mosaic_votes of io.exposure_bytes given the same pm, the same integers.  skip_zero
+        tests the raw byte.  gain, bias: [F], a scalar for all frames, or None for 1 and 0 (which gives mosaic_frames' sums).  The dict of mosaic_frames."""
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        knots = np.ascontiguousarray(traj.knots_xyzw, dtype=np.float64).reshape(-1, 4)
+        dropped, skipped = C.c_uint64(0), C.c_uint64(0)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        a, b = self._exposure_args(gain, bias, F)
+        self._check(self._L.emba_mosaic_frames_exposure(self._ctx, _p(frames, _u8p), _p(ts, _i64p), F, _p(a, _dp), _p(b, _dp), _p(knots, _dp), knots.shape[0],
+                                                        int(traj.t0_ns), int(traj.dt_ns), 1 if skip_zero else 0, 1 if accumulate else 0, C.byref(dropped),
+                                                        C.byref(skipped), _p(pm, _dp)))
+        return dict(dropped=dropped.value, skipped=skipped.value, pm=pm)
+
+    @staticmethod
+    def _exposure_args(gain, bias, F):
+        """gain, bias as contiguous float64 [F] (a scalar is broadcast; None is 1 or 0); what is in them is the entry point's to refuse."""
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if gain is None else gain, dtype=np.float64), (F,)))
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if bias is None else bias, dtype=np.float64), (F,)))
+        return a, b
+
     def mosaic(self, min_weight=256, fill=0.0):
         """The mosaic as it stands (emba_mosaic_get): a dict of sum_w, sum_v uint64 [pano_h, pano_w], covered bool (sum_w >= min_weight; 256 is one whole
         pixel's worth), mean float64 (sum_v / sum_w in byte units where covered, else `fill`) and n_covered — io.mosaic_mean of the sums, bit for bit."""
@@ -433,6 +458,46 @@ class LEGM:
                                               int(min_weight), float(fill), float(lo), float(hi), 1 if skip_zero else 0, C.addressof(cs), _p(q_out, _dp),
                                               _p(sums, _dp), _p(counts, u64p), _p(status, _i32p), _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p)))
         return dict(q=q_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64))
+
+    def exposure_eval(self, frames, q_xyzw, gain=None, bias=None, plane=None, valid=None, use_mosaic=False, min_weight=256, fill=0.0, lo=0.0, hi=255.0,
+                      skip_zero=False, huber_k=0.0, want_pm=False, want_resid=False):
+        """align_frames_eval with a gain and a bias per frame (emba_frames_exposure_eval; the rule: include/emba_hip.h): the residual is
+        val - (gain[f] I0 + bias[f]), the parameters are the rotation, the gain and the bias.  A dict of sums float64 [F, 21] (H's upper triangle over
+        (delta, a, b) in row-major order, b's five, the cost), counts int64 [F, 4], pm and resid (None unless asked for) — io.exposure_terms and
+        io.exposure_sums given the same pm."""
+        frames, q, F, S, plane, valid = self._align_args(frames, q_xyzw, plane, valid, use_mosaic)
+        a, b = self._exposure_args(gain, bias, F)
+        sums, counts = np.zeros((F, 21)), np.zeros((F, 4), np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        resid = np.empty((F, S)) if want_resid else None
+        self._check(self._L.emba_frames_exposure_eval(self._ctx, _p(frames, _u8p), F, _p(q, _dp), _p(a, _dp), _p(b, _dp), _p(plane, _dp), _p(valid, _u8p),
+                                                      1 if use_mosaic else 0, int(min_weight), float(fill), float(lo), float(hi), 1 if skip_zero else 0,
+                                                      float(huber_k), _p(sums, _dp), _p(counts, C.POINTER(C.c_uint64)), _p(pm, _dp), _p(resid, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), pm=pm, resid=resid)
+
+    def align_frames_exposure(self, frames, q_xyzw, gain=None, bias=None, estimate=3, plane=None, valid=None, use_mosaic=False, min_weight=256, fill=0.0,
+                              lo=0.0, hi=255.0, skip_zero=False, gain_min=None, gain_max=None, **settings):
+        """Poses and exposures from frames (emba_frames_exposure_align): align_frames with a gain and a bias per frame, estimated with the rotation where
+        `estimate` (io.EXPOSURE_GAIN | io.EXPOSURE_BIAS) says so and kept otherwise; a trial whose estimated gain leaves [gain_min, gain_max]
+        (io.EXPOSURE_BOUNDS) is rejected.  A dict of q [F, 4], gain, bias [F], sums [F, 21] and counts [F, 4] at them, status, iters, cost0, n0 [F].
+        io.align_frames_exposure is the same loop in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        g_lo = float(emba_io.EXPOSURE_BOUNDS["gain_min"] if gain_min is None else gain_min)
+        g_hi = float(emba_io.EXPOSURE_BOUNDS["gain_max"] if gain_max is None else gain_max)
+        frames, q, F, S, plane, valid = self._align_args(frames, q_xyzw, plane, valid, use_mosaic)
+        a, b = self._exposure_args(gain, bias, F)
+        cs = _lib.EmbaExposureSettings(_lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]),
+                                                              float(s["lambda_down"]), float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]),
+                                                              float(s["huber_k"])), g_lo, g_hi)
+        q_out, a_out, b_out, sums, counts = q.copy(), a.copy(), b.copy(), np.zeros((F, 21)), np.zeros((F, 4), np.uint64)
+        status, iters, cost0, n0 = np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F), np.zeros(F, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_exposure_align(self._ctx, _p(frames, _u8p), F, _p(q, _dp), _p(a, _dp), _p(b, _dp), int(estimate), _p(plane, _dp),
+                                                       _p(valid, _u8p), 1 if use_mosaic else 0, int(min_weight), float(fill), float(lo), float(hi),
+                                                       1 if skip_zero else 0, C.addressof(cs), _p(q_out, _dp), _p(a_out, _dp), _p(b_out, _dp), _p(sums, _dp),
+                                                       _p(counts, u64p), _p(status, _i32p), _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p)))
+        return dict(q=q_out, gain=a_out, bias=b_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64))
 
     def track_frames(self, frames, frame_t_ns, q0=(0.0, 0.0, 0.0, 1.0), levels=(0,), batch=1, predict=True, skip_zero=False, min_weight=256, min_overlap=0.5,
                      want_pm=False, **settings):

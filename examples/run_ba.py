@@ -75,31 +75,48 @@ def load_frames(frames_dir, sw, sh):
     return frames, np.array(t_ns, dtype=np.int64)
 
 
-def frame_mosaic(legm, frames, t_ns, traj, skip_zero):
-    """The frames whose times the trajectory covers, voted into the context's mosaic on the device.  Returns how many those were."""
+def frame_mosaic(legm, frames, t_ns, traj, skip_zero, exposure=None):
+    """The frames whose times the trajectory covers, voted into the context's mosaic on the device.  Returns how many those were.
+    exposure: (gain, bias) per frame of --frames-exposure, and the frames vote their compensated bytes."""
     keep = (t_ns >= traj.t0_ns) & (t_ns < traj.t0_ns + traj.dt_ns * (traj.size() - 1))
     if not keep.any():
         raise SystemExit("--frames: no frame time lies inside the trajectory's knots")
-    legm.mosaic_frames(frames[keep], t_ns[keep], traj, skip_zero=skip_zero)
+    if exposure is None:
+        legm.mosaic_frames(frames[keep], t_ns[keep], traj, skip_zero=skip_zero)
+    else:
+        legm.mosaic_frames_exposure(frames[keep], t_ns[keep], traj, exposure[0][keep], exposure[1][keep], skip_zero=skip_zero)
     return int(keep.sum())
 
 
-def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_zero, log=print):
+def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_zero, log=print, estimate=None):
     """--refine-frames N: poses from frames.  Per round: the frames are stitched along the current raw trajectory, every frame is
     aligned to that mosaic's mean under its covered cells on the device, and io.fit_ctrl_poses of the aligned rotations at the frame times, merged with the
     raw poses outside the frames' span, becomes the raw trajectory.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the aligned
-    rotation, the status and the mean cost before and after, of the last round."""
+    rotation, the status and the mean cost before and after, of the last round.
+    estimate (--frames-exposure bias / gain-bias: io.EXPOSURE_BIAS, or EXPOSURE_GAIN | EXPOSURE_BIAS): every frame carries a gain
+    and a bias in byte units, 1 and 0 at the start.  Per round the frames are stitched with them, aligned with them estimated beside the rotation, and
+    the common tone of the frames that did not end degenerate is fixed by io.exposure_gauge, before the trajectory is refitted.  The rows then end in the
+    gain and the bias, and a fifth value is returned: (gain, bias) for every frame of --frames, 1 and 0 for those the trajectory does not cover."""
     keep = (t_ns >= traj.t0_ns) & (t_ns < traj.t0_ns + traj.dt_ns * (traj.size() - 1))
     if not keep.any():
         raise SystemExit("--frames: no frame time lies inside the trajectory's knots")
     fr, ts = frames[keep], t_ns[keep]
     t_beg, dt = traj.t0_ns * 1e-9, traj.dt_ns * 1e-9
     rows = []
+    gain, bias = np.ones(len(ts)), np.zeros(len(ts))
     for rnd in range(1, rounds + 1):
-        legm.mosaic_frames(fr, ts, traj, skip_zero=skip_zero)
         q0 = np.array([traj.evaluate(int(tn)) for tn in ts])
-        r = legm.align_frames(fr, q0, use_mosaic=True, lo=0.0, hi=255.0, skip_zero=skip_zero, huber_k=huber_k)
-        before, after = r["cost0"] / np.maximum(r["n0"], 1), r["sums"][:, 9] / np.maximum(r["counts"][:, 0], 1)
+        if estimate is None:
+            legm.mosaic_frames(fr, ts, traj, skip_zero=skip_zero)
+            r = legm.align_frames(fr, q0, use_mosaic=True, lo=0.0, hi=255.0, skip_zero=skip_zero, huber_k=huber_k)
+            cost = r["sums"][:, 9]
+        else:
+            legm.mosaic_frames_exposure(fr, ts, traj, gain, bias, skip_zero=skip_zero)
+            r = legm.align_frames_exposure(fr, q0, gain, bias, estimate, use_mosaic=True, lo=0.0, hi=255.0, skip_zero=skip_zero, huber_k=huber_k)
+            cost = r["sums"][:, eio.EXPOSURE_COST]
+            gain, bias = eio.exposure_gauge(r["gain"], r["bias"], r["status"] != eio.ALIGN_DEGENERATE)
+            log(f"refine-frames round {rnd}: gain {gain.min():.4f} ... {gain.max():.4f} (std {gain.std():.4f}), bias {bias.min():.3f} ... {bias.max():.3f} bytes")
+        before, after = r["cost0"] / np.maximum(r["n0"], 1), cost / np.maximum(r["counts"][:, 0], 1)
         tf = ts * 1e-9
         outside = (t_raw < tf[0]) | (t_raw > tf[-1])
         t_all, q_all = np.concatenate([t_raw[outside], tf]), np.concatenate([q_raw[outside], r["q"]])
@@ -111,7 +128,11 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
         log(f"refine-frames round {rnd}: {len(ts)} frames aligned to their mosaic ({names}); mean cost {before.mean():.4g} -> {after.mean():.4g}, "
             f"mean turn {moved.mean():.3e} rad, up to {int(r['iters'].max())} trials")
         rows = [(tn, q, int(st), b, a_) for tn, q, st, b, a_ in zip(ts, r["q"], r["status"], before, after)]
-    return traj, t_raw, q_raw, rows
+    if estimate is None:
+        return traj, t_raw, q_raw, rows
+    g_all, b_all = np.ones(len(t_ns)), np.zeros(len(t_ns))
+    g_all[keep], b_all[keep] = gain, bias
+    return traj, t_raw, q_raw, [row + (g, o) for row, g, o in zip(rows, gain, bias)], (g_all, b_all)
 
 
 def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
@@ -243,6 +264,9 @@ def main():
     ap.add_argument("--refine-frames", type=int, default=0, metavar="N", help="with --frames and given poses: N rounds before the BA, each stitching the frames along "
                     "the current raw trajectory, aligning every frame's rotation to that mosaic on the device and fitting the raw trajectory to the aligned "
                     "rotations (DESIGN.md section 20); writes <out>/frames_aligned.txt")
+    ap.add_argument("--frames-exposure", choices=("none", "bias", "gain-bias"), default="none", help="with --refine-frames: a bias, or a gain and a bias, per frame "
+                    "(compensated byte = gain * byte + bias), estimated with the frame's rotation in every round and applied when the frames are stitched, the "
+                    "mosaic of --init-map frames and frame_mosaic.pgm included (DESIGN.md section 22); frames_aligned.txt gains the two columns")
     ap.add_argument("--frames-huber", type=float, default=0.0, metavar="K", help="with --refine-frames: the Huber threshold of the alignment, in byte units (0: quadratic)")
     ap.add_argument("--init-poses", default="given", choices=["given", "events", "identity", "frames"], help="frames: no --poses is needed — the intensity frames of "
                     "--frames are tracked against their own growing mosaic on the device from --track-q0 on, and the tracked frames' rotations are the raw poses "
@@ -299,6 +323,8 @@ def main():
                  "whose trajectory at that point carries the timing only")
     if a.refine_frames < 0 or (a.refine_frames and not a.frames):
         ap.error("--refine-frames N (N >= 0) aligns the frames of --frames DIR")
+    if a.frames_exposure != "none" and not a.refine_frames:
+        ap.error("--frames-exposure estimates the exposure in the rounds of --refine-frames N: it needs N >= 1")
     if a.refine_frames and a.init_poses not in ("given", "frames"):
         ap.error("--refine-frames aligns the frames from the raw trajectory: it needs given poses (--poses, or --demo), not --init-poses events / identity")
     if not (np.isfinite(a.frames_huber) and a.frames_huber >= 0.0):
@@ -422,19 +448,27 @@ def main():
                 fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost\n")
                 for tn, q, st, ov, cost in rows:
                     fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {ov:.9g} {cost:.9g}\n")
+    frames_exposure = None      # (gain, bias) per frame of --frames, once --frames-exposure has estimated them
+    exposure_estimate = {"none": None, "bias": eio.EXPOSURE_BIAS, "gain-bias": eio.EXPOSURE_GAIN | eio.EXPOSURE_BIAS}[a.frames_exposure]
     if a.refine_frames:      # poses from frames: the raw trajectory is refitted to the frames' aligned rotations before anything else reads it
-        traj, t, qs, rows = refine_frames(legm, frames, frames_t_ns, traj, np.asarray(t, dtype=np.float64), np.asarray(qs, dtype=np.float64), a.refine_frames,
-                                          a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None))
+        refined = refine_frames(legm, frames, frames_t_ns, traj, np.asarray(t, dtype=np.float64), np.asarray(qs, dtype=np.float64), a.refine_frames,
+                                a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None), estimate=exposure_estimate)
+        traj, t, qs, rows = refined[:4]
+        if exposure_estimate is not None:
+            frames_exposure = refined[4]
         if rank == 0:
             with open(os.path.join(a.out, "frames_aligned.txt"), "w") as fh:
-                fh.write("# t[s] qx qy qz qw status(1 converged, 2 stalled, 3 iterations, 4 degenerate) mean_cost_before mean_cost_after\n")
-                for tn, q, st, b, a_ in rows:
-                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {b:.9g} {a_:.9g}\n")
+                fh.write("# t[s] qx qy qz qw status(1 converged, 2 stalled, 3 iterations, 4 degenerate) mean_cost_before mean_cost_after"
+                         + (" gain bias[bytes]" if exposure_estimate is not None else "") + "\n")
+                for row in rows:
+                    tn, q, st, b, a_ = row[:5]
+                    more = "".join(f" {v:.17g}" for v in row[5:])
+                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {b:.9g} {a_:.9g}{more}\n")
     if a.init_map == "frames":      # the mosaic of the frames along the raw trajectory, on the device; its gradient map is handed on as the given map
         if tracked_mosaic and not a.refine_frames:      # the mosaic the tracker left: no second stitch
             used = int(sum(1 for row in rows if row[2] != eio.TRACK_LOST))
         else:
-            used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero)
+            used = frame_mosaic(legm, frames, frames_t_ns, traj, a.frames_skip_zero, frames_exposure)
         fm = legm.mosaic_map(lo=a.frames_lo, hi=a.frames_hi, eps=a.frames_eps, take_log=bool(a.frames_log))
         Gx, Gy = fm["Gx"], fm["Gy"]
         if rank == 0:
@@ -534,7 +568,7 @@ def main():
     # intensity panorama from the refined gradient map (solver.cpp:417-425 / 471-479), reconstructed on the device
     eio.save_pgm(os.path.join(a.out, "map_poisson_opt.pgm"), eio.normalize_robust(legm.reconstructIntensity(boundary=a.panorama_boundary), 0.1))
     if a.frames:      # the frames along the FINAL trajectory: an independent picture of the scene, to set against map_poisson_opt.pgm
-        used = frame_mosaic(legm, frames, frames_t_ns, res.traj, a.frames_skip_zero)
+        used = frame_mosaic(legm, frames, frames_t_ns, res.traj, a.frames_skip_zero, frames_exposure)
         mo = legm.mosaic()
         eio.save_pgm(os.path.join(a.out, "frame_mosaic.pgm"), np.clip(np.rint(mo["mean"]), 0, 255).astype(np.uint8))
         eio.save_pgm(os.path.join(a.out, "frame_mosaic_covered.pgm"), np.where(mo["covered"], 255, 0).astype(np.uint8))

@@ -739,6 +739,63 @@ emba_status emba_track_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] 
                             double* resid_out /* [F, sh*sw] */);
 emba_status emba_track_level_get(emba_ctx* ctx, int32_t level, uint64_t* sum_w_out /* [H_l, W_l] */, uint64_t* sum_v_out /* [H_l, W_l] */);
 
+/* ---- Per-frame exposure: the photometric half of the alignment.  A camera with auto-exposure changes its tone from frame to frame; here
+ * frame f carries (q_f, a_f, b_f), its compensated intensity is a_f * I0 + b_f, the two are estimated with the rotation and applied when the frames are
+ * stitched.  The rule lives in emba_amd/csrc/exposure_rule.h; emba_amd.io.exposure_terms / exposure_sums / exposure_step / align_frames_exposure /
+ * exposure_bytes / exposure_gauge are the same rule in numpy.
+ *
+ *   model             I0 = lo + v * (hi - lo) / 255, emba_frames_align's expression.  I = gain[f] * I0 + bias[f]: multiply, then add, without contraction.
+ *                     r = val - I.  The warp, the cell, the sample and its gradient, the Huber weight, g and the precedence outside / masked / skipped are
+ *                     emba_frames_align's; skipped tests the raw byte v.  With gain = 1 and bias = 0, I is I0 exactly.
+ *   parameters        five per frame: delta (the rotation's left perturbation), a, b.  The Jacobian row of r is J = (g, -I0, -1).
+ *   sums              21 per frame: H = sum w J^T J as the 15 entries of its upper triangle in row-major order (00 01 02 03 04 11 12 13 14 22 23 24 33 34 44),
+ *                     b = sum w J^T r (five), cost = sum rho.  Entries 0 1 2 5 6 9, 15 16 17 and 20 are emba_frames_align_eval's ten, from the same
+ *                     operations in the same order of reduction: with gain = 1, bias = 0 they are its bits.  The four counts are its counts.
+ *   estimate          a bitmask: EMBA_EXPOSURE_GAIN, EMBA_EXPOSURE_BIAS.  A parameter that is not estimated keeps its input value and has no row or column
+ *                     in the solve.  The rotation is always estimated.
+ *   step              (H + lambda diag H) x = -b on the active rows by a Cholesky, the leading 3 x 3 block in emba_frames_align's order of operations
+ *                     (estimate = 0 gives its bits).  A frame is degenerate when a pivot is not positive or n < min_pixels — and, with both gain and bias
+ *                     estimated, when their columns are collinear: the damping keeps the pivots of such a system positive, so the undamped pivot of the
+ *                     bias behind the gain, H44 - H34^2 / H33, is tested against 1e-9 of H44.  A frame of one constant byte is degenerate this way.
+ *   trial             q' = normalise(exp(delta) (x) q), a' = a + x_a, b' = b + x_b.  Accepted as emba_frames_align accepts; a trial whose estimated gain
+ *                     lies outside [gain_min, gain_max] is rejected like one that raises the mean cost.  lambda and the four ways a frame ends are
+ *                     emba_frames_align's; converged tests |delta| < tol_rot, the rotation alone.
+ *   compensated byte  clamp(rint(a * v + b), 0, 255), ties to even, in fp64 without contraction: what frame f votes into the mosaic in the place of v.  The
+ *                     mosaic is in byte units (lo = 0, hi = 255), and so is a bias that is used here.  The two integer sums keep their units and their
+ *                     2^36 bound; emba_mosaic_get, emba_mosaic_map, use_mosaic and emba_frames_track read them as they stand.
+ *   gauge             aligning to a fixed plane has no freedom left.  Aligning to the frames' own mosaic leaves the common affine tone free; a caller who
+ *                     alternates fixes it on the host after every round: alpha = mean a, beta = mean b over the frames that count, a <- a / alpha,
+ *                     b <- (b - beta) / alpha (exposure_rule.h: exposure_gauge; emba_amd.io.exposure_gauge).
+ *
+ * emba_frames_exposure_eval: emba_frames_align_eval with gain [F] and bias [F]; sums_out [F, 21], the other outputs as there.
+ * emba_frames_exposure_align: emba_frames_align with gain_in, bias_in [F], estimate and the two bounds; gain_out, bias_out [F] beside q_out; sums_out [F, 21].
+ * emba_mosaic_frames_exposure: emba_mosaic_frames with gain [F] and bias [F]: the same pose stage, warp, vote, skip_zero (on the raw byte), accumulate, chunks,
+ * counters and pm_out, the compensated byte in the place of v.  With gain = 1, bias = 0 the sums are emba_mosaic_frames'.
+ * Refusals: everything the three originals refuse, and EMBA_ERR_INVALID_ARG for gain or bias NULL with F > 0, a gain or bias that is not finite, a gain <= 0,
+ * estimate outside 0 ... 3, gain bounds that are not finite or not 0 < gain_min <= 1 <= gain_max.  They are decided before anything is uploaded, zeroed or
+ * voted and leave every output and the mosaic untouched.  What the originals leave alone, these leave alone.  While emba_enable_kernel_timing is on, timer
+ * slot 7 brackets the first evaluation kernel (the first chunk's vote kernel) of a call. */
+#define EMBA_EXPOSURE_GAIN 1
+#define EMBA_EXPOSURE_BIAS 2
+typedef struct {
+    emba_align_settings align;
+    double gain_min, gain_max;
+} emba_exposure_settings;
+emba_status emba_frames_exposure_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                                      const double* gain /* [F] */, const double* bias /* [F] */, const double* plane_host /* H*W or NULL */,
+                                      const uint8_t* valid_host /* H*W or NULL */, int32_t use_mosaic, uint64_t min_weight, double fill, double lo, double hi,
+                                      int32_t skip_zero, double huber_k, double* sums_out /* [F, 21] */, uint64_t* counts_out /* [F, 4] */,
+                                      double* pm_out /* [F, sh*sw, 2] */, double* resid_out /* [F, sh*sw] */);
+emba_status emba_frames_exposure_align(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                                       const double* gain_in /* [F] */, const double* bias_in /* [F] */, int32_t estimate, const double* plane_host /* H*W or NULL */,
+                                       const uint8_t* valid_host /* H*W or NULL */, int32_t use_mosaic, uint64_t min_weight, double fill, double lo, double hi,
+                                       int32_t skip_zero, const emba_exposure_settings* settings, double* q_out /* [F, 4] */, double* gain_out /* [F] */,
+                                       double* bias_out /* [F] */, double* sums_out /* [F, 21] */, uint64_t* counts_out /* [F, 4] */, int32_t* status_out /* [F] */,
+                                       int32_t* iters_out /* [F] */, double* cost0_out /* [F] */, uint64_t* n0_out /* [F] */);
+emba_status emba_mosaic_frames_exposure(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, const int64_t* frame_t_ns, size_t F, const double* gain /* [F] */,
+                                        const double* bias /* [F] */, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t skip_zero,
+                                        int32_t accumulate, uint64_t* dropped_out, uint64_t* skipped_out, double* pm_out /* [F, sh*sw, 2] or NULL */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
