@@ -1,7 +1,7 @@
 // emba_amd/csrc/context.h — the context behind the C ABI of include/emba_hip.h: what it owns in HBM, what the host knows about the window, the order,
 // the evaluation, the equations and the last solve, and the helpers every host function uses (fail, HIP_TRY, ensure, nblocks).
 // Included by emba_hip.hip and the host headers of its translation unit (transfer_host.h, order_host.h, step_host.h, map_host.h, readback_host.h,
-// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, align_host.h, track_host.h, exposure_host.h, group.h); host code only.
+// cost_host.h, options_host.h, timing_host.h, solve_host.h, poisson_host.h, render_host.h, sequence_host.h, cmax_host.h, panorama_host.h, contrast_host.h, view_host.h, mosaic_host.h, sim_host.h, frame_host.h, align_host.h, track_host.h, exposure_host.h, group.h); host code only.
 #pragma once
 #include "../../include/emba_hip.h"
 
@@ -254,35 +254,35 @@ struct MosaicBuffers {
     DevBuf t, pose, knots, head, frames, pm, counters, mean, covered, L, covered_log, gx, gy;
 };
 
-// Intensity frames aligned to a panorama plane (align_host.h); all of it scratch of one call.  plane, valid: the plane the frames are aligned to and its mask
-// (a caller's, or the mosaic's mean and covered cells); one chunk of frames as bytes, as pm and as residuals; partial: the evaluation kernel's sums per
-// (frame, workgroup); q_trial, esums, ecounts: the rotation every frame of the chunk is evaluated at and what the evaluation gave there; q ... n0: the
-// members of align_rule.h's AlignFrame, one array each, with the first evaluation's cost and n; running: the frames a step left running.
-struct AlignBuffers {
-    DevBuf plane, valid, frames, pm, resid, partial, q_trial, esums, ecounts;
+// What a stage that evaluates intensity frames and runs the per-frame Levenberg-Marquardt loop on them keeps (frame_host.h); all of it scratch of one call,
+// and each stage has its own.  One chunk of frames as bytes, as pm and as residuals; partial: the evaluation kernel's sums per (frame, workgroup); q_trial,
+// esums, ecounts: the rotation every frame of the chunk is evaluated at and what the evaluation gave there; q ... have_trial: the members of the rule header's
+// frame state (AlignFrame, ExposureFrame), one array each; cost0, n0: the first evaluation's cost and n; running: the frames a step left running.
+struct FrameLoopBuffers {
+    DevBuf frames, pm, resid, partial, q_trial, esums, ecounts;
     DevBuf q, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
 };
+
+// Intensity frames aligned to a panorama plane (align_host.h); all of it scratch of one call.  plane, valid: the plane the frames are aligned to and its mask
+// (a caller's, or the mosaic's mean and covered cells).
+struct AlignBuffers { DevBuf plane, valid; FrameLoopBuffers loop; };
 
 // Intensity frames tracked against their own growing mosaic (track_host.h).  lw, lv: the two uint64 sums per cell of the levels 1 ... 7 [H_l, W_l], resident
 // between calls (level 0's are the mosaic's sum_w, sum_v); voted: bit l is set when the last successful emba_frames_track voted into level l.  Scratch of one
 // call, over its F frames: the frame times, every frame's rotation, status, iterations per level, cost, counts and overlap; counters: [0] dropped votes,
-// [1] skipped pixels.  Over one batch (or one chunk of emba_track_eval): pred, the predicted starts; pm and resid; the rest is what AlignBuffers holds for
-// emba_frames_align's loop, here for this stage's own.  frames: one chunk of bytes.
+// [1] skipped pixels.  Over one batch (or one chunk of emba_track_eval): pred, the predicted starts, and the loop's state; loop.frames: one chunk of bytes.
 struct TrackBuffers {
     DevBuf lw[8], lv[8]; uint32_t voted = 0;
-    DevBuf t, q_all, status_all, iters_all, cost_all, overlap_all, counts_all, counters;
-    DevBuf frames, pred, pm, resid, partial, q_trial, esums, ecounts;
-    DevBuf q, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
+    DevBuf t, q_all, status_all, iters_all, cost_all, overlap_all, counts_all, counters, pred;
+    FrameLoopBuffers loop;
 };
 
-// Per-frame exposure (exposure_host.h); all of it scratch of one call.  One chunk of frames as bytes, as pm and as residuals; partial: the evaluation kernel's
-// sums per (frame, workgroup); q_trial, gain_trial, bias_trial, esums, ecounts: where every frame of the chunk is evaluated and what the evaluation gave
-// there; q ... n0: the members of exposure_rule.h's ExposureFrame, one array each, with the first evaluation's cost and n; running: the frames a step left
-// running.  vote_gain, vote_bias: all F gains and biases of emba_mosaic_frames_exposure.  (The plane and its mask are AlignBuffers'; the pose table, the
-// bytes and the counters of the vote are MosaicBuffers'.)
+// Per-frame exposure (exposure_host.h); all of it scratch of one call.  gain_trial, bias_trial: where, with loop.q_trial, every frame of the chunk is
+// evaluated; gain, bias: the rest of exposure_rule.h's ExposureFrame.  vote_gain, vote_bias: all F gains and biases of emba_mosaic_frames_exposure.  (The plane
+// and its mask are AlignBuffers'; the pose table, the bytes and the counters of the vote are MosaicBuffers'.)
 struct ExposureBuffers {
-    DevBuf frames, pm, resid, partial, q_trial, gain_trial, bias_trial, esums, ecounts;
-    DevBuf q, gain, bias, sums, counts, lambda, dnorm, status, iters, have_trial, cost0, n0, running;
+    FrameLoopBuffers loop;
+    DevBuf gain_trial, bias_trial, gain, bias;
     DevBuf vote_gain, vote_bias;
 };
 

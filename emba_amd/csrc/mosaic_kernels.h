@@ -2,9 +2,9 @@
 // emba_view_kernel, and the gradient map made from the mosaic.
 // The rules: mosaic_rule.h, panorama_rule.h (pano_vote), include/emba_hip.h (emba_mosaic_frames, emba_mosaic_get, emba_mosaic_map), DESIGN.md §19.
 //   * pose stage                 the rotations at the F frame times: emba_pose_kernel (kernels.h) as it is, into the pose table of mosaic_host.h
-//   * emba_mosaic_vote_kernel    one lane per frame pixel, the frame in blockIdx.y: the byte (coalesced), the warp of emba_view_kernel (quat_to_matrix, the
-//                                sum3 products, project_chain<false>), pano_vote's four cells, and per cell two return-less 64-bit integer atomic adds
-//                                into sum_w and sum_v in HBM; a wave's dropped votes and skipped pixels go up in one atomic each
+//   * emba_mosaic_vote_kernel    one lane per frame pixel, the frame in blockIdx.y: the byte (coalesced), frame_warp (frame_kernels.h), pano_vote's
+//                                four cells, and per cell two return-less 64-bit integer atomic adds into sum_w and sum_v in HBM (frame_vote_cells); a
+//                                wave's dropped votes and skipped pixels go up in one atomic each (frame_vote_counters)
 //   * emba_mosaic_mean_kernel    one lane per cell: mosaic_mean, the covered byte, a wave's count of covered cells in one atomic
 //   * emba_mosaic_log_kernel     one lane per cell: mosaic_log of the mean, the byte of the cells that stay covered
 //   * emba_mosaic_map_kernel     one lane per cell: mosaic_gradient of the L and the bytes the log kernel wrote (a second pass: the neighbours' L are read,
@@ -14,13 +14,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "device_math.h"
+#include "frame_kernels.h"
 #include "kernels.h"      // kPoseStride, emba_pose_kernel
 #include "mosaic_rule.h"
 
 namespace emba {
 
-constexpr int kMosaicThreads = 256;
+constexpr int kMosaicThreads = kFrameThreads;      // the vote kernel's, and the per-cell kernels' below
 
 struct MosaicVoteParams {
     const double* lut;            // bearing vector per sensor pixel [S, 3]
@@ -45,35 +45,13 @@ __global__ __launch_bounds__(kMosaicThreads) void emba_mosaic_vote_kernel(Mosaic
     if (s < p.S) {
         const size_t o = f * (size_t)p.S + (size_t)s;
         const unsigned int v = p.frames[o];
-        const double* P = p.pose + (size_t)kPoseStride * f;      // wave-uniform
-        const double q[4] = {P[0], P[1], P[2], P[3]};
-        double R[9];
-        quat_to_matrix(q, R);
-        const double* bv = p.lut + 3 * (size_t)s;
-        const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
-        double rb[3], pm[2], J23[6];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
-        project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
+        double pm[2], J23[6];
+        frame_warp(p.lut, p.pose + (size_t)kPoseStride * f, s, p.fx, p.fy, p.cx, p.cy, pm, J23);
         if (p.pm) { p.pm[2 * o] = pm[0]; p.pm[2 * o + 1] = pm[1]; }
         if (p.skip_zero && v == 0) skipped = 1;
-        else {
-            const PanoVotes pv = pano_vote(pm[0], pm[1], p.W, p.H);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!pv.w[k]) continue;
-                if (pv.cell[k] < 0) { ++dropped; continue; }
-                atomicAdd(p.sum_w + pv.cell[k], (unsigned long long)pv.w[k]);                          // (results unused: return-less adds)
-                if (v) atomicAdd(p.sum_v + pv.cell[k], (unsigned long long)pv.w[k] * (unsigned long long)v);
-            }
-        }
+        else frame_vote_cells(pano_vote(pm[0], pm[1], p.W, p.H), v, p.sum_w, p.sum_v, dropped);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { dropped += __shfl_xor(dropped, o); skipped += __shfl_xor(skipped, o); }
-    if ((threadIdx.x & 63) == 0) {
-        if (dropped) atomicAdd(p.counters, (unsigned long long)dropped);
-        if (skipped) atomicAdd(p.counters + 1, (unsigned long long)skipped);
-    }
+    frame_vote_counters(dropped, skipped, p.counters);
 }
 #pragma clang fp contract(fast)
 

@@ -2,11 +2,14 @@
 // and step kernels of align_kernels.h): the tracker (emba_frames_track), one evaluation against a level's planes as they stand (emba_track_eval) and the
 // planes themselves (emba_track_level_get).  What is plain arithmetic — the argument checks, the levels, the batches, the prediction, the pixel, the verdict
 // — is decided in track_rule.h; here are the buffers (emba_ctx::track), the launches and the C ABI.
-// Part of emba_hip.hip's translation unit, included by it below align_host.h; it uses sequence_host.h (SEQ_TRY), transfer_host.h (d2h_pageable),
-// panorama_host.h (kSeqStageTimerSlot) and mosaic_host.h (mosaic_zero_sums: level 0's planes are the mosaic's sums).  Nothing of the registered window, of
+// Part of emba_hip.hip's translation unit, included by it below align_host.h; it uses frame_host.h (the buffers of a batch, one evaluation, the chunked
+// evaluation, the loop: DESIGN.md §23), align_host.h (align_launch_step), sequence_host.h (SEQ_TRY), transfer_host.h (d2h_pageable) and mosaic_host.h
+// (mosaic_zero_sums: level 0's planes are the mosaic's sums).  Nothing of the registered window, of
 // the resident sequence, of the resident map or of any other stage's buffers is written, but for the mosaic's sums and its count of votes.
 #pragma once
+#include "align_host.h"
 #include "context.h"
+#include "frame_host.h"
 #include "track_kernels.h"
 #include "track_rule.h"
 
@@ -59,52 +62,16 @@ emba_status track_refusals(emba_ctx* c, const uint8_t* frames, const int64_t* t_
     return EMBA_OK;
 }
 
-// the buffers of a batch (or an evaluation chunk) of at most nf frames; `loop`: the frames' state as well
-emba_status track_ensure_batch(emba_ctx* c, size_t nf, bool want_pm, bool want_resid, bool loop)
-{
-    TrackBuffers& T = c->track;
-    const size_t S = c->S, nb = nblocks(S, kTrackThreads);
-    if (want_pm) SEQ_TRY(ensure<double>(c, T.pm, 2 * nf * S));
-    if (want_resid) SEQ_TRY(ensure<double>(c, T.resid, nf * S));
-    SEQ_TRY(ensure<double>(c, T.partial, nf * nb * (size_t)kAlignPartial));
-    SEQ_TRY(ensure<double>(c, T.q_trial, 4 * nf));
-    SEQ_TRY(ensure<double>(c, T.esums, (size_t)kAlignSums * nf));
-    SEQ_TRY(ensure<unsigned long long>(c, T.ecounts, 4 * nf));
-    if (!loop) return EMBA_OK;
-    SEQ_TRY(ensure<double>(c, T.pred, 4 * nf));
-    SEQ_TRY(ensure<double>(c, T.q, 4 * nf));
-    SEQ_TRY(ensure<double>(c, T.sums, (size_t)kAlignSums * nf));
-    SEQ_TRY(ensure<unsigned long long>(c, T.counts, 4 * nf));
-    SEQ_TRY(ensure<double>(c, T.lambda, nf));
-    SEQ_TRY(ensure<double>(c, T.dnorm, nf));
-    SEQ_TRY(ensure<int32_t>(c, T.status, nf));
-    SEQ_TRY(ensure<int32_t>(c, T.iters, nf));
-    SEQ_TRY(ensure<int32_t>(c, T.have_trial, nf));
-    SEQ_TRY(ensure<double>(c, T.cost0, nf));
-    SEQ_TRY(ensure<unsigned long long>(c, T.n0, nf));
-    SEQ_TRY(ensure<unsigned int>(c, T.running, 1));
-    return EMBA_OK;
-}
-
 // one evaluation of nf frames (bytes at `bytes`) at T.q_trial against `plane` into T.esums / T.ecounts: the evaluation kernel and §20's reduction of its
 // partial sums.  `status`: the loop's status words, or nullptr (every frame is evaluated); `timed`: timer slot 7 around the evaluation kernel
 emba_status track_launch_eval(emba_ctx* c, const TrackPlane& plane, const uint8_t* bytes, size_t nf, const int32_t* status, uint64_t min_weight, int32_t skip_zero,
                               double huber_k, bool want_pm, bool want_resid, bool timed)
 {
-    TrackBuffers& T = c->track;
-    hipStream_t s = c->stream;
-    const unsigned nb = nblocks(c->S, kTrackThreads);
-    TrackEvalParams P{c->d_lut.as<double>(), T.q_trial.as<double>(), status, bytes, plane.sum_w, plane.sum_v, (int)c->S, plane.W, plane.H, plane.scale,
-                      c->fx, c->fy, c->cx, c->cy, (unsigned long long)min_weight, huber_k, skip_zero != 0, T.partial.as<double>(),
-                      want_pm ? T.pm.as<double>() : nullptr, want_resid ? T.resid.as<double>() : nullptr};
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_start[kSeqStageTimerSlot], s));
-    hipLaunchKernelGGL(emba_frames_track_eval_kernel, dim3(nb, (unsigned)nf), dim3(kTrackThreads), 0, s, P);
-    if (timed) HIP_TRY(c, hipEventRecord(c->ev_stop[kSeqStageTimerSlot], s));
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(emba_frames_align_reduce_kernel, dim3(nblocks(nf * (size_t)(kAlignSums + 4), kAlignThreads)), dim3(kAlignThreads), 0, s,
-                       (const double*)T.partial.as<double>(), (int)nb, (long)nf, status, T.esums.as<double>(), T.ecounts.as<unsigned long long>());
-    HIP_TRY(c, hipGetLastError());
-    return EMBA_OK;
+    FrameLoopBuffers& T = c->track.loop;
+    const TrackEvalParams P{c->d_lut.as<double>(), T.q_trial.as<double>(), status, bytes, plane.sum_w, plane.sum_v, (int)c->S, plane.W, plane.H, plane.scale,
+                            c->fx, c->fy, c->cx, c->cy, (unsigned long long)min_weight, huber_k, skip_zero != 0, T.partial.as<double>(),
+                            want_pm ? T.pm.as<double>() : nullptr, want_resid ? T.resid.as<double>() : nullptr};
+    return frame_launch_eval(c, T, emba_frames_track_eval_kernel, P, emba_frames_align_reduce_kernel, kAlignSums, nf, timed);
 }
 
 emba_status track_launch_frames(emba_ctx* c, TrackFrameParams P)
@@ -124,6 +91,7 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     TrackBuffers& T = c->track;
+    FrameLoopBuffers& L = T.loop;
     const size_t S = c->S, NL = (size_t)set->n_levels;
 
     // the planes: every level a tracked frame votes into, zero
@@ -152,8 +120,9 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
         SEQ_TRY(ensure<double>(c, T.overlap_all, F));
         SEQ_TRY(ensure<unsigned long long>(c, T.counts_all, 4 * F));
         SEQ_TRY(ensure<unsigned long long>(c, T.counters, 2));
-        SEQ_TRY(ensure<uint8_t>(c, T.frames, std::min(per, F) * S));
-        SEQ_TRY(track_ensure_batch(c, maxb, pm_out != nullptr, false, true));
+        SEQ_TRY(ensure<uint8_t>(c, L.frames, std::min(per, F) * S));      // (a chunk's bytes; the batches below are no longer than a chunk)
+        SEQ_TRY(ensure<double>(c, T.pred, 4 * maxb));
+        SEQ_TRY(frame_ensure(c, L, kAlignSums, maxb, pm_out != nullptr, false, true));
     }
     SEQ_TRY(mosaic_zero_sums(c));      // (it allocates the mosaic's two sums, where they are missing, before it zeroes either)
     T.voted = 0;
@@ -184,7 +153,7 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
     HIP_TRY(c, hipMemsetAsync(T.status_all.p, 0, F * sizeof(int32_t), s));
     HIP_TRY(c, hipMemsetAsync(T.counters.p, 0, 2 * sizeof(unsigned long long), s));
     V.counters = T.counters.as<unsigned long long>();
-    V.pm = pm_out ? T.pm.as<double>() : nullptr;
+    V.pm = pm_out ? L.pm.as<double>() : nullptr;
 
     TrackFrameParams B{};
     B.n_levels = (int)NL; B.predict = set->predict != 0; B.min_overlap = set->min_overlap; B.S = (unsigned long long)S;
@@ -192,16 +161,16 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
     B.t = reinterpret_cast<const long long*>(T.t.as<int64_t>());
     B.q_all = T.q_all.as<double>(); B.status_all = T.status_all.as<int32_t>(); B.iters_all = T.iters_all.as<int32_t>();
     B.cost_all = T.cost_all.as<double>(); B.overlap_all = T.overlap_all.as<double>(); B.counts_all = T.counts_all.as<unsigned long long>();
-    B.pred = T.pred.as<double>(); B.q = T.q.as<double>(); B.q_trial = T.q_trial.as<double>(); B.sums = T.sums.as<double>();
-    B.counts = T.counts.as<unsigned long long>(); B.status = T.status.as<int32_t>(); B.iters = T.iters.as<int32_t>();
+    B.pred = T.pred.as<double>(); B.q = L.q.as<double>(); B.q_trial = L.q_trial.as<double>(); B.sums = L.sums.as<double>();
+    B.counts = L.counts.as<unsigned long long>(); B.status = L.status.as<int32_t>(); B.iters = L.iters.as<int32_t>();
 
     bool timed = c->kernel_timing != 0;
     for (size_t i = 0; i < chunks; ++i) {
         const ViewChunk ch = view_chunk(F, per, i);
-        HIP_TRY(c, hipMemcpyAsync(T.frames.p, frames + ch.f0 * S, ch.nf * S, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(L.frames.p, frames + ch.f0 * S, ch.nf * S, hipMemcpyHostToDevice, s));
         for (size_t f0 = ch.f0; f0 < ch.f0 + ch.nf;) {
             const size_t nf = track_batch_frames(f0, F, per, (size_t)set->batch);
-            const uint8_t* bytes = T.frames.as<uint8_t>() + (f0 - ch.f0) * S;
+            const uint8_t* bytes = L.frames.as<uint8_t>() + (f0 - ch.f0) * S;
             B.nf = (long)nf; B.f0 = (long)f0;
             if (f0 == 0) {
                 B.phase = kTrackAnchor;
@@ -209,24 +178,16 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
             } else {
                 B.phase = kTrackPredict;
                 SEQ_TRY(track_launch_frames(c, B));
-                AlignStepParams P{(long)nf, 1, set->align, T.q.as<double>(), T.q_trial.as<double>(), T.sums.as<double>(), T.lambda.as<double>(), T.dnorm.as<double>(),
-                                  T.counts.as<unsigned long long>(), T.status.as<int32_t>(), T.iters.as<int32_t>(), T.have_trial.as<int32_t>(), T.esums.as<double>(),
-                                  T.ecounts.as<unsigned long long>(), T.cost0.as<double>(), T.n0.as<unsigned long long>(), T.running.as<unsigned int>()};
                 for (size_t k = 0; k < NL; ++k) {
-                    // §20's loop against this level: evaluation 0 where the previous level ended, then per iteration a step and the evaluation of the frames still running
-                    for (int32_t it = 0;; ++it) {
-                        SEQ_TRY(track_launch_eval(c, sched[k], bytes, nf, it ? T.status.as<int32_t>() : nullptr, set->min_weight, set->skip_zero, set->align.huber_k,
-                                                  false, false, timed));
-                        timed = false;
-                        P.first = it == 0;
-                        HIP_TRY(c, hipMemsetAsync(T.running.p, 0, sizeof(unsigned int), s));
-                        hipLaunchKernelGGL(emba_frames_align_step_kernel, dim3(nblocks(nf, 64)), dim3(64), 0, s, P);
-                        HIP_TRY(c, hipGetLastError());
-                        unsigned int running = 0;
-                        HIP_TRY(c, hipMemcpyAsync(&running, T.running.p, sizeof running, hipMemcpyDeviceToHost, s));
-                        HIP_TRY(c, hipStreamSynchronize(s));
-                        if (!running) break;
-                    }
+                    // §20's loop against this level: evaluation 0 where the previous level ended
+                    SEQ_TRY(frame_lm_loop(
+                        c, L,
+                        [&](const int32_t* status, bool) {
+                            const bool t = timed;
+                            timed = false;
+                            return track_launch_eval(c, sched[k], bytes, nf, status, set->min_weight, set->skip_zero, set->align.huber_k, false, false, t);
+                        },
+                        [&](bool first) { align_launch_step(c, L, nf, set->align, first); }));
                     B.phase = kTrackLevelEnd; B.level_index = (int)k;
                     SEQ_TRY(track_launch_frames(c, B));
                 }
@@ -234,11 +195,11 @@ extern "C" emba_status emba_frames_track(emba_ctx* c, const uint8_t* frames, con
                 SEQ_TRY(track_launch_frames(c, B));
             }
             V.q = T.q_all.as<double>() + 4 * f0; V.status = T.status_all.as<int32_t>() + f0; V.frames = bytes;
-            hipLaunchKernelGGL(emba_frames_track_vote_kernel, dim3(nblocks(S, kTrackThreads), (unsigned)nf), dim3(kTrackThreads), 0, s, V);
+            hipLaunchKernelGGL(emba_frames_track_vote_kernel, dim3(nblocks(S, kFrameThreads), (unsigned)nf), dim3(kFrameThreads), 0, s, V);
             HIP_TRY(c, hipGetLastError());
             if (pm_out) {
                 HIP_TRY(c, hipStreamSynchronize(s));
-                SEQ_TRY(d2h_pageable(c, pm_out + 2 * f0 * S, T.pm.p, 2 * nf * S * sizeof(double)));
+                SEQ_TRY(d2h_pageable(c, pm_out + 2 * f0 * S, L.pm.p, 2 * nf * S * sizeof(double)));
             }
             f0 += nf;
         }
@@ -278,29 +239,18 @@ extern "C" emba_status emba_track_eval(emba_ctx* c, const uint8_t* frames, size_
     if (min_weight < 1) return fail(c, EMBA_ERR_INVALID_ARG, "min_weight = 0: a covered cell has a weight of 1 at the least");
     const size_t bad = align_first_bad_q(q_xyzw, F);
     if (bad < F) return fail(c, EMBA_ERR_INVALID_ARG, "q_xyzw[%zu] is not finite or has zero norm", bad);
-    TrackBuffers& T = c->track;
-    if (!(T.voted >> level & 1u)) return fail(c, EMBA_ERR_STATE, "level %d was not voted into by the last emba_frames_track", (int)level);
+    if (!(c->track.voted >> level & 1u)) return fail(c, EMBA_ERR_STATE, "level %d was not voted into by the last emba_frames_track", (int)level);
     if (!F) return EMBA_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+    FrameLoopBuffers& T = c->track.loop;
     const TrackPlane plane = track_plane(c, level);
-    const size_t S = c->S, per = view_chunk_frames(S, 1), chunks = view_chunk_count(F, per);
-    SEQ_TRY(ensure<uint8_t>(c, T.frames, std::min(per, F) * S));
-    SEQ_TRY(track_ensure_batch(c, std::min(per, F), pm_out != nullptr, resid_out != nullptr, false));
-    for (size_t i = 0; i < chunks; ++i) {
-        const ViewChunk ch = view_chunk(F, per, i);
-        const size_t cells = ch.nf * S, off = ch.f0 * S;
-        HIP_TRY(c, hipMemcpyAsync(T.frames.p, frames + off, cells, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(T.q_trial.p, q_xyzw + 4 * ch.f0, 4 * ch.nf * sizeof(double), hipMemcpyHostToDevice, s));
-        SEQ_TRY(track_launch_eval(c, plane, T.frames.as<uint8_t>(), ch.nf, nullptr, min_weight, skip_zero, huber_k, pm_out != nullptr, resid_out != nullptr,
-                                  c->kernel_timing && i == 0));
-        HIP_TRY(c, hipStreamSynchronize(s));      // (the chunk's bytes have been read: the next chunk overwrites them)
-        if (sums_out) SEQ_TRY(d2h_pageable(c, sums_out + (size_t)kAlignSums * ch.f0, T.esums.p, (size_t)kAlignSums * ch.nf * sizeof(double)));
-        if (counts_out) SEQ_TRY(d2h_pageable(c, counts_out + 4 * ch.f0, T.ecounts.p, 4 * ch.nf * sizeof(uint64_t)));
-        if (pm_out) SEQ_TRY(d2h_pageable(c, pm_out + 2 * off, T.pm.p, 2 * cells * sizeof(double)));
-        if (resid_out) SEQ_TRY(d2h_pageable(c, resid_out + off, T.resid.p, cells * sizeof(double)));
-    }
-    return EMBA_OK;
+    SEQ_TRY(frame_ensure(c, T, kAlignSums, std::min(view_chunk_frames(c->S, 1), F), pm_out != nullptr, resid_out != nullptr, false));
+    return frame_eval_chunks(
+        c, T, kAlignSums, frames, q_xyzw, F, [](const ViewChunk&) { return EMBA_OK; },
+        [&](size_t nf, bool timed) {
+            return track_launch_eval(c, plane, T.frames.as<uint8_t>(), nf, nullptr, min_weight, skip_zero, huber_k, pm_out != nullptr, resid_out != nullptr, timed);
+        },
+        sums_out, counts_out, pm_out, resid_out);
 }
 
 extern "C" emba_status emba_track_level_get(emba_ctx* c, int32_t level, uint64_t* sum_w_out, uint64_t* sum_v_out)

@@ -1,13 +1,13 @@
 // emba_amd/csrc/track_kernels.h — intensity frames tracked against their own growing mosaic (gfx950, wave64): a frame's normal equations against a level's
 // two integer sums, the vote of the tracked frames into every level, and the per-frame bookkeeping between them.
-// The rules: track_rule.h, align_rule.h, mosaic_rule.h, panorama_rule.h (pano_vote), include/emba_hip.h (emba_frames_track, emba_track_eval), DESIGN.md §21.
-//   * emba_frames_track_eval_kernel    emba_frames_align_eval_kernel with the level's camera and the plane read from the two sums: one lane per frame pixel,
-//                                      the frame in blockIdx.y; the warp once at level 0, pm and J23 scaled by 2^-l; track_pixel forms the four means in
-//                                      registers; the same shuffle butterfly, the same wave-order sum in LDS, the same partial[frame][workgroup][12].  The
-//                                      reduce and step kernels behind it are align_kernels.h's, as they are
+// The rules: track_rule.h, align_rule.h, mosaic_rule.h, panorama_rule.h (pano_vote), include/emba_hip.h (emba_frames_track, emba_track_eval), DESIGN.md §21;
+// the bodies: frame_kernels.h.
+//   * emba_frames_track_eval_kernel    frame_eval_body with track_pixel: the warp once at level 0, pm and J23 scaled by 2^-l; track_pixel forms the four
+//                                      means of the level's two sums in registers; ten sums, partial[frame][workgroup][12].  The reduce and step kernels
+//                                      behind it are align_kernels.h's, as they are
 //   * emba_frames_track_vote_kernel    one lane per frame pixel, the frame in blockIdx.y; a frame that is neither tracked nor the anchor leaves at once (and
-//                                      fills its pm with NaN); the warp once, then per plane pano_vote on the level's grid and two return-less 64-bit integer
-//                                      atomic adds per cell; a wave's dropped votes and skipped pixels go up in one atomic each
+//                                      fills its pm with NaN); frame_warp once, then per plane pano_vote on the level's grid and frame_vote_cells;
+//                                      frame_vote_counters
 //   * emba_frames_track_frame_kernel   one lane per frame of a batch, by phase: the anchor; the prediction from the last two tracked frames (found by walking
 //                                      the statuses back from the batch's first frame); the end of a level (its iterations, the next level's start); the
 //                                      verdict.  Batches follow each other on the stream without the host reading a pose
@@ -17,12 +17,10 @@
 #include <stdint.h>
 
 #include "align_kernels.h"
-#include "device_math.h"
+#include "frame_kernels.h"
 #include "track_rule.h"
 
 namespace emba {
-
-constexpr int kTrackThreads = kAlignThreads;
 
 struct TrackEvalParams {
     const double* lut;                    // bearing vector per sensor pixel [S, 3]
@@ -37,69 +35,32 @@ struct TrackEvalParams {
     unsigned long long min_weight;
     double huber_k;
     int skip_zero;
-    double* partial;                      // [nf, gridDim.x, kAlignPartial]
+    double* partial;                      // [nf, gridDim.x, frame_partial(kAlignSums)]
     double* pm;                           // [nf, S, 2] or nullptr: the level's pm
     double* resid;                        // [nf, S] or nullptr
 };
 
 // Compiled without contraction: pm feeds floor(), and r is compared by its bits.
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(kTrackThreads) void emba_frames_track_eval_kernel(TrackEvalParams p)
-{
-    __shared__ double red[kAlignWaves][kAlignSums];
-    __shared__ unsigned int redc[kAlignWaves][4];
-    const size_t f = blockIdx.y;
-    if (p.status && p.status[f] != EMBA_ALIGN_RUNNING) return;      // (the whole workgroup: f is blockIdx.y)
-    const int s = (int)blockIdx.x * kTrackThreads + (int)threadIdx.x;
-    double acc[kAlignSums];
-    unsigned int cnt[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < kAlignSums; ++k) acc[k] = 0.0;
-    if (s < p.S) {
-        const size_t o = f * (size_t)p.S + (size_t)s;
-        const unsigned int v = p.frames[o];
-        const double* Q = p.q + 4 * f;      // wave-uniform
-        const double q[4] = {Q[0], Q[1], Q[2], Q[3]};
-        double R[9];
-        quat_to_matrix(q, R);
-        const double* bv = p.lut + 3 * (size_t)s;
-        const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
-        double rb[3], pm[2], J23[6];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
-        project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
+// the pixel rule of frame_eval_body: ten sums, pm and J23 on the level's grid, track_pixel on the level's two sums
+struct TrackEvalRule {
+    static constexpr int kSums = kAlignSums;
+    using Term = AlignTerm;
+    static __device__ __forceinline__ void level(const TrackEvalParams& p, double* pm, double* J23)
+    {
         pm[0] *= p.scale; pm[1] *= p.scale;      // (a power of two: exact)
 #pragma unroll
         for (int j = 0; j < 6; ++j) J23[j] *= p.scale;
-        if (p.pm) { p.pm[2 * o] = pm[0]; p.pm[2 * o + 1] = pm[1]; }
-        AlignTerm t;
-        const int cls = track_pixel(reinterpret_cast<const uint64_t*>(p.sum_w), reinterpret_cast<const uint64_t*>(p.sum_v), p.W, p.H, pm[0], pm[1], J23, v,
-                                    (uint64_t)p.min_weight, p.skip_zero != 0, p.huber_k, &t);
-        if (p.resid) p.resid[o] = t.r;
-        if (cls == kAlignUsed) align_accumulate(t, acc);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cnt[k] = cls == k ? 1u : 0u;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kAlignSums; ++k) acc[k] += __shfl_xor(acc[k], o);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cnt[k] += __shfl_xor(cnt[k], o);
+    static __device__ __forceinline__ int pixel(const TrackEvalParams& p, size_t, const double* pm, const double* J23, unsigned int v, AlignTerm* t)
+    {
+        return track_pixel(reinterpret_cast<const uint64_t*>(p.sum_w), reinterpret_cast<const uint64_t*>(p.sum_v), p.W, p.H, pm[0], pm[1], J23, v,
+                           (uint64_t)p.min_weight, p.skip_zero != 0, p.huber_k, t);
     }
-    const int wave = (int)threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kAlignSums; ++k) red[wave][k] = acc[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) redc[wave][k] = cnt[k];
-    }
-    __syncthreads();
-    double* out = p.partial + (f * (size_t)gridDim.x + (size_t)blockIdx.x) * (size_t)kAlignPartial;
-    const int k = (int)threadIdx.x;
-    if (k < kAlignSums) out[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    else if (k < kAlignSums + 4) reinterpret_cast<unsigned int*>(out + kAlignSums)[k - kAlignSums] = ((redc[0][k - kAlignSums] + redc[1][k - kAlignSums]) + redc[2][k - kAlignSums]) + redc[3][k - kAlignSums];
-}
+    static __device__ __forceinline__ void accumulate(const AlignTerm& t, double* acc) { align_accumulate(t, acc); }
+};
+
+__global__ __launch_bounds__(kFrameThreads) void emba_frames_track_eval_kernel(TrackEvalParams p) { frame_eval_body<TrackEvalRule>(p); }
 
 struct TrackPlane { unsigned long long *sum_w, *sum_v; int W, H; double scale; };
 struct TrackVoteParams {
@@ -115,9 +76,9 @@ struct TrackVoteParams {
     TrackPlane plane[kTrackMaxPlanes];
 };
 
-__global__ __launch_bounds__(kTrackThreads) void emba_frames_track_vote_kernel(TrackVoteParams p)
+__global__ __launch_bounds__(kFrameThreads) void emba_frames_track_vote_kernel(TrackVoteParams p)
 {
-    const int s = (int)blockIdx.x * kTrackThreads + (int)threadIdx.x;
+    const int s = (int)blockIdx.x * kFrameThreads + (int)threadIdx.x;
     const size_t f = blockIdx.y;
     if (!track_votes(p.status[f])) {      // (the whole workgroup)
         if (p.pm && s < p.S) { const size_t o = f * (size_t)p.S + (size_t)s; p.pm[2 * o] = p.pm[2 * o + 1] = __builtin_nan(""); }
@@ -127,39 +88,19 @@ __global__ __launch_bounds__(kTrackThreads) void emba_frames_track_vote_kernel(T
     if (s < p.S) {
         const size_t o = f * (size_t)p.S + (size_t)s;
         const unsigned int v = p.frames[o];
-        const double* Q = p.q + 4 * f;      // wave-uniform
-        const double q[4] = {Q[0], Q[1], Q[2], Q[3]};
-        double R[9];
-        quat_to_matrix(q, R);
-        const double* bv = p.lut + 3 * (size_t)s;
-        const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
-        double rb[3], pm[2], J23[6];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
-        project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
+        double pm[2], J23[6];
+        frame_warp(p.lut, p.q + 4 * f, s, p.fx, p.fy, p.cx, p.cy, pm, J23);
         if (p.pm) { p.pm[2 * o] = pm[0]; p.pm[2 * o + 1] = pm[1]; }
         if (p.skip_zero && v == 0) skipped = 1;
         else {
 #pragma unroll 1
             for (int l = 0; l < p.n_planes; ++l) {
                 const TrackPlane& L = p.plane[l];      // (uniform: read from the kernel's arguments)
-                const PanoVotes pv = pano_vote(pm[0] * L.scale, pm[1] * L.scale, L.W, L.H);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (!pv.w[k]) continue;
-                    if (pv.cell[k] < 0) { ++dropped; continue; }
-                    atomicAdd(L.sum_w + pv.cell[k], (unsigned long long)pv.w[k]);                          // (results unused: return-less adds)
-                    if (v) atomicAdd(L.sum_v + pv.cell[k], (unsigned long long)pv.w[k] * (unsigned long long)v);
-                }
+                frame_vote_cells(pano_vote(pm[0] * L.scale, pm[1] * L.scale, L.W, L.H), v, L.sum_w, L.sum_v, dropped);
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { dropped += __shfl_xor(dropped, o); skipped += __shfl_xor(skipped, o); }
-    if ((threadIdx.x & 63) == 0) {
-        if (dropped) atomicAdd(p.counters, (unsigned long long)dropped);
-        if (skipped) atomicAdd(p.counters + 1, (unsigned long long)skipped);
-    }
+    frame_vote_counters(dropped, skipped, p.counters);
 }
 #pragma clang fp contract(fast)
 

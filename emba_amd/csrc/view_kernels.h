@@ -2,8 +2,9 @@
 // panorama plane, and what it reported between two frame times, counted from the resident event sequence.
 // The rules: view_rule.h, include/emba_hip.h (emba_render_views, emba_seq_event_frames), DESIGN.md §17.
 //   * pose stage                 the rotations at the F frame times: emba_pose_kernel (kernels.h) as it is, into the pose table of view_host.h
-//   * emba_view_kernel           one lane per sensor pixel, the frame in blockIdx.y: the bearing turned by the frame's rotation (the sum3 products of
-//                                seq_event_warp), pm by project_chain<false> (the Jacobian is dead code), view_sample's four gathers, view_u8
+//   * emba_view_kernel           one lane per sensor pixel, the frame in blockIdx.y: frame_warp (frame_kernels.h, DESIGN.md §23: the bearing turned by the
+//                                frame's rotation, the sum3 products of seq_event_warp, pm by project_chain<false>; the Jacobian is dead code),
+//                                view_sample's four gathers, view_u8
 //   * emba_event_frames_kernel   one lane per event: view_frame_of (a binary search over the edges) and one return-less int32 atomic add into the frame's
 //                                pixel in HBM
 // The view kernel streams: 24 B of LUT in and 8 B (+ 1) out per pixel, coalesced; the frame's pose record sits at a wave-uniform address, and the four
@@ -13,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "device_math.h"
+#include "frame_kernels.h"
 #include "kernels.h"      // kPoseStride, emba_pose_kernel
 #include "view_rule.h"
 
@@ -42,16 +43,8 @@ __global__ __launch_bounds__(kViewThreads) void emba_view_kernel(ViewParams p)
     const size_t f = blockIdx.y;
     unsigned int out = 0;
     if (s < p.S) {
-        const double* P = p.pose + (size_t)kPoseStride * f;      // wave-uniform
-        const double q[4] = {P[0], P[1], P[2], P[3]};
-        double R[9];
-        quat_to_matrix(q, R);
-        const double* bv = p.lut + 3 * (size_t)s;
-        const double b0 = bv[0], b1 = bv[1], b2 = bv[2];
-        double rb[3], pm[2], J23[6];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) rb[r] = sum3(R[3 * r] * b0, R[3 * r + 1] * b1, R[3 * r + 2] * b2);
-        project_chain<false>(rb, p.fx, p.fy, p.cx, p.cy, pm, J23);
+        double pm[2], J23[6];
+        frame_warp(p.lut, p.pose + (size_t)kPoseStride * f, s, p.fx, p.fy, p.cx, p.cy, pm, J23);
         const size_t o = f * (size_t)p.S + (size_t)s;
         if (p.pm) { p.pm[2 * o] = pm[0]; p.pm[2 * o + 1] = pm[1]; }
         double v;
