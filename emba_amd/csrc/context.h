@@ -271,9 +271,12 @@ struct AlignBuffers { DevBuf plane, valid; FrameLoopBuffers loop; };
 // between calls (level 0's are the mosaic's sum_w, sum_v); voted: bit l is set when the last successful emba_frames_track voted into level l.  Scratch of one
 // call, over its F frames: the frame times, every frame's rotation, status, iterations per level, cost, counts and overlap; counters: [0] dropped votes,
 // [1] skipped pixels.  Over one batch (or one chunk of emba_track_eval): pred, the predicted starts, and the loop's state; loop.frames: one chunk of bytes.
+// The tracker with exposure (track_exposure_host.h) keeps beside them every frame's gain and bias (gain_all, bias_all) and, over one batch, the start, the
+// trial and the accepted gain and bias (gain_pred / gain_trial / gain, and the same three of the bias).
 struct TrackBuffers {
     DevBuf lw[8], lv[8]; uint32_t voted = 0;
     DevBuf t, q_all, status_all, iters_all, cost_all, overlap_all, counts_all, counters, pred;
+    DevBuf gain_all, bias_all, gain_pred, bias_pred, gain_trial, bias_trial, gain, bias;
     FrameLoopBuffers loop;
 };
 

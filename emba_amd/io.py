@@ -1654,6 +1654,136 @@ def track_frames(frames_u8, frame_t_ns, lut, pano_w, pano_h, q0=(0.0, 0.0, 0.0, 
     return out
 
 
+# ---- the frame tracker with a per-frame exposure (numpy forms of emba_frames_track_exposure and emba_track_exposure_eval, include/emba_hip.h; the device
+# forms are LEGM.track_frames_exposure and LEGM.track_exposure_eval).  The rule is emba_amd/csrc/track_exposure_rule.h's, over track_rule.h
+# and exposure_rule.h: given the same level-0 pm and the same (gain, bias) the level sums are the same integers; given the same sums and the same level pm the
+# classes are the same and the residuals have the same bits.
+def track_exposure_terms(frame_u8, pm_l, lut, q, sum_w, sum_v, gain=1.0, bias=0.0, min_weight=256, skip_zero=False, huber_k=0.0):
+    """track_terms with the frame's gain and bias (track_exposure_pixel, track_exposure_rule.h): the plane is mosaic_mean of the level's two sums, masked where
+    any of a pixel's four cells has sum_w < min_weight, I0 = v (byte units), r = val - (gain * I0 + bias).  exposure_terms' dict, I0 among it."""
+    mean, covered = mosaic_mean(sum_w, sum_v, min_weight, 0.0)
+    return exposure_terms(frame_u8, pm_l, lut, q, mean, gain, bias, covered, 0.0, 255.0, skip_zero, huber_k)
+
+
+def track_votes_exposure(frames_u8, pm, status, gain, bias, pano_w, pano_h, levels, skip_zero=False):
+    """track_votes of the compensated bytes: the frames whose status is TRACK_ANCHOR or TRACK_TRACKED vote exposure_bytes(v, gain[f], bias[f]) in the place of
+    v at pm * 2^-l on (W_l, H_l), for every level of track_vote_levels(levels); skip_zero tests the raw byte.  track_votes' dict."""
+    status = np.asarray(status).reshape(-1)
+    F = status.size
+    votes = (status == TRACK_ANCHOR) | (status == TRACK_TRACKED)
+    raw = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)[votes]
+    a, b = exposure_check(np.asarray(gain, dtype=np.float64).reshape(-1)[votes], np.asarray(bias, dtype=np.float64).reshape(-1)[votes], int(votes.sum()))
+    comp = exposure_bytes(raw, a, b).reshape(-1)
+    pm = np.asarray(pm, dtype=np.float64).reshape(F, -1, 2)[votes].reshape(-1, 2)
+    keep = (raw.reshape(-1) != 0) if skip_zero else np.ones(comp.size, bool)
+    planes, dropped = {}, 0
+    for l in track_vote_levels(levels):
+        Wl, Hl, _ = track_level_shape(pano_w, pano_h, l)
+        sw, sv, d, _ = mosaic_votes(comp[keep], track_level_pm(pm[keep], l), Wl, Hl, False)
+        planes[l] = (sw, sv)
+        dropped += d
+    return dict(planes=planes, dropped=dropped, skipped=int((~keep).sum()))
+
+
+def track_frames_exposure(frames_u8, frame_t_ns, lut, pano_w, pano_h, q0=(0.0, 0.0, 0.0, 1.0), levels=(0,), batch=1, predict=True, skip_zero=False,
+                          min_weight=256, min_overlap=0.5, estimate=3, gain_min=None, gain_max=None, **settings):
+    """The whole tracker of emba_frames_track_exposure in numpy, with numpy's own pm: track_frames with (a, b) beside every q.  Frame 0 is voted at
+    normalise(q0) with a = 1, b = 0; a later frame starts at track_predict's rotation and at the gain and bias of the last tracked frame in front of its
+    batch, is aligned level by level with align_frames_exposure's loop (exposure_sums of track_exposure_terms, exposure_step on the rows of `estimate`; every
+    level starts where the previous one ended) and, when tracked, votes its compensated bytes at every level.  A lost frame keeps its predicted rotation and
+    its start gain and bias.  track_frames' dict, and gain, bias [F]; `levels_degenerate`: the (frame, level) pairs that ended degenerate.  Batches are cut by
+    `batch` alone, as in track_frames."""
+    s = align_settings(**settings)
+    g_lo, g_hi = exposure_bounds(gain_min, gain_max)
+    estimate = int(estimate)
+    if not 0 <= estimate <= 3:
+        raise ValueError("estimate is a mask of EXPOSURE_GAIN and EXPOSURE_BIAS")
+    W, H = int(pano_w), int(pano_h)
+    ts = np.asarray(frame_t_ns, dtype=np.int64).reshape(-1)
+    F = ts.size
+    if (np.diff(ts) <= 0).any():
+        raise ValueError("the frame times must be strictly increasing")
+    if int(batch) < 1 or not 0.0 <= float(min_overlap) <= 1.0 or int(min_weight) < 1 or not 1 <= len(levels) <= 8:
+        raise ValueError("batch >= 1, 0 <= min_overlap <= 1, min_weight >= 1, 1 ... 8 levels")
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)
+    S = frames.shape[1]
+    shapes = {l: track_level_shape(W, H, l) for l in track_vote_levels(levels)}
+    planes = {l: (np.zeros((Hl, Wl), np.uint64), np.zeros((Hl, Wl), np.uint64)) for l, (Wl, Hl, _) in shapes.items()}
+    out = dict(q=np.zeros((F, 4)), gain=np.ones(F), bias=np.zeros(F), status=np.zeros(F, np.int32), iters=np.zeros((F, len(levels)), np.int32), cost=np.zeros(F),
+               overlap=np.zeros(F), counts=np.zeros((F, 4), np.int64), pm=np.full((F, S, 2), np.nan), planes=planes, levels_degenerate=[])
+
+    def vote(f):
+        pm = align_warp(lut, out["q"][f], W, H)[1]
+        out["pm"][f] = pm
+        comp = exposure_bytes(frames[f:f + 1], out["gain"][f:f + 1], out["bias"][f:f + 1]).reshape(-1)
+        keep = (frames[f] != 0) if skip_zero else np.ones(S, bool)
+        for l, (Wl, Hl, scale) in shapes.items():
+            sw, sv, _, _ = mosaic_votes(comp[keep], pm[keep] * scale, Wl, Hl, False)
+            planes[l][0][...] += sw
+            planes[l][1][...] += sv
+
+    def evaluate(f, q, a, b, l):
+        Wl, Hl, scale = shapes[l]
+        return exposure_sums(track_exposure_terms(frames[f], align_warp(lut, q, W, H)[1] * scale, lut, q, planes[l][0], planes[l][1], a, b, min_weight, skip_zero,
+                                                  s["huber_k"]))
+
+    def align_level(f, q, a, b, l):      # align_frames_exposure's loop for one frame against one level: (q, a, b, sums, counts, status, iters)
+        sums, counts = evaluate(f, q, a, b, l)
+        lam, iters = float(s["lambda0"]), 0
+        while True:
+            x = exposure_step(sums, lam, estimate) if counts[0] >= s["min_pixels"] else None
+            if x is None:
+                return q, a, b, sums, counts, ALIGN_DEGENERATE, iters
+            if iters >= s["max_iters"]:
+                return q, a, b, sums, counts, ALIGN_ITERATIONS, iters
+            trial, ta, tb = so3.mul(so3.exp(x[:3]), q), a + x[3], b + x[4]
+            tsums, tcounts = evaluate(f, trial, ta, tb, l)
+            iters += 1
+            take = tcounts[0] >= s["min_pixels"] and tsums[EXPOSURE_COST] / tcounts[0] < sums[EXPOSURE_COST] / counts[0]
+            if (estimate & EXPOSURE_GAIN) and not g_lo <= ta <= g_hi:
+                take = False
+            if take:
+                q, a, b, sums, counts = trial, ta, tb, tsums, tcounts
+                lam = max(lam / s["lambda_down"], s["lambda_min"])
+                if np.linalg.norm(x[:3]) < s["tol_rot"]:
+                    return q, a, b, sums, counts, ALIGN_CONVERGED, iters
+            else:
+                lam *= s["lambda_up"]
+                if lam > s["lambda_max"]:
+                    return q, a, b, sums, counts, ALIGN_STALLED, iters
+
+    if not F:
+        return out
+    out["q"][0], out["status"][0] = so3.normalize(np.asarray(q0, dtype=np.float64)), TRACK_ANCHOR
+    vote(0)
+    tracked = [0]
+    f0 = 1
+    while f0 < F:
+        nf = min(int(batch), F - f0)
+        tb_ = tracked[-1]
+        ta_ = tracked[-2] if len(tracked) > 1 else None
+        a0, b0 = float(out["gain"][tb_]), float(out["bias"][tb_])
+        for f in range(f0, f0 + nf):
+            pred = track_predict(None if ta_ is None else out["q"][ta_], None if ta_ is None else ts[ta_], out["q"][tb_], ts[tb_], ts[f], predict)
+            q, a, b = pred, a0, b0
+            for k, l in enumerate(levels):
+                q, a, b, sums, counts, status, out["iters"][f, k] = align_level(f, q, a, b, int(l))
+                if status == ALIGN_DEGENERATE:
+                    out["levels_degenerate"].append((f, int(l)))
+            denom = S - counts[3]
+            overlap = counts[0] / denom if denom > 0 else 0.0
+            ok = status != ALIGN_DEGENERATE and overlap >= float(min_overlap)
+            out["q"][f], out["status"][f] = (q if ok else pred), (TRACK_TRACKED if ok else TRACK_LOST)
+            out["gain"][f], out["bias"][f] = (a, b) if ok else (a0, b0)
+            out["cost"][f], out["overlap"][f], out["counts"][f] = sums[EXPOSURE_COST], overlap, counts
+        for f in range(f0, f0 + nf):
+            if out["status"][f] == TRACK_TRACKED:
+                vote(f)
+                tracked.append(f)
+        f0 += nf
+    return out
+
+
 def rotation_angle_between(qa, qb):
     """The angle (rad) of the rotation from qa to qb, quaternions xyzw [..., 4]."""
     qa, qb = np.asarray(qa, dtype=np.float64).reshape(-1, 4), np.asarray(qb, dtype=np.float64).reshape(-1, 4)

@@ -556,6 +556,58 @@ class LEGM:
         self._check(self._L.emba_track_level_get(self._ctx, level, _p(sum_w, u64p), _p(sum_v, u64p)))
         return sum_w, sum_v
 
+    def track_frames_exposure(self, frames, frame_t_ns, q0=(0.0, 0.0, 0.0, 1.0), levels=(0,), batch=1, predict=True, skip_zero=False, min_weight=256,
+                              min_overlap=0.5, estimate=3, gain_min=None, gain_max=None, want_pm=False, **settings):
+        """track_frames for the frames of a camera with auto-exposure (emba_frames_track_exposure; the rule: include/emba_hip.h): every frame carries a gain
+        and a bias beside its rotation, estimated with it at every level where `estimate` (io.EXPOSURE_GAIN | io.EXPOSURE_BIAS) says so, started at those of
+        the last tracked frame, and a tracked frame votes its compensated bytes; a trial whose estimated gain leaves [gain_min, gain_max]
+        (io.EXPOSURE_BOUNDS) is rejected.  estimate = 0 is track_frames.  track_frames' dict and gain, bias [F] (the anchor's: 1 and 0; a lost frame's: its
+        start).  io.track_frames_exposure is the same tracker in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        g_lo = float(emba_io.EXPOSURE_BOUNDS["gain_min"] if gain_min is None else gain_min)
+        g_hi = float(emba_io.EXPOSURE_BOUNDS["gain_max"] if gain_max is None else gain_max)
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        levels = [int(l) for l in levels]
+        if not 1 <= len(levels) <= 8:
+            raise ValueError("a schedule names 1 ... 8 levels")
+        q0 = np.ascontiguousarray(q0, dtype=np.float64).reshape(4)
+        ts_ = _lib.EmbaTrackSettings(len(levels), (C.c_int32 * 8)(*levels), int(batch), 1 if predict else 0, 1 if skip_zero else 0, int(min_weight), float(min_overlap),
+                                     _lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                                            float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]), float(s["huber_k"])))
+        cs = _lib.EmbaTrackExposureSettings(ts_, int(estimate), g_lo, g_hi)
+        q, gain, bias, status, iters = np.zeros((F, 4)), np.zeros(F), np.zeros(F), np.zeros(F, np.int32), np.zeros((F, len(levels)), np.int32)
+        cost, counts, overlap, stats = np.zeros(F), np.zeros((F, 4), np.uint64), np.zeros(F), np.zeros(4, np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_track_exposure(self._ctx, _p(frames, _u8p), _p(ts, _i64p), F, _p(q0, _dp), C.addressof(cs), _p(q, _dp), _p(gain, _dp),
+                                                       _p(bias, _dp), _p(status, _i32p), _p(iters, _i32p), _p(cost, _dp), _p(counts, u64p), _p(overlap, _dp),
+                                                       _p(stats, u64p), _p(pm, _dp)))
+        return dict(q=q, gain=gain, bias=bias, status=status, iters=iters, cost=cost, counts=counts.astype(np.int64), overlap=overlap, tracked=int(stats[0]),
+                    lost=int(stats[1]), dropped=int(stats[2]), skipped=int(stats[3]), pm=pm)
+
+    def track_exposure_eval(self, frames, q_xyzw, gain=None, bias=None, level=0, min_weight=256, skip_zero=False, huber_k=0.0, want_pm=False, want_resid=False):
+        """track_eval with a gain and a bias per frame (emba_track_exposure_eval): the residual is val - (gain[f] v + bias[f]) against the two integer sums of
+        `level` as the last tracker call left them.  A dict as exposure_eval's (sums [F, 21]); pm is the level's — io.track_exposure_terms and
+        io.exposure_sums given the same pm."""
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+        F, S = q.shape[0], self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        a, b = self._exposure_args(gain, bias, F)
+        sums, counts = np.zeros((F, 21)), np.zeros((F, 4), np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        resid = np.empty((F, S)) if want_resid else None
+        self._check(self._L.emba_track_exposure_eval(self._ctx, _p(frames, _u8p), F, _p(q, _dp), _p(a, _dp), _p(b, _dp), int(level), int(min_weight),
+                                                     1 if skip_zero else 0, float(huber_k), _p(sums, _dp), _p(counts, C.POINTER(C.c_uint64)), _p(pm, _dp),
+                                                     _p(resid, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), pm=pm, resid=resid)
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

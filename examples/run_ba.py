@@ -88,7 +88,7 @@ def frame_mosaic(legm, frames, t_ns, traj, skip_zero, exposure=None):
     return int(keep.sum())
 
 
-def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_zero, log=print, estimate=None):
+def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_zero, log=print, estimate=None, exposure0=None):
     """--refine-frames N: poses from frames.  Per round: the frames are stitched along the current raw trajectory, every frame is
     aligned to that mosaic's mean under its covered cells on the device, and io.fit_ctrl_poses of the aligned rotations at the frame times, merged with the
     raw poses outside the frames' span, becomes the raw trajectory.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the aligned
@@ -96,7 +96,8 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
     estimate (--frames-exposure bias / gain-bias: io.EXPOSURE_BIAS, or EXPOSURE_GAIN | EXPOSURE_BIAS): every frame carries a gain
     and a bias in byte units, 1 and 0 at the start.  Per round the frames are stitched with them, aligned with them estimated beside the rotation, and
     the common tone of the frames that did not end degenerate is fixed by io.exposure_gauge, before the trajectory is refitted.  The rows then end in the
-    gain and the bias, and a fifth value is returned: (gain, bias) for every frame of --frames, 1 and 0 for those the trajectory does not cover."""
+    gain and the bias, and a fifth value is returned: (gain, bias) for every frame of --frames, 1 and 0 for those the trajectory does not cover.
+    exposure0: (gain, bias) per frame of --frames that the rounds start from instead of 1 and 0 (--track-exposure: the tracker's)."""
     keep = (t_ns >= traj.t0_ns) & (t_ns < traj.t0_ns + traj.dt_ns * (traj.size() - 1))
     if not keep.any():
         raise SystemExit("--frames: no frame time lies inside the trajectory's knots")
@@ -104,6 +105,8 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
     t_beg, dt = traj.t0_ns * 1e-9, traj.dt_ns * 1e-9
     rows = []
     gain, bias = np.ones(len(ts)), np.zeros(len(ts))
+    if exposure0 is not None and estimate is not None:
+        gain, bias = np.array(exposure0[0][keep], dtype=np.float64), np.array(exposure0[1][keep], dtype=np.float64)
     for rnd in range(1, rounds + 1):
         q0 = np.array([traj.evaluate(int(tn)) for tn in ts])
         if estimate is None:
@@ -139,9 +142,13 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
     """--init-poses frames: poses from the frames alone.  The frames are tracked against their own growing mosaic on the device; the
     tracked frames' (t, q), sampled on a 5 ms grid over the span and held at both ends where the frames do not reach them, are the raw poses, and
     io.fit_ctrl_poses of them the trajectory.
-    Lost frames are left out.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the rotation, the status, the overlap and the cost."""
-    r = legm.track_frames(frames, t_ns, q0=a.track_q0, levels=a.track_levels, batch=a.track_batch, predict=bool(a.track_predict), skip_zero=a.frames_skip_zero,
-                          min_overlap=a.track_min_overlap, huber_k=a.frames_huber)
+    Lost frames are left out.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the rotation, the status, the overlap and the cost.
+    --track-exposure bias / gain-bias: every frame carries a gain and a bias in byte units, estimated with its rotation, and votes its
+    compensated bytes; the rows then end in the gain and the bias."""
+    kw = dict(q0=a.track_q0, levels=a.track_levels, batch=a.track_batch, predict=bool(a.track_predict), skip_zero=a.frames_skip_zero,
+              min_overlap=a.track_min_overlap, huber_k=a.frames_huber)
+    estimate = {"none": None, "bias": eio.EXPOSURE_BIAS, "gain-bias": eio.EXPOSURE_GAIN | eio.EXPOSURE_BIAS}[a.track_exposure]
+    r = legm.track_frames(frames, t_ns, **kw) if estimate is None else legm.track_frames_exposure(frames, t_ns, estimate=estimate, **kw)
     ok = r["status"] != eio.TRACK_LOST
     tf, qf = t_ns[ok] * 1e-9, r["q"][ok]
     # the raw poses a sliding-window run reads: the tracked rotations on a 5 ms grid over the trajectory's span (io.pose_at: interpolated between tracked
@@ -154,6 +161,10 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
         f"overlap >= {r['overlap'][1:].min() if len(t_ns) > 1 else 0.0:.3f}, up to {int(r['iters'].max()) if r['iters'].size else 0} trials per level, "
         f"{r['dropped']} votes dropped, {r['skipped']} pixels skipped")
     rows = [(int(tn), q, int(st), float(ov), float(c)) for tn, q, st, ov, c in zip(t_ns, r["q"], r["status"], r["overlap"], r["cost"])]
+    if estimate is not None:
+        log(f"track-exposure {a.track_exposure}: gain {r['gain'].min():.4f} ... {r['gain'].max():.4f}, bias {r['bias'].min():.3f} ... {r['bias'].max():.3f} bytes "
+            f"(the anchor's tone is the gauge: gain 1, bias 0)")
+        rows = [row + (float(g), float(o)) for row, g, o in zip(rows, r["gain"], r["bias"])]
     return traj, t_raw, q_raw, rows
 
 
@@ -278,6 +289,10 @@ def main():
     ap.add_argument("--track-predict", type=int, default=1, choices=[0, 1], help="--init-poses frames: start a frame from the last two tracked frames' angular velocity")
     ap.add_argument("--track-min-overlap", type=float, default=0.3, metavar="X", help="--init-poses frames: a frame whose used pixels fall below this share is lost")
     ap.add_argument("--track-q0", default="0,0,0,1", metavar="x,y,z,w", help="--init-poses frames: the rotation of the first frame")
+    ap.add_argument("--track-exposure", choices=("none", "bias", "gain-bias"), default="none", help="--init-poses frames: a bias, or a gain and a bias, per frame "
+                    "estimated with its rotation inside the tracker, for frames of a camera with auto-exposure; the tracked frames vote their compensated bytes, "
+                    "--init-map frames and frame_mosaic.pgm use them, and --refine-frames N --frames-exposure X starts from them (DESIGN.md section 24; "
+                    "frames_tracked.txt gains the columns gain and bias)")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
     ap.add_argument("--record-contrast", action="store_true", help="print, per window, the contrast J = sum I^2 of the panorama of the window's warped events at its "
@@ -323,6 +338,8 @@ def main():
                  "whose trajectory at that point carries the timing only")
     if a.refine_frames < 0 or (a.refine_frames and not a.frames):
         ap.error("--refine-frames N (N >= 0) aligns the frames of --frames DIR")
+    if a.track_exposure != "none" and a.init_poses != "frames":
+        ap.error("--track-exposure estimates the exposure inside the tracker of --init-poses frames: it needs --init-poses frames")
     if a.frames_exposure != "none" and not a.refine_frames:
         ap.error("--frames-exposure estimates the exposure in the rounds of --refine-frames N: it needs N >= 1")
     if a.refine_frames and a.init_poses not in ("given", "frames"):
@@ -445,14 +462,19 @@ def main():
         tracked_mosaic = True
         if rank == 0:
             with open(os.path.join(a.out, "frames_tracked.txt"), "w") as fh:
-                fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost\n")
-                for tn, q, st, ov, cost in rows:
-                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {ov:.9g} {cost:.9g}\n")
-    frames_exposure = None      # (gain, bias) per frame of --frames, once --frames-exposure has estimated them
+                fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost" + (" gain bias[bytes]" if a.track_exposure != "none" else "") + "\n")
+                for row in rows:
+                    tn, q, st, ov, cost = row[:5]
+                    more = "".join(f" {v:.17g}" for v in row[5:])
+                    fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {ov:.9g} {cost:.9g}{more}\n")
+    frames_exposure = None      # (gain, bias) per frame of --frames, once --track-exposure or --frames-exposure has estimated them
+    if a.init_poses == "frames" and a.track_exposure != "none":
+        frames_exposure = (np.array([row[5] for row in rows]), np.array([row[6] for row in rows]))
     exposure_estimate = {"none": None, "bias": eio.EXPOSURE_BIAS, "gain-bias": eio.EXPOSURE_GAIN | eio.EXPOSURE_BIAS}[a.frames_exposure]
     if a.refine_frames:      # poses from frames: the raw trajectory is refitted to the frames' aligned rotations before anything else reads it
         refined = refine_frames(legm, frames, frames_t_ns, traj, np.asarray(t, dtype=np.float64), np.asarray(qs, dtype=np.float64), a.refine_frames,
-                                a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None), estimate=exposure_estimate)
+                                a.frames_huber, a.frames_skip_zero, log=print if rank == 0 else (lambda *_: None), estimate=exposure_estimate,
+                                exposure0=frames_exposure)
         traj, t, qs, rows = refined[:4]
         if exposure_estimate is not None:
             frames_exposure = refined[4]

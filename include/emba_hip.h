@@ -796,6 +796,51 @@ emba_status emba_mosaic_frames_exposure(emba_ctx* ctx, const uint8_t* frames /* 
                                         const double* bias /* [F] */, const double* knots_xyzw, int32_t K, int64_t t0_ns, int64_t dt_ns, int32_t skip_zero,
                                         int32_t accumulate, uint64_t* dropped_out, uint64_t* skipped_out, double* pm_out /* [F, sh*sw, 2] or NULL */);
 
+/* ---- The frame tracker with a per-frame exposure: emba_frames_track for the frames of a camera with auto-exposure.  Frame f carries
+ * (q_f, a_f, b_f); gain and bias are estimated with the rotation at every level of the schedule, and every tracked frame votes its compensated bytes into
+ * every level plane.  The rule lives in emba_amd/csrc/track_exposure_rule.h, over track_rule.h and exposure_rule.h; emba_amd.io.track_exposure_terms /
+ * track_votes_exposure / track_frames_exposure are the same rule in numpy.  Everything that is not said here is emba_frames_track's.
+ *
+ *   pixel             emba_track_eval's pixel with the frame's gain and bias: the cell of pm_l, the mask on sum_w_l < min_weight, the four means formed in
+ *                     registers, the sample and its gradient, the precedence outside / masked / skipped (skipped tests the raw byte v).  Then I0 = v (the
+ *                     level planes are in byte units: lo = 0, hi = 255), r = val - (a * I0 + b): multiply, then add, without contraction; the Huber weight;
+ *                     g from the level's J23.  The Jacobian row of r is (g, -I0, -1), the 21 sums are emba_frames_exposure_eval's.  With a = 1, b = 0 every
+ *                     member of the term is emba_track_eval's bit for bit, and entries 0 1 2 5 6 9, 15 16 17 and 20 of the sums are its ten.
+ *   step              emba_frames_exposure_align's, as it is, on the active rows of settings.estimate: the gain bounds, the collinear test when both are
+ *                     estimated, converged on |delta| < tol_rot alone.  estimate = 0 is emba_frames_track: the same bits in every output and every plane.
+ *   anchor            frame 0 is voted at normalise(q0) with a = 1, b = 0.  It fixes the common tone: a frame aligned to a mosaic that the anchor started has
+ *                     no affine freedom left, so there is no gauge step inside the tracker.
+ *   start of a frame  the rotation as emba_frames_track predicts it; gain and bias those of the last tracked frame in front of the frame's batch (the anchor
+ *                     counts), whether predict is on or off: exposure is not extrapolated.
+ *   levels            (q, a, b) of a level start where the previous level ended; a level that ends degenerate leaves all three as they were.
+ *   verdict           emba_frames_track's.  A lost frame reports its predicted rotation and its start gain and bias, casts no vote, and is skipped by later
+ *                     frames for the rotation and for the exposure alike.
+ *   vote              a tracked frame votes clamp(rint(a_f * v + b_f), 0, 255) (emba_mosaic_frames_exposure's compensated byte) in the place of v into every
+ *                     plane emba_frames_track votes into; skip_zero tests the raw byte.  The integer sums keep their units and their 2^36 bound:
+ *                     emba_mosaic_get, emba_mosaic_map, use_mosaic, emba_track_level_get and emba_track_eval read them as they stand.
+ *
+ * emba_frames_track_exposure: emba_frames_track with settings.estimate and the two bounds of the gain; gain_out, bias_out [F] beside q_out (the anchor's are 1
+ * and 0); cost_out is entry 20 of the last level's sums.  emba_track_exposure_eval: emba_track_eval with gain [F] and bias [F]; sums_out [F, 21].  Both read
+ * and write the level planes emba_frames_track does: either tracker's planes serve either evaluation.
+ * Refusals: emba_frames_track_exposure refuses what emba_frames_track refuses, then gain bounds that are not finite or not 0 < gain_min <= 1 <= gain_max, then
+ * an estimate outside 0 ... 3; emba_track_exposure_eval refuses what emba_track_eval refuses, and gain or bias NULL with F > 0, a gain or bias that is not
+ * finite, a gain <= 0; EMBA_ERR_STATE at a level that the last successful tracker call did not vote into.  Refusals are decided before anything is zeroed
+ * and leave every output, the mosaic and the level planes untouched.  Chunks, batches, stats_out, pm_out and timer slot 7 are emba_frames_track's. */
+typedef struct {
+    emba_track_settings track;
+    int32_t estimate;
+    double gain_min, gain_max;
+} emba_track_exposure_settings;
+emba_status emba_frames_track_exposure(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, const int64_t* frame_t_ns /* [F] */, size_t F,
+                                       const double* q0_xyzw /* [4] */, const emba_track_exposure_settings* settings, double* q_out /* [F, 4] */,
+                                       double* gain_out /* [F] */, double* bias_out /* [F] */, int32_t* status_out /* [F] */, int32_t* iters_out /* [F, n_levels] */,
+                                       double* cost_out /* [F] */, uint64_t* counts_out /* [F, 4] */, double* overlap_out /* [F] */, uint64_t* stats_out /* [4] */,
+                                       double* pm_out /* [F, sh*sw, 2] */);
+emba_status emba_track_exposure_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                                     const double* gain /* [F] */, const double* bias /* [F] */, int32_t level, uint64_t min_weight, int32_t skip_zero, double huber_k,
+                                     double* sums_out /* [F, 21] */, uint64_t* counts_out /* [F, 4] */, double* pm_out /* [F, sh*sw, 2] */,
+                                     double* resid_out /* [F, sh*sw] */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
