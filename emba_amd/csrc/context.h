@@ -272,11 +272,13 @@ struct AlignBuffers { DevBuf plane, valid; FrameLoopBuffers loop; };
 // call, over its F frames: the frame times, every frame's rotation, status, iterations per level, cost, counts and overlap; counters: [0] dropped votes,
 // [1] skipped pixels.  Over one batch (or one chunk of emba_track_eval): pred, the predicted starts, and the loop's state; loop.frames: one chunk of bytes.
 // The tracker with exposure (track_exposure_host.h) keeps beside them every frame's gain and bias (gain_all, bias_all) and, over one batch, the start, the
-// trial and the accepted gain and bias (gain_pred / gain_trial / gain, and the same three of the bias).
+// trial and the accepted gain and bias (gain_pred / gain_trial / gain, and the same three of the bias).  The refit (refit_host.h) keeps beside them every
+// frame's code of the sweep (refit_all).
 struct TrackBuffers {
     DevBuf lw[8], lv[8]; uint32_t voted = 0;
     DevBuf t, q_all, status_all, iters_all, cost_all, overlap_all, counts_all, counters, pred;
     DevBuf gain_all, bias_all, gain_pred, bias_pred, gain_trial, bias_trial, gain, bias;
+    DevBuf refit_all;
     FrameLoopBuffers loop;
 };
 

@@ -70,8 +70,16 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # sequence is resident, else io.event_frames).  0: off.
     views_hz: float = 0.0
     view_events: bool = False
+    # Raw poses that come from tracked intensity frames (LEGM.track_frames / track_frames_exposure in front of run_sequence) are refitted first: track_refit
+    # sweeps of LEGM.refit_frames — every frame taken out of the integer mosaic, aligned to the mosaic of the other frames and voted back (the rule:
+    # include/emba_hip.h, emba_frames_refit) — ended early behind a sweep whose largest rotation change is below track_refit_tol (rad; 0:
+    # never).  refit_tracked_frames below applies them.  0: off.
+    track_refit: int = 0
+    track_refit_tol: float = 0.0
 
     def __post_init__(self):
+        if int(self.track_refit) < 0 or not float(self.track_refit_tol) >= 0.0:
+            raise ValueError(f"SequenceSettings.track_refit = {self.track_refit}, track_refit_tol = {self.track_refit_tol}: sweeps and a tolerance, neither negative")
         if not (np.isfinite(self.views_hz) and self.views_hz >= 0):
             raise ValueError(f"SequenceSettings.views_hz = {self.views_hz}: frames per second, finite and not negative (0: off)")
         if self.init_poses not in ("given", "events"):
@@ -85,6 +93,22 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
             raise ValueError(f"SequenceSettings.cmax_slice_events = {self.cmax_slice_events}: a slice has at least one event")
         if not (np.isfinite(self.cmax_omega_max) and self.cmax_omega_max > 0):
             raise ValueError("SequenceSettings.cmax_omega_max must be finite and positive")
+
+
+def refit_tracked_frames(model, frames, frame_t_ns, tracked, seq, **track_kw):
+    """`tracked`: what model.track_frames or model.track_frames_exposure returned for these frames under the tracker settings track_kw (levels, batch,
+    skip_zero, min_weight, min_overlap, estimate, the gain bounds, the members of io.ALIGN_DEFAULTS; q0 and predict are the tracker's alone).  With
+    seq.track_refit sweeps it is refitted on the device (LEGM.refit_frames) and the tracker's dict comes back with q, gain, bias, status, iters, cost, counts,
+    overlap and the four stats as the refit left them, and `refit` (io.REFIT_* per frame), `sweep` and `sweeps_done` beside them; the mosaic in the context
+    is the refitted one.  With track_refit = 0 `tracked` is returned as it is."""
+    if not seq.track_refit:
+        return tracked
+    kw = {k: v for k, v in track_kw.items() if k not in ("q0", "predict", "want_pm")}
+    r = model.refit_frames(frames, frame_t_ns, tracked["q"], tracked["status"], tracked.get("gain"), tracked.get("bias"), sweeps=int(seq.track_refit),
+                           sweep_tol=float(seq.track_refit_tol), **kw)
+    out = dict(tracked)
+    out.update({k: v for k, v in r.items() if k != "pm"})
+    return out
 
 
 @dataclass

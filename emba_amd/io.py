@@ -1784,6 +1784,188 @@ def track_frames_exposure(frames_u8, frame_t_ns, lut, pano_w, pano_h, q0=(0.0, 0
     return out
 
 
+# ---- tracked frames refitted against the mosaic of the other frames (the numpy form of emba_frames_refit, include/emba_hip.h; the device form is
+# LEGM.refit_frames).  The rule is emba_amd/csrc/refit_rule.h's, over the trackers': the level sums are unsigned 64-bit integers, a frame's
+# votes leave them by subtraction modulo 2^64, and given the device's pm and (gain, bias) track_votes_exposure gives the device's integers.
+REFIT_ANCHOR, REFIT_MOVED, REFIT_KEPT, REFIT_RECOVERED, REFIT_LOST = 1, 2, 3, 4, 5      # EMBA_REFIT_*
+REFIT_NAMES = {0: "-", 1: "anchor", 2: "moved", 3: "kept", 4: "recovered", 5: "lost"}
+
+
+def refit_batches(F, batch):
+    """The batches of F frames as the trackers cut them (track_batch_frames without the chunk edges): frame 0 alone, then `batch` frames each: [(f0, nf)]."""
+    out, f0 = [], 0
+    while f0 < F:
+        nf = 1 if f0 == 0 else min(int(batch), F - f0)
+        out.append((f0, nf))
+        f0 += nf
+    return out
+
+
+def refit_start(status, ts, q, gain, bias, f):
+    """refit_start (refit_rule.h): where frame f starts — a voting frame at its own (q, a, b); a lost frame from the nearest voting frames a < f < b by
+    index: track_predict's formula at t_f (its factor is negative: an interpolation) with gain and bias linear in the same factor, or the values of the
+    one neighbour there is.  (q, a, b), or None where no frame votes."""
+    status = np.asarray(status).reshape(-1)
+    votes = (status == TRACK_ANCHOR) | (status == TRACK_TRACKED)
+    if votes[f]:
+        return np.array(q[f], dtype=np.float64), float(gain[f]), float(bias[f])
+    before, after = np.flatnonzero(votes[:f]), f + 1 + np.flatnonzero(votes[f + 1:])
+    if not before.size and not after.size:
+        return None
+    if not before.size or not after.size:
+        o = int(after[0] if not before.size else before[-1])
+        return np.array(q[o], dtype=np.float64), float(gain[o]), float(bias[o])
+    a, b = int(before[-1]), int(after[0])
+    u = float(int(ts[f]) - int(ts[b])) / float(int(ts[b]) - int(ts[a]))
+    return track_predict(q[a], ts[a], q[b], ts[b], ts[f], True), float(gain[b] + (gain[b] - gain[a]) * u), float(bias[b] + (bias[b] - bias[a]) * u)
+
+
+def _exposure_align_level(evaluate, q, a, b, s, estimate, g_lo, g_hi):
+    """align_frames_exposure's loop for one frame against one level (track_frames_exposure runs the same): (q, a, b, sums, counts, status, iters)."""
+    sums, counts = evaluate(q, a, b)
+    lam, iters = float(s["lambda0"]), 0
+    while True:
+        x = exposure_step(sums, lam, estimate) if counts[0] >= s["min_pixels"] else None
+        if x is None:
+            return q, a, b, sums, counts, ALIGN_DEGENERATE, iters
+        if iters >= s["max_iters"]:
+            return q, a, b, sums, counts, ALIGN_ITERATIONS, iters
+        trial, ta, tb = so3.mul(so3.exp(x[:3]), q), a + x[3], b + x[4]
+        tsums, tcounts = evaluate(trial, ta, tb)
+        iters += 1
+        take = tcounts[0] >= s["min_pixels"] and tsums[EXPOSURE_COST] / tcounts[0] < sums[EXPOSURE_COST] / counts[0]
+        if (estimate & EXPOSURE_GAIN) and not g_lo <= ta <= g_hi:
+            take = False
+        if take:
+            q, a, b, sums, counts = trial, ta, tb, tsums, tcounts
+            lam = max(lam / s["lambda_down"], s["lambda_min"])
+            if np.linalg.norm(x[:3]) < s["tol_rot"]:
+                return q, a, b, sums, counts, ALIGN_CONVERGED, iters
+        else:
+            lam *= s["lambda_up"]
+            if lam > s["lambda_max"]:
+                return q, a, b, sums, counts, ALIGN_STALLED, iters
+
+
+def refit_frames(frames_u8, frame_t_ns, lut, pano_w, pano_h, q, status, gain=None, bias=None, levels=(0,), batch=1, sweeps=1, alternate=True, recover=True,
+                 sweep_tol=0.0, estimate=0, skip_zero=False, min_weight=256, min_overlap=0.5, gain_min=None, gain_max=None, **settings):
+    """The whole refit of emba_frames_refit in numpy, with numpy's own pm.  The planes are built from every voting frame at its given (q, a, b)
+    (track_votes_exposure).  A sweep visits the batches (refit_batches; with `alternate` the odd sweeps backwards): the tracked frames of the batch take
+    their votes out of the uint64 sums again (subtraction modulo 2^64), every active frame — tracked, or lost under `recover` — starts at refit_start and
+    is aligned level by level by track_frames_exposure's loop against what is left, and the verdict moves it, keeps it, recovers it or leaves it lost; the
+    tracked frames of the batch are then voted back.  A dict of q, gain, bias, status, refit [F] (REFIT_*), iters [F, len(levels)], cost, overlap, counts
+    (the last sweep's), sweep [sweeps_done, 4] (moved, recovered, largest rotation change, sum of the last-level costs), sweeps_done, iters_sweeps
+    [sweeps_done, len(levels)] (trials per level summed over the frames), refit_sweeps [sweeps_done, F], pm [F, S, 2], planes {level: (sum_w, sum_v)},
+    dropped and skipped.  Batches are cut by `batch` alone, as in track_frames."""
+    s = align_settings(**settings)
+    g_lo, g_hi = exposure_bounds(gain_min, gain_max)
+    estimate, sweeps = int(estimate), int(sweeps)
+    if not 0 <= estimate <= 3:
+        raise ValueError("estimate is a mask of EXPOSURE_GAIN and EXPOSURE_BIAS")
+    W, H = int(pano_w), int(pano_h)
+    ts = np.asarray(frame_t_ns, dtype=np.int64).reshape(-1)
+    F = ts.size
+    if (np.diff(ts) <= 0).any():
+        raise ValueError("the frame times must be strictly increasing")
+    if int(batch) < 1 or not 0.0 <= float(min_overlap) <= 1.0 or int(min_weight) < 1 or not 1 <= len(levels) <= 8:
+        raise ValueError("batch >= 1, 0 <= min_overlap <= 1, min_weight >= 1, 1 ... 8 levels")
+    if sweeps < 0 or not float(sweep_tol) >= 0.0:
+        raise ValueError("sweeps >= 0, sweep_tol >= 0")
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(F, -1)
+    S = frames.shape[1]
+    q = np.array(q, dtype=np.float64).reshape(F, 4)
+    status = np.array(status, dtype=np.int32).reshape(F)
+    gain = np.broadcast_to(np.asarray(1.0 if gain is None else gain, dtype=np.float64), (F,)).copy()
+    bias = np.broadcast_to(np.asarray(0.0 if bias is None else bias, dtype=np.float64), (F,)).copy()
+    # refit_args_ok's refusals, in its order
+    if not np.isin(status, (TRACK_ANCHOR, TRACK_TRACKED, TRACK_LOST)).all():
+        raise ValueError("a status is TRACK_ANCHOR, TRACK_TRACKED or TRACK_LOST")
+    if not np.isin(status, (TRACK_ANCHOR, TRACK_TRACKED)).any():
+        raise ValueError("no frame votes: a refit needs an anchor or a tracked frame")
+    for f in range(F):
+        n2 = float((q[f] * q[f]).sum())
+        if not (np.isfinite(n2) and n2 > 0.0):
+            raise ValueError(f"q[{f}] is not finite or has zero norm")
+        if not (np.isfinite(gain[f]) and g_lo <= gain[f] <= g_hi):
+            raise ValueError(f"gain[{f}] = {gain[f]} is not finite or outside the bounds")
+        if not np.isfinite(bias[f]):
+            raise ValueError(f"bias[{f}] is not finite")
+    vote_levels = track_vote_levels(levels)
+    shapes = {l: track_level_shape(W, H, l) for l in vote_levels}
+    planes = {l: (np.zeros((Hl, Wl), np.uint64), np.zeros((Hl, Wl), np.uint64)) for l, (Wl, Hl, _) in shapes.items()}
+    pm = np.full((F, S, 2), np.nan)
+    counters = [0, 0]
+    mask = (1 << 64) - 1
+
+    def vote(f, negate=False):
+        if not negate:
+            pm[f] = align_warp(lut, q[f], W, H)[1]
+        v = track_votes_exposure(frames[f:f + 1], pm[f:f + 1], [TRACK_TRACKED], gain[f:f + 1], bias[f:f + 1], W, H, levels, skip_zero)
+        for l in vote_levels:
+            for k in (0, 1):
+                if negate:
+                    planes[l][k][...] -= v["planes"][l][k]      # (uint64: modulo 2^64)
+                else:
+                    planes[l][k][...] += v["planes"][l][k]
+        for k, name in enumerate(("dropped", "skipped")):
+            counters[k] = (counters[k] + (-v[name] if negate else v[name])) & mask
+
+    def evaluate_at(f, l):
+        _, _, scale = shapes[l]
+        return lambda qq, aa, bb: exposure_sums(track_exposure_terms(frames[f], align_warp(lut, qq, W, H)[1] * scale, lut, qq, planes[l][0], planes[l][1], aa, bb,
+                                                                     min_weight, skip_zero, s["huber_k"]))
+
+    votes_now = lambda: (status == TRACK_ANCHOR) | (status == TRACK_TRACKED)      # noqa: E731
+    for f in np.flatnonzero(votes_now()):
+        vote(int(f))
+    refit = np.where(status == TRACK_ANCHOR, REFIT_ANCHOR, np.where(status == TRACK_LOST, REFIT_LOST, 0)).astype(np.int32)
+    iters, cost, overlap, counts = np.zeros((F, len(levels)), np.int32), np.zeros(F), np.zeros(F), np.zeros((F, 4), np.int64)
+    sweep_rows, iters_sweeps, refit_sweeps = [], [], []
+    batches = refit_batches(F, batch)
+    for sweep in range(sweeps):
+        q_before = q.copy()
+        refit = np.where(status == TRACK_ANCHOR, REFIT_ANCHOR, np.where(status == TRACK_LOST, REFIT_LOST, 0)).astype(np.int32)
+        iters[...], cost[...], overlap[...], counts[...] = 0, 0.0, 0.0, 0
+        for f0, nf in (batches[::-1] if alternate and sweep & 1 else batches):
+            fs = range(f0, f0 + nf)
+            entered = status.copy()
+            active = [f for f in fs if entered[f] == TRACK_TRACKED or (recover and entered[f] == TRACK_LOST)]
+            for f in fs:
+                if entered[f] == TRACK_TRACKED:
+                    vote(f, negate=True)
+            starts = {f: refit_start(entered, ts, q, gain, bias, f) for f in active}
+            new = {}
+            for f in active:
+                qq, aa, bb = starts[f]
+                for k, l in enumerate(levels):
+                    qq, aa, bb, sums, cnt, st, iters[f, k] = _exposure_align_level(evaluate_at(f, int(l)), qq, aa, bb, s, estimate, g_lo, g_hi)
+                denom = S - cnt[3]
+                overlap[f] = cnt[0] / denom if denom > 0 else 0.0
+                cost[f], counts[f] = sums[EXPOSURE_COST], cnt
+                passed = st != ALIGN_DEGENERATE and overlap[f] >= float(min_overlap)
+                was_lost = entered[f] == TRACK_LOST
+                refit[f] = (REFIT_RECOVERED if was_lost else REFIT_MOVED) if passed else (REFIT_LOST if was_lost else REFIT_KEPT)
+                if passed:
+                    new[f] = (qq, aa, bb)
+            for f, (qq, aa, bb) in new.items():
+                q[f], gain[f], bias[f], status[f] = qq, aa, bb, TRACK_TRACKED
+            for f in fs:
+                if status[f] == TRACK_TRACKED:
+                    vote(f)
+        change = float(rotation_angle_between(q_before, q).max())
+        sweep_rows.append([float((refit == REFIT_MOVED).sum()), float((refit == REFIT_RECOVERED).sum()), change, float(cost.sum())])
+        iters_sweeps.append(iters.sum(axis=0))
+        refit_sweeps.append(refit.copy())
+        if change < float(sweep_tol):
+            break
+    pm[~votes_now()] = np.nan
+    n_lv = len(levels)
+    return dict(q=q, gain=gain, bias=bias, status=status, refit=refit, iters=iters, cost=cost, overlap=overlap, counts=counts,
+                sweep=np.array(sweep_rows, dtype=np.float64).reshape(-1, 4), sweeps_done=len(sweep_rows),
+                iters_sweeps=np.array(iters_sweeps, dtype=np.int64).reshape(-1, n_lv), refit_sweeps=np.array(refit_sweeps, dtype=np.int32).reshape(-1, F), pm=pm,
+                planes=planes, dropped=counters[0], skipped=counters[1])
+
+
 def rotation_angle_between(qa, qb):
     """The angle (rad) of the rotation from qa to qb, quaternions xyzw [..., 4]."""
     qa, qb = np.asarray(qa, dtype=np.float64).reshape(-1, 4), np.asarray(qb, dtype=np.float64).reshape(-1, 4)

@@ -608,6 +608,50 @@ class LEGM:
                                                      _p(resid, _dp)))
         return dict(sums=sums, counts=counts.astype(np.int64), pm=pm, resid=resid)
 
+    def refit_frames(self, frames, frame_t_ns, q, status, gain=None, bias=None, levels=(0,), batch=1, sweeps=1, alternate=True, recover=True, sweep_tol=0.0,
+                     estimate=0, skip_zero=False, min_weight=256, min_overlap=0.5, gain_min=None, gain_max=None, want_pm=False, **settings):
+        """A tracker's frames refitted against the mosaic of the other frames (emba_frames_refit; the rule: include/emba_hip.h): q [F, 4], status [F] and,
+        from the tracker with exposure, gain and bias [F] (1 and 0 without) are what track_frames / track_frames_exposure returned.  The planes are built from
+        every voting frame; then `sweeps` times every batch is taken out of them exactly, aligned to what is left — the frames before it and behind it — and
+        voted back.  Anchors never move; with `recover` a lost frame starts between its voting neighbours and may become tracked; with `alternate` the odd
+        sweeps run backwards; a sweep whose largest rotation change is below sweep_tol (rad) is the last.  sweeps = 0 stitches at the given rotations.  A
+        dict of q, gain, bias, status, refit int32 [F] (io.REFIT_*), iters [F, len(levels)], cost, counts, overlap (the last sweep's), sweep
+        [sweeps_done, 4] (moved, recovered, largest rotation change, sum of the last-level costs), sweeps_done, tracked, lost, dropped, skipped and pm
+        [F, S, 2] (None without want_pm; NaN for a frame that does not vote).  io.refit_frames is the same rule in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        g_lo = float(emba_io.EXPOSURE_BOUNDS["gain_min"] if gain_min is None else gain_min)
+        g_hi = float(emba_io.EXPOSURE_BOUNDS["gain_max"] if gain_max is None else gain_max)
+        ts = np.ascontiguousarray(frame_t_ns, dtype=np.int64).reshape(-1)
+        F, S = ts.size, self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size != F * S:
+            raise ValueError(f"frames must be {F} x sensor_height x sensor_width bytes")
+        levels = [int(l) for l in levels]
+        if not 1 <= len(levels) <= 8:
+            raise ValueError("a schedule names 1 ... 8 levels")
+        q_in = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 4)
+        st_in = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+        a_in, b_in = self._exposure_args(gain, bias, F)
+        if q_in.shape[0] != F or st_in.size != F:
+            raise ValueError(f"q must be [{F}, 4] and status [{F}]")
+        sweeps = int(sweeps)
+        ts_ = _lib.EmbaTrackSettings(len(levels), (C.c_int32 * 8)(*levels), int(batch), 0, 1 if skip_zero else 0, int(min_weight), float(min_overlap),
+                                     _lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                                            float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]), float(s["huber_k"])))
+        cs = _lib.EmbaRefitSettings(_lib.EmbaTrackExposureSettings(ts_, int(estimate), g_lo, g_hi), sweeps, 1 if alternate else 0, 1 if recover else 0, float(sweep_tol))
+        q_out, a_out, b_out, st_out, refit = np.zeros((F, 4)), np.zeros(F), np.zeros(F), np.zeros(F, np.int32), np.zeros(F, np.int32)
+        iters, cost, counts, overlap = np.zeros((F, len(levels)), np.int32), np.zeros(F), np.zeros((F, 4), np.uint64), np.zeros(F)
+        sweep, done, stats = np.zeros((max(sweeps, 0), 4)), np.zeros(1, np.int32), np.zeros(4, np.uint64)
+        pm = np.empty((F, S, 2)) if want_pm else None
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_refit(self._ctx, _p(frames, _u8p), _p(ts, _i64p), F, _p(q_in, _dp), _p(a_in, _dp), _p(b_in, _dp), _p(st_in, _i32p),
+                                              C.addressof(cs), _p(q_out, _dp), _p(a_out, _dp), _p(b_out, _dp), _p(st_out, _i32p), _p(refit, _i32p), _p(iters, _i32p),
+                                              _p(cost, _dp), _p(counts, u64p), _p(overlap, _dp), _p(sweep, _dp), _p(done, _i32p), _p(stats, u64p), _p(pm, _dp)))
+        return dict(q=q_out, gain=a_out, bias=b_out, status=st_out, refit=refit, iters=iters, cost=cost, counts=counts.astype(np.int64), overlap=overlap,
+                    sweep=sweep[:int(done[0])], sweeps_done=int(done[0]), tracked=int(stats[0]), lost=int(stats[1]), dropped=int(stats[2]), skipped=int(stats[3]),
+                    pm=pm)
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

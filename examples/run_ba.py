@@ -144,11 +144,21 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
     io.fit_ctrl_poses of them the trajectory.
     Lost frames are left out.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the rotation, the status, the overlap and the cost.
     --track-exposure bias / gain-bias: every frame carries a gain and a bias in byte units, estimated with its rotation, and votes its
-    compensated bytes; the rows then end in the gain and the bias."""
+    compensated bytes; the rows then end in the gain and the bias.
+    --track-refit N: N sweeps of the refit behind the tracker; the rows then end in the refit code."""
     kw = dict(q0=a.track_q0, levels=a.track_levels, batch=a.track_batch, predict=bool(a.track_predict), skip_zero=a.frames_skip_zero,
               min_overlap=a.track_min_overlap, huber_k=a.frames_huber)
     estimate = {"none": None, "bias": eio.EXPOSURE_BIAS, "gain-bias": eio.EXPOSURE_GAIN | eio.EXPOSURE_BIAS}[a.track_exposure]
     r = legm.track_frames(frames, t_ns, **kw) if estimate is None else legm.track_frames_exposure(frames, t_ns, estimate=estimate, **kw)
+    if a.track_refit:      # the sweeps behind the tracker, before the raw poses are sampled (DESIGN.md section 25): the mosaic in the context is the refitted one
+        from emba_amd.driver import SequenceSettings, refit_tracked_frames
+        before = r["q"]
+        r = refit_tracked_frames(legm, frames, t_ns, r, SequenceSettings(1.0, 1.0, track_refit=a.track_refit, track_refit_tol=a.track_refit_tol),
+                                 estimate=estimate or 0, **kw)
+        codes = [int((r["refit"] == c).sum()) for c in (eio.REFIT_MOVED, eio.REFIT_KEPT, eio.REFIT_RECOVERED, eio.REFIT_LOST)]
+        log(f"track-refit: {r['sweeps_done']} of {a.track_refit} sweeps, largest rotation change per sweep {', '.join(f'{v:.3g}' for v in r['sweep'][:, 2])} rad; "
+            f"{codes[0]} frames moved, {codes[1]} kept, {codes[2]} recovered, {codes[3]} lost; worst change against the tracker "
+            f"{eio.rotation_angle_between(before, r['q']).max():.3g} rad")
     ok = r["status"] != eio.TRACK_LOST
     tf, qf = t_ns[ok] * 1e-9, r["q"][ok]
     # the raw poses a sliding-window run reads: the tracked rotations on a 5 ms grid over the trajectory's span (io.pose_at: interpolated between tracked
@@ -165,6 +175,8 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
         log(f"track-exposure {a.track_exposure}: gain {r['gain'].min():.4f} ... {r['gain'].max():.4f}, bias {r['bias'].min():.3f} ... {r['bias'].max():.3f} bytes "
             f"(the anchor's tone is the gauge: gain 1, bias 0)")
         rows = [row + (float(g), float(o)) for row, g, o in zip(rows, r["gain"], r["bias"])]
+    if a.track_refit:      # (the last column, behind gain and bias where they are there)
+        rows = [row + (int(c),) for row, c in zip(rows, r["refit"])]
     return traj, t_raw, q_raw, rows
 
 
@@ -293,6 +305,11 @@ def main():
                     "estimated with its rotation inside the tracker, for frames of a camera with auto-exposure; the tracked frames vote their compensated bytes, "
                     "--init-map frames and frame_mosaic.pgm use them, and --refine-frames N --frames-exposure X starts from them (DESIGN.md section 24; "
                     "frames_tracked.txt gains the columns gain and bias)")
+    ap.add_argument("--track-refit", type=int, default=0, metavar="N", help="--init-poses frames: behind the tracker (either one), N sweeps in which every frame is taken "
+                    "out of the integer mosaic, aligned to the mosaic of all the other frames and voted back, before the raw poses are sampled; lost frames are "
+                    "tried again; --init-map frames takes the refitted mosaic (DESIGN.md section 25; frames_tracked.txt gains the refit code as its last column: "
+                    "1 anchor, 2 moved, 3 kept, 4 recovered, 5 lost).  0: off")
+    ap.add_argument("--track-refit-tol", type=float, default=0.0, metavar="X", help="with --track-refit: stop behind a sweep whose largest rotation change is below X rad (0: never)")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
     ap.add_argument("--record-contrast", action="store_true", help="print, per window, the contrast J = sum I^2 of the panorama of the window's warped events at its "
@@ -340,6 +357,10 @@ def main():
         ap.error("--refine-frames N (N >= 0) aligns the frames of --frames DIR")
     if a.track_exposure != "none" and a.init_poses != "frames":
         ap.error("--track-exposure estimates the exposure inside the tracker of --init-poses frames: it needs --init-poses frames")
+    if (a.track_refit or a.track_refit_tol) and a.init_poses != "frames":
+        ap.error("--track-refit refits the frames tracked by --init-poses frames: it needs --init-poses frames")
+    if a.track_refit < 0 or not a.track_refit_tol >= 0.0:
+        ap.error("--track-refit N and --track-refit-tol X are not negative")
     if a.frames_exposure != "none" and not a.refine_frames:
         ap.error("--frames-exposure estimates the exposure in the rounds of --refine-frames N: it needs N >= 1")
     if a.refine_frames and a.init_poses not in ("given", "frames"):
@@ -462,10 +483,11 @@ def main():
         tracked_mosaic = True
         if rank == 0:
             with open(os.path.join(a.out, "frames_tracked.txt"), "w") as fh:
-                fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost" + (" gain bias[bytes]" if a.track_exposure != "none" else "") + "\n")
+                fh.write("# t[s] qx qy qz qw status(1 anchor, 2 tracked, 3 lost) overlap cost" + (" gain bias[bytes]" if a.track_exposure != "none" else "")
+                         + (" refit(1 anchor, 2 moved, 3 kept, 4 recovered, 5 lost)" if a.track_refit else "") + "\n")
                 for row in rows:
                     tn, q, st, ov, cost = row[:5]
-                    more = "".join(f" {v:.17g}" for v in row[5:])
+                    more = "".join(f" {v:.17g}" if isinstance(v, float) else f" {v}" for v in row[5:])
                     fh.write(f"{tn // 1_000_000_000}.{tn % 1_000_000_000:09d} {q[0]:.17g} {q[1]:.17g} {q[2]:.17g} {q[3]:.17g} {st} {ov:.9g} {cost:.9g}{more}\n")
     frames_exposure = None      # (gain, bias) per frame of --frames, once --track-exposure or --frames-exposure has estimated them
     if a.init_poses == "frames" and a.track_exposure != "none":
@@ -509,7 +531,8 @@ def main():
                                init_poses="events" if a.init_poses == "events" else "given", cmax_slice_events=a.cmax_slice_events, cmax_omega_max=a.cmax_omega_max,
                                record_contrast=a.record_contrast, event_panorama=a.event_panorama, refine_contrast=a.refine_contrast,
                                contrast_iters=a.contrast_iters, contrast_levels=a.contrast_levels, contrast_prior=a.contrast_prior,
-                               contrast_prior_weight=a.contrast_prior_weight, views_hz=a.views_hz if rank == 0 else 0.0, view_events=a.view_events)
+                               contrast_prior_weight=a.contrast_prior_weight, views_hz=a.views_hz if rank == 0 else 0.0, view_events=a.view_events,
+                               track_refit=a.track_refit, track_refit_tol=a.track_refit_tol)
         sres = run_sequence(model, events, *((None, None) if a.init_poses == "events" else (t, qs)), *((None, None) if a.init_map == "events" else (Gx, Gy)), seq, ba, LMSettings(max_num_iter=a.max_iter), runtime_log=rlog, map_recorder=mrec, resident=True,
                             verbose=a.verbose)
         if rank == 0 and sres.filter_stats is not None:

@@ -841,6 +841,62 @@ emba_status emba_track_exposure_eval(emba_ctx* ctx, const uint8_t* frames /* [F,
                                      double* sums_out /* [F, 21] */, uint64_t* counts_out /* [F, 4] */, double* pm_out /* [F, sh*sw, 2] */,
                                      double* resid_out /* [F, sh*sw] */);
 
+/* ---- Tracked frames refitted against the mosaic of the other frames.  A tracker aligns every frame once, against the frames before it
+ * only.  The level planes are exact integer sums, so a frame's votes can be taken out again exactly: the same warp and the same cells, the added values
+ * negated modulo 2^64.  What is left is the mosaic of all the other frames, earlier and later; aligning the frame to it and voting it back is one
+ * Gauss-Seidel step of a global photometric refit.  The rule lives in emba_amd/csrc/refit_rule.h, over track_rule.h, track_exposure_rule.h and
+ * exposure_rule.h; emba_amd.io.refit_frames is the same rule in numpy.  Everything that is not said here is emba_frames_track_exposure's.
+ *
+ *   input             F frames of bytes at frame_t_ns (strictly increasing) and per frame q [F, 4], gain [F], bias [F], status [F] (EMBA_TRACK_*): what either
+ *                     tracker returns (the plain tracker's output takes gain 1 and bias 0).  The rotations are used as they are given: unit quaternions.
+ *                     Anchors vote and never move: they are the gauge; any number of them, none among it.  At least one frame votes.
+ *   settings          settings.track: the schedule, batch, skip_zero, min_weight, min_overlap, align, estimate and the gain bounds (predict is ignored);
+ *                     sweeps >= 0; alternate: the odd sweeps visit the batches from the last to the first; recover: lost frames are tried; sweep_tol: the
+ *                     call ends behind a sweep whose largest rotation change (rad) is below it, 0: never.
+ *   build             the mosaic and every level plane of the schedule, and level 0, are zeroed, and every voting frame votes at its given (q, a, b):
+ *                     emba_frames_track_exposure's vote.  What the context held is not trusted.  sweeps = 0 is this alone: a stitch at given rotations.
+ *   a sweep           visits the batches as the tracker cuts them (frame 0 alone, then `batch` frames, a chunk boundary a batch boundary; a batch of
+ *                     anchors alone is passed over).  Per batch:
+ *                       un-vote   every tracked frame of the batch takes its votes out of every plane and its counts out of the two counters (dropped,
+ *                                 skipped): the vote's kernel with every added value negated modulo 2^64
+ *                       start     a tracked frame starts at its own (q, a, b).  With recover a lost frame starts from the nearest voting frames a < f < b by
+ *                                 index, as the statuses stand at the start of the batch: the prediction's formula at t_f, whose factor (t_f - t_b) /
+ *                                 (t_b - t_a) is negative — an interpolation — and gain and bias linear in the same factor; with a voting frame on one side
+ *                                 only, that frame's values.  Without recover a lost frame is passed over
+ *                       align     emba_frames_track_exposure's loop, level by level, against planes that no longer hold the batch's frames
+ *                       verdict   emba_frames_track's.  A tracked frame that passes takes the new (q, a, b): EMBA_REFIT_MOVED; one that fails keeps what it
+ *                                 had: EMBA_REFIT_KEPT.  A lost frame that passes becomes tracked: EMBA_REFIT_RECOVERED; one that fails keeps its input
+ *                                 (q, a, b): EMBA_REFIT_LOST.  An anchor reports EMBA_REFIT_ANCHOR
+ *                       vote      every tracked frame of the batch votes at the values it has now (a kept frame puts back what it took out)
+ *   invariant         behind every batch every plane and both counters equal, as integers, the vote of all voting frames at their current (q, a, b).
+ *
+ * Outputs, each may be NULL: q_out, gain_out, bias_out, status_out (EMBA_TRACK_*) as they stand behind the call; refit_out [F]: the code of the last sweep
+ * (behind sweeps = 0: EMBA_REFIT_ANCHOR for an anchor, EMBA_REFIT_LOST for a lost frame, 0 for a tracked one); iters_out [F, n_levels], cost_out, counts_out,
+ * overlap_out: the last sweep's, 0 for a frame it did not align; sweep_out [sweeps, 4]: per sweep that ran the frames moved, the frames recovered, the
+ * largest rotation change (rad; formed on the host from the rotations before and behind the sweep) and the sum of the last-level costs; sweeps_done_out;
+ * stats_out [4] as emba_frames_track's; pm_out [F, sh*sw, 2]: the level-0 pm of each frame's last vote, NaN for a frame that does not vote.
+ * Every sweep uploads the frames again chunk by chunk; rotations, exposures and statuses stay on the device for the whole call; behind each sweep the host
+ * reads the rotations, the codes and the costs.  Refusals are decided before anything is zeroed and leave every output, the mosaic and the level planes
+ * untouched: what emba_frames_track_exposure refuses (but for q0), and EMBA_ERR_INVALID_ARG for q, gain, bias or status NULL with F > 0, sweeps < 0, a
+ * sweep_tol that is negative or a NaN, a status outside the three values, no voting frame, a q that is not finite or of zero norm, a gain that is not finite or
+ * outside the bounds, a bias that is not finite.  What the trackers leave alone, this leaves alone. */
+#define EMBA_REFIT_ANCHOR 1
+#define EMBA_REFIT_MOVED 2
+#define EMBA_REFIT_KEPT 3
+#define EMBA_REFIT_RECOVERED 4
+#define EMBA_REFIT_LOST 5
+typedef struct {
+    emba_track_exposure_settings track;
+    int32_t sweeps, alternate, recover;
+    double sweep_tol;
+} emba_refit_settings;
+emba_status emba_frames_refit(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, const int64_t* frame_t_ns /* [F] */, size_t F, const double* q_xyzw /* [F, 4] */,
+                              const double* gain /* [F] */, const double* bias /* [F] */, const int32_t* status /* [F] */, const emba_refit_settings* settings,
+                              double* q_out /* [F, 4] */, double* gain_out /* [F] */, double* bias_out /* [F] */, int32_t* status_out /* [F] */,
+                              int32_t* refit_out /* [F] */, int32_t* iters_out /* [F, n_levels] */, double* cost_out /* [F] */, uint64_t* counts_out /* [F, 4] */,
+                              double* overlap_out /* [F] */, double* sweep_out /* [sweeps, 4] */, int32_t* sweeps_done_out, uint64_t* stats_out /* [4] */,
+                              double* pm_out /* [F, sh*sw, 2] */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
