@@ -51,6 +51,11 @@ class EmbaRefitSettings(C.Structure):
     _fields_ = [("track", EmbaTrackExposureSettings), ("sweeps", C.c_int32), ("alternate", C.c_int32), ("recover", C.c_int32), ("sweep_tol", C.c_double)]
 
 
+class EmbaGraphSettings(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("cg_max_iters", C.c_int32), ("lambda0", C.c_double), ("lambda_up", C.c_double), ("lambda_down", C.c_double),
+                ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("tol", C.c_double), ("cg_tol", C.c_double)]
+
+
 # symbol -> (restype, argtypes); exactly the entry points include/emba_hip.h declares
 SIGNATURES = {
     "emba_abi_version": (C.c_int, []),
@@ -172,6 +177,11 @@ SIGNATURES = {
                                            _dp, _dp]),
     "emba_frames_refit": (C.c_int, [C.c_void_p, _u8p, _i64p, C.c_size_t, _dp, _dp, _dp, _i32p, C.c_void_p, _dp, _dp, _dp, _i32p, _i32p, _i32p, _dp,
                                     C.POINTER(C.c_uint64), _dp, _dp, _i32p, C.POINTER(C.c_uint64), _dp]),
+    "emba_frames_pair_eval": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _i32p, C.c_size_t, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp,
+                                        C.c_int32, C.c_double, _dp, C.POINTER(C.c_uint64), _dp, _dp]),
+    "emba_frames_pair_align": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _i32p, C.c_size_t, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _dp,
+                                         C.c_int32, C.c_void_p, _dp, _dp, C.POINTER(C.c_uint64), _i32p, _i32p, _dp, C.POINTER(C.c_uint64), _dp]),
+    "emba_rotation_graph_solve": (C.c_int, [_dp, _i32p, C.c_size_t, _i32p, _dp, _dp, C.c_size_t, C.c_void_p, _dp, _dp, _i32p, _i32p, _szp]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

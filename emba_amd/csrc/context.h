@@ -291,6 +291,10 @@ struct ExposureBuffers {
     DevBuf vote_gain, vote_bias;
 };
 
+// One frame aligned to another (pair_host.h); all of it scratch of one call.  loop.frames: the whole sequence [F, S], uploaded once per call (where the other
+// stages keep a chunk); loop.pm: uv; the rest of loop over one chunk of pairs; pairs, gain, bias: the chunk's (i, j) and relative exposures.
+struct PairBuffers { DevBuf pairs, gain, bias; FrameLoopBuffers loop; };
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -491,6 +495,7 @@ struct emba_ctx {
     AlignBuffers align;           // intensity frames aligned to a panorama plane: the scratch of a call (align_host.h)
     TrackBuffers track;           // intensity frames tracked against their own growing mosaic: the level planes and the scratch of a call (track_host.h)
     ExposureBuffers exposure;     // per-frame exposure: the scratch of a call (exposure_host.h)
+    PairBuffers pair;             // one frame aligned to another: the resident sequence of a call and the scratch of a chunk of pairs (pair_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

@@ -45,6 +45,38 @@ __device__ __forceinline__ void frame_warp(const double* lut, const double* q4, 
     project_chain<false>(rb, fx, fy, cx, cy, pm, J23);
 }
 
+// The tail of an evaluation kernel's body, every lane of the workgroup in it: a lane's N sums and four class counts summed over the wave by the xor butterfly
+// (offsets 32 ... 1) and over the workgroup's four waves in LDS in wave order; the record partial[item][workgroup][frame_partial(N)] is written, the counts as uint32 in the space
+// of the last two doubles.  frame_eval_body and the pair kernel (pair_kernels.h) end in it.
+template <int N>
+__device__ __forceinline__ void frame_sum_tail(double* acc, unsigned int* cnt, double* partial, size_t item)
+{
+    __shared__ double red[kFrameWaves][N];
+    __shared__ unsigned int redc[kFrameWaves][4];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += __shfl_xor(acc[k], o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cnt[k] += __shfl_xor(cnt[k], o);
+    }
+    const int wave = (int)threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[wave][k] = acc[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) redc[wave][k] = cnt[k];
+    }
+    __syncthreads();
+    double* out = partial + (item * (size_t)gridDim.x + (size_t)blockIdx.x) * (size_t)frame_partial(N);
+    const int k = (int)threadIdx.x;
+    if (k < N) out[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    else if (k < N + 4) {
+        const int j = k - N;
+        reinterpret_cast<unsigned int*>(out + N)[j] = ((redc[0][j] + redc[1][j]) + redc[2][j]) + redc[3][j];
+    }
+}
+
 // An evaluation kernel's body.  Params has lut, q, status, frames, S, fx, fy, cx, cy, partial, pm, resid; Rule has
 //   kSums                                the number of sums N
 //   Term                                 a pixel's term, with its residual r
@@ -55,8 +87,6 @@ template <class Rule, class Params>
 __device__ __forceinline__ void frame_eval_body(const Params& p)
 {
     constexpr int N = Rule::kSums;
-    __shared__ double red[kFrameWaves][N];
-    __shared__ unsigned int redc[kFrameWaves][4];
     const size_t f = blockIdx.y;
     if (p.status && p.status[f] != EMBA_ALIGN_RUNNING) return;      // (the whole workgroup: f is blockIdx.y)
     const int s = (int)blockIdx.x * kFrameThreads + (int)threadIdx.x;
@@ -78,28 +108,7 @@ __device__ __forceinline__ void frame_eval_body(const Params& p)
 #pragma unroll
         for (int k = 0; k < 4; ++k) cnt[k] = cls == k ? 1u : 0u;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[k] += __shfl_xor(acc[k], o);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cnt[k] += __shfl_xor(cnt[k], o);
-    }
-    const int wave = (int)threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) red[wave][k] = acc[k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) redc[wave][k] = cnt[k];
-    }
-    __syncthreads();
-    double* out = p.partial + (f * (size_t)gridDim.x + (size_t)blockIdx.x) * (size_t)frame_partial(N);
-    const int k = (int)threadIdx.x;
-    if (k < N) out[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    else if (k < N + 4) {
-        const int j = k - N;
-        reinterpret_cast<unsigned int*>(out + N)[j] = ((redc[0][j] + redc[1][j]) + redc[2][j]) + redc[3][j];
-    }
+    frame_sum_tail<N>(acc, cnt, p.partial, f);
 }
 
 // sums [nf, N] and counts [nf, 4] of the frames' partial sums, added in workgroup order

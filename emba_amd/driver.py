@@ -76,8 +76,23 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # never).  refit_tracked_frames below applies them.  0: off.
     track_refit: int = 0
     track_refit_tol: float = 0.0
+    # ... and, before any refit, their loops are closed: track_close aligns pairs of tracked frames that see the same place with each other
+    # (LEGM.pair_align) and solves the rotation graph of the kept pairs with the tracker's anchors held exactly (LEGM.rotation_graph_solve; the rules:
+    # include/emba_hip.h, emba_frames_pair_align and emba_rotation_graph_solve).  The pairs are io.pair_candidates of the tracked rotations
+    # under close_window, close_gap, close_angle (rad) and close_per_frame; close_huber is the pairs' Huber threshold in bytes (0: quadratic);
+    # close_min_overlap the share of used pixels a kept pair needs.  close_tracked_frames below applies it.  Off by default.
+    track_close: bool = False
+    close_window: int = 1
+    close_gap: int = 4
+    close_angle: float = 0.2
+    close_per_frame: int = 2
+    close_huber: float = 0.0
+    close_min_overlap: float = 0.3
 
     def __post_init__(self):
+        if (int(self.close_window) < 0 or int(self.close_gap) < 0 or int(self.close_per_frame) < 0 or not float(self.close_angle) >= 0.0
+                or not 0.0 <= float(self.close_min_overlap) <= 1.0 or np.isnan(self.close_huber)):
+            raise ValueError("SequenceSettings.close_*: window, gap and per_frame are counts, the angle is not negative, the overlap a share, the threshold a number")
         if int(self.track_refit) < 0 or not float(self.track_refit_tol) >= 0.0:
             raise ValueError(f"SequenceSettings.track_refit = {self.track_refit}, track_refit_tol = {self.track_refit_tol}: sweeps and a tolerance, neither negative")
         if not (np.isfinite(self.views_hz) and self.views_hz >= 0):
@@ -109,6 +124,57 @@ def refit_tracked_frames(model, frames, frame_t_ns, tracked, seq, **track_kw):
     out = dict(tracked)
     out.update({k: v for k, v in r.items() if k != "pm"})
     return out
+
+
+def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track_kw):
+    """`tracked`: what model.track_frames or model.track_frames_exposure returned for these frames under the tracker settings track_kw (as
+    refit_tracked_frames takes them); calib: the camera of the frames (io.pair_calib).  With seq.track_close: the candidates of the tracked rotations
+    (io.pair_candidates), started from the tracked (q, gain, bias) (io.pair_start), are aligned on the device (LEGM.pair_align); the pairs that ended
+    converged or on iterations with n / S >= close_min_overlap are the edges of the rotation graph, their information floored at io.PAIR_NOISE_FLOOR, which
+    is solved with the tracker's anchors fixed (LEGM.rotation_graph_solve); the frames are then stitched again at the new rotations
+    (LEGM.refit_frames, sweeps = 0), so the mosaic in the context is the closed one.  The tracker's dict comes back with the new q and, beside it, `pairs`
+    [P, 2], `pair_status`, `pair_n`, `pair_cost` (mean), `pair_moved` (rad, against the pair's start), `pair_kept` and `graph` (cost0, cost, iters,
+    cg_iters, end).  Without seq.track_close, or where no pair is kept, `tracked` is returned as it is (with the pairs, where there were any)."""
+    if not seq.track_close:
+        return tracked
+    kw = {k: v for k, v in track_kw.items() if k not in ("q0", "predict", "want_pm")}
+    S = model.sensor_w * model.sensor_h
+    pairs = emba_io.pair_candidates(tracked["q"], tracked["status"], window=seq.close_window, min_gap=seq.close_gap, max_angle=seq.close_angle,
+                                    max_per_frame=seq.close_per_frame)
+    Q0, a, b = emba_io.pair_start(tracked["q"], tracked.get("gain"), tracked.get("bias"), pairs)
+    align_kw = {k: v for k, v in kw.items() if k in emba_io.ALIGN_DEFAULTS}
+    align_kw["huber_k"] = float(seq.close_huber)
+    al = model.pair_align(frames, pairs, Q0, calib, gain=a, bias=b, skip_zero=bool(kw.get("skip_zero", False)), **align_kw)
+    n = al["counts"][:, 0]
+    kept = ((al["status"] == emba_io.ALIGN_CONVERGED) | (al["status"] == emba_io.ALIGN_ITERATIONS)) & (n >= seq.close_min_overlap * S)
+    out = dict(tracked)
+    out.update(pairs=pairs, pair_status=al["status"], pair_n=n, pair_cost=al["sums"][:, 9] / np.maximum(n, 1), pair_kept=kept,
+               pair_moved=emba_io.rotation_angle_between(Q0, al["q"]) if len(pairs) else np.zeros(0), graph=None)
+    if not kept.any():
+        return out
+    info = emba_io.pair_information(al["sums"], al["counts"], floor=emba_io.PAIR_NOISE_FLOOR)
+    reach = _reached(tracked["status"], pairs[kept])
+    kept &= reach[pairs[:, 0]] & reach[pairs[:, 1]]      # (a group of frames that no kept pair ties to an anchor stays where the tracker put it)
+    if not kept.any():
+        return out
+    g = model.rotation_graph_solve(tracked["q"], tracked["status"], pairs[kept], al["q"][kept], info[kept])
+    out["q"], out["pair_kept"], out["graph"] = g["q"], kept, {k: v for k, v in g.items() if k != "q"}
+    r = model.refit_frames(frames, frame_t_ns, g["q"], tracked["status"], tracked.get("gain"), tracked.get("bias"), sweeps=0, **kw)
+    out.update({k: r[k] for k in ("dropped", "skipped")})
+    return out
+
+
+def _reached(status, edges):
+    """bool [F]: the frames an anchor reaches along the edges (graph_reach of graph_rule.h)."""
+    reached = np.asarray(status) == emba_io.TRACK_ANCHOR
+    grew = True
+    while grew:
+        grew = False
+        for i, j in edges:
+            if reached[i] != reached[j]:
+                reached[i] = reached[j] = True
+                grew = True
+    return reached
 
 
 @dataclass

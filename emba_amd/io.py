@@ -1970,3 +1970,353 @@ def rotation_angle_between(qa, qb):
     """The angle (rad) of the rotation from qa to qb, quaternions xyzw [..., 4]."""
     qa, qb = np.asarray(qa, dtype=np.float64).reshape(-1, 4), np.asarray(qb, dtype=np.float64).reshape(-1, 4)
     return np.array([np.linalg.norm(so3.log(so3.mul(b, so3.inverse(a)))) for a, b in zip(qa, qb)])
+
+
+# ---- loops closed among tracked frames (numpy forms of emba_frames_pair_eval, emba_frames_pair_align and emba_rotation_graph_solve, include/emba_hip.h; the
+# device forms are LEGM.pair_eval and LEGM.pair_align, the host form LEGM.rotation_graph_solve; DESIGN.md §26).  The rules are emba_amd/csrc/pair_rule.h's
+# and graph_rule.h's: given the same uv, the classes are the same and the residuals have the same bits.  rb, uv and the Jacobians are numpy's own.
+PAIR_MAX_BYTES = 1 << 30                 # kPairMaxBytes: the resident sequence of a call
+PAIR_MAX_CANDIDATE_FRAMES = 4096         # pair_candidates is O(F^2) on the host: 16 M angles at the bound
+GRAPH_CONVERGED, GRAPH_STALLED, GRAPH_ITERATIONS, GRAPH_DEGENERATE = 1, 2, 3, 4      # EMBA_GRAPH_*
+GRAPH_END_NAMES = {1: "converged", 2: "stalled", 3: "iterations", 4: "degenerate"}
+GRAPH_DEFAULTS = dict(max_iters=50, cg_max_iters=200, lambda0=1e-4, lambda_up=10.0, lambda_down=10.0, lambda_min=1e-12, lambda_max=1e8, tol=1e-10, cg_tol=1e-10)
+TRACK_ANCHOR = 1                         # EMBA_TRACK_ANCHOR
+PAIR_NOISE_FLOOR = 1.0 / 12.0            # the variance of a byte's rounding: the floor close_tracked_frames puts under a pair's s^2
+
+
+def pair_calib(fu, fv, cu, cv, D=None):
+    """The camera of a pair call: a dict of fu, fv, cu, cv and D (k1, k2, p1, p2, k3 as bearing_lut_from_calibration takes them; None: the pinhole)."""
+    return dict(fu=float(fu), fv=float(fv), cu=float(cu), cv=float(cv), D=None if D is None else np.concatenate([np.asarray(D, np.float64).ravel(), np.zeros(5)])[:5])
+
+
+def pair_start(q, gain, bias, pairs):
+    """(Q [P, 4], a [P], b [P]) of the pairs (i, j) from per-frame camera-to-world rotations q [F, 4] and exposures: Q = q_j^-1 (x) q_i, a = a_i / a_j,
+    b = (b_i - b_j) / a_j (gain, bias: [F], or None for 1 and 0)."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, 4)
+    F = q.shape[0]
+    g = np.ones(F) if gain is None else np.broadcast_to(np.asarray(gain, dtype=np.float64), (F,))
+    o = np.zeros(F) if bias is None else np.broadcast_to(np.asarray(bias, dtype=np.float64), (F,))
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    Q = np.array([so3.mul(so3.inverse(q[j]), q[i]) for i, j in pairs]).reshape(-1, 4)
+    i, j = pairs[:, 0], pairs[:, 1]
+    return Q, g[i] / g[j], (o[i] - o[j]) / g[j]
+
+
+def pair_project(lut, Q, calib):
+    """numpy's own projection of one pair: rb = R(Q) lut [S, 3]; uv [S, 2] through the plumb_bob model (NaN where rb_z <= 0); J23 [S, 2, 3] = d(u, v) / d rb;
+    Ju [S, 2, 3] = J23 (-[rb]x), the Jacobian for Q <- exp(delta) Q."""
+    from . import synth
+    lut = np.asarray(lut, dtype=np.float64).reshape(-1, 3)
+    rb = lut @ synth._quat_to_R(so3.normalize(Q)).T
+    z = rb[:, 2]
+    ok = z > 0.0
+    zs = np.where(ok, z, 1.0)
+    x, y = rb[:, 0] / zs, rb[:, 1] / zs
+    D = calib.get("D")
+    k1, k2, p1, p2, k3 = np.zeros(5) if D is None else D
+    fu, fv, cu, cv = calib["fu"], calib["fv"], calib["cu"], calib["cv"]
+    r2 = x * x + y * y
+    radial = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2
+    xd = x * radial + (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))
+    yd = y * radial + (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)
+    uv = np.stack([np.where(ok, fu * xd + cu, np.nan), np.where(ok, fv * yd + cv, np.nan)], axis=1)
+    rd = (3.0 * k3 * r2 + 2.0 * k2) * r2 + k1
+    cross = 2.0 * x * y * rd + 2.0 * p1 * x + 2.0 * p2 * y
+    axx = radial + 2.0 * x * x * rd + 2.0 * p1 * y + 6.0 * p2 * x
+    ayy = radial + 2.0 * y * y * rd + 6.0 * p1 * y + 2.0 * p2 * x
+    iz = 1.0 / zs
+    J23 = np.stack([np.stack([fu * axx * iz, fu * cross * iz, -fu * (axx * x + cross * y) * iz], axis=1),
+                    np.stack([fv * cross * iz, fv * ayy * iz, -fv * (cross * x + ayy * y) * iz], axis=1)], axis=1)
+    zero = np.zeros_like(z)
+    M = np.stack([np.stack([zero, rb[:, 2], -rb[:, 1]], axis=1), np.stack([-rb[:, 2], zero, rb[:, 0]], axis=1), np.stack([rb[:, 1], -rb[:, 0], zero], axis=1)], axis=1)
+    return rb, uv, J23, J23 @ M
+
+
+def pair_terms(src_u8, tgt_u8, uv, lut, Q, calib, gain=1.0, bias=0.0, skip_zero=False, huber_k=0.0):
+    """The terms of one pair's source pixels (pair_pixel, pair_rule.h) from a given uv [S, 2] (the device's uv_out, or pair_project's) and numpy's own Ju of
+    Q: src_u8 [S] the source frame, tgt_u8 [sh, sw] the target frame.  A dict as align_terms': cls (ALIGN_USED / OUTSIDE / MASKED / SKIPPED, in this
+    precedence; masked and skipped only with skip_zero), r = val - (gain v + bias), w, rho, g [S, 3]."""
+    T = np.asarray(tgt_u8, dtype=np.uint8)
+    sh, sw = T.shape
+    v = np.asarray(src_u8, dtype=np.uint8).reshape(-1)
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    if uv.shape[0] != v.size:
+        raise ValueError(f"uv has {uv.shape[0]} rows, the frame has {v.size} pixels")
+    with np.errstate(invalid="ignore"):
+        fin = (np.abs(uv[:, 0]) < 2147483648.0) & (np.abs(uv[:, 1]) < 2147483648.0)
+    x, y = np.where(fin, uv[:, 0], -1.0), np.where(fin, uv[:, 1], -1.0)
+    fx, fy = np.floor(x), np.floor(y)
+    ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+    inside = fin & (ix >= 0) & (ix + 1 <= sw - 1) & (iy >= 0) & (iy + 1 <= sh - 1)
+    ix, iy = np.where(inside, ix, 0), np.where(inside, iy, 0)
+    ax, ay = x - fx, y - fy
+    b00, b01, b10, b11 = T[iy, ix], T[iy, ix + 1], T[iy + 1, ix], T[iy + 1, ix + 1]
+    p00, p01, p10, p11 = (b.astype(np.float64) for b in (b00, b01, b10, b11))
+    top = (1.0 - ax) * p00 + ax * p01
+    bot = (1.0 - ax) * p10 + ax * p11
+    val = (1.0 - ay) * top + ay * bot
+    gx = (1.0 - ay) * (p01 - p00) + ay * (p11 - p10)
+    gy = (1.0 - ax) * (p10 - p00) + ax * (p11 - p01)
+    cls = np.full(v.size, ALIGN_USED, dtype=np.int64)
+    if skip_zero:
+        cls[v == 0] = ALIGN_SKIPPED
+        cls[(b00 == 0) | (b01 == 0) | (b10 == 0) | (b11 == 0)] = ALIGN_MASKED
+    cls[~inside] = ALIGN_OUTSIDE
+    used = cls == ALIGN_USED
+    r = np.where(used, val - (float(gain) * v.astype(np.float64) + float(bias)), 0.0)
+    w, rho = align_huber(r, huber_k)
+    Ju = pair_project(lut, Q, calib)[3]
+    g = gx[:, None] * Ju[:, 0, :] + gy[:, None] * Ju[:, 1, :]
+    return dict(cls=cls, r=r, w=np.where(used, w, 0.0), rho=np.where(used, rho, 0.0), g=np.where(used[:, None], g, 0.0))
+
+
+def pair_sums(terms, with_scale=False):
+    """The ten sums and the four counts of one pair's terms: align_sums."""
+    return align_sums(terms, with_scale)
+
+
+def pair_information(sums, counts, floor=0.0):
+    """Lambda [..., 6] = H / s^2 (00 01 02 11 12 22) with s^2 = cost / max(n - 3, 1), of sums [..., 10] and counts [..., 4] (or n itself).  floor: a lower
+    bound on s^2 (byte units squared), 0 for the rule as it stands; PAIR_NOISE_FLOOR is the variance a byte's rounding alone leaves, what two frames that
+    happen to agree bit for bit (s^2 = 0, an infinite information) still differ by."""
+    sums = np.asarray(sums, dtype=np.float64)
+    n = np.asarray(counts, dtype=np.int64)
+    n = n[..., 0] if n.ndim == sums.ndim else n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s2 = np.maximum(sums[..., 9] / np.maximum(n - 3, 1).astype(np.float64), float(floor))
+        return sums[..., :6] / s2[..., None]
+
+
+def pair_align(frames_u8, pairs, Q_xyzw, lut, calib, sensor, gain=None, bias=None, skip_zero=False, **settings):
+    """The loop of emba_frames_pair_align in numpy, with numpy's own uv: per pair (i, j) of frames_u8 [F, S] the Levenberg-Marquardt iteration of align_step
+    (align_rule.h) on pair_terms' sums, as align_frames runs it.  sensor: (sw, sh).  A dict of q [P, 4], sums [P, 10], counts [P, 4], status, iters, cost0,
+    n0 [P] and info [P, 6]."""
+    s = align_settings(**settings)
+    sw, sh = int(sensor[0]), int(sensor[1])
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    P = pairs.shape[0]
+    Q_in = np.asarray(Q_xyzw, dtype=np.float64).reshape(P, 4)
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(-1, sh * sw)
+    a = np.ones(P) if gain is None else np.broadcast_to(np.asarray(gain, dtype=np.float64), (P,))
+    b = np.zeros(P) if bias is None else np.broadcast_to(np.asarray(bias, dtype=np.float64), (P,))
+
+    def evaluate(p, q):
+        i, j = pairs[p]
+        return pair_sums(pair_terms(frames[i], frames[j].reshape(sh, sw), pair_project(lut, q, calib)[1], lut, q, calib, a[p], b[p], skip_zero, s["huber_k"]))
+
+    out = dict(q=Q_in.copy(), sums=np.zeros((P, 10)), counts=np.zeros((P, 4), np.int64), status=np.zeros(P, np.int32), iters=np.zeros(P, np.int32),
+               cost0=np.zeros(P), n0=np.zeros(P, np.int64))
+    for p in range(P):
+        q = Q_in[p].copy()
+        sums, counts = evaluate(p, q)
+        out["cost0"][p], out["n0"][p] = sums[9], counts[0]
+        lam, iters = float(s["lambda0"]), 0
+        while True:
+            delta = align_step(sums[:6], sums[6:9], lam) if counts[0] >= s["min_pixels"] else None
+            if delta is None:
+                status = ALIGN_DEGENERATE
+                break
+            if iters >= s["max_iters"]:
+                status = ALIGN_ITERATIONS
+                break
+            trial = so3.mul(so3.exp(delta), q)
+            tsums, tcounts = evaluate(p, trial)
+            iters += 1
+            if tcounts[0] >= s["min_pixels"] and tsums[9] / tcounts[0] < sums[9] / counts[0]:
+                q, sums, counts = trial, tsums, tcounts
+                lam = max(lam / s["lambda_down"], s["lambda_min"])
+                if np.linalg.norm(delta) < s["tol_rot"]:
+                    status = ALIGN_CONVERGED
+                    break
+            else:
+                lam *= s["lambda_up"]
+                if lam > s["lambda_max"]:
+                    status = ALIGN_STALLED
+                    break
+        out["q"][p], out["sums"][p], out["counts"][p], out["status"][p], out["iters"][p] = q, sums, counts, status, iters
+    out["info"] = pair_information(out["sums"], out["counts"])
+    return out
+
+
+def pair_candidates(q, status, window=1, min_gap=None, max_angle=0.0, max_per_frame=0):
+    """The pairs (i, j), i < j, sorted, that a loop closure tries, from tracked rotations q [F, 4] and status [F] (io.TRACK_*; lost frames take no part): every
+    pair of voting frames with j - i <= window, and, for |j - i| > min_gap (None: window), per frame the max_per_frame frames with the smallest rotation angle
+    <= max_angle (rad) to it, ties to the lower index.  O(F^2) on the host; refused above PAIR_MAX_CANDIDATE_FRAMES frames."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, 4)
+    F = q.shape[0]
+    if F > PAIR_MAX_CANDIDATE_FRAMES:
+        raise ValueError(f"F = {F}: the candidate search is O(F^2) on the host and bounded at {PAIR_MAX_CANDIDATE_FRAMES} frames")
+    st = np.asarray(status, dtype=np.int64).reshape(-1)
+    if st.size != F:
+        raise ValueError(f"status must be [{F}]")
+    votes = (st == TRACK_ANCHOR) | (st == 2)
+    gap = int(window) if min_gap is None else int(min_gap)
+    out = set()
+    idx = np.flatnonzero(votes)
+    for i in idx:
+        for j in idx[(idx > i) & (idx - i <= int(window))]:
+            out.add((int(i), int(j)))
+    if max_per_frame > 0 and idx.size:
+        qn = q / np.linalg.norm(q, axis=1, keepdims=True)
+        ang = 2.0 * np.arccos(np.clip(np.abs(qn @ qn.T), 0.0, 1.0))
+        for i in idx:
+            cand = idx[(np.abs(idx - i) > gap) & (ang[i, idx] <= float(max_angle))]
+            order = cand[np.argsort(ang[i, cand], kind="stable")][:int(max_per_frame)]
+            for j in order:
+                out.add((int(min(i, j)), int(max(i, j))))
+    return np.array(sorted(out), dtype=np.int32).reshape(-1, 2)
+
+
+def graph_settings(**kw):
+    """GRAPH_DEFAULTS with the given members replaced; the refusals of emba_rotation_graph_solve's settings as ValueError."""
+    unknown = set(kw) - set(GRAPH_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)}")
+    s = dict(GRAPH_DEFAULTS, **kw)
+    ok = (int(s["max_iters"]) >= 0 and int(s["cg_max_iters"]) >= 1 and np.isfinite(s["lambda0"]) and s["lambda0"] > 0.0 and np.isfinite(s["lambda_up"])
+          and np.isfinite(s["lambda_down"]) and s["lambda_up"] > 1.0 and s["lambda_down"] > 1.0 and 0.0 <= s["lambda_min"] <= s["lambda_max"]
+          and s["lambda_max"] > 0.0 and s["tol"] >= 0.0 and s["cg_tol"] >= 0.0)
+    if not ok:
+        raise ValueError(f"settings out of range: {s}")
+    return s
+
+
+def graph_log(q):
+    """The rotation vector of the shorter way round of the quaternion q (xyzw): graph_qlog."""
+    q = np.asarray(q, dtype=np.float64)
+    q = -q if q[3] < 0.0 else q
+    n2 = float(q[:3] @ q[:3])
+    if n2 < 1e-20:
+        f = 2.0 / q[3] - (2.0 / 3.0) * n2 / q[3] ** 3
+    else:
+        n = np.sqrt(n2)
+        f = 2.0 * np.arctan2(n, q[3]) / n
+    return f * q[:3]
+
+
+def graph_jr_inv(e):
+    """Jr^-1(e) = I + [e]x / 2 + c [e]x^2, c = (1 - (th / 2) cot(th / 2)) / th^2: graph_jr_inv."""
+    e = np.asarray(e, dtype=np.float64)
+    th2 = float(e @ e)
+    if th2 < 1e-8:
+        c = 1.0 / 12.0 + th2 / 720.0
+    else:
+        th = np.sqrt(th2)
+        c = (1.0 - 0.5 * th * np.cos(0.5 * th) / np.sin(0.5 * th)) / th2
+    K = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
+    return np.eye(3) + 0.5 * K + c * (K @ K)
+
+
+def _graph_info(info6):
+    a = np.asarray(info6, dtype=np.float64)
+    return np.array([[a[0], a[1], a[2]], [a[1], a[3], a[4]], [a[2], a[4], a[5]]])
+
+
+def graph_residual(Qij, qi, qj):
+    """e = log(Q_ij (x) q_i^-1 (x) q_j)."""
+    return graph_log(so3.mul(so3.mul(Qij, so3.inverse(qi)), qj))
+
+
+def rotation_graph_solve(q_xyzw, status, edges, Q_xyzw, info, **settings):
+    """emba_rotation_graph_solve in numpy (graph_rule.h): the anchors of status (TRACK_ANCHOR) held exactly, damped Gauss-Newton with the linear system
+    assembled densely and solved directly, where the C form runs preconditioned conjugate gradients to cg_tol: the two agree to that tolerance.  A dict of q,
+    cost0, cost, iters, end.  The refusals are graph_args_ok's, in its order, as ValueError: the settings, a q that is not finite or of zero norm, no anchor,
+    an edge out of range, an edge's Q not finite or of zero norm, an info that is not finite, the first unreachable frame (named in the message)."""
+    from . import synth
+    s = graph_settings(**settings)
+    q = np.array(q_xyzw, dtype=np.float64).reshape(-1, 4)
+    st = np.asarray(status, dtype=np.int64).reshape(-1)
+    F = q.shape[0]
+    ed = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    E = ed.shape[0]
+    Qe = np.asarray(Q_xyzw, dtype=np.float64).reshape(E, 4)
+    Lam = np.asarray(info, dtype=np.float64).reshape(E, 6)
+    def first_bad(quats):      # the first quaternion that is not finite or has zero norm (align_q_ok), None where there is none
+        n2 = (quats * quats).sum(axis=1)
+        bad = np.flatnonzero(~(np.isfinite(n2) & (n2 > 0.0)))
+        return int(bad[0]) if bad.size else None
+
+    if st.size != F:
+        raise ValueError(f"status must be [{F}]")
+    if first_bad(q) is not None:      # (the refusals in graph_args_ok's order)
+        raise ValueError(f"q_xyzw[{first_bad(q)}] is not finite or has zero norm")
+    if not (st == TRACK_ANCHOR).any():
+        raise ValueError("no anchor: a rotation graph needs a frame that is held")
+    if E and (ed.min() < 0 or ed.max() >= F):
+        raise ValueError("an edge names a frame outside [0, F)")
+    if first_bad(Qe) is not None:
+        raise ValueError(f"Q_xyzw[{first_bad(Qe)}] is not finite or has zero norm")
+    if not np.isfinite(Lam).all():
+        raise ValueError("an info is not finite")
+    reached = st == TRACK_ANCHOR
+    grew = True
+    while grew:
+        grew = False
+        for i, j in ed:
+            if reached[i] != reached[j]:
+                reached[i] = reached[j] = True
+                grew = True
+    touched = np.zeros(F, bool)
+    touched[ed.reshape(-1)] = True
+    bad = np.flatnonzero(touched & ~reached)
+    if bad.size:
+        raise ValueError(f"frame {int(bad[0])} is named by an edge, but no path of edges leads from an anchor to it")
+    free = touched & (st != TRACK_ANCHOR)
+
+    def cost_of(qq):
+        return float(sum(e @ _graph_info(Lam[k]) @ e for k in range(E) for e in [graph_residual(Qe[k], qq[ed[k, 0]], qq[ed[k, 1]])]))
+
+    q_in = q.copy()
+    cost0 = cost = cost_of(q)
+    out = dict(q=q_in.copy(), cost0=cost0, cost=cost, iters=0, end=GRAPH_CONVERGED)
+    if not free.any():
+        return out
+    lam, iters, end = float(s["lambda0"]), 0, GRAPH_ITERATIONS
+    col = -np.ones(F, np.int64)
+    col[free] = np.arange(int(free.sum()))
+    n = 3 * int(free.sum())
+    while iters < s["max_iters"]:
+        A, g = np.zeros((n, n)), np.zeros(n)
+        for k in range(E):
+            i, j = ed[k]
+            if i == j:
+                continue
+            e = graph_residual(Qe[k], q[i], q[j])
+            M = graph_jr_inv(e) @ synth._quat_to_R(q[j]).T
+            L = _graph_info(Lam[k])
+            W, ge = M.T @ L @ M, M.T @ (L @ e)
+            for a_, sa in ((i, -1.0), (j, 1.0)):
+                if col[a_] < 0:
+                    continue
+                ra = slice(3 * col[a_], 3 * col[a_] + 3)
+                g[ra] += sa * ge
+                for b_, sb in ((i, -1.0), (j, 1.0)):
+                    if col[b_] >= 0:
+                        A[ra, 3 * col[b_]:3 * col[b_] + 3] += sa * sb * W
+        try:
+            x = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+        except np.linalg.LinAlgError:
+            end = GRAPH_DEGENERATE
+            break
+        trial = q.copy()
+        for f in np.flatnonzero(free):
+            trial[f] = so3.mul(so3.exp(x[3 * col[f]:3 * col[f] + 3]), q[f])
+        c1 = cost_of(trial)
+        iters += 1
+        dmax = float(np.abs(x).max())
+        if c1 < cost:
+            q, cost = trial, c1
+            lam = max(lam / s["lambda_down"], s["lambda_min"])
+            if dmax < s["tol"]:
+                end = GRAPH_CONVERGED
+                break
+        else:
+            if dmax < s["tol"]:
+                end = GRAPH_CONVERGED
+                break
+            lam *= s["lambda_up"]
+            if lam > s["lambda_max"]:
+                end = GRAPH_STALLED
+                break
+    q[~free] = q_in[~free]
+    return dict(q=q, cost0=cost0, cost=cost, iters=iters, end=end)

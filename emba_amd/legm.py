@@ -652,6 +652,86 @@ class LEGM:
                     sweep=sweep[:int(done[0])], sweeps_done=int(done[0]), tracked=int(stats[0]), lost=int(stats[1]), dropped=int(stats[2]), skipped=int(stats[3]),
                     pm=pm)
 
+    def _pair_args(self, frames, pairs, Q_xyzw, gain, bias, calib):
+        S = self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size % S:
+            raise ValueError("frames must be F x sensor_height x sensor_width bytes")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = pairs.shape[0]
+        Q = np.ascontiguousarray(Q_xyzw, dtype=np.float64).reshape(-1, 4)
+        if Q.shape[0] != P:
+            raise ValueError(f"Q_xyzw must be [{P}, 4]")
+        a = None if gain is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float64), (P,)))
+        b = None if bias is None else np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (P,)))
+        fu, fv, cu, cv = (float(calib[k]) for k in ("fu", "fv", "cu", "cv"))
+        D = calib.get("D")
+        D = None if D is None else np.ascontiguousarray(np.concatenate([np.asarray(D, dtype=np.float64).ravel(), np.zeros(5)])[:5])
+        return frames, frames.size // S, S, pairs, P, Q, a, b, (fu, fv, cu, cv), D
+
+    def pair_eval(self, frames, pairs, Q_xyzw, calib, gain=None, bias=None, skip_zero=False, huber_k=0.0, want_uv=False, want_resid=False):
+        """One frame against another (emba_frames_pair_eval; the rule: include/emba_hip.h): for every pair (i, j) of `pairs` [P, 2] the normal equations of
+        the photometric alignment of frame i's pixels to frame j's bytes at the relative rotation Q_xyzw [P, 4] and the relative exposure (gain, bias:
+        [P], a scalar, or None for 1 and 0).  calib: a dict of fu, fv, cu, cv and D (five plumb_bob coefficients, or None).  A dict of sums [P, 10],
+        counts int64 [P, 4], uv [P, S, 2] and resid [P, S] (None unless asked for) — io.pair_terms and io.pair_sums given the same uv."""
+        frames, F, S, pairs, P, Q, a, b, k4, D = self._pair_args(frames, pairs, Q_xyzw, gain, bias, calib)
+        sums, counts = np.zeros((P, 10)), np.zeros((P, 4), np.uint64)
+        uv = np.empty((P, S, 2)) if want_uv else None
+        resid = np.empty((P, S)) if want_resid else None
+        self._check(self._L.emba_frames_pair_eval(self._ctx, _p(frames, _u8p), F, _p(pairs, _i32p), P, _p(Q, _dp), _p(a, _dp), _p(b, _dp), *k4, _p(D, _dp),
+                                                  1 if skip_zero else 0, float(huber_k), _p(sums, _dp), _p(counts, C.POINTER(C.c_uint64)), _p(uv, _dp),
+                                                  _p(resid, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), uv=uv, resid=resid)
+
+    def pair_align(self, frames, pairs, Q_xyzw, calib, gain=None, bias=None, skip_zero=False, **settings):
+        """Relative rotations from pairs of frames (emba_frames_pair_align): every pair's Q refined by align_frames' loop on pair_eval's normal equations
+        (arguments as pair_eval; settings: the members of io.ALIGN_DEFAULTS).  A dict of q [P, 4], sums [P, 10] and counts [P, 4] at q, status, iters,
+        cost0, n0 [P] as align_frames', and info [P, 6]: the pair's information about its rotation (io.pair_information).  io.pair_align is the same
+        loop in numpy."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        frames, F, S, pairs, P, Q, a, b, k4, D = self._pair_args(frames, pairs, Q_xyzw, gain, bias, calib)
+        cs = _lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                    float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]), float(s["huber_k"]))
+        q_out, sums, counts, info = Q.copy(), np.zeros((P, 10)), np.zeros((P, 4), np.uint64), np.zeros((P, 6))
+        status, iters, cost0, n0 = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P), np.zeros(P, np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_pair_align(self._ctx, _p(frames, _u8p), F, _p(pairs, _i32p), P, _p(Q, _dp), _p(a, _dp), _p(b, _dp), *k4, _p(D, _dp),
+                                                   1 if skip_zero else 0, C.addressof(cs), _p(q_out, _dp), _p(sums, _dp), _p(counts, u64p), _p(status, _i32p),
+                                                   _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p), _p(info, _dp)))
+        return dict(q=q_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64), info=info)
+
+    @staticmethod
+    def rotation_graph_solve(q_xyzw, status, edges, Q_xyzw, info, **settings):
+        """The rotation graph on the host (emba_rotation_graph_solve; the rule: include/emba_hip.h): q_xyzw [F, 4] with status [F] (io.TRACK_ANCHOR frames
+        are held exactly), edges [E, 2] with their relative rotations Q_xyzw [E, 4] and information info [E, 6]; settings: the members of
+        io.GRAPH_DEFAULTS.  A dict of q [F, 4], cost0, cost, iters, cg_iters, end (io.GRAPH_*).  It needs no context and no device.
+        io.rotation_graph_solve is the same solve in numpy."""
+        from . import io as emba_io
+        s = emba_io.graph_settings(**settings)
+        L = _lib.load()
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(-1, 4)
+        st = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+        F = q.shape[0]
+        if st.size != F:
+            raise ValueError(f"status must be [{F}]")
+        ed = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        E = ed.shape[0]
+        Qe = np.ascontiguousarray(Q_xyzw, dtype=np.float64).reshape(-1, 4)
+        inf = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 6)
+        if Qe.shape[0] != E or inf.shape[0] != E:
+            raise ValueError(f"Q_xyzw must be [{E}, 4] and info [{E}, 6]")
+        cs = _lib.EmbaGraphSettings(int(s["max_iters"]), int(s["cg_max_iters"]), float(s["lambda0"]), float(s["lambda_up"]), float(s["lambda_down"]),
+                                    float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol"]), float(s["cg_tol"]))
+        q_out, cost, iters, end, at = q.copy(), np.zeros(2), np.zeros(2, np.int32), np.zeros(1, np.int32), C.c_size_t(0)
+        rc = L.emba_rotation_graph_solve(_p(q, _dp), _p(st, _i32p), F, _p(ed, _i32p), _p(Qe, _dp), _p(inf, _dp), E, C.addressof(cs), _p(q_out, _dp),
+                                         _p(cost, _dp), _p(iters, _i32p), _p(end, _i32p), C.byref(at))
+        if rc != _lib.OK:
+            err = _lib.EmbaError(rc, L.emba_last_error(None).decode())
+            err.at = int(at.value)
+            raise err
+        return dict(q=q_out, cost0=float(cost[0]), cost=float(cost[1]), iters=int(iters[0]), cg_iters=int(iters[1]), end=int(end[0]))
+
     def simulate_events(self, step_t_ns, knots, t0_ns, dt_ns, plane=None, boundary="dirichlet", c_on=None, c_off=None, max_per_step=255, max_events=0):
         """A recording from a log-intensity plane and a trajectory, on the device (emba_simulate_events; the rule: include/emba_hip.h): the events of the
         F = len(step_t_ns) - 1 steps between the step times along the linear SO(3) spline (knots [K, 4], t0_ns, dt_ns), from the samples render_views gives

@@ -138,18 +138,35 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
     return traj, t_raw, q_raw, [row + (g, o) for row, g, o in zip(rows, gain, bias)], (g_all, b_all)
 
 
-def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print):
+def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print, calib=None, pairs_path=None):
     """--init-poses frames: poses from the frames alone.  The frames are tracked against their own growing mosaic on the device; the
     tracked frames' (t, q), sampled on a 5 ms grid over the span and held at both ends where the frames do not reach them, are the raw poses, and
     io.fit_ctrl_poses of them the trajectory.
     Lost frames are left out.  Returns (traj, t_raw, q_raw, rows): rows holds per frame the time, the rotation, the status, the overlap and the cost.
     --track-exposure bias / gain-bias: every frame carries a gain and a bias in byte units, estimated with its rotation, and votes its
     compensated bytes; the rows then end in the gain and the bias.
-    --track-refit N: N sweeps of the refit behind the tracker; the rows then end in the refit code."""
+    --track-refit N: N sweeps of the refit behind the tracker; the rows then end in the refit code.
+    --track-close: before any refit, pairs of tracked frames that see the same place are aligned with each other and the rotation
+    graph of the kept pairs is solved with the anchor held; pairs_path takes one line per pair."""
     kw = dict(q0=a.track_q0, levels=a.track_levels, batch=a.track_batch, predict=bool(a.track_predict), skip_zero=a.frames_skip_zero,
               min_overlap=a.track_min_overlap, huber_k=a.frames_huber)
     estimate = {"none": None, "bias": eio.EXPOSURE_BIAS, "gain-bias": eio.EXPOSURE_GAIN | eio.EXPOSURE_BIAS}[a.track_exposure]
     r = legm.track_frames(frames, t_ns, **kw) if estimate is None else legm.track_frames_exposure(frames, t_ns, estimate=estimate, **kw)
+    if a.track_close:      # loops closed among the tracked frames, before any refit (DESIGN.md section 26): the mosaic in the context is the closed one
+        from emba_amd.driver import SequenceSettings, close_tracked_frames
+        before = r["q"]
+        r = close_tracked_frames(legm, frames, t_ns, r, SequenceSettings(1.0, 1.0, track_close=True, close_window=a.close_window, close_gap=a.close_gap,
+                                                                         close_angle=a.close_angle, close_per_frame=a.close_per_frame, close_huber=a.close_huber),
+                                 calib, estimate=estimate or 0, **kw)
+        g = r["graph"]
+        log(f"track-close: {len(r['pairs'])} pairs, {int(r['pair_kept'].sum())} kept; "
+            + (f"graph cost {g['cost0']:.6g} -> {g['cost']:.6g} in {g['iters']} steps ({g['cg_iters']} CG iterations, {eio.GRAPH_END_NAMES[g['end']]}); "
+               f"worst change against the tracker {eio.rotation_angle_between(before, r['q']).max():.3g} rad" if g else "no graph: the tracker's rotations stay"))
+        if pairs_path:
+            with open(pairs_path, "w") as fh:
+                fh.write("# i j status(1 converged, 2 stalled, 3 iterations, 4 degenerate) n mean_cost moved[rad] kept\n")
+                for (i, j), st, n, c, mv, kp in zip(r["pairs"], r["pair_status"], r["pair_n"], r["pair_cost"], r["pair_moved"], r["pair_kept"]):
+                    fh.write(f"{i} {j} {int(st)} {int(n)} {c:.9g} {mv:.9g} {int(kp)}\n")
     if a.track_refit:      # the sweeps behind the tracker, before the raw poses are sampled (DESIGN.md section 25): the mosaic in the context is the refitted one
         from emba_amd.driver import SequenceSettings, refit_tracked_frames
         before = r["q"]
@@ -309,6 +326,17 @@ def main():
                     "out of the integer mosaic, aligned to the mosaic of all the other frames and voted back, before the raw poses are sampled; lost frames are "
                     "tried again; --init-map frames takes the refitted mosaic (DESIGN.md section 25; frames_tracked.txt gains the refit code as its last column: "
                     "1 anchor, 2 moved, 3 kept, 4 recovered, 5 lost).  0: off")
+    ap.add_argument("--track-close", action="store_true", help="--init-poses frames: behind the tracker and before --track-refit, close loops among the tracked "
+                    "frames: pairs of frames that see the same place are aligned with each other on the device and a rotation graph over all frames is solved "
+                    "with the anchor held exactly; --init-map frames takes the mosaic stitched again at the new rotations (DESIGN.md section 26; writes "
+                    "<out>/frames_pairs.txt: i j, the pair's code, n, the mean cost, the angle moved, kept)")
+    ap.add_argument("--close-window", type=int, default=1, metavar="N", help="with --track-close: every pair of voting frames at most N frames apart is tried")
+    ap.add_argument("--close-gap", type=int, default=4, metavar="N", help="... and, more than N frames apart, per frame the --close-per-frame nearest by rotation")
+    ap.add_argument("--close-angle", type=float, default=0.2, metavar="RAD", help="... whose tracked rotations differ by at most RAD")
+    ap.add_argument("--close-per-frame", type=int, default=2, metavar="N")
+    ap.add_argument("--close-huber", type=float, default=0.0, metavar="K", help="the Huber threshold of a pair's residuals in bytes (0: quadratic)")
+    ap.add_argument("--close-calib", metavar="fu,fv,cu,cv[,k1,k2,p1,p2,k3]", help="the camera the pairs project through (default: --calib's K and D; --demo: the "
+                    "demo's pinhole)")
     ap.add_argument("--track-refit-tol", type=float, default=0.0, metavar="X", help="with --track-refit: stop behind a sweep whose largest rotation change is below X rad (0: never)")
     ap.add_argument("--cmax-slice-events", type=int, default=10000, help="events per slice of the contrast maximisation (--init-poses events)")
     ap.add_argument("--cmax-omega-max", type=float, default=8.0, help="rad/s: the compass search of a slice starts with steps of half of this (--init-poses events)")
@@ -359,6 +387,10 @@ def main():
         ap.error("--track-exposure estimates the exposure inside the tracker of --init-poses frames: it needs --init-poses frames")
     if (a.track_refit or a.track_refit_tol) and a.init_poses != "frames":
         ap.error("--track-refit refits the frames tracked by --init-poses frames: it needs --init-poses frames")
+    if a.track_close and a.init_poses != "frames":
+        ap.error("--track-close closes loops among the frames tracked by --init-poses frames: it needs --init-poses frames")
+    if a.close_window < 0 or a.close_gap < 0 or a.close_per_frame < 0 or not a.close_angle >= 0.0 or np.isnan(a.close_huber):
+        ap.error("--close-window, --close-gap, --close-per-frame and --close-angle are not negative, --close-huber is a number")
     if a.track_refit < 0 or not a.track_refit_tol >= 0.0:
         ap.error("--track-refit N and --track-refit-tol X are not negative")
     if a.frames_exposure != "none" and not a.refine_frames:
@@ -479,7 +511,19 @@ def main():
         frames, frames_t_ns = load_frames(a.frames, sw, sh)
     tracked_mosaic = False
     if a.init_poses == "frames":      # poses from the frames alone: the tracked frames' rotations are the raw poses, the tracker's mosaic stays in the context
-        traj, t, qs, rows = track_frames(legm, frames, frames_t_ns, traj, t_beg, t_end, a, log=print if rank == 0 else (lambda *_: None))
+        close_calib = None
+        if a.track_close:
+            if a.close_calib:
+                v = [float(x) for x in a.close_calib.split(",")]
+                if len(v) not in (4, 9):
+                    ap.error("--close-calib takes fu,fv,cu,cv or fu,fv,cu,cv,k1,k2,p1,p2,k3")
+                close_calib = eio.pair_calib(*v[:4], v[4:] or None)
+            elif a.demo:
+                close_calib = eio.pair_calib(120.0, 120.0, sw / 2.0, sh / 2.0)
+            else:
+                close_calib = eio.pair_calib(cal["K"][0, 0], cal["K"][1, 1], cal["K"][0, 2], cal["K"][1, 2], cal["D"])
+        traj, t, qs, rows = track_frames(legm, frames, frames_t_ns, traj, t_beg, t_end, a, log=print if rank == 0 else (lambda *_: None), calib=close_calib,
+                                         pairs_path=os.path.join(a.out, "frames_pairs.txt") if a.track_close and rank == 0 else None)
         tracked_mosaic = True
         if rank == 0:
             with open(os.path.join(a.out, "frames_tracked.txt"), "w") as fh:

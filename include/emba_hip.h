@@ -897,6 +897,77 @@ emba_status emba_frames_refit(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw
                               double* overlap_out /* [F] */, double* sweep_out /* [sweeps, 4] */, int32_t* sweeps_done_out, uint64_t* stats_out /* [4] */,
                               double* pm_out /* [F, sh*sw, 2] */);
 
+/* ---- Loops closed among tracked frames: one frame aligned to another, and a rotation graph over all of them.  Every stage above compares a
+ * frame with a panorama plane; here two frames that see the same place are compared with each other, and all rotations are solved for at once with the
+ * anchors held exactly.  The rules live in emba_amd/csrc/pair_rule.h (over align_rule.h) and emba_amd/csrc/graph_rule.h; emba_amd.io.pair_* and
+ * io.rotation_graph_solve are the same rules in numpy.
+ *
+ *   a pair            p = (i, j): source frame i, target frame j, both of the context's sensor [sh, sw]; a relative rotation Q_p (xyzw; used as it is given: a unit
+ *                     quaternion) and a relative exposure (a_p, b_p), given and not estimated (NULL: 1 and 0).  A bearing
+ *                     b of camera i is the bearing R(Q_p) b of camera j: with camera-to-world rotations Q = q_j^-1 (x) q_i, and with per-frame exposures
+ *                     a = a_i / a_j, b = (b_i - b_j) / a_j.  i = j is a pair like any other, and a pair may be listed more than once.
+ *   project           rb = R(Q) bearing_lut[s] by frame_warp's matrix and three sums; rb_z <= 0 is outside.  x = rb_x / rb_z, y = rb_y / rb_z; the
+ *                     plumb_bob forward model with D = (k1, k2, p1, p2, k3) (NULL: zero, the pinhole): r2 = x^2 + y^2, c = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ *                     x' = x c + (2 p1 x y + p2 (r2 + 2 x^2)), y' = y c + (p1 (r2 + 2 y^2) + 2 p2 x y); u = fu x' + cu, v = fv y' + cv.  Without
+ *                     contraction.  The intrinsics are arguments of the call: the context holds the bearing table alone.
+ *   sample            frame j's bytes bilinearly at (u, v): ix = floor(u), iy = floor(v); outside for ix < 0, ix + 1 > sw - 1, iy < 0, iy + 1 > sh - 1, a
+ *                     point that is not finite or >= 2^31 in size.  No wrap.  val, gx, gy are emba_frames_align's expressions on the four bytes as doubles.
+ *   classes           emba_frames_align's four in its precedence: outside; masked: skip_zero and any of the four target bytes is 0; skipped: skip_zero
+ *                     and the source byte is 0; used.
+ *   term              r = val - (a v + b) in byte units (multiply, add, subtract: no contraction); the Huber weight of emba_frames_align;
+ *                     g = gx Ju[0,:] + gy Ju[1,:] with Ju = d(u, v) / d rb (-[rb]x): the left perturbation Q <- exp(delta) Q.  The ten sums and the four
+ *                     counts are emba_frames_align's, summed in a fixed order: the same inputs give the same bits.
+ *   loop              emba_frames_align's, per pair, under the same settings, with the same four ways to end.
+ *   information       info [6] = H / s^2 (00 01 02 11 12 22), s^2 = cost / max(n - 3, 1), of the accepted state: in camera j's coordinates.
+ *
+ * emba_frames_pair_eval: one evaluation of every pair at Q.  Outputs, each may be NULL: sums_out [P, 10], counts_out [P, 4] (used, outside, masked,
+ * skipped), uv_out [P, sh*sw, 2] (NaN where rb_z <= 0), resid_out [P, sh*sw] (0 where the pixel is not used).
+ * emba_frames_pair_align: the loop; q_out, sums_out, counts_out, status_out (EMBA_ALIGN_*), iters_out, cost0_out, n0_out as emba_frames_align's, info_out
+ * [P, 6].  The frames are uploaded once, whole, into a buffer of this stage's own; the pairs are cut into chunks of at most 65 535 (and 32 MiB of source
+ * pixels); a chunk's state stays on the device between iterations.  P = 0 launches nothing.  Timer slot 7 as in emba_frames_align.
+ * Refusals, before anything is uploaded, every output untouched, EMBA_ERR_INVALID_ARG in this order: frames, pairs or Q NULL with P > 0; P >= 2^31; a pair
+ * with a frame outside [0, F); a Q that is not finite or of zero norm; a gain that is not finite or not positive, a bias that is not finite; fu or fv not
+ * finite or not positive; cu or cv not finite; a D that is not finite; huber_k a NaN; the settings as emba_frames_align refuses them; F * sh * sw above
+ * 2^30 bytes (the sequence is resident for the whole call).  Nothing of the registered window, the last evaluation, the resident sequence, the mosaic, the
+ * level planes, the resident map or any other stage's buffers is written. */
+emba_status emba_frames_pair_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* pairs /* [P, 2] */, size_t P,
+                                  const double* Q_xyzw /* [P, 4] */, const double* gain /* [P] or NULL */, const double* bias /* [P] or NULL */, double fu, double fv,
+                                  double cu, double cv, const double* D /* [5] or NULL */, int32_t skip_zero, double huber_k, double* sums_out /* [P, 10] */,
+                                  uint64_t* counts_out /* [P, 4] */, double* uv_out /* [P, sh*sw, 2] */, double* resid_out /* [P, sh*sw] */);
+emba_status emba_frames_pair_align(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* pairs /* [P, 2] */, size_t P,
+                                   const double* Q_xyzw /* [P, 4] */, const double* gain /* [P] or NULL */, const double* bias /* [P] or NULL */, double fu, double fv,
+                                   double cu, double cv, const double* D /* [5] or NULL */, int32_t skip_zero, const emba_align_settings* settings,
+                                   double* q_out /* [P, 4] */, double* sums_out /* [P, 10] */, uint64_t* counts_out /* [P, 4] */, int32_t* status_out /* [P] */,
+                                   int32_t* iters_out /* [P] */, double* cost0_out /* [P] */, uint64_t* n0_out /* [P] */, double* info_out /* [P, 6] */);
+
+/* emba_rotation_graph_solve: the rotation graph, on the host (it needs no context; emba_last_error(NULL) has the message of a refusal).
+ *   unknowns          one rotation per frame (camera to world, xyzw).  Frames whose status is EMBA_TRACK_ANCHOR are constants: the gauge is exact.  A frame
+ *                     that no edge names keeps its input.  q_out of either is the input bit for bit.
+ *   edge              (i, j, Q_ij, Lambda_ij [6]: 00 01 02 11 12 22): e = log(Q_ij (x) q_i^-1 (x) q_j), the rotation vector of the shorter way round, in
+ *                     camera j's coordinates, where emba_frames_pair_align's info lives.  The cost is the sum of e^T Lambda e over the edges.
+ *   step              with q <- exp(delta) q on both ends e' ~ e + Jr^-1(e) R_j^T (delta_j - delta_i); (A + lambda diag A) delta = -g by conjugate
+ *                     gradients with the 3 x 3 block-Jacobi preconditioner, matrix-free over the edges in edge order, ended at |r| <= cg_tol |r0| or
+ *                     behind cg_max_iters iterations.  The trial is accepted when its cost is below the cost: lambda <- max(lambda / lambda_down,
+ *                     lambda_min); otherwise lambda <- lambda lambda_up.
+ *   ends              EMBA_GRAPH_CONVERGED: |delta|_inf < tol (also: nothing is free); EMBA_GRAPH_STALLED: lambda > lambda_max; EMBA_GRAPH_ITERATIONS:
+ *                     max_iters trials; EMBA_GRAPH_DEGENERATE: a diagonal block is not positive definite.
+ * Outputs, each may be NULL: q_out [F, 4]; cost_out [2]: before and behind; iters_out [2]: the trials and the conjugate-gradient iterations of all of
+ * them; end_out; at_out: the frame or edge a refusal names.  Refusals, EMBA_ERR_INVALID_ARG in this order, every output but at_out untouched: q or status
+ * NULL with F > 0; edges, Q or info NULL with E > 0; settings NULL or out of range; a q that is not finite or of zero norm; no anchor; an edge with a frame
+ * outside [0, F); an edge's Q not finite or of zero norm; an info that is not finite; a frame that is no anchor, that an edge names and that no path of
+ * edges connects to an anchor: the first such frame. */
+#define EMBA_GRAPH_CONVERGED 1
+#define EMBA_GRAPH_STALLED 2
+#define EMBA_GRAPH_ITERATIONS 3
+#define EMBA_GRAPH_DEGENERATE 4
+typedef struct {
+    int32_t max_iters, cg_max_iters;
+    double lambda0, lambda_up, lambda_down, lambda_min, lambda_max, tol, cg_tol;
+} emba_graph_settings;
+emba_status emba_rotation_graph_solve(const double* q_xyzw /* [F, 4] */, const int32_t* status /* [F] */, size_t F, const int32_t* edges /* [E, 2] */,
+                                      const double* Q_xyzw /* [E, 4] */, const double* info /* [E, 6] */, size_t E, const emba_graph_settings* settings,
+                                      double* q_out /* [F, 4] */, double* cost_out /* [2] */, int32_t* iters_out /* [2] */, int32_t* end_out, size_t* at_out);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
