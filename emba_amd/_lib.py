@@ -87,6 +87,7 @@ SIGNATURES = {
     "emba_costs_launch": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int32]),
     "emba_costs_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, _dp, _dp]),
     "emba_dump_state": (C.c_int, [C.c_void_p, _dp, _dp, _i32p, _i32p, _i32p, _dp, _dp, _dp]),
+    "emba_dump_segments": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _szp]),
     "emba_upload_map": (C.c_int, [C.c_void_p, _dp, _dp]),
     "emba_bind_map_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "emba_solve_normal_eq": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, _dp, _dp]),

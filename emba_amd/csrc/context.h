@@ -78,8 +78,10 @@ struct EvalState {
     uint32_t count_stamp = 0;     // record stamp (set_stamp) of the evaluation whose materialised, LOCAL counts d_count_own holds; 0: none (build_lists)
     int acc_irls = 0; double acc_eta = 0.0;   // the robust cost the per-pixel sums of this evaluation were weighted with
     int use_texel = 0;            // the Hessian source this evaluation uses: 0 fly, 1 full pack, 3 rectangle (step_rule.h: hessian_source)
+    bool prep_on_host = false;    // no launch in front of the warp kernel: the host formed the segment records, they travel in the warp kernel's arguments (step_rule.h: prep_on_host)
     bool prep_in_warp = false;    // no launch in front of the warp kernel: its workgroup 0 formed the segment records (step_rule.h: prep_inside_warp)
     bool texels_packed = false;   // the launch in front of the warp kernel carried texel blocks (source 3: only when the texels were stale)
+    int n_seg = 0;                // segment records this evaluation left in d_seg (K - 1 in the tile order and with segpose, else none): emba_dump_segments
     bool segpose = false;         // pixel order: this evaluation takes the pose per event from segment records (option segpose); emba_dump_state re-warps the same way
     bool readable() const { return launched && (done || inl_pending || ep_deferred); }   // there is an evaluation whose residuals / counts can be asked for
 };
@@ -349,7 +351,8 @@ struct emba_ctx {
     int texel_mode = 0;   // 0 auto, 1 pack every texel, 2 always on-the-fly stencil, 3 texel rectangle (option texel)
     DevBuf d_rect;       // [0..3] {xmin,ymin,xmax,ymax} of the pixels the last formed evaluation touched; [4..7] the box the texels are PACKED for (what the warp kernel trusts)
     uint32_t seg_seq = 0;     // the flag value of the last in-warp hand-off of segment records (never 0: the flag word starts at 0)
-    int step_prep = 0, step_prep_polls = 1024;   // option step_prep (A/B): 0 (default) the launch in front of the warp kernel always, 1 none where its work fits the warp launch; option step_prep_polls: the consumers' poll budget (0: none)
+    int step_prep = 2, step_prep_polls = 1024;   // option step_prep (A/B): 0 the launch in front of the warp kernel always, 1 none where its work fits the warp launch, 2 (default) none where the host can form the records; option step_prep_polls: the consumers' poll budget (0: none)
+    emba::SegHostDuties seg_duties{}; emba::SegRecordsByValue seg_host{};   // ... and where the host formed the records (ev.prep_on_host)
     emba::InlineSegParams seg_inline{}; emba::InlineKnots seg_knots{};   // what launch_prep_pose_texel leaves for the warp launch of the same evaluation (ev.prep_in_warp)
     DevBuf d_seg_flag;   // [0] the segment records' flag (a line of its own), [32] waves that formed their records themselves (diagnostics)
     DevBuf d_blk_rect;   // per prep-block boxes

@@ -143,7 +143,8 @@ __device__ __forceinline__ void pose_thread(int b, const int64_t* __restrict__ b
 }
 
 // Tile order: per-SEGMENT constants instead (device_math.h: segment_consts / spline2_event); thread s fills segment s of seg[12 s].
-constexpr int kSegStride = 12;
+constexpr int kSegStride = kSegRecordDoubles;   // (seg_record_rule.h: the host strides its records by the same constant)
+static_assert(kSegStride == 12, "a record is {p0[4], delta[3], r1, k[3], r2}");
 // (the record of segment sidx as VALUES: whoever forms it — the prep launch, workgroup 0 of the warp launch, a wave that gave up waiting for that one — gets the
 // same bits, and nothing downstream is contracted into the chain: the values pass through registers the compiler cannot see into)
 __device__ __forceinline__ void seg_record(int sidx, const double* __restrict__ knots, double* __restrict__ o)
@@ -384,6 +385,39 @@ __device__ __forceinline__ bool inline_seg_wait(const InlineSegParams& h)
     return ready;
 }
 
+// ---- the segment records formed on the HOST (step_rule.h: prep_on_host; seg_record_rule.h: segment_records) ---------------------------------------------------
+// The same steady step — clean lines, fresh texels, pixel order with the pose per event — with the K - 1 records computed by the host thread (the chain of the prep
+// launch compiled for the host, while the previous Gram launch still runs) and handed to the warp kernel BY VALUE in its arguments: no launch in front, no
+// producer inside, no flag.  Every one-wave workgroup copies the (K - 1) x 96 B it may index from the argument segment into LDS behind its event-word loads — into
+// the bytes of the record staging tile, which is not used before the per-event part is over, so the kernel's LDS and its waves per SIMD stay what they were — and
+// the per-event pose reads LDS.  Workgroup 0 takes over block 0's other duties of the launch this replaces, and leaves the records in d_seg with plain vector
+// stores for whoever reads them AFTER the launch (dumps, the tile order's preparation, the solvers): nothing in the launch reads them back.
+// The carrier's size: a dispatch's argument segment is 4096 B, of which the compiler keeps up to 256 B for its hidden arguments behind the explicit ones.
+constexpr int kKernargBytes = 4096, kKernargHiddenBytes = 256;
+struct SegHostDuties {
+    double* seg_out; double* knots_out; int* err_next;   // d_seg; the device copy of the control poses; the next evaluation's status word
+    int K;
+    double last_knot[4];                                 // control pose K - 1 (poses 0 ... K - 2 are the records' p0)
+};
+constexpr int kSegByValue = (int)((kKernargBytes - kKernargHiddenBytes - sizeof(WarpParams) - sizeof(SegHostDuties)) / (kSegStride * sizeof(double)));   // records; K <= kSegByValue + 1
+struct alignas(16) SegRecordsByValue { double r[kSegStride * kSegByValue]; };   // (16-B copies out of the argument segment)
+static_assert(sizeof(WarpParams) + sizeof(SegHostDuties) + sizeof(SegRecordsByValue) + kKernargHiddenBytes <= kKernargBytes, "the records must fit the argument segment beside the kernel's other arguments");
+static_assert(kSegByValue >= 20, "the benchmark's K = 21 must travel by value");
+static_assert(kSegStride * kSegByValue <= 32 * kRecLds, "the records share the bytes of the record staging tile");
+static_assert(kSegStride % 2 == 0 && sizeof(WarpParams) % 16 == 0 && sizeof(SegHostDuties) % 16 == 0, "16-B copies of the records");
+
+__device__ __forceinline__ void host_seg_duties(const SegHostDuties& d, const SegRecordsByValue& sr, int t)
+{
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    const int n2 = (d.K - 1) * (kSegStride / 2);
+    for (int k = t; k < n2; k += kWarpBlock) reinterpret_cast<v2d*>(d.seg_out)[k] = reinterpret_cast<const v2d*>(sr.r)[k];
+    if (t == 63) d.err_next[0] = 0;
+    if (d.knots_out) {      // (for whoever reads the device copy later; the two sources in loops of their own: each stays a load from the argument segment)
+        for (int i = t; i < 4 * (d.K - 1); i += kWarpBlock) d.knots_out[i] = sr.r[kSegStride * (i >> 2) + (i & 3)];
+        if (t < 4) d.knots_out[4 * (d.K - 1) + t] = d.last_knot[t];
+    }
+}
+
 // What one lane knows about its measurement after the shared part.
 #ifndef WARP_LATE_EP
 #define WARP_LATE_EP 0     // pixel-order kernel: residual / flag stores issued after the record stores and atomics instead of in the middle
@@ -423,8 +457,9 @@ struct NoPrefetch { __device__ __forceinline__ void operator()() const {} };
 // SEGPOSE (round 4; pixel order with a LARGE window): the pose is evaluated per event from its batch's spline parameter and segment record, as in the tile
 // order, instead of gathered from the per-batch table — at 10 M events that table is 11 MB of 112-B records, every event pulls one or two 128-B lines of it
 // past the L2 (counters: 1.37x the algorithmic bytes); u and the segment travel per entry with the event words (10 B, streamed), the K-1 segment records are a few KB.
-template <bool DUMP, bool COMPACT = false, class PF = NoPrefetch, bool LATE_EP = false, bool SEGPOSE = false, bool INLINE_SEG = false>
-__device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const LaneIn& in, int t, LaneOut& o, PF prefetch = PF(), const InlineSegLane* is = nullptr)
+// SEG_SRC: where a lane reads its segment record — 0 p.seg, 1 the records written inside this launch (inline_seg_*), 2 the workgroup's LDS copy of the host's records (s_seg)
+template <bool DUMP, bool COMPACT = false, class PF = NoPrefetch, bool LATE_EP = false, bool SEGPOSE = false, int SEG_SRC = 0>
+__device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const LaneIn& in, int t, LaneOut& o, PF prefetch = PF(), const InlineSegLane* is = nullptr, const double* s_seg = nullptr)
 {
     const bool valid = in.valid;
     double pm[2] = {0, 0};
@@ -447,7 +482,7 @@ __device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const Lan
             // prefetched with the event words they cost 24 VGPRs per pipeline stage)
             const uint32_t sg = bi; const double uu = in.u;
             double seg[kSegStride];
-            if (INLINE_SEG) {   // the records were written inside this launch (inline_seg_*): sc1 loads only
+            if (SEG_SRC == 1) {   // the records were written inside this launch (inline_seg_*): sc1 loads only
                 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
                 typedef double v2d __attribute__((ext_vector_type(2)));
                 const int off = (int)(sg * (uint32_t)(kSegStride * sizeof(double)));
@@ -457,7 +492,8 @@ __device__ __forceinline__ void warp_lane(const WarpParams& p, long i, const Lan
                     seg[2 * k] = v.x; seg[2 * k + 1] = v.y;
                 }
             } else {
-                const double2* S2 = reinterpret_cast<const double2*>(p.seg + (size_t)kSegStride * (EMBA_ABL(p.ablate, 16) ? (sg & 1u) : sg));
+                const double2* S2 = (SEG_SRC == 2) ? reinterpret_cast<const double2*>(s_seg + kSegStride * sg)
+                                                   : reinterpret_cast<const double2*>(p.seg + (size_t)kSegStride * (EMBA_ABL(p.ablate, 16) ? (sg & 1u) : sg));
                 const double2 s0 = S2[0], s1 = S2[1], s2 = S2[2], s3 = S2[3], s4 = S2[4], s5 = S2[5];
                 seg[0] = s0.x; seg[1] = s0.y; seg[2] = s1.x; seg[3] = s1.y; seg[4] = s2.x; seg[5] = s2.y;
                 seg[6] = s3.x; seg[7] = s3.y; seg[8] = s4.x; seg[9] = s4.y; seg[10] = s5.x; seg[11] = s5.y;
@@ -646,8 +682,8 @@ __device__ __forceinline__ void store_records(const WarpParams& p, int t, const 
 #ifndef WARP_OCC
 #define WARP_OCC
 #endif
-template <bool DUMP, bool COMPACT, bool SEGPOSE, bool INLINE_SEG>
-__device__ __forceinline__ void warp_residual_body(const WarpParams& p, const InlineSegParams* h, const double* knots)
+template <bool DUMP, bool COMPACT, bool SEGPOSE, int SEG_SRC>
+__device__ __forceinline__ void warp_residual_body(const WarpParams& p, const InlineSegParams* h, const double* knots, const SegHostDuties* hd = nullptr, const SegRecordsByValue* sr = nullptr)
 {
     // One wave per workgroup, LDS operations complete in order: the record staging tile (first) and the run sums (afterwards) share
     // the same bytes, so that LDS (160 KB per CU) does not cap the resident waves below what the registers allow.
@@ -658,7 +694,8 @@ __device__ __forceinline__ void warp_residual_body(const WarpParams& p, const In
     __shared__ uint32_t s_slot[32];                                         // record slots of the staged half's inliers
 
     const int t = threadIdx.x;   // == lane
-    if (INLINE_SEG && blockIdx.x == 0) inline_seg_produce(*h, knots, t, true);   // before anything else, and whether or not this workgroup has entries of its own
+    if (SEG_SRC == 1 && blockIdx.x == 0) inline_seg_produce(*h, knots, t, true);   // before anything else, and whether or not this workgroup has entries of its own
+    if (SEG_SRC == 2 && blockIdx.x == 0) host_seg_duties(*hd, *sr, t);
     const long b = xcd_contiguous_block(blockIdx.x, gridDim.x);
     if (b >= p.nblk) return;  // the whole wave exits together
     const long i = b * kWarpNew + t - 1;
@@ -666,14 +703,21 @@ __device__ __forceinline__ void warp_residual_body(const WarpParams& p, const In
     LaneOut o;
     LaneIn in;
     load_event_words<COMPACT, SEGPOSE>(p, i, valid, in);
-    if (INLINE_SEG) {
+    if (SEG_SRC == 2) {   // the host's records: argument segment -> LDS, behind the event-word loads just issued (one wave: LDS operations complete in order, no barrier;
+                          // vector loads return in order, so these LDS writes wait for the event words as well: no extra round trip, and nothing hidden that was measured)
+        typedef double v2d __attribute__((ext_vector_type(2)));
+        const int n2 = (hd->K - 1) * (kSegStride / 2);       // <= kSegByValue * kSegStride / 2 (step_rule.h: prep_on_host): inside s_tile
+        for (int k = t; k < n2; k += kWarpBlock) reinterpret_cast<v2d*>(s_tile)[k] = reinterpret_cast<const v2d*>(sr->r)[k];
+        warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE, 2>(p, i, in, t, o, NoPrefetch(), nullptr, s_tile);
+        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the record reads are done before the staging tile takes the same bytes
+    } else if (SEG_SRC == 1) {
         InlineSegLane is;
         is.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)h->seg, 0, (int)h->seg_bytes, 0x00020000);    // raw buffer, 32-bit data format; loads past seg_bytes return 0
         if (blockIdx.x != 0 && !inline_seg_wait(*h)) {       // (workgroup 0 has returned from inline_seg_produce: its own stores are drained)
             inline_seg_produce(*h, knots, t, false);
             if (t == 0) atomicAdd(h->fallbacks, 1u);
         }
-        warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE, true>(p, i, in, t, o, NoPrefetch(), &is);
+        warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE, 1>(p, i, in, t, o, NoPrefetch(), &is);
     } else {
         warp_lane<DUMP, COMPACT, NoPrefetch, (WARP_LATE_EP != 0) && !DUMP, SEGPOSE>(p, i, in, t, o);
     }
@@ -751,7 +795,7 @@ __device__ __forceinline__ void warp_residual_body(const WarpParams& p, const In
 template <bool DUMP, bool COMPACT = false, bool SEGPOSE = false>
 __global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel(WarpParams p)
 {
-    warp_residual_body<DUMP, COMPACT, SEGPOSE, false>(p, nullptr, nullptr);
+    warp_residual_body<DUMP, COMPACT, SEGPOSE, 0>(p, nullptr, nullptr);
 }
 // pixel order, pose per event, the segment records formed by workgroup 0 of this launch (inline_seg_*)
 // (five waves per SIMD like the form it replaces: the producer's chain — so3_log, sin, cos: 128 VGPRs on its own — spills 144 B per lane in the two places that run
@@ -761,7 +805,12 @@ __global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_kernel
 #endif
 __global__ __launch_bounds__(kWarpBlock) EMBA_INLINE_WARP_OCC void emba_warp_residual_inline_kernel(WarpParams p, InlineSegParams h, InlineKnots kn)
 {
-    warp_residual_body<false, false, true, true>(p, &h, kn.q);
+    warp_residual_body<false, false, true, 1>(p, &h, kn.q);
+}
+// pixel order, pose per event, the segment records formed by the host and carried in the arguments (SegRecordsByValue)
+__global__ __launch_bounds__(kWarpBlock) WARP_OCC void emba_warp_residual_hostseg_kernel(WarpParams p, SegHostDuties d, SegRecordsByValue sr)
+{
+    warp_residual_body<false, false, true, 2>(p, nullptr, nullptr, &d, &sr);
 }
 
 // Tile order: blockIdx -> chunk of one panorama bin's events (ChunkDesc).  The workgroup's waves take the chunk's 63-entry groups

@@ -39,8 +39,8 @@ const OptionRef kOptions[] = {
     {"solve_debug", &emba_ctx::opt_solve_debug, 0, 1, false},
     {"poisson", &emba_ctx::opt_poisson, 0, 2, false},
     {"gemm64", &emba_ctx::opt_gemm64, 0, 1, false},
-    // the hand-off of the segment records inside the warp launch (step_rule.h: prep_inside_warp)
-    {"step_prep", &emba_ctx::step_prep, 0, 1, false},
+    // who forms the steady step's segment records: the launch in front of the warp kernel, workgroup 0 of the warp launch, the host (step_rule.h: prep_inside_warp, prep_on_host)
+    {"step_prep", &emba_ctx::step_prep, 0, 2, false},
     {"step_prep_polls", &emba_ctx::step_prep_polls, 0, 1 << 16, false},
     // the vote kernel of emba_seq_contrast_gradient_level (contrast_rule.h: contrast_vote_plan)
     {"contrast_vote", &emba_ctx::opt_contrast_vote, -1, 1, false},
@@ -63,6 +63,8 @@ emba_status read_step_prep_fallbacks(emba_ctx* c, int32_t* value)
 // read-only names: what the last call of its kind did
 struct ReadOnlyRef { const char* name; emba_status (*read)(emba_ctx*, int32_t*); };
 const ReadOnlyRef kReadOnly[] = {
+    {"prep_on_host", [](emba_ctx* c, int32_t* v) { *v = c->ev.prep_on_host ? 1 : 0; return EMBA_OK; }},          // the last evaluation: no launch in front of its warp kernel, the host formed its segment records
+    {"seg_by_value", [](emba_ctx*, int32_t* v) { *v = kSegByValue; return EMBA_OK; }},                            // segment records the warp kernel's arguments carry: step_prep = 2 up to K = seg_by_value + 1
     {"prep_in_warp", [](emba_ctx* c, int32_t* v) { *v = c->ev.prep_in_warp ? 1 : 0; return EMBA_OK; }},          // the last evaluation: no launch in front of its warp kernel
     {"texels_packed", [](emba_ctx* c, int32_t* v) { *v = c->ev.texels_packed ? 1 : 0; return EMBA_OK; }},        // the last evaluation: its first launch carried texel blocks
     {"step_prep_fallbacks", read_step_prep_fallbacks},

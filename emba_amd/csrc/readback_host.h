@@ -207,6 +207,23 @@ emba_status emba_dump_state(emba_ctx* c, double* pm, double* D, int32_t* cp_idx,
     return EMBA_OK;
 }
 
+// The segment records of the last evaluation as they stand in d_seg, whoever wrote them there (the launch in front of the warp kernel, its workgroup 0 from its
+// own chain, or its workgroup 0 from the host's records): a plain copy behind the stream, no kernel.
+emba_status emba_dump_segments(emba_ctx* c, double* seg, size_t cap, size_t* n_seg)
+{
+    if (!c) return EMBA_ERR_INVALID_ARG;
+    if (!c->ev.readable()) return fail(c, EMBA_ERR_STATE, "no evaluateDataError state to dump");
+    HIP_TRY(c, hipSetDevice(c->device));
+    { emba_status st0 = resolve_pending(c); if (st0) return st0; }
+    const size_t n = (size_t)c->ev.n_seg;
+    if (n_seg) *n_seg = n;
+    if (!seg || !n) return EMBA_OK;
+    if (cap < n) return fail(c, EMBA_ERR_CAPACITY, "dump_segments: room for %zu records, the evaluation left %zu", cap, n);
+    HIP_TRY(c, hipMemcpyAsync(seg, c->d_seg.as<double>(), n * kSegStride * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return EMBA_OK;
+}
+
 emba_status emba_last_counts(emba_ctx* c, size_t* n_inliers, size_t* P)
 {
     if (!c) return EMBA_ERR_INVALID_ARG;

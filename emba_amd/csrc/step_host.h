@@ -303,6 +303,7 @@ emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, 
     const bool seg_records = c->order.tile_order || c->ev.segpose;
     q.n_pose = ((seg_records ? (int)K - 1 : nb) + 63) / 64;   // (K-1 segment records instead of nb batch poses)
     q.seg = seg_records ? c->d_seg.as<double>() : nullptr;
+    c->ev.n_seg = seg_records ? (int)K - 1 : 0;
     // texels are packed when they are stale, not in every evaluation: another map, or the last formed box has left the packed one (h_pinned[5]: the verdict of
     // the active-set write that reduced it — it precedes the sequence words, so once c->seq is there it is this step's)
     const MapState& map = c->map.state();
@@ -314,6 +315,15 @@ emba_status launch_prep_pose_texel(emba_ctx* c, const double* knots, int32_t K, 
     q.rect = c->d_rect.as<int>(); q.rect_packed = c->d_rect.as<int>() + 4;
     q.texel = c->d_texel.as<double>();
     if (c->kernel_timing && c->kt_all) { HIP_TRY(c, hipEventRecord(c->kt[4], s)); c->kt_valid[c->kt_slot][2] = true; }   // (no launch in front: an empty first interval)
+    c->ev.prep_on_host = prep_on_host(c->step_prep, c->order.tile_order, c->ev.segpose, (int)K, kSegByValue, c->win.n_sorted, n_prep_blk, q.n_tex, c->ev.use_texel);
+    if (c->ev.prep_on_host) {      // the host forms the segment records (the prep launch's own chain: seg_record_rule.h); workgroup 0 of the warp launch takes over block 0's duties
+        c->ev.prep_in_warp = false;
+        segment_records(knots, (int)K, c->seg_host.r);
+        SegHostDuties& d = c->seg_duties;
+        d.seg_out = c->d_seg.as<double>(); d.knots_out = c->d_knots.as<double>(); d.err_next = q.err_next; d.K = (int)K;
+        memcpy(d.last_knot, knots + (size_t)4 * (K - 1), 4 * sizeof(double));
+        return EMBA_OK;
+    }
     c->ev.prep_in_warp = prep_inside_warp(c->step_prep, c->order.tile_order, c->ev.segpose, (int)K, kInlineKnots, c->win.n_sorted, n_prep_blk, q.n_tex, c->ev.use_texel);
     if (c->ev.prep_in_warp) {      // workgroup 0 of the warp launch forms the segment records and takes over block 0's duties
         memcpy(c->seg_knots.q, knots, (size_t)4 * K * sizeof(double));
@@ -372,6 +382,7 @@ emba_status launch_warp(emba_ctx* c, const EvalOpts& opt)
     p.chunks = c->d_chunks.as<ChunkDesc>(); p.n_chunks = c->order.n_chunks; p.chunks_linear = c->order.chunks_lpt ? 1 : 0;
     if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->kt[0], s));
     if (tile) launch_warp_tiled(c->order.tile_shape, dim3((unsigned)grid8(c->order.n_chunks)), s, p);
+    else if (c->ev.prep_on_host) hipLaunchKernelGGL(emba_warp_residual_hostseg_kernel, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p, c->seg_duties, c->seg_host);
     else if (c->ev.prep_in_warp) hipLaunchKernelGGL(emba_warp_residual_inline_kernel, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p, c->seg_inline, c->seg_knots);
     else if (c->ev.segpose) hipLaunchKernelGGL((emba_warp_residual_kernel<false, false, true>), dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);
     else hipLaunchKernelGGL(emba_warp_residual_kernel<false>, dim3((unsigned)grid8(c->win.nblk)), dim3(kWarpBlock), 0, s, p);

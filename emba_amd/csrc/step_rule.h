@@ -72,13 +72,22 @@ inline bool texels_stale(bool map_owned, uint32_t map_version, uint32_t packed_v
 // The texel blocks of the launch in front of the warp kernel: 1024 for source 3 with stale texels, none otherwise
 inline int texel_blocks(int hessian_src, bool stale) { return (hessian_src == 3 && stale) ? 1024 : 0; }
 
-// No launch in front of the warp kernel at all (option step_prep: 0, the default, the launch always; 1 where this rule allows — measured at 1 M events: the hand-off
+// No launch in front of the warp kernel at all (option step_prep: 0 the launch always; 1 where this rule allows — measured at 1 M events: the hand-off
 // costs the warp kernel what the launch cost): what is left of it once the lines are clean and the texels fresh is
 // one block that writes K - 1 segment records; workgroup 0 of the warp kernel writes them instead and hands them to the others (kernels.h: inline_seg_*).  Pixel order
 // with segment records, the control poses in the kernel arguments, a window with entries, and nothing else for the launch to do.
 inline bool prep_inside_warp(int step_prep, bool tile_order, bool segpose, int K, int inline_knots, size_t n_sorted, int n_prep_blk, int n_tex_blk, int hessian_src)
 {
-    return step_prep != 0 && !tile_order && segpose && K <= inline_knots && n_sorted > 0 && n_prep_blk == 0 && n_tex_blk == 0 && hessian_src != 1;
+    return step_prep == 1 && !tile_order && segpose && K <= inline_knots && n_sorted > 0 && n_prep_blk == 0 && n_tex_blk == 0 && hessian_src != 1;
+}
+
+// ... or the K - 1 records formed by the HOST (option step_prep = 2, the default; seg_record_rule.h: segment_records) and carried to the warp kernel by value in its
+// arguments (kernels.h: SegRecordsByValue, `seg_by_value` = kSegByValue records): the same steady step — pixel order with segment poses, no texel blocks, no
+// clearing blocks, a window with entries — as long as the K - 1 records fit the carrier.  Everything else keeps the launch: stale texels, a first evaluation,
+// the tile order, the per-batch pose table, a larger K, an empty window.
+inline bool prep_on_host(int step_prep, bool tile_order, bool segpose, int K, int seg_by_value, size_t n_sorted, int n_prep_blk, int n_tex_blk, int hessian_src)
+{
+    return step_prep == 2 && !tile_order && segpose && K >= 2 && K - 1 <= seg_by_value && n_sorted > 0 && n_prep_blk == 0 && n_tex_blk == 0 && hessian_src != 1;
 }
 
 // Blocks of the clearing pass over count map + accumulator lines in front of an evaluation.  It is only needed when the previous evaluation's sums are still

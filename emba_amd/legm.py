@@ -1176,6 +1176,15 @@ class LEGM:
                                             g("pm_int", _i32p), g("dp", _dp), g("Gpm", _dp), g("temp", _dp)))
         return d
 
+    def dump_segments(self):
+        """The segment records {p0, delta, r1, k, r2} the last evaluation left on the device, (K - 1) x 12 (none with the per-batch pose table), for parity tests."""
+        n = C.c_size_t()
+        self._check(self._L.emba_dump_segments(self._ctx, None, 0, C.byref(n)))
+        seg = np.zeros((n.value, 12))
+        if n.value:
+            self._check(self._L.emba_dump_segments(self._ctx, _p(seg, _dp), n.value, None))
+        return seg
+
     # -- phase-level, HBM-resident interface (bench.py, sharded host) -------------------------------
     def upload_map(self, Gx, Gy):
         Gx = np.ascontiguousarray(Gx, dtype=np.float64); Gy = np.ascontiguousarray(Gy, dtype=np.float64)

@@ -202,6 +202,10 @@ emba_status emba_costs_finish(emba_ctx* ctx, int32_t irls, double eta, double al
  * measurement), pm_int n*2 (-1 if not an inlier), dp/Gpm/temp n*2. */
 emba_status emba_dump_state(emba_ctx* ctx, double* pm, double* D, int32_t* cp_idx, int32_t* inlier_idx,
                             int32_t* pm_int, double* dp, double* Gpm, double* temp);
+/* The segment records the last evaluation left on the device, for parity tests: 12 doubles {p0 xyzw, delta xyz, r1, k xyz, r2} per pair of
+ * neighbouring control poses, K - 1 of them in the tile order and in pixel order with the pose per event, none with the per-batch pose table.
+ * *n_seg (may be NULL) their number; seg (host, capacity `cap` records; NULL to ask for the number only).  Synchronizes. */
+emba_status emba_dump_segments(emba_ctx* ctx, double* seg, size_t cap, size_t* n_seg);
 
 /* ---- phase-level, HBM-resident entry points (bench.py, multi-GPU host) ----------------------- */
 
@@ -1134,11 +1138,15 @@ emba_status emba_set_cost(emba_ctx* ctx, int32_t irls, double eta);
  *   step_fast      1 emba_step zeroes the per-pixel sums behind their reader (no clearing pass) | 0 keeps the clearing pass
  *   step_gather    0 sweeping active-set write | 1 list-driven gather as a launch | 2 (default) inside the Gram kernel | 3 inside it at every size
  *   step_one_set   1 emba_step keeps one record set | 0 alternates between two like an LM loop
- *   step_prep      0 (default) the launch in front of the warp kernel always | 1 none on clean accumulator lines and fresh texels (pixel order, segpose, K <= 104):
+ *   step_prep      0 the launch in front of the warp kernel always | 2 (default) none on clean accumulator lines and fresh texels (pixel order, segpose, K <= seg_by_value + 1):
+ *                  the host forms the K-1 segment records (the launch's own chain compiled for the host; its atan / sin / cos are the host C library's, the launch's
+ *                  are the device library's: the records agree to the last bits, not always in them) and the warp kernel takes them by value in its arguments; its
+ *                  workgroup 0 leaves them in device memory for later readers | 1 the same step (K <= 104):
  *                  workgroup 0 of the warp kernel forms the K-1 segment records and hands them to the others inside the launch (measured: no faster).  step_prep_polls (1024; 0 ... 65536): polls a wave waits for
  *                  the records before it forms its own (0: every wave does; same bits).
- *                  emba_get_option, read-only, of the last evaluation: "prep_in_warp" (no launch in front), "texels_packed"
- *                  (its launch packed texels); "step_prep_fallbacks": waves that formed their own records since the context was created (drains the stream)
+ *                  emba_get_option, read-only, of the last evaluation: "prep_on_host", "prep_in_warp" (no launch in front: value 2, value 1), "texels_packed"
+ *                  (its launch packed texels); "step_prep_fallbacks": waves that formed their own records since the context was created (drains the stream);
+ *                  "seg_by_value": segment records the warp kernel's arguments have room for
  *   gram_sparse    -1 auto (by the active-pixel count of the window's last equations) | 0 | 1 the Gram kernel's form for slot streams with few live records (pixel
  *                  order on a large panorama): stages of 128 tags, the live slots compacted, only their records fetched;  gram_sparse_chunk 1 ... 8 (4): its slots per wave, x 1024
  *   gather_waves   0 auto (4) | 1 | 2 | 4 waves of a Gram workgroup do its slice of the gather
