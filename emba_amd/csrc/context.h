@@ -297,6 +297,16 @@ struct ExposureBuffers {
 // stages keep a chunk); loop.pm: uv; the rest of loop over one chunk of pairs; pairs, gain, bias: the chunk's (i, j) and relative exposures.
 struct PairBuffers { DevBuf pairs, gain, bias; FrameLoopBuffers loop; };
 
+// The pair alignment coarse to fine (pair_level_host.h); all of it scratch of one call.  loop.frames: the whole sequence [F, S], uploaded once per call;
+// bytes: the bytes [F, S_l] of every distinct level above 0 of the schedule, one behind the other; lut: their tables [S_l, 3] likewise; pairs, gain_trial,
+// bias_trial, gain, bias and the rest of loop: one chunk of pairs at one level (exposure_rule.h's ExposureFrame); out_of and r_*: the chunk's result over
+// the schedule (pair_level_kernels.h: PairHandoverParams).
+struct PairLevelBuffers {
+    DevBuf pairs, gain_trial, bias_trial, gain, bias, bytes, lut, out_of;
+    DevBuf r_q, r_gain, r_bias, r_sums, r_cost0, r_counts, r_n0, r_status, r_iters, r_level_status, r_level_iters;
+    FrameLoopBuffers loop;
+};
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -499,6 +509,7 @@ struct emba_ctx {
     TrackBuffers track;           // intensity frames tracked against their own growing mosaic: the level planes and the scratch of a call (track_host.h)
     ExposureBuffers exposure;     // per-frame exposure: the scratch of a call (exposure_host.h)
     PairBuffers pair;             // one frame aligned to another: the resident sequence of a call and the scratch of a chunk of pairs (pair_host.h)
+    PairLevelBuffers pair_level;  // the pair alignment coarse to fine: the sequence, its pyramid and the scratch of a chunk of pairs (pair_level_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

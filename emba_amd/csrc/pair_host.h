@@ -25,8 +25,8 @@ struct PairCall {
     double fu, fv, cu, cv; const double* D; int32_t skip_zero; double huber_k;
 };
 
-// every refusal, before anything is uploaded; `set`: the loop's settings, or nullptr for the evaluation alone
-emba_status pair_refusals(emba_ctx* c, const PairCall& a, const emba_align_settings* set, bool loop)
+// the refusals of the arguments up to huber_k (pair_args_ok), which pair_level_host.h's calls begin with as well
+emba_status pair_args_refusal(emba_ctx* c, const PairCall& a)
 {
     size_t at = 0;
     switch (pair_args_ok(a.frames != nullptr, a.F, a.pairs, a.P, a.Q, a.gain, a.bias, a.fu, a.fv, a.cu, a.cv, a.D, a.huber_k, &at)) {
@@ -44,6 +44,13 @@ emba_status pair_refusals(emba_ctx* c, const PairCall& a, const emba_align_setti
     case PairArgStatus::bad_distortion: return fail(c, EMBA_ERR_INVALID_ARG, "D is not finite");
     case PairArgStatus::huber_not_finite: return fail(c, EMBA_ERR_INVALID_ARG, "huber_k is not a number");
     }
+    return EMBA_OK;
+}
+
+// every refusal, before anything is uploaded; `set`: the loop's settings, or nullptr for the evaluation alone
+emba_status pair_refusals(emba_ctx* c, const PairCall& a, const emba_align_settings* set, bool loop)
+{
+    SEQ_TRY(pair_args_refusal(c, a));
     if (loop) SEQ_TRY(align_settings_refusal(c, set));
     if (!pair_bytes_ok(a.F, c->S)) return fail(c, EMBA_ERR_INVALID_ARG, "F = %zu frames of %zu bytes: the resident sequence is bounded at %zu bytes", a.F, c->S, kPairMaxBytes);
     return EMBA_OK;

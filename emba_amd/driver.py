@@ -88,8 +88,19 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     close_per_frame: int = 2
     close_huber: float = 0.0
     close_min_overlap: float = 0.3
+    # How a pair is aligned (the rule: include/emba_hip.h, emba_frames_pair_align_levels): close_levels is the schedule over a pyramid of the sensor
+    # frames, coarse to fine (level l: the frames box-reduced by 2^l; each 0 ... 7, at most 8), and close_exposure says what of the pair's relative exposure is
+    # estimated with its rotation: "none", "bias" or "gain-bias".  With both at their defaults the pairs go through LEGM.pair_align as before; otherwise
+    # through LEGM.pair_align_levels from the same starts.  The graph stays one of rotations alone.
+    close_levels: tuple = (0,)
+    close_exposure: str = "none"
 
     def __post_init__(self):
+        self.close_levels = tuple(int(l) for l in np.asarray(self.close_levels).reshape(-1))
+        if not 1 <= len(self.close_levels) <= emba_io.PAIR_MAX_LEVELS or any(not 0 <= l <= emba_io.PAIR_MAX_LEVEL for l in self.close_levels):
+            raise ValueError(f"SequenceSettings.close_levels = {self.close_levels}: 1 ... {emba_io.PAIR_MAX_LEVELS} levels, each 0 ... {emba_io.PAIR_MAX_LEVEL}")
+        if self.close_exposure not in emba_io.PAIR_EXPOSURE_MODES:
+            raise ValueError(f"SequenceSettings.close_exposure must be one of {sorted(emba_io.PAIR_EXPOSURE_MODES)}, not {self.close_exposure!r}")
         if (int(self.close_window) < 0 or int(self.close_gap) < 0 or int(self.close_per_frame) < 0 or not float(self.close_angle) >= 0.0
                 or not 0.0 <= float(self.close_min_overlap) <= 1.0 or np.isnan(self.close_huber)):
             raise ValueError("SequenceSettings.close_*: window, gap and per_frame are counts, the angle is not negative, the overlap a share, the threshold a number")
@@ -134,7 +145,10 @@ def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track
     is solved with the tracker's anchors fixed (LEGM.rotation_graph_solve); the frames are then stitched again at the new rotations
     (LEGM.refit_frames, sweeps = 0), so the mosaic in the context is the closed one.  The tracker's dict comes back with the new q and, beside it, `pairs`
     [P, 2], `pair_status`, `pair_n`, `pair_cost` (mean), `pair_moved` (rad, against the pair's start), `pair_kept` and `graph` (cost0, cost, iters,
-    cg_iters, end).  Without seq.track_close, or where no pair is kept, `tracked` is returned as it is (with the pairs, where there were any)."""
+    cg_iters, end).  Without seq.track_close, or where no pair is kept, `tracked` is returned as it is (with the pairs, where there were any).  With
+    seq.close_levels or seq.close_exposure off their defaults the pairs go through LEGM.pair_align_levels instead, from the same starts; a pair is kept by the
+    same gate on the counts of its last level run against that level's pixels, and `pair_gain`, `pair_bias`, `pair_level_status` [P, n] and
+    `pair_last_level` come back beside the rest.  The graph stays one of rotations alone."""
     if not seq.track_close:
         return tracked
     kw = {k: v for k, v in track_kw.items() if k not in ("q0", "predict", "want_pm")}
@@ -144,15 +158,27 @@ def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track
     Q0, a, b = emba_io.pair_start(tracked["q"], tracked.get("gain"), tracked.get("bias"), pairs)
     align_kw = {k: v for k, v in kw.items() if k in emba_io.ALIGN_DEFAULTS}
     align_kw["huber_k"] = float(seq.close_huber)
-    al = model.pair_align(frames, pairs, Q0, calib, gain=a, bias=b, skip_zero=bool(kw.get("skip_zero", False)), **align_kw)
+    levelled = seq.close_levels != (0,) or seq.close_exposure != "none"
+    if not levelled:
+        al = model.pair_align(frames, pairs, Q0, calib, gain=a, bias=b, skip_zero=bool(kw.get("skip_zero", False)), **align_kw)
+        ten, S_last = al["sums"], S
+    else:      # coarse to fine, the pair's exposure estimated: the same starts, the gate on the last level run against that level's pixels
+        al = model.pair_align_levels(frames, pairs, Q0, calib, levels=seq.close_levels, estimate=emba_io.PAIR_EXPOSURE_MODES[seq.close_exposure], gain=a, bias=b,
+                                     skip_zero=bool(kw.get("skip_zero", False)), gain_min=kw.get("gain_min"), gain_max=kw.get("gain_max"), **align_kw)
+        ten = al["sums"][:, list(emba_io.EXPOSURE_SHARED)]
+        ran = np.maximum((al["level_status"] != 0).sum(axis=1) - 1, 0)      # (the levels of a pair are run in order: the last one run)
+        last = np.asarray(seq.close_levels)[ran] if len(pairs) else np.zeros(0, np.int64)
+        S_last = (model.sensor_w >> last) * (model.sensor_h >> last)
     n = al["counts"][:, 0]
-    kept = ((al["status"] == emba_io.ALIGN_CONVERGED) | (al["status"] == emba_io.ALIGN_ITERATIONS)) & (n >= seq.close_min_overlap * S)
+    kept = ((al["status"] == emba_io.ALIGN_CONVERGED) | (al["status"] == emba_io.ALIGN_ITERATIONS)) & (n >= seq.close_min_overlap * S_last)
     out = dict(tracked)
-    out.update(pairs=pairs, pair_status=al["status"], pair_n=n, pair_cost=al["sums"][:, 9] / np.maximum(n, 1), pair_kept=kept,
+    out.update(pairs=pairs, pair_status=al["status"], pair_n=n, pair_cost=ten[:, 9] / np.maximum(n, 1), pair_kept=kept,
                pair_moved=emba_io.rotation_angle_between(Q0, al["q"]) if len(pairs) else np.zeros(0), graph=None)
+    if levelled:
+        out.update(pair_gain=al["gain"], pair_bias=al["bias"], pair_level_status=al["level_status"], pair_last_level=last)
     if not kept.any():
         return out
-    info = emba_io.pair_information(al["sums"], al["counts"], floor=emba_io.PAIR_NOISE_FLOOR)
+    info = emba_io.pair_information(ten, al["counts"], floor=emba_io.PAIR_NOISE_FLOOR)
     reach = _reached(tracked["status"], pairs[kept])
     kept &= reach[pairs[:, 0]] & reach[pairs[:, 1]]      # (a group of frames that no kept pair ties to an anchor stays where the tracker put it)
     if not kept.any():

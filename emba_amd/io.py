@@ -2138,6 +2138,178 @@ def pair_align(frames_u8, pairs, Q_xyzw, lut, calib, sensor, gain=None, bias=Non
     return out
 
 
+# ---- the pair alignment coarse to fine over a pyramid of the sensor frames, with the pair's exposure estimated (numpy forms of emba_frames_pair_level_eval
+# and emba_frames_pair_align_levels, include/emba_hip.h; the device forms are LEGM.pair_level_eval and LEGM.pair_align_levels).  The rules are
+# emba_amd/csrc/pair_level_rule.h's: the level bytes are equal integers, the level table and the level camera have the same bits.
+PAIR_MAX_LEVEL = 7                       # kPairMaxLevel
+PAIR_MAX_LEVELS = 8                      # kPairMaxLevels: entries of a schedule
+PAIR_EXPOSURE_MODES = {"none": 0, "bias": EXPOSURE_BIAS, "gain-bias": EXPOSURE_GAIN | EXPOSURE_BIAS}
+
+
+def pair_level_size(sensor, level):
+    """(sw >> l, sh >> l) of sensor = (sw, sh); ValueError for a level outside 0 ... PAIR_MAX_LEVEL or one below 2 x 2 (a bilinear cell needs 2 x 2)."""
+    sw, sh, l = int(sensor[0]), int(sensor[1]), int(level)
+    if not 0 <= l <= PAIR_MAX_LEVEL:
+        raise ValueError(f"level {l} is outside 0 ... {PAIR_MAX_LEVEL}")
+    if (sw >> l) < 2 or (sh >> l) < 2:
+        raise ValueError(f"level {l} of a {sw} x {sh} sensor is {sw >> l} x {sh >> l}: a bilinear cell needs 2 x 2")
+    return sw >> l, sh >> l
+
+
+def pair_check_levels(levels, sensor):
+    """The schedule as a tuple of ints; the refusals of emba_frames_pair_align_levels' schedule as ValueError."""
+    lv = tuple(int(l) for l in np.asarray(levels).reshape(-1))
+    if not 1 <= len(lv) <= PAIR_MAX_LEVELS:
+        raise ValueError(f"a schedule has 1 ... {PAIR_MAX_LEVELS} levels, not {len(lv)}")
+    for l in lv:
+        if not 0 <= l <= PAIR_MAX_LEVEL:
+            raise ValueError(f"level {l} is outside 0 ... {PAIR_MAX_LEVEL}")
+    for l in lv:
+        pair_level_size(sensor, l)
+    return lv
+
+
+def pair_level_bytes(frames_u8, level, skip_zero=False):
+    """Level `level` of frames_u8 [..., sh, sw]: uint8 [..., sh >> l, sw >> l], (sum of the box + 4^l / 2) >> 2l in integers from level 0 directly; under
+    skip_zero a box that holds a zero byte is 0.  The columns and rows left over at the right and at the bottom take no part."""
+    fr = np.asarray(frames_u8, dtype=np.uint8)
+    sh, sw = fr.shape[-2:]
+    wl, hl = pair_level_size((sw, sh), level)
+    l = int(level)
+    if l == 0:
+        return fr.copy()
+    n = 1 << l
+    box = fr[..., :hl * n, :wl * n].reshape(fr.shape[:-2] + (hl, n, wl, n))
+    out = (box.astype(np.int64).sum(axis=(-3, -1)) + ((1 << (2 * l)) >> 1)) >> (2 * l)
+    if skip_zero:
+        out = np.where((box == 0).any(axis=(-3, -1)), 0, out)
+    return out.astype(np.uint8)
+
+
+def pair_level_lut(lut, sensor, level):
+    """The bearing table [S_l, 3] of level `level` from the table lut [S, 3] of sensor = (sw, sh): level 0 the table; above it 0.25 ((b00 + b01) + (b10 +
+    b11)) of the four pixels around the centre of each box, componentwise in this order."""
+    sw, sh = int(sensor[0]), int(sensor[1])
+    wl, hl = pair_level_size(sensor, level)
+    l = int(level)
+    T = np.asarray(lut, dtype=np.float64).reshape(sh, sw, 3)
+    if l == 0:
+        return T.reshape(-1, 3).copy()
+    h = 1 << (l - 1)
+    ys, xs = np.arange(hl) * 2 * h + h - 1, np.arange(wl) * 2 * h + h - 1
+    b00, b01 = T[ys[:, None], xs[None, :]], T[ys[:, None], xs[None, :] + 1]
+    b10, b11 = T[ys[:, None] + 1, xs[None, :]], T[ys[:, None] + 1, xs[None, :] + 1]
+    return (0.25 * ((b00 + b01) + (b10 + b11))).reshape(-1, 3)
+
+
+def pair_level_calib(calib, level):
+    """The camera of level `level`: fu / 2^l, fv / 2^l, (cu - (2^l - 1) / 2) / 2^l, cv likewise, D unchanged.  Level 0 is the camera bit for bit."""
+    l = int(level)
+    if not 0 <= l <= PAIR_MAX_LEVEL:
+        raise ValueError(f"level {l} is outside 0 ... {PAIR_MAX_LEVEL}")
+    n, half = float(1 << l), (float(1 << l) - 1.0) / 2.0
+    return dict(fu=float(calib["fu"]) / n, fv=float(calib["fv"]) / n, cu=(float(calib["cu"]) - half) / n, cv=(float(calib["cv"]) - half) / n, D=calib.get("D"))
+
+
+def pair_level_min_pixels(min_pixels, level):
+    """min_pixels at a level: min_pixels >> 2l, but not below the smaller of min_pixels and 8."""
+    return max(int(min_pixels) >> (2 * int(level)), min(int(min_pixels), 8))
+
+
+def pair_exposure_terms(src_u8, tgt_u8, uv, lut, Q, calib, gain=1.0, bias=0.0, skip_zero=False, huber_k=0.0):
+    """pair_terms with the exposure's column: its dict and I0 [S] = the source byte as a double (0 where the pixel is not used).  The Jacobian row of r in
+    (delta, a, b) is (g, -I0, -1).  Everything is the level's: bytes, uv, table and camera."""
+    t = pair_terms(src_u8, tgt_u8, uv, lut, Q, calib, gain, bias, skip_zero, huber_k)
+    v = np.asarray(src_u8, dtype=np.uint8).reshape(-1).astype(np.float64)
+    t["I0"] = np.where(t["cls"] == ALIGN_USED, v, 0.0)
+    return t
+
+
+def pair_exposure_sums(terms, with_scale=False):
+    """The 21 sums and the four counts of one pair's terms: exposure_sums."""
+    return exposure_sums(terms, with_scale)
+
+
+def pair_align_levels(frames_u8, pairs, Q_xyzw, lut, calib, sensor, levels=(0,), estimate=0, gain=None, bias=None, skip_zero=False, gain_min=None, gain_max=None,
+                      order=None, **settings):
+    """The schedule of emba_frames_pair_align_levels in numpy, with numpy's own uv: per pair (i, j) of frames_u8 [F, S], level by level through `levels`, the
+    loop of align_frames_exposure (exposure_step on pair_exposure_sums) on the level's bytes, table and camera, min_pixels by pair_level_min_pixels; level
+    k + 1 starts from the accepted (Q, a, b) of level k; a level that ends degenerate ends the pair.  sensor: (sw, sh).  order: a function n -> a permutation
+    of a level's n pixels, in which the sums are then taken in plain fp64 (None: np.longdouble in pixel order) — what measures the spread of the result under
+    the order of summation.  A dict of q [P, 4], gain, bias [P], sums [P, 21], counts [P, 4], status, iters [P], level_status, level_iters [P, n], cost0, n0
+    [P], info [P, 6] and last_x [P, 5]: the last accepted step (delta, x_a, x_b) of the last level run, what the stopping rule leaves undetermined."""
+    s = align_settings(**settings)
+    g_lo, g_hi = exposure_bounds(gain_min, gain_max)
+    estimate = int(estimate)
+    if not 0 <= estimate <= 3:
+        raise ValueError("estimate is a mask of EXPOSURE_GAIN and EXPOSURE_BIAS")
+    sw, sh = int(sensor[0]), int(sensor[1])
+    lv = pair_check_levels(levels, sensor)
+    n = len(lv)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    P = pairs.shape[0]
+    Q_in = np.asarray(Q_xyzw, dtype=np.float64).reshape(P, 4)
+    frames = np.asarray(frames_u8, dtype=np.uint8).reshape(-1, sh, sw)
+    a_in = np.ones(P) if gain is None else np.broadcast_to(np.asarray(gain, dtype=np.float64), (P,))
+    b_in = np.zeros(P) if bias is None else np.broadcast_to(np.asarray(bias, dtype=np.float64), (P,))
+    pyramid = {l: (pair_level_bytes(frames, l, skip_zero), pair_level_lut(lut, sensor, l), pair_level_calib(calib, l)) for l in set(lv)}
+
+    def evaluate(l, p, q, a, b):
+        fb, tl, cl = pyramid[l]
+        i, j = pairs[p]
+        t = pair_exposure_terms(fb[i].reshape(-1), fb[j], pair_project(tl, q, cl)[1], tl, q, cl, a, b, skip_zero, s["huber_k"])
+        if order is None:
+            return pair_exposure_sums(t)
+        perm = np.asarray(order(t["cls"].size))      # (... and plain fp64 one term after the other, where pair_exposure_sums accumulates in np.longdouble)
+        return np.cumsum(exposure_sum_terms(t)[perm], axis=0)[-1], np.bincount(t["cls"], minlength=4).astype(np.int64)
+
+    out = dict(q=Q_in.copy(), gain=a_in.copy(), bias=b_in.copy(), sums=np.zeros((P, EXPOSURE_SUMS)), counts=np.zeros((P, 4), np.int64), status=np.zeros(P, np.int32),
+               iters=np.zeros(P, np.int32), level_status=np.zeros((P, n), np.int32), level_iters=np.zeros((P, n), np.int32), cost0=np.zeros(P), n0=np.zeros(P, np.int64),
+               last_x=np.zeros((P, 5)))
+    for p in range(P):
+        q, a, b = Q_in[p].copy(), float(a_in[p]), float(b_in[p])
+        for k, l in enumerate(lv):
+            out["last_x"][p] = 0.0
+            min_pixels = pair_level_min_pixels(s["min_pixels"], l)
+            sums, counts = evaluate(l, p, q, a, b)
+            if k == 0:
+                out["cost0"][p], out["n0"][p] = sums[EXPOSURE_COST], counts[0]
+            lam, iters = float(s["lambda0"]), 0
+            while True:
+                x = exposure_step(sums, lam, estimate) if counts[0] >= min_pixels else None
+                if x is None:
+                    status = ALIGN_DEGENERATE
+                    break
+                if iters >= s["max_iters"]:
+                    status = ALIGN_ITERATIONS
+                    break
+                trial, ta, tb = so3.mul(so3.exp(x[:3]), q), a + x[3], b + x[4]
+                tsums, tcounts = evaluate(l, p, trial, ta, tb)
+                iters += 1
+                take = tcounts[0] >= min_pixels and tsums[EXPOSURE_COST] / tcounts[0] < sums[EXPOSURE_COST] / counts[0]
+                if (estimate & EXPOSURE_GAIN) and not g_lo <= ta <= g_hi:
+                    take = False
+                if take:
+                    q, a, b, sums, counts = trial, ta, tb, tsums, tcounts
+                    out["last_x"][p] = x
+                    lam = max(lam / s["lambda_down"], s["lambda_min"])
+                    if np.linalg.norm(x[:3]) < s["tol_rot"]:
+                        status = ALIGN_CONVERGED
+                        break
+                else:
+                    lam *= s["lambda_up"]
+                    if lam > s["lambda_max"]:
+                        status = ALIGN_STALLED
+                        break
+            out["level_status"][p, k], out["level_iters"][p, k] = status, iters
+            out["iters"][p] += iters
+            out["q"][p], out["gain"][p], out["bias"][p], out["sums"][p], out["counts"][p], out["status"][p] = q, a, b, sums, counts, status
+            if status == ALIGN_DEGENERATE:
+                break
+    out["info"] = pair_information(out["sums"][:, list(EXPOSURE_SHARED)], out["counts"])
+    return out
+
+
 def pair_candidates(q, status, window=1, min_gap=None, max_angle=0.0, max_per_frame=0):
     """The pairs (i, j), i < j, sorted, that a loop closure tries, from tracked rotations q [F, 4] and status [F] (io.TRACK_*; lost frames take no part): every
     pair of voting frames with j - i <= window, and, for |j - i| > min_gap (None: window), per frame the max_per_frame frames with the smallest rotation angle

@@ -701,6 +701,57 @@ class LEGM:
                                                    _p(iters, _i32p), _p(cost0, _dp), _p(n0, u64p), _p(info, _dp)))
         return dict(q=q_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, cost0=cost0, n0=n0.astype(np.int64), info=info)
 
+    def pair_level_eval(self, frames, pairs, Q_xyzw, calib, level, gain=None, bias=None, skip_zero=False, huber_k=0.0, want_uv=False, want_resid=False,
+                        want_level=False):
+        """pair_eval on level `level` of the pyramid of the sensor frames, with the exposure's rows (emba_frames_pair_level_eval; the rule:
+        include/emba_hip.h): a dict of sums [P, 21], counts int64 [P, 4], uv [P, S_l, 2], resid [P, S_l] and, with want_level, level_bytes uint8
+        [F, sh_l, sw_l] and level_lut [S_l, 3] (None unless asked for) — io.pair_exposure_terms and io.pair_exposure_sums on io.pair_level_bytes,
+        io.pair_level_lut and io.pair_level_calib, given the same uv."""
+        frames, F, S, pairs, P, Q, a, b, k4, D = self._pair_args(frames, pairs, Q_xyzw, gain, bias, calib)
+        level = int(level)
+        wl, hl = (self.sensor_w >> level, self.sensor_h >> level) if 0 <= level <= 7 else (0, 0)
+        Sl = wl * hl
+        sums, counts = np.zeros((P, 21)), np.zeros((P, 4), np.uint64)
+        uv = np.empty((P, Sl, 2)) if want_uv else None
+        resid = np.empty((P, Sl)) if want_resid else None
+        lb = np.zeros((F, hl, wl), np.uint8) if want_level else None
+        ll = np.zeros((Sl, 3)) if want_level else None
+        self._check(self._L.emba_frames_pair_level_eval(self._ctx, _p(frames, _u8p), F, _p(pairs, _i32p), P, _p(Q, _dp), _p(a, _dp), _p(b, _dp), *k4, _p(D, _dp),
+                                                        1 if skip_zero else 0, float(huber_k), level, _p(sums, _dp), _p(counts, C.POINTER(C.c_uint64)),
+                                                        _p(uv, _dp), _p(resid, _dp), _p(lb, _u8p), _p(ll, _dp)))
+        return dict(sums=sums, counts=counts.astype(np.int64), uv=uv, resid=resid, level_bytes=lb, level_lut=ll)
+
+    def pair_align_levels(self, frames, pairs, Q_xyzw, calib, levels=(0,), estimate=0, gain=None, bias=None, skip_zero=False, gain_min=None, gain_max=None,
+                          **settings):
+        """pair_align coarse to fine, with the pair's exposure estimated (emba_frames_pair_align_levels; the rule: include/emba_hip.h): every pair goes
+        through the schedule `levels` (each 0 ... 7, level l the frames box-reduced by 2^l), from one level's accepted (Q, gain, bias) to the next, its
+        relative gain and bias estimated where `estimate` (io.EXPOSURE_GAIN | io.EXPOSURE_BIAS) says so, within [gain_min, gain_max]
+        (io.EXPOSURE_BOUNDS).  settings: the members of io.ALIGN_DEFAULTS.  A dict of q [P, 4], gain, bias [P], sums [P, 21] and counts [P, 4] of the last
+        level run, status, iters (summed) [P], level_status, level_iters [P, n] (0: not run), cost0, n0 [P] of the first level, info [P, 6].
+        io.pair_align_levels is the same schedule in numpy; levels = (0,) with estimate = 0 is pair_align bit for bit."""
+        from . import io as emba_io
+        s = emba_io.align_settings(**settings)
+        g_lo = float(emba_io.EXPOSURE_BOUNDS["gain_min"] if gain_min is None else gain_min)
+        g_hi = float(emba_io.EXPOSURE_BOUNDS["gain_max"] if gain_max is None else gain_max)
+        frames, F, S, pairs, P, Q, a, b, k4, D = self._pair_args(frames, pairs, Q_xyzw, gain, bias, calib)
+        lv = np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+        n = lv.size
+        cs = _lib.EmbaExposureSettings(_lib.EmbaAlignSettings(int(s["max_iters"]), int(s["min_pixels"]), float(s["lambda0"]), float(s["lambda_up"]),
+                                                              float(s["lambda_down"]), float(s["lambda_min"]), float(s["lambda_max"]), float(s["tol_rot"]),
+                                                              float(s["huber_k"])), g_lo, g_hi)
+        q_out, sums, counts, info = Q.copy(), np.zeros((P, 21)), np.zeros((P, 4), np.uint64), np.zeros((P, 6))
+        a_out = np.ones(P) if a is None else a.copy()
+        b_out = np.zeros(P) if b is None else b.copy()
+        status, iters, cost0, n0 = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P), np.zeros(P, np.uint64)
+        lst, lit = np.zeros((P, n), np.int32), np.zeros((P, n), np.int32)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_pair_align_levels(self._ctx, _p(frames, _u8p), F, _p(pairs, _i32p), P, _p(Q, _dp), _p(a, _dp), _p(b, _dp), *k4, _p(D, _dp),
+                                                          1 if skip_zero else 0, _p(lv, _i32p) if n else None, n, int(estimate), C.addressof(cs), _p(q_out, _dp),
+                                                          _p(a_out, _dp), _p(b_out, _dp), _p(sums, _dp), _p(counts, u64p), _p(status, _i32p), _p(iters, _i32p),
+                                                          _p(lst, _i32p), _p(lit, _i32p), _p(cost0, _dp), _p(n0, u64p), _p(info, _dp)))
+        return dict(q=q_out, gain=a_out, bias=b_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, level_status=lst, level_iters=lit,
+                    cost0=cost0, n0=n0.astype(np.int64), info=info)
+
     @staticmethod
     def rotation_graph_solve(q_xyzw, status, edges, Q_xyzw, info, **settings):
         """The rotation graph on the host (emba_rotation_graph_solve; the rule: include/emba_hip.h): q_xyzw [F, 4] with status [F] (io.TRACK_ANCHOR frames

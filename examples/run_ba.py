@@ -156,7 +156,8 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print, calib=Non
         from emba_amd.driver import SequenceSettings, close_tracked_frames
         before = r["q"]
         r = close_tracked_frames(legm, frames, t_ns, r, SequenceSettings(1.0, 1.0, track_close=True, close_window=a.close_window, close_gap=a.close_gap,
-                                                                         close_angle=a.close_angle, close_per_frame=a.close_per_frame, close_huber=a.close_huber),
+                                                                         close_angle=a.close_angle, close_per_frame=a.close_per_frame, close_huber=a.close_huber,
+                                                                         close_levels=a.close_levels or (0,), close_exposure=a.close_exposure or "none"),
                                  calib, estimate=estimate or 0, **kw)
         g = r["graph"]
         log(f"track-close: {len(r['pairs'])} pairs, {int(r['pair_kept'].sum())} kept; "
@@ -164,9 +165,14 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print, calib=Non
                f"worst change against the tracker {eio.rotation_angle_between(before, r['q']).max():.3g} rad" if g else "no graph: the tracker's rotations stay"))
         if pairs_path:
             with open(pairs_path, "w") as fh:
-                fh.write("# i j status(1 converged, 2 stalled, 3 iterations, 4 degenerate) n mean_cost moved[rad] kept\n")
-                for (i, j), st, n, c, mv, kp in zip(r["pairs"], r["pair_status"], r["pair_n"], r["pair_cost"], r["pair_moved"], r["pair_kept"]):
-                    fh.write(f"{i} {j} {int(st)} {int(n)} {c:.9g} {mv:.9g} {int(kp)}\n")
+                levelled = a.close_levels is not None or a.close_exposure is not None      # (the columns gain, bias, last level only with one of the two flags)
+                fh.write("# i j status(1 converged, 2 stalled, 3 iterations, 4 degenerate) n mean_cost moved[rad] kept" + (" gain bias last_level" if levelled else "") + "\n")
+                if levelled and "pair_gain" not in r:      # (a flag given at its default value: the pairs went through level 0 alone, their exposure as given)
+                    _, pg, pb = eio.pair_start(before, r.get("gain"), r.get("bias"), r["pairs"])
+                    r = dict(r, pair_gain=pg, pair_bias=pb, pair_last_level=np.zeros(len(r["pairs"]), np.int64))
+                for p, ((i, j), st, n, c, mv, kp) in enumerate(zip(r["pairs"], r["pair_status"], r["pair_n"], r["pair_cost"], r["pair_moved"], r["pair_kept"])):
+                    more = f" {r['pair_gain'][p]:.9g} {r['pair_bias'][p]:.9g} {int(r['pair_last_level'][p])}" if levelled else ""
+                    fh.write(f"{i} {j} {int(st)} {int(n)} {c:.9g} {mv:.9g} {int(kp)}{more}\n")
     if a.track_refit:      # the sweeps behind the tracker, before the raw poses are sampled: the mosaic in the context is the refitted one
         from emba_amd.driver import SequenceSettings, refit_tracked_frames
         before = r["q"]
@@ -335,6 +341,10 @@ def main():
     ap.add_argument("--close-angle", type=float, default=0.2, metavar="RAD", help="... whose tracked rotations differ by at most RAD")
     ap.add_argument("--close-per-frame", type=int, default=2, metavar="N")
     ap.add_argument("--close-huber", type=float, default=0.0, metavar="K", help="the Huber threshold of a pair's residuals in bytes (0: quadratic)")
+    ap.add_argument("--close-levels", metavar="L,L,...", help="with --track-close: the pairs are aligned coarse to fine through these levels of a pyramid of the "
+                    "sensor frames (level l: the frames box-reduced by 2^l), e.g. 2,1,0 (default: level 0 alone)")
+    ap.add_argument("--close-exposure", choices=("none", "bias", "gain-bias"), default=None, help="with --track-close: what of a pair's relative exposure is "
+                    "estimated with its rotation (default: none, the tracker's exposure is taken as it is)")
     ap.add_argument("--close-calib", metavar="fu,fv,cu,cv[,k1,k2,p1,p2,k3]", help="the camera the pairs project through (default: --calib's K and D; --demo: the "
                     "demo's pinhole)")
     ap.add_argument("--track-refit-tol", type=float, default=0.0, metavar="X", help="with --track-refit: stop behind a sweep whose largest rotation change is below X rad (0: never)")
@@ -389,6 +399,15 @@ def main():
         ap.error("--track-refit refits the frames tracked by --init-poses frames: it needs --init-poses frames")
     if a.track_close and a.init_poses != "frames":
         ap.error("--track-close closes loops among the frames tracked by --init-poses frames: it needs --init-poses frames")
+    if (a.close_levels is not None or a.close_exposure is not None) and not a.track_close:
+        ap.error("--close-levels and --close-exposure say how --track-close aligns its pairs: they need --track-close")
+    if a.close_levels is not None:
+        try:
+            a.close_levels = tuple(int(x) for x in a.close_levels.split(","))
+        except ValueError:
+            ap.error("--close-levels takes levels separated by commas, e.g. 2,1,0")
+        if not 1 <= len(a.close_levels) <= eio.PAIR_MAX_LEVELS or any(not 0 <= l <= eio.PAIR_MAX_LEVEL for l in a.close_levels):
+            ap.error(f"--close-levels takes 1 ... {eio.PAIR_MAX_LEVELS} levels, each 0 ... {eio.PAIR_MAX_LEVEL}")
     if a.close_window < 0 or a.close_gap < 0 or a.close_per_frame < 0 or not a.close_angle >= 0.0 or np.isnan(a.close_huber):
         ap.error("--close-window, --close-gap, --close-per-frame and --close-angle are not negative, --close-huber is a number")
     if a.track_refit < 0 or not a.track_refit_tol >= 0.0:

@@ -944,6 +944,57 @@ emba_status emba_frames_pair_align(emba_ctx* ctx, const uint8_t* frames /* [F, s
                                    double* q_out /* [P, 4] */, double* sums_out /* [P, 10] */, uint64_t* counts_out /* [P, 4] */, int32_t* status_out /* [P] */,
                                    int32_t* iters_out /* [P] */, double* cost0_out /* [P] */, uint64_t* n0_out /* [P] */, double* info_out /* [P, 6] */);
 
+/* ---- The pair alignment coarse to fine over a pyramid of the sensor frames, with the pair's exposure estimated.  emba_frames_pair_align
+ * starts inside the basin of the full-resolution alignment and takes the pair's exposure as given; here the same pair is aligned level by level, from frames
+ * box-reduced by 2^l down to the frames themselves, and its relative gain and bias are estimated with its rotation.  The rule lives in
+ * emba_amd/csrc/pair_level_rule.h (over pair_rule.h and exposure_rule.h); emba_amd.io.pair_level_* / pair_exposure_* / pair_align_levels are the same rule in
+ * numpy.
+ *
+ *   level sizes       level l of the sensor [sh, sw] is [sh >> l, sw >> l], l = 0 ... 7; level pixel (X, Y) is the box of the pixels x in [X 2^l, (X + 1) 2^l),
+ *                     y likewise; the columns and rows left over at the right and at the bottom take no part.  A level below 2 x 2 is refused.
+ *   level bytes       (sum of the box + 4^l / 2) >> 2l in integers, formed from level 0 directly.  Under skip_zero a box that holds a zero byte is 0 ("no
+ *                     data" stays "no data"), and a box without one gives 1 at the least.  Level 0 is the frame.
+ *   level bearings    level 0 is the context's table (x', y', 1).  For l >= 1 the centre of a box is the corner shared by its four central pixels, and the
+ *                     level's bearing is 0.25 ((b00 + b01) + (b10 + b11)) of those four, componentwise in this order: z stays 1.  Behind a pinhole that is
+ *                     the centre's bearing but for rounding; behind a lens it is the bilinear midpoint.
+ *   level camera      fu_l = fu / 2^l, fv_l = fv / 2^l, cu_l = (cu - (2^l - 1) / 2) / 2^l, cv_l likewise, D unchanged.  Level 0 is the camera bit for bit.
+ *   term              emba_frames_pair_eval's, on the level's table, bytes, size and camera; with the source byte v the Jacobian row of r = val - (a v + b) in
+ *                     (delta, a, b) is (g, -v, -1), and the 21 sums and four counts are emba_frames_exposure_eval's with I0 = v.  The ten sums they share
+ *                     with emba_frames_pair_eval are its bits at level 0, and so are uv, the residuals and the counts.
+ *   loop of a level   emba_frames_exposure_align's step on those sums: estimate (EMBA_EXPOSURE_GAIN | EMBA_EXPOSURE_BIAS), the gain bounds on the pair's
+ *                     relative gain, the four ways to end.  min_pixels at level l is min_pixels >> 2l, but not below min(min_pixels, 8); every other setting
+ *                     is the same at every level.
+ *   schedule          levels[0 ... n_levels), 1 <= n_levels <= 8, each 0 ... 7, in any order.  A pair starts level k + 1 from its accepted (Q, a, b) of level
+ *                     k.  A level that ends converged, on iterations or stalled hands its accepted state on; a level that ends degenerate ends the pair
+ *                     there: its final status is degenerate and its outputs are that level's accepted state.  The final status, sums and counts are the
+ *                     last level run; info is emba_frames_pair_align's, from that level's ten shared sums.  The schedule (0) with estimate = 0 is
+ *                     emba_frames_pair_align bit for bit.
+ *
+ * emba_frames_pair_level_eval: one evaluation of every pair at Q on level `level`, S_l = (sh >> l) (sw >> l).  Outputs, each may be NULL: sums_out [P, 21],
+ * counts_out [P, 4], uv_out [P, S_l, 2], resid_out [P, S_l], level_bytes_out [F, S_l], level_lut_out [S_l, 3].
+ * emba_frames_pair_align_levels: the schedule.  Outputs, each may be NULL: q_out [P, 4], gain_out, bias_out [P], sums_out [P, 21], counts_out [P, 4],
+ * status_out [P], iters_out [P] (summed over the levels), level_status_out and level_iters_out [P, n_levels] (0 where a level was not run), cost0_out and
+ * n0_out [P] (of the first level), info_out [P, 6].  The frames are uploaded once and their pyramid is made once per call; the pairs go in
+ * emba_frames_pair_align's chunks, the schedule runs inside a chunk, and the state stays on the device between levels.  P = 0 launches nothing.  Timer slot 7
+ * brackets the first evaluation kernel of a call, timer slot 6 the launches of the kernel that makes the level bytes (where a level above 0 is asked for).
+ * Refusals, before anything is uploaded, every output untouched, EMBA_ERR_INVALID_ARG in this order: emba_frames_pair_eval's up to huber_k; levels NULL or
+ * n_levels = 0; n_levels > 8; a level outside 0 ... 7; a level too small for the sensor, named in the message; estimate outside 0 ... 3; the gain bounds;
+ * the loop's settings; F * sh * sw above 2^30 bytes.  (emba_frames_pair_level_eval: the arguments, the level, the bytes.)  Nothing of the registered window,
+ * the resident sequence, the mosaic, the level planes of the trackers, the resident map or any other stage's buffers is written. */
+emba_status emba_frames_pair_level_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* pairs /* [P, 2] */, size_t P,
+                                        const double* Q_xyzw /* [P, 4] */, const double* gain /* [P] or NULL */, const double* bias /* [P] or NULL */, double fu,
+                                        double fv, double cu, double cv, const double* D /* [5] or NULL */, int32_t skip_zero, double huber_k, int32_t level,
+                                        double* sums_out /* [P, 21] */, uint64_t* counts_out /* [P, 4] */, double* uv_out /* [P, S_l, 2] */,
+                                        double* resid_out /* [P, S_l] */, uint8_t* level_bytes_out /* [F, S_l] */, double* level_lut_out /* [S_l, 3] */);
+emba_status emba_frames_pair_align_levels(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* pairs /* [P, 2] */, size_t P,
+                                          const double* Q_xyzw /* [P, 4] */, const double* gain /* [P] or NULL */, const double* bias /* [P] or NULL */, double fu,
+                                          double fv, double cu, double cv, const double* D /* [5] or NULL */, int32_t skip_zero, const int32_t* levels /* [n_levels] */,
+                                          size_t n_levels, int32_t estimate, const emba_exposure_settings* settings, double* q_out /* [P, 4] */,
+                                          double* gain_out /* [P] */, double* bias_out /* [P] */, double* sums_out /* [P, 21] */, uint64_t* counts_out /* [P, 4] */,
+                                          int32_t* status_out /* [P] */, int32_t* iters_out /* [P] */, int32_t* level_status_out /* [P, n_levels] */,
+                                          int32_t* level_iters_out /* [P, n_levels] */, double* cost0_out /* [P] */, uint64_t* n0_out /* [P] */,
+                                          double* info_out /* [P, 6] */);
+
 /* emba_rotation_graph_solve: the rotation graph, on the host (it needs no context; emba_last_error(NULL) has the message of a refusal).
  *   unknowns          one rotation per frame (camera to world, xyzw).  Frames whose status is EMBA_TRACK_ANCHOR are constants: the gauge is exact.  A frame
  *                     that no edge names keeps its input.  q_out of either is the input bit for bit.
