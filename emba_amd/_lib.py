@@ -188,6 +188,11 @@ SIGNATURES = {
                                                 C.c_int32, _i32p, C.c_size_t, C.c_int32, C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), _i32p, _i32p, _i32p,
                                                 _i32p, _dp, C.POINTER(C.c_uint64), _dp]),
     "emba_rotation_graph_solve": (C.c_int, [_dp, _i32p, C.c_size_t, _i32p, _dp, _dp, C.c_size_t, C.c_void_p, _dp, _dp, _i32p, _i32p, _szp]),
+    "emba_frames_match_eval": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _i32p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _dp, _i32p,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "emba_frames_match_search": (C.c_int, [C.c_void_p, _u8p, C.c_size_t, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_double,
+                                           C.c_int32, _i32p, _dp, _i32p, C.POINTER(C.c_uint64)]),
+    "emba_match_start": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp]),
     "emba_median_blur3_map": (C.c_int, [C.c_void_p]),
     "emba_median_blur3": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_int32, _dp]),
     "emba_bind_exchange_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

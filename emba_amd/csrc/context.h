@@ -307,6 +307,11 @@ struct PairLevelBuffers {
     FrameLoopBuffers loop;
 };
 
+// Loop-closure pairs found by appearance (match_host.h); all of it scratch of one call.  frames: the whole sequence [F, S], uploaded once per call; bytes: its
+// thumbnails [F, S_l] of the level asked for (level 0: frames itself); pairs, records, sums: one chunk of a pair list, its results (match_rule.h: MatchBest)
+// and the six sums of every shift; votes [F], table (the triangular table of MatchBest) and partner, score, shift, n [F, k]: a search.
+struct MatchBuffers { DevBuf frames, bytes, pairs, records, sums, votes, table, partner, score, shift, n; };
+
 // The event simulator (sim_host.h).  The simulated recording, resident: x, y, pol, t of n events (have: a simulation has succeeded, also one of no events) and
 // the stats of the call that made it; x2 ... t2 take the next one and are swapped in when it has succeeded.  Scratch of one call: a caller's source plane
 // [H, W]; the step times, their pose table and the control poses they were evaluated from (this stage's own); head: the pose stage's status word; frames: one
@@ -510,6 +515,7 @@ struct emba_ctx {
     ExposureBuffers exposure;     // per-frame exposure: the scratch of a call (exposure_host.h)
     PairBuffers pair;             // one frame aligned to another: the resident sequence of a call and the scratch of a chunk of pairs (pair_host.h)
     PairLevelBuffers pair_level;  // the pair alignment coarse to fine: the sequence, its pyramid and the scratch of a chunk of pairs (pair_level_host.h)
+    MatchBuffers match;           // loop-closure pairs found by appearance: the sequence, its thumbnails, a chunk of pairs or the table of a search (match_host.h)
     DevBuf d_blur;                // emba_median_blur3[_map]: the plane the stencil writes (it must not read its own output)
 };
 

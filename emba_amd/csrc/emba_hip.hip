@@ -7,7 +7,7 @@
 // contrast maximisation on it cmax_host.h / cmax_rule.h, the panorama of warped events panorama_host.h / panorama_rule.h and its smooth contrast and gradient
 // contrast_host.h / contrast_rule.h, the sensor views along the trajectory view_host.h / view_rule.h, the mosaic of intensity frames mosaic_host.h / mosaic_rule.h, the event simulator
 // sim_host.h / sim_rule.h, the stages over intensity frames frame_host.h (what they share) and align_host.h / align_rule.h, track_host.h / track_rule.h,
-// exposure_host.h / exposure_rule.h, track_exposure_host.h / track_exposure_rule.h, refit_host.h / refit_rule.h, pair_host.h / pair_rule.h / graph_rule.h, pair_level_host.h / pair_level_rule.h, the multi-GPU group group.h: all one translation unit.
+// exposure_host.h / exposure_rule.h, track_exposure_host.h / track_exposure_rule.h, refit_host.h / refit_rule.h, pair_host.h / pair_rule.h / graph_rule.h, pair_level_host.h / pair_level_rule.h, match_host.h / match_rule.h, the multi-GPU group group.h: all one translation unit.
 // Host code is C++17; every per-event / per-pixel computation runs in the HIP kernels of kernels.h.
 // There is no CPU compute path in this file: the host only sorts indices once per window
 // (emba_set_events: pose-independent structure), launches kernels and moves bytes.
@@ -201,6 +201,7 @@ void emba_destroy(emba_ctx* c)
 #include "refit_host.h"      // tracked frames refitted: each batch taken out of the integer planes, aligned to the mosaic of the others, voted back
 #include "pair_host.h"       // loops closed among tracked frames: one frame aligned to another, pair by pair, and the rotation graph over all of them (host)
 #include "pair_level_host.h" // ... coarse to fine over a pyramid of the sensor frames, with the pair's exposure estimated
+#include "match_host.h"      // loop-closure pairs found by appearance: thumbnails compared under every shift of a range, per frame the k best partners
 
 // ---- single-process multi-GPU host (emba_group_*) ----------------------------------------------------------------------------
 #include "group.h"

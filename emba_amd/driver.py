@@ -94,8 +94,28 @@ class SequenceSettings:         # include/emba/params.h:14-61 (BA_config), docs/
     # through LEGM.pair_align_levels from the same starts.  The graph stays one of rotations alone.
     close_levels: tuple = (0,)
     close_exposure: str = "none"
+    # Where the pairs beyond the window come from (the rule: include/emba_hip.h, emba_frames_match_search): "rotations" — io.pair_candidates of the
+    # tracked rotations, as above; "appearance" — the window's neighbours plus the pairs LEGM.match_search finds more than close_gap frames apart from the frames'
+    # bytes alone: level close_match_level of the pyramid, shifts up to close_match_range = (rx, ry) level pixels, per frame the close_match_per_frame partners
+    # of score >= close_match_score (the signed square of the correlation), a shift scored on close_match_min_overlap of the thumbnail at the least; a matched
+    # pair starts from the rotation its shift stands for (io.match_start), not from the tracked rotations; "both" — the two sets together, a pair that is in
+    # both starting from the tracked rotations.
+    close_search: str = "rotations"
+    close_match_level: int = 2
+    close_match_range: tuple = (6, 4)
+    close_match_score: float = 0.5
+    close_match_per_frame: int = 2
+    close_match_min_overlap: float = 0.25
 
     def __post_init__(self):
+        if self.close_search not in emba_io.MATCH_SEARCH_MODES:
+            raise ValueError(f"SequenceSettings.close_search must be one of {emba_io.MATCH_SEARCH_MODES}, not {self.close_search!r}")
+        self.close_match_range = tuple(int(v) for v in np.asarray(self.close_match_range).reshape(-1))
+        if (len(self.close_match_range) != 2 or min(self.close_match_range) < 0 or not 0 <= int(self.close_match_level) <= emba_io.PAIR_MAX_LEVEL
+                or not 1 <= int(self.close_match_per_frame) <= emba_io.MATCH_MAX_PER_FRAME or np.isnan(self.close_match_score)
+                or not 0.0 <= float(self.close_match_min_overlap) <= 1.0):
+            raise ValueError(f"SequenceSettings.close_match_*: a level 0 ... {emba_io.PAIR_MAX_LEVEL}, a range (rx, ry) that is not negative, 1 ... "
+                             f"{emba_io.MATCH_MAX_PER_FRAME} partners per frame, a score that is a number, an overlap that is a share")
         self.close_levels = tuple(int(l) for l in np.asarray(self.close_levels).reshape(-1))
         if not 1 <= len(self.close_levels) <= emba_io.PAIR_MAX_LEVELS or any(not 0 <= l <= emba_io.PAIR_MAX_LEVEL for l in self.close_levels):
             raise ValueError(f"SequenceSettings.close_levels = {self.close_levels}: 1 ... {emba_io.PAIR_MAX_LEVELS} levels, each 0 ... {emba_io.PAIR_MAX_LEVEL}")
@@ -148,14 +168,22 @@ def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track
     cg_iters, end).  Without seq.track_close, or where no pair is kept, `tracked` is returned as it is (with the pairs, where there were any).  With
     seq.close_levels or seq.close_exposure off their defaults the pairs go through LEGM.pair_align_levels instead, from the same starts; a pair is kept by the
     same gate on the counts of its last level run against that level's pixels, and `pair_gain`, `pair_bias`, `pair_level_status` [P, n] and
-    `pair_last_level` come back beside the rest.  The graph stays one of rotations alone."""
+    `pair_last_level` come back beside the rest.  The graph stays one of rotations alone.  seq.close_search says where the pairs beyond the window come
+    from: "rotations" makes exactly the calls above; "appearance" and "both" add the pairs LEGM.match_search finds from the frames' bytes,
+    started from io.match_start of their shifts (_matched_pairs below); everything behind the pairs is the same.  `pair_source` (0 window, 1 rotations,
+    2 appearance), `pair_match_score` (io.MATCH_UNSCORED where the search did not propose the pair) and `pair_match_shift` [P, 2] come back in every mode."""
     if not seq.track_close:
         return tracked
     kw = {k: v for k, v in track_kw.items() if k not in ("q0", "predict", "want_pm")}
     S = model.sensor_w * model.sensor_h
-    pairs = emba_io.pair_candidates(tracked["q"], tracked["status"], window=seq.close_window, min_gap=seq.close_gap, max_angle=seq.close_angle,
-                                    max_per_frame=seq.close_per_frame)
-    Q0, a, b = emba_io.pair_start(tracked["q"], tracked.get("gain"), tracked.get("bias"), pairs)
+    if seq.close_search == "rotations":
+        pairs = emba_io.pair_candidates(tracked["q"], tracked["status"], window=seq.close_window, min_gap=seq.close_gap, max_angle=seq.close_angle,
+                                        max_per_frame=seq.close_per_frame)
+        Q0, a, b = emba_io.pair_start(tracked["q"], tracked.get("gain"), tracked.get("bias"), pairs)
+        source = np.where(pairs[:, 1] - pairs[:, 0] <= int(seq.close_window), 0, 1).astype(np.int32)
+        m_score, m_shift = np.full(len(pairs), emba_io.MATCH_UNSCORED), np.zeros((len(pairs), 2), np.int32)
+    else:
+        pairs, source, Q0, a, b, m_score, m_shift = _matched_pairs(model, frames, tracked, seq, calib, bool(kw.get("skip_zero", False)))
     align_kw = {k: v for k, v in kw.items() if k in emba_io.ALIGN_DEFAULTS}
     align_kw["huber_k"] = float(seq.close_huber)
     levelled = seq.close_levels != (0,) or seq.close_exposure != "none"
@@ -173,7 +201,8 @@ def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track
     kept = ((al["status"] == emba_io.ALIGN_CONVERGED) | (al["status"] == emba_io.ALIGN_ITERATIONS)) & (n >= seq.close_min_overlap * S_last)
     out = dict(tracked)
     out.update(pairs=pairs, pair_status=al["status"], pair_n=n, pair_cost=ten[:, 9] / np.maximum(n, 1), pair_kept=kept,
-               pair_moved=emba_io.rotation_angle_between(Q0, al["q"]) if len(pairs) else np.zeros(0), graph=None)
+               pair_moved=emba_io.rotation_angle_between(Q0, al["q"]) if len(pairs) else np.zeros(0), graph=None, pair_source=source,
+               pair_match_score=m_score, pair_match_shift=m_shift)
     if levelled:
         out.update(pair_gain=al["gain"], pair_bias=al["bias"], pair_level_status=al["level_status"], pair_last_level=last)
     if not kept.any():
@@ -188,6 +217,34 @@ def close_tracked_frames(model, frames, frame_t_ns, tracked, seq, calib, **track
     r = model.refit_frames(frames, frame_t_ns, g["q"], tracked["status"], tracked.get("gain"), tracked.get("bias"), sweeps=0, **kw)
     out.update({k: r[k] for k in ("dropped", "skipped")})
     return out
+
+
+def _matched_pairs(model, frames, tracked, seq, calib, skip_zero):
+    """The pairs of close_search = "appearance" and "both" (DESIGN.md §28): the window's neighbours (source 0), with "both" the angle candidates of the
+    tracked rotations (1), and the pairs LEGM.match_search finds more than close_gap frames apart (2 where nothing else proposes them).  Every pair starts from
+    the tracked (q, gain, bias) but a pair of source 2, whose rotation starts from io.match_start of its shift.  (pairs [P, 2] sorted, source [P], Q0 [P, 4],
+    a [P], b [P], the match score [P] (io.MATCH_UNSCORED where the search did not propose the pair) and shift [P, 2])."""
+    sw, sh, level = model.sensor_w, model.sensor_h, int(seq.close_match_level)
+    rx, ry = seq.close_match_range
+    n_min = max(int(np.ceil(float(seq.close_match_min_overlap) * (sw >> level) * (sh >> level))), 1)
+    cand = dict(window=seq.close_window, min_gap=seq.close_gap, max_angle=seq.close_angle)
+    win = {tuple(p) for p in emba_io.pair_candidates(tracked["q"], tracked["status"], max_per_frame=0, **cand).tolist()}
+    rot = {tuple(p) for p in emba_io.pair_candidates(tracked["q"], tracked["status"], max_per_frame=seq.close_per_frame, **cand).tolist()} if seq.close_search == "both" else win
+    found = model.match_search(frames, tracked["status"], level=level, rx=rx, ry=ry, min_gap=seq.close_gap, skip_zero=skip_zero, n_min=n_min,
+                               score_min=float(seq.close_match_score), k=int(seq.close_match_per_frame))
+    mp, ms, md = emba_io.match_pairs(found, with_info=True)
+    app = {tuple(p): (s, d) for p, s, d in zip(mp.tolist(), ms, md)}
+    keys = sorted(win | rot | set(app))
+    pairs = np.array(keys, dtype=np.int32).reshape(-1, 2)
+    source = np.array([0 if p in win else 1 if p in rot else 2 for p in keys], dtype=np.int32)
+    Q0, a, b = emba_io.pair_start(tracked["q"], tracked.get("gain"), tracked.get("bias"), pairs)
+    score, shift = np.full(len(keys), emba_io.MATCH_UNSCORED), np.zeros((len(keys), 2), np.int32)
+    for n, p in enumerate(keys):
+        if p in app:
+            score[n], shift[n] = app[p]
+            if source[n] == 2:
+                Q0[n] = model.match_start(shift[n, 0], shift[n, 1], level, calib, (sw, sh))
+    return pairs, source, Q0, a, b, score, shift
 
 
 def _reached(status, edges):

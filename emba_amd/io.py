@@ -2339,6 +2339,169 @@ def pair_candidates(q, status, window=1, min_gap=None, max_angle=0.0, max_per_fr
     return np.array(sorted(out), dtype=np.int32).reshape(-1, 2)
 
 
+# ---- loop-closure pairs found by appearance (numpy forms of emba_frames_match_eval, emba_frames_match_search and emba_match_start, include/emba_hip.h; the
+# device forms are LEGM.match_eval and LEGM.match_search, the host form LEGM.match_start).  The rule is emba_amd/csrc/match_rule.h's: the six
+# sums of a shift are integers, the score's five operations are correctly rounded on both sides, so everything here has the device's bits.
+MATCH_MAX_PIXELS = 16384                 # kMatchMaxPixels: a thumbnail
+MATCH_MAX_PER_FRAME = 64                 # kMatchMaxPerFrame
+MATCH_UNSCORED = -2.0                    # kMatchUnscored: the score of a pair without a scored shift
+MATCH_SEARCH_MODES = ("rotations", "appearance", "both")
+
+
+def match_check(sensor, level, rx, ry, n_min=1):
+    """(w, h) of the thumbnails; the refusals of emba_frames_match_eval's level, range and n_min as ValueError, in its order."""
+    sw, sh = int(sensor[0]), int(sensor[1])
+    w, h = pair_level_size(sensor, level)
+    if w * h > MATCH_MAX_PIXELS:
+        l = next(l for l in range(64) if (sw >> l) * (sh >> l) <= MATCH_MAX_PIXELS)
+        raise ValueError(f"level {int(level)} of a {sw} x {sh} sensor has {w} x {h} pixels: a thumbnail has {MATCH_MAX_PIXELS} at the most; the smallest level that fits is {l}")
+    if not (0 <= int(rx) < w and 0 <= int(ry) < h):
+        raise ValueError(f"rx = {rx}, ry = {ry}: 0 <= rx < {w} and 0 <= ry < {h} at level {int(level)}")
+    if int(n_min) < 1:
+        raise ValueError("n_min = 0: a scored shift has one pixel at the least")
+    return w, h
+
+
+def match_shifts(rx, ry):
+    """The shifts (dx, dy) of a range, int64 [(2 rx + 1)(2 ry + 1), 2], row-major: dy from -ry, then dx from -rx."""
+    dy, dx = np.meshgrid(np.arange(-int(ry), int(ry) + 1), np.arange(-int(rx), int(rx) + 1), indexing="ij")
+    return np.stack([dx.ravel(), dy.ravel()], axis=1).astype(np.int64)
+
+
+def _match_overlap(w, h, dx, dy):
+    return max(-dx, 0), min(w - dx, w), max(-dy, 0), min(h - dy, h)
+
+
+def match_sums(a_u8, b_u8, rx, ry, skip_zero=False):
+    """The six integer sums of every shift of thumbnails a, b [h, w]: uint64 [shifts, 6] = n, sum a, sum b, sum a^2, sum b^2, sum a b over the overlap of
+    A(x, y) with B(x + dx, y + dy); under skip_zero a point where either byte is 0 takes no part."""
+    A, B = np.asarray(a_u8, dtype=np.uint8).astype(np.int64), np.asarray(b_u8, dtype=np.uint8).astype(np.int64)
+    h, w = A.shape
+    out = np.zeros((len(match_shifts(rx, ry)), 6), np.uint64)
+    for s, (dx, dy) in enumerate(match_shifts(rx, ry)):
+        x0, x1, y0, y1 = _match_overlap(w, h, int(dx), int(dy))
+        if x1 <= x0 or y1 <= y0:
+            continue
+        a, b = A[y0:y1, x0:x1], B[y0 + dy:y1 + dy, x0 + dx:x1 + dx]
+        m = ((a != 0) & (b != 0)) if skip_zero else np.ones(a.shape, bool)
+        a, b = a[m], b[m]
+        out[s] = (a.size, a.sum(), b.sum(), (a * a).sum(), (b * b).sum(), (a * b).sum())
+    return out
+
+
+def match_score(sums, n_min=1):
+    """(score, scored) of sums [..., 6]: cov = n sab - sa sb, va = n saa - sa^2, vb likewise in int64; score = (double)cov |(double)cov| / ((double)va
+    (double)vb), in this order; not scored (score MATCH_UNSCORED) where n < n_min, va = 0 or vb = 0."""
+    s = np.asarray(sums).astype(np.int64)
+    n, sa, sb, saa, sbb, sab = (s[..., k] for k in range(6))
+    cov, va, vb = n * sab - sa * sb, n * saa - sa * sa, n * sbb - sb * sb
+    scored = (n >= int(n_min)) & (va != 0) & (vb != 0)
+    c = cov.astype(np.float64)
+    den = np.where(scored, va.astype(np.float64) * vb.astype(np.float64), 1.0)
+    return np.where(scored, (c * np.abs(c)) / den, MATCH_UNSCORED), scored
+
+
+def match_best(a_u8, b_u8, rx, ry, skip_zero=False, n_min=1):
+    """The best of a pair of thumbnails: the scored shift of greatest score, ties to the lowest shift index.  A dict of score, dx, dy, n, shift (the index)
+    and sums [shifts, 6]; without a scored shift: MATCH_UNSCORED, (0, 0), 0."""
+    sums = match_sums(a_u8, b_u8, rx, ry, skip_zero)
+    score, scored = match_score(sums, n_min)
+    if not scored.any():
+        return dict(score=MATCH_UNSCORED, dx=0, dy=0, n=0, shift=0, sums=sums)
+    s = int(np.argmax(np.where(scored, score, -np.inf)))      # (argmax: the first of equals)
+    dx, dy = match_shifts(rx, ry)[s]
+    return dict(score=float(score[s]), dx=int(dx), dy=int(dy), n=int(sums[s, 0]), shift=s, sums=sums)
+
+
+def match_table(thumbs_u8, rx, ry, skip_zero=False, n_min=1):
+    """The best of every ordered pair (i, j) of thumbnails [F, h, w] at once: score [F, F] (MATCH_UNSCORED: none), shift int64 [F, F, 2], n int64 [F, F].  The
+    sums of a shift are matrix products over the overlap, taken in fp64 where every partial sum is an integer below 2^53: exact in any order."""
+    T = np.asarray(thumbs_u8, dtype=np.uint8)
+    F, h, w = T.shape
+    best, have = np.full((F, F), MATCH_UNSCORED), np.zeros((F, F), bool)
+    bshift, bn = np.zeros((F, F, 2), np.int64), np.zeros((F, F), np.int64)
+    for dx, dy in match_shifts(rx, ry):
+        dx, dy = int(dx), int(dy)
+        x0, x1, y0, y1 = _match_overlap(w, h, dx, dy)
+        if x1 <= x0 or y1 <= y0:
+            continue
+        A = T[:, y0:y1, x0:x1].reshape(F, -1).astype(np.float64)
+        B = T[:, y0 + dy:y1 + dy, x0 + dx:x1 + dx].reshape(F, -1).astype(np.float64)
+        Ma, Mb = ((A != 0).astype(np.float64), (B != 0).astype(np.float64)) if skip_zero else (np.ones_like(A), np.ones_like(B))
+        sums = np.stack([Ma @ Mb.T, A @ Mb.T, Ma @ B.T, (A * A) @ Mb.T, Ma @ (B * B).T, A @ B.T], axis=-1).astype(np.int64)
+        score, scored = match_score(sums, n_min)
+        take = scored & (~have | (score > best))      # (the shifts come in index order: an equal score stays with the lower index)
+        best, have = np.where(take, score, best), have | take
+        bshift[take], bn[take] = (dx, dy), sums[..., 0][take]
+    return best, bshift, bn
+
+
+def match_search(frames_u8, status=None, level=0, rx=0, ry=0, min_gap=0, skip_zero=False, n_min=1, score_min=0.0, k=1):
+    """emba_frames_match_search in numpy: frames_u8 [F, sh, sw]; the thumbnails are pair_level_bytes of `level`; candidates are i < j with j - i > min_gap,
+    both frames voting (status [F] of TRACK_*: anchor or tracked; None: all); per frame the k partners of greatest best score >= score_min, ties to the lower
+    partner index.  A dict of partner int32 [F, k] (-1), score [F, k] (MATCH_UNSCORED), shift int32 [F, k, 2] (from the lower index to the higher), n int64
+    [F, k]."""
+    fr = np.asarray(frames_u8, dtype=np.uint8)
+    F, sh, sw = fr.shape
+    match_check((sw, sh), level, rx, ry, n_min)
+    k, gap = int(k), int(min_gap)
+    if not 1 <= k <= MATCH_MAX_PER_FRAME or gap < 0 or np.isnan(score_min):
+        raise ValueError(f"k = {k} (1 ... {MATCH_MAX_PER_FRAME}), min_gap = {gap} (not negative), score_min = {score_min} (a number)")
+    st = np.full(F, TRACK_ANCHOR, np.int64) if status is None else np.asarray(status, dtype=np.int64).reshape(-1)
+    votes = (st == TRACK_ANCHOR) | (st == 2)
+    best, bshift, bn = match_table(pair_level_bytes(fr, level, skip_zero), rx, ry, skip_zero, n_min)
+    iu = np.triu(np.ones((F, F), bool), 1)      # (i < j as evaluated, mirrored: the partner's side keeps the orientation)
+    best, bn = np.where(iu, best, best.T), np.where(iu, bn, bn.T)
+    bshift = np.where(iu[..., None], bshift, bshift.transpose(1, 0, 2))
+    idx = np.arange(F)
+    ok = votes[:, None] & votes[None, :] & (np.abs(idx[:, None] - idx[None, :]) > gap) & (bn > 0) & (best >= float(score_min))
+    out = dict(partner=np.full((F, k), -1, np.int32), score=np.full((F, k), MATCH_UNSCORED), shift=np.zeros((F, k, 2), np.int32), n=np.zeros((F, k), np.int64))
+    for f in range(F):
+        g = np.flatnonzero(ok[f])
+        g = g[np.lexsort((g, -best[f, g]))][:k]
+        out["partner"][f, :g.size], out["score"][f, :g.size], out["shift"][f, :g.size], out["n"][f, :g.size] = g, best[f, g], bshift[f, g], bn[f, g]
+    return out
+
+
+def match_pairs(found, with_info=False):
+    """The pairs (i, j), i < j, int32 [P, 2], sorted: the union of the per-frame lists of match_search / LEGM.match_search.  with_info: also score [P] and
+    shift int32 [P, 2] of each."""
+    seen = {}
+    for f, row in enumerate(np.asarray(found["partner"])):
+        for t, g in enumerate(row):
+            if g >= 0:
+                seen[(min(f, int(g)), max(f, int(g)))] = (float(found["score"][f, t]), tuple(int(v) for v in found["shift"][f, t]))
+    keys = sorted(seen)
+    pairs = np.array(keys, dtype=np.int32).reshape(-1, 2)
+    if not with_info:
+        return pairs
+    return pairs, np.array([seen[p][0] for p in keys], dtype=np.float64), np.array([seen[p][1] for p in keys], dtype=np.int32).reshape(-1, 2)
+
+
+def match_start(dx, dy, level, fu, fv, cu, cv, sw, sh):
+    """emba_match_start in Python floats (IEEE doubles; + - * / sqrt in match_rule.h's order, so the same bits): xyzw [4] of the shortest arc from the pinhole
+    bearing of p_i = c - t to that of p_j = c + t, c = ((sw - 1) / 2, (sh - 1) / 2), t = 2^l (dx, dy) / 2.  R(Q) b_i = b_j: pair_start's convention."""
+    import math
+    l = int(level)
+    fu, fv, cu, cv = float(fu), float(fv), float(cu), float(cv)
+    if not (0 <= l <= PAIR_MAX_LEVEL and int(sw) > 0 and int(sh) > 0 and math.isfinite(fu) and math.isfinite(fv) and fu > 0.0 and fv > 0.0 and math.isfinite(cu)
+            and math.isfinite(cv)):
+        raise ValueError("match_start: a level 0 ... 7, a sensor with pixels, fu and fv finite and positive, cu and cv finite")
+    cx, cy = (float(int(sw)) - 1.0) / 2.0, (float(int(sh)) - 1.0) / 2.0
+    tx, ty = float(1 << l) * float(int(dx)) / 2.0, float(1 << l) * float(int(dy)) / 2.0
+
+    def bearing(x, y):
+        bx, by = (x - cu) / fu, (y - cv) / fv
+        n = math.sqrt((bx * bx + by * by) + 1.0)
+        return bx / n, by / n, 1.0 / n
+
+    bi, bj = bearing(cx - tx, cy - ty), bearing(cx + tx, cy + ty)
+    x, y, z = bi[1] * bj[2] - bi[2] * bj[1], bi[2] * bj[0] - bi[0] * bj[2], bi[0] * bj[1] - bi[1] * bj[0]
+    w = 1.0 + ((bi[0] * bj[0] + bi[1] * bj[1]) + bi[2] * bj[2])
+    n = math.sqrt(((x * x + y * y) + z * z) + w * w)
+    return np.array([x / n, y / n, z / n, w / n])
+
+
 def graph_settings(**kw):
     """GRAPH_DEFAULTS with the given members replaced; the refusals of emba_rotation_graph_solve's settings as ValueError."""
     unknown = set(kw) - set(GRAPH_DEFAULTS)

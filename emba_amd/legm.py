@@ -752,6 +752,60 @@ class LEGM:
         return dict(q=q_out, gain=a_out, bias=b_out, sums=sums, counts=counts.astype(np.int64), status=status, iters=iters, level_status=lst, level_iters=lit,
                     cost0=cost0, n0=n0.astype(np.int64), info=info)
 
+    def _match_frames(self, frames):
+        S = self.sensor_w * self.sensor_h
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.size % S:
+            raise ValueError("frames must be F x sensor_height x sensor_width bytes")
+        return frames, frames.size // S
+
+    def match_eval(self, frames, pairs, level, rx, ry, skip_zero=False, n_min=1, want_sums=False):
+        """The best shift of every pair of a list, by appearance (emba_frames_match_eval; the rule: include/emba_hip.h): level `level` of frames i and j
+        compared under every shift |dx| <= rx, |dy| <= ry by the signed square of the zero-mean normalised correlation over the overlap, formed from six
+        exact integer sums; a shift with fewer than n_min pixels or without variance is not scored.  A dict of score [P] (-2: no scored shift), shift int32
+        [P, 2] (dx, dy), n int64 [P] and, with want_sums, sums uint64 [P, shifts, 6] (n, sum a, sum b, sum a^2, sum b^2, sum a b; shifts row-major, dy
+        from -ry) — io.match_best and io.match_sums on io.pair_level_bytes, bit for bit."""
+        frames, F = self._match_frames(frames)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P = pairs.shape[0]
+        shifts = max((2 * int(rx) + 1) * (2 * int(ry) + 1), 0)
+        score, shift, n = np.full(P, -2.0), np.zeros((P, 2), np.int32), np.zeros(P, np.uint64)
+        sums = np.zeros((P, shifts, 6), np.uint64) if want_sums else None
+        u64p = C.POINTER(C.c_uint64)
+        self._check(self._L.emba_frames_match_eval(self._ctx, _p(frames, _u8p), F, _p(pairs, _i32p), P, int(level), int(rx), int(ry), 1 if skip_zero else 0,
+                                                   int(n_min), _p(score, _dp), _p(shift, _i32p), _p(n, u64p), _p(sums, u64p)))
+        return dict(score=score, shift=shift, n=n.astype(np.int64), sums=sums)
+
+    def match_search(self, frames, status=None, level=0, rx=0, ry=0, min_gap=0, skip_zero=False, n_min=1, score_min=0.0, k=1):
+        """Loop-closure pairs by appearance (emba_frames_match_search; the rule: include/emba_hip.h): every pair i < j of voting frames (status [F] of
+        io.TRACK_*, None: all) with j - i > min_gap is scored as match_eval scores it, and per frame the k partners of greatest score >= score_min are kept,
+        ties to the lower index.  A dict of partner int32 [F, k] (-1: none), score [F, k] (-2), shift int32 [F, k, 2] (from the lower index to the higher)
+        and n int64 [F, k] — io.match_search, bit for bit; io.match_pairs makes the pairs of it."""
+        frames, F = self._match_frames(frames)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+        if st is not None and st.size != F:
+            raise ValueError(f"status must be [{F}]")
+        K = max(int(k), 0)
+        partner, score = np.full((F, K), -1, np.int32), np.full((F, K), -2.0)
+        shift, n = np.zeros((F, K, 2), np.int32), np.zeros((F, K), np.uint64)
+        self._check(self._L.emba_frames_match_search(self._ctx, _p(frames, _u8p), F, _p(st, _i32p), int(level), int(rx), int(ry), int(min_gap),
+                                                     1 if skip_zero else 0, int(n_min), float(score_min), int(k), _p(partner, _i32p), _p(score, _dp),
+                                                     _p(shift, _i32p), _p(n, C.POINTER(C.c_uint64))))
+        return dict(partner=partner, score=score, shift=shift, n=n.astype(np.int64))
+
+    @staticmethod
+    def match_start(dx, dy, level, calib, sensor):
+        """The rotation a matched pair starts from (emba_match_start; the rule: include/emba_hip.h): the shortest arc between the pinhole bearings of the
+        two pixels the shift (dx, dy) of level `level` puts on the same place; calib: fu, fv, cu, cv (a lens is ignored); sensor: (sw, sh).  xyzw [4].  It
+        needs no context and no device.  io.match_start is the same arithmetic in Python, bit for bit."""
+        L = _lib.load()
+        q = np.zeros(4)
+        rc = L.emba_match_start(int(dx), int(dy), int(level), float(calib["fu"]), float(calib["fv"]), float(calib["cu"]), float(calib["cv"]), int(sensor[0]),
+                                int(sensor[1]), _p(q, _dp))
+        if rc != _lib.OK:
+            raise _lib.EmbaError(rc, L.emba_last_error(None).decode())
+        return q
+
     @staticmethod
     def rotation_graph_solve(q_xyzw, status, edges, Q_xyzw, info, **settings):
         """The rotation graph on the host (emba_rotation_graph_solve; the rule: include/emba_hip.h): q_xyzw [F, 4] with status [F] (io.TRACK_ANCHOR frames

@@ -138,6 +138,13 @@ def refine_frames(legm, frames, t_ns, traj, t_raw, q_raw, rounds, huber_k, skip_
     return traj, t_raw, q_raw, [row + (g, o) for row, g, o in zip(rows, gain, bias)], (g_all, b_all)
 
 
+def match_settings(a):
+    """--close-search and the --close-match-* flags as members of driver.SequenceSettings: only what was given."""
+    given = dict(close_search=a.close_search, close_match_level=a.close_match_level, close_match_range=a.close_match_range, close_match_score=a.close_match_score,
+                 close_match_per_frame=a.close_match_per_frame)
+    return {k: v for k, v in given.items() if v is not None}
+
+
 def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print, calib=None, pairs_path=None):
     """--init-poses frames: poses from the frames alone.  The frames are tracked against their own growing mosaic on the device; the
     tracked frames' (t, q), sampled on a 5 ms grid over the span and held at both ends where the frames do not reach them, are the raw poses, and
@@ -157,21 +164,26 @@ def track_frames(legm, frames, t_ns, traj, t_beg, t_end, a, log=print, calib=Non
         before = r["q"]
         r = close_tracked_frames(legm, frames, t_ns, r, SequenceSettings(1.0, 1.0, track_close=True, close_window=a.close_window, close_gap=a.close_gap,
                                                                          close_angle=a.close_angle, close_per_frame=a.close_per_frame, close_huber=a.close_huber,
-                                                                         close_levels=a.close_levels or (0,), close_exposure=a.close_exposure or "none"),
+                                                                         close_levels=a.close_levels or (0,), close_exposure=a.close_exposure or "none",
+                                                                         **match_settings(a)),
                                  calib, estimate=estimate or 0, **kw)
         g = r["graph"]
         log(f"track-close: {len(r['pairs'])} pairs, {int(r['pair_kept'].sum())} kept; "
+            + (f"search {a.close_search}: {np.bincount(r['pair_source'], minlength=3).tolist()} from the window, the rotations, the appearance; " if a.close_search else "")
             + (f"graph cost {g['cost0']:.6g} -> {g['cost']:.6g} in {g['iters']} steps ({g['cg_iters']} CG iterations, {eio.GRAPH_END_NAMES[g['end']]}); "
                f"worst change against the tracker {eio.rotation_angle_between(before, r['q']).max():.3g} rad" if g else "no graph: the tracker's rotations stay"))
         if pairs_path:
             with open(pairs_path, "w") as fh:
                 levelled = a.close_levels is not None or a.close_exposure is not None      # (the columns gain, bias, last level only with one of the two flags)
-                fh.write("# i j status(1 converged, 2 stalled, 3 iterations, 4 degenerate) n mean_cost moved[rad] kept" + (" gain bias last_level" if levelled else "") + "\n")
+                fh.write("# i j status(1 converged, 2 stalled, 3 iterations, 4 degenerate) n mean_cost moved[rad] kept" + (" gain bias last_level" if levelled else "")
+                         + (" source(0 window, 1 rotations, 2 appearance) match_score dx dy" if a.close_search else "") + "\n")
                 if levelled and "pair_gain" not in r:      # (a flag given at its default value: the pairs went through level 0 alone, their exposure as given)
                     _, pg, pb = eio.pair_start(before, r.get("gain"), r.get("bias"), r["pairs"])
                     r = dict(r, pair_gain=pg, pair_bias=pb, pair_last_level=np.zeros(len(r["pairs"]), np.int64))
                 for p, ((i, j), st, n, c, mv, kp) in enumerate(zip(r["pairs"], r["pair_status"], r["pair_n"], r["pair_cost"], r["pair_moved"], r["pair_kept"])):
                     more = f" {r['pair_gain'][p]:.9g} {r['pair_bias'][p]:.9g} {int(r['pair_last_level'][p])}" if levelled else ""
+                    if a.close_search:      # (the columns source, match score, dx, dy only with --close-search)
+                        more += f" {int(r['pair_source'][p])} {r['pair_match_score'][p]:.9g} {int(r['pair_match_shift'][p][0])} {int(r['pair_match_shift'][p][1])}"
                     fh.write(f"{i} {j} {int(st)} {int(n)} {c:.9g} {mv:.9g} {int(kp)}{more}\n")
     if a.track_refit:      # the sweeps behind the tracker, before the raw poses are sampled: the mosaic in the context is the refitted one
         from emba_amd.driver import SequenceSettings, refit_tracked_frames
@@ -345,6 +357,13 @@ def main():
                     "sensor frames (level l: the frames box-reduced by 2^l), e.g. 2,1,0 (default: level 0 alone)")
     ap.add_argument("--close-exposure", choices=("none", "bias", "gain-bias"), default=None, help="with --track-close: what of a pair's relative exposure is "
                     "estimated with its rotation (default: none, the tracker's exposure is taken as it is)")
+    ap.add_argument("--close-search", choices=("rotations", "appearance", "both"), default=None, help="with --track-close: where the pairs beyond the window come "
+                    "from: the tracked rotations (default), the frames' bytes alone — every frame's thumbnail compared with every other's under every shift of a "
+                    "range, on the device (DESIGN.md section 28) — or both (frames_pairs.txt gains the columns source, match score, dx, dy)")
+    ap.add_argument("--close-match-level", type=int, default=None, metavar="L", help="with --close-search appearance / both: the level of the thumbnails (default 2)")
+    ap.add_argument("--close-match-range", default=None, metavar="RX,RY", help="... the largest shift tried, in level pixels (default 6,4)")
+    ap.add_argument("--close-match-score", type=float, default=None, metavar="X", help="... the least score of a matched pair: the signed square of the correlation (default 0.5)")
+    ap.add_argument("--close-match-per-frame", type=int, default=None, metavar="N", help="... matched partners kept per frame (default 2)")
     ap.add_argument("--close-calib", metavar="fu,fv,cu,cv[,k1,k2,p1,p2,k3]", help="the camera the pairs project through (default: --calib's K and D; --demo: the "
                     "demo's pinhole)")
     ap.add_argument("--track-refit-tol", type=float, default=0.0, metavar="X", help="with --track-refit: stop behind a sweep whose largest rotation change is below X rad (0: never)")
@@ -401,6 +420,18 @@ def main():
         ap.error("--track-close closes loops among the frames tracked by --init-poses frames: it needs --init-poses frames")
     if (a.close_levels is not None or a.close_exposure is not None) and not a.track_close:
         ap.error("--close-levels and --close-exposure say how --track-close aligns its pairs: they need --track-close")
+    if any(v is not None for v in (a.close_search, a.close_match_level, a.close_match_range, a.close_match_score, a.close_match_per_frame)) and not a.track_close:
+        ap.error("--close-search and --close-match-* say where --track-close finds its pairs: they need --track-close")
+    if a.close_match_range is not None:
+        try:
+            a.close_match_range = tuple(int(x) for x in a.close_match_range.split(","))
+        except ValueError:
+            a.close_match_range = ()
+        if len(a.close_match_range) != 2 or min(a.close_match_range) < 0:
+            ap.error("--close-match-range takes RX,RY, neither negative, e.g. 6,4")
+    if ((a.close_match_level is not None and not 0 <= a.close_match_level <= eio.PAIR_MAX_LEVEL) or (a.close_match_score is not None and np.isnan(a.close_match_score))
+            or (a.close_match_per_frame is not None and not 1 <= a.close_match_per_frame <= eio.MATCH_MAX_PER_FRAME)):
+        ap.error(f"--close-match-level takes 0 ... {eio.PAIR_MAX_LEVEL}, --close-match-score a number, --close-match-per-frame 1 ... {eio.MATCH_MAX_PER_FRAME}")
     if a.close_levels is not None:
         try:
             a.close_levels = tuple(int(x) for x in a.close_levels.split(","))

@@ -1023,6 +1023,54 @@ emba_status emba_rotation_graph_solve(const double* q_xyzw /* [F, 4] */, const i
                                       const double* Q_xyzw /* [E, 4] */, const double* info /* [E, 6] */, size_t E, const emba_graph_settings* settings,
                                       double* q_out /* [F, 4] */, double* cost_out /* [2] */, int32_t* iters_out /* [2] */, int32_t* end_out, size_t* at_out);
 
+/* ---- Loop-closure pairs found by appearance: coarse frame matching.  The pairs above are chosen from the tracked rotations, so a loop that
+ * the tracker's drift hides is not found.  Here pairs are proposed from the frames' bytes alone: every frame's thumbnail is compared with every other's under
+ * every integer shift of a range, and a matched pair brings the coarse start its shift stands for.  The rule lives in emba_amd/csrc/match_rule.h (over
+ * pair_level_rule.h); emba_amd.io.match_* is the same rule in numpy.  Everything is integer arithmetic up to one score per shift, whose five floating-point
+ * operations are correctly rounded on both sides: numpy gives the same integers and the same score bits.
+ *
+ *   thumbnails        level l of every frame by emba_frames_pair_level_eval's level bytes, under skip_zero as there (a box that holds a zero is 0: "no data");
+ *                     level 0 is the frames themselves.  w = sw >> l, h = sh >> l, S_l = w h <= 16 384.
+ *   a shift           d = (dx, dy), |dx| <= rx, |dy| <= ry, claims A_i(x, y) ~ A_j(x + dx, y + dy).  Its overlap is every (x, y) with both points inside
+ *                     [0, w) x [0, h); under skip_zero a point where either byte is 0 takes no part.  Over the overlap six integer sums: n, sum a, sum b,
+ *                     sum a^2, sum b^2, sum a b (each below 2^32; reported as uint64).  The shift index is row-major: dy from -ry, then dx from -rx.
+ *   score             cov = n sab - sa sb, va = n saa - sa^2, vb = n sbb - sb^2, exact in int64; score = (double)cov |(double)cov| / ((double)va (double)vb),
+ *                     in this order, without contraction: the signed square of the zero-mean normalised correlation.  A shift is not scored where
+ *                     n < n_min, va = 0 or vb = 0.
+ *   best of a pair    the scored shift of greatest score, ties to the lowest shift index; a pair with no scored shift reports score = -2, d = (0, 0), n = 0.
+ *   search            candidates are the pairs i < j with j - i > min_gap whose frames both vote (status [F]: EMBA_TRACK_ANCHOR or EMBA_TRACK_TRACKED; NULL:
+ *                     every frame).  Per frame f the k partners, on either side of f, of greatest best score among those with score >= score_min (a pair
+ *                     without a scored shift never is one), ties to the lower partner index.  The shift is oriented from the lower index to the higher, as
+ *                     evaluated (the sums are symmetric: only i < j is evaluated).  Where fewer than k qualify: partner -1, score -2, shift (0, 0), n 0.
+ *   start             emba_match_start: with c = ((sw - 1) / 2, (sh - 1) / 2) and t = 2^l (dx, dy) / 2, the pixels p_i = c - t of frame i and p_j = c + t of
+ *                     frame j show the same place.  Pinhole bearings ((x - cu) / fu, (y - cv) / fv, 1), normalised: b = (bx, by, 1) / sqrt((bx^2 + by^2) + 1).
+ *                     Q = (b_i x b_j, 1 + ((b_ix b_jx + b_iy b_jy) + b_iz b_jz)) / its norm sqrt(((x^2 + y^2) + z^2) + w^2): the shortest arc, R(Q) b_i =
+ *                     b_j, zero roll — emba_frames_pair_eval's convention.  A lens is ignored: the alignment refines the start.  d = 0 is (0, 0, 0, 1).
+ *
+ * emba_frames_match_eval: the best shift of every pair of a list (i = j and i > j are pairs like any other, evaluated as given).  Outputs, each may be NULL:
+ * score_out [P], shift_out [P, 2] (dx, dy), n_out [P], sums_out [P, (2 rx + 1)(2 ry + 1), 6].
+ * emba_frames_match_search: the search.  Outputs, each may be NULL: partner_out [F, k], score_out [F, k], shift_out [F, k, 2], n_out [F, k].
+ * The frames are uploaded once and their thumbnails are made once per call (emba_frames_pair_level_eval's pyramid kernel; none at level 0).  One workgroup
+ * per pair, in launches of at most 2^20 pairs (with sums_out: at most 64 MiB of sums); the search keeps the best of every pair i < j in a triangular table of
+ * 24 bytes per pair on the device, bounded at 2^30 bytes (F = 9 459), and one wave per frame selects from it.  P = 0, or a search without a candidate pair,
+ * launches nothing (the search then fills its outputs with "none").  With kernel timing on, timer slot 7 brackets the first evaluation launch of a call and
+ * timer slot 6 the select kernel.
+ * Refusals, before anything is uploaded, every output untouched, EMBA_ERR_INVALID_ARG in this order: frames NULL; F = 0 or F >= 2^31; (the list) pairs NULL
+ * with P > 0, P >= 2^31, a pair with a frame outside [0, F); a level outside 0 ... 7; a level below 2 x 2, named in the message; S_l > 16 384, with the smallest
+ * level that fits in the message; rx < 0, ry < 0, rx >= w or ry >= h; n_min = 0; (the search) k outside 1 ... 64, min_gap < 0, score_min a NaN; F * sh * sw
+ * above 2^30 bytes; (the search) the table above 2^30 bytes.  emba_match_start needs no context (emba_last_error(NULL) has the message): q_out NULL, a level
+ * outside 0 ... 7, sw or sh not positive, fu or fv not finite or not positive, cu or cv not finite.  Nothing of the registered window, the resident sequence,
+ * the mosaic, the level planes, the resident map or any other stage's buffers is written. */
+emba_status emba_frames_match_eval(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* pairs /* [P, 2] */, size_t P, int32_t level,
+                                   int32_t rx, int32_t ry, int32_t skip_zero, uint32_t n_min, double* score_out /* [P] */, int32_t* shift_out /* [P, 2] */,
+                                   uint64_t* n_out /* [P] */, uint64_t* sums_out /* [P, shifts, 6] */);
+emba_status emba_frames_match_search(emba_ctx* ctx, const uint8_t* frames /* [F, sh, sw] */, size_t F, const int32_t* status /* [F] or NULL */, int32_t level,
+                                     int32_t rx, int32_t ry, int32_t min_gap, int32_t skip_zero, uint32_t n_min, double score_min, int32_t k,
+                                     int32_t* partner_out /* [F, k] */, double* score_out /* [F, k] */, int32_t* shift_out /* [F, k, 2] */,
+                                     uint64_t* n_out /* [F, k] */);
+emba_status emba_match_start(int32_t dx, int32_t dy, int32_t level, double fu, double fv, double cu, double cv, int32_t sensor_w, int32_t sensor_h,
+                             double* q_out /* [4] */);
+
 /* The median blur of the initial map (emba.cpp:357-364): convertTo(CV_32FC1) (round to nearest even), cv::medianBlur(., ., 3) with replicated borders
  * (SURVEY.md Appendix A), convertTo(CV_64FC1).  The median selects one of its nine inputs, so the result is exact; NaN input is undefined, as in OpenCV.
  * emba_median_blur3_map: both planes of the CURRENT resident map, in place (a map bound with emba_bind_map_dev is left untouched: the blurred map becomes
